@@ -2,6 +2,7 @@
 """bench.py -- online FM + FTRL-proximal on synthetic Criteo-39 (BASELINE.json configs[1]/[2]).
 
     python bench.py --gpus N --steps K --warmup W        (N > 1: launched by torch.distributed.run, one rank per GPU)
+    python bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR   (also writes the timed path's outputs as DIR/*.npy)
 
 A "step" is one pass of the hot path over one mini-batch: sort the batch's occurrences, gather + bi-interaction
 forward with the fused BCE loss, row-reduced backward + fused FTRL-proximal update of every touched row.  Inputs (a
@@ -16,13 +17,9 @@ import time
 import numpy as np
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
-# Hardware queues per process (must be set before the HIP runtime starts).  The runtime's default is 4; with it two of the streams
-# of the multi-GPU step (main, prefetch, RCCL's) share a queue and a prefetched sort waits behind the step it should overlap (77 vs
-# 110 us per 16,384-sample step, replicated mode rehearsed on one GPU), and the Python paths that keep a torch side stream beside
-# the work stream read a quarter of their rate (trainer step 13.7 vs 51 M samples/s).  With 8 the FOURTH and ELEVENTH stream a
-# process creates land on the queue of the library's side stream and a loop there runs behind the sorts (89 instead of 21 us per
-# step; with 16 queues every fourth stream; tools/queue_alias.py) -- hence work_stream() below: ONE stream for every loop.
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
+# The streams of a process share the HIP runtime's hardware queues (four per process by default): a loop whose stream lands
+# on the queue of the library's side stream runs behind the sorts (tools/queue_alias.py) -- hence work_stream() below: ONE
+# stream for every loop.  The bench leaves the queue count to the environment.
 sys.path.insert(0, os.path.join(ROOT, "fm-for-online-recommendation_amd"))
 sys.path.insert(0, ROOT)
 
@@ -73,7 +70,7 @@ def work_stream(torch, dev):
     """ONE stream of its own for every loop of this process (not torch's legacy default stream, which is ordered against every
     blocking stream and slow to enqueue on).  One, not one per probe: HIP spreads the streams of a process over its hardware queues,
     and a loop whose stream lands on the queue of the library's side stream runs BEHIND the sorts it should run beside -- with
-    GPU_MAX_HW_QUEUES = 8 the fourth and the eleventh stream a process created did: 32-89 instead of 21 us per step
+    eight queues the fourth and the eleventh stream a process created did: 32-89 instead of 21 us per step
     (tools/queue_alias.py, tools/zipf_trace.sh)."""
     key = (dev.type, dev.index)
     if key not in _WORK:
@@ -457,6 +454,39 @@ def stream_read_probe(fmx, torch, dev):
 GATHER_CEILINGS = None
 
 
+DUMP_SAMPLE_ROWS = 32768
+
+
+def dump_outputs(out_dir, torch, eng, table, idx_np, losses, steps):
+    """--dump-outputs: what the timed loop computed, read right after it (the passes that follow go on updating the table).
+    Every call of the loop starts at batch 0 of the pool, so its last step ran on batch (steps - 1) % N_POOL.  Written as
+    float32 (float64 for row numbers): the mean loss of every timed step; the last step's per-sample logit, dz and loss; the
+    table rows that step updated, whole (row_stride floats), with their row numbers; a fixed seeded sample of all rows; the
+    bias.  About 22 MB in all."""
+    last = (steps - 1) % N_POOL
+    offs = np.concatenate([[0], np.cumsum(CRITEO_SIZES)])[:-1].astype(np.int64)
+    touched = np.unique(idx_np[last].astype(np.int64) + offs[None, :])
+    sample = np.sort(np.random.default_rng(SEED).choice(table.n_rows, size=min(DUMP_SAMPLE_ROWS, table.n_rows), replace=False))
+    rows = table.rows
+    out = {
+        "loss_per_step": np.asarray(losses, dtype=np.float32),
+        "last_step_logit": eng.logit[:BATCH].cpu().numpy(),
+        "last_step_dz": eng.dz[:BATCH].cpu().numpy(),
+        "last_step_sample_loss": eng.loss_b[:BATCH].cpu().numpy(),
+        "last_step_touched_row_ids": touched.astype(np.float64),
+        "last_step_touched_rows": rows[torch.from_numpy(touched).to(rows.device)].cpu().numpy(),
+        "table_sample_row_ids": sample.astype(np.float64),
+        "table_sample_rows": rows[torch.from_numpy(sample).to(rows.device)].cpu().numpy(),
+        "bias": table.bias.cpu().numpy(),
+    }
+    total = sum(a.nbytes for a in out.values())
+    assert total <= 64 << 20, f"--dump-outputs: {total} bytes"
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in out.items():
+        assert a.dtype in (np.float32, np.float64), name
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -479,7 +509,12 @@ def main():
                          "MLP, SGD, data-parallel with one fused all-reduce of the dense gradients")
     ap.add_argument("--rule", default="ftrl", choices=["ftrl", "sgd", "signadam"],
                     help="update rule (the headline metric is ftrl; the others are for kernel comparisons)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path computed (its last step) as DIR/<name>.npy (fm workload, "
+                         "one GPU)")
     args = ap.parse_args()
+    if args.dump_outputs and (args.workload != "fm" or args.gpus != 1):
+        raise SystemExit("--dump-outputs: the fm workload on one GPU only")
 
     import torch
     import torch.distributed as dist
@@ -566,6 +601,8 @@ def main():
         eng.check_error_flag()
         losses = loss_buf[:args.steps].cpu().numpy()
         assert np.isfinite(losses).all(), "non-finite loss in the timed region"
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, torch, eng, table, idx_np, losses, args.steps)
         # what a 20-step call costs (the driver's round-end run is --steps 20 --warmup 5: pipeline start included)
         if args.steps != 20 and not args.loop_only:
             ts = []
