@@ -20,6 +20,8 @@
 //
 // Everything is HBM / cache-line bound integer+fp32 work; there is no GEMM here and no MFMA.
 
+#include <type_traits>
+
 #include "fmx_common.h"
 
 // ------------------------------------------------------------------------------------------------------------
@@ -1669,6 +1671,35 @@ int lpr_of(int kp) {
   }
 }
 
+// f(std::integral_constant<int, LPR>{}) for a table's kp (anything lpr_of rejects takes the widest)
+template <class Fn>
+decltype(auto) with_lpr(int kp, Fn &&f) {
+  switch (lpr_of(kp)) {
+    case 1: return f(std::integral_constant<int, 1>{});
+    case 2: return f(std::integral_constant<int, 2>{});
+    case 4: return f(std::integral_constant<int, 4>{});
+    case 8: return f(std::integral_constant<int, 8>{});
+    default: return f(std::integral_constant<int, 16>{});
+  }
+}
+
+// f(std::integral_constant<int, V>{}) for the V of VS that equals v; false (and no call) when none does
+template <int... VS, class Fn>
+bool with_one_of(int v, Fn &&f) {
+  return ((v == VS && (f(std::integral_constant<int, VS>{}), true)) || ...);
+}
+
+// f(LAYOUT, RULE) as integral constants for an update rule: SIGNADAM and SGD on the weights layout, anything else FTRL
+template <class Fn>
+decltype(auto) with_rule(int rule, Fn &&f) {
+  using Weights = std::integral_constant<int, FMX_LAYOUT_WEIGHTS>;
+  switch (rule) {
+    case FMX_RULE_SIGNADAM: return f(Weights{}, std::integral_constant<int, FMX_RULE_SIGNADAM>{});
+    case FMX_RULE_SGD: return f(Weights{}, std::integral_constant<int, FMX_RULE_SGD>{});
+    default: return f(std::integral_constant<int, FMX_LAYOUT_FTRL>{}, std::integral_constant<int, FMX_RULE_FTRL>{});
+  }
+}
+
 int check_table(const fmx_table_t *t) {
   if (!t) return fail(FMX_ERR_ARG, "table is null");
   if (!t->rows || !t->field_offsets || !t->bias) return fail(FMX_ERR_ARG, "table has a null pointer");
@@ -1832,32 +1863,22 @@ Side *side_for_current_device() {
 
 constexpr int OVERLAP_MIN_BATCH = 512;  // below this the extra event traffic costs more than the sort
 
-template <int LPR, int NPASS>
+template <int LPR, int NPASS, bool MAPPED = false>
 void launch_forward_np(const FwdArgs &a, int layout, hipStream_t st) {
   const int wpb = tune().wpb_fwd;
   const dim3 grid((a.B + wpb - 1) / wpb), block(64 * wpb);
-  if (layout == FMX_LAYOUT_WEIGHTS) hipLaunchKernelGGL((k_fm_forward<LPR, FMX_LAYOUT_WEIGHTS, NPASS>), grid, block, 0, st, a);
-  else hipLaunchKernelGGL((k_fm_forward<LPR, FMX_LAYOUT_FTRL, NPASS>), grid, block, 0, st, a);
+  if (layout == FMX_LAYOUT_WEIGHTS) hipLaunchKernelGGL((k_fm_forward<LPR, FMX_LAYOUT_WEIGHTS, NPASS, MAPPED>), grid, block, 0, st, a);
+  else hipLaunchKernelGGL((k_fm_forward<LPR, FMX_LAYOUT_FTRL, NPASS, MAPPED>), grid, block, 0, st, a);
 }
 
 template <int LPR>
 void launch_forward(const FwdArgs &a, int layout, hipStream_t st) {
   const int slots = WAVE / LPR;
   const int np = (a.F + slots - 1) / slots;
-  if (a.fcols || a.fbase) {  // fields are pieces of index columns: the generic field loop (the additions and their order are the same)
-    const int wpb = tune().wpb_fwd;
-    const dim3 grid((a.B + wpb - 1) / wpb), block(64 * wpb);
-    if (layout == FMX_LAYOUT_WEIGHTS) hipLaunchKernelGGL((k_fm_forward<LPR, FMX_LAYOUT_WEIGHTS, 0, true>), grid, block, 0, st, a);
-    else hipLaunchKernelGGL((k_fm_forward<LPR, FMX_LAYOUT_FTRL, 0, true>), grid, block, 0, st, a);
-    return;
-  }
-  switch (np) {
-    case 1: launch_forward_np<LPR, 1>(a, layout, st); break;
-    case 2: launch_forward_np<LPR, 2>(a, layout, st); break;
-    case 3: launch_forward_np<LPR, 3>(a, layout, st); break;
-    case 4: launch_forward_np<LPR, 4>(a, layout, st); break;
-    default: launch_forward_np<LPR, 0>(a, layout, st); break;
-  }
+  if (a.fcols || a.fbase)  // fields are pieces of index columns: the generic field loop (the additions and their order are the same)
+    launch_forward_np<LPR, 0, true>(a, layout, st);
+  else if (!with_one_of<1, 2, 3, 4>(np, [&](auto NP) { launch_forward_np<LPR, NP>(a, layout, st); }))
+    launch_forward_np<LPR, 0>(a, layout, st);
 }
 
 // The in-launch hand-offs tag their flag words with a per-launch sequence number passed as a kernel argument; a captured
@@ -1873,17 +1894,7 @@ void launch_update(const UpdArgs &a, int rule, hipStream_t st) {
   const int tiles = a.F * (a.Bp >> 6);
   const int wpb = tune().wpb_upd;
   const dim3 grid((tiles + wpb - 1) / wpb + red_slices(a.B)), block(64 * wpb);
-  switch (rule) {
-    case FMX_RULE_SIGNADAM:
-      hipLaunchKernelGGL((k_fm_update<LPR, FMX_LAYOUT_WEIGHTS, FMX_RULE_SIGNADAM, HAS_GBI, INL>), grid, block, 0, st, a);
-      break;
-    case FMX_RULE_SGD:
-      hipLaunchKernelGGL((k_fm_update<LPR, FMX_LAYOUT_WEIGHTS, FMX_RULE_SGD, HAS_GBI, INL>), grid, block, 0, st, a);
-      break;
-    default:
-      hipLaunchKernelGGL((k_fm_update<LPR, FMX_LAYOUT_FTRL, FMX_RULE_FTRL, HAS_GBI, INL>), grid, block, 0, st, a);
-      break;
-  }
+  with_rule(rule, [&](auto LAYOUT, auto RULE) { hipLaunchKernelGGL((k_fm_update<LPR, LAYOUT, RULE, HAS_GBI, INL>), grid, block, 0, st, a); });
 }
 
 template <int LPR>
@@ -1892,17 +1903,9 @@ void launch_update_rider(const UpdArgs &a, int rule, const MlpReduceArgs &r, hip
   const int wpb = tune().wpb_upd;
   const int n_upd = (tiles + wpb - 1) / wpb + red_slices(a.B), per = mlp_reduce_blocks_per_layer(r, 64 * wpb);
   const dim3 grid(n_upd + per * r.n_layers), block(64 * wpb);
-  switch (rule) {
-    case FMX_RULE_SIGNADAM:
-      hipLaunchKernelGGL((k_fm_update_rider<LPR, FMX_LAYOUT_WEIGHTS, FMX_RULE_SIGNADAM, true>), grid, block, 0, st, a, r, n_upd, per);
-      break;
-    case FMX_RULE_SGD:
-      hipLaunchKernelGGL((k_fm_update_rider<LPR, FMX_LAYOUT_WEIGHTS, FMX_RULE_SGD, true>), grid, block, 0, st, a, r, n_upd, per);
-      break;
-    default:
-      hipLaunchKernelGGL((k_fm_update_rider<LPR, FMX_LAYOUT_FTRL, FMX_RULE_FTRL, true>), grid, block, 0, st, a, r, n_upd, per);
-      break;
-  }
+  with_rule(rule, [&](auto LAYOUT, auto RULE) {
+    hipLaunchKernelGGL((k_fm_update_rider<LPR, LAYOUT, RULE, true>), grid, block, 0, st, a, r, n_upd, per);
+  });
 }
 
 template <int LPR>
@@ -1910,13 +1913,7 @@ void launch_fixup(const UpdArgs &a, int rule, hipStream_t st) {
   const int tiles = a.F * (a.Bp >> 6);
   const int wpb = tune().wpb_upd;
   const dim3 grid((tiles + wpb - 1) / wpb + (red_slices(a.B) > 1 ? 1 : 0)), block(64 * wpb);
-  switch (rule) {
-    case FMX_RULE_SIGNADAM:
-      hipLaunchKernelGGL((k_fm_fixup<LPR, FMX_LAYOUT_WEIGHTS, FMX_RULE_SIGNADAM>), grid, block, 0, st, a);
-      break;
-    case FMX_RULE_SGD: hipLaunchKernelGGL((k_fm_fixup<LPR, FMX_LAYOUT_WEIGHTS, FMX_RULE_SGD>), grid, block, 0, st, a); break;
-    default: hipLaunchKernelGGL((k_fm_fixup<LPR, FMX_LAYOUT_FTRL, FMX_RULE_FTRL>), grid, block, 0, st, a); break;
-  }
+  with_rule(rule, [&](auto LAYOUT, auto RULE) { hipLaunchKernelGGL((k_fm_fixup<LPR, LAYOUT, RULE>), grid, block, 0, st, a); });
 }
 
 template <int LPR>
@@ -2026,15 +2023,102 @@ int sort_impl(const fmx_table_t *table, const int32_t *idx, int32_t B, uint32_t 
   int E = a.Bp <= 64 ? 1 : a.Bp <= 128 ? 2 : a.Bp <= 4096 ? 4 : a.Bp <= 8192 ? 8 : a.Bp <= 16384 ? 16 : 32;
   const int want = tune().sort_e;
   if (want > E && want <= 32 && (want & (want - 1)) == 0 && a.Bp / want >= 64) E = want;
-  switch (E) {
-    case 1: launch_sort<1>(a, st); break;
-    case 2: launch_sort<2>(a, st); break;
-    case 4: launch_sort<4>(a, st); break;
-    case 8: launch_sort<8>(a, st); break;
-    case 16: launch_sort<16>(a, st); break;
-    default: launch_sort<32>(a, st); break;
-  }
+  if (!with_one_of<1, 2, 4, 8, 16>(E, [&](auto E_) { launch_sort<E_>(a, st); })) launch_sort<32>(a, st);
   return check_launch("k_sort_occ");
+}
+
+// sorts steps [first_step, first_step + n) of a pool of n_pool batches (step s takes batch s mod n_pool) with one launch, into
+// n consecutive sorted buffers of the workspace from `sorted` on
+int sort_pool(const fmx_table_t *table, const int32_t *idx_pool, int n_pool, int B, int first_step, int n, const Workspace &w,
+              uint32_t *sorted, int32_t *error, hipStream_t st) {
+  SortBatch mb;
+  mb.n_pool = n_pool;
+  mb.first = first_step % n_pool;
+  mb.n_batches = n;
+  mb.pool_stride = (int64_t)B * (int64_t)n_cols(table);
+  mb.sorted_stride = (int64_t)w.sorted_stride;
+  return sort_impl(table, idx_pool, B, sorted, w.runs, error, st, &mb);
+}
+
+// A loop called on the legacy default stream (handle 0: it cannot be captured and is slow to enqueue on) runs on the side's
+// stand-in main stream instead, after the caller's work; the caller's stream waits for it when the guard goes.  `st` is the
+// stream to issue on.  No detour without a side (sd == nullptr) or on any other stream.
+struct Detour {
+  Side *sd;
+  hipStream_t user, st;
+  Detour(Side *side, hipStream_t stream) : sd(stream == nullptr ? side : nullptr), user(stream), st(stream) {
+    if (!sd) return;
+    (void)hipEventRecord(sd->user_fork, user);
+    st = sd->main;
+    (void)hipStreamWaitEvent(st, sd->user_fork, 0);
+  }
+  ~Detour() {
+    if (!sd) return;
+    (void)hipEventRecord(sd->user_join, st);
+    (void)hipStreamWaitEvent(user, sd->user_join, 0);
+  }
+  Detour(const Detour &) = delete;
+  Detour &operator=(const Detour &) = delete;
+};
+
+// The online loop over a device-resident pool (fmx_fm_stream, fmx_deepfm_stream): step s takes batch s mod n_pool and runs
+// before_update(s, idx, y, st), then update(s, sorted, st) with the batch's sorted occurrence list; either returns a status.
+// The occurrence sort does not depend on the weights: groups of `ahead` batches are sorted by ONE launch on the side stream
+// while the previous group runs forward / update / fixup on `stream`.  Ring of 2 * ahead sorted buffers; per group one sort
+// launch and four event operations, so the host issues ~3.6 runtime calls per step instead of 8 (at ~4 us each the per-batch
+// version was host-bound).  Below OVERLAP_MIN_BATCH every group is sorted on `stream` in front of its steps.
+template <class BeforeUpdate, class Update>
+int pool_loop(const fmx_table_t *table, const int32_t *idx_pool, const float *y_pool, int n_pool, int B, int n_steps,
+              const Workspace &w, int32_t *error, hipStream_t stream, BeforeUpdate &&before_update, Update &&update) {
+  Side *sd = (B >= OVERLAP_MIN_BATCH && n_steps > 0) ? side_for_current_device() : nullptr;
+  const Detour detour(sd, stream);
+  const hipStream_t st = detour.st;
+  const size_t F = (size_t)n_cols(table);
+  int ahead = tune().sort_ahead;
+  if (ahead < 1) ahead = 1;
+  if (ahead > SORT_AHEAD_MAX) ahead = SORT_AHEAD_MAX;
+  // the first group holds up to 4 batches, the others `ahead` (8): one launch sorts four batches in about the time of one (one
+  // workgroup per field and batch: 18.4 against 17.1 us, tools/micro/sort_bench.hip), so the first update waits no longer than
+  // behind a one-batch group, and a short call issues three sort launches and their events instead of five while the device
+  // is still waiting for the host.  Group g uses half (g & 1) of the ring of 2 * ahead sorted buffers.
+  auto group_size = [&](int g, int first_step) {
+    int n = g == 0 ? 4 : ahead;
+    if (n > ahead) n = ahead;
+    if (n > n_steps - first_step) n = n_steps - first_step;
+    return n;
+  };
+  auto sort_group = [&](int g, int first_step, int n, hipStream_t where) -> int {  // steps [first_step, first_step + n)
+    return sort_pool(table, idx_pool, n_pool, B, first_step, n, w, w.sorted + (size_t)(g & 1) * ahead * w.sorted_stride, error, where);
+  };
+  int rc = FMX_OK;
+  if (sd) {
+    (void)hipEventRecord(sd->fork, st);
+    (void)hipStreamWaitEvent(sd->stream, sd->fork, 0);
+    rc = sort_group(0, 0, group_size(0, 0), sd->stream);
+    (void)hipEventRecord(sd->sorted[0], sd->stream);
+  }
+  int first_step = 0;
+  for (int g = 0; first_step < n_steps && rc == FMX_OK; ++g) {
+    const int n = group_size(g, first_step);
+    const int next_first = first_step + n;
+    if (!sd) rc = sort_group(g, first_step, n, st);
+    for (int i = 0; i < n && rc == FMX_OK; ++i) {
+      const int s = first_step + i, j = s % n_pool;
+      rc = before_update(s, idx_pool + (size_t)j * B * F, y_pool + (size_t)j * B, st);
+      if (sd && i == 0) (void)hipStreamWaitEvent(st, sd->sorted[g & 1], 0);
+      if (rc == FMX_OK) rc = update(s, w.sorted + ((size_t)(g & 1) * ahead + i) * w.sorted_stride, st);
+      // the next group is sorted while this one runs; its launch is issued BEHIND the group's first step, so that at the start
+      // of a call -- the device idle, every launch waiting for the host -- the first forward and update are not held up by it
+      if (sd && i == 0 && next_first < n_steps && rc == FMX_OK) {
+        if (g >= 1) (void)hipStreamWaitEvent(sd->stream, sd->consumed[(g + 1) & 1], 0);  // group g-1 is done with that half
+        rc = sort_group(g + 1, next_first, group_size(g + 1, next_first), sd->stream);
+        (void)hipEventRecord(sd->sorted[(g + 1) & 1], sd->stream);
+      }
+    }
+    if (sd) (void)hipEventRecord(sd->consumed[g & 1], st);
+    first_step = next_first;
+  }
+  return rc;
 }
 
 FwdArgs fill_fwd(const fmx_table_t *table, const fmx_hyper_t *hyper, const int32_t *idx, const float *xv, const float *y,
@@ -2067,13 +2151,7 @@ FwdArgs fill_fwd(const fmx_table_t *table, const fmx_hyper_t *hyper, const int32
 int forward_impl(const fmx_table_t *table, const fmx_hyper_t *hyper, const int32_t *idx, const float *xv, const float *y,
                  int32_t B, int32_t loss_kind, float inv_b, const fmx_fwd_out_t *out, hipStream_t st) {
   const FwdArgs a = fill_fwd(table, hyper, idx, xv, y, B, loss_kind, inv_b, out);
-  switch (lpr_of(table->kp)) {
-    case 1: launch_forward<1>(a, table->layout, st); break;
-    case 2: launch_forward<2>(a, table->layout, st); break;
-    case 4: launch_forward<4>(a, table->layout, st); break;
-    case 8: launch_forward<8>(a, table->layout, st); break;
-    default: launch_forward<16>(a, table->layout, st); break;
-  }
+  with_lpr(table->kp, [&](auto LPR) { launch_forward<LPR>(a, table->layout, st); });
   return check_launch("k_fm_forward");
 }
 
@@ -2130,44 +2208,19 @@ int update_impl(const fmx_table_t *table, const fmx_hyper_t *hyper, int32_t rule
                              sample_ld, err_flag);
   if (rider) {
     if (gbi != nullptr && tune().inline_fixup && !is_capturing(st)) {  // the one-launch form of the update: the rider goes with it
-      switch (lpr_of(table->kp)) {
-        case 1: launch_update_rider<1>(a, rule, *rider, st); break;
-        case 2: launch_update_rider<2>(a, rule, *rider, st); break;
-        case 4: launch_update_rider<4>(a, rule, *rider, st); break;
-        case 8: launch_update_rider<8>(a, rule, *rider, st); break;
-        default: launch_update_rider<16>(a, rule, *rider, st); break;
-      }
+      with_lpr(table->kp, [&](auto LPR) { launch_update_rider<LPR>(a, rule, *rider, st); });
       return check_launch("k_fm_update_rider");
     }
     mlp_launch_reduce(*rider, st);  // otherwise the reduction as a launch of its own, in front
   }
-  switch (lpr_of(table->kp)) {
-    case 1: launch_update_pair<1>(a, rule, gbi != nullptr, st); break;
-    case 2: launch_update_pair<2>(a, rule, gbi != nullptr, st); break;
-    case 4: launch_update_pair<4>(a, rule, gbi != nullptr, st); break;
-    case 8: launch_update_pair<8>(a, rule, gbi != nullptr, st); break;
-    default: launch_update_pair<16>(a, rule, gbi != nullptr, st); break;
-  }
+  with_lpr(table->kp, [&](auto LPR) { launch_update_pair<LPR>(a, rule, gbi != nullptr, st); });
   return check_launch("k_fm_update / k_fm_fixup");
 }
 
 template <int LPR, int LAYOUT, int RULE>
 void launch_online_np(const OnlineArgs &a, int np, hipStream_t st) {
-  switch (np) {
-    case 1: hipLaunchKernelGGL((k_fm_online<LPR, LAYOUT, RULE, 1>), dim3(1), dim3(64), 0, st, a); break;
-    case 2: hipLaunchKernelGGL((k_fm_online<LPR, LAYOUT, RULE, 2>), dim3(1), dim3(64), 0, st, a); break;
-    case 3: hipLaunchKernelGGL((k_fm_online<LPR, LAYOUT, RULE, 3>), dim3(1), dim3(64), 0, st, a); break;
-    default: hipLaunchKernelGGL((k_fm_online<LPR, LAYOUT, RULE, 4>), dim3(1), dim3(64), 0, st, a); break;
-  }
-}
-
-template <int LPR>
-void launch_online(const OnlineArgs &a, int rule, int np, hipStream_t st) {
-  switch (rule) {
-    case FMX_RULE_SIGNADAM: launch_online_np<LPR, FMX_LAYOUT_WEIGHTS, FMX_RULE_SIGNADAM>(a, np, st); break;
-    case FMX_RULE_SGD: launch_online_np<LPR, FMX_LAYOUT_WEIGHTS, FMX_RULE_SGD>(a, np, st); break;
-    default: launch_online_np<LPR, FMX_LAYOUT_FTRL, FMX_RULE_FTRL>(a, np, st); break;
-  }
+  auto launch = [&](auto NP) { hipLaunchKernelGGL((k_fm_online<LPR, LAYOUT, RULE, NP>), dim3(1), dim3(64), 0, st, a); };
+  if (!with_one_of<1, 2, 3>(np, launch)) launch(std::integral_constant<int, 4>{});
 }
 
 constexpr int ONLINE_MLP_MAX_PARAMS = 8192;  // floats of MLP parameters kept in LDS by k_online_mlp
@@ -2184,23 +2237,11 @@ void launch_online_mlp_k(const OnlineMlpArgs &a, hipStream_t st) {
 }
 
 template <int LPR>
-void launch_online_mlp(const OnlineMlpArgs &a, int layout, int rule, hipStream_t st) {
-  if (layout == FMX_LAYOUT_FTRL) launch_online_mlp_k<LPR, FMX_LAYOUT_FTRL, FMX_RULE_FTRL>(a, st);  // Hedge only: tables are read
-  else if (rule == FMX_RULE_SGD) launch_online_mlp_k<LPR, FMX_LAYOUT_WEIGHTS, FMX_RULE_SGD>(a, st);
-  else launch_online_mlp_k<LPR, FMX_LAYOUT_WEIGHTS, FMX_RULE_SIGNADAM>(a, st);
-}
-
-template <int LPR>
 int launch_forward_part(const PartArgs &a, int np, int n_local_blocks, hipStream_t st) {
   const int per_wave = (WAVE / LPR) >> a.sl_log2, waves = (a.B + per_wave - 1) / per_wave;
   const dim3 grid((waves + 3) / 4, n_local_blocks), block(256);
-  switch (np) {
-    case 1: hipLaunchKernelGGL((k_fm_forward_part<LPR, 1>), grid, block, 0, st, a); break;
-    case 2: hipLaunchKernelGGL((k_fm_forward_part<LPR, 2>), grid, block, 0, st, a); break;
-    case 3: hipLaunchKernelGGL((k_fm_forward_part<LPR, 3>), grid, block, 0, st, a); break;
-    case 4: hipLaunchKernelGGL((k_fm_forward_part<LPR, 4>), grid, block, 0, st, a); break;
-    default: return fail(FMX_ERR_UNSUPPORTED, "fmx_fm_forward_partial: more than 4 fields per lane group");
-  }
+  if (!with_one_of<1, 2, 3, 4>(np, [&](auto NP) { hipLaunchKernelGGL((k_fm_forward_part<LPR, NP>), grid, block, 0, st, a); }))
+    return fail(FMX_ERR_UNSUPPORTED, "fmx_fm_forward_partial: more than 4 fields per lane group");
   return check_launch("k_fm_forward_part");
 }
 
@@ -2208,14 +2249,8 @@ template <int LPR, int LAYOUT>
 int launch_forward_finish_g(const FinishArgs &a, int G, hipStream_t st) {
   const int waves = (a.B + (WAVE / LPR) - 1) / (WAVE / LPR);
   const dim3 grid((waves + 3) / 4), block(256);
-  switch (G) {
-    case 1: hipLaunchKernelGGL((k_fm_forward_finish<LPR, LAYOUT, 1>), grid, block, 0, st, a); break;
-    case 2: hipLaunchKernelGGL((k_fm_forward_finish<LPR, LAYOUT, 2>), grid, block, 0, st, a); break;
-    case 4: hipLaunchKernelGGL((k_fm_forward_finish<LPR, LAYOUT, 4>), grid, block, 0, st, a); break;
-    case 8: hipLaunchKernelGGL((k_fm_forward_finish<LPR, LAYOUT, 8>), grid, block, 0, st, a); break;
-    case 16: hipLaunchKernelGGL((k_fm_forward_finish<LPR, LAYOUT, 16>), grid, block, 0, st, a); break;
-    default: return fail(FMX_ERR_ARG, "fmx_fm_forward_finish: n_owners must be 1, 2, 4, 8 or 16");
-  }
+  if (!with_one_of<1, 2, 4, 8, 16>(G, [&](auto G_) { hipLaunchKernelGGL((k_fm_forward_finish<LPR, LAYOUT, G_>), grid, block, 0, st, a); }))
+    return fail(FMX_ERR_ARG, "fmx_fm_forward_finish: n_owners must be 1, 2, 4, 8 or 16");
   return check_launch("k_fm_forward_finish");
 }
 
@@ -2256,13 +2291,7 @@ int part_impl(const fmx_table_t *table, const int32_t *idx, const float *xv, int
   a.sl_log2 = sl_log2;
   a.group = group;
   const int np = (table->n_fields + n_local_blocks * sl - 1) / (n_local_blocks * sl);
-  switch (lpr) {
-    case 1: return launch_forward_part<1>(a, np, n_local_blocks, st);
-    case 2: return launch_forward_part<2>(a, np, n_local_blocks, st);
-    case 4: return launch_forward_part<4>(a, np, n_local_blocks, st);
-    case 8: return launch_forward_part<8>(a, np, n_local_blocks, st);
-    default: return launch_forward_part<16>(a, np, n_local_blocks, st);
-  }
+  return with_lpr(table->kp, [&](auto LPR) { return launch_forward_part<LPR>(a, np, n_local_blocks, st); });
 }
 
 int check_forward_args(const fmx_table_t *table, const fmx_hyper_t *hyper, const int32_t *idx, const float *y, int32_t B,
@@ -2380,13 +2409,7 @@ int fmx_fm_forward_finish(const fmx_hyper_t *hyper, const float *bias, int32_t l
   a.ld1 = out->sample_ld > 0 ? out->sample_ld : 1;
   a.inv_b = inv_b;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  switch (lpr_of(kp)) {
-    case 1: return launch_forward_finish<1>(a, layout, n_owners, st);
-    case 2: return launch_forward_finish<2>(a, layout, n_owners, st);
-    case 4: return launch_forward_finish<4>(a, layout, n_owners, st);
-    case 8: return launch_forward_finish<8>(a, layout, n_owners, st);
-    default: return launch_forward_finish<16>(a, layout, n_owners, st);
-  }
+  return with_lpr(kp, [&](auto LPR) { return launch_forward_finish<LPR>(a, layout, n_owners, st); });
 }
 
 int fmx_sort_occurrences(const fmx_table_t *table, const int32_t *idx, int32_t B, void *workspace, int64_t workspace_bytes, int32_t *error,
@@ -2427,7 +2450,7 @@ __global__ void k_first_plus_bias(float *out, const float *sfirst, const float *
 
 // The mini-batch DeepFM loop over a device-resident pool (BASELINE configs[3]): per step the forward of the tables, the MLP
 // section on bi (fmx_mlp_section: k_mlp_chain, k_mlp_wgrad_stream, k_mlp_reduce with the SGD of the MLP applied in it) and the
-// table update with dL/dbi, all issued from here; the occurrence sorts run in groups on the side stream as in fmx_fm_stream.
+// table update with dL/dbi, all issued from here; the occurrence sorts run in groups on the side stream (pool_loop).
 // Through the Python trainer the same step is bound by its host side (84 us of calls per step for 67 us of kernels).
 int fmx_deepfm_stream(const fmx_table_t *table, const fmx_hyper_t *hyper, int32_t rule, const fmx_mlp_t *mlp, int32_t loss_kind, int32_t fm_term,
                       const int32_t *idx_pool, const float *y_pool, int32_t n_pool, int32_t B, float inv_b, int32_t n_steps,
@@ -2444,80 +2467,25 @@ int fmx_deepfm_stream(const fmx_table_t *table, const fmx_hyper_t *hyper, int32_
   if (mlp->k > table->kp) return fail(FMX_ERR_SHAPE, "fmx_deepfm_stream: the MLP reads k=%d columns of a bi of kp=%d", mlp->k, table->kp);
   if (!aligned16(gbi) || !aligned16(dz)) return fail(FMX_ERR_ALIGN, "dz and gbi must be 16-byte aligned");
   if (int rc = check_sort_geometry(table, B)) return rc;
-  hipStream_t st = static_cast<hipStream_t>(stream);
   if (int rc = check_workspace(table, B, workspace, workspace_bytes, "fmx_deepfm_stream")) return rc;
   const Workspace w = carve(table, B, workspace);
-  const size_t F = (size_t)n_cols(table);
-  int rc = FMX_OK;
-  Side *sd = (B >= OVERLAP_MIN_BATCH && n_steps > 0) ? side_for_current_device() : nullptr;
-  hipStream_t user = st;
-  const bool detour = sd && st == nullptr;  // off the legacy default stream (see fmx_fm_stream)
-  if (detour) {
-    (void)hipEventRecord(sd->user_fork, user);
-    st = sd->main;
-    (void)hipStreamWaitEvent(st, sd->user_fork, 0);
-  }
-  int ahead = tune().sort_ahead;
-  if (ahead < 1) ahead = 1;
-  if (ahead > SORT_AHEAD_MAX) ahead = SORT_AHEAD_MAX;
-  auto group_size = [&](int g, int first_step) {
-    int n = g == 0 ? 4 : ahead;
-    if (n > ahead) n = ahead;
-    if (n > n_steps - first_step) n = n_steps - first_step;
-    return n;
-  };
-  auto sort_group = [&](int g, int first_step, int n, hipStream_t where) -> int {
-    SortBatch mb;
-    mb.n_pool = n_pool;
-    mb.first = first_step % n_pool;
-    mb.n_batches = n;
-    mb.pool_stride = (int64_t)B * (int64_t)F;
-    mb.sorted_stride = (int64_t)w.sorted_stride;
-    return sort_impl(table, idx_pool, B, w.sorted + (size_t)(g & 1) * ahead * w.sorted_stride, w.runs, fwd->error, where, &mb);
-  };
-  if (sd && n_steps > 0) {
-    (void)hipEventRecord(sd->fork, st);
-    (void)hipStreamWaitEvent(sd->stream, sd->fork, 0);
-    rc = sort_group(0, 0, group_size(0, 0), sd->stream);
-    (void)hipEventRecord(sd->sorted[0], sd->stream);
-  }
-  int first_step = 0;
-  for (int g = 0; first_step < n_steps && rc == FMX_OK; ++g) {
-    const int n = group_size(g, first_step);
-    const int next_first = first_step + n;
-    if (!sd) rc = sort_group(g, first_step, n, st);
-    for (int i = 0; i < n && rc == FMX_OK; ++i) {
-      const int s = first_step + i, j = s % n_pool;
-      const int32_t *idx = idx_pool + (size_t)j * B * F;
-      const float *y = y_pool + (size_t)j * B;
-      const uint32_t *sorted = w.sorted + ((size_t)(g & 1) * ahead + i) * w.sorted_stride;
-      rc = forward_impl(table, hyper, idx, nullptr, nullptr, B, FMX_LOSS_NONE, inv_b, fwd, st);
-      if (rc == FMX_OK && !fm_term) {  // NFM: the network's input logit is first-order + bias; the FM logit's buffer holds it
-        hipLaunchKernelGGL(k_first_plus_bias, dim3((B + 255) / 256), dim3(256), 0, st, fwd->logit, fwd->sfirst, table->bias, B);
-        rc = check_launch("fmx_deepfm_stream (k_first_plus_bias)");
-      }
-      MlpReduceArgs red;  // the section's last launch rides inside the table update's (k_fm_update_rider)
-      if (rc == FMX_OK)
-        rc = mlp_section_deferred_reduce(mlp, loss_kind, fwd->bi, table->kp, fwd->logit, y, B, inv_b, mlp_workspace, nullptr, dz, gbi, table->kp,
-                                         grads, lr_mlp, loss_out ? loss_out + s : nullptr, st, &red);
-      if (sd && i == 0) (void)hipStreamWaitEvent(st, sd->sorted[g & 1], 0);
-      if (rc == FMX_OK)
-        rc = update_impl(table, hyper, rule, w, sorted, nullptr, fwd->S, dz, fm_term ? dz : nullptr, gbi, B, nullptr, inv_b, nullptr, st, nullptr, 0,
-                         fwd->error, &red);
-      if (sd && i == 0 && next_first < n_steps && rc == FMX_OK) {
-        if (g >= 1) (void)hipStreamWaitEvent(sd->stream, sd->consumed[(g + 1) & 1], 0);
-        rc = sort_group(g + 1, next_first, group_size(g + 1, next_first), sd->stream);
-        (void)hipEventRecord(sd->sorted[(g + 1) & 1], sd->stream);
-      }
+  MlpReduceArgs red;  // the section's last launch, set up by before_update, rides inside the table update's (k_fm_update_rider)
+  auto before_update = [&](int s, const int32_t *idx, const float *y, hipStream_t st) -> int {
+    int rc = forward_impl(table, hyper, idx, nullptr, nullptr, B, FMX_LOSS_NONE, inv_b, fwd, st);
+    if (rc == FMX_OK && !fm_term) {  // NFM: the network's input logit is first-order + bias; the FM logit's buffer holds it
+      hipLaunchKernelGGL(k_first_plus_bias, dim3((B + 255) / 256), dim3(256), 0, st, fwd->logit, fwd->sfirst, table->bias, B);
+      rc = check_launch("fmx_deepfm_stream (k_first_plus_bias)");
     }
-    if (sd) (void)hipEventRecord(sd->consumed[g & 1], st);
-    first_step = next_first;
-  }
-  if (detour) {
-    (void)hipEventRecord(sd->user_join, st);
-    (void)hipStreamWaitEvent(user, sd->user_join, 0);
-  }
-  return rc;
+    if (rc == FMX_OK)
+      rc = mlp_section_deferred_reduce(mlp, loss_kind, fwd->bi, table->kp, fwd->logit, y, B, inv_b, mlp_workspace, nullptr, dz, gbi, table->kp,
+                                       grads, lr_mlp, loss_out ? loss_out + s : nullptr, st, &red);
+    return rc;
+  };
+  auto update = [&](int, const uint32_t *sorted, hipStream_t st) {
+    return update_impl(table, hyper, rule, w, sorted, nullptr, fwd->S, dz, fm_term ? dz : nullptr, gbi, B, nullptr, inv_b, nullptr, st, nullptr, 0,
+                       fwd->error, &red);
+  };
+  return pool_loop(table, idx_pool, y_pool, n_pool, B, n_steps, w, fwd->error, static_cast<hipStream_t>(stream), before_update, update);
 }
 
 // ---- the field-owner step with the library's own communicator (fmx_comm.hip) ----
@@ -2630,84 +2598,15 @@ int fmx_fm_stream(const fmx_table_t *table, const fmx_hyper_t *hyper, int32_t ru
   hipStream_t st = static_cast<hipStream_t>(stream);
   if (int rc = check_workspace(table, B, workspace, workspace_bytes, "fmx_fm_stream")) return rc;
   const Workspace w = carve(table, B, workspace);
-  const size_t F = (size_t)n_cols(table);
-  int rc = FMX_OK;
-
-  if (!kernel_ms) {
-    // production path.  The occurrence sort does not depend on the weights: groups of `ahead` batches are sorted by ONE
-    // launch on the side stream while the previous group runs forward / update / fixup on `stream`.  Ring of
-    // 2 * ahead sorted buffers; per group one sort launch and four event operations, so the host issues ~3.6 runtime
-    // calls per step instead of 8 (at ~4 us each the per-batch version was host-bound).
-    Side *sd = (B >= OVERLAP_MIN_BATCH && n_steps > 0) ? side_for_current_device() : nullptr;
-    hipStream_t user = st;
-    const bool detour = sd && st == nullptr;  // the legacy default stream cannot be captured / is slow to enqueue on
-    if (detour) {
-      (void)hipEventRecord(sd->user_fork, user);
-      st = sd->main;
-      (void)hipStreamWaitEvent(st, sd->user_fork, 0);
-    }
-    auto rejoin = [&](int r) -> int {
-      if (detour) {
-        (void)hipEventRecord(sd->user_join, st);
-        (void)hipStreamWaitEvent(user, sd->user_join, 0);
-      }
-      return r;
+  if (!kernel_ms) {  // production path
+    auto forward = [&](int, const int32_t *idx, const float *y, hipStream_t st) {
+      return forward_impl(table, hyper, idx, nullptr, y, B, loss_kind, inv_b, fwd, st);
     };
-    int ahead = tune().sort_ahead;
-    if (ahead < 1) ahead = 1;
-    if (ahead > SORT_AHEAD_MAX) ahead = SORT_AHEAD_MAX;
-    // the first group holds up to 4 batches, the others `ahead` (8): one launch sorts four batches in about the time of one (one
-    // workgroup per field and batch: 18.4 against 17.1 us, tools/micro/sort_bench.hip), so the first update waits no longer than
-    // behind a one-batch group, and a short call issues three sort launches and their events instead of five while the device
-    // is still waiting for the host.  Group g uses half (g & 1) of the ring of 2 * ahead sorted buffers.
-    auto group_size = [&](int g, int first_step) {
-      int n = g == 0 ? 4 : ahead;
-      if (n > ahead) n = ahead;
-      if (n > n_steps - first_step) n = n_steps - first_step;
-      return n;
+    auto update = [&](int s, const uint32_t *sorted, hipStream_t st) {
+      return update_impl(table, hyper, rule, w, sorted, nullptr, fwd->S, fwd->dz, fwd->dz, nullptr, B, fwd->loss, inv_b,
+                         loss_out ? loss_out + s : nullptr, st, nullptr, fwd->sample_ld, fwd->error);
     };
-    auto sort_group = [&](int g, int first_step, int n, hipStream_t where) -> int {  // steps [first_step, first_step + n)
-      SortBatch mb;
-      mb.n_pool = n_pool;
-      mb.first = first_step % n_pool;
-      mb.n_batches = n;
-      mb.pool_stride = (int64_t)B * (int64_t)F;
-      mb.sorted_stride = (int64_t)w.sorted_stride;
-      return sort_impl(table, idx_pool, B, w.sorted + (size_t)(g & 1) * ahead * w.sorted_stride, w.runs, fwd->error, where, &mb);
-    };
-    if (sd && n_steps > 0) {
-      (void)hipEventRecord(sd->fork, st);
-      (void)hipStreamWaitEvent(sd->stream, sd->fork, 0);
-      rc = sort_group(0, 0, group_size(0, 0), sd->stream);
-      (void)hipEventRecord(sd->sorted[0], sd->stream);
-    }
-    int first_step = 0;
-    for (int g = 0; first_step < n_steps && rc == FMX_OK; ++g) {
-      const int n = group_size(g, first_step);
-      const int next_first = first_step + n;
-      if (!sd) rc = sort_group(g, first_step, n, st);
-      for (int i = 0; i < n && rc == FMX_OK; ++i) {
-        const int s = first_step + i, j = s % n_pool;
-        const int32_t *idx = idx_pool + (size_t)j * B * F;
-        const float *y = y_pool + (size_t)j * B;
-        const uint32_t *sorted = w.sorted + ((size_t)(g & 1) * ahead + i) * w.sorted_stride;
-        rc = forward_impl(table, hyper, idx, nullptr, y, B, loss_kind, inv_b, fwd, st);
-        if (sd && i == 0) (void)hipStreamWaitEvent(st, sd->sorted[g & 1], 0);
-        if (rc == FMX_OK)
-          rc = update_impl(table, hyper, rule, w, sorted, nullptr, fwd->S, fwd->dz, fwd->dz, nullptr, B, fwd->loss, inv_b,
-                           loss_out ? loss_out + s : nullptr, st, nullptr, fwd->sample_ld, fwd->error);
-        // the next group is sorted while this one runs; its launch is issued BEHIND the group's first step, so that at the start
-        // of a call -- the device idle, every launch waiting for the host -- the first forward and update are not held up by it
-        if (sd && i == 0 && next_first < n_steps && rc == FMX_OK) {
-          if (g >= 1) (void)hipStreamWaitEvent(sd->stream, sd->consumed[(g + 1) & 1], 0);  // group g-1 is done with that half
-          rc = sort_group(g + 1, next_first, group_size(g + 1, next_first), sd->stream);
-          (void)hipEventRecord(sd->sorted[(g + 1) & 1], sd->stream);
-        }
-      }
-      if (sd) (void)hipEventRecord(sd->consumed[g & 1], st);
-      first_step = next_first;
-    }
-    return rejoin(rc);
+    return pool_loop(table, idx_pool, y_pool, n_pool, B, n_steps, w, fwd->error, st, forward, update);
   }
 
   // measuring mode: everything on `stream`.  An event pair costs several microseconds of its own on this stack (slot 3
@@ -2718,55 +2617,44 @@ int fmx_fm_stream(const fmx_table_t *table, const fmx_hyper_t *hyper, int32_t ru
   // instead of from an L2 warmed by the previous launch of the same batch.  The forwards of a group all read the table
   // before the group's updates, so this pass is a measurement, not the online algorithm.
   const int REP = 8, n_ev = 5;
-  hipStream_t user_t = st;
-  Side *sdt = (st == nullptr) ? side_for_current_device() : nullptr;  // same detour off the legacy stream as above
-  if (sdt) {
-    (void)hipEventRecord(sdt->user_fork, user_t);
-    st = sdt->main;
-    (void)hipStreamWaitEvent(st, sdt->user_fork, 0);
-  }
   const int n_groups = (n_steps + REP - 1) / REP;
+  const size_t F = (size_t)n_cols(table);
   const size_t region = align_up((size_t)B * table->kp + 2 * (size_t)B, 64);  // floats: S | dz | loss of one batch
   float *tmp = nullptr;
-  if (n_groups > 0 && hipMalloc(&tmp, REP * region * sizeof(float)) != hipSuccess) return fail(FMX_ERR_LAUNCH, "hipMalloc (measuring mode)");
-  hipEvent_t *ev = new hipEvent_t[(size_t)n_groups * n_ev];
-  for (int i = 0; i < n_groups * n_ev; ++i) (void)hipEventCreate(&ev[i]);
-  for (int g = 0; g < n_groups && rc == FMX_OK; ++g) {
-    const int first = g * REP, n = (n_steps - first) < REP ? (n_steps - first) : REP;
-    hipEvent_t *e = ev + (size_t)g * n_ev;
-    (void)hipEventRecord(e[0], st);
-    {
-      SortBatch mb;
-      mb.n_pool = n_pool;
-      mb.first = first % n_pool;
-      mb.n_batches = n;
-      mb.pool_stride = (int64_t)B * (int64_t)F;
-      mb.sorted_stride = (int64_t)w.sorted_stride;
-      rc = sort_impl(table, idx_pool, B, w.sorted, w.runs, fwd->error, st, &mb);
+  hipEvent_t *ev = nullptr;
+  int rc = FMX_OK;
+  {
+    const Detour detour(st == nullptr ? side_for_current_device() : nullptr, st);  // off the legacy stream, as in pool_loop
+    st = detour.st;
+    if (n_groups > 0 && hipMalloc(&tmp, REP * region * sizeof(float)) != hipSuccess)
+      return fail(FMX_ERR_LAUNCH, "hipMalloc (measuring mode)");
+    ev = new hipEvent_t[(size_t)n_groups * n_ev];
+    for (int i = 0; i < n_groups * n_ev; ++i) (void)hipEventCreate(&ev[i]);
+    for (int g = 0; g < n_groups && rc == FMX_OK; ++g) {
+      const int first = g * REP, n = (n_steps - first) < REP ? (n_steps - first) : REP;
+      hipEvent_t *e = ev + (size_t)g * n_ev;
+      (void)hipEventRecord(e[0], st);
+      rc = sort_pool(table, idx_pool, n_pool, B, first, n, w, w.sorted, fwd->error, st);
+      (void)hipEventRecord(e[1], st);
+      for (int r = 0; r < n && rc == FMX_OK; ++r) {
+        const int j = (first + r) % n_pool;
+        fmx_fwd_out_t fr = *fwd;
+        fr.S = tmp + (size_t)r * region;
+        fr.dz = fr.S + (size_t)B * table->kp;
+        fr.loss = fr.dz + B;
+        fr.sample_ld = 0;
+        rc = forward_impl(table, hyper, idx_pool + (size_t)j * B * F, nullptr, y_pool + (size_t)j * B, B, loss_kind, inv_b, &fr, st);
+      }
+      (void)hipEventRecord(e[2], st);
+      for (int r = 0; r < n && rc == FMX_OK; ++r) {
+        const float *S = tmp + (size_t)r * region, *dz = S + (size_t)B * table->kp;
+        rc = update_impl(table, hyper, rule, w, w.sorted + (size_t)r * w.sorted_stride, nullptr, S, dz, dz, nullptr, B, dz + B, inv_b,
+                         loss_out ? loss_out + first + r : nullptr, st, nullptr, 0, fwd->error);
+      }
+      (void)hipEventRecord(e[3], st);
+      (void)hipEventRecord(e[4], st);
     }
-    (void)hipEventRecord(e[1], st);
-    for (int r = 0; r < n && rc == FMX_OK; ++r) {
-      const int j = (first + r) % n_pool;
-      fmx_fwd_out_t fr = *fwd;
-      fr.S = tmp + (size_t)r * region;
-      fr.dz = fr.S + (size_t)B * table->kp;
-      fr.loss = fr.dz + B;
-      fr.sample_ld = 0;
-      rc = forward_impl(table, hyper, idx_pool + (size_t)j * B * F, nullptr, y_pool + (size_t)j * B, B, loss_kind, inv_b, &fr, st);
-    }
-    (void)hipEventRecord(e[2], st);
-    for (int r = 0; r < n && rc == FMX_OK; ++r) {
-      const float *S = tmp + (size_t)r * region, *dz = S + (size_t)B * table->kp;
-      rc = update_impl(table, hyper, rule, w, w.sorted + (size_t)r * w.sorted_stride, nullptr, S, dz, dz, nullptr, B, dz + B, inv_b,
-                       loss_out ? loss_out + first + r : nullptr, st, nullptr, 0, fwd->error);
-    }
-    (void)hipEventRecord(e[3], st);
-    (void)hipEventRecord(e[4], st);
-  }
-  (void)hipStreamSynchronize(st);
-  if (sdt) {
-    (void)hipEventRecord(sdt->user_join, st);
-    (void)hipStreamWaitEvent(user_t, sdt->user_join, 0);
+    (void)hipStreamSynchronize(st);
   }
   for (int k = 0; k < 4; ++k) kernel_ms[k] = 0.f;
   if (rc == FMX_OK && n_groups > 0) {
@@ -2826,13 +2714,9 @@ int fmx_fm_online_run(const fmx_table_t *table, const fmx_hyper_t *hyper, int32_
   a.zoff = table->z_offset;
   a.loss_kind = loss_kind;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  switch (lpr) {
-    case 1: launch_online<1>(a, rule, np, st); break;
-    case 2: launch_online<2>(a, rule, np, st); break;
-    case 4: launch_online<4>(a, rule, np, st); break;
-    case 8: launch_online<8>(a, rule, np, st); break;
-    default: launch_online<16>(a, rule, np, st); break;
-  }
+  with_lpr(table->kp, [&](auto LPR) {
+    with_rule(rule, [&](auto LAYOUT, auto RULE) { launch_online_np<LPR, LAYOUT, RULE>(a, np, st); });
+  });
   return check_launch("k_fm_online");
 }
 
@@ -2908,13 +2792,11 @@ int fmx_online_run_mlp(const fmx_table_t *table, const fmx_hyper_t *hyper, int32
       a.fm_term = fm_term;
       a.rule = rule;
       a.loss_kind = loss_kind;
-      switch (lpr) {
-        case 1: launch_online_mlp<1>(a, table->layout, rule, st); break;
-        case 2: launch_online_mlp<2>(a, table->layout, rule, st); break;
-        case 4: launch_online_mlp<4>(a, table->layout, rule, st); break;
-        case 8: launch_online_mlp<8>(a, table->layout, rule, st); break;
-        default: launch_online_mlp<16>(a, table->layout, rule, st); break;
-      }
+      // FTRL-layout tables are read only (Hedge): FTRL pairs with that layout alone, any rule but SGD takes SIGNADAM
+      const int kernel_rule = table->layout == FMX_LAYOUT_FTRL ? FMX_RULE_FTRL : rule == FMX_RULE_SGD ? FMX_RULE_SGD : FMX_RULE_SIGNADAM;
+      with_lpr(table->kp, [&](auto LPR) {
+        with_rule(kernel_rule, [&](auto LAYOUT, auto RULE) { launch_online_mlp_k<LPR, LAYOUT, RULE>(a, st); });
+      });
       return check_launch("k_online_mlp");
     }
   }

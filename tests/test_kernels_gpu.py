@@ -384,32 +384,57 @@ def test_full_size_criteo(fmx, rule):
 def test_stream_matches_repeated_steps(fmx):
     """fmx_fm_stream over a pool == the same steps issued one by one; the measuring variant (which repeats every launch,
     so its table is not compared) returns kernel times."""
-    sizes, k, B, n_pool, n_steps = MIXED_SIZES, 16, 512, 3, 7
+    stream_vs_steps(fmx, "signadam", 512, 3, 7, on_side_stream=False)
+
+
+@pytest.mark.parametrize("on_side_stream", [False, True])
+@pytest.mark.parametrize("B", [256, 1024])
+@pytest.mark.parametrize("rule", ["signadam", "sgd", "ftrl"])
+def test_stream_sort_groups_rules_and_streams(fmx, rule, B, on_side_stream):
+    """As test_stream_matches_repeated_steps, through every part of the loop: B = 256 takes the single-stream loop, B = 1024
+    the sorts ahead on the side stream (OVERLAP_MIN_BATCH = 512); 21 steps over a pool of 5 batches are sort groups of
+    4 + 8 + 8 + 1 that wrap the pool and reuse both halves of the sorted ring.  Torch's default stream (handle 0, the legacy
+    default stream: the loop detours off it) and a stream of its own."""
+    stream_vs_steps(fmx, rule, B, 5, 21, on_side_stream)
+
+
+def stream_vs_steps(fmx, rule, B, n_pool, n_steps, on_side_stream):
+    sizes, k = MIXED_SIZES, 16
     prs = [make_problem(sizes, k, B, seed=40 + j) for j in range(n_pool)]
     hyp = fmx.Hyper(**HYP)
-    t1 = weights_table(fmx, sizes, k, prs[0])
-    e1 = fmx.FMEngine(t1, max_batch=B)
-    losses1 = []
-    for s in range(n_steps):
-        pr = prs[s % n_pool]
-        idx_d, _, y_d = e1.to_device(pr["idx"], None, pr["y"])
-        e1.step(hyp, "signadam", "logits", idx_d, None, y_d)
-        losses1.append(float(e1.loss_out.item()))
-    for timed in (False, True):
-        t2 = weights_table(fmx, sizes, k, prs[0])
-        e2 = fmx.FMEngine(t2, max_batch=B)
-        idx_pool = torch.from_numpy(np.stack([p["idx"] for p in prs])).cuda()
-        y_pool = torch.from_numpy(np.stack([p["y"] for p in prs])).cuda()
-        loss_out = torch.zeros(n_steps, device="cuda")
-        ms = e2.stream(hyp, "signadam", "logits", idx_pool, y_pool, n_steps, loss_out, timed=timed)
-        torch.cuda.synchronize()
-        e2.check_error_flag()
-        if timed:
-            assert len(ms) == 4 and all(v > 0 for v in ms)
-            assert np.isfinite(t2.rows.cpu().numpy()).all()
-            continue
-        np.testing.assert_array_equal(t1.rows.cpu().numpy(), t2.rows.cpu().numpy())
-        np.testing.assert_array_equal(np.asarray(losses1, dtype=np.float32), loss_out.cpu().numpy())
+
+    def table():
+        return ftrl_table(fmx, sizes, k, ftrl_state(prs[0], HYP)) if rule == "ftrl" else weights_table(fmx, sizes, k, prs[0])
+
+    side = torch.cuda.Stream() if on_side_stream else torch.cuda.default_stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        assert (torch.cuda.current_stream().cuda_stream == 0) != on_side_stream
+        t1 = table()
+        e1 = fmx.FMEngine(t1, max_batch=B)
+        losses1 = []
+        for s in range(n_steps):
+            pr = prs[s % n_pool]
+            idx_d, _, y_d = e1.to_device(pr["idx"], None, pr["y"])
+            e1.step(hyp, rule, "logits", idx_d, None, y_d)
+            losses1.append(float(e1.loss_out.item()))
+        for timed in (False, True):
+            t2 = table()
+            e2 = fmx.FMEngine(t2, max_batch=B)
+            idx_pool = torch.from_numpy(np.stack([p["idx"] for p in prs])).cuda()
+            y_pool = torch.from_numpy(np.stack([p["y"] for p in prs])).cuda()
+            loss_out = torch.zeros(n_steps, device="cuda")
+            ms = e2.stream(hyp, rule, "logits", idx_pool, y_pool, n_steps, loss_out, timed=timed)
+            torch.cuda.synchronize()
+            e2.check_error_flag()
+            if timed:
+                assert len(ms) == 4 and all(v > 0 for v in ms)
+                assert np.isfinite(t2.rows.cpu().numpy()).all()
+                continue
+            np.testing.assert_array_equal(t1.rows.cpu().numpy(), t2.rows.cpu().numpy())
+            np.testing.assert_array_equal(t1.bias.cpu().numpy(), t2.bias.cpu().numpy())
+            np.testing.assert_array_equal(np.asarray(losses1, dtype=np.float32), loss_out.cpu().numpy())
+    torch.cuda.synchronize()
 
 
 @pytest.mark.parametrize("rule,real_x", [("ftrl", False), ("sgd", True)])

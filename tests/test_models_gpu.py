@@ -417,39 +417,59 @@ def test_deep_trainer_step_vs_oracle(name, native):
 @pytest.mark.parametrize("fm_term", [True, False])
 def test_deepfm_stream_equals_trainer_steps(fm_term):
     """fmx_deepfm_stream (DeepFMTrainer.prepare_stream: the steps of a pool of batches issued from one foreign call, the sorts in
-    groups on the side stream) against DeepFMTrainer.step on the same batches, DeepFM and NFM (fm_term=False: base = first-order +
-    bias): tables, MLP parameters and per-step losses identical bits.  B = 256 takes the side-stream path, 13 steps over a pool of 5 batches cross a sort group and wrap the pool;
-    the step path itself is pinned against the oracle by test_deep_trainer_step_vs_oracle."""
+    groups on the side stream from B = 512 on) against DeepFMTrainer.step on the same batches, DeepFM and NFM (fm_term=False:
+    base = first-order + bias): tables, MLP parameters and per-step losses identical bits.  B = 256 takes the single-stream loop;
+    13 steps over a pool of 5 batches in two calls (4, then 9 starting in the middle of the pool) cross a sort group and wrap the
+    pool; the step path itself is pinned against the oracle by test_deep_trainer_step_vs_oracle."""
+    deepfm_stream_vs_steps(fm_term, 256, 13, on_side_stream=False)
+
+
+@pytest.mark.parametrize("on_side_stream", [False, True])
+@pytest.mark.parametrize("B", [256, 1024])
+@pytest.mark.parametrize("fm_term", [True, False])
+def test_deepfm_stream_sort_groups_and_streams(fm_term, B, on_side_stream):
+    """As test_deepfm_stream_equals_trainer_steps, through every part of the loop: B = 256 takes the single-stream loop, B = 1024
+    the side-stream one; 25 steps in two calls (4, then 21 starting in the middle of the pool: sort groups of 4 + 8 + 8 + 1 that
+    wrap the pool and reuse both halves of the sorted ring), on torch's default stream (handle 0, the legacy default stream: the
+    loop detours off it) and on a stream of its own."""
+    deepfm_stream_vs_steps(fm_term, B, 25, on_side_stream)
+
+
+def deepfm_stream_vs_steps(fm_term, B, n_steps, on_side_stream):
     import fmx
     import torch.nn as nn
-    sizes, k, H, L, B, n_pool, n_steps, lr = [50, 7, 300, 2, 1200, 33], 16, 256, 3, 256, 5, 13, 0.01
+    sizes, k, H, L, n_pool, lr = [50, 7, 300, 2, 1200, 33], 16, 256, 3, 5, 0.01
     rng = np.random.default_rng(3)
     idx = np.stack([np.stack([rng.integers(0, s, size=B) for s in sizes], axis=1) for _ in range(n_pool)]).astype(np.int32)
     y = (rng.uniform(size=(n_pool, B)) < 0.4).astype(np.float32)
     results = []
-    for mode in ("steps", "stream"):
-        torch.manual_seed(5)
-        table = fmx.FlatTable(sizes, k, layout="weights")
-        g = torch.Generator(device="cuda").manual_seed(9)
-        table.rows[:, :k + 1] = torch.randn((table.n_rows, k + 1), generator=g, device="cuda") * 0.1
-        eng = fmx.FMEngine(table, max_batch=B)
-        layers = [nn.Linear(k if j == 0 else H, H).cuda() for j in range(L)]
-        table.set_bias_weight(0.3)
-        tr = fmx.DeepFMTrainer(fmx.HipDeepBackend(eng, fmx.Hyper(lr=lr), "sgd"), layers, k, table.kp, mlp_lr=lr, fm_term=fm_term)
-        assert tr.native
-        idx_d, y_d = torch.from_numpy(idx).cuda(), torch.from_numpy(y).cuda()
-        losses = torch.zeros(n_steps, device="cuda")
-        if mode == "steps":
-            for s in range(n_steps):
-                losses[s] = tr.step(idx_d[s % n_pool], y_d[s % n_pool])
-        else:
-            run = tr.prepare_stream(idx_d, y_d, loss_out=losses)
-            run(4)                                    # two calls: the second starts in the middle of the pool
-            run2 = tr.prepare_stream(torch.roll(idx_d, -4, 0).contiguous(), torch.roll(y_d, -4, 0).contiguous(), loss_out=losses[4:])
-            run2(n_steps - 4)
-        torch.cuda.synchronize()
-        eng.check_error_flag()
-        results.append((table.rows.cpu().numpy().copy(), tr.flat.cpu().numpy().copy(), losses.cpu().numpy().copy()))
+    side = torch.cuda.Stream() if on_side_stream else torch.cuda.default_stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        for mode in ("steps", "stream"):
+            assert (torch.cuda.current_stream().cuda_stream == 0) != on_side_stream
+            torch.manual_seed(5)
+            table = fmx.FlatTable(sizes, k, layout="weights")
+            g = torch.Generator(device="cuda").manual_seed(9)
+            table.rows[:, :k + 1] = torch.randn((table.n_rows, k + 1), generator=g, device="cuda") * 0.1
+            eng = fmx.FMEngine(table, max_batch=B)
+            layers = [nn.Linear(k if j == 0 else H, H).cuda() for j in range(L)]
+            table.set_bias_weight(0.3)
+            tr = fmx.DeepFMTrainer(fmx.HipDeepBackend(eng, fmx.Hyper(lr=lr), "sgd"), layers, k, table.kp, mlp_lr=lr, fm_term=fm_term)
+            assert tr.native
+            idx_d, y_d = torch.from_numpy(idx).cuda(), torch.from_numpy(y).cuda()
+            losses = torch.zeros(n_steps, device="cuda")
+            if mode == "steps":
+                for s in range(n_steps):
+                    losses[s] = tr.step(idx_d[s % n_pool], y_d[s % n_pool])
+            else:
+                run = tr.prepare_stream(idx_d, y_d, loss_out=losses)
+                run(4)                                    # two calls: the second starts in the middle of the pool
+                run2 = tr.prepare_stream(torch.roll(idx_d, -4, 0).contiguous(), torch.roll(y_d, -4, 0).contiguous(), loss_out=losses[4:])
+                run2(n_steps - 4)
+            torch.cuda.synchronize()
+            eng.check_error_flag()
+            results.append((table.rows.cpu().numpy().copy(), tr.flat.cpu().numpy().copy(), losses.cpu().numpy().copy()))
     for a, b, what in zip(results[0], results[1], ("tables", "MLP parameters", "losses")):
         assert np.array_equal(a, b), what
     assert np.all(np.isfinite(results[0][2])) and results[0][2].std() > 0
