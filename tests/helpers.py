@@ -115,3 +115,95 @@ def oracle_float64():
     mod.__file__ = path
     exec(compile(src.replace("f32 = np.float32", "f32 = np.float64"), path, "exec"), mod.__dict__)
     return mod
+
+
+def mlp_f64(params, k, H, L, bi, base, y=None, loss="logits", inv_b=1.0, hedge_alpha=None):
+    """Float64 torch autograd statement of the relu MLP on bi (reference deepfm_adam.py:79-89,106-119; Hedge backprop
+    deepfm_onn.py:109-154).  params: the flat layout (W_l [H, in] then b_l [H] per layer).  Returns a dict:
+      out [B] = base + sum x_L ; layers [L, B] = sigmoid(base + sum x_l) ; and with y:
+      loss (mean: inv_b * sum), dz [B] = dL/dlogit, gbi [B, k] = dL/dbi, grads = [(dW_l, db_l)], flat (grads in the params
+      layout), gnoise = [(noise of dW_l, noise of db_l)]: the fp32 rounding noise to expect in every gradient element
+      (_mlp_grad_noise).
+    hedge_alpha [L]: Hedge instead -- losses [L] (BCELoss of each layer's sigmoid, mean over the batch) and the gradient of
+    sum_l alpha_l losses_l."""
+    import torch
+    import torch.nn.functional as Fn
+    p = torch.as_tensor(np.asarray(params, dtype=np.float64))
+    bi = torch.as_tensor(np.asarray(bi, dtype=np.float64)).requires_grad_(True)
+    base = torch.as_tensor(np.asarray(base, dtype=np.float64)).requires_grad_(True)
+    Ws, bs, off = [], [], 0
+    for l in range(L):
+        i = k if l == 0 else H
+        Ws.append(p[off:off + H * i].view(H, i).clone().requires_grad_(True)); off += H * i
+        bs.append(p[off:off + H].clone().requires_grad_(True)); off += H
+    xs, x = [bi], bi
+    for W, b in zip(Ws, bs):
+        x = Fn.relu(x @ W.t() + b)
+        xs.append(x)
+    r = dict(out=(base + x.sum(1)).detach().numpy(),
+             layers=torch.stack([torch.sigmoid(base + a.sum(1)) for a in xs[1:]]).detach().numpy())
+    if y is None:
+        return r
+    yt = torch.as_tensor(np.asarray(y, dtype=np.float64))
+    if hedge_alpha is None:
+        out = base + x.sum(1)
+        z = torch.sigmoid(out) if loss == "sigmoid" else out
+        ls = Fn.binary_cross_entropy_with_logits(z, yt, reduction="sum") * inv_b
+        r["loss"] = float(ls.detach())
+        dlog = [None] * (L - 1) + [torch.autograd.grad(ls, out, retain_graph=True)[0].detach()]
+        ls.backward()
+        r["dz"] = base.grad.numpy()
+        r["gbi"] = bi.grad.numpy()
+    else:
+        outs = [base + a.sum(1) for a in xs[1:]]
+        losses = torch.stack([Fn.binary_cross_entropy(torch.sigmoid(o), yt) for o in outs])
+        tot = (torch.as_tensor(np.asarray(hedge_alpha, dtype=np.float64)) * losses).sum()
+        dlog = [g.detach() for g in torch.autograd.grad(tot, outs, retain_graph=True)]
+        tot.backward()
+        r["losses"] = losses.detach().numpy()
+    r["grads"] = [(W.grad.numpy(), b.grad.numpy()) for W, b in zip(Ws, bs)]
+    r["flat"] = np.concatenate([t.reshape(-1) for pair in r["grads"] for t in pair])
+    # |d dL/dlogit_l / d logit_l|: p (1 - p) times alpha_l (Hedge), 1 (logits) or at most 5/4 (the double sigmoid)
+    slope = [None if g is None else
+             torch.sigmoid(o) * (1 - torch.sigmoid(o)) * (abs(float(hedge_alpha[l])) if hedge_alpha is not None else
+                                                          1.25 if loss == "sigmoid" else 1.0)
+             for l, (g, o) in enumerate(zip(dlog, [base + a.sum(1) for a in xs[1:]]))]
+    r["gnoise"] = _mlp_grad_noise([t.detach().numpy() for t in xs], [W.detach().numpy() for W in Ws],
+                                  [b.detach().numpy() for b in bs], [None if g is None else g.numpy() for g in dlog],
+                                  [None if c is None else c.detach().numpy() * inv_b for c in slope])
+    return r
+
+
+def _mlp_grad_noise(xs, Ws, bs, dlog, slope):
+    """The fp32 rounding noise to expect in each gradient element of the MLP (one standard deviation's worth, per element):
+    every sum of n terms adds EPS32 sqrt(n) times the sum of ITS OWN |terms| (a layer's own products, not a chain of |W|),
+    and the noise already in its inputs is carried through the same signed products in quadrature (independent roundings:
+    sqrt(e^2 . W^2)), forward through the activations and the logit, then backward through dL/dlogit (slope[l]: its
+    derivative by logit l, inv_b included) and the dgrad chain.  -> [(noise of dW_l [H, in], noise of db_l [H])]."""
+    u = 2.0 ** -24
+    L = len(Ws)
+    ex = [np.zeros_like(xs[0])]                        # noise of x_l (the input itself is exact)
+    for l in range(L):
+        W, b, x, e = Ws[l], bs[l], xs[l], ex[l]
+        local = u * np.sqrt(W.shape[1] + 1) * (np.abs(x) @ np.abs(W).T + np.abs(b))
+        ex.append((local + np.sqrt((e * e) @ (W * W).T)) * (xs[l + 1] > 0))
+    def dlog_noise(l):                                 # dL/dlogit_l's own rounding + the logit's noise times its slope
+        xo, eo = xs[l + 1], ex[l + 1]
+        e_out = u * np.sqrt(xo.shape[1]) * np.abs(xo).sum(1) + np.sqrt((eo * eo).sum(1))
+        return 4 * u * np.abs(dlog[l]) + slope[l] * e_out
+    d = np.zeros_like(xs[-1])
+    e = np.zeros_like(xs[-1])
+    out = [None] * L
+    for l in range(L - 1, -1, -1):
+        if dlog[l] is not None:
+            d = d + dlog[l][:, None]
+            e = e + dlog_noise(l)[:, None]
+        mask = xs[l + 1] > 0
+        d, e = d * mask, e * mask
+        x, exl, W = xs[l], ex[l], Ws[l]
+        B = x.shape[0]
+        nW = u * np.sqrt(B) * (np.abs(d).T @ np.abs(x)) + np.sqrt((e * e).T @ (x * x) + (d * d).T @ (exl * exl))
+        nb = u * np.sqrt(B) * np.abs(d).sum(0) + np.sqrt((e * e).sum(0))
+        out[l] = (nW, nb)
+        d, e = d @ W, u * np.sqrt(W.shape[0]) * (np.abs(d) @ np.abs(W)) + np.sqrt((e * e) @ (W * W))
+    return out

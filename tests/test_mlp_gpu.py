@@ -1,11 +1,12 @@
 """fmx_mlp_section (the relu MLP at mini-batch sizes: fp32 MFMA GEMMs for forward, loss, backward) against a float64
 PyTorch autograd reference of the same network (reference deepfm_adam.py:79-89,106-119: nn.Linear + relu + autograd).
 Tolerance: fp32 sums over up to 4096 samples in a different order than the reference -> 2e-5 relative to the largest
-magnitude of each output."""
+magnitude of each output, and of each layer's W and b gradient on its own (plus the fp32 noise floor of a cancelled sum)."""
 import numpy as np
 import pytest
 import torch
-import torch.nn.functional as F
+
+from helpers import mlp_f64
 
 pytestmark = pytest.mark.gpu
 
@@ -31,38 +32,81 @@ CASES = [  # B, k, kp, hidden, layers, loss
     (100, 16, 16, 256, 8, "logits"),
     (2048, 16, 16, 128, 3, "logits"),       # GEMM launches for the chain's part, streaming weight gradients (128-wide layers)
     (700, 24, 24, 72, 3, "logits"),         # narrow first layer of 24 columns (two natural tiles), 72-wide layers (two blocks, ragged)
+    (1, 16, 16, 256, 3, "logits"),          # one sample
+    (17, 16, 16, 256, 3, "logits"),         # one row past a 16-row slab
+    (129, 52, 52, 64, 2, "logits"),         # 48 < in < 64: layer 0 off the streamed weight gradients
+    (300, 64, 66, 256, 2, "logits"),        # layer 0 at in >= 64 with ld_bi % 4 != 0: the GEMM weight gradients
+    (64, 4, 4, 1, 2, "logits"),             # hidden = 1
+    (500, 24, 32, 72, 8, "logits"),         # eight layers away from hidden = 256
+    (4096, 16, 16, 256, 3, "sigmoid"),      # configs[3] under the double-sigmoid loss
 ]
 
 
 def reference(params, k, H, L, loss, bi, base, y, inv_b):
-    p = params.double().cpu()
-    bi = bi.double().cpu().requires_grad_(True)
-    base = base.double().cpu().requires_grad_(True)
-    Ws, bs, off = [], [], 0
+    r = mlp_f64(params.cpu().numpy(), k, H, L, bi.cpu().numpy(), base.cpu().numpy(), y.cpu().numpy(), loss, inv_b)
+    return r["loss"], r["dz"], r["gbi"], r["flat"], r["out"], r
+
+
+def live_units(params, k, H, L, bi):
+    """params with the incoming weights and bias of every unit that is dead (relu off) for every sample negated, layer by
+    layer on the float64 forward: such a unit contributes nothing and receives an exactly-0 gradient, so a kernel that
+    skipped or mis-indexed it would still pass.  Negation is exact in fp32; units live for some sample are left alone."""
+    p = np.asarray(params, dtype=np.float32).copy()
+    x, off = np.asarray(bi, np.float64), 0
     for l in range(L):
         i = k if l == 0 else H
-        Ws.append(p[off:off + H * i].view(H, i).clone().requires_grad_(True)); off += H * i
-        bs.append(p[off:off + H].clone().requires_grad_(True)); off += H
-    x = bi
-    for W, b in zip(Ws, bs):
-        x = F.relu(x @ W.t() + b)
-    out = base + x.sum(1)
-    z = torch.sigmoid(out) if loss == "sigmoid" else out
-    ls = F.binary_cross_entropy_with_logits(z, y.double().cpu(), reduction="sum") * inv_b
-    ls.backward()
-    flat = torch.cat([t.grad.reshape(-1) for pair in zip(Ws, bs) for t in pair])
-    return float(ls.detach()), base.grad.numpy(), bi.grad.numpy(), flat.numpy(), out.detach().numpy()
+        W, b = p[off:off + H * i].reshape(H, i), p[off + H * i:off + H * i + H]
+        dead = ((x @ W.astype(np.float64).T + b) <= 0).all(0)
+        W[dead] *= -1
+        b[dead] *= -1
+        x = np.maximum(x @ W.astype(np.float64).T + b, 0.0)
+        off += H * i + H
+    return p
 
 
-def close(a, b, what, rel=2e-5):
+def assert_live(r, L, what):
+    """Every layer's float64 gradient has non-zero W and b entries: the case exercises every layer."""
+    for l in range(L):
+        assert np.any(r["grads"][l][0]) and np.any(r["grads"][l][1]), f"{what}: layer {l} has no live unit (a dead network)"
+
+
+def close(a, b, what, rel=2e-5, floor=0.0):
     a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
     scale = max(np.abs(b).max(), 1e-30)
-    err = np.abs(a - b).max()
-    assert err <= rel * scale, f"{what}: max err {err:.3e} vs scale {scale:.3e}"
+    err = np.abs(a - b)
+    assert (err <= rel * scale + floor).all(), f"{what}: max err {err.max():.3e} vs scale {scale:.3e}"
+
+
+def close_per_tensor(grads, r, k, H, L, B, what):
+    """Each layer's W and b gradient against its own maximum (an error confined to one layer's bias, one split or one 16-row
+    slab of a small layer stays visible), plus four times the fp32 rounding noise expected in the element (helpers.mlp_f64's
+    gnoise: each sum's own |terms|, the inputs' noise carried through the signed products)."""
+    off = 0
+    for l in range(L):
+        i = k if l == 0 else H
+        for name, n, g_ref, g_noise in (("W", H * i, r["grads"][l][0], r["gnoise"][l][0]), ("b", H, r["grads"][l][1], r["gnoise"][l][1])):
+            close(grads[off:off + n], g_ref.reshape(-1), f"{what}: {name}{l}", floor=4 * g_noise.reshape(-1))
+            off += n
+    assert off == grads.size
 
 
 @pytest.mark.parametrize("B,k,kp,H,L,loss", CASES)
 def test_mlp_section_vs_autograd(fmx, B, k, kp, H, L, loss):
+    section_vs_autograd(fmx, B, k, kp, H, L, loss)
+
+
+@pytest.mark.parametrize("B,k,kp,H,L,loss", [(4096, 16, 16, 256, 3, "logits"), (1000, 32, 32, 256, 2, "sigmoid")])
+def test_mlp_section_without_chain_vs_autograd(fmx, B, k, kp, H, L, loss):
+    """mlp_chain = 0: the separate GEMM launches instead of k_mlp_chain at hidden = 256 (configs[3], and a ragged last slab)."""
+    lib = fmx._lib.load()
+    prev = lib.fmx_set_option(b"mlp_chain", 0)
+    try:
+        section_vs_autograd(fmx, B, k, kp, H, L, loss)
+    finally:
+        lib.fmx_set_option(b"mlp_chain", prev)
+
+
+def section_vs_autograd(fmx, B, k, kp, H, L, loss):
     torch.manual_seed(B + H + L)
     n_par = sum(H * (k if l == 0 else H) + H for l in range(L))
     # the double-sigmoid loss multiplies by p (1 - p), p = sigmoid(z): with 256 relu outputs summed into z, N(0, 1 / H) weights put
@@ -72,6 +116,7 @@ def test_mlp_section_vs_autograd(fmx, B, k, kp, H, L, loss):
     params = (torch.randn(n_par) * (wscale / np.sqrt(H))).cuda()
     bi_full = torch.zeros(B, kp)
     bi_full[:, :k] = torch.randn(B, k) * 0.5
+    params = torch.from_numpy(live_units(params.cpu().numpy(), k, H, L, bi_full[:, :k].numpy())).cuda()
     bi_d = bi_full.cuda()
     base = (torch.randn(B) * 0.3).cuda()
     y = (torch.rand(B) < 0.3).float().cuda()
@@ -90,13 +135,15 @@ def test_mlp_section_vs_autograd(fmx, B, k, kp, H, L, loss):
                                        inv_b, ws.data_ptr(), logit.data_ptr(), dz.data_ptr(), gbi.data_ptr(), kp,
                                        grads.data_ptr(), 0.0, loss_out.data_ptr(), torch.cuda.current_stream().cuda_stream))
     torch.cuda.synchronize()
-    r_loss, r_dz, r_gbi, r_flat, r_out = reference(params, k, H, L, loss, bi_d[:, :k], base, y, inv_b)
+    r_loss, r_dz, r_gbi, r_flat, r_out, r = reference(params, k, H, L, loss, bi_d[:, :k], base, y, inv_b)
+    assert_live(r, L, "section")
     close(logit.cpu().numpy(), r_out, "logit")
     close(loss_out.item(), r_loss, "loss")
     close(dz.cpu().numpy(), r_dz, "dz")
     close(gbi.cpu().numpy()[:, :k], r_gbi, "gbi")
     assert (gbi.cpu().numpy()[:, k:] == 0).all(), "padding columns of gbi must be zeroed"
     close(grads.cpu().numpy(), r_flat, "flat gradients")
+    close_per_tensor(grads.cpu().numpy(), r, k, H, L, B, "gradients")
     assert torch.equal(params, p0), "lr_apply = 0 must leave the parameters alone"
     # determinism + the fused SGD application
     grads2 = torch.zeros_like(params)
@@ -121,7 +168,8 @@ def test_mlp_section_rejects_bad_arguments(fmx):
     assert rc == fmx._lib.ERR_SHAPE                                # ld_bi < k
 
 
-@pytest.mark.parametrize("B,k,kp,H,L", [(4096, 16, 16, 256, 3), (300, 10, 12, 40, 2), (50, 4, 4, 33, 4)])
+@pytest.mark.parametrize("B,k,kp,H,L", [(4096, 16, 16, 256, 3), (300, 10, 12, 40, 2), (50, 4, 4, 33, 4), (200, 16, 16, 64, 1),
+                                        (300, 10, 12, 40, 8), (17, 16, 16, 256, 3)])
 def test_mlp_hedge_section_vs_autograd(fmx, B, k, kp, H, L):
     """fmx_mlp_hedge_section against a float64 autograd statement of Hedge backprop (reference deepfm_onn.py:109-154)."""
     import ctypes as C
@@ -132,27 +180,18 @@ def test_mlp_hedge_section_vs_autograd(fmx, B, k, kp, H, L):
     params = (torch.randn(n_par) * min(1.0 / np.sqrt(H), 2.0 / H)).cuda()
     bi = torch.zeros(B, kp)
     bi[:, :k] = torch.randn(B, k) * 0.5
+    params = torch.from_numpy(live_units(params.cpu().numpy(), k, H, L, bi[:, :k].numpy())).cuda()
     bi_d, base = bi.cuda(), (torch.randn(B) * 0.3).cuda()
     y = (torch.rand(B) < 0.3).float().cuda()
     alpha = torch.full((L,), 1.0 / (L + 1)).cuda()
     lr, hb, hs = 0.05, 0.99, 0.2
-    # float64 reference
-    p = params.double().cpu()
-    Ws, bs, off = [], [], 0
-    for l in range(L):
-        i = k if l == 0 else H
-        Ws.append(p[off:off + H * i].view(H, i).clone().requires_grad_(True)); off += H * i
-        bs.append(p[off:off + H].clone().requires_grad_(True)); off += H
-    x, losses = bi_d[:, :k].double().cpu(), []
-    for W, b in zip(Ws, bs):
-        x = F.relu(x @ W.t() + b)
-        losses.append(F.binary_cross_entropy(torch.sigmoid(base.double().cpu() + x.sum(1)), y.double().cpu()))
-    a0 = alpha.double().cpu()
-    (a0 * torch.stack(losses)).sum().backward()
-    new = torch.cat([(t - lr * t.grad).reshape(-1) for pair in zip(Ws, bs) for t in pair]).detach().numpy()
-    a1 = torch.maximum(a0 * torch.pow(torch.tensor(hb, dtype=torch.float64), torch.stack(losses).detach()),
-                       torch.tensor(hs / L, dtype=torch.float64))
-    a1 = (a1 / a1.sum()).numpy()
+    a0 = alpha.cpu().numpy().astype(np.float64)
+    r = mlp_f64(params.cpu().numpy(), k, H, L, bi[:, :k].numpy(), base.cpu().numpy(), y.cpu().numpy(), hedge_alpha=a0)
+    assert_live(r, L, "hedge section")
+    p = params.cpu().numpy().astype(np.float64)
+    new = p - lr * r["flat"]
+    a1 = np.maximum(a0 * hb ** r["losses"], hs / L)
+    a1 = a1 / a1.sum()
     lib = fmx._lib.load()
     m = fmx._lib.Mlp(params.data_ptr(), L, k, H, 0)
     ws = torch.empty(int(lib.fmx_mlp_section_workspace_bytes(C.byref(m), B)) // 4, device="cuda")
@@ -161,8 +200,39 @@ def test_mlp_hedge_section_vs_autograd(fmx, B, k, kp, H, L):
                                              y.data_ptr(), B, ws.data_ptr(), grads.data_ptr(), lout.data_ptr(),
                                              torch.cuda.current_stream().cuda_stream))
     torch.cuda.synchronize()
-    close(lout.cpu().numpy(), torch.stack(losses).detach().numpy(), "per-layer losses")
+    close(lout.cpu().numpy(), r["losses"], "per-layer losses")
     close(alpha.cpu().numpy(), a1, "alpha")
-    close((params - p0).cpu().numpy(), new - p.numpy(), "parameter deltas", rel=5e-5)
+    close((params - p0).cpu().numpy(), new - p, "parameter deltas", rel=5e-5)
+    close_per_tensor(grads.cpu().numpy(), r, k, H, L, B, "hedge gradients")
     np.testing.assert_array_equal((p0 - lr * grads).cpu().numpy(), params.cpu().numpy())
 
+
+
+@pytest.mark.parametrize("B,k,ld_bi,H,L", [(4096, 16, 16, 256, 3), (300, 10, 12, 40, 2), (1, 4, 4, 1, 1), (700, 24, 36, 72, 3),
+                                           (17, 16, 20, 256, 2)])
+def test_mlp_forward_batch_vs_f64(fmx, B, k, ld_bi, H, L):
+    """fmx_mlp_forward_batch (forward() / predict() of the MLP classes beyond 16 samples) against float64: the logit and every
+    layer's sigmoid, bi rows strided (ld_bi > k) in two cases."""
+    import ctypes as C
+    torch.manual_seed(B + k + H)
+    n_par = sum(H * (k if l == 0 else H) + H for l in range(L))
+    params = (torch.randn(n_par) * min(1.0 / np.sqrt(H), 2.0 / H)).cuda()
+    bi = torch.zeros(B, ld_bi)
+    bi[:, :k] = torch.randn(B, k) * 0.5
+    bi[:, k:] = 1e3                                   # columns past k must not be read
+    params = torch.from_numpy(live_units(params.cpu().numpy(), k, H, L, bi[:, :k].numpy())).cuda()
+    bi_d, base = bi.cuda(), (torch.randn(B) * 0.3).cuda()
+    lib = fmx._lib.load()
+    m = fmx._lib.Mlp(params.data_ptr(), L, k, H, 0)
+    ws = torch.empty(int(lib.fmx_mlp_section_workspace_bytes(C.byref(m), B)) // 4, device="cuda")
+    logit, layers = torch.full((B,), 7.0, device="cuda"), torch.full((L, B), 7.0, device="cuda")
+    p0 = params.clone()
+    fmx._lib.check(lib.fmx_mlp_forward_batch(C.byref(m), bi_d.data_ptr(), ld_bi, base.data_ptr(), B, ws.data_ptr(), logit.data_ptr(),
+                                             layers.data_ptr(), torch.cuda.current_stream().cuda_stream))
+    torch.cuda.synchronize()
+    r = mlp_f64(params.cpu().numpy(), k, H, L, bi[:, :k].numpy(), base.cpu().numpy())
+    assert np.any(r["out"] != base.cpu().numpy()), "the network must contribute to the logit"
+    close(logit.cpu().numpy(), r["out"], "logit")
+    for l in range(L):
+        close(layers.cpu().numpy()[l], r["layers"][l], f"layers_out[{l}]")
+    assert torch.equal(params, p0)

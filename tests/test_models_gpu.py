@@ -402,16 +402,22 @@ def test_deep_trainer_step_vs_oracle(name, native):
     om = orc.OracleModel(name, sd0, update_rule="sgd")
     om.fit(Xi, z["A/Xv1"], Y)
     ref = om.state_dict()
-    first, second = table.export_reference()
-    got = {"bias": table.bias_weight().cpu().numpy()}
-    for i in range(F_):
-        got[f"first_order_embeddings.{i}.weight"] = first[i].numpy()
-        got[f"second_order_embeddings.{i}.weight"] = second[i].numpy()
-    for j, layer in enumerate(layers):
-        got[f"hidden_layers.{j}.weight"] = layer.weight.detach().cpu().numpy()
-        got[f"hidden_layers.{j}.bias"] = layer.bias.detach().cpu().numpy()
+    got = trainer_state(table, layers)
     ref = {kk: v for kk, v in ref.items() if kk in got}
     assert_state_close(got, ref, {kk: sd0[kk] for kk in ref}, what=f"{name} sgd step")
+
+
+def trainer_state(table, layers):
+    """A DeepFMTrainer's tables and hidden layers under the reference's state_dict keys (numpy copies)."""
+    first, second = table.export_reference()
+    sd = {"bias": table.bias_weight().cpu().numpy()}
+    for i in range(len(first)):
+        sd[f"first_order_embeddings.{i}.weight"] = first[i].numpy().copy()
+        sd[f"second_order_embeddings.{i}.weight"] = second[i].numpy().copy()
+    for j, layer in enumerate(layers):
+        sd[f"hidden_layers.{j}.weight"] = layer.weight.detach().cpu().numpy().copy()
+        sd[f"hidden_layers.{j}.bias"] = layer.bias.detach().cpu().numpy().copy()
+    return sd
 
 
 @pytest.mark.parametrize("fm_term", [True, False])
@@ -435,10 +441,69 @@ def test_deepfm_stream_sort_groups_and_streams(fm_term, B, on_side_stream):
     deepfm_stream_vs_steps(fm_term, B, 25, on_side_stream)
 
 
-def deepfm_stream_vs_steps(fm_term, B, n_steps, on_side_stream):
+@pytest.mark.parametrize("k,H,L,rule,loss,layout,B", [
+    (10, 40, 2, "signadam", "sigmoid", "weights", 256),    # k != kp, the rider's scalar path (in % 4 != 0), the GEMM section
+    (16, 72, 1, "ftrl", "logits", "ftrl", 256),            # FTRL tables, one layer
+    (16, 33, 8, "sgd", "logits", "weights", 256),          # hidden % 4 != 0, eight layers: the rider's per-layer split at its widest
+    (10, 40, 2, "sgd", "logits", "weights", 1024),         # the side-stream loop away from 3 x 256
+])
+def test_deepfm_stream_shapes_equal_trainer_steps(k, H, L, rule, loss, layout, B):
+    """fmx_deepfm_stream (DeepFM) away from configs[3]'s 16 -> 3 x 256 under SGD: other widths, depths, rules, losses and the FTRL
+    layout, identical bits to DeepFMTrainer.step."""
+    deepfm_stream_vs_steps(True, B, 9, on_side_stream=False, k=k, H=H, L=L, rule=rule, loss=loss, layout=layout)
+
+
+def test_deep_trainer_step_away_from_configs3_vs_f64_oracle():
+    """One DeepFMTrainer step (SGD, the native section) at k = 10 (kp = 16), hidden 40, two layers, against the oracle's class
+    step evaluated in float64 (helpers.oracle_float64): tables, bias and hidden layers within assert_state_close."""
     import fmx
     import torch.nn as nn
-    sizes, k, H, L, n_pool, lr = [50, 7, 300, 2, 1200, 33], 16, 256, 3, 5, 0.01
+    sizes, k, H, L, lr, B = [50, 7, 300, 2, 1200, 33], 10, 40, 2, 0.01, 256
+    torch.manual_seed(5)
+    table = make_stream_table(sizes, k, "weights")
+    eng = fmx.FMEngine(table, max_batch=B)
+    layers = [nn.Linear(k if j == 0 else H, H).cuda() for j in range(L)]
+    sd0 = dict(trainer_state(table, layers), n=np.float32(lr))
+    tr = fmx.DeepFMTrainer(fmx.HipDeepBackend(eng, fmx.Hyper(lr=lr), "sgd"), layers, k, table.kp, mlp_lr=lr, fm_term=True,
+                           loss=orc.LOSS_KIND[("DeepFMAdam", "fit")])
+    assert tr.native
+    rng = np.random.default_rng(4)
+    Xi = np.stack([rng.integers(0, s_, size=B) for s_ in sizes], axis=1).astype(np.int32)
+    Y = (rng.uniform(size=B) < 0.4).astype(np.float32)
+    idx_d, _, y_d = eng.to_device(Xi, None, Y)
+    tr.step(idx_d, y_d)
+    torch.cuda.synchronize()
+    om = oracle_float64().OracleModel("DeepFMAdam", sd0, update_rule="sgd")
+    om.fit(Xi, np.ones(Xi.shape, np.float32), Y)
+    ref = om.state_dict()
+    got = trainer_state(table, layers)
+    ref = {kk: np.asarray(v).reshape(np.shape(got[kk])) for kk, v in ref.items() if kk in got}
+    assert_state_close(got, ref, {kk: np.asarray(sd0[kk]).reshape(np.shape(got[kk])) for kk in ref}, what="trainer step vs float64")
+
+
+def make_stream_table(sizes, k, layout, seed=9):
+    import fmx
+    if layout == "weights":
+        table = fmx.FlatTable(sizes, k, layout="weights")
+        g = torch.Generator(device="cuda").manual_seed(seed)
+        r = torch.randn((table.n_rows, k + 1), generator=g, device="cuda") * 0.1
+        table.rows[:, :k] = r[:, :k]                  # V; the padding columns k .. kp-1 stay 0
+        table.rows[:, table.kp] = r[:, k]             # the first-order weight
+    else:
+        h = dict(alpha=0.05, beta=1.0, l1=0.001, l2=0.01)
+        table = fmx.FlatTable(sizes, k, layout="ftrl", ftrl=h)
+        rng = np.random.default_rng(seed)
+        R = table.n_rows
+        table.load_ftrl_state(orc.ftrl_z_for_weight(rng.normal(size=(R, k)).astype(np.float32) * 0.1, **h), np.full((R, k), 0.1, np.float32),
+                              orc.ftrl_z_for_weight(rng.normal(size=R).astype(np.float32) * 0.1, **h), np.full(R, 0.1, np.float32))
+    table.set_bias_weight(0.3)
+    return table
+
+
+def deepfm_stream_vs_steps(fm_term, B, n_steps, on_side_stream, k=16, H=256, L=3, rule="sgd", loss="logits", layout="weights"):
+    import fmx
+    import torch.nn as nn
+    sizes, n_pool, lr = [50, 7, 300, 2, 1200, 33], 5, 0.01
     rng = np.random.default_rng(3)
     idx = np.stack([np.stack([rng.integers(0, s, size=B) for s in sizes], axis=1) for _ in range(n_pool)]).astype(np.int32)
     y = (rng.uniform(size=(n_pool, B)) < 0.4).astype(np.float32)
@@ -449,13 +514,11 @@ def deepfm_stream_vs_steps(fm_term, B, n_steps, on_side_stream):
         for mode in ("steps", "stream"):
             assert (torch.cuda.current_stream().cuda_stream == 0) != on_side_stream
             torch.manual_seed(5)
-            table = fmx.FlatTable(sizes, k, layout="weights")
-            g = torch.Generator(device="cuda").manual_seed(9)
-            table.rows[:, :k + 1] = torch.randn((table.n_rows, k + 1), generator=g, device="cuda") * 0.1
+            table = make_stream_table(sizes, k, layout)
             eng = fmx.FMEngine(table, max_batch=B)
             layers = [nn.Linear(k if j == 0 else H, H).cuda() for j in range(L)]
-            table.set_bias_weight(0.3)
-            tr = fmx.DeepFMTrainer(fmx.HipDeepBackend(eng, fmx.Hyper(lr=lr), "sgd"), layers, k, table.kp, mlp_lr=lr, fm_term=fm_term)
+            tr = fmx.DeepFMTrainer(fmx.HipDeepBackend(eng, fmx.Hyper(lr=lr, **table.ftrl), rule), layers, k, table.kp, mlp_lr=lr,
+                                   fm_term=fm_term, loss=loss)
             assert tr.native
             idx_d, y_d = torch.from_numpy(idx).cuda(), torch.from_numpy(y).cuda()
             losses = torch.zeros(n_steps, device="cuda")
