@@ -5,6 +5,7 @@ libfmx.so (hand-written gfx950 kernels, fm-for-online-recommendation_amd/csrc/) 
 There is no CPU path and no PyTorch fallback: without a ROCm GPU or without the built library the constructors raise.
 """
 from . import _lib  # noqa: F401
+from . import recommend  # noqa: F401
 from .table import FlatTable, padded_k  # noqa: F401
 from .engine import FMEngine, Hyper, normalize_inputs  # noqa: F401
 from .distributed import DataParallelFM, HipBackend  # noqa: F401

@@ -454,6 +454,30 @@ class OnlineFMBase(nn.Module):
         pred = torch.sigmoid(out).cpu()
         return pred.data.numpy() > 0.5
 
+    def recommend(self, Xi, Xv, item_fields, K, candidates=None, exclude=None):
+        """Top-K candidates for every context row (fmx/recommend.py, fmx_fm_topk).  Xi / Xv: [U, F] full-width rows whose
+        item columns are ignored (Xv may be None: all ones).  candidates=None: every row of the one item field, a position is
+        that field's local index; else (cand_Xi [N, F], cand_Xv or None) whose non-item columns are ignored.  exclude: per-user
+        position lists or a CSR pair (offsets, positions).  Returns numpy (positions int64 [U, K], -1 padded; logits fp32
+        [U, K], -inf padded), each row by logit descending, then position ascending."""
+        if self._has_mlp:
+            raise NotImplementedError(f"{self._name}.recommend: the MLP on the bi-interaction vector does not decompose over "
+                                      "the context / item field split")
+        item_fields = [int(f) for f in (item_fields if hasattr(item_fields, "__len__") else [item_fields])]
+        F = self.field_size
+        if candidates is None:
+            if len(item_fields) != 1:
+                raise ValueError("candidates=None needs exactly one item field (its rows are the candidates)")
+            f = item_fields[0]
+            cand_idx = torch.zeros((self.feature_sizes[f], F), dtype=torch.int32, device=self.device)
+            cand_idx[:, f] = torch.arange(self.feature_sizes[f], dtype=torch.int32, device=self.device)
+            cand_xv = None
+        else:
+            cand_idx, cand_xv = candidates
+        cands = fmx.recommend.Candidates(self._table, item_fields, cand_idx, cand_xv, hyper=self._hyper)
+        pos, logit = fmx.recommend.topk(self._table, Xi, Xv, cands, K, exclude=exclude, hyper=self._hyper)
+        return pos.cpu().numpy(), logit.cpu().numpy()
+
     def _device_loop_ok(self):
         """Can run_experiment's predict-then-fit loop run on the device for this model?"""
         if not getattr(self, "device_online_loop", True):

@@ -55,8 +55,8 @@
 extern "C" {
 #endif
 
-#define FMX_VERSION 104 /* 0.1.4: fmx_deepfm_stream (0.1.3: fields as row-range pieces of index columns -- field_cols / field_base /
-                           n_cols --, workspace_bytes arguments, fmx_owner_*) */
+#define FMX_VERSION 104 /* 0.1.4: fmx_deepfm_stream, fmx_fm_topk / fmx_fm_topk_workspace_bytes (0.1.3: fields as row-range pieces
+                           of index columns -- field_cols / field_base / n_cols --, workspace_bytes arguments, fmx_owner_*) */
 
 typedef void *fmx_stream_t; /* hipStream_t */
 
@@ -428,6 +428,30 @@ int fmx_sftrl_run(const double *X, const double *y, int32_t N, int32_t D, int32_
 int fmx_sftrl_grid(const double *X, const double *y, int32_t N, int32_t D, int32_t d, int32_t n_settings, const int32_t *ms,
                    const double *etas, int32_t m_max, double thres, int32_t task, double *BP, double *BN, int32_t *counts, double *w,
                    double *g_w, double *pred_out, int32_t *status, fmx_stream_t stream);
+
+/* ---- top-K recommendation over an FM table's candidates (fmx/recommend.py) ----
+ * Replaces: the caller-side loop of forward() over assembled (context, candidate) samples followed by torch.topk; the reference
+ * has no counterpart (no recommendation call).  Split a sample's fields into context fields and item fields; then
+ *     logit(u + c) = a_u + a_c + <S_u, S_c>
+ * with a_u the logit of u's context fields alone (bias included), a_c = sfirst + sbi of c's item fields alone, S_u / S_c their
+ * sums of V x -- both come out of fmx_fm_forward with the other side's fields given xv = 0 (fmx/recommend.py).
+ *   Su [U, ld_u], au [U]: context sums;  Sc [N, ld_c], ac [N]: candidate sums (ld_u, ld_c multiples of 4, >= kp; Su, Sc
+ *   16-byte aligned);  kp 4 / 8 / 16 / 32 / 64;  1 <= K <= 256 (larger: FMX_ERR_UNSUPPORTED).
+ *   excl_offsets [U + 1] / excl_pos: per user, the candidate positions never to return, CSR with each user's list ascending
+ *   (binary-searched); both null: no exclusions.
+ *   top_pos [U, K] int32, top_score [U, K] fp32: each row sorted by score descending, then position ascending (a total order:
+ *   the result does not depend on scheduling); rows with fewer than K eligible candidates are padded with -1 / -inf.
+ *   A NaN score and an excluded position are never returned; a score of -0 is returned as +0.
+ * The score is one fixed function of (u, c), whatever U, N, the tile or the split of the pair:
+ *     score(u, c) = (au[u] + ac[c]) + dot,  dot = fma(Su[kp-1], Sc[kp-1], ... fma(Su[1], Sc[1], Su[0] * Sc[0]) ...)
+ * (fp32, one rounding per operation, d ascending).  One launch when a user tile's candidates are scanned by one workgroup,
+ * else two (scan into per-split partial lists in the workspace, then a merge).  The workspace (16-byte aligned, no
+ * initialisation needed) must hold fmx_fm_topk_workspace_bytes(U, N, K) bytes, else FMX_ERR_SHAPE; every argument is
+ * checked before anything is launched. */
+int64_t fmx_fm_topk_workspace_bytes(int32_t U, int32_t N, int32_t K);
+int fmx_fm_topk(const float *Su, int32_t ld_u, const float *au, int32_t U, const float *Sc, int32_t ld_c, const float *ac, int32_t N,
+                int32_t kp, const int32_t *excl_offsets, const int32_t *excl_pos, int32_t K, void *workspace, int64_t workspace_bytes,
+                int32_t *top_pos, float *top_score, fmx_stream_t stream);
 
 /* Streaming read of `bytes` (multiple of 16) with 16-byte loads; sink [1] receives a checksum so the loads stay
  * live.  Used by bench.py to measure the HBM-read ceiling on the same GPU in the same run. */
