@@ -8,6 +8,9 @@
 // 0 while fewer than K are held) is appended; a slot that could overflow in the next chunk is sorted (bitonic, descending) and
 // cut to its K best, which raises the threshold.  The set kept is the exact top K of what the slot has seen, whatever the
 // order of the appends, so the result is independent of scheduling.
+//
+// fmx_mlp_topk (the DeepFM / NFM classes, at the end of this file) feeds the same slots from a scan that runs the whole
+// network on every pair.
 #include "fmx_common.h"
 
 namespace {
@@ -340,6 +343,375 @@ int fmx_fm_topk(const float *Su, int32_t ld_u, const float *au, int32_t U, const
     case 32: return launch_topk<32>(a, g, st);
     default: return launch_topk<64>(a, g, st);
   }
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------------------------------------------
+// fmx_mlp_topk: the same selection over the scores of the DeepFM / NFM network on the pair's bi-interaction vector
+// ---------------------------------------------------------------------------------------------------------------------
+// bi(u + c) = bi_u + bi_c + S_u (.) S_c, so a pair's network input is built in LDS from the two sides' rows, and the U x N
+// forwards of the network run as GEMMs on chunks of 64 pairs (one user, 64 consecutive candidates): [64 x in] . W_l^T on
+// v_mfma_f32_16x16x4_f32 (exact f32 products, accumulated in k order: the same bits as the fmaf chain the header states).
+// Workgroup = one user x one candidate split, four waves: wave (wr, wc) of a WR x WC grid owns the row tiles wr * RPW ..
+// + RPW - 1 (RPW = 4 / WR) and the column tiles wc, wc + WC, ... of every layer.  The weights go from L2 straight into the
+// multiplying wave's registers (a pre-packed copy in the workspace, one 16-byte load per lane and four k-steps), the
+// activations stay in LDS in the MFMA's operand order (one ds_read_b128 per lane and four k-steps).  Each pair's scores
+// then go through the slot / compact / merge of fmx_fm_topk.
+namespace {
+
+constexpr int TM_ROWS = 64;                 // pairs per chunk: four MFMA row tiles
+constexpr int TM_MAX_H = 256, TM_MAX_L = 8;
+constexpr int TM_TILE_BUDGET = 2048;        // workgroups the scan aims for: 256 CUs, two resident each, four times over
+constexpr int TM_MAX_SPLITS = 1024;
+constexpr int TM_SPLIT_WORK = 1 << 22;      // FLOPs a split holds at least (the network's cost sets the fewest candidates)
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+
+struct MlpShape {
+  int k, H, L, K0, Hp, NT;  // K0 = k and Hp = H rounded up to 16; NT = Hp / 16 column tiles
+};
+inline MlpShape mlp_shape(const fmx_mlp_t *m) {
+  MlpShape s;
+  s.k = m->k;
+  s.H = m->hidden;
+  s.L = m->n_layers;
+  s.K0 = (s.k + 15) / 16 * 16;
+  s.Hp = (s.H + 15) / 16 * 16;
+  s.NT = s.Hp / 16;
+  return s;
+}
+// the packed copy: per layer NT * (in / 16) blocks of 64 lanes x 4 floats (lane 16 kq + m, element s: W[16 ct + m][16 g + 4 s
+// + kq], zero outside [H, in)), then the Hp biases (zero past H)
+inline int64_t mlp_packed_floats(const MlpShape &s, int64_t *woff, int64_t *boff) {
+  int64_t o = 0;
+  for (int l = 0; l < s.L; ++l) {
+    const int in = l == 0 ? s.K0 : s.Hp;
+    if (woff) woff[l] = o;
+    o += (int64_t)s.NT * in * 16;
+    if (boff) boff[l] = o;
+    o += s.Hp;
+  }
+  return o;
+}
+
+struct MlpTopkGeom {
+  int cap, splits, per;
+};
+inline int64_t tm_split_min(const MlpShape &s) {
+  const int64_t flops = 2LL * s.Hp * (s.K0 + (int64_t)(s.L - 1) * s.Hp);
+  const int64_t m = (TM_SPLIT_WORK / flops + TM_ROWS - 1) / TM_ROWS * TM_ROWS;
+  return std::min<int64_t>(8192, std::max<int64_t>(TM_ROWS, m));
+}
+inline int64_t tm_max_splits(const MlpShape &s, int N) {
+  const int64_t sm = tm_split_min(s);
+  return std::min<int64_t>(TM_MAX_SPLITS, (N + sm - 1) / sm);
+}
+// one user per workgroup; splits = ceil(budget / U) within [1, tm_max_splits]; a slot holds K + one chunk, a power of two
+inline MlpTopkGeom mlp_topk_geom(const MlpShape &s, int U, int N, int K) {
+  MlpTopkGeom g;
+  g.cap = 128;
+  while (g.cap < K + TM_ROWS) g.cap <<= 1;
+  const int64_t sp = std::max<int64_t>(1, std::min<int64_t>(tm_max_splits(s, N), (TM_TILE_BUDGET + U - 1) / U));
+  const int64_t per0 = (N + sp - 1) / sp;
+  g.per = (int)((per0 + TM_ROWS - 1) / TM_ROWS * TM_ROWS);
+  g.splits = (N + g.per - 1) / g.per;
+  return g;
+}
+// packed weights, then the partial lists uint64 [U, splits, K]: U * splits <= U * ceil(budget / U) < U + budget
+inline int64_t mlp_topk_ws_bytes(const MlpShape &s, int U, int N, int K) {
+  const int64_t parts = std::min<int64_t>((int64_t)U * tm_max_splits(s, N), (int64_t)U + TM_TILE_BUDGET);
+  return mlp_packed_floats(s, nullptr, nullptr) * 4 + parts * K * 8;
+}
+
+struct MlpPackArgs {
+  const float *params;
+  float *packed;
+  long long src_w[TM_MAX_L], src_b[TM_MAX_L], dst_w[TM_MAX_L], dst_b[TM_MAX_L];
+  long long total;
+  int k, H, L, K0, Hp, NT;
+};
+
+// one thread per packed float
+__global__ __launch_bounds__(256) void k_mlp_topk_pack(MlpPackArgs a) {
+  const long long o = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (o >= a.total) return;
+  int l = 0;
+  while (l + 1 < a.L && o >= a.dst_w[l + 1]) ++l;
+  const int in = l == 0 ? a.k : a.H, inp = l == 0 ? a.K0 : a.Hp;
+  float v = 0.f;
+  if (o < a.dst_b[l]) {
+    const long long e = o - a.dst_w[l];
+    const int blk = (int)(e >> 8), lane = (int)(e >> 2) & 63, s = (int)e & 3;
+    const int ct = blk / (inp / 16), g = blk - ct * (inp / 16);
+    const int n = 16 * ct + (lane & 15), i = 16 * g + 4 * s + (lane >> 4);
+    if (n < a.H && i < in) v = a.params[a.src_w[l] + (long long)n * in + i];
+  } else {
+    const int j = (int)(o - a.dst_b[l]);
+    if (j < a.H) v = a.params[a.src_b[l] + j];
+  }
+  a.packed[o] = v;
+}
+
+struct MlpTopkArgs {
+  const float *Su, *Bu, *au, *Sc, *Bc, *ac;
+  const int32_t *excl_off, *excl_pos;
+  const float *packed;
+  long long woff[TM_MAX_L], boff[TM_MAX_L];
+  uint64_t *parts;
+  int32_t *top_pos;
+  float *top_score;
+  int ld_u, ld_c, U, N, K, kp, k, H, L, K0, Hp, fm_term, cap, splits, per;
+};
+
+// activation (row r < 64, column d) of a chunk with G groups of 16 columns: [row tile][G][lane 16 (d % 4) + r % 16][(d / 4) % 4]
+__device__ __forceinline__ int xidx(int r, int d, int G) {
+  return ((((r >> 4) * G + (d >> 4)) * 64 + (d & 3) * 16 + (r & 15)) << 2) + ((d >> 2) & 3);
+}
+
+// grid (U, splits).  Per chunk of 64 candidates: x0 into LDS, the L layers (MFMA, then relu into the same buffer between two
+// barriers), then wave 0 scores row r = candidate c0 + r and appends it to the user's slot.
+template <int WC, int NCT>
+__global__ __launch_bounds__(256) void k_mlp_topk_scan(MlpTopkArgs a) {
+  extern __shared__ __attribute__((aligned(16))) float tm_lds[];
+  constexpr int RPW = WC;  // row tiles per wave (4 row tiles over 4 / WC wave rows)
+  const int NT = a.Hp / 16;
+  const int wmax = a.K0 > a.Hp ? a.K0 : a.Hp;
+  float *X = tm_lds;
+  Slots s;
+  init_slots(s, reinterpret_cast<uint64_t *>(X + (size_t)TM_ROWS * wmax), 1, a.cap);
+  const int t = threadIdx.x, lane = t & 63, w = t >> 6, wr = w / WC, wc = w % WC;
+  const int m = lane & 15, kq = lane >> 4;
+  const int u = blockIdx.x;
+  const float *__restrict__ Su = a.Su + (size_t)u * a.ld_u;
+  const float *__restrict__ Bu = a.Bu + (size_t)u * a.ld_u;
+  const float au = a.au[u];
+  const int c_begin = blockIdx.y * a.per, c_end = min(a.N, c_begin + a.per);
+  const int G0 = a.K0 / 16, Gh = a.Hp / 16;
+  for (int c0 = c_begin; c0 < c_end; c0 += TM_ROWS) {
+    // x0[r][d] = fma(Su[d], Sc[d], Bu[d] + Bc[d]) for d < k, 0 on the pad columns (rows past the split repeat its last one)
+    for (int e = t; e < TM_ROWS * a.K0; e += 256) {
+      const int r = e / a.K0, d = e - r * a.K0;
+      const size_t c = (size_t)min(c0 + r, c_end - 1);
+      float v = 0.f;
+      if (d < a.k) v = fmaf(Su[d], a.Sc[c * a.ld_c + d], Bu[d] + a.Bc[c * a.ld_c + d]);
+      X[xidx(r, d, G0)] = v;
+    }
+    __syncthreads();
+    for (int l = 0; l < a.L; ++l) {
+      const int G = l == 0 ? G0 : Gh;
+      const f32x4 *Wp = reinterpret_cast<const f32x4 *>(a.packed + a.woff[l]) + lane;
+      const float *bp = a.packed + a.boff[l];
+      f32x4 acc[RPW][NCT], bcur[NCT], bnxt[NCT];
+#pragma unroll
+      for (int j = 0; j < NCT; ++j) {
+        const int ct = wc + WC * j;
+        const float b = ct < NT ? bp[16 * ct + m] : 0.f;
+#pragma unroll
+        for (int i = 0; i < RPW; ++i) acc[i][j] = f32x4{b, b, b, b};
+        bcur[j] = ct < NT ? Wp[(size_t)ct * G * 64] : f32x4{0.f, 0.f, 0.f, 0.f};
+      }
+      for (int g = 0; g < G; ++g) {
+#pragma unroll
+        for (int j = 0; j < NCT; ++j) {
+          const int ct = wc + WC * j;
+          bnxt[j] = (ct < NT && g + 1 < G) ? Wp[((size_t)ct * G + g + 1) * 64] : bcur[j];
+        }
+        f32x4 av[RPW];
+#pragma unroll
+        for (int i = 0; i < RPW; ++i) av[i] = reinterpret_cast<const f32x4 *>(X)[((wr * RPW + i) * G + g) * 64 + lane];
+#pragma unroll
+        for (int st = 0; st < 4; ++st)
+#pragma unroll
+          for (int j = 0; j < NCT; ++j) {
+            if (wc + WC * j >= NT) continue;
+#pragma unroll
+            for (int i = 0; i < RPW; ++i) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[i][st], bcur[j][st], acc[i][j], 0, 0, 0);
+          }
+#pragma unroll
+        for (int j = 0; j < NCT; ++j) bcur[j] = bnxt[j];
+      }
+      __syncthreads();  // every wave has read this layer's input
+      // lane (m, kq), register q holds row 4 kq + q, column m of the tile; relu keeps a NaN (as torch.relu does)
+#pragma unroll
+      for (int j = 0; j < NCT; ++j) {
+        const int ct = wc + WC * j;
+        if (ct >= NT) continue;
+#pragma unroll
+        for (int i = 0; i < RPW; ++i)
+#pragma unroll
+          for (int q = 0; q < 4; ++q) {
+            const float v = acc[i][j][q];
+            X[xidx(16 * (wr * RPW + i) + 4 * kq + q, 16 * ct + m, Gh)] = v < 0.f ? 0.f : v;
+          }
+      }
+      __syncthreads();
+    }
+    if (t < TM_ROWS) {
+      const int c = c0 + t;
+      const bool valid = c < c_end;
+      const size_t cr = (size_t)(valid ? c : c_begin);
+      float sum = X[xidx(t, 0, Gh)];
+      for (int j = 1; j < a.H; ++j) sum = sum + X[xidx(t, j, Gh)];
+      float base = au + a.ac[cr];
+      if (a.fm_term) {
+        const float *sc = a.Sc + cr * a.ld_c;
+        float dot = Su[0] * sc[0];
+        for (int d = 1; d < a.kp; ++d) dot = fmaf(Su[d], sc[d], dot);
+        base = base + dot;
+      }
+      const float score = base + sum;
+      const uint64_t key = make_key(score, c);
+      bool keep = valid && score == score && key > s.thr[0];
+      if (keep && a.excl_off) keep = !excluded(a.excl_off, a.excl_pos, u, c);
+      append(s, 0, a.cap, keep, key);
+    }
+    __syncthreads();
+    compact(s, 1, a.cap, a.K, c0 == c_begin ? a.K : a.cap - TM_ROWS);
+  }
+  compact(s, 1, a.cap, a.K, -1);
+  if (a.splits > 1)
+    emit(s, 0, a.cap, a.K, a.parts + ((size_t)u * a.splits + blockIdx.y) * a.K, nullptr, nullptr);
+  else
+    emit(s, 0, a.cap, a.K, nullptr, a.top_pos + (size_t)u * a.K, a.top_score + (size_t)u * a.K);
+}
+
+size_t mlp_topk_lds(const MlpShape &s, int cap) { return (size_t)TM_ROWS * std::max(s.K0, s.Hp) * 4 + slots_lds(1, cap); }
+
+template <int WC, int NCT>
+int launch_mlp_topk_scan(const MlpTopkArgs &a, dim3 grid, size_t lds, hipStream_t st) {
+  static const bool raised = [] {  // 64 KiB of activations at hidden = 256 + the slot: above the default dynamic LDS limit
+    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_mlp_topk_scan<WC, NCT>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                              80 * 1024);
+    return true;
+  }();
+  (void)raised;
+  hipLaunchKernelGGL((k_mlp_topk_scan<WC, NCT>), grid, dim3(256), lds, st, a);
+  return check_launch("k_mlp_topk_scan");
+}
+
+int check_mlp_topk_sizes(const fmx_mlp_t *mlp, int32_t U, int32_t N, int32_t K) {
+  if (!mlp) return fail(FMX_ERR_ARG, "fmx_mlp_topk: null mlp");
+  if (U < 1 || N < 1) return fail(FMX_ERR_ARG, "fmx_mlp_topk: U=%d and N=%d must be >= 1", U, N);
+  if (K < 1) return fail(FMX_ERR_ARG, "fmx_mlp_topk: K=%d must be >= 1", K);
+  if (K > TK_MAX_K) return fail(FMX_ERR_UNSUPPORTED, "fmx_mlp_topk: K=%d, the kernels cover K <= %d", K, TK_MAX_K);
+  if (mlp->n_layers < 1 || mlp->n_layers > TM_MAX_L || mlp->hidden < 1 || mlp->hidden > TM_MAX_H || mlp->k < 1 || mlp->k > 64)
+    return fail(FMX_ERR_UNSUPPORTED, "fmx_mlp_topk: needs 1 <= layers <= %d, 1 <= hidden <= %d, 1 <= k <= 64 (got %d, %d, %d)", TM_MAX_L,
+                TM_MAX_H, mlp->n_layers, mlp->hidden, mlp->k);
+  return FMX_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int64_t fmx_mlp_topk_workspace_bytes(const fmx_mlp_t *mlp, int32_t U, int32_t N, int32_t K) {
+  if (int rc = check_mlp_topk_sizes(mlp, U, N, K)) return rc;
+  return mlp_topk_ws_bytes(mlp_shape(mlp), U, N, K);
+}
+
+int fmx_mlp_topk(const fmx_mlp_t *mlp, int32_t fm_term, const float *Su, const float *Bu, int32_t ld_u, const float *au, int32_t U,
+                 const float *Sc, const float *Bc, int32_t ld_c, const float *ac, int32_t N, int32_t kp, const int32_t *excl_offsets,
+                 const int32_t *excl_pos, int32_t K, void *workspace, int64_t workspace_bytes, int32_t *top_pos, float *top_score,
+                 fmx_stream_t stream) {
+  if (!mlp || !mlp->params || !Su || !Bu || !au || !Sc || !Bc || !ac || !workspace || !top_pos || !top_score)
+    return fail(FMX_ERR_ARG, "fmx_mlp_topk: null argument");
+  if ((excl_offsets == nullptr) != (excl_pos == nullptr))
+    return fail(FMX_ERR_ARG, "fmx_mlp_topk: excl_offsets and excl_pos go together");
+  if (fm_term != 0 && fm_term != 1) return fail(FMX_ERR_ARG, "fmx_mlp_topk: fm_term=%d must be 0 or 1", fm_term);
+  if (int rc = check_mlp_topk_sizes(mlp, U, N, K)) return rc;
+  if (kp != 4 && kp != 8 && kp != 16 && kp != 32 && kp != 64) return fail(FMX_ERR_UNSUPPORTED, "fmx_mlp_topk: kp=%d must be 4/8/16/32/64", kp);
+  if (mlp->k > kp) return fail(FMX_ERR_UNSUPPORTED, "fmx_mlp_topk: k=%d exceeds kp=%d", mlp->k, kp);
+  if (ld_u < kp || ld_c < kp || ld_u % 4 || ld_c % 4)
+    return fail(FMX_ERR_SHAPE, "fmx_mlp_topk: ld_u=%d and ld_c=%d must be multiples of 4 and >= kp=%d", ld_u, ld_c, kp);
+  if (!aligned16(Su) || !aligned16(Bu) || !aligned16(Sc) || !aligned16(Bc) || !aligned16(workspace))
+    return fail(FMX_ERR_ALIGN, "fmx_mlp_topk: Su, Bu, Sc, Bc and the workspace must be 16-byte aligned");
+  const MlpShape sh = mlp_shape(mlp);
+  const int64_t need = mlp_topk_ws_bytes(sh, U, N, K);
+  if (workspace_bytes < need)
+    return fail(FMX_ERR_SHAPE, "fmx_mlp_topk: workspace of %lld bytes, fmx_mlp_topk_workspace_bytes(mlp, %d, %d, %d) = %lld",
+                (long long)workspace_bytes, U, N, K, (long long)need);
+  const MlpTopkGeom g = mlp_topk_geom(sh, U, N, K);
+  int64_t woff[TM_MAX_L], boff[TM_MAX_L];
+  const int64_t packed_n = mlp_packed_floats(sh, woff, boff);
+  float *packed = static_cast<float *>(workspace);
+  MlpPackArgs p;
+  p.params = mlp->params;
+  p.packed = packed;
+  int64_t src = 0;
+  for (int l = 0; l < sh.L; ++l) {
+    const int in = l == 0 ? sh.k : sh.H;
+    p.src_w[l] = src;
+    p.src_b[l] = src + (int64_t)sh.H * in;
+    src = p.src_b[l] + sh.H;
+    p.dst_w[l] = woff[l];
+    p.dst_b[l] = boff[l];
+  }
+  p.total = packed_n;
+  p.k = sh.k;
+  p.H = sh.H;
+  p.L = sh.L;
+  p.K0 = sh.K0;
+  p.Hp = sh.Hp;
+  p.NT = sh.NT;
+  MlpTopkArgs a;
+  a.Su = Su;
+  a.Bu = Bu;
+  a.au = au;
+  a.Sc = Sc;
+  a.Bc = Bc;
+  a.ac = ac;
+  a.excl_off = excl_offsets;
+  a.excl_pos = excl_pos;
+  a.packed = packed;
+  for (int l = 0; l < sh.L; ++l) {
+    a.woff[l] = woff[l];
+    a.boff[l] = boff[l];
+  }
+  a.parts = reinterpret_cast<uint64_t *>(packed + packed_n);
+  a.top_pos = top_pos;
+  a.top_score = top_score;
+  a.ld_u = ld_u;
+  a.ld_c = ld_c;
+  a.U = U;
+  a.N = N;
+  a.K = K;
+  a.kp = kp;
+  a.k = sh.k;
+  a.H = sh.H;
+  a.L = sh.L;
+  a.K0 = sh.K0;
+  a.Hp = sh.Hp;
+  a.fm_term = fm_term;
+  a.cap = g.cap;
+  a.splits = g.splits;
+  a.per = g.per;
+  const hipStream_t st = static_cast<hipStream_t>(stream);
+  hipLaunchKernelGGL(k_mlp_topk_pack, dim3((unsigned)((packed_n + 255) / 256)), dim3(256), 0, st, p);
+  if (int rc = check_launch("k_mlp_topk_pack")) return rc;
+  const dim3 grid(U, g.splits);
+  const size_t lds = mlp_topk_lds(sh, g.cap);
+  int rc;
+  switch (sh.NT) {
+    case 1: rc = launch_mlp_topk_scan<1, 1>(a, grid, lds, st); break;
+    case 2: rc = launch_mlp_topk_scan<2, 1>(a, grid, lds, st); break;
+    case 3: rc = launch_mlp_topk_scan<2, 2>(a, grid, lds, st); break;
+    case 4: rc = launch_mlp_topk_scan<4, 1>(a, grid, lds, st); break;
+    case 5: case 6: case 7: case 8: rc = launch_mlp_topk_scan<4, 2>(a, grid, lds, st); break;
+    case 9: case 10: case 11: case 12: rc = launch_mlp_topk_scan<4, 3>(a, grid, lds, st); break;
+    default: rc = launch_mlp_topk_scan<4, 4>(a, grid, lds, st); break;
+  }
+  if (rc || g.splits == 1) return rc;
+  TopkArgs m{};  // the merge of fmx_fm_topk: it reads the partial keys, the sizes and the outputs only
+  m.parts = a.parts;
+  m.top_pos = top_pos;
+  m.top_score = top_score;
+  m.U = U;
+  m.N = N;
+  m.K = K;
+  m.cap = K <= 128 ? 512 : 1024;
+  m.splits = g.splits;
+  hipLaunchKernelGGL(k_topk_merge, dim3(U), dim3(TK_THREADS), slots_lds(1, m.cap), st, m);
+  return check_launch("k_topk_merge");
 }
 
 }  // extern "C"

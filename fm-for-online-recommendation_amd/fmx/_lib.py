@@ -20,10 +20,11 @@ EXPORTS = ["fmx_version", "fmx_last_error_string", "fmx_set_option", "fmx_sorted
            "fmx_sort_occurrences", "fmx_fm_update", "fmx_fm_step", "fmx_fm_stream", "fmx_deepfm_stream", "fmx_stream_read",
            "fmx_fm_forward_partial", "fmx_fm_forward_finish", "fmx_sftrl_run", "fmx_sftrl_grid",
            "fmx_gather_read", "fmx_comm_unique_id", "fmx_comm_create", "fmx_comm_destroy", "fmx_owner_prefetch", "fmx_owner_step",
-           "fmx_fm_topk_workspace_bytes", "fmx_fm_topk"]
+           "fmx_fm_topk_workspace_bytes", "fmx_fm_topk", "fmx_mlp_topk_workspace_bytes", "fmx_mlp_topk"]
 
 
-I64_RETURNS = ("fmx_workspace_bytes", "fmx_mlp_section_workspace_bytes", "fmx_fm_topk_workspace_bytes")   # byte counts: int64_t in include/fmx.h
+I64_RETURNS = ("fmx_workspace_bytes", "fmx_mlp_section_workspace_bytes", "fmx_fm_topk_workspace_bytes",
+               "fmx_mlp_topk_workspace_bytes")   # byte counts: int64_t in include/fmx.h
 
 
 class FmxError(RuntimeError):
@@ -112,6 +113,8 @@ def load():
     lib.fmx_deepfm_stream.argtypes = [TP, HP, i32, MP, i32, i32, p, p, i32, i32, f32, i32, p, i64, p, FP, p, p, p, f32, p, p]
     lib.fmx_fm_topk_workspace_bytes.argtypes = [i32, i32, i32]
     lib.fmx_fm_topk.argtypes = [p, i32, p, i32, p, i32, p, i32, i32, p, p, i32, p, i64, p, p, p]
+    lib.fmx_mlp_topk_workspace_bytes.argtypes = [MP, i32, i32, i32]
+    lib.fmx_mlp_topk.argtypes = [MP, i32, p, p, i32, p, i32, p, p, i32, p, i32, i32, p, p, i32, p, i64, p, p, p]
     for name in EXPORTS:
         fn = getattr(lib, name)
         if name in I64_RETURNS:

@@ -9,6 +9,11 @@ a_u: the logit of u's context fields alone (bias included); a_c: sfirst + sbi of
 V x.  Both sides are fmx_fm_forward over full-width rows in which the other side's fields carry index 0 and value 0 (a zero
 value adds exact zeros to S, to sum e^2 and to the first-order sum).  What remains -- U x N kp-wide dot products and an exact
 per-user top-K -- is one fmx_fm_topk call.
+
+The DeepFM / NFM classes put a relu MLP on the bi-interaction vector.  The network does not split, its input does:
+bi(u + c) = bi_u + bi_c + S_u * S_c, so each side is still computed once (side_terms) and fmx_mlp_topk runs the U x N
+forwards of the network on the device, then the same exact selection (topk_network).  Networks the kernel does not take
+(hidden > 256) go through mlp_topk_torch, a chunked torch statement of the same score and result order.
 """
 import ctypes as C
 
@@ -42,11 +47,9 @@ def _as_values(a, shape, device):
     return t.contiguous()
 
 
-def side_sums(table, idx, xv, keep_fields, hyper=None, want_bias=True):
-    """fmx_fm_forward over the rows of idx / xv ([R, F], full width) with every field outside keep_fields given index 0 and
-    value 0.  Returns (S [R, kp], a [R]) on the device: a = the logit (bias included) when want_bias, else sfirst + sbi.
-    An index outside its field (in a kept column) raises IndexError."""
-    F, dev, kp = table.n_fields, table.device, table.kp
+def _masked_side(table, idx, xv, keep_fields):
+    """(idx int32 [R, F], xv fp32 [R, F]) on the device with every field outside keep_fields given index 0 and value 0."""
+    F, dev = table.n_fields, table.device
     idx = _as_index(idx, F, dev)
     R = idx.shape[0]
     xv = _as_values(xv, (R, F), dev)
@@ -54,6 +57,16 @@ def side_sums(table, idx, xv, keep_fields, hyper=None, want_bias=True):
     keep[list(keep_fields)] = True
     idx = torch.where(keep[None, :], idx, torch.zeros_like(idx)).contiguous()
     xv = torch.where(keep[None, :], xv, torch.zeros_like(xv)).contiguous()
+    return idx, xv
+
+
+def side_sums(table, idx, xv, keep_fields, hyper=None, want_bias=True):
+    """fmx_fm_forward over the rows of idx / xv ([R, F], full width) with every field outside keep_fields given index 0 and
+    value 0.  Returns (S [R, kp], a [R]) on the device: a = the logit (bias included) when want_bias, else sfirst + sbi.
+    An index outside its field (in a kept column) raises IndexError."""
+    dev, kp = table.device, table.kp
+    idx, xv = _masked_side(table, idx, xv, keep_fields)
+    R = idx.shape[0]
     lib, h = _lib.load(), _hyper_for(table, hyper)
     S = torch.empty((R, kp), dtype=torch.float32, device=dev)
     a = torch.empty(R, dtype=torch.float32, device=dev)
@@ -80,6 +93,39 @@ def side_sums(table, idx, xv, keep_fields, hyper=None, want_bias=True):
     return S, a
 
 
+def side_terms(table, idx, xv, keep_fields, hyper=None):
+    """As side_sums, but everything the network classes need from the one fmx_fm_forward call per chunk: returns device
+    tensors (S [R, kp], bi [R, kp], sfirst [R], sbi [R], logit [R]) of the masked rows (logit = sfirst + sbi + bias)."""
+    dev, kp = table.device, table.kp
+    idx, xv = _masked_side(table, idx, xv, keep_fields)
+    R = idx.shape[0]
+    lib, h = _lib.load(), _hyper_for(table, hyper)
+    S = torch.empty((R, kp), dtype=torch.float32, device=dev)
+    bi = torch.empty((R, kp), dtype=torch.float32, device=dev)
+    sfirst, sbi, logit = (torch.empty(R, dtype=torch.float32, device=dev) for _ in range(3))
+    error = torch.zeros(1, dtype=torch.int32, device=dev)
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    for r0 in range(0, R, CHUNK):
+        B = min(CHUNK, R - r0)
+        o = _lib.FwdOut()
+        o.S, o.bi = S[r0:].data_ptr(), bi[r0:].data_ptr()
+        o.sfirst, o.sbi, o.logit = sfirst[r0:].data_ptr(), sbi[r0:].data_ptr(), logit[r0:].data_ptr()
+        o.error = error.data_ptr()
+        _lib.check(lib.fmx_fm_forward(table.c_struct(), h.ref(), idx[r0:].data_ptr(), xv[r0:].data_ptr(), None, B,
+                                      _lib.LOSS_NONE, 1.0, C.byref(o), stream))
+    if int(error.item()) != 0:
+        raise IndexError("index out of range in self (flagged by the fmx kernels)")
+    return S, bi, sfirst, sbi, logit
+
+
+def network_bases(table, sfirst, sbi, logit, fm_term, context):
+    """The score's base terms of one side (include/fmx.h, fmx_mlp_topk): DeepFM (fm_term = 1) a_u = logit, a_c = sfirst + sbi;
+    NFM (fm_term = 0) f_u = sfirst + bias, f_c = sfirst."""
+    if fm_term:
+        return logit if context else sfirst + sbi
+    return sfirst + table.bias_weight().reshape(-1)[0] if context else sfirst
+
+
 class Candidates:
     """The candidate side of a recommendation: Sc [N, kp] and ac [N] of cand_idx's item fields ([N, F] full-width rows, the
     other columns ignored), computed on the device.  Call refresh() after the table has been trained."""
@@ -100,6 +146,23 @@ class Candidates:
 
     def refresh(self):
         self.Sc, self.ac = side_sums(self.table, self.idx, self.xv, self.item_fields, self.hyper, want_bias=False)
+        return self
+
+
+class NetworkCandidates(Candidates):
+    """The candidate side for the DeepFM / NFM classes: Sc [N, kp], Bc [N, kp] (bi) and ac [N] (fm_term = 1: sfirst + sbi,
+    0: sfirst) of cand_idx's item fields.  Call refresh() after the table has been trained."""
+
+    def __init__(self, table, item_fields, cand_idx, cand_xv=None, fm_term=1, hyper=None):
+        if fm_term not in (0, 1):
+            raise ValueError(f"fm_term={fm_term}: 1 (DeepFM) or 0 (NFM)")
+        self.fm_term = int(fm_term)
+        super().__init__(table, item_fields, cand_idx, cand_xv, hyper)
+
+    def refresh(self):
+        S, bi, sfirst, sbi, logit = side_terms(self.table, self.idx, self.xv, self.item_fields, self.hyper)
+        self.Sc, self.Bc = S, bi
+        self.ac = network_bases(self.table, sfirst, sbi, logit, self.fm_term, context=False).contiguous()
         return self
 
 
@@ -156,4 +219,125 @@ def topk(table, ctx_idx, ctx_xv, candidates, K, exclude=None, hyper=None):
     Su, au = side_sums(table, ctx_idx, ctx_xv, ctx_fields, hyper if hyper is not None else candidates.hyper, want_bias=True)
     off, pos = exclusions_csr(exclude, Su.shape[0], table.device)
     top_pos, top_score = fm_topk(Su, au, candidates.Sc, candidates.ac, int(K), off, pos)
+    return top_pos.long(), top_score
+
+
+MLP_TOPK_MAX_HIDDEN = 256    # fmx_mlp_topk's limits (include/fmx.h); larger networks take mlp_topk_torch
+MLP_TOPK_MAX_LAYERS = 8
+MLP_TOPK_MAX_K = 256         # for every network
+
+
+def _mlp_struct(mlp):
+    params, k, hidden, n_layers = mlp
+    if params.dtype != torch.float32 or not params.is_contiguous():
+        raise ValueError("mlp params: a contiguous fp32 device tensor (W_l [hidden, in_l] then b_l per layer)")
+    return _lib.Mlp(params.data_ptr(), int(n_layers), int(k), int(hidden), 0)
+
+
+def mlp_topk(mlp, fm_term, Su, Bu, au, Sc, Bc, ac, K, excl_offsets=None, excl_pos=None, workspace=None, out=None, stream=None,
+             kp=None):
+    """The raw call of fmx_mlp_topk.  mlp = (params, k, hidden, n_layers) with params the flat fp32 device buffer; Su / Bu
+    [U, >= kp] share a row stride, Sc / Bc [N, >= kp] too (multiples of 4, 16-byte aligned); kp defaults to Sc's width.
+    Returns (top_pos int32 [U, K], top_score fp32 [U, K]) on the device."""
+    U, N = Su.shape[0], Sc.shape[0]
+    kp = Sc.shape[1] if kp is None else int(kp)
+    if Bu.stride(0) != Su.stride(0) or Bc.stride(0) != Sc.stride(0):
+        raise ValueError("Bu / Bc must share the row strides of Su / Sc")
+    lib, dev = _lib.load(), Su.device
+    m = _mlp_struct(mlp)
+    need = int(lib.fmx_mlp_topk_workspace_bytes(C.byref(m), U, N, K))
+    _lib.check(min(need, 0))
+    if workspace is None or workspace.numel() * workspace.element_size() < need:
+        workspace = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
+    if out is None:
+        out = (torch.empty((U, K), dtype=torch.int32, device=dev), torch.empty((U, K), dtype=torch.float32, device=dev))
+    st = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
+    _lib.check(lib.fmx_mlp_topk(C.byref(m), int(fm_term), Su.data_ptr(), Bu.data_ptr(), Su.stride(0), au.data_ptr(), U,
+                                Sc.data_ptr(), Bc.data_ptr(), Sc.stride(0), ac.data_ptr(), N, kp,
+                                None if excl_offsets is None else excl_offsets.data_ptr(),
+                                None if excl_pos is None else excl_pos.data_ptr(), K, workspace.data_ptr(),
+                                workspace.numel() * workspace.element_size(), out[0].data_ptr(), out[1].data_ptr(), st))
+    return out
+
+
+def mlp_topk_torch(mlp, fm_term, Su, Bu, au, Sc, Bc, ac, K, excl_offsets=None, excl_pos=None, kp=None, max_elems=1 << 25):
+    """The same score (up to fp32 summation order) and the same result order as fmx_mlp_topk, as chunked torch: for a block
+    of users, every candidate's network output, then a stable sort on (score descending, position ascending); NaN and
+    excluded candidates are never returned, rows are padded with -1 / -inf, -0 is returned as +0.  The path of networks the
+    kernel does not take, and the baseline of tools/mlp_topk_times.py."""
+    params, k, H, L = mlp
+    U, N, dev = Su.shape[0], Sc.shape[0], Su.device
+    kp = Sc.shape[1] if kp is None else int(kp)
+    Ws, off = [], 0
+    for l in range(L):
+        n_in = k if l == 0 else H
+        W = params[off:off + H * n_in].view(H, n_in)
+        b = params[off + H * n_in:off + H * n_in + H]
+        Ws.append((W, b))
+        off += H * n_in + H
+    top_pos = torch.full((U, K), -1, dtype=torch.int32, device=dev)
+    top_score = torch.full((U, K), float("-inf"), dtype=torch.float32, device=dev)
+    Sck, Bck = Sc[:, :k], Bc[:, :k]
+    ub = max(1, min(U, max_elems // max(1, N * max(H, k))))
+    cb = max(1, min(N, max_elems // max(1, ub * max(H, k))))
+    with torch.no_grad():
+        for u0 in range(0, U, ub):
+            u1 = min(U, u0 + ub)
+            score = torch.empty((u1 - u0, N), dtype=torch.float32, device=dev)
+            for c0 in range(0, N, cb):
+                c1 = min(N, c0 + cb)
+                x = (Bu[u0:u1, None, :k] + Bck[None, c0:c1]) + Su[u0:u1, None, :k] * Sck[None, c0:c1]
+                for W, b in Ws:
+                    x = torch.relu(torch.nn.functional.linear(x, W, b))
+                base = au[u0:u1, None] + ac[None, c0:c1]
+                if fm_term:
+                    base = base + Su[u0:u1, :kp] @ Sc[c0:c1, :kp].T
+                score[:, c0:c1] = base + x.sum(-1)
+            score = score + 0.0                              # -0 -> +0
+            ok = ~torch.isnan(score)
+            if excl_offsets is not None:
+                offs = excl_offsets.long().cpu()
+                for u in range(u0, u1):
+                    p = excl_pos[int(offs[u]):int(offs[u + 1])].long()
+                    p = p[p < N]
+                    ok[u - u0, p] = False
+            score = torch.where(ok, score, torch.full_like(score, float("-inf")))
+            s1, i1 = torch.sort(score, dim=1, descending=True, stable=True)
+            ok1 = torch.gather(ok, 1, i1)
+            _, i2 = torch.sort(ok1.to(torch.int8), dim=1, descending=True, stable=True)
+            idx = torch.gather(i1, 1, i2)[:, :K]
+            sc = torch.gather(s1, 1, i2)[:, :K]
+            valid = torch.gather(ok1, 1, i2)[:, :K]
+            n = idx.shape[1]
+            top_pos[u0:u1, :n] = torch.where(valid, idx, torch.full_like(idx, -1)).to(torch.int32)
+            top_score[u0:u1, :n] = torch.where(valid, sc, torch.full_like(sc, float("-inf")))
+    return top_pos, top_score
+
+
+def mlp_kernel_takes(mlp):
+    """Does fmx_mlp_topk take this network?  (Else the chunked torch path; K > 256 is refused either way.)"""
+    _, k, H, L = mlp
+    return 1 <= H <= MLP_TOPK_MAX_HIDDEN and 1 <= L <= MLP_TOPK_MAX_LAYERS and 1 <= k <= 64
+
+
+def topk_network(table, mlp, fm_term, ctx_idx, ctx_xv, candidates, K, exclude=None, hyper=None):
+    """Top-K candidates for every context row under the DeepFM (fm_term = 1) / NFM (fm_term = 0) network mlp = (params,
+    k, hidden, n_layers): the logit of the combined sample for the Adam classes, the logit whose sigmoid forward() returns
+    for the ONN classes.  candidates: a NetworkCandidates of the same table and fm_term.  Returns device tensors (positions
+    int64 [U, K], -1 padded; scores fp32 [U, K], -inf padded), each row by score descending, then position ascending."""
+    if candidates.table is not table:
+        raise ValueError("candidates were computed for another table")
+    if not isinstance(candidates, NetworkCandidates) or candidates.fm_term != int(fm_term):
+        raise ValueError(f"candidates: a NetworkCandidates with fm_term={int(fm_term)}")
+    ctx_fields = [f for f in range(table.n_fields) if f not in candidates.item_fields]
+    S, bi, sfirst, sbi, logit = side_terms(table, ctx_idx, ctx_xv, ctx_fields,
+                                           hyper if hyper is not None else candidates.hyper)
+    au = network_bases(table, sfirst, sbi, logit, fm_term, context=True).contiguous()
+    off, pos = exclusions_csr(exclude, S.shape[0], table.device)
+    K = int(K)
+    args = (mlp, fm_term, S, bi, au, candidates.Sc, candidates.Bc, candidates.ac, K, off, pos)
+    if mlp_kernel_takes(mlp) or not 1 <= K <= MLP_TOPK_MAX_K:     # the kernel's checks raise on a bad K
+        top_pos, top_score = mlp_topk(*args)
+    else:
+        top_pos, top_score = mlp_topk_torch(*args)
     return top_pos.long(), top_score

@@ -454,15 +454,18 @@ class OnlineFMBase(nn.Module):
         pred = torch.sigmoid(out).cpu()
         return pred.data.numpy() > 0.5
 
-    def recommend(self, Xi, Xv, item_fields, K, candidates=None, exclude=None):
+    def recommend(self, Xi, Xv, item_fields, K, candidates=None, exclude=None, full=False):
         """Top-K candidates for every context row (fmx/recommend.py, fmx_fm_topk).  Xi / Xv: [U, F] full-width rows whose
         item columns are ignored (Xv may be None: all ones).  candidates=None: every row of the one item field, a position is
         that field's local index; else (cand_Xi [N, F], cand_Xv or None) whose non-item columns are ignored.  exclude: per-user
         position lists or a CSR pair (offsets, positions).  Returns numpy (positions int64 [U, K], -1 padded; logits fp32
-        [U, K], -inf padded), each row by logit descending, then position ascending."""
-        if self._has_mlp:
+        [U, K], -inf padded), each row by logit descending, then position ascending.
+        full=True scores every pair through the whole network (fmx_mlp_topk): for DeepFMAdam / NFMAdam the logit forward()
+        returns, for DeepFMOnn / NFMOnn the logit whose sigmoid forward() returns; on FMAdam it is the default call."""
+        if self._has_mlp and not full:
             raise NotImplementedError(f"{self._name}.recommend: the MLP on the bi-interaction vector does not decompose over "
-                                      "the context / item field split")
+                                      "the context / item field split; recommend(..., full=True) scores every pair through "
+                                      "the network")
         item_fields = [int(f) for f in (item_fields if hasattr(item_fields, "__len__") else [item_fields])]
         F = self.field_size
         if candidates is None:
@@ -474,6 +477,13 @@ class OnlineFMBase(nn.Module):
             cand_xv = None
         else:
             cand_idx, cand_xv = candidates
+        if self._has_mlp:
+            fm_term = 1 if self._fm_term_in_forward else 0
+            mlp = (self._mlp_flat, self.embedding_size, self.neuron_per_hidden_layer, self.num_hidden_layers)
+            cands = fmx.recommend.NetworkCandidates(self._table, item_fields, cand_idx, cand_xv, fm_term=fm_term, hyper=self._hyper)
+            pos, logit = fmx.recommend.topk_network(self._table, mlp, fm_term, Xi, Xv, cands, K, exclude=exclude,
+                                                    hyper=self._hyper)
+            return pos.cpu().numpy(), logit.cpu().numpy()
         cands = fmx.recommend.Candidates(self._table, item_fields, cand_idx, cand_xv, hyper=self._hyper)
         pos, logit = fmx.recommend.topk(self._table, Xi, Xv, cands, K, exclude=exclude, hyper=self._hyper)
         return pos.cpu().numpy(), logit.cpu().numpy()

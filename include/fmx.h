@@ -55,8 +55,9 @@
 extern "C" {
 #endif
 
-#define FMX_VERSION 104 /* 0.1.4: fmx_deepfm_stream, fmx_fm_topk / fmx_fm_topk_workspace_bytes (0.1.3: fields as row-range pieces
-                           of index columns -- field_cols / field_base / n_cols --, workspace_bytes arguments, fmx_owner_*) */
+#define FMX_VERSION 104 /* 0.1.4: fmx_deepfm_stream, fmx_fm_topk / fmx_fm_topk_workspace_bytes, fmx_mlp_topk /
+                           fmx_mlp_topk_workspace_bytes (0.1.3: fields as row-range pieces of index columns -- field_cols /
+                           field_base / n_cols --, workspace_bytes arguments, fmx_owner_*) */
 
 typedef void *fmx_stream_t; /* hipStream_t */
 
@@ -452,6 +453,37 @@ int64_t fmx_fm_topk_workspace_bytes(int32_t U, int32_t N, int32_t K);
 int fmx_fm_topk(const float *Su, int32_t ld_u, const float *au, int32_t U, const float *Sc, int32_t ld_c, const float *ac, int32_t N,
                 int32_t kp, const int32_t *excl_offsets, const int32_t *excl_pos, int32_t K, void *workspace, int64_t workspace_bytes,
                 int32_t *top_pos, float *top_score, fmx_stream_t stream);
+
+/* ---- top-K recommendation for the classes with an MLP (DeepFM / NFM, fmx/recommend.py) ----
+ * Replaces: forward() over assembled (context, candidate) samples followed by torch.topk (reference deepfm_adam.py:79-89,
+ * nfm_adam.py:78-88, deepfm_onn.py:88-104, nfm_onn.py:90-104 for the network).  The network does not split over the field
+ * split, its input does: with both sides computed alone as for fmx_fm_topk,
+ *     bi(u + c) = bi_u + bi_c + S_u (.) S_c
+ * so the U x N forwards run on a k-vector built on the device.
+ *   mlp: the network (params flat, W_l [hidden, in_l] then b_l [hidden] per layer, in_0 = k); fm_term = 1: DeepFM, 0: NFM
+ *   Su, Bu [U, ld_u], au [U]: the contexts' S, bi and base;  Sc, Bc [N, ld_c], ac [N]: the candidates' (Bu / Bc share the
+ *   strides of Su / Sc; ld_u, ld_c multiples of 4, >= kp; the four 16-byte aligned).  DeepFM: au = the logit of u alone (bias
+ *   in), ac = sfirst_c + sbi_c;  NFM: au = sfirst_u + bias, ac = sfirst_c.
+ *   kp, exclusions, K, top_pos / top_score: exactly as fmx_fm_topk (orders, -1 / -inf padding, NaN never returned, -0 as +0).
+ * The score is one fixed function of (u, c), whatever U, N, the tile, the split or the candidate order (fp32, one rounding per
+ * operation):
+ *     x_0[d] = fma(Su[d], Sc[d], Bu[d] + Bc[d])                     d < k (columns k .. kp-1 are not read)
+ *     x_l[j] = relu(acc),  acc = fma(x_{l-1}[in-1], W_l[j][in-1], ... fma(x_{l-1}[0], W_l[j][0], b_l[j]) ...)   (i ascending;
+ *              relu(v) = v < 0 ? 0 : v, a NaN stays NaN)
+ *     sum    = (... ((x_L[0] + x_L[1]) + x_L[2]) ... ) + x_L[hidden-1]
+ *     base   = fm_term ? (au[u] + ac[c]) + dot : au[u] + ac[c]      dot: the fma chain of fmx_fm_topk over d < kp
+ *     score  = base + sum
+ * For the ONN classes this is the logit whose sigmoid forward() returns: the same order, without saturation ties.
+ * Limits: kp 4 / 8 / 16 / 32 / 64, 1 <= k <= kp, 1 <= hidden <= 256, 1 <= n_layers <= 8, 1 <= K <= 256; anything outside:
+ * FMX_ERR_UNSUPPORTED.  The workspace (16-byte aligned, no initialisation needed) holds a copy of the weights in the kernels'
+ * operand order and the partial lists of a split scan: fmx_mlp_topk_workspace_bytes(mlp, U, N, K) bytes (monotone in U, N
+ * and K), else FMX_ERR_SHAPE.  Three launches at most (the weight copy, the scan, the merge); every argument is checked before
+ * anything is launched. */
+int64_t fmx_mlp_topk_workspace_bytes(const fmx_mlp_t *mlp, int32_t U, int32_t N, int32_t K);
+int fmx_mlp_topk(const fmx_mlp_t *mlp, int32_t fm_term, const float *Su, const float *Bu, int32_t ld_u, const float *au, int32_t U,
+                 const float *Sc, const float *Bc, int32_t ld_c, const float *ac, int32_t N, int32_t kp,
+                 const int32_t *excl_offsets, const int32_t *excl_pos, int32_t K, void *workspace, int64_t workspace_bytes,
+                 int32_t *top_pos, float *top_score, fmx_stream_t stream);
 
 /* Streaming read of `bytes` (multiple of 16) with 16-byte loads; sink [1] receives a checksum so the loads stay
  * live.  Used by bench.py to measure the HBM-read ceiling on the same GPU in the same run. */
