@@ -28,10 +28,12 @@ struct TopkGeom {
 
 // K <= 128: 16 users x 512 keys; K <= 256: 8 users x 1024 keys.  Both 64 KiB of LDS (two workgroups per CU).  A slot is
 // compacted when it holds more than cap - 256 keys (a chunk may add 256) and then holds K, so a compaction drops >= 128 keys.
+// The merge's single slot has the same capacity.
+constexpr int topk_cap(int K) { return K <= 128 ? 512 : 1024; }
 inline TopkGeom topk_geom(int U, int N, int K) {
   TopkGeom g;
   g.ut = K <= 128 ? 16 : 8;
-  g.cap = K <= 128 ? 512 : 1024;
+  g.cap = topk_cap(K);
   g.tiles = (U + g.ut - 1) / g.ut;
   const int sn = std::min(TK_MAX_SPLITS, (N + TK_SPLIT_MIN - 1) / TK_SPLIT_MIN);
   const int s = std::max(1, std::min(sn, TK_TILE_BUDGET / g.tiles));
@@ -266,87 +268,6 @@ __global__ __launch_bounds__(TK_THREADS) void k_topk_merge(TopkArgs a) {
   emit(s, 0, a.cap, a.K, nullptr, a.top_pos + (size_t)u * a.K, a.top_score + (size_t)u * a.K);
 }
 
-size_t slots_lds(int n, int cap) { return (size_t)n * cap * 8 + (size_t)n * 8 + (size_t)n * 4; }
-
-template <int KP>
-int launch_topk(const TopkArgs &a, const TopkGeom &g, hipStream_t st) {
-  static const bool raised = [] {  // 64 KiB of keys + the counts and thresholds: above the default dynamic LDS limit
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_topk_scan<KP>), hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_topk_merge), hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
-    return true;
-  }();
-  (void)raised;
-  hipLaunchKernelGGL(k_topk_scan<KP>, dim3(g.tiles, g.splits), dim3(TK_THREADS), slots_lds(g.ut, g.cap), st, a);
-  if (int rc = check_launch("k_topk_scan")) return rc;
-  if (g.splits == 1) return FMX_OK;
-  hipLaunchKernelGGL(k_topk_merge, dim3(a.U), dim3(TK_THREADS), slots_lds(1, g.cap), st, a);
-  return check_launch("k_topk_merge");
-}
-
-int check_topk_sizes(int32_t U, int32_t N, int32_t K) {
-  if (U < 1 || N < 1) return fail(FMX_ERR_ARG, "fmx_fm_topk: U=%d and N=%d must be >= 1", U, N);
-  if (K < 1) return fail(FMX_ERR_ARG, "fmx_fm_topk: K=%d must be >= 1", K);
-  if (K > TK_MAX_K) return fail(FMX_ERR_UNSUPPORTED, "fmx_fm_topk: K=%d, the kernels cover K <= %d", K, TK_MAX_K);
-  return FMX_OK;
-}
-
-}  // namespace
-
-extern "C" {
-
-int64_t fmx_fm_topk_workspace_bytes(int32_t U, int32_t N, int32_t K) {
-  if (int rc = check_topk_sizes(U, N, K)) return rc;
-  return topk_ws_bytes(U, N, K);
-}
-
-int fmx_fm_topk(const float *Su, int32_t ld_u, const float *au, int32_t U, const float *Sc, int32_t ld_c, const float *ac, int32_t N,
-                int32_t kp, const int32_t *excl_offsets, const int32_t *excl_pos, int32_t K, void *workspace, int64_t workspace_bytes,
-                int32_t *top_pos, float *top_score, fmx_stream_t stream) {
-  if (!Su || !au || !Sc || !ac || !workspace || !top_pos || !top_score) return fail(FMX_ERR_ARG, "fmx_fm_topk: null argument");
-  if ((excl_offsets == nullptr) != (excl_pos == nullptr))
-    return fail(FMX_ERR_ARG, "fmx_fm_topk: excl_offsets and excl_pos go together");
-  if (int rc = check_topk_sizes(U, N, K)) return rc;
-  if (kp != 4 && kp != 8 && kp != 16 && kp != 32 && kp != 64) return fail(FMX_ERR_SHAPE, "fmx_fm_topk: kp=%d must be 4/8/16/32/64", kp);
-  if (ld_u < kp || ld_c < kp || ld_u % 4 || ld_c % 4)
-    return fail(FMX_ERR_SHAPE, "fmx_fm_topk: ld_u=%d and ld_c=%d must be multiples of 4 and >= kp=%d", ld_u, ld_c, kp);
-  if (!aligned16(Su) || !aligned16(Sc) || !aligned16(workspace))
-    return fail(FMX_ERR_ALIGN, "fmx_fm_topk: Su, Sc and the workspace must be 16-byte aligned");
-  const int64_t need = topk_ws_bytes(U, N, K);
-  if (workspace_bytes < need)
-    return fail(FMX_ERR_SHAPE, "fmx_fm_topk: workspace of %lld bytes, fmx_fm_topk_workspace_bytes(%d, %d, %d) = %lld",
-                (long long)workspace_bytes, U, N, K, (long long)need);
-  const TopkGeom g = topk_geom(U, N, K);
-  TopkArgs a;
-  a.Su = Su;
-  a.au = au;
-  a.Sc = Sc;
-  a.ac = ac;
-  a.excl_off = excl_offsets;
-  a.excl_pos = excl_pos;
-  a.parts = static_cast<uint64_t *>(workspace);
-  a.top_pos = top_pos;
-  a.top_score = top_score;
-  a.ld_u = ld_u;
-  a.ld_c = ld_c;
-  a.U = U;
-  a.N = N;
-  a.K = K;
-  a.ut = g.ut;
-  a.cap = g.cap;
-  a.splits = g.splits;
-  a.per = g.per;
-  const hipStream_t st = static_cast<hipStream_t>(stream);
-  switch (kp) {
-    case 4: return launch_topk<4>(a, g, st);
-    case 8: return launch_topk<8>(a, g, st);
-    case 16: return launch_topk<16>(a, g, st);
-    case 32: return launch_topk<32>(a, g, st);
-    default: return launch_topk<64>(a, g, st);
-  }
-}
-
-}  // extern "C"
-
 // ---------------------------------------------------------------------------------------------------------------------
 // fmx_mlp_topk: the same selection over the scores of the DeepFM / NFM network on the pair's bi-interaction vector
 // ---------------------------------------------------------------------------------------------------------------------
@@ -358,7 +279,6 @@ int fmx_fm_topk(const float *Su, int32_t ld_u, const float *au, int32_t U, const
 // multiplying wave's registers (a pre-packed copy in the workspace, one 16-byte load per lane and four k-steps), the
 // activations stay in LDS in the MFMA's operand order (one ds_read_b128 per lane and four k-steps).  Each pair's scores
 // then go through the slot / compact / merge of fmx_fm_topk.
-namespace {
 
 constexpr int TM_ROWS = 64;                 // pairs per chunk: four MFMA row tiles
 constexpr int TM_MAX_H = 256, TM_MAX_L = 8;
@@ -380,19 +300,33 @@ inline MlpShape mlp_shape(const fmx_mlp_t *m) {
   s.NT = s.Hp / 16;
   return s;
 }
-// the packed copy: per layer NT * (in / 16) blocks of 64 lanes x 4 floats (lane 16 kq + m, element s: W[16 ct + m][16 g + 4 s
-// + kq], zero outside [H, in)), then the Hp biases (zero past H)
-inline int64_t mlp_packed_floats(const MlpShape &s, int64_t *woff, int64_t *boff) {
-  int64_t o = 0;
+struct MlpPackArgs {
+  const float *params;
+  float *packed;
+  long long src_w[TM_MAX_L], src_b[TM_MAX_L], dst_w[TM_MAX_L], dst_b[TM_MAX_L];
+  long long total;
+  int k, H, L, K0, Hp, NT;
+};
+
+// Per layer l, where W_l [H, in_l] and b_l sit in mlp->params (src_*) and in the packed copy (dst_*): NT * (in / 16) blocks of
+// 64 lanes x 4 floats (lane 16 kq + m, element s: W[16 ct + m][16 g + 4 s + kq], zero outside [H, in)), then the Hp biases
+// (zero past H).  Returns the packed copy's floats; p may be null.
+inline int64_t mlp_packed_floats(const MlpShape &s, MlpPackArgs *p) {
+  int64_t src = 0, dst = 0;
   for (int l = 0; l < s.L; ++l) {
-    const int in = l == 0 ? s.K0 : s.Hp;
-    if (woff) woff[l] = o;
-    o += (int64_t)s.NT * in * 16;
-    if (boff) boff[l] = o;
-    o += s.Hp;
+    const int64_t in = l == 0 ? s.k : s.H, inp = l == 0 ? s.K0 : s.Hp;
+    if (p) {
+      p->src_w[l] = src;
+      p->src_b[l] = src + s.H * in;
+      p->dst_w[l] = dst;
+      p->dst_b[l] = dst + s.NT * inp * 16;
+    }
+    src += s.H * in + s.H;
+    dst += s.NT * inp * 16 + s.Hp;
   }
-  return o;
+  return dst;
 }
+
 
 struct MlpTopkGeom {
   int cap, splits, per;
@@ -420,16 +354,8 @@ inline MlpTopkGeom mlp_topk_geom(const MlpShape &s, int U, int N, int K) {
 // packed weights, then the partial lists uint64 [U, splits, K]: U * splits <= U * ceil(budget / U) < U + budget
 inline int64_t mlp_topk_ws_bytes(const MlpShape &s, int U, int N, int K) {
   const int64_t parts = std::min<int64_t>((int64_t)U * tm_max_splits(s, N), (int64_t)U + TM_TILE_BUDGET);
-  return mlp_packed_floats(s, nullptr, nullptr) * 4 + parts * K * 8;
+  return mlp_packed_floats(s, nullptr) * 4 + parts * K * 8;
 }
-
-struct MlpPackArgs {
-  const float *params;
-  float *packed;
-  long long src_w[TM_MAX_L], src_b[TM_MAX_L], dst_w[TM_MAX_L], dst_b[TM_MAX_L];
-  long long total;
-  int k, H, L, K0, Hp, NT;
-};
 
 // one thread per packed float
 __global__ __launch_bounds__(256) void k_mlp_topk_pack(MlpPackArgs a) {
@@ -574,29 +500,72 @@ __global__ __launch_bounds__(256) void k_mlp_topk_scan(MlpTopkArgs a) {
   else
     emit(s, 0, a.cap, a.K, nullptr, a.top_pos + (size_t)u * a.K, a.top_score + (size_t)u * a.K);
 }
-
+// ---------------------------------------------------------------------------------------------------------------------
+// host side of both entry points
+// ---------------------------------------------------------------------------------------------------------------------
+constexpr size_t slots_lds(int n, int cap) { return (size_t)n * cap * 8 + (size_t)n * 8 + (size_t)n * 4; }
 size_t mlp_topk_lds(const MlpShape &s, int cap) { return (size_t)TM_ROWS * std::max(s.K0, s.Hp) * 4 + slots_lds(1, cap); }
 
-template <int WC, int NCT>
-int launch_mlp_topk_scan(const MlpTopkArgs &a, dim3 grid, size_t lds, hipStream_t st) {
-  static const bool raised = [] {  // 64 KiB of activations at hidden = 256 + the slot: above the default dynamic LDS limit
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_mlp_topk_scan<WC, NCT>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                              80 * 1024);
+// A launch of one of the slot kernels (256 threads).  The scans hold 64 KiB of keys or of activations plus a slot, above the
+// default dynamic LDS limit, so every slot kernel's limit is raised to 80 KiB on its first launch.
+template <auto Kernel, class Args>
+int launch_slots(const char *name, dim3 grid, size_t lds, hipStream_t st, const Args &a) {
+  static const bool raised = [] {
+    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
     return true;
   }();
   (void)raised;
-  hipLaunchKernelGGL((k_mlp_topk_scan<WC, NCT>), grid, dim3(256), lds, st, a);
-  return check_launch("k_mlp_topk_scan");
+  hipLaunchKernelGGL(Kernel, grid, dim3(TK_THREADS), lds, st, a);
+  return check_launch(name);
 }
 
-int check_mlp_topk_sizes(const fmx_mlp_t *mlp, int32_t U, int32_t N, int32_t K) {
-  if (!mlp) return fail(FMX_ERR_ARG, "fmx_mlp_topk: null mlp");
-  if (U < 1 || N < 1) return fail(FMX_ERR_ARG, "fmx_mlp_topk: U=%d and N=%d must be >= 1", U, N);
-  if (K < 1) return fail(FMX_ERR_ARG, "fmx_mlp_topk: K=%d must be >= 1", K);
-  if (K > TK_MAX_K) return fail(FMX_ERR_UNSUPPORTED, "fmx_mlp_topk: K=%d, the kernels cover K <= %d", K, TK_MAX_K);
+// The merge of either scan's partial lists uint64 [U, splits, K] into the final rows; nothing to do for one split.  It reads
+// the partial keys, K, the slot capacity, the splits and the outputs only.
+int merge_topk(uint64_t *parts, int32_t *top_pos, float *top_score, int32_t U, int32_t K, int splits, hipStream_t st) {
+  if (splits == 1) return FMX_OK;
+  TopkArgs m{};
+  m.parts = parts;
+  m.top_pos = top_pos;
+  m.top_score = top_score;
+  m.U = U;
+  m.K = K;
+  m.cap = topk_cap(K);
+  m.splits = splits;
+  return launch_slots<k_topk_merge>("k_topk_merge", dim3(U), slots_lds(1, m.cap), st, m);
+}
+
+int check_topk_sizes(const char *fn, int32_t U, int32_t N, int32_t K) {
+  if (U < 1 || N < 1) return fail(FMX_ERR_ARG, "%s: U=%d and N=%d must be >= 1", fn, U, N);
+  if (K < 1) return fail(FMX_ERR_ARG, "%s: K=%d must be >= 1", fn, K);
+  if (K > TK_MAX_K) return fail(FMX_ERR_UNSUPPORTED, "%s: K=%d, the kernels cover K <= %d", fn, K, TK_MAX_K);
+  return FMX_OK;
+}
+
+int check_network(const fmx_mlp_t *mlp) {
   if (mlp->n_layers < 1 || mlp->n_layers > TM_MAX_L || mlp->hidden < 1 || mlp->hidden > TM_MAX_H || mlp->k < 1 || mlp->k > 64)
     return fail(FMX_ERR_UNSUPPORTED, "fmx_mlp_topk: needs 1 <= layers <= %d, 1 <= hidden <= %d, 1 <= k <= 64 (got %d, %d, %d)", TM_MAX_L,
                 TM_MAX_H, mlp->n_layers, mlp->hidden, mlp->k);
+  return FMX_OK;
+}
+
+// The checks both entry points make, in this order.  A kp outside 4/8/16/32/64 returns bad_kp (include/fmx.h: FMX_ERR_SHAPE
+// from fmx_fm_topk, FMX_ERR_UNSUPPORTED from fmx_mlp_topk).  net: fmx_mlp_topk's checked network, null for fmx_fm_topk.
+int check_topk_args(const char *fn, int bad_kp, const MlpShape *net, const float *Su, int32_t ld_u, const float *au, int32_t U,
+                    const float *Sc, int32_t ld_c, const float *ac, int32_t N, int32_t kp, const int32_t *excl_off,
+                    const int32_t *excl_pos, int32_t K, const void *ws, int64_t ws_bytes, const int32_t *top_pos,
+                    const float *top_score) {
+  if (!Su || !au || !Sc || !ac || !ws || !top_pos || !top_score) return fail(FMX_ERR_ARG, "%s: null argument", fn);
+  if ((excl_off == nullptr) != (excl_pos == nullptr)) return fail(FMX_ERR_ARG, "%s: excl_offsets and excl_pos go together", fn);
+  if (int rc = check_topk_sizes(fn, U, N, K)) return rc;
+  if (kp != 4 && kp != 8 && kp != 16 && kp != 32 && kp != 64) return fail(bad_kp, "%s: kp=%d must be 4/8/16/32/64", fn, kp);
+  if (ld_u < kp || ld_c < kp || ld_u % 4 || ld_c % 4)
+    return fail(FMX_ERR_SHAPE, "%s: ld_u=%d and ld_c=%d must be multiples of 4 and >= kp=%d", fn, ld_u, ld_c, kp);
+  if (!aligned16(Su) || !aligned16(Sc) || !aligned16(ws))
+    return fail(FMX_ERR_ALIGN, "%s: Su, Sc and the workspace must be 16-byte aligned", fn);
+  const int64_t need = net ? mlp_topk_ws_bytes(*net, U, N, K) : topk_ws_bytes(U, N, K);
+  if (ws_bytes < need)
+    return fail(FMX_ERR_SHAPE, "%s: workspace of %lld bytes, %s_workspace_bytes(%s%d, %d, %d) = %lld", fn, (long long)ws_bytes, fn,
+                net ? "mlp, " : "", U, N, K, (long long)need);
   return FMX_OK;
 }
 
@@ -604,114 +573,85 @@ int check_mlp_topk_sizes(const fmx_mlp_t *mlp, int32_t U, int32_t N, int32_t K) 
 
 extern "C" {
 
+int64_t fmx_fm_topk_workspace_bytes(int32_t U, int32_t N, int32_t K) {
+  if (int rc = check_topk_sizes("fmx_fm_topk", U, N, K)) return rc;
+  return topk_ws_bytes(U, N, K);
+}
+
 int64_t fmx_mlp_topk_workspace_bytes(const fmx_mlp_t *mlp, int32_t U, int32_t N, int32_t K) {
-  if (int rc = check_mlp_topk_sizes(mlp, U, N, K)) return rc;
+  if (!mlp) return fail(FMX_ERR_ARG, "fmx_mlp_topk: null mlp");
+  if (int rc = check_topk_sizes("fmx_mlp_topk", U, N, K)) return rc;
+  if (int rc = check_network(mlp)) return rc;
   return mlp_topk_ws_bytes(mlp_shape(mlp), U, N, K);
+}
+
+int fmx_fm_topk(const float *Su, int32_t ld_u, const float *au, int32_t U, const float *Sc, int32_t ld_c, const float *ac, int32_t N,
+                int32_t kp, const int32_t *excl_offsets, const int32_t *excl_pos, int32_t K, void *workspace, int64_t workspace_bytes,
+                int32_t *top_pos, float *top_score, fmx_stream_t stream) {
+  if (int rc = check_topk_args("fmx_fm_topk", FMX_ERR_SHAPE, nullptr, Su, ld_u, au, U, Sc, ld_c, ac, N, kp, excl_offsets, excl_pos, K,
+                               workspace, workspace_bytes, top_pos, top_score))
+    return rc;
+  const TopkGeom g = topk_geom(U, N, K);
+  const TopkArgs a{Su, au, Sc, ac,
+                   excl_offsets, excl_pos,
+                   static_cast<uint64_t *>(workspace),
+                   top_pos, top_score,
+                   ld_u, ld_c, U, N, K, g.ut, g.cap, g.splits, g.per};
+  const hipStream_t st = static_cast<hipStream_t>(stream);
+  const dim3 grid(g.tiles, g.splits);
+  const size_t lds = slots_lds(g.ut, g.cap);
+  int rc;
+  switch (kp) {
+    case 4: rc = launch_slots<k_topk_scan<4>>("k_topk_scan", grid, lds, st, a); break;
+    case 8: rc = launch_slots<k_topk_scan<8>>("k_topk_scan", grid, lds, st, a); break;
+    case 16: rc = launch_slots<k_topk_scan<16>>("k_topk_scan", grid, lds, st, a); break;
+    case 32: rc = launch_slots<k_topk_scan<32>>("k_topk_scan", grid, lds, st, a); break;
+    default: rc = launch_slots<k_topk_scan<64>>("k_topk_scan", grid, lds, st, a); break;
+  }
+  return rc ? rc : merge_topk(a.parts, top_pos, top_score, U, K, g.splits, st);
 }
 
 int fmx_mlp_topk(const fmx_mlp_t *mlp, int32_t fm_term, const float *Su, const float *Bu, int32_t ld_u, const float *au, int32_t U,
                  const float *Sc, const float *Bc, int32_t ld_c, const float *ac, int32_t N, int32_t kp, const int32_t *excl_offsets,
                  const int32_t *excl_pos, int32_t K, void *workspace, int64_t workspace_bytes, int32_t *top_pos, float *top_score,
                  fmx_stream_t stream) {
-  if (!mlp || !mlp->params || !Su || !Bu || !au || !Sc || !Bc || !ac || !workspace || !top_pos || !top_score)
-    return fail(FMX_ERR_ARG, "fmx_mlp_topk: null argument");
-  if ((excl_offsets == nullptr) != (excl_pos == nullptr))
-    return fail(FMX_ERR_ARG, "fmx_mlp_topk: excl_offsets and excl_pos go together");
+  if (!mlp || !mlp->params || !Bu || !Bc) return fail(FMX_ERR_ARG, "fmx_mlp_topk: null argument");
   if (fm_term != 0 && fm_term != 1) return fail(FMX_ERR_ARG, "fmx_mlp_topk: fm_term=%d must be 0 or 1", fm_term);
-  if (int rc = check_mlp_topk_sizes(mlp, U, N, K)) return rc;
-  if (kp != 4 && kp != 8 && kp != 16 && kp != 32 && kp != 64) return fail(FMX_ERR_UNSUPPORTED, "fmx_mlp_topk: kp=%d must be 4/8/16/32/64", kp);
+  if (int rc = check_network(mlp)) return rc;
   if (mlp->k > kp) return fail(FMX_ERR_UNSUPPORTED, "fmx_mlp_topk: k=%d exceeds kp=%d", mlp->k, kp);
-  if (ld_u < kp || ld_c < kp || ld_u % 4 || ld_c % 4)
-    return fail(FMX_ERR_SHAPE, "fmx_mlp_topk: ld_u=%d and ld_c=%d must be multiples of 4 and >= kp=%d", ld_u, ld_c, kp);
-  if (!aligned16(Su) || !aligned16(Bu) || !aligned16(Sc) || !aligned16(Bc) || !aligned16(workspace))
-    return fail(FMX_ERR_ALIGN, "fmx_mlp_topk: Su, Bu, Sc, Bc and the workspace must be 16-byte aligned");
   const MlpShape sh = mlp_shape(mlp);
-  const int64_t need = mlp_topk_ws_bytes(sh, U, N, K);
-  if (workspace_bytes < need)
-    return fail(FMX_ERR_SHAPE, "fmx_mlp_topk: workspace of %lld bytes, fmx_mlp_topk_workspace_bytes(mlp, %d, %d, %d) = %lld",
-                (long long)workspace_bytes, U, N, K, (long long)need);
+  if (int rc = check_topk_args("fmx_mlp_topk", FMX_ERR_UNSUPPORTED, &sh, Su, ld_u, au, U, Sc, ld_c, ac, N, kp, excl_offsets, excl_pos,
+                               K, workspace, workspace_bytes, top_pos, top_score))
+    return rc;
+  if (!aligned16(Bu) || !aligned16(Bc)) return fail(FMX_ERR_ALIGN, "fmx_mlp_topk: Bu and Bc must be 16-byte aligned");
   const MlpTopkGeom g = mlp_topk_geom(sh, U, N, K);
-  int64_t woff[TM_MAX_L], boff[TM_MAX_L];
-  const int64_t packed_n = mlp_packed_floats(sh, woff, boff);
-  float *packed = static_cast<float *>(workspace);
-  MlpPackArgs p;
-  p.params = mlp->params;
-  p.packed = packed;
-  int64_t src = 0;
-  for (int l = 0; l < sh.L; ++l) {
-    const int in = l == 0 ? sh.k : sh.H;
-    p.src_w[l] = src;
-    p.src_b[l] = src + (int64_t)sh.H * in;
-    src = p.src_b[l] + sh.H;
-    p.dst_w[l] = woff[l];
-    p.dst_b[l] = boff[l];
-  }
-  p.total = packed_n;
-  p.k = sh.k;
-  p.H = sh.H;
-  p.L = sh.L;
-  p.K0 = sh.K0;
-  p.Hp = sh.Hp;
-  p.NT = sh.NT;
-  MlpTopkArgs a;
-  a.Su = Su;
-  a.Bu = Bu;
-  a.au = au;
-  a.Sc = Sc;
-  a.Bc = Bc;
-  a.ac = ac;
-  a.excl_off = excl_offsets;
-  a.excl_pos = excl_pos;
-  a.packed = packed;
-  for (int l = 0; l < sh.L; ++l) {
-    a.woff[l] = woff[l];
-    a.boff[l] = boff[l];
-  }
-  a.parts = reinterpret_cast<uint64_t *>(packed + packed_n);
-  a.top_pos = top_pos;
-  a.top_score = top_score;
-  a.ld_u = ld_u;
-  a.ld_c = ld_c;
-  a.U = U;
-  a.N = N;
-  a.K = K;
-  a.kp = kp;
-  a.k = sh.k;
-  a.H = sh.H;
-  a.L = sh.L;
-  a.K0 = sh.K0;
-  a.Hp = sh.Hp;
-  a.fm_term = fm_term;
-  a.cap = g.cap;
-  a.splits = g.splits;
-  a.per = g.per;
+  MlpPackArgs p{mlp->params, static_cast<float *>(workspace), {}, {}, {}, {}, 0, sh.k, sh.H, sh.L, sh.K0, sh.Hp, sh.NT};
+  p.total = mlp_packed_floats(sh, &p);
+  MlpTopkArgs a{Su, Bu, au, Sc, Bc, ac,
+                excl_offsets, excl_pos,
+                p.packed,
+                {}, {},
+                reinterpret_cast<uint64_t *>(p.packed + p.total),
+                top_pos, top_score,
+                ld_u, ld_c, U, N, K, kp, sh.k, sh.H, sh.L, sh.K0, sh.Hp, fm_term, g.cap, g.splits, g.per};
+  std::copy(p.dst_w, p.dst_w + sh.L, a.woff);
+  std::copy(p.dst_b, p.dst_b + sh.L, a.boff);
   const hipStream_t st = static_cast<hipStream_t>(stream);
-  hipLaunchKernelGGL(k_mlp_topk_pack, dim3((unsigned)((packed_n + 255) / 256)), dim3(256), 0, st, p);
+  hipLaunchKernelGGL(k_mlp_topk_pack, dim3((unsigned)((p.total + 255) / 256)), dim3(256), 0, st, p);
   if (int rc = check_launch("k_mlp_topk_pack")) return rc;
   const dim3 grid(U, g.splits);
   const size_t lds = mlp_topk_lds(sh, g.cap);
   int rc;
   switch (sh.NT) {
-    case 1: rc = launch_mlp_topk_scan<1, 1>(a, grid, lds, st); break;
-    case 2: rc = launch_mlp_topk_scan<2, 1>(a, grid, lds, st); break;
-    case 3: rc = launch_mlp_topk_scan<2, 2>(a, grid, lds, st); break;
-    case 4: rc = launch_mlp_topk_scan<4, 1>(a, grid, lds, st); break;
-    case 5: case 6: case 7: case 8: rc = launch_mlp_topk_scan<4, 2>(a, grid, lds, st); break;
-    case 9: case 10: case 11: case 12: rc = launch_mlp_topk_scan<4, 3>(a, grid, lds, st); break;
-    default: rc = launch_mlp_topk_scan<4, 4>(a, grid, lds, st); break;
+    case 1: rc = launch_slots<k_mlp_topk_scan<1, 1>>("k_mlp_topk_scan", grid, lds, st, a); break;
+    case 2: rc = launch_slots<k_mlp_topk_scan<2, 1>>("k_mlp_topk_scan", grid, lds, st, a); break;
+    case 3: rc = launch_slots<k_mlp_topk_scan<2, 2>>("k_mlp_topk_scan", grid, lds, st, a); break;
+    case 4: rc = launch_slots<k_mlp_topk_scan<4, 1>>("k_mlp_topk_scan", grid, lds, st, a); break;
+    case 5: case 6: case 7: case 8: rc = launch_slots<k_mlp_topk_scan<4, 2>>("k_mlp_topk_scan", grid, lds, st, a); break;
+    case 9: case 10: case 11: case 12: rc = launch_slots<k_mlp_topk_scan<4, 3>>("k_mlp_topk_scan", grid, lds, st, a); break;
+    default: rc = launch_slots<k_mlp_topk_scan<4, 4>>("k_mlp_topk_scan", grid, lds, st, a); break;
   }
-  if (rc || g.splits == 1) return rc;
-  TopkArgs m{};  // the merge of fmx_fm_topk: it reads the partial keys, the sizes and the outputs only
-  m.parts = a.parts;
-  m.top_pos = top_pos;
-  m.top_score = top_score;
-  m.U = U;
-  m.N = N;
-  m.K = K;
-  m.cap = K <= 128 ? 512 : 1024;
-  m.splits = g.splits;
-  hipLaunchKernelGGL(k_topk_merge, dim3(U), dim3(TK_THREADS), slots_lds(1, m.cap), st, m);
-  return check_launch("k_topk_merge");
+  return rc ? rc : merge_topk(a.parts, top_pos, top_score, U, K, g.splits, st);
 }
 
 }  // extern "C"

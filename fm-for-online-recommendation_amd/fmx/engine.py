@@ -39,6 +39,11 @@ def _ptr(t):
     return None if t is None else t.data_ptr()
 
 
+def mlp_struct(params, k, hidden, n_layers):
+    """The fmx_mlp_t of a network whose flat fp32 device buffer `params` holds W_l [hidden, in_l] then b_l per layer."""
+    return _lib.Mlp(params.data_ptr(), int(n_layers), int(k), int(hidden), 0)
+
+
 class HandOffTimeout(RuntimeError):
     """Device error word 2 (k_fm_update: a crossing run's row update was skipped): an in-launch hand-off ran into its spin
     bound.  Never observed; the table must be considered corrupt."""
@@ -265,8 +270,7 @@ class FMEngine:
             return ok and k + n_layers <= 64
         return ok and k <= 64
 
-    def _mlp_struct(self, params, k, hidden, n_layers):
-        return _lib.Mlp(params.data_ptr(), n_layers, k, hidden, 0)
+    _mlp_struct = staticmethod(mlp_struct)
 
     def mlp_forward(self, params, k, hidden, n_layers, base, B, want_layers):
         out = torch.empty(B, dtype=torch.float32, device=self.device)

@@ -21,7 +21,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .engine import Hyper
+from .engine import Hyper, _ptr, mlp_struct
 
 CHUNK = 65536   # rows per forward launch of the side computations
 
@@ -60,62 +60,50 @@ def _masked_side(table, idx, xv, keep_fields):
     return idx, xv
 
 
-def side_sums(table, idx, xv, keep_fields, hyper=None, want_bias=True):
+def _side_pass(table, idx, xv, keep_fields, hyper, outputs, after_chunk=None):
     """fmx_fm_forward over the rows of idx / xv ([R, F], full width) with every field outside keep_fields given index 0 and
-    value 0.  Returns (S [R, kp], a [R]) on the device: a = the logit (bias included) when want_bias, else sfirst + sbi.
-    An index outside its field (in a kept column) raises IndexError."""
+    value 0, CHUNK rows per launch, writing only the FwdOut outputs named in `outputs` (S, bi [R, kp]; sfirst, sbi, logit
+    [R]).  Returns those device tensors in that order; after_chunk(out, r0, B), given the dict of them, runs after the launch
+    of rows r0 .. r0 + B - 1.  An index outside its field (in a kept column) raises IndexError."""
     dev, kp = table.device, table.kp
     idx, xv = _masked_side(table, idx, xv, keep_fields)
     R = idx.shape[0]
     lib, h = _lib.load(), _hyper_for(table, hyper)
-    S = torch.empty((R, kp), dtype=torch.float32, device=dev)
-    a = torch.empty(R, dtype=torch.float32, device=dev)
-    n = min(R, CHUNK)
-    sfirst = torch.empty(n, dtype=torch.float32, device=dev)
-    sbi = torch.empty(n, dtype=torch.float32, device=dev)
+    out = {n: torch.empty((R, kp) if n in ("S", "bi") else R, dtype=torch.float32, device=dev) for n in outputs}
     error = torch.zeros(1, dtype=torch.int32, device=dev)
     stream = torch.cuda.current_stream(dev).cuda_stream
     for r0 in range(0, R, CHUNK):
         B = min(CHUNK, R - r0)
-        o = _lib.FwdOut()
-        o.S = S[r0:].data_ptr()
-        if want_bias:
-            o.logit = a[r0:].data_ptr()
-        else:
-            o.sfirst, o.sbi = sfirst.data_ptr(), sbi.data_ptr()
-        o.error = error.data_ptr()
+        o = _lib.FwdOut(error=error.data_ptr(), **{n: t[r0:].data_ptr() for n, t in out.items()})
         _lib.check(lib.fmx_fm_forward(table.c_struct(), h.ref(), idx[r0:].data_ptr(), xv[r0:].data_ptr(), None, B,
                                       _lib.LOSS_NONE, 1.0, C.byref(o), stream))
-        if not want_bias:
-            torch.add(sfirst[:B], sbi[:B], out=a[r0:r0 + B])
+        if after_chunk is not None:
+            after_chunk(out, r0, B)
     if int(error.item()) != 0:
         raise IndexError("index out of range in self (flagged by the fmx kernels)")
+    return tuple(out[n] for n in outputs)
+
+
+def _add_first_terms(out, r0, B):
+    """sfirst += sbi over rows r0 .. r0 + B - 1: side_sums' a without the bias."""
+    rows = slice(r0, r0 + B)
+    torch.add(out["sfirst"][rows], out["sbi"][rows], out=out["sfirst"][rows])
+
+
+def side_sums(table, idx, xv, keep_fields, hyper=None, want_bias=True):
+    """fmx_fm_forward over the rows of idx / xv ([R, F], full width) with every field outside keep_fields given index 0 and
+    value 0.  Returns (S [R, kp], a [R]) on the device: a = the logit (bias included) when want_bias, else sfirst + sbi.
+    An index outside its field (in a kept column) raises IndexError."""
+    if want_bias:
+        return _side_pass(table, idx, xv, keep_fields, hyper, ("S", "logit"))
+    S, a, _ = _side_pass(table, idx, xv, keep_fields, hyper, ("S", "sfirst", "sbi"), _add_first_terms)
     return S, a
 
 
 def side_terms(table, idx, xv, keep_fields, hyper=None):
     """As side_sums, but everything the network classes need from the one fmx_fm_forward call per chunk: returns device
     tensors (S [R, kp], bi [R, kp], sfirst [R], sbi [R], logit [R]) of the masked rows (logit = sfirst + sbi + bias)."""
-    dev, kp = table.device, table.kp
-    idx, xv = _masked_side(table, idx, xv, keep_fields)
-    R = idx.shape[0]
-    lib, h = _lib.load(), _hyper_for(table, hyper)
-    S = torch.empty((R, kp), dtype=torch.float32, device=dev)
-    bi = torch.empty((R, kp), dtype=torch.float32, device=dev)
-    sfirst, sbi, logit = (torch.empty(R, dtype=torch.float32, device=dev) for _ in range(3))
-    error = torch.zeros(1, dtype=torch.int32, device=dev)
-    stream = torch.cuda.current_stream(dev).cuda_stream
-    for r0 in range(0, R, CHUNK):
-        B = min(CHUNK, R - r0)
-        o = _lib.FwdOut()
-        o.S, o.bi = S[r0:].data_ptr(), bi[r0:].data_ptr()
-        o.sfirst, o.sbi, o.logit = sfirst[r0:].data_ptr(), sbi[r0:].data_ptr(), logit[r0:].data_ptr()
-        o.error = error.data_ptr()
-        _lib.check(lib.fmx_fm_forward(table.c_struct(), h.ref(), idx[r0:].data_ptr(), xv[r0:].data_ptr(), None, B,
-                                      _lib.LOSS_NONE, 1.0, C.byref(o), stream))
-    if int(error.item()) != 0:
-        raise IndexError("index out of range in self (flagged by the fmx kernels)")
-    return S, bi, sfirst, sbi, logit
+    return _side_pass(table, idx, xv, keep_fields, hyper, ("S", "bi", "sfirst", "sbi", "logit"))
 
 
 def network_bases(table, sfirst, sbi, logit, fm_term, context):
@@ -189,35 +177,51 @@ def exclusions_csr(exclude, U, device):
     return torch.from_numpy(off).to(device), torch.from_numpy(pos).to(device)
 
 
-def fm_topk(Su, au, Sc, ac, K, excl_offsets=None, excl_pos=None, workspace=None, out=None, stream=None, kp=None):
-    """The raw call: Su [U, >= kp], au [U], Sc [N, >= kp], ac [N] fp32 device tensors (row strides multiples of 4, 16-byte
-    aligned); kp defaults to Sc's width.  Returns (top_pos int32 [U, K], top_score fp32 [U, K]) on the device."""
-    U, N = Su.shape[0], Sc.shape[0]
-    kp = Sc.shape[1] if kp is None else int(kp)
-    lib, dev = _lib.load(), Su.device
-    need = int(lib.fmx_fm_topk_workspace_bytes(U, N, K))
+def _call_buffers(need, U, K, dev, workspace, out, stream):
+    """What the raw calls share: `need` workspace bytes (a *_workspace_bytes result; a negative one raises), a workspace
+    allocated when the given one is missing or short, the outputs when not given, the stream.  Returns (workspace pointer,
+    workspace bytes, out, stream)."""
+    need = int(need)
     _lib.check(min(need, 0))
     if workspace is None or workspace.numel() * workspace.element_size() < need:
         workspace = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
     if out is None:
         out = (torch.empty((U, K), dtype=torch.int32, device=dev), torch.empty((U, K), dtype=torch.float32, device=dev))
     st = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
+    return workspace.data_ptr(), workspace.numel() * workspace.element_size(), out, st
+
+
+def fm_topk(Su, au, Sc, ac, K, excl_offsets=None, excl_pos=None, workspace=None, out=None, stream=None, kp=None):
+    """The raw call: Su [U, >= kp], au [U], Sc [N, >= kp], ac [N] fp32 device tensors (row strides multiples of 4, 16-byte
+    aligned); kp defaults to Sc's width.  Returns (top_pos int32 [U, K], top_score fp32 [U, K]) on the device."""
+    U, N = Su.shape[0], Sc.shape[0]
+    kp = Sc.shape[1] if kp is None else int(kp)
+    lib = _lib.load()
+    ws, ws_n, out, st = _call_buffers(lib.fmx_fm_topk_workspace_bytes(U, N, K), U, K, Su.device, workspace, out, stream)
     _lib.check(lib.fmx_fm_topk(Su.data_ptr(), Su.stride(0), au.data_ptr(), U, Sc.data_ptr(), Sc.stride(0), ac.data_ptr(), N, kp,
-                               None if excl_offsets is None else excl_offsets.data_ptr(),
-                               None if excl_pos is None else excl_pos.data_ptr(), K, workspace.data_ptr(),
-                               workspace.numel() * workspace.element_size(), out[0].data_ptr(), out[1].data_ptr(), st))
+                               _ptr(excl_offsets), _ptr(excl_pos), K, ws, ws_n, out[0].data_ptr(), out[1].data_ptr(), st))
     return out
+
+
+def _context_side(table, candidates, ctx_idx, ctx_xv, exclude, hyper, side, fm_term=None):
+    """What topk and topk_network share before the selection: the candidates' check (fm_term: the network's, None for the
+    FM), side(table, ctx_idx, ctx_xv, context fields, hyper) over the fields that are not item fields, whose first result
+    has a row per context, and the exclusions.  Returns (side's results, exclusion offsets, exclusion positions)."""
+    if candidates.table is not table:
+        raise ValueError("candidates were computed for another table")
+    if fm_term is not None and (not isinstance(candidates, NetworkCandidates) or candidates.fm_term != int(fm_term)):
+        raise ValueError(f"candidates: a NetworkCandidates with fm_term={int(fm_term)}")
+    ctx_fields = [f for f in range(table.n_fields) if f not in candidates.item_fields]
+    sides = side(table, ctx_idx, ctx_xv, ctx_fields, hyper if hyper is not None else candidates.hyper)
+    off, pos = exclusions_csr(exclude, sides[0].shape[0], table.device)
+    return sides, off, pos
 
 
 def topk(table, ctx_idx, ctx_xv, candidates, K, exclude=None, hyper=None):
     """Top-K candidates for every context row of ctx_idx / ctx_xv ([U, F] full width, the item columns ignored).  Returns
     device tensors (positions int64 [U, K], -1 padded; logits fp32 [U, K], -inf padded), each row by logit descending, then
     position ascending.  exclude: see exclusions_csr."""
-    if candidates.table is not table:
-        raise ValueError("candidates were computed for another table")
-    ctx_fields = [f for f in range(table.n_fields) if f not in candidates.item_fields]
-    Su, au = side_sums(table, ctx_idx, ctx_xv, ctx_fields, hyper if hyper is not None else candidates.hyper, want_bias=True)
-    off, pos = exclusions_csr(exclude, Su.shape[0], table.device)
+    (Su, au), off, pos = _context_side(table, candidates, ctx_idx, ctx_xv, exclude, hyper, side_sums)
     top_pos, top_score = fm_topk(Su, au, candidates.Sc, candidates.ac, int(K), off, pos)
     return top_pos.long(), top_score
 
@@ -231,7 +235,7 @@ def _mlp_struct(mlp):
     params, k, hidden, n_layers = mlp
     if params.dtype != torch.float32 or not params.is_contiguous():
         raise ValueError("mlp params: a contiguous fp32 device tensor (W_l [hidden, in_l] then b_l per layer)")
-    return _lib.Mlp(params.data_ptr(), int(n_layers), int(k), int(hidden), 0)
+    return mlp_struct(params, k, hidden, n_layers)
 
 
 def mlp_topk(mlp, fm_term, Su, Bu, au, Sc, Bc, ac, K, excl_offsets=None, excl_pos=None, workspace=None, out=None, stream=None,
@@ -243,20 +247,12 @@ def mlp_topk(mlp, fm_term, Su, Bu, au, Sc, Bc, ac, K, excl_offsets=None, excl_po
     kp = Sc.shape[1] if kp is None else int(kp)
     if Bu.stride(0) != Su.stride(0) or Bc.stride(0) != Sc.stride(0):
         raise ValueError("Bu / Bc must share the row strides of Su / Sc")
-    lib, dev = _lib.load(), Su.device
-    m = _mlp_struct(mlp)
-    need = int(lib.fmx_mlp_topk_workspace_bytes(C.byref(m), U, N, K))
-    _lib.check(min(need, 0))
-    if workspace is None or workspace.numel() * workspace.element_size() < need:
-        workspace = torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
-    if out is None:
-        out = (torch.empty((U, K), dtype=torch.int32, device=dev), torch.empty((U, K), dtype=torch.float32, device=dev))
-    st = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
+    lib, m = _lib.load(), _mlp_struct(mlp)
+    ws, ws_n, out, st = _call_buffers(lib.fmx_mlp_topk_workspace_bytes(C.byref(m), U, N, K), U, K, Su.device, workspace, out,
+                                      stream)
     _lib.check(lib.fmx_mlp_topk(C.byref(m), int(fm_term), Su.data_ptr(), Bu.data_ptr(), Su.stride(0), au.data_ptr(), U,
-                                Sc.data_ptr(), Bc.data_ptr(), Sc.stride(0), ac.data_ptr(), N, kp,
-                                None if excl_offsets is None else excl_offsets.data_ptr(),
-                                None if excl_pos is None else excl_pos.data_ptr(), K, workspace.data_ptr(),
-                                workspace.numel() * workspace.element_size(), out[0].data_ptr(), out[1].data_ptr(), st))
+                                Sc.data_ptr(), Bc.data_ptr(), Sc.stride(0), ac.data_ptr(), N, kp, _ptr(excl_offsets),
+                                _ptr(excl_pos), K, ws, ws_n, out[0].data_ptr(), out[1].data_ptr(), st))
     return out
 
 
@@ -325,15 +321,11 @@ def topk_network(table, mlp, fm_term, ctx_idx, ctx_xv, candidates, K, exclude=No
     k, hidden, n_layers): the logit of the combined sample for the Adam classes, the logit whose sigmoid forward() returns
     for the ONN classes.  candidates: a NetworkCandidates of the same table and fm_term.  Returns device tensors (positions
     int64 [U, K], -1 padded; scores fp32 [U, K], -inf padded), each row by score descending, then position ascending."""
-    if candidates.table is not table:
-        raise ValueError("candidates were computed for another table")
-    if not isinstance(candidates, NetworkCandidates) or candidates.fm_term != int(fm_term):
-        raise ValueError(f"candidates: a NetworkCandidates with fm_term={int(fm_term)}")
-    ctx_fields = [f for f in range(table.n_fields) if f not in candidates.item_fields]
-    S, bi, sfirst, sbi, logit = side_terms(table, ctx_idx, ctx_xv, ctx_fields,
-                                           hyper if hyper is not None else candidates.hyper)
-    au = network_bases(table, sfirst, sbi, logit, fm_term, context=True).contiguous()
-    off, pos = exclusions_csr(exclude, S.shape[0], table.device)
+    def side(table, idx, xv, fields, hyper):
+        S, bi, sfirst, sbi, logit = side_terms(table, idx, xv, fields, hyper)
+        return S, bi, network_bases(table, sfirst, sbi, logit, fm_term, context=True).contiguous()
+
+    (S, bi, au), off, pos = _context_side(table, candidates, ctx_idx, ctx_xv, exclude, hyper, side, fm_term)
     K = int(K)
     args = (mlp, fm_term, S, bi, au, candidates.Sc, candidates.Bc, candidates.ac, K, off, pos)
     if mlp_kernel_takes(mlp) or not 1 <= K <= MLP_TOPK_MAX_K:     # the kernel's checks raise on a bad K

@@ -477,15 +477,15 @@ class OnlineFMBase(nn.Module):
             cand_xv = None
         else:
             cand_idx, cand_xv = candidates
+        rec, t, h = fmx.recommend, self._table, self._hyper
         if self._has_mlp:
             fm_term = 1 if self._fm_term_in_forward else 0
             mlp = (self._mlp_flat, self.embedding_size, self.neuron_per_hidden_layer, self.num_hidden_layers)
-            cands = fmx.recommend.NetworkCandidates(self._table, item_fields, cand_idx, cand_xv, fm_term=fm_term, hyper=self._hyper)
-            pos, logit = fmx.recommend.topk_network(self._table, mlp, fm_term, Xi, Xv, cands, K, exclude=exclude,
-                                                    hyper=self._hyper)
-            return pos.cpu().numpy(), logit.cpu().numpy()
-        cands = fmx.recommend.Candidates(self._table, item_fields, cand_idx, cand_xv, hyper=self._hyper)
-        pos, logit = fmx.recommend.topk(self._table, Xi, Xv, cands, K, exclude=exclude, hyper=self._hyper)
+            cands = rec.NetworkCandidates(t, item_fields, cand_idx, cand_xv, fm_term=fm_term, hyper=h)
+            pos, logit = rec.topk_network(t, mlp, fm_term, Xi, Xv, cands, K, exclude=exclude, hyper=h)
+        else:
+            cands = rec.Candidates(t, item_fields, cand_idx, cand_xv, hyper=h)
+            pos, logit = rec.topk(t, Xi, Xv, cands, K, exclude=exclude, hyper=h)
         return pos.cpu().numpy(), logit.cpu().numpy()
 
     def _device_loop_ok(self):
