@@ -145,6 +145,45 @@ __device__ __forceinline__ float4 apply_rule4(float4 p, float4 g, const fmx_hype
           apply_rule<RULE>(p.w, g.w, h)};
 }
 
+// ---- the persistent adaptive rules (FMX_LAYOUT_MOMENTS).  On the device h.lr holds the step's step size (ADAM: lr sqrt(1 -
+//      beta2^t) / (1 - beta1^t), ADAGRAD: lr), h.beta1 / h.beta2 hold 1 - beta1 / 1 - beta2: adam_consts, in double, once per
+//      step on the host (k_fm_online: once per sample on the device, with the same function and the same bits) ----
+// b^t by squaring: the same multiplications in the same order on the host and on the device
+__host__ __device__ inline double pow_step(double b, int32_t t) {
+  double r = 1.0, p = b;
+  for (uint32_t e = (uint32_t)t; e; e >>= 1) {
+    if (e & 1u) r = r * p;
+    p = p * p;
+  }
+  return r;
+}
+// the device-side constants of ADAM's step t (1-based) from the caller's hyper-parameters
+__host__ __device__ inline void adam_consts(float lr, float beta1, float beta2, int32_t t, float &step_size, float &c1, float &c2) {
+  const double b1 = beta1, b2 = beta2;
+  step_size = (float)((double)lr * sqrt(1.0 - pow_step(b2, t)) / (1.0 - pow_step(b1, t)));
+  c1 = (float)(1.0 - b1);
+  c2 = (float)(1.0 - b2);
+}
+// one coordinate: p, m, v by gradient g (h as above)
+template <int RULE>
+__device__ __forceinline__ void moments_upd(float &p, float &m, float &v, float g, const fmx_hyper_t &h) {
+  if (RULE == FMX_RULE_ADAM) {
+    m = m + h.beta1 * (g - m);
+    v = v + h.beta2 * (g * g - v);
+    p = p - h.lr * (m * rcp_(sqrt_(v) + h.eps));
+  } else {  // FMX_RULE_ADAGRAD: G in the v slot
+    v = v + g * g;
+    p = p - h.lr * (g * rcp_(sqrt_(v) + h.eps));
+  }
+}
+template <int RULE>
+__device__ __forceinline__ void moments_upd4(float4 &p, float4 &m, float4 &v, float4 g, const fmx_hyper_t &h) {
+  moments_upd<RULE>(p.x, m.x, v.x, g.x, h);
+  moments_upd<RULE>(p.y, m.y, v.y, g.y, h);
+  moments_upd<RULE>(p.z, m.z, v.z, g.z, h);
+  moments_upd<RULE>(p.w, m.w, v.w, g.w, h);
+}
+
 __device__ __forceinline__ float sigmoidf_(float z) { return 1.f / (1.f + expf(-z)); }
 // F.binary_cross_entropy_with_logits per element
 __device__ __forceinline__ float bcewl(float z, float y) {

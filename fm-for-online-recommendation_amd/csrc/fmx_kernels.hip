@@ -494,6 +494,12 @@ template <int LAYOUT, int RULE>
 __device__ __forceinline__ void apply_bias_and_loss(const UpdArgs &a, float db, float ls) {
   if (LAYOUT == FMX_LAYOUT_WEIGHTS) {
     st4(a.bias, apply_rule<RULE>(a.bias[0], db, a.h));
+  } else if (LAYOUT == FMX_LAYOUT_MOMENTS) {  // (b, m_b, v_b, 0): the bias is one more coordinate
+    float p = a.bias[0], m = a.bias[1], v = a.bias[2];
+    moments_upd<RULE>(p, m, v, db, a.h);
+    st4(a.bias, p);
+    if (RULE == FMX_RULE_ADAM) st4(a.bias + 1, m);
+    st4(a.bias + 2, v);
   } else {
     float z = a.bias[0], n = a.bias[1];
     const float w = ftrl_w(z, n, a.h);
@@ -568,13 +574,15 @@ __device__ void bias_and_loss(const UpdArgs &a, int r) {
 //   WEIGHTS row  [ V(kp) | w | pad ]
 //   FTRL row     [ V(kp) | w, zw, nw, pad | ... | zV(kp) | nV(kp) ]   zV starts at float `zoff`;
 //                V and w are the weights derived from (z, n), re-derived and stored by every update
+//   MOMENTS row  [ V(kp) | w, mw, vw, pad | ... | mV(kp) | vV(kp) ]   the FTRL geometry; V and w are the parameters
+//                (ADAGRAD neither loads nor stores the m slots: z stays zero in the registers)
 struct RowRegs {
   float4 v;       // V
-  float4 z, n;    // FTRL only
-  float4 fo;      // lane 0: (w, zw, nw, -)
+  float4 z, n;    // FTRL: (z, n); MOMENTS: (m, v)
+  float4 fo;      // lane 0: (w, zw, nw, -) / (w, mw, vw, -)
 };
 
-template <int LAYOUT>
+template <int LAYOUT, int RULE>
 __device__ __forceinline__ RowRegs load_row(const float *rp, int q, int kp, int zoff) {
   RowRegs r;
   r.v = *reinterpret_cast<const float4 *>(rp + 4 * q);
@@ -586,7 +594,7 @@ __device__ __forceinline__ RowRegs load_row(const float *rp, int q, int kp, int 
   if (LAYOUT == FMX_LAYOUT_WEIGHTS) {
     r.fo.x = rp[kp];
   } else {
-    r.z = *reinterpret_cast<const float4 *>(rp + zoff + 4 * q);
+    if (LAYOUT == FMX_LAYOUT_FTRL || RULE == FMX_RULE_ADAM) r.z = *reinterpret_cast<const float4 *>(rp + zoff + 4 * q);
     r.n = *reinterpret_cast<const float4 *>(rp + zoff + kp + 4 * q);
     r.fo = *reinterpret_cast<const float4 *>(rp + kp);
   }
@@ -603,6 +611,18 @@ __device__ __forceinline__ void update_row(float *rp, int q, int kp, int zoff, R
   if (LAYOUT == FMX_LAYOUT_WEIGHTS) {
     st16(rp + 4 * q, apply_rule4<RULE>(r.v, gr, h));
     if (q == 0) st4(rp + kp, apply_rule<RULE>(r.fo.x, cw, h));
+  } else if (LAYOUT == FMX_LAYOUT_MOMENTS) {
+    float4 p4 = r.v, m4 = r.z, v4 = r.n;
+    moments_upd4<RULE>(p4, m4, v4, gr, h);
+    // the (m, v) half is read by nobody but the next update of this row (a later launch): plain stores
+    if (RULE == FMX_RULE_ADAM) *reinterpret_cast<float4 *>(rp + zoff + 4 * q) = m4;
+    *reinterpret_cast<float4 *>(rp + zoff + kp + 4 * q) = v4;
+    st16(rp + 4 * q, p4);
+    if (q == 0) {
+      float4 fo = r.fo;
+      moments_upd<RULE>(fo.x, fo.y, fo.z, cw, h);
+      st16(rp + kp, fo);
+    }
   } else {
     float4 z4 = r.z, n4 = r.n;
     ftrl_upd(z4.x, n4.x, r.v.x, gr.x, h);
@@ -735,11 +755,11 @@ __device__ __forceinline__ void update_body(const UpdArgs &a, const int blk) {
 #pragma unroll
       for (int j = 0; j < EPG; ++j) {
         const bool need = tail[j] && k[j] != tile_prevkey;
-        row[j] = load_row<LAYOUT>(a.rows + (row0 + (need ? k[j] : 0u)) * (size_t)a.stride, q, kp, a.zoff);
+        row[j] = load_row<LAYOUT, RULE>(a.rows + (row0 + (need ? k[j] : 0u)) * (size_t)a.stride, q, kp, a.zoff);
       }
     }
     if (INL)  // (branch-free like the rows above; used by lane group 0 of a closing tile only)
-      row_in = load_row<LAYOUT>(a.rows + (row0 + ((slot == 0 && run_comes_in) ? tile_prevkey : 0u)) * (size_t)a.stride, q, kp, a.zoff);
+      row_in = load_row<LAYOUT, RULE>(a.rows + (row0 + ((slot == 0 && run_comes_in) ? tile_prevkey : 0u)) * (size_t)a.stride, q, kp, a.zoff);
   };
   // A tile whose last run goes on into the next tile PUBLISHES its partial sums (below) for the tile that closes the run,
   // and the publication waits for everything this wave has in flight (s_waitcnt vmcnt(0) before the flag): such a tile
@@ -918,7 +938,7 @@ __device__ __forceinline__ void update_body(const UpdArgs &a, const int blk) {
     if (tail[j]) {
       if (k[j] != tile_prevkey) {
         float *rp = a.rows + (row0 + k[j]) * (size_t)a.stride;
-        const RowRegs r = PREFETCH_ROWS ? row[PREFETCH_ROWS ? j : 0] : load_row<LAYOUT>(rp, q, kp, a.zoff);
+        const RowRegs r = PREFETCH_ROWS ? row[PREFETCH_ROWS ? j : 0] : load_row<LAYOUT, RULE>(rp, q, kp, a.zoff);
         update_row<LAYOUT, RULE>(rp, q, kp, a.zoff, r, accV, accA.vec(), accw, a.h);
       } else {
         // the run that came in from the previous tile ends here: its part inside this tile stays in registers for this
@@ -1050,7 +1070,7 @@ struct OnlineArgs {
   int32_t N, F, stride, zoff, loss_kind;
 };
 
-template <int LAYOUT>
+template <int LAYOUT, int RULE>
 __device__ __forceinline__ RowRegs load_row_sc1(const float *rp, int q, int kp, int zoff) {
   RowRegs r;
   r.v = ld_sc1_4(rp + 4 * q);
@@ -1060,7 +1080,7 @@ __device__ __forceinline__ RowRegs load_row_sc1(const float *rp, int q, int kp, 
   if (LAYOUT == FMX_LAYOUT_WEIGHTS) {  // (every lane, as in load_row: no branch around a load)
     r.fo.x = ld_sc1(rp + kp);
   } else {
-    r.z = ld_sc1_4(rp + zoff + 4 * q);
+    if (LAYOUT == FMX_LAYOUT_FTRL || RULE == FMX_RULE_ADAM) r.z = ld_sc1_4(rp + zoff + 4 * q);
     r.n = ld_sc1_4(rp + zoff + kp + 4 * q);
     r.fo = ld_sc1_4(rp + kp);
   }
@@ -1073,7 +1093,9 @@ __global__ __launch_bounds__(64) void k_fm_online(OnlineArgs a) {
   const int lane = threadIdx.x & 63;
   const int slot = lane / LPR, q = lane % LPR;
   const int kp = LPR * 4;
-  float b0 = a.bias[0], b1 = LAYOUT == FMX_LAYOUT_FTRL ? a.bias[1] : 0.f;  // the bias (or its (z, n)) stays in registers
+  constexpr bool MOM = LAYOUT == FMX_LAYOUT_MOMENTS;
+  // the bias (or its (z, n), or (b, m_b, v_b)) stays in registers
+  float b0 = a.bias[0], b1 = LAYOUT != FMX_LAYOUT_WEIGHTS ? a.bias[1] : 0.f, b2 = MOM ? a.bias[2] : 0.f;
   int64_t lo[NP];
   uint32_t vocab[NP];
   bool live[NP];
@@ -1125,7 +1147,7 @@ __global__ __launch_bounds__(64) void k_fm_online(OnlineArgs a) {
       ok[p] = live[p] && li[p] < vocab[p];
       // branch-free: a dead lane group or a bad index requests the table's first row and drops it (with a branch per
       // pass the rows of a sample went out in NP dependent round trips)
-      row[p] = load_row_sc1<LAYOUT>(a.rows + (size_t)(ok[p] ? lo[p] + li[p] : 0) * a.stride, q, kp, a.zoff);
+      row[p] = load_row_sc1<LAYOUT, RULE>(a.rows + (size_t)(ok[p] ? lo[p] + li[p] : 0) * a.stride, q, kp, a.zoff);
       bad = bad || (live[p] && !ok[p]);
     }
     fetch_inputs(i + 1);  // independent of the weights: in flight while this sample is processed
@@ -1154,8 +1176,11 @@ __global__ __launch_bounds__(64) void k_fm_online(OnlineArgs a) {
 #pragma unroll
     for (int m = 1; m < LPR; m <<= 1) sbi += __shfl_xor(sbi, m);
     fo = __shfl(fo, 0);
-    const float bias_w = LAYOUT == FMX_LAYOUT_WEIGHTS ? b0 : ftrl_w(b0, b1, a.h);
+    const float bias_w = LAYOUT == FMX_LAYOUT_FTRL ? ftrl_w(b0, b1, a.h) : b0;
     const float z = fo + sbi + bias_w;
+    // ADAM: sample i is step a.h.step + i + 1 -- its constants as the host derives them for a launch (same function, same bits)
+    fmx_hyper_t h = a.h;
+    if (RULE == FMX_RULE_ADAM) adam_consts(a.h.lr, a.h.beta1, a.h.beta2, a.h.step + i + 1, h.lr, h.beta1, h.beta2);
     float loss, dz;
     if (a.loss_kind == FMX_LOSS_BCE_LOGITS) {
       loss = bcewl(z, y);
@@ -1175,11 +1200,13 @@ __global__ __launch_bounds__(64) void k_fm_online(OnlineArgs a) {
       if (ok[p]) {
         const float xG = x[p] * dz;
         update_row<LAYOUT, RULE>(a.rows + (size_t)(lo[p] + li[p]) * a.stride, q, kp, a.zoff, row[p], xG * s, splat(x[p] * xG),
-                                 xG, a.h);
+                                 xG, h);
       }
     }
     if (LAYOUT == FMX_LAYOUT_WEIGHTS) {
       b0 = apply_rule<RULE>(b0, dz, a.h);
+    } else if (MOM) {
+      moments_upd<RULE>(b0, b1, b2, dz, h);
     } else {
       const float w = ftrl_w(b0, b1, a.h);
       ftrl_upd(b0, b1, w, dz, a.h);
@@ -1189,7 +1216,8 @@ __global__ __launch_bounds__(64) void k_fm_online(OnlineArgs a) {
   const bool any_bad = __ballot(bad) != 0ull;  // an out-of-range index seen by any lane group
   if (lane == 0) {
     a.bias[0] = b0;
-    if (LAYOUT == FMX_LAYOUT_FTRL) a.bias[1] = b1;
+    if (LAYOUT == FMX_LAYOUT_FTRL || (MOM && RULE == FMX_RULE_ADAM)) a.bias[1] = b1;
+    if (MOM) a.bias[2] = b2;
     if (any_bad && a.error) *a.error = 1;
   }
 }
@@ -1223,7 +1251,7 @@ __global__ __launch_bounds__(256) void k_fm_fixup(UpdArgs a) {
   if (my_trail != 1) return;  // wave-uniform
   float *rp = a.rows + ((size_t)a.foff[f] + key) * (size_t)a.stride;
   RowRegs r;
-  if (lane < LPR) r = load_row<LAYOUT>(rp, q, kp, a.zoff);
+  if (lane < LPR) r = load_row<LAYOUT, RULE>(rp, q, kp, a.zoff);
   // m = number of following tiles that hold a piece of the run
   int m = 0;
   for (int j0 = 1; t + j0 < tiles_per_field; j0 += 64) {
@@ -1523,7 +1551,7 @@ __global__ __launch_bounds__(256) void k_online_mlp(OnlineMlpArgs a) {
         if (lane == 0) y_lds = y_n;
 #pragma unroll
         for (int p = 0; p < NP; ++p) {
-          row[p] = load_row_sc1<LAYOUT>(a.rows + (size_t)(ok[p] ? lo[p] + li[p] : 0) * a.stride, q, kp, a.zoff);
+          row[p] = load_row_sc1<LAYOUT, RULE>(a.rows + (size_t)(ok[p] ? lo[p] + li[p] : 0) * a.stride, q, kp, a.zoff);
           bad = bad || (live[p] && !ok[p]);
         }
         fetch_inputs(i + 1);
@@ -1689,15 +1717,43 @@ bool with_one_of(int v, Fn &&f) {
   return ((v == VS && (f(std::integral_constant<int, VS>{}), true)) || ...);
 }
 
-// f(LAYOUT, RULE) as integral constants for an update rule: SIGNADAM and SGD on the weights layout, anything else FTRL
-template <class Fn>
-decltype(auto) with_rule(int rule, Fn &&f) {
+// f(LAYOUT, RULE) as integral constants for an update rule and the layout it pairs with (check_rule); false, and no call,
+// for a rule it does not know.  with_rule_wf: the rules of the weights and FTRL layouts only (the launches the adaptive
+// rules do not take -- the update's rider, k_online_mlp -- are not instantiated for them).
+template <bool MOMENTS_RULES, class Fn>
+bool with_rule_impl(int rule, Fn &&f) {
   using Weights = std::integral_constant<int, FMX_LAYOUT_WEIGHTS>;
+  using Moments = std::integral_constant<int, FMX_LAYOUT_MOMENTS>;
   switch (rule) {
-    case FMX_RULE_SIGNADAM: return f(Weights{}, std::integral_constant<int, FMX_RULE_SIGNADAM>{});
-    case FMX_RULE_SGD: return f(Weights{}, std::integral_constant<int, FMX_RULE_SGD>{});
-    default: return f(std::integral_constant<int, FMX_LAYOUT_FTRL>{}, std::integral_constant<int, FMX_RULE_FTRL>{});
+    case FMX_RULE_SIGNADAM: f(Weights{}, std::integral_constant<int, FMX_RULE_SIGNADAM>{}); return true;
+    case FMX_RULE_SGD: f(Weights{}, std::integral_constant<int, FMX_RULE_SGD>{}); return true;
+    case FMX_RULE_FTRL: f(std::integral_constant<int, FMX_LAYOUT_FTRL>{}, std::integral_constant<int, FMX_RULE_FTRL>{}); return true;
+    case FMX_RULE_ADAGRAD:
+      if constexpr (MOMENTS_RULES) {
+        f(Moments{}, std::integral_constant<int, FMX_RULE_ADAGRAD>{});
+        return true;
+      }
+      return false;
+    case FMX_RULE_ADAM:
+      if constexpr (MOMENTS_RULES) {
+        f(Moments{}, std::integral_constant<int, FMX_RULE_ADAM>{});
+        return true;
+      }
+      return false;
+    default: return false;
   }
+}
+template <class Fn>
+bool with_rule(int rule, Fn &&f) { return with_rule_impl<true>(rule, f); }
+template <class Fn>
+bool with_rule_wf(int rule, Fn &&f) { return with_rule_impl<false>(rule, f); }
+
+inline bool adaptive_rule(int rule) { return rule == FMX_RULE_ADAGRAD || rule == FMX_RULE_ADAM; }
+inline const char *rule_name(int rule) { return rule == FMX_RULE_ADAM ? "FMX_RULE_ADAM" : "FMX_RULE_ADAGRAD"; }
+// the entry points outside the pure-FM table steps: a refusal that names the rule
+int refuse_adaptive(int rule, const char *who) {
+  return fail(FMX_ERR_UNSUPPORTED, "%s: %s is not supported here (fmx_fm_update / fmx_fm_step / fmx_fm_stream / fmx_fm_online_run take it)",
+              who, rule_name(rule));
 }
 
 int check_table(const fmx_table_t *t) {
@@ -1705,9 +1761,10 @@ int check_table(const fmx_table_t *t) {
   if (!t->rows || !t->field_offsets || !t->bias) return fail(FMX_ERR_ARG, "table has a null pointer");
   if (t->n_fields < 1 || t->n_rows < 1 || t->k < 1) return fail(FMX_ERR_ARG, "table sizes must be positive");
   if (!lpr_of(t->kp) || t->k > t->kp) return fail(FMX_ERR_SHAPE, "kp=%d must be 4/8/16/32/64 and >= k=%d", t->kp, t->k);
-  if (t->layout != FMX_LAYOUT_WEIGHTS && t->layout != FMX_LAYOUT_FTRL) return fail(FMX_ERR_ARG, "unknown layout %d", t->layout);
+  if (t->layout != FMX_LAYOUT_WEIGHTS && t->layout != FMX_LAYOUT_FTRL && t->layout != FMX_LAYOUT_MOMENTS)
+    return fail(FMX_ERR_ARG, "unknown layout %d", t->layout);
   int need = t->kp + 4;
-  if (t->layout == FMX_LAYOUT_FTRL) {
+  if (t->layout != FMX_LAYOUT_WEIGHTS) {  // FTRL and MOMENTS: [ head | pad | kp | kp ] from z_offset
     if (t->z_offset % 4 || t->z_offset < t->kp + 4)
       return fail(FMX_ERR_SHAPE, "z_offset=%d must be a multiple of 4 and >= kp + 4 = %d", t->z_offset, t->kp + 4);
     need = t->z_offset + 2 * t->kp;
@@ -1728,9 +1785,21 @@ int check_rule(const fmx_table_t *t, int rule) {
     if (t->layout != FMX_LAYOUT_FTRL) return fail(FMX_ERR_ARG, "FMX_RULE_FTRL needs FMX_LAYOUT_FTRL");
   } else if (rule == FMX_RULE_SIGNADAM || rule == FMX_RULE_SGD) {
     if (t->layout != FMX_LAYOUT_WEIGHTS) return fail(FMX_ERR_ARG, "rule %d needs FMX_LAYOUT_WEIGHTS", rule);
+  } else if (adaptive_rule(rule)) {
+    if (t->layout != FMX_LAYOUT_MOMENTS) return fail(FMX_ERR_ARG, "%s needs FMX_LAYOUT_MOMENTS", rule_name(rule));
   } else {
     return fail(FMX_ERR_ARG, "unknown rule %d", rule);
   }
+  return FMX_OK;
+}
+
+// ADAM's hyper-parameters for a call of n_steps steps: betas in [0, 1) (torch's bounds) and t = step + n_steps in int32
+int check_adam(const fmx_hyper_t *h, int rule, int64_t n_steps) {
+  if (rule != FMX_RULE_ADAM || !h) return FMX_OK;
+  if (!(h->beta1 >= 0.f && h->beta1 < 1.f && h->beta2 >= 0.f && h->beta2 < 1.f))
+    return fail(FMX_ERR_ARG, "FMX_RULE_ADAM: beta1 = %g and beta2 = %g must lie in [0, 1)", h->beta1, h->beta2);
+  if (h->step < 0 || (int64_t)h->step + n_steps > INT32_MAX)
+    return fail(FMX_ERR_ARG, "FMX_RULE_ADAM: step = %d must be >= 0 and step + steps of the call <= 2^31 - 1", h->step);
   return FMX_OK;
 }
 
@@ -1867,8 +1936,9 @@ template <int LPR, int NPASS, bool MAPPED = false>
 void launch_forward_np(const FwdArgs &a, int layout, hipStream_t st) {
   const int wpb = tune().wpb_fwd;
   const dim3 grid((a.B + wpb - 1) / wpb), block(64 * wpb);
-  if (layout == FMX_LAYOUT_WEIGHTS) hipLaunchKernelGGL((k_fm_forward<LPR, FMX_LAYOUT_WEIGHTS, NPASS, MAPPED>), grid, block, 0, st, a);
-  else hipLaunchKernelGGL((k_fm_forward<LPR, FMX_LAYOUT_FTRL, NPASS, MAPPED>), grid, block, 0, st, a);
+  // the forward reads [ V | w ] and the bias weight: a MOMENTS table is read as a WEIGHTS one (bias[0] is the weight)
+  if (layout == FMX_LAYOUT_FTRL) hipLaunchKernelGGL((k_fm_forward<LPR, FMX_LAYOUT_FTRL, NPASS, MAPPED>), grid, block, 0, st, a);
+  else hipLaunchKernelGGL((k_fm_forward<LPR, FMX_LAYOUT_WEIGHTS, NPASS, MAPPED>), grid, block, 0, st, a);
 }
 
 template <int LPR>
@@ -1903,7 +1973,7 @@ void launch_update_rider(const UpdArgs &a, int rule, const MlpReduceArgs &r, hip
   const int wpb = tune().wpb_upd;
   const int n_upd = (tiles + wpb - 1) / wpb + red_slices(a.B), per = mlp_reduce_blocks_per_layer(r, 64 * wpb);
   const dim3 grid(n_upd + per * r.n_layers), block(64 * wpb);
-  with_rule(rule, [&](auto LAYOUT, auto RULE) {
+  with_rule_wf(rule, [&](auto LAYOUT, auto RULE) {  // (fmx_deepfm_stream refuses the adaptive rules)
     hipLaunchKernelGGL((k_fm_update_rider<LPR, LAYOUT, RULE, true>), grid, block, 0, st, a, r, n_upd, per);
   });
 }
@@ -2121,6 +2191,26 @@ int pool_loop(const fmx_table_t *table, const int32_t *idx_pool, const float *y_
   return rc;
 }
 
+// The caller's hyper-parameters as the launches take them: the six floats every rule reads, and the fields appended after
+// them (beta1, beta2, step) for FMX_RULE_ADAM only -- a caller built against the six-float struct passes a shorter struct and
+// keeps working with the other rules; nothing past its end is read.  Appended fields not read are zero.
+fmx_hyper_t hyper_for(const fmx_hyper_t *h, int rule) {
+  fmx_hyper_t r;
+  memset(&r, 0, sizeof(r));
+  r.lr = h->lr;
+  r.eps = h->eps;
+  r.alpha = h->alpha;
+  r.beta = h->beta;
+  r.l1 = h->l1;
+  r.l2 = h->l2;
+  if (rule == FMX_RULE_ADAM) {
+    r.beta1 = h->beta1;
+    r.beta2 = h->beta2;
+    r.step = h->step;
+  }
+  return r;
+}
+
 FwdArgs fill_fwd(const fmx_table_t *table, const fmx_hyper_t *hyper, const int32_t *idx, const float *xv, const float *y,
                  int32_t B, int32_t loss_kind, float inv_b, const fmx_fwd_out_t *out) {
   FwdArgs a;
@@ -2133,7 +2223,7 @@ FwdArgs fill_fwd(const fmx_table_t *table, const fmx_hyper_t *hyper, const int32
   a.xv = xv;
   a.y = y;
   a.out = *out;
-  a.h = *hyper;
+  a.h = hyper_for(hyper, -1);
   a.B = B;
   a.F = table->n_fields;
   a.Fc = n_cols(table);
@@ -2185,7 +2275,7 @@ UpdArgs fill_upd(const fmx_table_t *table, const fmx_hyper_t *hyper, const Works
   a.loss_b = loss_b;
   a.loss_out = loss_out;
   a.step_counter = step_counter;
-  a.h = *hyper;
+  a.h = hyper_for(hyper, -1);  // (ADAM's constants: update_impl)
   a.B = B;
   a.F = n_sort_fields(table);
   a.Bp = fmx_sorted_width(B);
@@ -2204,8 +2294,10 @@ int update_impl(const fmx_table_t *table, const fmx_hyper_t *hyper, int32_t rule
                 const float *loss_b, float inv_b, float *loss_out, hipStream_t st,
                 int32_t *step_counter = nullptr, int32_t sample_ld = 0,
                 int32_t *err_flag = nullptr, const MlpReduceArgs *rider = nullptr) {
-  const UpdArgs a = fill_upd(table, hyper, w, sorted, xv, S, dz_first, dz_bi, gbi, B, loss_b, inv_b, loss_out, step_counter,
-                             sample_ld, err_flag);
+  UpdArgs a = fill_upd(table, hyper, w, sorted, xv, S, dz_first, dz_bi, gbi, B, loss_b, inv_b, loss_out, step_counter,
+                       sample_ld, err_flag);
+  if (rule == FMX_RULE_ADAM)  // this launch is step t = hyper->step + 1: its constants in double, once (adam_consts)
+    adam_consts(hyper->lr, hyper->beta1, hyper->beta2, hyper->step + 1, a.h.lr, a.h.beta1, a.h.beta2);
   if (rider) {
     if (gbi != nullptr && tune().inline_fixup && !is_capturing(st)) {  // the one-launch form of the update: the rider goes with it
       with_lpr(table->kp, [&](auto LPR) { launch_update_rider<LPR>(a, rule, *rider, st); });
@@ -2257,8 +2349,8 @@ int launch_forward_finish_g(const FinishArgs &a, int G, hipStream_t st) {
 template <int LPR>
 int launch_forward_finish(const FinishArgs &a, int layout, int G, hipStream_t st) {
   if (G > WAVE / LPR) return fail(FMX_ERR_ARG, "fmx_fm_forward_finish: more owners than lane groups");
-  return layout == FMX_LAYOUT_WEIGHTS ? launch_forward_finish_g<LPR, FMX_LAYOUT_WEIGHTS>(a, G, st)
-                                      : launch_forward_finish_g<LPR, FMX_LAYOUT_FTRL>(a, G, st);
+  return layout == FMX_LAYOUT_FTRL ? launch_forward_finish_g<LPR, FMX_LAYOUT_FTRL>(a, G, st)      // MOMENTS: as WEIGHTS (bias[0])
+                                   : launch_forward_finish_g<LPR, FMX_LAYOUT_WEIGHTS>(a, G, st);
 }
 
 // the tree cut into n_blocks blocks, the table holding n_local_blocks of them: fields [lb NP SL, (lb + 1) NP SL) are block lb's
@@ -2314,6 +2406,7 @@ int check_step_args(const fmx_table_t *table, const fmx_hyper_t *hyper, int32_t 
   if (int rc = check_rule(table, rule)) return rc;
   if (int rc = check_sort_geometry(table, B)) return rc;
   if (!hyper || !workspace) return fail(FMX_ERR_ARG, "null hyper / workspace");
+  if (int rc = check_adam(hyper, rule, 1)) return rc;
   if (!aligned16(workspace)) return fail(FMX_ERR_ALIGN, "workspace must be 16-byte aligned");
   if (!fwd || !fwd->S || !fwd->dz || !fwd->loss) return fail(FMX_ERR_ARG, "fwd->S, fwd->loss, fwd->dz are required");
   if (!aligned16(fwd->S) || !aligned16(fwd->dz) || !aligned16(fwd->loss))
@@ -2386,7 +2479,8 @@ int fmx_fm_forward_finish(const fmx_hyper_t *hyper, const float *bias, int32_t l
                           int64_t owner_stride, int32_t n_owners, const float *y, int32_t B, int32_t loss_kind, float inv_b,
                           const fmx_fwd_out_t *out, fmx_stream_t stream) {
   if (!hyper || !bias || !parts || !out) return fail(FMX_ERR_ARG, "fmx_fm_forward_finish: null argument");
-  if (layout != FMX_LAYOUT_WEIGHTS && layout != FMX_LAYOUT_FTRL) return fail(FMX_ERR_ARG, "unknown layout %d", layout);
+  if (layout != FMX_LAYOUT_WEIGHTS && layout != FMX_LAYOUT_FTRL && layout != FMX_LAYOUT_MOMENTS)
+    return fail(FMX_ERR_ARG, "unknown layout %d", layout);
   if (!lpr_of(kp)) return fail(FMX_ERR_SHAPE, "kp=%d must be 4/8/16/32/64", kp);
   if (B < 1) return fail(FMX_ERR_ARG, "B must be >= 1");
   if (loss_kind < FMX_LOSS_NONE || loss_kind > FMX_LOSS_BCE_SIGMOID) return fail(FMX_ERR_ARG, "unknown loss %d", loss_kind);
@@ -2401,7 +2495,7 @@ int fmx_fm_forward_finish(const fmx_hyper_t *hyper, const float *bias, int32_t l
   a.bias = bias;
   a.y = y;
   a.out = *out;
-  a.h = *hyper;
+  a.h = hyper_for(hyper, -1);
   a.h.alpha = 1.0f / hyper->alpha;  // the kernels multiply by 1/alpha
   a.B = B;
   a.loss_kind = loss_kind;
@@ -2431,6 +2525,7 @@ int fmx_fm_update(const fmx_table_t *table, const fmx_hyper_t *hyper, int32_t ru
     return fail(FMX_ERR_SHAPE, "sample_ld=%d must be 0 or a multiple of 4 that is >= kp", sample_ld);
   if (int rc = check_rule(table, rule)) return rc;
   if (!hyper || !workspace || !S || !dz_first) return fail(FMX_ERR_ARG, "fmx_fm_update: null argument");
+  if (int rc = check_adam(hyper, rule, 1)) return rc;
   if (!dz_bi && !gbi) return fail(FMX_ERR_ARG, "fmx_fm_update: one of dz_bi / gbi is required");
   if (int rc = check_sort_geometry(table, B)) return rc;
   if (!aligned16(workspace) || !aligned16(S) || (gbi && !aligned16(gbi)) ||
@@ -2456,6 +2551,7 @@ int fmx_deepfm_stream(const fmx_table_t *table, const fmx_hyper_t *hyper, int32_
                       const int32_t *idx_pool, const float *y_pool, int32_t n_pool, int32_t B, float inv_b, int32_t n_steps,
                       void *workspace, int64_t workspace_bytes, void *mlp_workspace, const fmx_fwd_out_t *fwd, float *dz, float *gbi,
                       float *grads, float lr_mlp, float *loss_out, fmx_stream_t stream) {
+  if (adaptive_rule(rule)) return refuse_adaptive(rule, "fmx_deepfm_stream");
   if (int rc = check_table(table)) return rc;
   if (int rc = check_rule(table, rule)) return rc;
   if (!hyper || !mlp || !workspace || !mlp_workspace || !fwd || !fwd->S || !fwd->bi || !fwd->logit || !dz || !gbi || !grads)
@@ -2528,6 +2624,7 @@ int fmx_owner_step(fmx_comm_t *comm, const fmx_table_t *table, const fmx_hyper_t
                    const fmx_owner_bufs_t *bufs, float *loss_out, int32_t *error, fmx_stream_t stream) {
   Comm *c = reinterpret_cast<Comm *>(comm);
   int GB = 0;
+  if (adaptive_rule(rule)) return refuse_adaptive(rule, "fmx_owner_step");
   if (int rc = owner_geometry(c, table, B, slot, GB, "fmx_owner_step")) return rc;
   if (int rc = check_rule(table, rule)) return rc;
   if (!hyper || !idx_all || !y_local || !bufs || !bufs->parts_send || !bufs->parts_recv || !bufs->rec_local || !bufs->rec_all)
@@ -2595,6 +2692,7 @@ int fmx_fm_stream(const fmx_table_t *table, const fmx_hyper_t *hyper, int32_t ru
                   fmx_stream_t stream) {
   if (int rc = check_step_args(table, hyper, rule, loss_kind, B, workspace, fwd)) return rc;
   if (!idx_pool || !y_pool || n_pool < 1 || n_steps < 0) return fail(FMX_ERR_ARG, "fmx_fm_stream: bad pool / step count");
+  if (int rc = check_adam(hyper, rule, n_steps)) return rc;
   hipStream_t st = static_cast<hipStream_t>(stream);
   if (int rc = check_workspace(table, B, workspace, workspace_bytes, "fmx_fm_stream")) return rc;
   const Workspace w = carve(table, B, workspace);
@@ -2603,7 +2701,9 @@ int fmx_fm_stream(const fmx_table_t *table, const fmx_hyper_t *hyper, int32_t ru
       return forward_impl(table, hyper, idx, nullptr, y, B, loss_kind, inv_b, fwd, st);
     };
     auto update = [&](int s, const uint32_t *sorted, hipStream_t st) {
-      return update_impl(table, hyper, rule, w, sorted, nullptr, fwd->S, fwd->dz, fwd->dz, nullptr, B, fwd->loss, inv_b,
+      fmx_hyper_t hs = hyper_for(hyper, rule);  // step s of the call is step t = hyper->step + s + 1 of the table
+      hs.step += s;
+      return update_impl(table, &hs, rule, w, sorted, nullptr, fwd->S, fwd->dz, fwd->dz, nullptr, B, fwd->loss, inv_b,
                          loss_out ? loss_out + s : nullptr, st, nullptr, fwd->sample_ld, fwd->error);
     };
     return pool_loop(table, idx_pool, y_pool, n_pool, B, n_steps, w, fwd->error, st, forward, update);
@@ -2648,7 +2748,9 @@ int fmx_fm_stream(const fmx_table_t *table, const fmx_hyper_t *hyper, int32_t ru
       (void)hipEventRecord(e[2], st);
       for (int r = 0; r < n && rc == FMX_OK; ++r) {
         const float *S = tmp + (size_t)r * region, *dz = S + (size_t)B * table->kp;
-        rc = update_impl(table, hyper, rule, w, w.sorted + (size_t)r * w.sorted_stride, nullptr, S, dz, dz, nullptr, B, dz + B, inv_b,
+        fmx_hyper_t hs = hyper_for(hyper, rule);
+        hs.step += first + r;
+        rc = update_impl(table, &hs, rule, w, w.sorted + (size_t)r * w.sorted_stride, nullptr, S, dz, dz, nullptr, B, dz + B, inv_b,
                          loss_out ? loss_out + first + r : nullptr, st, nullptr, 0, fwd->error);
       }
       (void)hipEventRecord(e[3], st);
@@ -2690,6 +2792,7 @@ int fmx_fm_online_run(const fmx_table_t *table, const fmx_hyper_t *hyper, int32_
   if (N < 0) return fail(FMX_ERR_ARG, "fmx_fm_online_run: N must be >= 0");
   if (N == 0) return FMX_OK;  // an empty stream (its buffers may be null)
   if (!hyper || !idx || !y || !pred_out) return fail(FMX_ERR_ARG, "fmx_fm_online_run: null argument");
+  if (int rc = check_adam(hyper, rule, N)) return rc;
   if (loss_kind != FMX_LOSS_BCE_LOGITS && loss_kind != FMX_LOSS_BCE_SIGMOID) return fail(FMX_ERR_ARG, "fit needs a loss");
   const int lpr = lpr_of(table->kp), slots = WAVE / lpr;
   const int np = (table->n_fields + slots - 1) / slots;
@@ -2706,7 +2809,7 @@ int fmx_fm_online_run(const fmx_table_t *table, const fmx_hyper_t *hyper, int32_
   a.pred = pred_out;
   a.loss = loss_out;
   a.error = error;
-  a.h = *hyper;
+  a.h = hyper_for(hyper, rule);  // ADAM: the kernel derives each sample's constants from lr, beta1, beta2, step
   a.h.alpha = 1.0f / hyper->alpha;  // the kernels multiply by 1/alpha
   a.N = N;
   a.F = table->n_fields;
@@ -2748,6 +2851,7 @@ int fmx_online_run_mlp(const fmx_table_t *table, const fmx_hyper_t *hyper, int32
   if (!aligned16(workspace) || !aligned16(scratch)) return fail(FMX_ERR_ALIGN, "workspace and scratch must be 16-byte aligned");
   if (hedge && !alpha) return fail(FMX_ERR_ARG, "fmx_online_run_mlp: Hedge needs alpha");
   if (!hedge) {
+    if (adaptive_rule(rule)) return refuse_adaptive(rule, "fmx_online_run_mlp (fit mode)");
     if (int rc = check_rule(table, rule)) return rc;
     if (rule != FMX_RULE_SIGNADAM && rule != FMX_RULE_SGD) return fail(FMX_ERR_ARG, "fmx_online_run_mlp: rule must be SIGNADAM or SGD");
     if (loss_kind != FMX_LOSS_BCE_LOGITS && loss_kind != FMX_LOSS_BCE_SIGMOID) return fail(FMX_ERR_ARG, "fit needs a loss");
@@ -2776,7 +2880,7 @@ int fmx_online_run_mlp(const fmx_table_t *table, const fmx_hyper_t *hyper, int32
       a.error = fwd->error;
       a.params = mlp->params;
       a.alpha = alpha;
-      a.h = *hyper;
+      a.h = hyper_for(hyper, -1);
       a.h.alpha = 1.0f / hyper->alpha;
       a.hedge_b = hedge_b;
       a.hedge_s = hedge_s;
@@ -2792,10 +2896,11 @@ int fmx_online_run_mlp(const fmx_table_t *table, const fmx_hyper_t *hyper, int32
       a.fm_term = fm_term;
       a.rule = rule;
       a.loss_kind = loss_kind;
-      // FTRL-layout tables are read only (Hedge): FTRL pairs with that layout alone, any rule but SGD takes SIGNADAM
+      // FTRL-layout tables are read only (Hedge): FTRL pairs with that layout alone, any rule but SGD takes SIGNADAM (a MOMENTS
+      // table, read only too, is read as a weights one)
       const int kernel_rule = table->layout == FMX_LAYOUT_FTRL ? FMX_RULE_FTRL : rule == FMX_RULE_SGD ? FMX_RULE_SGD : FMX_RULE_SIGNADAM;
       with_lpr(table->kp, [&](auto LPR) {
-        with_rule(kernel_rule, [&](auto LAYOUT, auto RULE) { launch_online_mlp_k<LPR, LAYOUT, RULE>(a, st); });
+        with_rule_wf(kernel_rule, [&](auto LAYOUT, auto RULE) { launch_online_mlp_k<LPR, LAYOUT, RULE>(a, st); });
       });
       return check_launch("k_online_mlp");
     }
@@ -2816,12 +2921,12 @@ int fmx_online_run_mlp(const fmx_table_t *table, const fmx_hyper_t *hyper, int32
     if (!fm_term) {  // NFM: the logit without the MLP term is the first-order sum plus the bias weight
       a.base_bias = table->bias;
       a.base_bias_ftrl = table->layout == FMX_LAYOUT_FTRL;
-      a.h_table = *hyper;
+      a.h_table = hyper_for(hyper, -1);
       a.h_table.alpha = 1.0f / hyper->alpha;
     }
     a.y = y + i;
     a.pred_out = pred_out + i;
-    a.h = *hyper;
+    a.h = hyper_for(hyper, -1);
     a.inv_b = 1.0f;
     if (hedge) {
       a.alpha = alpha;
@@ -2860,6 +2965,7 @@ int fmx_mlp_forward(const fmx_mlp_t *mlp, const float *bi, int32_t kp, const flo
 int fmx_mlp_fit(const fmx_mlp_t *mlp, const fmx_hyper_t *hyper, int32_t rule, int32_t loss_kind, const float *bi, int32_t kp,
                 const float *base, const float *y, int32_t B, float inv_b, float *dz_out, float *gbi_out, float *loss_out,
                 fmx_stream_t stream) {
+  if (adaptive_rule(rule)) return refuse_adaptive(rule, "fmx_mlp_fit");
   if (!hyper || !bi || !base || !y || !dz_out || !gbi_out) return fail(FMX_ERR_ARG, "fmx_mlp_fit: null argument");
   if (rule != FMX_RULE_SIGNADAM && rule != FMX_RULE_SGD) return fail(FMX_ERR_ARG, "fmx_mlp_fit: rule must be SIGNADAM or SGD");
   if (loss_kind != FMX_LOSS_BCE_LOGITS && loss_kind != FMX_LOSS_BCE_SIGMOID) return fail(FMX_ERR_ARG, "fmx_mlp_fit needs a loss");
@@ -2871,7 +2977,7 @@ int fmx_mlp_fit(const fmx_mlp_t *mlp, const fmx_hyper_t *hyper, int32_t rule, in
   a.dz_out = dz_out;
   a.gbi_out = gbi_out;
   a.out = loss_out;
-  a.h = *hyper;
+  a.h = hyper_for(hyper, -1);
   a.mode = MLP_MODE_FIT;
   a.rule = rule;
   a.loss_kind = loss_kind;

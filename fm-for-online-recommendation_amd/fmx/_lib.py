@@ -7,11 +7,13 @@ LIB_PATH = os.environ.get("FMX_LIB_PATH") or os.path.join(_HERE, "libfmx.so")  #
 
 # enums of include/fmx.h
 OK, ERR_ARG, ERR_SHAPE, ERR_ALIGN, ERR_LAUNCH, ERR_UNSUPPORTED = 0, -1, -2, -3, -4, -5
-LAYOUT_WEIGHTS, LAYOUT_FTRL = 0, 1
-RULE_SIGNADAM, RULE_SGD, RULE_FTRL = 0, 1, 2
+LAYOUT_WEIGHTS, LAYOUT_FTRL, LAYOUT_MOMENTS = 0, 1, 2
+RULE_SIGNADAM, RULE_SGD, RULE_FTRL, RULE_ADAGRAD, RULE_ADAM = 0, 1, 2, 3, 4
 LOSS_NONE, LOSS_BCE_LOGITS, LOSS_BCE_SIGMOID = 0, 1, 2
 
-RULES = {"signadam": RULE_SIGNADAM, "sgd": RULE_SGD, "ftrl": RULE_FTRL}
+RULES = {"signadam": RULE_SIGNADAM, "sgd": RULE_SGD, "ftrl": RULE_FTRL, "adagrad": RULE_ADAGRAD, "adam": RULE_ADAM}
+ADAPTIVE_RULES = ("adagrad", "adam")      # persistent per-coordinate state: tables in the moments layout
+LAYOUTS = {"weights": LAYOUT_WEIGHTS, "ftrl": LAYOUT_FTRL, "moments": LAYOUT_MOMENTS}
 LOSSES = {None: LOSS_NONE, "none": LOSS_NONE, "logits": LOSS_BCE_LOGITS, "sigmoid": LOSS_BCE_SIGMOID}
 
 EXPORTS = ["fmx_version", "fmx_last_error_string", "fmx_set_option", "fmx_sorted_width", "fmx_sorted_bbits", "fmx_workspace_bytes",
@@ -44,7 +46,8 @@ class Table(C.Structure):
 
 class Hyper(C.Structure):
     _fields_ = [("lr", C.c_float), ("eps", C.c_float), ("alpha", C.c_float), ("beta", C.c_float),
-                ("l1", C.c_float), ("l2", C.c_float)]
+                ("l1", C.c_float), ("l2", C.c_float),
+                ("beta1", C.c_float), ("beta2", C.c_float), ("step", C.c_int32), ("reserved", C.c_int32)]   # (appended: read for the adam rule only)
 
 
 class Mlp(C.Structure):

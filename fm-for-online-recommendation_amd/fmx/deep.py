@@ -17,9 +17,14 @@ import torch
 import torch.distributed as dist
 import torch.nn.functional as F
 
+from . import _lib
+
 
 class HipDeepBackend:
     def __init__(self, engine, hyper, rule):
+        if rule in _lib.ADAPTIVE_RULES:
+            raise ValueError(f"{type(self).__name__}: update_rule {rule!r} is single-GPU only (FMEngine / the model classes); "
+                             "the multi-GPU trainers take 'signadam', 'sgd' and 'ftrl'")
         self.e, self.hyper, self.rule = engine, hyper, rule
 
     def forward(self, idx):

@@ -17,6 +17,8 @@ import os
 import torch
 import torch.distributed as dist
 
+from . import _lib
+
 
 def max_step_batch(max_field_rows):
     """Largest batch one exact step can take: 32,768 (a field's occurrence list is merged inside one workgroup's LDS;
@@ -28,6 +30,9 @@ class HipBackend:
     """The product backend: fmx.FMEngine on this rank's GPU."""
 
     def __init__(self, engine, hyper, rule, loss):
+        if rule in _lib.ADAPTIVE_RULES:
+            raise ValueError(f"{type(self).__name__}: update_rule {rule!r} is single-GPU only (FMEngine / the model classes); "
+                             "the multi-GPU trainers take 'signadam', 'sgd' and 'ftrl'")
         self.e, self.hyper, self.rule, self.loss = engine, hyper, rule, loss
         self.max_global_batch = max_step_batch(max(engine.table.feature_sizes))
 

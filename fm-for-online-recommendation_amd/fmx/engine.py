@@ -11,8 +11,8 @@ from .table import FlatTable
 class Hyper:
     """Update-rule hyper-parameters (include/fmx.h fmx_hyper_t)."""
 
-    def __init__(self, lr=0.01, eps=1e-8, alpha=0.05, beta=1.0, l1=0.0, l2=0.0):
-        self.c = _lib.Hyper(lr, eps, alpha, beta, l1, l2)
+    def __init__(self, lr=0.01, eps=1e-8, alpha=0.05, beta=1.0, l1=0.0, l2=0.0, beta1=0.9, beta2=0.999, step=0):
+        self.c = _lib.Hyper(lr, eps, alpha, beta, l1, l2, beta1, beta2, int(step), 0)
 
     def ref(self):
         return C.byref(self.c)
@@ -86,6 +86,16 @@ class FMEngine:
         self.loss_out = torch.zeros(1, **f32)
         self.error = torch.zeros(1, dtype=torch.int32, device=dev)
         self.max_batch = B
+
+    def _steps(self, hyper):
+        """A moments-layout table counts its steps (the adam rule's t - 1): the call's first step is hyper's `step`; after the
+        call the table's count advances by the steps it took (_advance).  Other layouts: nothing to count."""
+        if self.table.layout == "moments":
+            hyper.c.step = self.table.step
+
+    def _advance(self, n):
+        if self.table.layout == "moments":
+            self.table.step += int(n)
 
     def _ws_bytes(self):
         return self.workspace.numel() * self.workspace.element_size()
@@ -174,10 +184,12 @@ class FMEngine:
             loss_b = self.loss_b if loss_b is None else loss_b
             S_p, dzf_p, dzb_p, loss_p = S.data_ptr(), dz_first.data_ptr(), _ptr(dz_bi), loss_b.data_ptr()
         ws = self.workspace if workspace is None else workspace
+        self._steps(hyper)
         _lib.check(self.lib.fmx_fm_update(self.table.c_struct(), hyper.ref(), _lib.RULES[rule], ws.data_ptr(), ws.numel() * ws.element_size(),
                                           _ptr(xv_d), S_p, dzf_p, dzb_p, _ptr(gbi), B, ld,
                                           loss_p if with_loss else None, inv_b,
                                           self.loss_out.data_ptr() if with_loss else None, self._stream(stream)))
+        self._advance(1)
 
     def step(self, hyper, rule, loss, idx_d, xv_d, y_d, inv_b=None):
         """One pure-FM mini-batch step; the mean loss lands in self.loss_out[0] (no sync here)."""
@@ -188,9 +200,11 @@ class FMEngine:
             self._step_out = cached = (self.S.data_ptr(), self._fwd_out(want_first=False, want_bi=False))
         out = cached[1]
         inv_b = 1.0 / B if inv_b is None else inv_b
+        self._steps(hyper)
         _lib.check(self.lib.fmx_fm_step(self.table.c_struct(), hyper.ref(), _lib.RULES[rule], _lib.LOSSES[loss],
                                         idx_d.data_ptr(), _ptr(xv_d), y_d.data_ptr(), B, inv_b, self.workspace.data_ptr(), self._ws_bytes(),
                                         C.byref(out), self.loss_out.data_ptr(), self._stream()))
+        self._advance(1)
 
     def stream(self, hyper, rule, loss, idx_pool, y_pool, n_steps, loss_out=None, timed=False):
         """The online loop over a resident pool of batches (fmx_fm_stream).  Returns per-launch ms [sort, forward, update, empty event pair] when timed (the measuring mode repeats launches: see fmx.h)."""
@@ -199,9 +213,11 @@ class FMEngine:
         self._ensure(B)
         out = self._fwd_out(want_first=False, want_bi=False)
         ms = (C.c_float * 4)() if timed else None
+        self._steps(hyper)
         _lib.check(self.lib.fmx_fm_stream(self.table.c_struct(), hyper.ref(), _lib.RULES[rule], _lib.LOSSES[loss],
                                           idx_pool.data_ptr(), y_pool.data_ptr(), n_pool, B, 1.0 / B, n_steps,
                                           self.workspace.data_ptr(), self._ws_bytes(), C.byref(out), _ptr(loss_out), ms, self._stream()))
+        self._advance(n_steps)
         return None if ms is None else [float(v) for v in ms]
 
     def prepare_stream(self, hyper, rule, loss, idx_pool, y_pool, loss_out=None, stream=None):
@@ -222,10 +238,14 @@ class FMEngine:
         cap = None if loss_out is None else loss_out.numel()
         keep = (out, hyper, idx_pool, y_pool, loss_out, self.workspace)   # referenced by the closure: stay alive with it
 
+        steps, advance = self._steps, self._advance
+
         def run(n_steps):
             if cap is not None and n_steps > cap:
                 raise ValueError(f"loss_out holds {cap} steps, {n_steps} asked for")
+            steps(hyper)
             check(fn(*fixed, n_steps, *tail))
+            advance(n_steps)        # (the bound struct is hyper's own: a second call continues the table's count)
         run.keep = keep
         return run
 
@@ -301,9 +321,11 @@ class FMEngine:
         N = idx_d.shape[0]
         pred = torch.empty(N, dtype=torch.uint8, device=self.device)
         loss_b = torch.empty(N, dtype=torch.float32, device=self.device) if want_loss else None
+        self._steps(hyper)
         _lib.check(self.lib.fmx_fm_online_run(self.table.c_struct(), hyper.ref(), _lib.RULES[rule], _lib.LOSSES[loss],
                                               idx_d.data_ptr(), _ptr(xv_d), y_d.data_ptr(), N, pred.data_ptr(), _ptr(loss_b),
                                               self.error.data_ptr(), self._stream()))
+        self._advance(N)
         return pred, loss_b
 
     def online_run_mlp(self, hyper, rule, loss, params, k, hidden, n_layers, hedge, fm_term, hedge_b, hedge_s, alpha,

@@ -45,6 +45,9 @@ class HipOwnerBackend:
 
     def __init__(self, feature_sizes, k, hyper, rule, loss, rank, world, layout=None, ftrl=None, device=None, max_local_batch=4096,
                  plan=None):
+        if rule in _lib.ADAPTIVE_RULES:
+            raise ValueError(f"{type(self).__name__}: update_rule {rule!r} is single-GPU only (FMEngine / the model classes); "
+                             "the multi-GPU trainers take 'signadam', 'sgd' and 'ftrl'")
         self.rank, self.world, self.rule, self.loss, self.hyper = rank, world, rule, loss, hyper
         self.feature_sizes = [int(s) for s in feature_sizes]
         self.plan = plan if plan is not None else OwnerPlan(self.feature_sizes, k, world, global_batch=max_local_batch * world)

@@ -7,6 +7,8 @@ gathers of one 64-byte request each, inside one 128-byte line (layouts in includ
     weights layout   [ V[0..kp) | w | pad ]                                         (rules 'signadam', 'sgd')
     ftrl layout      [ V[0..kp) | w, zw, nw, 0 | pad | zV[0..kp) | nV[0..kp) ]      (rule 'ftrl'; state is (z, n), V and
                                                                                      w are the weights derived from it)
+    moments layout   [ V[0..kp) | w, mw, vw, 0 | pad | mV[0..kp) | vV[0..kp) ]      (rules 'adam', 'adagrad'; V and w are
+                                                                                     the parameters, (m, v) their moments)
 """
 import ctypes as C
 
@@ -59,8 +61,9 @@ class FlatTable:
         self.k = int(k)
         self.kp = padded_k(self.k)
         self.layout = layout
-        if layout not in ("weights", "ftrl"):
+        if layout not in _lib.LAYOUTS:
             raise ValueError(layout)
+        self.step = 0       # moments layout: the steps the table has taken (FMEngine advances it; the adam rule's t - 1)
         self.ftrl = dict(alpha=0.05, beta=1.0, l1=0.0, l2=0.0)
         if ftrl:
             self.ftrl.update({k_: float(v) for k_, v in ftrl.items() if k_ in self.ftrl})
@@ -70,7 +73,7 @@ class FlatTable:
             need = kp + 4
             default = _round_up(need, 32) if kp >= 16 else 2 * kp      # k = 16: one 128-byte line per row
         else:
-            # the (z, n) half starts on its own 128-byte line for kp >= 16; smaller rows share one line
+            # the (z, n) / (m, v) half starts on its own 128-byte line for kp >= 16; smaller rows share one line
             self.z_offset = _round_up(kp + 4, 32) if kp >= 16 else 2 * kp
             need = self.z_offset + 2 * kp
             default = _round_up(need, 32) if kp >= 16 else 4 * kp
@@ -95,7 +98,7 @@ class FlatTable:
         if self.mapped:
             self.field_cols = torch.tensor(self.field_cols_host, dtype=torch.int32, device=self.device)
             self.field_base = torch.tensor(self.field_base_host, dtype=torch.int32, device=self.device)
-        self.bias = torch.zeros(1 if layout == "weights" else 2, dtype=torch.float32, device=self.device)
+        self.bias = torch.zeros({"weights": 1, "ftrl": 2, "moments": 4}[layout], dtype=torch.float32, device=self.device)
         self._cstruct = None
         self._sort_split = None
         self.sort_cap_override = None
@@ -110,7 +113,7 @@ class FlatTable:
             t.n_rows = self.n_rows
             t.n_fields = self.n_fields
             t.k, t.kp, t.row_stride = self.k, self.kp, self.row_stride
-            t.layout = _lib.LAYOUT_WEIGHTS if self.layout == "weights" else _lib.LAYOUT_FTRL
+            t.layout = _lib.LAYOUTS[self.layout]
             t.z_offset = self.z_offset
             t.max_field_rows = max(self.feature_sizes)
             if self._sort_split is not None:
@@ -169,12 +172,12 @@ class FlatTable:
     # ---- reference-shaped import / export ----
     def load_reference(self, first_list, second_list):
         """first_list[f]: [size_f, 1]; second_list[f]: [size_f, k] (reference nn.Embedding weights).
-        FTRL layout: n = 0 and the z that reproduces these weights."""
+        FTRL layout: n = 0 and the z that reproduces these weights.  Moments layout: the weights, moments zero."""
         V = torch.cat([torch.as_tensor(t, dtype=torch.float32).reshape(s, self.k)
                        for t, s in zip(second_list, self.feature_sizes)]).to(self.device)
         w = torch.cat([torch.as_tensor(t, dtype=torch.float32).reshape(s)
                        for t, s in zip(first_list, self.feature_sizes)]).to(self.device)
-        if self.layout == "weights":
+        if self.layout in ("weights", "moments"):
             self.rows.zero_()
             self.rows[:, :self.k] = V
             self.rows[:, self.kp] = w
@@ -212,15 +215,37 @@ class FlatTable:
         r = self.rows.detach().cpu()
         return (r[:, zo:zo + k].clone(), r[:, zo + kp:zo + kp + k].clone(), r[:, kp + 1].clone(), r[:, kp + 2].clone())
 
+    # ---- moments layout: the (m, v) state of the adaptive rules next to the parameters (adagrad: v holds G, m stays 0) ----
+    def export_moments_state(self):
+        """{'mV' [R,k], 'vV' [R,k], 'mw' [R], 'vw' [R], 'bias_mv' [2], 'step'} on the CPU (rows flat over the fields)."""
+        assert self.layout == "moments"
+        kp, k, zo = self.kp, self.k, self.z_offset
+        r = self.rows.detach().cpu()
+        return {"mV": r[:, zo:zo + k].clone(), "vV": r[:, zo + kp:zo + kp + k].clone(), "mw": r[:, kp + 1].clone(),
+                "vw": r[:, kp + 2].clone(), "bias_mv": self.bias[1:3].detach().cpu().clone(), "step": int(self.step)}
+
+    def load_moments_state(self, st):
+        """Restore the state export_moments_state() returned, bit for bit; the parameters (V, w, bias weight) are left as
+        they are."""
+        assert self.layout == "moments"
+        kp, k, zo, dev = self.kp, self.k, self.z_offset, self.device
+        f32 = dict(dtype=torch.float32)
+        self.rows[:, zo:zo + k] = torch.as_tensor(st["mV"], **f32).to(dev)
+        self.rows[:, zo + kp:zo + kp + k] = torch.as_tensor(st["vV"], **f32).to(dev)
+        self.rows[:, kp + 1] = torch.as_tensor(st["mw"], **f32).to(dev)
+        self.rows[:, kp + 2] = torch.as_tensor(st["vw"], **f32).to(dev)
+        self.bias[1:3] = torch.as_tensor(st["bias_mv"], **f32).to(dev)
+        self.step = int(st["step"])
+
     def bias_weight(self):
         """The bias as a 0-d device tensor (FTRL: derived from its (z, n) pair)."""
-        if self.layout == "weights":
+        if self.layout in ("weights", "moments"):
             return self.bias[0]
         return ftrl_weight_torch(self.bias[0], self.bias[1], self.ftrl)
 
     def set_bias_weight(self, value):
         value = float(value)
-        if self.layout == "weights":
+        if self.layout in ("weights", "moments"):
             self.bias[0] = value
         else:
             self.bias[0] = float(ftrl_z_for_weight_torch(torch.tensor(value), self.ftrl))

@@ -44,7 +44,12 @@ class OnlineFMBase(nn.Module):
     _loss_fit = "sigmoid"
 
     def __init__(self, feature_sizes, embedding_size=4, num_hidden_layers=0, neuron_per_hidden_layer=0, batch_size=1,
-                 num_classes=1, b=0.99, n=0.01, s=0.2, use_cuda=True, update_rule="signadam", ftrl=None):
+                 num_classes=1, b=0.99, n=0.01, s=0.2, use_cuda=True, update_rule="signadam", ftrl=None, adam=None,
+                 adagrad=None):
+        """update_rule: 'signadam' (the reference's fresh Adam per call), 'sgd', 'ftrl' (settings ftrl=dict(alpha, beta, l1,
+        l2)), or the persistent adaptive rules 'adam' (torch.optim.SparseAdam on the tables; adam=dict(beta1, beta2, eps)) and
+        'adagrad' (torch.optim.Adagrad; adagrad=dict(eps)).  Every rule's learning rate is n.  The hyper-parameters reach
+        the kernels as fp32: the betas in effect are float32(beta1), float32(beta2)."""
         super().__init__()
         if not (use_cuda and torch.cuda.is_available()):
             raise RuntimeError(f"{self._name}: this build runs the hot path in gfx950 kernels only -- it needs use_cuda=True "
@@ -59,7 +64,7 @@ class OnlineFMBase(nn.Module):
         self.num_classes = num_classes
         self.dtype = torch.long
         self.update_rule = update_rule
-        if update_rule not in ("signadam", "sgd", "ftrl"):
+        if update_rule not in ("signadam", "sgd", "ftrl", "adagrad", "adam"):
             raise ValueError(update_rule)
 
         # ---- parameter initialisation in the reference's RNG order (reference fm_adam.py:26-32,
@@ -78,12 +83,19 @@ class OnlineFMBase(nn.Module):
         self._ftrl = dict(alpha=0.05, beta=1.0, l1=0.0, l2=0.0)
         if ftrl:
             self._ftrl.update(ftrl)
-        self._table = fmx.FlatTable(feature_sizes, embedding_size, layout="ftrl" if update_rule == "ftrl" else "weights",
-                                    device=self.device, ftrl=self._ftrl)
+        self._adam = dict(beta1=0.9, beta2=0.999, eps=1e-8)           # torch.optim.Adam / SparseAdam defaults
+        if adam:
+            self._adam.update({k_: float(v) for k_, v in adam.items() if k_ in self._adam})
+        self._adagrad = dict(eps=1e-10)                                # torch.optim.Adagrad's default
+        if adagrad:
+            self._adagrad.update({k_: float(v) for k_, v in adagrad.items() if k_ in self._adagrad})
+        adaptive = update_rule in ("adagrad", "adam")
+        layout = "ftrl" if update_rule == "ftrl" else "moments" if adaptive else "weights"
+        self._table = fmx.FlatTable(feature_sizes, embedding_size, layout=layout, device=self.device, ftrl=self._ftrl)
         self._load_weights(first, second, bias0)
         del first, second
         self._engine = fmx.FMEngine(self._table, max_batch=max(int(batch_size), 64))
-        self._hyper = fmx.Hyper(lr=float(n), eps=1e-8, **self._ftrl)
+        self._hyper = self._make_hyper(n)
 
         layers = []
         if self._has_mlp:
@@ -100,12 +112,30 @@ class OnlineFMBase(nn.Module):
                 for p in (layer.weight, layer.bias):
                     p.data = self._mlp_flat[off:off + p.numel()].view(p.shape)
                     off += p.numel()
+            # the adaptive rules: ONE optimizer over the hidden layers for the model's life (its state persists like the
+            # tables' moments); the ONN classes train them by Hedge instead
+            self._mlp_opt = None
+            if adaptive and not self._onn:
+                params = self.hidden_layers.parameters()
+                if update_rule == "adam":
+                    self._mlp_opt = torch.optim.Adam(params, lr=float(n), betas=self._betas(), eps=self._adam["eps"])
+                else:
+                    self._mlp_opt = torch.optim.Adagrad(params, lr=float(n), eps=self._adagrad["eps"])
         if self._onn:
             # a plain device tensor (on a GPU the reference's Parameter(...).to(device) is one too)
             self.alpha = torch.full((num_hidden_layers,), 1 / (num_hidden_layers + 1), dtype=torch.float32,
                                     device=self.device)
         self.first_order_embeddings = [_FieldView(self._table, f, False) for f in range(self.field_size)]
         self.second_order_embeddings = [_FieldView(self._table, f, True) for f in range(self.field_size)]
+
+    def _betas(self):
+        """The betas the kernels use (fp32 in fmx_hyper_t), as Python floats: the hidden layers' optimizer takes the same."""
+        return (float(np.float32(self._adam["beta1"])), float(np.float32(self._adam["beta2"])))
+
+    def _make_hyper(self, n):
+        eps = {"adam": self._adam["eps"], "adagrad": self._adagrad["eps"]}.get(self.update_rule, 1e-8)
+        b1, b2 = self._betas()
+        return fmx.Hyper(lr=float(n), eps=eps, beta1=b1, beta2=b2, **self._ftrl)
 
     # ------------------------------------------------------------------------------------------------------
     # table <-> reference-shaped weights
@@ -154,7 +184,7 @@ class OnlineFMBase(nn.Module):
         self._load_weights(first, second, sd["bias"].float().cpu())
         with torch.no_grad():
             self.n.copy_(sd["n"].float().cpu())
-            self._hyper = fmx.Hyper(lr=float(self.n), eps=1e-8, **self._ftrl)
+            self._hyper = self._make_hyper(float(self.n))
             if self._has_mlp:
                 for j, layer in enumerate(self.hidden_layers):
                     layer.weight.copy_(sd[f"hidden_layers.{j}.weight"].float().to(self.device))
@@ -188,24 +218,51 @@ class OnlineFMBase(nn.Module):
             self._table.V.copy_(torch.as_tensor(st["V_cached"], dtype=torch.float32).to(self.device))
             self._table.w.copy_(torch.as_tensor(st["w_cached"], dtype=torch.float32).to(self.device))
 
+    # ---- the state of the adaptive rules ('adam', 'adagrad'; extensions like 'ftrl'): state_dict() holds the parameters;
+    #      a resumed run also needs every coordinate's moments, the table's step count and the hidden layers' optimizer ----
+    def optimizer_state_dict(self):
+        """{'table': FlatTable.export_moments_state() (mV, vV, mw, vw, bias_mv, step), 'mlp': the hidden layers'
+        torch optimizer state_dict or None} on the CPU; None for the other rules."""
+        if self.update_rule not in ("adagrad", "adam"):
+            return None
+        opt = getattr(self, "_mlp_opt", None)
+        mlp = None
+        if opt is not None:
+            mlp = opt.state_dict()
+            mlp = {"state": {i: {k_: (v.detach().cpu().clone() if torch.is_tensor(v) else v) for k_, v in st.items()}
+                             for i, st in mlp["state"].items()}, "param_groups": mlp["param_groups"]}
+        return {"table": self._table.export_moments_state(), "mlp": mlp}
+
+    def load_optimizer_state_dict(self, st):
+        """Restore what optimizer_state_dict() returned, bit for bit (the parameters come from load_state_dict)."""
+        if self.update_rule not in ("adagrad", "adam"):
+            raise ValueError("load_optimizer_state_dict: this model does not use update_rule 'adam' or 'adagrad'")
+        self._table.load_moments_state(st["table"])
+        if st.get("mlp") is not None and getattr(self, "_mlp_opt", None) is not None:
+            self._mlp_opt.load_state_dict(st["mlp"])
+
     # pickle support (reference main_experiment.py:160-162 pickles the whole model): tensors go through the CPU
     def __getstate__(self):
         return {"ctor": dict(feature_sizes=list(self.feature_sizes), embedding_size=self.embedding_size,
                              num_hidden_layers=self.num_hidden_layers,
                              neuron_per_hidden_layer=self.neuron_per_hidden_layer, batch_size=self.batch_size,
-                             num_classes=self.num_classes, update_rule=self.update_rule, ftrl=dict(self._ftrl)),
+                             num_classes=self.num_classes, update_rule=self.update_rule, ftrl=dict(self._ftrl),
+                             adam=dict(self._adam), adagrad=dict(self._adagrad)),
                 "cls": self._name, "state_dict": {k: v.cpu() for k, v in self.state_dict().items()},
-                "ftrl_state": self.ftrl_state_dict()}
+                "ftrl_state": self.ftrl_state_dict(), "optimizer_state": self.optimizer_state_dict()}
 
     def __setstate__(self, state):
         ctor = state["ctor"]
         OnlineFMBase.__init__(self, ctor["feature_sizes"], embedding_size=ctor["embedding_size"],
                               num_hidden_layers=ctor["num_hidden_layers"],
                               neuron_per_hidden_layer=ctor["neuron_per_hidden_layer"], batch_size=ctor["batch_size"],
-                              num_classes=ctor["num_classes"], update_rule=ctor["update_rule"], ftrl=ctor["ftrl"])
+                              num_classes=ctor["num_classes"], update_rule=ctor["update_rule"], ftrl=ctor["ftrl"],
+                              adam=ctor.get("adam"), adagrad=ctor.get("adagrad"))
         self.load_state_dict(state["state_dict"])
         if state.get("ftrl_state") is not None:       # after the weights: (z, n) is the state, V / w / bias follow from it
             self.load_ftrl_state_dict(state["ftrl_state"])
+        if state.get("optimizer_state") is not None:
+            self.load_optimizer_state_dict(state["optimizer_state"])
 
     # ------------------------------------------------------------------------------------------------------
     # forward pieces (reference deepfm_adam.py:46-89)
@@ -361,14 +418,15 @@ class OnlineFMBase(nn.Module):
         e, k = self._engine, self.embedding_size
         e.sort(idx_d)
         B = e.forward(self._hyper, idx_d, xv_d)
-        if self.update_rule != "ftrl" and e.mlp_fits(B, k, self.neuron_per_hidden_layer, self.num_hidden_layers, "fit"):
+        fused = self.update_rule in ("signadam", "sgd")     # the fused MLP kernels apply those two rules only
+        if fused and e.mlp_fits(B, k, self.neuron_per_hidden_layer, self.num_hidden_layers, "fit"):
             # one launch: MLP forward, loss, backward, fresh-Adam update of the hidden layers; then the table update
             dz, gbi = e.mlp_fit(self._mlp_flat, k, self.neuron_per_hidden_layer, self.num_hidden_layers, self._hyper,
                                 self.update_rule, self._loss_fit, self._base_logit(B).contiguous(), y_d, B)
             e.update(self._hyper, self.update_rule, B, xv_d, dz, dz if self._fm_term_in_forward else None, gbi,
                      with_loss=False)
             return
-        if self.update_rule != "ftrl" and getattr(self, "native_mlp", True):
+        if fused and getattr(self, "native_mlp", True):
             # mini-batch sizes: the MLP section as fp32 MFMA GEMMs (fmx_mlp_section); the hidden layers then take the
             # closed form of the reference's fresh-Adam first step, p -= lr * g / (|g| + 1e-8) (or plain SGD)
             if getattr(self, "_mlp_gflat", None) is None:
@@ -402,6 +460,9 @@ class OnlineFMBase(nn.Module):
         gbi = gbi.contiguous()
         e.update(self._hyper, self.update_rule, B, xv_d, dz, dz if self._fm_term_in_forward else None, gbi,
                  with_loss=False)
+        if self._mlp_opt is not None:        # 'adam' / 'adagrad': the model's one persistent optimizer
+            self._mlp_opt.step()
+            return
         # hidden layers: literally the reference's optimizer (a new Adam, first step)
         torch.optim.Adam(self.hidden_layers.parameters(), lr=float(self.n)).step()
 
@@ -498,7 +559,7 @@ class OnlineFMBase(nn.Module):
         H, L = self.neuron_per_hidden_layer, self.num_hidden_layers
         if self._onn:
             return self.batch_size == 1 and e.mlp_fits(1, k, H, L, "hedge")
-        return self.update_rule != "ftrl" and e.mlp_fits(1, k, H, L, "fit")
+        return self.update_rule in ("signadam", "sgd") and e.mlp_fits(1, k, H, L, "fit")
 
     def _run_experiment_on_device(self, data_Xi, data_Xv, data_Y):
         """The whole predict-then-fit loop on the device, same arithmetic as predict() + fit() per sample: pure FM as one

@@ -38,13 +38,17 @@
  *   FMX_LAYOUT_WEIGHTS  row = [ V[0..kp) | w | pad ]                                  row_stride >= kp + 4
  *   FMX_LAYOUT_FTRL     row = [ V[0..kp) | w, zw, nw, 0 | pad | zV[0..kp) | nV[0..kp) ]    zV at float z_offset,
  *                                                                                     row_stride >= z_offset + 2*kp
+ *   FMX_LAYOUT_MOMENTS  row = [ V[0..kp) | w, mw, vw, 0 | pad | mV[0..kp) | vV[0..kp) ]    the FTRL geometry and checks;
+ *                                                                                     mV at float z_offset
  * kp is k rounded up to 4, 8, 16, 32 or 64; the pad components must be zero (they then stay zero under every
- * rule).  row_stride and z_offset are in floats and multiples of 4 (16-byte pieces).  Both layouts start with the
+ * rule).  row_stride and z_offset are in floats and multiples of 4 (16-byte pieces).  All layouts start with the
  * weights the forward pass reads, so a forward gather is ONE 64-byte request per row (k = 16) inside one 128-byte
  * line.  In the FTRL layout the state is (z, n); V and w are the weights derived from it,
  *     w = 0 if |z| <= l1 else -(z - sgn(z) l1) / ((beta + sqrt(n)) / alpha + l2)      (McMahan et al. 2013),
  * re-derived and stored by every update -- a cache, never an independent parameter: whoever writes (z, n) or changes
- * the hyper-parameters must rewrite V and w with the same formula.
+ * the hyper-parameters must rewrite V and w with the same formula.  In the MOMENTS layout the head of the row IS the
+ * parameter and (m, v) are the first and second moments of FMX_RULE_ADAM (FMX_RULE_ADAGRAD keeps its sum of squared
+ * gradients in the v slots and leaves the m slots untouched: zero).
  */
 #ifndef FMX_H
 #define FMX_H
@@ -56,8 +60,9 @@ extern "C" {
 #endif
 
 #define FMX_VERSION 104 /* 0.1.4: fmx_deepfm_stream, fmx_fm_topk / fmx_fm_topk_workspace_bytes, fmx_mlp_topk /
-                           fmx_mlp_topk_workspace_bytes (0.1.3: fields as row-range pieces of index columns -- field_cols /
-                           field_base / n_cols --, workspace_bytes arguments, fmx_owner_*) */
+                           fmx_mlp_topk_workspace_bytes; FMX_LAYOUT_MOMENTS, FMX_RULE_ADAGRAD / FMX_RULE_ADAM and the fields
+                           appended to fmx_hyper_t, backward compatible as stated there; 0.1.3: fields as row-range pieces
+                           of index columns -- field_cols / field_base / n_cols --, workspace_bytes arguments, fmx_owner_* */
 
 typedef void *fmx_stream_t; /* hipStream_t */
 
@@ -70,15 +75,26 @@ enum fmx_status {
   FMX_ERR_UNSUPPORTED = -5  /* valid request the kernels do not cover (batch too large for the LDS sort, ...) */
 };
 
-enum fmx_layout { FMX_LAYOUT_WEIGHTS = 0, FMX_LAYOUT_FTRL = 1 };
+enum fmx_layout { FMX_LAYOUT_WEIGHTS = 0, FMX_LAYOUT_FTRL = 1, FMX_LAYOUT_MOMENTS = 2 };
 
 /* per-coordinate update rules (g = gradient summed over every occurrence of the row in the mini-batch) */
 enum fmx_rule {
   FMX_RULE_SIGNADAM = 0, /* p -= lr * g / (|g| + eps): what a fresh torch.optim.Adam per call reduces to
                             (reference fm_adam.py:60,68 / :75,82).  FMX_LAYOUT_WEIGHTS */
   FMX_RULE_SGD = 1,      /* p -= lr * g (stale notebook prototypes only; parity unpinned).  FMX_LAYOUT_WEIGHTS */
-  FMX_RULE_FTRL = 2      /* FTRL-proximal on (z, n) (not in the reference; parity unpinned).  FMX_LAYOUT_FTRL */
+  FMX_RULE_FTRL = 2,     /* FTRL-proximal on (z, n) (not in the reference; parity unpinned).  FMX_LAYOUT_FTRL */
+  /* The persistent adaptive rules (not in the reference; torch.optim.Adagrad / torch.optim.SparseAdam on
+     nn.Embedding(sparse=True)).  FMX_LAYOUT_MOMENTS.  Lazy: a row is touched when its index occurs in the batch, whatever
+     its x (x = 0 included); untouched rows keep their bits.  The bias is one more coordinate, touched by every step. */
+  FMX_RULE_ADAGRAD = 3,  /* G += g*g;  p -= lr * g / (sqrt(G) + eps)                    (lr_decay = weight_decay = 0) */
+  FMX_RULE_ADAM = 4      /* m += (1-beta1)(g - m);  v += (1-beta2)(g*g - v);
+                            p -= step_size * m / (sqrt(v) + eps),  step_size = lr sqrt(1 - beta2^t) / (1 - beta1^t),
+                            t = fmx_hyper_t.step + 1 (torch.optim.SparseAdam's order of operations) */
 };
+/* The adaptive rules are taken by fmx_fm_update, fmx_fm_step, fmx_fm_stream and fmx_fm_online_run on a MOMENTS table.
+ * fmx_deepfm_stream, fmx_online_run_mlp (fit mode), fmx_mlp_fit and fmx_owner_step return FMX_ERR_UNSUPPORTED for them.
+ * A MOMENTS table is accepted wherever a table is only read (fmx_fm_forward, fmx_fm_forward_partial / _finish, the Hedge
+ * mode of fmx_online_run_mlp): the bias weight is bias[0], as in the weights layout. */
 
 /* loss applied to the FM logit z in the fused epilogue of fmx_fm_forward */
 enum fmx_loss {
@@ -90,14 +106,14 @@ enum fmx_loss {
 typedef struct fmx_table {
   float *rows;                  /* [n_rows, row_stride] */
   const int64_t *field_offsets; /* [n_fields + 1] prefix sums of the per-field vocabulary sizes */
-  float *bias;                  /* WEIGHTS: [1] = bias;  FTRL: [2] = (z, n) of the bias */
+  float *bias;                  /* WEIGHTS: [1] = bias;  FTRL: [2] = (z, n) of the bias;  MOMENTS: [4] = (b, m_b, v_b, 0) */
   int64_t n_rows;
   int32_t n_fields;
   int32_t k;          /* embedding size */
   int32_t kp;         /* k padded to 4 / 8 / 16 / 32 / 64 */
   int32_t row_stride; /* floats */
   int32_t layout;     /* enum fmx_layout */
-  int32_t z_offset;   /* FTRL: float offset of zV inside the row (multiple of 4, >= kp + 4); WEIGHTS: ignored */
+  int32_t z_offset;   /* FTRL / MOMENTS: float offset of zV / mV inside the row (multiple of 4, >= kp + 4); WEIGHTS: ignored */
   int64_t max_field_rows; /* largest per-field vocabulary (host copy; bounds the sort's composite keys) */
   /* SORT FIELDS (optional; n_sort_fields = 0: the fields themselves).  The occurrence lists and the update work per "sort
    * field".  An occurrence list packs (index, sample) into 32 bits, so a field of 176,373 rows (18 bits) leaves 14 bits for
@@ -126,8 +142,15 @@ typedef struct fmx_table {
 } fmx_table_t;
 
 typedef struct fmx_hyper {
-  float lr, eps;             /* SIGNADAM / SGD */
+  float lr, eps;             /* SIGNADAM / SGD / ADAGRAD / ADAM */
   float alpha, beta, l1, l2; /* FTRL */
+  /* APPENDED with the adaptive rules: the struct grew from 24 to 40 bytes.  The library reads them for FMX_RULE_ADAM only, so a
+     caller compiled against the six-float struct keeps working with every other rule; FMX_RULE_ADAM needs the 40-byte form. */
+  float beta1, beta2;        /* ADAM */
+  int32_t step;              /* ADAM: steps this table has already taken; the call's first step is t = step + 1.
+                                fmx_fm_stream: step s of the call uses t = step + s + 1; fmx_fm_online_run: sample i uses
+                                t = step + i + 1.  The library never writes it back: the caller advances its count. */
+  int32_t reserved;
 } fmx_hyper_t;
 
 /* Outputs of the forward pass.  Any pointer may be null except S when an update follows. */
