@@ -91,11 +91,24 @@ struct FwdArgs {
   int32_t Fc;
 };
 
+#ifdef FMX_STAMPS  // diagnostic build (tools/forward_stamps.sh): s_memrealtime (100 MHz) of every wave of the LAST k_fm_forward launch
+__device__ unsigned long long g_fwd_stamps[8192 * 6];
+#define FMX_FSTAMP(slot_, dep_)                                                                                     \
+  do {                                                                                                              \
+    unsigned long long t_;                                                                                          \
+    asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_) : "v"(dep_) : "memory");                      \
+    if (lane == 0 && b < 8192) g_fwd_stamps[(size_t)b * 6 + (slot_)] = t_;                                           \
+  } while (0)
+#else
+#define FMX_FSTAMP(slot_, dep_) do {} while (0)
+#endif
+
 // The part of the forward pass behind the row gather: field sums (butterfly over the lane groups), bi-interaction, logit,
-// loss and dlogit, stores.  s / ss / fo: this lane's partial sums of e, e*e and of the first-order terms over ITS fields.
-template <int LPR, int LAYOUT>
+// loss and dlogit, stores.  s / ss / fo: this lane's partial sums of e, e*e and of the first-order terms over ITS fields;
+// bias: the bias weight (resolved while the rows were in flight).
+template <int LPR>
 __device__ __forceinline__ void forward_finish(const FwdArgs &a, const int b, const int lane, float4 s, float4 ss, float fo, bool bad,
-                                               const float y_early, const float bias0_early, const float bias1_early) {
+                                               const float y_early, const float bias) {
   const int q = lane % LPR;
   const int kp = LPR * 4;
   if (bad && a.out.error) *a.out.error = 1;
@@ -115,15 +128,13 @@ __device__ __forceinline__ void forward_finish(const FwdArgs &a, const int b, co
   for (int m = 1; m < LPR; m <<= 1) sbi += __shfl_xor(sbi, m);
   // fo: lanes with q != 0 hold the sum of zeros; take the q == 0 value
   fo = __shfl(fo, 0);
+  FMX_FSTAMP(3, sbi);
 
   if (lane < LPR) {
     if (a.out.S) *reinterpret_cast<float4 *>(a.out.S + (size_t)b * a.ldS + 4 * q) = s;
     if (a.out.bi) *reinterpret_cast<float4 *>(a.out.bi + (size_t)b * kp + 4 * q) = bi;
   }
   if (lane == 0) {
-    float bias;
-    if (LAYOUT == FMX_LAYOUT_WEIGHTS) bias = bias0_early;
-    else bias = ftrl_w(bias0_early, bias1_early, a.h);
     const float z = fo + sbi + bias;
     if (a.out.sfirst) a.out.sfirst[b] = fo;
     if (a.out.sbi) a.out.sbi[b] = sbi;
@@ -139,88 +150,115 @@ __device__ __forceinline__ void forward_finish(const FwdArgs &a, const int b, co
         loss = bcewl(p, y);
         dz = (sigmoidf_(p) - y) * p * (1.f - p) * a.inv_b;
       }
+      FMX_FSTAMP(4, dz);
       if (a.out.loss) a.out.loss[(size_t)b * a.ld1] = loss;
       if (a.out.dz) a.out.dz[(size_t)b * a.ld1] = dz;
     }
+    FMX_FSTAMP(5, z);
   }
 }
 
-// NPASS > 0: the field loop is fully unrolled (F <= NPASS * SLOTS) and every index, value, offset and row load of the
-// sample is issued before the first use, so one wave keeps up to 3 * NPASS row requests in flight.  NPASS == 0: generic.
+// 64-bit lane exchange (two ds_bpermute)
+__device__ __forceinline__ int64_t shfl64(int64_t v, int src) {
+  const int lo = __shfl((int)(uint32_t)v, src), hi = __shfl((int)(v >> 32), src);
+  return (int64_t)(((uint64_t)(uint32_t)hi << 32) | (uint32_t)lo);
+}
+constexpr int64_t ROW_ABSENT = int64_t(1) << 62;  // set in a resolved row: the index lies outside the field (row = the field's first)
+
+// NPASS > 0: the field loop is fully unrolled (F <= NPASS * SLOTS) and every load of the sample is issued before the first
+// use.  NPASS == 0: generic.
+// The sample's fields are resolved ONE PER LANE first: lane l of a window of WAVE consecutive fields loads field l's offsets,
+// index and value and forms the table row, so the first round trip is one load per window of each (offsets, index, value)
+// however many passes the sample takes; the passes then take their rows from the window by lane exchanges.  The rows, the
+// order of the additions and so every result are those of k_fm_forward_part at one block, which loads per pass.
 // MAPPED (tables whose fields are pieces of index columns; the generic field loop only): field f reads column fcols[f], holds
 // the indices [fbase[f], fbase[f] + rows) of it, and an index outside belongs to another piece: no contribution, no error.
-template <int LPR, int LAYOUT, int NPASS, bool MAPPED = false>
+// HAS_X: xv is not null (without values every x is 1 and nothing is loaded for it).
+template <int LPR, int LAYOUT, int NPASS, bool MAPPED, bool HAS_X>
 __device__ __forceinline__ void forward_sample(const FwdArgs &a, const int b, const int lane) {
   constexpr int SLOTS = WAVE / LPR;
   constexpr int NP = NPASS > 0 ? NPASS : 1;
+  constexpr int NW = NPASS > 0 ? (NP * SLOTS + WAVE - 1) / WAVE : 1;  // windows of WAVE fields
   const int slot = lane / LPR, q = lane % LPR;
   const int kp = LPR * 4;
+  FMX_FSTAMP(0, lane);
 
   float4 s = splat(0.f), ss = splat(0.f);
   float fo = 0.f;
   bool bad = false;
-  // the label and the bias are only needed by lane 0's epilogue, but a load issued there is one more dependent round trip
+  // the label and the bias are only needed by the epilogue, but a load issued there is one more dependent round trip
   // at the end of every wave: request them now, with the indices (every lane the same address: one request each)
   const float y_early = a.loss_kind != FMX_LOSS_NONE ? a.y[b] : 0.f;
   const float bias0_early = a.bias[0];
   const float bias1_early = LAYOUT == FMX_LAYOUT_WEIGHTS ? 0.f : a.bias[1];
   __builtin_amdgcn_sched_barrier(0);  // (left to itself the scheduler sinks the bias load behind the first waits of the gather:
                                       //  in-order vmcnt then makes the row requests wait for it -- one more round trip)
+  float bias = 0.f;
   const int n_outer = NPASS > 0 ? 1 : (a.F + SLOTS - 1) / SLOTS;
   for (int it = 0; it < n_outer; ++it) {
-    uint32_t li[NP];
-    float x[NP];
-    int64_t lo[NP];
-    uint32_t vocab[NP];
-    bool live[NP];
-    // Branch-free: a lane group beyond the last field reads field F - 1's index and offsets, an index beyond the field's
+    // Branch-free: a lane beyond the last field reads field F - 1's index and offsets, an index beyond the field's
     // vocabulary reads the field's first row, and the results are dropped by selects.  With `if (live) { loads; arithmetic on
-    // them }` per pass the compiler put an s_waitcnt vmcnt(0) at the end of every pass's region: three dependent round trips
-    // for the indices of a 39-field sample instead of one.
-    const float *xsrc = a.xv ? a.xv : reinterpret_cast<const float *>(a.idx);  // something loadable when there are no values
-    const bool has_x = a.xv != nullptr;
-    float xl[NP];
-    int64_t hi[NP];
-    int fc[NP];
+    // them }` the compiler put an s_waitcnt vmcnt(0) at the end of every region: one dependent round trip per region.
+    int fl[NW];
+    bool wlive[NW];
+    int64_t lo[NW], hi[NW];
+    uint32_t li[NW];
+    float xl[NW];
 #pragma unroll
-    for (int p = 0; p < NP; ++p) {
-      const int f = (it * NP + p) * SLOTS + slot;
-      live[p] = f < a.F;
-      fc[p] = live[p] ? f : a.F - 1;
+    for (int w = 0; w < NW; ++w) {
+      const int f = (NPASS > 0 ? w * WAVE : it * SLOTS) + lane;
+      wlive[w] = f < a.F;
+      fl[w] = wlive[w] ? f : a.F - 1;
     }
 #pragma unroll
-    for (int p = 0; p < NP; ++p) {  // the offsets do not depend on the sample: first
-      lo[p] = a.foff[fc[p]];
-      hi[p] = a.foff[fc[p] + 1];
+    for (int w = 0; w < NW; ++w) {  // the offsets do not depend on the sample: first
+      lo[w] = a.foff[fl[w]];
+      hi[w] = a.foff[fl[w] + 1];
     }
 #pragma unroll
-    for (int p = 0; p < NP; ++p) {
-      size_t o = (size_t)b * a.F + fc[p];
+    for (int w = 0; w < NW; ++w) {
+      size_t o = (size_t)b * a.F + fl[w];
       uint32_t fb = 0u;
       if (MAPPED) {
-        o = (size_t)b * a.Fc + (a.fcols ? a.fcols[fc[p]] : fc[p]);
-        fb = a.fbase ? (uint32_t)a.fbase[fc[p]] : 0u;
+        o = (size_t)b * a.Fc + (a.fcols ? a.fcols[fl[w]] : fl[w]);
+        fb = a.fbase ? (uint32_t)a.fbase[fl[w]] : 0u;
       }
-      li[p] = (uint32_t)a.idx[o] - fb;  // (wraps to a huge value below the piece)
-      xl[p] = xsrc[o];
+      li[w] = (uint32_t)a.idx[o] - fb;  // (wraps to a huge value below the piece)
+      xl[w] = HAS_X ? a.xv[o] : 1.f;
     }
+    int64_t row[NW];
 #pragma unroll
-    for (int p = 0; p < NP; ++p) {
-      x[p] = has_x ? xl[p] : 1.f;
-      vocab[p] = (uint32_t)(hi[p] - lo[p]);
+    for (int w = 0; w < NW; ++w) {
+      const bool okw = wlive[w] && li[w] < (uint32_t)(hi[w] - lo[w]);
+      row[w] = lo[w] + (okw ? li[w] : 0u);
+      if (!okw) row[w] |= ROW_ABSENT;
+      bad = bad || (!MAPPED && wlive[w] && !okw);
     }
+    FMX_FSTAMP(1, (uint32_t)row[0]);
     // both layouts keep [ V | w ] at the head of the row: the forward never touches the FTRL (z, n) half
+    float x[NP];
     float4 r0[NP];
     float rw[NP];
-    bool ok[NP];
+    bool ok[NP], live[NP];
 #pragma unroll
     for (int p = 0; p < NP; ++p) {
-      ok[p] = live[p] && li[p] < vocab[p];
-      const float *rp = a.rows + (size_t)(lo[p] + (ok[p] ? li[p] : 0u)) * a.stride;
+      const int f = NPASS > 0 ? p * SLOTS + slot : slot;  // relative to the first field of the window set
+      const int w = NPASS > 0 ? (p * SLOTS) / WAVE : 0;
+      live[p] = (NPASS > 0 ? f : it * SLOTS + f) < a.F;
+      const int64_t r = shfl64(row[w], f % WAVE);
+      x[p] = HAS_X ? __shfl(xl[w], f % WAVE) : 1.f;
+      ok[p] = live[p] && !(r & ROW_ABSENT);
+      const float *rp = a.rows + (size_t)(r & ~ROW_ABSENT) * a.stride;
       r0[p] = *reinterpret_cast<const float4 *>(rp + 4 * q);
       rw[p] = rp[kp];  // (every lane of the group: the same address, one request)
     }
     __builtin_amdgcn_sched_barrier(0);  // ... and every row request before the first sum
+    // the bias weight while the rows are in flight (its loads came back with the window's)
+    if (it == 0) {
+      bias = LAYOUT == FMX_LAYOUT_WEIGHTS ? bias0_early : ftrl_w(bias0_early, bias1_early, a.h);
+      asm volatile("" ::"v"(bias));  // (otherwise the compiler sinks it into lane 0's epilogue, behind the butterfly)
+    }
+    __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
     for (int p = 0; p < NP; ++p) {
       const float4 e = x[p] * r0[p];
@@ -230,11 +268,11 @@ __device__ __forceinline__ void forward_sample(const FwdArgs &a, const int b, co
         ss = ss + e * e;
         fo += f1;
       }
-      bad = bad || (!MAPPED && live[p] && !ok[p]);
       if (live[p] && a.out.first && q == 0) a.out.first[(size_t)b * a.F + (it * NP + p) * SLOTS + slot] = f1;
     }
+    FMX_FSTAMP(2, s.x + ss.x + fo);  // (every row of the pass set arrived and added)
   }
-  forward_finish<LPR, LAYOUT>(a, b, lane, s, ss, fo, bad, y_early, bias0_early, bias1_early);
+  forward_finish<LPR>(a, b, lane, s, ss, fo, bad, y_early, bias);
 }
 
 template <int LPR, int LAYOUT, int NPASS, bool MAPPED = false>
@@ -242,7 +280,8 @@ __global__ __launch_bounds__(256) void k_fm_forward(FwdArgs a) {
   __builtin_amdgcn_s_setprio(3);  // ahead of the side-stream sort's waves at the CU's instruction arbiter
   const int b = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
   if (b >= a.B) return;  // wave-uniform
-  forward_sample<LPR, LAYOUT, NPASS, MAPPED>(a, b, threadIdx.x & 63);
+  if (a.xv) forward_sample<LPR, LAYOUT, NPASS, MAPPED, true>(a, b, threadIdx.x & 63);
+  else forward_sample<LPR, LAYOUT, NPASS, MAPPED, false>(a, b, threadIdx.x & 63);
 }
 
 // ------------------------------------------------------------------------------------------------------------
@@ -3020,6 +3059,9 @@ int fmx_gather_read(const void *buf, int64_t bytes, int32_t row_bytes, int64_t n
 #ifdef FMX_STAMPS
 int fmx_debug_update_stamps(unsigned long long *host_out) {  // [8192][6]; diagnostic build only (not in include/fmx.h)
   return hipMemcpyFromSymbol(host_out, HIP_SYMBOL(g_upd_stamps), sizeof(unsigned long long) * 8192 * 6) == hipSuccess ? FMX_OK : FMX_ERR_LAUNCH;
+}
+int fmx_debug_forward_stamps(unsigned long long *host_out) {  // [8192][6]; diagnostic build only (not in include/fmx.h)
+  return hipMemcpyFromSymbol(host_out, HIP_SYMBOL(g_fwd_stamps), sizeof(unsigned long long) * 8192 * 6) == hipSuccess ? FMX_OK : FMX_ERR_LAUNCH;
 }
 #endif
 
