@@ -1,0 +1,519 @@
+// fmx_afm.hip -- gfx950 kernels of the attentional factorization machine (AFM; Xiao et al. 2017) and its C ABI.
+//
+// The model (include/fmx.h, DESIGN.md section 3 "AFM"): per sample, e_f = x_f V[row_f], the P = F (F - 1) / 2 pairs in the fixed
+// order i = 0 .. F-2, j = i+1 .. F-1, q_ij = e_i (.) e_j, s_ij = h . relu(W q_ij + b), a = softmax(s), and
+//     logit = bias + sum_f w_f x_f + p . sum_ij a_ij q_ij.
+//
+//   k_afm<KP, FTRL, BWD>  one wavefront per workgroup; a workgroup walks the samples blockIdx.x, blockIdx.x + gridDim.x, ...
+//                         The sample's F x kp embeddings go to LDS once (lane f gathers field f's row).  The pairs are cut into
+//                         TILES of whole pair rows i (at most 64 pairs: one per lane); each lane evaluates its pair's W q + b,
+//                         relu, h and p products from LDS (the attention parameters sit in LDS for the whole launch) and leaves
+//                         (s, p . q) in LDS.  The softmax then runs over the sample's P scores in LDS: max, exp, sums.
+//                         BWD (the training step) walks the tiles again: every lane recomputes its pair's terms and leaves
+//                         dL/dq, q and the per-unit coefficients of the tile in LDS; the lanes then add the tile into
+//                         accumulators they OWN -- dW / db / dh / dp entries, and the (field, coordinate) entries of dL/de --
+//                         in pair order.  dL/dV_row = x dL/de goes to E [B, F, kp]; the attention accumulators leave the
+//                         launch as one partial per workgroup.
+//   k_afm_reduce          the partials of the workgroups summed in workgroup order into [ dW | db | dh | dp ].
+//
+// No float is accumulated with atomics and every sum has one fixed order that depends on (B, F, t, k) alone: results are
+// bit-identical run to run.  The table update between the two launches is fmx_fm_update_occ (fmx_kernels.hip).
+
+#include "fmx_common.h"
+
+namespace {
+
+constexpr int AFM_TILE = 64;       // pairs per tile at most: one per lane of the wavefront
+constexpr int AFM_MAX_WG = 1024;   // workgroups of a launch; with fewer samples, one workgroup per sample
+constexpr int AFM_MAX_F = 64, AFM_MAX_T = 64;
+
+inline int afm_grid(int B) { return B < AFM_MAX_WG ? B : AFM_MAX_WG; }
+__host__ __device__ inline int r4(int x) { return (x + 3) & ~3; }
+
+// LDS carving in floats (every section starts on 16 bytes): the sample's embeddings, the attention parameters (W rows padded to kp
+// with zeros), the pair scores; BWD: the tile's q, dL/dq, unit coefficients and dlogit x a, the sample's dL/de, the accumulators
+struct AfmLds {
+  int e, W, bW, h, p, s, r, q, c, co, hr, ga, Ea, aW, ab, ah, ap, total;
+};
+__host__ __device__ inline AfmLds afm_lds(int F, int kp, int t, bool bwd) {
+  AfmLds L;
+  const int P = F * (F - 1) / 2;
+  int o = 0;
+  L.e = o; o += F * kp;
+  L.W = o; o += t * kp;
+  L.bW = o; o += r4(t);
+  L.h = o; o += r4(t);
+  L.p = o; o += kp;
+  L.s = o; o += r4(P);
+  L.r = o; o += r4(P);
+  L.q = L.c = L.co = L.hr = L.ga = L.Ea = L.aW = L.ab = L.ah = L.ap = o;
+  if (bwd) {
+    L.q = o; o += AFM_TILE * kp;
+    L.c = o; o += AFM_TILE * kp;
+    L.co = o; o += r4(AFM_TILE * t);
+    L.hr = o; o += r4(AFM_TILE * t);
+    L.ga = o; o += AFM_TILE;
+    L.Ea = o; o += F * kp;
+    L.aW = o; o += t * kp;
+    L.ab = o; o += r4(t);
+    L.ah = o; o += r4(t);
+    L.ap = o; o += kp;
+  }
+  L.total = o;
+  return L;
+}
+
+struct AfmArgs {
+  const float *rows;
+  const int64_t *foff;
+  const float *bias;
+  const int32_t *idx;
+  const float *xv;
+  const float *y;
+  const float *params;  // [ W (t x k) | b (t) | h (t) | p (k) ]
+  float *logit, *loss, *dz;  // [B] each or null
+  float *E;                  // BWD: [B, F * kp]
+  float *part;               // BWD: [gridDim.x, G]
+  int32_t *error;
+  fmx_hyper_t h;
+  int32_t B, F, k, t, stride, loss_kind, G;
+  float inv_b;
+};
+
+// butterfly over the wavefront: every lane ends with the same bits (a + b == b + a at every level)
+__device__ __forceinline__ float wave_sum(float v) {
+#pragma unroll
+  for (int m = 1; m < WAVE; m <<= 1) v += __shfl_xor(v, m);
+  return v;
+}
+__device__ __forceinline__ float wave_max(float v) {
+#pragma unroll
+  for (int m = 1; m < WAVE; m <<= 1) v = fmaxf(v, __shfl_xor(v, m));
+  return v;
+}
+
+// the next tile: pair rows [i0, i1) holding n <= AFM_TILE pairs (a row has F - 1 - i <= 63 pairs: at least one row fits)
+__device__ __forceinline__ int next_tile(int F, int i0, int &n) {
+  int i1 = i0;
+  n = 0;
+  while (i1 < F - 1 && n + (F - 1 - i1) <= AFM_TILE) {
+    n += F - 1 - i1;
+    ++i1;
+  }
+  return i1;
+}
+
+// pair `l` of the tile starting at row i0 -> (i, j)
+__device__ __forceinline__ void tile_pair(int F, int i0, int l, int &i, int &j) {
+  i = i0;
+  while (l >= F - 1 - i) {
+    l -= F - 1 - i;
+    ++i;
+  }
+  j = i + 1 + l;
+}
+
+// q = e_i (.) e_j; r = p . q (d ascending); s = h . relu(W q + b) (u ascending, each unit's sum d ascending from b_u)
+template <int KP>
+__device__ __forceinline__ void pair_terms(const float *sm, const AfmLds &L, int t, int i, int j, float (&q)[KP], float &r, float &s) {
+#pragma unroll
+  for (int d = 0; d < KP; d += 4) {
+    const float4 a = *reinterpret_cast<const float4 *>(sm + L.e + i * KP + d);
+    const float4 b = *reinterpret_cast<const float4 *>(sm + L.e + j * KP + d);
+    q[d] = a.x * b.x;
+    q[d + 1] = a.y * b.y;
+    q[d + 2] = a.z * b.z;
+    q[d + 3] = a.w * b.w;
+  }
+  r = 0.f;
+#pragma unroll
+  for (int d = 0; d < KP; ++d) r = fmaf(sm[L.p + d], q[d], r);
+  s = 0.f;
+  for (int u = 0; u < t; ++u) {
+    float z = sm[L.bW + u];
+#pragma unroll
+    for (int d = 0; d < KP; ++d) z = fmaf(sm[L.W + u * KP + d], q[d], z);
+    s = fmaf(sm[L.h + u], fmaxf(z, 0.f), s);
+  }
+}
+
+template <int KP, bool FTRL, bool BWD>
+__global__ __launch_bounds__(64) void k_afm(AfmArgs a) {
+  extern __shared__ float4 lds4[];
+  float *sm = reinterpret_cast<float *>(lds4);
+  const int lane = threadIdx.x;
+  const int F = a.F, k = a.k, t = a.t, P = F * (F - 1) / 2;
+  const AfmLds L = afm_lds(F, KP, t, BWD);
+  for (int i = lane; i < t * KP; i += WAVE) {
+    const int u = i / KP, d = i - u * KP;
+    sm[L.W + i] = d < k ? a.params[u * k + d] : 0.f;
+  }
+  for (int u = lane; u < t; u += WAVE) {
+    sm[L.bW + u] = a.params[t * k + u];
+    sm[L.h + u] = a.params[t * k + t + u];
+  }
+  for (int d = lane; d < KP; d += WAVE) sm[L.p + d] = d < k ? a.params[t * k + 2 * t + d] : 0.f;
+  if (BWD) {
+    for (int i = lane; i < t * KP; i += WAVE) sm[L.aW + i] = 0.f;
+    for (int u = lane; u < t; u += WAVE) sm[L.ab + u] = sm[L.ah + u] = 0.f;
+    for (int d = lane; d < KP; d += WAVE) sm[L.ap + d] = 0.f;
+  }
+  const float bias_w = FTRL ? ftrl_w(a.bias[0], a.bias[1], a.h) : a.bias[0];
+
+  for (int b = blockIdx.x; b < a.B; b += gridDim.x) {
+    // ---- gather: lane f loads field f's row (an index outside its field: the row is absent, the error word says so) ----
+    float fo = 0.f;
+    if (lane < F) {
+      const int64_t base = a.foff[lane], rows_f = a.foff[lane + 1] - base;
+      const int ix = a.idx[(size_t)b * F + lane];
+      const float x = a.xv ? a.xv[(size_t)b * F + lane] : 1.f;
+      const bool ok = ix >= 0 && (int64_t)ix < rows_f;
+      if (!ok && a.error) *a.error = 1;
+      const float *rp = a.rows + (size_t)(base + (ok ? ix : 0)) * a.stride;
+#pragma unroll
+      for (int d = 0; d < KP; d += 4) {
+        const float4 v = ok ? *reinterpret_cast<const float4 *>(rp + d) : splat(0.f);
+        *reinterpret_cast<float4 *>(sm + L.e + lane * KP + d) = x * v;
+      }
+      fo = ok ? rp[KP] * x : 0.f;
+    }
+    fo = wave_sum(fo);
+    __syncthreads();
+
+    // ---- pass A: every pair's score s and p . q ----
+    for (int i0 = 0, pb = 0; i0 < F - 1;) {
+      int n;
+      const int i1 = next_tile(F, i0, n);
+      if (lane < n) {
+        int i, j;
+        tile_pair(F, i0, lane, i, j);
+        float q[KP], r, s;
+        pair_terms<KP>(sm, L, t, i, j, q, r, s);
+        sm[L.s + pb + lane] = s;
+        sm[L.r + pb + lane] = r;
+      }
+      pb += n;
+      i0 = i1;
+    }
+    __syncthreads();
+
+    // ---- softmax over the sample's pairs (max-subtracted); the logit, loss and dlogit ----
+    float mx = -INFINITY;
+    for (int l = lane; l < P; l += WAVE) mx = fmaxf(mx, sm[L.s + l]);
+    mx = wave_max(mx);
+    float Z = 0.f, N = 0.f;
+    for (int l = lane; l < P; l += WAVE) {
+      const float ex = expf(sm[L.s + l] - mx);
+      sm[L.s + l] = ex;  // (this lane's own slots: read by the other lanes after the barrier below)
+      Z += ex;
+      N += ex * sm[L.r + l];
+    }
+    Z = wave_sum(Z);
+    N = wave_sum(N);
+    const float att = N / Z;  // p . sum_ij a_ij q_ij
+    const float logit = (bias_w + fo) + att;
+    float loss = 0.f, g = 0.f;
+    if (a.loss_kind != FMX_LOSS_NONE) {
+      const float yv = a.y[b];
+      if (a.loss_kind == FMX_LOSS_BCE_LOGITS) {
+        loss = bcewl(logit, yv);
+        g = (sigmoidf_(logit) - yv) * a.inv_b;
+      } else {
+        const float pp = sigmoidf_(logit);
+        loss = bcewl(pp, yv);
+        g = (sigmoidf_(pp) - yv) * pp * (1.f - pp) * a.inv_b;
+      }
+    }
+    if (lane == 0) {
+      if (a.logit) a.logit[b] = logit;
+      if (a.loss) a.loss[b] = loss;
+      if (a.dz) a.dz[b] = g;
+    }
+    if (!BWD) {
+      __syncthreads();  // the next sample's gather overwrites e
+      continue;
+    }
+
+    // ---- pass B: recompute every tile's pairs, then add the tile into the owned accumulators in pair order ----
+    for (int l = lane; l < F * KP; l += WAVE) sm[L.Ea + l] = 0.f;
+    __syncthreads();
+    for (int i0 = 0, pb = 0; i0 < F - 1;) {
+      int n;
+      const int i1 = next_tile(F, i0, n);
+      if (lane < n) {
+        int i, j;
+        tile_pair(F, i0, lane, i, j);
+        float q[KP], r, s;
+        pair_terms<KP>(sm, L, t, i, j, q, r, s);
+        const float ai = sm[L.s + pb + lane] / Z;
+        const float ga = g * ai;              // dL/dr_ij
+        const float delta = ga * (r - att);   // dL/ds_ij
+        float dq[KP];
+#pragma unroll
+        for (int d = 0; d < KP; ++d) dq[d] = ga * sm[L.p + d];
+        for (int u = 0; u < t; ++u) {
+          float z = sm[L.bW + u];
+#pragma unroll
+          for (int d = 0; d < KP; ++d) z = fmaf(sm[L.W + u * KP + d], q[d], z);
+          const float co = z > 0.f ? delta * sm[L.h + u] : 0.f;  // dL/dz_u
+          sm[L.co + lane * t + u] = co;
+          sm[L.hr + lane * t + u] = delta * fmaxf(z, 0.f);       // dL/dh_u's term
+#pragma unroll
+          for (int d = 0; d < KP; ++d) dq[d] = fmaf(co, sm[L.W + u * KP + d], dq[d]);
+        }
+#pragma unroll
+        for (int d = 0; d < KP; d += 4) {
+          *reinterpret_cast<float4 *>(sm + L.q + lane * KP + d) = float4{q[d], q[d + 1], q[d + 2], q[d + 3]};
+          *reinterpret_cast<float4 *>(sm + L.c + lane * KP + d) = float4{dq[d], dq[d + 1], dq[d + 2], dq[d + 3]};
+        }
+        sm[L.ga + lane] = ga;
+      }
+      __syncthreads();
+      for (int l = lane; l < t * KP; l += WAVE) {  // dW[u][d] += sum_pairs dL/dz_u q_d
+        const int u = l / KP, d = l - u * KP;
+        float acc = sm[L.aW + l];
+        for (int m = 0; m < n; ++m) acc = fmaf(sm[L.co + m * t + u], sm[L.q + m * KP + d], acc);
+        sm[L.aW + l] = acc;
+      }
+      for (int u = lane; u < t; u += WAVE) {
+        float ab = sm[L.ab + u], ah = sm[L.ah + u];
+        for (int m = 0; m < n; ++m) {
+          ab += sm[L.co + m * t + u];
+          ah += sm[L.hr + m * t + u];
+        }
+        sm[L.ab + u] = ab;
+        sm[L.ah + u] = ah;
+      }
+      for (int d = lane; d < KP; d += WAVE) {
+        float ap = sm[L.ap + d];
+        for (int m = 0; m < n; ++m) ap = fmaf(sm[L.ga + m], sm[L.q + m * KP + d], ap);
+        sm[L.ap + d] = ap;
+      }
+      // dL/de_f[d]: the pairs (i, f), i < f, then (f, j), j > f -- the pair order, whatever the tiling
+      for (int l = lane; l < F * KP; l += WAVE) {
+        const int f = l / KP, d = l - f * KP;
+        float acc = sm[L.Ea + l];
+        int lb = 0;  // tile-local index of row i's first pair
+        for (int i = i0; i < i1 && i <= f; lb += F - 1 - i, ++i) {
+          if (i < f) {
+            acc = fmaf(sm[L.c + (lb + f - i - 1) * KP + d], sm[L.e + i * KP + d], acc);
+          } else {
+            for (int jj = i + 1; jj < F; ++jj) acc = fmaf(sm[L.c + (lb + jj - i - 1) * KP + d], sm[L.e + jj * KP + d], acc);
+          }
+        }
+        sm[L.Ea + l] = acc;
+      }
+      __syncthreads();
+      pb += n;
+      i0 = i1;
+    }
+    // dL/dV_row = x dL/de
+    float *Eb = a.E + (size_t)b * F * KP;
+    for (int l = lane * 4; l < F * KP; l += WAVE * 4) {
+      const int f = l / KP;
+      const float x = a.xv ? a.xv[(size_t)b * F + f] : 1.f;
+      *reinterpret_cast<float4 *>(Eb + l) = x * *reinterpret_cast<const float4 *>(sm + L.Ea + l);
+    }
+    __syncthreads();
+  }
+  if (!BWD) return;
+  float *part = a.part + (size_t)blockIdx.x * a.G;
+  for (int l = lane; l < t * k; l += WAVE) {
+    const int u = l / k, d = l - u * k;
+    part[l] = sm[L.aW + u * KP + d];
+  }
+  for (int u = lane; u < t; u += WAVE) {
+    part[t * k + u] = sm[L.ab + u];
+    part[t * k + t + u] = sm[L.ah + u];
+  }
+  for (int d = lane; d < k; d += WAVE) part[t * k + 2 * t + d] = sm[L.ap + d];
+}
+
+// grad[g] = sum over the n workgroups' partials, workgroup order: 4 quarters of 64 columns per workgroup, then the quarters in order
+__global__ __launch_bounds__(256) void k_afm_reduce(const float *part, int n, int G, float *grad) {
+  __shared__ float sm[4][64];
+  const int c = threadIdx.x & 63, qt = threadIdx.x >> 6;
+  const int g = blockIdx.x * 64 + c;
+  float acc = 0.f;
+  if (g < G) {
+    constexpr int U = 8;
+    for (int w0 = qt; w0 < n; w0 += 4 * U) {
+      float v[U];
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        const int w = w0 + 4 * u;
+        v[u] = w < n ? part[(size_t)w * G + g] : 0.f;
+      }
+#pragma unroll
+      for (int u = 0; u < U; ++u) acc += v[u];
+    }
+  }
+  sm[qt][c] = acc;
+  __syncthreads();
+  if (qt == 0 && g < G) grad[g] = ((sm[0][c] + sm[1][c]) + sm[2][c]) + sm[3][c];
+}
+
+// ------------------------------------------------------------------------------------------------------------
+// host side
+// ------------------------------------------------------------------------------------------------------------
+int kp_ok(int kp) { return kp == 4 || kp == 8 || kp == 16 || kp == 32 || kp == 64; }
+
+int check_afm(const fmx_table_t *t, const fmx_afm_t *afm, const char *who) {
+  if (!t || !afm) return fail(FMX_ERR_ARG, "%s: null table / afm", who);
+  if (!t->rows || !t->field_offsets || !t->bias) return fail(FMX_ERR_ARG, "%s: table has a null pointer", who);
+  if (!afm->params) return fail(FMX_ERR_ARG, "%s: null attention parameters", who);
+  if (!kp_ok(t->kp) || t->k < 1 || t->k > t->kp) return fail(FMX_ERR_SHAPE, "%s: kp=%d must be 4/8/16/32/64 and >= k=%d", who, t->kp, t->k);
+  if (t->layout != FMX_LAYOUT_WEIGHTS && t->layout != FMX_LAYOUT_FTRL && t->layout != FMX_LAYOUT_MOMENTS)
+    return fail(FMX_ERR_ARG, "%s: unknown layout %d", who, t->layout);
+  if (t->row_stride % 4 || t->row_stride < t->kp + 4) return fail(FMX_ERR_SHAPE, "%s: row_stride=%d", who, t->row_stride);
+  if (!aligned16(t->rows)) return fail(FMX_ERR_ALIGN, "%s: table rows must be 16-byte aligned", who);
+  if (t->field_cols || t->field_base)
+    return fail(FMX_ERR_UNSUPPORTED, "%s: tables whose fields are pieces of index columns are not supported", who);
+  if (t->n_fields < 2 || t->n_fields > AFM_MAX_F)
+    return fail(FMX_ERR_UNSUPPORTED, "%s: %d fields; the AFM kernels take 2 <= F <= %d", who, t->n_fields, AFM_MAX_F);
+  if (afm->k != t->k) return fail(FMX_ERR_SHAPE, "%s: afm->k=%d differs from the table's k=%d", who, afm->k, t->k);
+  if (afm->t < 1 || afm->t > AFM_MAX_T) return fail(FMX_ERR_UNSUPPORTED, "%s: attention size t=%d; the AFM kernels take 1 <= t <= %d", who, afm->t, AFM_MAX_T);
+  return FMX_OK;
+}
+
+template <int KP, bool FTRL, bool BWD>
+int launch_afm_k(const AfmArgs &a, hipStream_t st) {
+  const size_t lds = (size_t)afm_lds(a.F, KP, a.t, BWD).total * 4;
+  static std::once_flag once;
+  static hipError_t raised = hipSuccess;
+  std::call_once(once, [] {
+    raised = hipFuncSetAttribute(reinterpret_cast<const void *>(k_afm<KP, FTRL, BWD>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                 (int)(afm_lds(AFM_MAX_F, KP, AFM_MAX_T, BWD).total * 4));
+  });
+  if (raised != hipSuccess) return fail(FMX_ERR_LAUNCH, "hipFuncSetAttribute(k_afm): %s", hipGetErrorString(raised));
+  hipLaunchKernelGGL((k_afm<KP, FTRL, BWD>), dim3(afm_grid(a.B)), dim3(64), lds, st, a);
+  return check_launch("k_afm");
+}
+
+template <bool BWD>
+int launch_afm(const AfmArgs &a, int kp, bool ftrl, hipStream_t st) {
+  auto go = [&](auto KP) { return ftrl ? launch_afm_k<KP, true, BWD>(a, st) : launch_afm_k<KP, false, BWD>(a, st); };
+  switch (kp) {
+    case 4: return go(std::integral_constant<int, 4>{});
+    case 8: return go(std::integral_constant<int, 8>{});
+    case 16: return go(std::integral_constant<int, 16>{});
+    case 32: return go(std::integral_constant<int, 32>{});
+    default: return go(std::integral_constant<int, 64>{});
+  }
+}
+
+AfmArgs fill_afm(const fmx_table_t *table, const fmx_afm_t *afm, const fmx_hyper_t *hyper, const int32_t *idx, const float *xv,
+                 const float *y, int32_t B, int32_t loss_kind, float inv_b, int32_t *error) {
+  AfmArgs a;
+  memset(&a, 0, sizeof(a));
+  a.rows = table->rows;
+  a.foff = table->field_offsets;
+  a.bias = table->bias;
+  a.idx = idx;
+  a.xv = xv;
+  a.y = y;
+  a.params = afm->params;
+  a.error = error;
+  a.h.lr = hyper->lr;
+  a.h.eps = hyper->eps;
+  a.h.alpha = 1.0f / hyper->alpha;  // the kernels multiply by 1/alpha (ftrl_w)
+  a.h.beta = hyper->beta;
+  a.h.l1 = hyper->l1;
+  a.h.l2 = hyper->l2;
+  a.B = B;
+  a.F = table->n_fields;
+  a.k = afm->k;
+  a.t = afm->t;
+  a.stride = table->row_stride;
+  a.loss_kind = loss_kind;
+  a.G = afm->t * afm->k + 2 * afm->t + afm->k;
+  a.inv_b = inv_b;
+  return a;
+}
+
+// the step's workspace: [ the table's step workspace | dz [B] | loss [B] | E [B, F, kp] | partials [grid, G] ], 256-byte sections
+struct AfmWs {
+  int64_t table_bytes;
+  float *dz, *loss, *E, *part;
+  int64_t bytes;
+};
+AfmWs carve_afm(const fmx_table_t *table, const fmx_afm_t *afm, int B, void *base) {
+  AfmWs w;
+  w.table_bytes = fmx_workspace_bytes(table, B);
+  char *p = static_cast<char *>(base);
+  size_t o = align_up((size_t)(w.table_bytes > 0 ? w.table_bytes : 0), 256);
+  w.dz = reinterpret_cast<float *>(p + o);
+  o += align_up((size_t)B * 4, 256);
+  w.loss = reinterpret_cast<float *>(p + o);
+  o += align_up((size_t)B * 4, 256);
+  w.E = reinterpret_cast<float *>(p + o);
+  o += align_up((size_t)B * table->n_fields * table->kp * 4, 256);
+  w.part = reinterpret_cast<float *>(p + o);
+  o += align_up((size_t)afm_grid(B) * (afm->t * afm->k + 2 * afm->t + afm->k) * 4, 256);
+  w.bytes = (int64_t)o;
+  return w;
+}
+
+int check_rule_layout(const fmx_table_t *t, int rule) {
+  const bool ok = ((rule == FMX_RULE_SIGNADAM || rule == FMX_RULE_SGD) && t->layout == FMX_LAYOUT_WEIGHTS) ||
+                  (rule == FMX_RULE_FTRL && t->layout == FMX_LAYOUT_FTRL) ||
+                  ((rule == FMX_RULE_ADAGRAD || rule == FMX_RULE_ADAM) && t->layout == FMX_LAYOUT_MOMENTS);
+  return ok ? FMX_OK : fail(FMX_ERR_ARG, "fmx_afm_step: rule %d does not go with layout %d", rule, t->layout);
+}
+
+}  // namespace
+
+extern "C" {
+
+int fmx_afm_forward(const fmx_table_t *table, const fmx_afm_t *afm, const fmx_hyper_t *hyper, const int32_t *idx, const float *xv,
+                    const float *y, int32_t B, int32_t loss_kind, float inv_b, float *logit_out, float *loss_out, int32_t *error,
+                    fmx_stream_t stream) {
+  if (int rc = check_afm(table, afm, "fmx_afm_forward")) return rc;
+  if (!hyper || !idx) return fail(FMX_ERR_ARG, "fmx_afm_forward: null argument");
+  if (B < 1) return fail(FMX_ERR_ARG, "fmx_afm_forward: B must be >= 1");
+  if (loss_kind < FMX_LOSS_NONE || loss_kind > FMX_LOSS_BCE_SIGMOID) return fail(FMX_ERR_ARG, "unknown loss %d", loss_kind);
+  if (loss_kind != FMX_LOSS_NONE && !y) return fail(FMX_ERR_ARG, "fmx_afm_forward: a loss needs labels y");
+  AfmArgs a = fill_afm(table, afm, hyper, idx, xv, y, B, loss_kind, inv_b, error);
+  a.logit = logit_out;
+  a.loss = loss_kind != FMX_LOSS_NONE ? loss_out : nullptr;
+  return launch_afm<false>(a, table->kp, table->layout == FMX_LAYOUT_FTRL, static_cast<hipStream_t>(stream));
+}
+
+int64_t fmx_afm_workspace_bytes(const fmx_table_t *table, const fmx_afm_t *afm, int32_t B) {
+  if (int rc = check_afm(table, afm, "fmx_afm_workspace_bytes")) return rc;
+  if (B < 1) return fail(FMX_ERR_ARG, "fmx_afm_workspace_bytes: B must be >= 1");
+  const AfmWs w = carve_afm(table, afm, B, nullptr);
+  if (w.table_bytes < 0) return w.table_bytes;
+  return w.bytes;
+}
+
+int fmx_afm_step(const fmx_table_t *table, const fmx_hyper_t *hyper, int32_t rule, const fmx_afm_t *afm, const int32_t *idx,
+                 const float *xv, const float *y, int32_t B, float inv_b, void *workspace, int64_t workspace_bytes,
+                 float *attn_grad_out, float *loss_out, int32_t *error, fmx_stream_t stream) {
+  if (int rc = check_afm(table, afm, "fmx_afm_step")) return rc;
+  if (!hyper || !idx || !y || !workspace || !attn_grad_out) return fail(FMX_ERR_ARG, "fmx_afm_step: null argument");
+  if (B < 1) return fail(FMX_ERR_ARG, "fmx_afm_step: B must be >= 1");
+  if (int rc = check_rule_layout(table, rule)) return rc;
+  if (!aligned16(workspace)) return fail(FMX_ERR_ALIGN, "fmx_afm_step: workspace must be 16-byte aligned");
+  const AfmWs w = carve_afm(table, afm, B, workspace);
+  if (w.table_bytes < 0) return (int)w.table_bytes;
+  if (workspace_bytes < w.bytes)
+    return fail(FMX_ERR_SHAPE, "fmx_afm_step: workspace of %lld bytes, %lld needed (fmx_afm_workspace_bytes)", (long long)workspace_bytes,
+                (long long)w.bytes);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  // sort -> forward + backward -> table update (its last workgroups reduce the bias gradient and the loss) -> attention gradient
+  if (int rc = fmx_sort_occurrences(table, idx, B, workspace, w.table_bytes, error, stream)) return rc;
+  AfmArgs a = fill_afm(table, afm, hyper, idx, xv, y, B, FMX_LOSS_BCE_LOGITS, inv_b, error);
+  a.dz = w.dz;
+  a.loss = w.loss;
+  a.E = w.E;
+  a.part = w.part;
+  if (int rc = launch_afm<true>(a, table->kp, table->layout == FMX_LAYOUT_FTRL, st)) return rc;
+  if (int rc = fmx_fm_update_occ(table, hyper, rule, workspace, w.table_bytes, xv, w.dz, w.E, table->n_fields * table->kp, B, w.loss,
+                                 inv_b, loss_out, stream))
+    return rc;
+  hipLaunchKernelGGL(k_afm_reduce, dim3((a.G + 63) / 64), dim3(256), 0, st, w.part, afm_grid(B), a.G, attn_grad_out);
+  return check_launch("k_afm_reduce");
+}
+
+}  // extern "C"

@@ -721,7 +721,9 @@ __device__ unsigned long long g_upd_stamps[8192 * 6];
 // walks EPG = 64 / SLOTS CONSECUTIVE occurrences sequentially, so duplicates inside a group are summed in registers;
 // one segmented scan over the SLOTS groups (log2(SLOTS) steps of wave shuffles) carries the sums of runs that span
 // groups.  At the tail of a run: the row update when the run began in this tile, a partial record otherwise.
-template <int LPR, int LAYOUT, int RULE, bool HAS_GBI, bool INL>
+// OCC (fmx_fm_update_occ): the occurrence's gradient is given explicitly -- cV adds E[b, field] (a.gbi, a.ldG floats per
+// sample, kp per field; x already applied), cA = 0 -- instead of x (S_b - x V) G_b; everything else is the same code.
+template <int LPR, int LAYOUT, int RULE, bool HAS_GBI, bool INL, bool OCC = false>
 __device__ __forceinline__ void update_body(const UpdArgs &a, const int blk) {
   constexpr int SLOTS = WAVE / LPR;  // lane groups
   constexpr int EPG = LPR;           // consecutive occurrences per group
@@ -814,6 +816,8 @@ __device__ __forceinline__ void update_body(const UpdArgs &a, const int blk) {
     const float *xsrc = has_x ? a.xv : a.dz_first;  // something loadable
     const int fld = (has_x && a.cols) ? a.cols[f] : f;
     const int col = (has_x && a.fcols) ? a.fcols[fld] : fld;
+    int efld = 0;  // OCC: the field whose slot of E this sort field's occurrences read
+    if constexpr (OCC) efld = a.cols ? a.cols[f] : f;
     float4 S4[EPG], G4[EPG];
     float xl[EPG], dzf[EPG], dzbl[EPG];
     uint32_t bj[EPG];
@@ -841,7 +845,8 @@ __device__ __forceinline__ void update_body(const UpdArgs &a, const int blk) {
 #pragma unroll
     for (int j = 0; j < EPG; ++j) {
       const uint32_t b = bj[j];
-      S4[j] = *reinterpret_cast<const float4 *>(a.S + (size_t)b * a.ldS + 4 * q);
+      if constexpr (OCC) S4[j] = *reinterpret_cast<const float4 *>(a.gbi + (size_t)b * a.ldG + (size_t)efld * kp + 4 * q);
+      else S4[j] = *reinterpret_cast<const float4 *>(a.S + (size_t)b * a.ldS + 4 * q);
       dzf[j] = a.dz_first[(size_t)b * a.ld1];
       if constexpr (HAS_GBI) G4[j] = *reinterpret_cast<const float4 *>(a.gbi + (size_t)b * a.ldG + 4 * q);
       else G4[j] = splat(0.f);
@@ -854,7 +859,10 @@ __device__ __forceinline__ void update_body(const UpdArgs &a, const int blk) {
       const float w1 = x * dzf[j];
       float4 v;
       CA ca;
-      if constexpr (HAS_GBI) {
+      if constexpr (OCC) {
+        v = S4[j];
+        ca.zero();
+      } else if constexpr (HAS_GBI) {
         const float4 G = splat(dzb) + G4[j];
         const float4 xG = x * G;
         v = xG * S4[j];
@@ -1068,6 +1076,13 @@ template <int LPR, int LAYOUT, int RULE, bool HAS_GBI, bool INL>
 __global__ __launch_bounds__(256) void k_fm_update(UpdArgs a) {
   __builtin_amdgcn_s_setprio(3);  // ahead of the side-stream sort's waves at the CU's instruction arbiter
   update_body<LPR, LAYOUT, RULE, HAS_GBI, INL>(a, blockIdx.x);
+}
+
+// The table update from explicit per-occurrence gradients (fmx_fm_update_occ; the AFM step's embedding gradient)
+template <int LPR, int LAYOUT, int RULE, bool INL>
+__global__ __launch_bounds__(256) void k_fm_update_occ(UpdArgs a) {
+  __builtin_amdgcn_s_setprio(3);
+  update_body<LPR, LAYOUT, RULE, false, INL, true>(a, blockIdx.x);
 }
 
 // The same launch with a RIDER: the workgroups behind the update's own carry the fixed-order reduction of the MLP's partial weight
@@ -2037,6 +2052,20 @@ void launch_update_pair(const UpdArgs &a, int rule, bool has_gbi, hipStream_t st
   launch_fixup<LPR>(a, rule, st);
 }
 
+// the update from explicit per-occurrence gradients: the same grid, hand-off and fixup as launch_update_pair
+template <int LPR>
+void launch_update_occ_pair(const UpdArgs &a, int rule, hipStream_t st) {
+  const int tiles = a.F * (a.Bp >> 6);
+  const int wpb = tune().wpb_upd;
+  const dim3 grid((tiles + wpb - 1) / wpb + red_slices(a.B)), block(64 * wpb);
+  const bool inl = tune().inline_fixup && !is_capturing(st);
+  with_rule(rule, [&](auto LAYOUT, auto RULE) {
+    if (inl) hipLaunchKernelGGL((k_fm_update_occ<LPR, LAYOUT, RULE, true>), grid, block, 0, st, a);
+    else hipLaunchKernelGGL((k_fm_update_occ<LPR, LAYOUT, RULE, false>), grid, block, 0, st, a);
+  });
+  if (!inl) launch_fixup<LPR>(a, rule, st);
+}
+
 template <int E>
 void launch_sort(SortArgs a, hipStream_t st) {
   const int threads = a.Bp / E;
@@ -2348,6 +2377,18 @@ int update_impl(const fmx_table_t *table, const fmx_hyper_t *hyper, int32_t rule
   return check_launch("k_fm_update / k_fm_fixup");
 }
 
+// occ [B, ld_occ]: sample b's gradients of its fields' rows, field f's kp floats at b * ld_occ + f * kp (update_body's OCC)
+int update_occ_impl(const fmx_table_t *table, const fmx_hyper_t *hyper, int32_t rule, const Workspace &w, const float *xv,
+                    const float *dz_first, const float *occ, int32_t ld_occ, int32_t B, const float *loss_b, float inv_b,
+                    float *loss_out, hipStream_t st) {
+  UpdArgs a = fill_upd(table, hyper, w, w.sorted, xv, nullptr, dz_first, nullptr, occ, B, loss_b, inv_b, loss_out, nullptr, 0,
+                       nullptr);
+  a.ldG = ld_occ;
+  if (rule == FMX_RULE_ADAM) adam_consts(hyper->lr, hyper->beta1, hyper->beta2, hyper->step + 1, a.h.lr, a.h.beta1, a.h.beta2);
+  with_lpr(table->kp, [&](auto LPR) { launch_update_occ_pair<LPR>(a, rule, st); });
+  return check_launch("k_fm_update_occ / k_fm_fixup");
+}
+
 template <int LPR, int LAYOUT, int RULE>
 void launch_online_np(const OnlineArgs &a, int np, hipStream_t st) {
   auto launch = [&](auto NP) { hipLaunchKernelGGL((k_fm_online<LPR, LAYOUT, RULE, NP>), dim3(1), dim3(64), 0, st, a); };
@@ -2574,6 +2615,26 @@ int fmx_fm_update(const fmx_table_t *table, const fmx_hyper_t *hyper, int32_t ru
   const Workspace w = carve(table, B, workspace);
   return update_impl(table, hyper, rule, w, w.sorted, xv, S, dz_first, dz_bi, gbi, B, loss_b, inv_b, loss_out,
                      static_cast<hipStream_t>(stream), nullptr, sample_ld);
+}
+
+int fmx_fm_update_occ(const fmx_table_t *table, const fmx_hyper_t *hyper, int32_t rule, void *workspace, int64_t workspace_bytes,
+                      const float *xv, const float *dz_first, const float *occ_grad, int32_t ld_occ, int32_t B, const float *loss_b,
+                      float inv_b, float *loss_out, fmx_stream_t stream) {
+  if (int rc = check_table(table)) return rc;
+  if (mapped(table)) return fail(FMX_ERR_UNSUPPORTED, "fmx_fm_update_occ: tables whose fields are pieces of index columns are not supported");
+  if (int rc = check_rule(table, rule)) return rc;
+  if (!hyper || !workspace || !dz_first || !occ_grad) return fail(FMX_ERR_ARG, "fmx_fm_update_occ: null argument");
+  if (int rc = check_adam(hyper, rule, 1)) return rc;
+  if (int rc = check_sort_geometry(table, B)) return rc;
+  if (ld_occ % 4 || (int64_t)ld_occ < (int64_t)table->n_fields * table->kp)
+    return fail(FMX_ERR_SHAPE, "fmx_fm_update_occ: ld_occ=%d must be a multiple of 4 and >= n_fields * kp = %d", ld_occ,
+                table->n_fields * table->kp);
+  if (!aligned16(workspace) || !aligned16(occ_grad) || !aligned16(dz_first) || (loss_b && !aligned16(loss_b)))
+    return fail(FMX_ERR_ALIGN, "fmx_fm_update_occ: workspace, occ_grad, dz_first and loss_b must be 16-byte aligned");
+  if (int rc = check_workspace(table, B, workspace, workspace_bytes, "fmx_fm_update_occ")) return rc;
+  const Workspace w = carve(table, B, workspace);
+  return update_occ_impl(table, hyper, rule, w, xv, dz_first, occ_grad, ld_occ, B, loss_b, inv_b, loss_out,
+                         static_cast<hipStream_t>(stream));
 }
 
 // NFM's input logit: the first-order sum plus the bias (reference nfm_adam.py:78-88), one fp32 add per sample as the trainer does it

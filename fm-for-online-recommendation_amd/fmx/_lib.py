@@ -22,11 +22,12 @@ EXPORTS = ["fmx_version", "fmx_last_error_string", "fmx_set_option", "fmx_sorted
            "fmx_sort_occurrences", "fmx_fm_update", "fmx_fm_step", "fmx_fm_stream", "fmx_deepfm_stream", "fmx_stream_read",
            "fmx_fm_forward_partial", "fmx_fm_forward_finish", "fmx_sftrl_run", "fmx_sftrl_grid",
            "fmx_gather_read", "fmx_comm_unique_id", "fmx_comm_create", "fmx_comm_destroy", "fmx_owner_prefetch", "fmx_owner_step",
-           "fmx_fm_topk_workspace_bytes", "fmx_fm_topk", "fmx_mlp_topk_workspace_bytes", "fmx_mlp_topk"]
+           "fmx_fm_topk_workspace_bytes", "fmx_fm_topk", "fmx_mlp_topk_workspace_bytes", "fmx_mlp_topk",
+           "fmx_fm_update_occ", "fmx_afm_forward", "fmx_afm_workspace_bytes", "fmx_afm_step"]
 
 
 I64_RETURNS = ("fmx_workspace_bytes", "fmx_mlp_section_workspace_bytes", "fmx_fm_topk_workspace_bytes",
-               "fmx_mlp_topk_workspace_bytes")   # byte counts: int64_t in include/fmx.h
+               "fmx_mlp_topk_workspace_bytes", "fmx_afm_workspace_bytes")   # byte counts: int64_t in include/fmx.h
 
 
 class FmxError(RuntimeError):
@@ -58,6 +59,10 @@ class Mlp(C.Structure):
 class FwdOut(C.Structure):
     _fields_ = ([(n, C.c_void_p) for n in ("S", "bi", "first", "sfirst", "sbi", "logit", "loss", "dz", "error")]
                 + [("sample_ld", C.c_int32), ("reserved", C.c_int32)])
+
+
+class Afm(C.Structure):
+    _fields_ = [("params", C.c_void_p), ("k", C.c_int32), ("t", C.c_int32)]
 
 
 class OwnerBufs(C.Structure):
@@ -118,6 +123,11 @@ def load():
     lib.fmx_fm_topk.argtypes = [p, i32, p, i32, p, i32, p, i32, i32, p, p, i32, p, i64, p, p, p]
     lib.fmx_mlp_topk_workspace_bytes.argtypes = [MP, i32, i32, i32]
     lib.fmx_mlp_topk.argtypes = [MP, i32, p, p, i32, p, i32, p, p, i32, p, i32, i32, p, p, i32, p, i64, p, p, p]
+    AP = C.POINTER(Afm)
+    lib.fmx_fm_update_occ.argtypes = [TP, HP, i32, p, i64, p, p, p, i32, i32, p, f32, p, p]
+    lib.fmx_afm_forward.argtypes = [TP, AP, HP, p, p, p, i32, i32, f32, p, p, p, p]
+    lib.fmx_afm_workspace_bytes.argtypes = [TP, AP, i32]
+    lib.fmx_afm_step.argtypes = [TP, HP, i32, AP, p, p, p, i32, f32, p, i64, p, p, p, p]
     for name in EXPORTS:
         fn = getattr(lib, name)
         if name in I64_RETURNS:

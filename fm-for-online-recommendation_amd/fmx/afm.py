@@ -1,0 +1,78 @@
+"""AFMEngine: workspace + launch sequencing of the attentional FM (fmx_afm_forward / fmx_afm_step) for one FlatTable.
+
+The attention parameters live in ONE flat fp32 device buffer [ W (t x k) | b (t) | h (t) | p (k) ] (include/fmx.h, fmx_afm_t);
+the step returns their gradient in the same layout and leaves updating them to the caller."""
+import ctypes as C
+
+import torch
+
+from . import _lib
+from .engine import FMEngine, _ptr
+from .table import FlatTable
+
+
+def afm_param_count(k, t):
+    return t * k + 2 * t + k
+
+
+class AFMEngine:
+    def __init__(self, table: FlatTable, params, t, max_batch=4096):
+        if not torch.cuda.is_available():
+            raise RuntimeError("fmx needs a ROCm GPU: the hot path has no CPU implementation")
+        self.lib = _lib.load()
+        self.table = table
+        self.device = table.device
+        self.k, self.t = table.k, int(t)
+        assert params.dtype == torch.float32 and params.is_contiguous() and params.numel() == afm_param_count(self.k, self.t)
+        self.params = params
+        self.c_afm = _lib.Afm(params.data_ptr(), self.k, self.t)
+        self.grad = torch.zeros_like(params)
+        self.loss_out = torch.zeros(1, dtype=torch.float32, device=self.device)
+        self.error = torch.zeros(1, dtype=torch.int32, device=self.device)
+        self.max_batch = 0
+        self._alloc(max_batch)
+
+    def _alloc(self, B):
+        B = int(B)
+        self.table.ensure_sort_split(B)      # large fields are cut into sort pieces when (index, sample) would not fit 32 bits
+        nbytes = int(self.lib.fmx_afm_workspace_bytes(self.table.c_struct(), C.byref(self.c_afm), B))
+        if nbytes < 0:
+            _lib.check(nbytes)
+        self.workspace = torch.zeros(nbytes // 4, dtype=torch.int32, device=self.device)
+        self.logit = torch.empty(B, dtype=torch.float32, device=self.device)
+        self.loss_b = torch.empty(B, dtype=torch.float32, device=self.device)
+        self.max_batch = B
+
+    def _ensure(self, B):
+        # the table's sort fields may be split further for a larger batch: the workspace follows fmx_afm_workspace_bytes
+        need = int(self.lib.fmx_afm_workspace_bytes(self.table.c_struct(), C.byref(self.c_afm), max(B, self.max_batch)))
+        if B > self.max_batch or need > self.workspace.numel() * 4:
+            self._alloc(max(B, self.max_batch))
+
+    _stream = FMEngine._stream
+    to_device = FMEngine.to_device
+    check_error_flag = FMEngine.check_error_flag
+
+    def forward(self, hyper, idx_d, xv_d=None, y_d=None, loss=None, inv_b=None, stream=None):
+        """-> B; logits in self.logit[:B], per-sample losses in self.loss_b[:B] when `loss` ('logits' / 'sigmoid') and y_d."""
+        B = idx_d.shape[0]
+        self._ensure(B)
+        _lib.check(self.lib.fmx_afm_forward(self.table.c_struct(), C.byref(self.c_afm), hyper.ref(), idx_d.data_ptr(), _ptr(xv_d),
+                                            _ptr(y_d), B, _lib.LOSSES[loss], 1.0 / B if inv_b is None else inv_b,
+                                            self.logit.data_ptr(), self.loss_b.data_ptr(), self.error.data_ptr(),
+                                            self._stream(stream)))
+        return B
+
+    def step(self, hyper, rule, idx_d, xv_d, y_d, inv_b=None, stream=None):
+        """One mini-batch step: the table updated under `rule`, the mean loss in self.loss_out[0], the attention gradient in
+        self.grad (no sync here)."""
+        B = idx_d.shape[0]
+        self._ensure(B)
+        if self.table.layout == "moments":
+            hyper.c.step = self.table.step
+        _lib.check(self.lib.fmx_afm_step(self.table.c_struct(), hyper.ref(), _lib.RULES[rule], C.byref(self.c_afm), idx_d.data_ptr(),
+                                         _ptr(xv_d), y_d.data_ptr(), B, 1.0 / B if inv_b is None else inv_b,
+                                         self.workspace.data_ptr(), self.workspace.numel() * 4, self.grad.data_ptr(),
+                                         self.loss_out.data_ptr(), self.error.data_ptr(), self._stream(stream)))
+        if self.table.layout == "moments":
+            self.table.step += 1

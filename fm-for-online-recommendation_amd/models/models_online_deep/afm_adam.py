@@ -1,0 +1,301 @@
+"""AFMAdam: the attentional factorization machine (Xiao et al. 2017) on the gfx950 kernels (fmx_afm_forward / fmx_afm_step).
+
+The model (include/fmx.h, DESIGN.md section 3 "AFM"): per sample, with e_f = x_f V[row_f] and w_f the first-order weight, over
+the P = F (F - 1) / 2 pairs in the order i = 0..F-2, j = i+1..F-1,
+
+    q_ij = e_i * e_j,   s_ij = H . relu(W q_ij + b),   a_ij = softmax over the sample's pairs of s_ij,
+    logit = bias + sum_f w_f x_f + P . sum_ij a_ij q_ij
+
+with W, b = attention_linear.weight / .bias, H and P the reference's parameters (reference afm_adam.py:39-41).
+
+Where this class departs from the reference's code, which cannot run as written (SURVEY.md row afm_adam.py):
+  * the reference builds its "interaction layer" from per-field squares (afm_adam.py:62), so its shapes only line up at F = 3;
+    here the interaction layer is the pairwise products of the paper;
+  * the reference defines `activation = F.relu` (:63) and never applies it; here the ReLU of the paper is applied;
+  * `.view` with a float (:67, :69), `loss.data[0]` and the undefined self.verbose / evaluate / eval_metric (:120-123, :167)
+    are gone: fit() returns the per-epoch mean log-loss of the training (and validation) data and reports no other metric;
+  * the reference's fit() uses ONE persistent torch.optim.Adam over every parameter (:93).  The default update_rule 'adam' is
+    that optimizer's SparseAdam form on the tables -- a row's moments move only when the row occurs in the batch (a dense Adam
+    would keep moving every row on its old moments) -- and one persistent torch.optim.Adam on the attention parameters.
+Parameters are created in the reference's RNG order (:25-41), so one torch seed gives the reference's initial model.
+There is no CPU path: constructing the class without a ROCm GPU raises.
+"""
+from time import time
+
+import numpy as np
+import torch
+import torch.nn as nn
+
+import fmx
+from fmx.afm import AFMEngine
+
+from ._base import OnlineFMBase, _FieldView
+
+
+class AFMAdam(nn.Module):
+    _name = "AFMAdam"
+
+    def __init__(self, feature_sizes, embedding_size=4, attention_size=4, n_epochs=64, batch_size=256, num_classes=1, b=0.99,
+                 n=0.003, use_cuda=True, update_rule="adam", ftrl=None, adam=None, adagrad=None):
+        """update_rule: 'adam' (default: SparseAdam on the tables, a persistent Adam on the attention parameters), 'adagrad',
+        'signadam' (a fresh Adam per step), 'sgd' or 'ftrl' (settings ftrl=dict(alpha, beta, l1, l2)) -- the tables' rules of
+        the other classes; the attention parameters take what the hidden layers of DeepFM / NFM take under the same rule.
+        Every rule's learning rate is n."""
+        super().__init__()
+        if not (use_cuda and torch.cuda.is_available()):
+            raise RuntimeError(f"{self._name}: this build runs the hot path in gfx950 kernels only -- it needs use_cuda=True "
+                               "and a ROCm GPU (there is no CPU or PyTorch fallback; use the reference for CPU runs)")
+        if update_rule not in ("signadam", "sgd", "ftrl", "adagrad", "adam"):
+            raise ValueError(update_rule)
+        self.device = torch.device("cuda", torch.cuda.current_device())
+        self.field_size = len(feature_sizes)
+        self.feature_sizes = feature_sizes
+        self.embedding_size = embedding_size
+        self.attention_size = attention_size
+        self.n_epochs = n_epochs
+        self.batch_size = batch_size
+        self.num_classes = num_classes
+        self.use_cuda = use_cuda
+        self.update_rule = update_rule
+        k, t = embedding_size, attention_size
+
+        # ---- the reference's RNG order (afm_adam.py:30-41) ----
+        bias0 = torch.tensor(b)
+        self.n = torch.nn.Parameter(torch.tensor(n), requires_grad=False)
+        first = [nn.Embedding(fs, 1).weight.data for fs in feature_sizes]
+        second = [nn.Embedding(fs, k).weight.data for fs in feature_sizes]
+        lin = nn.Linear(k, t)
+        H0 = torch.randn(t)
+        P0 = torch.randn(k)
+        self._bias_shape = tuple(bias0.shape)
+
+        self._ftrl = dict(alpha=0.05, beta=1.0, l1=0.0, l2=0.0)
+        if ftrl:
+            self._ftrl.update(ftrl)
+        self._adam = dict(beta1=0.9, beta2=0.999, eps=1e-8)
+        if adam:
+            self._adam.update({k_: float(v) for k_, v in adam.items() if k_ in self._adam})
+        self._adagrad = dict(eps=1e-10)
+        if adagrad:
+            self._adagrad.update({k_: float(v) for k_, v in adagrad.items() if k_ in self._adagrad})
+        adaptive = update_rule in ("adagrad", "adam")
+        layout = "ftrl" if update_rule == "ftrl" else "moments" if adaptive else "weights"
+        self._table = fmx.FlatTable(feature_sizes, k, layout=layout, device=self.device, ftrl=self._ftrl)
+        self._load_weights(first, second, bias0)
+        del first, second
+        self._hyper = self._make_hyper(n)
+
+        # one flat device buffer [W | b | H | P] behind the attention parameters: the kernels read it, the modules see views of it
+        self._attn_flat = torch.cat([lin.weight.detach().reshape(-1), lin.bias.detach(), H0, P0]).float().to(self.device).contiguous()
+        self.attention_linear = lin.to(self.device)
+        self.H = nn.Parameter(torch.empty(0, device=self.device))
+        self.P = nn.Parameter(torch.empty(0, device=self.device))
+        o = 0
+        for prm, shape in ((self.attention_linear.weight, (t, k)), (self.attention_linear.bias, (t,)), (self.H, (t,)), (self.P, (k,))):
+            m = int(np.prod(shape))
+            prm.data = self._attn_flat[o:o + m].view(shape)
+            o += m
+        self._attn_opt = None
+        if adaptive:       # the model's ONE persistent optimizer over the attention parameters (the tables keep their moments)
+            params = self._attn_params()
+            if update_rule == "adam":
+                self._attn_opt = torch.optim.Adam(params, lr=float(n), betas=self._betas(), eps=self._adam["eps"])
+            else:
+                self._attn_opt = torch.optim.Adagrad(params, lr=float(n), eps=self._adagrad["eps"])
+        self._engine = AFMEngine(self._table, self._attn_flat, t, max_batch=max(int(batch_size), 64))
+        self.first_order_embeddings = [_FieldView(self._table, f, False) for f in range(self.field_size)]
+        self.second_order_embeddings = [_FieldView(self._table, f, True) for f in range(self.field_size)]
+
+    def _attn_params(self):
+        return [self.attention_linear.weight, self.attention_linear.bias, self.H, self.P]
+
+    # what is honestly shared with the other classes: the hyper-parameters, the table <-> reference weights, the input path,
+    # the index check and the FTRL state
+    _betas = OnlineFMBase._betas
+    _make_hyper = OnlineFMBase._make_hyper
+    _load_weights = OnlineFMBase._load_weights
+    _export_weights = OnlineFMBase._export_weights
+    bias = OnlineFMBase.bias
+    _inputs = OnlineFMBase._inputs
+    _inputs_fast = OnlineFMBase._inputs_fast
+    strict_index_check = True
+    check_index_flag = OnlineFMBase.check_index_flag
+    _after_step = OnlineFMBase._after_step
+    ftrl_state_dict = OnlineFMBase.ftrl_state_dict
+    load_ftrl_state_dict = OnlineFMBase.load_ftrl_state_dict
+
+    # ------------------------------------------------------------------------------------------------------
+    # forward / predict (reference afm_adam.py:43-74, 170-191)
+    # ------------------------------------------------------------------------------------------------------
+    def forward(self, Xi, Xv):
+        idx_d, xv_d, _ = self._inputs(Xi, Xv)
+        B = self._engine.forward(self._hyper, idx_d, xv_d)
+        self._after_step()
+        return self._engine.logit[:B].clone()
+
+    def predict_proba(self, Xi, Xv):
+        self.eval()
+        return torch.sigmoid(self.forward(Xi, Xv)).cpu().numpy()
+
+    def predict(self, Xi, Xv):
+        return self.predict_proba(Xi, Xv) > 0.5
+
+    # ------------------------------------------------------------------------------------------------------
+    # training
+    # ------------------------------------------------------------------------------------------------------
+    def _apply_attention(self, g):
+        """The attention parameters' update under the model's rule -- the policy OnlineFMBase._fit applies to the hidden layers:
+        sgd the plain step; signadam and ftrl the closed form of a fresh Adam's first step; adam / adagrad the persistent
+        optimizer."""
+        lr = float(self.n)
+        with torch.no_grad():
+            if self._attn_opt is not None:
+                o = 0
+                for prm in self._attn_params():
+                    prm.grad = g[o:o + prm.numel()].view(prm.shape).clone()
+                    o += prm.numel()
+                self._attn_opt.step()
+            elif self.update_rule == "sgd":
+                self._attn_flat.sub_(g, alpha=lr)
+            else:
+                self._attn_flat.sub_(lr * g / (g.abs() + 1e-8))
+
+    def update_embedding(self, Xi, Xv, Y):
+        """One mini-batch step of the whole model (tables and attention) on BCE-with-logits; returns the mean loss."""
+        self.train()
+        idx_d, xv_d, y_d = self._inputs(Xi, Xv, Y)
+        if y_d.numel() != idx_d.shape[0]:
+            raise ValueError(f"Target size ({y_d.numel()}) must be the same as input size ({idx_d.shape[0]})")
+        e = self._engine
+        e.step(self._hyper, self.update_rule, idx_d, xv_d, y_d)
+        self._apply_attention(e.grad)
+        out = e.loss_out[0].clone()
+        self._after_step()
+        return out
+
+    def _mean_logloss(self, Xi, Xv, y, chunk=16384):
+        """The mean BCE-with-logits over a data set, evaluated by batches (reference eval_by_batch, :143-165)."""
+        total, N = 0.0, len(y)
+        self.eval()
+        for o in range(0, N, chunk):
+            idx_d, xv_d, y_d = self._inputs(Xi[o:o + chunk], Xv[o:o + chunk], y[o:o + chunk])
+            B = self._engine.forward(self._hyper, idx_d, xv_d, y_d, loss="logits")
+            total += float(self._engine.loss_b[:B].double().sum())
+            self._after_step()
+        return total / N
+
+    def fit(self, Xi_train, Xv_train, y_train, Xi_valid=None, Xv_valid=None, y_valid=None):
+        """The reference's epoch x batch loop (afm_adam.py:76-141).  -> (train_result, valid_result): per epoch the mean
+        log-loss of the training data and of the validation data (empty without it)."""
+        F = self.field_size
+        Xi_train = np.asarray(Xi_train).reshape((-1, F))
+        Xv_train = np.asarray(Xv_train, dtype=np.float32).reshape((-1, F))
+        y_train = np.asarray(y_train, dtype=np.float32).reshape(-1)
+        is_valid = Xi_valid is not None and len(Xi_valid) > 0
+        if is_valid:
+            Xi_valid = np.asarray(Xi_valid).reshape((-1, F))
+            Xv_valid = np.asarray(Xv_valid, dtype=np.float32).reshape((-1, F))
+            y_valid = np.asarray(y_valid, dtype=np.float32).reshape(-1)
+        x_size = Xi_train.shape[0]
+        train_result, valid_result = [], []
+        for epoch in range(self.n_epochs):
+            epoch_begin_time = time()
+            for offset in range(0, x_size, self.batch_size):
+                end = min(x_size, offset + self.batch_size)
+                self.update_embedding(Xi_train[offset:end], Xv_train[offset:end], y_train[offset:end])
+            train_loss = self._mean_logloss(Xi_train, Xv_train, y_train)
+            train_result.append(train_loss)
+            print("[%d] loss: %.6f time: %.1f s" % (epoch + 1, train_loss, time() - epoch_begin_time))
+            if is_valid:
+                valid_loss = self._mean_logloss(Xi_valid, Xv_valid, y_valid)
+                valid_result.append(valid_loss)
+                print("[%d] valid loss: %.6f time: %.1f s" % (epoch + 1, valid_loss, time() - epoch_begin_time))
+        return train_result, valid_result
+
+    def run_experiment(self, data_Xi, data_Xv, data_Y):
+        """predict() over the data, then the confusion matrix and its checkpoints every 1,000 samples (afm_adam.py:193-223)."""
+        pred = np.asarray(self.predict(data_Xi, data_Xv)).reshape(-1)
+        start = time()
+        y = np.asarray(data_Y).reshape(-1)
+        n = len(y)
+        pos, hit = y == 1, pred == y
+        tp, fn = np.cumsum(pos & hit), np.cumsum(pos & ~hit)
+        tn, fp = np.cumsum(~pos & hit), np.cumsum(~pos & ~hit)
+        accuracy, roc = [], []
+        for i in sorted(set(range(0, n, 1000)) | {n - 1}):
+            roc.append({"tpr": tp[i] / (tp[i] + fn[i] + 1e-16), "fpr": fp[i] / (fp[i] + tn[i] + 1e-16)})
+            accuracy.append((tp[i] + tn[i]) / (i + 1) * 100)
+        cm = {"tp": int(tp[-1]), "fp": int(fp[-1]), "tn": int(tn[-1]), "fn": int(fn[-1])}
+        return time() - start, float(accuracy[-1]), {k: float(v) for k, v in roc[-1].items()}, cm
+
+    # ------------------------------------------------------------------------------------------------------
+    # state (the reference's keys) and pickling
+    # ------------------------------------------------------------------------------------------------------
+    def state_dict(self, *args, **kwargs):
+        first, second, bias = self._export_weights()
+        sd = {"bias": bias.reshape(self._bias_shape).clone(), "n": self.n.detach().clone(),
+              "H": self.H.detach().cpu().clone(), "P": self.P.detach().cpu().clone()}
+        for i in range(self.field_size):
+            sd[f"first_order_embeddings.{i}.weight"] = first[i]
+        for i in range(self.field_size):
+            sd[f"second_order_embeddings.{i}.weight"] = second[i]
+        sd["attention_linear.weight"] = self.attention_linear.weight.detach().cpu().clone()
+        sd["attention_linear.bias"] = self.attention_linear.bias.detach().cpu().clone()
+        return sd
+
+    def load_state_dict(self, state_dict, strict=True):
+        sd = {k: torch.as_tensor(np.asarray(v) if not torch.is_tensor(v) else v) for k, v in state_dict.items()}
+        want = set(self.state_dict().keys())
+        if strict and set(sd.keys()) != want:
+            raise RuntimeError(f"state_dict keys differ: missing {sorted(want - set(sd))}, unexpected {sorted(set(sd) - want)}")
+        first = [sd[f"first_order_embeddings.{i}.weight"].float().cpu() for i in range(self.field_size)]
+        second = [sd[f"second_order_embeddings.{i}.weight"].float().cpu() for i in range(self.field_size)]
+        self._load_weights(first, second, sd["bias"].float().cpu())
+        with torch.no_grad():
+            self.n.copy_(sd["n"].float().cpu())
+            self._hyper = self._make_hyper(float(self.n))
+            for prm, key in zip(self._attn_params(), ("attention_linear.weight", "attention_linear.bias", "H", "P")):
+                prm.copy_(sd[key].float().to(self.device))
+            if self._attn_opt is not None:
+                for g in self._attn_opt.param_groups:
+                    g["lr"] = float(self.n)
+
+    def optimizer_state_dict(self):
+        """{'table': FlatTable.export_moments_state(), 'attention': the attention optimizer's state_dict} on the CPU for the
+        rules with moments ('adam', 'adagrad'); None for the others."""
+        if self._attn_opt is None:
+            return None
+        st = self._attn_opt.state_dict()
+        st = {"state": {i: {k_: (v.detach().cpu().clone() if torch.is_tensor(v) else v) for k_, v in s.items()}
+                        for i, s in st["state"].items()}, "param_groups": st["param_groups"]}
+        return {"table": self._table.export_moments_state(), "attention": st}
+
+    def load_optimizer_state_dict(self, st):
+        if self._attn_opt is None:
+            raise ValueError("load_optimizer_state_dict: this model does not use update_rule 'adam' or 'adagrad'")
+        self._table.load_moments_state(st["table"])
+        self._table.step = int(st["table"]["step"])
+        self._attn_opt.load_state_dict(st["attention"])
+
+    def __getstate__(self):
+        return {"ctor": dict(feature_sizes=list(self.feature_sizes), embedding_size=self.embedding_size,
+                             attention_size=self.attention_size, n_epochs=self.n_epochs, batch_size=self.batch_size,
+                             num_classes=self.num_classes, update_rule=self.update_rule, ftrl=dict(self._ftrl),
+                             adam=dict(self._adam), adagrad=dict(self._adagrad)),
+                "state_dict": {k: v.cpu() for k, v in self.state_dict().items()},
+                "ftrl_state": self.ftrl_state_dict(), "optimizer_state": self.optimizer_state_dict()}
+
+    def __setstate__(self, state):
+        c = state["ctor"]
+        AFMAdam.__init__(self, c["feature_sizes"], embedding_size=c["embedding_size"], attention_size=c["attention_size"],
+                         n_epochs=c["n_epochs"], batch_size=c["batch_size"], num_classes=c["num_classes"],
+                         update_rule=c["update_rule"], ftrl=c["ftrl"], adam=c["adam"], adagrad=c["adagrad"])
+        self.load_state_dict(state["state_dict"])
+        if state.get("ftrl_state") is not None:
+            self.load_ftrl_state_dict(state["ftrl_state"])
+        if state.get("optimizer_state") is not None:
+            self.load_optimizer_state_dict(state["optimizer_state"])
+
+    def __str__(self):
+        return (f"{self._name}-Feature_Sizes{self.feature_sizes}-Embedding_Sizes{self.embedding_size}-"
+                f"Attention_Size{self.attention_size}-Num_Classes{self.num_classes}")

@@ -303,6 +303,23 @@ int fmx_fm_update(const fmx_table_t *table, const fmx_hyper_t *hyper, int32_t ru
                   const float *xv, const float *S, const float *dz_first, const float *dz_bi, const float *gbi,
                   int32_t B, int32_t sample_ld, const float *loss_b, float inv_b, float *loss_out, fmx_stream_t stream);
 
+/* The same row-reduced update from EXPLICIT per-occurrence gradients (a model whose embedding gradient is not of the form
+ * x (S_b - x V) G_b: the attentional FM below).  For every unique row of the batch
+ *     dV[row] = sum_b E[b, f]          dw[row] = sum_b x dz_first[b]
+ * summed in sample order, then ONE application of `rule` per coordinate; the bias gets sum_b dz_first[b].  Same sort, runs,
+ * hand-offs and rule arithmetic as fmx_fm_update (whose dV is the cV - V cA of its runs; here cV = sum E and cA = 0).
+ *   workspace  the one fmx_sort_occurrences filled for the same idx (split large fields are honoured: a piece's occurrences read
+ *              the slot of the field it belongs to)
+ *   xv         [B, F] or null (== 1): the first-order weights' x
+ *   occ_grad   [B, ld_occ]: E[b, f] = dL/dV_row of sample b's row of field f (x applied), kp floats at b * ld_occ + f * kp;
+ *              ld_occ a multiple of 4, >= n_fields * kp; 16-byte aligned
+ *   loss_b, inv_b, loss_out  as fmx_fm_update
+ * Tables whose fields are pieces of index columns (field_cols / field_base) return FMX_ERR_UNSUPPORTED.
+ * Replaces: the embedding part of loss.backward() + optimizer.step() of AFMAdam.fit (reference afm_adam.py:113-118). */
+int fmx_fm_update_occ(const fmx_table_t *table, const fmx_hyper_t *hyper, int32_t rule, void *workspace, int64_t workspace_bytes,
+                      const float *xv, const float *dz_first, const float *occ_grad, int32_t ld_occ, int32_t B, const float *loss_b,
+                      float inv_b, float *loss_out, fmx_stream_t stream);
+
 /* One pure-FM mini-batch step = sort + forward(+loss) + update on one stream.
  * Replaces: FMAdam.update_embedding / FMAdam.fit (reference fm_adam.py:56-82) and every class's
  * update_embedding (deepfm_adam.py:91-104 etc.), which all train on forward_fm only.
@@ -507,6 +524,43 @@ int fmx_mlp_topk(const fmx_mlp_t *mlp, int32_t fm_term, const float *Su, const f
                  const float *Sc, const float *Bc, int32_t ld_c, const float *ac, int32_t N, int32_t kp,
                  const int32_t *excl_offsets, const int32_t *excl_pos, int32_t K, void *workspace, int64_t workspace_bytes,
                  int32_t *top_pos, float *top_score, fmx_stream_t stream);
+
+/* ---- the attentional factorization machine (AFM, Xiao et al. 2017; models/models_online_deep/afm_adam.py) ----
+ * Per sample, with e_f = x_f V[row_f] (k floats) and w_f the first-order weight, over the P = F (F - 1) / 2 pairs in the fixed
+ * order i = 0 .. F-2, j = i+1 .. F-1:
+ *     q_ij = e_i (.) e_j,   s_ij = h . relu(W q_ij + b),   a_ij = softmax over the sample's pairs of s_ij (max-subtracted)
+ *     logit = bias + sum_f w_f x_f + p . sum_ij a_ij q_ij
+ * params: ONE flat fp32 buffer [ W (t x k, row-major) | b (t) | h (t) | p (k) ] (the reference's attention_linear.weight / .bias,
+ * H, P).  Limits: 2 <= n_fields <= 64, k <= 64 (the table's kp), 1 <= t <= 64; anything else: FMX_ERR_UNSUPPORTED.  Tables whose
+ * fields are pieces of index columns: FMX_ERR_UNSUPPORTED.  Every sum is taken in a fixed order and no float is accumulated
+ * with atomics: results are bit-identical run to run. */
+typedef struct fmx_afm {
+  float *params;
+  int32_t k, t;
+} fmx_afm_t;
+
+/* Gather + attention forward: logit_out [B] (may be null); with loss_kind != FMX_LOSS_NONE and y, loss_out [B] = the per-sample
+ * loss (unscaled; may be null).  error [1] or null: set to 1 when an index lies outside its field (that row is treated as absent).
+ * Replaces: AFMAdam.forward (reference afm_adam.py:43-74), with the loss of :95,116. */
+int fmx_afm_forward(const fmx_table_t *table, const fmx_afm_t *afm, const fmx_hyper_t *hyper, const int32_t *idx, const float *xv,
+                    const float *y, int32_t B, int32_t loss_kind, float inv_b, float *logit_out, float *loss_out, int32_t *error,
+                    fmx_stream_t stream);
+
+/* Bytes of caller-owned device workspace an AFM step of batch size B needs: the table's step workspace (fmx_workspace_bytes), the
+ * per-sample dlogit / loss, the per-occurrence embedding gradients [B, F, kp] and the attention partials of the workgroups.  It
+ * must be ZERO-FILLED once before its first use, as fmx_workspace_bytes' is.  Negative on bad arguments. */
+int64_t fmx_afm_workspace_bytes(const fmx_table_t *table, const fmx_afm_t *afm, int32_t B);
+
+/* One AFM mini-batch step on one stream: occurrence sort -> forward with BCE-with-logits -> backward (per-occurrence embedding
+ * gradients, dlogit, per-workgroup attention partials) -> the table update under `rule` (fmx_fm_update_occ) -> the fixed-order
+ * reduction of the attention partials.  The attention parameters are NOT updated: attn_grad_out [t k + 2 t + k] receives the
+ * gradient of the mean loss (inv_b folded in) in the layout of fmx_afm_t.params.  loss_out [1] = inv_b * sum of the per-sample
+ * losses (may be null).  error [1] or null as in fmx_afm_forward.
+ * Replaces: the body of AFMAdam.fit's batch loop (reference afm_adam.py:113-118: forward, loss, backward, optimizer.step on the
+ * embeddings; the caller applies its rule to the attention parameters). */
+int fmx_afm_step(const fmx_table_t *table, const fmx_hyper_t *hyper, int32_t rule, const fmx_afm_t *afm, const int32_t *idx,
+                 const float *xv, const float *y, int32_t B, float inv_b, void *workspace, int64_t workspace_bytes,
+                 float *attn_grad_out, float *loss_out, int32_t *error, fmx_stream_t stream);
 
 /* Streaming read of `bytes` (multiple of 16) with 16-byte loads; sink [1] receives a checksum so the loads stay
  * live.  Used by bench.py to measure the HBM-read ceiling on the same GPU in the same run. */
