@@ -213,17 +213,7 @@ __global__ __launch_bounds__(64) void k_afm(AfmArgs a) {
     const float att = N / Z;  // p . sum_ij a_ij q_ij
     const float logit = (bias_w + fo) + att;
     float loss = 0.f, g = 0.f;
-    if (a.loss_kind != FMX_LOSS_NONE) {
-      const float yv = a.y[b];
-      if (a.loss_kind == FMX_LOSS_BCE_LOGITS) {
-        loss = bcewl(logit, yv);
-        g = (sigmoidf_(logit) - yv) * a.inv_b;
-      } else {
-        const float pp = sigmoidf_(logit);
-        loss = bcewl(pp, yv);
-        g = (sigmoidf_(pp) - yv) * pp * (1.f - pp) * a.inv_b;
-      }
-    }
+    if (a.loss_kind != FMX_LOSS_NONE) bce_loss_dz(a.loss_kind, logit, a.y[b], a.inv_b, loss, g);
     if (lane == 0) {
       if (a.logit) a.logit[b] = logit;
       if (a.loss) a.loss[b] = loss;

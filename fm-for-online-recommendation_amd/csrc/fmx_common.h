@@ -184,10 +184,41 @@ __device__ __forceinline__ void moments_upd4(float4 &p, float4 &m, float4 &v, fl
   moments_upd<RULE>(p.w, m.w, v.w, g.w, h);
 }
 
+// ---- the table's bias, held as the words (b0, b1, b2) of fmx_table_t.bias: WEIGHTS (b, -, -), FTRL (z, n, -), MOMENTS (b, m, v) ----
+// the bias weight the logit adds
+template <int LAYOUT>
+__device__ __forceinline__ float bias_weight(float b0, float b1, const fmx_hyper_t &h) {
+  return LAYOUT == FMX_LAYOUT_FTRL ? ftrl_w(b0, b1, h) : b0;
+}
+// one step of the rule by the bias gradient g
+template <int LAYOUT, int RULE>
+__device__ __forceinline__ void bias_step(float &b0, float &b1, float &b2, float g, const fmx_hyper_t &h) {
+  if (LAYOUT == FMX_LAYOUT_WEIGHTS) {
+    b0 = apply_rule<RULE>(b0, g, h);
+  } else if (LAYOUT == FMX_LAYOUT_MOMENTS) {
+    moments_upd<RULE>(b0, b1, b2, g, h);
+  } else {
+    const float w = ftrl_w(b0, b1, h);
+    ftrl_upd(b0, b1, w, g, h);
+  }
+}
+
 __device__ __forceinline__ float sigmoidf_(float z) { return 1.f / (1.f + expf(-z)); }
 // F.binary_cross_entropy_with_logits per element
 __device__ __forceinline__ float bcewl(float z, float y) {
   return (1.f - y) * z + log1pf(expf(-fabsf(z))) + fmaxf(-z, 0.f);
+}
+// the loss of logit z against label y and its gradient d loss / d z scaled by inv_b (1 / batch): FMX_LOSS_BCE_LOGITS, or
+// FMX_LOSS_BCE_SIGMOID (the reference's BCEWithLogits applied to sigmoid(z))
+__device__ __forceinline__ void bce_loss_dz(int loss_kind, float z, float y, float inv_b, float &loss, float &dz) {
+  if (loss_kind == FMX_LOSS_BCE_LOGITS) {
+    loss = bcewl(z, y);
+    dz = (sigmoidf_(z) - y) * inv_b;
+  } else {
+    const float p = sigmoidf_(z);
+    loss = bcewl(p, y);
+    dz = (sigmoidf_(p) - y) * p * (1.f - p) * inv_b;
+  }
 }
 
 // lane ^ M exchanges without the LDS crossbar (ds_bpermute made the sort LDS-pipe bound): DPP for M = 1, 2, 4, 8,
@@ -219,6 +250,38 @@ __device__ __forceinline__ float xor_lane_f(float v, int lane) {
 template <int M>
 __device__ __forceinline__ float4 xor_lane_f4(float4 v, int lane) {
   return {xor_lane_f<M>(v.x, lane), xor_lane_f<M>(v.y, lane), xor_lane_f<M>(v.z, lane), xor_lane_f<M>(v.w, lane)};
+}
+
+// ---- the FM's per-sample sums: lane group `slot` (LPR lanes, lane q owns coordinates 4q..4q+3) holds the partial sums s, ss, fo
+//      of e = x V, e * e and x w over ITS fields ----
+template <int M, int LPR>
+__device__ __forceinline__ void fm_sums_level(float4 &s, float4 &ss, float &fo, int lane, int groups) {
+  if (LPR <= M && M / LPR < groups) {
+    s = s + xor_lane_f4<M>(s, lane);
+    ss = ss + xor_lane_f4<M>(ss, lane);
+    fo += xor_lane_f<M>(fo, lane);
+  }
+}
+// the field sums: a butterfly over the lane groups (lanes with equal q; slot ^ 1, ^ 2, ^ 4, ...), DPP / permlane exchanges (no LDS
+// crossbar).  `groups` (a power of two) stops it inside runs of that many lane groups (k_fm_forward_part: an owner's block); by
+// default every lane group of the wave ends with the sums of all of them.
+template <int LPR>
+__device__ __forceinline__ void fm_field_sums(float4 &s, float4 &ss, float &fo, int lane, int groups = WAVE) {
+  fm_sums_level<1, LPR>(s, ss, fo, lane, groups);
+  fm_sums_level<2, LPR>(s, ss, fo, lane, groups);
+  fm_sums_level<4, LPR>(s, ss, fo, lane, groups);
+  fm_sums_level<8, LPR>(s, ss, fo, lane, groups);
+  fm_sums_level<16, LPR>(s, ss, fo, lane, groups);
+  fm_sums_level<32, LPR>(s, ss, fo, lane, groups);
+}
+// the bi-interaction vector from the field sums, and its sum over the LPR lanes of a group (every lane of the group gets it)
+template <int LPR>
+__device__ __forceinline__ float4 fm_bi(float4 s, float4 ss, float &sbi) {
+  const float4 bi = 0.5f * (s * s - ss);
+  sbi = (bi.x + bi.y) + (bi.z + bi.w);
+#pragma unroll
+  for (int m = 1; m < LPR; m <<= 1) sbi += __shfl_xor(sbi, m);
+  return bi;
 }
 
 // deterministic block reduction of src[0..n): every thread sums a strided set of elements (16-byte groups when dense),

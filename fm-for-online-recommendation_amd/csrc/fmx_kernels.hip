@@ -113,19 +113,9 @@ __device__ __forceinline__ void forward_finish(const FwdArgs &a, const int b, co
   const int kp = LPR * 4;
   if (bad && a.out.error) *a.out.error = 1;
 
-  // field sums: butterfly over the slots (lanes with equal q), DPP / permlane exchanges (no LDS crossbar)
-#define FMX_BFLY(M)                               \
-  if (LPR <= M) {                                 \
-    s = s + xor_lane_f4<M>(s, lane);              \
-    ss = ss + xor_lane_f4<M>(ss, lane);           \
-    fo += xor_lane_f<M>(fo, lane);                \
-  }
-  FMX_BFLY(1) FMX_BFLY(2) FMX_BFLY(4) FMX_BFLY(8) FMX_BFLY(16) FMX_BFLY(32)
-#undef FMX_BFLY
-  const float4 bi = 0.5f * (s * s - ss);
-  float sbi = (bi.x + bi.y) + (bi.z + bi.w);
-#pragma unroll
-  for (int m = 1; m < LPR; m <<= 1) sbi += __shfl_xor(sbi, m);
+  fm_field_sums<LPR>(s, ss, fo, lane);
+  float sbi;
+  const float4 bi = fm_bi<LPR>(s, ss, sbi);
   // fo: lanes with q != 0 hold the sum of zeros; take the q == 0 value
   fo = __shfl(fo, 0);
   FMX_FSTAMP(3, sbi);
@@ -140,16 +130,8 @@ __device__ __forceinline__ void forward_finish(const FwdArgs &a, const int b, co
     if (a.out.sbi) a.out.sbi[b] = sbi;
     if (a.out.logit) a.out.logit[b] = z;
     if (a.loss_kind != FMX_LOSS_NONE) {
-      const float y = y_early;
       float loss, dz;
-      if (a.loss_kind == FMX_LOSS_BCE_LOGITS) {
-        loss = bcewl(z, y);
-        dz = (sigmoidf_(z) - y) * a.inv_b;
-      } else {
-        const float p = sigmoidf_(z);
-        loss = bcewl(p, y);
-        dz = (sigmoidf_(p) - y) * p * (1.f - p) * a.inv_b;
-      }
+      bce_loss_dz(a.loss_kind, z, y_early, a.inv_b, loss, dz);
       FMX_FSTAMP(4, dz);
       if (a.out.loss) a.out.loss[(size_t)b * a.ld1] = loss;
       if (a.out.dz) a.out.dz[(size_t)b * a.ld1] = dz;
@@ -255,7 +237,7 @@ __device__ __forceinline__ void forward_sample(const FwdArgs &a, const int b, co
     __builtin_amdgcn_sched_barrier(0);  // ... and every row request before the first sum
     // the bias weight while the rows are in flight (its loads came back with the window's)
     if (it == 0) {
-      bias = LAYOUT == FMX_LAYOUT_WEIGHTS ? bias0_early : ftrl_w(bias0_early, bias1_early, a.h);
+      bias = bias_weight<LAYOUT>(bias0_early, bias1_early, a.h);
       asm volatile("" ::"v"(bias));  // (otherwise the compiler sinks it into lane 0's epilogue, behind the butterfly)
     }
     __builtin_amdgcn_sched_barrier(0);
@@ -380,15 +362,7 @@ __global__ __launch_bounds__(256) void k_fm_forward_part(PartArgs a) {
     bad = bad || (!pieces && live[p] && !ok[p]);
   }
   if (bad && a.error) *a.error = 1;
-  // the butterfly levels inside the block's lane groups (wave-uniform conditions)
-#define FMX_BFLY_L(M)                              \
-  if (LPR <= M && (M / LPR) < SL) {                \
-    s = s + xor_lane_f4<M>(s, lane);               \
-    ss = ss + xor_lane_f4<M>(ss, lane);            \
-    fo += xor_lane_f<M>(fo, lane);                 \
-  }
-  FMX_BFLY_L(1) FMX_BFLY_L(2) FMX_BFLY_L(4) FMX_BFLY_L(8) FMX_BFLY_L(16) FMX_BFLY_L(32)
-#undef FMX_BFLY_L
+  fm_field_sums<LPR>(s, ss, fo, lane, SL);  // the butterfly levels inside the block's lane groups (wave-uniform conditions)
   if (valid && slot_l == 0) {
     const int dst = b / a.group;
     float *r = a.rec + (((size_t)dst * gridDim.y + blockIdx.y) * a.group + (b - dst * a.group)) * REC;
@@ -443,32 +417,19 @@ __global__ __launch_bounds__(256) void k_fm_forward_finish(FinishArgs a) {
       fo[r] += fo[r + st];
     }
   }
-  const float4 bi = 0.5f * (s[0] * s[0] - ss[0]);
-  float sbi = (bi.x + bi.y) + (bi.z + bi.w);
-#pragma unroll
-  for (int m = 1; m < LPR; m <<= 1) sbi += __shfl_xor(sbi, m);
+  float sbi;
+  const float4 bi = fm_bi<LPR>(s[0], ss[0], sbi);
   if (!valid) return;
   if (a.out.S) *reinterpret_cast<float4 *>(a.out.S + (size_t)b * a.ldS + 4 * q) = s[0];
   if (a.out.bi) *reinterpret_cast<float4 *>(a.out.bi + (size_t)b * kp + 4 * q) = bi;
   if (q == 0) {
-    float bias;
-    if (LAYOUT == FMX_LAYOUT_WEIGHTS) bias = bias0;
-    else bias = ftrl_w(bias0, bias1, a.h);
-    const float z = fo[0] + sbi + bias;
+    const float z = fo[0] + sbi + bias_weight<LAYOUT>(bias0, bias1, a.h);
     if (a.out.sfirst) a.out.sfirst[b] = fo[0];
     if (a.out.sbi) a.out.sbi[b] = sbi;
     if (a.out.logit) a.out.logit[b] = z;
     if (a.loss_kind != FMX_LOSS_NONE) {
-      const float y = y_early;
       float loss, dz;
-      if (a.loss_kind == FMX_LOSS_BCE_LOGITS) {
-        loss = bcewl(z, y);
-        dz = (sigmoidf_(z) - y) * a.inv_b;
-      } else {
-        const float pp = sigmoidf_(z);
-        loss = bcewl(pp, y);
-        dz = (sigmoidf_(pp) - y) * pp * (1.f - pp) * a.inv_b;
-      }
+      bce_loss_dz(a.loss_kind, z, y_early, a.inv_b, loss, dz);
       if (a.out.loss) a.out.loss[(size_t)b * a.ld1] = loss;
       if (a.out.dz) a.out.dz[(size_t)b * a.ld1] = dz;
     }
@@ -531,21 +492,12 @@ __host__ __device__ inline int red_slices(int B) { return (B + RED_SLICE - 1) / 
 
 template <int LAYOUT, int RULE>
 __device__ __forceinline__ void apply_bias_and_loss(const UpdArgs &a, float db, float ls) {
-  if (LAYOUT == FMX_LAYOUT_WEIGHTS) {
-    st4(a.bias, apply_rule<RULE>(a.bias[0], db, a.h));
-  } else if (LAYOUT == FMX_LAYOUT_MOMENTS) {  // (b, m_b, v_b, 0): the bias is one more coordinate
-    float p = a.bias[0], m = a.bias[1], v = a.bias[2];
-    moments_upd<RULE>(p, m, v, db, a.h);
-    st4(a.bias, p);
-    if (RULE == FMX_RULE_ADAM) st4(a.bias + 1, m);
-    st4(a.bias + 2, v);
-  } else {
-    float z = a.bias[0], n = a.bias[1];
-    const float w = ftrl_w(z, n, a.h);
-    ftrl_upd(z, n, w, db, a.h);
-    st4(a.bias, z);
-    st4(a.bias + 1, n);
-  }
+  constexpr bool MOM = LAYOUT == FMX_LAYOUT_MOMENTS;
+  float b0 = a.bias[0], b1 = LAYOUT != FMX_LAYOUT_WEIGHTS ? a.bias[1] : 0.f, b2 = MOM ? a.bias[2] : 0.f;
+  bias_step<LAYOUT, RULE>(b0, b1, b2, db, a.h);
+  st4(a.bias, b0);
+  if (LAYOUT == FMX_LAYOUT_FTRL || (MOM && RULE == FMX_RULE_ADAM)) st4(a.bias + 1, b1);
+  if (MOM) st4(a.bias + 2, b2);
   if (a.loss_b && a.loss_out) {
     int i = 0;
     if (a.step_counter) {
@@ -1141,6 +1093,8 @@ __device__ __forceinline__ RowRegs load_row_sc1(const float *rp, int q, int kp, 
   return r;
 }
 
+// (The field walk below and k_online_mlp's stay two copies: one shared walk left k_fm_online's forward waiting on the prefetch
+// of the next sample with vmcnt(0) instead of the row loads only: 3.2 -> 3.6 us per sample.)
 template <int LPR, int LAYOUT, int RULE, int NP>
 __global__ __launch_bounds__(64) void k_fm_online(OnlineArgs a) {
   constexpr int SLOTS = WAVE / LPR;
@@ -1217,33 +1171,17 @@ __global__ __launch_bounds__(64) void k_fm_online(OnlineArgs a) {
         fo += row[p].fo.x * x[p];
       }
     }
-#define FMX_BFLY(M)                               \
-  if (LPR <= M) {                                 \
-    s = s + xor_lane_f4<M>(s, lane);              \
-    ss = ss + xor_lane_f4<M>(ss, lane);           \
-    fo += xor_lane_f<M>(fo, lane);                \
-  }
-    FMX_BFLY(1) FMX_BFLY(2) FMX_BFLY(4) FMX_BFLY(8) FMX_BFLY(16) FMX_BFLY(32)
-#undef FMX_BFLY
-    const float4 bi = 0.5f * (s * s - ss);
-    float sbi = (bi.x + bi.y) + (bi.z + bi.w);
-#pragma unroll
-    for (int m = 1; m < LPR; m <<= 1) sbi += __shfl_xor(sbi, m);
+    fm_field_sums<LPR>(s, ss, fo, lane);
+    float sbi;
+    fm_bi<LPR>(s, ss, sbi);
     fo = __shfl(fo, 0);
-    const float bias_w = LAYOUT == FMX_LAYOUT_FTRL ? ftrl_w(b0, b1, a.h) : b0;
+    const float bias_w = bias_weight<LAYOUT>(b0, b1, a.h);
     const float z = fo + sbi + bias_w;
     // ADAM: sample i is step a.h.step + i + 1 -- its constants as the host derives them for a launch (same function, same bits)
     fmx_hyper_t h = a.h;
     if (RULE == FMX_RULE_ADAM) adam_consts(a.h.lr, a.h.beta1, a.h.beta2, a.h.step + i + 1, h.lr, h.beta1, h.beta2);
     float loss, dz;
-    if (a.loss_kind == FMX_LOSS_BCE_LOGITS) {
-      loss = bcewl(z, y);
-      dz = sigmoidf_(z) - y;
-    } else {
-      const float pz = sigmoidf_(z);
-      loss = bcewl(pz, y);
-      dz = (sigmoidf_(pz) - y) * pz * (1.f - pz);
-    }
+    bce_loss_dz(a.loss_kind, z, y, 1.0f, loss, dz);
     if (lane == 0) {
       a.pred[i] = sigmoidf_(z) > 0.5f ? 1 : 0;
       if (a.loss) a.loss[i] = loss;
@@ -1257,14 +1195,7 @@ __global__ __launch_bounds__(64) void k_fm_online(OnlineArgs a) {
                                  xG, h);
       }
     }
-    if (LAYOUT == FMX_LAYOUT_WEIGHTS) {
-      b0 = apply_rule<RULE>(b0, dz, a.h);
-    } else if (MOM) {
-      moments_upd<RULE>(b0, b1, b2, dz, h);
-    } else {
-      const float w = ftrl_w(b0, b1, a.h);
-      ftrl_upd(b0, b1, w, dz, a.h);
-    }
+    bias_step<LAYOUT, RULE>(b0, b1, b2, dz, h);  // (h is a.h but under ADAM, which pairs with MOMENTS alone)
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the row stores are acknowledged before the next sample's loads
   }
   const bool any_bad = __ballot(bad) != 0ull;  // an out-of-range index seen by any lane group
@@ -1418,16 +1349,8 @@ __device__ void mlp_small_body(const MlpArgs &a) {
         if (a.layers_out) a.layers_out[(size_t)l * B + b] = sigmoidf_(z);
         if (l == L - 1 && a.out) a.out[b] = z;
       } else if (a.mode == MLP_MODE_FIT) {
-        const float yy = a.y[b];
         float loss;
-        if (a.loss_kind == FMX_LOSS_BCE_LOGITS) {
-          loss = bcewl(z, yy);
-          g = (sigmoidf_(z) - yy) * a.inv_b;
-        } else {
-          const float p = sigmoidf_(z);
-          loss = bcewl(p, yy);
-          g = (sigmoidf_(p) - yy) * p * (1.f - p) * a.inv_b;
-        }
+        bce_loss_dz(a.loss_kind, z, a.y[b], a.inv_b, loss, g);
         a.dz_out[b] = g;
         X(0, b, MLP_MAX_W - 1) = loss;  // parked for the ordered sum below (k <= 63 is host-checked in FIT mode)
       } else {  // HEDGE: BCELoss(sigmoid(z), y), mean over the batch; d/dz = (p - y) / B
@@ -1555,7 +1478,7 @@ __global__ __launch_bounds__(256) void k_online_mlp(OnlineMlpArgs a) {
   const int kp = LPR * 4;
   for (int i = tid; i < a.n_params; i += blockDim.x) p_lds[i] = a.params[i];
   if (a.hedge && tid < a.n_layers) alpha_lds[tid] = a.alpha[tid];
-  float b0 = a.bias[0], b1 = LAYOUT == FMX_LAYOUT_FTRL ? a.bias[1] : 0.f;
+  float b0 = a.bias[0], b1 = LAYOUT == FMX_LAYOUT_FTRL ? a.bias[1] : 0.f, b2 = 0.f;  // (with_rule_wf: never MOMENTS)
   int64_t lo[NP];
   uint32_t vocab[NP];
   bool live[NP];
@@ -1621,21 +1544,12 @@ __global__ __launch_bounds__(256) void k_online_mlp(OnlineMlpArgs a) {
           fo += row[p].fo.x * x[p];
         }
       }
-#define FMX_BFLY(M)                               \
-  if (LPR <= M) {                                 \
-    s = s + xor_lane_f4<M>(s, lane);              \
-    ss = ss + xor_lane_f4<M>(ss, lane);           \
-    fo += xor_lane_f<M>(fo, lane);                \
-  }
-      FMX_BFLY(1) FMX_BFLY(2) FMX_BFLY(4) FMX_BFLY(8) FMX_BFLY(16) FMX_BFLY(32)
-#undef FMX_BFLY
+      fm_field_sums<LPR>(s, ss, fo, lane);
       S = s;
-      const float4 bi = 0.5f * (s * s - ss);
-      float sbi = (bi.x + bi.y) + (bi.z + bi.w);
-#pragma unroll
-      for (int m = 1; m < LPR; m <<= 1) sbi += __shfl_xor(sbi, m);
+      float sbi;
+      const float4 bi = fm_bi<LPR>(s, ss, sbi);
       fo = __shfl(fo, 0);
-      const float bias_w = LAYOUT == FMX_LAYOUT_WEIGHTS ? b0 : ftrl_w(b0, b1, a.h);
+      const float bias_w = bias_weight<LAYOUT>(b0, b1, a.h);
       if (lane < LPR) {
         bi_lds[4 * q] = bi.x;
         bi_lds[4 * q + 1] = bi.y;
@@ -1686,12 +1600,7 @@ __global__ __launch_bounds__(256) void k_online_mlp(OnlineMlpArgs a) {
                                    a.h);
         }
       }
-      if (LAYOUT == FMX_LAYOUT_WEIGHTS) {
-        b0 = apply_rule<RULE>(b0, dz, a.h);
-      } else {
-        const float w = ftrl_w(b0, b1, a.h);
-        ftrl_upd(b0, b1, w, dz, a.h);
-      }
+      bias_step<LAYOUT, RULE>(b0, b1, b2, dz, a.h);
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the row stores are acknowledged before the next sample's loads
     }
     __syncthreads();

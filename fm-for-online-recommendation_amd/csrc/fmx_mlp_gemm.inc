@@ -309,16 +309,8 @@ __global__ __launch_bounds__(256) void k_mlp_loss(MlpLossArgs a) {
 #pragma unroll
   for (int m = 1; m < 64; m <<= 1) s += __shfl_xor(s, m);
   const float z = a.base[b] + s;
-  const float y = a.y[b];
   float loss, dz;
-  if (a.loss_kind == FMX_LOSS_BCE_LOGITS) {
-    loss = bcewl(z, y);
-    dz = (sigmoidf_(z) - y) * a.inv_b;
-  } else {
-    const float p = sigmoidf_(z);
-    loss = bcewl(p, y);
-    dz = (sigmoidf_(p) - y) * p * (1.f - p) * a.inv_b;
-  }
+  bce_loss_dz(a.loss_kind, z, a.y[b], a.inv_b, loss, dz);
   if (lane == 0) {
     if (a.out) a.out[b] = z;
     a.dz[b] = dz;
@@ -712,16 +704,9 @@ __global__ __launch_bounds__(256) void k_mlp_chain(ChainArgs a) {
     float dz = 0.f;
     if (b < a.B) {
       const float s = ((red[t] + red[CH_R + t]) + red[2 * CH_R + t]) + red[3 * CH_R + t];
-      const float z = a.base[b] + s, yy = a.y[b];
+      const float z = a.base[b] + s;
       float loss;
-      if (a.loss_kind == FMX_LOSS_BCE_LOGITS) {
-        loss = bcewl(z, yy);
-        dz = (sigmoidf_(z) - yy) * a.inv_b;
-      } else {
-        const float pp = sigmoidf_(z);
-        loss = bcewl(pp, yy);
-        dz = (sigmoidf_(pp) - yy) * pp * (1.f - pp) * a.inv_b;
-      }
+      bce_loss_dz(a.loss_kind, z, a.y[b], a.inv_b, loss, dz);
       if (a.logit_out) a.logit_out[b] = z;
       a.dz_out[b] = dz;
       a.loss_b[b] = loss;
