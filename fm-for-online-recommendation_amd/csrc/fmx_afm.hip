@@ -113,6 +113,39 @@ __device__ __forceinline__ void tile_pair(int F, int i0, int l, int &i, int &j) 
   j = i + 1 + l;
 }
 
+// the attention parameters into LDS for the whole launch, W rows and p padded to kp with zeros
+template <int KP>
+__device__ __forceinline__ void stage_params(float *sm, const AfmLds &L, const float *params, int k, int t, int lane) {
+  for (int i = lane; i < t * KP; i += WAVE) {
+    const int u = i / KP, d = i - u * KP;
+    sm[L.W + i] = d < k ? params[u * k + d] : 0.f;
+  }
+  for (int u = lane; u < t; u += WAVE) {
+    sm[L.bW + u] = params[t * k + u];
+    sm[L.h + u] = params[t * k + t + u];
+  }
+  for (int d = lane; d < KP; d += WAVE) sm[L.p + d] = d < k ? params[t * k + 2 * t + d] : 0.f;
+}
+
+// field f of sample b (full-width rows [B, F]): x V[row] (kp floats) to dst, returns x w[row]; an index outside its field is
+// an absent row (zeros) and sets the error word
+template <int KP>
+__device__ __forceinline__ float gather_field(const float *rows, const int64_t *foff, const int32_t *idx, const float *xv, int32_t *error,
+                                              int stride, int F, int b, int f, float *dst) {
+  const int64_t base = foff[f], rows_f = foff[f + 1] - base;
+  const int ix = idx[(size_t)b * F + f];
+  const float x = xv ? xv[(size_t)b * F + f] : 1.f;
+  const bool ok = ix >= 0 && (int64_t)ix < rows_f;
+  if (!ok && error) *error = 1;
+  const float *rp = rows + (size_t)(base + (ok ? ix : 0)) * stride;
+#pragma unroll
+  for (int d = 0; d < KP; d += 4) {
+    const float4 v = ok ? *reinterpret_cast<const float4 *>(rp + d) : splat(0.f);
+    *reinterpret_cast<float4 *>(dst + d) = x * v;
+  }
+  return ok ? rp[KP] * x : 0.f;
+}
+
 // q = e_i (.) e_j; r = p . q (d ascending); s = h . relu(W q + b) (u ascending, each unit's sum d ascending from b_u)
 template <int KP>
 __device__ __forceinline__ void pair_terms(const float *sm, const AfmLds &L, int t, int i, int j, float (&q)[KP], float &r, float &s) {
@@ -137,6 +170,25 @@ __device__ __forceinline__ void pair_terms(const float *sm, const AfmLds &L, int
   }
 }
 
+// every pair's s and p . q of the F embeddings in LDS, tile by tile, into L.s / L.r in pair order
+template <int KP>
+__device__ __forceinline__ void score_pairs(float *sm, const AfmLds &L, int F, int t, int lane) {
+  for (int i0 = 0, pb = 0; i0 < F - 1;) {
+    int n;
+    const int i1 = next_tile(F, i0, n);
+    if (lane < n) {
+      int i, j;
+      tile_pair(F, i0, lane, i, j);
+      float q[KP], r, s;
+      pair_terms<KP>(sm, L, t, i, j, q, r, s);
+      sm[L.s + pb + lane] = s;
+      sm[L.r + pb + lane] = r;
+    }
+    pb += n;
+    i0 = i1;
+  }
+}
+
 template <int KP, bool FTRL, bool BWD>
 __global__ __launch_bounds__(64) void k_afm(AfmArgs a) {
   extern __shared__ float4 lds4[];
@@ -144,15 +196,7 @@ __global__ __launch_bounds__(64) void k_afm(AfmArgs a) {
   const int lane = threadIdx.x;
   const int F = a.F, k = a.k, t = a.t, P = F * (F - 1) / 2;
   const AfmLds L = afm_lds(F, KP, t, BWD);
-  for (int i = lane; i < t * KP; i += WAVE) {
-    const int u = i / KP, d = i - u * KP;
-    sm[L.W + i] = d < k ? a.params[u * k + d] : 0.f;
-  }
-  for (int u = lane; u < t; u += WAVE) {
-    sm[L.bW + u] = a.params[t * k + u];
-    sm[L.h + u] = a.params[t * k + t + u];
-  }
-  for (int d = lane; d < KP; d += WAVE) sm[L.p + d] = d < k ? a.params[t * k + 2 * t + d] : 0.f;
+  stage_params<KP>(sm, L, a.params, k, t, lane);
   if (BWD) {
     for (int i = lane; i < t * KP; i += WAVE) sm[L.aW + i] = 0.f;
     for (int u = lane; u < t; u += WAVE) sm[L.ab + u] = sm[L.ah + u] = 0.f;
@@ -163,38 +207,12 @@ __global__ __launch_bounds__(64) void k_afm(AfmArgs a) {
   for (int b = blockIdx.x; b < a.B; b += gridDim.x) {
     // ---- gather: lane f loads field f's row (an index outside its field: the row is absent, the error word says so) ----
     float fo = 0.f;
-    if (lane < F) {
-      const int64_t base = a.foff[lane], rows_f = a.foff[lane + 1] - base;
-      const int ix = a.idx[(size_t)b * F + lane];
-      const float x = a.xv ? a.xv[(size_t)b * F + lane] : 1.f;
-      const bool ok = ix >= 0 && (int64_t)ix < rows_f;
-      if (!ok && a.error) *a.error = 1;
-      const float *rp = a.rows + (size_t)(base + (ok ? ix : 0)) * a.stride;
-#pragma unroll
-      for (int d = 0; d < KP; d += 4) {
-        const float4 v = ok ? *reinterpret_cast<const float4 *>(rp + d) : splat(0.f);
-        *reinterpret_cast<float4 *>(sm + L.e + lane * KP + d) = x * v;
-      }
-      fo = ok ? rp[KP] * x : 0.f;
-    }
+    if (lane < F) fo = gather_field<KP>(a.rows, a.foff, a.idx, a.xv, a.error, a.stride, F, b, lane, sm + L.e + lane * KP);
     fo = wave_sum(fo);
     __syncthreads();
 
     // ---- pass A: every pair's score s and p . q ----
-    for (int i0 = 0, pb = 0; i0 < F - 1;) {
-      int n;
-      const int i1 = next_tile(F, i0, n);
-      if (lane < n) {
-        int i, j;
-        tile_pair(F, i0, lane, i, j);
-        float q[KP], r, s;
-        pair_terms<KP>(sm, L, t, i, j, q, r, s);
-        sm[L.s + pb + lane] = s;
-        sm[L.r + pb + lane] = r;
-      }
-      pb += n;
-      i0 = i1;
-    }
+    score_pairs<KP>(sm, L, F, t, lane);
     __syncthreads();
 
     // ---- softmax over the sample's pairs (max-subtracted); the logit, loss and dlogit ----
@@ -343,6 +361,60 @@ __global__ __launch_bounds__(256) void k_afm_reduce(const float *part, int n, in
   if (qt == 0 && g < G) grad[g] = ((sm[0][c] + sm[1][c]) + sm[2][c]) + sm[3][c];
 }
 
+// fmx_afm_side: one side of a recommendation (the context fields or the item fields of full-width rows)
+struct AfmSideArgs {
+  const float *rows;
+  const int64_t *foff;
+  const float *bias;
+  const int32_t *idx;
+  const float *xv;
+  const float *params;
+  float *E;      // [R, n, kp]
+  float *stats;  // [R, 4]: (lin, m, Z, R)
+  int32_t *error;
+  fmx_hyper_t h;
+  int32_t R, F, n, k, t, stride, with_bias;
+  int8_t fields[AFM_MAX_F];
+};
+
+// k_afm's forward on the n selected fields of each row alone: lane l gathers field fields[l] (k_afm's gather), pass A over the
+// n (n - 1) / 2 pairs of the selected fields in pair order, then the max-subtracted sums of k_afm's softmax.  One wavefront per
+// row and nothing shared between rows: a row's results do not depend on R or on the other rows.
+template <int KP, bool FTRL>
+__global__ __launch_bounds__(64) void k_afm_side(AfmSideArgs a) {
+  extern __shared__ float4 lds4[];
+  float *sm = reinterpret_cast<float *>(lds4);
+  const int lane = threadIdx.x;
+  const int n = a.n, t = a.t, P = n * (n - 1) / 2;
+  const AfmLds L = afm_lds(n, KP, t, false);
+  stage_params<KP>(sm, L, a.params, a.k, t, lane);
+  const float bias_w = !a.with_bias ? 0.f : FTRL ? ftrl_w(a.bias[0], a.bias[1], a.h) : a.bias[0];
+  for (int b = blockIdx.x; b < a.R; b += gridDim.x) {
+    float fo = 0.f;
+    if (lane < n) fo = gather_field<KP>(a.rows, a.foff, a.idx, a.xv, a.error, a.stride, a.F, b, a.fields[lane], sm + L.e + lane * KP);
+    fo = wave_sum(fo);
+    __syncthreads();
+    score_pairs<KP>(sm, L, n, t, lane);
+    __syncthreads();
+    float mx = -INFINITY;
+    for (int l = lane; l < P; l += WAVE) mx = fmaxf(mx, sm[L.s + l]);
+    mx = wave_max(mx);
+    float Z = 0.f, N = 0.f;
+    for (int l = lane; l < P; l += WAVE) {
+      const float ex = expf(sm[L.s + l] - mx);
+      Z += ex;
+      N += ex * sm[L.r + l];
+    }
+    Z = wave_sum(Z);
+    N = wave_sum(N);
+    if (lane == 0)
+      *reinterpret_cast<float4 *>(a.stats + (size_t)b * 4) = float4{a.with_bias ? bias_w + fo : fo, mx, Z, N};
+    float *Eb = a.E + (size_t)b * n * KP;
+    for (int l = lane * 4; l < n * KP; l += WAVE * 4) *reinterpret_cast<float4 *>(Eb + l) = *reinterpret_cast<const float4 *>(sm + L.e + l);
+    __syncthreads();  // the next row's gather overwrites e
+  }
+}
+
 // ------------------------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------------------------
@@ -378,6 +450,20 @@ int launch_afm_k(const AfmArgs &a, hipStream_t st) {
   if (raised != hipSuccess) return fail(FMX_ERR_LAUNCH, "hipFuncSetAttribute(k_afm): %s", hipGetErrorString(raised));
   hipLaunchKernelGGL((k_afm<KP, FTRL, BWD>), dim3(afm_grid(a.B)), dim3(64), lds, st, a);
   return check_launch("k_afm");
+}
+
+template <int KP, bool FTRL>
+int launch_afm_side_k(const AfmSideArgs &a, hipStream_t st) {
+  const size_t lds = (size_t)afm_lds(a.n, KP, a.t, false).total * 4;
+  static std::once_flag once;
+  static hipError_t raised = hipSuccess;
+  std::call_once(once, [] {
+    raised = hipFuncSetAttribute(reinterpret_cast<const void *>(k_afm_side<KP, FTRL>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                 (int)(afm_lds(AFM_MAX_F, KP, AFM_MAX_T, false).total * 4));
+  });
+  if (raised != hipSuccess) return fail(FMX_ERR_LAUNCH, "hipFuncSetAttribute(k_afm_side): %s", hipGetErrorString(raised));
+  hipLaunchKernelGGL((k_afm_side<KP, FTRL>), dim3(afm_grid(a.R)), dim3(64), lds, st, a);
+  return check_launch("k_afm_side");
 }
 
 template <bool BWD>
@@ -504,6 +590,52 @@ int fmx_afm_step(const fmx_table_t *table, const fmx_hyper_t *hyper, int32_t rul
     return rc;
   hipLaunchKernelGGL(k_afm_reduce, dim3((a.G + 63) / 64), dim3(256), 0, st, w.part, afm_grid(B), a.G, attn_grad_out);
   return check_launch("k_afm_reduce");
+}
+
+int fmx_afm_side(const fmx_table_t *table, const fmx_afm_t *afm, const fmx_hyper_t *hyper, const int32_t *idx, const float *xv,
+                 int32_t R, const int32_t *fields, int32_t n_sel, int32_t with_bias, float *E_out, float *stats_out, int32_t *error,
+                 fmx_stream_t stream) {
+  if (int rc = check_afm(table, afm, "fmx_afm_side")) return rc;
+  if (!hyper || !idx || !fields || !E_out || !stats_out) return fail(FMX_ERR_ARG, "fmx_afm_side: null argument");
+  if (R < 1) return fail(FMX_ERR_ARG, "fmx_afm_side: R must be >= 1");
+  if (with_bias != 0 && with_bias != 1) return fail(FMX_ERR_ARG, "fmx_afm_side: with_bias=%d must be 0 or 1", with_bias);
+  const int F = table->n_fields;
+  if (n_sel < 1 || n_sel > F) return fail(FMX_ERR_SHAPE, "fmx_afm_side: n_sel=%d must lie in [1, %d]", n_sel, F);
+  for (int l = 0; l < n_sel; ++l)
+    if (fields[l] < 0 || fields[l] >= F || (l > 0 && fields[l] <= fields[l - 1]))
+      return fail(FMX_ERR_ARG, "fmx_afm_side: fields must be ascending field numbers of 0 .. %d", F - 1);
+  if (!aligned16(E_out) || !aligned16(stats_out)) return fail(FMX_ERR_ALIGN, "fmx_afm_side: E_out and stats_out must be 16-byte aligned");
+  AfmSideArgs a;
+  memset(&a, 0, sizeof(a));
+  const AfmArgs f = fill_afm(table, afm, hyper, idx, xv, nullptr, R, FMX_LOSS_NONE, 1.f, error);
+  a.rows = f.rows;
+  a.foff = f.foff;
+  a.bias = f.bias;
+  a.idx = idx;
+  a.xv = xv;
+  a.params = afm->params;
+  a.E = E_out;
+  a.stats = stats_out;
+  a.error = error;
+  a.h = f.h;
+  a.R = R;
+  a.F = F;
+  a.n = n_sel;
+  a.k = afm->k;
+  a.t = afm->t;
+  a.stride = table->row_stride;
+  a.with_bias = with_bias;
+  for (int l = 0; l < n_sel; ++l) a.fields[l] = (int8_t)fields[l];
+  const hipStream_t st = static_cast<hipStream_t>(stream);
+  const bool ftrl = table->layout == FMX_LAYOUT_FTRL;
+  auto go = [&](auto KP) { return ftrl ? launch_afm_side_k<KP, true>(a, st) : launch_afm_side_k<KP, false>(a, st); };
+  switch (table->kp) {
+    case 4: return go(std::integral_constant<int, 4>{});
+    case 8: return go(std::integral_constant<int, 8>{});
+    case 16: return go(std::integral_constant<int, 16>{});
+    case 32: return go(std::integral_constant<int, 32>{});
+    default: return go(std::integral_constant<int, 64>{});
+  }
 }
 
 }  // extern "C"

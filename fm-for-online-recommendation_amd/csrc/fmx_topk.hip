@@ -501,7 +501,140 @@ __global__ __launch_bounds__(256) void k_mlp_topk_scan(MlpTopkArgs a) {
     emit(s, 0, a.cap, a.K, nullptr, a.top_pos + (size_t)u * a.K, a.top_score + (size_t)u * a.K);
 }
 // ---------------------------------------------------------------------------------------------------------------------
-// host side of both entry points
+// fmx_afm_topk: the same selection over the exact AFM logit of the combined sample
+// ---------------------------------------------------------------------------------------------------------------------
+// The context side (stats_u) and the item side (stats_c) carry their own pairs' softmax statistics (fmx_afm_side); what is
+// left per (u, c) is the n_ctx x n_item cross pairs.  Workgroup = one user x one candidate split; thread = one candidate of
+// a chunk of 256.  The user's embeddings and the attention parameters (a copy padded to kp in the workspace) are the same for
+// every lane: the compiler reads them with scalar loads and they enter the FMAs as scalar operands, so the VALU does nothing
+// but the pair arithmetic (n_ctx n_item (kp (t + 2) + 2 t) FMA-class operations per pair and one exp per cross pair).
+
+constexpr int AT_SPLIT_WORK = 1 << 22;   // FLOPs a split holds at least
+constexpr int AT_TILE_BUDGET = 2048;     // workgroups the scan aims for: 256 CUs, eight resident each
+constexpr int AT_MAX_SPLITS = 1024;
+
+struct AfmTopkArgs {
+  const float *Eu, *su, *Ec, *sc;
+  const float *packed;  // [ W (t x kp) | b (t) | h (t) | p (kp) ], zero-padded columns
+  const int32_t *excl_off, *excl_pos;
+  uint64_t *parts;
+  int32_t *top_pos;
+  float *top_score;
+  int U, N, K, t, n_ctx, n_item, cap, splits, per;
+};
+
+inline int64_t at_pair_flops(int n_ctx, int n_item, int t, int kp) {
+  return (int64_t)n_ctx * n_item * (2LL * t * kp + 4LL * t + 2LL * kp);
+}
+inline int64_t at_split_min(int n_ctx, int n_item, int t, int kp) {
+  const int64_t m = (AT_SPLIT_WORK / at_pair_flops(n_ctx, n_item, t, kp) + TK_THREADS - 1) / TK_THREADS * TK_THREADS;
+  return std::min<int64_t>(8192, std::max<int64_t>(TK_THREADS, m));
+}
+inline int64_t at_max_splits(int64_t split_min, int N) { return std::min<int64_t>(AT_MAX_SPLITS, (N + split_min - 1) / split_min); }
+inline int at_kp(int k) { return k <= 4 ? 4 : k <= 8 ? 8 : k <= 16 ? 16 : k <= 32 ? 32 : 64; }
+inline int64_t at_packed_bytes(int t) { return (int64_t)align_up((size_t)(t * 64 + 2 * t + 64) * 4, 256); }
+// the padded parameter copy (sized for kp = 64), then the partial lists uint64 [U, splits, K] (U * splits < U + budget).  The
+// split minimum is taken at the smallest kp that holds k, by the workspace size and by the call alike.
+inline int64_t afm_topk_ws_bytes(const fmx_afm_t *afm, int n_ctx, int n_item, int U, int N, int K) {
+  const int64_t sm = at_split_min(n_ctx, n_item, afm->t, at_kp(afm->k));
+  const int64_t parts = std::min<int64_t>((int64_t)U * at_max_splits(sm, N), (int64_t)U + AT_TILE_BUDGET);
+  return at_packed_bytes(afm->t) + parts * K * 8;
+}
+
+// one thread per float of the padded copy
+__global__ __launch_bounds__(256) void k_afm_topk_pack(const float *params, int k, int t, int kp, float *packed) {
+  const int o = blockIdx.x * 256 + threadIdx.x;
+  const int nW = t * kp;
+  if (o >= nW + 2 * t + kp) return;
+  float v;
+  if (o < nW) {
+    const int u = o / kp, d = o - u * kp;
+    v = d < k ? params[u * k + d] : 0.f;
+  } else if (o < nW + 2 * t) {
+    v = params[t * k + (o - nW)];
+  } else {
+    const int d = o - nW - 2 * t;
+    v = d < k ? params[t * k + 2 * t + d] : 0.f;
+  }
+  packed[o] = v;
+}
+
+// grid (U, splits).  The score (include/fmx.h, fmx_afm_topk): the cross pairs j-major (item field j ascending, then context
+// field i ascending), each as k_afm's pair_terms, folded into a running (max, Z, R) by online rescaling, then the two sides.
+template <int KP>
+__global__ __launch_bounds__(TK_THREADS) void k_afm_topk_scan(AfmTopkArgs a) {
+  extern __shared__ uint64_t tk_lds[];
+  Slots s;
+  init_slots(s, tk_lds, 1, a.cap);
+  const int u = blockIdx.x, t = a.t;
+  const float *__restrict__ W = a.packed;
+  const float *__restrict__ bW = W + t * KP;
+  const float *__restrict__ h = bW + t;
+  const float *__restrict__ p = h + t;
+  const float *__restrict__ Eu = a.Eu + (size_t)u * a.n_ctx * KP;
+  const float4 stu = reinterpret_cast<const float4 *>(a.su)[u];  // (lin_u, m_u, Z_u, R_u)
+  const int c_begin = blockIdx.y * a.per, c_end = min(a.N, c_begin + a.per);
+  for (int c0 = c_begin; c0 < c_end; c0 += TK_THREADS) {
+    const int c = c0 + (int)threadIdx.x;
+    const bool valid = c < c_end;
+    const size_t cr = (size_t)(valid ? c : c_begin);
+    float mx = -INFINITY, Zx = 0.f, Rx = 0.f;
+    for (int j = 0; j < a.n_item; ++j) {
+      const float4 *row = reinterpret_cast<const float4 *>(a.Ec + (cr * a.n_item + j) * KP);
+      float ec[KP];
+#pragma unroll
+      for (int q4 = 0; q4 < KP / 4; ++q4) {
+        const float4 v = row[q4];
+        ec[4 * q4] = v.x;
+        ec[4 * q4 + 1] = v.y;
+        ec[4 * q4 + 2] = v.z;
+        ec[4 * q4 + 3] = v.w;
+      }
+      for (int i = 0; i < a.n_ctx; ++i) {
+        const float *eu = Eu + i * KP;
+        float q[KP];
+#pragma unroll
+        for (int d = 0; d < KP; ++d) q[d] = eu[d] * ec[d];
+        float r = 0.f;
+#pragma unroll
+        for (int d = 0; d < KP; ++d) r = fmaf(p[d], q[d], r);
+        float sx = 0.f;
+        for (int v = 0; v < t; ++v) {
+          float z = bW[v];
+#pragma unroll
+          for (int d = 0; d < KP; ++d) z = fmaf(W[v * KP + d], q[d], z);
+          sx = fmaf(h[v], fmaxf(z, 0.f), sx);
+        }
+        // online rescaling: a new maximum scales the running sums by e^(old - new) and enters with weight 1
+        const bool up = sx > mx;
+        const float e = expf(up ? mx - sx : sx - mx);
+        Zx = up ? fmaf(Zx, e, 1.f) : Zx + e;
+        Rx = up ? fmaf(Rx, e, r) : fmaf(e, r, Rx);
+        mx = up ? sx : mx;
+      }
+    }
+    const float4 stc = reinterpret_cast<const float4 *>(a.sc)[cr];
+    const float M = fmaxf(fmaxf(stu.y, stc.y), mx);
+    const float eu_ = expf(stu.y - M), ec_ = expf(stc.y - M), ex = expf(mx - M);
+    const float Z = fmaf(Zx, ex, fmaf(stc.z, ec_, stu.z * eu_));
+    const float R = fmaf(Rx, ex, fmaf(stc.w, ec_, stu.w * eu_));
+    const float score = (stu.x + stc.x) + R / Z;
+    const uint64_t key = make_key(score, c);
+    bool keep = valid && score == score && key > s.thr[0];
+    if (keep && a.excl_off) keep = !excluded(a.excl_off, a.excl_pos, u, c);
+    append(s, 0, a.cap, keep, key);
+    __syncthreads();
+    compact(s, 1, a.cap, a.K, c0 == c_begin ? a.K : a.cap - TK_THREADS);
+  }
+  compact(s, 1, a.cap, a.K, -1);
+  if (a.splits > 1)
+    emit(s, 0, a.cap, a.K, a.parts + ((size_t)u * a.splits + blockIdx.y) * a.K, nullptr, nullptr);
+  else
+    emit(s, 0, a.cap, a.K, nullptr, a.top_pos + (size_t)u * a.K, a.top_score + (size_t)u * a.K);
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// host side of the entry points
 // ---------------------------------------------------------------------------------------------------------------------
 constexpr size_t slots_lds(int n, int cap) { return (size_t)n * cap * 8 + (size_t)n * 8 + (size_t)n * 4; }
 size_t mlp_topk_lds(const MlpShape &s, int cap) { return (size_t)TM_ROWS * std::max(s.K0, s.Hp) * 4 + slots_lds(1, cap); }
@@ -652,6 +785,74 @@ int fmx_mlp_topk(const fmx_mlp_t *mlp, int32_t fm_term, const float *Su, const f
     default: rc = launch_slots<k_mlp_topk_scan<4, 4>>("k_mlp_topk_scan", grid, lds, st, a); break;
   }
   return rc ? rc : merge_topk(a.parts, top_pos, top_score, U, K, g.splits, st);
+}
+
+}  // extern "C"
+
+namespace {
+
+int check_afm_topk_shape(const fmx_afm_t *afm, int32_t n_ctx, int32_t n_item, int32_t U, int32_t N, int32_t K) {
+  if (!afm) return fail(FMX_ERR_ARG, "fmx_afm_topk: null afm");
+  if (int rc = check_topk_sizes("fmx_afm_topk", U, N, K)) return rc;
+  if (afm->t < 1 || afm->t > 64 || afm->k < 1 || afm->k > 64)
+    return fail(FMX_ERR_UNSUPPORTED, "fmx_afm_topk: needs 1 <= t <= 64 and 1 <= k <= 64 (got t=%d, k=%d)", afm->t, afm->k);
+  if (n_ctx < 1 || n_item < 1) return fail(FMX_ERR_SHAPE, "fmx_afm_topk: n_ctx=%d and n_item=%d must be >= 1", n_ctx, n_item);
+  if (n_ctx + n_item > 64) return fail(FMX_ERR_UNSUPPORTED, "fmx_afm_topk: n_ctx + n_item = %d, the AFM takes at most 64 fields", n_ctx + n_item);
+  return FMX_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int64_t fmx_afm_topk_workspace_bytes(const fmx_afm_t *afm, int32_t n_ctx, int32_t n_item, int32_t U, int32_t N, int32_t K) {
+  if (int rc = check_afm_topk_shape(afm, n_ctx, n_item, U, N, K)) return rc;
+  return afm_topk_ws_bytes(afm, n_ctx, n_item, U, N, K);
+}
+
+int fmx_afm_topk(const fmx_afm_t *afm, const float *Eu, const float *stats_u, int32_t n_ctx, int32_t U, const float *Ec,
+                 const float *stats_c, int32_t n_item, int32_t N, int32_t kp, const int32_t *excl_offsets, const int32_t *excl_pos,
+                 int32_t K, void *workspace, int64_t workspace_bytes, int32_t *top_pos, float *top_score, fmx_stream_t stream) {
+  if (int rc = check_afm_topk_shape(afm, n_ctx, n_item, U, N, K)) return rc;
+  if (!afm->params || !Eu || !stats_u || !Ec || !stats_c || !workspace || !top_pos || !top_score)
+    return fail(FMX_ERR_ARG, "fmx_afm_topk: null argument");
+  if ((excl_offsets == nullptr) != (excl_pos == nullptr)) return fail(FMX_ERR_ARG, "fmx_afm_topk: excl_offsets and excl_pos go together");
+  if ((kp != 4 && kp != 8 && kp != 16 && kp != 32 && kp != 64) || kp < afm->k)
+    return fail(FMX_ERR_SHAPE, "fmx_afm_topk: kp=%d must be 4/8/16/32/64 and >= k=%d", kp, afm->k);
+  if (!aligned16(Eu) || !aligned16(stats_u) || !aligned16(Ec) || !aligned16(stats_c) || !aligned16(workspace))
+    return fail(FMX_ERR_ALIGN, "fmx_afm_topk: Eu, stats_u, Ec, stats_c and the workspace must be 16-byte aligned");
+  const int64_t need = afm_topk_ws_bytes(afm, n_ctx, n_item, U, N, K);
+  if (workspace_bytes < need)
+    return fail(FMX_ERR_SHAPE, "fmx_afm_topk: workspace of %lld bytes, fmx_afm_topk_workspace_bytes(afm, %d, %d, %d, %d, %d) = %lld",
+                (long long)workspace_bytes, n_ctx, n_item, U, N, K, (long long)need);
+  // geometry: one user per workgroup, splits = ceil(budget / U) within [1, max splits], a split a multiple of the chunk
+  const int64_t sm = at_split_min(n_ctx, n_item, afm->t, at_kp(afm->k));
+  const int64_t sp = std::max<int64_t>(1, std::min<int64_t>(at_max_splits(sm, N), (AT_TILE_BUDGET + U - 1) / U));
+  const int64_t per0 = (N + sp - 1) / sp;
+  const int per = (int)((per0 + TK_THREADS - 1) / TK_THREADS * TK_THREADS);
+  const int splits = (N + per - 1) / per;
+  AfmTopkArgs a{Eu, stats_u, Ec, stats_c,
+                static_cast<const float *>(workspace),
+                excl_offsets, excl_pos,
+                reinterpret_cast<uint64_t *>(static_cast<char *>(workspace) + at_packed_bytes(afm->t)),
+                top_pos, top_score,
+                U, N, K, afm->t, n_ctx, n_item, topk_cap(K), splits, per};
+  const hipStream_t st = static_cast<hipStream_t>(stream);
+  const int packed_n = afm->t * kp + 2 * afm->t + kp;
+  hipLaunchKernelGGL(k_afm_topk_pack, dim3((packed_n + 255) / 256), dim3(256), 0, st, afm->params, afm->k, afm->t, kp,
+                     static_cast<float *>(workspace));
+  if (int rc = check_launch("k_afm_topk_pack")) return rc;
+  const dim3 grid(U, splits);
+  const size_t lds = slots_lds(1, a.cap);
+  int rc;
+  switch (kp) {
+    case 4: rc = launch_slots<k_afm_topk_scan<4>>("k_afm_topk_scan", grid, lds, st, a); break;
+    case 8: rc = launch_slots<k_afm_topk_scan<8>>("k_afm_topk_scan", grid, lds, st, a); break;
+    case 16: rc = launch_slots<k_afm_topk_scan<16>>("k_afm_topk_scan", grid, lds, st, a); break;
+    case 32: rc = launch_slots<k_afm_topk_scan<32>>("k_afm_topk_scan", grid, lds, st, a); break;
+    default: rc = launch_slots<k_afm_topk_scan<64>>("k_afm_topk_scan", grid, lds, st, a); break;
+  }
+  return rc ? rc : merge_topk(a.parts, top_pos, top_score, U, K, splits, st);
 }
 
 }  // extern "C"

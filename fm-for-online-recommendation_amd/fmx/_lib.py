@@ -23,11 +23,12 @@ EXPORTS = ["fmx_version", "fmx_last_error_string", "fmx_set_option", "fmx_sorted
            "fmx_fm_forward_partial", "fmx_fm_forward_finish", "fmx_sftrl_run", "fmx_sftrl_grid",
            "fmx_gather_read", "fmx_comm_unique_id", "fmx_comm_create", "fmx_comm_destroy", "fmx_owner_prefetch", "fmx_owner_step",
            "fmx_fm_topk_workspace_bytes", "fmx_fm_topk", "fmx_mlp_topk_workspace_bytes", "fmx_mlp_topk",
-           "fmx_fm_update_occ", "fmx_afm_forward", "fmx_afm_workspace_bytes", "fmx_afm_step"]
+           "fmx_fm_update_occ", "fmx_afm_forward", "fmx_afm_workspace_bytes", "fmx_afm_step",
+           "fmx_afm_side", "fmx_afm_topk_workspace_bytes", "fmx_afm_topk"]
 
 
 I64_RETURNS = ("fmx_workspace_bytes", "fmx_mlp_section_workspace_bytes", "fmx_fm_topk_workspace_bytes",
-               "fmx_mlp_topk_workspace_bytes", "fmx_afm_workspace_bytes")   # byte counts: int64_t in include/fmx.h
+               "fmx_mlp_topk_workspace_bytes", "fmx_afm_workspace_bytes", "fmx_afm_topk_workspace_bytes")   # byte counts: int64_t in include/fmx.h
 
 
 class FmxError(RuntimeError):
@@ -128,6 +129,9 @@ def load():
     lib.fmx_afm_forward.argtypes = [TP, AP, HP, p, p, p, i32, i32, f32, p, p, p, p]
     lib.fmx_afm_workspace_bytes.argtypes = [TP, AP, i32]
     lib.fmx_afm_step.argtypes = [TP, HP, i32, AP, p, p, p, i32, f32, p, i64, p, p, p, p]
+    lib.fmx_afm_side.argtypes = [TP, AP, HP, p, p, i32, p, i32, i32, p, p, p, p]
+    lib.fmx_afm_topk_workspace_bytes.argtypes = [AP, i32, i32, i32, i32, i32]
+    lib.fmx_afm_topk.argtypes = [AP, p, p, i32, i32, p, p, i32, i32, i32, p, p, i32, p, i64, p, p, p]
     for name in EXPORTS:
         fn = getattr(lib, name)
         if name in I64_RETURNS:

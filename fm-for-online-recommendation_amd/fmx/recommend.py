@@ -14,6 +14,10 @@ The DeepFM / NFM classes put a relu MLP on the bi-interaction vector.  The netwo
 bi(u + c) = bi_u + bi_c + S_u * S_c, so each side is still computed once (side_terms) and fmx_mlp_topk runs the U x N
 forwards of the network on the device, then the same exact selection (topk_network).  Networks the kernel does not take
 (hidden > 256) go through mlp_topk_torch, a chunked torch statement of the same score and result order.
+
+The attentional FM (AFMAdam) does not decompose over a masked forward: a zeroed field still adds pairs to the softmax.  Each
+side instead keeps its own fields' embeddings and the softmax statistics (lin, m, Z, R) of its own pairs (afm_side,
+fmx_afm_side); fmx_afm_topk computes the cross pairs of every (u, c) and combines the three groups exactly (topk_afm).
 """
 import ctypes as C
 
@@ -332,4 +336,102 @@ def topk_network(table, mlp, fm_term, ctx_idx, ctx_xv, candidates, K, exclude=No
         top_pos, top_score = mlp_topk(*args)
     else:
         top_pos, top_score = mlp_topk_torch(*args)
+    return top_pos.long(), top_score
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# the attentional FM
+# ---------------------------------------------------------------------------------------------------------------------------
+def _afm_struct(table, afm):
+    params, t = afm
+    if not torch.is_tensor(params) or params.dtype != torch.float32 or not params.is_contiguous() or not params.is_cuda:
+        raise ValueError("afm params: a contiguous fp32 device tensor [W (t x k) | b (t) | h (t) | p (k)]")
+    t, k = int(t), table.k
+    if params.numel() != t * k + 2 * t + k:
+        raise ValueError(f"afm params: {params.numel()} floats, t={t} and k={k} need {t * k + 2 * t + k}")
+    return _lib.Afm(params.data_ptr(), k, t)
+
+
+def afm_side(table, afm, idx, xv, fields, with_bias, hyper=None):
+    """fmx_afm_side over the rows of idx / xv ([R, F] full width; xv None: ones) for the ascending fields `fields`.  afm =
+    (params, t) with params the flat fp32 device buffer.  Returns device tensors (E [R, n_sel, kp], stats [R, 4] = (lin, m,
+    Z, R)).  An index outside its field (in a selected column) raises IndexError."""
+    F, dev, kp = table.n_fields, table.device, table.kp
+    fields = sorted({int(f) for f in fields})
+    if not fields or not all(0 <= f < F for f in fields):
+        raise ValueError(f"fields {fields}: need at least one field of 0..{F - 1}")
+    a = _afm_struct(table, afm)
+    idx = _as_index(idx, F, dev)
+    R = idx.shape[0]
+    xv = None if xv is None else _as_values(xv, (R, F), dev)
+    E = torch.empty((max(R, 1), len(fields), kp), dtype=torch.float32, device=dev)
+    stats = torch.empty((max(R, 1), 4), dtype=torch.float32, device=dev)
+    if R == 0:
+        return E[:0], stats[:0]
+    error = torch.zeros(1, dtype=torch.int32, device=dev)
+    sel = (C.c_int32 * len(fields))(*fields)
+    lib, h = _lib.load(), _hyper_for(table, hyper)
+    _lib.check(lib.fmx_afm_side(table.c_struct(), C.byref(a), h.ref(), idx.data_ptr(), _ptr(xv), R, sel, len(fields),
+                                int(bool(with_bias)), E.data_ptr(), stats.data_ptr(), error.data_ptr(),
+                                torch.cuda.current_stream(dev).cuda_stream))
+    if int(error.item()) != 0:
+        raise IndexError("index out of range in self (flagged by the fmx kernels)")
+    return E, stats
+
+
+class AFMCandidates(Candidates):
+    """The candidate side under the AFM: Ec [N, n_item, kp] and stats_c [N, 4] of cand_idx's item fields ([N, F] full-width
+    rows, the other columns ignored) under the attention parameters afm = (params, t).  The statistics depend on the attention
+    parameters as well as on the table: call refresh() after either has been trained."""
+
+    def __init__(self, table, afm, item_fields, cand_idx, cand_xv=None, hyper=None):
+        self.afm = (afm[0], int(afm[1]))
+        fields = sorted({int(f) for f in item_fields})
+        if len(fields) >= table.n_fields:
+            raise ValueError(f"item_fields {list(item_fields)} cover every field: the AFM needs at least one context field")
+        super().__init__(table, item_fields, cand_idx, cand_xv, hyper)
+
+    @property
+    def t(self):
+        return self.afm[1]
+
+    def refresh(self):
+        self.Ec, self.stats = afm_side(self.table, self.afm, self.idx, self.xv, self.item_fields, False, self.hyper)
+        return self
+
+
+def afm_topk(afm, k, Eu, stats_u, Ec, stats_c, K, excl_offsets=None, excl_pos=None, workspace=None, out=None, stream=None):
+    """The raw call of fmx_afm_topk.  afm = (params, t), k the embedding size; Eu [U, n_ctx, kp], stats_u [U, 4], Ec [N, n_item,
+    kp], stats_c [N, 4] contiguous fp32 device tensors (afm_side's outputs).  Returns (top_pos int32 [U, K], top_score fp32
+    [U, K]) on the device."""
+    params, t = afm
+    U, n_ctx, kp = Eu.shape
+    N, n_item = Ec.shape[0], Ec.shape[1]
+    if Ec.shape[2] != kp or not all(x.is_contiguous() for x in (Eu, stats_u, Ec, stats_c)):
+        raise ValueError("Eu / Ec: contiguous [rows, fields, kp] with the same kp; stats contiguous [rows, 4]")
+    a = _lib.Afm(params.data_ptr(), int(k), int(t))
+    lib = _lib.load()
+    ws, ws_n, out, st = _call_buffers(lib.fmx_afm_topk_workspace_bytes(C.byref(a), n_ctx, n_item, U, N, K), U, K, Eu.device,
+                                      workspace, out, stream)
+    _lib.check(lib.fmx_afm_topk(C.byref(a), Eu.data_ptr(), stats_u.data_ptr(), n_ctx, U, Ec.data_ptr(), stats_c.data_ptr(), n_item,
+                                N, kp, _ptr(excl_offsets), _ptr(excl_pos), K, ws, ws_n, out[0].data_ptr(), out[1].data_ptr(), st))
+    return out
+
+
+def topk_afm(table, afm, ctx_idx, ctx_xv, candidates, K, exclude=None, hyper=None):
+    """Top-K candidates for every context row of ctx_idx / ctx_xv ([U, F] full width, the item columns ignored) under the AFM
+    afm = (params, t): the exact logit of the combined sample.  candidates: an AFMCandidates of the same table and attention
+    parameters.  Returns device tensors (positions int64 [U, K], -1 padded; logits fp32 [U, K], -inf padded), each row by
+    logit descending, then position ascending.  exclude: see exclusions_csr."""
+    params, t = afm[0], int(afm[1])
+    if not isinstance(candidates, AFMCandidates):
+        raise ValueError("candidates: an AFMCandidates (the AFM's candidate side)")
+    if candidates.table is table and (candidates.t != t or candidates.afm[0].data_ptr() != params.data_ptr()):
+        raise ValueError(f"candidates were computed for another attention (t={candidates.t}; this one has t={t})")
+
+    def side(table, idx, xv, fields, hyper):
+        return afm_side(table, (params, t), idx, xv, fields, True, hyper)
+
+    (Eu, stats_u), off, pos = _context_side(table, candidates, ctx_idx, ctx_xv, exclude, hyper, side)
+    top_pos, top_score = afm_topk((params, t), table.k, Eu, stats_u, candidates.Ec, candidates.stats, int(K), off, pos)
     return top_pos.long(), top_score

@@ -140,6 +140,31 @@ class AFMAdam(nn.Module):
     def predict(self, Xi, Xv):
         return self.predict_proba(Xi, Xv) > 0.5
 
+    def recommend(self, Xi, Xv, item_fields, K, candidates=None, exclude=None, full=False):
+        """Top-K candidates for every context row (fmx/recommend.py, fmx_afm_topk): the exact logit forward() gives the combined
+        sample.  Xi / Xv: [U, F] full-width rows whose item columns are ignored (Xv may be None: all ones).  candidates=None:
+        every row of the one item field, a position is that field's local index; else (cand_Xi [N, F], cand_Xv or None) whose
+        non-item columns are ignored.  exclude: per-user position lists or a CSR pair (offsets, positions).  Returns numpy
+        (positions int64 [U, K], -1 padded; logits fp32 [U, K], -inf padded), each row by logit descending, then position
+        ascending.  full is accepted for the other classes' signature: the score is always the whole model's."""
+        item_fields = [int(f) for f in (item_fields if hasattr(item_fields, "__len__") else [item_fields])]
+        F = self.field_size
+        if candidates is None:
+            if len(item_fields) != 1:
+                raise ValueError("candidates=None needs exactly one item field (its rows are the candidates)")
+            f = item_fields[0]
+            if not 0 <= f < F:
+                raise ValueError(f"item field {f}: not a field of 0..{F - 1}")
+            cand_idx = torch.zeros((self.feature_sizes[f], F), dtype=torch.int32, device=self.device)
+            cand_idx[:, f] = torch.arange(self.feature_sizes[f], dtype=torch.int32, device=self.device)
+            cand_xv = None
+        else:
+            cand_idx, cand_xv = candidates
+        rec, afm = fmx.recommend, (self._attn_flat, self.attention_size)
+        cands = rec.AFMCandidates(self._table, afm, item_fields, cand_idx, cand_xv, hyper=self._hyper)
+        pos, logit = rec.topk_afm(self._table, afm, Xi, Xv, cands, K, exclude=exclude, hyper=self._hyper)
+        return pos.cpu().numpy(), logit.cpu().numpy()
+
     # ------------------------------------------------------------------------------------------------------
     # training
     # ------------------------------------------------------------------------------------------------------

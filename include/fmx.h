@@ -562,6 +562,56 @@ int fmx_afm_step(const fmx_table_t *table, const fmx_hyper_t *hyper, int32_t rul
                  const float *xv, const float *y, int32_t B, float inv_b, void *workspace, int64_t workspace_bytes,
                  float *attn_grad_out, float *loss_out, int32_t *error, fmx_stream_t stream);
 
+/* ---- top-K recommendation under the AFM (fmx/recommend.py, AFMAdam.recommend) ----
+ * Split the fields into context fields C and item fields I (at least one of each).  A combined sample's pairs are the C x C
+ * pairs (u alone), the I x I pairs (c alone) and the |C| |I| cross pairs.  Each side's own pairs reduce to (lin, m, Z, R):
+ * lin = the first-order sum (plus the bias on the context side), m = max s, Z = sum e^(s - m), R = sum e^(s - m) (p . q).
+ * A side of one field has no pairs: m = -inf, Z = R = 0, and it adds exact zeros.  The other side's fields are NOT zeroed:
+ * a zero field would still add pairs to the softmax.
+ *
+ * fmx_afm_side: (lin, m, Z, R) and the gathered embeddings of the n_sel selected fields of R full-width rows.
+ *   idx / xv [R, F] (xv may be null: ones); fields: a HOST array of n_sel ascending field numbers; with_bias: 1 adds the
+ *   table's bias to lin (the context side), 0 does not (the item side).
+ *   E_out [R, n_sel, kp] = x V[row] of the selected fields (kp floats, as k_afm gathers them); stats_out [R, 4] = (lin, m, Z, R)
+ *   over the selected fields' own pairs in the AFM's pair order, with fmx_afm_forward's arithmetic: lin = bias + w-sum (or the
+ *   w-sum alone), m = the max, Z and R its max-subtracted sums.  Both 16-byte aligned.  error as in fmx_afm_forward.  A row's
+ *   results do not depend on R or on the other rows; every table layout gives the weights fmx_afm_forward uses.
+ * Replaces: nothing in the reference (it has no recommendation call); the AFM counterpart of fmx_fm_forward's masked sides. */
+int fmx_afm_side(const fmx_table_t *table, const fmx_afm_t *afm, const fmx_hyper_t *hyper, const int32_t *idx, const float *xv,
+                 int32_t R, const int32_t *fields, int32_t n_sel, int32_t with_bias, float *E_out, float *stats_out, int32_t *error,
+                 fmx_stream_t stream);
+
+/* fmx_afm_topk: exact top-K of the AFM logit over U contexts x N candidates.
+ * Replaces: forward() over assembled (context, candidate) samples followed by torch.topk (reference afm_adam.py:43-74 for
+ * the model).
+ *   Eu [U, n_ctx, kp], stats_u [U, 4]: the contexts' fmx_afm_side with with_bias = 1;  Ec [N, n_item, kp], stats_c [N, 4]: the
+ *   candidates' with with_bias = 0 (all four 16-byte aligned, rows dense).  afm: the parameters of fmx_afm_forward.
+ *   kp, exclusions, K, top_pos / top_score: exactly as fmx_fm_topk (rows sorted by score descending then position ascending,
+ *   -1 / -inf padding, a NaN score or an excluded position never returned, -0 returned as +0).
+ * The score is one fixed function of (u, c), whatever U, N, the split or the candidate order (fp32, one rounding per operation):
+ *     cross pairs in the order j = item field ascending, then i = context field ascending:
+ *       q[d] = Eu[u][i][d] * Ec[c][j][d]                                    d < kp
+ *       r    = fma(p[kp-1], q[kp-1], ... fma(p[0], q[0], 0) ...)             (p zero-padded past k)
+ *       z_v  = fma(W[v][kp-1], q[kp-1], ... fma(W[v][0], q[0], b[v]) ...)    (W rows zero-padded past k)
+ *       s    = fma(h[t-1], max(z_{t-1}, 0), ... fma(h[0], max(z_0, 0), 0) ...)
+ *     folded into (mx, Zx, Rx), starting from (-inf, 0, 0), by online rescaling:
+ *       s > mx:  e = exp(mx - s), Zx = fma(Zx, e, 1), Rx = fma(Rx, e, r), mx = s
+ *       else:    e = exp(s - mx), Zx = Zx + e,        Rx = fma(e, r, Rx)
+ *     M  = fmaxf(fmaxf(m_u, m_c), mx);  e_u = exp(m_u - M), e_c = exp(m_c - M), e_x = exp(mx - M)
+ *     Z  = fma(Zx, e_x, fma(Z_c, e_c, Z_u * e_u)),  R = fma(Rx, e_x, fma(R_c, e_c, R_u * e_u))
+ *     score = (lin_u + lin_c) + R / Z
+ * It agrees with fmx_afm_forward on the assembled sample up to the order of the softmax's sums.
+ * Limits: kp 4 / 8 / 16 / 32 / 64 and >= k, else FMX_ERR_SHAPE; n_ctx, n_item >= 1, else FMX_ERR_SHAPE; 1 <= t <= 64,
+ * n_ctx + n_item <= 64, K <= 256, else FMX_ERR_UNSUPPORTED; U, N, K >= 1, else FMX_ERR_ARG.  The workspace (16-byte aligned, no
+ * initialisation needed) holds the attention parameters padded to kp and the partial lists of a split scan:
+ * fmx_afm_topk_workspace_bytes(afm, n_ctx, n_item, U, N, K) bytes (monotone in U, N and K, computed on the host; negative on
+ * bad arguments), else FMX_ERR_SHAPE.  Three launches (the padded copy, the scan, the merge of the splits when there are
+ * several); every argument is checked before anything is launched. */
+int64_t fmx_afm_topk_workspace_bytes(const fmx_afm_t *afm, int32_t n_ctx, int32_t n_item, int32_t U, int32_t N, int32_t K);
+int fmx_afm_topk(const fmx_afm_t *afm, const float *Eu, const float *stats_u, int32_t n_ctx, int32_t U, const float *Ec,
+                 const float *stats_c, int32_t n_item, int32_t N, int32_t kp, const int32_t *excl_offsets, const int32_t *excl_pos,
+                 int32_t K, void *workspace, int64_t workspace_bytes, int32_t *top_pos, float *top_score, fmx_stream_t stream);
+
 /* Streaming read of `bytes` (multiple of 16) with 16-byte loads; sink [1] receives a checksum so the loads stay
  * live.  Used by bench.py to measure the HBM-read ceiling on the same GPU in the same run. */
 int fmx_stream_read(const void *buf, int64_t bytes, float *sink, fmx_stream_t stream);
