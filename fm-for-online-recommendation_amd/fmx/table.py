@@ -93,7 +93,10 @@ class FlatTable:
             self.n_cols = self.n_fields
         self.offsets_host = offs
         self.n_rows = int(offs[-1])
-        self.rows = torch.zeros((self.n_rows, self.row_stride), dtype=torch.float32, device=self.device)
+        # a mapped table may END in an empty field: the forward's branch-free gather then reads (and drops) the row at n_rows
+        # (include/fmx.h, field_cols), so such tables keep one spare zero row behind the last; n_rows does not count it
+        self._store = torch.zeros((self.n_rows + (1 if self.mapped else 0), self.row_stride), dtype=torch.float32, device=self.device)
+        self.rows = self._store[:self.n_rows]
         self.offsets = torch.from_numpy(offs).to(self.device)
         if self.mapped:
             self.field_cols = torch.tensor(self.field_cols_host, dtype=torch.int32, device=self.device)

@@ -134,7 +134,10 @@ typedef struct fmx_table {
    * group f % SLOTS, pass f / SLOTS, SLOTS = 64 / (kp / 4)), so which piece sits at which field number decides the order
    * of the floating-point additions: tables that place the same pieces at the same positions give identical bits however
    * the positions are dealt over owners.  With pieces the kernels cannot tell a bad index from one of another piece:
-   * device-side range errors (error word 1) are reported for unmapped tables only. */
+   * device-side range errors (error word 1) are reported for unmapped tables only.
+   * A table that ENDS in an empty field needs ONE READABLE ROW after n_rows (row_stride floats; their values do not matter): the
+   * forward passes gather without a branch, and for a sample that has no row in a field they read the field's first row and
+   * drop it -- for a trailing empty field that is row n_rows.  fmx.FlatTable allocates the spare row. */
   const int32_t *field_cols; /* [n_fields] or null */
   const int32_t *field_base; /* [n_fields] or null */
   int32_t n_cols;            /* columns of idx / xv; 0: n_fields */
@@ -386,7 +389,9 @@ int fmx_mlp_hedge_fit(const fmx_mlp_t *mlp, float lr, float hedge_b, float hedge
 /* The reference's online protocol for the classes with an MLP on a device-resident stream of N samples: per sample the
  * forward (pred_out[i] = what forward() returns: the logit for the Adam classes, sigmoid of the last layer's logit for
  * the ONN classes), then fit on that sample -- hedge = 0: fmx_mlp_fit + the table update (DeepFMAdam / NFMAdam.fit),
- * hedge = 1: fmx_mlp_hedge_fit (the ONN classes: hidden layers and alpha only).  fm_term: the FM logit is part of the
+ * hedge = 1: fmx_mlp_hedge_fit (the ONN classes: hidden layers and alpha only; a table of any layout is read).  The fit mode
+ * takes FMX_RULE_SIGNADAM / FMX_RULE_SGD, i.e. tables in the weights layout: any other pairing is FMX_ERR_ARG
+ * (FMX_ERR_UNSUPPORTED for the adaptive rules).  fm_term: the FM logit is part of the
  * network's input logit (DeepFM) or only the first-order sum and the bias (NFM).  One workgroup walks the stream with the
  * network's parameters in LDS (k_online_mlp) when they are at most 8,192 floats, the fields fit one wavefront and the tables
  * are not FTRL tables under a fit step; otherwise the launches of all samples are queued without any host synchronisation
