@@ -66,6 +66,12 @@ struct MlpReduceArgs {
   float *grads;
   float *params;  // with lr != 0: params -= lr * grad in the same pass (single-rank SGD)
   float lr;
+  // the network's rule (fmx_mlp_opt_t; mlp_reduce_set_opt): FMX_RULE_SGD as above, or FMX_RULE_ADAGRAD / FMX_RULE_ADAM on the flat
+  // moments m, v (the layout of params), applied in the same pass whatever lr is.  Under them lr, eps, c1, c2 are what
+  // moments_upd reads as h.lr, h.eps, h.beta1, h.beta2: the step's step size, eps (ADAM: eps sqrt(1 - beta2^t)), 1 - beta1, 1 - beta2
+  int rule;
+  float *m, *v;
+  float eps, c1, c2;
   int n_split[MLP_BIG_MAX_L], n_layers;
   const float *loss_b;
   float *loss_out;
@@ -77,8 +83,12 @@ struct MlpReduceArgs {
 // (mlp_launch_reduce).  Defined in fmx_mlp.hip.
 int mlp_section_deferred_reduce(const fmx_mlp_t *mlp, int32_t loss_kind, const float *bi, int32_t ld_bi, const float *base, const float *y, int32_t B,
                                 float inv_b, void *workspace, float *logit_out, float *dz_out, float *gbi_out, int32_t ld_gbi, float *grads,
-                                float lr_apply, float *loss_out, hipStream_t st, MlpReduceArgs *deferred);
+                                float lr_apply, float *loss_out, hipStream_t st, MlpReduceArgs *deferred, const char *who = "fmx_mlp_section");
 void mlp_launch_reduce(const MlpReduceArgs &a, hipStream_t st);
+// the host-side checks of fmx_mlp_section_opt / fmx_deepfm_stream_opt on the network, its buffers and its optimizer state for a
+// call of n_steps steps; `who` names the entry point in the message.  Defined in fmx_mlp.hip.
+int mlp_opt_check(const fmx_mlp_t *mlp, int32_t B, const void *workspace, int64_t workspace_bytes, const float *grads, const fmx_mlp_opt_t *opt,
+                  int64_t n_steps, const char *who);
 int mlp_reduce_blocks_per_layer(const MlpReduceArgs &a, int threads);
 }  // namespace fmxd
 using namespace fmxd;
@@ -157,12 +167,17 @@ __host__ __device__ inline double pow_step(double b, int32_t t) {
   }
   return r;
 }
-// the device-side constants of ADAM's step t (1-based) from the caller's hyper-parameters
-__host__ __device__ inline void adam_consts(float lr, float beta1, float beta2, int32_t t, float &step_size, float &c1, float &c2) {
+// the device-side constants of ADAM's step t (1-based) from the caller's hyper-parameters; eps_dense, when asked for, receives
+// eps sqrt(1 - beta2^t): what stands in eps' place when torch.optim.Adam's denominator sqrt(v) / sqrt(1 - beta2^t) + eps is
+// multiplied through by sqrt(1 - beta2^t) (the network's rule, fmx_mlp_opt_t)
+__host__ __device__ inline void adam_consts(float lr, float beta1, float beta2, int32_t t, float &step_size, float &c1, float &c2,
+                                            float eps = 0.f, float *eps_dense = nullptr) {
   const double b1 = beta1, b2 = beta2;
-  step_size = (float)((double)lr * sqrt(1.0 - pow_step(b2, t)) / (1.0 - pow_step(b1, t)));
+  const double s2 = sqrt(1.0 - pow_step(b2, t));
+  step_size = (float)((double)lr * s2 / (1.0 - pow_step(b1, t)));
   c1 = (float)(1.0 - b1);
   c2 = (float)(1.0 - b2);
+  if (eps_dense) *eps_dense = (float)((double)eps * s2);
 }
 // one coordinate: p, m, v by gradient g (h as above)
 template <int RULE>
@@ -350,23 +365,47 @@ __device__ float block_sum(const float *src, int n, int ld, float *sm) {
 
 inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
+// the network's rule for its step t (1-based) into the reduction's arguments: ADAM's constants in double, once per step
+inline void mlp_reduce_set_opt(MlpReduceArgs &a, const fmx_mlp_opt_t &o, int32_t t) {
+  a.rule = o.rule;
+  a.m = o.m;
+  a.v = o.v;
+  a.lr = o.lr;
+  a.eps = o.eps;
+  a.c1 = a.c2 = 0.f;
+  if (o.rule == FMX_RULE_ADAM) adam_consts(o.lr, o.beta1, o.beta2, t, a.lr, a.c1, a.c2, o.eps, &a.eps);
+}
+
 // Block `block` of `n_blocks` of layer l: one thread per 4 consecutive columns of one row of the layer's partial [out, ldp] (ldp a
 // multiple of 4: the weight columns, the bias column `in`, padding): 16-byte loads of up to 16 splits in flight, summed in the
 // order z = 0, 1, ...; block 0 of layer 0 also reduces the loss.  Any workgroup width (the table update's is 64 or 128 or 256).
+// The thread that sums a group also applies the network's rule to it (MlpReduceArgs.rule) and stores params (and m, v).
 __device__ __forceinline__ void mlp_reduce_block(const MlpReduceArgs &a, int l, int block, int n_blocks) {
   const int out = a.out_dim[l], in = a.in_dim[l], ldp = a.ldp[l], ns = a.n_split[l];
   const int groups = ldp >> 2;
   const long long n = (long long)out * groups;
   const float *p = a.parts[l];
   const size_t zs = (size_t)out * ldp;
+  // the network's rule: a wave-uniform run-time branch (a template parameter would multiply the rider's instantiations)
+  const bool adaptive = a.rule != FMX_RULE_SGD, apply = adaptive || a.lr != 0.f;
+  fmx_hyper_t h;
+  h.lr = a.lr;
+  h.eps = a.eps;
+  h.beta1 = a.c1;
+  h.beta2 = a.c2;
   for (long long i = (long long)block * blockDim.x + threadIdx.x; i < n; i += (long long)n_blocks * blockDim.x) {
     const int m = (int)(i / groups), c = (int)(i - (long long)m * groups) * 4;
     const float *q = p + (size_t)m * ldp + c;
     // the parameters this thread updates, requested with the partials instead of behind their sum (a dependent round trip less);
     // a group of four weight columns is 16 contiguous, 16-byte aligned bytes of W_l when in % 4 == 0 (else the scalar path below)
-    const bool vec4 = a.lr != 0.f && c + 3 < in && (in & 3) == 0 && (a.grad_off[l] & 3) == 0;
-    float4 pv = {0.f, 0.f, 0.f, 0.f};
-    if (vec4) pv = *reinterpret_cast<const float4 *>(a.params + a.grad_off[l] + (long long)m * in + c);
+    const bool vec4 = apply && c + 3 < in && (in & 3) == 0 && (a.grad_off[l] & 3) == 0;
+    float4 pv = {0.f, 0.f, 0.f, 0.f}, mv = pv, vv = pv;
+    if (vec4) {
+      const long long o = a.grad_off[l] + (long long)m * in + c;
+      pv = *reinterpret_cast<const float4 *>(a.params + o);
+      if (adaptive) vv = *reinterpret_cast<const float4 *>(a.v + o);
+      if (a.rule == FMX_RULE_ADAM) mv = *reinterpret_cast<const float4 *>(a.m + o);
+    }
     float4 s = {0.f, 0.f, 0.f, 0.f};
     for (int z0 = 0; z0 < ns; z0 += 16) {
       float4 r[16];
@@ -385,7 +424,17 @@ __device__ __forceinline__ void mlp_reduce_block(const MlpReduceArgs &a, int l, 
     if (vec4) {
       const long long o = a.grad_off[l] + (long long)m * in + c;
       *reinterpret_cast<float4 *>(a.grads + o) = s;
-      *reinterpret_cast<float4 *>(a.params + o) = float4{pv.x - a.lr * s.x, pv.y - a.lr * s.y, pv.z - a.lr * s.z, pv.w - a.lr * s.w};
+      if (a.rule == FMX_RULE_ADAM) {
+        moments_upd4<FMX_RULE_ADAM>(pv, mv, vv, s, h);
+        *reinterpret_cast<float4 *>(a.m + o) = mv;
+        *reinterpret_cast<float4 *>(a.v + o) = vv;
+      } else if (adaptive) {
+        moments_upd4<FMX_RULE_ADAGRAD>(pv, mv, vv, s, h);
+        *reinterpret_cast<float4 *>(a.v + o) = vv;
+      } else {
+        pv = float4{pv.x - a.lr * s.x, pv.y - a.lr * s.y, pv.z - a.lr * s.z, pv.w - a.lr * s.w};
+      }
+      *reinterpret_cast<float4 *>(a.params + o) = pv;
       continue;
     }
     const float v[4] = {s.x, s.y, s.z, s.w};
@@ -394,7 +443,15 @@ __device__ __forceinline__ void mlp_reduce_block(const MlpReduceArgs &a, int l, 
       if (c + j > in) break;  // padding
       const long long o = c + j < in ? a.grad_off[l] + (long long)m * in + c + j : a.grad_off[l] + (long long)out * in + m;
       a.grads[o] = v[j];
-      if (a.lr != 0.f) a.params[o] -= a.lr * v[j];
+      if (!apply) continue;
+      if (!adaptive) {
+        a.params[o] -= a.lr * v[j];
+      } else if (a.rule == FMX_RULE_ADAM) {
+        moments_upd<FMX_RULE_ADAM>(a.params[o], a.m[o], a.v[o], v[j], h);
+      } else {
+        float unused = 0.f;
+        moments_upd<FMX_RULE_ADAGRAD>(a.params[o], unused, a.v[o], v[j], h);
+      }
     }
   }
   if (block == 0 && l == 0 && a.loss_out) {

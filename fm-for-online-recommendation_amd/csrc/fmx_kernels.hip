@@ -1682,7 +1682,7 @@ bool with_one_of(int v, Fn &&f) {
 
 // f(LAYOUT, RULE) as integral constants for an update rule and the layout it pairs with (check_rule); false, and no call,
 // for a rule it does not know.  with_rule_wf: the rules of the weights and FTRL layouts only (the launches the adaptive
-// rules do not take -- the update's rider, k_online_mlp -- are not instantiated for them).
+// rules do not take -- k_online_mlp -- are not instantiated for them).
 template <bool MOMENTS_RULES, class Fn>
 bool with_rule_impl(int rule, Fn &&f) {
   using Weights = std::integral_constant<int, FMX_LAYOUT_WEIGHTS>;
@@ -1936,7 +1936,7 @@ void launch_update_rider(const UpdArgs &a, int rule, const MlpReduceArgs &r, hip
   const int wpb = tune().wpb_upd;
   const int n_upd = (tiles + wpb - 1) / wpb + red_slices(a.B), per = mlp_reduce_blocks_per_layer(r, 64 * wpb);
   const dim3 grid(n_upd + per * r.n_layers), block(64 * wpb);
-  with_rule_wf(rule, [&](auto LAYOUT, auto RULE) {  // (fmx_deepfm_stream refuses the adaptive rules)
+  with_rule(rule, [&](auto LAYOUT, auto RULE) {  // (the MOMENTS rules: fmx_deepfm_stream_opt)
     hipLaunchKernelGGL((k_fm_update_rider<LPR, LAYOUT, RULE, true>), grid, block, 0, st, a, r, n_upd, per);
   });
 }
@@ -2556,23 +2556,31 @@ __global__ void k_first_plus_bias(float *out, const float *sfirst, const float *
 // section on bi (fmx_mlp_section: k_mlp_chain, k_mlp_wgrad_stream, k_mlp_reduce with the SGD of the MLP applied in it) and the
 // table update with dL/dbi, all issued from here; the occurrence sorts run in groups on the side stream (pool_loop).
 // Through the Python trainer the same step is bound by its host side (84 us of calls per step for 67 us of kernels).
-int fmx_deepfm_stream(const fmx_table_t *table, const fmx_hyper_t *hyper, int32_t rule, const fmx_mlp_t *mlp, int32_t loss_kind, int32_t fm_term,
-                      const int32_t *idx_pool, const float *y_pool, int32_t n_pool, int32_t B, float inv_b, int32_t n_steps,
-                      void *workspace, int64_t workspace_bytes, void *mlp_workspace, const fmx_fwd_out_t *fwd, float *dz, float *gbi,
-                      float *grads, float lr_mlp, float *loss_out, fmx_stream_t stream) {
-  if (adaptive_rule(rule)) return refuse_adaptive(rule, "fmx_deepfm_stream");
+// fmx_deepfm_stream (opt null: the network under SGD by lr_mlp, the tables under the weights / FTRL rules) and fmx_deepfm_stream_opt
+// (the network under opt's rule, the tables under any rule; every check of the network in front of the first launch)
+static int deepfm_stream_impl(const fmx_table_t *table, const fmx_hyper_t *hyper, int32_t rule, const fmx_mlp_t *mlp, int32_t loss_kind,
+                              int32_t fm_term, const int32_t *idx_pool, const float *y_pool, int32_t n_pool, int32_t B, float inv_b,
+                              int32_t n_steps, void *workspace, int64_t workspace_bytes, void *mlp_workspace, int64_t mlp_workspace_bytes,
+                              const fmx_fwd_out_t *fwd, float *dz, float *gbi, float *grads, float lr_mlp, const fmx_mlp_opt_t *opt,
+                              float *loss_out, fmx_stream_t stream, const char *who) {
+  if (!opt && adaptive_rule(rule)) return refuse_adaptive(rule, who);
   if (int rc = check_table(table)) return rc;
   if (int rc = check_rule(table, rule)) return rc;
   if (!hyper || !mlp || !workspace || !mlp_workspace || !fwd || !fwd->S || !fwd->bi || !fwd->logit || !dz || !gbi || !grads)
-    return fail(FMX_ERR_ARG, "fmx_deepfm_stream: null argument (fwd needs S, bi and logit)");
-  if (fwd->sample_ld != 0) return fail(FMX_ERR_ARG, "fmx_deepfm_stream: dense forward outputs only (sample_ld = 0)");
-  if (!fm_term && (!fwd->sfirst || table->layout != FMX_LAYOUT_WEIGHTS))
-    return fail(FMX_ERR_UNSUPPORTED, "fmx_deepfm_stream: fm_term = 0 (NFM) needs fwd->sfirst and a table in the weights layout");
-  if (!idx_pool || !y_pool || n_pool < 1 || n_steps < 0 || B < 1) return fail(FMX_ERR_ARG, "fmx_deepfm_stream: bad pool / step count");
-  if (mlp->k > table->kp) return fail(FMX_ERR_SHAPE, "fmx_deepfm_stream: the MLP reads k=%d columns of a bi of kp=%d", mlp->k, table->kp);
+    return fail(FMX_ERR_ARG, "%s: null argument (fwd needs S, bi and logit)", who);
+  if (fwd->sample_ld != 0) return fail(FMX_ERR_ARG, "%s: dense forward outputs only (sample_ld = 0)", who);
+  // NFM: k_first_plus_bias reads bias[0], the bias weight of the weights and the moments layouts
+  if (!fm_term && (!fwd->sfirst || (opt ? table->layout == FMX_LAYOUT_FTRL : table->layout != FMX_LAYOUT_WEIGHTS)))
+    return fail(FMX_ERR_UNSUPPORTED, "%s: fm_term = 0 (NFM) needs fwd->sfirst and a table in the weights%s layout", who, opt ? " or the moments" : "");
+  if (!idx_pool || !y_pool || n_pool < 1 || n_steps < 0 || B < 1) return fail(FMX_ERR_ARG, "%s: bad pool / step count", who);
+  if (opt) {
+    if (int rc = check_adam(hyper, rule, n_steps)) return rc;
+    if (int rc = mlp_opt_check(mlp, B, mlp_workspace, mlp_workspace_bytes, grads, opt, n_steps, who)) return rc;
+  }
+  if (mlp->k > table->kp) return fail(FMX_ERR_SHAPE, "%s: the MLP reads k=%d columns of a bi of kp=%d", who, mlp->k, table->kp);
   if (!aligned16(gbi) || !aligned16(dz)) return fail(FMX_ERR_ALIGN, "dz and gbi must be 16-byte aligned");
   if (int rc = check_sort_geometry(table, B)) return rc;
-  if (int rc = check_workspace(table, B, workspace, workspace_bytes, "fmx_deepfm_stream")) return rc;
+  if (int rc = check_workspace(table, B, workspace, workspace_bytes, who)) return rc;
   const Workspace w = carve(table, B, workspace);
   MlpReduceArgs red;  // the section's last launch, set up by before_update, rides inside the table update's (k_fm_update_rider)
   auto before_update = [&](int s, const int32_t *idx, const float *y, hipStream_t st) -> int {
@@ -2583,14 +2591,35 @@ int fmx_deepfm_stream(const fmx_table_t *table, const fmx_hyper_t *hyper, int32_
     }
     if (rc == FMX_OK)
       rc = mlp_section_deferred_reduce(mlp, loss_kind, fwd->bi, table->kp, fwd->logit, y, B, inv_b, mlp_workspace, nullptr, dz, gbi, table->kp,
-                                       grads, lr_mlp, loss_out ? loss_out + s : nullptr, st, &red);
+                                       grads, opt ? 0.f : lr_mlp, loss_out ? loss_out + s : nullptr, st, &red, who);
+    if (rc == FMX_OK && opt) mlp_reduce_set_opt(red, *opt, opt->step + s + 1);  // step s of the call is step t = opt->step + s + 1 of the network
     return rc;
   };
-  auto update = [&](int, const uint32_t *sorted, hipStream_t st) {
-    return update_impl(table, hyper, rule, w, sorted, nullptr, fwd->S, dz, fm_term ? dz : nullptr, gbi, B, nullptr, inv_b, nullptr, st, nullptr, 0,
+  auto update = [&](int s, const uint32_t *sorted, hipStream_t st) {
+    fmx_hyper_t hs = hyper_for(hyper, rule);  // ... and step t = hyper->step + s + 1 of the tables (as in fmx_fm_stream)
+    hs.step += s;
+    return update_impl(table, &hs, rule, w, sorted, nullptr, fwd->S, dz, fm_term ? dz : nullptr, gbi, B, nullptr, inv_b, nullptr, st, nullptr, 0,
                        fwd->error, &red);
   };
   return pool_loop(table, idx_pool, y_pool, n_pool, B, n_steps, w, fwd->error, static_cast<hipStream_t>(stream), before_update, update);
+}
+
+int fmx_deepfm_stream(const fmx_table_t *table, const fmx_hyper_t *hyper, int32_t rule, const fmx_mlp_t *mlp, int32_t loss_kind, int32_t fm_term,
+                      const int32_t *idx_pool, const float *y_pool, int32_t n_pool, int32_t B, float inv_b, int32_t n_steps,
+                      void *workspace, int64_t workspace_bytes, void *mlp_workspace, const fmx_fwd_out_t *fwd, float *dz, float *gbi,
+                      float *grads, float lr_mlp, float *loss_out, fmx_stream_t stream) {
+  return deepfm_stream_impl(table, hyper, rule, mlp, loss_kind, fm_term, idx_pool, y_pool, n_pool, B, inv_b, n_steps, workspace, workspace_bytes,
+                            mlp_workspace, 0, fwd, dz, gbi, grads, lr_mlp, nullptr, loss_out, stream, "fmx_deepfm_stream");
+}
+
+int fmx_deepfm_stream_opt(const fmx_table_t *table, const fmx_hyper_t *hyper, int32_t rule, const fmx_mlp_t *mlp, int32_t loss_kind,
+                          int32_t fm_term, const int32_t *idx_pool, const float *y_pool, int32_t n_pool, int32_t B, float inv_b,
+                          int32_t n_steps, void *workspace, int64_t workspace_bytes, void *mlp_workspace, int64_t mlp_workspace_bytes,
+                          const fmx_fwd_out_t *fwd, float *dz, float *gbi, float *grads, const fmx_mlp_opt_t *opt, float *loss_out,
+                          fmx_stream_t stream) {
+  if (!opt) return fail(FMX_ERR_ARG, "fmx_deepfm_stream_opt: opt is null");
+  return deepfm_stream_impl(table, hyper, rule, mlp, loss_kind, fm_term, idx_pool, y_pool, n_pool, B, inv_b, n_steps, workspace, workspace_bytes,
+                            mlp_workspace, mlp_workspace_bytes, fwd, dz, gbi, grads, 0.f, opt, loss_out, stream, "fmx_deepfm_stream_opt");
 }
 
 // ---- the field-owner step with the library's own communicator (fmx_comm.hip) ----

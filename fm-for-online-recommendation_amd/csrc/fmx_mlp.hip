@@ -1,5 +1,6 @@
 // fmx_mlp.hip -- the relu MLP of DeepFM / NFM / the ONN classes at mini-batch sizes (fp32 MFMA) and its C ABI:
-// fmx_mlp_section, fmx_mlp_forward_batch, fmx_mlp_hedge_section, fmx_mlp_section_workspace_bytes.  Kernels: fmx_mlp_gemm.inc.
+// fmx_mlp_section, fmx_mlp_section_opt, fmx_mlp_forward_batch, fmx_mlp_hedge_section, fmx_mlp_section_workspace_bytes.  Kernels:
+// fmx_mlp_gemm.inc.
 #include "fmx_common.h"
 
 namespace {
@@ -261,6 +262,9 @@ static void mlp_big_backward(const fmx_mlp_t *mlp, const MlpBigWs &w, const floa
   a.grads = grads;
   a.params = mlp->params;
   a.lr = lr_apply;
+  a.rule = FMX_RULE_SGD;  // (fmx_mlp_section_opt / fmx_deepfm_stream_opt: mlp_reduce_set_opt on the deferred arguments)
+  a.m = a.v = nullptr;
+  a.eps = a.c1 = a.c2 = 0.f;
   a.n_layers = L;
   a.loss_b = w.loss_b;
   a.loss_out = loss_out;
@@ -288,14 +292,49 @@ int fmx_mlp_section(const fmx_mlp_t *mlp, int32_t loss_kind, const float *bi, in
                                      loss_out, static_cast<hipStream_t>(stream), nullptr);
 }
 
+extern "C++" int fmxd::mlp_opt_check(const fmx_mlp_t *mlp, int32_t B, const void *workspace, int64_t workspace_bytes, const float *grads,
+                                     const fmx_mlp_opt_t *opt, int64_t n_steps, const char *who) {
+  if (int rc = mlp_big_check(mlp, B, workspace, who)) return rc;
+  if (!grads || !opt) return fail(FMX_ERR_ARG, "%s: null argument (grads, opt)", who);
+  if (opt->rule != FMX_RULE_SGD && opt->rule != FMX_RULE_ADAGRAD && opt->rule != FMX_RULE_ADAM)
+    return fail(FMX_ERR_ARG, "%s: the network's rule %d is not FMX_RULE_SGD, FMX_RULE_ADAGRAD or FMX_RULE_ADAM", who, opt->rule);
+  if (!opt->v || (opt->rule == FMX_RULE_ADAM && !opt->m)) return fail(FMX_ERR_ARG, "%s: opt->v (and opt->m under FMX_RULE_ADAM) must be given", who);
+  if (opt->rule == FMX_RULE_ADAM && !(opt->beta1 >= 0.f && opt->beta1 < 1.f && opt->beta2 >= 0.f && opt->beta2 < 1.f))
+    return fail(FMX_ERR_ARG, "%s: opt->beta1 = %g and opt->beta2 = %g must lie in [0, 1)", who, opt->beta1, opt->beta2);
+  if (opt->step < 0 || (int64_t)opt->step + n_steps > INT32_MAX)
+    return fail(FMX_ERR_ARG, "%s: opt->step = %d must be >= 0 and step + steps of the call <= 2^31 - 1", who, opt->step);
+  if (!aligned16(mlp->params) || !aligned16(grads) || !aligned16(opt->v) || (opt->m && !aligned16(opt->m)))
+    return fail(FMX_ERR_ALIGN, "%s: mlp->params, grads, opt->m and opt->v must be 16-byte aligned", who);
+  const int64_t need = (int64_t)mlp_big_carve(mlp, B, nullptr).bytes;
+  if (workspace_bytes < need)
+    return fail(FMX_ERR_SHAPE, "%s: the MLP workspace holds %lld bytes, fmx_mlp_section_workspace_bytes asks for %lld", who,
+                (long long)workspace_bytes, (long long)need);
+  return FMX_OK;
+}
+
+int fmx_mlp_section_opt(const fmx_mlp_t *mlp, int32_t loss_kind, const float *bi, int32_t ld_bi, const float *base, const float *y, int32_t B,
+                        float inv_b, void *workspace, int64_t workspace_bytes, float *logit_out, float *dz_out, float *gbi_out, int32_t ld_gbi,
+                        float *grads, const fmx_mlp_opt_t *opt, float *loss_out, fmx_stream_t stream) {
+  const char *who = "fmx_mlp_section_opt";
+  if (int rc = mlp_opt_check(mlp, B, workspace, workspace_bytes, grads, opt, 1, who)) return rc;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  MlpReduceArgs red;  // the section with lr_apply = 0, its reduction carrying the network's rule for step t = opt->step + 1
+  if (int rc = mlp_section_deferred_reduce(mlp, loss_kind, bi, ld_bi, base, y, B, inv_b, workspace, logit_out, dz_out, gbi_out, ld_gbi, grads, 0.f,
+                                           loss_out, st, &red, who))
+    return rc;
+  mlp_reduce_set_opt(red, *opt, opt->step + 1);
+  mlp_launch_reduce(red, st);
+  return check_launch(who);
+}
+
 extern "C++" int fmxd::mlp_section_deferred_reduce(const fmx_mlp_t *mlp, int32_t loss_kind, const float *bi, int32_t ld_bi, const float *base,
                                                    const float *y, int32_t B, float inv_b, void *workspace, float *logit_out, float *dz_out,
                                                    float *gbi_out, int32_t ld_gbi, float *grads, float lr_apply, float *loss_out, hipStream_t st,
-                                                   MlpReduceArgs *deferred) {
-  if (int rc = mlp_big_check(mlp, B, workspace, "fmx_mlp_section")) return rc;
-  if (!bi || !base || !y || !dz_out || !gbi_out || !grads) return fail(FMX_ERR_ARG, "fmx_mlp_section: null argument");
-  if (ld_bi < mlp->k || ld_gbi < mlp->k) return fail(FMX_ERR_SHAPE, "fmx_mlp_section: ld_bi / ld_gbi smaller than k");
-  if (loss_kind != FMX_LOSS_BCE_LOGITS && loss_kind != FMX_LOSS_BCE_SIGMOID) return fail(FMX_ERR_ARG, "fmx_mlp_section needs a loss");
+                                                   MlpReduceArgs *deferred, const char *who) {
+  if (int rc = mlp_big_check(mlp, B, workspace, who)) return rc;
+  if (!bi || !base || !y || !dz_out || !gbi_out || !grads) return fail(FMX_ERR_ARG, "%s: null argument", who);
+  if (ld_bi < mlp->k || ld_gbi < mlp->k) return fail(FMX_ERR_SHAPE, "%s: ld_bi / ld_gbi smaller than k", who);
+  if (loss_kind != FMX_LOSS_BCE_LOGITS && loss_kind != FMX_LOSS_BCE_SIGMOID) return fail(FMX_ERR_ARG, "%s needs a loss", who);
   const MlpBigWs w = mlp_big_carve(mlp, B, workspace);
   const int L = mlp->n_layers, H = mlp->hidden;
   const size_t act = align_up((size_t)B * H * 4, 256) / 4;

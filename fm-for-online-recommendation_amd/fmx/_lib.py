@@ -24,7 +24,7 @@ EXPORTS = ["fmx_version", "fmx_last_error_string", "fmx_set_option", "fmx_sorted
            "fmx_gather_read", "fmx_comm_unique_id", "fmx_comm_create", "fmx_comm_destroy", "fmx_owner_prefetch", "fmx_owner_step",
            "fmx_fm_topk_workspace_bytes", "fmx_fm_topk", "fmx_mlp_topk_workspace_bytes", "fmx_mlp_topk",
            "fmx_fm_update_occ", "fmx_afm_forward", "fmx_afm_workspace_bytes", "fmx_afm_step",
-           "fmx_afm_side", "fmx_afm_topk_workspace_bytes", "fmx_afm_topk"]
+           "fmx_afm_side", "fmx_afm_topk_workspace_bytes", "fmx_afm_topk", "fmx_mlp_section_opt", "fmx_deepfm_stream_opt"]
 
 
 I64_RETURNS = ("fmx_workspace_bytes", "fmx_mlp_section_workspace_bytes", "fmx_fm_topk_workspace_bytes",
@@ -55,6 +55,11 @@ class Hyper(C.Structure):
 class Mlp(C.Structure):
     _fields_ = [("params", C.c_void_p), ("n_layers", C.c_int32), ("k", C.c_int32), ("hidden", C.c_int32),
                 ("reserved", C.c_int32)]
+
+
+class MlpOpt(C.Structure):
+    _fields_ = [("m", C.c_void_p), ("v", C.c_void_p), ("lr", C.c_float), ("eps", C.c_float), ("beta1", C.c_float),
+                ("beta2", C.c_float), ("rule", C.c_int32), ("step", C.c_int32)]
 
 
 class FwdOut(C.Structure):
@@ -120,6 +125,9 @@ def load():
     lib.fmx_mlp_section_workspace_bytes.argtypes = [MP, i32]
     lib.fmx_mlp_section.argtypes = [MP, i32, p, i32, p, p, i32, f32, p, p, p, p, i32, p, f32, p, p]
     lib.fmx_deepfm_stream.argtypes = [TP, HP, i32, MP, i32, i32, p, p, i32, i32, f32, i32, p, i64, p, FP, p, p, p, f32, p, p]
+    OP = C.POINTER(MlpOpt)
+    lib.fmx_mlp_section_opt.argtypes = [MP, i32, p, i32, p, p, i32, f32, p, i64, p, p, p, i32, p, OP, p, p]
+    lib.fmx_deepfm_stream_opt.argtypes = [TP, HP, i32, MP, i32, i32, p, p, i32, i32, f32, i32, p, i64, p, i64, FP, p, p, p, OP, p, p]
     lib.fmx_fm_topk_workspace_bytes.argtypes = [i32, i32, i32]
     lib.fmx_fm_topk.argtypes = [p, i32, p, i32, p, i32, p, i32, i32, p, p, i32, p, i64, p, p, p]
     lib.fmx_mlp_topk_workspace_bytes.argtypes = [MP, i32, i32, i32]

@@ -65,6 +65,22 @@ class HipDeepBackend:
         e.update(self.hyper, self.rule, GB, None, dz_g, dz_g if fm_term else None, gbi_g, inv_b=inv_b, with_loss=False, S=S_g)
 
 
+class HipDeepOptBackend(HipDeepBackend):
+    """HipDeepBackend for ONE rank with the network under a rule of its own (mlp_opt: an fmx.MlpOpt -- 'adam', 'adagrad' or
+    'sgd') and the tables under any rule, the adaptive ones on a moments table included: the MLP section and the stream go
+    through fmx_mlp_section_opt / fmx_deepfm_stream_opt.  The trainer's mlp_lr is not read: the network's learning rate is
+    mlp_opt's."""
+
+    def __init__(self, engine, hyper, rule, mlp_opt):
+        if dist.is_initialized() and dist.get_world_size() > 1:
+            raise ValueError(f"{type(self).__name__}: single-GPU only; the multi-GPU trainers take 'signadam', 'sgd' and 'ftrl' "
+                             "with SGD on the network (HipDeepBackend)")
+        self.e, self.hyper, self.rule, self.mlp_opt = engine, hyper, rule, mlp_opt
+
+    def mlp_section(self, flat, gflat, k, hidden, n_layers, loss, bi, base, y, inv_b, lr_apply):
+        return self.e.mlp_section(flat, gflat, k, hidden, n_layers, loss, bi, base, y, bi.shape[0], inv_b, mlp_opt=self.mlp_opt)
+
+
 class DeepFMTrainer:
     def __init__(self, backend, hidden_layers, k, kp, mlp_lr, fm_term=True, loss="logits", group=None, use_graph=False,
                  native_mlp=True):
@@ -76,11 +92,16 @@ class DeepFMTrainer:
         self.mlp_lr, self.fm_term, self.loss, self.group = mlp_lr, fm_term, loss, group
         self.use_graph = use_graph      # replay the PyTorch MLP section as a captured graph (static batch size)
         self.world = dist.get_world_size(group) if dist.is_initialized() else 1
+        self.mlp_opt = getattr(backend, "mlp_opt", None)     # HipDeepOptBackend: the network's rule is applied in the native section
+        if self.mlp_opt is not None and self.world > 1:
+            raise ValueError("DeepFMTrainer: a backend with an optimizer state for the network (HipDeepOptBackend) is single-GPU only")
         self.params = [p for layer in self.layers for p in (layer.weight, layer.bias)]
         self._bufs = {}
         widths = {layer.out_features for layer in self.layers} | {layer.in_features for layer in self.layers[1:]}
         self.native = bool(native_mlp and hasattr(backend, "mlp_section") and len(widths) == 1 and
                            self.layers[0].in_features == k and len(self.layers) <= 8 and self.params[0].is_cuda)
+        if self.mlp_opt is not None and not self.native:
+            raise ValueError("DeepFMTrainer: HipDeepOptBackend needs the native MLP section (equal hidden widths, at most 8 layers)")
         if self.native:   # one flat buffer (W_l then b_l per layer) that the nn.Linear parameters become views of
             self.hidden = self.layers[0].out_features
             self.flat = torch.cat([p.detach().reshape(-1) for p in self.params]).contiguous()
@@ -98,10 +119,12 @@ class DeepFMTrainer:
         if not (self.native and self.world == 1 and hasattr(self.backend, "e")):
             raise ValueError("prepare_stream: one rank and the native MLP section only; use step()")
         be = self.backend
-        if not self.fm_term and be.e.table.layout != "weights":
-            raise ValueError("prepare_stream: NFM (fm_term=False) needs tables in the weights layout; use step()")
+        if not self.fm_term and be.e.table.layout not in (("weights",) if self.mlp_opt is None else ("weights", "moments")):
+            raise ValueError("prepare_stream: NFM (fm_term=False) needs tables in the weights layout (with a HipDeepOptBackend: "
+                             "weights or moments); use step()")
         return be.e.prepare_deepfm_stream(be.hyper, be.rule, self.loss, self.flat, self.gflat, self.k, self.hidden, len(self.layers),
-                                          self.mlp_lr, idx_pool, y_pool, loss_out=loss_out, stream=stream, fm_term=self.fm_term)
+                                          self.mlp_lr, idx_pool, y_pool, loss_out=loss_out, stream=stream, fm_term=self.fm_term,
+                                          mlp_opt=self.mlp_opt)
 
     def _gathered(self, name, local):
         if self.world == 1:

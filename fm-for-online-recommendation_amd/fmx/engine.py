@@ -44,6 +44,36 @@ def mlp_struct(params, k, hidden, n_layers):
     return _lib.Mlp(params.data_ptr(), int(n_layers), int(k), int(hidden), 0)
 
 
+class MlpOpt:
+    """The network's optimizer state for fmx_mlp_section_opt / fmx_deepfm_stream_opt (include/fmx.h fmx_mlp_opt_t): the flat
+    fp32 device tensors m, v (the layout of the flat parameter buffer; adagrad keeps its sum of squares in v), the
+    hyper-parameters and the count of steps taken.  FMEngine advances `step` after each call, as it does FlatTable.step.
+    rule: 'adam' (torch.optim.Adam), 'adagrad' (torch.optim.Adagrad) or 'sgd'."""
+
+    RULES = ("sgd", "adagrad", "adam")
+
+    def __init__(self, n_params, rule, lr=0.01, eps=None, beta1=0.9, beta2=0.999, device=None, step=0):
+        if rule not in self.RULES:
+            raise ValueError(f"MlpOpt: rule {rule!r} is not one of {self.RULES}")
+        eps = (1e-10 if rule == "adagrad" else 1e-8) if eps is None else eps
+        self.rule, self.step = rule, int(step)
+        self.m = torch.zeros(int(n_params), dtype=torch.float32, device=device)
+        self.v = torch.zeros_like(self.m)
+        self.c = _lib.MlpOpt(self.m.data_ptr(), self.v.data_ptr(), lr, eps, beta1, beta2, _lib.RULES[rule], self.step)
+
+    def ref(self):
+        self.c.step = self.step
+        return C.byref(self.c)
+
+    def state_dict(self):
+        return {"m": self.m.detach().cpu().clone(), "v": self.v.detach().cpu().clone(), "step": self.step}
+
+    def load_state_dict(self, st):
+        self.m.copy_(torch.as_tensor(st["m"], dtype=torch.float32))
+        self.v.copy_(torch.as_tensor(st["v"], dtype=torch.float32))
+        self.step = int(st["step"])
+
+
 class HandOffTimeout(RuntimeError):
     """Device error word 2 (k_fm_update: a crossing run's row update was skipped): an in-launch hand-off ran into its spin
     bound.  Never observed; the table must be considered corrupt."""
@@ -250,12 +280,15 @@ class FMEngine:
         return run
 
     def prepare_deepfm_stream(self, hyper, rule, loss, params, grads, k, hidden, n_layers, lr_mlp, idx_pool, y_pool, loss_out=None,
-                              stream=None, fm_term=True):
+                              stream=None, fm_term=True, mlp_opt=None):
         """-> run(n_steps): the mini-batch DeepFM loop over a resident pool (fmx_deepfm_stream), every argument but the step count
         bound once; per step forward, MLP section (SGD of the MLP applied in it: lr_mlp), table update, all issued from one call
         (fm_term=False: NFM -- the network's base is first-order + bias; weights-layout tables).
         `params` / `grads`: the flat MLP buffers (W_l then b_l per layer).  The caller keeps the tensors alive and does not grow
-        the engine between prepare and run."""
+        the engine between prepare and run.
+        mlp_opt (an MlpOpt): fmx_deepfm_stream_opt instead -- the network under mlp_opt's rule (lr_mlp is not read), the tables
+        under any rule, the adaptive ones on a moments table included (NFM then takes weights or moments tables); a run advances
+        the table's and mlp_opt's step counts by its steps."""
         n_pool, B, F = idx_pool.shape
         assert F == self.table.n_fields and y_pool.shape == (n_pool, B)
         assert loss_out is None or loss_out.is_contiguous()
@@ -266,6 +299,8 @@ class FMEngine:
         fn, check = self.lib.fmx_deepfm_stream, _lib.check
         fixed = (self.table.c_struct(), hyper.ref(), _lib.RULES[rule], C.byref(m), _lib.LOSSES[loss], int(bool(fm_term)), idx_pool.data_ptr(), y_pool.data_ptr(),
                  n_pool, B, 1.0 / B)
+        if mlp_opt is not None:
+            return self._prepare_deepfm_stream_opt(hyper, mlp_opt, fixed, out, m, params, grads, idx_pool, y_pool, loss_out, stream)
         tail = (self.workspace.data_ptr(), self._ws_bytes(), self._mlp_ws.data_ptr(), C.byref(out), self._mlp_dz.data_ptr(),
                 self._mlp_gbi.data_ptr(), grads.data_ptr(), lr_mlp, _ptr(loss_out), self._stream(stream))
         cap = None if loss_out is None else loss_out.numel()
@@ -275,6 +310,25 @@ class FMEngine:
             if cap is not None and n_steps > cap:
                 raise ValueError(f"loss_out holds {cap} steps, {n_steps} asked for")
             check(fn(*fixed, n_steps, *tail))
+        run.keep = keep
+        return run
+
+    def _prepare_deepfm_stream_opt(self, hyper, mlp_opt, fixed, out, m, params, grads, idx_pool, y_pool, loss_out, stream):
+        fn, check = self.lib.fmx_deepfm_stream_opt, _lib.check
+        tail = (self.workspace.data_ptr(), self._ws_bytes(), self._mlp_ws.data_ptr(), self._mlp_ws.numel() * 4, C.byref(out),
+                self._mlp_dz.data_ptr(), self._mlp_gbi.data_ptr(), grads.data_ptr(), mlp_opt.ref(), _ptr(loss_out), self._stream(stream))
+        cap = None if loss_out is None else loss_out.numel()
+        keep = (out, m, hyper, mlp_opt, params, grads, idx_pool, y_pool, loss_out, self.workspace, self._mlp_ws, self._mlp_dz, self._mlp_gbi)
+        steps, advance = self._steps, self._advance
+
+        def run(n_steps):
+            if cap is not None and n_steps > cap:
+                raise ValueError(f"loss_out holds {cap} steps, {n_steps} asked for")
+            steps(hyper)
+            mlp_opt.c.step = mlp_opt.step     # (the bound structs are hyper's and mlp_opt's own: a second call continues both counts)
+            check(fn(*fixed, n_steps, *tail))
+            advance(n_steps)
+            mlp_opt.step += n_steps
         run.keep = keep
         return run
 
@@ -378,11 +432,20 @@ class FMEngine:
                                                   bi.stride(0), base.data_ptr(), y_d.data_ptr(), B, self._mlp_ws.data_ptr(),
                                                   grads.data_ptr(), None, self._stream()))
 
-    def mlp_section(self, params, grads, k, hidden, n_layers, loss, bi, base, y_d, B, inv_b, lr_apply=0.0):
+    def mlp_section(self, params, grads, k, hidden, n_layers, loss, bi, base, y_d, B, inv_b, lr_apply=0.0, mlp_opt=None):
         """The MLP on `bi` at mini-batch sizes (fmx_mlp_section: fp32 MFMA GEMMs): forward, loss, backward.
-        -> (loss [1], dz [B], gbi [B, kp]); `grads` (flat, the layout of `params`) is filled; lr_apply != 0 also applies SGD."""
+        -> (loss [1], dz [B], gbi [B, kp]); `grads` (flat, the layout of `params`) is filled; lr_apply != 0 also applies SGD.
+        mlp_opt (an MlpOpt): fmx_mlp_section_opt instead -- the network's rule is mlp_opt's (lr_apply is not read), applied in
+        the same pass; mlp_opt.step advances by one."""
         m = self._mlp_struct(params, k, hidden, n_layers)
         self._mlp_big_buffers(m, k, hidden, n_layers, B)
+        if mlp_opt is not None:
+            _lib.check(self.lib.fmx_mlp_section_opt(C.byref(m), _lib.LOSSES[loss], bi.data_ptr(), bi.stride(0), base.data_ptr(),
+                                                    y_d.data_ptr(), B, inv_b, self._mlp_ws.data_ptr(), self._mlp_ws.numel() * 4, None,
+                                                    self._mlp_dz.data_ptr(), self._mlp_gbi.data_ptr(), self.table.kp, grads.data_ptr(),
+                                                    mlp_opt.ref(), self._mlp_loss.data_ptr(), self._stream()))
+            mlp_opt.step += 1
+            return self._mlp_loss, self._mlp_dz, self._mlp_gbi
         _lib.check(self.lib.fmx_mlp_section(C.byref(m), _lib.LOSSES[loss], bi.data_ptr(), bi.stride(0), base.data_ptr(),
                                             y_d.data_ptr(), B, inv_b, self._mlp_ws.data_ptr(), None, self._mlp_dz.data_ptr(),
                                             self._mlp_gbi.data_ptr(), self.table.kp, grads.data_ptr(), lr_apply,

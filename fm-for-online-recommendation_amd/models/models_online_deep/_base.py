@@ -45,11 +45,14 @@ class OnlineFMBase(nn.Module):
 
     def __init__(self, feature_sizes, embedding_size=4, num_hidden_layers=0, neuron_per_hidden_layer=0, batch_size=1,
                  num_classes=1, b=0.99, n=0.01, s=0.2, use_cuda=True, update_rule="signadam", ftrl=None, adam=None,
-                 adagrad=None):
+                 adagrad=None, fused_optimizer=False):
         """update_rule: 'signadam' (the reference's fresh Adam per call), 'sgd', 'ftrl' (settings ftrl=dict(alpha, beta, l1,
         l2)), or the persistent adaptive rules 'adam' (torch.optim.SparseAdam on the tables; adam=dict(beta1, beta2, eps)) and
         'adagrad' (torch.optim.Adagrad; adagrad=dict(eps)).  Every rule's learning rate is n.  The hyper-parameters reach
-        the kernels as fp32: the betas in effect are float32(beta1), float32(beta2)."""
+        the kernels as fp32: the betas in effect are float32(beta1), float32(beta2).
+        fused_optimizer (DeepFM / NFM under 'adam' / 'adagrad'): False keeps the hidden layers on a torch optimizer (autograd);
+        True trains them inside the MLP section's gradient reduction (fmx_mlp_section_opt: torch.optim.Adam / Adagrad's
+        arithmetic on flat moments the model owns) at every batch size -- there is no torch optimizer then."""
         super().__init__()
         if not (use_cuda and torch.cuda.is_available()):
             raise RuntimeError(f"{self._name}: this build runs the hot path in gfx950 kernels only -- it needs use_cuda=True "
@@ -90,6 +93,9 @@ class OnlineFMBase(nn.Module):
         if adagrad:
             self._adagrad.update({k_: float(v) for k_, v in adagrad.items() if k_ in self._adagrad})
         adaptive = update_rule in ("adagrad", "adam")
+        self.fused_optimizer = bool(fused_optimizer)
+        if self.fused_optimizer and not (adaptive and self._has_mlp and not self._onn):
+            raise ValueError(f"{self._name}: fused_optimizer=True is for DeepFM / NFM under update_rule 'adam' or 'adagrad'")
         layout = "ftrl" if update_rule == "ftrl" else "moments" if adaptive else "weights"
         self._table = fmx.FlatTable(feature_sizes, embedding_size, layout=layout, device=self.device, ftrl=self._ftrl)
         self._load_weights(first, second, bias0)
@@ -115,7 +121,14 @@ class OnlineFMBase(nn.Module):
             # the adaptive rules: ONE optimizer over the hidden layers for the model's life (its state persists like the
             # tables' moments); the ONN classes train them by Hedge instead
             self._mlp_opt = None
-            if adaptive and not self._onn:
+            self._mlp_fused = None      # fused_optimizer=True: the flat moments and the step count instead (fmx.MlpOpt)
+            if self.fused_optimizer:
+                eps = self._adam["eps"] if update_rule == "adam" else self._adagrad["eps"]
+                b1, b2 = self._betas()
+                self._mlp_fused = fmx.MlpOpt(self._mlp_flat.numel(), update_rule, lr=float(n), eps=eps, beta1=b1, beta2=b2,
+                                             device=self.device)
+                self._mlp_gflat = torch.zeros_like(self._mlp_flat)
+            elif adaptive and not self._onn:
                 params = self.hidden_layers.parameters()
                 if update_rule == "adam":
                     self._mlp_opt = torch.optim.Adam(params, lr=float(n), betas=self._betas(), eps=self._adam["eps"])
@@ -185,6 +198,8 @@ class OnlineFMBase(nn.Module):
         with torch.no_grad():
             self.n.copy_(sd["n"].float().cpu())
             self._hyper = self._make_hyper(float(self.n))
+            if getattr(self, "_mlp_fused", None) is not None:
+                self._mlp_fused.c.lr = float(self.n)
             if self._has_mlp:
                 for j, layer in enumerate(self.hidden_layers):
                     layer.weight.copy_(sd[f"hidden_layers.{j}.weight"].float().to(self.device))
@@ -222,12 +237,15 @@ class OnlineFMBase(nn.Module):
     #      a resumed run also needs every coordinate's moments, the table's step count and the hidden layers' optimizer ----
     def optimizer_state_dict(self):
         """{'table': FlatTable.export_moments_state() (mV, vV, mw, vw, bias_mv, step), 'mlp': the hidden layers'
-        torch optimizer state_dict or None} on the CPU; None for the other rules."""
+        torch optimizer state_dict or None -- with fused_optimizer=True {'m', 'v', 'step'}: the flat moments (the layout of
+        the flat parameter buffer) and the network's step count} on the CPU; None for the other rules."""
         if self.update_rule not in ("adagrad", "adam"):
             return None
         opt = getattr(self, "_mlp_opt", None)
         mlp = None
-        if opt is not None:
+        if getattr(self, "_mlp_fused", None) is not None:
+            mlp = self._mlp_fused.state_dict()
+        elif opt is not None:
             mlp = opt.state_dict()
             mlp = {"state": {i: {k_: (v.detach().cpu().clone() if torch.is_tensor(v) else v) for k_, v in st.items()}
                              for i, st in mlp["state"].items()}, "param_groups": mlp["param_groups"]}
@@ -238,7 +256,9 @@ class OnlineFMBase(nn.Module):
         if self.update_rule not in ("adagrad", "adam"):
             raise ValueError("load_optimizer_state_dict: this model does not use update_rule 'adam' or 'adagrad'")
         self._table.load_moments_state(st["table"])
-        if st.get("mlp") is not None and getattr(self, "_mlp_opt", None) is not None:
+        if st.get("mlp") is not None and getattr(self, "_mlp_fused", None) is not None:
+            self._mlp_fused.load_state_dict(st["mlp"])
+        elif st.get("mlp") is not None and getattr(self, "_mlp_opt", None) is not None:
             self._mlp_opt.load_state_dict(st["mlp"])
 
     # pickle support (reference main_experiment.py:160-162 pickles the whole model): tensors go through the CPU
@@ -247,7 +267,7 @@ class OnlineFMBase(nn.Module):
                              num_hidden_layers=self.num_hidden_layers,
                              neuron_per_hidden_layer=self.neuron_per_hidden_layer, batch_size=self.batch_size,
                              num_classes=self.num_classes, update_rule=self.update_rule, ftrl=dict(self._ftrl),
-                             adam=dict(self._adam), adagrad=dict(self._adagrad)),
+                             adam=dict(self._adam), adagrad=dict(self._adagrad), fused_optimizer=self.fused_optimizer),
                 "cls": self._name, "state_dict": {k: v.cpu() for k, v in self.state_dict().items()},
                 "ftrl_state": self.ftrl_state_dict(), "optimizer_state": self.optimizer_state_dict()}
 
@@ -257,7 +277,8 @@ class OnlineFMBase(nn.Module):
                               num_hidden_layers=ctor["num_hidden_layers"],
                               neuron_per_hidden_layer=ctor["neuron_per_hidden_layer"], batch_size=ctor["batch_size"],
                               num_classes=ctor["num_classes"], update_rule=ctor["update_rule"], ftrl=ctor["ftrl"],
-                              adam=ctor.get("adam"), adagrad=ctor.get("adagrad"))
+                              adam=ctor.get("adam"), adagrad=ctor.get("adagrad"),
+                              fused_optimizer=ctor.get("fused_optimizer", False))
         self.load_state_dict(state["state_dict"])
         if state.get("ftrl_state") is not None:       # after the weights: (z, n) is the state, V / w / bias follow from it
             self.load_ftrl_state_dict(state["ftrl_state"])
@@ -416,6 +437,16 @@ class OnlineFMBase(nn.Module):
         # the MLP through autograd, every parameter updated by the fresh-Adam rule
         idx_d, xv_d, y_d = self._inputs(Xi, Xv, Y)
         e, k = self._engine, self.embedding_size
+        if self._mlp_fused is not None:
+            # fused_optimizer=True: forward, the MLP section with the hidden layers' adam / adagrad step applied in its
+            # gradient reduction (fmx_mlp_section_opt), sort, table update -- at every batch size, no autograd
+            B = e.forward(self._hyper, idx_d, xv_d)
+            _, dz, gbi = e.mlp_section(self._mlp_flat, self._mlp_gflat, k, self.neuron_per_hidden_layer, self.num_hidden_layers,
+                                       self._loss_fit, e.bi[:B], self._base_logit(B).contiguous(), y_d, B, 1.0 / B,
+                                       mlp_opt=self._mlp_fused)
+            e.sort(idx_d)
+            e.update(self._hyper, self.update_rule, B, xv_d, dz, dz if self._fm_term_in_forward else None, gbi, with_loss=False)
+            return
         e.sort(idx_d)
         B = e.forward(self._hyper, idx_d, xv_d)
         fused = self.update_rule in ("signadam", "sgd")     # the fused MLP kernels apply those two rules only

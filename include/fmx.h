@@ -93,6 +93,8 @@ enum fmx_rule {
 };
 /* The adaptive rules are taken by fmx_fm_update, fmx_fm_step, fmx_fm_stream and fmx_fm_online_run on a MOMENTS table.
  * fmx_deepfm_stream, fmx_online_run_mlp (fit mode), fmx_mlp_fit and fmx_owner_step return FMX_ERR_UNSUPPORTED for them.
+ * DeepFM / NFM under these rules: fmx_deepfm_stream_opt (tables under any rule, the network under fmx_mlp_opt_t's) and
+ * fmx_mlp_section_opt (the network's section alone), below.
  * A MOMENTS table is accepted wherever a table is only read (fmx_fm_forward, fmx_fm_forward_partial / _finish, the Hedge
  * mode of fmx_online_run_mlp): the bias weight is bias[0], as in the weights layout. */
 
@@ -441,6 +443,50 @@ int fmx_deepfm_stream(const fmx_table_t *table, const fmx_hyper_t *hyper, int32_
                       const int32_t *idx_pool, const float *y_pool, int32_t n_pool, int32_t B, float inv_b, int32_t n_steps,
                       void *workspace, int64_t workspace_bytes, void *mlp_workspace, const fmx_fwd_out_t *fwd, float *dz, float *gbi,
                       float *grads, float lr_mlp, float *loss_out, fmx_stream_t stream);
+
+/* ---- the network under a persistent rule of its own: fmx_mlp_section / fmx_deepfm_stream with a caller-owned optimizer state ----
+ * m, v: flat fp32 device buffers in the layout of fmx_mlp_t.params (W_l [out, in] then b_l [out] per layer), 16-byte aligned.
+ * The rule is applied to every parameter inside the fixed-order reduction of the weight gradients, in the pass that sums
+ * them (no further launch, no atomics); `grads` receives the summed gradient g as in fmx_mlp_section.
+ *   FMX_RULE_SGD      p -= lr * g                                               (m, v not touched; v must still be given)
+ *   FMX_RULE_ADAGRAD  G += g*g;  p -= lr * g / (sqrt(G) + eps)                  (G in v; m may be null.  torch.optim.Adagrad,
+ *                                                                               lr_decay = weight_decay = 0)
+ *   FMX_RULE_ADAM     m += (1-beta1)(g - m);  v += (1-beta2)(g*g - v);
+ *                     p -= step_size * m / (sqrt(v) + eps sqrt(1 - beta2^t)),  step_size = lr sqrt(1 - beta2^t) / (1 - beta1^t)
+ *                     -- torch.optim.Adam, lr / (1 - beta1^t) * m / (sqrt(v) / sqrt(1 - beta2^t) + eps), rearranged; it differs
+ *                     from the tables' FMX_RULE_ADAM (SparseAdam) in where eps enters.  t = step + 1 for the call's first step.
+ * step_size and eps sqrt(1 - beta2^t) are computed on the host in double, once per step.  `step` is read, never written: the
+ * caller advances it by the steps a call took. */
+typedef struct fmx_mlp_opt {
+  float *m, *v;
+  float lr, eps, beta1, beta2;
+  int32_t rule; /* FMX_RULE_SGD, FMX_RULE_ADAGRAD or FMX_RULE_ADAM */
+  int32_t step; /* FMX_RULE_ADAM: steps already taken */
+} fmx_mlp_opt_t;
+
+/* fmx_mlp_section with the network's update under opt->rule instead of lr_apply, and with the workspace's size.  grads,
+ * dz_out, gbi_out, logit_out and loss_out are bit-identical to fmx_mlp_section with lr_apply = 0 on the same inputs; under
+ * FMX_RULE_SGD params too are those of fmx_mlp_section(lr_apply = opt->lr).
+ * Before anything is launched: opt null, an unknown rule, v null, m null under FMX_RULE_ADAM, a beta outside [0, 1), step < 0
+ * or step + 1 beyond int32: FMX_ERR_ARG; mlp->params, grads, m or v not 16-byte aligned: FMX_ERR_ALIGN; workspace_bytes <
+ * fmx_mlp_section_workspace_bytes(mlp, B): FMX_ERR_SHAPE. */
+int fmx_mlp_section_opt(const fmx_mlp_t *mlp, int32_t loss_kind, const float *bi, int32_t ld_bi, const float *base,
+                        const float *y, int32_t B, float inv_b, void *workspace, int64_t workspace_bytes, float *logit_out,
+                        float *dz_out, float *gbi_out, int32_t ld_gbi, float *grads, const fmx_mlp_opt_t *opt, float *loss_out,
+                        fmx_stream_t stream);
+
+/* fmx_deepfm_stream with the network under opt->rule and the tables under ANY rule fmx_fm_stream takes, FMX_RULE_ADAGRAD /
+ * FMX_RULE_ADAM on a MOMENTS table included.  Step s of the call is step t = hyper->step + s + 1 of the tables (as in
+ * fmx_fm_stream) and t = opt->step + s + 1 of the network.  The result is the one of calling fmx_fm_forward,
+ * fmx_mlp_section_opt, fmx_sort_occurrences and fmx_fm_update per step with both counts advanced by the caller, bit for bit.
+ * fm_term = 0 (NFM) takes tables in the weights or the moments layout (bias[0] is the bias weight in both), not FTRL tables.
+ * Every argument is checked before the first launch: fmx_deepfm_stream's checks, FMX_RULE_ADAM's hyper-parameters
+ * (fmx_fm_stream), fmx_mlp_section_opt's checks of mlp, grads, opt (step + n_steps within int32) and mlp_workspace_bytes. */
+int fmx_deepfm_stream_opt(const fmx_table_t *table, const fmx_hyper_t *hyper, int32_t rule, const fmx_mlp_t *mlp, int32_t loss_kind,
+                          int32_t fm_term, const int32_t *idx_pool, const float *y_pool, int32_t n_pool, int32_t B, float inv_b,
+                          int32_t n_steps, void *workspace, int64_t workspace_bytes, void *mlp_workspace, int64_t mlp_workspace_bytes,
+                          const fmx_fwd_out_t *fwd, float *dz, float *gbi, float *grads, const fmx_mlp_opt_t *opt, float *loss_out,
+                          fmx_stream_t stream);
 
 /* Hedge backprop at mini-batch sizes (the ONN classes' fit() beyond 16 samples; reference deepfm_onn.py:109-154): per
  * layer BCELoss(sigmoid(base + sum_j x_l[j]), y), hidden layers updated by lr * sum_{i >= j} alpha_i dloss_i/dlayer_j (one
