@@ -89,6 +89,8 @@ void mlp_launch_reduce(const MlpReduceArgs &a, hipStream_t st);
 // call of n_steps steps; `who` names the entry point in the message.  Defined in fmx_mlp.hip.
 int mlp_opt_check(const fmx_mlp_t *mlp, int32_t B, const void *workspace, int64_t workspace_bytes, const float *grads, const fmx_mlp_opt_t *opt,
                   int64_t n_steps, const char *who);
+// ... its checks of a non-null opt alone (rule, m / v given, betas, step count), shared with the one-workgroup kernel's _opt calls
+int mlp_opt_state_check(const fmx_mlp_opt_t *opt, int64_t n_steps, const char *who);
 int mlp_reduce_blocks_per_layer(const MlpReduceArgs &a, int threads);
 }  // namespace fmxd
 using namespace fmxd;

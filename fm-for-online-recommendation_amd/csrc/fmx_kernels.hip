@@ -1298,7 +1298,29 @@ struct MlpArgs {
   float hedge_b, hedge_s;
   int32_t B, k, kp, hidden, n_layers, mode, rule, loss_kind;
   float inv_b;
+  // FIT under a persistent rule of the network's own (fmx_mlp_opt_t; fmx_mlp_fit_opt / fmx_online_run_mlp_opt): opt_rule is
+  // FMX_RULE_ADAGRAD or FMX_RULE_ADAM on the flat moments m, v (the layout of params; global or LDS), 0 otherwise (`rule` applies).
+  // oh is what moments_upd reads: lr = the step's step size, eps (ADAM: eps sqrt(1 - beta2^t)), beta1 / beta2 = 1 - beta1 / 1 - beta2
+  int32_t opt_rule;
+  float *m, *v;
+  fmx_hyper_t oh;
 };
+
+// the network's rule for its step t (1-based) as k_mlp_small takes it: ADAM's constants in double, once per step (adam_consts)
+inline void mlp_small_set_opt(MlpArgs &a, const fmx_mlp_opt_t &o, int32_t t) {
+  a.m = o.m;
+  a.v = o.v;
+  if (o.rule == FMX_RULE_SGD) {  // the SGD line of the update as it stands, by the network's own learning rate
+    a.opt_rule = 0;
+    a.rule = FMX_RULE_SGD;
+    a.h.lr = o.lr;
+    return;
+  }
+  a.opt_rule = o.rule;
+  a.oh.lr = o.lr;
+  a.oh.eps = o.eps;
+  if (o.rule == FMX_RULE_ADAM) adam_consts(o.lr, o.beta1, o.beta2, t, a.oh.lr, a.oh.beta1, a.oh.beta2, o.eps, &a.oh.eps);
+}
 
 __device__ __forceinline__ int mlp_in(const MlpArgs &a, int l) { return l == 0 ? a.k : a.hidden; }
 __device__ __forceinline__ float *mlp_w(const MlpArgs &a, int l) {
@@ -1414,7 +1436,15 @@ __device__ void mlp_small_body(const MlpArgs &a) {
         for (int b = 0; b < B; ++b) g += dcur[b * MLP_MAX_W + j];
         p = bias + j;
       }
-      if (a.mode == MLP_MODE_HEDGE || a.rule == FMX_RULE_SGD) *p = *p - a.h.lr * g;
+      if (a.opt_rule != 0) {  // the network's persistent rule: a workgroup-uniform run-time branch, as in mlp_reduce_block
+        const size_t o = (size_t)(p - a.params);
+        if (a.opt_rule == FMX_RULE_ADAM) {
+          moments_upd<FMX_RULE_ADAM>(*p, a.m[o], a.v[o], g, a.oh);
+        } else {  // ADAGRAD: m is neither loaded nor stored
+          float unused = 0.f;
+          moments_upd<FMX_RULE_ADAGRAD>(*p, unused, a.v[o], g, a.oh);
+        }
+      } else if (a.mode == MLP_MODE_HEDGE || a.rule == FMX_RULE_SGD) *p = *p - a.h.lr * g;
       else *p = *p - a.h.lr * g * rcp_(fabsf(g) + a.h.eps);
     }
     __syncthreads();
@@ -1450,6 +1480,11 @@ __global__ __launch_bounds__(256) void k_mlp_small(MlpArgs a) { mlp_small_body(a
 // that live in LDS for the length of the stream; wave 0 then applies the table update of k_fm_update at B = 1 from the
 // rows it still holds (not with Hedge, which leaves the tables alone).  Same arithmetic as the per-sample launches
 // (forward, k_mlp_small, sort, update), so the parameters end bit-identical; no launch gaps, no host in the loop.
+// fmx_online_run_mlp_opt (has_opt): the network under its own persistent rule -- its moments live in LDS beside the parameters
+// (v under ADAGRAD, v and m under ADAM) and are written back at the end -- and the tables under any rule but FTRL, the MOMENTS
+// rules included.  Sample i is step hyper->step + i + 1 of the tables and opt.step + i + 1 of the network: ADAM's constants of
+// both are derived once per sample by one lane of wave 1 (adam_consts, the function the host uses for a launch: same bits) while
+// wave 0 waits for the sample's rows, and reach the other threads through LDS words.
 struct OnlineMlpArgs {
   float *rows;
   const int64_t *foff;
@@ -1465,20 +1500,35 @@ struct OnlineMlpArgs {
   float hedge_b, hedge_s;
   int32_t N, F, stride, zoff, n_params;
   int32_t k, hidden, n_layers, hedge, fm_term, rule, loss_kind;
+  int32_t has_opt;    // fmx_online_run_mlp_opt: the network under opt (m, v global: copied into LDS, written back at the end)
+  fmx_mlp_opt_t opt;
 };
 
-template <int LPR, int LAYOUT, int RULE>
+__device__ __forceinline__ float uniform_f(float x) { return __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(x))); }
+
+// OPT: the instantiations of fmx_online_run_mlp_opt (has_opt); fmx_online_run_mlp's own carry none of it
+template <int LPR, int LAYOUT, int RULE, bool OPT>
 __global__ __launch_bounds__(256) void k_online_mlp(OnlineMlpArgs a) {
   constexpr int SLOTS = WAVE / LPR, NP = 4;
-  extern __shared__ float p_lds[];  // [n_params] the MLP's parameters
+  constexpr bool MOM = LAYOUT == FMX_LAYOUT_MOMENTS;
+  extern __shared__ float p_lds[];  // [n_params] the MLP's parameters; has_opt: then v [n_params] (ADAGRAD, ADAM), then m [n_params] (ADAM)
+  __shared__ float kc[8];  // ADAM's constants of the sample: tables (step size, 1 - beta1, 1 - beta2), network (the same and eps sqrt(1 - beta2^t))
   __shared__ float bi_lds[MLP_MAX_W], gbi_lds[MLP_MAX_W], alpha_lds[MLP_MAX_L];
   __shared__ float base_lds, dz_lds;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int slot = lane / LPR, q = lane % LPR;
   const int kp = LPR * 4;
   for (int i = tid; i < a.n_params; i += blockDim.x) p_lds[i] = a.params[i];
+  const int net_rule = OPT ? a.opt.rule : -1;  // workgroup-uniform
+  const bool net_adaptive = net_rule == FMX_RULE_ADAGRAD || net_rule == FMX_RULE_ADAM, net_adam = net_rule == FMX_RULE_ADAM;
+  float *v_lds = p_lds + a.n_params, *m_lds = v_lds + a.n_params;
+  if (net_adaptive)
+    for (int i = tid; i < a.n_params; i += blockDim.x) v_lds[i] = a.opt.v[i];
+  if (net_adam)
+    for (int i = tid; i < a.n_params; i += blockDim.x) m_lds[i] = a.opt.m[i];
   if (a.hedge && tid < a.n_layers) alpha_lds[tid] = a.alpha[tid];
-  float b0 = a.bias[0], b1 = LAYOUT == FMX_LAYOUT_FTRL ? a.bias[1] : 0.f, b2 = 0.f;  // (with_rule_wf: never MOMENTS)
+  // the bias (or its (z, n), or (b, m_b, v_b)) stays in wave 0's registers
+  float b0 = a.bias[0], b1 = LAYOUT != FMX_LAYOUT_WEIGHTS ? a.bias[1] : 0.f, b2 = MOM ? a.bias[2] : 0.f;
   int64_t lo[NP];
   uint32_t vocab[NP];
   bool live[NP];
@@ -1514,6 +1564,10 @@ __global__ __launch_bounds__(256) void k_online_mlp(OnlineMlpArgs a) {
     RowRegs row[NP];
     bool ok[NP];
     float4 S = splat(0.f);
+    if (OPT && tid == WAVE && (RULE == FMX_RULE_ADAM || net_adam)) {  // one lane of wave 1, idle until the MLP step
+      if (RULE == FMX_RULE_ADAM) adam_consts(a.h.lr, a.h.beta1, a.h.beta2, a.h.step + i + 1, kc[0], kc[1], kc[2]);
+      if (net_adam) adam_consts(a.opt.lr, a.opt.beta1, a.opt.beta2, a.opt.step + i + 1, kc[3], kc[4], kc[5], a.opt.eps, &kc[6]);
+    }
     if (wave == 0) {
       // ---- the FM part: the arithmetic of k_fm_forward ----
       // branch-free, all row loads together (see forward_sample / k_fm_online): with the loads of a pass under
@@ -1584,6 +1638,18 @@ __global__ __launch_bounds__(256) void k_online_mlp(OnlineMlpArgs a) {
       m.mode = MLP_MODE_FIT;
       m.rule = a.rule;
       m.loss_kind = a.loss_kind;
+      if (net_rule == FMX_RULE_SGD) {  // (mlp_small_set_opt)
+        m.rule = FMX_RULE_SGD;
+        m.h.lr = a.opt.lr;
+      } else if (net_adaptive) {
+        m.opt_rule = net_rule;
+        m.m = m_lds;
+        m.v = v_lds;
+        m.oh.lr = net_adam ? uniform_f(kc[3]) : a.opt.lr;
+        m.oh.eps = net_adam ? uniform_f(kc[6]) : a.opt.eps;
+        m.oh.beta1 = net_adam ? uniform_f(kc[4]) : 0.f;
+        m.oh.beta2 = net_adam ? uniform_f(kc[5]) : 0.f;
+      }
     }
     mlp_small_body(m);
     __syncthreads();
@@ -1592,27 +1658,38 @@ __global__ __launch_bounds__(256) void k_online_mlp(OnlineMlpArgs a) {
       const float dz = dz_lds;
       const float4 g4 = {gbi_lds[4 * q], gbi_lds[4 * q + 1], gbi_lds[4 * q + 2], gbi_lds[4 * q + 3]};
       const float4 G = splat(a.fm_term ? dz : 0.f) + g4;
+      fmx_hyper_t h = a.h;
+      if (RULE == FMX_RULE_ADAM) {  // the sample's constants, as update_impl derives them for a launch
+        h.lr = uniform_f(kc[0]);
+        h.beta1 = uniform_f(kc[1]);
+        h.beta2 = uniform_f(kc[2]);
+      }
 #pragma unroll
       for (int p = 0; p < NP; ++p) {
         if (ok[p]) {
           const float4 xG = x[p] * G;
           update_row<LAYOUT, RULE>(a.rows + (size_t)(lo[p] + li[p]) * a.stride, q, kp, a.zoff, row[p], xG * S, x[p] * xG, x[p] * dz,
-                                   a.h);
+                                   h);
         }
       }
-      bias_step<LAYOUT, RULE>(b0, b1, b2, dz, a.h);
+      bias_step<LAYOUT, RULE>(b0, b1, b2, dz, h);
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the row stores are acknowledged before the next sample's loads
     }
     __syncthreads();
   }
   for (int i = tid; i < a.n_params; i += blockDim.x) a.params[i] = p_lds[i];
+  if (net_adaptive)
+    for (int i = tid; i < a.n_params; i += blockDim.x) a.opt.v[i] = v_lds[i];
+  if (net_adam)
+    for (int i = tid; i < a.n_params; i += blockDim.x) a.opt.m[i] = m_lds[i];
   if (a.hedge && tid < a.n_layers) a.alpha[tid] = alpha_lds[tid];
   if (wave == 0) {
     const bool any_bad = __ballot(bad) != 0ull;
     if (lane == 0) {
       if (!a.hedge) {
         a.bias[0] = b0;
-        if (LAYOUT == FMX_LAYOUT_FTRL) a.bias[1] = b1;
+        if (LAYOUT == FMX_LAYOUT_FTRL || (MOM && RULE == FMX_RULE_ADAM)) a.bias[1] = b1;
+        if (MOM) a.bias[2] = b2;
       }
       if (any_bad && a.error) *a.error = 1;
     }
@@ -1682,7 +1759,7 @@ bool with_one_of(int v, Fn &&f) {
 
 // f(LAYOUT, RULE) as integral constants for an update rule and the layout it pairs with (check_rule); false, and no call,
 // for a rule it does not know.  with_rule_wf: the rules of the weights and FTRL layouts only (the launches the adaptive
-// rules do not take -- k_online_mlp -- are not instantiated for them).
+// rules do not take -- fmx_online_run_mlp's k_online_mlp -- are not instantiated for them).
 template <bool MOMENTS_RULES, class Fn>
 bool with_rule_impl(int rule, Fn &&f) {
   using Weights = std::integral_constant<int, FMX_LAYOUT_WEIGHTS>;
@@ -2305,16 +2382,26 @@ void launch_online_np(const OnlineArgs &a, int np, hipStream_t st) {
 }
 
 constexpr int ONLINE_MLP_MAX_PARAMS = 8192;  // floats of MLP parameters kept in LDS by k_online_mlp
+// ... and with the network's moments beside them (fmx_online_run_mlp_opt): the same cap -- params, v and m are then 96 KB of
+// dynamic LDS next to the kernel's 47 KB of static arrays, of the CU's 160 KiB
+constexpr int ONLINE_MLP_OPT_MAX_PARAMS = 8192;
 
-template <int LPR, int LAYOUT, int RULE>
+// the parameter arrays k_online_mlp keeps in LDS: params, v under the network's ADAGRAD / ADAM, m under its ADAM
+inline int online_mlp_arrays(const OnlineMlpArgs &a) {
+  if (!a.has_opt || a.opt.rule == FMX_RULE_SGD) return 1;
+  return a.opt.rule == FMX_RULE_ADAM ? 3 : 2;
+}
+
+template <int LPR, int LAYOUT, int RULE, bool OPT>
 void launch_online_mlp_k(const OnlineMlpArgs &a, hipStream_t st) {
-  static bool raised = false;
-  if (!raised) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_online_mlp<LPR, LAYOUT, RULE>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, ONLINE_MLP_MAX_PARAMS * 4);
-    raised = true;
+  static int raised = 0;  // arrays of ONLINE_MLP_MAX_PARAMS floats the kernel may ask for so far
+  const int arrays = online_mlp_arrays(a);
+  if (raised < arrays) {
+    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_online_mlp<LPR, LAYOUT, RULE, OPT>),
+                              hipFuncAttributeMaxDynamicSharedMemorySize, arrays * ONLINE_MLP_MAX_PARAMS * 4);
+    raised = arrays;
   }
-  hipLaunchKernelGGL((k_online_mlp<LPR, LAYOUT, RULE>), dim3(1), dim3(256), (size_t)a.n_params * 4, st, a);
+  hipLaunchKernelGGL((k_online_mlp<LPR, LAYOUT, RULE, OPT>), dim3(1), dim3(256), (size_t)arrays * a.n_params * 4, st, a);
 }
 
 template <int LPR>
@@ -2877,37 +2964,69 @@ static int mlp_launch(const fmx_mlp_t *mlp, MlpArgs &a, int32_t B, int32_t kp, f
   return check_launch("k_mlp_small");
 }
 
-int fmx_online_run_mlp(const fmx_table_t *table, const fmx_hyper_t *hyper, int32_t rule, int32_t loss_kind,
-                       const fmx_mlp_t *mlp, int32_t hedge, int32_t fm_term, float hedge_b, float hedge_s, float *alpha,
-                       const int32_t *idx, const float *xv, const float *y, int32_t N, void *workspace, int64_t workspace_bytes,
-                       const fmx_fwd_out_t *fwd, float *scratch, float *pred_out, fmx_stream_t stream) {
-  if (int rc = check_table(table)) return rc;
-  if (!hyper || !mlp || !idx || !y || !workspace || !fwd || !scratch || !pred_out)
-    return fail(FMX_ERR_ARG, "fmx_online_run_mlp: null argument");
-  if (mapped(table)) return fail(FMX_ERR_UNSUPPORTED, "fmx_online_run_mlp: tables whose fields are pieces of index columns are not taken");
-  if (!fwd->S || !fwd->bi || !fwd->sfirst || !fwd->logit) return fail(FMX_ERR_ARG, "fmx_online_run_mlp: fwd needs S, bi, sfirst, logit");
-  if (!aligned16(workspace) || !aligned16(scratch)) return fail(FMX_ERR_ALIGN, "workspace and scratch must be 16-byte aligned");
-  if (hedge && !alpha) return fail(FMX_ERR_ARG, "fmx_online_run_mlp: Hedge needs alpha");
-  if (!hedge) {
-    if (adaptive_rule(rule)) return refuse_adaptive(rule, "fmx_online_run_mlp (fit mode)");
-    if (int rc = check_rule(table, rule)) return rc;
-    if (rule != FMX_RULE_SIGNADAM && rule != FMX_RULE_SGD) return fail(FMX_ERR_ARG, "fmx_online_run_mlp: rule must be SIGNADAM or SGD");
-    if (loss_kind != FMX_LOSS_BCE_LOGITS && loss_kind != FMX_LOSS_BCE_SIGMOID) return fail(FMX_ERR_ARG, "fit needs a loss");
-    if (mlp->k > MLP_MAX_W - 1) return fail(FMX_ERR_UNSUPPORTED, "fmx_online_run_mlp: k <= %d", MLP_MAX_W - 1);
-    if (int rc = check_sort_geometry(table, 1)) return rc;
-  } else if (mlp->k + mlp->n_layers > MLP_MAX_W) {
-    return fail(FMX_ERR_UNSUPPORTED, "fmx_online_run_mlp: k + layers <= %d", MLP_MAX_W);
+// the network's optimizer state for a call of n_steps steps (fmx_mlp_fit_opt, fmx_online_run_mlp_opt): mlp_opt_check's checks of opt
+static int mlp_small_opt_check(const fmx_mlp_t *mlp, const fmx_mlp_opt_t *opt, int64_t n_steps, const char *who) {
+  if (!opt) return fail(FMX_ERR_ARG, "%s: opt is null", who);
+  if (int rc = mlp_opt_state_check(opt, n_steps, who)) return rc;
+  if (!aligned16(mlp->params) || !aligned16(opt->v) || (opt->m && !aligned16(opt->m)))
+    return fail(FMX_ERR_ALIGN, "%s: mlp->params, opt->m and opt->v must be 16-byte aligned", who);
+  return FMX_OK;
+}
+// a shared check's refusal, with the entry point in front of its message
+static int named(int rc, const char *who) {
+  if (rc != FMX_OK && !strstr(g_err, who)) {
+    char msg[sizeof(g_err)];
+    snprintf(msg, sizeof(msg), "%s", g_err);
+    snprintf(g_err, sizeof(g_err), "%s: %s", who, msg);
   }
-  if (N < 0) return fail(FMX_ERR_ARG, "N must be >= 0");
+  return rc;
+}
+
+// fmx_online_run_mlp (opt null) and fmx_online_run_mlp_opt (fit mode with the network under opt's rule, the tables under any rule)
+static int online_run_mlp_impl(const fmx_table_t *table, const fmx_hyper_t *hyper, int32_t rule, int32_t loss_kind, const fmx_mlp_t *mlp,
+                               int32_t hedge, int32_t fm_term, float hedge_b, float hedge_s, float *alpha, const int32_t *idx,
+                               const float *xv, const float *y, int32_t N, void *workspace, int64_t workspace_bytes,
+                               const fmx_fwd_out_t *fwd, float *scratch, float *pred_out, const fmx_mlp_opt_t *opt, bool with_opt,
+                               fmx_stream_t stream, const char *who) {
+  if (int rc = check_table(table)) return with_opt ? named(rc, who) : rc;
+  if (!hyper || !mlp || !idx || !y || !workspace || !fwd || !scratch || !pred_out) return fail(FMX_ERR_ARG, "%s: null argument", who);
+  if (mapped(table)) return fail(FMX_ERR_UNSUPPORTED, "%s: tables whose fields are pieces of index columns are not taken", who);
+  if (!fwd->S || !fwd->bi || !fwd->sfirst || !fwd->logit) return fail(FMX_ERR_ARG, "%s: fwd needs S, bi, sfirst, logit", who);
+  if (!aligned16(workspace) || !aligned16(scratch)) return fail(FMX_ERR_ALIGN, "%s: workspace and scratch must be 16-byte aligned", who);
+  if (hedge && !alpha) return fail(FMX_ERR_ARG, "%s: Hedge needs alpha", who);
+  if (with_opt) {
+    if (!mlp->params) return fail(FMX_ERR_ARG, "%s: null mlp", who);
+    if (int rc = mlp_small_opt_check(mlp, opt, N > 0 ? N : 0, who)) return rc;
+    if (int rc = check_rule(table, rule)) return named(rc, who);
+    if (int rc = check_adam(hyper, rule, N > 0 ? N : 0)) return named(rc, who);
+    if (!fm_term && table->layout == FMX_LAYOUT_FTRL)
+      return fail(FMX_ERR_UNSUPPORTED, "%s: fm_term = 0 (NFM) needs a table in the weights or the moments layout", who);
+  }
+  if (!hedge) {
+    if (!with_opt) {
+      if (adaptive_rule(rule)) return refuse_adaptive(rule, "fmx_online_run_mlp (fit mode)");
+      if (int rc = check_rule(table, rule)) return rc;
+      if (rule != FMX_RULE_SIGNADAM && rule != FMX_RULE_SGD) return fail(FMX_ERR_ARG, "%s: rule must be SIGNADAM or SGD", who);
+    }
+    if (loss_kind != FMX_LOSS_BCE_LOGITS && loss_kind != FMX_LOSS_BCE_SIGMOID) return fail(FMX_ERR_ARG, "%s: fit needs a loss", who);
+    if (mlp->k > MLP_MAX_W - 1) return fail(FMX_ERR_UNSUPPORTED, "%s: k <= %d", who, MLP_MAX_W - 1);
+    if (int rc = check_sort_geometry(table, 1)) return with_opt ? named(rc, who) : rc;
+  } else if (mlp->k + mlp->n_layers > MLP_MAX_W) {
+    return fail(FMX_ERR_UNSUPPORTED, "%s: k + layers <= %d", who, MLP_MAX_W);
+  }
+  if (N < 0) return fail(FMX_ERR_ARG, "%s: N must be >= 0", who);
   hipStream_t st = static_cast<hipStream_t>(stream);
   {  // one workgroup walks the stream when the network fits in LDS and the fields fit one wavefront (k_online_mlp)
     long long n_params = 0;
     for (int l = 0; l < mlp->n_layers; ++l) n_params += (long long)mlp->hidden * (l == 0 ? mlp->k : mlp->hidden) + mlp->hidden;
     const int lpr = lpr_of(table->kp), slots = WAVE / lpr;
-    const bool tables_ok = hedge || table->layout == FMX_LAYOUT_WEIGHTS;
-    if (tune().online_persistent && n_params <= ONLINE_MLP_MAX_PARAMS && table->n_fields <= 4 * slots && tables_ok &&
-        mlp->hidden <= MLP_MAX_W && mlp->n_layers <= MLP_MAX_L && mlp->k <= MLP_MAX_W - 1 && N > 0) {
+    // a fit step on FTRL tables keeps the queued launches; the MOMENTS rules are instantiated for the _opt call alone
+    const bool tables_ok = hedge || table->layout == FMX_LAYOUT_WEIGHTS || (with_opt && table->layout == FMX_LAYOUT_MOMENTS);
+    if (tune().online_persistent && n_params <= (with_opt ? ONLINE_MLP_OPT_MAX_PARAMS : ONLINE_MLP_MAX_PARAMS) &&
+        table->n_fields <= 4 * slots && tables_ok && mlp->hidden <= MLP_MAX_W && mlp->n_layers <= MLP_MAX_L &&
+        mlp->k <= MLP_MAX_W - 1 && N > 0) {
       OnlineMlpArgs a;
+      memset(&a, 0, sizeof(a));
       a.rows = table->rows;
       a.foff = table->field_offsets;
       a.bias = table->bias;
@@ -2918,7 +3037,7 @@ int fmx_online_run_mlp(const fmx_table_t *table, const fmx_hyper_t *hyper, int32
       a.error = fwd->error;
       a.params = mlp->params;
       a.alpha = alpha;
-      a.h = hyper_for(hyper, -1);
+      a.h = hyper_for(hyper, with_opt ? rule : -1);  // ADAM tables: the kernel derives each sample's constants from lr, beta1, beta2, step
       a.h.alpha = 1.0f / hyper->alpha;
       a.hedge_b = hedge_b;
       a.hedge_s = hedge_s;
@@ -2934,16 +3053,26 @@ int fmx_online_run_mlp(const fmx_table_t *table, const fmx_hyper_t *hyper, int32
       a.fm_term = fm_term;
       a.rule = rule;
       a.loss_kind = loss_kind;
+      if (with_opt) {
+        a.has_opt = 1;
+        a.opt = *opt;
+        with_lpr(table->kp, [&](auto LPR) {
+          with_rule(rule, [&](auto LAYOUT, auto RULE) {
+            if constexpr (LAYOUT != FMX_LAYOUT_FTRL) launch_online_mlp_k<LPR, LAYOUT, RULE, true>(a, st);  // (tables_ok: never FTRL)
+          });
+        });
+        return check_launch("k_online_mlp");
+      }
       // FTRL-layout tables are read only (Hedge): FTRL pairs with that layout alone, any rule but SGD takes SIGNADAM (a MOMENTS
       // table, read only too, is read as a weights one)
       const int kernel_rule = table->layout == FMX_LAYOUT_FTRL ? FMX_RULE_FTRL : rule == FMX_RULE_SGD ? FMX_RULE_SGD : FMX_RULE_SIGNADAM;
       with_lpr(table->kp, [&](auto LPR) {
-        with_rule_wf(kernel_rule, [&](auto LAYOUT, auto RULE) { launch_online_mlp_k<LPR, LAYOUT, RULE>(a, st); });
+        with_rule_wf(kernel_rule, [&](auto LAYOUT, auto RULE) { launch_online_mlp_k<LPR, LAYOUT, RULE, false>(a, st); });
       });
       return check_launch("k_online_mlp");
     }
   }
-  if (int rc = check_workspace(table, 1, workspace, workspace_bytes, "fmx_online_run_mlp")) return rc;
+  if (int rc = check_workspace(table, 1, workspace, workspace_bytes, who)) return rc;
   const Workspace w = carve(table, 1, workspace);
   const size_t F = (size_t)table->n_fields;
   fmx_fwd_out_t f1 = *fwd;  // one sample: dense outputs
@@ -2977,15 +3106,34 @@ int fmx_online_run_mlp(const fmx_table_t *table, const fmx_hyper_t *hyper, int32
       a.mode = MLP_MODE_FIT;
       a.rule = rule;
       a.loss_kind = loss_kind;
+      if (with_opt) mlp_small_set_opt(a, *opt, opt->step + i + 1);  // sample i of the call is step t = opt->step + i + 1 of the network
     }
-    if (int rc = mlp_launch(mlp, a, 1, table->kp, stream, "fmx_online_run_mlp")) return rc;
+    if (int rc = mlp_launch(mlp, a, 1, table->kp, stream, who)) return rc;
     if (hedge) continue;  // Hedge trains the hidden layers and alpha only (reference deepfm_onn.py:109-154)
     if (int rc = sort_impl(table, idx_i, 1, w.sorted, w.runs, fwd->error, st)) return rc;
-    if (int rc = update_impl(table, hyper, rule, w, w.sorted, xv_i, fwd->S, dz, fm_term ? dz : nullptr, gbi, 1, nullptr, 1.0f, nullptr,
+    fmx_hyper_t hs = hyper_for(hyper, with_opt ? rule : -1);  // ... and step t = hyper->step + i + 1 of the tables
+    hs.step += i;
+    if (int rc = update_impl(table, &hs, rule, w, w.sorted, xv_i, fwd->S, dz, fm_term ? dz : nullptr, gbi, 1, nullptr, 1.0f, nullptr,
                              st, nullptr, 0, fwd->error))
       return rc;
   }
   return FMX_OK;
+}
+
+int fmx_online_run_mlp(const fmx_table_t *table, const fmx_hyper_t *hyper, int32_t rule, int32_t loss_kind,
+                       const fmx_mlp_t *mlp, int32_t hedge, int32_t fm_term, float hedge_b, float hedge_s, float *alpha,
+                       const int32_t *idx, const float *xv, const float *y, int32_t N, void *workspace, int64_t workspace_bytes,
+                       const fmx_fwd_out_t *fwd, float *scratch, float *pred_out, fmx_stream_t stream) {
+  return online_run_mlp_impl(table, hyper, rule, loss_kind, mlp, hedge, fm_term, hedge_b, hedge_s, alpha, idx, xv, y, N, workspace,
+                             workspace_bytes, fwd, scratch, pred_out, nullptr, false, stream, "fmx_online_run_mlp");
+}
+
+int fmx_online_run_mlp_opt(const fmx_table_t *table, const fmx_hyper_t *hyper, int32_t rule, int32_t loss_kind, const fmx_mlp_t *mlp,
+                           int32_t fm_term, const int32_t *idx, const float *xv, const float *y, int32_t N, void *workspace,
+                           int64_t workspace_bytes, const fmx_fwd_out_t *fwd, float *scratch, float *pred_out,
+                           const fmx_mlp_opt_t *opt, fmx_stream_t stream) {
+  return online_run_mlp_impl(table, hyper, rule, loss_kind, mlp, 0, fm_term, 0.f, 0.f, nullptr, idx, xv, y, N, workspace, workspace_bytes,
+                             fwd, scratch, pred_out, opt, true, stream, "fmx_online_run_mlp_opt");
 }
 
 int fmx_mlp_forward(const fmx_mlp_t *mlp, const float *bi, int32_t kp, const float *base, int32_t B, float *out,
@@ -3000,14 +3148,20 @@ int fmx_mlp_forward(const fmx_mlp_t *mlp, const float *bi, int32_t kp, const flo
   return mlp_launch(mlp, a, B, kp, stream, "fmx_mlp_forward");
 }
 
-int fmx_mlp_fit(const fmx_mlp_t *mlp, const fmx_hyper_t *hyper, int32_t rule, int32_t loss_kind, const float *bi, int32_t kp,
-                const float *base, const float *y, int32_t B, float inv_b, float *dz_out, float *gbi_out, float *loss_out,
-                fmx_stream_t stream) {
-  if (adaptive_rule(rule)) return refuse_adaptive(rule, "fmx_mlp_fit");
-  if (!hyper || !bi || !base || !y || !dz_out || !gbi_out) return fail(FMX_ERR_ARG, "fmx_mlp_fit: null argument");
-  if (rule != FMX_RULE_SIGNADAM && rule != FMX_RULE_SGD) return fail(FMX_ERR_ARG, "fmx_mlp_fit: rule must be SIGNADAM or SGD");
-  if (loss_kind != FMX_LOSS_BCE_LOGITS && loss_kind != FMX_LOSS_BCE_SIGMOID) return fail(FMX_ERR_ARG, "fmx_mlp_fit needs a loss");
-  if (mlp && mlp->k > MLP_MAX_W - 1) return fail(FMX_ERR_UNSUPPORTED, "fmx_mlp_fit: k <= %d", MLP_MAX_W - 1);
+// fmx_mlp_fit (opt null) and fmx_mlp_fit_opt (the hidden layers under opt's rule; `hyper` and `rule` are then not read)
+static int mlp_fit_impl(const fmx_mlp_t *mlp, const fmx_hyper_t *hyper, int32_t rule, int32_t loss_kind, const float *bi, int32_t kp,
+                        const float *base, const float *y, int32_t B, float inv_b, float *dz_out, float *gbi_out, float *loss_out,
+                        const fmx_mlp_opt_t *opt, bool with_opt, fmx_stream_t stream, const char *who) {
+  if (!with_opt && adaptive_rule(rule)) return refuse_adaptive(rule, who);
+  if ((!with_opt && !hyper) || !bi || !base || !y || !dz_out || !gbi_out) return fail(FMX_ERR_ARG, "%s: null argument", who);
+  if (with_opt) {
+    if (!mlp || !mlp->params) return fail(FMX_ERR_ARG, "%s: null mlp", who);
+    if (int rc = mlp_small_opt_check(mlp, opt, 1, who)) return rc;
+  } else if (rule != FMX_RULE_SIGNADAM && rule != FMX_RULE_SGD) {
+    return fail(FMX_ERR_ARG, "%s: rule must be SIGNADAM or SGD", who);
+  }
+  if (loss_kind != FMX_LOSS_BCE_LOGITS && loss_kind != FMX_LOSS_BCE_SIGMOID) return fail(FMX_ERR_ARG, "%s needs a loss", who);
+  if (mlp && mlp->k > MLP_MAX_W - 1) return fail(FMX_ERR_UNSUPPORTED, "%s: k <= %d", who, MLP_MAX_W - 1);
   MlpArgs a{};
   a.bi = bi;
   a.base = base;
@@ -3015,12 +3169,26 @@ int fmx_mlp_fit(const fmx_mlp_t *mlp, const fmx_hyper_t *hyper, int32_t rule, in
   a.dz_out = dz_out;
   a.gbi_out = gbi_out;
   a.out = loss_out;
-  a.h = hyper_for(hyper, -1);
+  if (hyper) a.h = hyper_for(hyper, -1);
   a.mode = MLP_MODE_FIT;
   a.rule = rule;
   a.loss_kind = loss_kind;
   a.inv_b = inv_b;
-  return mlp_launch(mlp, a, B, kp, stream, "fmx_mlp_fit");
+  if (with_opt) mlp_small_set_opt(a, *opt, opt->step + 1);
+  return mlp_launch(mlp, a, B, kp, stream, who);
+}
+
+int fmx_mlp_fit(const fmx_mlp_t *mlp, const fmx_hyper_t *hyper, int32_t rule, int32_t loss_kind, const float *bi, int32_t kp,
+                const float *base, const float *y, int32_t B, float inv_b, float *dz_out, float *gbi_out, float *loss_out,
+                fmx_stream_t stream) {
+  return mlp_fit_impl(mlp, hyper, rule, loss_kind, bi, kp, base, y, B, inv_b, dz_out, gbi_out, loss_out, nullptr, false, stream, "fmx_mlp_fit");
+}
+
+int fmx_mlp_fit_opt(const fmx_mlp_t *mlp, const fmx_hyper_t *hyper, int32_t loss_kind, const float *bi, int32_t kp, const float *base,
+                    const float *y, int32_t B, float inv_b, float *dz_out, float *gbi_out, float *loss_out, const fmx_mlp_opt_t *opt,
+                    fmx_stream_t stream) {
+  return mlp_fit_impl(mlp, hyper, FMX_RULE_SGD, loss_kind, bi, kp, base, y, B, inv_b, dz_out, gbi_out, loss_out, opt, true, stream,
+                      "fmx_mlp_fit_opt");
 }
 
 int fmx_mlp_hedge_fit(const fmx_mlp_t *mlp, float lr, float hedge_b, float hedge_s, float *alpha, const float *bi, int32_t kp,

@@ -292,10 +292,7 @@ int fmx_mlp_section(const fmx_mlp_t *mlp, int32_t loss_kind, const float *bi, in
                                      loss_out, static_cast<hipStream_t>(stream), nullptr);
 }
 
-extern "C++" int fmxd::mlp_opt_check(const fmx_mlp_t *mlp, int32_t B, const void *workspace, int64_t workspace_bytes, const float *grads,
-                                     const fmx_mlp_opt_t *opt, int64_t n_steps, const char *who) {
-  if (int rc = mlp_big_check(mlp, B, workspace, who)) return rc;
-  if (!grads || !opt) return fail(FMX_ERR_ARG, "%s: null argument (grads, opt)", who);
+extern "C++" int fmxd::mlp_opt_state_check(const fmx_mlp_opt_t *opt, int64_t n_steps, const char *who) {
   if (opt->rule != FMX_RULE_SGD && opt->rule != FMX_RULE_ADAGRAD && opt->rule != FMX_RULE_ADAM)
     return fail(FMX_ERR_ARG, "%s: the network's rule %d is not FMX_RULE_SGD, FMX_RULE_ADAGRAD or FMX_RULE_ADAM", who, opt->rule);
   if (!opt->v || (opt->rule == FMX_RULE_ADAM && !opt->m)) return fail(FMX_ERR_ARG, "%s: opt->v (and opt->m under FMX_RULE_ADAM) must be given", who);
@@ -303,6 +300,14 @@ extern "C++" int fmxd::mlp_opt_check(const fmx_mlp_t *mlp, int32_t B, const void
     return fail(FMX_ERR_ARG, "%s: opt->beta1 = %g and opt->beta2 = %g must lie in [0, 1)", who, opt->beta1, opt->beta2);
   if (opt->step < 0 || (int64_t)opt->step + n_steps > INT32_MAX)
     return fail(FMX_ERR_ARG, "%s: opt->step = %d must be >= 0 and step + steps of the call <= 2^31 - 1", who, opt->step);
+  return FMX_OK;
+}
+
+extern "C++" int fmxd::mlp_opt_check(const fmx_mlp_t *mlp, int32_t B, const void *workspace, int64_t workspace_bytes, const float *grads,
+                                     const fmx_mlp_opt_t *opt, int64_t n_steps, const char *who) {
+  if (int rc = mlp_big_check(mlp, B, workspace, who)) return rc;
+  if (!grads || !opt) return fail(FMX_ERR_ARG, "%s: null argument (grads, opt)", who);
+  if (int rc = mlp_opt_state_check(opt, n_steps, who)) return rc;
   if (!aligned16(mlp->params) || !aligned16(grads) || !aligned16(opt->v) || (opt->m && !aligned16(opt->m)))
     return fail(FMX_ERR_ALIGN, "%s: mlp->params, grads, opt->m and opt->v must be 16-byte aligned", who);
   const int64_t need = (int64_t)mlp_big_carve(mlp, B, nullptr).bytes;

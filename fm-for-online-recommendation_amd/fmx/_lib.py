@@ -24,7 +24,8 @@ EXPORTS = ["fmx_version", "fmx_last_error_string", "fmx_set_option", "fmx_sorted
            "fmx_gather_read", "fmx_comm_unique_id", "fmx_comm_create", "fmx_comm_destroy", "fmx_owner_prefetch", "fmx_owner_step",
            "fmx_fm_topk_workspace_bytes", "fmx_fm_topk", "fmx_mlp_topk_workspace_bytes", "fmx_mlp_topk",
            "fmx_fm_update_occ", "fmx_afm_forward", "fmx_afm_workspace_bytes", "fmx_afm_step",
-           "fmx_afm_side", "fmx_afm_topk_workspace_bytes", "fmx_afm_topk", "fmx_mlp_section_opt", "fmx_deepfm_stream_opt"]
+           "fmx_afm_side", "fmx_afm_topk_workspace_bytes", "fmx_afm_topk", "fmx_mlp_section_opt", "fmx_deepfm_stream_opt",
+           "fmx_mlp_fit_opt", "fmx_online_run_mlp_opt"]
 
 
 I64_RETURNS = ("fmx_workspace_bytes", "fmx_mlp_section_workspace_bytes", "fmx_fm_topk_workspace_bytes",
@@ -128,6 +129,8 @@ def load():
     OP = C.POINTER(MlpOpt)
     lib.fmx_mlp_section_opt.argtypes = [MP, i32, p, i32, p, p, i32, f32, p, i64, p, p, p, i32, p, OP, p, p]
     lib.fmx_deepfm_stream_opt.argtypes = [TP, HP, i32, MP, i32, i32, p, p, i32, i32, f32, i32, p, i64, p, i64, FP, p, p, p, OP, p, p]
+    lib.fmx_mlp_fit_opt.argtypes = [MP, HP, i32, p, i32, p, p, i32, f32, p, p, p, OP, p]
+    lib.fmx_online_run_mlp_opt.argtypes = [TP, HP, i32, i32, MP, i32, p, p, p, i32, p, i64, FP, p, p, OP, p]
     lib.fmx_fm_topk_workspace_bytes.argtypes = [i32, i32, i32]
     lib.fmx_fm_topk.argtypes = [p, i32, p, i32, p, i32, p, i32, i32, p, p, i32, p, i64, p, p, p]
     lib.fmx_mlp_topk_workspace_bytes.argtypes = [MP, i32, i32, i32]

@@ -354,11 +354,19 @@ class FMEngine:
                                             _ptr(layers), self._stream()))
         return out, layers
 
-    def mlp_fit(self, params, k, hidden, n_layers, hyper, rule, loss, base, y_d, B, inv_b=None):
-        """-> (dz [B], gbi [B, kp]) for self.update(); the hidden layers in `params` are updated in place."""
+    def mlp_fit(self, params, k, hidden, n_layers, hyper, rule, loss, base, y_d, B, inv_b=None, mlp_opt=None):
+        """-> (dz [B], gbi [B, kp]) for self.update(); the hidden layers in `params` are updated in place.
+        mlp_opt (an MlpOpt): fmx_mlp_fit_opt instead -- the hidden layers under mlp_opt's rule (`rule` and hyper's lr / eps are
+        not read); mlp_opt.step advances by one."""
         dz = torch.empty(B, dtype=torch.float32, device=self.device)
         gbi = torch.empty((B, self.table.kp), dtype=torch.float32, device=self.device)
         m = self._mlp_struct(params, k, hidden, n_layers)
+        if mlp_opt is not None:
+            _lib.check(self.lib.fmx_mlp_fit_opt(C.byref(m), hyper.ref(), _lib.LOSSES[loss], self.bi.data_ptr(), self.table.kp,
+                                                base.data_ptr(), y_d.data_ptr(), B, 1.0 / B if inv_b is None else inv_b,
+                                                dz.data_ptr(), gbi.data_ptr(), self.loss_out.data_ptr(), mlp_opt.ref(), self._stream()))
+            mlp_opt.step += 1
+            return dz, gbi
         _lib.check(self.lib.fmx_mlp_fit(C.byref(m), hyper.ref(), _lib.RULES[rule], _lib.LOSSES[loss], self.bi.data_ptr(),
                                         self.table.kp, base.data_ptr(), y_d.data_ptr(), B, 1.0 / B if inv_b is None else inv_b,
                                         dz.data_ptr(), gbi.data_ptr(), self.loss_out.data_ptr(), self._stream()))
@@ -383,8 +391,11 @@ class FMEngine:
         return pred, loss_b
 
     def online_run_mlp(self, hyper, rule, loss, params, k, hidden, n_layers, hedge, fm_term, hedge_b, hedge_s, alpha,
-                       idx_d, xv_d, y_d):
-        """The online protocol for the classes with an MLP (fmx_online_run_mlp) -> forward() value per sample [N]."""
+                       idx_d, xv_d, y_d, mlp_opt=None):
+        """The online protocol for the classes with an MLP (fmx_online_run_mlp) -> forward() value per sample [N].
+        mlp_opt (an MlpOpt; fit mode only): fmx_online_run_mlp_opt instead -- the network under mlp_opt's rule, the tables under
+        any rule, the adaptive ones on a moments table included; the call advances mlp_opt.step and, on a moments table, the
+        table's step count by N."""
         N = idx_d.shape[0]
         self._ensure(1)
         out = self._fwd_out(want_first=False, want_bi=True)
@@ -392,6 +403,17 @@ class FMEngine:
         pred = torch.empty(N, dtype=torch.float32, device=self.device)
         if getattr(self, "_online_scratch", None) is None:
             self._online_scratch = torch.zeros(self.table.kp + 8, dtype=torch.float32, device=self.device)
+        if mlp_opt is not None:
+            if hedge:
+                raise ValueError("online_run_mlp: mlp_opt is for the fit mode (Hedge has a rule of its own)")
+            self._steps(hyper)
+            _lib.check(self.lib.fmx_online_run_mlp_opt(self.table.c_struct(), hyper.ref(), _lib.RULES[rule], _lib.LOSSES[loss], C.byref(m),
+                                                       1 if fm_term else 0, idx_d.data_ptr(), _ptr(xv_d), y_d.data_ptr(), N,
+                                                       self.workspace.data_ptr(), self._ws_bytes(), C.byref(out),
+                                                       self._online_scratch.data_ptr(), pred.data_ptr(), mlp_opt.ref(), self._stream()))
+            self._advance(N)
+            mlp_opt.step += N
+            return pred
         _lib.check(self.lib.fmx_online_run_mlp(self.table.c_struct(), hyper.ref(), _lib.RULES[rule], _lib.LOSSES[loss], C.byref(m),
                                                1 if hedge else 0, 1 if fm_term else 0, hedge_b, hedge_s, _ptr(alpha),
                                                idx_d.data_ptr(), _ptr(xv_d), y_d.data_ptr(), N, self.workspace.data_ptr(), self._ws_bytes(),

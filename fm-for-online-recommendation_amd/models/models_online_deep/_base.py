@@ -581,7 +581,12 @@ class OnlineFMBase(nn.Module):
         return pos.cpu().numpy(), logit.cpu().numpy()
 
     def _device_loop_ok(self):
-        """Can run_experiment's predict-then-fit loop run on the device for this model?"""
+        """Can run_experiment's predict-then-fit loop run on the device for this model?
+        DeepFM / NFM under 'adam' / 'adagrad': with fused_optimizer=True (fmx_online_run_mlp_opt; the hidden layers' torch
+        optimizer of fused_optimizer=False cannot run there).  The device loop then follows fmx_mlp_fit_opt's arithmetic -- the
+        one-workgroup kernel's, as for the other rules -- while fit() keeps fmx_mlp_section_opt at every batch size: the two
+        differ at B = 1 in the order of fp32 summations only, so a run_experiment stream and the same stream through
+        predict() + fit() agree to rounding, not bit for bit."""
         if not getattr(self, "device_online_loop", True):
             return False
         e, k = self._engine, self.embedding_size
@@ -590,12 +595,15 @@ class OnlineFMBase(nn.Module):
         H, L = self.neuron_per_hidden_layer, self.num_hidden_layers
         if self._onn:
             return self.batch_size == 1 and e.mlp_fits(1, k, H, L, "hedge")
+        if self.update_rule in ("adagrad", "adam"):
+            return self._mlp_fused is not None and e.mlp_fits(1, k, H, L, "fit")
         return self.update_rule in ("signadam", "sgd") and e.mlp_fits(1, k, H, L, "fit")
 
     def _run_experiment_on_device(self, data_Xi, data_Xv, data_Y):
         """The whole predict-then-fit loop on the device, same arithmetic as predict() + fit() per sample: pure FM as one
         wavefront walking the stream (fmx_fm_online_run); the MLP classes as the per-sample launches queued back to back
-        without host synchronisation (fmx_online_run_mlp).  The confusion matrix and its checkpoints are then counted on
+        without host synchronisation (fmx_online_run_mlp; with fused_optimizer=True fmx_online_run_mlp_opt, whose network step
+        is fmx_mlp_fit_opt's -- see _device_loop_ok).  The confusion matrix and its checkpoints are then counted on
         the host from the per-sample predictions, in the reference's order."""
         start = time()
         idx_d, xv_d, y_d = self._inputs(data_Xi, data_Xv, data_Y)
@@ -608,7 +616,8 @@ class OnlineFMBase(nn.Module):
             out = e.online_run_mlp(self._hyper, self.update_rule, self._loss_fit, self._mlp_flat, self.embedding_size,
                                    self.neuron_per_hidden_layer, self.num_hidden_layers, self._onn, self._fm_term_in_forward,
                                    float(self.b.detach()) if self._onn else 0.0, float(self.s.detach()) if self._onn else 0.0,
-                                   self.alpha if self._onn else None, idx_d, xv_d, y_d)
+                                   self.alpha if self._onn else None, idx_d, xv_d, y_d,
+                                   mlp_opt=None if self._onn else getattr(self, "_mlp_fused", None))
             pred = (torch.sigmoid(out) > 0.5).cpu().numpy()          # predict(): sigmoid of what forward() returns
         e.check_error_flag()
         y = np.asarray(data_Y).reshape(-1)
@@ -624,6 +633,9 @@ class OnlineFMBase(nn.Module):
         return time() - start, float(accuracy[-1]), {k: float(v) for k, v in roc[-1].items()}, cm
 
     def run_experiment(self, data_Xi, data_Xv, data_Y):
+        """The reference's online protocol: predict, then fit, one sample at a time -> (seconds, accuracy, roc, confusion matrix).
+        On the device where _device_loop_ok() says so (its docstring: which models, and with which arithmetic), else the loop
+        below over predict() and fit()."""
         data_size = len(data_Y)
         if data_size > 0 and self._device_loop_ok():
             return self._run_experiment_on_device(data_Xi, data_Xv, data_Y)

@@ -94,7 +94,8 @@ enum fmx_rule {
 /* The adaptive rules are taken by fmx_fm_update, fmx_fm_step, fmx_fm_stream and fmx_fm_online_run on a MOMENTS table.
  * fmx_deepfm_stream, fmx_online_run_mlp (fit mode), fmx_mlp_fit and fmx_owner_step return FMX_ERR_UNSUPPORTED for them.
  * DeepFM / NFM under these rules: fmx_deepfm_stream_opt (tables under any rule, the network under fmx_mlp_opt_t's) and
- * fmx_mlp_section_opt (the network's section alone), below.
+ * fmx_mlp_section_opt (the network's section alone) at mini-batch sizes; fmx_online_run_mlp_opt (the online predict-then-fit
+ * loop) and fmx_mlp_fit_opt (its network step alone) one sample at a time, below.
  * A MOMENTS table is accepted wherever a table is only read (fmx_fm_forward, fmx_fm_forward_partial / _finish, the Hedge
  * mode of fmx_online_run_mlp): the bias weight is bias[0], as in the weights layout. */
 
@@ -455,8 +456,8 @@ int fmx_deepfm_stream(const fmx_table_t *table, const fmx_hyper_t *hyper, int32_
  *                     p -= step_size * m / (sqrt(v) + eps sqrt(1 - beta2^t)),  step_size = lr sqrt(1 - beta2^t) / (1 - beta1^t)
  *                     -- torch.optim.Adam, lr / (1 - beta1^t) * m / (sqrt(v) / sqrt(1 - beta2^t) + eps), rearranged; it differs
  *                     from the tables' FMX_RULE_ADAM (SparseAdam) in where eps enters.  t = step + 1 for the call's first step.
- * step_size and eps sqrt(1 - beta2^t) are computed on the host in double, once per step.  `step` is read, never written: the
- * caller advances it by the steps a call took. */
+ * step_size and eps sqrt(1 - beta2^t) are computed on the host in double, once per step (fmx_online_run_mlp_opt's one-workgroup
+ * form: on the device, by the same function).  `step` is read, never written: the caller advances it by the steps a call took. */
 typedef struct fmx_mlp_opt {
   float *m, *v;
   float lr, eps, beta1, beta2;
@@ -487,6 +488,44 @@ int fmx_deepfm_stream_opt(const fmx_table_t *table, const fmx_hyper_t *hyper, in
                           int32_t n_steps, void *workspace, int64_t workspace_bytes, void *mlp_workspace, int64_t mlp_workspace_bytes,
                           const fmx_fwd_out_t *fwd, float *dz, float *gbi, float *grads, const fmx_mlp_opt_t *opt, float *loss_out,
                           fmx_stream_t stream);
+
+/* fmx_mlp_fit (the one-workgroup kernel: B <= 16, k <= 63, hidden <= 64, layers <= 8) with the hidden layers under opt->rule
+ * (FMX_RULE_SGD, FMX_RULE_ADAGRAD, FMX_RULE_ADAM as stated at fmx_mlp_opt_t: the network's ADAM is torch.optim.Adam, the tables'
+ * is SparseAdam) instead of `rule`: the thread that sums a parameter's gradient over the batch in sample order applies the rule to
+ * (p, m, v) of that parameter.  This call is step t = opt->step + 1; opt->step is read and never written.  hyper is not read
+ * (it may be null): the network's learning rate and eps are opt's.  dz_out, gbi_out and loss_out are bit-identical to
+ * fmx_mlp_fit on the same inputs (the update does not feed them); under FMX_RULE_SGD params too are those of
+ * fmx_mlp_fit(rule = FMX_RULE_SGD, lr = opt->lr).
+ * Before anything is launched: fmx_mlp_fit's checks, then opt null, an unknown rule, v null, m null under FMX_RULE_ADAM, a beta
+ * outside [0, 1), step < 0 or step + 1 beyond int32: FMX_ERR_ARG; mlp->params, m or v not 16-byte aligned: FMX_ERR_ALIGN.
+ * Replaces: DeepFMAdam.fit / NFMAdam.fit minus the table part (reference deepfm_adam.py:106-119, nfm_adam.py:105-118) with a
+ * persistent torch.optim.Adam / Adagrad over the hidden layers in place of the fresh Adam per call. */
+int fmx_mlp_fit_opt(const fmx_mlp_t *mlp, const fmx_hyper_t *hyper, int32_t loss_kind, const float *bi, int32_t kp,
+                    const float *base, const float *y, int32_t B, float inv_b, float *dz_out, float *gbi_out, float *loss_out,
+                    const fmx_mlp_opt_t *opt, fmx_stream_t stream);
+
+/* The fit mode of fmx_online_run_mlp (no Hedge: Hedge has a rule of its own) with the network under opt->rule and the tables
+ * under ANY rule fmx_fm_online_run takes, FMX_RULE_ADAGRAD / FMX_RULE_ADAM on a MOMENTS table included; the two rules are
+ * independent.  Sample i of the call is step t = hyper->step + i + 1 of the tables and t = opt->step + i + 1 of the network
+ * (both counts are read, never written: the caller advances them by N).
+ * One workgroup walks the stream (k_online_mlp) when the network has at most 8,192 parameters, the fields fit one wavefront and
+ * the tables are not FTRL tables: the parameters AND the network's moments live in LDS for the length of the stream (4 bytes
+ * per parameter, 8 under FMX_RULE_ADAGRAD, 12 under FMX_RULE_ADAM: at most 96 KB beside the kernel's 47 KB of static arrays, of
+ * the CU's 160 KiB) and are written back at the end; ADAM's constants of a sample are derived on the device by the function the
+ * host uses (same bits).  Otherwise, and with fmx_set_option("online_persistent", 0), the launches of all samples are queued
+ * without any host synchronisation (forward, the network's step with the host's per-sample constants, sort, update).  Both forms
+ * end in the bits of per-sample calls -- fmx_fm_forward, fmx_mlp_fit_opt, fmx_sort_occurrences, fmx_fm_update with hyper->step
+ * and opt->step advanced by the caller: rows (moments included), bias words, params, m, v and pred_out.
+ * Every argument is checked before the first launch (N = 0 included, which then launches nothing): fmx_online_run_mlp's checks,
+ * fmx_mlp_fit_opt's checks of opt with step + N within int32, the pairing of rule and layout and FMX_RULE_ADAM's hyper-parameters
+ * with step + N within int32 as in fmx_fm_online_run (FMX_ERR_ARG); fm_term = 0 on an FTRL table: FMX_ERR_UNSUPPORTED.
+ * workspace, fwd, scratch: as for fmx_online_run_mlp.
+ * Replaces: the loop body of run_experiment (reference deepfm_adam.py:128-130, nfm_adam.py:128-130) over predict and fit
+ * (deepfm_adam.py:106-130, nfm_adam.py:105-130) with persistent optimizers in place of the fresh Adam per call. */
+int fmx_online_run_mlp_opt(const fmx_table_t *table, const fmx_hyper_t *hyper, int32_t rule, int32_t loss_kind,
+                           const fmx_mlp_t *mlp, int32_t fm_term, const int32_t *idx, const float *xv, const float *y, int32_t N,
+                           void *workspace, int64_t workspace_bytes, const fmx_fwd_out_t *fwd, float *scratch, float *pred_out,
+                           const fmx_mlp_opt_t *opt, fmx_stream_t stream);
 
 /* Hedge backprop at mini-batch sizes (the ONN classes' fit() beyond 16 samples; reference deepfm_onn.py:109-154): per
  * layer BCELoss(sigmoid(base + sum_j x_l[j]), y), hidden layers updated by lr * sum_{i >= j} alpha_i dloss_i/dlayer_j (one
