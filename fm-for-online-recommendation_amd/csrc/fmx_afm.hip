@@ -15,6 +15,8 @@
 //                         in pair order.  dL/dV_row = x dL/de goes to E [B, F, kp]; the attention accumulators leave the
 //                         launch as one partial per workgroup.
 //   k_afm_reduce          the partials of the workgroups summed in workgroup order into [ dW | db | dh | dp ].
+//   k_afm_reduce_opt<RULE> the same sums (afm_reduce_column); the thread that finishes column g also applies the attention
+//                         parameters' rule to (params[g], m[g], v[g]) and stores them (fmx_afm_step_opt, fmx_afm_stream).
 //
 // No float is accumulated with atomics and every sum has one fixed order that depends on (B, F, t, k) alone: results are
 // bit-identical run to run.  The table update between the two launches is fmx_fm_update_occ (fmx_kernels.hip).
@@ -337,9 +339,9 @@ __global__ __launch_bounds__(64) void k_afm(AfmArgs a) {
   for (int d = lane; d < k; d += WAVE) part[t * k + 2 * t + d] = sm[L.ap + d];
 }
 
-// grad[g] = sum over the n workgroups' partials, workgroup order: 4 quarters of 64 columns per workgroup, then the quarters in order
-__global__ __launch_bounds__(256) void k_afm_reduce(const float *part, int n, int G, float *grad) {
-  __shared__ float sm[4][64];
+// column g's sum over the n workgroups' partials, workgroup order: 4 quarters of 64 columns per workgroup, then the quarters in
+// order; the value is returned to the threads of quarter 0 with g < G (the others return 0)
+__device__ __forceinline__ float afm_reduce_column(const float *part, int n, int G, float (&sm)[4][64]) {
   const int c = threadIdx.x & 63, qt = threadIdx.x >> 6;
   const int g = blockIdx.x * 64 + c;
   float acc = 0.f;
@@ -358,7 +360,46 @@ __global__ __launch_bounds__(256) void k_afm_reduce(const float *part, int n, in
   }
   sm[qt][c] = acc;
   __syncthreads();
-  if (qt == 0 && g < G) grad[g] = ((sm[0][c] + sm[1][c]) + sm[2][c]) + sm[3][c];
+  return qt == 0 && g < G ? ((sm[0][c] + sm[1][c]) + sm[2][c]) + sm[3][c] : 0.f;
+}
+
+// grad[g] = column g's sum
+__global__ __launch_bounds__(256) void k_afm_reduce(const float *part, int n, int G, float *grad) {
+  __shared__ float sm[4][64];
+  const int g = blockIdx.x * 64 + (threadIdx.x & 63);
+  const float s = afm_reduce_column(part, n, G, sm);
+  if ((threadIdx.x >> 6) == 0 && g < G) grad[g] = s;
+}
+
+// ... and the attention parameters under their rule in the same pass: the thread that holds column g's sum applies RULE to
+// (params[g], m[g], v[g]), requested ahead of the sum, and stores them.  Every parameter moves on every step, a zero gradient
+// included (dense Adam: the moments keep decaying).  h: what apply_rule / moments_upd read (afm_opt_args).
+struct AfmOptArgs {
+  float *params, *m, *v;
+  fmx_hyper_t h;
+};
+template <int RULE>
+__global__ __launch_bounds__(256) void k_afm_reduce_opt(const float *part, int n, int G, float *grad, AfmOptArgs o) {
+  __shared__ float sm[4][64];
+  const int g = blockIdx.x * 64 + (threadIdx.x & 63);
+  const bool mine = (threadIdx.x >> 6) == 0 && g < G;
+  float p = 0.f, m = 0.f, v = 0.f;
+  if (mine) {
+    p = o.params[g];
+    if (RULE == FMX_RULE_ADAGRAD || RULE == FMX_RULE_ADAM) v = o.v[g];
+    if (RULE == FMX_RULE_ADAM) m = o.m[g];
+  }
+  const float s = afm_reduce_column(part, n, G, sm);
+  if (!mine) return;
+  grad[g] = s;
+  if (RULE == FMX_RULE_ADAGRAD || RULE == FMX_RULE_ADAM) {
+    moments_upd<RULE>(p, m, v, s, o.h);
+    o.v[g] = v;
+    if (RULE == FMX_RULE_ADAM) o.m[g] = m;
+  } else {
+    p = apply_rule<RULE>(p, s, o.h);
+  }
+  o.params[g] = p;
 }
 
 // fmx_afm_side: one side of a recommendation (the context fields or the item fields of full-width rows)
@@ -530,11 +571,97 @@ AfmWs carve_afm(const fmx_table_t *table, const fmx_afm_t *afm, int B, void *bas
   return w;
 }
 
-int check_rule_layout(const fmx_table_t *t, int rule) {
+int check_rule_layout(const fmx_table_t *t, int rule, const char *who) {
   const bool ok = ((rule == FMX_RULE_SIGNADAM || rule == FMX_RULE_SGD) && t->layout == FMX_LAYOUT_WEIGHTS) ||
                   (rule == FMX_RULE_FTRL && t->layout == FMX_LAYOUT_FTRL) ||
                   ((rule == FMX_RULE_ADAGRAD || rule == FMX_RULE_ADAM) && t->layout == FMX_LAYOUT_MOMENTS);
-  return ok ? FMX_OK : fail(FMX_ERR_ARG, "fmx_afm_step: rule %d does not go with layout %d", rule, t->layout);
+  return ok ? FMX_OK : fail(FMX_ERR_ARG, "%s: rule %d does not go with layout %d", who, rule, t->layout);
+}
+
+// fmx_afm_step's own checks; w receives the carved workspace
+int check_afm_step(const fmx_table_t *table, const fmx_hyper_t *hyper, int32_t rule, const fmx_afm_t *afm, const int32_t *idx, const float *y,
+                   int32_t B, void *workspace, int64_t workspace_bytes, const float *attn_grad_out, AfmWs &w, const char *who) {
+  if (int rc = check_afm(table, afm, who)) return rc;
+  if (!hyper || !idx || !y || !workspace || !attn_grad_out) return fail(FMX_ERR_ARG, "%s: null argument", who);
+  if (B < 1) return fail(FMX_ERR_ARG, "%s: B must be >= 1", who);
+  if (int rc = check_rule_layout(table, rule, who)) return rc;
+  if (!aligned16(workspace)) return fail(FMX_ERR_ALIGN, "%s: workspace must be 16-byte aligned", who);
+  w = carve_afm(table, afm, B, workspace);
+  if (w.table_bytes < 0) return (int)w.table_bytes;
+  if (workspace_bytes < w.bytes)
+    return fail(FMX_ERR_SHAPE, "%s: workspace of %lld bytes, %lld needed (fmx_afm_workspace_bytes)", who, (long long)workspace_bytes,
+                (long long)w.bytes);
+  return FMX_OK;
+}
+
+// the attention parameters' optimizer state for a call of n_steps steps (fmx_mlp_opt_t with FMX_RULE_SIGNADAM accepted), and
+// what the steps' other calls would refuse after the first launch: the tables' FMX_RULE_ADAM hyper-parameters and the sort's
+// geometry.  Everything here is decided before anything is launched.
+int check_afm_opt(const fmx_table_t *table, const fmx_hyper_t *hyper, int32_t rule, const fmx_afm_t *afm, int32_t B, const fmx_mlp_opt_t *opt,
+                  int64_t n_steps, const char *who) {
+  if (!opt) return fail(FMX_ERR_ARG, "%s: null argument (opt)", who);
+  const int r = opt->rule;
+  if (r != FMX_RULE_SIGNADAM && r != FMX_RULE_SGD && r != FMX_RULE_ADAGRAD && r != FMX_RULE_ADAM)
+    return fail(FMX_ERR_ARG, "%s: the attention rule %d is not FMX_RULE_SIGNADAM, FMX_RULE_SGD, FMX_RULE_ADAGRAD or FMX_RULE_ADAM", who, r);
+  if (((r == FMX_RULE_ADAGRAD || r == FMX_RULE_ADAM) && !opt->v) || (r == FMX_RULE_ADAM && !opt->m))
+    return fail(FMX_ERR_ARG, "%s: opt->v (FMX_RULE_ADAGRAD, FMX_RULE_ADAM) and opt->m (FMX_RULE_ADAM) must be given", who);
+  if (r == FMX_RULE_ADAM && !(opt->beta1 >= 0.f && opt->beta1 < 1.f && opt->beta2 >= 0.f && opt->beta2 < 1.f))
+    return fail(FMX_ERR_ARG, "%s: opt->beta1 = %g and opt->beta2 = %g must lie in [0, 1)", who, opt->beta1, opt->beta2);
+  if (opt->step < 0 || (int64_t)opt->step + n_steps > INT32_MAX)
+    return fail(FMX_ERR_ARG, "%s: opt->step = %d must be >= 0 and step + steps of the call <= 2^31 - 1", who, opt->step);
+  if (!aligned16(afm->params) || (opt->m && !aligned16(opt->m)) || (opt->v && !aligned16(opt->v)))
+    return fail(FMX_ERR_ALIGN, "%s: afm->params, opt->m and opt->v must be 16-byte aligned", who);
+  if (rule == FMX_RULE_ADAM) {
+    if (!(hyper->beta1 >= 0.f && hyper->beta1 < 1.f && hyper->beta2 >= 0.f && hyper->beta2 < 1.f))
+      return fail(FMX_ERR_ARG, "%s: FMX_RULE_ADAM: beta1 = %g and beta2 = %g must lie in [0, 1)", who, hyper->beta1, hyper->beta2);
+    if (hyper->step < 0 || (int64_t)hyper->step + n_steps > INT32_MAX)
+      return fail(FMX_ERR_ARG, "%s: FMX_RULE_ADAM: step = %d must be >= 0 and step + steps of the call <= 2^31 - 1", who, hyper->step);
+  }
+  return step_geometry_check(table, B, who);
+}
+
+// what apply_rule / moments_upd read for step t (1-based) of the attention parameters: ADAM's constants in double, once per step
+AfmOptArgs afm_opt_args(const fmx_afm_t *afm, const fmx_mlp_opt_t &o, int32_t t) {
+  AfmOptArgs a;
+  memset(&a, 0, sizeof(a));
+  a.params = afm->params;
+  a.m = o.m;
+  a.v = o.v;
+  a.h.lr = o.lr;
+  a.h.eps = o.eps;
+  if (o.rule == FMX_RULE_ADAM) adam_consts(o.lr, o.beta1, o.beta2, t, a.h.lr, a.h.beta1, a.h.beta2, o.eps, &a.h.eps);
+  return a;
+}
+
+// One step on `st`: sort -> forward + backward -> table update (its last workgroups reduce the bias gradient and the loss) ->
+// attention gradient, with the attention parameters' rule for their step opt_t when opt is given.  The arguments have been checked.
+int afm_step_launches(const fmx_table_t *table, const fmx_hyper_t *hyper, int32_t rule, const fmx_afm_t *afm, const int32_t *idx,
+                      const float *xv, const float *y, int32_t B, float inv_b, void *workspace, const AfmWs &w, float *attn_grad_out,
+                      float *loss_out, int32_t *error, const fmx_mlp_opt_t *opt, int32_t opt_t, hipStream_t st) {
+  if (int rc = fmx_sort_occurrences(table, idx, B, workspace, w.table_bytes, error, st)) return rc;
+  AfmArgs a = fill_afm(table, afm, hyper, idx, xv, y, B, FMX_LOSS_BCE_LOGITS, inv_b, error);
+  a.dz = w.dz;
+  a.loss = w.loss;
+  a.E = w.E;
+  a.part = w.part;
+  if (int rc = launch_afm<true>(a, table->kp, table->layout == FMX_LAYOUT_FTRL, st)) return rc;
+  if (int rc = fmx_fm_update_occ(table, hyper, rule, workspace, w.table_bytes, xv, w.dz, w.E, table->n_fields * table->kp, B, w.loss,
+                                 inv_b, loss_out, st))
+    return rc;
+  const dim3 grid((a.G + 63) / 64), block(256);
+  const int n = afm_grid(B);
+  if (!opt) {
+    hipLaunchKernelGGL(k_afm_reduce, grid, block, 0, st, w.part, n, a.G, attn_grad_out);
+    return check_launch("k_afm_reduce");
+  }
+  const AfmOptArgs o = afm_opt_args(afm, *opt, opt_t);
+  switch (opt->rule) {
+    case FMX_RULE_SIGNADAM: hipLaunchKernelGGL(k_afm_reduce_opt<FMX_RULE_SIGNADAM>, grid, block, 0, st, w.part, n, a.G, attn_grad_out, o); break;
+    case FMX_RULE_SGD: hipLaunchKernelGGL(k_afm_reduce_opt<FMX_RULE_SGD>, grid, block, 0, st, w.part, n, a.G, attn_grad_out, o); break;
+    case FMX_RULE_ADAGRAD: hipLaunchKernelGGL(k_afm_reduce_opt<FMX_RULE_ADAGRAD>, grid, block, 0, st, w.part, n, a.G, attn_grad_out, o); break;
+    default: hipLaunchKernelGGL(k_afm_reduce_opt<FMX_RULE_ADAM>, grid, block, 0, st, w.part, n, a.G, attn_grad_out, o); break;
+  }
+  return check_launch("k_afm_reduce_opt");
 }
 
 }  // namespace
@@ -566,30 +693,59 @@ int64_t fmx_afm_workspace_bytes(const fmx_table_t *table, const fmx_afm_t *afm, 
 int fmx_afm_step(const fmx_table_t *table, const fmx_hyper_t *hyper, int32_t rule, const fmx_afm_t *afm, const int32_t *idx,
                  const float *xv, const float *y, int32_t B, float inv_b, void *workspace, int64_t workspace_bytes,
                  float *attn_grad_out, float *loss_out, int32_t *error, fmx_stream_t stream) {
-  if (int rc = check_afm(table, afm, "fmx_afm_step")) return rc;
-  if (!hyper || !idx || !y || !workspace || !attn_grad_out) return fail(FMX_ERR_ARG, "fmx_afm_step: null argument");
-  if (B < 1) return fail(FMX_ERR_ARG, "fmx_afm_step: B must be >= 1");
-  if (int rc = check_rule_layout(table, rule)) return rc;
-  if (!aligned16(workspace)) return fail(FMX_ERR_ALIGN, "fmx_afm_step: workspace must be 16-byte aligned");
-  const AfmWs w = carve_afm(table, afm, B, workspace);
-  if (w.table_bytes < 0) return (int)w.table_bytes;
-  if (workspace_bytes < w.bytes)
-    return fail(FMX_ERR_SHAPE, "fmx_afm_step: workspace of %lld bytes, %lld needed (fmx_afm_workspace_bytes)", (long long)workspace_bytes,
-                (long long)w.bytes);
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  // sort -> forward + backward -> table update (its last workgroups reduce the bias gradient and the loss) -> attention gradient
-  if (int rc = fmx_sort_occurrences(table, idx, B, workspace, w.table_bytes, error, stream)) return rc;
-  AfmArgs a = fill_afm(table, afm, hyper, idx, xv, y, B, FMX_LOSS_BCE_LOGITS, inv_b, error);
-  a.dz = w.dz;
-  a.loss = w.loss;
-  a.E = w.E;
-  a.part = w.part;
-  if (int rc = launch_afm<true>(a, table->kp, table->layout == FMX_LAYOUT_FTRL, st)) return rc;
-  if (int rc = fmx_fm_update_occ(table, hyper, rule, workspace, w.table_bytes, xv, w.dz, w.E, table->n_fields * table->kp, B, w.loss,
-                                 inv_b, loss_out, stream))
-    return rc;
-  hipLaunchKernelGGL(k_afm_reduce, dim3((a.G + 63) / 64), dim3(256), 0, st, w.part, afm_grid(B), a.G, attn_grad_out);
-  return check_launch("k_afm_reduce");
+  const char *who = "fmx_afm_step";
+  AfmWs w;
+  if (int rc = check_afm_step(table, hyper, rule, afm, idx, y, B, workspace, workspace_bytes, attn_grad_out, w, who)) return rc;
+  return afm_step_launches(table, hyper, rule, afm, idx, xv, y, B, inv_b, workspace, w, attn_grad_out, loss_out, error, nullptr, 0,
+                           static_cast<hipStream_t>(stream));
+}
+
+int fmx_afm_step_opt(const fmx_table_t *table, const fmx_hyper_t *hyper, int32_t rule, const fmx_afm_t *afm, const int32_t *idx,
+                     const float *xv, const float *y, int32_t B, float inv_b, void *workspace, int64_t workspace_bytes,
+                     float *attn_grad_out, const fmx_mlp_opt_t *opt, float *loss_out, int32_t *error, fmx_stream_t stream) {
+  const char *who = "fmx_afm_step_opt";
+  AfmWs w;
+  if (int rc = check_afm_step(table, hyper, rule, afm, idx, y, B, workspace, workspace_bytes, attn_grad_out, w, who)) return rc;
+  if (int rc = check_afm_opt(table, hyper, rule, afm, B, opt, 1, who)) return rc;
+  return afm_step_launches(table, hyper, rule, afm, idx, xv, y, B, inv_b, workspace, w, attn_grad_out, loss_out, error, opt,
+                           opt->step + 1, static_cast<hipStream_t>(stream));
+}
+
+int fmx_afm_stream(const fmx_table_t *table, const fmx_hyper_t *hyper, int32_t rule, const fmx_afm_t *afm, const int32_t *idx_pool,
+                   const float *xv_pool, const float *y_pool, int32_t n_pool, int32_t B, float inv_b, int32_t n_steps, void *workspace,
+                   int64_t workspace_bytes, float *attn_grad_out, const fmx_mlp_opt_t *opt, float *loss_out, int32_t *error,
+                   fmx_stream_t stream) {
+  const char *who = "fmx_afm_stream";
+  AfmWs w;
+  if (int rc = check_afm_step(table, hyper, rule, afm, idx_pool, y_pool, B, workspace, workspace_bytes, attn_grad_out, w, who)) return rc;
+  if (n_pool < 1 || n_steps < 0) return fail(FMX_ERR_ARG, "%s: n_pool = %d must be >= 1 and n_steps = %d >= 0", who, n_pool, n_steps);
+  if (int rc = check_afm_opt(table, hyper, rule, afm, B, opt, n_steps, who)) return rc;
+  const hipStream_t st = static_cast<hipStream_t>(stream);
+  const size_t F = (size_t)table->n_fields;
+  // Every batch is sorted on `stream` in front of its step, as fmx_afm_step does it: the steps are one plain queue of launches
+  // (no side stream, no events; the sort-ahead loop of fmx_fm_stream is not used here).
+  // (a field added to fmx_hyper_t must be carried over below, or the stream parts from fmx_afm_step_opt)
+  static_assert(sizeof(fmx_hyper_t) == 40, "fmx_afm_stream copies fmx_hyper_t field by field: add the new field to the copy");
+  fmx_hyper_t hs;  // step s of the call is step hyper->step + s + 1 of the tables (the fields appended for ADAM are read for it alone)
+  memset(&hs, 0, sizeof(hs));
+  hs.lr = hyper->lr;
+  hs.eps = hyper->eps;
+  hs.alpha = hyper->alpha;
+  hs.beta = hyper->beta;
+  hs.l1 = hyper->l1;
+  hs.l2 = hyper->l2;
+  if (rule == FMX_RULE_ADAM) {
+    hs.beta1 = hyper->beta1;
+    hs.beta2 = hyper->beta2;
+    hs.step = hyper->step;
+  }
+  for (int s = 0; s < n_steps; ++s, ++hs.step) {
+    const size_t j = (size_t)(s % n_pool);
+    if (int rc = afm_step_launches(table, &hs, rule, afm, idx_pool + j * B * F, xv_pool ? xv_pool + j * B * F : nullptr, y_pool + j * B, B,
+                                   inv_b, workspace, w, attn_grad_out, loss_out ? loss_out + s : nullptr, error, opt, opt->step + s + 1, st))
+      return rc;
+  }
+  return FMX_OK;
 }
 
 int fmx_afm_side(const fmx_table_t *table, const fmx_afm_t *afm, const fmx_hyper_t *hyper, const int32_t *idx, const float *xv,

@@ -92,6 +92,9 @@ int mlp_opt_check(const fmx_mlp_t *mlp, int32_t B, const void *workspace, int64_
 // ... its checks of a non-null opt alone (rule, m / v given, betas, step count), shared with the one-workgroup kernel's _opt calls
 int mlp_opt_state_check(const fmx_mlp_opt_t *opt, int64_t n_steps, const char *who);
 int mlp_reduce_blocks_per_layer(const MlpReduceArgs &a, int threads);
+// what fmx_sort_occurrences and fmx_fm_update_occ check of a table and a batch size before they launch (the table's fields, the
+// sort's width and its 32-bit composites), for a caller that must refuse before ITS first launch.  Defined in fmx_kernels.hip.
+int step_geometry_check(const fmx_table_t *table, int32_t B, const char *who);
 }  // namespace fmxd
 using namespace fmxd;
 

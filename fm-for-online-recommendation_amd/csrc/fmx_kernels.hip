@@ -1865,6 +1865,14 @@ int check_sort_geometry(const fmx_table_t *t, int B) {
 
 }  // namespace
 namespace fmxd {
+int step_geometry_check(const fmx_table_t *table, int32_t B, const char *who) {
+  int rc = check_table(table);
+  if (rc == FMX_OK) rc = check_sort_geometry(table, B);
+  if (rc == FMX_OK) return rc;
+  char msg[sizeof(g_err)];
+  snprintf(msg, sizeof(msg), "%s", g_err);
+  return fail(rc, "%s: %s", who, msg);
+}
 Tune &tune() {
   static Tune t = [] {
     Tune x;

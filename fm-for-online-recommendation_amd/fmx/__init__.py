@@ -10,4 +10,4 @@ from .table import FlatTable, padded_k  # noqa: F401
 from .engine import FMEngine, Hyper, MlpOpt, normalize_inputs  # noqa: F401
 from .distributed import DataParallelFM, HipBackend  # noqa: F401
 from .deep import DeepFMTrainer, HipDeepBackend, HipDeepOptBackend, OwnerDeepFMTrainer  # noqa: F401
-from .afm import AFMEngine  # noqa: F401
+from .afm import AFMEngine, AfmOpt  # noqa: F401

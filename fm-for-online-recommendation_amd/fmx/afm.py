@@ -1,18 +1,28 @@
-"""AFMEngine: workspace + launch sequencing of the attentional FM (fmx_afm_forward / fmx_afm_step) for one FlatTable.
+"""AFMEngine: workspace + launch sequencing of the attentional FM (fmx_afm_forward / fmx_afm_step / fmx_afm_step_opt /
+fmx_afm_stream) for one FlatTable.
 
 The attention parameters live in ONE flat fp32 device buffer [ W (t x k) | b (t) | h (t) | p (k) ] (include/fmx.h, fmx_afm_t);
-the step returns their gradient in the same layout and leaves updating them to the caller."""
+the step returns their gradient in the same layout and leaves updating them to the caller -- or, given an AfmOpt, applies their
+rule inside the gradient's reduction."""
 import ctypes as C
 
 import torch
 
 from . import _lib
-from .engine import FMEngine, _ptr
+from .engine import FMEngine, MlpOpt, _ptr
 from .table import FlatTable
 
 
 def afm_param_count(k, t):
     return t * k + 2 * t + k
+
+
+class AfmOpt(MlpOpt):
+    """The attention parameters' optimizer state for fmx_afm_step_opt / fmx_afm_stream: fmx.MlpOpt over the flat buffer
+    [W | b | h | p], with 'signadam' (p -= lr g / (|g| + eps): a fresh Adam's first step) taken beside 'sgd', 'adagrad', 'adam'.
+    'signadam' and 'sgd' keep no moments: m and v stay zero."""
+
+    RULES = ("signadam", "sgd", "adagrad", "adam")
 
 
 class AFMEngine:
@@ -63,16 +73,44 @@ class AFMEngine:
                                             self._stream(stream)))
         return B
 
-    def step(self, hyper, rule, idx_d, xv_d, y_d, inv_b=None, stream=None):
+    def step(self, hyper, rule, idx_d, xv_d, y_d, inv_b=None, stream=None, opt=None):
         """One mini-batch step: the table updated under `rule`, the mean loss in self.loss_out[0], the attention gradient in
-        self.grad (no sync here)."""
+        self.grad (no sync here).  opt (an AfmOpt): the attention parameters take its rule in the same call (fmx_afm_step_opt)
+        and its step count advances; None leaves them to the caller."""
         B = idx_d.shape[0]
         self._ensure(B)
         if self.table.layout == "moments":
             hyper.c.step = self.table.step
-        _lib.check(self.lib.fmx_afm_step(self.table.c_struct(), hyper.ref(), _lib.RULES[rule], C.byref(self.c_afm), idx_d.data_ptr(),
-                                         _ptr(xv_d), y_d.data_ptr(), B, 1.0 / B if inv_b is None else inv_b,
-                                         self.workspace.data_ptr(), self.workspace.numel() * 4, self.grad.data_ptr(),
-                                         self.loss_out.data_ptr(), self.error.data_ptr(), self._stream(stream)))
+        head = (self.table.c_struct(), hyper.ref(), _lib.RULES[rule], C.byref(self.c_afm), idx_d.data_ptr(), _ptr(xv_d),
+                y_d.data_ptr(), B, 1.0 / B if inv_b is None else inv_b, self.workspace.data_ptr(), self.workspace.numel() * 4,
+                self.grad.data_ptr())
+        tail = (self.loss_out.data_ptr(), self.error.data_ptr(), self._stream(stream))
+        if opt is None:
+            _lib.check(self.lib.fmx_afm_step(*head, *tail))
+        else:
+            _lib.check(self.lib.fmx_afm_step_opt(*head, opt.ref(), *tail))
+            opt.step += 1
         if self.table.layout == "moments":
             self.table.step += 1
+
+    def stream(self, hyper, rule, idx_pool, xv_pool, y_pool, B, n_steps, opt, inv_b=None, losses=None, stream=None):
+        """n_steps steps over a device-resident pool in one call (fmx_afm_stream; no sync here): idx_pool [n_pool, B, F] int32,
+        xv_pool the same shape in fp32 or None (ones), y_pool [n_pool, B]; step s takes batch s mod n_pool.  losses: an fp32
+        device tensor of n_steps elements for the steps' mean losses, or None.  The table's step count and opt's advance by
+        n_steps; self.grad holds the last step's attention gradient."""
+        B, n_steps = int(B), int(n_steps)
+        n_pool = idx_pool.numel() // (B * self.table.n_fields)
+        assert idx_pool.dtype == torch.int32 and idx_pool.is_contiguous() and n_pool >= 1 and y_pool.numel() == n_pool * B
+        assert xv_pool is None or (xv_pool.dtype == torch.float32 and xv_pool.is_contiguous() and xv_pool.numel() == idx_pool.numel())
+        assert losses is None or (losses.dtype == torch.float32 and losses.numel() >= n_steps)
+        self._ensure(B)
+        if self.table.layout == "moments":
+            hyper.c.step = self.table.step
+        _lib.check(self.lib.fmx_afm_stream(self.table.c_struct(), hyper.ref(), _lib.RULES[rule], C.byref(self.c_afm),
+                                           idx_pool.data_ptr(), _ptr(xv_pool), y_pool.data_ptr(), n_pool, B,
+                                           1.0 / B if inv_b is None else inv_b, n_steps, self.workspace.data_ptr(),
+                                           self.workspace.numel() * 4, self.grad.data_ptr(), opt.ref(), _ptr(losses),
+                                           self.error.data_ptr(), self._stream(stream)))
+        opt.step += n_steps
+        if self.table.layout == "moments":
+            self.table.step += n_steps

@@ -27,7 +27,7 @@ import torch
 import torch.nn as nn
 
 import fmx
-from fmx.afm import AFMEngine
+from fmx.afm import AFMEngine, AfmOpt
 
 from ._base import OnlineFMBase, _FieldView
 
@@ -36,11 +36,16 @@ class AFMAdam(nn.Module):
     _name = "AFMAdam"
 
     def __init__(self, feature_sizes, embedding_size=4, attention_size=4, n_epochs=64, batch_size=256, num_classes=1, b=0.99,
-                 n=0.003, use_cuda=True, update_rule="adam", ftrl=None, adam=None, adagrad=None):
+                 n=0.003, use_cuda=True, update_rule="adam", ftrl=None, adam=None, adagrad=None, fused_optimizer=False):
         """update_rule: 'adam' (default: SparseAdam on the tables, a persistent Adam on the attention parameters), 'adagrad',
         'signadam' (a fresh Adam per step), 'sgd' or 'ftrl' (settings ftrl=dict(alpha, beta, l1, l2)) -- the tables' rules of
         the other classes; the attention parameters take what the hidden layers of DeepFM / NFM take under the same rule.
-        Every rule's learning rate is n."""
+        Every rule's learning rate is n.
+        fused_optimizer: False keeps the attention parameters on torch (a torch optimizer under 'adam' / 'adagrad', element-wise
+        ops under the others) after every fmx_afm_step.  True, for every update_rule: their rule is applied inside the step's
+        gradient reduction (fmx_afm_step_opt: update_embedding is one call and no torch op touches the parameters), and fit()
+        uploads the data once and runs each epoch's full batches as one fmx_afm_stream call.  The two settings agree to rounding,
+        not bit for bit (the kernels' 1-ulp reciprocal and square root against torch's)."""
         super().__init__()
         if not (use_cuda and torch.cuda.is_available()):
             raise RuntimeError(f"{self._name}: this build runs the hot path in gfx950 kernels only -- it needs use_cuda=True "
@@ -57,6 +62,7 @@ class AFMAdam(nn.Module):
         self.num_classes = num_classes
         self.use_cuda = use_cuda
         self.update_rule = update_rule
+        self.fused_optimizer = bool(fused_optimizer)
         k, t = embedding_size, attention_size
 
         # ---- the reference's RNG order (afm_adam.py:30-41) ----
@@ -96,7 +102,13 @@ class AFMAdam(nn.Module):
             prm.data = self._attn_flat[o:o + m].view(shape)
             o += m
         self._attn_opt = None
-        if adaptive:       # the model's ONE persistent optimizer over the attention parameters (the tables keep their moments)
+        self._attn_fused = None     # fused_optimizer=True: the flat moments and the step count instead (fmx.AfmOpt)
+        if self.fused_optimizer:    # the policy of _apply_attention: ftrl tables go with signadam on the attention parameters
+            arule = "signadam" if update_rule == "ftrl" else update_rule
+            b1, b2 = self._betas()
+            self._attn_fused = AfmOpt(self._attn_flat.numel(), arule, lr=float(n), beta1=b1, beta2=b2, device=self.device,
+                                      eps=self._adam["eps"] if arule == "adam" else self._adagrad["eps"] if arule == "adagrad" else 1e-8)
+        elif adaptive:     # the model's ONE persistent optimizer over the attention parameters (the tables keep their moments)
             params = self._attn_params()
             if update_rule == "adam":
                 self._attn_opt = torch.optim.Adam(params, lr=float(n), betas=self._betas(), eps=self._adam["eps"])
@@ -192,8 +204,9 @@ class AFMAdam(nn.Module):
         if y_d.numel() != idx_d.shape[0]:
             raise ValueError(f"Target size ({y_d.numel()}) must be the same as input size ({idx_d.shape[0]})")
         e = self._engine
-        e.step(self._hyper, self.update_rule, idx_d, xv_d, y_d)
-        self._apply_attention(e.grad)
+        e.step(self._hyper, self.update_rule, idx_d, xv_d, y_d, opt=self._attn_fused)
+        if self._attn_fused is None:
+            self._apply_attention(e.grad)
         out = e.loss_out[0].clone()
         self._after_step()
         return out
@@ -223,11 +236,16 @@ class AFMAdam(nn.Module):
             y_valid = np.asarray(y_valid, dtype=np.float32).reshape(-1)
         x_size = Xi_train.shape[0]
         train_result, valid_result = [], []
+        if self._attn_fused is not None:      # the training data on the device once: the epochs' batches are slices of it
+            idx_d, xv_d, y_d = self._inputs(Xi_train, Xv_train, y_train)
         for epoch in range(self.n_epochs):
             epoch_begin_time = time()
-            for offset in range(0, x_size, self.batch_size):
-                end = min(x_size, offset + self.batch_size)
-                self.update_embedding(Xi_train[offset:end], Xv_train[offset:end], y_train[offset:end])
+            if self._attn_fused is not None:
+                self._fit_epoch_fused(idx_d, xv_d, y_d)
+            else:
+                for offset in range(0, x_size, self.batch_size):
+                    end = min(x_size, offset + self.batch_size)
+                    self.update_embedding(Xi_train[offset:end], Xv_train[offset:end], y_train[offset:end])
             train_loss = self._mean_logloss(Xi_train, Xv_train, y_train)
             train_result.append(train_loss)
             print("[%d] loss: %.6f time: %.1f s" % (epoch + 1, train_loss, time() - epoch_begin_time))
@@ -236,6 +254,24 @@ class AFMAdam(nn.Module):
                 valid_result.append(valid_loss)
                 print("[%d] valid loss: %.6f time: %.1f s" % (epoch + 1, valid_loss, time() - epoch_begin_time))
         return train_result, valid_result
+
+    def _fit_epoch_fused(self, idx_d, xv_d, y_d):
+        """One epoch over device-resident data in the order of fit()'s batch loop: the full batches as ONE fmx_afm_stream call,
+        a ragged last batch as one fmx_afm_step_opt call with inv_b = 1 / its size -- the bits of update_embedding batch by
+        batch.  The index flag is read once per call, not per step."""
+        self.train()
+        e, B = self._engine, int(self.batch_size)
+        n_full = idx_d.shape[0] // B
+        cut = n_full * B
+        if n_full:
+            e.stream(self._hyper, self.update_rule, idx_d[:cut], None if xv_d is None else xv_d[:cut], y_d[:cut], B, n_full,
+                     self._attn_fused)
+            if self.strict_index_check:
+                self.check_index_flag()
+        if cut < idx_d.shape[0]:
+            e.step(self._hyper, self.update_rule, idx_d[cut:], None if xv_d is None else xv_d[cut:], y_d[cut:], opt=self._attn_fused)
+            if self.strict_index_check:
+                self.check_index_flag()
 
     def run_experiment(self, data_Xi, data_Xv, data_Y):
         """predict() over the data, then the confusion matrix and its checkpoints every 1,000 samples (afm_adam.py:193-223)."""
@@ -284,10 +320,17 @@ class AFMAdam(nn.Module):
             if self._attn_opt is not None:
                 for g in self._attn_opt.param_groups:
                     g["lr"] = float(self.n)
+            if self._attn_fused is not None:
+                self._attn_fused.c.lr = float(self.n)
 
     def optimizer_state_dict(self):
         """{'table': FlatTable.export_moments_state(), 'attention': the attention optimizer's state_dict} on the CPU for the
-        rules with moments ('adam', 'adagrad'); None for the others."""
+        rules with moments ('adam', 'adagrad'); None for the others.  With fused_optimizer=True, under every rule: 'attention' is
+        {'m', 'v', 'step'} -- the flat moments in the layout [W | b | H | P] and the attention parameters' step count -- and
+        'table' is None unless the rule keeps moments."""
+        if self._attn_fused is not None:
+            return {"table": self._table.export_moments_state() if self._table.layout == "moments" else None,
+                    "attention": self._attn_fused.state_dict()}
         if self._attn_opt is None:
             return None
         st = self._attn_opt.state_dict()
@@ -296,6 +339,12 @@ class AFMAdam(nn.Module):
         return {"table": self._table.export_moments_state(), "attention": st}
 
     def load_optimizer_state_dict(self, st):
+        if self._attn_fused is not None:
+            if st.get("table") is not None:
+                self._table.load_moments_state(st["table"])
+                self._table.step = int(st["table"]["step"])
+            self._attn_fused.load_state_dict(st["attention"])
+            return
         if self._attn_opt is None:
             raise ValueError("load_optimizer_state_dict: this model does not use update_rule 'adam' or 'adagrad'")
         self._table.load_moments_state(st["table"])
@@ -306,7 +355,7 @@ class AFMAdam(nn.Module):
         return {"ctor": dict(feature_sizes=list(self.feature_sizes), embedding_size=self.embedding_size,
                              attention_size=self.attention_size, n_epochs=self.n_epochs, batch_size=self.batch_size,
                              num_classes=self.num_classes, update_rule=self.update_rule, ftrl=dict(self._ftrl),
-                             adam=dict(self._adam), adagrad=dict(self._adagrad)),
+                             adam=dict(self._adam), adagrad=dict(self._adagrad), fused_optimizer=self.fused_optimizer),
                 "state_dict": {k: v.cpu() for k, v in self.state_dict().items()},
                 "ftrl_state": self.ftrl_state_dict(), "optimizer_state": self.optimizer_state_dict()}
 
@@ -314,7 +363,8 @@ class AFMAdam(nn.Module):
         c = state["ctor"]
         AFMAdam.__init__(self, c["feature_sizes"], embedding_size=c["embedding_size"], attention_size=c["attention_size"],
                          n_epochs=c["n_epochs"], batch_size=c["batch_size"], num_classes=c["num_classes"],
-                         update_rule=c["update_rule"], ftrl=c["ftrl"], adam=c["adam"], adagrad=c["adagrad"])
+                         update_rule=c["update_rule"], ftrl=c["ftrl"], adam=c["adam"], adagrad=c["adagrad"],
+                         fused_optimizer=c.get("fused_optimizer", False))
         self.load_state_dict(state["state_dict"])
         if state.get("ftrl_state") is not None:
             self.load_ftrl_state_dict(state["ftrl_state"])

@@ -461,7 +461,7 @@ int fmx_deepfm_stream(const fmx_table_t *table, const fmx_hyper_t *hyper, int32_
 typedef struct fmx_mlp_opt {
   float *m, *v;
   float lr, eps, beta1, beta2;
-  int32_t rule; /* FMX_RULE_SGD, FMX_RULE_ADAGRAD or FMX_RULE_ADAM */
+  int32_t rule; /* FMX_RULE_SGD, FMX_RULE_ADAGRAD or FMX_RULE_ADAM (fmx_afm_step_opt / fmx_afm_stream: FMX_RULE_SIGNADAM too) */
   int32_t step; /* FMX_RULE_ADAM: steps already taken */
 } fmx_mlp_opt_t;
 
@@ -651,6 +651,45 @@ int64_t fmx_afm_workspace_bytes(const fmx_table_t *table, const fmx_afm_t *afm, 
 int fmx_afm_step(const fmx_table_t *table, const fmx_hyper_t *hyper, int32_t rule, const fmx_afm_t *afm, const int32_t *idx,
                  const float *xv, const float *y, int32_t B, float inv_b, void *workspace, int64_t workspace_bytes,
                  float *attn_grad_out, float *loss_out, int32_t *error, fmx_stream_t stream);
+
+/* fmx_afm_step with the attention parameters under a rule of their own, applied inside the fixed-order reduction of the
+ * attention partials: the thread that finishes summing column g of the workgroups' partials applies the rule to (params[g],
+ * m[g], v[g]) and stores them (no further launch, no atomics).  opt: fmx_mlp_opt_t, with m, v flat fp32 device buffers in the
+ * layout of fmx_afm_t.params (t k + 2 t + k floats), 16-byte aligned:
+ *   FMX_RULE_SGD       p -= lr * g                                   (m, v may be null)
+ *   FMX_RULE_SIGNADAM  p -= lr * g / (|g| + eps)                     (m, v may be null; a fresh Adam's first step.  The AFM calls
+ *                                                                    alone take it in fmx_mlp_opt_t; the MLP calls refuse it)
+ *   FMX_RULE_ADAGRAD   torch.optim.Adagrad, G in v                   (m may be null)
+ *   FMX_RULE_ADAM      torch.optim.Adam as fmx_mlp_opt_t states it.  It is dense: every parameter's moments move on every
+ *                      step, a zero gradient (a dead ReLU unit) included
+ * The call is step t = opt->step + 1 of the attention parameters; opt->step is read, never written.  attn_grad_out, loss_out,
+ * error and every table word (moments and bias words included) are bit-identical to fmx_afm_step on the same inputs: the
+ * forward reads the parameters before the step's reduction writes them.
+ * Before anything is launched, each naming this entry point in fmx_last_error_string(): fmx_afm_step's checks; opt null, an
+ * unknown rule, v null under FMX_RULE_ADAGRAD / FMX_RULE_ADAM, m null under FMX_RULE_ADAM, a beta outside [0, 1), step < 0 or
+ * step + 1 beyond int32 (of opt, and of hyper under the tables' FMX_RULE_ADAM): FMX_ERR_ARG; afm->params, m or v not 16-byte
+ * aligned: FMX_ERR_ALIGN; the table and batch size as fmx_sort_occurrences checks them.
+ * Replaces: the body of AFMAdam.fit's batch loop with the model's ONE persistent optimizer (reference afm_adam.py:93,113-118:
+ * forward, loss, backward, optimizer.step) -- SparseAdam's form on the tables, the dense form on the attention parameters. */
+int fmx_afm_step_opt(const fmx_table_t *table, const fmx_hyper_t *hyper, int32_t rule, const fmx_afm_t *afm, const int32_t *idx,
+                     const float *xv, const float *y, int32_t B, float inv_b, void *workspace, int64_t workspace_bytes,
+                     float *attn_grad_out, const fmx_mlp_opt_t *opt, float *loss_out, int32_t *error, fmx_stream_t stream);
+
+/* n_steps AFM steps over a device-resident pool, issued from one call without any host synchronisation: idx_pool [n_pool, B, F],
+ * xv_pool [n_pool, B, F] or null (ones), y_pool [n_pool, B]; step s takes batch s mod n_pool and is step hyper->step + s + 1 of
+ * the tables and opt->step + s + 1 of the attention parameters (both counts are read, never written: the caller advances them
+ * by n_steps).  ADAM's constants of a step are computed on the host in double, once per step.  loss_out [n_steps] or null
+ * receives each step's mean loss; attn_grad_out holds the last step's gradient.  workspace: fmx_afm_workspace_bytes(table, afm,
+ * B) bytes (every batch is sorted on `stream` in front of its step; nothing is sorted ahead).  error [1] or null: set when any
+ * index of any step lies outside its field.
+ * The result is, bit for bit, the one of n_steps calls of fmx_afm_step_opt with both step counts advanced by the caller: rows,
+ * moments, bias words, params, m, v and the per-step losses.  Every argument is checked before the first launch --
+ * fmx_afm_step_opt's checks with step + n_steps within int32, n_pool >= 1, n_steps >= 0 -- and n_steps = 0 launches nothing.
+ * Replaces: AFMAdam.fit's loop over the batches of an epoch (reference afm_adam.py:98-141, with the optimizer of :93). */
+int fmx_afm_stream(const fmx_table_t *table, const fmx_hyper_t *hyper, int32_t rule, const fmx_afm_t *afm, const int32_t *idx_pool,
+                   const float *xv_pool, const float *y_pool, int32_t n_pool, int32_t B, float inv_b, int32_t n_steps, void *workspace,
+                   int64_t workspace_bytes, float *attn_grad_out, const fmx_mlp_opt_t *opt, float *loss_out, int32_t *error,
+                   fmx_stream_t stream);
 
 /* ---- top-K recommendation under the AFM (fmx/recommend.py, AFMAdam.recommend) ----
  * Split the fields into context fields C and item fields I (at least one of each).  A combined sample's pairs are the C x C
