@@ -29,7 +29,8 @@ int check_launch(const char *what);
 
 // ---- launch geometry knobs (waves per workgroup), overridable from the environment for experiments ----
 struct Tune {
-  int wpb_fwd = 2, wpb_upd = 2;  // waves per workgroup (FMX_WPB_FWD / FMX_WPB_UPD: 1, 2 or 4; a 3 x 3 sweep is flat within 1 %)
+  int wpb_fwd = 4, wpb_upd = 2;  // waves per workgroup (FMX_WPB_FWD / FMX_WPB_UPD: 1, 2 or 4).  The forward's first wave evaluates
+                                 // the workgroup's loss epilogues together: 4 (19.85-19.89 us per loop step; 2: 20.24-20.46)
   int sort_e = 0;     // FMX_SORT_E: elements per thread of the bitonic sort (0 = default)
   int inline_fixup = 1;  // FMX_INLINE_FIXUP=0 / fmx_set_option("inline_fixup", 0): partial records are combined by a second
                          // launch (k_fm_fixup) instead of the in-launch hand-off; both give identical bits
@@ -301,6 +302,18 @@ __device__ __forceinline__ float4 fm_bi(float4 s, float4 ss, float &sbi) {
   sbi = (bi.x + bi.y) + (bi.z + bi.w);
 #pragma unroll
   for (int m = 1; m < LPR; m <<= 1) sbi += __shfl_xor(sbi, m);
+  return bi;
+}
+// ... with the exchanges of the LPR lanes by DPP instead of the LDS crossbar: the same operands added in the same order, the
+// same bits (k_fm_forward; the other kernels keep the form above)
+template <int LPR>
+__device__ __forceinline__ float4 fm_bi_dpp(float4 s, float4 ss, float &sbi) {
+  const float4 bi = 0.5f * (s * s - ss);
+  sbi = (bi.x + bi.y) + (bi.z + bi.w);
+  if (LPR > 1) sbi += xor_lane_f<1>(sbi, 0);
+  if (LPR > 2) sbi += xor_lane_f<2>(sbi, 0);
+  if (LPR > 4) sbi += xor_lane_f<4>(sbi, 0);
+  if (LPR > 8) sbi += xor_lane_f<8>(sbi, 0);
   return bi;
 }
 

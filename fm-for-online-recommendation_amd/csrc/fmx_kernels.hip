@@ -92,51 +92,78 @@ struct FwdArgs {
 };
 
 #ifdef FMX_STAMPS  // diagnostic build (tools/forward_stamps.sh): s_memrealtime (100 MHz) of every wave of the LAST k_fm_forward launch
-__device__ unsigned long long g_fwd_stamps[8192 * 6];
-#define FMX_FSTAMP(slot_, dep_)                                                                                     \
+__device__ unsigned long long g_fwd_stamps[8192 * 6];  // one record per sample; lane i stamps sample first_ + i, for i < count_
+#define FMX_FSTAMP_AT(slot_, dep_, first_, count_)                                                                  \
   do {                                                                                                              \
     unsigned long long t_;                                                                                          \
     asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_) : "v"(dep_) : "memory");                      \
-    if (lane == 0 && b < 8192) g_fwd_stamps[(size_t)b * 6 + (slot_)] = t_;                                           \
+    if (lane < (count_) && (first_) + lane < 8192) g_fwd_stamps[(size_t)((first_) + lane) * 6 + (slot_)] = t_;       \
   } while (0)
 #else
-#define FMX_FSTAMP(slot_, dep_) do {} while (0)
+#define FMX_FSTAMP_AT(slot_, dep_, first_, count_) do {} while (0)
 #endif
+#define FMX_FSTAMP(slot_, dep_) FMX_FSTAMP_AT(slot_, dep_, b, (int)exists)  // the wave's own sample
+
+__device__ __forceinline__ float first_lane_f(float v) { return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(v))); }
 
 // The part of the forward pass behind the row gather: field sums (butterfly over the lane groups), bi-interaction, logit,
 // loss and dlogit, stores.  s / ss / fo: this lane's partial sums of e, e*e and of the first-order terms over ITS fields;
 // bias: the bias weight (resolved while the rows were in flight).
+// The loss epilogue (bce_loss_dz: two expf, a log1pf, an IEEE divide, ~100 VALU instructions) is a pure function of one sample's
+// (z, y).  Evaluated by every wave on its lane 0 it takes the issue slots of a whole wave for one useful lane of 64, four waves per
+// SIMD at once; instead the waves of a workgroup leave (fo, sbi, y) in LDS and, behind ONE barrier, the workgroup's first wave
+// evaluates all of them, sample i on lane i: the same function of the same operands -- the same bits -- for a quarter of the
+// instruction issue at four waves per workgroup.  Without a loss (the DeepFM loop) every wave stores its own three words.
 template <int LPR>
-__device__ __forceinline__ void forward_finish(const FwdArgs &a, const int b, const int lane, float4 s, float4 ss, float fo, bool bad,
-                                               const float y_early, const float bias) {
+__device__ __forceinline__ void forward_finish(const FwdArgs &a, int b, const bool exists, const int lane, float4 s, float4 ss, float fo,
+                                               bool bad, float y, const float bias) {
   const int q = lane % LPR;
   const int kp = LPR * 4;
-  if (bad && a.out.error) *a.out.error = 1;
+  if (bad && a.out.error) *a.out.error = 1;  // (a wave that repeats the last sample repeats its verdict)
 
   fm_field_sums<LPR>(s, ss, fo, lane);
   float sbi;
-  const float4 bi = fm_bi<LPR>(s, ss, sbi);
+  const float4 bi = fm_bi_dpp<LPR>(s, ss, sbi);
   // fo: lanes with q != 0 hold the sum of zeros; take the q == 0 value
-  fo = __shfl(fo, 0);
+  fo = first_lane_f(fo);
   FMX_FSTAMP(3, sbi);
 
-  if (lane < LPR) {
+  if (exists && lane < LPR) {
     if (a.out.S) *reinterpret_cast<float4 *>(a.out.S + (size_t)b * a.ldS + 4 * q) = s;
     if (a.out.bi) *reinterpret_cast<float4 *>(a.out.bi + (size_t)b * kp + 4 * q) = bi;
   }
-  if (lane == 0) {
+  int n = exists ? 1 : 0;  // lanes 0 .. n - 1 finish samples b .. b + n - 1
+  if (a.loss_kind != FMX_LOSS_NONE && blockDim.x > WAVE) {  // (uniform over the launch)
+    __shared__ float sh[3][4];
+    const int w = threadIdx.x >> 6, wpb = blockDim.x >> 6;
+    if (lane == 0) {
+      sh[0][w] = fo;
+      sh[1][w] = sbi;
+      sh[2][w] = y;
+    }
+    __syncthreads();
+    if (w != 0) return;
+    b = blockIdx.x * wpb;  // (this wave's own sample: it exists)
+    n = min(wpb, a.B - b);
+    const int l = lane < n ? lane : 0;
+    fo = sh[0][l];
+    sbi = sh[1][l];
+    y = sh[2][l];
+  }
+  if (lane < n) {
+    const int bl = b + lane;
     const float z = fo + sbi + bias;
-    if (a.out.sfirst) a.out.sfirst[b] = fo;
-    if (a.out.sbi) a.out.sbi[b] = sbi;
-    if (a.out.logit) a.out.logit[b] = z;
+    if (a.out.sfirst) a.out.sfirst[bl] = fo;
+    if (a.out.sbi) a.out.sbi[bl] = sbi;
+    if (a.out.logit) a.out.logit[bl] = z;
     if (a.loss_kind != FMX_LOSS_NONE) {
       float loss, dz;
-      bce_loss_dz(a.loss_kind, z, y_early, a.inv_b, loss, dz);
-      FMX_FSTAMP(4, dz);
-      if (a.out.loss) a.out.loss[(size_t)b * a.ld1] = loss;
-      if (a.out.dz) a.out.dz[(size_t)b * a.ld1] = dz;
+      bce_loss_dz(a.loss_kind, z, y, a.inv_b, loss, dz);
+      FMX_FSTAMP_AT(4, dz, b, n);
+      if (a.out.loss) a.out.loss[(size_t)bl * a.ld1] = loss;
+      if (a.out.dz) a.out.dz[(size_t)bl * a.ld1] = dz;
     }
-    FMX_FSTAMP(5, z);
+    FMX_FSTAMP_AT(5, z, b, n);
   }
 }
 
@@ -156,8 +183,10 @@ constexpr int64_t ROW_ABSENT = int64_t(1) << 62;  // set in a resolved row: the 
 // MAPPED (tables whose fields are pieces of index columns; the generic field loop only): field f reads column fcols[f], holds
 // the indices [fbase[f], fbase[f] + rows) of it, and an index outside belongs to another piece: no contribution, no error.
 // HAS_X: xv is not null (without values every x is 1 and nothing is loaded for it).
+// exists (wave-uniform): false for a wave behind the batch's last sample, which repeats that sample for the workgroup's barrier and
+// stores nothing.
 template <int LPR, int LAYOUT, int NPASS, bool MAPPED, bool HAS_X>
-__device__ __forceinline__ void forward_sample(const FwdArgs &a, const int b, const int lane) {
+__device__ __forceinline__ void forward_sample(const FwdArgs &a, const int b, const bool exists, const int lane) {
   constexpr int SLOTS = WAVE / LPR;
   constexpr int NP = NPASS > 0 ? NPASS : 1;
   constexpr int NW = NPASS > 0 ? (NP * SLOTS + WAVE - 1) / WAVE : 1;  // windows of WAVE fields
@@ -250,20 +279,21 @@ __device__ __forceinline__ void forward_sample(const FwdArgs &a, const int b, co
         ss = ss + e * e;
         fo += f1;
       }
-      if (live[p] && a.out.first && q == 0) a.out.first[(size_t)b * a.F + (it * NP + p) * SLOTS + slot] = f1;
+      if (exists && live[p] && a.out.first && q == 0) a.out.first[(size_t)b * a.F + (it * NP + p) * SLOTS + slot] = f1;
     }
     FMX_FSTAMP(2, s.x + ss.x + fo);  // (every row of the pass set arrived and added)
   }
-  forward_finish<LPR>(a, b, lane, s, ss, fo, bad, y_early, bias);
+  forward_finish<LPR>(a, b, exists, lane, s, ss, fo, bad, y_early, bias);
 }
 
 template <int LPR, int LAYOUT, int NPASS, bool MAPPED = false>
 __global__ __launch_bounds__(256) void k_fm_forward(FwdArgs a) {
   __builtin_amdgcn_s_setprio(3);  // ahead of the side-stream sort's waves at the CU's instruction arbiter
-  const int b = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
-  if (b >= a.B) return;  // wave-uniform
-  if (a.xv) forward_sample<LPR, LAYOUT, NPASS, MAPPED, true>(a, b, threadIdx.x & 63);
-  else forward_sample<LPR, LAYOUT, NPASS, MAPPED, false>(a, b, threadIdx.x & 63);
+  int b = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+  const bool exists = b < a.B;  // wave-uniform
+  if (!exists) b = a.B - 1;     // (forward_finish has a workgroup barrier: the wave goes along and stores nothing)
+  if (a.xv) forward_sample<LPR, LAYOUT, NPASS, MAPPED, true>(a, b, exists, threadIdx.x & 63);
+  else forward_sample<LPR, LAYOUT, NPASS, MAPPED, false>(a, b, exists, threadIdx.x & 63);
 }
 
 // ------------------------------------------------------------------------------------------------------------
@@ -1885,7 +1915,7 @@ Tune &tune() {
     if (const char *e = getenv("FMX_SORT_CHUNKED")) x.sort_chunked = atoi(e);
     if (const char *e = getenv("FMX_MLP_CHAIN")) x.mlp_chain = atoi(e);
     auto ok = [](int v) { return v == 1 || v == 2 || v == 4; };
-    if (!ok(x.wpb_fwd)) x.wpb_fwd = 2;
+    if (!ok(x.wpb_fwd)) x.wpb_fwd = 4;
     if (!ok(x.wpb_upd)) x.wpb_upd = 2;
     return x;
   }();
