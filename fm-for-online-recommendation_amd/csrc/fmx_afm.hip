@@ -18,6 +18,10 @@
 //   k_afm_reduce_opt<RULE> the same sums (afm_reduce_column); the thread that finishes column g also applies the attention
 //                         parameters' rule to (params[g], m[g], v[g]) and stores them (fmx_afm_step_opt, fmx_afm_stream).
 //
+//   k_afm_online<KP>      one workgroup of 8 waves walks a stream one sample at a time (fmx_afm_online_run): k_afm's sample spread over
+//                         the waves, the table update and the attention rule in the same launch; the bits of B = 1 steps (its own
+//                         comment further down).
+//
 // No float is accumulated with atomics and every sum has one fixed order that depends on (B, F, t, k) alone: results are
 // bit-identical run to run.  The table update between the two launches is fmx_fm_update_occ (fmx_kernels.hip).
 
@@ -95,7 +99,7 @@ __device__ __forceinline__ float wave_max(float v) {
 }
 
 // the next tile: pair rows [i0, i1) holding n <= AFM_TILE pairs (a row has F - 1 - i <= 63 pairs: at least one row fits)
-__device__ __forceinline__ int next_tile(int F, int i0, int &n) {
+__host__ __device__ __forceinline__ int next_tile(int F, int i0, int &n) {
   int i1 = i0;
   n = 0;
   while (i1 < F - 1 && n + (F - 1 - i1) <= AFM_TILE) {
@@ -115,18 +119,18 @@ __device__ __forceinline__ void tile_pair(int F, int i0, int l, int &i, int &j) 
   j = i + 1 + l;
 }
 
-// the attention parameters into LDS for the whole launch, W rows and p padded to kp with zeros
+// the attention parameters into LDS for the whole launch, W rows and p padded to kp with zeros (thread `lane` of `nt`)
 template <int KP>
-__device__ __forceinline__ void stage_params(float *sm, const AfmLds &L, const float *params, int k, int t, int lane) {
-  for (int i = lane; i < t * KP; i += WAVE) {
+__device__ __forceinline__ void stage_params(float *sm, const AfmLds &L, const float *params, int k, int t, int lane, int nt = WAVE) {
+  for (int i = lane; i < t * KP; i += nt) {
     const int u = i / KP, d = i - u * KP;
     sm[L.W + i] = d < k ? params[u * k + d] : 0.f;
   }
-  for (int u = lane; u < t; u += WAVE) {
+  for (int u = lane; u < t; u += nt) {
     sm[L.bW + u] = params[t * k + u];
     sm[L.h + u] = params[t * k + t + u];
   }
-  for (int d = lane; d < KP; d += WAVE) sm[L.p + d] = d < k ? params[t * k + 2 * t + d] : 0.f;
+  for (int d = lane; d < KP; d += nt) sm[L.p + d] = d < k ? params[t * k + 2 * t + d] : 0.f;
 }
 
 // field f of sample b (full-width rows [B, F]): x V[row] (kp floats) to dst, returns x w[row]; an index outside its field is
@@ -172,13 +176,14 @@ __device__ __forceinline__ void pair_terms(const float *sm, const AfmLds &L, int
   }
 }
 
-// every pair's s and p . q of the F embeddings in LDS, tile by tile, into L.s / L.r in pair order
+// every pair's s and p . q of the F embeddings in LDS, tile by tile, into L.s / L.r in pair order; wave `wv` of `nw` takes the
+// tiles wv, wv + nw, ... (a pair's terms depend on nothing but the pair)
 template <int KP>
-__device__ __forceinline__ void score_pairs(float *sm, const AfmLds &L, int F, int t, int lane) {
-  for (int i0 = 0, pb = 0; i0 < F - 1;) {
+__device__ __forceinline__ void score_pairs(float *sm, const AfmLds &L, int F, int t, int lane, int wv = 0, int nw = 1) {
+  for (int i0 = 0, pb = 0, tile = 0; i0 < F - 1; ++tile) {
     int n;
     const int i1 = next_tile(F, i0, n);
-    if (lane < n) {
+    if (tile % nw == wv && lane < n) {
       int i, j;
       tile_pair(F, i0, lane, i, j);
       float q[KP], r, s;
@@ -188,6 +193,83 @@ __device__ __forceinline__ void score_pairs(float *sm, const AfmLds &L, int F, i
     }
     pb += n;
     i0 = i1;
+  }
+}
+
+// where one tile's backward terms lie in LDS: q and dL/dq [64, kp], the unit coefficients dL/dz and dL/dh's terms [64, t], dL/dr [64]
+struct AfmTileBuf {
+  int q, c, co, hr, ga;
+};
+
+// the backward of pair (i, j), slot `lane` of its tile: ex = exp(s_ij - max), Z the softmax's sum, g = dlogit, att = p . sum a q.
+// The pair's terms are recomputed and q, dL/dq and the per-unit coefficients go to the tile's buffers T
+template <int KP>
+__device__ __forceinline__ void pair_backward(float *sm, const AfmLds &L, const AfmTileBuf &T, int t, int i, int j, int lane, float ex,
+                                              float Z, float g, float att) {
+  float q[KP], r, s;
+  pair_terms<KP>(sm, L, t, i, j, q, r, s);
+  const float ai = ex / Z;
+  const float ga = g * ai;              // dL/dr_ij
+  const float delta = ga * (r - att);   // dL/ds_ij
+  float dq[KP];
+#pragma unroll
+  for (int d = 0; d < KP; ++d) dq[d] = ga * sm[L.p + d];
+  for (int u = 0; u < t; ++u) {
+    float z = sm[L.bW + u];
+#pragma unroll
+    for (int d = 0; d < KP; ++d) z = fmaf(sm[L.W + u * KP + d], q[d], z);
+    const float co = z > 0.f ? delta * sm[L.h + u] : 0.f;  // dL/dz_u
+    sm[T.co + lane * t + u] = co;
+    sm[T.hr + lane * t + u] = delta * fmaxf(z, 0.f);       // dL/dh_u's term
+#pragma unroll
+    for (int d = 0; d < KP; ++d) dq[d] = fmaf(co, sm[L.W + u * KP + d], dq[d]);
+  }
+#pragma unroll
+  for (int d = 0; d < KP; d += 4) {
+    *reinterpret_cast<float4 *>(sm + T.q + lane * KP + d) = float4{q[d], q[d + 1], q[d + 2], q[d + 3]};
+    *reinterpret_cast<float4 *>(sm + T.c + lane * KP + d) = float4{dq[d], dq[d + 1], dq[d + 2], dq[d + 3]};
+  }
+  sm[T.ga + lane] = ga;
+}
+
+// the tile of pair rows [i0, i1) (n pairs, its terms in T) added into the accumulators in pair order; thread `tid` of `nt` owns the
+// accumulators tid, tid + nt, ... of each kind, so an accumulator's terms arrive in the same order whatever nt is
+template <int KP>
+__device__ __forceinline__ void add_tile(float *sm, const AfmLds &L, const AfmTileBuf &T, int F, int t, int i0, int i1, int n, int tid,
+                                         int nt) {
+  for (int l = tid; l < t * KP; l += nt) {  // dW[u][d] += sum_pairs dL/dz_u q_d
+    const int u = l / KP, d = l - u * KP;
+    float acc = sm[L.aW + l];
+    for (int m = 0; m < n; ++m) acc = fmaf(sm[T.co + m * t + u], sm[T.q + m * KP + d], acc);
+    sm[L.aW + l] = acc;
+  }
+  for (int u = tid; u < t; u += nt) {
+    float ab = sm[L.ab + u], ah = sm[L.ah + u];
+    for (int m = 0; m < n; ++m) {
+      ab += sm[T.co + m * t + u];
+      ah += sm[T.hr + m * t + u];
+    }
+    sm[L.ab + u] = ab;
+    sm[L.ah + u] = ah;
+  }
+  for (int d = tid; d < KP; d += nt) {
+    float ap = sm[L.ap + d];
+    for (int m = 0; m < n; ++m) ap = fmaf(sm[T.ga + m], sm[T.q + m * KP + d], ap);
+    sm[L.ap + d] = ap;
+  }
+  // dL/de_f[d]: the pairs (i, f), i < f, then (f, j), j > f -- the pair order, whatever the tiling
+  for (int l = tid; l < F * KP; l += nt) {
+    const int f = l / KP, d = l - f * KP;
+    float acc = sm[L.Ea + l];
+    int lb = 0;  // tile-local index of row i's first pair
+    for (int i = i0; i < i1 && i <= f; lb += F - 1 - i, ++i) {
+      if (i < f) {
+        acc = fmaf(sm[T.c + (lb + f - i - 1) * KP + d], sm[L.e + i * KP + d], acc);
+      } else {
+        for (int jj = i + 1; jj < F; ++jj) acc = fmaf(sm[T.c + (lb + jj - i - 1) * KP + d], sm[L.e + jj * KP + d], acc);
+      }
+    }
+    sm[L.Ea + l] = acc;
   }
 }
 
@@ -247,72 +329,17 @@ __global__ __launch_bounds__(64) void k_afm(AfmArgs a) {
     // ---- pass B: recompute every tile's pairs, then add the tile into the owned accumulators in pair order ----
     for (int l = lane; l < F * KP; l += WAVE) sm[L.Ea + l] = 0.f;
     __syncthreads();
+    const AfmTileBuf T = {L.q, L.c, L.co, L.hr, L.ga};
     for (int i0 = 0, pb = 0; i0 < F - 1;) {
       int n;
       const int i1 = next_tile(F, i0, n);
       if (lane < n) {
         int i, j;
         tile_pair(F, i0, lane, i, j);
-        float q[KP], r, s;
-        pair_terms<KP>(sm, L, t, i, j, q, r, s);
-        const float ai = sm[L.s + pb + lane] / Z;
-        const float ga = g * ai;              // dL/dr_ij
-        const float delta = ga * (r - att);   // dL/ds_ij
-        float dq[KP];
-#pragma unroll
-        for (int d = 0; d < KP; ++d) dq[d] = ga * sm[L.p + d];
-        for (int u = 0; u < t; ++u) {
-          float z = sm[L.bW + u];
-#pragma unroll
-          for (int d = 0; d < KP; ++d) z = fmaf(sm[L.W + u * KP + d], q[d], z);
-          const float co = z > 0.f ? delta * sm[L.h + u] : 0.f;  // dL/dz_u
-          sm[L.co + lane * t + u] = co;
-          sm[L.hr + lane * t + u] = delta * fmaxf(z, 0.f);       // dL/dh_u's term
-#pragma unroll
-          for (int d = 0; d < KP; ++d) dq[d] = fmaf(co, sm[L.W + u * KP + d], dq[d]);
-        }
-#pragma unroll
-        for (int d = 0; d < KP; d += 4) {
-          *reinterpret_cast<float4 *>(sm + L.q + lane * KP + d) = float4{q[d], q[d + 1], q[d + 2], q[d + 3]};
-          *reinterpret_cast<float4 *>(sm + L.c + lane * KP + d) = float4{dq[d], dq[d + 1], dq[d + 2], dq[d + 3]};
-        }
-        sm[L.ga + lane] = ga;
+        pair_backward<KP>(sm, L, T, t, i, j, lane, sm[L.s + pb + lane], Z, g, att);
       }
       __syncthreads();
-      for (int l = lane; l < t * KP; l += WAVE) {  // dW[u][d] += sum_pairs dL/dz_u q_d
-        const int u = l / KP, d = l - u * KP;
-        float acc = sm[L.aW + l];
-        for (int m = 0; m < n; ++m) acc = fmaf(sm[L.co + m * t + u], sm[L.q + m * KP + d], acc);
-        sm[L.aW + l] = acc;
-      }
-      for (int u = lane; u < t; u += WAVE) {
-        float ab = sm[L.ab + u], ah = sm[L.ah + u];
-        for (int m = 0; m < n; ++m) {
-          ab += sm[L.co + m * t + u];
-          ah += sm[L.hr + m * t + u];
-        }
-        sm[L.ab + u] = ab;
-        sm[L.ah + u] = ah;
-      }
-      for (int d = lane; d < KP; d += WAVE) {
-        float ap = sm[L.ap + d];
-        for (int m = 0; m < n; ++m) ap = fmaf(sm[L.ga + m], sm[L.q + m * KP + d], ap);
-        sm[L.ap + d] = ap;
-      }
-      // dL/de_f[d]: the pairs (i, f), i < f, then (f, j), j > f -- the pair order, whatever the tiling
-      for (int l = lane; l < F * KP; l += WAVE) {
-        const int f = l / KP, d = l - f * KP;
-        float acc = sm[L.Ea + l];
-        int lb = 0;  // tile-local index of row i's first pair
-        for (int i = i0; i < i1 && i <= f; lb += F - 1 - i, ++i) {
-          if (i < f) {
-            acc = fmaf(sm[L.c + (lb + f - i - 1) * KP + d], sm[L.e + i * KP + d], acc);
-          } else {
-            for (int jj = i + 1; jj < F; ++jj) acc = fmaf(sm[L.c + (lb + jj - i - 1) * KP + d], sm[L.e + jj * KP + d], acc);
-          }
-        }
-        sm[L.Ea + l] = acc;
-      }
+      add_tile<KP>(sm, L, T, F, t, i0, i1, n, lane, WAVE);
       __syncthreads();
       pb += n;
       i0 = i1;
@@ -378,6 +405,12 @@ struct AfmOptArgs {
   float *params, *m, *v;
   fmx_hyper_t h;
 };
+// the attention parameters' rule on one column: (p, m, v) by its gradient s
+template <int RULE>
+__device__ __forceinline__ void afm_opt_column(float &p, float &m, float &v, float s, const fmx_hyper_t &h) {
+  if (RULE == FMX_RULE_ADAGRAD || RULE == FMX_RULE_ADAM) moments_upd<RULE>(p, m, v, s, h);
+  else p = apply_rule<RULE>(p, s, h);
+}
 template <int RULE>
 __global__ __launch_bounds__(256) void k_afm_reduce_opt(const float *part, int n, int G, float *grad, AfmOptArgs o) {
   __shared__ float sm[4][64];
@@ -392,13 +425,9 @@ __global__ __launch_bounds__(256) void k_afm_reduce_opt(const float *part, int n
   const float s = afm_reduce_column(part, n, G, sm);
   if (!mine) return;
   grad[g] = s;
-  if (RULE == FMX_RULE_ADAGRAD || RULE == FMX_RULE_ADAM) {
-    moments_upd<RULE>(p, m, v, s, o.h);
-    o.v[g] = v;
-    if (RULE == FMX_RULE_ADAM) o.m[g] = m;
-  } else {
-    p = apply_rule<RULE>(p, s, o.h);
-  }
+  afm_opt_column<RULE>(p, m, v, s, o.h);
+  if (RULE == FMX_RULE_ADAGRAD || RULE == FMX_RULE_ADAM) o.v[g] = v;
+  if (RULE == FMX_RULE_ADAM) o.m[g] = m;
   o.params[g] = p;
 }
 
@@ -453,6 +482,404 @@ __global__ __launch_bounds__(64) void k_afm_side(AfmSideArgs a) {
     float *Eb = a.E + (size_t)b * n * KP;
     for (int l = lane * 4; l < n * KP; l += WAVE * 4) *reinterpret_cast<float4 *>(Eb + l) = *reinterpret_cast<const float4 *>(sm + L.e + l);
     __syncthreads();  // the next row's gather overwrites e
+  }
+}
+
+// ------------------------------------------------------------------------------------------------------------
+// k_afm_online: the online predict-then-fit loop of the AFM on a device-resident stream (fmx_afm_online_run)
+// ------------------------------------------------------------------------------------------------------------
+// Steps of one sample are sequential (sample i + 1 reads the rows and the attention parameters sample i wrote), so ONE workgroup
+// walks the stream and the work INSIDE a sample is spread over its AFM_ONL_WAVES waves; every float is the one fmx_afm_step_opt
+// gives at B = 1, inv_b = 1 (k_afm on one sample, k_fm_update_occ on F runs of one occurrence, k_afm_reduce_opt over one partial):
+//   gather   LPR = kp / 4 threads per field: the row by sc1 loads (the previous sample may have written it) into registers, where
+//            it stays for the update; e = x V and x w to LDS
+//   pass A   the pair tiles dealt over the waves (score_pairs)
+//   softmax  every wave evaluates k_afm's one-wave max and sums itself (the same lanes, the same order) and so holds the logit,
+//            the loss and dlogit without a broadcast; the exponentials are shared out over all threads in between
+//   pass B   rounds of nb tiles: wave w recomputes tile w of the round into tile buffer w (pair_backward), then every thread adds
+//            the round's tiles, in tile order, into the accumulators it owns (add_tile: the t kp + 2 t + kp attention entries and
+//            the F kp entries of dL/de over all the threads instead of k_afm's 64 lanes; an accumulator's terms still arrive in
+//            pair order)
+//   update   the attention parameters live in LDS for the whole stream (their moments too where they fit, else in global memory,
+//            touched by the owning thread alone): column g's owner applies the rule to 0 + its accumulator -- afm_reduce_column
+//            over ONE workgroup's partial, which turns a -0 into +0 -- and the threads that hold the rows apply the tables' rule
+//            to dL/dV = 0 + x dL/de, dL/dw = 0 + x dlogit (update_body's run of one occurrence); thread 0 steps the bias words,
+//            which stay in LDS.  The stores are acknowledged (vmcnt(0)) and a barrier passed before the next sample's gather.
+// ADAM's constants of sample i -- step hyper.step + i + 1 of the tables, opt.step + i + 1 of the attention parameters -- are
+// derived by one thread per sample with adam_consts, the function the host uses for a launch (same bits), as in k_online_mlp.
+constexpr int AFM_ONL_WAVES = 8, AFM_ONL_THREADS = AFM_ONL_WAVES * WAVE;  // 2 waves per SIMD: 256 VGPRs each (pair_backward at
+                                                                          // kp = 64 holds q and dL/dq: 128 registers)
+constexpr int AFM_LDS_BYTES = 160 * 1024;
+
+// LDS carving in floats: k_afm's sections (L) with the accumulators [ dL/de | dW | db | dh | dp ] in one run, the exponentials,
+// the fields' x w, (bias words | ADAM's constants | the index flag), nb tile buffers and, when they fit, the moments
+struct AfmOnlLds {
+  AfmLds L;
+  int x, fo, misc, acc_len, tile0, tile_sz, m, v, total;
+};
+constexpr int ONL_KC = 4, ONL_FLAG = 12, ONL_MISC = 16;  // offsets inside misc
+__host__ __device__ inline int afm_tile_floats(int kp, int t) { return 2 * AFM_TILE * kp + 2 * r4(AFM_TILE * t) + AFM_TILE; }
+__host__ __device__ inline AfmOnlLds afm_online_lds(int F, int kp, int t, int G, int nb, bool mom) {
+  AfmOnlLds O;
+  AfmLds &L = O.L;
+  const int P = F * (F - 1) / 2;
+  int o = 0;
+  L.e = o; o += F * kp;
+  L.W = o; o += t * kp;
+  L.bW = o; o += r4(t);
+  L.h = o; o += r4(t);
+  L.p = o; o += kp;
+  L.s = o; o += r4(P);
+  L.r = o; o += r4(P);
+  O.x = o; o += r4(P);
+  L.Ea = o; o += F * kp;
+  L.aW = o; o += t * kp;
+  L.ab = o; o += r4(t);
+  L.ah = o; o += r4(t);
+  L.ap = o; o += kp;
+  O.acc_len = o - L.Ea;
+  O.fo = o; o += WAVE;
+  O.misc = o; o += ONL_MISC;
+  O.tile0 = o;
+  O.tile_sz = afm_tile_floats(kp, t);
+  o += nb * O.tile_sz;
+  L.q = L.c = L.co = L.hr = L.ga = O.tile0;  // (buffer 0; tile_buf gives each buffer's sections)
+  O.m = O.v = o;
+  if (mom) {
+    O.m = o; o += r4(G);
+    O.v = o; o += r4(G);
+  }
+  O.total = L.total = o;
+  return O;
+}
+__device__ __forceinline__ AfmTileBuf tile_buf(const AfmOnlLds &O, int kp, int t, int b) {
+  AfmTileBuf T;
+  T.q = O.tile0 + b * O.tile_sz;
+  T.c = T.q + AFM_TILE * kp;
+  T.co = T.c + AFM_TILE * kp;
+  T.hr = T.co + r4(AFM_TILE * t);
+  T.ga = T.hr + r4(AFM_TILE * t);
+  return T;
+}
+// the pair tiles of a sample
+inline int afm_n_tiles(int F) {
+  int nt = 0;
+  for (int i0 = 0, n; i0 < F - 1; ++nt) i0 = next_tile(F, i0, n);
+  return nt;
+}
+// tile buffers of the one-workgroup form at this shape: as many as waves, tiles and the LDS allow; the moments go to LDS too when
+// that costs no buffer.  0: the form is not used -- not even two tiles' buffers fit beside the sample, so the pair work could not
+// be spread over waves
+inline int afm_online_buffers(int F, int kp, int t, int G, bool want_mom, bool &mom) {
+  const int tiles = afm_n_tiles(F), most = tiles < AFM_ONL_WAVES ? tiles : AFM_ONL_WAVES, least = tiles < 2 ? tiles : 2;
+  auto fits = [&](int nb, bool mo) { return (size_t)afm_online_lds(F, kp, t, G, nb, mo).total * 4 <= (size_t)AFM_LDS_BYTES; };
+  mom = false;
+  int nb = most;
+  while (nb >= least && !fits(nb, false)) --nb;
+  if (nb < least) return 0;
+  mom = want_mom && fits(nb, true);
+  return nb;
+}
+
+struct AfmOnlArgs {
+  float *rows;
+  const int64_t *foff;
+  float *bias;
+  const int32_t *idx;  // [N, F]
+  const float *xv;     // [N, F] or null
+  const float *y;      // [N]
+  float *params, *m, *v;  // the attention parameters and their moments (m, v: as the rule needs them)
+  float *grad;            // [G] the last sample's attention gradient
+  float *logit, *loss;    // [N] each or null
+  int32_t *error;
+  fmx_hyper_t h;  // the tables' (alpha holds 1 / alpha); ADAM: lr, beta1, beta2, step as the caller gave them
+  float o_lr, o_eps, o_beta1, o_beta2;  // the attention parameters' (fmx_mlp_opt_t)
+  int32_t o_rule, o_step;
+  int32_t N, F, k, t, stride, zoff, rule, G, nb, mom_lds;
+};
+
+// the tables' rule is a workgroup-uniform run-time switch around the row helpers (a template parameter would multiply the five
+// kp instantiations by five for a few instructions per sample)
+__device__ __forceinline__ RowRegs onl_load_row(int rule, const float *rp, int q, int kp, int zoff) {
+  switch (rule) {
+    case FMX_RULE_FTRL: return load_row_sc1<FMX_LAYOUT_FTRL, FMX_RULE_FTRL>(rp, q, kp, zoff);
+    case FMX_RULE_ADAGRAD: return load_row_sc1<FMX_LAYOUT_MOMENTS, FMX_RULE_ADAGRAD>(rp, q, kp, zoff);
+    case FMX_RULE_ADAM: return load_row_sc1<FMX_LAYOUT_MOMENTS, FMX_RULE_ADAM>(rp, q, kp, zoff);
+    default: return load_row_sc1<FMX_LAYOUT_WEIGHTS, FMX_RULE_SGD>(rp, q, kp, zoff);
+  }
+}
+__device__ __forceinline__ void onl_update_row(int rule, float *rp, int q, int kp, int zoff, const RowRegs &r, float4 cV, float cw,
+                                               const fmx_hyper_t &h) {
+  const float4 cA = splat(0.f);
+  switch (rule) {
+    case FMX_RULE_SIGNADAM: update_row<FMX_LAYOUT_WEIGHTS, FMX_RULE_SIGNADAM>(rp, q, kp, zoff, r, cV, cA, cw, h); break;
+    case FMX_RULE_SGD: update_row<FMX_LAYOUT_WEIGHTS, FMX_RULE_SGD>(rp, q, kp, zoff, r, cV, cA, cw, h); break;
+    case FMX_RULE_FTRL: update_row<FMX_LAYOUT_FTRL, FMX_RULE_FTRL>(rp, q, kp, zoff, r, cV, cA, cw, h); break;
+    case FMX_RULE_ADAGRAD: update_row<FMX_LAYOUT_MOMENTS, FMX_RULE_ADAGRAD>(rp, q, kp, zoff, r, cV, cA, cw, h); break;
+    default: update_row<FMX_LAYOUT_MOMENTS, FMX_RULE_ADAM>(rp, q, kp, zoff, r, cV, cA, cw, h); break;
+  }
+}
+__device__ __forceinline__ void onl_bias_step(int rule, float &b0, float &b1, float &b2, float g, const fmx_hyper_t &h) {
+  switch (rule) {
+    case FMX_RULE_SIGNADAM: bias_step<FMX_LAYOUT_WEIGHTS, FMX_RULE_SIGNADAM>(b0, b1, b2, g, h); break;
+    case FMX_RULE_SGD: bias_step<FMX_LAYOUT_WEIGHTS, FMX_RULE_SGD>(b0, b1, b2, g, h); break;
+    case FMX_RULE_FTRL: bias_step<FMX_LAYOUT_FTRL, FMX_RULE_FTRL>(b0, b1, b2, g, h); break;
+    case FMX_RULE_ADAGRAD: bias_step<FMX_LAYOUT_MOMENTS, FMX_RULE_ADAGRAD>(b0, b1, b2, g, h); break;
+    default: bias_step<FMX_LAYOUT_MOMENTS, FMX_RULE_ADAM>(b0, b1, b2, g, h); break;
+  }
+}
+// column g of [ W (t x k) | b | h | p ] -> its offset from L.W / L.aW's section starts (W rows are padded to kp in LDS)
+__device__ __forceinline__ void onl_column(const AfmLds &L, int g, int k, int t, int kp, int &par, int &acc) {
+  if (g < t * k) {
+    const int u = g / k, d = g - u * k;
+    par = L.W + u * kp + d;
+    acc = L.aW + u * kp + d;
+  } else if (g < t * k + t) {
+    par = L.bW + (g - t * k);
+    acc = L.ab + (g - t * k);
+  } else if (g < t * k + 2 * t) {
+    par = L.h + (g - t * k - t);
+    acc = L.ah + (g - t * k - t);
+  } else {
+    par = L.p + (g - t * k - 2 * t);
+    acc = L.ap + (g - t * k - 2 * t);
+  }
+}
+
+template <int KP>
+__global__ __launch_bounds__(AFM_ONL_THREADS) void k_afm_online(AfmOnlArgs a) {
+  constexpr int NT = AFM_ONL_THREADS, NW = AFM_ONL_WAVES, LPR = KP / 4;
+  constexpr int NP = (AFM_MAX_F * LPR + NT - 1) / NT;  // rows a thread holds (kp = 64: 64 fields x 16 threads over 512)
+  extern __shared__ float4 lds4[];
+  float *sm = reinterpret_cast<float *>(lds4);
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const int F = a.F, k = a.k, t = a.t, P = F * (F - 1) / 2, G = a.G, nb = a.nb;
+  const AfmOnlLds O = afm_online_lds(F, KP, t, G, nb, a.mom_lds != 0);
+  const AfmLds &L = O.L;
+  const bool ftrl = a.rule == FMX_RULE_FTRL, mom_rule = a.rule == FMX_RULE_ADAGRAD || a.rule == FMX_RULE_ADAM;
+  const bool o_v = a.o_rule == FMX_RULE_ADAGRAD || a.o_rule == FMX_RULE_ADAM, o_m = a.o_rule == FMX_RULE_ADAM;
+
+  stage_params<KP>(sm, L, a.params, k, t, tid, NT);
+  if (tid < WAVE) sm[O.fo + tid] = 0.f;
+  if (tid < ONL_MISC) sm[O.misc + tid] = 0.f;
+  __syncthreads();
+  if (tid == 0) {
+    sm[O.misc] = a.bias[0];
+    if (ftrl || mom_rule) sm[O.misc + 1] = a.bias[1];
+    if (mom_rule) sm[O.misc + 2] = a.bias[2];
+  }
+  // the moments: in LDS for the whole stream, or left in global memory (the same code through a generic pointer)
+  float *mm = a.mom_lds ? sm + O.m : a.m, *vv = a.mom_lds ? sm + O.v : a.v;
+  if (a.mom_lds) {
+    for (int g = tid; g < G; g += NT) {
+      if (o_m) mm[g] = a.m[g];
+      if (o_v) vv[g] = a.v[g];
+    }
+  }
+
+  // the rows this thread gathers and updates: row rr = tid + p NT is lanes q of field f
+  int fld[NP], qq[NP];
+  int64_t lo[NP];
+  uint32_t vocab[NP];
+  bool live[NP];
+#pragma unroll
+  for (int p = 0; p < NP; ++p) {
+    const int rr = tid + p * NT;
+    fld[p] = rr / LPR;
+    qq[p] = rr - fld[p] * LPR;
+    live[p] = fld[p] < F;
+    lo[p] = live[p] ? a.foff[fld[p]] : 0;
+    vocab[p] = live[p] ? (uint32_t)(a.foff[fld[p] + 1] - lo[p]) : 0u;
+  }
+  uint32_t li_n[NP];
+  float x_n[NP], y_n = 0.f;
+  // branch-free (k_fm_online): beyond the stream or the last field the loads read element 0 and are dropped
+  const float *xsrc = a.xv ? a.xv : reinterpret_cast<const float *>(a.idx);
+  const bool has_x = a.xv != nullptr;
+  auto fetch_inputs = [&](int i) {
+    const bool in = i < a.N;
+    uint32_t l_[NP];
+    float x_[NP];
+#pragma unroll
+    for (int p = 0; p < NP; ++p) {
+      const size_t o = (live[p] && in) ? (size_t)i * F + fld[p] : (size_t)0;
+      l_[p] = (uint32_t)a.idx[o];
+      x_[p] = xsrc[o];
+    }
+    const float yy = a.y[in ? i : 0];
+#pragma unroll
+    for (int p = 0; p < NP; ++p) {
+      li_n[p] = (live[p] && in) ? l_[p] : 0u;
+      x_n[p] = (has_x && live[p] && in) ? x_[p] : 1.f;
+    }
+    y_n = in ? yy : 0.f;
+  };
+  fetch_inputs(0);
+  bool bad = false;
+  __syncthreads();
+
+  for (int i = 0; i < a.N; ++i) {
+    // ---- gather: the rows by sc1 loads; the next sample's inputs behind them ----
+    uint32_t li[NP];
+    float x[NP];
+    const float y = y_n;
+    RowRegs row[NP];
+    bool ok[NP];
+#pragma unroll
+    for (int p = 0; p < NP; ++p) {
+      li[p] = li_n[p];
+      x[p] = x_n[p];
+      ok[p] = live[p] && li[p] < vocab[p];  // (a negative index is a large unsigned one)
+      row[p] = onl_load_row(a.rule, a.rows + (size_t)(ok[p] ? lo[p] + li[p] : 0) * a.stride, qq[p], KP, a.zoff);
+      bad = bad || (live[p] && !ok[p]);
+    }
+    fetch_inputs(i + 1);
+    if (tid == WAVE) {  // ADAM's constants of this sample: [0..2] the tables', [3..6] the attention parameters'
+      float *kc = sm + O.misc + ONL_KC;
+      if (a.rule == FMX_RULE_ADAM) adam_consts(a.h.lr, a.h.beta1, a.h.beta2, a.h.step + i + 1, kc[0], kc[1], kc[2]);
+      if (o_m) adam_consts(a.o_lr, a.o_beta1, a.o_beta2, a.o_step + i + 1, kc[3], kc[4], kc[5], a.o_eps, &kc[6]);
+    }
+    for (int l = tid; l < O.acc_len; l += NT) sm[L.Ea + l] = 0.f;
+#pragma unroll
+    for (int p = 0; p < NP; ++p) {
+      if (live[p]) {  // gather_field's products: e = x V, x w; an absent row is zeros
+        *reinterpret_cast<float4 *>(sm + L.e + fld[p] * KP + 4 * qq[p]) = ok[p] ? x[p] * row[p].v : splat(0.f);
+        if (qq[p] == 0) sm[O.fo + fld[p]] = ok[p] ? row[p].fo.x * x[p] : 0.f;
+      }
+    }
+    __syncthreads();
+
+    // ---- pass A over the waves ----
+    score_pairs<KP>(sm, L, F, t, lane, wv, NW);
+    __syncthreads();
+
+    // ---- softmax: k_afm's one-wave reductions in every wave; the exponentials over all threads ----
+    float mx = -INFINITY;
+    for (int l = lane; l < P; l += WAVE) mx = fmaxf(mx, sm[L.s + l]);
+    mx = wave_max(mx);
+    for (int l = tid; l < P; l += NT) sm[O.x + l] = expf(sm[L.s + l] - mx);
+    const float fo = wave_sum(sm[O.fo + lane]);
+    __syncthreads();
+    float Z = 0.f, N = 0.f;
+    for (int l = lane; l < P; l += WAVE) {
+      const float ex = sm[O.x + l];
+      Z += ex;
+      N += ex * sm[L.r + l];
+    }
+    Z = wave_sum(Z);
+    N = wave_sum(N);
+    const float att = N / Z;
+    const float bias_w = ftrl ? ftrl_w(sm[O.misc], sm[O.misc + 1], a.h) : sm[O.misc];
+    const float logit = (bias_w + fo) + att;
+    float loss, g;
+    bce_loss_dz(FMX_LOSS_BCE_LOGITS, logit, y, 1.0f, loss, g);
+    if (tid == 0) {
+      if (a.logit) a.logit[i] = logit;
+      if (a.loss) a.loss[i] = 0.f + loss;  // the update's block_sum over one sample
+    }
+
+    // ---- pass B: rounds of nb tiles ----
+    for (int i0r = 0, pbr = 0; i0r < F - 1;) {
+      int i0 = i0r, pb = pbr, cnt = 0;
+      for (; cnt < nb && i0 < F - 1; ++cnt) {
+        int n;
+        const int i1 = next_tile(F, i0, n);
+        if (cnt == wv && lane < n) {
+          int pi, pj;
+          tile_pair(F, i0, lane, pi, pj);
+          pair_backward<KP>(sm, L, tile_buf(O, KP, t, cnt), t, pi, pj, lane, sm[O.x + pb + lane], Z, g, att);
+        }
+        pb += n;
+        i0 = i1;
+      }
+      __syncthreads();
+      i0 = i0r;
+      for (int c = 0; c < cnt; ++c) {
+        int n;
+        const int i1 = next_tile(F, i0, n);
+        add_tile<KP>(sm, L, tile_buf(O, KP, t, c), F, t, i0, i1, n, tid, NT);
+        i0 = i1;
+      }
+      __syncthreads();
+      i0r = i0;
+      pbr = pb;
+    }
+
+    // ---- the attention parameters: column g's gradient is 0 + the one workgroup's partial (afm_reduce_column), then the rule ----
+    {
+      fmx_hyper_t ho;
+      ho.lr = a.o_lr;
+      ho.eps = a.o_eps;
+      if (o_m) {
+        const float *kc = sm + O.misc + ONL_KC;
+        ho.lr = kc[3];
+        ho.beta1 = kc[4];
+        ho.beta2 = kc[5];
+        ho.eps = kc[6];
+      }
+      for (int c = tid; c < G; c += NT) {
+        int par, acc;
+        onl_column(L, c, k, t, KP, par, acc);
+        const float s = 0.f + sm[acc];
+        if (i == a.N - 1) a.grad[c] = s;
+        float p = sm[par], m = 0.f, v = 0.f;
+        if (o_v) v = vv[c];
+        if (o_m) m = mm[c];
+        switch (a.o_rule) {
+          case FMX_RULE_SIGNADAM: afm_opt_column<FMX_RULE_SIGNADAM>(p, m, v, s, ho); break;
+          case FMX_RULE_SGD: afm_opt_column<FMX_RULE_SGD>(p, m, v, s, ho); break;
+          case FMX_RULE_ADAGRAD: afm_opt_column<FMX_RULE_ADAGRAD>(p, m, v, s, ho); break;
+          default: afm_opt_column<FMX_RULE_ADAM>(p, m, v, s, ho); break;
+        }
+        if (o_v) vv[c] = v;
+        if (o_m) mm[c] = m;
+        sm[par] = p;
+      }
+    }
+    // ---- the tables: every row of the sample is a run of one occurrence of k_fm_update_occ ----
+    fmx_hyper_t ht = a.h;
+    if (a.rule == FMX_RULE_ADAM) {
+      const float *kc = sm + O.misc + ONL_KC;
+      ht.lr = kc[0];
+      ht.beta1 = kc[1];
+      ht.beta2 = kc[2];
+    }
+#pragma unroll
+    for (int p = 0; p < NP; ++p) {
+      if (ok[p]) {
+        const float4 E = x[p] * *reinterpret_cast<const float4 *>(sm + L.Ea + fld[p] * KP + 4 * qq[p]);  // k_afm's dL/dV_row
+        onl_update_row(a.rule, a.rows + (size_t)(lo[p] + li[p]) * a.stride, qq[p], KP, a.zoff, row[p], splat(0.f) + E, 0.f + x[p] * g,
+                       ht);
+      }
+    }
+    if (tid == 0) {
+      float b0 = sm[O.misc], b1 = sm[O.misc + 1], b2 = sm[O.misc + 2];
+      onl_bias_step(a.rule, b0, b1, b2, 0.f + g, ht);
+      sm[O.misc] = b0;
+      sm[O.misc + 1] = b1;
+      sm[O.misc + 2] = b2;
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the row stores are acknowledged ...
+    __syncthreads();                                   // ... before any thread's next gather
+  }
+
+  // ---- the state back to global memory ----
+  if (bad) sm[O.misc + ONL_FLAG] = 1.f;
+  for (int c = tid; c < G; c += NT) {
+    int par, acc;
+    onl_column(L, c, k, t, KP, par, acc);
+    a.params[c] = sm[par];
+    if (a.mom_lds) {
+      if (o_m) a.m[c] = mm[c];
+      if (o_v) a.v[c] = vv[c];
+    }
+  }
+  __syncthreads();
+  if (tid == 0) {
+    a.bias[0] = sm[O.misc];
+    if (ftrl || a.rule == FMX_RULE_ADAM) a.bias[1] = sm[O.misc + 1];
+    if (mom_rule) a.bias[2] = sm[O.misc + 2];
+    if (sm[O.misc + ONL_FLAG] != 0.f && a.error) *a.error = 1;
   }
 }
 
@@ -637,9 +1064,11 @@ AfmOptArgs afm_opt_args(const fmx_afm_t *afm, const fmx_mlp_opt_t &o, int32_t t)
 // attention gradient, with the attention parameters' rule for their step opt_t when opt is given.  The arguments have been checked.
 int afm_step_launches(const fmx_table_t *table, const fmx_hyper_t *hyper, int32_t rule, const fmx_afm_t *afm, const int32_t *idx,
                       const float *xv, const float *y, int32_t B, float inv_b, void *workspace, const AfmWs &w, float *attn_grad_out,
-                      float *loss_out, int32_t *error, const fmx_mlp_opt_t *opt, int32_t opt_t, hipStream_t st) {
+                      float *loss_out, int32_t *error, const fmx_mlp_opt_t *opt, int32_t opt_t, hipStream_t st,
+                      float *logit_out = nullptr) {
   if (int rc = fmx_sort_occurrences(table, idx, B, workspace, w.table_bytes, error, st)) return rc;
   AfmArgs a = fill_afm(table, afm, hyper, idx, xv, y, B, FMX_LOSS_BCE_LOGITS, inv_b, error);
+  a.logit = logit_out;  // [B] or null (fmx_afm_online_run's per-sample launches)
   a.dz = w.dz;
   a.loss = w.loss;
   a.E = w.E;
@@ -662,6 +1091,40 @@ int afm_step_launches(const fmx_table_t *table, const fmx_hyper_t *hyper, int32_
     default: hipLaunchKernelGGL(k_afm_reduce_opt<FMX_RULE_ADAM>, grid, block, 0, st, w.part, n, a.G, attn_grad_out, o); break;
   }
   return check_launch("k_afm_reduce_opt");
+}
+
+// the caller's hyper-parameters for the steps of one call: step s of the call is step hyper->step + s + 1 of the tables (the fields
+// appended for ADAM are read for it alone); the caller of this advances .step
+// (a field added to fmx_hyper_t must be carried over below, or fmx_afm_stream / fmx_afm_online_run part from fmx_afm_step_opt)
+static_assert(sizeof(fmx_hyper_t) == 40, "afm_call_hyper copies fmx_hyper_t field by field: add the new field to the copy");
+fmx_hyper_t afm_call_hyper(const fmx_hyper_t *hyper, int32_t rule) {
+  fmx_hyper_t hs;
+  memset(&hs, 0, sizeof(hs));
+  hs.lr = hyper->lr;
+  hs.eps = hyper->eps;
+  hs.alpha = hyper->alpha;
+  hs.beta = hyper->beta;
+  hs.l1 = hyper->l1;
+  hs.l2 = hyper->l2;
+  if (rule == FMX_RULE_ADAM) {
+    hs.beta1 = hyper->beta1;
+    hs.beta2 = hyper->beta2;
+    hs.step = hyper->step;
+  }
+  return hs;
+}
+
+template <int KP>
+int launch_afm_online_k(const AfmOnlArgs &a, hipStream_t st) {
+  const size_t lds = (size_t)afm_online_lds(a.F, KP, a.t, a.G, a.nb, a.mom_lds != 0).total * 4;
+  static std::once_flag once;
+  static hipError_t raised = hipSuccess;
+  std::call_once(once, [] {
+    raised = hipFuncSetAttribute(reinterpret_cast<const void *>(k_afm_online<KP>), hipFuncAttributeMaxDynamicSharedMemorySize, AFM_LDS_BYTES);
+  });
+  if (raised != hipSuccess) return fail(FMX_ERR_LAUNCH, "hipFuncSetAttribute(k_afm_online): %s", hipGetErrorString(raised));
+  hipLaunchKernelGGL((k_afm_online<KP>), dim3(1), dim3(AFM_ONL_THREADS), lds, st, a);
+  return check_launch("k_afm_online");
 }
 
 }  // namespace
@@ -724,21 +1187,7 @@ int fmx_afm_stream(const fmx_table_t *table, const fmx_hyper_t *hyper, int32_t r
   const size_t F = (size_t)table->n_fields;
   // Every batch is sorted on `stream` in front of its step, as fmx_afm_step does it: the steps are one plain queue of launches
   // (no side stream, no events; the sort-ahead loop of fmx_fm_stream is not used here).
-  // (a field added to fmx_hyper_t must be carried over below, or the stream parts from fmx_afm_step_opt)
-  static_assert(sizeof(fmx_hyper_t) == 40, "fmx_afm_stream copies fmx_hyper_t field by field: add the new field to the copy");
-  fmx_hyper_t hs;  // step s of the call is step hyper->step + s + 1 of the tables (the fields appended for ADAM are read for it alone)
-  memset(&hs, 0, sizeof(hs));
-  hs.lr = hyper->lr;
-  hs.eps = hyper->eps;
-  hs.alpha = hyper->alpha;
-  hs.beta = hyper->beta;
-  hs.l1 = hyper->l1;
-  hs.l2 = hyper->l2;
-  if (rule == FMX_RULE_ADAM) {
-    hs.beta1 = hyper->beta1;
-    hs.beta2 = hyper->beta2;
-    hs.step = hyper->step;
-  }
+  fmx_hyper_t hs = afm_call_hyper(hyper, rule);
   for (int s = 0; s < n_steps; ++s, ++hs.step) {
     const size_t j = (size_t)(s % n_pool);
     if (int rc = afm_step_launches(table, &hs, rule, afm, idx_pool + j * B * F, xv_pool ? xv_pool + j * B * F : nullptr, y_pool + j * B, B,
@@ -746,6 +1195,73 @@ int fmx_afm_stream(const fmx_table_t *table, const fmx_hyper_t *hyper, int32_t r
       return rc;
   }
   return FMX_OK;
+}
+
+int fmx_afm_online_run(const fmx_table_t *table, const fmx_hyper_t *hyper, int32_t rule, const fmx_afm_t *afm, const int32_t *idx,
+                       const float *xv, const float *y, int32_t N, void *workspace, int64_t workspace_bytes, float *attn_grad_out,
+                       const fmx_mlp_opt_t *opt, float *logit_out, float *loss_out, int32_t *error, fmx_stream_t stream) {
+  const char *who = "fmx_afm_online_run";
+  AfmWs w;
+  if (int rc = check_afm_step(table, hyper, rule, afm, idx, y, 1, workspace, workspace_bytes, attn_grad_out, w, who)) return rc;
+  if (N < 0) return fail(FMX_ERR_ARG, "%s: N = %d must be >= 0", who, N);
+  if (int rc = check_afm_opt(table, hyper, rule, afm, 1, opt, N, who)) return rc;
+  if (N == 0) return FMX_OK;
+  const hipStream_t st = static_cast<hipStream_t>(stream);
+  const int F = table->n_fields, G = afm->t * afm->k + 2 * afm->t + afm->k;
+  const bool want_mom = opt->rule == FMX_RULE_ADAGRAD || opt->rule == FMX_RULE_ADAM;
+  bool mom = false;
+  const int nb = tune().afm_online_persistent ? afm_online_buffers(F, table->kp, afm->t, G, want_mom, mom) : 0;
+  if (nb == 0) {
+    // the per-sample launches of fmx_afm_step_opt(B = 1, inv_b = 1), queued without any host synchronisation
+    fmx_hyper_t hs = afm_call_hyper(hyper, rule);
+    for (int i = 0; i < N; ++i, ++hs.step) {
+      if (int rc = afm_step_launches(table, &hs, rule, afm, idx + (size_t)i * F, xv ? xv + (size_t)i * F : nullptr, y + i, 1, 1.0f, workspace,
+                                     w, attn_grad_out, loss_out ? loss_out + i : nullptr, error, opt, opt->step + i + 1, st,
+                                     logit_out ? logit_out + i : nullptr))
+        return rc;
+    }
+    return FMX_OK;
+  }
+  AfmOnlArgs a;
+  memset(&a, 0, sizeof(a));
+  a.rows = table->rows;
+  a.foff = table->field_offsets;
+  a.bias = table->bias;
+  a.idx = idx;
+  a.xv = xv;
+  a.y = y;
+  a.params = afm->params;
+  a.m = opt->m;
+  a.v = opt->v;
+  a.grad = attn_grad_out;
+  a.logit = logit_out;
+  a.loss = loss_out;
+  a.error = error;
+  a.h = afm_call_hyper(hyper, rule);  // ADAM: the kernel derives each sample's constants from lr, beta1, beta2, step
+  a.h.alpha = 1.0f / hyper->alpha;    // the kernels multiply by 1/alpha (ftrl_w)
+  a.o_lr = opt->lr;
+  a.o_eps = opt->eps;
+  a.o_beta1 = opt->beta1;
+  a.o_beta2 = opt->beta2;
+  a.o_rule = opt->rule;
+  a.o_step = opt->step;
+  a.N = N;
+  a.F = F;
+  a.k = afm->k;
+  a.t = afm->t;
+  a.stride = table->row_stride;
+  a.zoff = table->z_offset;
+  a.rule = rule;
+  a.G = G;
+  a.nb = nb;
+  a.mom_lds = mom ? 1 : 0;
+  switch (table->kp) {
+    case 4: return launch_afm_online_k<4>(a, st);
+    case 8: return launch_afm_online_k<8>(a, st);
+    case 16: return launch_afm_online_k<16>(a, st);
+    case 32: return launch_afm_online_k<32>(a, st);
+    default: return launch_afm_online_k<64>(a, st);
+  }
 }
 
 int fmx_afm_side(const fmx_table_t *table, const fmx_afm_t *afm, const fmx_hyper_t *hyper, const int32_t *idx, const float *xv,

@@ -58,10 +58,6 @@ namespace {
 // the in-launch hand-off of partial records uses on BOTH sides (MI355X_MICROARCH.md, "Valid forms": every store and every
 // load of the handed-off bytes sc1, the storing wave's s_waitcnt vmcnt(0) before its flag store).
 __device__ __forceinline__ void st_sc1(float *p, float v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ float ld_sc1(const float *p) {
-  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ float4 ld_sc1_4(const float *p) { return {ld_sc1(p), ld_sc1(p + 1), ld_sc1(p + 2), ld_sc1(p + 3)}; }
 // 16-byte store: one instruction per lane (`global_store_dwordx4 ... sc1`; scalar sc1 stores are one fabric write each).
 typedef float v4f __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ void st_sc1_4(float *p, float4 v) {
@@ -500,14 +496,6 @@ struct UpdArgs {
 // tile meta states
 constexpr int LEAD_NONE = 0, LEAD_CLOSES = 1, LEAD_THROUGH = 2;
 
-// Row stores are nontemporal: the lines go out while the launch runs instead of staying dirty in L2 for the write-back at its end
-// (same-box A/B of the online loop, tools/ab_old_new.sh: 21.51 / 21.60 against 21.90 / 21.83 us per step).
-__device__ __forceinline__ void st16(float *p, float4 v) {
-  typedef float f4v __attribute__((ext_vector_type(4)));
-  __builtin_nontemporal_store(f4v{v.x, v.y, v.z, v.w}, reinterpret_cast<f4v *>(p));
-}
-__device__ __forceinline__ void st4(float *p, float v) { __builtin_nontemporal_store(v, p); }
-
 // The bias gradient (sum of dlogit over the batch) and the mean loss.  The batch is cut into slices of RED_SLICE samples, one
 // workgroup each (the first workgroups of the launch): with the samples' (S, dlogit, loss) records gathered from G ranks the
 // values lie 80 bytes apart, one 64-byte request each, and ONE workgroup walking 2 x 32,768 of them was the longest path of
@@ -589,78 +577,6 @@ __device__ void bias_and_loss(const UpdArgs &a, int r) {
   }
   if (threadIdx.x == 0) st_sc1_4(a.red + 4 * r, float4{db, ls, __uint_as_float(a.seq), 0.f});
   if (INL && r == 0) finish_bias_and_loss<LAYOUT, RULE>(a, R, true);
-}
-
-// The state of one row as LPR lanes hold it: lane q owns coordinates 4q..4q+3; lane 0 also the first-order part.
-//   WEIGHTS row  [ V(kp) | w | pad ]
-//   FTRL row     [ V(kp) | w, zw, nw, pad | ... | zV(kp) | nV(kp) ]   zV starts at float `zoff`;
-//                V and w are the weights derived from (z, n), re-derived and stored by every update
-//   MOMENTS row  [ V(kp) | w, mw, vw, pad | ... | mV(kp) | vV(kp) ]   the FTRL geometry; V and w are the parameters
-//                (ADAGRAD neither loads nor stores the m slots: z stays zero in the registers)
-struct RowRegs {
-  float4 v;       // V
-  float4 z, n;    // FTRL: (z, n); MOMENTS: (m, v)
-  float4 fo;      // lane 0: (w, zw, nw, -) / (w, mw, vw, -)
-};
-
-template <int LAYOUT, int RULE>
-__device__ __forceinline__ RowRegs load_row(const float *rp, int q, int kp, int zoff) {
-  RowRegs r;
-  r.v = *reinterpret_cast<const float4 *>(rp + 4 * q);
-  r.z = splat(0.f);
-  r.n = splat(0.f);
-  r.fo = splat(0.f);
-  // the first-order part is used by lane 0 of the group only, but every lane requests it (same address: one request): a
-  // load under `if (q == 0)` is a branch, and the compiler's wait counts fall back to vmcnt(0) around it
-  if (LAYOUT == FMX_LAYOUT_WEIGHTS) {
-    r.fo.x = rp[kp];
-  } else {
-    if (LAYOUT == FMX_LAYOUT_FTRL || RULE == FMX_RULE_ADAM) r.z = *reinterpret_cast<const float4 *>(rp + zoff + 4 * q);
-    r.n = *reinterpret_cast<const float4 *>(rp + zoff + kp + 4 * q);
-    r.fo = *reinterpret_cast<const float4 *>(rp + kp);
-  }
-  return r;
-}
-
-// gradient of the row from the run sums (dV = cV - V * cA, dw = cw), one application of the rule, store
-template <int LAYOUT, int RULE>
-__device__ __forceinline__ void update_row(float *rp, int q, int kp, int zoff, RowRegs r, float4 cV, float4 cA, float cw,
-                                           const fmx_hyper_t &h) {
-  // two roundings on purpose (no fma): where a sample is the row's only contribution to S (x = 1), cV = dz * V and
-  // V * cA = V * dz round alike and the gradient is exactly 0, as in the reference's dz * x * (S - e)
-  const float4 gr = cV - r.v * cA;
-  if (LAYOUT == FMX_LAYOUT_WEIGHTS) {
-    st16(rp + 4 * q, apply_rule4<RULE>(r.v, gr, h));
-    if (q == 0) st4(rp + kp, apply_rule<RULE>(r.fo.x, cw, h));
-  } else if (LAYOUT == FMX_LAYOUT_MOMENTS) {
-    float4 p4 = r.v, m4 = r.z, v4 = r.n;
-    moments_upd4<RULE>(p4, m4, v4, gr, h);
-    // the (m, v) half is read by nobody but the next update of this row (a later launch): plain stores
-    if (RULE == FMX_RULE_ADAM) *reinterpret_cast<float4 *>(rp + zoff + 4 * q) = m4;
-    *reinterpret_cast<float4 *>(rp + zoff + kp + 4 * q) = v4;
-    st16(rp + 4 * q, p4);
-    if (q == 0) {
-      float4 fo = r.fo;
-      moments_upd<RULE>(fo.x, fo.y, fo.z, cw, h);
-      st16(rp + kp, fo);
-    }
-  } else {
-    float4 z4 = r.z, n4 = r.n;
-    ftrl_upd(z4.x, n4.x, r.v.x, gr.x, h);
-    ftrl_upd(z4.y, n4.y, r.v.y, gr.y, h);
-    ftrl_upd(z4.z, n4.z, r.v.z, gr.z, h);
-    ftrl_upd(z4.w, n4.w, r.v.w, gr.w, h);
-    // the (z, n) half is read by nobody but the next update of this row (a later launch): plain stores
-    *reinterpret_cast<float4 *>(rp + zoff + 4 * q) = z4;
-    *reinterpret_cast<float4 *>(rp + zoff + kp + 4 * q) = n4;
-    st16(rp + 4 * q, ftrl_w4(z4, n4, h));
-    if (q == 0) {
-      float4 fo = r.fo;
-      ftrl_upd(fo.y, fo.z, fo.x, cw, h);
-      fo.x = ftrl_w(fo.y, fo.z, h);
-      st16(rp + kp, fo);
-    }
-  }
 }
 
 // partial-sum record: [cV (kp) | cA (kp) | cw, pad3]
@@ -1105,23 +1021,6 @@ struct OnlineArgs {
   fmx_hyper_t h;
   int32_t N, F, stride, zoff, loss_kind;
 };
-
-template <int LAYOUT, int RULE>
-__device__ __forceinline__ RowRegs load_row_sc1(const float *rp, int q, int kp, int zoff) {
-  RowRegs r;
-  r.v = ld_sc1_4(rp + 4 * q);
-  r.z = splat(0.f);
-  r.n = splat(0.f);
-  r.fo = splat(0.f);
-  if (LAYOUT == FMX_LAYOUT_WEIGHTS) {  // (every lane, as in load_row: no branch around a load)
-    r.fo.x = ld_sc1(rp + kp);
-  } else {
-    if (LAYOUT == FMX_LAYOUT_FTRL || RULE == FMX_RULE_ADAM) r.z = ld_sc1_4(rp + zoff + 4 * q);
-    r.n = ld_sc1_4(rp + zoff + kp + 4 * q);
-    r.fo = ld_sc1_4(rp + kp);
-  }
-  return r;
-}
 
 // (The field walk below and k_online_mlp's stay two copies: one shared walk left k_fm_online's forward waiting on the prefetch
 // of the next sample with vmcnt(0) instead of the row loads only: 3.2 -> 3.6 us per sample.)
@@ -2545,6 +2444,7 @@ int fmx_set_option(const char *name, int value) {
   if (!strcmp(name, "inline_fixup")) slot = &t.inline_fixup;
   else if (!strcmp(name, "sort_ahead")) slot = &t.sort_ahead;
   else if (!strcmp(name, "online_persistent")) slot = &t.online_persistent;
+  else if (!strcmp(name, "afm_online_persistent")) slot = &t.afm_online_persistent;
   else if (!strcmp(name, "sort_chunked")) slot = &t.sort_chunked;
   else if (!strcmp(name, "mlp_chain")) slot = &t.mlp_chain;
   else return fail(FMX_ERR_ARG, "fmx_set_option: unknown option '%s'", name);

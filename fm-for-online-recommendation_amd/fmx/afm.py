@@ -1,5 +1,5 @@
 """AFMEngine: workspace + launch sequencing of the attentional FM (fmx_afm_forward / fmx_afm_step / fmx_afm_step_opt /
-fmx_afm_stream) for one FlatTable.
+fmx_afm_stream / fmx_afm_online_run) for one FlatTable.
 
 The attention parameters live in ONE flat fp32 device buffer [ W (t x k) | b (t) | h (t) | p (k) ] (include/fmx.h, fmx_afm_t);
 the step returns their gradient in the same layout and leaves updating them to the caller -- or, given an AfmOpt, applies their
@@ -114,3 +114,26 @@ class AFMEngine:
         opt.step += n_steps
         if self.table.layout == "moments":
             self.table.step += n_steps
+
+    def online_run(self, hyper, rule, idx_d, xv_d, y_d, opt, logits=None, losses=None, stream=None):
+        """The online predict-then-fit loop over a device-resident stream in one call (fmx_afm_online_run; no sync here): idx_d
+        [N, F] int32, xv_d the same shape in fp32 or None (ones), y_d [N].  Sample i is predicted, then fitted on: N steps of
+        step(B = 1, inv_b = 1).  logits / losses: fp32 device tensors of N elements for each sample's logit BEFORE its update
+        and its loss, or None.  The table's step count and opt's advance by N; self.grad holds the last sample's attention
+        gradient."""
+        N = int(idx_d.shape[0])
+        assert idx_d.dtype == torch.int32 and idx_d.is_contiguous() and idx_d.numel() == N * self.table.n_fields
+        assert y_d.dtype == torch.float32 and y_d.numel() == N
+        assert xv_d is None or (xv_d.dtype == torch.float32 and xv_d.is_contiguous() and xv_d.numel() == idx_d.numel())
+        for out in (logits, losses):
+            assert out is None or (out.dtype == torch.float32 and out.is_contiguous() and out.numel() >= N)
+        self._ensure(1)
+        if self.table.layout == "moments":
+            hyper.c.step = self.table.step
+        _lib.check(self.lib.fmx_afm_online_run(self.table.c_struct(), hyper.ref(), _lib.RULES[rule], C.byref(self.c_afm),
+                                               idx_d.data_ptr(), _ptr(xv_d), y_d.data_ptr(), N, self.workspace.data_ptr(),
+                                               self.workspace.numel() * 4, self.grad.data_ptr(), opt.ref(), _ptr(logits),
+                                               _ptr(losses), self.error.data_ptr(), self._stream(stream)))
+        opt.step += N
+        if self.table.layout == "moments":
+            self.table.step += N

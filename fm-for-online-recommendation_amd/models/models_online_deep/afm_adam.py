@@ -289,6 +289,51 @@ class AFMAdam(nn.Module):
         cm = {"tp": int(tp[-1]), "fp": int(fp[-1]), "tn": int(tn[-1]), "fn": int(fn[-1])}
         return time() - start, float(accuracy[-1]), {k: float(v) for k, v in roc[-1].items()}, cm
 
+    @staticmethod
+    def _online_report(pred, data_Y, start):
+        """(seconds, accuracy %, last roc point, confusion matrix) of the predictions taken before each sample's update, with
+        the checkpoints of the other classes' run_experiment: every 1,000 samples and at the last sample."""
+        y = np.asarray(data_Y).reshape(-1)
+        n = len(y)
+        pos, hit = y == 1, pred == (y == 1)
+        tp, fn = np.cumsum(pos & hit), np.cumsum(pos & ~hit)
+        tn, fp = np.cumsum(~pos & hit), np.cumsum(~pos & ~hit)
+        accuracy, roc = [], []
+        for i in sorted(set(range(0, n, 1000)) | {n - 1}):
+            roc.append({"tpr": tp[i] / (tp[i] + fn[i] + 1e-16), "fpr": fp[i] / (fp[i] + tn[i] + 1e-16)})
+            accuracy.append((tp[i] + tn[i]) / (i + 1) * 100)
+        cm = {"tp": int(tp[-1]), "fp": int(fp[-1]), "tn": int(tn[-1]), "fn": int(fn[-1])}
+        return time() - start, float(accuracy[-1]), {k: float(v) for k, v in roc[-1].items()}, cm
+
+    def run_online_experiment(self, data_Xi, data_Xv, data_Y):
+        """The online protocol of the other classes' run_experiment (reference fm_adam.py:90-119), which the reference's AFM
+        lacks: predict a sample (sigmoid(logit) > 0.5), then fit on it, one sample at a time -> (seconds, accuracy %,
+        {'tpr', 'fpr'}, {'tp', 'fp', 'tn', 'fn'}).  run_experiment keeps the reference's predict-only behaviour.
+        fused_optimizer=True: one upload and ONE fmx_afm_online_run call -- the bits of a loop of predict() and
+        update_embedding() over one-sample batches; the index flag is read once.  fused_optimizer=False: that loop itself."""
+        F = self.field_size
+        Xi = np.asarray(data_Xi).reshape((-1, F))
+        Xv = np.asarray(data_Xv, dtype=np.float32).reshape((-1, F))
+        Y = np.asarray(data_Y, dtype=np.float32).reshape(-1)
+        N = len(Y)
+        if N == 0:
+            raise ValueError("run_online_experiment: no samples")
+        start = time()
+        if self._attn_fused is not None:
+            self.train()
+            idx_d, xv_d, y_d = self._inputs(Xi, Xv, Y)
+            logits = torch.empty(N, dtype=torch.float32, device=self.device)
+            self._engine.online_run(self._hyper, self.update_rule, idx_d, xv_d, y_d, self._attn_fused, logits=logits)
+            pred = (torch.sigmoid(logits) > 0.5).cpu().numpy()
+            if self.strict_index_check:
+                self.check_index_flag()
+        else:
+            pred = np.zeros(N, dtype=bool)
+            for i in range(N):
+                pred[i] = bool(np.asarray(self.predict(Xi[i:i + 1], Xv[i:i + 1])).reshape(-1)[0])
+                self.update_embedding(Xi[i:i + 1], Xv[i:i + 1], Y[i:i + 1])
+        return self._online_report(pred, Y, start)
+
     # ------------------------------------------------------------------------------------------------------
     # state (the reference's keys) and pickling
     # ------------------------------------------------------------------------------------------------------

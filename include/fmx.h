@@ -691,6 +691,34 @@ int fmx_afm_stream(const fmx_table_t *table, const fmx_hyper_t *hyper, int32_t r
                    int64_t workspace_bytes, float *attn_grad_out, const fmx_mlp_opt_t *opt, float *loss_out, int32_t *error,
                    fmx_stream_t stream);
 
+/* The online predict-then-fit loop of the AFM on a device-resident stream, in one call: idx [N, F], xv [N, F] or null (ones),
+ * y [N].  Sample i is predicted and then fitted on, one sample at a time: the call is N steps of fmx_afm_step_opt with B = 1 and
+ * inv_b = 1, sample i being step hyper->step + i + 1 of the tables and step opt->step + i + 1 of the attention parameters (both
+ * counts are read, never written: the caller advances them by N).  logit_out [N] or null receives each sample's logit under the
+ * weights BEFORE its update (predict and fit share one forward); loss_out [N] or null its BCE-with-logits loss; attn_grad_out
+ * [t k + 2 t + k] holds the last sample's attention gradient; error [1] or null is set to 1 when any index of the stream lies
+ * outside its field (that row is absent for its sample; the walk goes on).  rule / opt->rule: every table rule fmx_afm_step_opt
+ * takes, with its layout, and FMX_RULE_SGD / FMX_RULE_SIGNADAM / FMX_RULE_ADAGRAD / FMX_RULE_ADAM on the attention parameters.
+ * workspace: fmx_afm_workspace_bytes(table, afm, 1) bytes.
+ * One workgroup walks the stream and spreads each sample over its waves: the attention parameters (and their moments where they
+ * fit) stay in LDS until the end of the stream, the bias words too; ADAM's constants of a sample are derived on the device by
+ * the function the host uses for a launch.  A shape that does not leave room in the CU's 160 KiB of LDS for two pair tiles'
+ * buffers beside the sample (the largest F, k and t together), or fmx_set_option("afm_online_persistent", 0), takes the
+ * per-sample launches of fmx_afm_step_opt instead, queued without any host synchronisation.  No float is accumulated with
+ * atomics; the result is deterministic run to run.
+ * The result is, bit for bit, the one of N calls of fmx_afm_step_opt(B = 1, inv_b = 1) with both step counts advanced by the
+ * caller, in either form: rows (moments and FTRL state included), bias words, params, m, v, the per-sample logits and losses,
+ * the last attn_grad_out and the error word.
+ * Limits: those of fmx_afm_step_opt (every shape it accepts is accepted).  Every argument is checked before the first launch,
+ * each failure naming this entry point in fmx_last_error_string(): fmx_afm_step_opt's checks, with N < 0 and step + N beyond
+ * int32 (of opt, and of hyper under the tables' FMX_RULE_ADAM): FMX_ERR_ARG; workspace_bytes too small: FMX_ERR_SHAPE; tables
+ * whose fields are pieces of index columns: FMX_ERR_UNSUPPORTED.  N = 0 launches nothing and returns 0.
+ * Replaces: a loop over the samples of AFMAdam.predict (reference afm_adam.py:170-191) followed by one fit step on the sample
+ * (:113-118) -- the protocol of the other classes' run_experiment (reference fm_adam.py:90-119), which the reference's AFM lacks. */
+int fmx_afm_online_run(const fmx_table_t *table, const fmx_hyper_t *hyper, int32_t rule, const fmx_afm_t *afm, const int32_t *idx,
+                       const float *xv, const float *y, int32_t N, void *workspace, int64_t workspace_bytes, float *attn_grad_out,
+                       const fmx_mlp_opt_t *opt, float *logit_out, float *loss_out, int32_t *error, fmx_stream_t stream);
+
 /* ---- top-K recommendation under the AFM (fmx/recommend.py, AFMAdam.recommend) ----
  * Split the fields into context fields C and item fields I (at least one of each).  A combined sample's pairs are the C x C
  * pairs (u alone), the I x I pairs (c alone) and the |C| |I| cross pairs.  Each side's own pairs reduce to (lin, m, Z, R):
