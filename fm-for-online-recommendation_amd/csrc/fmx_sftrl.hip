@@ -1,9 +1,31 @@
-// fmx_sftrl.hip -- the sketched-FTRL family on the device and its C ABI: fmx_sftrl_run, fmx_sftrl_grid.
-// Kernel: fmx_sftrl.inc.
+// fmx_sftrl.hip -- hot path B on the device and its C ABI: the sketched-FTRL
+// family (fmx_sftrl_run, fmx_sftrl_grid; kernel: fmx_sftrl.inc), FM_FTRL (fmx_ftrl_dense_run, fmx_ftrl_dense_grid) and RRF_Online
+// (fmx_rrf_run, fmx_rrf_grid; kernels: fmx_pathb.inc).
 #include "fmx_common.h"
 
 namespace {
 #include "fmx_sftrl.inc"
+#include "fmx_pathb.inc"
+
+// the dynamic LDS of the two walkers of fmx_pathb.inc, in bytes (their header comments give the layout)
+size_t ftrl_dense_lds(int D, int m2) { return ((size_t)2 * PB_MAX_D + (size_t)m2 * ((D - 1) | 1)) * sizeof(double); }
+size_t rrf_lds(int D, int Ds) { return ((size_t)2 * PB_MAX_D + PB_MAX_DS + (size_t)D * (Ds | 1)) * sizeof(double); }
+
+// what fmx_ftrl_dense_run and fmx_ftrl_dense_grid check of a stream and the largest W2 before they launch
+int ftrl_dense_check(const char *who, int32_t N, int32_t D, int32_t m2, int32_t task) {
+  if (N < 0 || D < 2 || m2 < 2 || (m2 & 1)) return fail(FMX_ERR_ARG, "%s: bad sizes (N >= 0, D >= 2, 2 m even and >= 2)", who);
+  if (task != 0 && task != 1) return fail(FMX_ERR_ARG, "%s: task must be 0 (cls) or 1 (reg)", who);
+  if (D > PB_MAX_D || m2 > PB_MAX_M2)
+    return fail(FMX_ERR_UNSUPPORTED, "%s: needs features <= %d, 2 m <= %d (got %d, %d)", who, PB_MAX_D, PB_MAX_M2, D, m2);
+  return FMX_OK;
+}
+int rrf_check(const char *who, int32_t N, int32_t D, int32_t Ds, int32_t loss) {
+  if (N < 0 || D < 1 || Ds < 1) return fail(FMX_ERR_ARG, "%s: bad sizes", who);
+  if (loss != 0 && loss != 1) return fail(FMX_ERR_ARG, "%s: loss must be 0 (logit) or 1 (l2); hinge and l1 are not implemented", who);
+  if (D > PB_MAX_D || Ds > PB_MAX_DS)
+    return fail(FMX_ERR_UNSUPPORTED, "%s: needs features <= %d, spectral samples <= %d (got %d, %d)", who, PB_MAX_D, PB_MAX_DS, D, Ds);
+  return FMX_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -90,6 +112,119 @@ int fmx_sftrl_grid(const double *X, const double *y, int32_t N, int32_t D, int32
   }
   hipLaunchKernelGGL(k_sftrl_online, dim3(n_settings), dim3(64), lds, static_cast<hipStream_t>(stream), a);
   return check_launch("k_sftrl_online (grid)");
+}
+
+int fmx_ftrl_dense_run(const double *X, const double *y, int32_t N, int32_t D, int32_t m2, double eta, int32_t task, double *w1,
+                       double *W2, double *g_w1, double *g_W2, double *pred_out, int32_t *status, fmx_stream_t stream) {
+  if (!X || !y || !w1 || !W2 || !g_w1 || !g_W2 || !pred_out || !status) return fail(FMX_ERR_ARG, "fmx_ftrl_dense_run: null argument");
+  if (const int rc = ftrl_dense_check("fmx_ftrl_dense_run", N, D, m2, task)) return rc;
+  if (N == 0) return FMX_OK;
+  FtrlDenseArgs a;
+  a.X = X;
+  a.y = y;
+  a.w1 = w1;
+  a.g_w1 = g_w1;
+  a.W2 = W2;
+  a.g_W2 = g_W2;
+  a.pred = pred_out;
+  a.status = status;
+  a.eta = eta;
+  a.N = N;
+  a.D = D;
+  a.m2 = m2;
+  a.cls = task == 0;
+  a.m2s = nullptr;
+  a.etas = nullptr;
+  a.W_stride = a.pred_stride = 0;
+  hipLaunchKernelGGL(k_ftrl_dense, dim3(1), dim3(64), ftrl_dense_lds(D, m2), static_cast<hipStream_t>(stream), a);
+  return check_launch("k_ftrl_dense");
+}
+
+int fmx_ftrl_dense_grid(const double *X, const double *y, int32_t N, int32_t D, int32_t n_settings, const int32_t *m2s, const double *etas,
+                        int32_t m2_max, int32_t task, double *w1, double *W2, double *g_w1, double *g_W2, double *pred_out,
+                        int32_t *status, fmx_stream_t stream) {
+  if (!X || !y || !m2s || !etas || !w1 || !W2 || !g_w1 || !g_W2 || !pred_out || !status)
+    return fail(FMX_ERR_ARG, "fmx_ftrl_dense_grid: null argument");
+  if (n_settings < 0) return fail(FMX_ERR_ARG, "fmx_ftrl_dense_grid: bad sizes");
+  if (const int rc = ftrl_dense_check("fmx_ftrl_dense_grid", N, D, m2_max, task)) return rc;
+  if (N == 0 || n_settings == 0) return FMX_OK;
+  FtrlDenseArgs a;
+  a.X = X;
+  a.y = y;
+  a.w1 = w1;
+  a.g_w1 = g_w1;
+  a.W2 = W2;
+  a.g_W2 = g_W2;
+  a.pred = pred_out;
+  a.status = status;
+  a.eta = 0.0;
+  a.N = N;
+  a.D = D;
+  a.m2 = m2_max;
+  a.cls = task == 0;
+  a.m2s = m2s;
+  a.etas = etas;
+  a.W_stride = (long long)m2_max * (D - 1);
+  a.pred_stride = N;
+  hipLaunchKernelGGL(k_ftrl_dense, dim3(n_settings), dim3(64), ftrl_dense_lds(D, m2_max), static_cast<hipStream_t>(stream), a);
+  return check_launch("k_ftrl_dense (grid)");
+}
+
+int fmx_rrf_run(const double *X, const double *y, int32_t N, int32_t D, int32_t Ds, double lr_w, double lr_gamma, int32_t loss,
+                const double *eps, double *gamma, double *w, double *pred_out, int32_t *status, fmx_stream_t stream) {
+  if (!X || !y || !eps || !gamma || !w || !pred_out || !status) return fail(FMX_ERR_ARG, "fmx_rrf_run: null argument");
+  if (const int rc = rrf_check("fmx_rrf_run", N, D, Ds, loss)) return rc;
+  if (N == 0) return FMX_OK;
+  RrfArgs a;
+  a.X = X;
+  a.y = y;
+  a.eps = eps;
+  a.gamma = gamma;
+  a.w = w;
+  a.pred = pred_out;
+  a.status = status;
+  a.lr_w = lr_w;
+  a.lr_g = lr_gamma;
+  a.N = N;
+  a.D = D;
+  a.Ds = Ds;
+  a.l2 = loss == 1;
+  a.Dss = nullptr;
+  a.lr_ws = a.lr_gs = nullptr;
+  a.eps_stride = a.w_stride = a.pred_stride = 0;
+  hipLaunchKernelGGL(k_rrf_online, dim3(1), dim3(64), rrf_lds(D, Ds), static_cast<hipStream_t>(stream), a);
+  return check_launch("k_rrf_online");
+}
+
+int fmx_rrf_grid(const double *X, const double *y, int32_t N, int32_t D, int32_t n_settings, const int32_t *Dss, const double *lr_ws,
+                 const double *lr_gammas, int32_t Ds_max, int32_t loss, const double *eps, double *gamma, double *w, double *pred_out,
+                 int32_t *status, fmx_stream_t stream) {
+  if (!X || !y || !Dss || !lr_ws || !lr_gammas || !eps || !gamma || !w || !pred_out || !status)
+    return fail(FMX_ERR_ARG, "fmx_rrf_grid: null argument");
+  if (n_settings < 0) return fail(FMX_ERR_ARG, "fmx_rrf_grid: bad sizes");
+  if (const int rc = rrf_check("fmx_rrf_grid", N, D, Ds_max, loss)) return rc;
+  if (N == 0 || n_settings == 0) return FMX_OK;
+  RrfArgs a;
+  a.X = X;
+  a.y = y;
+  a.eps = eps;
+  a.gamma = gamma;
+  a.w = w;
+  a.pred = pred_out;
+  a.status = status;
+  a.lr_w = a.lr_g = 0.0;
+  a.N = N;
+  a.D = D;
+  a.Ds = Ds_max;
+  a.l2 = loss == 1;
+  a.Dss = Dss;
+  a.lr_ws = lr_ws;
+  a.lr_gs = lr_gammas;
+  a.eps_stride = (long long)D * Ds_max;
+  a.w_stride = 2ll * Ds_max;
+  a.pred_stride = N;
+  hipLaunchKernelGGL(k_rrf_online, dim3(n_settings), dim3(64), rrf_lds(D, Ds_max), static_cast<hipStream_t>(stream), a);
+  return check_launch("k_rrf_online (grid)");
 }
 
 }  // extern "C"

@@ -21,6 +21,7 @@ EXPORTS = ["fmx_version", "fmx_last_error_string", "fmx_set_option", "fmx_sorted
            "fmx_mlp_section_workspace_bytes", "fmx_fm_online_run", "fmx_online_run_mlp", "fmx_mlp_forward_batch", "fmx_mlp_hedge_section",
            "fmx_sort_occurrences", "fmx_fm_update", "fmx_fm_step", "fmx_fm_stream", "fmx_deepfm_stream", "fmx_stream_read",
            "fmx_fm_forward_partial", "fmx_fm_forward_finish", "fmx_sftrl_run", "fmx_sftrl_grid",
+           "fmx_ftrl_dense_run", "fmx_ftrl_dense_grid", "fmx_rrf_run", "fmx_rrf_grid",
            "fmx_gather_read", "fmx_comm_unique_id", "fmx_comm_create", "fmx_comm_destroy", "fmx_owner_prefetch", "fmx_owner_step",
            "fmx_fm_topk_workspace_bytes", "fmx_fm_topk", "fmx_mlp_topk_workspace_bytes", "fmx_mlp_topk",
            "fmx_fm_update_occ", "fmx_afm_forward", "fmx_afm_workspace_bytes", "fmx_afm_step",
@@ -102,6 +103,10 @@ def load():
     lib.fmx_sort_occurrences.argtypes = [TP, p, i32, p, i64, p, p]
     lib.fmx_sftrl_run.argtypes = [p, p, i32, i32, i32, i32, C.c_double, C.c_double, i32, p, p, p, p, p, p, p, p]
     lib.fmx_sftrl_grid.argtypes = [p, p, i32, i32, i32, i32, p, p, i32, C.c_double, i32, p, p, p, p, p, p, p, p]
+    lib.fmx_ftrl_dense_run.argtypes = [p, p, i32, i32, i32, C.c_double, i32, p, p, p, p, p, p, p]
+    lib.fmx_ftrl_dense_grid.argtypes = [p, p, i32, i32, i32, p, p, i32, i32, p, p, p, p, p, p, p]
+    lib.fmx_rrf_run.argtypes = [p, p, i32, i32, i32, C.c_double, C.c_double, i32, p, p, p, p, p, p]
+    lib.fmx_rrf_grid.argtypes = [p, p, i32, i32, i32, p, p, p, i32, i32, p, p, p, p, p, p]
     lib.fmx_fm_forward_partial.argtypes = [TP, p, p, i32, i32, i32, i32, p, p, p]
     lib.fmx_fm_forward_finish.argtypes = [HP, p, i32, i32, p, i64, i32, p, i32, i32, f32, FP, p]
     lib.fmx_fm_update.argtypes = [TP, HP, i32, p, i64, p, p, p, p, p, i32, i32, p, f32, p, p]

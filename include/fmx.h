@@ -560,6 +560,63 @@ int fmx_sftrl_grid(const double *X, const double *y, int32_t N, int32_t D, int32
                    const double *etas, int32_t m_max, double thres, int32_t task, double *BP, double *BN, int32_t *counts, double *w,
                    double *g_w, double *pred_out, int32_t *status, fmx_stream_t stream);
 
+/* FM_FTRL on a device-resident stream (hot path B's dense baseline): per sample x (D features; x' = x without its last one)
+ *     t = W2 x';  y_hat = w1 . x + t . t;  s = (-1 / (1 + exp(y_hat y))) y (task 0, cls) or 2 (y_hat - y) (task 1, reg);
+ *     g_w1 += s x;  g_W2 += 2 t x'^T (no factor s: the reference's quirk);  w1 = -eta g_w1;  W2 = -eta g_W2.
+ * fp64, strictly sequential: ONE wavefront walks the stream; g_W2 lives in LDS and W2 is derived from it element by element (one
+ * multiplication, the host's rounding of -eta * g_W2) -- only the first sample reads the caller's W2.
+ *   X [N, D], y [N];  m2 = 2 m rows of W2;  w1, g_w1 [D] and W2, g_W2 [m2, D - 1] row-major are read and written back: a caller
+ *   continues a stream by passing them on (a run cut in two gives the bits of the uninterrupted run); a fresh stream passes
+ *   g_w1 = g_W2 = 0.  pred_out [N] receives the RAW y_hat (the caller takes the sign for cls).
+ *   status [2]: (1, i) when y_hat of sample i was NaN: the walk stops in front of that sample's update; else not written.
+ * Order of the floating-point operations (no atomics; the same bits on every run):
+ *   t_r = fma(W2[r][j], x[j], t_r), j ascending from t_r = 0;
+ *   y_hat = the sum over lanes l = 0..63 of fma(t_{l+64}, t_{l+64}, fma(t_l, t_l, w1[l] * x[l])) (absent terms are 0), added by
+ *   the xor butterfly l ^ 1, l ^ 2, l ^ 4, ..., l ^ 32;
+ *   the state updates are one multiplication and one addition each, as written above (no fma).
+ * Limits: 2 <= D <= 64, m2 even, 2 <= m2 <= 128; beyond 64 / 128: FMX_ERR_UNSUPPORTED (there is no host fallback).  N = 0 launches nothing.
+ * Replaces: FM_FTRL.online_learning (reference models/models_online/FM_FTRL.py:61-80). */
+int fmx_ftrl_dense_run(const double *X, const double *y, int32_t N, int32_t D, int32_t m2, double eta, int32_t task, double *w1,
+                       double *W2, double *g_w1, double *g_W2, double *pred_out, int32_t *status, fmx_stream_t stream);
+
+/* A GRID of FM_FTRL settings over the same stream in one launch: workgroup s runs (m2s[s], etas[s]) (the reference's notebooks run
+ * one (eta, m) pair per FM_FTRL object, reference models/models_online/FM_FTRL.py:27-92).  m2s [S] int32, etas [S] fp64 are device
+ * arrays.  Per setting s:
+ *   w1, g_w1 [S, D];  W2, g_W2 [S][m2_max * (D - 1)]: setting s's matrix as [m2s[s], D - 1] row-major at the start of its slot;
+ *   pred_out [S, N];  status [S, 2]  -- everything else as fmx_ftrl_dense_run, the limits applied to m2_max;
+ *   status[s] = (2, m2s[s]): m2s[s] is odd or outside [2, m2_max] (the launch is sized for m2_max): setting s was not run and
+ *   none of its slabs was written.
+ * Every setting's result is bit-identical to its own fmx_ftrl_dense_run. */
+int fmx_ftrl_dense_grid(const double *X, const double *y, int32_t N, int32_t D, int32_t n_settings, const int32_t *m2s, const double *etas,
+                        int32_t m2_max, int32_t task, double *w1, double *W2, double *g_w1, double *g_W2, double *pred_out,
+                        int32_t *status, fmx_stream_t stream);
+
+/* RRF_Online (reparameterised random Fourier features) on a device-resident stream: per sample x, with eps [D, Ds] fixed,
+ *     z = x (e^gamma * eps);  phi = [cos z, sin z];  y_hat = phi . w;  coef = -y (loss 0, logit) or y_hat - y (loss 1, l2);
+ *     d_w = lr_w exp(w) + coef phi;  q_d = -sin z_d (coef w_d) + cos z_d (coef w_{Ds+d});
+ *     d_gamma_n = (sum_d (x_n eps_nd) q_d) e^gamma_n;  w -= lr_w d_w;  gamma -= lr_gamma d_gamma.
+ * fp64, ONE wavefront; eps in LDS, w and gamma in registers.  The device's exp / sin / cos are not the host libm's bit for bit.
+ *   X [N, D], y [N];  eps [D, Ds] row-major (read only);  gamma [D], w [2 Ds] are read and written back;  pred_out [N] raw y_hat.
+ *   A NaN y_hat leaves gamma and w untouched, writes NaN to that sample's pred_out and the walk goes on (the reference's loop skips
+ *   the sample).  status [2] is always written: (number of NaN samples, the first of them or -1).
+ * Order: z_d = fma(x_n, e^gamma_n * eps_nd, z_d), n ascending;  y_hat = the sum over lanes d of fma(sin z_d, w_{Ds+d}, cos z_d * w_d)
+ * by the xor butterfly d ^ 1, ..., d ^ 32;  the sum of d_gamma_n = fma(x_n * eps_nd, q_d, .), d ascending;  the rest as written.
+ * Limits: D <= 64, Ds <= 64, else FMX_ERR_UNSUPPORTED; the hinge and l1 losses are not implemented (FMX_ERR_ARG), as on the host.
+ * Replaces: RRF_Online.online_learning (reference models/models_online/RRF_Online.py:70-123, :142-187). */
+int fmx_rrf_run(const double *X, const double *y, int32_t N, int32_t D, int32_t Ds, double lr_w, double lr_gamma, int32_t loss,
+                const double *eps, double *gamma, double *w, double *pred_out, int32_t *status, fmx_stream_t stream);
+
+/* A GRID of RRF_Online settings over the same stream in one launch (reference RRF_Online.py:18-67 builds one setting per
+ * object): workgroup s runs (Dss[s], lr_ws[s], lr_gammas[s]), device arrays of S elements.  Per setting s:
+ *   eps [S][D * Ds_max]: setting s's matrix as [D, Dss[s]] row-major at the start of its slot;  gamma [S, D];
+ *   w [S][2 * Ds_max]: setting s's 2 Dss[s] weights at the start of its slot;  pred_out [S, N];  status [S, 2].
+ *   status[s] = (-2, Dss[s]): Dss[s] lies outside [1, Ds_max]: setting s was not run and none of its slabs was written.  (The
+ *   refusal code 2 of the other grids, negated: a setting that ran reports its NaN count, >= 0, in status[s][0].)
+ * Every setting's result is bit-identical to its own fmx_rrf_run. */
+int fmx_rrf_grid(const double *X, const double *y, int32_t N, int32_t D, int32_t n_settings, const int32_t *Dss, const double *lr_ws,
+                 const double *lr_gammas, int32_t Ds_max, int32_t loss, const double *eps, double *gamma, double *w, double *pred_out,
+                 int32_t *status, fmx_stream_t stream);
+
 /* ---- top-K recommendation over an FM table's candidates (fmx/recommend.py) ----
  * Replaces: the caller-side loop of forward() over assembled (context, candidate) samples followed by torch.topk; the reference
  * has no counterpart (no recommendation call).  Split a sample's fields into context fields and item fields; then
