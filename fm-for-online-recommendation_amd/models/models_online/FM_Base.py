@@ -3,7 +3,8 @@
 Path B is strictly sequential (each prediction depends on the previous update) on d = 8 features, so the default of
 every class is the host, like the reference's own CPU path (BASELINE.json configs[0]: "plumbing only").  All four
 learners of the family (FM_FTRL, SFTRL_CCFM, SFTRL_Vanila, RRF_Online) also take device="gpu": the whole stream in one
-launch, one wavefront per stream (include/fmx.h: fmx_ftrl_dense_run, fmx_sftrl_run, fmx_rrf_run).  Measured on an MI355X at 8
+launch, one wavefront per stream (include/fmx.h: fmx_ftrl_dense_run, fmx_sftrl_run, fmx_rrf_run; the host glue around those
+calls, shared by the four classes, is _device.py).  Measured on an MI355X at 8
 features (profiles/path_b_times.json): one FM_FTRL / RRF_Online stream runs at 1.0-1.7 us per sample on the
 device against 5-10 on the host; the sketch classes, whose shrink is a Jacobi eigen-decomposition on one wavefront, at 13-66 against
 8.  The classes' grid() classmethods run many settings over one device-resident stream side by side: 256 settings take about
@@ -12,6 +13,8 @@ the time of a few, 290-380 times the host running them one after another.
 import numpy as np
 import torch
 from torch.nn import Module
+
+from models.models_online import _device
 
 tensor_type = torch.DoubleTensor
 
@@ -28,29 +31,15 @@ class FM_Base(Module):
         self.eta = learning_rate
         self.m = feature_m
 
-    def _loss(self, x):
-        """reference :34-41"""
-        if self.task == "reg":
-            return x ** 2
-        if self.task == "cls":
-            return 1 / (1 + torch.exp(x))
-        return None
+    def _stream(self):
+        """-> the stream as contiguous fp64 numpy, X [N, d] and y [N]"""
+        return _device.host_stream(self.At.t(), self.b)
 
-    def _grad_loss(self, x):
-        """reg: 2x; cls: -1 / (1 + e^x)   (reference :44-51)"""
-        if self.task == "reg":
-            return 2.0 * x
-        if self.task == "cls":
-            return -1.0 / (1.0 + torch.exp(x))
-        return None
-
-    def _predict(self, scalar):
-        """reg: (s, s); cls: (s, +-1 as a DoubleTensor of one element)   (reference :54-65)"""
-        if self.task == "reg":
-            return scalar, scalar
-        if self.task == "cls":
-            return scalar, torch.tensor([1.0 if scalar >= 0 else -1.0]).type(tensor_type)
-        raise NotImplementedError
+    @staticmethod
+    def _grad_loss(scalar, y, cls):
+        """d loss / d y_hat of the numpy host loops: cls (-1 / (1 + e^(s y))) y, reg 2 (s - y)   (reference :44-51 applied as in
+        FM_FTRL.py:69, SFTRL_CCFM.py:50)"""
+        return (-1.0 / (1.0 + np.exp(scalar * y))) * y if cls else 2.0 * (scalar - y)
 
     def online_learning(self, logger=None):
         raise NotImplementedError

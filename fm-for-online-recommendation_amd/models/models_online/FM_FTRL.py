@@ -4,7 +4,8 @@ Per sample x (a column of At):  y_hat = w1^T x + ||W2 x'||^2 with x' = x without
 cumulative gradients g_w1 += s x, g_W2 += 2 W2 x' x'^T -- without the factor s, a reference quirk kept here (:76-77);
 then w1 = -eta g_w1, W2 = -eta g_W2 (:79-80).  device="host" (the default, like the reference's CPU path): the loop runs
 in numpy fp64 (one matvec and one rank-1 update per sample instead of the reference's two matmuls).  device="gpu": the
-same draws, then the whole stream in one fmx_ftrl_dense_run launch (include/fmx.h: one wavefront, g_W2 in LDS) -- same
+same draws, then the whole stream in one fmx_ftrl_dense_run launch (include/fmx.h: one wavefront, g_W2 in LDS; staging, slabs
+and progress lines: _device.py) -- same
 return value and prints, predictions and weights equal to the host's up to the order of the fp64 sums (measured: 7e-16 of the
 largest magnitude; profiles/path_b_times.json).  Measured at 8 features, m = 8, 4,000 samples on an MI355X: 1.0-1.1 us per sample,
 copies included, against the host loop's 5.3-6.6; FM_FTRL.grid -- many settings walking one device-resident stream side by side --
@@ -17,31 +18,23 @@ import time
 import numpy as np
 import torch
 
+from models.models_online import _device
 from models.models_online.FM_Base import FM_Base
 
 Tensor_type = torch.DoubleTensor
 numpy_type = np.float64
 
-GRID_MAX_SETTINGS = 256      # settings per launch: one workgroup each, one per CU of an MI355X
-
 
 class FM_FTRL(FM_Base):
     def __init__(self, inputs_matrix, outputs, task, learning_rate, num_feature, device="host"):
         super(FM_FTRL, self).__init__(inputs_matrix, outputs, task, learning_rate, num_feature)
-        if device not in ("host", "gpu"):
-            raise ValueError("device must be 'host' or 'gpu'")
-        self.device = device
+        self.device = _device.check_device(device)
         self.model_name = "FM_FTRL"
 
     def _init_parameter(self):
         """randn init in the reference's draw order (:42-43)"""
         self.w1 = torch.randn(self.num_feature, 1).type(Tensor_type)
         self.W2 = torch.randn(2 * self.m, self.num_feature - 1).type(Tensor_type)
-
-    def _stream(self):
-        X = self.At.t().contiguous().numpy().astype(numpy_type, copy=False)      # [N, d]
-        y = np.asarray(self.b.reshape(-1).numpy(), dtype=numpy_type)
-        return X, y
 
     def _shape_predictions(self, scalars, cls):
         """raw y_hat [N] -> what online_learning returns: (N, 1) of +-1 for cls, (N, 1, 1) for reg"""
@@ -76,12 +69,8 @@ class FM_FTRL(FM_Base):
             scalar = w1 @ x + t @ t
             if np.isnan(scalar):
                 raise ValueError("Nan contained")
-            if cls:
-                pred = 1.0 if scalar >= 0 else -1.0
-                sign_idx = (-1.0 / (1.0 + np.exp(scalar * y[idx]))) * y[idx]
-            else:
-                pred = scalar
-                sign_idx = 2.0 * (scalar - y[idx])
+            pred = (1.0 if scalar >= 0 else -1.0) if cls else scalar
+            sign_idx = self._grad_loss(scalar, y[idx], cls)
             g_w1 += sign_idx * x
             g_W2 += 2.0 * np.outer(t, xs)
             w1 = -eta * g_w1
@@ -98,31 +87,17 @@ class FM_FTRL(FM_Base):
 
     def _online_learning_gpu(self, X, y, cls):
         """The same stream through fmx_ftrl_dense_run, from the parameters just drawn and zero cumulative gradients."""
-        import ctypes as C
-
-        from fmx import _lib
-        lib = _lib.load()
-        dev = torch.device("cuda", torch.cuda.current_device())
-        n, D = X.shape
-        Xd, yd = torch.from_numpy(X).to(dev), torch.from_numpy(y).to(dev)
-        w1, W2 = self.w1.reshape(-1).to(dev).contiguous(), self.W2.to(dev).contiguous()
+        g = _device.Launch(X, y)
+        w1, W2 = g.put(self.w1.reshape(-1)), g.put(self.W2)
         g_w1, g_W2 = torch.zeros_like(w1), torch.zeros_like(W2)
-        pred = torch.empty(n, dtype=torch.float64, device=dev)
-        status = torch.zeros(2, dtype=torch.int32, device=dev)
-        ptr = lambda t: C.c_void_p(t.data_ptr())
-        _lib.check(lib.fmx_ftrl_dense_run(ptr(Xd), ptr(yd), n, D, 2 * self.m, float(self.eta), 0 if cls else 1, ptr(w1), ptr(W2),
-                                          ptr(g_w1), ptr(g_W2), ptr(pred), ptr(status),
-                                          C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
-        st = status.cpu()
-        n_ok = int(st[1]) if int(st[0]) == 1 else n                # samples in front of a NaN prediction
-        self.y_hat = pred.cpu().numpy()
-        p = self._shape_predictions(self.y_hat, cls)
-        for idx in range(0, n_ok, 1000):                             # the host loop's lines, up to where it would have raised
-            print(" %d th : pred %f , real %f " % (idx, p[idx].item(), y[idx]))
-        if n_ok < n:
-            raise ValueError("Nan contained")
+        g.call("fmx_ftrl_dense_run", 2 * self.m, float(self.eta), 0 if cls else 1, w1, W2, g_w1, g_W2)
+        st = g.host_status()
+        n_ok = int(st[0, 1]) if int(st[0, 0]) == 1 else g.n          # samples in front of a NaN prediction
+        self.y_hat = g.pred.cpu().numpy()
+        _device.print_progress(self.y_hat, y, cls, n_ok)             # the host loop's lines, up to where it would have raised
+        _device.check_status(st, "fmx_ftrl_dense_run")
         self.w1, self.W2 = w1.cpu().reshape(-1, 1), W2.cpu()
-        return p
+        return self._shape_predictions(self.y_hat, cls)
 
     @classmethod
     def grid(cls, inputs_matrix, outputs, task, learning_rates, num_features, device="gpu"):
@@ -133,8 +108,7 @@ class FM_FTRL(FM_Base):
         settings per launch; every model is what `cls(..., lr, m, device="gpu").online_learning()` leaves behind, bit for
         bit.  device="host": the same settings one after another through the host loop (prints included)."""
         import itertools
-        if device not in ("host", "gpu"):
-            raise ValueError("device must be 'host' or 'gpu'")
+        _device.check_device(device)
         if task not in ("cls", "reg"):
             raise NotImplementedError
         settings = list(itertools.product(learning_rates, num_features))
@@ -143,46 +117,22 @@ class FM_FTRL(FM_Base):
             return [(mdl, mdl.online_learning()[0]) for mdl in models]
         for mdl in models:
             mdl._init_parameter()
-        out = []
-        for lo in range(0, len(models), GRID_MAX_SETTINGS):
-            out.extend(cls._grid_launch(models[lo:lo + GRID_MAX_SETTINGS], task == "cls"))
-        return out
+        return [r for part in _device.launches(models) for r in cls._grid_launch(part, task == "cls")]
 
     @staticmethod
     def _grid_launch(models, is_cls):
-        import ctypes as C
-
-        from fmx import _lib
-        lib = _lib.load()
-        dev = torch.device("cuda", torch.cuda.current_device())
-        X, y = models[0]._stream()
-        n, D = X.shape
-        S, m2_max = len(models), max(2 * mdl.m for mdl in models)
-        Xd, yd = torch.from_numpy(X).to(dev), torch.from_numpy(y).to(dev)
-        m2s = torch.tensor([2 * mdl.m for mdl in models], dtype=torch.int32, device=dev)
-        etas = torch.tensor([float(mdl.eta) for mdl in models], dtype=torch.float64, device=dev)
-        w1_h = torch.stack([mdl.w1.reshape(-1) for mdl in models])
-        W2_h = torch.zeros((S, m2_max * (D - 1)), dtype=torch.float64)
-        for s, mdl in enumerate(models):
-            W2_h[s, :2 * mdl.m * (D - 1)] = mdl.W2.reshape(-1)
-        w1, W2 = w1_h.to(dev).contiguous(), W2_h.to(dev)
+        g = _device.Launch(*models[0]._stream(), S=len(models))
+        m2s = torch.tensor([2 * mdl.m for mdl in models], dtype=torch.int32, device=g.dev)
+        etas = torch.tensor([float(mdl.eta) for mdl in models], dtype=torch.float64, device=g.dev)
+        w1, W2 = g.put(_device.pack_slab([mdl.w1 for mdl in models])), g.put(_device.pack_slab([mdl.W2 for mdl in models]))
         g_w1, g_W2 = torch.zeros_like(w1), torch.zeros_like(W2)
-        pred = torch.empty((S, n), dtype=torch.float64, device=dev)
-        status = torch.zeros((S, 2), dtype=torch.int32, device=dev)
-        ptr = lambda t: C.c_void_p(t.data_ptr())
-        _lib.check(lib.fmx_ftrl_dense_grid(ptr(Xd), ptr(yd), n, D, S, ptr(m2s), ptr(etas), m2_max, 0 if is_cls else 1, ptr(w1), ptr(W2),
-                                           ptr(g_w1), ptr(g_W2), ptr(pred), ptr(status),
-                                           C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
-        st_h = status.cpu()
-        if bool((st_h[:, 0] == 2).any()):
-            raise ValueError("a setting's num_feature lies outside [1, max]: not run (fmx_ftrl_dense_grid status 2)")
-        if bool((st_h[:, 0] == 1).any()):
-            raise ValueError("Nan contained")
-        w1_o, W2_o, ph = w1.cpu(), W2.cpu(), pred.cpu().numpy()
+        g.call("fmx_ftrl_dense_grid", len(models), m2s, etas, max(2 * mdl.m for mdl in models), 0 if is_cls else 1, w1, W2, g_w1, g_W2)
+        _device.check_status(g.host_status(), "fmx_ftrl_dense_grid", "num_feature")
+        ph = g.pred.cpu().numpy()
+        w1s = _device.unpack_slab(w1.cpu(), [mdl.w1.shape for mdl in models])
+        W2s = _device.unpack_slab(W2.cpu(), [mdl.W2.shape for mdl in models])
         out = []
         for s, mdl in enumerate(models):
-            mdl.w1 = w1_o[s].reshape(-1, 1).clone()
-            mdl.W2 = W2_o[s, :2 * mdl.m * (D - 1)].reshape(2 * mdl.m, D - 1).clone()
-            mdl.y_hat = ph[s].copy()
+            mdl.w1, mdl.W2, mdl.y_hat = w1s[s], W2s[s], ph[s].copy()
             out.append((mdl, mdl._shape_predictions(mdl.y_hat, is_cls)))
         return out

@@ -3,8 +3,8 @@ features, online).  phi(x) = [cos, sin](x (e^gamma * eps)) (:70-75); SGD on w an
 formulas (:88-123), including its `lr_w * exp(w)` term in d_w (:97) and, for the logit loss, the per-batch softmax
 weight that equals 1 at batch size 1 (:101-102).  fp64.  device="host" (the default, like the reference's CPU path) runs
 the loop in numpy; device="gpu" runs the whole stream in one fmx_rrf_run launch (include/fmx.h: one wavefront, eps in
-LDS): same return triple and prints, NaN samples dropped from pred and real as the host loop drops them.  The device's
-exp / sin / cos differ from the host's in the last place and this model's dynamics amplify that (tests/golden/
+LDS; staging, slabs and progress lines: _device.py): same return triple and prints, NaN samples dropped from pred and real as the
+host loop drops them.  The device's exp / sin / cos differ from the host's in the last place and this model's dynamics amplify that (tests/golden/
 make_golden.py pins 100 steps for that reason): agreement is to a tolerance, not to the bit (measured: 6e-16 of the largest
 magnitude over the fixtures; profiles/path_b_times.json).  Measured at 8 features, 6 spectral samples, 4,000 samples on an MI355X:
 1.6-1.7 us per sample, copies included, against the host loop's 9.6-9.7; RRF_Online.grid -- many (lr_w, lr_gamma, spectral
@@ -18,18 +18,16 @@ import numpy as np
 import torch
 from torch.nn import Module
 
-Tensor_type = torch.DoubleTensor
+from models.models_online import _device
 
-GRID_MAX_SETTINGS = 256      # settings per launch: one workgroup each, one per CU of an MI355X
+Tensor_type = torch.DoubleTensor
 
 
 class RRF_Online(Module):
     def __init__(self, inputs_matrix, outputs, task, loss_type=None, gamma=None, w=None, num_sampled_spectral=10,
                  random_seed=100, lr_RRF_w=0.05, lr_RRF_gamma=0.05, device="host"):
         super(RRF_Online, self).__init__()
-        if device not in ("host", "gpu"):
-            raise ValueError("device must be 'host' or 'gpu'")
-        self.device = device
+        self.device = _device.check_device(device)
         self.X = inputs_matrix
         self.Y = outputs
         self.loss_type = loss_type
@@ -69,8 +67,7 @@ class RRF_Online(Module):
         print("==" * 20)
         if self.loss_type not in ("logit", "l2"):
             raise NotImplementedError("wrong loss type in get_grad")
-        X = self.X.numpy().astype(np.float64, copy=False)
-        Y = np.asarray(self.Y.reshape(-1).numpy(), dtype=np.float64)
+        X, Y = _device.host_stream(self.X, self.Y)
         gamma = self.gamma.numpy().reshape(-1).copy()
         w = self.w.numpy().copy()
         eps = self.eps.numpy()
@@ -118,32 +115,15 @@ class RRF_Online(Module):
         pred = (np.where(kept >= 0, 1.0, -1.0) if cls else kept).reshape(-1, 1)
         return np.asarray(pred, dtype=np.float64), np.asarray(Y[keep], dtype=np.float64)
 
-    @staticmethod
-    def _print_progress(scalars, Y, cls):
-        for t in range(0, scalars.shape[0], 1000):
-            s = scalars[t]
-            print(" %d th : pred %f , real %f " % (t, (1.0 if s >= 0 else -1.0) if cls and not np.isnan(s) else s, Y[t]))
-
     def _online_learning_gpu(self, X, Y, cls):
         """The same stream through fmx_rrf_run; gamma and w are read and written back."""
-        import ctypes as C
-
-        from fmx import _lib
-        lib = _lib.load()
-        dev = torch.device("cuda", torch.cuda.current_device())
-        n, D = X.shape
-        Xd, yd = torch.from_numpy(np.ascontiguousarray(X)).to(dev), torch.from_numpy(Y).to(dev)
-        eps = self.eps.to(dev).contiguous()
-        gamma, w = self.gamma.reshape(-1).to(dev).contiguous(), self.w.to(dev).contiguous()
-        pred = torch.empty(n, dtype=torch.float64, device=dev)
-        status = torch.zeros(2, dtype=torch.int32, device=dev)
-        ptr = lambda t: C.c_void_p(t.data_ptr())
-        _lib.check(lib.fmx_rrf_run(ptr(Xd), ptr(yd), n, D, self.num_sampled_spectral, float(self.lr_RRF_w), float(self.lr_RRF_gamma),
-                                   0 if self.loss_type == "logit" else 1, ptr(eps), ptr(gamma), ptr(w), ptr(pred), ptr(status),
-                                   C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
-        scalars = self.y_hat = pred.cpu().numpy()
+        g = _device.Launch(X, Y)
+        eps, gamma, w = g.put(self.eps), g.put(self.gamma.reshape(-1)), g.put(self.w)
+        g.call("fmx_rrf_run", self.num_sampled_spectral, float(self.lr_RRF_w), float(self.lr_RRF_gamma),
+               0 if self.loss_type == "logit" else 1, eps, gamma, w)
+        scalars = self.y_hat = g.pred.cpu().numpy()
         self.w, self.gamma = w.cpu(), gamma.cpu().reshape(-1, 1)
-        self._print_progress(scalars, Y, cls)
+        _device.print_progress(scalars, Y, cls)
         return self._kept(scalars, Y, cls)
 
     @classmethod
@@ -155,8 +135,7 @@ class RRF_Online(Module):
         launches of at most 256 settings; every model is what its own device="gpu" run leaves behind, bit for bit.
         device="host": the same settings one after another through the host loop (prints included)."""
         import itertools
-        if device not in ("host", "gpu"):
-            raise ValueError("device must be 'host' or 'gpu'")
+        _device.check_device(device)
         settings = list(itertools.product(lr_ws, lr_gammas, num_sampled_spectrals))
         models = [cls(inputs_matrix, outputs, task, loss_type=loss_type, num_sampled_spectral=ds, lr_RRF_w=lw, lr_RRF_gamma=lg,
                       device=device) for lw, lg, ds in settings]
@@ -164,47 +143,25 @@ class RRF_Online(Module):
             raise NotImplementedError("wrong loss type in get_grad")
         if device == "host":
             return [(mdl, mdl.online_learning()[0]) for mdl in models]
-        out = []
-        for lo in range(0, len(models), GRID_MAX_SETTINGS):
-            out.extend(cls._grid_launch(models[lo:lo + GRID_MAX_SETTINGS]))
-        return out
+        return [r for part in _device.launches(models) for r in cls._grid_launch(part)]
 
     @staticmethod
     def _grid_launch(models):
-        import ctypes as C
-
-        from fmx import _lib
-        lib = _lib.load()
-        dev = torch.device("cuda", torch.cuda.current_device())
         m0 = models[0]
-        X = np.ascontiguousarray(m0.X.numpy().astype(np.float64, copy=False))
-        Y = np.asarray(m0.Y.reshape(-1).numpy(), dtype=np.float64)
-        n, D = X.shape
-        S, ds_max = len(models), max(mdl.num_sampled_spectral for mdl in models)
-        Xd, yd = torch.from_numpy(X).to(dev), torch.from_numpy(Y).to(dev)
-        dss = torch.tensor([mdl.num_sampled_spectral for mdl in models], dtype=torch.int32, device=dev)
-        lws = torch.tensor([float(mdl.lr_RRF_w) for mdl in models], dtype=torch.float64, device=dev)
-        lgs = torch.tensor([float(mdl.lr_RRF_gamma) for mdl in models], dtype=torch.float64, device=dev)
-        eps_h = torch.zeros((S, D * ds_max), dtype=torch.float64)
-        w_h = torch.zeros((S, 2 * ds_max), dtype=torch.float64)
-        for s, mdl in enumerate(models):
-            eps_h[s, :D * mdl.num_sampled_spectral] = mdl.eps.reshape(-1)
-            w_h[s, :2 * mdl.num_sampled_spectral] = mdl.w
-        eps, w = eps_h.to(dev), w_h.to(dev)
-        gamma = torch.stack([mdl.gamma.reshape(-1) for mdl in models]).to(dev).contiguous()
-        pred = torch.empty((S, n), dtype=torch.float64, device=dev)
-        status = torch.zeros((S, 2), dtype=torch.int32, device=dev)
-        ptr = lambda t: C.c_void_p(t.data_ptr())
-        _lib.check(lib.fmx_rrf_grid(ptr(Xd), ptr(yd), n, D, S, ptr(dss), ptr(lws), ptr(lgs), ds_max, 0 if m0.loss_type == "logit" else 1,
-                                    ptr(eps), ptr(gamma), ptr(w), ptr(pred), ptr(status),
-                                    C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
-        if bool((status.cpu()[:, 0] < 0).any()):
-            raise ValueError("a setting's num_sampled_spectral lies outside [1, max]: not run (fmx_rrf_grid status -2)")
-        w_o, g_o, ph = w.cpu(), gamma.cpu(), pred.cpu().numpy()
+        X, Y = _device.host_stream(m0.X, m0.Y)
+        g = _device.Launch(X, Y, S=len(models))
+        dss = torch.tensor([mdl.num_sampled_spectral for mdl in models], dtype=torch.int32, device=g.dev)
+        lws = torch.tensor([float(mdl.lr_RRF_w) for mdl in models], dtype=torch.float64, device=g.dev)
+        lgs = torch.tensor([float(mdl.lr_RRF_gamma) for mdl in models], dtype=torch.float64, device=g.dev)
+        eps, gamma, w = (g.put(_device.pack_slab([getattr(mdl, name) for mdl in models])) for name in ("eps", "gamma", "w"))
+        g.call("fmx_rrf_grid", len(models), dss, lws, lgs, max(mdl.num_sampled_spectral for mdl in models),
+               0 if m0.loss_type == "logit" else 1, eps, gamma, w)
+        _device.check_status(g.host_status(), "fmx_rrf_grid", "num_sampled_spectral")
+        ph = g.pred.cpu().numpy()
+        ws = _device.unpack_slab(w.cpu(), [mdl.w.shape for mdl in models])
+        gammas = _device.unpack_slab(gamma.cpu(), [mdl.gamma.shape for mdl in models])
         out = []
         for s, mdl in enumerate(models):
-            mdl.w = w_o[s, :2 * mdl.num_sampled_spectral].clone()
-            mdl.gamma = g_o[s].reshape(-1, 1).clone()
-            mdl.y_hat = ph[s].copy()
+            mdl.w, mdl.gamma, mdl.y_hat = ws[s], gammas[s], ph[s].copy()
             out.append((mdl, mdl._kept(mdl.y_hat, Y, mdl.task == "cls")[0]))
         return out

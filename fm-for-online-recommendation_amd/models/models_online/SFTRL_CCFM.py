@@ -2,7 +2,7 @@
 
 y_hat = ||BP^T x||^2 - ||BN^T x||^2 (:42-44); the gradient sign s picks the sketch: s <= 0 appends sqrt(-eta s) x to
 BP, s > 0 appends sqrt(eta s) x to BN (:77-121).  fp64 like the reference.  device="host" (the default, like the
-reference's CPU path; see _sketch.py) or device="gpu": the whole stream in one fmx_sftrl_run launch (include/fmx.h;
+reference's CPU path; see _sketch.py) or device="gpu": the whole stream in one fmx_sftrl_run launch (include/fmx.h, staged by _device.py;
 one wavefront, sketches in LDS, the shrink as a Jacobi eigen-decomposition of B B^T -- same B B^T, predictions and
 counts, columns of B up to sign).  The gpu path never falls back: outside the kernel's limits it raises."""
 import time
@@ -10,6 +10,7 @@ import time
 import numpy as np
 import torch
 
+from models.models_online import _device
 from models.models_online.FM_Base import FM_Base
 from models.models_online._sketch import Sketch
 
@@ -21,9 +22,7 @@ class SFTRL_CCFM(FM_Base):
 
     def __init__(self, inputs_matrix, outputs, task, learning_rate, num_feature, device="host"):
         super(SFTRL_CCFM, self).__init__(inputs_matrix, outputs, task, learning_rate, num_feature)
-        if device not in ("host", "gpu"):
-            raise ValueError("device must be 'host' or 'gpu'")
-        self.device = device
+        self.device = _device.check_device(device)
         self.model_name = "SFTRL_CCFM"
         self.row_count_p = 0
         self.row_count_n = 0
@@ -41,8 +40,7 @@ class SFTRL_CCFM(FM_Base):
         if self.task not in ("cls", "reg"):
             raise NotImplementedError
         cls = self.task == "cls"
-        X = self.At.t().contiguous().numpy().astype(np.float64, copy=False)
-        y = np.asarray(self.b.reshape(-1).numpy(), dtype=np.float64)
+        X, y = self._stream()
         d = self._sketch_dim()
         if self.device == "gpu":
             preds = self._online_learning_gpu(X, y, d, cls)
@@ -64,12 +62,8 @@ class SFTRL_CCFM(FM_Base):
                 scalar += float(w @ x)
             if np.isnan(scalar):
                 raise ValueError("Nan contained")
-            if cls:
-                pred = 1.0 if scalar >= 0 else -1.0
-                sign = (-1.0 / (1.0 + np.exp(scalar * y[idx]))) * y[idx]
-            else:
-                pred = scalar
-                sign = 2.0 * (scalar - y[idx])
+            pred = (1.0 if scalar >= 0 else -1.0) if cls else scalar
+            sign = self._grad_loss(scalar, y[idx], cls)
             if self._linear_term:
                 g_w += sign * x
                 w = -self.eta * g_w
@@ -91,36 +85,20 @@ class SFTRL_CCFM(FM_Base):
 
     def _online_learning_gpu(self, X, y, d, cls):
         """The same stream through fmx_sftrl_run; state (sketches, counts, linear term) is read and written back."""
-        import ctypes as C
-
-        from fmx import _lib
-        lib = _lib.load()
-        dev = torch.device("cuda", torch.cuda.current_device())
-        n, D = X.shape
-        Xd, yd = torch.from_numpy(X).to(dev), torch.from_numpy(y).to(dev)
-        BP, BN = self.BT_P.to(dev).contiguous(), self.BT_N.to(dev).contiguous()
-        counts = torch.tensor([self.row_count_p, self.row_count_n], dtype=torch.int32, device=dev)
-        w = g_w = None
-        if self._linear_term:
-            w, g_w = self.w.reshape(-1).to(dev).contiguous(), self.g_w.reshape(-1).to(dev).contiguous()
-        pred = torch.empty(n, dtype=torch.float64, device=dev)
-        status = torch.zeros(2, dtype=torch.int32, device=dev)
-        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())
-        _lib.check(lib.fmx_sftrl_run(ptr(Xd), ptr(yd), n, D, d, self.m, float(self.eta), float(self._thres), 0 if cls else 1,
-                                     ptr(BP), ptr(BN), ptr(counts), ptr(w), ptr(g_w), ptr(pred), ptr(status),
-                                     C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
-        st = status.cpu()
-        if int(st[0]) == 1:
-            raise ValueError("Nan contained")
+        g = _device.Launch(X, y)
+        BP, BN = g.put(self.BT_P), g.put(self.BT_N)
+        counts = torch.tensor([self.row_count_p, self.row_count_n], dtype=torch.int32, device=g.dev)
+        w, g_w = (g.put(self.w.reshape(-1)), g.put(self.g_w.reshape(-1))) if self._linear_term else (None, None)
+        g.call("fmx_sftrl_run", d, self.m, float(self.eta), float(self._thres), 0 if cls else 1, BP, BN, counts, w, g_w)
+        _device.check_status(g.host_status(), "fmx_sftrl_run")
         c = counts.cpu()
         self.BT_P, self.row_count_p = BP.cpu(), int(c[0])
         self.BT_N, self.row_count_n = BN.cpu(), int(c[1])
         if self._linear_term:
             self.w, self.g_w = w.cpu().reshape(-1, 1), g_w.cpu().reshape(-1, 1)
-        p = pred.cpu().numpy()
-        for idx in range(0, n, 1000):
-            print(" %d th : pred %f , real %f " % (idx, p[idx], y[idx]))
-        return p.reshape((n,) + self._pred_shape(cls))
+        p = g.pred.cpu().numpy()
+        _device.print_progress(p, y, False)                          # the device's prediction as it is (+-1 already for cls)
+        return p.reshape((g.n,) + self._pred_shape(cls))
 
     @classmethod
     def grid(cls, inputs_matrix, outputs, task, learning_rates, num_features):
@@ -128,52 +106,36 @@ class SFTRL_CCFM(FM_Base):
         `learning_rates` x `num_features` over the SAME stream in ONE launch (fmx_sftrl_grid: one wavefront per setting,
         up to 256 settings side by side).  -> list of (model, predictions) in the order of itertools.product; every model
         is what `cls(..., lr, m, device="gpu").online_learning()` leaves behind, bit for bit."""
-        import ctypes as C
         import itertools
-
-        from fmx import _lib
         if task not in ("cls", "reg"):
             raise NotImplementedError
-        settings = list(itertools.product(learning_rates, num_features))
-        models = [cls(inputs_matrix, outputs, task, lr, m, device="gpu") for lr, m in settings]
-        if not settings:
-            return []
-        lib = _lib.load()
-        dev = torch.device("cuda", torch.cuda.current_device())
+        models = [cls(inputs_matrix, outputs, task, lr, m, device="gpu") for lr, m in itertools.product(learning_rates, num_features)]
+        return cls._grid_launch(models, task == "cls") if models else []
+
+    @staticmethod
+    def _grid_launch(models, is_cls):
         m0 = models[0]
-        X = m0.At.t().contiguous().numpy().astype(np.float64, copy=False)
-        y = np.asarray(m0.b.reshape(-1).numpy(), dtype=np.float64)
-        n, D = X.shape
-        d, S, m_max = m0._sketch_dim(), len(settings), max(m for _, m in settings)
-        Xd, yd = torch.from_numpy(X).to(dev), torch.from_numpy(y).to(dev)
-        ms = torch.tensor([m for _, m in settings], dtype=torch.int32, device=dev)
-        etas = torch.tensor([float(lr) for lr, _ in settings], dtype=torch.float64, device=dev)
-        BP = torch.zeros((S, d * 2 * m_max), dtype=torch.float64, device=dev)
-        BN = torch.zeros_like(BP)
-        counts = torch.zeros((S, 2), dtype=torch.int32, device=dev)
+        g = _device.Launch(*m0._stream(), S=len(models))
+        ms = torch.tensor([mdl.m for mdl in models], dtype=torch.int32, device=g.dev)
+        etas = torch.tensor([float(mdl.eta) for mdl in models], dtype=torch.float64, device=g.dev)
+        BP, BN = g.put(_device.pack_slab([mdl.BT_P for mdl in models])), g.put(_device.pack_slab([mdl.BT_N for mdl in models]))
+        counts = torch.tensor([[mdl.row_count_p, mdl.row_count_n] for mdl in models], dtype=torch.int32, device=g.dev)
         w = g_w = None
-        if cls._linear_term:
-            w, g_w = torch.zeros((S, D), dtype=torch.float64, device=dev), torch.zeros((S, D), dtype=torch.float64, device=dev)
-        pred = torch.empty((S, n), dtype=torch.float64, device=dev)
-        status = torch.zeros((S, 2), dtype=torch.int32, device=dev)
-        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())
-        _lib.check(lib.fmx_sftrl_grid(ptr(Xd), ptr(yd), n, D, d, S, ptr(ms), ptr(etas), m_max, float(m0._thres), 0 if task == "cls" else 1,
-                                      ptr(BP), ptr(BN), ptr(counts), ptr(w), ptr(g_w), ptr(pred), ptr(status),
-                                      C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
-        st_h = status.cpu()
-        if bool((st_h[:, 0] == 2).any()):
-            raise ValueError("a setting's num_feature lies outside [1, max]: not run (fmx_sftrl_grid status 2)")
-        if bool((st_h[:, 0] == 1).any()):
-            raise ValueError("Nan contained")
-        BPh, BNh, ch, ph = BP.cpu(), BN.cpu(), counts.cpu(), pred.cpu().numpy()
+        if m0._linear_term:
+            w, g_w = g.put(_device.pack_slab([mdl.w for mdl in models])), g.put(_device.pack_slab([mdl.g_w for mdl in models]))
+        g.call("fmx_sftrl_grid", m0._sketch_dim(), len(models), ms, etas, max(mdl.m for mdl in models), float(m0._thres), 0 if is_cls else 1,
+               BP, BN, counts, w, g_w)
+        _device.check_status(g.host_status(), "fmx_sftrl_grid", "num_feature")
+        ch, ph = counts.cpu(), g.pred.cpu().numpy()
+        BPs, BNs = (_device.unpack_slab(B.cpu(), [mdl.BT_P.shape for mdl in models]) for B in (BP, BN))
+        if m0._linear_term:
+            ws, g_ws = (_device.unpack_slab(t.cpu(), [mdl.w.shape for mdl in models]) for t in (w, g_w))
         out = []
-        for s, (mdl, (_, m)) in enumerate(zip(models, settings)):
-            mdl.BT_P = BPh[s, :d * 2 * m].reshape(d, 2 * m).clone()
-            mdl.BT_N = BNh[s, :d * 2 * m].reshape(d, 2 * m).clone()
-            mdl.row_count_p, mdl.row_count_n = int(ch[s, 0]), int(ch[s, 1])
-            if cls._linear_term:
-                mdl.w, mdl.g_w = w[s].cpu().reshape(-1, 1), g_w[s].cpu().reshape(-1, 1)
-            out.append((mdl, ph[s].reshape((n,) + mdl._pred_shape(task == "cls"))))
+        for s, mdl in enumerate(models):
+            mdl.BT_P, mdl.BT_N, mdl.row_count_p, mdl.row_count_n = BPs[s], BNs[s], int(ch[s, 0]), int(ch[s, 1])
+            if m0._linear_term:
+                mdl.w, mdl.g_w = ws[s], g_ws[s]
+            out.append((mdl, ph[s].reshape((g.n,) + mdl._pred_shape(is_cls))))
         return out
 
     def _pred_shape(self, cls):

@@ -1,7 +1,7 @@
 """SFTRL_Vanila -- drop-in for reference models/models_online/SFTRL_Vanila.py:16-130.
 
 As SFTRL_CCFM plus a linear term w = -eta * sum s x (:59-60); the sketches see the feature vector without its last
-entry (:43-44,62)."""
+entry (:43-44,62).  The device path is SFTRL_CCFM's (its glue: _device.py)."""
 import numpy as np
 import torch
 

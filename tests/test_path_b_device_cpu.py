@@ -1,6 +1,7 @@
 """CPU-side checks of the `device=` surface of FM_FTRL and RRF_Online and of their grid() classmethods: the host twin of a
 grid pins the order in which the settings draw their parameters (what the device grid must reproduce), explicit
-device="host" is today's default bit for bit, and include/fmx.h / libfmx.so carry the four entry points."""
+device="host" is today's default bit for bit, and include/fmx.h / libfmx.so carry the four entry points.  Also the slabs a grid
+launch packs its settings' parameters into (models/models_online/_device.py) and the host loops' progress lines."""
 import itertools
 import os
 import random
@@ -135,6 +136,53 @@ def test_empty_grids_and_bad_arguments():
         fm_ftrl().grid(X, y, "rank", [0.1], [4], device="host")
     with pytest.raises(NotImplementedError):             # hinge / l1 are refused before anything runs
         rrf().grid(X, y, "reg", [0.05], [0.05], [6], loss_type="l1", device="host")
+
+
+def test_slab_round_trip():
+    """Tensors of 3, 8 and 1 elements -> one zero-filled [3, 8] slab -> equal tensors that own their memory."""
+    from models.models_online import _device
+    rng = np.random.default_rng(0)
+    tensors = [torch.from_numpy(rng.standard_normal(shape)) for shape in ((3,), (2, 4), (1, 1))]
+    slab = _device.pack_slab(tensors)
+    assert slab.shape == (3, 8) and slab.dtype == torch.float64 and slab.is_contiguous()
+    for s, t in enumerate(tensors):
+        assert torch.equal(slab[s, :t.numel()], t.reshape(-1))
+        assert bool((slab[s, t.numel():] == 0.0).all())
+    back = _device.unpack_slab(slab, [t.shape for t in tensors])
+    assert len(back) == 3
+    for t, b in zip(tensors, back):
+        assert b.shape == t.shape and b.dtype == torch.float64 and torch.equal(b, t)
+    before = slab.clone()
+    for b in back:
+        b.fill_(7.0)
+    assert torch.equal(slab, before)
+
+
+def progress_lines(out):
+    """the ' <idx> th : pred <p> , real <r> ' lines of an online_learning() run -> [(idx, pred text, real text)]"""
+    return [(int(i), p, r) for i, p, r in re.findall(r"^ (\d+) th : pred (\S+) , real (\S+) $", out, flags=re.M)]
+
+
+@pytest.mark.parametrize("task", ["cls", "reg"])
+@pytest.mark.parametrize("name", ["FM_FTRL", "RRF_Online", "SFTRL_CCFM", "SFTRL_Vanila"])
+def test_host_progress_lines_every_1000th_sample(name, task, capsys):
+    """2,001 samples: the smallest stream on which the lines of samples 0, 1000 and 2000 all appear (the host twin of the device
+    tests' test_progress_lines_equal_on_both_devices)."""
+    from models.models_online.SFTRL_CCFM import SFTRL_CCFM
+    from models.models_online.SFTRL_Vanila import SFTRL_Vanila
+    X, y = stream(2001, 8, 7, task)
+    seed_all(9)
+    if name == "RRF_Online":
+        m = rrf()(X, y, task, num_sampled_spectral=6)
+    else:
+        m = dict(FM_FTRL=fm_ftrl(), SFTRL_CCFM=SFTRL_CCFM, SFTRL_Vanila=SFTRL_Vanila)[name](X, y, task, 0.005 if name == "FM_FTRL" else 0.05, 4)
+    m.online_learning()
+    out = capsys.readouterr().out
+    lines = progress_lines(out)
+    assert out.count(" th : pred ") == 3 and [i for i, _, _ in lines] == [0, 1000, 2000]
+    assert [float(r) for _, _, r in lines] == [float("%f" % y[i]) for i in (0, 1000, 2000)]
+    if task == "cls":
+        assert all(p in ("1.000000", "-1.000000") for _, p, _ in lines)
 
 
 NEW_ENTRY_POINTS = ("fmx_ftrl_dense_run", "fmx_ftrl_dense_grid", "fmx_rrf_run", "fmx_rrf_grid")

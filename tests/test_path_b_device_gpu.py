@@ -15,6 +15,7 @@ import ctypes as C
 import itertools
 import os
 import random
+import re
 
 import numpy as np
 import pytest
@@ -186,6 +187,40 @@ def test_rrf_reg_full_fixture_length_vs_host(golden_dir, capsys):
     assert pg.shape == ph.shape == (300, 1)
     for name, v in figures.items():
         assert v <= tol, (name, v)
+
+
+def progress_lines(out):
+    """the ' <idx> th : pred <p> , real <r> ' lines of an online_learning() run -> [(idx, pred text, real text)]"""
+    return [(int(i), p, r) for i, p, r in re.findall(r"^ (\d+) th : pred (\S+) , real (\S+) $", out, flags=re.M)]
+
+
+@pytest.mark.parametrize("task", ["cls", "reg"])
+@pytest.mark.parametrize("name", ["FM_FTRL", "RRF_Online"])
+def test_progress_lines_equal_on_both_devices(name, task, capsys):
+    """2,001 samples of 8 features, the smallest stream on which the lines of samples 0, 1000 and 2000 all appear: the device run
+    prints what the host loop prints.  cls: the +-1 as text; reg: as numbers under the class's fixture tolerance (%f rounds to 1e-6, so
+    scores equal to that tolerance can still differ in the last printed digit)."""
+    X, y = make_stream(2001, 8, 7, task)
+    Xt, yt = torch.DoubleTensor(X), torch.DoubleTensor(y)
+    outs = {}
+    for device in ("host", "gpu"):
+        seed_all(9)
+        m = (FM()(Xt, yt, task, 0.005, 8, device=device) if name == "FM_FTRL"
+             else RRF()(Xt, yt, task, num_sampled_spectral=6, device=device))
+        m.online_learning()
+        outs[device] = capsys.readouterr().out
+    h, g = progress_lines(outs["host"]), progress_lines(outs["gpu"])
+    print(f"{name} {task} host {h}\n{name} {task} gpu  {g}")
+    assert outs["host"].count("\n") == outs["gpu"].count("\n") and len(h) == len(g) == 3
+    assert [i for i, _, _ in g] == [i for i, _, _ in h] == [0, 1000, 2000]
+    assert [r for _, _, r in g] == [r for _, _, r in h]
+    pg, ph = [p for _, p, _ in g], [p for _, p, _ in h]
+    if task == "cls":
+        assert pg == ph and set(pg) <= {"1.000000", "-1.000000"}
+    elif name == "FM_FTRL":
+        np.testing.assert_allclose(np.array(pg, dtype=np.float64), np.array(ph, dtype=np.float64), rtol=RTOL, atol=ATOL)
+    else:
+        assert rel_dev(np.array(pg, dtype=np.float64), np.array(ph, dtype=np.float64)) <= RRF_TOL[task]
 
 
 # ---------------------------------------------------------------- against the host classes on wider shapes

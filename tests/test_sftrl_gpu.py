@@ -4,6 +4,7 @@ against the host fp64 path on wider sketches.  fp64; tolerance 1e-7 relative on 
 Gram matrices B B^T (the columns of B are defined up to sign by an SVD), counters exact."""
 import ctypes as C
 import os
+import re
 
 import numpy as np
 import pytest
@@ -44,6 +45,29 @@ def make_stream(n, D, seed, task):
     s = X @ wt + 0.5 * (X[:, 0] * X[:, 1] - X[:, 2] * X[:, -1]) * D
     y = np.where(s >= 0, 1.0, -1.0) if task == "cls" else s
     return X, y
+
+
+@pytest.mark.parametrize("task", ["cls", "reg"])
+@pytest.mark.parametrize("name", ["SFTRL_CCFM", "SFTRL_Vanila"])
+def test_progress_lines_equal_on_both_devices(name, task, capsys):
+    """2,001 samples of 8 features, the smallest stream on which the lines of samples 0, 1000 and 2000 all appear: the device run
+    prints what the host loop prints.  cls: the +-1 as text; reg: as numbers under the fixture test's tolerance."""
+    X, y = make_stream(2001, 8, 7, task)
+    outs = {}
+    for device in ("host", "gpu"):
+        classes()[name](torch.DoubleTensor(X), torch.DoubleTensor(y), task, 0.05, 4, device=device).online_learning()
+        outs[device] = capsys.readouterr().out
+    h, g = ([(int(i), p, r) for i, p, r in re.findall(r"^ (\d+) th : pred (\S+) , real (\S+) $", outs[device], flags=re.M)]
+            for device in ("host", "gpu"))
+    print(f"{name} {task} host {h}\n{name} {task} gpu  {g}")
+    assert outs["host"].count("\n") == outs["gpu"].count("\n") and len(h) == len(g) == 3
+    assert [i for i, _, _ in g] == [i for i, _, _ in h] == [0, 1000, 2000]
+    assert [r for _, _, r in g] == [r for _, _, r in h]
+    pg, ph = [p for _, p, _ in g], [p for _, p, _ in h]
+    if task == "cls":
+        assert pg == ph and set(pg) <= {"1.000000", "-1.000000"}
+    else:
+        np.testing.assert_allclose(np.array(pg, dtype=np.float64), np.array(ph, dtype=np.float64), rtol=1e-7, atol=1e-9)
 
 
 @pytest.mark.parametrize("name,task,D,m", [("SFTRL_CCFM", "cls", 32, 8), ("SFTRL_CCFM", "reg", 20, 32), ("SFTRL_Vanila", "cls", 33, 5),
