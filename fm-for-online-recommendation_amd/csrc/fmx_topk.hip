@@ -175,16 +175,35 @@ __device__ void init_slots(Slots &s, uint64_t *lds, int n, int cap) {
   __syncthreads();
 }
 
+}  // namespace
+
+#include "fmx_rank.inc"
+
+namespace {
+
 // grid (user tiles, splits).  Thread t scores candidate c0 + t against every user of the tile; the user's S_u and a_u are
 // wave-uniform (scalar loads), the candidate's S_c row sits in the thread's registers for the whole chunk.
 //   score(u, c) = (au[u] + ac[c]) + dot,   dot = fma(Su[kp-1], Sc[kp-1], ... fma(Su[1], Sc[1], Su[0] * Sc[0]))
-template <int KP>
-__global__ __launch_bounds__(TK_THREADS) void k_topk_scan(TopkArgs a) {
+// MODE (fmx_rank.inc): the top-K selection (Args = TopkArgs), or one of the rank call's two phases (Args = FmRankArgs; ut = 1
+// and grid (U, T) for SCAN_KEYS).
+template <int KP, int MODE = SCAN_TOPK, class Args = TopkArgs>
+__global__ __launch_bounds__(TK_THREADS) void k_topk_scan(Args a) {
   extern __shared__ uint64_t tk_lds[];
   Slots s;
+  RankLds rk;
+  int target = -1;
   const int u0 = blockIdx.x * a.ut, nu = min(a.ut, a.U - u0);
-  init_slots(s, tk_lds, nu, a.cap);
-  const int c_begin = blockIdx.y * a.per, c_end = min(a.N, c_begin + a.per);
+  if constexpr (MODE == SCAN_TOPK) init_slots(s, tk_lds, nu, a.cap);
+  if constexpr (MODE == SCAN_COUNT) {
+    __shared__ RankShared<TK_MAX_UT> sh;
+    init_rank(rk, sh, a.r.tkeys + (size_t)u0 * a.r.T, nu, a.r.T);
+  }
+  if constexpr (MODE == SCAN_KEYS) {
+    target = keys_target(a.r, u0, blockIdx.y, a.N);
+    if (target < 0) return;
+  }
+  const int c_begin = MODE == SCAN_KEYS ? target / TK_THREADS * TK_THREADS : blockIdx.y * a.per;
+  const int c_end = min(a.N, c_begin + (MODE == SCAN_KEYS ? TK_THREADS : a.per));
   const float *__restrict__ Su = a.Su;
   const float *__restrict__ au = a.au;
   for (int c0 = c_begin; c0 < c_end; c0 += TK_THREADS) {
@@ -224,22 +243,36 @@ __global__ __launch_bounds__(TK_THREADS) void k_topk_scan(TopkArgs a) {
         const int j = j0 + r;
         if (R > 1 && j >= nu) break;
         const uint64_t key = make_key(score[r], c);
-        bool keep = valid && score[r] == score[r] && key > s.thr[j];
-        if (keep && a.excl_off) keep = !excluded(a.excl_off, a.excl_pos, u0 + j, c);
-        append(s, j, a.cap, keep, key);
+        if constexpr (MODE == SCAN_TOPK) {
+          bool keep = valid && score[r] == score[r] && key > s.thr[j];
+          if (keep && a.excl_off) keep = !excluded(a.excl_off, a.excl_pos, u0 + j, c);
+          append(s, j, a.cap, keep, key);
+        } else if constexpr (MODE == SCAN_COUNT) {
+          count_pair(rk, j, a.r.T, valid, score[r], key, a.excl_off, a.excl_pos, u0 + j, c);
+        } else if (valid && c == target) {
+          a.r.tkeys[(size_t)u0 * a.r.T + blockIdx.y] = target_key(score[r], c, a.excl_off, a.excl_pos, u0);
+        }
       }
     }
-    __syncthreads();
-    // after the first chunk every slot is cut to K at once (the thresholds start rising); later only slots that could overflow
-    compact(s, nu, a.cap, a.K, c0 == c_begin ? a.K : a.cap - TK_THREADS);
+    if constexpr (MODE == SCAN_TOPK) {
+      __syncthreads();
+      // after the first chunk every slot is cut to K at once (the thresholds start rising); later only slots that could overflow
+      compact(s, nu, a.cap, a.K, c0 == c_begin ? a.K : a.cap - TK_THREADS);
+    }
   }
-  compact(s, nu, a.cap, a.K, -1);
-  for (int j = 0; j < nu; ++j) {
-    const int u = u0 + j;
-    if (a.splits > 1)
-      emit(s, j, a.cap, a.K, a.parts + ((size_t)u * a.splits + blockIdx.y) * a.K, nullptr, nullptr);
-    else
-      emit(s, j, a.cap, a.K, nullptr, a.top_pos + (size_t)u * a.K, a.top_score + (size_t)u * a.K);
+  if constexpr (MODE == SCAN_COUNT) {
+    __syncthreads();
+    emit_counts(rk, a.r, u0, nu, a.splits, blockIdx.y);
+  }
+  if constexpr (MODE == SCAN_TOPK) {
+    compact(s, nu, a.cap, a.K, -1);
+    for (int j = 0; j < nu; ++j) {
+      const int u = u0 + j;
+      if (a.splits > 1)
+        emit(s, j, a.cap, a.K, a.parts + ((size_t)u * a.splits + blockIdx.y) * a.K, nullptr, nullptr);
+      else
+        emit(s, j, a.cap, a.K, nullptr, a.top_pos + (size_t)u * a.K, a.top_score + (size_t)u * a.K);
+    }
   }
 }
 
@@ -388,6 +421,9 @@ struct MlpTopkArgs {
   float *top_score;
   int ld_u, ld_c, U, N, K, kp, k, H, L, K0, Hp, fm_term, cap, splits, per;
 };
+struct MlpRankArgs : MlpTopkArgs {
+  RankIo r;
+};
 
 // activation (row r < 64, column d) of a chunk with G groups of 16 columns: [row tile][G][lane 16 (d % 4) + r % 16][(d / 4) % 4]
 __device__ __forceinline__ int xidx(int r, int d, int G) {
@@ -396,22 +432,35 @@ __device__ __forceinline__ int xidx(int r, int d, int G) {
 
 // grid (U, splits).  Per chunk of 64 candidates: x0 into LDS, the L layers (MFMA, then relu into the same buffer between two
 // barriers), then wave 0 scores row r = candidate c0 + r and appends it to the user's slot.
-template <int WC, int NCT>
-__global__ __launch_bounds__(256) void k_mlp_topk_scan(MlpTopkArgs a) {
+// MODE (fmx_rank.inc): the top-K selection (Args = MlpTopkArgs), or one of the rank call's two phases (Args = MlpRankArgs;
+// grid (U, T) for SCAN_KEYS).  MFMA rows are independent: a pair's score does not depend on the chunk it is computed in.
+template <int WC, int NCT, int MODE = SCAN_TOPK, class Args = MlpTopkArgs>
+__global__ __launch_bounds__(256) void k_mlp_topk_scan(Args a) {
   extern __shared__ __attribute__((aligned(16))) float tm_lds[];
   constexpr int RPW = WC;  // row tiles per wave (4 row tiles over 4 / WC wave rows)
   const int NT = a.Hp / 16;
   const int wmax = a.K0 > a.Hp ? a.K0 : a.Hp;
   float *X = tm_lds;
   Slots s;
-  init_slots(s, reinterpret_cast<uint64_t *>(X + (size_t)TM_ROWS * wmax), 1, a.cap);
+  RankLds rk;
+  int target = -1;
+  if constexpr (MODE == SCAN_TOPK) init_slots(s, reinterpret_cast<uint64_t *>(X + (size_t)TM_ROWS * wmax), 1, a.cap);
+  if constexpr (MODE == SCAN_COUNT) {
+    __shared__ RankShared<1> sh;
+    init_rank(rk, sh, a.r.tkeys + (size_t)blockIdx.x * a.r.T, 1, a.r.T);
+  }
+  if constexpr (MODE == SCAN_KEYS) {
+    target = keys_target(a.r, blockIdx.x, blockIdx.y, a.N);
+    if (target < 0) return;
+  }
   const int t = threadIdx.x, lane = t & 63, w = t >> 6, wr = w / WC, wc = w % WC;
   const int m = lane & 15, kq = lane >> 4;
   const int u = blockIdx.x;
   const float *__restrict__ Su = a.Su + (size_t)u * a.ld_u;
   const float *__restrict__ Bu = a.Bu + (size_t)u * a.ld_u;
   const float au = a.au[u];
-  const int c_begin = blockIdx.y * a.per, c_end = min(a.N, c_begin + a.per);
+  const int c_begin = MODE == SCAN_KEYS ? target / TM_ROWS * TM_ROWS : blockIdx.y * a.per;
+  const int c_end = min(a.N, c_begin + (MODE == SCAN_KEYS ? TM_ROWS : a.per));
   const int G0 = a.K0 / 16, Gh = a.Hp / 16;
   for (int c0 = c_begin; c0 < c_end; c0 += TM_ROWS) {
     // x0[r][d] = fma(Su[d], Sc[d], Bu[d] + Bc[d]) for d < k, 0 on the pad columns (rows past the split repeat its last one)
@@ -487,18 +536,27 @@ __global__ __launch_bounds__(256) void k_mlp_topk_scan(MlpTopkArgs a) {
       }
       const float score = base + sum;
       const uint64_t key = make_key(score, c);
-      bool keep = valid && score == score && key > s.thr[0];
-      if (keep && a.excl_off) keep = !excluded(a.excl_off, a.excl_pos, u, c);
-      append(s, 0, a.cap, keep, key);
+      if constexpr (MODE == SCAN_TOPK) {
+        bool keep = valid && score == score && key > s.thr[0];
+        if (keep && a.excl_off) keep = !excluded(a.excl_off, a.excl_pos, u, c);
+        append(s, 0, a.cap, keep, key);
+      } else if constexpr (MODE == SCAN_COUNT) {
+        count_pair(rk, 0, a.r.T, valid, score, key, a.excl_off, a.excl_pos, u, c);
+      } else if (valid && c == target) {
+        a.r.tkeys[(size_t)u * a.r.T + blockIdx.y] = target_key(score, c, a.excl_off, a.excl_pos, u);
+      }
     }
-    __syncthreads();
-    compact(s, 1, a.cap, a.K, c0 == c_begin ? a.K : a.cap - TM_ROWS);
+    __syncthreads();  // the row sums have been read: the next chunk may overwrite the activations
+    if constexpr (MODE == SCAN_TOPK) compact(s, 1, a.cap, a.K, c0 == c_begin ? a.K : a.cap - TM_ROWS);
   }
-  compact(s, 1, a.cap, a.K, -1);
-  if (a.splits > 1)
-    emit(s, 0, a.cap, a.K, a.parts + ((size_t)u * a.splits + blockIdx.y) * a.K, nullptr, nullptr);
-  else
-    emit(s, 0, a.cap, a.K, nullptr, a.top_pos + (size_t)u * a.K, a.top_score + (size_t)u * a.K);
+  if constexpr (MODE == SCAN_COUNT) emit_counts(rk, a.r, u, 1, a.splits, blockIdx.y);
+  if constexpr (MODE == SCAN_TOPK) {
+    compact(s, 1, a.cap, a.K, -1);
+    if (a.splits > 1)
+      emit(s, 0, a.cap, a.K, a.parts + ((size_t)u * a.splits + blockIdx.y) * a.K, nullptr, nullptr);
+    else
+      emit(s, 0, a.cap, a.K, nullptr, a.top_pos + (size_t)u * a.K, a.top_score + (size_t)u * a.K);
+  }
 }
 // ---------------------------------------------------------------------------------------------------------------------
 // fmx_afm_topk: the same selection over the exact AFM logit of the combined sample
@@ -521,6 +579,9 @@ struct AfmTopkArgs {
   int32_t *top_pos;
   float *top_score;
   int U, N, K, t, n_ctx, n_item, cap, splits, per;
+};
+struct AfmRankArgs : AfmTopkArgs {
+  RankIo r;
 };
 
 inline int64_t at_pair_flops(int n_ctx, int n_item, int t, int kp) {
@@ -561,11 +622,23 @@ __global__ __launch_bounds__(256) void k_afm_topk_pack(const float *params, int 
 
 // grid (U, splits).  The score (include/fmx.h, fmx_afm_topk): the cross pairs j-major (item field j ascending, then context
 // field i ascending), each as k_afm's pair_terms, folded into a running (max, Z, R) by online rescaling, then the two sides.
-template <int KP>
-__global__ __launch_bounds__(TK_THREADS) void k_afm_topk_scan(AfmTopkArgs a) {
+// MODE (fmx_rank.inc): the top-K selection (Args = AfmTopkArgs), or one of the rank call's two phases (Args = AfmRankArgs; grid
+// (U, T) for SCAN_KEYS).
+template <int KP, int MODE = SCAN_TOPK, class Args = AfmTopkArgs>
+__global__ __launch_bounds__(TK_THREADS) void k_afm_topk_scan(Args a) {
   extern __shared__ uint64_t tk_lds[];
   Slots s;
-  init_slots(s, tk_lds, 1, a.cap);
+  RankLds rk;
+  int target = -1;
+  if constexpr (MODE == SCAN_TOPK) init_slots(s, tk_lds, 1, a.cap);
+  if constexpr (MODE == SCAN_COUNT) {
+    __shared__ RankShared<1> sh;
+    init_rank(rk, sh, a.r.tkeys + (size_t)blockIdx.x * a.r.T, 1, a.r.T);
+  }
+  if constexpr (MODE == SCAN_KEYS) {
+    target = keys_target(a.r, blockIdx.x, blockIdx.y, a.N);
+    if (target < 0) return;
+  }
   const int u = blockIdx.x, t = a.t;
   const float *__restrict__ W = a.packed;
   const float *__restrict__ bW = W + t * KP;
@@ -573,7 +646,8 @@ __global__ __launch_bounds__(TK_THREADS) void k_afm_topk_scan(AfmTopkArgs a) {
   const float *__restrict__ p = h + t;
   const float *__restrict__ Eu = a.Eu + (size_t)u * a.n_ctx * KP;
   const float4 stu = reinterpret_cast<const float4 *>(a.su)[u];  // (lin_u, m_u, Z_u, R_u)
-  const int c_begin = blockIdx.y * a.per, c_end = min(a.N, c_begin + a.per);
+  const int c_begin = MODE == SCAN_KEYS ? target / TK_THREADS * TK_THREADS : blockIdx.y * a.per;
+  const int c_end = min(a.N, c_begin + (MODE == SCAN_KEYS ? TK_THREADS : a.per));
   for (int c0 = c_begin; c0 < c_end; c0 += TK_THREADS) {
     const int c = c0 + (int)threadIdx.x;
     const bool valid = c < c_end;
@@ -620,17 +694,29 @@ __global__ __launch_bounds__(TK_THREADS) void k_afm_topk_scan(AfmTopkArgs a) {
     const float R = fmaf(Rx, ex, fmaf(stc.w, ec_, stu.w * eu_));
     const float score = (stu.x + stc.x) + R / Z;
     const uint64_t key = make_key(score, c);
-    bool keep = valid && score == score && key > s.thr[0];
-    if (keep && a.excl_off) keep = !excluded(a.excl_off, a.excl_pos, u, c);
-    append(s, 0, a.cap, keep, key);
-    __syncthreads();
-    compact(s, 1, a.cap, a.K, c0 == c_begin ? a.K : a.cap - TK_THREADS);
+    if constexpr (MODE == SCAN_TOPK) {
+      bool keep = valid && score == score && key > s.thr[0];
+      if (keep && a.excl_off) keep = !excluded(a.excl_off, a.excl_pos, u, c);
+      append(s, 0, a.cap, keep, key);
+      __syncthreads();
+      compact(s, 1, a.cap, a.K, c0 == c_begin ? a.K : a.cap - TK_THREADS);
+    } else if constexpr (MODE == SCAN_COUNT) {
+      count_pair(rk, 0, a.r.T, valid, score, key, a.excl_off, a.excl_pos, u, c);
+    } else if (valid && c == target) {
+      a.r.tkeys[(size_t)u * a.r.T + blockIdx.y] = target_key(score, c, a.excl_off, a.excl_pos, u);
+    }
   }
-  compact(s, 1, a.cap, a.K, -1);
-  if (a.splits > 1)
-    emit(s, 0, a.cap, a.K, a.parts + ((size_t)u * a.splits + blockIdx.y) * a.K, nullptr, nullptr);
-  else
-    emit(s, 0, a.cap, a.K, nullptr, a.top_pos + (size_t)u * a.K, a.top_score + (size_t)u * a.K);
+  if constexpr (MODE == SCAN_COUNT) {
+    __syncthreads();
+    emit_counts(rk, a.r, u, 1, a.splits, blockIdx.y);
+  }
+  if constexpr (MODE == SCAN_TOPK) {
+    compact(s, 1, a.cap, a.K, -1);
+    if (a.splits > 1)
+      emit(s, 0, a.cap, a.K, a.parts + ((size_t)u * a.splits + blockIdx.y) * a.K, nullptr, nullptr);
+    else
+      emit(s, 0, a.cap, a.K, nullptr, a.top_pos + (size_t)u * a.K, a.top_score + (size_t)u * a.K);
+  }
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -674,27 +760,40 @@ int check_topk_sizes(const char *fn, int32_t U, int32_t N, int32_t K) {
   return FMX_OK;
 }
 
-int check_network(const fmx_mlp_t *mlp) {
+int check_network(const fmx_mlp_t *mlp, const char *fn = "fmx_mlp_topk") {
   if (mlp->n_layers < 1 || mlp->n_layers > TM_MAX_L || mlp->hidden < 1 || mlp->hidden > TM_MAX_H || mlp->k < 1 || mlp->k > 64)
-    return fail(FMX_ERR_UNSUPPORTED, "fmx_mlp_topk: needs 1 <= layers <= %d, 1 <= hidden <= %d, 1 <= k <= 64 (got %d, %d, %d)", TM_MAX_L,
+    return fail(FMX_ERR_UNSUPPORTED, "%s: needs 1 <= layers <= %d, 1 <= hidden <= %d, 1 <= k <= 64 (got %d, %d, %d)", fn, TM_MAX_L,
                 TM_MAX_H, mlp->n_layers, mlp->hidden, mlp->k);
   return FMX_OK;
 }
 
 // The checks both entry points make, in this order.  A kp outside 4/8/16/32/64 returns bad_kp (include/fmx.h: FMX_ERR_SHAPE
 // from fmx_fm_topk, FMX_ERR_UNSUPPORTED from fmx_mlp_topk).  net: fmx_mlp_topk's checked network, null for fmx_fm_topk.
-int check_topk_args(const char *fn, int bad_kp, const MlpShape *net, const float *Su, int32_t ld_u, const float *au, int32_t U,
-                    const float *Sc, int32_t ld_c, const float *ac, int32_t N, int32_t kp, const int32_t *excl_off,
-                    const int32_t *excl_pos, int32_t K, const void *ws, int64_t ws_bytes, const int32_t *top_pos,
-                    const float *top_score) {
-  if (!Su || !au || !Sc || !ac || !ws || !top_pos || !top_score) return fail(FMX_ERR_ARG, "%s: null argument", fn);
+// The pointer checks (first) and the layout checks (after the sizes) of the two sides, shared with the rank calls
+// (fmx_rank.inc): out_a / out_b are the call's two required outputs.
+int check_pair_ptrs(const char *fn, const float *Su, const float *au, const float *Sc, const float *ac, const int32_t *excl_off,
+                    const int32_t *excl_pos, const void *ws, const void *out_a, const void *out_b) {
+  if (!Su || !au || !Sc || !ac || !ws || !out_a || !out_b) return fail(FMX_ERR_ARG, "%s: null argument", fn);
   if ((excl_off == nullptr) != (excl_pos == nullptr)) return fail(FMX_ERR_ARG, "%s: excl_offsets and excl_pos go together", fn);
-  if (int rc = check_topk_sizes(fn, U, N, K)) return rc;
+  return FMX_OK;
+}
+int check_pair_layout(const char *fn, int bad_kp, const float *Su, int32_t ld_u, const float *Sc, int32_t ld_c, int32_t kp,
+                      const void *ws) {
   if (kp != 4 && kp != 8 && kp != 16 && kp != 32 && kp != 64) return fail(bad_kp, "%s: kp=%d must be 4/8/16/32/64", fn, kp);
   if (ld_u < kp || ld_c < kp || ld_u % 4 || ld_c % 4)
     return fail(FMX_ERR_SHAPE, "%s: ld_u=%d and ld_c=%d must be multiples of 4 and >= kp=%d", fn, ld_u, ld_c, kp);
   if (!aligned16(Su) || !aligned16(Sc) || !aligned16(ws))
     return fail(FMX_ERR_ALIGN, "%s: Su, Sc and the workspace must be 16-byte aligned", fn);
+  return FMX_OK;
+}
+
+int check_topk_args(const char *fn, int bad_kp, const MlpShape *net, const float *Su, int32_t ld_u, const float *au, int32_t U,
+                    const float *Sc, int32_t ld_c, const float *ac, int32_t N, int32_t kp, const int32_t *excl_off,
+                    const int32_t *excl_pos, int32_t K, const void *ws, int64_t ws_bytes, const int32_t *top_pos,
+                    const float *top_score) {
+  if (int rc = check_pair_ptrs(fn, Su, au, Sc, ac, excl_off, excl_pos, ws, top_pos, top_score)) return rc;
+  if (int rc = check_topk_sizes(fn, U, N, K)) return rc;
+  if (int rc = check_pair_layout(fn, bad_kp, Su, ld_u, Sc, ld_c, kp, ws)) return rc;
   const int64_t need = net ? mlp_topk_ws_bytes(*net, U, N, K) : topk_ws_bytes(U, N, K);
   if (ws_bytes < need)
     return fail(FMX_ERR_SHAPE, "%s: workspace of %lld bytes, %s_workspace_bytes(%s%d, %d, %d) = %lld", fn, (long long)ws_bytes, fn,
@@ -791,14 +890,45 @@ int fmx_mlp_topk(const fmx_mlp_t *mlp, int32_t fm_term, const float *Su, const f
 
 namespace {
 
+// what fmx_afm_topk and the AFM rank call (fmx_rank.inc) check alike, around their own size checks
+int check_afm_pair_shape(const char *fn, const fmx_afm_t *afm, int32_t n_ctx, int32_t n_item) {
+  if (afm->t < 1 || afm->t > 64 || afm->k < 1 || afm->k > 64)
+    return fail(FMX_ERR_UNSUPPORTED, "%s: needs 1 <= t <= 64 and 1 <= k <= 64 (got t=%d, k=%d)", fn, afm->t, afm->k);
+  if (n_ctx < 1 || n_item < 1) return fail(FMX_ERR_SHAPE, "%s: n_ctx=%d and n_item=%d must be >= 1", fn, n_ctx, n_item);
+  if (n_ctx + n_item > 64) return fail(FMX_ERR_UNSUPPORTED, "%s: n_ctx + n_item = %d, the AFM takes at most 64 fields", fn, n_ctx + n_item);
+  return FMX_OK;
+}
+int check_afm_pair_args(const char *fn, const fmx_afm_t *afm, const float *Eu, const float *stats_u, const float *Ec,
+                        const float *stats_c, int32_t kp, const int32_t *excl_offsets, const int32_t *excl_pos, const void *workspace,
+                        const void *out_a, const void *out_b) {
+  if (!afm->params || !Eu || !stats_u || !Ec || !stats_c || !workspace || !out_a || !out_b) return fail(FMX_ERR_ARG, "%s: null argument", fn);
+  if ((excl_offsets == nullptr) != (excl_pos == nullptr)) return fail(FMX_ERR_ARG, "%s: excl_offsets and excl_pos go together", fn);
+  if ((kp != 4 && kp != 8 && kp != 16 && kp != 32 && kp != 64) || kp < afm->k)
+    return fail(FMX_ERR_SHAPE, "%s: kp=%d must be 4/8/16/32/64 and >= k=%d", fn, kp, afm->k);
+  if (!aligned16(Eu) || !aligned16(stats_u) || !aligned16(Ec) || !aligned16(stats_c) || !aligned16(workspace))
+    return fail(FMX_ERR_ALIGN, "%s: Eu, stats_u, Ec, stats_c and the workspace must be 16-byte aligned", fn);
+  return FMX_OK;
+}
+
 int check_afm_topk_shape(const fmx_afm_t *afm, int32_t n_ctx, int32_t n_item, int32_t U, int32_t N, int32_t K) {
   if (!afm) return fail(FMX_ERR_ARG, "fmx_afm_topk: null afm");
   if (int rc = check_topk_sizes("fmx_afm_topk", U, N, K)) return rc;
-  if (afm->t < 1 || afm->t > 64 || afm->k < 1 || afm->k > 64)
-    return fail(FMX_ERR_UNSUPPORTED, "fmx_afm_topk: needs 1 <= t <= 64 and 1 <= k <= 64 (got t=%d, k=%d)", afm->t, afm->k);
-  if (n_ctx < 1 || n_item < 1) return fail(FMX_ERR_SHAPE, "fmx_afm_topk: n_ctx=%d and n_item=%d must be >= 1", n_ctx, n_item);
-  if (n_ctx + n_item > 64) return fail(FMX_ERR_UNSUPPORTED, "fmx_afm_topk: n_ctx + n_item = %d, the AFM takes at most 64 fields", n_ctx + n_item);
-  return FMX_OK;
+  return check_afm_pair_shape("fmx_afm_topk", afm, n_ctx, n_item);
+}
+
+// geometry of the AFM scans: one user per workgroup, splits = ceil(budget / U) within [1, max splits], a split a multiple of
+// the chunk
+struct AfmGeom {
+  int per, splits;
+};
+inline AfmGeom afm_scan_geom(const fmx_afm_t *afm, int n_ctx, int n_item, int U, int N) {
+  const int64_t sm = at_split_min(n_ctx, n_item, afm->t, at_kp(afm->k));
+  const int64_t sp = std::max<int64_t>(1, std::min<int64_t>(at_max_splits(sm, N), (AT_TILE_BUDGET + U - 1) / U));
+  const int64_t per0 = (N + sp - 1) / sp;
+  AfmGeom g;
+  g.per = (int)((per0 + TK_THREADS - 1) / TK_THREADS * TK_THREADS);
+  g.splits = (N + g.per - 1) / g.per;
+  return g;
 }
 
 }  // namespace
@@ -814,23 +944,14 @@ int fmx_afm_topk(const fmx_afm_t *afm, const float *Eu, const float *stats_u, in
                  const float *stats_c, int32_t n_item, int32_t N, int32_t kp, const int32_t *excl_offsets, const int32_t *excl_pos,
                  int32_t K, void *workspace, int64_t workspace_bytes, int32_t *top_pos, float *top_score, fmx_stream_t stream) {
   if (int rc = check_afm_topk_shape(afm, n_ctx, n_item, U, N, K)) return rc;
-  if (!afm->params || !Eu || !stats_u || !Ec || !stats_c || !workspace || !top_pos || !top_score)
-    return fail(FMX_ERR_ARG, "fmx_afm_topk: null argument");
-  if ((excl_offsets == nullptr) != (excl_pos == nullptr)) return fail(FMX_ERR_ARG, "fmx_afm_topk: excl_offsets and excl_pos go together");
-  if ((kp != 4 && kp != 8 && kp != 16 && kp != 32 && kp != 64) || kp < afm->k)
-    return fail(FMX_ERR_SHAPE, "fmx_afm_topk: kp=%d must be 4/8/16/32/64 and >= k=%d", kp, afm->k);
-  if (!aligned16(Eu) || !aligned16(stats_u) || !aligned16(Ec) || !aligned16(stats_c) || !aligned16(workspace))
-    return fail(FMX_ERR_ALIGN, "fmx_afm_topk: Eu, stats_u, Ec, stats_c and the workspace must be 16-byte aligned");
+  if (int rc = check_afm_pair_args("fmx_afm_topk", afm, Eu, stats_u, Ec, stats_c, kp, excl_offsets, excl_pos, workspace, top_pos, top_score))
+    return rc;
   const int64_t need = afm_topk_ws_bytes(afm, n_ctx, n_item, U, N, K);
   if (workspace_bytes < need)
     return fail(FMX_ERR_SHAPE, "fmx_afm_topk: workspace of %lld bytes, fmx_afm_topk_workspace_bytes(afm, %d, %d, %d, %d, %d) = %lld",
                 (long long)workspace_bytes, n_ctx, n_item, U, N, K, (long long)need);
-  // geometry: one user per workgroup, splits = ceil(budget / U) within [1, max splits], a split a multiple of the chunk
-  const int64_t sm = at_split_min(n_ctx, n_item, afm->t, at_kp(afm->k));
-  const int64_t sp = std::max<int64_t>(1, std::min<int64_t>(at_max_splits(sm, N), (AT_TILE_BUDGET + U - 1) / U));
-  const int64_t per0 = (N + sp - 1) / sp;
-  const int per = (int)((per0 + TK_THREADS - 1) / TK_THREADS * TK_THREADS);
-  const int splits = (N + per - 1) / per;
+  const AfmGeom g = afm_scan_geom(afm, n_ctx, n_item, U, N);
+  const int per = g.per, splits = g.splits;
   AfmTopkArgs a{Eu, stats_u, Ec, stats_c,
                 static_cast<const float *>(workspace),
                 excl_offsets, excl_pos,
@@ -856,3 +977,5 @@ int fmx_afm_topk(const fmx_afm_t *afm, const float *Eu, const float *stats_u, in
 }
 
 }  // extern "C"
+
+#include "fmx_rank_host.inc"

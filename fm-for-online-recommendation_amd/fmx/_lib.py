@@ -26,11 +26,14 @@ EXPORTS = ["fmx_version", "fmx_last_error_string", "fmx_set_option", "fmx_sorted
            "fmx_fm_topk_workspace_bytes", "fmx_fm_topk", "fmx_mlp_topk_workspace_bytes", "fmx_mlp_topk",
            "fmx_fm_update_occ", "fmx_afm_forward", "fmx_afm_workspace_bytes", "fmx_afm_step",
            "fmx_afm_side", "fmx_afm_topk_workspace_bytes", "fmx_afm_topk", "fmx_mlp_section_opt", "fmx_deepfm_stream_opt",
-           "fmx_mlp_fit_opt", "fmx_online_run_mlp_opt", "fmx_afm_step_opt", "fmx_afm_stream", "fmx_afm_online_run"]
+           "fmx_mlp_fit_opt", "fmx_online_run_mlp_opt", "fmx_afm_step_opt", "fmx_afm_stream", "fmx_afm_online_run",
+           "fmx_fm_rank_workspace_bytes", "fmx_fm_rank", "fmx_mlp_rank_workspace_bytes", "fmx_mlp_rank",
+           "fmx_afm_rank_workspace_bytes", "fmx_afm_rank"]
 
 
 I64_RETURNS = ("fmx_workspace_bytes", "fmx_mlp_section_workspace_bytes", "fmx_fm_topk_workspace_bytes",
-               "fmx_mlp_topk_workspace_bytes", "fmx_afm_workspace_bytes", "fmx_afm_topk_workspace_bytes")   # byte counts: int64_t in include/fmx.h
+               "fmx_mlp_topk_workspace_bytes", "fmx_afm_workspace_bytes", "fmx_afm_topk_workspace_bytes",
+               "fmx_fm_rank_workspace_bytes", "fmx_mlp_rank_workspace_bytes", "fmx_afm_rank_workspace_bytes")   # byte counts: int64_t in include/fmx.h
 
 
 class FmxError(RuntimeError):
@@ -151,6 +154,12 @@ def load():
     lib.fmx_afm_side.argtypes = [TP, AP, HP, p, p, i32, p, i32, i32, p, p, p, p]
     lib.fmx_afm_topk_workspace_bytes.argtypes = [AP, i32, i32, i32, i32, i32]
     lib.fmx_afm_topk.argtypes = [AP, p, p, i32, i32, p, p, i32, i32, i32, p, p, i32, p, i64, p, p, p]
+    lib.fmx_fm_rank_workspace_bytes.argtypes = [i32, i32, i32]
+    lib.fmx_fm_rank.argtypes = [p, i32, p, i32, p, i32, p, i32, i32, p, p, p, i32, i32, p, i64, p, p, p, p]
+    lib.fmx_mlp_rank_workspace_bytes.argtypes = [MP, i32, i32, i32]
+    lib.fmx_mlp_rank.argtypes = [MP, i32, p, p, i32, p, i32, p, p, i32, p, i32, i32, p, p, p, i32, i32, p, i64, p, p, p, p]
+    lib.fmx_afm_rank_workspace_bytes.argtypes = [AP, i32, i32, i32, i32, i32]
+    lib.fmx_afm_rank.argtypes = [AP, p, p, i32, i32, p, p, i32, i32, i32, p, p, p, i32, i32, p, i64, p, p, p, p]
     for name in EXPORTS:
         fn = getattr(lib, name)
         if name in I64_RETURNS:

@@ -18,6 +18,10 @@ forwards of the network on the device, then the same exact selection (topk_netwo
 The attentional FM (AFMAdam) does not decompose over a masked forward: a zeroed field still adds pairs to the softmax.  Each
 side instead keeps its own fields' embeddings and the softmax statistics (lin, m, Z, R) of its own pairs (afm_side,
 fmx_afm_side); fmx_afm_topk computes the cross pairs of every (u, c) and combines the three groups exactly (topk_afm).
+
+Ranking evaluation (rank, rank_network, rank_afm; fmx_fm_rank, fmx_mlp_rank, fmx_afm_rank): for held-out target positions,
+the number of eligible candidates the top-K order puts in front of each -- the index the target would have in an unbounded
+top-K row -- from which ranking_metrics takes hit rate, NDCG, MRR and AUC.
 """
 import ctypes as C
 
@@ -435,3 +439,272 @@ def topk_afm(table, afm, ctx_idx, ctx_xv, candidates, K, exclude=None, hyper=Non
     (Eu, stats_u), off, pos = _context_side(table, candidates, ctx_idx, ctx_xv, exclude, hyper, side)
     top_pos, top_score = afm_topk((params, t), table.k, Eu, stats_u, candidates.Ec, candidates.stats, int(K), off, pos)
     return top_pos.long(), top_score
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# ranking evaluation: the rank of held-out targets among all candidates
+# ---------------------------------------------------------------------------------------------------------------------------
+RANK_MAX_T = 16    # targets per user in one fmx_*_rank call (include/fmx.h); rank / rank_network / rank_afm chunk over more
+
+
+def targets_matrix(targets, U, device):
+    """targets: a [U] or [U, T] array or tensor of candidate positions, or a list of U lists (ragged rows are padded with
+    -1, which no call ranks).  Returns (the int32 [U, T] device matrix, T >= 1; its column chunks of at most RANK_MAX_T
+    columns, contiguous).  Anything that does not have U rows raises ValueError."""
+    if torch.is_tensor(targets):
+        t = targets.detach().cpu().numpy()
+    elif isinstance(targets, np.ndarray):
+        t = targets
+    else:
+        rows = [np.asarray(r.cpu() if torch.is_tensor(r) else r, dtype=np.int64).reshape(-1) for r in targets]
+        if len(rows) != U:
+            raise ValueError(f"targets has {len(rows)} rows for {U} users")
+        T = max([len(r) for r in rows] + [1])
+        t = np.full((U, T), -1, dtype=np.int64)
+        for u, r in enumerate(rows):
+            t[u, :len(r)] = r
+    t = np.asarray(t, dtype=np.int64)
+    if t.ndim == 1:
+        t = t[:, None]
+    if t.ndim != 2 or t.shape[0] != U:
+        raise ValueError(f"targets of shape {tuple(t.shape)} for {U} users: [U] or [U, T]")
+    if t.shape[1] == 0:
+        t = np.full((U, 1), -1, dtype=np.int64)
+    t = np.where((t < 0) | (t >= 2 ** 31 - 1), -1, t).astype(np.int32)
+    full = torch.from_numpy(np.ascontiguousarray(t)).to(device)
+    return full, [full[:, c0:c0 + RANK_MAX_T].contiguous() for c0 in range(0, full.shape[1], RANK_MAX_T)]
+
+
+def _rank_buffers(need, U, T, dev, workspace, out, stream):
+    """The rank calls' buffers: the workspace and stream of _call_buffers, out = (rank int32 [U, T], score fp32 [U, T], n_cand
+    int32 [U]) when not given."""
+    if out is None:
+        out = (torch.empty((U, T), dtype=torch.int32, device=dev), torch.empty((U, T), dtype=torch.float32, device=dev),
+               torch.empty(U, dtype=torch.int32, device=dev))
+    return _call_buffers(need, U, T, dev, workspace, out, stream)
+
+
+def _targets_arg(targets, U):
+    if targets.dtype != torch.int32 or targets.dim() != 2 or targets.shape[0] != U or not targets.is_contiguous():
+        raise ValueError(f"targets: a contiguous int32 [U = {U}, T] device tensor")
+    return targets.shape[1]
+
+
+def fm_rank(Su, au, Sc, ac, targets, filtered=False, excl_offsets=None, excl_pos=None, workspace=None, out=None, stream=None,
+            kp=None):
+    """The raw call of fmx_fm_rank: fm_topk's arguments with targets int32 [U, T <= 16] (contiguous, on the device) in place
+    of K.  Returns device tensors (rank int32 [U, T], -1: not eligible; score fp32 [U, T], -inf there; n_cand int32 [U])."""
+    U, N = Su.shape[0], Sc.shape[0]
+    kp = Sc.shape[1] if kp is None else int(kp)
+    T = _targets_arg(targets, U)
+    lib = _lib.load()
+    ws, ws_n, out, st = _rank_buffers(lib.fmx_fm_rank_workspace_bytes(U, N, T), U, T, Su.device, workspace, out, stream)
+    _lib.check(lib.fmx_fm_rank(Su.data_ptr(), Su.stride(0), au.data_ptr(), U, Sc.data_ptr(), Sc.stride(0), ac.data_ptr(), N, kp,
+                               _ptr(excl_offsets), _ptr(excl_pos), targets.data_ptr(), T, int(bool(filtered)), ws, ws_n,
+                               out[0].data_ptr(), out[1].data_ptr(), out[2].data_ptr(), st))
+    return out
+
+
+def mlp_rank(mlp, fm_term, Su, Bu, au, Sc, Bc, ac, targets, filtered=False, excl_offsets=None, excl_pos=None, workspace=None,
+             out=None, stream=None, kp=None):
+    """The raw call of fmx_mlp_rank: mlp_topk's arguments with targets int32 [U, T <= 16] in place of K.  Returns as fm_rank."""
+    U, N = Su.shape[0], Sc.shape[0]
+    kp = Sc.shape[1] if kp is None else int(kp)
+    if Bu.stride(0) != Su.stride(0) or Bc.stride(0) != Sc.stride(0):
+        raise ValueError("Bu / Bc must share the row strides of Su / Sc")
+    T = _targets_arg(targets, U)
+    lib, m = _lib.load(), _mlp_struct(mlp)
+    ws, ws_n, out, st = _rank_buffers(lib.fmx_mlp_rank_workspace_bytes(C.byref(m), U, N, T), U, T, Su.device, workspace, out,
+                                      stream)
+    _lib.check(lib.fmx_mlp_rank(C.byref(m), int(fm_term), Su.data_ptr(), Bu.data_ptr(), Su.stride(0), au.data_ptr(), U,
+                                Sc.data_ptr(), Bc.data_ptr(), Sc.stride(0), ac.data_ptr(), N, kp, _ptr(excl_offsets),
+                                _ptr(excl_pos), targets.data_ptr(), T, int(bool(filtered)), ws, ws_n, out[0].data_ptr(),
+                                out[1].data_ptr(), out[2].data_ptr(), st))
+    return out
+
+
+def afm_rank(afm, k, Eu, stats_u, Ec, stats_c, targets, filtered=False, excl_offsets=None, excl_pos=None, workspace=None,
+             out=None, stream=None):
+    """The raw call of fmx_afm_rank: afm_topk's arguments with targets int32 [U, T <= 16] in place of K.  Returns as fm_rank."""
+    params, t = afm
+    U, n_ctx, kp = Eu.shape
+    N, n_item = Ec.shape[0], Ec.shape[1]
+    if Ec.shape[2] != kp or not all(x.is_contiguous() for x in (Eu, stats_u, Ec, stats_c)):
+        raise ValueError("Eu / Ec: contiguous [rows, fields, kp] with the same kp; stats contiguous [rows, 4]")
+    T = _targets_arg(targets, U)
+    a = _lib.Afm(params.data_ptr(), int(k), int(t))
+    lib = _lib.load()
+    ws, ws_n, out, st = _rank_buffers(lib.fmx_afm_rank_workspace_bytes(C.byref(a), n_ctx, n_item, U, N, T), U, T, Eu.device,
+                                      workspace, out, stream)
+    _lib.check(lib.fmx_afm_rank(C.byref(a), Eu.data_ptr(), stats_u.data_ptr(), n_ctx, U, Ec.data_ptr(), stats_c.data_ptr(), n_item,
+                                N, kp, _ptr(excl_offsets), _ptr(excl_pos), targets.data_ptr(), T, int(bool(filtered)), ws, ws_n,
+                                out[0].data_ptr(), out[1].data_ptr(), out[2].data_ptr(), st))
+    return out
+
+
+def _rank_key(score, pos):
+    """The top-K order as one int64 per (score, position), greater = earlier: make_key of csrc/fmx_topk.hip (score descending,
+    then position ascending, -0 taken as +0).  score fp32, pos integer, same shape."""
+    b = (score.float() + 0.0).contiguous().view(torch.int32).long() & 0xFFFFFFFF
+    o = torch.where(b >= 0x80000000, 0xFFFFFFFF - b, b + 0x80000000)           # the float bits made monotone
+    return ((o - 0x80000000) << 32) + (0xFFFFFFFF - pos.long())                 # shifted into int64's signed range
+
+
+def mlp_rank_torch(mlp, fm_term, Su, Bu, au, Sc, Bc, ac, targets, filtered=False, excl_offsets=None, excl_pos=None, kp=None,
+                   max_elems=1 << 25):
+    """fmx_mlp_rank's definition on mlp_topk_torch's statement of the score (the same up to fp32 summation order), as chunked
+    torch: for a block of users every candidate's score, the eligible ones (not NaN, not excluded), and for each target the
+    number of eligible candidates with a greater (score, position) key.  targets: int32 [U, T], any T.  The path of networks
+    the kernel does not take, and the baseline of tools/rank_times.py.  Returns as fm_rank."""
+    params, k, H, L = mlp
+    U, N, dev = Su.shape[0], Sc.shape[0], Su.device
+    kp = Sc.shape[1] if kp is None else int(kp)
+    T = targets.shape[1]
+    Ws, off = [], 0
+    for l in range(L):
+        n_in = k if l == 0 else H
+        Ws.append((params[off:off + H * n_in].view(H, n_in), params[off + H * n_in:off + H * n_in + H]))
+        off += H * n_in + H
+    rank = torch.full((U, T), -1, dtype=torch.int32, device=dev)
+    score_out = torch.full((U, T), float("-inf"), dtype=torch.float32, device=dev)
+    n_cand = torch.zeros(U, dtype=torch.int32, device=dev)
+    Sck, Bck = Sc[:, :k], Bc[:, :k]
+    ub = max(1, min(U, max_elems // max(1, N * max(H, k))))
+    cb = max(1, min(N, max_elems // max(1, ub * max(H, k))))
+    positions = torch.arange(N, device=dev)
+    with torch.no_grad():
+        for u0 in range(0, U, ub):
+            u1 = min(U, u0 + ub)
+            score = torch.empty((u1 - u0, N), dtype=torch.float32, device=dev)
+            for c0 in range(0, N, cb):
+                c1 = min(N, c0 + cb)
+                x = (Bu[u0:u1, None, :k] + Bck[None, c0:c1]) + Su[u0:u1, None, :k] * Sck[None, c0:c1]
+                for W, b in Ws:
+                    x = torch.relu(torch.nn.functional.linear(x, W, b))
+                base = au[u0:u1, None] + ac[None, c0:c1]
+                if fm_term:
+                    base = base + Su[u0:u1, :kp] @ Sc[c0:c1, :kp].T
+                score[:, c0:c1] = base + x.sum(-1)
+            score = score + 0.0                              # -0 -> +0
+            ok = ~torch.isnan(score)
+            if excl_offsets is not None:
+                offs = excl_offsets.long().cpu()
+                for u in range(u0, u1):
+                    p = excl_pos[int(offs[u]):int(offs[u + 1])].long()
+                    p = p[(p >= 0) & (p < N)]
+                    ok[u - u0, p] = False
+            n_cand[u0:u1] = ok.sum(1).to(torch.int32)
+            key = _rank_key(torch.where(ok, score, torch.zeros_like(score)), positions[None, :].expand_as(score))
+            tg = targets[u0:u1].long()
+            inside = (tg >= 0) & (tg < N)
+            tgc = torch.where(inside, tg, torch.zeros_like(tg))
+            t_ok = inside & torch.gather(ok, 1, tgc)
+            t_key = torch.gather(key, 1, tgc)
+            for t in range(T):
+                ahead = ok & (key > t_key[:, t:t + 1])
+                if filtered:                                 # the user's other eligible targets are not counted
+                    others = torch.zeros_like(ok)
+                    rows = torch.arange(u1 - u0, device=dev)[:, None].expand(-1, T)
+                    others[rows[t_ok], tgc[t_ok]] = True
+                    ahead = ahead & ~others
+                rank[u0:u1, t] = torch.where(t_ok[:, t], ahead.sum(1), torch.full_like(tg[:, t], -1)).to(torch.int32)
+            score_out[u0:u1] = torch.where(t_ok, torch.gather(score, 1, tgc), torch.full_like(score_out[u0:u1], float("-inf")))
+    return rank, score_out, n_cand
+
+
+def _rank_chunks(call, targets, U, device, filtered):
+    """What rank, rank_network and rank_afm share after their sides: call(chunk int32 [U, <= 16], filtered) -> (rank, score,
+    n_cand) over the column chunks of targets_matrix, concatenated.  `filtered` within a chunk is the call's; across chunks it
+    is resolved here from the returned scores and the target positions with the same key order (_rank_key): a target's rank
+    loses one for every distinct eligible target of another chunk that is ahead of it."""
+    full, chunks = targets_matrix(targets, U, device)
+    outs = [call(ch, filtered) for ch in chunks]
+    ranks = torch.cat([o[0] for o in outs], dim=1).long()
+    scores = torch.cat([o[1] for o in outs], dim=1)
+    n_cand = outs[0][2].long()
+    if filtered and len(chunks) > 1:
+        T = full.shape[1]
+        valid = ranks >= 0
+        key = _rank_key(torch.where(valid, scores, torch.zeros_like(scores)), full.clamp(min=0))
+        chunk_of = torch.arange(T, device=device) // RANK_MAX_T
+        # first[u, t]: no earlier column lists the same position (a target listed twice was counted once as a candidate)
+        eq = full[:, :, None] == full[:, None, :]
+        first = ~(eq & torch.tril(torch.ones(T, T, dtype=torch.bool, device=device), -1)[None]).any(dim=2)
+        same_chunk = chunk_of[None, :] == chunk_of[:, None]
+        # mine[u, t, t2]: t's own chunk lists t2's position too, so the call has already left it out
+        mine = torch.matmul(same_chunk.float()[None], eq.float()) > 0
+        ahead = (key[:, None, :] > key[:, :, None]) & (valid & first)[:, None, :] & ~same_chunk[None] & ~mine
+        ranks = torch.where(valid, ranks - ahead.sum(dim=2), ranks)
+    return ranks, scores, n_cand
+
+
+def rank(table, ctx_idx, ctx_xv, candidates, targets, exclude=None, hyper=None, filtered=False):
+    """The rank of the target positions among all N candidates for every context row of ctx_idx / ctx_xv ([U, F] full width,
+    the item columns ignored): the number of eligible candidates (not NaN, not excluded) that topk's order puts in front of
+    the target, i.e. its 0-based index in an unbounded topk row.  targets: see targets_matrix (positions in the sense of
+    topk's results).  filtered: the user's other targets are not counted (leave-n-out evaluation).  Returns device tensors
+    (ranks int64 [U, T], -1: no eligible target; scores fp32 [U, T], -inf there; n_cand int64 [U]).  More than 16 targets per
+    user run as several calls; `filtered` across them is resolved on the host side of the call (see _rank_chunks) from the
+    returned scores and positions with the same key order."""
+    (Su, au), off, pos = _context_side(table, candidates, ctx_idx, ctx_xv, exclude, hyper, side_sums)
+    return _rank_chunks(lambda tg, f: fm_rank(Su, au, candidates.Sc, candidates.ac, tg, f, off, pos), targets, Su.shape[0],
+                        table.device, filtered)
+
+
+def rank_network(table, mlp, fm_term, ctx_idx, ctx_xv, candidates, targets, exclude=None, hyper=None, filtered=False):
+    """As rank, under the DeepFM (fm_term = 1) / NFM (fm_term = 0) network mlp = (params, k, hidden, n_layers) and topk_network's
+    score and order.  Networks fmx_mlp_rank does not take (hidden > 256) go through mlp_rank_torch."""
+    def side(table, idx, xv, fields, hyper):
+        S, bi, sfirst, sbi, logit = side_terms(table, idx, xv, fields, hyper)
+        return S, bi, network_bases(table, sfirst, sbi, logit, fm_term, context=True).contiguous()
+
+    (S, bi, au), off, pos = _context_side(table, candidates, ctx_idx, ctx_xv, exclude, hyper, side, fm_term)
+    fn = mlp_rank if mlp_kernel_takes(mlp) else mlp_rank_torch
+    return _rank_chunks(lambda tg, f: fn(mlp, fm_term, S, bi, au, candidates.Sc, candidates.Bc, candidates.ac, tg, f, off, pos),
+                        targets, S.shape[0], table.device, filtered)
+
+
+def rank_afm(table, afm, ctx_idx, ctx_xv, candidates, targets, exclude=None, hyper=None, filtered=False):
+    """As rank, under the AFM afm = (params, t) and topk_afm's score and order.  candidates: an AFMCandidates of the same table
+    and attention parameters."""
+    params, t = afm[0], int(afm[1])
+    if not isinstance(candidates, AFMCandidates):
+        raise ValueError("candidates: an AFMCandidates (the AFM's candidate side)")
+    if candidates.table is table and (candidates.t != t or candidates.afm[0].data_ptr() != params.data_ptr()):
+        raise ValueError(f"candidates were computed for another attention (t={candidates.t}; this one has t={t})")
+
+    def side(table, idx, xv, fields, hyper):
+        return afm_side(table, (params, t), idx, xv, fields, True, hyper)
+
+    (Eu, stats_u), off, pos = _context_side(table, candidates, ctx_idx, ctx_xv, exclude, hyper, side)
+    return _rank_chunks(lambda tg, f: afm_rank((params, t), table.k, Eu, stats_u, candidates.Ec, candidates.stats, tg, f, off, pos),
+                        targets, Eu.shape[0], table.device, filtered)
+
+
+def ranking_metrics(ranks, n_cand, ks=(1, 5, 10)):
+    """Ranking metrics of rank's results; pure torch, CPU tensors welcome.  ranks [U, T] (or [U]) integer, -1 for targets that
+    were not ranked; n_cand [U].  Over the valid targets (rank >= 0): hr@K = mean [r < K]; ndcg@K = mean [r < K] / log2(r + 2);
+    mrr = mean 1 / (r + 1); auc = mean 1 - r / (n_cand - 1) over the targets whose user has n_cand > 1; n = their number.
+    Returns a dict of Python floats (NaN where nothing is averaged) and the int n."""
+    ranks = torch.as_tensor(ranks)
+    if ranks.dim() == 1:
+        ranks = ranks[:, None]
+    n_cand = torch.as_tensor(n_cand).reshape(-1, 1).expand_as(ranks)
+    valid = ranks >= 0
+    r = ranks[valid].to(torch.float64)
+    nc = n_cand[valid].to(torch.float64)
+    n = int(r.numel())
+
+    def mean(x):
+        return float(x.sum() / x.numel()) if x.numel() else float("nan")
+
+    out = {}
+    for K in ks:
+        hit = (r < K).to(torch.float64)
+        out[f"hr@{int(K)}"] = mean(hit)
+        out[f"ndcg@{int(K)}"] = mean(hit / torch.log2(r + 2.0))
+    out["mrr"] = mean(1.0 / (r + 1.0))
+    wide = nc > 1
+    out["auc"] = mean(1.0 - r[wide] / (nc[wide] - 1.0))
+    out["n"] = n
+    return out

@@ -826,6 +826,47 @@ int fmx_afm_topk(const fmx_afm_t *afm, const float *Eu, const float *stats_u, in
                  const float *stats_c, int32_t n_item, int32_t N, int32_t kp, const int32_t *excl_offsets, const int32_t *excl_pos,
                  int32_t K, void *workspace, int64_t workspace_bytes, int32_t *top_pos, float *top_score, fmx_stream_t stream);
 
+/* ---- exact ranking evaluation: the rank of held-out targets among all candidates (fmx/recommend.py) ----
+ * Replaces: recommending K = 256 and hoping the held-out item is inside, or forward() over U x N assembled samples followed
+ * by a comparison count; the reference has no counterpart (utils/metric_manager.py keeps classification counts only).
+ * One call per scoring family.  Each takes the arguments of the family's top-K call, with the same meaning and the same
+ * limits (kp, k, hidden <= 256, n_layers <= 8, the AFM's t, n_ctx and n_item bounds), and K, top_pos, top_score replaced by
+ *   targets [U, T] int32: candidate positions, 1 <= T <= 16 (larger: FMX_ERR_UNSUPPORTED; T < 1: FMX_ERR_ARG);  filtered: 0 or 1
+ *   rank_out [U, T] int32;  score_out [U, T] fp32, may be null;  n_cand_out [U] int32, may be null.
+ * Score: score(u, c) is the fixed function stated at the family's top-K call above (see there for the formula).  It gives the
+ * same bits for a pair whatever U, N, T, the tile or the split, and the same bits that top-K call computes: the device code
+ * of the score is shared, not restated.
+ * Eligibility: candidate c is eligible for user u when 0 <= c < N, score(u, c) is not NaN and c is not in u's exclusion list --
+ * exactly the candidates the top-K call may return.  n_cand_out[u] is their number.
+ * Targets: a target p that is not eligible (-1 padding, p >= N, excluded, NaN score) gets rank -1 and score -inf.  Otherwise
+ * score_out[u, t] = score(u, p) with -0 returned as +0, and rank_out[u, t] = the number of eligible c whose key is greater
+ * than p's in the top-K order (score descending, then position ascending, -0 taken as +0): the 0-based index p would have in
+ * an unbounded top-K row.  Hence p sits at index r of the family's top-K row exactly when rank = r < K.  filtered = 1: the
+ * user's other eligible targets are not counted (the filtered rank of leave-n-out evaluation); filtered = 0: they count like
+ * any candidate, and a target listed twice gets the same rank twice.
+ * The workspace (16-byte aligned, no initialisation needed; the outputs need none either) holds the targets' keys and the
+ * per-split partial counts, after the family's parameter copy: *_rank_workspace_bytes bytes (int64, monotone in U, N and T,
+ * negative on bad sizes), else FMX_ERR_SHAPE.  Every argument is checked before anything is launched, with the codes the
+ * top-K call returns for the same mistake.  Asynchronous on `stream`, safe under graph capture; the counts are integers, so the
+ * result is identical run to run.  Launches: the parameter copy (network, AFM), the targets' keys, the counting scan, the
+ * finishing step. */
+int64_t fmx_fm_rank_workspace_bytes(int32_t U, int32_t N, int32_t T);
+int fmx_fm_rank(const float *Su, int32_t ld_u, const float *au, int32_t U, const float *Sc, int32_t ld_c, const float *ac, int32_t N,
+                int32_t kp, const int32_t *excl_offsets, const int32_t *excl_pos, const int32_t *targets, int32_t T, int32_t filtered,
+                void *workspace, int64_t workspace_bytes, int32_t *rank_out, float *score_out, int32_t *n_cand_out,
+                fmx_stream_t stream);
+int64_t fmx_mlp_rank_workspace_bytes(const fmx_mlp_t *mlp, int32_t U, int32_t N, int32_t T);
+int fmx_mlp_rank(const fmx_mlp_t *mlp, int32_t fm_term, const float *Su, const float *Bu, int32_t ld_u, const float *au, int32_t U,
+                 const float *Sc, const float *Bc, int32_t ld_c, const float *ac, int32_t N, int32_t kp,
+                 const int32_t *excl_offsets, const int32_t *excl_pos, const int32_t *targets, int32_t T, int32_t filtered,
+                 void *workspace, int64_t workspace_bytes, int32_t *rank_out, float *score_out, int32_t *n_cand_out,
+                 fmx_stream_t stream);
+int64_t fmx_afm_rank_workspace_bytes(const fmx_afm_t *afm, int32_t n_ctx, int32_t n_item, int32_t U, int32_t N, int32_t T);
+int fmx_afm_rank(const fmx_afm_t *afm, const float *Eu, const float *stats_u, int32_t n_ctx, int32_t U, const float *Ec,
+                 const float *stats_c, int32_t n_item, int32_t N, int32_t kp, const int32_t *excl_offsets, const int32_t *excl_pos,
+                 const int32_t *targets, int32_t T, int32_t filtered, void *workspace, int64_t workspace_bytes, int32_t *rank_out,
+                 float *score_out, int32_t *n_cand_out, fmx_stream_t stream);
+
 /* Streaming read of `bytes` (multiple of 16) with 16-byte loads; sink [1] receives a checksum so the loads stay
  * live.  Used by bench.py to measure the HBM-read ceiling on the same GPU in the same run. */
 int fmx_stream_read(const void *buf, int64_t bytes, float *sink, fmx_stream_t stream);
