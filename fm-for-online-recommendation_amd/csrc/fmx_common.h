@@ -243,6 +243,24 @@ __device__ __forceinline__ void bce_loss_dz(int loss_kind, float z, float y, flo
   }
 }
 
+// The pairwise-ranking loss of a logit difference d = z_pos - z_neg: loss = -log(sigmoid(d) + margin), margin >= 0, and its
+// gradient d loss / d d = -sigmoid(d) sigmoid(-d) / (sigmoid(d) + margin), scaled by inv_b.  margin == 0 (BPR) in the stable
+// softplus form, where the gradient is -sigmoid(-d); sigmoid(-d) is evaluated as such, not as 1 - sigmoid(d), which loses its
+// digits once d is large.  Finite for every finite d.
+__device__ __forceinline__ void pair_loss_dz(float d, float margin, float inv_b, float &loss, float &dz) {
+  const float sn = 1.f / (1.f + expf(d));  // sigmoid(-d)
+  float g;
+  if (margin == 0.f) {
+    loss = log1pf(expf(-fabsf(d))) + fmaxf(-d, 0.f);
+    g = -sn;
+  } else {
+    const float sp = sigmoidf_(d);
+    loss = -logf(sp + margin);
+    g = -(sp * sn) / (sp + margin);
+  }
+  dz = g * inv_b;
+}
+
 // lane ^ M exchanges without the LDS crossbar (ds_bpermute made the sort LDS-pipe bound): DPP for M = 1, 2, 4, 8,
 // v_permlane16/32_swap for M = 16, 32.
 template <int M>

@@ -85,6 +85,7 @@ struct FwdArgs {
   // fields as pieces of index columns (fmx_table_t.field_cols / field_base; both null on ordinary tables): Fc = columns of idx
   const int32_t *fcols, *fbase;
   int32_t Fc;
+  float margin;  // PAIR (fmx_pair.inc): the pair loss's margin; nothing else reads it
 };
 
 #ifdef FMX_STAMPS  // diagnostic build (tools/forward_stamps.sh): s_memrealtime (100 MHz) of every wave of the LAST k_fm_forward launch
@@ -110,7 +111,10 @@ __device__ __forceinline__ float first_lane_f(float v) { return __int_as_float(_
 // SIMD at once; instead the waves of a workgroup leave (fo, sbi, y) in LDS and, behind ONE barrier, the workgroup's first wave
 // evaluates all of them, sample i on lane i: the same function of the same operands -- the same bits -- for a quarter of the
 // instruction issue at four waves per workgroup.  Without a loss (the DeepFM loop) every wave stores its own three words.
-template <int LPR>
+// PAIR (fmx_fm_pair_forward, fmx_pair.inc; at least two waves per workgroup, B even): samples 2i and 2i + 1 are the positive and the
+// negative of pair i and sit on neighbouring lanes of that first wave; each takes its partner's logit from lane ^ 1 and both
+// evaluate the pair loss of the same difference -- the positive stores (loss_i, dz_i), the negative (0, -dz_i).  No label is read.
+template <int LPR, bool PAIR = false>
 __device__ __forceinline__ void forward_finish(const FwdArgs &a, int b, const bool exists, const int lane, float4 s, float4 ss, float fo,
                                                bool bad, float y, const float bias) {
   const int q = lane % LPR;
@@ -129,7 +133,7 @@ __device__ __forceinline__ void forward_finish(const FwdArgs &a, int b, const bo
     if (a.out.bi) *reinterpret_cast<float4 *>(a.out.bi + (size_t)b * kp + 4 * q) = bi;
   }
   int n = exists ? 1 : 0;  // lanes 0 .. n - 1 finish samples b .. b + n - 1
-  if (a.loss_kind != FMX_LOSS_NONE && blockDim.x > WAVE) {  // (uniform over the launch)
+  if ((PAIR || a.loss_kind != FMX_LOSS_NONE) && blockDim.x > WAVE) {  // (uniform over the launch)
     __shared__ float sh[3][4];
     const int w = threadIdx.x >> 6, wpb = blockDim.x >> 6;
     if (lane == 0) {
@@ -152,7 +156,14 @@ __device__ __forceinline__ void forward_finish(const FwdArgs &a, int b, const bo
     if (a.out.sfirst) a.out.sfirst[bl] = fo;
     if (a.out.sbi) a.out.sbi[bl] = sbi;
     if (a.out.logit) a.out.logit[bl] = z;
-    if (a.loss_kind != FMX_LOSS_NONE) {
+    if constexpr (PAIR) {
+      const float zo = xor_lane_f<1>(z, lane);  // the partner's logit (n is even: the partner's lane is active)
+      const bool pos = (lane & 1) == 0;
+      float loss, dz;
+      pair_loss_dz(pos ? z - zo : zo - z, a.margin, a.inv_b, loss, dz);  // both lanes: the same operands, the same bits
+      if (a.out.loss) a.out.loss[(size_t)bl * a.ld1] = pos ? loss : 0.f;
+      if (a.out.dz) a.out.dz[(size_t)bl * a.ld1] = pos ? dz : -dz;
+    } else if (a.loss_kind != FMX_LOSS_NONE) {
       float loss, dz;
       bce_loss_dz(a.loss_kind, z, y, a.inv_b, loss, dz);
       FMX_FSTAMP_AT(4, dz, b, n);
@@ -181,7 +192,7 @@ constexpr int64_t ROW_ABSENT = int64_t(1) << 62;  // set in a resolved row: the 
 // HAS_X: xv is not null (without values every x is 1 and nothing is loaded for it).
 // exists (wave-uniform): false for a wave behind the batch's last sample, which repeats that sample for the workgroup's barrier and
 // stores nothing.
-template <int LPR, int LAYOUT, int NPASS, bool MAPPED, bool HAS_X>
+template <int LPR, int LAYOUT, int NPASS, bool MAPPED, bool HAS_X, bool PAIR = false>
 __device__ __forceinline__ void forward_sample(const FwdArgs &a, const int b, const bool exists, const int lane) {
   constexpr int SLOTS = WAVE / LPR;
   constexpr int NP = NPASS > 0 ? NPASS : 1;
@@ -195,7 +206,7 @@ __device__ __forceinline__ void forward_sample(const FwdArgs &a, const int b, co
   bool bad = false;
   // the label and the bias are only needed by the epilogue, but a load issued there is one more dependent round trip
   // at the end of every wave: request them now, with the indices (every lane the same address: one request each)
-  const float y_early = a.loss_kind != FMX_LOSS_NONE ? a.y[b] : 0.f;
+  const float y_early = (!PAIR && a.loss_kind != FMX_LOSS_NONE) ? a.y[b] : 0.f;
   const float bias0_early = a.bias[0];
   const float bias1_early = LAYOUT == FMX_LAYOUT_WEIGHTS ? 0.f : a.bias[1];
   __builtin_amdgcn_sched_barrier(0);  // (left to itself the scheduler sinks the bias load behind the first waits of the gather:
@@ -279,17 +290,17 @@ __device__ __forceinline__ void forward_sample(const FwdArgs &a, const int b, co
     }
     FMX_FSTAMP(2, s.x + ss.x + fo);  // (every row of the pass set arrived and added)
   }
-  forward_finish<LPR>(a, b, exists, lane, s, ss, fo, bad, y_early, bias);
+  forward_finish<LPR, PAIR>(a, b, exists, lane, s, ss, fo, bad, y_early, bias);
 }
 
-template <int LPR, int LAYOUT, int NPASS, bool MAPPED = false>
+template <int LPR, int LAYOUT, int NPASS, bool MAPPED = false, bool PAIR = false>
 __global__ __launch_bounds__(256) void k_fm_forward(FwdArgs a) {
   __builtin_amdgcn_s_setprio(3);  // ahead of the side-stream sort's waves at the CU's instruction arbiter
   int b = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
   const bool exists = b < a.B;  // wave-uniform
   if (!exists) b = a.B - 1;     // (forward_finish has a workgroup barrier: the wave goes along and stores nothing)
-  if (a.xv) forward_sample<LPR, LAYOUT, NPASS, MAPPED, true>(a, b, exists, threadIdx.x & 63);
-  else forward_sample<LPR, LAYOUT, NPASS, MAPPED, false>(a, b, exists, threadIdx.x & 63);
+  if (a.xv) forward_sample<LPR, LAYOUT, NPASS, MAPPED, true, PAIR>(a, b, exists, threadIdx.x & 63);
+  else forward_sample<LPR, LAYOUT, NPASS, MAPPED, false, PAIR>(a, b, exists, threadIdx.x & 63);
 }
 
 // ------------------------------------------------------------------------------------------------------------
@@ -1909,23 +1920,29 @@ Side *side_for_current_device() {
 
 constexpr int OVERLAP_MIN_BATCH = 512;  // below this the extra event traffic costs more than the sort
 
-template <int LPR, int NPASS, bool MAPPED = false>
+// PAIR (fmx_fm_pair_forward): at least two waves per workgroup -- the batch is even and so is every workgroup's first sample, so
+// a pair never straddles workgroups
+template <int LPR, int NPASS, bool MAPPED = false, bool PAIR = false>
 void launch_forward_np(const FwdArgs &a, int layout, hipStream_t st) {
-  const int wpb = tune().wpb_fwd;
+  const int wpb = PAIR && tune().wpb_fwd < 2 ? 2 : tune().wpb_fwd;
   const dim3 grid((a.B + wpb - 1) / wpb), block(64 * wpb);
   // the forward reads [ V | w ] and the bias weight: a MOMENTS table is read as a WEIGHTS one (bias[0] is the weight)
-  if (layout == FMX_LAYOUT_FTRL) hipLaunchKernelGGL((k_fm_forward<LPR, FMX_LAYOUT_FTRL, NPASS, MAPPED>), grid, block, 0, st, a);
-  else hipLaunchKernelGGL((k_fm_forward<LPR, FMX_LAYOUT_WEIGHTS, NPASS, MAPPED>), grid, block, 0, st, a);
+  if (layout == FMX_LAYOUT_FTRL) hipLaunchKernelGGL((k_fm_forward<LPR, FMX_LAYOUT_FTRL, NPASS, MAPPED, PAIR>), grid, block, 0, st, a);
+  else hipLaunchKernelGGL((k_fm_forward<LPR, FMX_LAYOUT_WEIGHTS, NPASS, MAPPED, PAIR>), grid, block, 0, st, a);
 }
 
-template <int LPR>
+template <int LPR, bool PAIR = false>
 void launch_forward(const FwdArgs &a, int layout, hipStream_t st) {
   const int slots = WAVE / LPR;
   const int np = (a.F + slots - 1) / slots;
-  if (a.fcols || a.fbase)  // fields are pieces of index columns: the generic field loop (the additions and their order are the same)
-    launch_forward_np<LPR, 0, true>(a, layout, st);
-  else if (!with_one_of<1, 2, 3, 4>(np, [&](auto NP) { launch_forward_np<LPR, NP>(a, layout, st); }))
-    launch_forward_np<LPR, 0>(a, layout, st);
+  if constexpr (!PAIR) {  // (the pair forward refuses such tables on the host)
+    if (a.fcols || a.fbase) {  // fields are pieces of index columns: the generic field loop (the additions and their order are the same)
+      launch_forward_np<LPR, 0, true>(a, layout, st);
+      return;
+    }
+  }
+  if (!with_one_of<1, 2, 3, 4>(np, [&](auto NP) { launch_forward_np<LPR, NP, false, PAIR>(a, layout, st); }))
+    launch_forward_np<LPR, 0, false, PAIR>(a, layout, st);
 }
 
 // The in-launch hand-offs tag their flag words with a per-launch sequence number passed as a kernel argument; a captured
@@ -2165,7 +2182,7 @@ int pool_loop(const fmx_table_t *table, const int32_t *idx_pool, const float *y_
     if (!sd) rc = sort_group(g, first_step, n, st);
     for (int i = 0; i < n && rc == FMX_OK; ++i) {
       const int s = first_step + i, j = s % n_pool;
-      rc = before_update(s, idx_pool + (size_t)j * B * F, y_pool + (size_t)j * B, st);
+      rc = before_update(s, idx_pool + (size_t)j * B * F, y_pool ? y_pool + (size_t)j * B : nullptr, st);  // (no labels: the pair loss)
       if (sd && i == 0) (void)hipStreamWaitEvent(st, sd->sorted[g & 1], 0);
       if (rc == FMX_OK) rc = update(s, w.sorted + ((size_t)(g & 1) * ahead + i) * w.sorted_stride, st);
       // the next group is sorted while this one runs; its launch is issued BEHIND the group's first step, so that at the start
@@ -2226,6 +2243,7 @@ FwdArgs fill_fwd(const fmx_table_t *table, const fmx_hyper_t *hyper, const int32
   a.loss_kind = loss_kind;
   a.h.alpha = 1.0f / hyper->alpha;  // the kernels multiply by 1/alpha
   a.inv_b = inv_b;
+  a.margin = 0.f;
   return a;
 }
 
@@ -2427,6 +2445,18 @@ int check_step_args(const fmx_table_t *table, const fmx_hyper_t *hyper, int32_t 
   if (loss_kind != FMX_LOSS_BCE_LOGITS && loss_kind != FMX_LOSS_BCE_SIGMOID) return fail(FMX_ERR_ARG, "a step needs a loss");
   return FMX_OK;
 }
+
+// a shared check's refusal, with the entry point in front of its message
+int named(int rc, const char *who) {
+  if (rc != FMX_OK && !strstr(g_err, who)) {
+    char msg[sizeof(g_err)];
+    snprintf(msg, sizeof(msg), "%s", g_err);
+    snprintf(g_err, sizeof(g_err), "%s: %s", who, msg);
+  }
+  return rc;
+}
+
+#include "fmx_pair.inc"
 
 }  // namespace
 
@@ -2886,6 +2916,33 @@ int fmx_fm_online_run(const fmx_table_t *table, const fmx_hyper_t *hyper, int32_
   return check_launch("k_fm_online");
 }
 
+// ---- the pairwise-ranking loss (fmx_pair.inc) ----
+int fmx_fm_pair_forward(const fmx_table_t *table, const fmx_hyper_t *hyper, const int32_t *idx, const float *xv, int32_t B_pairs,
+                        float margin, float inv_b, const fmx_fwd_out_t *out, fmx_stream_t stream) {
+  return pair_forward_call(table, hyper, idx, xv, B_pairs, margin, inv_b, out, static_cast<hipStream_t>(stream));
+}
+
+int fmx_fm_pair_step(const fmx_table_t *table, const fmx_hyper_t *hyper, int32_t rule, const int32_t *idx, const float *xv,
+                     int32_t B_pairs, float margin, float inv_b, void *workspace, int64_t workspace_bytes, const fmx_fwd_out_t *fwd,
+                     float *loss_out, fmx_stream_t stream) {
+  return pair_step_call(table, hyper, rule, idx, xv, B_pairs, margin, inv_b, workspace, workspace_bytes, fwd, loss_out,
+                        static_cast<hipStream_t>(stream));
+}
+
+int fmx_fm_pair_stream(const fmx_table_t *table, const fmx_hyper_t *hyper, int32_t rule, const int32_t *idx_pool, int32_t n_pool,
+                       int32_t B_pairs, float margin, float inv_b, int32_t n_steps, void *workspace, int64_t workspace_bytes,
+                       const fmx_fwd_out_t *fwd, float *loss_out, fmx_stream_t stream) {
+  return pair_stream_call(table, hyper, rule, idx_pool, n_pool, B_pairs, margin, inv_b, n_steps, workspace, workspace_bytes, fwd,
+                          loss_out, static_cast<hipStream_t>(stream));
+}
+
+int fmx_fm_pair_online_run(const fmx_table_t *table, const fmx_hyper_t *hyper, int32_t rule, const int32_t *idx, const float *xv,
+                           int32_t N, float margin, uint8_t *pred_out, float *logit_out, float *loss_out, int32_t *error,
+                           fmx_stream_t stream) {
+  return pair_online_call(table, hyper, rule, idx, xv, N, margin, pred_out, logit_out, loss_out, error,
+                          static_cast<hipStream_t>(stream));
+}
+
 static int mlp_launch(const fmx_mlp_t *mlp, MlpArgs &a, int32_t B, int32_t kp, fmx_stream_t stream, const char *who) {
   if (!mlp || !mlp->params) return fail(FMX_ERR_ARG, "%s: null mlp", who);
   if (mlp->n_layers < 1 || mlp->n_layers > MLP_MAX_L || mlp->hidden < 1 || mlp->hidden > MLP_MAX_W || mlp->k < 1 ||
@@ -2909,15 +2966,6 @@ static int mlp_small_opt_check(const fmx_mlp_t *mlp, const fmx_mlp_opt_t *opt, i
   if (!aligned16(mlp->params) || !aligned16(opt->v) || (opt->m && !aligned16(opt->m)))
     return fail(FMX_ERR_ALIGN, "%s: mlp->params, opt->m and opt->v must be 16-byte aligned", who);
   return FMX_OK;
-}
-// a shared check's refusal, with the entry point in front of its message
-static int named(int rc, const char *who) {
-  if (rc != FMX_OK && !strstr(g_err, who)) {
-    char msg[sizeof(g_err)];
-    snprintf(msg, sizeof(msg), "%s", g_err);
-    snprintf(g_err, sizeof(g_err), "%s: %s", who, msg);
-  }
-  return rc;
 }
 
 // fmx_online_run_mlp (opt null) and fmx_online_run_mlp_opt (fit mode with the network under opt's rule, the tables under any rule)

@@ -6,6 +6,7 @@ There is no CPU path and no PyTorch fallback: without a ROCm GPU or without the 
 """
 from . import _lib  # noqa: F401
 from . import recommend  # noqa: F401
+from . import pairwise  # noqa: F401
 from .table import FlatTable, padded_k  # noqa: F401
 from .engine import FMEngine, Hyper, MlpOpt, normalize_inputs  # noqa: F401
 from .distributed import DataParallelFM, HipBackend  # noqa: F401

@@ -390,6 +390,65 @@ class FMEngine:
         self._advance(N)
         return pred, loss_b
 
+    # ---- pairwise-ranking (BPR) training: idx_d [2B, F], row 2i the positive of pair i, row 2i + 1 the negative (fmx/pairwise.py) ----
+    @staticmethod
+    def _n_pairs(idx_d):
+        if idx_d.dim() != 2 or idx_d.shape[0] % 2 or idx_d.shape[0] < 2:
+            raise ValueError(f"pair rows must be [2B, F] with B >= 1, got {tuple(idx_d.shape)}")
+        return idx_d.shape[0] // 2
+
+    def pair_forward(self, hyper, idx_d, xv_d=None, margin=0.0, inv_b=None, want_first=False, want_bi=False, stream=None):
+        """fmx_fm_pair_forward on B pairs: S / sfirst / sbi / logit of the 2B rows, and the pair loss and its dlogit in
+        self.loss_b / self.dz (loss_b[2i] = loss_i, loss_b[2i + 1] = 0, dz[2i + 1] = -dz[2i]).  -> B"""
+        B = self._n_pairs(idx_d)
+        self._ensure(2 * B)
+        out = self._fwd_out(want_first, want_bi)
+        _lib.check(self.lib.fmx_fm_pair_forward(self.table.c_struct(), hyper.ref(), idx_d.data_ptr(), _ptr(xv_d), B, float(margin),
+                                                1.0 / B if inv_b is None else inv_b, C.byref(out), self._stream(stream)))
+        return B
+
+    def pair_step(self, hyper, rule, idx_d, xv_d=None, margin=0.0, inv_b=None):
+        """One pair step on B pairs (fmx_fm_pair_step); the mean pair loss lands in self.loss_out[0] (no sync here)."""
+        B = self._n_pairs(idx_d)
+        self._ensure(2 * B)
+        cached = getattr(self, "_step_out", None)
+        if cached is None or cached[0] != self.S.data_ptr():
+            self._step_out = cached = (self.S.data_ptr(), self._fwd_out(want_first=False, want_bi=False))
+        self._steps(hyper)
+        _lib.check(self.lib.fmx_fm_pair_step(self.table.c_struct(), hyper.ref(), _lib.RULES[rule], idx_d.data_ptr(), _ptr(xv_d), B,
+                                             float(margin), 1.0 / B if inv_b is None else inv_b, self.workspace.data_ptr(),
+                                             self._ws_bytes(), C.byref(cached[1]), self.loss_out.data_ptr(), self._stream()))
+        self._advance(1)
+
+    def pair_stream(self, hyper, rule, idx_pool, n_steps, margin=0.0, loss_out=None):
+        """n_steps pair steps over a resident pool idx_pool [n_pool, 2B, F] (fmx_fm_pair_stream); loss_out [n_steps] or None."""
+        n_pool, B2, F = idx_pool.shape
+        assert F == self.table.n_fields and B2 % 2 == 0 and idx_pool.is_contiguous()
+        if loss_out is not None and (loss_out.numel() < n_steps or not loss_out.is_contiguous()):
+            raise ValueError(f"loss_out holds {loss_out.numel()} steps, {n_steps} asked for")
+        B = B2 // 2
+        self._ensure(B2)
+        out = self._fwd_out(want_first=False, want_bi=False)
+        self._steps(hyper)
+        _lib.check(self.lib.fmx_fm_pair_stream(self.table.c_struct(), hyper.ref(), _lib.RULES[rule], idx_pool.data_ptr(), n_pool, B,
+                                               float(margin), 1.0 / B, int(n_steps), self.workspace.data_ptr(), self._ws_bytes(),
+                                               C.byref(out), _ptr(loss_out), self._stream()))
+        self._advance(n_steps)
+
+    def pair_online_run(self, hyper, rule, idx_d, xv_d=None, margin=0.0, want_logit=False, want_loss=False):
+        """The online protocol on N device-resident pairs (fmx_fm_pair_online_run): per pair predict (z_pos > z_neg), then one
+        pair step on that pair.  -> (pred uint8 [N], logit [2N] or None, loss [N] or None)."""
+        N = self._n_pairs(idx_d)
+        pred = torch.empty(N, dtype=torch.uint8, device=self.device)
+        logit = torch.empty(2 * N, dtype=torch.float32, device=self.device) if want_logit else None
+        loss_b = torch.empty(N, dtype=torch.float32, device=self.device) if want_loss else None
+        self._steps(hyper)
+        _lib.check(self.lib.fmx_fm_pair_online_run(self.table.c_struct(), hyper.ref(), _lib.RULES[rule], idx_d.data_ptr(), _ptr(xv_d),
+                                                   N, float(margin), pred.data_ptr(), _ptr(logit), _ptr(loss_b),
+                                                   self.error.data_ptr(), self._stream()))
+        self._advance(N)
+        return pred, logit, loss_b
+
     def online_run_mlp(self, hyper, rule, loss, params, k, hidden, n_layers, hedge, fm_term, hedge_b, hedge_s, alpha,
                        idx_d, xv_d, y_d, mlp_opt=None):
         """The online protocol for the classes with an MLP (fmx_online_run_mlp) -> forward() value per sample [N].

@@ -1,0 +1,104 @@
+"""Pairwise-ranking (BPR) training data: torch plumbing around fmx_fm_pair_* (include/fmx.h), no kernels of its own.
+
+A batch of B pairs is [2B, F] full-width rows, row 2i the positive sample of pair i and row 2i + 1 its negative: the
+positive's row with the item columns replaced.  sample_negatives draws the replacements, assemble_pairs interleaves the rows;
+FMEngine.pair_step / pair_stream / pair_online_run take the result.
+"""
+import torch
+
+
+def _item_fields(item_fields):
+    fields = [int(f) for f in (item_fields if hasattr(item_fields, "__len__") else [item_fields])]
+    if not fields or len(set(fields)) != len(fields):
+        raise ValueError(f"item_fields {item_fields!r}: one or more distinct field indices")
+    return fields
+
+
+def _negatives_3d(neg_items, B, m, what="neg_items"):
+    """-> [B, n_neg, m]: accepts [B, n_neg, m], [B, m] (one negative per positive) and, with one item field, [B]."""
+    t = torch.as_tensor(neg_items)
+    if t.dim() == 1 and m == 1:
+        t = t.reshape(B, 1, 1)
+    elif t.dim() == 2:
+        t = t.reshape(B, 1, m)
+    if t.dim() != 3 or t.shape[0] != B or t.shape[2] != m:
+        raise ValueError(f"{what} of shape {tuple(t.shape)}: expected [{B}, n_neg, {m}] (or [{B}, {m}] for one negative each)")
+    return t
+
+
+def assemble_pairs(pos_idx, pos_xv, item_fields, neg_items, neg_xv=None):
+    """The interleaved rows of B * n_neg pairs -> (idx [2 B n_neg, F] int32, xv [2 B n_neg, F] float32 or None).
+
+    pos_idx [B, F] (pos_xv [B, F] or None: every value 1); neg_items [B, n_neg, m] holds, per positive and negative, the indices
+    of the m item fields in the order of item_fields ([B, m]: one negative each).  Pair b * n_neg + j is positive b against its
+    j-th negative: row 2p is the positive, row 2p + 1 the positive with the item columns replaced -- so with n_neg > 1 a positive
+    is repeated once per negative.  neg_xv (same shape as neg_items) replaces the item columns' values too; by default the
+    negative keeps the positive's values."""
+    fields = _item_fields(item_fields)
+    pos_idx = torch.as_tensor(pos_idx)
+    if pos_idx.dim() != 2:
+        raise ValueError(f"pos_idx of shape {tuple(pos_idx.shape)}: expected [B, F]")
+    B, F = pos_idx.shape
+    if max(fields) >= F or min(fields) < 0:
+        raise ValueError(f"item_fields {fields} outside the {F} columns of pos_idx")
+    dev = pos_idx.device
+    neg = _negatives_3d(neg_items, B, len(fields)).to(device=dev, dtype=pos_idx.dtype)
+    n_neg = neg.shape[1]
+    cols = torch.as_tensor(fields, dtype=torch.long, device=dev)
+    rows = pos_idx.reshape(B, 1, 1, F).expand(B, n_neg, 2, F).clone()
+    rows[:, :, 1, cols] = neg
+    rows = rows.reshape(2 * B * n_neg, F).to(torch.int32).contiguous()
+    if pos_xv is None and neg_xv is None:
+        return rows, None
+    xv = torch.ones((B, F), dtype=torch.float32, device=dev) if pos_xv is None else torch.as_tensor(pos_xv, dtype=torch.float32).to(dev)
+    if xv.shape != (B, F):
+        raise ValueError(f"pos_xv of shape {tuple(xv.shape)}: expected {(B, F)}")
+    vals = xv.reshape(B, 1, 1, F).expand(B, n_neg, 2, F).clone()
+    if neg_xv is not None:
+        vals[:, :, 1, cols] = _negatives_3d(neg_xv, B, len(fields), "neg_xv").to(device=dev, dtype=torch.float32).expand(B, n_neg, len(fields))
+    return rows, vals.reshape(2 * B * n_neg, F).contiguous()
+
+
+def sample_negatives(pos_idx, item_fields, sizes_or_candidates, n_neg=1, generator=None):
+    """Uniform negative items for every positive row -> [B, n_neg, m] int64 on pos_idx's device (m = len(item_fields)).
+
+    sizes_or_candidates: a sequence of m ints -- the vocabulary sizes of the item fields, each field drawn independently -- or a
+    tensor of candidate items [N, m] ([N] with one item field), one drawn per negative.  A draw equal to the row's own positive
+    item (in every item column) is redrawn, so a row never gets its own positive as a negative.  Draws are made on the
+    generator's device (by default pos_idx's) and are deterministic under a seeded generator."""
+    fields = _item_fields(item_fields)
+    m = len(fields)
+    pos_idx = torch.as_tensor(pos_idx)
+    dev = pos_idx.device
+    gdev = generator.device if generator is not None else dev
+    B, n_neg = pos_idx.shape[0], int(n_neg)
+    if n_neg < 1:
+        raise ValueError("n_neg must be >= 1")
+    own = pos_idx[:, fields].to(device=gdev, dtype=torch.int64).reshape(B, 1, m).expand(B, n_neg, m)
+    cand = None
+    if torch.is_tensor(sizes_or_candidates):
+        cand = sizes_or_candidates.to(device=gdev, dtype=torch.int64).reshape(-1, m)
+        n_distinct = torch.unique(cand, dim=0).shape[0]
+    else:
+        sizes = [int(s) for s in sizes_or_candidates]
+        if len(sizes) != m or min(sizes) < 1:
+            raise ValueError(f"sizes {sizes}: one positive size per item field {fields}")
+        n_distinct = 1
+        for s in sizes:
+            n_distinct *= s
+    if n_distinct < 2:
+        raise ValueError("sample_negatives: fewer than two distinct items to draw from")
+
+    def draw(n):
+        if cand is not None:
+            return cand[torch.randint(cand.shape[0], (n,), generator=generator, device=gdev)]
+        return torch.stack([torch.randint(s, (n,), generator=generator, device=gdev) for s in sizes], dim=1)
+
+    out = draw(B * n_neg).reshape(B, n_neg, m)
+    while True:
+        again = (out == own).all(dim=2)
+        n = int(again.sum())
+        if n == 0:
+            break
+        out[again] = draw(n)
+    return out.to(dev)

@@ -536,6 +536,72 @@ class OnlineFMBase(nn.Module):
             self.alpha = a / a.sum()
 
     # ------------------------------------------------------------------------------------------------------
+    # pairwise-ranking (BPR) training of the pure FM (fmx/pairwise.py, fmx_fm_pair_*): for a context, score the observed item
+    # above a sampled one -- loss -log(sigmoid(z_pos - z_neg) + margin), margin 0 being BPR
+    # ------------------------------------------------------------------------------------------------------
+    def _pair_refusal(self, method):
+        if self._has_mlp:
+            raise NotImplementedError(f"{self._name}.{method}: the pair loss is built for the pure FM logit (FMAdam); the "
+                                      "classes with an MLP would need the pair epilogue inside the MLP section")
+
+    def _pair_rows(self, Xi, Xv, item_fields, negatives, n_neg, candidates, generator):
+        """-> (rows int32 [2P, F], xv [2P, F] or None) on the device: P = B * n_neg pairs, row 2p the positive, 2p + 1 the negative"""
+        idx_d, xv_d, _ = self._inputs(Xi, Xv)
+        fields = [int(f) for f in (item_fields if hasattr(item_fields, "__len__") else [item_fields])]
+        if negatives is None:
+            src = candidates if candidates is not None else [self.feature_sizes[f] for f in fields]
+            negatives = fmx.pairwise.sample_negatives(idx_d, fields, src, n_neg=n_neg, generator=generator)
+        self._fast_inputs_pending = True      # the negatives' indices are range-checked by the kernels
+        return fmx.pairwise.assemble_pairs(idx_d, xv_d, fields, negatives)
+
+    def fit_pairs(self, Xi, Xv, item_fields, negatives=None, n_neg=1, margin=0.0, candidates=None, generator=None):
+        """One mini-batch pair step under the model's update rule; returns the loss tensor (the mean pair loss), as
+        update_embedding does.  Xi / Xv: the positive samples [B, F] (Xv may be None: all ones).  negatives: the item columns of
+        every positive's negatives, [B, n_neg, m] for m item fields ([B, m]: one each); None draws n_neg per positive uniformly
+        (fmx.pairwise.sample_negatives) from `candidates` ([N, m] items) or, by default, from the item fields' vocabularies --
+        never the row's own item, deterministic under a seeded `generator`."""
+        self._pair_refusal("fit_pairs")
+        self.train()
+        rows, xv = self._pair_rows(Xi, Xv, item_fields, negatives, n_neg, candidates, generator)
+        self._engine.pair_step(self._hyper, self.update_rule, rows, xv, margin=margin)
+        out = self._engine.loss_out[0].clone()
+        self._after_step()
+        return out
+
+    def run_pair_experiment(self, Xi, Xv, item_fields, negatives=None, n_neg=1, margin=0.0, candidates=None, generator=None):
+        """The online protocol restated for pairs: for every pair predict (z_pos > z_neg), then fit on that pair alone ->
+        (seconds, pairwise accuracy in %, the accuracy at every pair i with i % 1000 == 0 and at the last, {"correct", "wrong"}).
+        On the device (fmx_fm_pair_online_run: one wavefront walks the stream) where run_experiment's loop runs there; otherwise
+        a loop over fit_pairs on one pair at a time -- the same bits."""
+        self._pair_refusal("run_pair_experiment")
+        start = time()
+        self.train()
+        rows, xv = self._pair_rows(Xi, Xv, item_fields, negatives, n_neg, candidates, generator)
+        n, e = rows.shape[0] // 2, self._engine
+        if n == 0:
+            return time() - start, 0.0, [], {"correct": 0, "wrong": 0}
+        if self._device_loop_ok():
+            pred, _, _ = e.pair_online_run(self._hyper, self.update_rule, rows, xv, margin=margin)
+        else:
+            fields = [int(f) for f in (item_fields if hasattr(item_fields, "__len__") else [item_fields])]
+            pred = torch.empty(n, dtype=torch.uint8, device=self.device)
+            strict, self.strict_index_check = self.strict_index_check, False      # one check after the loop, no sync inside it
+            try:
+                for i in range(n):
+                    pos, neg = rows[2 * i:2 * i + 1], rows[2 * i + 1:2 * i + 2, fields]
+                    self.fit_pairs(pos, None if xv is None else xv[2 * i:2 * i + 1], fields, negatives=neg, margin=margin)
+                    pred[i] = e.logit[0] > e.logit[1]            # the step's own forward: the logits before its update
+            finally:
+                self.strict_index_check = strict
+        e.check_error_flag()
+        self._fast_inputs_pending = False
+        hit = pred.cpu().numpy().astype(bool)
+        correct = np.cumsum(hit)
+        accuracy = [float(correct[i] / (i + 1) * 100) for i in sorted(set(range(0, n, 1000)) | {n - 1})]
+        counts = {"correct": int(correct[-1]), "wrong": int(n - correct[-1])}
+        return time() - start, accuracy[-1], accuracy, counts
+
+    # ------------------------------------------------------------------------------------------------------
     # inference / online protocol (reference fm_adam.py:84-119)
     # ------------------------------------------------------------------------------------------------------
     def predict(self, Xi, Xv):

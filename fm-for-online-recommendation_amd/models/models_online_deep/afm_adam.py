@@ -224,6 +224,14 @@ class AFMAdam(nn.Module):
         self._after_step()
         return out
 
+    def fit_pairs(self, Xi, Xv, item_fields, negatives=None, n_neg=1, margin=0.0, candidates=None, generator=None):
+        raise NotImplementedError(f"{self._name}.fit_pairs: the pair loss is built for the pure FM logit (FMAdam); the "
+                                  "attentional FM would need the pair epilogue inside the AFM step")
+
+    def run_pair_experiment(self, Xi, Xv, item_fields, negatives=None, n_neg=1, margin=0.0, candidates=None, generator=None):
+        raise NotImplementedError(f"{self._name}.run_pair_experiment: the pair loss is built for the pure FM logit (FMAdam); the "
+                                  "attentional FM would need the pair epilogue inside the AFM step")
+
     def _mean_logloss(self, Xi, Xv, y, chunk=16384):
         """The mean BCE-with-logits over a data set, evaluated by batches (reference eval_by_batch, :143-165)."""
         total, N = 0.0, len(y)

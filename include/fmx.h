@@ -360,6 +360,52 @@ int fmx_fm_online_run(const fmx_table_t *table, const fmx_hyper_t *hyper, int32_
                       const int32_t *idx, const float *xv, const float *y, int32_t N, uint8_t *pred_out, float *loss_out,
                       int32_t *error, fmx_stream_t stream);
 
+/* ---- pairwise-ranking (BPR) training of the pure FM ----
+ * A batch of B_pairs pairs is idx [2 B_pairs, F] (and xv [2 B_pairs, F] or null) in fmx_fm_forward's layout: row 2i is the
+ * positive sample of pair i, row 2i + 1 the negative (typically the positive's row with the item columns replaced; nothing
+ * requires that).  With d_i = z[2i] - z[2i + 1]: loss_i = -log(sigmoid(d_i) + margin), margin >= 0 and finite (0: BPR, in the
+ * stable softplus form; the reference uses 0.1), g_i = d loss_i / d d_i = -sigmoid(d_i) sigmoid(-d_i) / (sigmoid(d_i) + margin).
+ * Shared refusals: a null table / hyper / idx, a count < 1 and a bad margin are FMX_ERR_ARG; tables whose fields are pieces of
+ * index columns (field_cols / field_base) FMX_ERR_UNSUPPORTED.  No labels are read.
+ * Restates: the pair objective of reference models/models_meta_emb/meta_fm.py:145-169 for the FM logit. */
+
+/* The forward pass of the 2 B_pairs rows with the pair epilogue: out->S / bi / first / sfirst / sbi / logit exactly as
+ * fmx_fm_forward(FMX_LOSS_NONE) writes them for the same rows (bit-identical), and, where asked for,
+ *   out->dz[2i] = g_i * inv_b, out->dz[2i + 1] = -out->dz[2i] (the same float negated: the two sum to exactly 0),
+ *   out->loss[2i] = loss_i, out->loss[2i + 1] = 0.
+ * With these fmx_fm_update(B = 2 B_pairs, dz_first = dz_bi = dz, loss_b = loss) is the exact step of inv_b * sum_i loss_i.
+ * (reference meta_fm.py:145-169: out_pos, out_neg, -log(sigmoid(out_pos - out_neg) + margin).) */
+int fmx_fm_pair_forward(const fmx_table_t *table, const fmx_hyper_t *hyper, const int32_t *idx, const float *xv, int32_t B_pairs,
+                        float margin, float inv_b, const fmx_fwd_out_t *out, fmx_stream_t stream);
+
+/* One pair step = fmx_sort_occurrences(2 B_pairs) + fmx_fm_pair_forward + fmx_fm_update(2 B_pairs) on one stream, under any rule
+ * the table's layout takes; loss_out[0] = inv_b * sum_i loss_i.  workspace: fmx_workspace_bytes(table, 2 * B_pairs) bytes
+ * (smaller: FMX_ERR_SHAPE); fwd->S, fwd->loss, fwd->dz must be non-null, sized for 2 B_pairs samples; 2 * B_pairs beyond the
+ * sort's width is refused as fmx_sort_occurrences refuses it.
+ * Replaces: the loss.backward() + optimizer.step() of the reference's pair objective (meta_fm.py:145-169). */
+int fmx_fm_pair_step(const fmx_table_t *table, const fmx_hyper_t *hyper, int32_t rule, const int32_t *idx, const float *xv,
+                     int32_t B_pairs, float margin, float inv_b, void *workspace, int64_t workspace_bytes, const fmx_fwd_out_t *fwd,
+                     float *loss_out, fmx_stream_t stream);
+
+/* n_steps pair steps over a device-resident pool idx_pool [n_pool, 2 B_pairs, F] (every feature value 1): step s takes batch
+ * (s mod n_pool) and, under FMX_RULE_ADAM, is step hyper->step + s + 1 of the table; loss_out [n_steps] or null.  The table ends
+ * bit-identical to n_steps calls of fmx_fm_pair_step.  (The pair objective of reference meta_fm.py:145-169, batched as
+ * fmx_fm_stream batches the pointwise one.) */
+int fmx_fm_pair_stream(const fmx_table_t *table, const fmx_hyper_t *hyper, int32_t rule, const int32_t *idx_pool, int32_t n_pool,
+                       int32_t B_pairs, float margin, float inv_b, int32_t n_steps, void *workspace, int64_t workspace_bytes,
+                       const fmx_fwd_out_t *fwd, float *loss_out, fmx_stream_t stream);
+
+/* The online predict-then-fit protocol restated for pairs, on N device-resident pairs idx [2N, F]: for every pair,
+ * pred_out[i] = z_pos > z_neg, logit_out[2i], logit_out[2i + 1] (or null) and loss_out[i] (or null) with the weights BEFORE the
+ * pair's update, then one pair step on that pair alone (B_pairs = 1, inv_b = 1).  One wavefront walks the stream; the table and
+ * bias end bit-identical to N calls of fmx_fm_pair_step with B_pairs = 1.  Under FMX_RULE_ADAM pair i is step
+ * hyper->step + i + 1.  Needs n_fields <= 4 * (64 / (kp / 4)) as fmx_fm_online_run does (both samples' rows fit the wavefront's
+ * registers), else FMX_ERR_UNSUPPORTED.  An out-of-range index sets *error to 1.
+ * (The pair objective of reference meta_fm.py:145-169 under the protocol of fm_adam.py:90-119.) */
+int fmx_fm_pair_online_run(const fmx_table_t *table, const fmx_hyper_t *hyper, int32_t rule, const int32_t *idx, const float *xv,
+                           int32_t N, float margin, uint8_t *pred_out, float *logit_out, float *loss_out, int32_t *error,
+                           fmx_stream_t stream);
+
 /* ---- the small relu MLP on top of the bi-interaction vector (online steps of DeepFM / NFM and the ONN classes) ----
  * params: per layer W [out, in] row-major then b [out]; layer 0 maps k -> hidden, the others hidden -> hidden; the network's
  * contribution to the logit is the sum of the last activation (reference deepfm_adam.py:82-88: there is no output layer).
