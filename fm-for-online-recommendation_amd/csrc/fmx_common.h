@@ -83,9 +83,12 @@ struct MlpReduceArgs {
 // fmx_mlp_section without its last launch: `deferred` receives the arguments of the reduction instead, for a caller that carries
 // its blocks in another launch of the same stream (fmx_deepfm_stream: inside the table update's) or launches it itself
 // (mlp_launch_reduce).  Defined in fmx_mlp.hip.
+// pair_margin >= 0: the pair mode (fmx_mlp_pair_section, fmx_deepfm_pair_stream) -- the B rows are B / 2 pairs, row 2 i the positive
+// and row 2 i + 1 the negative, the loss is pair_loss_dz of their logits' difference under that margin; y and loss_kind are not read.
 int mlp_section_deferred_reduce(const fmx_mlp_t *mlp, int32_t loss_kind, const float *bi, int32_t ld_bi, const float *base, const float *y, int32_t B,
                                 float inv_b, void *workspace, float *logit_out, float *dz_out, float *gbi_out, int32_t ld_gbi, float *grads,
-                                float lr_apply, float *loss_out, hipStream_t st, MlpReduceArgs *deferred, const char *who = "fmx_mlp_section");
+                                float lr_apply, float *loss_out, hipStream_t st, MlpReduceArgs *deferred, const char *who = "fmx_mlp_section",
+                                float pair_margin = -1.f);
 void mlp_launch_reduce(const MlpReduceArgs &a, hipStream_t st);
 // the host-side checks of fmx_mlp_section_opt / fmx_deepfm_stream_opt on the network, its buffers and its optimizer state for a
 // call of n_steps steps; `who` names the entry point in the message.  Defined in fmx_mlp.hip.

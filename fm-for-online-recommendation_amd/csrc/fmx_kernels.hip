@@ -2617,7 +2617,8 @@ static int deepfm_stream_impl(const fmx_table_t *table, const fmx_hyper_t *hyper
                               int32_t fm_term, const int32_t *idx_pool, const float *y_pool, int32_t n_pool, int32_t B, float inv_b,
                               int32_t n_steps, void *workspace, int64_t workspace_bytes, void *mlp_workspace, int64_t mlp_workspace_bytes,
                               const fmx_fwd_out_t *fwd, float *dz, float *gbi, float *grads, float lr_mlp, const fmx_mlp_opt_t *opt,
-                              float *loss_out, fmx_stream_t stream, const char *who) {
+                              float *loss_out, fmx_stream_t stream, const char *who, float pair_margin = -1.f) {
+  const bool pair = pair_margin >= 0.f;  // fmx_deepfm_pair_stream: B = 2 B_pairs rows, the pair loss under that margin, no labels
   if (!opt && adaptive_rule(rule)) return refuse_adaptive(rule, who);
   if (int rc = check_table(table)) return rc;
   if (int rc = check_rule(table, rule)) return rc;
@@ -2627,10 +2628,17 @@ static int deepfm_stream_impl(const fmx_table_t *table, const fmx_hyper_t *hyper
   // NFM: k_first_plus_bias reads bias[0], the bias weight of the weights and the moments layouts
   if (!fm_term && (!fwd->sfirst || (opt ? table->layout == FMX_LAYOUT_FTRL : table->layout != FMX_LAYOUT_WEIGHTS)))
     return fail(FMX_ERR_UNSUPPORTED, "%s: fm_term = 0 (NFM) needs fwd->sfirst and a table in the weights%s layout", who, opt ? " or the moments" : "");
-  if (!idx_pool || !y_pool || n_pool < 1 || n_steps < 0 || B < 1) return fail(FMX_ERR_ARG, "%s: bad pool / step count", who);
+  if (!idx_pool || (!pair && !y_pool) || n_pool < 1 || n_steps < 0 || B < 1) return fail(FMX_ERR_ARG, "%s: bad pool / step count", who);
   if (opt) {
     if (int rc = check_adam(hyper, rule, n_steps)) return rc;
     if (int rc = mlp_opt_check(mlp, B, mlp_workspace, mlp_workspace_bytes, grads, opt, n_steps, who)) return rc;
+  }
+  if (pair && !opt) {  // the pair stream is told the size of the network's workspace under either rule, and checks it
+    const int64_t need = fmx_mlp_section_workspace_bytes(mlp, B);
+    if (need < 0) return fail(FMX_ERR_UNSUPPORTED, "%s: needs 1 <= layers <= %d, k >= 1, hidden >= 1", who, MLP_BIG_MAX_L);
+    if (mlp_workspace_bytes < need)
+      return fail(FMX_ERR_SHAPE, "%s: the MLP workspace holds %lld bytes, fmx_mlp_section_workspace_bytes asks for %lld", who,
+                  (long long)mlp_workspace_bytes, (long long)need);
   }
   if (mlp->k > table->kp) return fail(FMX_ERR_SHAPE, "%s: the MLP reads k=%d columns of a bi of kp=%d", who, mlp->k, table->kp);
   if (!aligned16(gbi) || !aligned16(dz)) return fail(FMX_ERR_ALIGN, "dz and gbi must be 16-byte aligned");
@@ -2646,7 +2654,7 @@ static int deepfm_stream_impl(const fmx_table_t *table, const fmx_hyper_t *hyper
     }
     if (rc == FMX_OK)
       rc = mlp_section_deferred_reduce(mlp, loss_kind, fwd->bi, table->kp, fwd->logit, y, B, inv_b, mlp_workspace, nullptr, dz, gbi, table->kp,
-                                       grads, opt ? 0.f : lr_mlp, loss_out ? loss_out + s : nullptr, st, &red, who);
+                                       grads, opt ? 0.f : lr_mlp, loss_out ? loss_out + s : nullptr, st, &red, who, pair_margin);
     if (rc == FMX_OK && opt) mlp_reduce_set_opt(red, *opt, opt->step + s + 1);  // step s of the call is step t = opt->step + s + 1 of the network
     return rc;
   };
@@ -2675,6 +2683,26 @@ int fmx_deepfm_stream_opt(const fmx_table_t *table, const fmx_hyper_t *hyper, in
   if (!opt) return fail(FMX_ERR_ARG, "fmx_deepfm_stream_opt: opt is null");
   return deepfm_stream_impl(table, hyper, rule, mlp, loss_kind, fm_term, idx_pool, y_pool, n_pool, B, inv_b, n_steps, workspace, workspace_bytes,
                             mlp_workspace, mlp_workspace_bytes, fwd, dz, gbi, grads, 0.f, opt, loss_out, stream, "fmx_deepfm_stream_opt");
+}
+
+// the pair form of the two streams above: B_pairs pairs are 2 B_pairs rows of the pool (row 2 i the positive, row 2 i + 1 the
+// negative), the table forward has no loss, the MLP section evaluates the pair loss (k_mlp_chain<true> / k_mlp_pair_loss), and
+// sort, update and the riding reduction are the pointwise stream's on those rows.  The refusals of the fmx_fm_pair_* family come
+// first, then deepfm_stream_impl's
+int fmx_deepfm_pair_stream(const fmx_table_t *table, const fmx_hyper_t *hyper, int32_t rule, const fmx_mlp_t *mlp, int32_t fm_term,
+                           const int32_t *idx_pool, int32_t n_pool, int32_t B_pairs, float margin, float inv_b, int32_t n_steps,
+                           void *workspace, int64_t workspace_bytes, void *mlp_workspace, int64_t mlp_workspace_bytes,
+                           const fmx_fwd_out_t *fwd, float *dz, float *gbi, float *grads, float lr_mlp, const fmx_mlp_opt_t *opt,
+                           float *loss_out, fmx_stream_t stream) {
+  const char *who = "fmx_deepfm_pair_stream";
+  if (int rc = check_pair_args(table, hyper, idx_pool, B_pairs, "B_pairs", margin, who)) return rc;
+  if (int rc = check_sort_geometry(table, pair_rows(B_pairs))) return rc;  // (as fmx_sort_occurrences reports it)
+  if (n_pool < 1) return fail(FMX_ERR_ARG, "%s: n_pool = %d must be >= 1", who, n_pool);
+  if (n_steps < 0) return fail(FMX_ERR_ARG, "%s: n_steps = %d must be >= 0", who, n_steps);
+  return named(deepfm_stream_impl(table, hyper, rule, mlp, FMX_LOSS_NONE, fm_term, idx_pool, nullptr, n_pool, 2 * B_pairs, inv_b, n_steps, workspace,
+                                  workspace_bytes, mlp_workspace, mlp_workspace_bytes, fwd, dz, gbi, grads, opt ? 0.f : lr_mlp, opt,
+                                  loss_out, stream, who, margin),
+               who);
 }
 
 // ---- the field-owner step with the library's own communicator (fmx_comm.hip) ----

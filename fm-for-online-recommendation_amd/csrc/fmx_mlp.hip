@@ -1,7 +1,8 @@
 // fmx_mlp.hip -- the relu MLP of DeepFM / NFM / the ONN classes at mini-batch sizes (fp32 MFMA) and its C ABI:
-// fmx_mlp_section, fmx_mlp_section_opt, fmx_mlp_forward_batch, fmx_mlp_hedge_section, fmx_mlp_section_workspace_bytes.  Kernels:
+// fmx_mlp_section, fmx_mlp_section_opt, fmx_mlp_pair_section, fmx_mlp_forward_batch, fmx_mlp_hedge_section, fmx_mlp_section_workspace_bytes.  Kernels:
 // fmx_mlp_gemm.inc.
 #include "fmx_common.h"
+#include <cmath>
 
 namespace {
 #include "fmx_mlp_gemm.inc"
@@ -332,14 +333,46 @@ int fmx_mlp_section_opt(const fmx_mlp_t *mlp, int32_t loss_kind, const float *bi
   return check_launch(who);
 }
 
+int fmx_mlp_pair_section(const fmx_mlp_t *mlp, const float *bi, int32_t ld_bi, const float *base, int32_t B_pairs, float margin, float inv_b,
+                         void *workspace, int64_t workspace_bytes, float *logit_out, float *dz_out, float *gbi_out, int32_t ld_gbi,
+                         float *grads, float lr_apply, const fmx_mlp_opt_t *opt, float *loss_out, fmx_stream_t stream) {
+  const char *who = "fmx_mlp_pair_section";
+  if (B_pairs < 1 || B_pairs > INT32_MAX / 2)
+    return fail(FMX_ERR_ARG, "%s: B_pairs = %d must be >= 1 and 2 * B_pairs rows within int32", who, B_pairs);
+  if (!(margin >= 0.f) || !std::isfinite(margin)) return fail(FMX_ERR_ARG, "%s: margin = %g must be finite and >= 0", who, (double)margin);
+  const int32_t B = 2 * B_pairs;
+  if (opt) {
+    if (int rc = mlp_opt_check(mlp, B, workspace, workspace_bytes, grads, opt, 1, who)) return rc;
+  } else {
+    if (int rc = mlp_big_check(mlp, B, workspace, who)) return rc;
+    const int64_t need = (int64_t)mlp_big_carve(mlp, B, nullptr).bytes;
+    if (workspace_bytes < need)
+      return fail(FMX_ERR_SHAPE, "%s: the MLP workspace holds %lld bytes, fmx_mlp_section_workspace_bytes asks for %lld", who,
+                  (long long)workspace_bytes, (long long)need);
+  }
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (!opt)  // the network under SGD by lr_apply, applied in the section's own reduction (fmx_mlp_section)
+    return mlp_section_deferred_reduce(mlp, FMX_LOSS_NONE, bi, ld_bi, base, nullptr, B, inv_b, workspace, logit_out, dz_out, gbi_out, ld_gbi, grads,
+                                       lr_apply, loss_out, st, nullptr, who, margin);
+  MlpReduceArgs red;  // ... or under opt's rule for step t = opt->step + 1 (fmx_mlp_section_opt)
+  if (int rc = mlp_section_deferred_reduce(mlp, FMX_LOSS_NONE, bi, ld_bi, base, nullptr, B, inv_b, workspace, logit_out, dz_out, gbi_out, ld_gbi,
+                                           grads, 0.f, loss_out, st, &red, who, margin))
+    return rc;
+  mlp_reduce_set_opt(red, *opt, opt->step + 1);
+  mlp_launch_reduce(red, st);
+  return check_launch(who);
+}
+
 extern "C++" int fmxd::mlp_section_deferred_reduce(const fmx_mlp_t *mlp, int32_t loss_kind, const float *bi, int32_t ld_bi, const float *base,
                                                    const float *y, int32_t B, float inv_b, void *workspace, float *logit_out, float *dz_out,
                                                    float *gbi_out, int32_t ld_gbi, float *grads, float lr_apply, float *loss_out, hipStream_t st,
-                                                   MlpReduceArgs *deferred, const char *who) {
+                                                   MlpReduceArgs *deferred, const char *who, float pair_margin) {
+  const bool pair = pair_margin >= 0.f;
   if (int rc = mlp_big_check(mlp, B, workspace, who)) return rc;
-  if (!bi || !base || !y || !dz_out || !gbi_out || !grads) return fail(FMX_ERR_ARG, "%s: null argument", who);
+  if (!bi || !base || (!pair && !y) || !dz_out || !gbi_out || !grads) return fail(FMX_ERR_ARG, "%s: null argument", who);
   if (ld_bi < mlp->k || ld_gbi < mlp->k) return fail(FMX_ERR_SHAPE, "%s: ld_bi / ld_gbi smaller than k", who);
-  if (loss_kind != FMX_LOSS_BCE_LOGITS && loss_kind != FMX_LOSS_BCE_SIGMOID) return fail(FMX_ERR_ARG, "%s needs a loss", who);
+  if (!pair && loss_kind != FMX_LOSS_BCE_LOGITS && loss_kind != FMX_LOSS_BCE_SIGMOID) return fail(FMX_ERR_ARG, "%s needs a loss", who);
+  if (pair && B % 2) return fail(FMX_ERR_ARG, "%s: the pair mode takes an even number of rows, not %d", who, B);
   const MlpBigWs w = mlp_big_carve(mlp, B, workspace);
   const int L = mlp->n_layers, H = mlp->hidden;
   const size_t act = align_up((size_t)B * H * 4, 256) / 4;
@@ -372,6 +405,7 @@ extern "C++" int fmxd::mlp_section_deferred_reduce(const fmx_mlp_t *mlp, int32_t
     c.ld_gbi = ld_gbi;
     c.loss_kind = loss_kind;
     c.inv_b = inv_b;
+    c.margin = pair_margin;
     c.stamps = tune().mlp_chain == 2 ? reinterpret_cast<unsigned long long *>(w.loss_lb) : nullptr;  // debug: tools/mlp_chain_stamps.py
 #ifdef FMX_MLP_EXPERIMENTS  // diagnostic build only (tools/corun_experiment.py): FMX_EXP_ONLY_WGRAD=1 launches the gradient kernel alone
     static int only_wgrad = getenv("FMX_EXP_ONLY_WGRAD") ? atoi(getenv("FMX_EXP_ONLY_WGRAD")) : 0;
@@ -381,7 +415,8 @@ extern "C++" int fmxd::mlp_section_deferred_reduce(const fmx_mlp_t *mlp, int32_t
       return check_launch("fmx_mlp_section (gradient kernel only)");
     }
 #endif
-    hipLaunchKernelGGL(k_mlp_chain, dim3((B + CH_R - 1) / CH_R), dim3(256), chain_lds_bytes(H), st, c);
+    if (pair) hipLaunchKernelGGL(k_mlp_chain<true>, dim3((B + CH_R - 1) / CH_R), dim3(256), chain_lds_bytes(H), st, c);
+    else hipLaunchKernelGGL(k_mlp_chain<false>, dim3((B + CH_R - 1) / CH_R), dim3(256), chain_lds_bytes(H), st, c);
     mlp_big_backward(mlp, w, bi, ld_bi, B, nullptr, gbi_out, ld_gbi, grads, lr_apply, loss_out, inv_b, st, true, deferred);
     return check_launch("fmx_mlp_section (k_mlp_chain)");
   }
@@ -400,7 +435,9 @@ extern "C++" int fmxd::mlp_section_deferred_reduce(const fmx_mlp_t *mlp, int32_t
     a.ldh = H;
     a.loss_kind = loss_kind;
     a.inv_b = inv_b;
-    hipLaunchKernelGGL(k_mlp_loss, dim3((B + 3) / 4), dim3(256), 0, st, a);
+    a.margin = pair_margin;
+    if (pair) hipLaunchKernelGGL(k_mlp_pair_loss, dim3((B / 2 + 3) / 4), dim3(256), 0, st, a);
+    else hipLaunchKernelGGL(k_mlp_loss, dim3((B + 3) / 4), dim3(256), 0, st, a);
   }
   mlp_big_backward(mlp, w, bi, ld_bi, B, nullptr, gbi_out, ld_gbi, grads, lr_apply, loss_out, inv_b, st, false, deferred);
   return check_launch("fmx_mlp_section");

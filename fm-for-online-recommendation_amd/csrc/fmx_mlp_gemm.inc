@@ -297,7 +297,47 @@ struct MlpLossArgs {
   float *loss_b;      // [B]
   int B, hidden, ldh, loss_kind;
   float inv_b;
+  float margin;       // k_mlp_pair_loss only (appended: the offsets k_mlp_loss reads do not depend on it)
 };
+
+// the row sum of k_mlp_loss and k_mlp_pair_loss: strided per lane, then a fixed butterfly (every lane ends with the same bits)
+__device__ __forceinline__ float mlp_row_sum(const float *h, int hidden, int lane) {
+  float s = 0.f;
+  for (int j = lane; j < hidden; j += 64) s += h[j];
+#pragma unroll
+  for (int m = 1; m < 64; m <<= 1) s += __shfl_xor(s, m);
+  return s;
+}
+
+// ---- the pair form (fmx_mlp_pair_section): B = 2 B_pairs rows, row 2 i the positive of pair i, row 2 i + 1 its negative; the
+//      loss is pair_loss_dz of d_i = z[2 i] - z[2 i + 1].  ONE wave owns a PAIR: it takes both rows' sums as k_mlp_loss takes
+//      one (the same loop, the same butterfly: z has k_mlp_loss's bits), so nothing crosses a wave -- no LDS, no barrier.
+//      dz[2 i + 1] is dz[2 i] negated, loss_b[2 i + 1] = +0; no label is read. ----
+__global__ __launch_bounds__(256) void k_mlp_pair_loss(MlpLossArgs a) {
+  const int lane = threadIdx.x & 63;
+  const int b = 2 * (blockIdx.x * 4 + (threadIdx.x >> 6));  // the pair's positive row
+  if (b >= a.B) return;                                     // (a.B is even: both rows exist or neither)
+  const float *h = a.H + (size_t)b * a.ldh;
+  const float z0 = a.base[b] + mlp_row_sum(h, a.hidden, lane);
+  const float z1 = a.base[b + 1] + mlp_row_sum(h + a.ldh, a.hidden, lane);
+  float loss, dz;
+  pair_loss_dz(z0 - z1, a.margin, a.inv_b, loss, dz);
+  if (lane == 0) {
+    if (a.out) {
+      a.out[b] = z0;
+      a.out[b + 1] = z1;
+    }
+    a.dz[b] = dz;
+    a.dz[b + 1] = -dz;
+    a.loss_b[b] = loss;
+    a.loss_b[b + 1] = 0.f;
+  }
+  float *d = a.dH + (size_t)b * a.ldh;
+  for (int j = lane; j < a.hidden; j += 64) {
+    d[j] = h[j] > 0.f ? dz : 0.f;
+    d[a.ldh + j] = h[a.ldh + j] > 0.f ? -dz : 0.f;
+  }
+}
 
 __global__ __launch_bounds__(256) void k_mlp_loss(MlpLossArgs a) {
   const int lane = threadIdx.x & 63;
@@ -467,6 +507,7 @@ struct ChainArgs {
   int B, k, H, L, ld_bi, ld_gbi, loss_kind;
   float inv_b;
   unsigned long long *stamps;  // debug (FMX_MLP_CHAIN=2): [workgroup][16] s_memrealtime after every phase, else null
+  float margin;                // k_mlp_chain<true> only (appended: the offsets the pointwise kernel reads do not depend on it)
 };
 
 // LDS: two activation buffers [H / 4][16][4], the row-sum partials [4][16], dL/dlogit [16], the relu bits [L][256 threads]
@@ -630,6 +671,10 @@ __device__ __forceinline__ void chain_bwd_first(const float *W, const float *Ain
   for (int i = 0; i < NT0; ++i) reinterpret_cast<f32x4 *>(part)[(w * 4 + i) * 64 + lane] = acc[i];
 }
 
+// PAIR (fmx_mlp_pair_section): the rows are pairs, row 2 i the positive and row 2 i + 1 the negative, and the loss site evaluates
+// pair_loss_dz on z[2 i] - z[2 i + 1] instead of the BCE on a label.  A slab's first row and a.B are even, so a pair lies in one
+// slab, on two neighbouring lanes of the t < CH_R threads, valid or not together.  PAIR = false: the pointwise section.
+template <bool PAIR>
 __global__ __launch_bounds__(256) void k_mlp_chain(ChainArgs a) {
   extern __shared__ __attribute__((aligned(16))) float ch_smem[];
   constexpr int H = CH_MAXH;
@@ -702,7 +747,21 @@ __global__ __launch_bounds__(256) void k_mlp_chain(ChainArgs a) {
   if (t < CH_R) {
     const int b = b0 + t;
     float dz = 0.f;
-    if (b < a.B) {
+    if constexpr (PAIR) {
+      const bool ok = b < a.B;
+      const float s = ((red[t] + red[CH_R + t]) + red[2 * CH_R + t]) + red[3 * CH_R + t];
+      const float z = (ok ? a.base[b] : 0.f) + s;
+      const float zo = xor_lane_f<1>(z, lane);  // the partner's logit: taken by all sixteen lanes, in front of the branch on ok
+      const bool pos = (t & 1) == 0;
+      float loss, g;
+      pair_loss_dz(pos ? z - zo : zo - z, a.margin, a.inv_b, loss, g);  // both lanes: the same operands, the same bits
+      if (ok) {
+        dz = pos ? g : -g;
+        if (a.logit_out) a.logit_out[b] = z;
+        a.dz_out[b] = dz;
+        a.loss_b[b] = pos ? loss : 0.f;
+      }
+    } else if (b < a.B) {
       const float s = ((red[t] + red[CH_R + t]) + red[2 * CH_R + t]) + red[3 * CH_R + t];
       const float z = a.base[b] + s;
       float loss;

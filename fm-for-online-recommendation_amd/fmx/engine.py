@@ -313,6 +313,43 @@ class FMEngine:
         run.keep = keep
         return run
 
+    def prepare_deepfm_pair_stream(self, hyper, rule, params, grads, k, hidden, n_layers, lr_mlp, idx_pool, margin=0.0, loss_out=None,
+                                   stream=None, fm_term=True, mlp_opt=None):
+        """-> run(n_steps): prepare_deepfm_stream under the pair loss (fmx_deepfm_pair_stream) over a resident pool idx_pool
+        [n_pool, 2 B_pairs, F], row 2i the positive of pair i and row 2i + 1 its negative; no labels.  mlp_opt None: the network
+        under SGD by lr_mlp; an MlpOpt: its rule (lr_mlp is not read).  A run advances the table's step count (moments tables) and
+        mlp_opt's by its steps.  The caller keeps the tensors alive and does not grow the engine between prepare and run."""
+        n_pool, B2, F = idx_pool.shape
+        assert F == self.table.n_fields and B2 % 2 == 0 and B2 >= 2 and idx_pool.is_contiguous()
+        assert loss_out is None or loss_out.is_contiguous()
+        B = B2 // 2
+        self._ensure(B2)
+        out = self._fwd_out(want_first=False, want_bi=True)
+        m = self._mlp_struct(params, k, hidden, n_layers)
+        self._mlp_big_buffers(m, k, hidden, n_layers, B2)
+        fn, check = self.lib.fmx_deepfm_pair_stream, _lib.check
+        fixed = (self.table.c_struct(), hyper.ref(), _lib.RULES[rule], C.byref(m), int(bool(fm_term)), idx_pool.data_ptr(), n_pool, B,
+                 float(margin), 1.0 / B)
+        tail = (self.workspace.data_ptr(), self._ws_bytes(), self._mlp_ws.data_ptr(), self._mlp_ws.numel() * 4, C.byref(out),
+                self._mlp_dz.data_ptr(), self._mlp_gbi.data_ptr(), grads.data_ptr(), float(lr_mlp),
+                None if mlp_opt is None else mlp_opt.ref(), _ptr(loss_out), self._stream(stream))
+        cap = None if loss_out is None else loss_out.numel()
+        keep = (out, m, hyper, mlp_opt, params, grads, idx_pool, loss_out, self.workspace, self._mlp_ws, self._mlp_dz, self._mlp_gbi)
+        steps, advance = self._steps, self._advance
+
+        def run(n_steps):
+            if cap is not None and n_steps > cap:
+                raise ValueError(f"loss_out holds {cap} steps, {n_steps} asked for")
+            steps(hyper)
+            if mlp_opt is not None:
+                mlp_opt.c.step = mlp_opt.step     # (the bound structs are hyper's and mlp_opt's own: a second call continues both counts)
+            check(fn(*fixed, n_steps, *tail))
+            advance(n_steps)
+            if mlp_opt is not None:
+                mlp_opt.step += n_steps
+        run.keep = keep
+        return run
+
     def _prepare_deepfm_stream_opt(self, hyper, mlp_opt, fixed, out, m, params, grads, idx_pool, y_pool, loss_out, stream):
         fn, check = self.lib.fmx_deepfm_stream_opt, _lib.check
         tail = (self.workspace.data_ptr(), self._ws_bytes(), self._mlp_ws.data_ptr(), self._mlp_ws.numel() * 4, C.byref(out),
@@ -493,6 +530,7 @@ class FMEngine:
             self._mlp_dz = torch.empty(B, dtype=torch.float32, device=self.device)
             self._mlp_gbi = torch.empty((B, self.table.kp), dtype=torch.float32, device=self.device)
             self._mlp_loss = torch.zeros(1, dtype=torch.float32, device=self.device)
+            self._mlp_logit = torch.empty(B, dtype=torch.float32, device=self.device)      # mlp_pair_section's logit_out
             self._mlp_ws_key = key
 
     def mlp_forward_batch(self, params, k, hidden, n_layers, bi, base, B, want_layers):
@@ -532,6 +570,26 @@ class FMEngine:
                                             self._mlp_gbi.data_ptr(), self.table.kp, grads.data_ptr(), lr_apply,
                                             self._mlp_loss.data_ptr(), self._stream()))
         return self._mlp_loss, self._mlp_dz, self._mlp_gbi
+
+    def mlp_pair_section(self, params, grads, k, hidden, n_layers, bi, base, B_pairs, inv_b=None, margin=0.0, lr_apply=0.0,
+                         mlp_opt=None):
+        """mlp_section under the pair loss (fmx_mlp_pair_section): `bi` [2 B_pairs, ld] and `base` [2 B_pairs] hold row 2i = the
+        positive of pair i, row 2i + 1 = its negative; no labels.  -> (loss [1] = the mean pair loss, dz [2 B_pairs] with
+        dz[2i + 1] = -dz[2i], gbi [2 B_pairs, kp], logit [2 B_pairs]: the whole network's logits, fmx_mlp_section's bits).
+        `grads` is filled; lr_apply != 0 also applies SGD; mlp_opt (an MlpOpt): its rule instead, and its step advances by one."""
+        B_pairs = int(B_pairs)
+        if B_pairs < 1 or bi.shape[0] < 2 * B_pairs or base.numel() < 2 * B_pairs:
+            raise ValueError(f"mlp_pair_section: bi {tuple(bi.shape)} / base {tuple(base.shape)} do not hold 2 x {B_pairs} rows")
+        m = self._mlp_struct(params, k, hidden, n_layers)
+        self._mlp_big_buffers(m, k, hidden, n_layers, 2 * B_pairs)
+        _lib.check(self.lib.fmx_mlp_pair_section(C.byref(m), bi.data_ptr(), bi.stride(0), base.data_ptr(), B_pairs, float(margin),
+                                                 1.0 / B_pairs if inv_b is None else inv_b, self._mlp_ws.data_ptr(),
+                                                 self._mlp_ws.numel() * 4, self._mlp_logit.data_ptr(), self._mlp_dz.data_ptr(),
+                                                 self._mlp_gbi.data_ptr(), self.table.kp, grads.data_ptr(), lr_apply,
+                                                 None if mlp_opt is None else mlp_opt.ref(), self._mlp_loss.data_ptr(), self._stream()))
+        if mlp_opt is not None:
+            mlp_opt.step += 1
+        return self._mlp_loss, self._mlp_dz, self._mlp_gbi, self._mlp_logit
 
     def check_error_flag(self):
         """The device-side error word (include/fmx.h, Conventions): 1 -> IndexError like nn.Embedding; 2 -> HandOffTimeout

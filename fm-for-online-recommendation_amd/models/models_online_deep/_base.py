@@ -593,13 +593,69 @@ class OnlineFMBase(nn.Module):
                     pred[i] = e.logit[0] > e.logit[1]            # the step's own forward: the logits before its update
             finally:
                 self.strict_index_check = strict
-        e.check_error_flag()
+        return self._pair_experiment_result(start, pred)
+
+    def _pair_experiment_result(self, start, pred):
+        """run_pair_experiment's 4-tuple from the per-pair predictions [n] on the device (n >= 1); reads the index flag once"""
+        self._engine.check_error_flag()
         self._fast_inputs_pending = False
         hit = pred.cpu().numpy().astype(bool)
+        n = len(hit)
         correct = np.cumsum(hit)
         accuracy = [float(correct[i] / (i + 1) * 100) for i in sorted(set(range(0, n, 1000)) | {n - 1})]
         counts = {"correct": int(correct[-1]), "wrong": int(n - correct[-1])}
         return time() - start, accuracy[-1], accuracy, counts
+
+    # ---- the same objective on the whole network's logit (DeepFMAdam / NFMAdam: NetworkPairTraining below) ----
+    def _fit_pairs_full(self, Xi, Xv, item_fields, negatives, n_neg, margin, candidates, generator):
+        """fit_pairs(full=True): forward with no loss, the MLP section under the pair loss on bi (fmx_mlp_pair_section), sort,
+        table update with dz (and dz again for the FM term where forward() has it) and gbi.  The network's rule follows _fit's
+        native branches: 'sgd' inside the section's reduction, 'signadam' (and 'ftrl', whose hidden layers _fit also gives the
+        fresh Adam) the closed form p -= lr g / (|g| + 1e-8) on the flat gradients, 'adam' / 'adagrad' the model's fused
+        optimizer state.  Every batch size goes through the section."""
+        rule = self.update_rule
+        if rule in ("adam", "adagrad") and getattr(self, "_mlp_fused", None) is None:
+            raise ValueError(f"{self._name}.fit_pairs(full=True) under update_rule={rule!r} trains the hidden layers inside the MLP "
+                             "section: construct the model with fused_optimizer=True")
+        self.train()
+        rows, xv = self._pair_rows(Xi, Xv, item_fields, negatives, n_neg, candidates, generator)
+        e, k, lr = self._engine, self.embedding_size, float(self.n)
+        B2 = e.forward(self._hyper, rows, xv)
+        P = B2 // 2
+        if getattr(self, "_mlp_gflat", None) is None:
+            self._mlp_gflat = torch.zeros_like(self._mlp_flat)
+        loss, dz, gbi, _ = e.mlp_pair_section(self._mlp_flat, self._mlp_gflat, k, self.neuron_per_hidden_layer, self.num_hidden_layers,
+                                              e.bi[:B2], self._base_logit(B2).contiguous(), P, 1.0 / P, margin=margin,
+                                              lr_apply=lr if rule == "sgd" else 0.0, mlp_opt=self._mlp_fused)
+        if rule in ("signadam", "ftrl"):
+            g = self._mlp_gflat
+            with torch.no_grad():
+                self._mlp_flat.sub_(lr * g / (g.abs() + 1e-8))
+        e.sort(rows)
+        e.update(self._hyper, rule, B2, xv, dz, dz if self._fm_term_in_forward else None, gbi, inv_b=1.0 / P, with_loss=False)
+        out = loss[0].clone()
+        self._after_step()
+        return out
+
+    def _run_pair_experiment_full(self, Xi, Xv, item_fields, negatives, n_neg, margin, candidates, generator):
+        """run_pair_experiment(full=True): the host loop of one-pair fit_pairs(full=True) calls; pair i's prediction is
+        z_pos > z_neg of that step's own logits, the whole network's before its update."""
+        start = time()
+        rows, xv = self._pair_rows(Xi, Xv, item_fields, negatives, n_neg, candidates, generator)
+        n, e = rows.shape[0] // 2, self._engine
+        if n == 0:
+            return time() - start, 0.0, [], {"correct": 0, "wrong": 0}
+        fields = [int(f) for f in (item_fields if hasattr(item_fields, "__len__") else [item_fields])]
+        pred = torch.empty(n, dtype=torch.uint8, device=self.device)
+        strict, self.strict_index_check = self.strict_index_check, False      # one check after the loop, no sync inside it
+        try:
+            for i in range(n):
+                pos, neg = rows[2 * i:2 * i + 1], rows[2 * i + 1:2 * i + 2, fields]
+                self._fit_pairs_full(pos, None if xv is None else xv[2 * i:2 * i + 1], fields, neg, 1, margin, None, None)
+                pred[i] = e._mlp_logit[0] > e._mlp_logit[1]
+        finally:
+            self.strict_index_check = strict
+        return self._pair_experiment_result(start, pred)
 
     # ------------------------------------------------------------------------------------------------------
     # inference / online protocol (reference fm_adam.py:84-119)
@@ -766,3 +822,30 @@ class OnlineFMBase(nn.Module):
         if self._onn:
             s += f"-N{self.n}"
         return s
+
+
+class NetworkPairTraining:
+    """DeepFMAdam's and NFMAdam's fit_pairs / run_pair_experiment: OnlineFMBase's, with the keyword full.  full=False is the
+    base class's refusal (the pair loss of fmx_fm_pair_* is the pure FM logit's); full=True -- the word recommend / rank use for
+    the whole network -- trains on the pair loss of the logit forward() returns (fmx_mlp_pair_section).  Listed in front of
+    OnlineFMBase in the class's bases."""
+
+    def _pair_refusal_or_full(self, method, full):
+        if full:
+            return
+        try:
+            self._pair_refusal(method)
+        except NotImplementedError as err:
+            raise NotImplementedError(f"{err}; {method}(..., full=True) trains on the pair loss of the whole network's logit") from None
+
+    def fit_pairs(self, Xi, Xv, item_fields, negatives=None, n_neg=1, margin=0.0, candidates=None, generator=None, full=False):
+        """OnlineFMBase.fit_pairs's arguments; full=True: one mini-batch pair step of tables and network on the logit forward()
+        returns, under the model's update rule ('adam' / 'adagrad' need fused_optimizer=True).  Returns the mean pair loss."""
+        self._pair_refusal_or_full("fit_pairs", full)
+        return self._fit_pairs_full(Xi, Xv, item_fields, negatives, n_neg, margin, candidates, generator)
+
+    def run_pair_experiment(self, Xi, Xv, item_fields, negatives=None, n_neg=1, margin=0.0, candidates=None, generator=None, full=False):
+        """OnlineFMBase.run_pair_experiment's arguments and 4-tuple; full=True: predict z_pos > z_neg through the whole network,
+        then fit_pairs(full=True) on that pair alone, pair by pair."""
+        self._pair_refusal_or_full("run_pair_experiment", full)
+        return self._run_pair_experiment_full(Xi, Xv, item_fields, negatives, n_neg, margin, candidates, generator)

@@ -535,6 +535,47 @@ int fmx_deepfm_stream_opt(const fmx_table_t *table, const fmx_hyper_t *hyper, in
                           const fmx_fwd_out_t *fwd, float *dz, float *gbi, float *grads, const fmx_mlp_opt_t *opt, float *loss_out,
                           fmx_stream_t stream);
 
+/* ---- pairwise-ranking (BPR) training of DeepFM / NFM: the pair loss on the whole network's logit ----
+ * The layout is fmx_fm_pair_forward's: B_pairs pairs are 2 B_pairs rows, row 2i the positive and row 2i + 1 the negative;
+ * z_b = base_b + sum_j H_L[b, j] as the pointwise section sums it, d_i = z[2i] - z[2i + 1], loss_i = -log(sigmoid(d_i) + margin)
+ * and g_i = d loss_i / d d_i as stated there (one device function evaluates both families).  No label is read.
+ *
+ * fmx_mlp_section on pairs: bi [2 B_pairs, ld_bi], base [2 B_pairs]; logit_out [2 B_pairs] (may be null) has the bits
+ * fmx_mlp_section writes for the same bi / base;
+ *   dz_out[2i] = g_i * inv_b, dz_out[2i + 1] = -dz_out[2i] (the same float negated: the two sum to exactly 0),
+ *   gbi_out [2 B_pairs, ld_gbi] and grads as in fmx_mlp_section with that dz; loss_out [1] = inv_b * sum_i loss_i (may be null).
+ * opt null: params -= lr_apply * grads in the same pass (lr_apply = 0 leaves the parameters alone); opt given: opt->rule as in
+ * fmx_mlp_section_opt, this call being step t = opt->step + 1, and lr_apply is not read.  grads, dz_out, gbi_out and logit_out
+ * do not depend on opt / lr_apply.  workspace: fmx_mlp_section_workspace_bytes for 2 * B_pairs rows (smaller: FMX_ERR_SHAPE).
+ * Before anything is launched: B_pairs < 1 and a negative / NaN / infinite margin are FMX_ERR_ARG, then what fmx_mlp_section
+ * refuses and, with opt, what fmx_mlp_section_opt refuses.
+ * Replaces: nn.Linear + relu + autograd of DeepFMAdam.fit / NFMAdam.fit (reference deepfm_adam.py:79-89,106-119;
+ * nfm_adam.py:78-88,105-118) under the pair objective of reference models/models_meta_emb/meta_fm.py:145-169. */
+int fmx_mlp_pair_section(const fmx_mlp_t *mlp, const float *bi, int32_t ld_bi, const float *base, int32_t B_pairs, float margin,
+                         float inv_b, void *workspace, int64_t workspace_bytes, float *logit_out, float *dz_out, float *gbi_out,
+                         int32_t ld_gbi, float *grads, float lr_apply, const fmx_mlp_opt_t *opt, float *loss_out,
+                         fmx_stream_t stream);
+
+/* n_steps pair steps of DeepFM (fm_term = 1) / NFM (fm_term = 0) over a device-resident pool idx_pool [n_pool, 2 B_pairs, F]
+ * (every feature value 1): step s takes batch (s mod n_pool).  opt null: the checks and rules of fmx_deepfm_stream (the network
+ * under SGD by lr_mlp); opt given: those of fmx_deepfm_stream_opt (lr_mlp is not read; step s is step hyper->step + s + 1 of
+ * the tables and opt->step + s + 1 of the network).  In front of them the refusals of the fmx_fm_pair_stream family: a null table /
+ * hyper / idx_pool, B_pairs < 1, a bad margin: FMX_ERR_ARG; field_cols / field_base: FMX_ERR_UNSUPPORTED; 2 * B_pairs beyond the
+ * sort's width: what fmx_sort_occurrences reports.  fwd, dz, gbi, workspace and mlp_workspace are sized for 2 * B_pairs rows;
+ * mlp_workspace_bytes is checked under either rule.  fm_term = 1: base is the FM logit, the update takes dz_first = dz_bi = dz
+ * and gbi; fm_term = 0: base is first-order sum + bias, the update takes dz_first = dz, no dz_bi, and gbi.
+ * The result is, bit for bit, the one of calling fmx_fm_forward with FMX_LOSS_NONE on the 2 B_pairs rows, the NFM base add,
+ * fmx_mlp_pair_section, fmx_sort_occurrences and fmx_fm_update per step, the counts advanced by the caller.  The bias gradient
+ * sum_b dz_b is exactly +0, so FMX_RULE_SGD / SIGNADAM / FTRL / ADAGRAD leave the bias words as they are (FMX_RULE_ADAM decays its
+ * moments).  loss_out [n_steps] or null.
+ * Replaces: the mini-batch driver loop over DeepFMAdam.fit / NFMAdam.fit (reference main_experiment.py:92-105 with
+ * deepfm_adam.py:106-119, nfm_adam.py:105-118) under the pair objective of reference meta_fm.py:145-169. */
+int fmx_deepfm_pair_stream(const fmx_table_t *table, const fmx_hyper_t *hyper, int32_t rule, const fmx_mlp_t *mlp, int32_t fm_term,
+                           const int32_t *idx_pool, int32_t n_pool, int32_t B_pairs, float margin, float inv_b, int32_t n_steps,
+                           void *workspace, int64_t workspace_bytes, void *mlp_workspace, int64_t mlp_workspace_bytes,
+                           const fmx_fwd_out_t *fwd, float *dz, float *gbi, float *grads, float lr_mlp, const fmx_mlp_opt_t *opt,
+                           float *loss_out, fmx_stream_t stream);
+
 /* fmx_mlp_fit (the one-workgroup kernel: B <= 16, k <= 63, hidden <= 64, layers <= 8) with the hidden layers under opt->rule
  * (FMX_RULE_SGD, FMX_RULE_ADAGRAD, FMX_RULE_ADAM as stated at fmx_mlp_opt_t: the network's ADAM is torch.optim.Adam, the tables'
  * is SparseAdam) instead of `rule`: the thread that sums a parameter's gradient over the batch in sample order applies the rule to
