@@ -25,7 +25,7 @@
 // No float is accumulated with atomics and every sum has one fixed order that depends on (B, F, t, k) alone: results are
 // bit-identical run to run.  The table update between the two launches is fmx_fm_update_occ (fmx_kernels.hip).
 
-#include "fmx_common.h"
+#include "fmx_host.h"
 
 namespace {
 
@@ -886,19 +886,12 @@ __global__ __launch_bounds__(AFM_ONL_THREADS) void k_afm_online(AfmOnlArgs a) {
 // ------------------------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------------------------
-int kp_ok(int kp) { return kp == 4 || kp == 8 || kp == 16 || kp == 32 || kp == 64; }
-
+// the shared table check (FTRL and MOMENTS rows: z_offset and the row stride that covers both halves included), then what the
+// AFM kernels add to it
 int check_afm(const fmx_table_t *t, const fmx_afm_t *afm, const char *who) {
-  if (!t || !afm) return fail(FMX_ERR_ARG, "%s: null table / afm", who);
-  if (!t->rows || !t->field_offsets || !t->bias) return fail(FMX_ERR_ARG, "%s: table has a null pointer", who);
-  if (!afm->params) return fail(FMX_ERR_ARG, "%s: null attention parameters", who);
-  if (!kp_ok(t->kp) || t->k < 1 || t->k > t->kp) return fail(FMX_ERR_SHAPE, "%s: kp=%d must be 4/8/16/32/64 and >= k=%d", who, t->kp, t->k);
-  if (t->layout != FMX_LAYOUT_WEIGHTS && t->layout != FMX_LAYOUT_FTRL && t->layout != FMX_LAYOUT_MOMENTS)
-    return fail(FMX_ERR_ARG, "%s: unknown layout %d", who, t->layout);
-  if (t->row_stride % 4 || t->row_stride < t->kp + 4) return fail(FMX_ERR_SHAPE, "%s: row_stride=%d", who, t->row_stride);
-  if (!aligned16(t->rows)) return fail(FMX_ERR_ALIGN, "%s: table rows must be 16-byte aligned", who);
-  if (t->field_cols || t->field_base)
-    return fail(FMX_ERR_UNSUPPORTED, "%s: tables whose fields are pieces of index columns are not supported", who);
+  if (int rc = named(check_table(t), who)) return rc;
+  if (!afm || !afm->params) return fail(FMX_ERR_ARG, "%s: null attention parameters", who);
+  if (mapped(t)) return fail(FMX_ERR_UNSUPPORTED, "%s: tables whose fields are pieces of index columns are not supported", who);
   if (t->n_fields < 2 || t->n_fields > AFM_MAX_F)
     return fail(FMX_ERR_UNSUPPORTED, "%s: %d fields; the AFM kernels take 2 <= F <= %d", who, t->n_fields, AFM_MAX_F);
   if (afm->k != t->k) return fail(FMX_ERR_SHAPE, "%s: afm->k=%d differs from the table's k=%d", who, afm->k, t->k);
@@ -936,14 +929,7 @@ int launch_afm_side_k(const AfmSideArgs &a, hipStream_t st) {
 
 template <bool BWD>
 int launch_afm(const AfmArgs &a, int kp, bool ftrl, hipStream_t st) {
-  auto go = [&](auto KP) { return ftrl ? launch_afm_k<KP, true, BWD>(a, st) : launch_afm_k<KP, false, BWD>(a, st); };
-  switch (kp) {
-    case 4: return go(std::integral_constant<int, 4>{});
-    case 8: return go(std::integral_constant<int, 8>{});
-    case 16: return go(std::integral_constant<int, 16>{});
-    case 32: return go(std::integral_constant<int, 32>{});
-    default: return go(std::integral_constant<int, 64>{});
-  }
+  return with_kp(kp, [&](auto KP) { return ftrl ? launch_afm_k<KP, true, BWD>(a, st) : launch_afm_k<KP, false, BWD>(a, st); });
 }
 
 AfmArgs fill_afm(const fmx_table_t *table, const fmx_afm_t *afm, const fmx_hyper_t *hyper, const int32_t *idx, const float *xv,
@@ -958,12 +944,7 @@ AfmArgs fill_afm(const fmx_table_t *table, const fmx_afm_t *afm, const fmx_hyper
   a.y = y;
   a.params = afm->params;
   a.error = error;
-  a.h.lr = hyper->lr;
-  a.h.eps = hyper->eps;
-  a.h.alpha = 1.0f / hyper->alpha;  // the kernels multiply by 1/alpha (ftrl_w)
-  a.h.beta = hyper->beta;
-  a.h.l1 = hyper->l1;
-  a.h.l2 = hyper->l2;
+  a.h = kernel_hyper(hyper, -1);
   a.B = B;
   a.F = table->n_fields;
   a.k = afm->k;
@@ -998,20 +979,13 @@ AfmWs carve_afm(const fmx_table_t *table, const fmx_afm_t *afm, int B, void *bas
   return w;
 }
 
-int check_rule_layout(const fmx_table_t *t, int rule, const char *who) {
-  const bool ok = ((rule == FMX_RULE_SIGNADAM || rule == FMX_RULE_SGD) && t->layout == FMX_LAYOUT_WEIGHTS) ||
-                  (rule == FMX_RULE_FTRL && t->layout == FMX_LAYOUT_FTRL) ||
-                  ((rule == FMX_RULE_ADAGRAD || rule == FMX_RULE_ADAM) && t->layout == FMX_LAYOUT_MOMENTS);
-  return ok ? FMX_OK : fail(FMX_ERR_ARG, "%s: rule %d does not go with layout %d", who, rule, t->layout);
-}
-
 // fmx_afm_step's own checks; w receives the carved workspace
 int check_afm_step(const fmx_table_t *table, const fmx_hyper_t *hyper, int32_t rule, const fmx_afm_t *afm, const int32_t *idx, const float *y,
                    int32_t B, void *workspace, int64_t workspace_bytes, const float *attn_grad_out, AfmWs &w, const char *who) {
   if (int rc = check_afm(table, afm, who)) return rc;
   if (!hyper || !idx || !y || !workspace || !attn_grad_out) return fail(FMX_ERR_ARG, "%s: null argument", who);
   if (B < 1) return fail(FMX_ERR_ARG, "%s: B must be >= 1", who);
-  if (int rc = check_rule_layout(table, rule, who)) return rc;
+  if (int rc = named(check_rule(table, rule), who)) return rc;
   if (!aligned16(workspace)) return fail(FMX_ERR_ALIGN, "%s: workspace must be 16-byte aligned", who);
   w = carve_afm(table, afm, B, workspace);
   if (w.table_bytes < 0) return (int)w.table_bytes;
@@ -1038,13 +1012,8 @@ int check_afm_opt(const fmx_table_t *table, const fmx_hyper_t *hyper, int32_t ru
     return fail(FMX_ERR_ARG, "%s: opt->step = %d must be >= 0 and step + steps of the call <= 2^31 - 1", who, opt->step);
   if (!aligned16(afm->params) || (opt->m && !aligned16(opt->m)) || (opt->v && !aligned16(opt->v)))
     return fail(FMX_ERR_ALIGN, "%s: afm->params, opt->m and opt->v must be 16-byte aligned", who);
-  if (rule == FMX_RULE_ADAM) {
-    if (!(hyper->beta1 >= 0.f && hyper->beta1 < 1.f && hyper->beta2 >= 0.f && hyper->beta2 < 1.f))
-      return fail(FMX_ERR_ARG, "%s: FMX_RULE_ADAM: beta1 = %g and beta2 = %g must lie in [0, 1)", who, hyper->beta1, hyper->beta2);
-    if (hyper->step < 0 || (int64_t)hyper->step + n_steps > INT32_MAX)
-      return fail(FMX_ERR_ARG, "%s: FMX_RULE_ADAM: step = %d must be >= 0 and step + steps of the call <= 2^31 - 1", who, hyper->step);
-  }
-  return step_geometry_check(table, B, who);
+  if (int rc = named(check_adam(hyper, rule, n_steps), who)) return rc;
+  return named(check_sort_geometry(table, B), who);
 }
 
 // what apply_rule / moments_upd read for step t (1-based) of the attention parameters: ADAM's constants in double, once per step
@@ -1084,34 +1053,10 @@ int afm_step_launches(const fmx_table_t *table, const fmx_hyper_t *hyper, int32_
     return check_launch("k_afm_reduce");
   }
   const AfmOptArgs o = afm_opt_args(afm, *opt, opt_t);
-  switch (opt->rule) {
-    case FMX_RULE_SIGNADAM: hipLaunchKernelGGL(k_afm_reduce_opt<FMX_RULE_SIGNADAM>, grid, block, 0, st, w.part, n, a.G, attn_grad_out, o); break;
-    case FMX_RULE_SGD: hipLaunchKernelGGL(k_afm_reduce_opt<FMX_RULE_SGD>, grid, block, 0, st, w.part, n, a.G, attn_grad_out, o); break;
-    case FMX_RULE_ADAGRAD: hipLaunchKernelGGL(k_afm_reduce_opt<FMX_RULE_ADAGRAD>, grid, block, 0, st, w.part, n, a.G, attn_grad_out, o); break;
-    default: hipLaunchKernelGGL(k_afm_reduce_opt<FMX_RULE_ADAM>, grid, block, 0, st, w.part, n, a.G, attn_grad_out, o); break;
-  }
+  with_one_of<FMX_RULE_SIGNADAM, FMX_RULE_SGD, FMX_RULE_ADAGRAD, FMX_RULE_ADAM>(opt->rule, [&](auto RULE) {  // (check_afm_opt: one of these)
+    hipLaunchKernelGGL(k_afm_reduce_opt<RULE>, grid, block, 0, st, w.part, n, a.G, attn_grad_out, o);
+  });
   return check_launch("k_afm_reduce_opt");
-}
-
-// the caller's hyper-parameters for the steps of one call: step s of the call is step hyper->step + s + 1 of the tables (the fields
-// appended for ADAM are read for it alone); the caller of this advances .step
-// (a field added to fmx_hyper_t must be carried over below, or fmx_afm_stream / fmx_afm_online_run part from fmx_afm_step_opt)
-static_assert(sizeof(fmx_hyper_t) == 40, "afm_call_hyper copies fmx_hyper_t field by field: add the new field to the copy");
-fmx_hyper_t afm_call_hyper(const fmx_hyper_t *hyper, int32_t rule) {
-  fmx_hyper_t hs;
-  memset(&hs, 0, sizeof(hs));
-  hs.lr = hyper->lr;
-  hs.eps = hyper->eps;
-  hs.alpha = hyper->alpha;
-  hs.beta = hyper->beta;
-  hs.l1 = hyper->l1;
-  hs.l2 = hyper->l2;
-  if (rule == FMX_RULE_ADAM) {
-    hs.beta1 = hyper->beta1;
-    hs.beta2 = hyper->beta2;
-    hs.step = hyper->step;
-  }
-  return hs;
 }
 
 template <int KP>
@@ -1187,7 +1132,7 @@ int fmx_afm_stream(const fmx_table_t *table, const fmx_hyper_t *hyper, int32_t r
   const size_t F = (size_t)table->n_fields;
   // Every batch is sorted on `stream` in front of its step, as fmx_afm_step does it: the steps are one plain queue of launches
   // (no side stream, no events; the sort-ahead loop of fmx_fm_stream is not used here).
-  fmx_hyper_t hs = afm_call_hyper(hyper, rule);
+  fmx_hyper_t hs = hyper_for(hyper, rule);  // step s of the call is step hyper->step + s + 1 of the tables
   for (int s = 0; s < n_steps; ++s, ++hs.step) {
     const size_t j = (size_t)(s % n_pool);
     if (int rc = afm_step_launches(table, &hs, rule, afm, idx_pool + j * B * F, xv_pool ? xv_pool + j * B * F : nullptr, y_pool + j * B, B,
@@ -1213,7 +1158,7 @@ int fmx_afm_online_run(const fmx_table_t *table, const fmx_hyper_t *hyper, int32
   const int nb = tune().afm_online_persistent ? afm_online_buffers(F, table->kp, afm->t, G, want_mom, mom) : 0;
   if (nb == 0) {
     // the per-sample launches of fmx_afm_step_opt(B = 1, inv_b = 1), queued without any host synchronisation
-    fmx_hyper_t hs = afm_call_hyper(hyper, rule);
+    fmx_hyper_t hs = hyper_for(hyper, rule);
     for (int i = 0; i < N; ++i, ++hs.step) {
       if (int rc = afm_step_launches(table, &hs, rule, afm, idx + (size_t)i * F, xv ? xv + (size_t)i * F : nullptr, y + i, 1, 1.0f, workspace,
                                      w, attn_grad_out, loss_out ? loss_out + i : nullptr, error, opt, opt->step + i + 1, st,
@@ -1237,8 +1182,7 @@ int fmx_afm_online_run(const fmx_table_t *table, const fmx_hyper_t *hyper, int32
   a.logit = logit_out;
   a.loss = loss_out;
   a.error = error;
-  a.h = afm_call_hyper(hyper, rule);  // ADAM: the kernel derives each sample's constants from lr, beta1, beta2, step
-  a.h.alpha = 1.0f / hyper->alpha;    // the kernels multiply by 1/alpha (ftrl_w)
+  a.h = kernel_hyper(hyper, rule);  // ADAM: the kernel derives each sample's constants from lr, beta1, beta2, step
   a.o_lr = opt->lr;
   a.o_eps = opt->eps;
   a.o_beta1 = opt->beta1;
@@ -1255,13 +1199,7 @@ int fmx_afm_online_run(const fmx_table_t *table, const fmx_hyper_t *hyper, int32
   a.G = G;
   a.nb = nb;
   a.mom_lds = mom ? 1 : 0;
-  switch (table->kp) {
-    case 4: return launch_afm_online_k<4>(a, st);
-    case 8: return launch_afm_online_k<8>(a, st);
-    case 16: return launch_afm_online_k<16>(a, st);
-    case 32: return launch_afm_online_k<32>(a, st);
-    default: return launch_afm_online_k<64>(a, st);
-  }
+  return with_kp(table->kp, [&](auto KP) { return launch_afm_online_k<KP>(a, st); });
 }
 
 int fmx_afm_side(const fmx_table_t *table, const fmx_afm_t *afm, const fmx_hyper_t *hyper, const int32_t *idx, const float *xv,
@@ -1300,14 +1238,7 @@ int fmx_afm_side(const fmx_table_t *table, const fmx_afm_t *afm, const fmx_hyper
   for (int l = 0; l < n_sel; ++l) a.fields[l] = (int8_t)fields[l];
   const hipStream_t st = static_cast<hipStream_t>(stream);
   const bool ftrl = table->layout == FMX_LAYOUT_FTRL;
-  auto go = [&](auto KP) { return ftrl ? launch_afm_side_k<KP, true>(a, st) : launch_afm_side_k<KP, false>(a, st); };
-  switch (table->kp) {
-    case 4: return go(std::integral_constant<int, 4>{});
-    case 8: return go(std::integral_constant<int, 8>{});
-    case 16: return go(std::integral_constant<int, 16>{});
-    case 32: return go(std::integral_constant<int, 32>{});
-    default: return go(std::integral_constant<int, 64>{});
-  }
+  return with_kp(table->kp, [&](auto KP) { return ftrl ? launch_afm_side_k<KP, true>(a, st) : launch_afm_side_k<KP, false>(a, st); });
 }
 
 }  // extern "C"

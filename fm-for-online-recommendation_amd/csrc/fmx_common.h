@@ -1,5 +1,6 @@
 // fmx_common.h -- what the translation units of libfmx.so share: the error plumbing and the tuning switches (one copy, defined
-// in fmx_kernels.hip), and the device helpers every kernel file uses (per-unit copies in an anonymous namespace).
+// in fmx_kernels.hip), and the device helpers every kernel file uses (per-unit copies in an anonymous namespace).  The host-side
+// vocabulary of the units that take a table (checks, dispatchers, workspace) is fmx_host.h.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
@@ -97,9 +98,6 @@ int mlp_opt_check(const fmx_mlp_t *mlp, int32_t B, const void *workspace, int64_
 // ... its checks of a non-null opt alone (rule, m / v given, betas, step count), shared with the one-workgroup kernel's _opt calls
 int mlp_opt_state_check(const fmx_mlp_opt_t *opt, int64_t n_steps, const char *who);
 int mlp_reduce_blocks_per_layer(const MlpReduceArgs &a, int threads);
-// what fmx_sort_occurrences and fmx_fm_update_occ check of a table and a batch size before they launch (the table's fields, the
-// sort's width and its 32-bit composites), for a caller that must refuse before ITS first launch.  Defined in fmx_kernels.hip.
-int step_geometry_check(const fmx_table_t *table, int32_t B, const char *who);
 }  // namespace fmxd
 using namespace fmxd;
 
@@ -110,6 +108,7 @@ inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 
 constexpr uint32_t SENT = 0xFFFFFFFFu;
 constexpr int WAVE = 64;
 constexpr int MAX_SORT_WIDTH = 32768;  // 128 KiB of the 160 KiB LDS
+constexpr int SORT_CHUNK = 1024;       // composites per chunk of the chunked sort (fmx_sort.inc); the workspace holds its runs from 2 chunks on
 
 // ------------------------------------------------------------------------------------------------------------
 // device helpers

@@ -1,0 +1,193 @@
+// fmx_host.h -- the host-side vocabulary of the translation units that take an fmx_table_t: the kp / rule dispatchers, the
+// table's derived sizes, the hyper-parameters as the launches take them, the step workspace, and the shared checks and the
+// launch seams between the units (one definition each; the comment at a declaration names its home).  Host-only.
+#pragma once
+#include <type_traits>
+
+#include "fmx_common.h"
+
+namespace fmxd {
+
+// the step workspace: [ sorted u32 F*Bp (x 2*SORT_AHEAD_MAX: the online loop sorts a group of batches ahead) |
+//                       meta i32 F*tiles*2 | counter | parts f32 F*tiles*2*REC ], each 256-byte aligned (carve)
+struct Workspace {
+  uint32_t *sorted;       // buffer 0 of a ring of 2 * SORT_AHEAD_MAX buffers, `sorted_stride` elements apart
+  size_t sorted_stride;
+  uint32_t *runs;         // SORT_AHEAD_MAX buffers of the same shape: the chunk-sorted intermediate of k_sort_chunk / k_sort_merge
+  int32_t *meta;
+  int32_t *counter;  // step counter (one int32 in its own 256-byte slot; unused by the current loop)
+  float *parts;
+  size_t bytes;
+};
+
+struct SortBatch {  // several batches of a pool in one launch
+  int n_pool = 1, first = 0, n_batches = 1;
+  int64_t pool_stride = 0, sorted_stride = 0;
+};
+
+// ---- the shared checks (fmx_kernels.hip).  Each leaves its message in g_err; named() puts the entry point in front ----
+int check_table(const fmx_table_t *t);
+int check_rule(const fmx_table_t *t, int rule);
+// ADAM's hyper-parameters for a call of n_steps steps: betas in [0, 1) (torch's bounds) and t = step + n_steps in int32
+int check_adam(const fmx_hyper_t *h, int rule, int64_t n_steps);
+int check_sort_geometry(const fmx_table_t *t, int B);
+// the caller's workspace against what a step of B samples on this table needs NOW (the table's sort fields may have been
+// split since the buffer was sized: fmx_workspace_bytes grows with them)
+int check_workspace(const fmx_table_t *t, int B, const void *workspace, int64_t workspace_bytes, const char *who);
+// what every pair entry point refuses before it looks further: each message names the argument
+int check_pair_args(const fmx_table_t *table, const fmx_hyper_t *hyper, const int32_t *idx, int64_t n_pairs, const char *count_name,
+                    float margin, const char *who);
+// a shared check's refusal, with the entry point in front of its message
+int named(int rc, const char *who);
+// the entry points outside the pure-FM table steps: a refusal that names the rule
+int refuse_adaptive(int rule, const char *who);
+
+// ---- the launches one unit issues for another; the arguments have been checked ----
+// fmx_kernels.hip.  `runs`: the workspace's chunk-sort intermediate (Workspace::runs; used when Bp >= 2 * SORT_CHUNK)
+int forward_impl(const fmx_table_t *table, const fmx_hyper_t *hyper, const int32_t *idx, const float *xv, const float *y,
+                 int32_t B, int32_t loss_kind, float inv_b, const fmx_fwd_out_t *out, hipStream_t st);
+int sort_impl(const fmx_table_t *table, const int32_t *idx, int32_t B, uint32_t *sorted, uint32_t *runs, int32_t *error,
+              hipStream_t st, const SortBatch *mb = nullptr);
+// fmx_update.hip
+int update_impl(const fmx_table_t *table, const fmx_hyper_t *hyper, int32_t rule, const Workspace &w,
+                const uint32_t *sorted, const float *xv, const float *S, const float *dz_first, const float *dz_bi, const float *gbi,
+                int32_t B, const float *loss_b, float inv_b, float *loss_out, hipStream_t st, int32_t *step_counter = nullptr,
+                int32_t sample_ld = 0, int32_t *err_flag = nullptr, const MlpReduceArgs *rider = nullptr);
+// occ [B, ld_occ]: sample b's gradients of its fields' rows, field f's kp floats at b * ld_occ + f * kp (update_body's OCC)
+int update_occ_impl(const fmx_table_t *table, const fmx_hyper_t *hyper, int32_t rule, const Workspace &w, const float *xv,
+                    const float *dz_first, const float *occ, int32_t ld_occ, int32_t B, const float *loss_b, float inv_b,
+                    float *loss_out, hipStream_t st);
+
+}  // namespace fmxd
+
+namespace {
+
+inline int lpr_of(int kp) {
+  switch (kp) {
+    case 4: return 1;
+    case 8: return 2;
+    case 16: return 4;
+    case 32: return 8;
+    case 64: return 16;
+    default: return 0;
+  }
+}
+
+// f(std::integral_constant<int, LPR>{}) for a table's kp (anything lpr_of rejects takes the widest)
+template <class Fn>
+decltype(auto) with_lpr(int kp, Fn &&f) {
+  switch (lpr_of(kp)) {
+    case 1: return f(std::integral_constant<int, 1>{});
+    case 2: return f(std::integral_constant<int, 2>{});
+    case 4: return f(std::integral_constant<int, 4>{});
+    case 8: return f(std::integral_constant<int, 8>{});
+    default: return f(std::integral_constant<int, 16>{});
+  }
+}
+
+// ... the same with KP = 4 LPR, for the kernels that take the row width itself
+template <class Fn>
+decltype(auto) with_kp(int kp, Fn &&f) {
+  return with_lpr(kp, [&](auto LPR) { return f(std::integral_constant<int, 4 * LPR>{}); });
+}
+
+// f(std::integral_constant<int, V>{}) for the V of VS that equals v; false (and no call) when none does
+template <int... VS, class Fn>
+bool with_one_of(int v, Fn &&f) {
+  return ((v == VS && (f(std::integral_constant<int, VS>{}), true)) || ...);
+}
+
+// f(LAYOUT, RULE) as integral constants for an update rule and the layout it pairs with (check_rule); false, and no call,
+// for a rule it does not know.  with_rule_wf: the rules of the weights and FTRL layouts only (the launches the adaptive
+// rules do not take -- fmx_online_run_mlp's k_online_mlp -- are not instantiated for them).
+template <bool MOMENTS_RULES, class Fn>
+bool with_rule_impl(int rule, Fn &&f) {
+  using Weights = std::integral_constant<int, FMX_LAYOUT_WEIGHTS>;
+  using Moments = std::integral_constant<int, FMX_LAYOUT_MOMENTS>;
+  switch (rule) {
+    case FMX_RULE_SIGNADAM: f(Weights{}, std::integral_constant<int, FMX_RULE_SIGNADAM>{}); return true;
+    case FMX_RULE_SGD: f(Weights{}, std::integral_constant<int, FMX_RULE_SGD>{}); return true;
+    case FMX_RULE_FTRL: f(std::integral_constant<int, FMX_LAYOUT_FTRL>{}, std::integral_constant<int, FMX_RULE_FTRL>{}); return true;
+    case FMX_RULE_ADAGRAD:
+      if constexpr (MOMENTS_RULES) {
+        f(Moments{}, std::integral_constant<int, FMX_RULE_ADAGRAD>{});
+        return true;
+      }
+      return false;
+    case FMX_RULE_ADAM:
+      if constexpr (MOMENTS_RULES) {
+        f(Moments{}, std::integral_constant<int, FMX_RULE_ADAM>{});
+        return true;
+      }
+      return false;
+    default: return false;
+  }
+}
+template <class Fn>
+bool with_rule(int rule, Fn &&f) { return with_rule_impl<true>(rule, f); }
+template <class Fn>
+bool with_rule_wf(int rule, Fn &&f) { return with_rule_impl<false>(rule, f); }
+
+inline bool adaptive_rule(int rule) { return rule == FMX_RULE_ADAGRAD || rule == FMX_RULE_ADAM; }
+inline const char *rule_name(int rule) { return rule == FMX_RULE_ADAM ? "FMX_RULE_ADAM" : "FMX_RULE_ADAGRAD"; }
+
+// the SORT fields of a table: its fields, or the finer partition fmx_table_t.sort_offsets describes
+inline bool mapped(const fmx_table_t *t) { return t->field_cols || t->field_base; }  // fields are pieces of index columns
+inline int n_cols(const fmx_table_t *t) { return t->n_cols > 0 ? t->n_cols : t->n_fields; }
+inline int n_sort_fields(const fmx_table_t *t) { return t->n_sort_fields > 0 ? t->n_sort_fields : t->n_fields; }
+inline const int64_t *sort_offsets(const fmx_table_t *t) { return t->n_sort_fields > 0 ? t->sort_offsets : t->field_offsets; }
+inline const int32_t *sort_cols(const fmx_table_t *t) { return t->n_sort_fields > 0 ? t->sort_cols : nullptr; }
+inline int64_t max_sort_rows(const fmx_table_t *t) { return t->n_sort_fields > 0 ? t->max_sort_field_rows : t->max_field_rows; }
+
+// The caller's hyper-parameters as the launches take them: the six floats every rule reads, and the fields appended after
+// them (beta1, beta2, step) for FMX_RULE_ADAM only -- a caller built against the six-float struct passes a shorter struct and
+// keeps working with the other rules; nothing past its end is read.  Appended fields not read are zero.
+static_assert(sizeof(fmx_hyper_t) == 40, "hyper_for copies fmx_hyper_t field by field: add the new field to the copy");
+inline fmx_hyper_t hyper_for(const fmx_hyper_t *h, int rule) {
+  fmx_hyper_t r;
+  memset(&r, 0, sizeof(r));
+  r.lr = h->lr;
+  r.eps = h->eps;
+  r.alpha = h->alpha;
+  r.beta = h->beta;
+  r.l1 = h->l1;
+  r.l2 = h->l2;
+  if (rule == FMX_RULE_ADAM) {
+    r.beta1 = h->beta1;
+    r.beta2 = h->beta2;
+    r.step = h->step;
+  }
+  return r;
+}
+
+// ... and as a kernel's argument: the kernels multiply by 1/alpha
+inline fmx_hyper_t kernel_hyper(const fmx_hyper_t *h, int rule) {
+  fmx_hyper_t r = hyper_for(h, rule);
+  r.alpha = 1.0f / h->alpha;
+  return r;
+}
+
+constexpr int SORT_AHEAD_MAX = 16;  // batches sorted per side-stream launch in fmx_fm_stream (r3: 16, was 8 -- every group boundary puts a
+                                    // cross-stream wait of 5 - 6 us on the step's stream: 21.33 - 21.39 against 21.53 - 21.79 us per step)
+
+inline Workspace carve(const fmx_table_t *t, int B, void *base) {
+  const size_t F = (size_t)n_sort_fields(t), Bp = (size_t)fmx_sorted_width(B), tiles = Bp >> 6;
+  const size_t rec = 2 * (size_t)t->kp + 4;
+  const size_t o_sorted1 = align_up(F * Bp * 4, 256);
+  const size_t o_runs = 2 * SORT_AHEAD_MAX * o_sorted1;
+  const size_t o_meta = o_runs + (Bp >= 2 * SORT_CHUNK ? SORT_AHEAD_MAX * o_sorted1 : 0);
+  const size_t o_counter = o_meta + align_up(F * tiles * 2 * 4, 256);
+  const size_t o_parts = o_counter + 256;
+  Workspace w;
+  char *p = static_cast<char *>(base);
+  w.sorted = reinterpret_cast<uint32_t *>(p);
+  w.sorted_stride = o_sorted1 / 4;
+  w.runs = reinterpret_cast<uint32_t *>(p + o_runs);
+  w.meta = reinterpret_cast<int32_t *>(p + o_meta);
+  w.counter = reinterpret_cast<int32_t *>(p + o_counter);
+  w.parts = reinterpret_cast<float *>(p + o_parts);
+  w.bytes = o_parts + align_up(F * tiles * 2 * rec * 4, 256);
+  return w;
+}
+
+}  // namespace

@@ -460,7 +460,7 @@ __global__ __launch_bounds__(256) void k_mlp_hedge_alpha(MlpHedgeAlphaArgs a) {
 
 // ---- split-K partials -> flat gradients (W_l then b_l per layer, the layout of fmx_mlp_t.params), fixed order over the
 //      splits; block (0, 0) also reduces the per-sample losses.  blockIdx.y = layer. ----
-// (struct MlpReduceArgs and the reduction itself -- mlp_reduce_block -- live in fmx_common.h: k_fm_update_rider of fmx_kernels.hip
+// (struct MlpReduceArgs and the reduction itself -- mlp_reduce_block -- live in fmx_common.h: k_fm_update_rider of fmx_update.hip
 // carries the same blocks inside the table update's launch)
 __global__ __launch_bounds__(256) void k_mlp_reduce(MlpReduceArgs a) { mlp_reduce_block(a, blockIdx.y, blockIdx.x, gridDim.x); }
 

@@ -1,4 +1,4 @@
-// fmx_pair.inc -- pairwise-ranking (BPR) training of the pure FM: fmx_fm_pair_forward / _step / _stream / _online_run.
+// fmx_pair.inc -- pairwise-ranking (BPR) training of the pure FM, the batched calls: fmx_fm_pair_forward / _step / _stream.
 // Included by fmx_kernels.hip inside its anonymous namespace, behind the kernels and the host helpers it builds on.
 //
 // A batch of B pairs is 2B full-width rows: row 2i the positive sample of pair i, row 2i + 1 the negative.  With
@@ -9,189 +9,11 @@
 // per run, the two occurrences of a row both samples of a pair name included (their cA terms cancel exactly), and the bias
 // gradient is sum dz = exactly 0.  Nothing of the update changes.
 //
-// k_fm_pair_online is k_fm_online for pairs: one wavefront walks N pairs, predict (z_pos > z_neg) then fit on that pair.
-
-// ------------------------------------------------------------------------------------------------------------
-// k_fm_pair_online
-// ------------------------------------------------------------------------------------------------------------
-struct PairOnlineArgs {
-  float *rows;
-  const int64_t *foff;
-  float *bias;
-  const int32_t *idx;  // [2N, F]: rows 2i (positive) and 2i + 1 (negative) of pair i
-  const float *xv;     // [2N, F] or null
-  uint8_t *pred;       // [N] z_pos > z_neg BEFORE the pair's update
-  float *logit;        // [2N] or null
-  float *loss;         // [N] or null
-  int32_t *error;
-  fmx_hyper_t h;
-  int32_t N, F, stride, zoff;
-  float margin;
-};
-
-// The fit of pair i is k_fm_update on a batch of two samples (fmx_fm_pair_step with B = 1, inv_b = 1): per field the sorted list
-// holds the two occurrences by (row, sample).  Two different rows are two runs of one occurrence, each summed from zero; the same
-// row is ONE run whose sums add the positive's terms, then the negative's -- (0 + c_pos) + c_neg -- and the row takes one
-// update_row.  The bias gradient is block_sum's dz[0] + dz[1] = +0, which still goes through bias_step (ADAM's moments decay on a
-// zero gradient); the mean loss is (loss_i + 0) * inv_b.
-template <int LPR, int LAYOUT, int RULE, int NP>
-__global__ __launch_bounds__(64) void k_fm_pair_online(PairOnlineArgs a) {
-  constexpr int SLOTS = WAVE / LPR;
-  const int lane = threadIdx.x & 63;
-  const int slot = lane / LPR, q = lane % LPR;
-  const int kp = LPR * 4;
-  constexpr bool MOM = LAYOUT == FMX_LAYOUT_MOMENTS;
-  float b0 = a.bias[0], b1 = LAYOUT != FMX_LAYOUT_WEIGHTS ? a.bias[1] : 0.f, b2 = MOM ? a.bias[2] : 0.f;
-  int64_t lo[NP];
-  uint32_t vocab[NP];
-  bool live[NP];
-#pragma unroll
-  for (int p = 0; p < NP; ++p) {
-    const int f = p * SLOTS + slot;
-    live[p] = f < a.F;
-    lo[p] = live[p] ? a.foff[f] : 0;
-    vocab[p] = live[p] ? (uint32_t)(a.foff[f + 1] - lo[p]) : 0u;
-  }
-  // the next pair's indices and values: sample t = 0 (positive), 1 (negative).  Branch-free, as in k_fm_online
-  uint32_t li_n[2][NP];
-  float x_n[2][NP];
-  const float *xsrc = a.xv ? a.xv : reinterpret_cast<const float *>(a.idx);
-  const bool has_x = a.xv != nullptr;
-  auto fetch_inputs = [&](int i) {
-    const bool in = i < a.N;
-    uint32_t l_[2][NP];
-    float x_[2][NP];
-#pragma unroll
-    for (int t = 0; t < 2; ++t) {
-#pragma unroll
-      for (int p = 0; p < NP; ++p) {
-        const size_t o = (live[p] && in) ? ((size_t)2 * i + t) * a.F + p * SLOTS + slot : (size_t)0;
-        l_[t][p] = (uint32_t)a.idx[o];
-        x_[t][p] = xsrc[o];
-      }
-    }
-#pragma unroll
-    for (int t = 0; t < 2; ++t) {
-#pragma unroll
-      for (int p = 0; p < NP; ++p) {
-        li_n[t][p] = (live[p] && in) ? l_[t][p] : 0u;
-        x_n[t][p] = (has_x && live[p] && in) ? x_[t][p] : 1.f;
-      }
-    }
-  };
-  fetch_inputs(0);
-  bool bad = false;
-  for (int i = 0; i < a.N; ++i) {
-    uint32_t li[2][NP];
-    float x[2][NP];
-    RowRegs row[2][NP];
-    bool ok[2][NP];
-#pragma unroll
-    for (int t = 0; t < 2; ++t) {
-#pragma unroll
-      for (int p = 0; p < NP; ++p) {
-        li[t][p] = li_n[t][p];
-        x[t][p] = x_n[t][p];
-        ok[t][p] = live[p] && li[t][p] < vocab[p];
-        row[t][p] = load_row_sc1<LAYOUT, RULE>(a.rows + (size_t)(ok[t][p] ? lo[p] + li[t][p] : 0) * a.stride, q, kp, a.zoff);
-        bad = bad || (live[p] && !ok[t][p]);
-      }
-    }
-    fetch_inputs(i + 1);  // independent of the weights: in flight while this pair is processed
-    // ---- forward of both samples: the arithmetic of k_fm_forward ----
-    const float bias_w = bias_weight<LAYOUT>(b0, b1, a.h);
-    float4 S[2];
-    float z[2];
-#pragma unroll
-    for (int t = 0; t < 2; ++t) {
-      float4 s = splat(0.f), ss = splat(0.f);
-      float fo = 0.f;
-#pragma unroll
-      for (int p = 0; p < NP; ++p) {
-        if (ok[t][p]) {
-          const float4 e = x[t][p] * row[t][p].v;
-          s = s + e;
-          ss = ss + e * e;
-          fo += row[t][p].fo.x * x[t][p];
-        }
-      }
-      fm_field_sums<LPR>(s, ss, fo, lane);
-      float sbi;
-      fm_bi<LPR>(s, ss, sbi);
-      fo = __shfl(fo, 0);
-      S[t] = s;
-      z[t] = fo + sbi + bias_w;
-    }
-    fmx_hyper_t h = a.h;  // ADAM: pair i is step a.h.step + i + 1 (adam_consts, as the host derives them for a launch)
-    if (RULE == FMX_RULE_ADAM) adam_consts(a.h.lr, a.h.beta1, a.h.beta2, a.h.step + i + 1, h.lr, h.beta1, h.beta2);
-    float loss, dzp;
-    pair_loss_dz(z[0] - z[1], a.margin, 1.0f, loss, dzp);
-    const float dz[2] = {dzp, -dzp};
-    if (lane == 0) {
-      a.pred[i] = z[0] > z[1] ? 1 : 0;
-      if (a.logit) {
-        a.logit[2 * (size_t)i] = z[0];
-        a.logit[2 * (size_t)i + 1] = z[1];
-      }
-      if (a.loss) a.loss[i] = (0.f + loss) * 1.0f;
-    }
-    // ---- fit ----
-#pragma unroll
-    for (int p = 0; p < NP; ++p) {
-      float4 cV[2];
-      float cA[2], cw[2];
-#pragma unroll
-      for (int t = 0; t < 2; ++t) {  // the occurrence's terms as update_body forms them (dz_bi == dz_first)
-        const float xG = x[t][p] * dz[t];
-        cV[t] = xG * S[t];
-        cA[t] = x[t][p] * xG;
-        cw[t] = x[t][p] * dz[t];
-      }
-      float *rp0 = a.rows + (size_t)(lo[p] + li[0][p]) * a.stride, *rp1 = a.rows + (size_t)(lo[p] + li[1][p]) * a.stride;
-      if (ok[0][p] && ok[1][p] && li[0][p] == li[1][p]) {  // one run of two occurrences, in sample order
-        const float4 rV = (splat(0.f) + cV[0]) + cV[1];
-        const float rA = (0.f + cA[0]) + cA[1], rw = (0.f + cw[0]) + cw[1];
-        update_row<LAYOUT, RULE>(rp0, q, kp, a.zoff, row[0][p], rV, splat(rA), rw, h);
-      } else {
-        if (ok[0][p]) update_row<LAYOUT, RULE>(rp0, q, kp, a.zoff, row[0][p], splat(0.f) + cV[0], splat(0.f + cA[0]), 0.f + cw[0], h);
-        if (ok[1][p]) update_row<LAYOUT, RULE>(rp1, q, kp, a.zoff, row[1][p], splat(0.f) + cV[1], splat(0.f + cA[1]), 0.f + cw[1], h);
-      }
-    }
-    bias_step<LAYOUT, RULE>(b0, b1, b2, dz[0] + dz[1], h);            // exactly +0
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the row stores are acknowledged before the next pair's loads
-  }
-  const bool any_bad = __ballot(bad) != 0ull;
-  if (lane == 0) {
-    a.bias[0] = b0;
-    if (LAYOUT == FMX_LAYOUT_FTRL || (MOM && RULE == FMX_RULE_ADAM)) a.bias[1] = b1;
-    if (MOM) a.bias[2] = b2;
-    if (any_bad && a.error) *a.error = 1;
-  }
-}
-
-template <int LPR, int LAYOUT, int RULE>
-void launch_pair_online_np(const PairOnlineArgs &a, int np, hipStream_t st) {
-  auto launch = [&](auto NP) { hipLaunchKernelGGL((k_fm_pair_online<LPR, LAYOUT, RULE, NP>), dim3(1), dim3(64), 0, st, a); };
-  if (!with_one_of<1, 2, 3>(np, launch)) launch(std::integral_constant<int, 4>{});
-}
+// The online form (fmx_fm_pair_online_run, k_fm_pair_online) is with the other stream walkers in fmx_online.hip.
 
 // ------------------------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------------------------
-// what every pair entry point refuses before it looks further: each message names the argument
-int check_pair_args(const fmx_table_t *table, const fmx_hyper_t *hyper, const int32_t *idx, int64_t n_pairs, const char *count_name,
-                    float margin, const char *who) {
-  if (!table) return fail(FMX_ERR_ARG, "%s: table is null", who);
-  if (int rc = check_table(table)) return named(rc, who);
-  if (!hyper) return fail(FMX_ERR_ARG, "%s: hyper is null", who);
-  if (!idx) return fail(FMX_ERR_ARG, "%s: idx is null", who);
-  if (n_pairs < 1) return fail(FMX_ERR_ARG, "%s: %s = %lld must be >= 1", who, count_name, (long long)n_pairs);
-  if (!(margin >= 0.f) || !std::isfinite(margin)) return fail(FMX_ERR_ARG, "%s: margin = %g must be finite and >= 0", who, (double)margin);
-  if (mapped(table))
-    return fail(FMX_ERR_UNSUPPORTED, "%s: tables whose fields are pieces of index columns (field_cols / field_base) are not taken", who);
-  return FMX_OK;
-}
-
 // 2 * B_pairs as the sort and the update take it; beyond int32 it is clamped, which the sort's width check then refuses
 inline int32_t pair_rows(int32_t B_pairs) { return B_pairs > INT32_MAX / 2 ? INT32_MAX : 2 * B_pairs; }
 
@@ -274,39 +96,3 @@ int pair_stream_call(const fmx_table_t *table, const fmx_hyper_t *hyper, int32_t
   return pool_loop(table, idx_pool, nullptr, n_pool, B2, n_steps, w, fwd->error, st, forward, update);
 }
 
-int pair_online_call(const fmx_table_t *table, const fmx_hyper_t *hyper, int32_t rule, const int32_t *idx, const float *xv, int32_t N,
-                     float margin, uint8_t *pred_out, float *logit_out, float *loss_out, int32_t *error, hipStream_t st) {
-  const char *who = "fmx_fm_pair_online_run";
-  if (int rc = check_pair_args(table, hyper, idx, N, "N", margin, who)) return rc;
-  if (int rc = check_rule(table, rule)) return named(rc, who);
-  if (!pred_out) return fail(FMX_ERR_ARG, "%s: pred_out is null", who);
-  if (N > INT32_MAX / 2) return fail(FMX_ERR_ARG, "%s: N = %d: 2 * N rows exceed int32", who, N);
-  if (int rc = check_adam(hyper, rule, N)) return named(rc, who);
-  // two samples' rows in registers: 2 x 4 passes of RowRegs fit the wavefront's 512 registers, so the limit is fmx_fm_online_run's
-  const int lpr = lpr_of(table->kp), slots = WAVE / lpr;
-  const int np = (table->n_fields + slots - 1) / slots;
-  if (np > 4)
-    return fail(FMX_ERR_UNSUPPORTED, "%s: %d fields at kp = %d exceed the %d rows per sample one wavefront holds", who, table->n_fields,
-                table->kp, 4 * slots);
-  PairOnlineArgs a;
-  a.rows = table->rows;
-  a.foff = table->field_offsets;
-  a.bias = table->bias;
-  a.idx = idx;
-  a.xv = xv;
-  a.pred = pred_out;
-  a.logit = logit_out;
-  a.loss = loss_out;
-  a.error = error;
-  a.h = hyper_for(hyper, rule);  // ADAM: the kernel derives each pair's constants from lr, beta1, beta2, step
-  a.h.alpha = 1.0f / hyper->alpha;  // the kernels multiply by 1/alpha
-  a.N = N;
-  a.F = table->n_fields;
-  a.stride = table->row_stride;
-  a.zoff = table->z_offset;
-  a.margin = margin;
-  with_lpr(table->kp, [&](auto LPR) {
-    with_rule(rule, [&](auto LAYOUT, auto RULE) { launch_pair_online_np<LPR, LAYOUT, RULE>(a, np, st); });
-  });
-  return check_launch("k_fm_pair_online");
-}

@@ -353,7 +353,7 @@ __global__ __launch_bounds__(1024) void k_sort_occ(SortArgs a) {
 // read one chunk's [1024, F] slab of idx (each 128-byte line of it holds 32 of a sample's 39 indices and is read by
 // the workgroups of 32 fields) sit on ONE XCD, so the slab is fetched from HBM once instead of once per XCD; likewise
 // the C merge workgroups of a field read the same Bp words.  Placement is for speed only.
-constexpr int SORT_CHUNK = 1024, SORT_CHUNK_E = 4, SORT_CHUNK_THREADS = SORT_CHUNK / SORT_CHUNK_E;
+constexpr int SORT_CHUNK_E = 4, SORT_CHUNK_THREADS = SORT_CHUNK / SORT_CHUNK_E;  // (SORT_CHUNK: fmx_common.h)
 // from this width on the chunked form is the faster one for ONE batch per launch (MI355X, Criteo vocabulary: 4,096: 17.5 vs
 // 18.5 us; 8,192: 24 vs 36; 16,384: 60 vs 74; 32,768 x 6 fields: 58 us) -- launches of 8 batches: 29 vs 27, 71 vs 55, 294 vs 118
 constexpr int SORT_CHUNKED_MIN_WIDTH = 8192;

@@ -11,7 +11,7 @@
 //
 // fmx_mlp_topk (the DeepFM / NFM classes, at the end of this file) feeds the same slots from a scan that runs the whole
 // network on every pair.
-#include "fmx_common.h"
+#include "fmx_host.h"
 
 namespace {
 
@@ -779,7 +779,7 @@ int check_pair_ptrs(const char *fn, const float *Su, const float *au, const floa
 }
 int check_pair_layout(const char *fn, int bad_kp, const float *Su, int32_t ld_u, const float *Sc, int32_t ld_c, int32_t kp,
                       const void *ws) {
-  if (kp != 4 && kp != 8 && kp != 16 && kp != 32 && kp != 64) return fail(bad_kp, "%s: kp=%d must be 4/8/16/32/64", fn, kp);
+  if (!lpr_of(kp)) return fail(bad_kp, "%s: kp=%d must be 4/8/16/32/64", fn, kp);
   if (ld_u < kp || ld_c < kp || ld_u % 4 || ld_c % 4)
     return fail(FMX_ERR_SHAPE, "%s: ld_u=%d and ld_c=%d must be multiples of 4 and >= kp=%d", fn, ld_u, ld_c, kp);
   if (!aligned16(Su) || !aligned16(Sc) || !aligned16(ws))
@@ -832,14 +832,7 @@ int fmx_fm_topk(const float *Su, int32_t ld_u, const float *au, int32_t U, const
   const hipStream_t st = static_cast<hipStream_t>(stream);
   const dim3 grid(g.tiles, g.splits);
   const size_t lds = slots_lds(g.ut, g.cap);
-  int rc;
-  switch (kp) {
-    case 4: rc = launch_slots<k_topk_scan<4>>("k_topk_scan", grid, lds, st, a); break;
-    case 8: rc = launch_slots<k_topk_scan<8>>("k_topk_scan", grid, lds, st, a); break;
-    case 16: rc = launch_slots<k_topk_scan<16>>("k_topk_scan", grid, lds, st, a); break;
-    case 32: rc = launch_slots<k_topk_scan<32>>("k_topk_scan", grid, lds, st, a); break;
-    default: rc = launch_slots<k_topk_scan<64>>("k_topk_scan", grid, lds, st, a); break;
-  }
+  const int rc = with_kp(kp, [&](auto KP) { return launch_slots<k_topk_scan<KP>>("k_topk_scan", grid, lds, st, a); });
   return rc ? rc : merge_topk(a.parts, top_pos, top_score, U, K, g.splits, st);
 }
 
@@ -903,7 +896,7 @@ int check_afm_pair_args(const char *fn, const fmx_afm_t *afm, const float *Eu, c
                         const void *out_a, const void *out_b) {
   if (!afm->params || !Eu || !stats_u || !Ec || !stats_c || !workspace || !out_a || !out_b) return fail(FMX_ERR_ARG, "%s: null argument", fn);
   if ((excl_offsets == nullptr) != (excl_pos == nullptr)) return fail(FMX_ERR_ARG, "%s: excl_offsets and excl_pos go together", fn);
-  if ((kp != 4 && kp != 8 && kp != 16 && kp != 32 && kp != 64) || kp < afm->k)
+  if (!lpr_of(kp) || kp < afm->k)
     return fail(FMX_ERR_SHAPE, "%s: kp=%d must be 4/8/16/32/64 and >= k=%d", fn, kp, afm->k);
   if (!aligned16(Eu) || !aligned16(stats_u) || !aligned16(Ec) || !aligned16(stats_c) || !aligned16(workspace))
     return fail(FMX_ERR_ALIGN, "%s: Eu, stats_u, Ec, stats_c and the workspace must be 16-byte aligned", fn);
@@ -965,14 +958,7 @@ int fmx_afm_topk(const fmx_afm_t *afm, const float *Eu, const float *stats_u, in
   if (int rc = check_launch("k_afm_topk_pack")) return rc;
   const dim3 grid(U, splits);
   const size_t lds = slots_lds(1, a.cap);
-  int rc;
-  switch (kp) {
-    case 4: rc = launch_slots<k_afm_topk_scan<4>>("k_afm_topk_scan", grid, lds, st, a); break;
-    case 8: rc = launch_slots<k_afm_topk_scan<8>>("k_afm_topk_scan", grid, lds, st, a); break;
-    case 16: rc = launch_slots<k_afm_topk_scan<16>>("k_afm_topk_scan", grid, lds, st, a); break;
-    case 32: rc = launch_slots<k_afm_topk_scan<32>>("k_afm_topk_scan", grid, lds, st, a); break;
-    default: rc = launch_slots<k_afm_topk_scan<64>>("k_afm_topk_scan", grid, lds, st, a); break;
-  }
+  const int rc = with_kp(kp, [&](auto KP) { return launch_slots<k_afm_topk_scan<KP>>("k_afm_topk_scan", grid, lds, st, a); });
   return rc ? rc : merge_topk(a.parts, top_pos, top_score, U, K, splits, st);
 }
 

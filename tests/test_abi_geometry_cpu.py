@@ -228,6 +228,41 @@ def test_check_table_refuses_with_the_documented_code():
         assert nbytes > 0 and rc == L.ERR_ARG and "null argument" in msg, (layout, rc, msg)
 
 
+def _afm_verdict(t):
+    """fmx_afm_forward on a fake table of two fields: its table check is the shared one (behind the entry point's name), and a
+    null `idx` is refused right after it -- an accepted table answers ERR_ARG ("null argument"), a refused one its own code."""
+    import fmx
+    L = fmx._lib
+    lib = L.load()
+    afm = L.Afm(0x40000, t.k, 4)
+    rc = lib.fmx_afm_forward(C.byref(t), C.byref(afm), fmx.Hyper().ref(), None, None, None, 64, L.LOSS_NONE, 1.0, None, None, None, None)
+    return rc, lib.fmx_last_error_string().decode()
+
+
+# the FTRL and MOMENTS rows the attentional FM's own table check used to let through (it asked for row_stride >= kp + 4 and
+# never looked at z_offset): (geometry, the shared check's message)
+AFM_NEWLY_REFUSED = [(("ftrl", 16, 16, 16, 64), "z_offset=16 must be a multiple of 4 and >= kp + 4 = 20"),
+                     (("ftrl", 16, 16, 20, 48), "row_stride=48 must be a multiple of 4 and >= 52"),
+                     (("moments", 16, 16, 16, 64), "z_offset=16 must be a multiple of 4 and >= kp + 4 = 20"),
+                     (("moments", 16, 16, 20, 48), "row_stride=48 must be a multiple of 4 and >= 52"),
+                     (("ftrl", 61, 64, 64, 256), "z_offset=64 must be a multiple of 4 and >= kp + 4 = 68"),
+                     (("moments", 61, 64, 68, 192), "row_stride=192 must be a multiple of 4 and >= 196")]
+
+
+@pytest.mark.parametrize("geom,message", AFM_NEWLY_REFUSED, ids=["-".join(str(v) for v in g) for g, _ in AFM_NEWLY_REFUSED])
+def test_afm_refuses_ftrl_and_moments_rows_that_do_not_hold_both_halves(geom, message):
+    import fmx
+    rc, msg = _afm_verdict(_fake(*geom))
+    assert rc == fmx._lib.ERR_SHAPE and msg == "fmx_afm_forward: " + message, (rc, msg)
+
+
+@pytest.mark.parametrize("geom", ACCEPTED, ids=lambda g: "-".join(str(v) for v in g))
+def test_afm_accepts_the_minimum_geometries(geom):
+    import fmx
+    rc, msg = _afm_verdict(_fake(*geom))
+    assert rc == fmx._lib.ERR_ARG and msg == "fmx_afm_forward: null argument", (rc, msg)     # past the table check, stopped by the null `idx`
+
+
 def test_flat_table_row_stride_takes_what_the_c_side_takes():
     import fmx
     lib = fmx._lib.load()

@@ -1,23 +1,20 @@
 #!/usr/bin/env python3
-"""Print VGPR / SGPR / scratch / occupancy / LDS per kernel from hipcc's kernel-resource-usage remarks.
-Usage: python tools/kernel_resources.py [substring filter]"""
+"""Print VGPR / SGPR / scratch / occupancy / LDS per kernel from the device listings of `make asm` (the numbers the compiler
+prints behind each function).  Usage: python tools/kernel_resources.py [substring filter]"""
+import glob
+import os
 import re
 import subprocess
 import sys
 
-out = subprocess.run(["make", "-C", "fm-for-online-recommendation_amd/csrc", "asm"], capture_output=True, text=True)
-cur, rows = None, {}
-for line in (out.stdout + out.stderr).splitlines():
-    m = re.search(r"remark:\s+Function Name: (\S+)", line)
-    if m:
-        cur = re.sub(r"_ZN12_GLOBAL__N_1\d+", "", m.group(1))
-        rows[cur] = {}
-        continue
-    m = re.search(r"remark:\s+([\w \[\]/]+?):\s+(\S+)\s+\[-Rpass", line)
-    if m and cur:
-        rows[cur][m.group(1).strip()] = m.group(2)
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from isa_diff import read_listing
+
+subprocess.run(["make", "-s", "-C", "fm-for-online-recommendation_amd/csrc", "asm"], check=True, capture_output=True)
 flt = sys.argv[1] if len(sys.argv) > 1 else ""
-for k, v in rows.items():
-    if flt in k:
-        print(f"{k[:48]:48s} VGPR={v.get('VGPRs'):>4} SGPR={v.get('TotalSGPRs'):>4} scratch={v.get('ScratchSize [bytes/lane]'):>3} "
-              f"occ={v.get('Occupancy [waves/SIMD]')} LDS={v.get('LDS Size [bytes/block]')}")
+for path in sorted(glob.glob("fm-for-online-recommendation_amd/csrc/build/asm/fmx_*.s")):
+    for name, f in read_listing(path).items():
+        k, v = re.sub(r"_ZN12_GLOBAL__N_1\d+", "", name), f["numbers"]
+        if f["desc"] is not None and flt in k:
+            print(f"{k[:48]:48s} VGPR={v.get('NumVgprs'):>4} SGPR={v.get('TotalNumSgprs'):>4} scratch={v.get('ScratchSize'):>3} "
+                  f"occ={v.get('Occupancy')} LDS={v.get('LDSByteSize')}")

@@ -10,7 +10,14 @@
   online    fmx_fm_pair_online_run (pairs/s) against a ctypes loop of fmx_fm_pair_step(B_pairs = 1) in the same process, under
             signadam and adam, with fmx_fm_online_run's samples/s alongside for scale.
 Each part runs in a child process of its own under a time limit; the first that fails ends the run.  Writes profiles/pair_times.json.
-  python tools/pair_times.py [--steps N] [--reps R] [--pairs N] [--loop-pairs M] [--out FILE]"""
+  python tools/pair_times.py [--steps N] [--reps R] [--pairs N] [--loop-pairs M] [--out FILE]
+
+  --ab-lib PATH   instead of the above: the stream walkers' instantiations one by one (k_fm_pair_online at every kp, under signadam
+            and sgd, at 2, 3 and 4 fields per lane group; k_fm_online at kp = 4; two more as controls), this tree's library against
+            another build of the same ABI at PATH, for a change that moved their instruction streams.  Fresh child processes
+            alternate PATH, this tree, PATH, ... (--ab-rounds each); every child times every instantiation (median of --reps calls
+            after a warm call) and sums the table it leaves.  Writes --out (give one): per instantiation both sides' us per item,
+            the spread of PATH's processes (max - min), the difference, and whether the tables' sums agree."""
 import argparse
 import ctypes as C
 import json
@@ -149,6 +156,95 @@ def child_online(args):
     print("RESULT " + json.dumps(res), flush=True)
 
 
+def walker_grid():
+    """(name as the kernel is instantiated, kind, kp, rule, fields): LAYOUT 0 = weights, 2 = moments; RULE 0 = signadam, 1 = sgd, 4 = adam"""
+    rule_id = {"signadam": 0, "sgd": 1, "adam": 4}
+    grid = []
+    for kp in (4, 8, 16, 32, 64):
+        lpr, slots = kp // 4, 64 // (kp // 4)
+        for rule in ("signadam", "sgd"):
+            for np_ in (2, 3, 4):
+                grid.append((f"k_fm_pair_online<{lpr}, 0, {rule_id[rule]}, {np_}>", "pair", kp, rule, np_ * slots))
+    grid += [(f"k_fm_online<1, 0, {rule_id[r]}, 1>", "fm", 4, r, 39) for r in ("signadam", "sgd")]
+    grid += [("control k_fm_online<4, 0, 0, 3>", "fm", 16, "signadam", 39), ("control k_fm_pair_online<4, 2, 4, 3>", "pair", 16, "adam", 39)]
+    return grid
+
+
+def child_walkers(args):
+    import numpy as np
+    import torch
+    import fmx
+    torch.cuda.set_device(0)
+    n = args.pairs
+    res = {}
+    for name, kind, kp, rule, F in walker_grid():
+        sizes = [2000] * F
+        t = fmx.FlatTable(sizes, kp, layout=LAYOUT[rule] if rule in LAYOUT else "weights")
+        g = torch.Generator(device="cuda").manual_seed(SEED)
+        t.rows[:, :kp] = torch.randn((t.n_rows, kp), generator=g, device="cuda") * 0.01
+        e = fmx.FMEngine(t, max_batch=64)
+        h = fmx.Hyper(**HYPER)
+        if kind == "pair":
+            rows = torch.from_numpy(pair_pool(np, sizes, 1, n, SEED + 2)[0]).cuda()
+            fn = lambda: e.pair_online_run(h, rule, rows, None, margin=0.0)
+        else:
+            rng = np.random.default_rng(SEED + 3)
+            rows = torch.from_numpy(np.stack([rng.integers(0, s, size=n) for s in sizes], axis=1).astype(np.int32)).cuda()
+            y = torch.from_numpy((rng.uniform(size=n) < 0.3).astype(np.float32)).cuda()
+            fn = lambda: e.online_run(h, rule, "logits", rows, None, y)
+        timed(torch, fn)                                         # warm
+        secs = [timed(torch, fn) for _ in range(args.reps)]
+        e.check_error_flag()
+        res[name] = dict(us_per_item=round(median(secs) / n * 1e6, 4), table_sum=float(t.rows.double().sum().item()),
+                         finite=bool(torch.isfinite(t.rows).all()))
+        del e, t, rows
+    print("RESULT " + json.dumps(res), flush=True)
+
+
+def main_ab(args):
+    libs = (("other", os.path.abspath(args.ab_lib)), ("this", ""))
+    runs = {"other": [], "this": []}
+    for r in range(args.ab_rounds):
+        for side, lib in libs:
+            cmd = [sys.executable, os.path.abspath(__file__), "--child", "walkers", "--reps", str(args.reps), "--pairs", str(args.pairs)]
+            try:
+                p = subprocess.run(cmd, env=dict(os.environ, FMX_LIB_PATH=lib), capture_output=True, text=True, timeout=args.timeout)
+            except subprocess.TimeoutExpired:
+                print(f"{side}, round {r}: no result within {args.timeout} s; stopping", flush=True)
+                return 1
+            line = [ln for ln in p.stdout.splitlines() if ln.startswith("RESULT ")]
+            if p.returncode != 0 or not line:
+                print(f"{side}, round {r}: exit status {p.returncode}; stopping\n{p.stdout[-2000:]}\n{p.stderr[-2000:]}", flush=True)
+                return 1
+            runs[side].append(json.loads(line[-1][len("RESULT "):]))
+            print(side, r, "done", flush=True)
+    table, slower = {}, []
+    for name, kind, kp, rule, F in walker_grid():
+        a = [x[name]["us_per_item"] for x in runs["other"]]
+        b = [x[name]["us_per_item"] for x in runs["this"]]
+        spread, diff = max(a) - min(a), median(b) - median(a)
+        sums = {x[name]["table_sum"] for x in runs["other"] + runs["this"]}
+        row = dict(kp=kp, rule=rule, fields=F, other_us_per_item=a, this_us_per_item=b, other_median=median(a), this_median=median(b),
+                   other_spread=round(spread, 4), this_minus_other=round(diff, 4), percent=round(100 * diff / median(a), 2),
+                   not_slower_than_twice_other_spread=bool(diff <= 2 * spread), faster_by_more_than_twice_other_spread=bool(-diff > 2 * spread),
+                   same_table_sum=len(sums) == 1, finite=all(x[name]["finite"] for x in runs["other"] + runs["this"]))
+        if not (row["not_slower_than_twice_other_spread"] and row["same_table_sum"] and row["finite"]):
+            slower.append(name)
+        table[name] = row
+        print(name, json.dumps(row), flush=True)
+    with open(args.out, "w") as fh:
+        json.dump(dict(what="us per item (pair or sample) of fmx_fm_pair_online_run / fmx_fm_online_run per kernel instantiation: this tree's "
+                            "library (this) against another build of the same ABI (other), fresh processes alternating other, this; each "
+                            "figure the median of reps calls of `items` items after a warm call; spread = max - min over other's processes",
+                       items=args.pairs, reps=args.reps, rounds=args.ab_rounds, rows_per_field=2000, instantiations=table,
+                       slower_or_different=slower), fh, indent=1)
+        fh.write("\n")
+    if slower:
+        print(f"slower than twice the other build's spread, or other results: {slower}", flush=True)
+        return 1
+    return 0
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch-pairs", type=int, default=2048)
@@ -158,10 +254,14 @@ def main():
     ap.add_argument("--loop-pairs", type=int, default=2000, help="pairs per call of the fmx_fm_pair_step loop")
     ap.add_argument("--timeout", type=int, default=200, help="seconds per child")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "pair_times.json"))
+    ap.add_argument("--ab-lib", default=None, help="time the walkers' instantiations against this build of the same ABI (see above)")
+    ap.add_argument("--ab-rounds", type=int, default=3)
     ap.add_argument("--child", default=None)
     args = ap.parse_args()
     if args.child:
-        return {"batched": child_batched, "online": child_online}[args.child](args)
+        return {"batched": child_batched, "online": child_online, "walkers": child_walkers}[args.child](args)
+    if args.ab_lib:
+        return main_ab(args)
     out = dict(what="the pair loss next to the pointwise one on the Criteo-39 table (1 M x 16): us/step of the batched streams, "
                     "pairs/s of the online loop; medians of reps calls after one warm call")
     for part in ("batched", "online"):

@@ -1,13 +1,24 @@
 #!/bin/bash
-# Diagnostic build of the FM unit with in-kernel stamps (-DFMX_STAMPS) into tools/micro/libfmx_stamps.so, and the report.  Run the BUILD
+# Diagnostic build of the FM units with in-kernel stamps (-DFMX_STAMPS) into tools/micro/libfmx_stamps.so, and the report.  Run the BUILD
 # here (hipcc cross-compiles), the report on the GPU box:  bash tools/update_stamps.sh build ;  gpurun -- bash tools/update_stamps.sh run
 set -e
 root=$(cd "$(dirname "$0")/.." && pwd)
 csrc=$root/fm-for-online-recommendation_amd/csrc
 if [ "$1" = "build" ]; then
   make -s -j4 -C $csrc
-  /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -I$root/include -I/opt/rocm/include -DFMX_STAMPS -c -o /tmp/fmx_kernels_stamps.o $csrc/fmx_kernels.hip
-  /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o $root/tools/micro/libfmx_stamps.so /tmp/fmx_kernels_stamps.o $csrc/build/fmx_mlp.o $csrc/build/fmx_sftrl.o $csrc/build/fmx_comm.o $csrc/build/fmx_topk.o $csrc/build/fmx_afm.o -ldl
+  objs="" pids=""
+  for u in $(cd $csrc && ls fmx_*.hip | sed 's/\.hip$//'); do   # every unit that holds FMX_STAMPS code with the define, the others as built
+    if grep -q FMX_STAMPS $csrc/$u.hip; then
+      rm -f /tmp/${u}_stamps.o
+      /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -I$root/include -I/opt/rocm/include -DFMX_STAMPS -c -o /tmp/${u}_stamps.o $csrc/$u.hip &
+      pids="$pids $!"
+      objs="$objs /tmp/${u}_stamps.o"
+    else
+      objs="$objs $csrc/build/$u.o"
+    fi
+  done
+  for p in $pids; do wait $p; done   # (set -e: a failed compile ends the build here)
+  /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o $root/tools/micro/libfmx_stamps.so $objs -ldl
 else
   FMX_LIB_PATH=$root/tools/micro/libfmx_stamps.so python3 $root/tools/update_stamps.py
 fi
