@@ -22,6 +22,9 @@
 //                         the waves, the table update and the attention rule in the same launch; the bits of B = 1 steps (its own
 //                         comment further down).
 //
+//   k_afm_pair<KP, FTRL, BWD>  (fmx_afm_pair.inc) pairwise-ranking training: a workgroup walks PAIRS of rows (positive, negative) and
+//                         runs k_afm's row forward and backward under the pair loss of the two logits (fmx_afm_pair_*).
+//
 // No float is accumulated with atomics and every sum has one fixed order that depends on (B, F, t, k) alone: results are
 // bit-identical run to run.  The table update between the two launches is fmx_fm_update_occ (fmx_kernels.hip).
 
@@ -979,12 +982,10 @@ AfmWs carve_afm(const fmx_table_t *table, const fmx_afm_t *afm, int B, void *bas
   return w;
 }
 
-// fmx_afm_step's own checks; w receives the carved workspace
-int check_afm_step(const fmx_table_t *table, const fmx_hyper_t *hyper, int32_t rule, const fmx_afm_t *afm, const int32_t *idx, const float *y,
-                   int32_t B, void *workspace, int64_t workspace_bytes, const float *attn_grad_out, AfmWs &w, const char *who) {
-  if (int rc = check_afm(table, afm, who)) return rc;
-  if (!hyper || !idx || !y || !workspace || !attn_grad_out) return fail(FMX_ERR_ARG, "%s: null argument", who);
-  if (B < 1) return fail(FMX_ERR_ARG, "%s: B must be >= 1", who);
+// the rule and the caller's workspace for a step of B rows (fmx_afm_step; the pair steps with B = 2 B_pairs); w receives the
+// carved workspace
+int check_afm_ws(const fmx_table_t *table, int32_t rule, const fmx_afm_t *afm, int32_t B, void *workspace, int64_t workspace_bytes, AfmWs &w,
+                 const char *who) {
   if (int rc = named(check_rule(table, rule), who)) return rc;
   if (!aligned16(workspace)) return fail(FMX_ERR_ALIGN, "%s: workspace must be 16-byte aligned", who);
   w = carve_afm(table, afm, B, workspace);
@@ -993,6 +994,15 @@ int check_afm_step(const fmx_table_t *table, const fmx_hyper_t *hyper, int32_t r
     return fail(FMX_ERR_SHAPE, "%s: workspace of %lld bytes, %lld needed (fmx_afm_workspace_bytes)", who, (long long)workspace_bytes,
                 (long long)w.bytes);
   return FMX_OK;
+}
+
+// fmx_afm_step's own checks
+int check_afm_step(const fmx_table_t *table, const fmx_hyper_t *hyper, int32_t rule, const fmx_afm_t *afm, const int32_t *idx, const float *y,
+                   int32_t B, void *workspace, int64_t workspace_bytes, const float *attn_grad_out, AfmWs &w, const char *who) {
+  if (int rc = check_afm(table, afm, who)) return rc;
+  if (!hyper || !idx || !y || !workspace || !attn_grad_out) return fail(FMX_ERR_ARG, "%s: null argument", who);
+  if (B < 1) return fail(FMX_ERR_ARG, "%s: B must be >= 1", who);
+  return check_afm_ws(table, rule, afm, B, workspace, workspace_bytes, w, who);
 }
 
 // the attention parameters' optimizer state for a call of n_steps steps (fmx_mlp_opt_t with FMX_RULE_SIGNADAM accepted), and
@@ -1029,25 +1039,33 @@ AfmOptArgs afm_opt_args(const fmx_afm_t *afm, const fmx_mlp_opt_t &o, int32_t t)
   return a;
 }
 
+// k_afm_pair (fmx_afm_pair.inc) over the a.B PAIRS of the 2 a.B rows of a.idx
+template <bool BWD>
+int launch_afm_pair(const AfmArgs &a, float margin, int kp, bool ftrl, hipStream_t st);
+
 // One step on `st`: sort -> forward + backward -> table update (its last workgroups reduce the bias gradient and the loss) ->
 // attention gradient, with the attention parameters' rule for their step opt_t when opt is given.  The arguments have been checked.
+// pair_margin >= 0: the pair mode (fmx_afm_pair_*) -- the B rows are B / 2 pairs, row 2 i the positive and row 2 i + 1 the negative,
+// forward + backward is k_afm_pair under that margin (one workgroup per pair: B / 2 partials at most); y is not read.
 int afm_step_launches(const fmx_table_t *table, const fmx_hyper_t *hyper, int32_t rule, const fmx_afm_t *afm, const int32_t *idx,
                       const float *xv, const float *y, int32_t B, float inv_b, void *workspace, const AfmWs &w, float *attn_grad_out,
                       float *loss_out, int32_t *error, const fmx_mlp_opt_t *opt, int32_t opt_t, hipStream_t st,
-                      float *logit_out = nullptr) {
+                      float *logit_out = nullptr, float pair_margin = -1.f) {
+  const bool pair = pair_margin >= 0.f;
   if (int rc = fmx_sort_occurrences(table, idx, B, workspace, w.table_bytes, error, st)) return rc;
-  AfmArgs a = fill_afm(table, afm, hyper, idx, xv, y, B, FMX_LOSS_BCE_LOGITS, inv_b, error);
-  a.logit = logit_out;  // [B] or null (fmx_afm_online_run's per-sample launches)
+  AfmArgs a = fill_afm(table, afm, hyper, idx, xv, y, pair ? B / 2 : B, FMX_LOSS_BCE_LOGITS, inv_b, error);
+  a.logit = logit_out;  // [B] or null (the online runs' per-sample launches)
   a.dz = w.dz;
   a.loss = w.loss;
   a.E = w.E;
   a.part = w.part;
-  if (int rc = launch_afm<true>(a, table->kp, table->layout == FMX_LAYOUT_FTRL, st)) return rc;
+  const bool ftrl = table->layout == FMX_LAYOUT_FTRL;
+  if (int rc = pair ? launch_afm_pair<true>(a, pair_margin, table->kp, ftrl, st) : launch_afm<true>(a, table->kp, ftrl, st)) return rc;
   if (int rc = fmx_fm_update_occ(table, hyper, rule, workspace, w.table_bytes, xv, w.dz, w.E, table->n_fields * table->kp, B, w.loss,
                                  inv_b, loss_out, st))
     return rc;
   const dim3 grid((a.G + 63) / 64), block(256);
-  const int n = afm_grid(B);
+  const int n = afm_grid(a.B);
   if (!opt) {
     hipLaunchKernelGGL(k_afm_reduce, grid, block, 0, st, w.part, n, a.G, attn_grad_out);
     return check_launch("k_afm_reduce");
@@ -1071,6 +1089,8 @@ int launch_afm_online_k(const AfmOnlArgs &a, hipStream_t st) {
   hipLaunchKernelGGL((k_afm_online<KP>), dim3(1), dim3(AFM_ONL_THREADS), lds, st, a);
   return check_launch("k_afm_online");
 }
+
+#include "fmx_afm_pair.inc"
 
 }  // namespace
 
@@ -1239,6 +1259,46 @@ int fmx_afm_side(const fmx_table_t *table, const fmx_afm_t *afm, const fmx_hyper
   const hipStream_t st = static_cast<hipStream_t>(stream);
   const bool ftrl = table->layout == FMX_LAYOUT_FTRL;
   return with_kp(table->kp, [&](auto KP) { return ftrl ? launch_afm_side_k<KP, true>(a, st) : launch_afm_side_k<KP, false>(a, st); });
+}
+
+// ---- pairwise-ranking (BPR) training: fmx_afm_pair.inc ----
+int fmx_afm_pair_forward(const fmx_table_t *table, const fmx_afm_t *afm, const fmx_hyper_t *hyper, const int32_t *idx, const float *xv,
+                         int32_t B_pairs, float margin, float inv_b, float *logit_out, float *loss_out, float *dz_out, int32_t *error,
+                         fmx_stream_t stream) {
+  return afm_pair_forward_call(table, afm, hyper, idx, xv, B_pairs, margin, inv_b, logit_out, loss_out, dz_out, error,
+                               static_cast<hipStream_t>(stream));
+}
+
+int fmx_afm_pair_step(const fmx_table_t *table, const fmx_hyper_t *hyper, int32_t rule, const fmx_afm_t *afm, const int32_t *idx,
+                      const float *xv, int32_t B_pairs, float margin, float inv_b, void *workspace, int64_t workspace_bytes,
+                      float *attn_grad_out, float *logit_out, float *loss_out, int32_t *error, fmx_stream_t stream) {
+  return afm_pair_steps_call("fmx_afm_pair_step", table, hyper, rule, afm, idx, xv, 1, B_pairs, margin, inv_b, 1, workspace,
+                             workspace_bytes, attn_grad_out, nullptr, false, logit_out, loss_out, error, static_cast<hipStream_t>(stream));
+}
+
+int fmx_afm_pair_step_opt(const fmx_table_t *table, const fmx_hyper_t *hyper, int32_t rule, const fmx_afm_t *afm, const int32_t *idx,
+                          const float *xv, int32_t B_pairs, float margin, float inv_b, void *workspace, int64_t workspace_bytes,
+                          float *attn_grad_out, const fmx_mlp_opt_t *opt, float *logit_out, float *loss_out, int32_t *error,
+                          fmx_stream_t stream) {
+  return afm_pair_steps_call("fmx_afm_pair_step_opt", table, hyper, rule, afm, idx, xv, 1, B_pairs, margin, inv_b, 1, workspace,
+                             workspace_bytes, attn_grad_out, opt, true, logit_out, loss_out, error, static_cast<hipStream_t>(stream));
+}
+
+int fmx_afm_pair_stream(const fmx_table_t *table, const fmx_hyper_t *hyper, int32_t rule, const fmx_afm_t *afm, const int32_t *idx_pool,
+                        const float *xv_pool, int32_t n_pool, int32_t B_pairs, float margin, float inv_b, int32_t n_steps,
+                        void *workspace, int64_t workspace_bytes, float *attn_grad_out, const fmx_mlp_opt_t *opt, float *loss_out,
+                        int32_t *error, fmx_stream_t stream) {
+  return afm_pair_steps_call("fmx_afm_pair_stream", table, hyper, rule, afm, idx_pool, xv_pool, n_pool, B_pairs, margin, inv_b, n_steps,
+                             workspace, workspace_bytes, attn_grad_out, opt, true, nullptr, loss_out, error,
+                             static_cast<hipStream_t>(stream));
+}
+
+int fmx_afm_pair_online_run(const fmx_table_t *table, const fmx_hyper_t *hyper, int32_t rule, const fmx_afm_t *afm, const int32_t *idx,
+                            const float *xv, int32_t N_pairs, float margin, void *workspace, int64_t workspace_bytes,
+                            float *attn_grad_out, const fmx_mlp_opt_t *opt, float *logit_out, float *loss_out, int32_t *error,
+                            fmx_stream_t stream) {
+  return afm_pair_online_call(table, hyper, rule, afm, idx, xv, N_pairs, margin, workspace, workspace_bytes, attn_grad_out, opt,
+                              logit_out, loss_out, error, static_cast<hipStream_t>(stream));
 }
 
 }  // extern "C"

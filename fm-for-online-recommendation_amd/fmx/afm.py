@@ -1,5 +1,5 @@
 """AFMEngine: workspace + launch sequencing of the attentional FM (fmx_afm_forward / fmx_afm_step / fmx_afm_step_opt /
-fmx_afm_stream / fmx_afm_online_run) for one FlatTable.
+fmx_afm_stream / fmx_afm_online_run, and their pairwise-ranking forms fmx_afm_pair_*) for one FlatTable.
 
 The attention parameters live in ONE flat fp32 device buffer [ W (t x k) | b (t) | h (t) | p (k) ] (include/fmx.h, fmx_afm_t);
 the step returns their gradient in the same layout and leaves updating them to the caller -- or, given an AfmOpt, applies their
@@ -134,6 +134,83 @@ class AFMEngine:
                                                idx_d.data_ptr(), _ptr(xv_d), y_d.data_ptr(), N, self.workspace.data_ptr(),
                                                self.workspace.numel() * 4, self.grad.data_ptr(), opt.ref(), _ptr(logits),
                                                _ptr(losses), self.error.data_ptr(), self._stream(stream)))
+        opt.step += N
+        if self.table.layout == "moments":
+            self.table.step += N
+
+    # ---- pairwise-ranking (BPR) training: rows [2P, F] from fmx.pairwise.assemble_pairs, row 2p the positive, 2p + 1 the negative ----
+    def _pair_rows(self, idx_d, xv_d):
+        assert idx_d.dtype == torch.int32 and idx_d.is_contiguous() and idx_d.dim() == 2 and idx_d.shape[0] % 2 == 0
+        assert idx_d.shape[1] == self.table.n_fields
+        assert xv_d is None or (xv_d.dtype == torch.float32 and xv_d.is_contiguous() and xv_d.shape == idx_d.shape)
+        return idx_d.shape[0] // 2
+
+    def pair_forward(self, hyper, idx_d, xv_d=None, margin=0.0, inv_b=None, dz=None, stream=None):
+        """-> P; the 2P logits in self.logit[:2P] (the bits of forward()), the pair losses in self.loss_b[0:2P:2] (the odd slots
+        +0).  dz: an fp32 device tensor of 2P elements for dlogit (inv_b folded in, default 1 / P), or None."""
+        P = self._pair_rows(idx_d, xv_d)
+        assert dz is None or (dz.dtype == torch.float32 and dz.is_contiguous() and dz.numel() >= 2 * P)
+        self._ensure(2 * P)
+        _lib.check(self.lib.fmx_afm_pair_forward(self.table.c_struct(), C.byref(self.c_afm), hyper.ref(), idx_d.data_ptr(), _ptr(xv_d),
+                                                 P, margin, 1.0 / P if inv_b is None else inv_b, self.logit.data_ptr(),
+                                                 self.loss_b.data_ptr(), _ptr(dz), self.error.data_ptr(), self._stream(stream)))
+        return P
+
+    def pair_step(self, hyper, rule, idx_d, xv_d=None, margin=0.0, inv_b=None, stream=None, opt=None):
+        """One mini-batch pair step: the table updated under `rule`, the mean pair loss in self.loss_out[0], the attention
+        gradient in self.grad, the 2P logits before the update in self.logit[:2P] (no sync here).  opt (an AfmOpt): the
+        attention parameters take its rule in the same call (fmx_afm_pair_step_opt) and its step count advances."""
+        P = self._pair_rows(idx_d, xv_d)
+        self._ensure(2 * P)
+        if self.table.layout == "moments":
+            hyper.c.step = self.table.step
+        head = (self.table.c_struct(), hyper.ref(), _lib.RULES[rule], C.byref(self.c_afm), idx_d.data_ptr(), _ptr(xv_d), P, margin,
+                1.0 / P if inv_b is None else inv_b, self.workspace.data_ptr(), self.workspace.numel() * 4, self.grad.data_ptr())
+        tail = (self.logit.data_ptr(), self.loss_out.data_ptr(), self.error.data_ptr(), self._stream(stream))
+        if opt is None:
+            _lib.check(self.lib.fmx_afm_pair_step(*head, *tail))
+        else:
+            _lib.check(self.lib.fmx_afm_pair_step_opt(*head, opt.ref(), *tail))
+            opt.step += 1
+        if self.table.layout == "moments":
+            self.table.step += 1
+
+    def pair_stream(self, hyper, rule, idx_pool, xv_pool, P, n_steps, opt, margin=0.0, inv_b=None, losses=None, stream=None):
+        """n_steps pair steps over a device-resident pool in one call (fmx_afm_pair_stream; no sync here): idx_pool
+        [n_pool, 2P, F] int32, xv_pool the same shape in fp32 or None (ones); step s takes batch s mod n_pool.  losses: an fp32
+        device tensor of n_steps elements, or None.  The table's step count and opt's advance by n_steps."""
+        P, n_steps = int(P), int(n_steps)
+        n_pool = idx_pool.numel() // (2 * P * self.table.n_fields)
+        assert idx_pool.dtype == torch.int32 and idx_pool.is_contiguous() and n_pool >= 1
+        assert xv_pool is None or (xv_pool.dtype == torch.float32 and xv_pool.is_contiguous() and xv_pool.numel() == idx_pool.numel())
+        assert losses is None or (losses.dtype == torch.float32 and losses.numel() >= n_steps)
+        self._ensure(2 * P)
+        if self.table.layout == "moments":
+            hyper.c.step = self.table.step
+        _lib.check(self.lib.fmx_afm_pair_stream(self.table.c_struct(), hyper.ref(), _lib.RULES[rule], C.byref(self.c_afm),
+                                                idx_pool.data_ptr(), _ptr(xv_pool), n_pool, P, margin,
+                                                1.0 / P if inv_b is None else inv_b, n_steps, self.workspace.data_ptr(),
+                                                self.workspace.numel() * 4, self.grad.data_ptr(), opt.ref(), _ptr(losses),
+                                                self.error.data_ptr(), self._stream(stream)))
+        opt.step += n_steps
+        if self.table.layout == "moments":
+            self.table.step += n_steps
+
+    def pair_online_run(self, hyper, rule, idx_d, xv_d, opt, margin=0.0, logits=None, losses=None, stream=None):
+        """The online protocol for pairs in one call (fmx_afm_pair_online_run; no sync here): every pair of idx_d [2N, F] is
+        predicted, then fitted on alone -- N steps of pair_step(P = 1, inv_b = 1).  logits: an fp32 device tensor of 2N elements
+        for each pair's two logits BEFORE its update; losses: N elements; or None.  The table's step count and opt's advance
+        by N."""
+        N = self._pair_rows(idx_d, xv_d)
+        assert logits is None or (logits.dtype == torch.float32 and logits.is_contiguous() and logits.numel() >= 2 * N)
+        assert losses is None or (losses.dtype == torch.float32 and losses.is_contiguous() and losses.numel() >= N)
+        self._ensure(2)
+        if self.table.layout == "moments":
+            hyper.c.step = self.table.step
+        _lib.check(self.lib.fmx_afm_pair_online_run(self.table.c_struct(), hyper.ref(), _lib.RULES[rule], C.byref(self.c_afm),
+                                                    idx_d.data_ptr(), _ptr(xv_d), N, margin, self.workspace.data_ptr(),
+                                                    self.workspace.numel() * 4, self.grad.data_ptr(), opt.ref(), _ptr(logits),
+                                                    _ptr(losses), self.error.data_ptr(), self._stream(stream)))
         opt.step += N
         if self.table.layout == "moments":
             self.table.step += N

@@ -1,4 +1,5 @@
-"""AFMAdam: the attentional factorization machine (Xiao et al. 2017) on the gfx950 kernels (fmx_afm_forward / fmx_afm_step).
+"""AFMAdam: the attentional factorization machine (Xiao et al. 2017) on the gfx950 kernels (fmx_afm_forward / fmx_afm_step;
+pairwise-ranking training on the same logit: fmx_afm_pair_*, fit_pairs / run_pair_experiment with attention=True).
 
 The model (include/fmx.h, DESIGN.md section 3 "AFM"): per sample, with e_f = x_f V[row_f] and w_f the first-order weight, over
 the P = F (F - 1) / 2 pairs in the order i = 0..F-2, j = i+1..F-1,
@@ -224,13 +225,62 @@ class AFMAdam(nn.Module):
         self._after_step()
         return out
 
-    def fit_pairs(self, Xi, Xv, item_fields, negatives=None, n_neg=1, margin=0.0, candidates=None, generator=None):
-        raise NotImplementedError(f"{self._name}.fit_pairs: the pair loss is built for the pure FM logit (FMAdam); the "
-                                  "attentional FM would need the pair epilogue inside the AFM step")
+    # ---- pairwise-ranking (BPR) training on the attentional logit (fmx_afm_pair_*; the pair objective of the other classes) ----
+    _pair_rows = OnlineFMBase._pair_rows
+    _pair_experiment_result = OnlineFMBase._pair_experiment_result
 
-    def run_pair_experiment(self, Xi, Xv, item_fields, negatives=None, n_neg=1, margin=0.0, candidates=None, generator=None):
-        raise NotImplementedError(f"{self._name}.run_pair_experiment: the pair loss is built for the pure FM logit (FMAdam); the "
-                                  "attentional FM would need the pair epilogue inside the AFM step")
+    def _pair_refusal(self, method, attention):
+        """The default keeps the other classes' reading of these two methods -- the pair loss of the pure FM logit, which this
+        model does not have; attention=True trains on the logit forward() gives."""
+        if not attention:
+            raise NotImplementedError(f"{self._name}.{method}: the pair loss is built for the pure FM logit (FMAdam); "
+                                      f"{method}(..., attention=True) trains on the pair loss of the attentional FM's logit")
+
+    def fit_pairs(self, Xi, Xv, item_fields, negatives=None, n_neg=1, margin=0.0, candidates=None, generator=None, attention=False):
+        """OnlineFMBase.fit_pairs's arguments; attention=True: one mini-batch pair step of the whole model (tables and attention)
+        on -log(sigmoid(z_pos - z_neg) + margin) over the logit forward() gives, inv_b = 1 / pairs; returns the mean pair loss.
+        fused_optimizer=True: one fmx_afm_pair_step_opt call; False: fmx_afm_pair_step, then the attention parameters' rule on
+        torch, as update_embedding splits."""
+        self._pair_refusal("fit_pairs", attention)
+        self.train()
+        rows, xv = self._pair_rows(Xi, Xv, item_fields, negatives, n_neg, candidates, generator)
+        e = self._engine
+        e.pair_step(self._hyper, self.update_rule, rows, xv, margin=margin, opt=self._attn_fused)
+        if self._attn_fused is None:
+            self._apply_attention(e.grad)
+        out = e.loss_out[0].clone()
+        self._after_step()
+        return out
+
+    def run_pair_experiment(self, Xi, Xv, item_fields, negatives=None, n_neg=1, margin=0.0, candidates=None, generator=None,
+                            attention=False):
+        """OnlineFMBase.run_pair_experiment's arguments and 4-tuple; attention=True: for every pair predict z_pos > z_neg from the
+        logits before the pair's update, then fit on that pair alone.  fused_optimizer=True: one upload and ONE
+        fmx_afm_pair_online_run call; False: the host loop of one-pair fit_pairs(attention=True) -- the same protocol."""
+        self._pair_refusal("run_pair_experiment", attention)
+        start = time()
+        self.train()
+        rows, xv = self._pair_rows(Xi, Xv, item_fields, negatives, n_neg, candidates, generator)
+        n, e = rows.shape[0] // 2, self._engine
+        if n == 0:
+            return time() - start, 0.0, [], {"correct": 0, "wrong": 0}
+        if self._attn_fused is not None:
+            logits = torch.empty(2 * n, dtype=torch.float32, device=self.device)
+            e.pair_online_run(self._hyper, self.update_rule, rows, xv, self._attn_fused, margin=margin, logits=logits)
+            pred = (logits[0::2] > logits[1::2]).to(torch.uint8)
+        else:
+            fields = [int(f) for f in (item_fields if hasattr(item_fields, "__len__") else [item_fields])]
+            pred = torch.empty(n, dtype=torch.uint8, device=self.device)
+            strict, self.strict_index_check = self.strict_index_check, False      # one check after the loop, no sync inside it
+            try:
+                for i in range(n):
+                    pos, neg = rows[2 * i:2 * i + 1], rows[2 * i + 1:2 * i + 2, fields]
+                    self.fit_pairs(pos, None if xv is None else xv[2 * i:2 * i + 1], fields, negatives=neg, margin=margin,
+                                   attention=True)
+                    pred[i] = e.logit[0] > e.logit[1]            # the step's own forward: the logits before its update
+            finally:
+                self.strict_index_check = strict
+        return self._pair_experiment_result(start, pred)
 
     def _mean_logloss(self, Xi, Xv, y, chunk=16384):
         """The mean BCE-with-logits over a data set, evaluated by batches (reference eval_by_batch, :143-165)."""

@@ -863,6 +863,80 @@ int fmx_afm_online_run(const fmx_table_t *table, const fmx_hyper_t *hyper, int32
                        const float *xv, const float *y, int32_t N, void *workspace, int64_t workspace_bytes, float *attn_grad_out,
                        const fmx_mlp_opt_t *opt, float *logit_out, float *loss_out, int32_t *error, fmx_stream_t stream);
 
+/* ---- pairwise-ranking (BPR) training of the AFM: the pair loss on the full attentional logit ----
+ * The layout is fmx_fm_pair_forward's: B_pairs pairs are idx [2 B_pairs, F] (xv the same shape, or null: ones), row 2i the
+ * positive sample of pair i and row 2i + 1 its negative, both full-width rows (typically the positive's row with the item columns
+ * replaced; nothing assumes that).  With d_i = z[2i] - z[2i + 1] over the logit of fmx_afm_forward the loss is
+ * loss_i = -log(sigmoid(d_i) + margin); margin 0 is BPR.  dL/dlogit of a row depends on its partner's logit, so one workgroup owns
+ * the PAIR: it walks the pairs blockIdx.x, blockIdx.x + gridDim.x, ... and per pair runs the negative's forward, the positive's
+ * forward, the loss, the positive's backward, then the negative's forward again (the same bits: the LDS has no room for two rows
+ * at the largest shape) and its backward.
+ * Order of the sums: the attention accumulators [ dW | db | dh | dp ] of a workgroup take a pair's positive tiles first, then its
+ * negative tiles, each in the pair order of fmx_afm_step; pairs in the workgroup's walk order; the workgroups' partials in
+ * workgroup order.  No float is accumulated with atomics; every sum has one fixed order that depends on (B_pairs, F, t, k) alone.
+ * The table update is fmx_fm_update_occ on the 2 B_pairs rows: a row both samples of a pair name is a run of two occurrences, and
+ * the bias gradient is the sum of dz, exactly +0 (dz[2i + 1] is dz[2i] negated): the bias word keeps its bits under every rule
+ * but FMX_RULE_ADAM, where it moves along its decayed moments alone.
+ * workspace of the step calls: fmx_afm_workspace_bytes(table, afm, 2 * B_pairs) bytes -- it covers dz, loss and E of the 2 B_pairs
+ * rows and more partials than the pair launch's workgroups write (smaller: FMX_ERR_SHAPE; not 16-byte aligned: FMX_ERR_ALIGN).
+ * Refused before anything is launched, each message naming the entry point: a null table / afm / hyper / idx / workspace /
+ * attn_grad_out / opt, B_pairs < 1, 2 * B_pairs beyond int32, a negative / NaN / infinite margin: FMX_ERR_ARG; then what
+ * fmx_afm_step / fmx_afm_step_opt refuse for 2 * B_pairs rows (the AFM's limits, the rule against the layout, the attention
+ * rule's state, FMX_RULE_ADAM's hyper-parameters, the sort's geometry).  error [1] or null: set to 1 when an index lies outside
+ * its field; that row is treated as absent, as in fmx_afm_step.
+ * Restates: the pair objective of reference models/models_meta_emb/meta_fm.py:145-169 for the AFM logit. */
+
+/* The forward pass of the 2 B_pairs rows with the pair epilogue.  logit_out [2 B_pairs]: the bits fmx_afm_forward(FMX_LOSS_NONE)
+ * gives on the same rows; loss_out [2 B_pairs]: loss[2i] = loss_i (unscaled), loss[2i + 1] = +0; dz_out [2 B_pairs]:
+ * dz[2i] = inv_b * d loss_i / d d_i, dz[2i + 1] = the same float negated.  Each of the three may be null.
+ * Replaces: the forward and loss of the reference's pair objective (meta_fm.py:145-169) on AFMAdam.forward (afm_adam.py:43-74). */
+int fmx_afm_pair_forward(const fmx_table_t *table, const fmx_afm_t *afm, const fmx_hyper_t *hyper, const int32_t *idx, const float *xv,
+                         int32_t B_pairs, float margin, float inv_b, float *logit_out, float *loss_out, float *dz_out, int32_t *error,
+                         fmx_stream_t stream);
+
+/* One pair step on one stream: fmx_sort_occurrences(2 B_pairs) -> pair forward + backward -> fmx_fm_update_occ(2 B_pairs) under
+ * `rule` -> the fixed-order reduction of the attention partials.  The attention parameters are NOT updated: attn_grad_out
+ * [t k + 2 t + k] receives the gradient of inv_b * sum_i loss_i.  logit_out [2 B_pairs] or null: the logits before the update;
+ * loss_out [1] = inv_b * sum_i loss_i (may be null).
+ * Replaces: fmx_afm_step's BCE by the reference's pair objective (meta_fm.py:145-169): forward, loss, backward, the embeddings'
+ * optimizer.step. */
+int fmx_afm_pair_step(const fmx_table_t *table, const fmx_hyper_t *hyper, int32_t rule, const fmx_afm_t *afm, const int32_t *idx,
+                      const float *xv, int32_t B_pairs, float margin, float inv_b, void *workspace, int64_t workspace_bytes,
+                      float *attn_grad_out, float *logit_out, float *loss_out, int32_t *error, fmx_stream_t stream);
+
+/* fmx_afm_pair_step with the attention parameters under opt's rule inside the reduction, as fmx_afm_step_opt: the call is step
+ * opt->step + 1 of the attention parameters (read, never written).  attn_grad_out, logit_out, loss_out, error and every table word
+ * are bit-identical to fmx_afm_pair_step on the same inputs.
+ * Replaces: fmx_afm_step_opt's BCE by the reference's pair objective (meta_fm.py:145-169) under the model's one optimizer. */
+int fmx_afm_pair_step_opt(const fmx_table_t *table, const fmx_hyper_t *hyper, int32_t rule, const fmx_afm_t *afm, const int32_t *idx,
+                          const float *xv, int32_t B_pairs, float margin, float inv_b, void *workspace, int64_t workspace_bytes,
+                          float *attn_grad_out, const fmx_mlp_opt_t *opt, float *logit_out, float *loss_out, int32_t *error,
+                          fmx_stream_t stream);
+
+/* n_steps pair steps over a device-resident pool idx_pool [n_pool, 2 B_pairs, F] (xv_pool the same shape, or null), issued from
+ * one call as a plain queue of launches without any host synchronisation, as fmx_afm_stream: step s takes batch s mod n_pool and
+ * is step hyper->step + s + 1 of the tables and opt->step + s + 1 of the attention parameters.  loss_out [n_steps] or null.
+ * Also refused: n_pool < 1, n_steps < 0, step + n_steps beyond int32: FMX_ERR_ARG; n_steps = 0 launches nothing.
+ * The result is, bit for bit, the one of n_steps calls of fmx_afm_pair_step_opt with both step counts advanced by the caller.
+ * Replaces: fmx_afm_stream's BCE by the reference's pair objective (meta_fm.py:145-169), batched as AFMAdam.fit batches. */
+int fmx_afm_pair_stream(const fmx_table_t *table, const fmx_hyper_t *hyper, int32_t rule, const fmx_afm_t *afm, const int32_t *idx_pool,
+                        const float *xv_pool, int32_t n_pool, int32_t B_pairs, float margin, float inv_b, int32_t n_steps,
+                        void *workspace, int64_t workspace_bytes, float *attn_grad_out, const fmx_mlp_opt_t *opt, float *loss_out,
+                        int32_t *error, fmx_stream_t stream);
+
+/* The online predict-then-fit protocol restated for pairs on N_pairs device-resident pairs idx [2 N_pairs, F]: every pair is
+ * predicted, then fitted on alone.  The contract: bit for bit N_pairs calls of fmx_afm_pair_step_opt(B_pairs = 1, inv_b = 1), pair
+ * i being step hyper->step + i + 1 of the tables and opt->step + i + 1 of the attention parameters (both read, never written).
+ * logit_out [2 N_pairs] or null: each pair's two logits BEFORE its update (the prediction is logit[2i] > logit[2i + 1]); loss_out
+ * [N_pairs] or null: each pair's loss.  workspace: fmx_afm_workspace_bytes(table, afm, 2) bytes.  N_pairs < 0: FMX_ERR_ARG;
+ * N_pairs = 0 launches nothing and returns 0.  The pairs' launches are queued without any host synchronisation (the form
+ * fmx_afm_online_run takes when its one-workgroup kernel does not fit); the contract leaves room for a one-workgroup form.
+ * Replaces: the protocol of reference fm_adam.py:90-119 under the pair objective of meta_fm.py:145-169, for the AFM. */
+int fmx_afm_pair_online_run(const fmx_table_t *table, const fmx_hyper_t *hyper, int32_t rule, const fmx_afm_t *afm, const int32_t *idx,
+                            const float *xv, int32_t N_pairs, float margin, void *workspace, int64_t workspace_bytes,
+                            float *attn_grad_out, const fmx_mlp_opt_t *opt, float *logit_out, float *loss_out, int32_t *error,
+                            fmx_stream_t stream);
+
 /* ---- top-K recommendation under the AFM (fmx/recommend.py, AFMAdam.recommend) ----
  * Split the fields into context fields C and item fields I (at least one of each).  A combined sample's pairs are the C x C
  * pairs (u alone), the I x I pairs (c alone) and the |C| |I| cross pairs.  Each side's own pairs reduce to (lin, m, Z, R):
