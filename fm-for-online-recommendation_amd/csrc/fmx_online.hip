@@ -1,7 +1,8 @@
 // fmx_online.hip -- the stream walkers, one wavefront or one workgroup walking a device-resident stream sample by sample (predict,
 // then fit on that sample), and their C ABI: k_fm_online (fmx_fm_online_run), k_fm_pair_online (fmx_fm_pair_online_run), k_mlp_small
-// (fmx_mlp_forward / _fit / _fit_opt / _hedge_fit) and k_online_mlp (fmx_online_run_mlp / _opt).  On the device they use fmx_common.h
-// alone; the per-sample fallback of fmx_online_run_mlp issues the batched launches of the other units through fmx_host.h.
+// (fmx_mlp_forward / _fit / _fit_opt / _hedge_fit), k_mlp_small_pair (fmx_mlp_pair_fit), k_online_mlp (fmx_online_run_mlp / _opt) and
+// k_online_mlp_pair (fmx_online_run_mlp_pair).  On the device they use fmx_common.h alone; the per-sample fallbacks of
+// fmx_online_run_mlp and fmx_online_run_mlp_pair issue the batched launches of the other units through fmx_host.h.
 
 #include "fmx_host.h"
 
@@ -345,6 +346,9 @@ struct MlpArgs {
   int32_t opt_rule;
   float *m, *v;
   fmx_hyper_t oh;
+  // the pair mode of the FIT step (mlp_small_body<true>; appended: the offsets the other modes read do not depend on them)
+  float margin;        // the pair loss's margin
+  uint8_t *pair_pred;  // [B / 2] z[2i] > z[2i + 1], before the update; or null
 };
 
 // the network's rule for its step t (1-based) as k_mlp_small takes it: ADAM's constants in double, once per step (adam_consts)
@@ -370,7 +374,13 @@ __device__ __forceinline__ float *mlp_w(const MlpArgs &a, int l) {
   return a.params + off;
 }
 
-// the body of k_mlp_small; also called once per sample by k_online_mlp (every pointer may then point into LDS)
+// the body of k_mlp_small; also called once per sample by k_online_mlp (every pointer may then point into LDS).
+// PAIR (k_mlp_small_pair, k_online_mlp_pair; FIT mode only): the B rows are B / 2 pairs, row 2i the positive and row 2i + 1 the
+// negative; the loss is pair_loss_dz of d_i = z[2i] - z[2i + 1] and no label is read.  The two rows of a pair belong to adjacent
+// lanes of one wavefront (l * B is even), which exchange their logits and evaluate pair_loss_dz on identical operands: the
+// negative's dz is the positive's float negated, its loss +0.  Everything else is the pointwise code, and the instantiation
+// without PAIR is the body as it was.
+template <bool PAIR>
 __device__ void mlp_small_body(const MlpArgs &a) {
   __shared__ float acts[(MLP_MAX_L + 1) * MLP_MAX_B * MLP_MAX_W];  // x_0 .. x_L, [l][b][j]
   __shared__ float dA[MLP_MAX_B * MLP_MAX_W], dB[MLP_MAX_B * MLP_MAX_W];  // d x_l (ping-pong); dA is reused as d pre
@@ -413,7 +423,19 @@ __device__ void mlp_small_body(const MlpArgs &a) {
         if (l == L - 1 && a.out) a.out[b] = z;
       } else if (a.mode == MLP_MODE_FIT) {
         float loss;
-        bce_loss_dz(a.loss_kind, z, a.y[b], a.inv_b, loss, g);
+        if constexpr (PAIR) {
+          const float zo = __shfl_xor(z, 1);  // the partner row's logit: b ^ 1 is lane ^ 1, and both lanes are here (same l)
+          const bool pos = (b & 1) == 0;
+          pair_loss_dz(pos ? z - zo : zo - z, a.margin, a.inv_b, loss, g);  // both lanes: the same operands, the same bits
+          if (!pos) {
+            g = -g;
+            loss = 0.f;
+          } else if (a.pair_pred) {
+            a.pair_pred[b >> 1] = z > zo ? 1 : 0;
+          }
+        } else {
+          bce_loss_dz(a.loss_kind, z, a.y[b], a.inv_b, loss, g);
+        }
         a.dz_out[b] = g;
         X(0, b, MLP_MAX_W - 1) = loss;  // parked for the ordered sum below (k <= 63 is host-checked in FIT mode)
       } else {  // HEDGE: BCELoss(sigmoid(z), y), mean over the batch; d/dz = (p - y) / B
@@ -511,7 +533,8 @@ __device__ void mlp_small_body(const MlpArgs &a) {
   }
 }
 
-__global__ __launch_bounds__(256) void k_mlp_small(MlpArgs a) { mlp_small_body(a); }
+__global__ __launch_bounds__(256) void k_mlp_small(MlpArgs a) { mlp_small_body<false>(a); }
+__global__ __launch_bounds__(256) void k_mlp_small_pair(MlpArgs a) { mlp_small_body<true>(a); }
 
 // ------------------------------------------------------------------------------------------------------------
 // k_online_mlp: the online predict-then-fit loop of the classes with an MLP, one workgroup walking the stream
@@ -692,7 +715,7 @@ __global__ __launch_bounds__(256) void k_online_mlp(OnlineMlpArgs a) {
         m.oh.beta2 = net_adam ? uniform_f(kc[5]) : 0.f;
       }
     }
-    mlp_small_body(m);
+    mlp_small_body<false>(m);
     __syncthreads();
     if (wave == 0 && !a.hedge) {
       // ---- the table update of k_fm_update at B = 1: every row is a run of one occurrence, G = dz [+ dL/dbi] ----
@@ -737,6 +760,235 @@ __global__ __launch_bounds__(256) void k_online_mlp(OnlineMlpArgs a) {
   }
 }
 
+// ------------------------------------------------------------------------------------------------------------
+// k_online_mlp_pair: k_online_mlp for pairs (fmx_online_run_mlp_pair): one workgroup walks N pairs, predict (z_pos > z_neg through
+// the whole network) then one pair step on that pair
+// ------------------------------------------------------------------------------------------------------------
+// Per pair: wave 0 holds BOTH samples' rows (as k_fm_pair_online does) and evaluates both FM parts with k_fm_forward's
+// arithmetic, leaving bi [2, kp] and base [2] in LDS; the whole workgroup runs mlp_small_body<true> at B = 2 on parameters (and
+// moments) that stay in LDS for the length of the stream; wave 0 then applies k_fm_update at B = 2 from the rows it still holds,
+// with k_fm_pair_online's run logic: a field whose two samples name the same valid row is ONE run of two occurrences summed in
+// sample order, (0 + c_pos) + c_neg, and takes one update_row; otherwise two runs of one, each 0 + c.  The bias gradient
+// dz[0] + dz[1] is exactly +0 and still goes through bias_step.  has_opt is a run-time word here (the weights rules take both
+// forms), so one instantiation per (kp, table rule) serves fmx_online_run_mlp_pair with and without opt.
+struct OnlineMlpPairArgs {
+  float *rows;
+  const int64_t *foff;
+  float *bias;
+  const int32_t *idx;  // [2N, F]: rows 2i (positive) and 2i + 1 (negative) of pair i
+  const float *xv;     // [2N, F] or null
+  uint8_t *pred;       // [N] z_pos > z_neg BEFORE the pair's update
+  float *logit;        // [2N] or null
+  float *loss;         // [N] or null
+  int32_t *error;
+  float *params;       // global: copied into LDS, written back at the end
+  fmx_hyper_t h;       // alpha already inverted (table rule); lr / eps also drive the MLP rule when has_opt == 0
+  int32_t N, F, stride, zoff, n_params;
+  int32_t k, hidden, n_layers, fm_term, rule;
+  int32_t has_opt;     // the network under opt (m, v global: copied into LDS, written back at the end)
+  float margin;
+  fmx_mlp_opt_t opt;
+};
+
+template <int LPR, int LAYOUT, int RULE>
+__global__ __launch_bounds__(256) void k_online_mlp_pair(OnlineMlpPairArgs a) {
+  constexpr int SLOTS = WAVE / LPR, NP = 4;
+  constexpr bool MOM = LAYOUT == FMX_LAYOUT_MOMENTS;
+  extern __shared__ float p_lds[];  // [n_params] the MLP's parameters; then v [n_params] (ADAGRAD, ADAM), then m [n_params] (ADAM)
+  __shared__ float kc[8];           // ADAM's constants of the pair, as in k_online_mlp
+  __shared__ float bi_lds[2 * MLP_MAX_W], gbi_lds[2 * MLP_MAX_W];  // [2, kp]
+  __shared__ float base_lds[2], dz_lds[2];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int slot = lane / LPR, q = lane % LPR;
+  const int kp = LPR * 4;
+  for (int i = tid; i < a.n_params; i += blockDim.x) p_lds[i] = a.params[i];
+  const int net_rule = a.has_opt ? a.opt.rule : -1;  // workgroup-uniform
+  const bool net_adaptive = net_rule == FMX_RULE_ADAGRAD || net_rule == FMX_RULE_ADAM, net_adam = net_rule == FMX_RULE_ADAM;
+  float *v_lds = p_lds + a.n_params, *m_lds = v_lds + a.n_params;
+  if (net_adaptive)
+    for (int i = tid; i < a.n_params; i += blockDim.x) v_lds[i] = a.opt.v[i];
+  if (net_adam)
+    for (int i = tid; i < a.n_params; i += blockDim.x) m_lds[i] = a.opt.m[i];
+  // the bias (or its (b, m_b, v_b)) stays in wave 0's registers
+  float b0 = a.bias[0], b1 = LAYOUT != FMX_LAYOUT_WEIGHTS ? a.bias[1] : 0.f, b2 = MOM ? a.bias[2] : 0.f;
+  int64_t lo[NP];
+  uint32_t vocab[NP];
+  bool live[NP];
+#pragma unroll
+  for (int p = 0; p < NP; ++p) {
+    const int f = p * SLOTS + slot;
+    live[p] = f < a.F;
+    lo[p] = live[p] ? a.foff[f] : 0;
+    vocab[p] = live[p] ? (uint32_t)(a.foff[f + 1] - lo[p]) : 0u;
+  }
+  bool bad = false;
+  // wave 0: the NEXT pair's indices (and values), sample t = 0 (positive), 1 (negative); branch-free, as in k_fm_pair_online
+  const float *xsrc = a.xv ? a.xv : reinterpret_cast<const float *>(a.idx);
+  const bool has_x = a.xv != nullptr;
+  uint32_t l_n[2][NP];
+  float x_n[2][NP];
+  auto fetch_inputs = [&](int i) {
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {
+#pragma unroll
+      for (int p = 0; p < NP; ++p) {
+        const size_t o = (live[p] && i < a.N) ? ((size_t)2 * i + t) * a.F + p * SLOTS + slot : (size_t)0;
+        l_n[t][p] = (uint32_t)a.idx[o];
+        x_n[t][p] = xsrc[o];
+      }
+    }
+  };
+  if (wave == 0) fetch_inputs(0);
+  __syncthreads();
+  for (int i = 0; i < a.N; ++i) {
+    uint32_t li[2][NP];
+    float x[2][NP];
+    RowRegs row[2][NP];
+    bool ok[2][NP];
+    float4 S[2] = {splat(0.f), splat(0.f)};
+    if (tid == WAVE && (RULE == FMX_RULE_ADAM || net_adam)) {  // one lane of wave 1, idle until the MLP step
+      if (RULE == FMX_RULE_ADAM) adam_consts(a.h.lr, a.h.beta1, a.h.beta2, a.h.step + i + 1, kc[0], kc[1], kc[2]);
+      if (net_adam) adam_consts(a.opt.lr, a.opt.beta1, a.opt.beta2, a.opt.step + i + 1, kc[3], kc[4], kc[5], a.opt.eps, &kc[6]);
+    }
+    if (wave == 0) {
+      // ---- the FM part of both samples: the arithmetic of k_fm_forward; all row loads together ----
+#pragma unroll
+      for (int t = 0; t < 2; ++t) {
+#pragma unroll
+        for (int p = 0; p < NP; ++p) {
+          li[t][p] = live[p] ? l_n[t][p] : 0u;
+          x[t][p] = (has_x && live[p]) ? x_n[t][p] : 1.f;
+          ok[t][p] = live[p] && li[t][p] < vocab[p];
+        }
+      }
+#pragma unroll
+      for (int t = 0; t < 2; ++t) {
+#pragma unroll
+        for (int p = 0; p < NP; ++p) {
+          row[t][p] = load_row_sc1<LAYOUT, RULE>(a.rows + (size_t)(ok[t][p] ? lo[p] + li[t][p] : 0) * a.stride, q, kp, a.zoff);
+          bad = bad || (live[p] && !ok[t][p]);
+        }
+      }
+      fetch_inputs(i + 1);
+      const float bias_w = bias_weight<LAYOUT>(b0, b1, a.h);
+#pragma unroll
+      for (int t = 0; t < 2; ++t) {
+        float4 s = splat(0.f), ss = splat(0.f);
+        float fo = 0.f;
+#pragma unroll
+        for (int p = 0; p < NP; ++p) {
+          if (ok[t][p]) {
+            const float4 e = x[t][p] * row[t][p].v;
+            s = s + e;
+            ss = ss + e * e;
+            fo += row[t][p].fo.x * x[t][p];
+          }
+        }
+        fm_field_sums<LPR>(s, ss, fo, lane);
+        S[t] = s;
+        float sbi;
+        const float4 bi = fm_bi<LPR>(s, ss, sbi);
+        fo = __shfl(fo, 0);
+        if (lane < LPR) {
+          bi_lds[t * kp + 4 * q] = bi.x;
+          bi_lds[t * kp + 4 * q + 1] = bi.y;
+          bi_lds[t * kp + 4 * q + 2] = bi.z;
+          bi_lds[t * kp + 4 * q + 3] = bi.w;
+        }
+        if (lane == 0) base_lds[t] = a.fm_term ? fo + sbi + bias_w : fo + bias_w;
+      }
+    }
+    __syncthreads();
+    // ---- the pair step of k_mlp_small_pair at B = 2 on LDS-resident parameters ----
+    MlpArgs m{};
+    m.params = p_lds;
+    m.bi = bi_lds;
+    m.base = base_lds;
+    m.pred_out = a.logit ? a.logit + 2 * (size_t)i : nullptr;
+    m.out = a.loss ? a.loss + i : nullptr;
+    m.pair_pred = a.pred + i;
+    m.margin = a.margin;
+    m.h = a.h;
+    m.inv_b = 1.0f;
+    m.B = 2;
+    m.k = a.k;
+    m.kp = kp;
+    m.hidden = a.hidden;
+    m.n_layers = a.n_layers;
+    m.dz_out = dz_lds;
+    m.gbi_out = gbi_lds;
+    m.mode = MLP_MODE_FIT;
+    m.rule = a.rule;
+    if (net_rule == FMX_RULE_SGD) {  // (mlp_small_set_opt)
+      m.rule = FMX_RULE_SGD;
+      m.h.lr = a.opt.lr;
+    } else if (net_adaptive) {
+      m.opt_rule = net_rule;
+      m.m = m_lds;
+      m.v = v_lds;
+      m.oh.lr = net_adam ? uniform_f(kc[3]) : a.opt.lr;
+      m.oh.eps = net_adam ? uniform_f(kc[6]) : a.opt.eps;
+      m.oh.beta1 = net_adam ? uniform_f(kc[4]) : 0.f;
+      m.oh.beta2 = net_adam ? uniform_f(kc[5]) : 0.f;
+    }
+    mlp_small_body<true>(m);
+    __syncthreads();
+    if (wave == 0) {
+      // ---- the table update of k_fm_update at B = 2: G_t = dz_t [+ dL/dbi_t], runs as in k_fm_pair_online ----
+      const float dz[2] = {dz_lds[0], dz_lds[1]};
+      float4 G[2];
+#pragma unroll
+      for (int t = 0; t < 2; ++t) {
+        const float4 g4 = {gbi_lds[t * kp + 4 * q], gbi_lds[t * kp + 4 * q + 1], gbi_lds[t * kp + 4 * q + 2], gbi_lds[t * kp + 4 * q + 3]};
+        G[t] = splat(a.fm_term ? dz[t] : 0.f) + g4;
+      }
+      fmx_hyper_t h = a.h;
+      if (RULE == FMX_RULE_ADAM) {  // the pair's constants, as update_impl derives them for a launch
+        h.lr = uniform_f(kc[0]);
+        h.beta1 = uniform_f(kc[1]);
+        h.beta2 = uniform_f(kc[2]);
+      }
+#pragma unroll
+      for (int p = 0; p < NP; ++p) {
+        float4 cV[2], cA[2];
+        float cw[2];
+#pragma unroll
+        for (int t = 0; t < 2; ++t) {  // the occurrence's terms as update_body forms them with gbi
+          const float4 xG = x[t][p] * G[t];
+          cV[t] = xG * S[t];
+          cA[t] = x[t][p] * xG;
+          cw[t] = x[t][p] * dz[t];
+        }
+        float *rp0 = a.rows + (size_t)(lo[p] + li[0][p]) * a.stride, *rp1 = a.rows + (size_t)(lo[p] + li[1][p]) * a.stride;
+        if (ok[0][p] && ok[1][p] && li[0][p] == li[1][p]) {  // one run of two occurrences, in sample order
+          update_row<LAYOUT, RULE>(rp0, q, kp, a.zoff, row[0][p], (splat(0.f) + cV[0]) + cV[1], (splat(0.f) + cA[0]) + cA[1],
+                                   (0.f + cw[0]) + cw[1], h);
+        } else {
+          if (ok[0][p]) update_row<LAYOUT, RULE>(rp0, q, kp, a.zoff, row[0][p], splat(0.f) + cV[0], splat(0.f) + cA[0], 0.f + cw[0], h);
+          if (ok[1][p]) update_row<LAYOUT, RULE>(rp1, q, kp, a.zoff, row[1][p], splat(0.f) + cV[1], splat(0.f) + cA[1], 0.f + cw[1], h);
+        }
+      }
+      bias_step<LAYOUT, RULE>(b0, b1, b2, dz[0] + dz[1], h);           // exactly +0
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the row stores are acknowledged before the next pair's loads
+    }
+    __syncthreads();
+  }
+  for (int i = tid; i < a.n_params; i += blockDim.x) a.params[i] = p_lds[i];
+  if (net_adaptive)
+    for (int i = tid; i < a.n_params; i += blockDim.x) a.opt.v[i] = v_lds[i];
+  if (net_adam)
+    for (int i = tid; i < a.n_params; i += blockDim.x) a.opt.m[i] = m_lds[i];
+  if (wave == 0) {
+    const bool any_bad = __ballot(bad) != 0ull;
+    if (lane == 0) {
+      a.bias[0] = b0;
+      if (MOM && RULE == FMX_RULE_ADAM) a.bias[1] = b1;
+      if (MOM) a.bias[2] = b2;
+      if (any_bad && a.error) *a.error = 1;
+    }
+  }
+}
+
 template <int LPR, int LAYOUT, int RULE>
 void launch_online_np(const OnlineArgs &a, int np, hipStream_t st) {
   auto launch = [&](auto NP) { hipLaunchKernelGGL((k_fm_online<LPR, LAYOUT, RULE, NP>), dim3(1), dim3(64), 0, st, a); };
@@ -764,6 +1016,18 @@ void launch_online_mlp_k(const OnlineMlpArgs &a, hipStream_t st) {
     raised = arrays;
   }
   hipLaunchKernelGGL((k_online_mlp<LPR, LAYOUT, RULE, OPT>), dim3(1), dim3(256), (size_t)arrays * a.n_params * 4, st, a);
+}
+
+template <int LPR, int LAYOUT, int RULE>
+void launch_online_mlp_pair_k(const OnlineMlpPairArgs &a, hipStream_t st) {
+  static int raised = 0;  // (launch_online_mlp_k)
+  const int arrays = !a.has_opt || a.opt.rule == FMX_RULE_SGD ? 1 : a.opt.rule == FMX_RULE_ADAM ? 3 : 2;
+  if (raised < arrays) {
+    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_online_mlp_pair<LPR, LAYOUT, RULE>),
+                              hipFuncAttributeMaxDynamicSharedMemorySize, arrays * ONLINE_MLP_MAX_PARAMS * 4);
+    raised = arrays;
+  }
+  hipLaunchKernelGGL((k_online_mlp_pair<LPR, LAYOUT, RULE>), dim3(1), dim3(256), (size_t)arrays * a.n_params * 4, st, a);
 }
 
 }  // namespace
@@ -846,7 +1110,7 @@ int fmx_fm_pair_online_run(const fmx_table_t *table, const fmx_hyper_t *hyper, i
   return check_launch("k_fm_pair_online");
 }
 
-static int mlp_launch(const fmx_mlp_t *mlp, MlpArgs &a, int32_t B, int32_t kp, fmx_stream_t stream, const char *who) {
+static int mlp_launch(const fmx_mlp_t *mlp, MlpArgs &a, int32_t B, int32_t kp, fmx_stream_t stream, const char *who, bool pair = false) {
   if (!mlp || !mlp->params) return fail(FMX_ERR_ARG, "%s: null mlp", who);
   if (mlp->n_layers < 1 || mlp->n_layers > MLP_MAX_L || mlp->hidden < 1 || mlp->hidden > MLP_MAX_W || mlp->k < 1 ||
       mlp->k > MLP_MAX_W || B < 1 || B > MLP_MAX_B || kp < mlp->k)
@@ -858,6 +1122,10 @@ static int mlp_launch(const fmx_mlp_t *mlp, MlpArgs &a, int32_t B, int32_t kp, f
   a.kp = kp;
   a.hidden = mlp->hidden;
   a.n_layers = mlp->n_layers;
+  if (pair) {
+    hipLaunchKernelGGL(k_mlp_small_pair, dim3(1), dim3(256), 0, static_cast<hipStream_t>(stream), a);
+    return check_launch("k_mlp_small_pair");
+  }
   hipLaunchKernelGGL(k_mlp_small, dim3(1), dim3(256), 0, static_cast<hipStream_t>(stream), a);
   return check_launch("k_mlp_small");
 }
@@ -1076,6 +1344,157 @@ int fmx_mlp_fit_opt(const fmx_mlp_t *mlp, const fmx_hyper_t *hyper, int32_t loss
                     fmx_stream_t stream) {
   return mlp_fit_impl(mlp, hyper, FMX_RULE_SGD, loss_kind, bi, kp, base, y, B, inv_b, dz_out, gbi_out, loss_out, opt, true, stream,
                       "fmx_mlp_fit_opt");
+}
+
+
+// what fmx_mlp_pair_fit refuses, and fmx_online_run_mlp_pair of its network: fmx_mlp_fit's limits on 2 * B_pairs rows, the pair
+// arguments, and with opt what fmx_mlp_fit_opt refuses (n_steps steps of the network)
+static int mlp_pair_fit_check(const fmx_mlp_t *mlp, const fmx_hyper_t *hyper, int32_t rule, int32_t kp, int32_t B_pairs, float margin,
+                              const fmx_mlp_opt_t *opt, int64_t n_steps, const char *who) {
+  if (B_pairs < 1) return fail(FMX_ERR_ARG, "%s: B_pairs = %d must be >= 1", who, B_pairs);
+  if (!(margin >= 0.f) || !std::isfinite(margin)) return fail(FMX_ERR_ARG, "%s: margin = %g must be finite and >= 0", who, (double)margin);
+  if (!mlp || !mlp->params) return fail(FMX_ERR_ARG, "%s: null mlp", who);
+  if (opt) {
+    if (int rc = mlp_small_opt_check(mlp, opt, n_steps, who)) return rc;
+  } else {
+    if (adaptive_rule(rule)) return refuse_adaptive(rule, who);
+    if (!hyper) return fail(FMX_ERR_ARG, "%s: null argument (hyper)", who);
+    if (rule != FMX_RULE_SIGNADAM && rule != FMX_RULE_SGD) return fail(FMX_ERR_ARG, "%s: rule must be SIGNADAM or SGD", who);
+  }
+  if (mlp->n_layers < 1 || mlp->n_layers > MLP_MAX_L || mlp->hidden < 1 || mlp->hidden > MLP_MAX_W || mlp->k < 1 ||
+      mlp->k > MLP_MAX_W - 1 || B_pairs > MLP_MAX_B / 2 || kp < mlp->k)
+    return fail(FMX_ERR_UNSUPPORTED, "%s: needs B_pairs <= %d, k <= %d, hidden <= %d, layers <= %d (got B_pairs=%d k=%d hidden=%d layers=%d)",
+                who, MLP_MAX_B / 2, MLP_MAX_W - 1, MLP_MAX_W, MLP_MAX_L, B_pairs, mlp->k, mlp->hidden, mlp->n_layers);
+  return FMX_OK;
+}
+
+// the pair step's arguments as k_mlp_small_pair takes them; the network's step t (1-based) under opt
+static void mlp_pair_fit_args(MlpArgs &a, const fmx_hyper_t *hyper, int32_t rule, float margin, float inv_b, const fmx_mlp_opt_t *opt,
+                              int32_t t) {
+  if (hyper) a.h = hyper_for(hyper, -1);
+  a.mode = MLP_MODE_FIT;
+  a.rule = rule;
+  a.margin = margin;
+  a.inv_b = inv_b;
+  if (opt) mlp_small_set_opt(a, *opt, t);
+}
+
+int fmx_mlp_pair_fit(const fmx_mlp_t *mlp, const fmx_hyper_t *hyper, int32_t rule, const float *bi, int32_t kp, const float *base,
+                     int32_t B_pairs, float margin, float inv_b, float *logit_out, float *dz_out, float *gbi_out, float *loss_out,
+                     const fmx_mlp_opt_t *opt, fmx_stream_t stream) {
+  const char *who = "fmx_mlp_pair_fit";
+  if (int rc = mlp_pair_fit_check(mlp, hyper, rule, kp, B_pairs, margin, opt, 1, who)) return rc;
+  if (!bi || !base || !dz_out || !gbi_out) return fail(FMX_ERR_ARG, "%s: null argument", who);
+  MlpArgs a{};
+  a.bi = bi;
+  a.base = base;
+  a.pred_out = logit_out;
+  a.dz_out = dz_out;
+  a.gbi_out = gbi_out;
+  a.out = loss_out;
+  mlp_pair_fit_args(a, opt ? nullptr : hyper, rule, margin, inv_b, opt, opt ? opt->step + 1 : 0);
+  return mlp_launch(mlp, a, 2 * B_pairs, kp, stream, who, true);
+}
+
+int fmx_online_run_mlp_pair(const fmx_table_t *table, const fmx_hyper_t *hyper, int32_t rule, const fmx_mlp_t *mlp, int32_t fm_term,
+                            const int32_t *idx, const float *xv, int32_t N, float margin, void *workspace, int64_t workspace_bytes,
+                            const fmx_fwd_out_t *fwd, float *scratch, uint8_t *pred_out, float *logit_out, float *loss_out,
+                            const fmx_mlp_opt_t *opt, fmx_stream_t stream) {
+  const char *who = "fmx_online_run_mlp_pair";
+  static const int32_t no_pairs = 0;  // an empty stream's buffers may be null; everything else is checked as for one pair
+  if (int rc = check_pair_args(table, hyper, N == 0 && !idx ? &no_pairs : idx, N > 0 ? N : 1, "N", margin, who)) return rc;
+  if (N < 0) return fail(FMX_ERR_ARG, "%s: N = %d must be >= 0", who, N);
+  if (N > INT32_MAX / 2) return fail(FMX_ERR_ARG, "%s: N = %d: 2 * N rows exceed int32", who, N);
+  if (N > 0 && !pred_out) return fail(FMX_ERR_ARG, "%s: pred_out is null", who);
+  if (!workspace || !fwd || !scratch) return fail(FMX_ERR_ARG, "%s: null argument", who);
+  if (!fwd->S || !fwd->bi || !fwd->sfirst || !fwd->logit) return fail(FMX_ERR_ARG, "%s: fwd needs S, bi, sfirst, logit", who);
+  if (!aligned16(workspace) || !aligned16(scratch)) return fail(FMX_ERR_ALIGN, "%s: workspace and scratch must be 16-byte aligned", who);
+  if (int rc = mlp_pair_fit_check(mlp, hyper, rule, table->kp, 1, margin, opt, N, who)) return rc;
+  if (int rc = check_rule(table, rule)) return named(rc, who);
+  if (opt) {
+    if (int rc = check_adam(hyper, rule, N)) return named(rc, who);
+    if (!fm_term && table->layout == FMX_LAYOUT_FTRL)
+      return fail(FMX_ERR_UNSUPPORTED, "%s: fm_term = 0 (NFM) needs a table in the weights or the moments layout", who);
+  }
+  if (int rc = check_sort_geometry(table, 2)) return named(rc, who);
+  if (int rc = check_workspace(table, 2, workspace, workspace_bytes, who)) return rc;
+  if (N == 0) return FMX_OK;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  {  // one workgroup walks the stream when the network fits in LDS and both samples' fields fit one wavefront (k_online_mlp_pair)
+    long long n_params = 0;
+    for (int l = 0; l < mlp->n_layers; ++l) n_params += (long long)mlp->hidden * (l == 0 ? mlp->k : mlp->hidden) + mlp->hidden;
+    const int slots = WAVE / lpr_of(table->kp);
+    if (tune().online_persistent && n_params <= ONLINE_MLP_OPT_MAX_PARAMS && table->n_fields <= 4 * slots &&
+        table->layout != FMX_LAYOUT_FTRL) {
+      OnlineMlpPairArgs a;
+      memset(&a, 0, sizeof(a));
+      a.rows = table->rows;
+      a.foff = table->field_offsets;
+      a.bias = table->bias;
+      a.idx = idx;
+      a.xv = xv;
+      a.pred = pred_out;
+      a.logit = logit_out;
+      a.loss = loss_out;
+      a.error = fwd->error;
+      a.params = mlp->params;
+      a.h = kernel_hyper(hyper, opt ? rule : -1);  // ADAM tables: the kernel derives each pair's constants from lr, beta1, beta2, step
+      a.N = N;
+      a.F = table->n_fields;
+      a.stride = table->row_stride;
+      a.zoff = table->z_offset;
+      a.n_params = (int32_t)n_params;
+      a.k = mlp->k;
+      a.hidden = mlp->hidden;
+      a.n_layers = mlp->n_layers;
+      a.fm_term = fm_term;
+      a.rule = rule;
+      a.margin = margin;
+      if (opt) {
+        a.has_opt = 1;
+        a.opt = *opt;
+      }
+      with_lpr(table->kp, [&](auto LPR) {
+        with_rule(rule, [&](auto LAYOUT, auto RULE) {
+          if constexpr (LAYOUT != FMX_LAYOUT_FTRL) launch_online_mlp_pair_k<LPR, LAYOUT, RULE>(a, st);  // (never FTRL here)
+        });
+      });
+      return check_launch("k_online_mlp_pair");
+    }
+  }
+  // the queued form: per pair forward(B = 2), k_mlp_small_pair, sort(B = 2), update(B = 2), no host synchronisation
+  const Workspace w = carve(table, 2, workspace);
+  const size_t F = (size_t)table->n_fields;
+  fmx_fwd_out_t f2 = *fwd;  // two samples: dense outputs
+  f2.sample_ld = 0;
+  float *dz = scratch, *gbi = scratch + 8;
+  for (int i = 0; i < N; ++i) {
+    const int32_t *idx_i = idx + (size_t)i * 2 * F;
+    const float *xv_i = xv ? xv + (size_t)i * 2 * F : nullptr;
+    if (int rc = forward_impl(table, hyper, idx_i, xv_i, nullptr, 2, FMX_LOSS_NONE, 1.0f, &f2, st)) return rc;
+    MlpArgs a{};
+    a.bi = fwd->bi;
+    a.base = fm_term ? fwd->logit : fwd->sfirst;
+    if (!fm_term) {  // NFM: the logit without the MLP term is the first-order sum plus the bias weight
+      a.base_bias = table->bias;
+      a.base_bias_ftrl = table->layout == FMX_LAYOUT_FTRL;
+      a.h_table = kernel_hyper(hyper, -1);
+    }
+    a.pred_out = logit_out ? logit_out + (size_t)i * 2 : nullptr;
+    a.out = loss_out ? loss_out + i : nullptr;
+    a.pair_pred = pred_out + i;
+    a.dz_out = dz;
+    a.gbi_out = gbi;
+    mlp_pair_fit_args(a, hyper, rule, margin, 1.0f, opt, opt ? opt->step + i + 1 : 0);
+    if (int rc = mlp_launch(mlp, a, 2, table->kp, stream, who, true)) return rc;
+    if (int rc = sort_impl(table, idx_i, 2, w.sorted, w.runs, fwd->error, st)) return rc;
+    fmx_hyper_t hs = hyper_for(hyper, opt ? rule : -1);  // pair i is step t = hyper->step + i + 1 of the tables
+    hs.step += i;
+    if (int rc = update_impl(table, &hs, rule, w, w.sorted, xv_i, fwd->S, dz, fm_term ? dz : nullptr, gbi, 2, nullptr, 1.0f, nullptr, st,
+                             nullptr, 0, fwd->error))
+      return rc;
+  }
+  return FMX_OK;
 }
 
 int fmx_mlp_hedge_fit(const fmx_mlp_t *mlp, float lr, float hedge_b, float hedge_s, float *alpha, const float *bi, int32_t kp,

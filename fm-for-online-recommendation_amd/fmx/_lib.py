@@ -30,7 +30,7 @@ EXPORTS = ["fmx_version", "fmx_last_error_string", "fmx_set_option", "fmx_sorted
            "fmx_fm_rank_workspace_bytes", "fmx_fm_rank", "fmx_mlp_rank_workspace_bytes", "fmx_mlp_rank",
            "fmx_afm_rank_workspace_bytes", "fmx_afm_rank",
            "fmx_fm_pair_forward", "fmx_fm_pair_step", "fmx_fm_pair_stream", "fmx_fm_pair_online_run",
-           "fmx_mlp_pair_section", "fmx_deepfm_pair_stream",
+           "fmx_mlp_pair_section", "fmx_deepfm_pair_stream", "fmx_mlp_pair_fit", "fmx_online_run_mlp_pair",
            "fmx_afm_pair_forward", "fmx_afm_pair_step", "fmx_afm_pair_step_opt", "fmx_afm_pair_stream", "fmx_afm_pair_online_run"]
 
 
@@ -169,6 +169,8 @@ def load():
     lib.fmx_fm_pair_online_run.argtypes = [TP, HP, i32, p, p, i32, f32, p, p, p, p, p]
     lib.fmx_mlp_pair_section.argtypes = [MP, p, i32, p, i32, f32, f32, p, i64, p, p, p, i32, p, f32, OP, p, p]
     lib.fmx_deepfm_pair_stream.argtypes = [TP, HP, i32, MP, i32, p, i32, i32, f32, f32, i32, p, i64, p, i64, FP, p, p, p, f32, OP, p, p]
+    lib.fmx_mlp_pair_fit.argtypes = [MP, HP, i32, p, i32, p, i32, f32, f32, p, p, p, p, OP, p]
+    lib.fmx_online_run_mlp_pair.argtypes = [TP, HP, i32, MP, i32, p, p, i32, f32, p, i64, FP, p, p, p, p, OP, p]
     lib.fmx_afm_pair_forward.argtypes = [TP, AP, HP, p, p, i32, f32, f32, p, p, p, p, p]
     lib.fmx_afm_pair_step.argtypes = [TP, HP, i32, AP, p, p, i32, f32, f32, p, i64, p, p, p, p, p]
     lib.fmx_afm_pair_step_opt.argtypes = [TP, HP, i32, AP, p, p, i32, f32, f32, p, i64, p, OP, p, p, p, p]

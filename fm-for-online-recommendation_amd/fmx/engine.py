@@ -409,6 +409,25 @@ class FMEngine:
                                         dz.data_ptr(), gbi.data_ptr(), self.loss_out.data_ptr(), self._stream()))
         return dz, gbi
 
+    def mlp_pair_fit(self, params, k, hidden, n_layers, hyper, rule, base, B_pairs, margin=0.0, inv_b=None, mlp_opt=None,
+                     want_logit=False):
+        """mlp_fit under the pair loss (fmx_mlp_pair_fit) on self.bi's first 2 B_pairs rows, row 2i the positive of pair i and
+        row 2i + 1 its negative; no labels.  -> (dz [2 B_pairs] with dz[2i + 1] = -dz[2i], gbi [2 B_pairs, kp], logit [2 B_pairs]
+        or None) for self.update(); the mean pair loss lands in self.loss_out[0]; the hidden layers in `params` are updated in
+        place under `rule`, or under mlp_opt's rule (an MlpOpt: `rule` and hyper are not read, mlp_opt.step advances by one)."""
+        B2 = 2 * int(B_pairs)
+        dz = torch.empty(B2, dtype=torch.float32, device=self.device)
+        gbi = torch.empty((B2, self.table.kp), dtype=torch.float32, device=self.device)
+        logit = torch.empty(B2, dtype=torch.float32, device=self.device) if want_logit else None
+        m = self._mlp_struct(params, k, hidden, n_layers)
+        _lib.check(self.lib.fmx_mlp_pair_fit(C.byref(m), hyper.ref(), _lib.RULES[rule], self.bi.data_ptr(), self.table.kp,
+                                             base.data_ptr(), int(B_pairs), float(margin), 1.0 / B_pairs if inv_b is None else inv_b,
+                                             _ptr(logit), dz.data_ptr(), gbi.data_ptr(), self.loss_out.data_ptr(),
+                                             None if mlp_opt is None else mlp_opt.ref(), self._stream()))
+        if mlp_opt is not None:
+            mlp_opt.step += 1
+        return dz, gbi, logit
+
     def mlp_hedge_fit(self, params, k, hidden, n_layers, lr, hedge_b, hedge_s, alpha, base, y_d, B):
         m = self._mlp_struct(params, k, hidden, n_layers)
         _lib.check(self.lib.fmx_mlp_hedge_fit(C.byref(m), lr, hedge_b, hedge_s, alpha.data_ptr(), self.bi.data_ptr(),
@@ -515,6 +534,33 @@ class FMEngine:
                                                idx_d.data_ptr(), _ptr(xv_d), y_d.data_ptr(), N, self.workspace.data_ptr(), self._ws_bytes(),
                                                C.byref(out), self._online_scratch.data_ptr(), pred.data_ptr(), self._stream()))
         return pred
+
+    def online_run_mlp_pair(self, hyper, rule, params, k, hidden, n_layers, fm_term, idx_d, xv_d=None, margin=0.0, mlp_opt=None,
+                            want_logit=False, want_loss=False):
+        """The online protocol on N device-resident pairs through the whole network of DeepFM / NFM (fmx_online_run_mlp_pair):
+        idx_d [2N, F], row 2i the positive of pair i and row 2i + 1 its negative; per pair predict (z_pos > z_neg), then one pair
+        step on that pair.  -> (pred uint8 [N], logit [2N] or None, loss [N] or None).  mlp_opt None: the network under `rule`
+        ('signadam' / 'sgd'); an MlpOpt: its rule, and the tables under any rule.  The call advances the table's step count (on
+        a moments table) and mlp_opt.step by N."""
+        N = self._n_pairs(idx_d)
+        self._ensure(2)
+        out = self._fwd_out(want_first=False, want_bi=True)
+        m = self._mlp_struct(params, k, hidden, n_layers)
+        pred = torch.empty(N, dtype=torch.uint8, device=self.device)
+        logit = torch.empty(2 * N, dtype=torch.float32, device=self.device) if want_logit else None
+        loss_b = torch.empty(N, dtype=torch.float32, device=self.device) if want_loss else None
+        if getattr(self, "_pair_online_scratch", None) is None:
+            self._pair_online_scratch = torch.zeros(2 * self.table.kp + 8, dtype=torch.float32, device=self.device)
+        self._steps(hyper)
+        _lib.check(self.lib.fmx_online_run_mlp_pair(self.table.c_struct(), hyper.ref(), _lib.RULES[rule], C.byref(m),
+                                                    1 if fm_term else 0, idx_d.data_ptr(), _ptr(xv_d), N, float(margin),
+                                                    self.workspace.data_ptr(), self._ws_bytes(), C.byref(out),
+                                                    self._pair_online_scratch.data_ptr(), pred.data_ptr(), _ptr(logit), _ptr(loss_b),
+                                                    None if mlp_opt is None else mlp_opt.ref(), self._stream()))
+        self._advance(N)
+        if mlp_opt is not None:
+            mlp_opt.step += N
+        return pred, logit, loss_b
 
     @staticmethod
     def online_run_fits(n_fields, kp):

@@ -830,6 +830,35 @@ class NetworkPairTraining:
     the whole network -- trains on the pair loss of the logit forward() returns (fmx_mlp_pair_section).  Listed in front of
     OnlineFMBase in the class's bases."""
 
+    # run_pair_experiment(full=True) on the device (fmx_online_run_mlp_pair) where _pair_device_loop_ok() says so.  Off by
+    # default: the host loop of section calls stays the class's own path; set it to True on an instance (or the class).
+    pair_loop_on_device = False
+
+    def _pair_device_loop_ok(self):
+        """Can run_pair_experiment(full=True)'s predict-then-fit loop run on the device for this model?  Under 'signadam' / 'sgd',
+        and under 'adam' / 'adagrad' with fused_optimizer=True (the hidden layers' flat moments; 'ftrl' and the torch optimizer
+        of fused_optimizer=False stay on the host loop), where the one-workgroup MLP step takes the network at two rows.
+        The device loop then follows fmx_mlp_pair_fit's arithmetic -- the one-workgroup kernel's summation order -- while the host
+        loop keeps fmx_mlp_pair_section at every batch size: the two differ at one pair in the order of fp32 summations only, so
+        a stream through either agrees to rounding, not bit for bit."""
+        rule = self.update_rule
+        if not (rule in ("signadam", "sgd") or (rule in ("adam", "adagrad") and getattr(self, "_mlp_fused", None) is not None)):
+            return False
+        return self._engine.mlp_fits(2, self.embedding_size, self.neuron_per_hidden_layer, self.num_hidden_layers, "fit")
+
+    def _run_pair_experiment_on_device(self, Xi, Xv, item_fields, negatives, n_neg, margin, candidates, generator):
+        """run_pair_experiment(full=True) as one call of fmx_online_run_mlp_pair: the per-pair sequence forward, fmx_mlp_pair_fit,
+        sort, update on the device (see _pair_device_loop_ok for its arithmetic against the host loop's)."""
+        start = time()
+        self.train()
+        rows, xv = self._pair_rows(Xi, Xv, item_fields, negatives, n_neg, candidates, generator)
+        if rows.shape[0] == 0:
+            return time() - start, 0.0, [], {"correct": 0, "wrong": 0}
+        pred, _, _ = self._engine.online_run_mlp_pair(self._hyper, self.update_rule, self._mlp_flat, self.embedding_size,
+                                                      self.neuron_per_hidden_layer, self.num_hidden_layers, self._fm_term_in_forward,
+                                                      rows, xv, margin=margin, mlp_opt=getattr(self, "_mlp_fused", None))
+        return self._pair_experiment_result(start, pred)
+
     def _pair_refusal_or_full(self, method, full):
         if full:
             return
@@ -846,6 +875,10 @@ class NetworkPairTraining:
 
     def run_pair_experiment(self, Xi, Xv, item_fields, negatives=None, n_neg=1, margin=0.0, candidates=None, generator=None, full=False):
         """OnlineFMBase.run_pair_experiment's arguments and 4-tuple; full=True: predict z_pos > z_neg through the whole network,
-        then fit_pairs(full=True) on that pair alone, pair by pair."""
+        then fit_pairs(full=True) on that pair alone, pair by pair -- the host loop of one-pair section calls, or, with the
+        attribute pair_loop_on_device set to True, one device call where _pair_device_loop_ok() says so (its docstring: which
+        models, and with which arithmetic)."""
         self._pair_refusal_or_full("run_pair_experiment", full)
+        if self.pair_loop_on_device and self._pair_device_loop_ok():
+            return self._run_pair_experiment_on_device(Xi, Xv, item_fields, negatives, n_neg, margin, candidates, generator)
         return self._run_pair_experiment_full(Xi, Xv, item_fields, negatives, n_neg, margin, candidates, generator)

@@ -614,6 +614,54 @@ int fmx_online_run_mlp_opt(const fmx_table_t *table, const fmx_hyper_t *hyper, i
                            void *workspace, int64_t workspace_bytes, const fmx_fwd_out_t *fwd, float *scratch, float *pred_out,
                            const fmx_mlp_opt_t *opt, fmx_stream_t stream);
 
+/* ---- the one-workgroup pair step and the online pair loop of DeepFM / NFM ----
+ * fmx_mlp_fit / fmx_mlp_fit_opt on 2 * B_pairs rows under the pair loss: row 2i is the positive of pair i, row 2i + 1 its
+ * negative, and no label is read.  z_b = base_b + sum_j x_L[b, j] summed as the pointwise modes sum it: logit_out [2 B_pairs]
+ * (may be null) has the bits fmx_mlp_forward writes for the same bi / base.  d_i = z[2i] - z[2i + 1], loss_i and g_i as stated at
+ * fmx_mlp_pair_section (one device function evaluates every pair family);
+ *   dz_out[2i] = g_i * inv_b, dz_out[2i + 1] = the same float negated (the two sum to exactly +0),
+ *   loss_out[0] (may be null) = inv_b * the ordered sum over the rows of loss_{2i} = loss_i, loss_{2i+1} = +0,
+ *   gbi_out [2 B_pairs, kp] as fmx_mlp_fit writes it (columns k..kp-1 zeroed).
+ * The backward pass and the parameter update are fmx_mlp_fit's: opt null -- `rule` (FMX_RULE_SIGNADAM / FMX_RULE_SGD) by hyper's
+ * lr / eps; opt given -- opt->rule as in fmx_mlp_fit_opt, this call being step opt->step + 1 (read, never written), and hyper and
+ * rule are not read.  dz_out, gbi_out, logit_out and loss_out do not depend on the rule.
+ * Limits: fmx_mlp_fit's on 2 * B_pairs rows -- 1 <= B_pairs <= 8, k <= 63, hidden <= 64, layers <= 8, else FMX_ERR_UNSUPPORTED.
+ * Before anything is launched: B_pairs < 1 and a negative / NaN / infinite margin are FMX_ERR_ARG, then fmx_mlp_fit's null
+ * checks and, with opt, what fmx_mlp_fit_opt refuses.
+ * Replaces: DeepFMAdam.fit / NFMAdam.fit minus the table part (reference deepfm_adam.py:106-119, nfm_adam.py:105-118) under the
+ * pair objective of reference models/models_meta_emb/meta_fm.py:145-169. */
+int fmx_mlp_pair_fit(const fmx_mlp_t *mlp, const fmx_hyper_t *hyper, int32_t rule, const float *bi, int32_t kp,
+                     const float *base, int32_t B_pairs, float margin, float inv_b, float *logit_out, float *dz_out,
+                     float *gbi_out, float *loss_out, const fmx_mlp_opt_t *opt, fmx_stream_t stream);
+
+/* The online predict-then-fit protocol on N device-resident pairs idx [2N, F] (xv [2N, F] or null) through the whole network
+ * of DeepFM (fm_term = 1) / NFM (fm_term = 0): for every pair, pred_out[i] = z_pos > z_neg, logit_out[2i], logit_out[2i + 1] (or
+ * null) and loss_out[i] (or null) with the weights BEFORE the pair's update, then one pair step on that pair alone.  The
+ * definition, bit for bit, is N times from outside: fmx_fm_forward(B = 2, FMX_LOSS_NONE), the NFM base add (sfirst + bias weight)
+ * when fm_term = 0, fmx_mlp_pair_fit(B_pairs = 1, inv_b = 1), fmx_sort_occurrences(B = 2), fmx_fm_update(B = 2, dz_first = dz,
+ * dz_bi = fm_term ? dz : null, gbi, inv_b = 1), the caller advancing hyper->step and opt->step -- rows (moments included), bias
+ * words, params, m, v, pred_out, logit_out and loss_out.  Pair i is step hyper->step + i + 1 of the tables and opt->step + i + 1
+ * of the network (both read, never written).
+ * opt null: the pairing of fmx_online_run_mlp's fit mode (FMX_RULE_SIGNADAM / FMX_RULE_SGD on a weights table, the network under
+ * the same rule); opt given: that of fmx_online_run_mlp_opt (any table rule, the network under opt->rule; fm_term = 0 on an FTRL
+ * table: FMX_ERR_UNSUPPORTED).  The bias gradient dz[0] + dz[1] is exactly +0: only FMX_RULE_ADAM moves the bias words.
+ * One workgroup walks the stream (k_online_mlp_pair: wave 0 holds both samples' rows, the parameters and the network's moments
+ * live in LDS, at most 96 KB beside the kernel's 47 KB of static arrays) when the network has at most 8,192 parameters,
+ * n_fields <= 4 * (64 / (kp / 4)) and the tables are not FTRL tables; otherwise, and with
+ * fmx_set_option("online_persistent", 0), the four launches of every pair are queued without any host synchronisation.
+ * Every argument is checked before the first launch, N = 0 included (which launches nothing; idx, xv and the three outputs may
+ * then be null): a null table / hyper / idx / pred_out, N < 0, 2 * N beyond int32, a bad margin: FMX_ERR_ARG; field_cols /
+ * field_base: FMX_ERR_UNSUPPORTED; then fmx_mlp_pair_fit's checks of mlp and opt (step + N within int32), the pairing of rule and
+ * layout, FMX_RULE_ADAM's hyper-parameters.  workspace: fmx_workspace_bytes(table, 2) bytes (smaller: FMX_ERR_SHAPE); fwd: S, bi,
+ * sfirst, logit of two samples, and fwd->error takes the index flag; scratch: >= 2 * kp + 8 floats (dz [2] at 0, gbi [2, kp]
+ * at 8), 16-byte aligned.
+ * Replaces: the loop body of run_experiment (reference deepfm_adam.py:128-130, nfm_adam.py:128-130) restated for the pair
+ * objective of reference meta_fm.py:145-169. */
+int fmx_online_run_mlp_pair(const fmx_table_t *table, const fmx_hyper_t *hyper, int32_t rule, const fmx_mlp_t *mlp,
+                            int32_t fm_term, const int32_t *idx, const float *xv, int32_t N, float margin, void *workspace,
+                            int64_t workspace_bytes, const fmx_fwd_out_t *fwd, float *scratch, uint8_t *pred_out,
+                            float *logit_out, float *loss_out, const fmx_mlp_opt_t *opt, fmx_stream_t stream);
+
 /* Hedge backprop at mini-batch sizes (the ONN classes' fit() beyond 16 samples; reference deepfm_onn.py:109-154): per
  * layer BCELoss(sigmoid(base + sum_j x_l[j]), y), hidden layers updated by lr * sum_{i >= j} alpha_i dloss_i/dlayer_j (one
  * backward pass on the same GEMMs; `grads` receives that gradient), then alpha_i <- max(alpha_i * hedge_b^loss_i,
