@@ -243,8 +243,10 @@ int afm_pair_steps_call(const char *who, const fmx_table_t *table, const fmx_hyp
   return FMX_OK;
 }
 
-// fmx_afm_pair_online_run: for every pair, fmx_afm_pair_step_opt(B_pairs = 1, inv_b = 1) -- its own forward gives the pair's logits
-// before its update -- queued without any host synchronisation (the form fmx_afm_online_run falls back to)
+// fmx_afm_pair_online_run.  Two forms, the same bits: k_afm_pair_online (fmx_afm_pair_online.hip), one workgroup walking the
+// stream, where afm_pair_online_buffers gives it tile buffers; otherwise, for every pair, fmx_afm_pair_step_opt(B_pairs = 1,
+// inv_b = 1) -- its own forward gives the pair's logits before its update -- queued without any host synchronisation (the form
+// fmx_afm_online_run falls back to)
 int afm_pair_online_call(const fmx_table_t *table, const fmx_hyper_t *hyper, int32_t rule, const fmx_afm_t *afm, const int32_t *idx,
                          const float *xv, int32_t N_pairs, float margin, void *workspace, int64_t workspace_bytes, float *attn_grad_out,
                          const fmx_mlp_opt_t *opt, float *logit_out, float *loss_out, int32_t *error, hipStream_t st) {
@@ -253,6 +255,10 @@ int afm_pair_online_call(const fmx_table_t *table, const fmx_hyper_t *hyper, int
   if (N_pairs < 0) return fail(FMX_ERR_ARG, "%s: N_pairs = %d must be >= 0", who, N_pairs);
   AfmWs w;
   if (int rc = check_afm_pair_step(table, hyper, rule, afm, 2, workspace, workspace_bytes, attn_grad_out, opt, true, N_pairs, w, who)) return rc;
+  if (N_pairs == 0) return FMX_OK;
+  bool mom = false;
+  if (const int nb = afm_pair_online_buffers(table->n_fields, afm->k, table->kp, afm->t, opt->rule, &mom))
+    return afm_pair_online_launch(table, hyper, rule, afm, idx, xv, N_pairs, margin, attn_grad_out, opt, logit_out, loss_out, error, nb, mom, st);
   const size_t F = (size_t)table->n_fields;
   fmx_hyper_t hs = hyper_for(hyper, rule);
   for (int i = 0; i < N_pairs; ++i, ++hs.step) {
@@ -262,4 +268,18 @@ int afm_pair_online_call(const fmx_table_t *table, const fmx_hyper_t *hyper, int
       return rc;
   }
   return FMX_OK;
+}
+
+// fmx_afm_pair_online_form: which of the two forms fmx_afm_pair_online_run takes at this shape -- the structs are read, nothing
+// is launched
+int afm_pair_online_form_call(const fmx_table_t *table, const fmx_afm_t *afm, int32_t attn_rule, int32_t *moments_in_lds) {
+  const char *who = "fmx_afm_pair_online_form";
+  if (int rc = check_afm(table, afm, who)) return rc;
+  if (attn_rule != FMX_RULE_SIGNADAM && attn_rule != FMX_RULE_SGD && attn_rule != FMX_RULE_ADAGRAD && attn_rule != FMX_RULE_ADAM)
+    return fail(FMX_ERR_ARG, "%s: the attention rule %d is not FMX_RULE_SIGNADAM, FMX_RULE_SGD, FMX_RULE_ADAGRAD or FMX_RULE_ADAM", who,
+                attn_rule);
+  bool mom = false;
+  const int nb = afm_pair_online_buffers(table->n_fields, afm->k, table->kp, afm->t, attn_rule, &mom);
+  if (moments_in_lds) *moments_in_lds = mom ? 1 : 0;
+  return nb;
 }

@@ -37,6 +37,7 @@ struct Tune {
                          // launch (k_fm_fixup) instead of the in-launch hand-off; both give identical bits
   int online_persistent = 1;  // FMX_ONLINE_PERSISTENT=0 / fmx_set_option("online_persistent", 0): fmx_online_run_mlp as per-sample launches
   int afm_online_persistent = 1;  // fmx_set_option("afm_online_persistent", 0): fmx_afm_online_run as per-sample launches (same bits)
+  int afm_pair_online_persistent = 1;  // fmx_set_option("afm_pair_online_persistent", 0): fmx_afm_pair_online_run as queued pair steps (same bits)
   int sort_ahead = 16;  // FMX_SORT_AHEAD: batches per side-stream sort launch in fmx_fm_stream (1..16)
   int mlp_chain = 1;          // FMX_MLP_CHAIN=0 / fmx_set_option("mlp_chain", 0): fmx_mlp_section as separate GEMM launches
                               // (forward x L, loss, dgrad x L) instead of k_mlp_chain; same results up to summation order

@@ -57,6 +57,13 @@ int update_impl(const fmx_table_t *table, const fmx_hyper_t *hyper, int32_t rule
 int update_occ_impl(const fmx_table_t *table, const fmx_hyper_t *hyper, int32_t rule, const Workspace &w, const float *xv,
                     const float *dz_first, const float *occ, int32_t ld_occ, int32_t B, const float *loss_b, float inv_b,
                     float *loss_out, hipStream_t st);
+// fmx_afm_pair_online.hip: the form fmx_afm_pair_online_run takes at this shape under this attention rule -- the tile buffers of
+// k_afm_pair_online, or 0 for the queued pair steps (the option "afm_pair_online_persistent" off, or not even min(2, tiles) buffers
+// fit beside a sample); *moments_in_lds (or null): whether the attention moments stay in LDS.  Then the launch in that form
+int afm_pair_online_buffers(int F, int k, int kp, int t, int attn_rule, bool *moments_in_lds);
+int afm_pair_online_launch(const fmx_table_t *table, const fmx_hyper_t *hyper, int32_t rule, const fmx_afm_t *afm, const int32_t *idx,
+                           const float *xv, int32_t N_pairs, float margin, float *attn_grad_out, const fmx_mlp_opt_t *opt,
+                           float *logit_out, float *loss_out, int32_t *error, int nb, bool moments_in_lds, hipStream_t st);
 
 }  // namespace fmxd
 

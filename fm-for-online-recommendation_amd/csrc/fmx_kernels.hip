@@ -1005,6 +1005,7 @@ int fmx_set_option(const char *name, int value) {
   else if (!strcmp(name, "sort_ahead")) slot = &t.sort_ahead;
   else if (!strcmp(name, "online_persistent")) slot = &t.online_persistent;
   else if (!strcmp(name, "afm_online_persistent")) slot = &t.afm_online_persistent;
+  else if (!strcmp(name, "afm_pair_online_persistent")) slot = &t.afm_pair_online_persistent;
   else if (!strcmp(name, "sort_chunked")) slot = &t.sort_chunked;
   else if (!strcmp(name, "mlp_chain")) slot = &t.mlp_chain;
   else return fail(FMX_ERR_ARG, "fmx_set_option: unknown option '%s'", name);

@@ -31,7 +31,8 @@ EXPORTS = ["fmx_version", "fmx_last_error_string", "fmx_set_option", "fmx_sorted
            "fmx_afm_rank_workspace_bytes", "fmx_afm_rank",
            "fmx_fm_pair_forward", "fmx_fm_pair_step", "fmx_fm_pair_stream", "fmx_fm_pair_online_run",
            "fmx_mlp_pair_section", "fmx_deepfm_pair_stream", "fmx_mlp_pair_fit", "fmx_online_run_mlp_pair",
-           "fmx_afm_pair_forward", "fmx_afm_pair_step", "fmx_afm_pair_step_opt", "fmx_afm_pair_stream", "fmx_afm_pair_online_run"]
+           "fmx_afm_pair_forward", "fmx_afm_pair_step", "fmx_afm_pair_step_opt", "fmx_afm_pair_stream", "fmx_afm_pair_online_run",
+           "fmx_afm_pair_online_form"]
 
 
 I64_RETURNS = ("fmx_workspace_bytes", "fmx_mlp_section_workspace_bytes", "fmx_fm_topk_workspace_bytes",
@@ -176,6 +177,7 @@ def load():
     lib.fmx_afm_pair_step_opt.argtypes = [TP, HP, i32, AP, p, p, i32, f32, f32, p, i64, p, OP, p, p, p, p]
     lib.fmx_afm_pair_stream.argtypes = [TP, HP, i32, AP, p, p, i32, i32, f32, f32, i32, p, i64, p, OP, p, p, p]
     lib.fmx_afm_pair_online_run.argtypes = [TP, HP, i32, AP, p, p, i32, f32, p, i64, p, OP, p, p, p, p]
+    lib.fmx_afm_pair_online_form.argtypes = [TP, AP, i32, C.POINTER(C.c_int32)]
     for name in EXPORTS:
         fn = getattr(lib, name)
         if name in I64_RETURNS:

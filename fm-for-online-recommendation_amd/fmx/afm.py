@@ -214,3 +214,13 @@ class AFMEngine:
         opt.step += N
         if self.table.layout == "moments":
             self.table.step += N
+
+    def pair_online_form(self, attn_rule):
+        """-> (tile buffers, moments in LDS) of the form pair_online_run takes for this table under the attention rule
+        `attn_rule` (a name of AfmOpt.RULES): tile buffers > 0 is the one-workgroup kernel, 0 the queued pair steps
+        (fmx_afm_pair_online_form; no device call)."""
+        mom = C.c_int32(0)
+        nb = self.lib.fmx_afm_pair_online_form(self.table.c_struct(), C.byref(self.c_afm), _lib.RULES[attn_rule], C.byref(mom))
+        if nb < 0:
+            _lib.check(nb)
+        return nb, bool(mom.value)

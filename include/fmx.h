@@ -977,13 +977,25 @@ int fmx_afm_pair_stream(const fmx_table_t *table, const fmx_hyper_t *hyper, int3
  * i being step hyper->step + i + 1 of the tables and opt->step + i + 1 of the attention parameters (both read, never written).
  * logit_out [2 N_pairs] or null: each pair's two logits BEFORE its update (the prediction is logit[2i] > logit[2i + 1]); loss_out
  * [N_pairs] or null: each pair's loss.  workspace: fmx_afm_workspace_bytes(table, afm, 2) bytes.  N_pairs < 0: FMX_ERR_ARG;
- * N_pairs = 0 launches nothing and returns 0.  The pairs' launches are queued without any host synchronisation (the form
- * fmx_afm_online_run takes when its one-workgroup kernel does not fit); the contract leaves room for a one-workgroup form.
+ * N_pairs = 0 launches nothing and returns 0.  Two forms, the same bits: one workgroup of 8 waves walks the stream with the
+ * attention parameters resident in LDS (k_afm_pair_online, as fmx_afm_online_run's kernel) wherever at least min(2, tiles) tile
+ * buffers fit beside a sample; otherwise, or under fmx_set_option("afm_pair_online_persistent", 0), the pairs' launches are queued
+ * without any host synchronisation.  fmx_afm_pair_online_form says which form a shape takes.
  * Replaces: the protocol of reference fm_adam.py:90-119 under the pair objective of meta_fm.py:145-169, for the AFM. */
 int fmx_afm_pair_online_run(const fmx_table_t *table, const fmx_hyper_t *hyper, int32_t rule, const fmx_afm_t *afm, const int32_t *idx,
                             const float *xv, int32_t N_pairs, float margin, void *workspace, int64_t workspace_bytes,
                             float *attn_grad_out, const fmx_mlp_opt_t *opt, float *logit_out, float *loss_out, int32_t *error,
                             fmx_stream_t stream);
+
+/* Which form fmx_afm_pair_online_run takes for this table and these attention parameters under the attention rule attn_rule
+ * (FMX_RULE_SIGNADAM, FMX_RULE_SGD, FMX_RULE_ADAGRAD or FMX_RULE_ADAM; another: FMX_ERR_ARG): the number of tile buffers of the
+ * one-workgroup kernel (> 0), or 0 for the queued pair steps (the shape leaves no room, or the option
+ * "afm_pair_online_persistent" is 0).  moments_in_lds (or null) receives 1 when the attention moments stay in LDS for the call,
+ * 0 when they stay in global memory or the rule has none.  The structs' shapes are read; no pointer in them is dereferenced and
+ * no device call is made.  The table and the attention parameters are refused as fmx_afm_pair_online_run refuses them.
+ * Replaces: nothing in the reference.  Restates: the dispatch of fmx_afm_pair_online_run, for callers and tests that must know
+ * which kernel a result came from. */
+int fmx_afm_pair_online_form(const fmx_table_t *table, const fmx_afm_t *afm, int32_t attn_rule, int32_t *moments_in_lds);
 
 /* ---- top-K recommendation under the AFM (fmx/recommend.py, AFMAdam.recommend) ----
  * Split the fields into context fields C and item fields I (at least one of each).  A combined sample's pairs are the C x C
