@@ -72,6 +72,26 @@ __device__ __forceinline__ float key_score(uint64_t k) {
 }
 __device__ __forceinline__ int key_pos(uint64_t k) { return (int)(0xFFFFFFFFu - (uint32_t)k); }
 
+// The FM score of a pair (include/fmx.h, fmx_fm_topk), stated once for the scan and for fmx_fm_mine_negatives:
+//   score(u, c) = (au[u] + ac[c]) + dot,   dot = fma(Su[kp-1], Sc[kp-1], ... fma(Su[1], Sc[1], Su[0] * Sc[0]))
+// su, au[u]: the user's row and its a_u (wave-uniform in both callers: scalar loads), v: the candidate's row in the lane's registers.
+template <int KP>
+__device__ __forceinline__ float fm_score(const float4 *su, const float *au, int u, const float4 (&v)[KP / 4], float acv) {
+  float acc = su[0].x * v[0].x;
+  acc = fmaf(su[0].y, v[0].y, acc);
+  acc = fmaf(su[0].z, v[0].z, acc);
+  acc = fmaf(su[0].w, v[0].w, acc);
+#pragma unroll
+  for (int q = 1; q < KP / 4; ++q) {
+    const float4 sq = su[q];
+    acc = fmaf(sq.x, v[q].x, acc);
+    acc = fmaf(sq.y, v[q].y, acc);
+    acc = fmaf(sq.z, v[q].z, acc);
+    acc = fmaf(sq.w, v[q].w, acc);
+  }
+  return (au[u] + acv) + acc;
+}
+
 struct Slots {  // LDS: keys [n][cap], count [n], threshold [n]
   uint64_t *buf;
   uint64_t *thr;
@@ -178,12 +198,13 @@ __device__ void init_slots(Slots &s, uint64_t *lds, int n, int cap) {
 }  // namespace
 
 #include "fmx_rank.inc"
+#include "fmx_mine.inc"
 
 namespace {
 
 // grid (user tiles, splits).  Thread t scores candidate c0 + t against every user of the tile; the user's S_u and a_u are
 // wave-uniform (scalar loads), the candidate's S_c row sits in the thread's registers for the whole chunk.
-//   score(u, c) = (au[u] + ac[c]) + dot,   dot = fma(Su[kp-1], Sc[kp-1], ... fma(Su[1], Sc[1], Su[0] * Sc[0]))
+// The score is fm_score above.
 // MODE (fmx_rank.inc): the top-K selection (Args = TopkArgs), or one of the rank call's two phases (Args = FmRankArgs; ut = 1
 // and grid (U, T) for SCAN_KEYS).
 template <int KP, int MODE = SCAN_TOPK, class Args = TopkArgs>
@@ -224,19 +245,7 @@ __global__ __launch_bounds__(TK_THREADS) void k_topk_scan(Args a) {
       for (int r = 0; r < R; ++r) {
         const int u = u0 + min(j0 + r, nu - 1);
         const float4 *su = reinterpret_cast<const float4 *>(Su + (size_t)u * a.ld_u);
-        float acc = su[0].x * v[0].x;
-        acc = fmaf(su[0].y, v[0].y, acc);
-        acc = fmaf(su[0].z, v[0].z, acc);
-        acc = fmaf(su[0].w, v[0].w, acc);
-#pragma unroll
-        for (int q = 1; q < KP / 4; ++q) {
-          const float4 sq = su[q];
-          acc = fmaf(sq.x, v[q].x, acc);
-          acc = fmaf(sq.y, v[q].y, acc);
-          acc = fmaf(sq.z, v[q].z, acc);
-          acc = fmaf(sq.w, v[q].w, acc);
-        }
-        score[r] = (au[u] + acv) + acc;
+        score[r] = fm_score<KP>(su, au, u, v, acv);
       }
 #pragma unroll
       for (int r = 0; r < R; ++r) {

@@ -32,7 +32,7 @@ EXPORTS = ["fmx_version", "fmx_last_error_string", "fmx_set_option", "fmx_sorted
            "fmx_fm_pair_forward", "fmx_fm_pair_step", "fmx_fm_pair_stream", "fmx_fm_pair_online_run",
            "fmx_mlp_pair_section", "fmx_deepfm_pair_stream", "fmx_mlp_pair_fit", "fmx_online_run_mlp_pair",
            "fmx_afm_pair_forward", "fmx_afm_pair_step", "fmx_afm_pair_step_opt", "fmx_afm_pair_stream", "fmx_afm_pair_online_run",
-           "fmx_afm_pair_online_form"]
+           "fmx_afm_pair_online_form", "fmx_fm_mine_negatives"]
 
 
 I64_RETURNS = ("fmx_workspace_bytes", "fmx_mlp_section_workspace_bytes", "fmx_fm_topk_workspace_bytes",
@@ -178,6 +178,8 @@ def load():
     lib.fmx_afm_pair_stream.argtypes = [TP, HP, i32, AP, p, p, i32, i32, f32, f32, i32, p, i64, p, OP, p, p, p]
     lib.fmx_afm_pair_online_run.argtypes = [TP, HP, i32, AP, p, p, i32, f32, p, i64, p, OP, p, p, p, p]
     lib.fmx_afm_pair_online_form.argtypes = [TP, AP, i32, C.POINTER(C.c_int32)]
+    lib.fmx_fm_mine_negatives.argtypes = [p, i32, p, i32, p, i32, p, i32, i32, p, p, p, i32, i32, C.c_uint64, C.c_uint64, C.c_uint32,
+                                          p, p, p]
     for name in EXPORTS:
         fn = getattr(lib, name)
         if name in I64_RETURNS:

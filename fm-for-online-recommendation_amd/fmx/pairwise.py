@@ -3,8 +3,14 @@
 A batch of B pairs is [2B, F] full-width rows, row 2i the positive sample of pair i and row 2i + 1 its negative: the
 positive's row with the item columns replaced.  sample_negatives draws the replacements, assemble_pairs interleaves the rows;
 FMEngine.pair_step / pair_stream / pair_online_run take the result.
+
+Hard negatives (dynamic negative sampling; Zhang et al. 2013, Rendle & Freudenthaler 2014): mine_negatives draws n_draw
+candidates per positive on the device, scores them under the current FM and keeps the n_neg best (fmx_fm_mine_negatives).
+HardNegatives carries the settings of that through the `negatives` argument of fit_pairs / run_pair_experiment.
 """
 import torch
+
+from . import _lib
 
 
 def _item_fields(item_fields):
@@ -102,3 +108,74 @@ def sample_negatives(pos_idx, item_fields, sizes_or_candidates, n_neg=1, generat
             break
         out[again] = draw(n)
     return out.to(dev)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# hard negatives: the best of n_draw drawn candidates under the current FM (include/fmx.h, fmx_fm_mine_negatives)
+# ---------------------------------------------------------------------------------------------------------------------------
+MINE_MAX_DRAW, MINE_MAX_NEG = 1024, 16      # the kernel's limits
+
+
+class HardNegatives:
+    """negatives=HardNegatives(...) of fit_pairs / run_pair_experiment: mine every positive's negatives under the current FM
+    score instead of drawing them uniformly.  n_draw: candidates drawn per positive (<= 1024); exclude: per-row candidate
+    positions never to return (see fmx.recommend.exclusions_csr); refresh_every: the candidates' sums are recomputed from the
+    table every that many mining calls (1: always the current model's); remine_every (run_pair_experiment only): the stream
+    is mined in blocks of that many positives, the candidates refreshed before each (None: once, up front).
+    negatives="hard" stands for HardNegatives()."""
+
+    def __init__(self, n_draw=32, exclude=None, refresh_every=1, remine_every=None):
+        self.n_draw, self.exclude = int(n_draw), exclude
+        self.refresh_every = int(refresh_every)
+        self.remine_every = None if remine_every is None else int(remine_every)
+        if self.n_draw < 1 or self.refresh_every < 1 or (self.remine_every is not None and self.remine_every < 1):
+            raise ValueError("HardNegatives: n_draw, refresh_every and remine_every must be >= 1")
+
+
+def hard_negatives(negatives):
+    """The HardNegatives behind a `negatives` argument ("hard": the defaults), or None for every other value."""
+    if isinstance(negatives, HardNegatives):
+        return negatives
+    if isinstance(negatives, str):
+        if negatives != "hard":
+            raise ValueError(f"negatives={negatives!r}: None (uniform), 'hard', a HardNegatives, or the negatives' item columns")
+        return HardNegatives()
+    return None
+
+
+def fm_mine_negatives(Su, au, Sc, ac, n_draw, n_neg=1, own_pos=None, seed=0, offset=0, u_base=0, excl_offsets=None, excl_pos=None,
+                      out=None, stream=None, kp=None):
+    """The raw call of fmx_fm_mine_negatives: Su [U, >= kp], au [U], Sc [N, >= kp], ac [N] as fmx.recommend.fm_topk takes them;
+    own_pos int32 [U] on the device or None.  Returns (neg_pos int32 [U, n_neg], neg_score fp32 [U, n_neg]) on the device."""
+    U, N = Su.shape[0], Sc.shape[0]
+    kp = Sc.shape[1] if kp is None else int(kp)
+    n_neg = int(n_neg)
+    if own_pos is not None and (own_pos.dtype != torch.int32 or own_pos.numel() != U or not own_pos.is_contiguous()):
+        raise ValueError(f"own_pos: a contiguous int32 [U = {U}] device tensor")
+    if out is None:
+        shape = (U, max(n_neg, 0))
+        out = (torch.empty(shape, dtype=torch.int32, device=Su.device), torch.empty(shape, dtype=torch.float32, device=Su.device))
+    st = stream if stream is not None else torch.cuda.current_stream(Su.device).cuda_stream
+
+    def ptr(t):
+        return None if t is None else t.data_ptr()
+
+    _lib.check(_lib.load().fmx_fm_mine_negatives(Su.data_ptr(), Su.stride(0), au.data_ptr(), U, Sc.data_ptr(), Sc.stride(0),
+                                                 ac.data_ptr(), N, kp, ptr(excl_offsets), ptr(excl_pos), ptr(own_pos), int(n_draw),
+                                                 n_neg, int(seed) & (2 ** 64 - 1), int(offset) & (2 ** 64 - 1),
+                                                 int(u_base) & 0xFFFFFFFF, out[0].data_ptr(), out[1].data_ptr(), st))
+    return out
+
+
+def mine_negatives(table, cand, ctx_idx, ctx_xv, own_pos, n_draw, n_neg=1, seed=0, offset=0, u_base=0, exclude=None, hyper=None):
+    """Hard negatives for every context row of ctx_idx / ctx_xv ([B, F] full width, the item columns ignored): n_draw positions
+    of `cand` (a fmx.recommend.Candidates) drawn per row -- Philox4x32-10 under (seed, offset, u_base + row), see include/fmx.h
+    -- scored as logit(u + c) = a_u + a_c + <S_u, S_c>, and the n_neg best kept that are neither the row's own_pos (int [B] or
+    None; -1: none) nor excluded (exclude: see fmx.recommend.exclusions_csr).  One forward launch for the context side
+    (side_sums over the non-item fields) and one mining launch.  Returns device tensors (neg_pos int32 [B, n_neg], -1 padded;
+    neg_score fp32 [B, n_neg], -inf padded), each row by score descending, then position ascending."""
+    from . import recommend
+    (Su, au), off, pos = recommend._context_side(table, cand, ctx_idx, ctx_xv, exclude, hyper, recommend.side_sums)
+    if own_pos is not None:
+        own_pos = torch.as_tensor(own_pos).to(device=table.device, dtype=torch.int32).reshape(-1).contiguous()
+    return fm_mine_negatives(Su, au, cand.Sc, cand.ac, n_draw, n_neg, own_pos, seed, offset, u_base, off, pos)

@@ -144,6 +144,66 @@ class Candidates:
         self.Sc, self.ac = side_sums(self.table, self.idx, self.xv, self.item_fields, self.hyper, want_bias=False)
         return self
 
+    @classmethod
+    def whole_field(cls, table, field, hyper=None):
+        """Every row of one item field as the candidates: a position is the field's local index."""
+        n = table.feature_sizes[int(field)]
+        idx = torch.zeros((n, table.n_fields), dtype=torch.int32, device=table.device)
+        idx[:, int(field)] = torch.arange(n, dtype=torch.int32, device=table.device)
+        self = cls(table, [int(field)], idx, None, hyper=hyper)
+        self._identity = True
+        return self
+
+    def positions_of(self, items, item_fields=None):
+        """The candidate position of each item of items [B, m] ([B] with one item field), or -1 where the item is not a
+        candidate -> int32 [B] on the device.  Columns in the order of item_fields (default: the candidates' ascending item
+        fields).  An item listed at several positions gives the lowest.  The inverse index is built once per candidate set, in
+        torch: one item field, a lookup table over the field's vocabulary; several, the rows' mixed-radix int64 keys sorted for
+        searchsorted.  The candidates of whole_field need none: the position is the index."""
+        dev = self.table.device
+        fields = self.item_fields if item_fields is None else [int(f) for f in item_fields]
+        if sorted(fields) != self.item_fields:
+            raise ValueError(f"item_fields {fields}: these candidates hold the fields {self.item_fields}")
+        m = len(fields)
+        it = torch.as_tensor(items).to(device=dev, dtype=torch.int64).reshape(-1, m)
+        it = it[:, [fields.index(f) for f in self.item_fields]]              # columns in ascending field order
+        sizes = [self.table.feature_sizes[f] for f in self.item_fields]
+        inside = torch.ones(it.shape[0], dtype=torch.bool, device=dev)
+        for j, n in enumerate(sizes):
+            inside &= (it[:, j] >= 0) & (it[:, j] < n)
+        none = torch.full((it.shape[0],), -1, dtype=torch.int64, device=dev)
+        if getattr(self, "_identity", False):
+            return torch.where(inside, it[:, 0], none).to(torch.int32)
+        inv = getattr(self, "_inverse", None)
+        if inv is None:
+            rows = self.idx[:, self.item_fields].to(torch.int64)
+            where = torch.arange(self.N, dtype=torch.int64, device=dev)
+            if m == 1:
+                lut = torch.full((sizes[0],), self.N, dtype=torch.int64, device=dev)
+                ok = (rows[:, 0] >= 0) & (rows[:, 0] < sizes[0])
+                lut.scatter_reduce_(0, rows[ok, 0], where[ok], reduce="amin")
+                inv = (torch.where(lut == self.N, torch.full_like(lut, -1), lut),)
+            else:
+                keys, order = torch.sort(self._radix_key(rows, sizes), stable=True)
+                inv = (keys, where[order])
+            self._inverse = inv
+        it = torch.where(inside[:, None], it, torch.zeros_like(it))
+        if m == 1:
+            found = inv[0][it[:, 0]]
+        else:
+            keys, where = inv
+            key = self._radix_key(it, sizes)
+            at = torch.searchsorted(keys, key).clamp(max=self.N - 1)
+            found = torch.where(keys[at] == key, where[at], none)
+        return torch.where(inside, found, none).to(torch.int32)
+
+    @staticmethod
+    def _radix_key(rows, sizes):
+        key = rows[:, 0].clone()
+        for j in range(1, len(sizes)):
+            key = key * sizes[j] + rows[:, j]
+        return key
+
 
 class NetworkCandidates(Candidates):
     """The candidate side for the DeepFM / NFM classes: Sc [N, kp], Bc [N, kp] (bi) and ac [N] (fm_term = 1: sfirst + sbi,

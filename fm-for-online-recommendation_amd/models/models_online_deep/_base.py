@@ -269,7 +269,8 @@ class OnlineFMBase(nn.Module):
                              num_classes=self.num_classes, update_rule=self.update_rule, ftrl=dict(self._ftrl),
                              adam=dict(self._adam), adagrad=dict(self._adagrad), fused_optimizer=self.fused_optimizer),
                 "cls": self._name, "state_dict": {k: v.cpu() for k, v in self.state_dict().items()},
-                "ftrl_state": self.ftrl_state_dict(), "optimizer_state": self.optimizer_state_dict()}
+                "ftrl_state": self.ftrl_state_dict(), "optimizer_state": self.optimizer_state_dict(),
+                "mining": {"seed": int(self.mining_seed), "offset": int(getattr(self, "_mining_offset", 0))}}
 
     def __setstate__(self, state):
         ctor = state["ctor"]
@@ -284,6 +285,10 @@ class OnlineFMBase(nn.Module):
             self.load_ftrl_state_dict(state["ftrl_state"])
         if state.get("optimizer_state") is not None:
             self.load_optimizer_state_dict(state["optimizer_state"])
+        mining = state.get("mining") or {}
+        self._mining_offset = int(mining.get("offset", 0))
+        if mining.get("seed", 0) != type(self).mining_seed:
+            self.mining_seed = int(mining["seed"])
 
     # ------------------------------------------------------------------------------------------------------
     # forward pieces (reference deepfm_adam.py:46-89)
@@ -539,6 +544,13 @@ class OnlineFMBase(nn.Module):
     # pairwise-ranking (BPR) training of the pure FM (fmx/pairwise.py, fmx_fm_pair_*): for a context, score the observed item
     # above a sampled one -- loss -log(sigmoid(z_pos - z_neg) + margin), margin 0 being BPR
     # ------------------------------------------------------------------------------------------------------
+    def _refuse_hard_negatives(self, method, negatives):
+        """The classes and modes fmx_fm_mine_negatives does not score for: negatives='hard' there is refused by name."""
+        if fmx.pairwise.hard_negatives(negatives) is not None:
+            raise NotImplementedError(f"{self._name}.{method}: negatives='hard' mines under the pure FM score (FMAdam; "
+                                      "fmx_fm_mine_negatives); mining under the whole network's score or the attentional score "
+                                      "needs the scan of fmx_mlp_topk / fmx_afm_topk fed by draws")
+
     def _pair_refusal(self, method):
         if self._has_mlp:
             raise NotImplementedError(f"{self._name}.{method}: the pair loss is built for the pure FM logit (FMAdam); the "
@@ -548,6 +560,10 @@ class OnlineFMBase(nn.Module):
         """-> (rows int32 [2P, F], xv [2P, F] or None) on the device: P = B * n_neg pairs, row 2p the positive, 2p + 1 the negative"""
         idx_d, xv_d, _ = self._inputs(Xi, Xv)
         fields = [int(f) for f in (item_fields if hasattr(item_fields, "__len__") else [item_fields])]
+        hard = fmx.pairwise.hard_negatives(negatives)
+        if hard is not None:
+            negatives, _ = self.mine_negatives(idx_d, xv_d, fields, hard.n_draw, n_neg=n_neg, candidates=candidates,
+                                               exclude=hard.exclude, generator=generator, refresh_every=hard.refresh_every)
         if negatives is None:
             src = candidates if candidates is not None else [self.feature_sizes[f] for f in fields]
             negatives = fmx.pairwise.sample_negatives(idx_d, fields, src, n_neg=n_neg, generator=generator)
@@ -559,7 +575,11 @@ class OnlineFMBase(nn.Module):
         update_embedding does.  Xi / Xv: the positive samples [B, F] (Xv may be None: all ones).  negatives: the item columns of
         every positive's negatives, [B, n_neg, m] for m item fields ([B, m]: one each); None draws n_neg per positive uniformly
         (fmx.pairwise.sample_negatives) from `candidates` ([N, m] items) or, by default, from the item fields' vocabularies --
-        never the row's own item, deterministic under a seeded `generator`."""
+        never the row's own item, deterministic under a seeded `generator`.
+        negatives="hard" (or a fmx.pairwise.HardNegatives carrying n_draw = 32, exclude, refresh_every = 1): every positive's
+        n_neg negatives are mined by mine_negatives -- the best of n_draw drawn candidates under the current FM score."""
+        if self._has_mlp:
+            self._refuse_hard_negatives("fit_pairs", negatives)
         self._pair_refusal("fit_pairs")
         self.train()
         rows, xv = self._pair_rows(Xi, Xv, item_fields, negatives, n_neg, candidates, generator)
@@ -572,14 +592,49 @@ class OnlineFMBase(nn.Module):
         """The online protocol restated for pairs: for every pair predict (z_pos > z_neg), then fit on that pair alone ->
         (seconds, pairwise accuracy in %, the accuracy at every pair i with i % 1000 == 0 and at the last, {"correct", "wrong"}).
         On the device (fmx_fm_pair_online_run: one wavefront walks the stream) where run_experiment's loop runs there; otherwise
-        a loop over fit_pairs on one pair at a time -- the same bits."""
+        a loop over fit_pairs on one pair at a time -- the same bits.
+        negatives="hard" (or a fmx.pairwise.HardNegatives): the stream is mined in blocks of remine_every positives (None: once,
+        up front), the candidates refreshed before each block, and the loop above runs on the block."""
+        if self._has_mlp:
+            self._refuse_hard_negatives("run_pair_experiment", negatives)
         self._pair_refusal("run_pair_experiment")
         start = time()
         self.train()
+        hard = fmx.pairwise.hard_negatives(negatives)
+        if hard is not None:
+            return self._run_pair_experiment_hard(start, Xi, Xv, item_fields, hard, n_neg, margin, candidates, generator)
         rows, xv = self._pair_rows(Xi, Xv, item_fields, negatives, n_neg, candidates, generator)
+        pred = self._pair_loop(rows, xv, item_fields, margin)
+        if pred is None:
+            return time() - start, 0.0, [], {"correct": 0, "wrong": 0}
+        return self._pair_experiment_result(start, pred)
+
+    def _run_pair_experiment_hard(self, start, Xi, Xv, item_fields, hard, n_neg, margin, candidates, generator):
+        """run_pair_experiment under mined negatives: blocks of remine_every positives, each mined under the model the blocks
+        before it have trained (refresh_every = 1 per block), then walked by the same loop."""
+        idx_d, xv_d, _ = self._inputs(Xi, Xv)
+        B = idx_d.shape[0]
+        step = B if hard.remine_every is None else hard.remine_every
+        block = fmx.pairwise.HardNegatives(hard.n_draw, None, 1)
+        excl = fmx.recommend.exclusions_csr(hard.exclude, B, "cpu")
+        preds = []
+        for b0 in range(0, B, max(step, 1)):
+            b1 = min(B, b0 + step)
+            if excl[0] is not None:
+                off, pos = excl
+                block.exclude = (off[b0:b1 + 1] - off[b0], pos[int(off[b0]):int(off[b1])])
+            rows, xv = self._pair_rows(idx_d[b0:b1], None if xv_d is None else xv_d[b0:b1], item_fields, block, n_neg, candidates,
+                                       generator)
+            preds.append(self._pair_loop(rows, xv, item_fields, margin))
+        if not preds:
+            return time() - start, 0.0, [], {"correct": 0, "wrong": 0}
+        return self._pair_experiment_result(start, torch.cat(preds))
+
+    def _pair_loop(self, rows, xv, item_fields, margin):
+        """The predict-then-fit loop over assembled pair rows -> the per-pair predictions uint8 [n] on the device (None: no pair)"""
         n, e = rows.shape[0] // 2, self._engine
         if n == 0:
-            return time() - start, 0.0, [], {"correct": 0, "wrong": 0}
+            return None
         if self._device_loop_ok():
             pred, _, _ = e.pair_online_run(self._hyper, self.update_rule, rows, xv, margin=margin)
         else:
@@ -593,7 +648,64 @@ class OnlineFMBase(nn.Module):
                     pred[i] = e.logit[0] > e.logit[1]            # the step's own forward: the logits before its update
             finally:
                 self.strict_index_check = strict
-        return self._pair_experiment_result(start, pred)
+        return pred
+
+    # ---- hard negatives (fmx.pairwise.mine_negatives, fmx_fm_mine_negatives) ----
+    mining_seed = 0      # the Philox seed of mine_negatives when no generator is given
+
+    def _mining_candidates(self, fields, candidates, refresh_every):
+        """The fmx.recommend.Candidates of the last (item_fields, candidates), kept on the model and refreshed from the table
+        every refresh_every mining calls.  They carry value 1 in the item columns."""
+        kept = getattr(self, "_mining_kept", None)
+        if kept is None or kept["fields"] != fields or kept["source"] is not candidates:
+            rec = fmx.recommend
+            if candidates is None:
+                if len(fields) != 1:
+                    raise ValueError("candidates=None needs exactly one item field: the product of several fields' vocabularies "
+                                     "cannot be enumerated -- pass the candidate items [N, m]")
+                cands = rec.Candidates.whole_field(self._table, fields[0], hyper=self._hyper)
+            else:
+                items = torch.as_tensor(candidates).to(device=self.device, dtype=torch.int32).reshape(-1, len(fields))
+                cand_idx = torch.zeros((items.shape[0], self.field_size), dtype=torch.int32, device=self.device)
+                cand_idx[:, fields] = items
+                cands = rec.Candidates(self._table, fields, cand_idx, None, hyper=self._hyper)
+            self._mining_kept = kept = {"fields": list(fields), "source": candidates, "cands": cands, "age": 0}
+        elif kept["age"] >= int(refresh_every):
+            kept["cands"].refresh()
+            kept["age"] = 0
+        kept["age"] += 1
+        return kept["cands"]
+
+    def mine_negatives(self, Xi, Xv, item_fields, n_draw, n_neg=1, candidates=None, exclude=None, generator=None, refresh_every=1):
+        """Hard negatives for every positive row (fmx.pairwise.mine_negatives): n_draw candidates drawn per row, scored under the
+        current FM, the n_neg best kept that are neither the row's own item nor excluded -> (items int64 [B, n_neg, m] in the
+        order of item_fields, scores fp32 [B, n_neg]) on the device, what fit_pairs takes as negatives.  candidates: [N, m]
+        items (None: every row of the one item field); exclude: per-row candidate positions (fmx.recommend.exclusions_csr).
+        The candidates are scored with value 1 in the item columns: a positive whose item Xv is not 1 is mined under that
+        approximation.  The draws are Philox4x32-10 under seed = generator.initial_seed() (no generator: the attribute
+        mining_seed) and offset = the model's count of mining calls, which pickling carries: the same model state, seed and
+        call number give the same negatives.  A row with fewer than n_neg eligible draws repeats its best one; a row with none
+        at all raises ValueError (one host read per call)."""
+        if self._has_mlp:
+            self._refuse_hard_negatives("mine_negatives", "hard")
+        idx_d, xv_d, _ = self._inputs(Xi, Xv)
+        fields = [int(f) for f in (item_fields if hasattr(item_fields, "__len__") else [item_fields])]
+        cands = self._mining_candidates(fields, candidates, refresh_every)
+        own = cands.positions_of(idx_d[:, fields], fields)
+        seed = int(generator.initial_seed()) if generator is not None else int(self.mining_seed)
+        offset = int(getattr(self, "_mining_offset", 0))
+        self._mining_offset = offset + 1
+        pos, score = fmx.pairwise.mine_negatives(self._table, cands, idx_d, xv_d, own, int(n_draw), int(n_neg), seed=seed,
+                                                 offset=offset, exclude=exclude, hyper=self._hyper)
+        missing = pos < 0
+        if bool(missing[:, 0].any()):
+            raise ValueError(f"{self._name}.mine_negatives: a row has no eligible candidate among its {int(n_draw)} draws "
+                             "(every draw was its own item, excluded or scored NaN)")
+        pos = torch.where(missing, pos[:, :1], pos).long()
+        score = torch.where(missing, score[:, :1], score)
+        items = cands.idx[pos.reshape(-1)][:, cands.item_fields].long()
+        items = items[:, [cands.item_fields.index(f) for f in fields]].reshape(pos.shape[0], pos.shape[1], len(fields))
+        return items, score
 
     def _pair_experiment_result(self, start, pred):
         """run_pair_experiment's 4-tuple from the per-pair predictions [n] on the device (n >= 1); reads the index flag once"""
@@ -870,6 +982,7 @@ class NetworkPairTraining:
     def fit_pairs(self, Xi, Xv, item_fields, negatives=None, n_neg=1, margin=0.0, candidates=None, generator=None, full=False):
         """OnlineFMBase.fit_pairs's arguments; full=True: one mini-batch pair step of tables and network on the logit forward()
         returns, under the model's update rule ('adam' / 'adagrad' need fused_optimizer=True).  Returns the mean pair loss."""
+        self._refuse_hard_negatives("fit_pairs", negatives)
         self._pair_refusal_or_full("fit_pairs", full)
         return self._fit_pairs_full(Xi, Xv, item_fields, negatives, n_neg, margin, candidates, generator)
 
@@ -878,6 +991,7 @@ class NetworkPairTraining:
         then fit_pairs(full=True) on that pair alone, pair by pair -- the host loop of one-pair section calls, or, with the
         attribute pair_loop_on_device set to True, one device call where _pair_device_loop_ok() says so (its docstring: which
         models, and with which arithmetic)."""
+        self._refuse_hard_negatives("run_pair_experiment", negatives)
         self._pair_refusal_or_full("run_pair_experiment", full)
         if self.pair_loop_on_device and self._pair_device_loop_ok():
             return self._run_pair_experiment_on_device(Xi, Xv, item_fields, negatives, n_neg, margin, candidates, generator)

@@ -228,6 +228,7 @@ class AFMAdam(nn.Module):
     # ---- pairwise-ranking (BPR) training on the attentional logit (fmx_afm_pair_*; the pair objective of the other classes) ----
     _pair_rows = OnlineFMBase._pair_rows
     _pair_experiment_result = OnlineFMBase._pair_experiment_result
+    _refuse_hard_negatives = OnlineFMBase._refuse_hard_negatives
 
     def _pair_refusal(self, method, attention):
         """The default keeps the other classes' reading of these two methods -- the pair loss of the pure FM logit, which this
@@ -241,6 +242,7 @@ class AFMAdam(nn.Module):
         on -log(sigmoid(z_pos - z_neg) + margin) over the logit forward() gives, inv_b = 1 / pairs; returns the mean pair loss.
         fused_optimizer=True: one fmx_afm_pair_step_opt call; False: fmx_afm_pair_step, then the attention parameters' rule on
         torch, as update_embedding splits."""
+        self._refuse_hard_negatives("fit_pairs", negatives)
         self._pair_refusal("fit_pairs", attention)
         self.train()
         rows, xv = self._pair_rows(Xi, Xv, item_fields, negatives, n_neg, candidates, generator)
@@ -257,6 +259,7 @@ class AFMAdam(nn.Module):
         """OnlineFMBase.run_pair_experiment's arguments and 4-tuple; attention=True: for every pair predict z_pos > z_neg from the
         logits before the pair's update, then fit on that pair alone.  fused_optimizer=True: one upload and ONE
         fmx_afm_pair_online_run call; False: the host loop of one-pair fit_pairs(attention=True) -- the same protocol."""
+        self._refuse_hard_negatives("run_pair_experiment", negatives)
         self._pair_refusal("run_pair_experiment", attention)
         start = time()
         self.train()

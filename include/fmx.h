@@ -1088,6 +1088,35 @@ int fmx_afm_rank(const fmx_afm_t *afm, const float *Eu, const float *stats_u, in
                  const int32_t *targets, int32_t T, int32_t filtered, void *workspace, int64_t workspace_bytes, int32_t *rank_out,
                  float *score_out, int32_t *n_cand_out, fmx_stream_t stream);
 
+/* ---- hard negatives for pairwise (BPR) training: the best of n_draw drawn candidates per user (fmx/pairwise.py) ----
+ * Replaces: uniform negatives (torch.randint with a redraw loop that reads a count back per round) followed, for dynamic
+ * negative sampling (Zhang et al. 2013; Rendle & Freudenthaler 2014), by n_draw assembled forwards per positive and torch.max;
+ * the reference has no counterpart (meta_fm.py:145-169 takes its negatives as given).
+ *   Su, ld_u, au, U, Sc, ld_c, ac, N, kp, excl_offsets / excl_pos: exactly as fmx_fm_topk.  No workspace.
+ *   own_pos [U] int32 or null: the position of the user's own (positive) item, never returned; -1: none.
+ *   neg_pos [U, n_neg] int32, neg_score [U, n_neg] fp32.
+ * Draws.  Draw j (0 <= j < n_draw) of user u is word j & 3 of Philox4x32-10 (multipliers 0xD2511F53 / 0xCD9E8D57, Weyl
+ * constants 0x9E3779B9 / 0xBB67AE85) with
+ *     key     = (seed & 0xffffffff, seed >> 32)
+ *     counter = (offset & 0xffffffff, offset >> 32, (u_base + u) mod 2^32, j >> 2)
+ * and the drawn position is (uint64(word) * N) >> 32: uniform over [0, N) up to a bias of at most N / 2^32 per position.  A
+ * user's draws depend on (seed, offset, u_base + u, N) only -- not on U, nor on how a batch is cut into calls.
+ * Eligibility.  A draw is eligible when its score is not NaN, its position is not own_pos[u], its position is not in the
+ * user's exclusion list, and its position was not counted already (a position drawn twice counts once).
+ * Score.  score(u, c) of fmx_fm_topk, the same bits: the device code of the score is shared, not restated.
+ * Result.  Row u holds the n_neg best eligible drawn positions in fmx_fm_topk's order (score descending, then position
+ * ascending, -0 returned as +0), padded with -1 / -inf: by definition what fmx_fm_topk with K = n_neg returns over the set of
+ * that user's drawn, non-own candidates.
+ * Limits.  kp 4 / 8 / 16 / 32 / 64, n_draw <= 1024, n_neg <= 16, else FMX_ERR_UNSUPPORTED; U, N, n_draw, n_neg >= 1 and
+ * n_neg <= n_draw, non-null Su / au / Sc / ac / outputs, excl_offsets and excl_pos together, else FMX_ERR_ARG; ld_u, ld_c
+ * multiples of 4 and Su, Sc 16-byte aligned, else FMX_ERR_ALIGN; ld_u, ld_c >= kp, else FMX_ERR_SHAPE.  Every argument is
+ * checked before anything is launched.  One launch (a wavefront per user), asynchronous on `stream`, safe under graph
+ * capture; no atomics and a total order, so the result is identical run to run. */
+int fmx_fm_mine_negatives(const float *Su, int32_t ld_u, const float *au, int32_t U, const float *Sc, int32_t ld_c, const float *ac,
+                          int32_t N, int32_t kp, const int32_t *excl_offsets, const int32_t *excl_pos, const int32_t *own_pos,
+                          int32_t n_draw, int32_t n_neg, uint64_t seed, uint64_t offset, uint32_t u_base, int32_t *neg_pos,
+                          float *neg_score, fmx_stream_t stream);
+
 /* Streaming read of `bytes` (multiple of 16) with 16-byte loads; sink [1] receives a checksum so the loads stay
  * live.  Used by bench.py to measure the HBM-read ceiling on the same GPU in the same run. */
 int fmx_stream_read(const void *buf, int64_t bytes, float *sink, fmx_stream_t stream);
