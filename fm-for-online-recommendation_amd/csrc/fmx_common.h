@@ -264,6 +264,28 @@ __device__ __forceinline__ void pair_loss_dz(float d, float margin, float inv_b,
   dz = g * inv_b;
 }
 
+// The listwise (sampled-softmax) loss of a list of G logits held on G consecutive lanes of a wave, the positive's first:
+// lane `lane` holds z of position lane % G, every lane of the list is active.  With m = max_j z_j, e_j = exp(z_j - m) and
+// s = e_0 + e_1 + ... + e_{G-1} added in that order: loss = log(s) - (z_0 - m) (softmax cross-entropy against position 0),
+// dz_j = e_j / s inv_b for a negative and dz_0 = -((e_1 + ... + e_{G-1}) / s) inv_b -- the negatives' mass itself, not 1 - p_0,
+// which loses its digits as p_0 -> 1 (as pair_loss_dz evaluates sigmoid(-d)).  Every lane of the list walks the G logits by
+// lane reads in the order j = 0 .. G-1 and evaluates the same operands in the same order, so the result depends on the logits
+// and G alone.  exp's argument is <= 0 and s >= 1: finite for finite logits.  `loss` is the list's on every lane.
+__device__ __forceinline__ void list_loss_dz(float z, int lane, int G, float inv_b, float &loss, float &dz) {
+  const int pos = lane % G, first = lane - pos;
+  const float z0 = __shfl(z, first);
+  float m = z0;
+  for (int j = 1; j < G; ++j) m = fmaxf(m, __shfl(z, first + j));
+  float s = expf(z0 - m), neg = 0.f;  // neg: e_1 + ... + e_{G-1}, in that order
+  for (int j = 1; j < G; ++j) {
+    const float e = expf(__shfl(z, first + j) - m);
+    s += e;
+    neg += e;
+  }
+  loss = logf(s) - (z0 - m);
+  dz = pos == 0 ? -(neg / s) * inv_b : (expf(z - m) / s) * inv_b;
+}
+
 // lane ^ M exchanges without the LDS crossbar (ds_bpermute made the sort LDS-pipe bound): DPP for M = 1, 2, 4, 8,
 // v_permlane16/32_swap for M = 16, 32.
 template <int M>

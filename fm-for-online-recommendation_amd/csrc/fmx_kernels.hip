@@ -69,7 +69,10 @@ struct FwdArgs {
   // fields as pieces of index columns (fmx_table_t.field_cols / field_base; both null on ordinary tables): Fc = columns of idx
   const int32_t *fcols, *fbase;
   int32_t Fc;
-  float margin;  // PAIR (fmx_pair.inc): the pair loss's margin; nothing else reads it
+  union {            // one word, so that the struct -- and with it every k_fm_forward's kernarg loads -- keeps its size
+    float margin;    // PAIR (fmx_pair.inc): the pair loss's margin; nothing else reads it
+    int32_t list_g;  // LIST (fmx_list.inc): rows per list (the positive, then its negatives); nothing else reads it
+  };
 };
 
 #ifdef FMX_STAMPS  // diagnostic build (tools/forward_stamps.sh): s_memrealtime (100 MHz) of every wave of the LAST k_fm_forward launch
@@ -98,7 +101,11 @@ __device__ __forceinline__ float first_lane_f(float v) { return __int_as_float(_
 // PAIR (fmx_fm_pair_forward, fmx_pair.inc; at least two waves per workgroup, B even): samples 2i and 2i + 1 are the positive and the
 // negative of pair i and sit on neighbouring lanes of that first wave; each takes its partner's logit from lane ^ 1 and both
 // evaluate the pair loss of the same difference -- the positive stores (loss_i, dz_i), the negative (0, -dz_i).  No label is read.
-template <int LPR, bool PAIR = false>
+// LIST (fmx_fm_list_forward, fmx_list.inc; G = a.list_g rows per list, G * max(1, 4 / G) waves per workgroup -- up to 16, hence
+// sh[3][16] and k_fm_forward_list's own launch bound -- and B a multiple of G): a workgroup holds whole lists, lane i of the first
+// wave is position i % G of list i / G, and every lane evaluates its list's softmax cross-entropy from the list's G logits
+// (list_loss_dz, fmx_common.h) -- the positive stores (loss_i, dz_0), a negative (0, dz_j).  No label and no loss_kind is read.
+template <int LPR, bool PAIR = false, bool LIST = false>
 __device__ __forceinline__ void forward_finish(const FwdArgs &a, int b, const bool exists, const int lane, float4 s, float4 ss, float fo,
                                                bool bad, float y, const float bias) {
   const int q = lane % LPR;
@@ -117,8 +124,8 @@ __device__ __forceinline__ void forward_finish(const FwdArgs &a, int b, const bo
     if (a.out.bi) *reinterpret_cast<float4 *>(a.out.bi + (size_t)b * kp + 4 * q) = bi;
   }
   int n = exists ? 1 : 0;  // lanes 0 .. n - 1 finish samples b .. b + n - 1
-  if ((PAIR || a.loss_kind != FMX_LOSS_NONE) && blockDim.x > WAVE) {  // (uniform over the launch)
-    __shared__ float sh[3][4];
+  if ((PAIR || LIST || a.loss_kind != FMX_LOSS_NONE) && blockDim.x > WAVE) {  // (uniform over the launch)
+    __shared__ float sh[3][LIST ? 16 : 4];
     const int w = threadIdx.x >> 6, wpb = blockDim.x >> 6;
     if (lane == 0) {
       sh[0][w] = fo;
@@ -147,6 +154,11 @@ __device__ __forceinline__ void forward_finish(const FwdArgs &a, int b, const bo
       pair_loss_dz(pos ? z - zo : zo - z, a.margin, a.inv_b, loss, dz);  // both lanes: the same operands, the same bits
       if (a.out.loss) a.out.loss[(size_t)bl * a.ld1] = pos ? loss : 0.f;
       if (a.out.dz) a.out.dz[(size_t)bl * a.ld1] = pos ? dz : -dz;
+    } else if constexpr (LIST) {
+      float loss, dz;  // (n is a multiple of G: every lane of the list is active)
+      list_loss_dz(z, lane, a.list_g, a.inv_b, loss, dz);
+      if (a.out.loss) a.out.loss[(size_t)bl * a.ld1] = lane % a.list_g == 0 ? loss : 0.f;
+      if (a.out.dz) a.out.dz[(size_t)bl * a.ld1] = dz;
     } else if (a.loss_kind != FMX_LOSS_NONE) {
       float loss, dz;
       bce_loss_dz(a.loss_kind, z, y, a.inv_b, loss, dz);
@@ -176,7 +188,7 @@ constexpr int64_t ROW_ABSENT = int64_t(1) << 62;  // set in a resolved row: the 
 // HAS_X: xv is not null (without values every x is 1 and nothing is loaded for it).
 // exists (wave-uniform): false for a wave behind the batch's last sample, which repeats that sample for the workgroup's barrier and
 // stores nothing.
-template <int LPR, int LAYOUT, int NPASS, bool MAPPED, bool HAS_X, bool PAIR = false>
+template <int LPR, int LAYOUT, int NPASS, bool MAPPED, bool HAS_X, bool PAIR = false, bool LIST = false>
 __device__ __forceinline__ void forward_sample(const FwdArgs &a, const int b, const bool exists, const int lane) {
   constexpr int SLOTS = WAVE / LPR;
   constexpr int NP = NPASS > 0 ? NPASS : 1;
@@ -190,7 +202,7 @@ __device__ __forceinline__ void forward_sample(const FwdArgs &a, const int b, co
   bool bad = false;
   // the label and the bias are only needed by the epilogue, but a load issued there is one more dependent round trip
   // at the end of every wave: request them now, with the indices (every lane the same address: one request each)
-  const float y_early = (!PAIR && a.loss_kind != FMX_LOSS_NONE) ? a.y[b] : 0.f;
+  const float y_early = (!PAIR && !LIST && a.loss_kind != FMX_LOSS_NONE) ? a.y[b] : 0.f;
   const float bias0_early = a.bias[0];
   const float bias1_early = LAYOUT == FMX_LAYOUT_WEIGHTS ? 0.f : a.bias[1];
   __builtin_amdgcn_sched_barrier(0);  // (left to itself the scheduler sinks the bias load behind the first waits of the gather:
@@ -274,7 +286,7 @@ __device__ __forceinline__ void forward_sample(const FwdArgs &a, const int b, co
     }
     FMX_FSTAMP(2, s.x + ss.x + fo);  // (every row of the pass set arrived and added)
   }
-  forward_finish<LPR, PAIR>(a, b, exists, lane, s, ss, fo, bad, y_early, bias);
+  forward_finish<LPR, PAIR, LIST>(a, b, exists, lane, s, ss, fo, bad, y_early, bias);
 }
 
 template <int LPR, int LAYOUT, int NPASS, bool MAPPED = false, bool PAIR = false>
@@ -285,6 +297,21 @@ __global__ __launch_bounds__(256) void k_fm_forward(FwdArgs a) {
   if (!exists) b = a.B - 1;     // (forward_finish has a workgroup barrier: the wave goes along and stores nothing)
   if (a.xv) forward_sample<LPR, LAYOUT, NPASS, MAPPED, true, PAIR>(a, b, exists, threadIdx.x & 63);
   else forward_sample<LPR, LAYOUT, NPASS, MAPPED, false, PAIR>(a, b, exists, threadIdx.x & 63);
+}
+
+// The LIST mode of k_fm_forward: the same body with forward_finish<LIST>'s epilogue, a kernel of its own because a workgroup of up
+// to 16 waves needs its own launch bound (128 VGPRs per wave at 1024 threads) while k_fm_forward's instantiations keep theirs.  (The
+// six lines are repeated, not shared through a device function: routed through one, the pointwise instantiations of k_fm_forward
+// came out with another register assignment, and their code is to stay what it was -- tools/isa_diff.py.)
+constexpr int LIST_MAX_G = 16;
+template <int LPR, int LAYOUT, int NPASS>
+__global__ __launch_bounds__(64 * LIST_MAX_G) void k_fm_forward_list(FwdArgs a) {
+  __builtin_amdgcn_s_setprio(3);
+  int b = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+  const bool exists = b < a.B;  // wave-uniform
+  if (!exists) b = a.B - 1;     // (the barrier again; B_lists G need not be a multiple of the workgroup's waves when they exceed G)
+  if (a.xv) forward_sample<LPR, LAYOUT, NPASS, false, true, false, true>(a, b, exists, threadIdx.x & 63);
+  else forward_sample<LPR, LAYOUT, NPASS, false, false, false, true>(a, b, exists, threadIdx.x & 63);
 }
 
 // ------------------------------------------------------------------------------------------------------------
@@ -670,6 +697,20 @@ void launch_forward(const FwdArgs &a, int layout, hipStream_t st) {
     launch_forward_np<LPR, 0, false, PAIR>(a, layout, st);
 }
 
+// LIST (fmx_fm_list_forward): G * max(1, 4 / G) waves per workgroup -- 4, 3, 4 at G = 2, 3, 4, then G -- so a workgroup holds whole
+// lists and no list straddles two; B_lists * G need not be a multiple of that (the waves past the last row go along to the barrier)
+template <int LPR>
+void launch_forward_list(const FwdArgs &a, int layout, hipStream_t st) {
+  const int G = a.list_g, wpb = G * (4 / G > 1 ? 4 / G : 1);
+  const dim3 grid((a.B + wpb - 1) / wpb), block(64 * wpb);
+  const int slots = WAVE / LPR, np = (a.F + slots - 1) / slots;
+  auto launch = [&](auto NP) {
+    if (layout == FMX_LAYOUT_FTRL) hipLaunchKernelGGL((k_fm_forward_list<LPR, FMX_LAYOUT_FTRL, NP>), grid, block, 0, st, a);
+    else hipLaunchKernelGGL((k_fm_forward_list<LPR, FMX_LAYOUT_WEIGHTS, NP>), grid, block, 0, st, a);
+  };
+  if (!with_one_of<1, 2, 3, 4>(np, launch)) launch(std::integral_constant<int, 0>{});
+}
+
 template <int E>
 void launch_sort(SortArgs a, hipStream_t st) {
   const int threads = a.Bp / E;
@@ -884,7 +925,7 @@ FwdArgs fill_fwd(const fmx_table_t *table, const fmx_hyper_t *hyper, const int32
   a.zoff = table->z_offset;
   a.loss_kind = loss_kind;
   a.inv_b = inv_b;
-  a.margin = 0.f;
+  a.margin = 0.f;  // (the list forward puts its G in the same word)
   return a;
 }
 
@@ -987,6 +1028,7 @@ int check_step_args(const fmx_table_t *table, const fmx_hyper_t *hyper, int32_t 
 }
 
 #include "fmx_pair.inc"
+#include "fmx_list.inc"
 
 }  // namespace
 
@@ -1452,6 +1494,33 @@ int fmx_fm_pair_stream(const fmx_table_t *table, const fmx_hyper_t *hyper, int32
                        const fmx_fwd_out_t *fwd, float *loss_out, fmx_stream_t stream) {
   return pair_stream_call(table, hyper, rule, idx_pool, n_pool, B_pairs, margin, inv_b, n_steps, workspace, workspace_bytes, fwd,
                           loss_out, static_cast<hipStream_t>(stream));
+}
+
+// ---- the listwise (sampled-softmax) loss (fmx_list.inc) ----
+int64_t fmx_fm_list_workspace_bytes(const fmx_table_t *table, int32_t B_lists, int32_t G) {
+  if (check_table(table) != FMX_OK) return FMX_ERR_ARG;
+  if (B_lists < 1 || G < 2 || G > LIST_MAX_G || (int64_t)B_lists * G > INT32_MAX)
+    return fail(FMX_ERR_ARG, "fmx_fm_list_workspace_bytes: B_lists >= 1, 2 <= G <= %d and B_lists * G within int32", LIST_MAX_G);
+  return list_workspace_bytes(table, B_lists * G);
+}
+
+int fmx_fm_list_forward(const fmx_table_t *table, const fmx_hyper_t *hyper, const int32_t *idx, const float *xv, int32_t B_lists,
+                        int32_t G, float inv_b, const fmx_fwd_out_t *out, fmx_stream_t stream) {
+  return list_forward_call(table, hyper, idx, xv, B_lists, G, inv_b, out, static_cast<hipStream_t>(stream));
+}
+
+int fmx_fm_list_step(const fmx_table_t *table, const fmx_hyper_t *hyper, int32_t rule, const int32_t *idx, const float *xv,
+                     int32_t B_lists, int32_t G, float inv_b, void *workspace, int64_t workspace_bytes, const fmx_fwd_out_t *fwd,
+                     float *loss_out, fmx_stream_t stream) {
+  return list_step_call(table, hyper, rule, idx, xv, B_lists, G, inv_b, workspace, workspace_bytes, fwd, loss_out,
+                        static_cast<hipStream_t>(stream));
+}
+
+int fmx_fm_list_stream(const fmx_table_t *table, const fmx_hyper_t *hyper, int32_t rule, const int32_t *idx_pool, int32_t n_pool,
+                       int32_t B_lists, int32_t G, float inv_b, int32_t n_steps, void *workspace, int64_t workspace_bytes,
+                       const fmx_fwd_out_t *fwd, float *loss_out, fmx_stream_t stream) {
+  return list_stream_call(table, hyper, rule, idx_pool, n_pool, B_lists, G, inv_b, n_steps, workspace, workspace_bytes, fwd, loss_out,
+                          static_cast<hipStream_t>(stream));
 }
 
 int fmx_gather_read(const void *buf, int64_t bytes, int32_t row_bytes, int64_t n_rows_read, uint32_t seed, float *sink, fmx_stream_t stream) {

@@ -1,0 +1,107 @@
+// fmx_list.inc -- listwise (sampled-softmax) training of the pure FM, the batched calls: fmx_fm_list_forward / _step / _stream.
+// Included by fmx_kernels.hip inside its anonymous namespace, behind fmx_pair.inc, whose checks it shares.
+//
+// A batch of B_lists lists of G rows is B_lists G full-width rows: row G i the positive sample of list i, rows G i + 1 .. G i + G - 1
+// its negatives.  The forward's epilogue (forward_finish<LIST>, list_loss_dz in fmx_common.h) leaves the softmax cross-entropy of
+// every list against its positive in loss[G i] (0 in the negatives' slots) and its gradient in dz, so k_fm_update on the rows with
+// dz_first = dz_bi = dz performs the step of inv_b sum_i loss_i.  Nothing of the update changes.
+//
+// The bias: a softmax does not move under a shift of all its logits, so the bias has no gradient -- but the dz of a list sum to
+// zero only up to rounding, and under signadam g / (|g| + eps) would turn that rounding into a step.  The update is therefore
+// handed a copy of the (host) table struct whose bias points at LIST_BIAS_SCRATCH bytes behind the ordinary step workspace: the
+// bias rule runs on scratch, the table's bias and its state stay bit-unchanged, the forward reads the real bias.  No such device
+// exists for the first-order weights of columns every row of a list shares (the context): their gradient is zero in exact
+// arithmetic and rounding-level here, and signadam normalises such a gradient like any other.
+
+constexpr int64_t LIST_BIAS_SCRATCH = 16;  // >= the 3 floats the bias rule of a moments table reads and writes; keeps 16-byte alignment
+
+inline int64_t list_workspace_bytes(const fmx_table_t *table, int32_t rows) { return (int64_t)carve(table, rows, nullptr).bytes + LIST_BIAS_SCRATCH; }
+
+// what every list entry point refuses before it looks further; *rows = B_lists * G
+int check_list_args(const fmx_table_t *table, const fmx_hyper_t *hyper, const int32_t *idx, int32_t B_lists, int32_t G, int32_t *rows,
+                    const char *who) {
+  if (int rc = check_pair_args(table, hyper, idx, B_lists, "B_lists", 0.f, who)) return rc;
+  if (G < 2) return fail(FMX_ERR_ARG, "%s: G = %d: a list is a positive and at least one negative (G >= 2)", who, G);
+  if (G > LIST_MAX_G) return fail(FMX_ERR_UNSUPPORTED, "%s: G = %d: at most %d rows per list (one workgroup holds a list's waves)", who, G, LIST_MAX_G);
+  if ((int64_t)B_lists * G > INT32_MAX) return fail(FMX_ERR_ARG, "%s: B_lists = %d, G = %d: B_lists * G rows exceed int32", who, B_lists, G);
+  *rows = B_lists * G;
+  return FMX_OK;
+}
+
+int list_forward_impl(const fmx_table_t *table, const fmx_hyper_t *hyper, const int32_t *idx, const float *xv, int32_t rows, int32_t G,
+                      float inv_b, const fmx_fwd_out_t *out, hipStream_t st) {
+  FwdArgs a = fill_fwd(table, hyper, idx, xv, nullptr, rows, FMX_LOSS_NONE, inv_b, out);
+  a.list_g = G;
+  with_lpr(table->kp, [&](auto LPR) { launch_forward_list<LPR>(a, table->layout, st); });
+  return check_launch("k_fm_forward_list");
+}
+
+int list_forward_call(const fmx_table_t *table, const fmx_hyper_t *hyper, const int32_t *idx, const float *xv, int32_t B_lists, int32_t G,
+                      float inv_b, const fmx_fwd_out_t *out, hipStream_t st) {
+  const char *who = "fmx_fm_list_forward";
+  int32_t rows = 0;
+  if (int rc = check_list_args(table, hyper, idx, B_lists, G, &rows, who)) return rc;
+  if (int rc = check_pair_out(table, out, "out", false, who)) return rc;
+  return list_forward_impl(table, hyper, idx, xv, rows, G, inv_b, out, st);
+}
+
+// the checks of a step (n_steps = 1) or a stream of them, in front of the first launch
+int check_list_step(const fmx_table_t *table, const fmx_hyper_t *hyper, int32_t rule, const int32_t *idx, int32_t B_lists, int32_t G,
+                    const void *workspace, int64_t workspace_bytes, const fmx_fwd_out_t *fwd, int64_t n_steps, int32_t *rows, const char *who) {
+  if (int rc = check_list_args(table, hyper, idx, B_lists, G, rows, who)) return rc;
+  if (int rc = check_rule(table, rule)) return named(rc, who);
+  if (int rc = check_adam(hyper, rule, n_steps)) return named(rc, who);
+  if (int rc = check_pair_out(table, fwd, "fwd", true, who)) return rc;
+  if (int rc = check_sort_geometry(table, *rows)) return rc;  // (as fmx_sort_occurrences reports it)
+  if (int rc = check_workspace(table, *rows, workspace, workspace_bytes, who)) return rc;
+  const int64_t need = list_workspace_bytes(table, *rows);
+  if (workspace_bytes < need)
+    return fail(FMX_ERR_SHAPE, "%s: workspace of %lld bytes, %lld needed: the step's and %lld bytes behind it (fmx_fm_list_workspace_bytes)", who,
+                (long long)workspace_bytes, (long long)need, (long long)LIST_BIAS_SCRATCH);
+  return FMX_OK;
+}
+
+// the table as the update of a list step takes it: the bias rule runs on the scratch behind the step workspace
+inline fmx_table_t list_update_table(const fmx_table_t *table, const Workspace &w, void *workspace) {
+  fmx_table_t t = *table;
+  t.bias = reinterpret_cast<float *>(static_cast<char *>(workspace) + w.bytes);
+  return t;
+}
+
+int list_step_call(const fmx_table_t *table, const fmx_hyper_t *hyper, int32_t rule, const int32_t *idx, const float *xv, int32_t B_lists,
+                   int32_t G, float inv_b, void *workspace, int64_t workspace_bytes, const fmx_fwd_out_t *fwd, float *loss_out,
+                   hipStream_t st) {
+  int32_t rows = 0;
+  if (int rc = check_list_step(table, hyper, rule, idx, B_lists, G, workspace, workspace_bytes, fwd, 1, &rows, "fmx_fm_list_step")) return rc;
+  const Workspace w = carve(table, rows, workspace);
+  const fmx_table_t tu = list_update_table(table, w, workspace);
+  // one stream: sort -> list forward -> update, as fmx_fm_step
+  if (int rc = sort_impl(table, idx, rows, w.sorted, w.runs, fwd->error, st)) return rc;
+  if (int rc = list_forward_impl(table, hyper, idx, xv, rows, G, inv_b, fwd, st)) return rc;
+  return update_impl(&tu, hyper, rule, w, w.sorted, xv, fwd->S, fwd->dz, fwd->dz, nullptr, rows, fwd->loss, inv_b, loss_out, st, nullptr,
+                     fwd->sample_ld, fwd->error);
+}
+
+int list_stream_call(const fmx_table_t *table, const fmx_hyper_t *hyper, int32_t rule, const int32_t *idx_pool, int32_t n_pool,
+                     int32_t B_lists, int32_t G, float inv_b, int32_t n_steps, void *workspace, int64_t workspace_bytes,
+                     const fmx_fwd_out_t *fwd, float *loss_out, hipStream_t st) {
+  const char *who = "fmx_fm_list_stream";
+  int32_t rows = 0;
+  if (int rc = check_list_step(table, hyper, rule, idx_pool, B_lists, G, workspace, workspace_bytes, fwd, n_steps > 0 ? n_steps : 0, &rows, who))
+    return rc;
+  if (n_pool < 1) return fail(FMX_ERR_ARG, "%s: n_pool = %d must be >= 1", who, n_pool);
+  if (n_steps < 0) return fail(FMX_ERR_ARG, "%s: n_steps = %d must be >= 0", who, n_steps);
+  const Workspace w = carve(table, rows, workspace);
+  const fmx_table_t tu = list_update_table(table, w, workspace);
+  // fmx_fm_stream's loop on the rows of a step (pool_loop: the sorts of a group of steps in one launch, ahead of them)
+  auto forward = [&](int, const int32_t *idx, const float *, hipStream_t s_) {
+    return list_forward_impl(table, hyper, idx, nullptr, rows, G, inv_b, fwd, s_);
+  };
+  auto update = [&](int s, const uint32_t *sorted, hipStream_t s_) {
+    fmx_hyper_t hs = hyper_for(hyper, rule);  // step s of the call is step t = hyper->step + s + 1 of the table
+    hs.step += s;
+    return update_impl(&tu, &hs, rule, w, sorted, nullptr, fwd->S, fwd->dz, fwd->dz, nullptr, rows, fwd->loss, inv_b,
+                       loss_out ? loss_out + s : nullptr, s_, nullptr, fwd->sample_ld, fwd->error);
+  };
+  return pool_loop(table, idx_pool, nullptr, n_pool, rows, n_steps, w, fwd->error, st, forward, update);
+}

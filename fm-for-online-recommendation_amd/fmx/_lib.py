@@ -15,6 +15,7 @@ RULES = {"signadam": RULE_SIGNADAM, "sgd": RULE_SGD, "ftrl": RULE_FTRL, "adagrad
 ADAPTIVE_RULES = ("adagrad", "adam")      # persistent per-coordinate state: tables in the moments layout
 LAYOUTS = {"weights": LAYOUT_WEIGHTS, "ftrl": LAYOUT_FTRL, "moments": LAYOUT_MOMENTS}
 LOSSES = {None: LOSS_NONE, "none": LOSS_NONE, "logits": LOSS_BCE_LOGITS, "sigmoid": LOSS_BCE_SIGMOID}
+LIST_MAX_G = 16      # rows per list of fmx_fm_list_*: one positive and up to 15 negatives
 
 EXPORTS = ["fmx_version", "fmx_last_error_string", "fmx_set_option", "fmx_sorted_width", "fmx_sorted_bbits", "fmx_workspace_bytes",
            "fmx_fm_forward", "fmx_mlp_forward", "fmx_mlp_fit", "fmx_mlp_hedge_fit", "fmx_mlp_section",
@@ -32,12 +33,14 @@ EXPORTS = ["fmx_version", "fmx_last_error_string", "fmx_set_option", "fmx_sorted
            "fmx_fm_pair_forward", "fmx_fm_pair_step", "fmx_fm_pair_stream", "fmx_fm_pair_online_run",
            "fmx_mlp_pair_section", "fmx_deepfm_pair_stream", "fmx_mlp_pair_fit", "fmx_online_run_mlp_pair",
            "fmx_afm_pair_forward", "fmx_afm_pair_step", "fmx_afm_pair_step_opt", "fmx_afm_pair_stream", "fmx_afm_pair_online_run",
-           "fmx_afm_pair_online_form", "fmx_fm_mine_negatives"]
+           "fmx_afm_pair_online_form", "fmx_fm_mine_negatives",
+           "fmx_fm_list_workspace_bytes", "fmx_fm_list_forward", "fmx_fm_list_step", "fmx_fm_list_stream"]
 
 
 I64_RETURNS = ("fmx_workspace_bytes", "fmx_mlp_section_workspace_bytes", "fmx_fm_topk_workspace_bytes",
                "fmx_mlp_topk_workspace_bytes", "fmx_afm_workspace_bytes", "fmx_afm_topk_workspace_bytes",
-               "fmx_fm_rank_workspace_bytes", "fmx_mlp_rank_workspace_bytes", "fmx_afm_rank_workspace_bytes")   # byte counts: int64_t in include/fmx.h
+               "fmx_fm_rank_workspace_bytes", "fmx_mlp_rank_workspace_bytes", "fmx_afm_rank_workspace_bytes",
+               "fmx_fm_list_workspace_bytes")   # byte counts: int64_t in include/fmx.h
 
 
 class FmxError(RuntimeError):
@@ -180,6 +183,10 @@ def load():
     lib.fmx_afm_pair_online_form.argtypes = [TP, AP, i32, C.POINTER(C.c_int32)]
     lib.fmx_fm_mine_negatives.argtypes = [p, i32, p, i32, p, i32, p, i32, i32, p, p, p, i32, i32, C.c_uint64, C.c_uint64, C.c_uint32,
                                           p, p, p]
+    lib.fmx_fm_list_workspace_bytes.argtypes = [TP, i32, i32]
+    lib.fmx_fm_list_forward.argtypes = [TP, HP, p, p, i32, i32, f32, FP, p]
+    lib.fmx_fm_list_step.argtypes = [TP, HP, i32, p, p, i32, i32, f32, p, i64, FP, p, p]
+    lib.fmx_fm_list_stream.argtypes = [TP, HP, i32, p, i32, i32, i32, f32, i32, p, i64, FP, p, p]
     for name in EXPORTS:
         fn = getattr(lib, name)
         if name in I64_RETURNS:

@@ -7,7 +7,6 @@ import torch
 from . import _lib
 from .table import FlatTable
 
-
 class Hyper:
     """Update-rule hyper-parameters (include/fmx.h fmx_hyper_t)."""
 
@@ -488,6 +487,64 @@ class FMEngine:
         self._steps(hyper)
         _lib.check(self.lib.fmx_fm_pair_stream(self.table.c_struct(), hyper.ref(), _lib.RULES[rule], idx_pool.data_ptr(), n_pool, B,
                                                float(margin), 1.0 / B, int(n_steps), self.workspace.data_ptr(), self._ws_bytes(),
+                                               C.byref(out), _ptr(loss_out), self._stream()))
+        self._advance(n_steps)
+
+    # ---- listwise (sampled-softmax) training: idx_d [B G, F], row G i the positive of list i, then its G - 1 negatives ----
+    def _n_lists(self, rows, G):
+        """-> B for B G rows; grows the buffers, and keeps the list steps' own workspace, self._list_ws, sized through
+        fmx_fm_list_workspace_bytes (the step workspace and the scratch behind it that the bias rule of a list step runs on).
+        The other calls' workspace and the buffers' allocation are left as they are."""
+        G = int(G)
+        if not 2 <= G <= _lib.LIST_MAX_G:
+            raise ValueError(f"G = {G}: a list is one positive and 1 to {_lib.LIST_MAX_G - 1} negatives")
+        if rows < G or rows % G:
+            raise ValueError(f"list rows must be [B G, F] with B >= 1 and G = {G}, got {rows} rows")
+        self._ensure(rows)
+        need = int(self.lib.fmx_fm_list_workspace_bytes(self.table.c_struct(), rows // G, G))
+        if need < 0:
+            _lib.check(need)
+        ws = getattr(self, "_list_ws", None)
+        if ws is None or need > ws.numel() * 4:
+            self._list_ws = torch.zeros(need // 4, dtype=torch.int32, device=self.device)     # (zero-filled once, as the header asks)
+        return rows // G
+
+    def list_forward(self, hyper, idx_d, G, xv_d=None, inv_b=None, want_first=False, want_bi=False, stream=None):
+        """fmx_fm_list_forward on B lists of G rows: S / sfirst / sbi / logit of the B G rows, and the softmax cross-entropy of
+        every list against its first row and its dlogit in self.loss_b / self.dz (loss_b[G i] = loss_i, 0 in the negatives'
+        slots).  -> B"""
+        if idx_d.dim() != 2:
+            raise ValueError(f"list rows must be [B G, F], got {tuple(idx_d.shape)}")
+        B = self._n_lists(idx_d.shape[0], G)
+        out = self._fwd_out(want_first, want_bi)
+        _lib.check(self.lib.fmx_fm_list_forward(self.table.c_struct(), hyper.ref(), idx_d.data_ptr(), _ptr(xv_d), B, int(G),
+                                                1.0 / B if inv_b is None else inv_b, C.byref(out), self._stream(stream)))
+        return B
+
+    def list_step(self, hyper, rule, idx_d, G, xv_d=None, inv_b=None):
+        """One list step on B lists of G rows (fmx_fm_list_step); the mean list loss lands in self.loss_out[0] (no sync here).
+        The table's bias is not touched."""
+        if idx_d.dim() != 2:
+            raise ValueError(f"list rows must be [B G, F], got {tuple(idx_d.shape)}")
+        B = self._n_lists(idx_d.shape[0], G)
+        out = self._fwd_out(want_first=False, want_bi=False)
+        self._steps(hyper)
+        _lib.check(self.lib.fmx_fm_list_step(self.table.c_struct(), hyper.ref(), _lib.RULES[rule], idx_d.data_ptr(), _ptr(xv_d), B,
+                                             int(G), 1.0 / B if inv_b is None else inv_b, self._list_ws.data_ptr(),
+                                             self._list_ws.numel() * 4, C.byref(out), self.loss_out.data_ptr(), self._stream()))
+        self._advance(1)
+
+    def list_stream(self, hyper, rule, idx_pool, G, n_steps, loss_out=None):
+        """n_steps list steps over a resident pool idx_pool [n_pool, B G, F] (fmx_fm_list_stream); loss_out [n_steps] or None."""
+        n_pool, rows, F = idx_pool.shape
+        assert F == self.table.n_fields and idx_pool.is_contiguous()
+        if loss_out is not None and (loss_out.numel() < n_steps or not loss_out.is_contiguous()):
+            raise ValueError(f"loss_out holds {loss_out.numel()} steps, {n_steps} asked for")
+        B = self._n_lists(rows, G)
+        out = self._fwd_out(want_first=False, want_bi=False)
+        self._steps(hyper)
+        _lib.check(self.lib.fmx_fm_list_stream(self.table.c_struct(), hyper.ref(), _lib.RULES[rule], idx_pool.data_ptr(), n_pool, B,
+                                               int(G), 1.0 / B, int(n_steps), self._list_ws.data_ptr(), self._list_ws.numel() * 4,
                                                C.byref(out), _ptr(loss_out), self._stream()))
         self._advance(n_steps)
 

@@ -6,7 +6,10 @@ FMEngine.pair_step / pair_stream / pair_online_run take the result.
 
 Hard negatives (dynamic negative sampling; Zhang et al. 2013, Rendle & Freudenthaler 2014): mine_negatives draws n_draw
 candidates per positive on the device, scores them under the current FM and keeps the n_neg best (fmx_fm_mine_negatives).
-HardNegatives carries the settings of that through the `negatives` argument of fit_pairs / run_pair_experiment.
+HardNegatives carries the settings of that through the `negatives` argument of fit_pairs / run_pair_experiment / fit_lists.
+
+Listwise (sampled-softmax) training (fmx_fm_list_*) takes the same positives and negatives as B lists of G = 1 + n_neg rows,
+[B G, F], the positive first: assemble_lists; FMEngine.list_step / list_stream take the result.
 """
 import torch
 
@@ -40,6 +43,19 @@ def assemble_pairs(pos_idx, pos_xv, item_fields, neg_items, neg_xv=None):
     j-th negative: row 2p is the positive, row 2p + 1 the positive with the item columns replaced -- so with n_neg > 1 a positive
     is repeated once per negative.  neg_xv (same shape as neg_items) replaces the item columns' values too; by default the
     negative keeps the positive's values."""
+    return _assemble(pos_idx, pos_xv, item_fields, neg_items, neg_xv, lists=False)
+
+
+def assemble_lists(pos_idx, pos_xv, item_fields, neg_items, neg_xv=None):
+    """The rows of B lists of G = 1 + n_neg -> (idx [B G, F] int32, xv [B G, F] float32 or None), what FMEngine.list_step takes
+    (fmx_fm_list_*, the sampled-softmax loss).  The arguments, the shapes accepted and the errors are assemble_pairs'; row G b is
+    positive b -- once, not once per negative -- and row G b + 1 + j the positive with the item columns replaced by its j-th
+    negative."""
+    return _assemble(pos_idx, pos_xv, item_fields, neg_items, neg_xv, lists=True)
+
+
+def _assemble(pos_idx, pos_xv, item_fields, neg_items, neg_xv, lists):
+    """pairs: [B, n_neg, (positive, negative), F]; lists: [B, (positive, negatives ...), F]; flattened over all but F"""
     fields = _item_fields(item_fields)
     pos_idx = torch.as_tensor(pos_idx)
     if pos_idx.dim() != 2:
@@ -51,18 +67,27 @@ def assemble_pairs(pos_idx, pos_xv, item_fields, neg_items, neg_xv=None):
     neg = _negatives_3d(neg_items, B, len(fields)).to(device=dev, dtype=pos_idx.dtype)
     n_neg = neg.shape[1]
     cols = torch.as_tensor(fields, dtype=torch.long, device=dev)
-    rows = pos_idx.reshape(B, 1, 1, F).expand(B, n_neg, 2, F).clone()
-    rows[:, :, 1, cols] = neg
-    rows = rows.reshape(2 * B * n_neg, F).to(torch.int32).contiguous()
+
+    def spread(t, repl):
+        if lists:
+            out = t.reshape(B, 1, F).expand(B, 1 + n_neg, F).clone()
+            if repl is not None:
+                out[:, 1:, cols] = repl
+        else:
+            out = t.reshape(B, 1, 1, F).expand(B, n_neg, 2, F).clone()
+            if repl is not None:
+                out[:, :, 1, cols] = repl
+        return out.reshape(-1, F)
+
+    rows = spread(pos_idx, neg).to(torch.int32).contiguous()
     if pos_xv is None and neg_xv is None:
         return rows, None
     xv = torch.ones((B, F), dtype=torch.float32, device=dev) if pos_xv is None else torch.as_tensor(pos_xv, dtype=torch.float32).to(dev)
     if xv.shape != (B, F):
         raise ValueError(f"pos_xv of shape {tuple(xv.shape)}: expected {(B, F)}")
-    vals = xv.reshape(B, 1, 1, F).expand(B, n_neg, 2, F).clone()
     if neg_xv is not None:
-        vals[:, :, 1, cols] = _negatives_3d(neg_xv, B, len(fields), "neg_xv").to(device=dev, dtype=torch.float32).expand(B, n_neg, len(fields))
-    return rows, vals.reshape(2 * B * n_neg, F).contiguous()
+        neg_xv = _negatives_3d(neg_xv, B, len(fields), "neg_xv").to(device=dev, dtype=torch.float32).expand(B, n_neg, len(fields))
+    return rows, spread(xv, neg_xv).contiguous()
 
 
 def sample_negatives(pos_idx, item_fields, sizes_or_candidates, n_neg=1, generator=None):

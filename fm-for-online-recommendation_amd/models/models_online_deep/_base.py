@@ -558,6 +558,11 @@ class OnlineFMBase(nn.Module):
 
     def _pair_rows(self, Xi, Xv, item_fields, negatives, n_neg, candidates, generator):
         """-> (rows int32 [2P, F], xv [2P, F] or None) on the device: P = B * n_neg pairs, row 2p the positive, 2p + 1 the negative"""
+        return self._negative_rows(fmx.pairwise.assemble_pairs, Xi, Xv, item_fields, negatives, n_neg, candidates, generator)
+
+    def _negative_rows(self, assemble, Xi, Xv, item_fields, negatives, n_neg, candidates, generator):
+        """The positives with their negatives -- given, mined ("hard" / a HardNegatives) or drawn uniformly (None) -- laid out by
+        `assemble` (fmx.pairwise.assemble_pairs / assemble_lists)"""
         idx_d, xv_d, _ = self._inputs(Xi, Xv)
         fields = [int(f) for f in (item_fields if hasattr(item_fields, "__len__") else [item_fields])]
         hard = fmx.pairwise.hard_negatives(negatives)
@@ -568,7 +573,7 @@ class OnlineFMBase(nn.Module):
             src = candidates if candidates is not None else [self.feature_sizes[f] for f in fields]
             negatives = fmx.pairwise.sample_negatives(idx_d, fields, src, n_neg=n_neg, generator=generator)
         self._fast_inputs_pending = True      # the negatives' indices are range-checked by the kernels
-        return fmx.pairwise.assemble_pairs(idx_d, xv_d, fields, negatives)
+        return assemble(idx_d, xv_d, fields, negatives)
 
     def fit_pairs(self, Xi, Xv, item_fields, negatives=None, n_neg=1, margin=0.0, candidates=None, generator=None):
         """One mini-batch pair step under the model's update rule; returns the loss tensor (the mean pair loss), as
@@ -584,6 +589,33 @@ class OnlineFMBase(nn.Module):
         self.train()
         rows, xv = self._pair_rows(Xi, Xv, item_fields, negatives, n_neg, candidates, generator)
         self._engine.pair_step(self._hyper, self.update_rule, rows, xv, margin=margin)
+        out = self._engine.loss_out[0].clone()
+        self._after_step()
+        return out
+
+    # ---- listwise (sampled-softmax) training of the pure FM (fmx_fm_list_*): softmax cross-entropy of the observed item against
+    #      its n_neg negatives -- 1 + n_neg rows per positive where the pair form carries 2 n_neg, each negative weighted by its
+    #      share of the probability mass ----
+    def fit_lists(self, Xi, Xv, item_fields, negatives=None, n_neg=4, candidates=None, generator=None):
+        """One mini-batch list step under the model's update rule; returns the loss tensor (the mean list loss), as fit_pairs
+        does.  Every positive of Xi / Xv [B, F] and its negatives form one list; the loss is -log softmax of the positive's
+        logit among the list's.  negatives: what fit_pairs takes -- the negatives' item columns [B, n_neg, m] ([B, m]: one each),
+        None for n_neg uniform draws per positive, "hard" or a fmx.pairwise.HardNegatives for the n_neg best of n_draw drawn
+        candidates under the current FM score (mine_negatives).  At most 15 negatives per positive.  The bias does not move."""
+        if self._has_mlp:
+            raise NotImplementedError(f"{self._name}.fit_lists: the list loss is built for the pure FM logit (FMAdam); the classes "
+                                      "with an MLP would need the softmax epilogue inside the MLP section")
+        limit = fmx._lib.LIST_MAX_G - 1
+        given = negatives is not None and fmx.pairwise.hard_negatives(negatives) is None
+        if not given and not 1 <= int(n_neg) <= limit:
+            raise ValueError(f"{self._name}.fit_lists: n_neg = {n_neg}: a list holds 1 to {limit} negatives")
+        self.train()
+        idx_d, xv_d, _ = self._inputs(Xi, Xv)
+        rows, xv = self._negative_rows(fmx.pairwise.assemble_lists, idx_d, xv_d, item_fields, negatives, n_neg, candidates, generator)
+        G = rows.shape[0] // idx_d.shape[0]
+        if G - 1 > limit:
+            raise ValueError(f"{self._name}.fit_lists: {G - 1} negatives per positive: a list holds 1 to {limit} negatives")
+        self._engine.list_step(self._hyper, self.update_rule, rows, G, xv)
         out = self._engine.loss_out[0].clone()
         self._after_step()
         return out

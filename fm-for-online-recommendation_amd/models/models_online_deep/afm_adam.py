@@ -227,6 +227,7 @@ class AFMAdam(nn.Module):
 
     # ---- pairwise-ranking (BPR) training on the attentional logit (fmx_afm_pair_*; the pair objective of the other classes) ----
     _pair_rows = OnlineFMBase._pair_rows
+    _negative_rows = OnlineFMBase._negative_rows
     _pair_experiment_result = OnlineFMBase._pair_experiment_result
     _refuse_hard_negatives = OnlineFMBase._refuse_hard_negatives
 
@@ -253,6 +254,11 @@ class AFMAdam(nn.Module):
         out = e.loss_out[0].clone()
         self._after_step()
         return out
+
+    def fit_lists(self, Xi, Xv, item_fields, negatives=None, n_neg=4, candidates=None, generator=None):
+        """The listwise (sampled-softmax) step of FMAdam.fit_lists: not built for this model."""
+        raise NotImplementedError(f"{self._name}.fit_lists: the list loss is built for the pure FM logit (FMAdam); the attentional "
+                                  "FM would need the softmax epilogue behind its own forward")
 
     def run_pair_experiment(self, Xi, Xv, item_fields, negatives=None, n_neg=1, margin=0.0, candidates=None, generator=None,
                             attention=False):

@@ -406,6 +406,67 @@ int fmx_fm_pair_online_run(const fmx_table_t *table, const fmx_hyper_t *hyper, i
                            int32_t N, float margin, uint8_t *pred_out, float *logit_out, float *loss_out, int32_t *error,
                            fmx_stream_t stream);
 
+/* ---- listwise (sampled-softmax) training of the pure FM: one positive, G - 1 negatives ----
+ * A batch of B_lists lists of G rows (2 <= G <= 16) is idx [B_lists G, F] (and xv of the same shape, or null) in fmx_fm_forward's
+ * layout: row G i is the positive sample of list i, rows G i + 1 .. G i + G - 1 its negatives (typically the positive's row with
+ * the item columns replaced; nothing requires that).  With z_j the FM logit of row G i + j, per list:
+ *     m = max_j z_j,   e_j = exp(z_j - m),   s = e_0 + e_1 + ... + e_{G-1}  (added in that order),
+ *     loss_i = log(s) - (z_0 - m)                                  softmax cross-entropy against position 0
+ *     dz_j   = (e_j / s) inv_b                          for j >= 1
+ *     dz_0   = -((e_1 + ... + e_{G-1}) / s) inv_b       the negatives' mass itself, not 1 - p_0, which loses its digits as p_0 -> 1
+ * loss and dz are finite for every finite set of logits (the max is subtracted: exp's argument is <= 0 and s >= 1); every lane
+ * of a list evaluates the same operands in the same order, so a list's result depends on its logits and G alone, never on its
+ * place in the batch or the launch's geometry.  At G = 2 this is BPR (fmx_fm_pair_forward under margin 0) in other arithmetic.  No
+ * labels are read; there is no temperature and no log-Q correction.
+ * The bias: a softmax does not move under a shift of all its logits, so the bias has no gradient, and the contract is the pair
+ * family's -- a list step leaves the bias and its state (z / n, moments) BIT-UNCHANGED under every rule.  The dz of a list sum to
+ * zero only up to rounding, so the step does not rely on the sum: the update's bias rule runs on 16 scratch bytes behind the
+ * ordinary step workspace (fmx_fm_list_workspace_bytes), the forward reads the real bias.
+ * The first-order weights of the columns every row of a list shares (the context) also have a gradient that is zero in exact
+ * arithmetic; nothing shields them: they receive rounding-level gradients, which FMX_RULE_SIGNADAM normalises like any other
+ * (g / (|g| + eps)), so under that rule they do move.
+ * Shared refusals, each decided on the host before any launch and naming the entry point: a null table / hyper / idx,
+ * B_lists < 1, G < 2, B_lists G beyond int32: FMX_ERR_ARG; G > 16 (a list's waves share one workgroup of at most 1024 threads):
+ * FMX_ERR_UNSUPPORTED; tables whose fields are pieces of index columns (field_cols / field_base): FMX_ERR_UNSUPPORTED.
+ * Replaces: nothing -- the reference has no listwise loss.  Its nearest counterpart is the pair objective of reference
+ * models/models_meta_emb/meta_fm.py:145-169, which this generalises from one negative to G - 1. */
+
+/* Bytes of caller-owned device workspace a list step of B_lists lists of G rows needs: fmx_workspace_bytes(table, B_lists G) plus
+ * the 16 scratch bytes the bias rule runs on (at the end; 16-byte aligned).  Zero-fill once before the first use, as
+ * fmx_workspace_bytes' buffer.  Negative on a bad table, B_lists < 1, G outside [2, 16] or B_lists G beyond int32.
+ * Replaces: nothing in the reference (the pair objective of meta_fm.py:145-169 is its nearest counterpart; it has no listwise loss). */
+int64_t fmx_fm_list_workspace_bytes(const fmx_table_t *table, int32_t B_lists, int32_t G);
+
+/* The forward pass of the B_lists G rows with the list epilogue: out->S / bi / first / sfirst / sbi / logit exactly as
+ * fmx_fm_forward(FMX_LOSS_NONE) writes them for the same rows (bit-identical), and, where asked for,
+ *   out->loss[G i] = loss_i (unscaled), out->loss[G i + j] = 0 for j >= 1;   out->dz[G i + j] = dz_j as above.
+ * G max(1, 4 / G) waves per workgroup (one row per wave): a workgroup holds whole lists.
+ * Replaces: nothing in the reference, which has no listwise loss; nearest: the forward and loss of the pair objective
+ * (meta_fm.py:145-169: out_pos, out_neg, -log(sigmoid(out_pos - out_neg) + margin)). */
+int fmx_fm_list_forward(const fmx_table_t *table, const fmx_hyper_t *hyper, const int32_t *idx, const float *xv, int32_t B_lists,
+                        int32_t G, float inv_b, const fmx_fwd_out_t *out, fmx_stream_t stream);
+
+/* One list step = fmx_sort_occurrences(B_lists G) + fmx_fm_list_forward + fmx_fm_update(B_lists G, dz_first = dz_bi = dz) on one
+ * stream, under any rule the table's layout takes: the step of inv_b sum_i loss_i; loss_out[0] = inv_b sum_i loss_i.  The table's
+ * bias and its state are bit-unchanged (above).  workspace: fmx_fm_list_workspace_bytes(table, B_lists, G) bytes (null:
+ * FMX_ERR_ARG, smaller: FMX_ERR_SHAPE); fwd->S, fwd->loss, fwd->dz must be non-null, sized for B_lists G samples; the rule against
+ * the layout and FMX_RULE_ADAM's hyper-parameters are checked as fmx_fm_pair_step checks them; B_lists G beyond the sort's width is
+ * refused as fmx_sort_occurrences refuses it.
+ * Replaces: nothing in the reference, which has no listwise loss; nearest: the loss.backward() + optimizer.step() of the pair
+ * objective (meta_fm.py:145-169). */
+int fmx_fm_list_step(const fmx_table_t *table, const fmx_hyper_t *hyper, int32_t rule, const int32_t *idx, const float *xv,
+                     int32_t B_lists, int32_t G, float inv_b, void *workspace, int64_t workspace_bytes, const fmx_fwd_out_t *fwd,
+                     float *loss_out, fmx_stream_t stream);
+
+/* n_steps list steps over a device-resident pool idx_pool [n_pool, B_lists G, F] (every feature value 1): step s takes batch
+ * (s mod n_pool) and, under FMX_RULE_ADAM, is step hyper->step + s + 1 of the table; loss_out [n_steps] or null.  The table ends
+ * bit-identical to n_steps calls of fmx_fm_list_step.  n_pool < 1 and n_steps < 0 are FMX_ERR_ARG.
+ * Replaces: nothing in the reference, which has no listwise loss; nearest: the pair objective of meta_fm.py:145-169, batched as
+ * fmx_fm_stream batches the pointwise one. */
+int fmx_fm_list_stream(const fmx_table_t *table, const fmx_hyper_t *hyper, int32_t rule, const int32_t *idx_pool, int32_t n_pool,
+                       int32_t B_lists, int32_t G, float inv_b, int32_t n_steps, void *workspace, int64_t workspace_bytes,
+                       const fmx_fwd_out_t *fwd, float *loss_out, fmx_stream_t stream);
+
 /* ---- the small relu MLP on top of the bi-interaction vector (online steps of DeepFM / NFM and the ONN classes) ----
  * params: per layer W [out, in] row-major then b [out]; layer 0 maps k -> hidden, the others hidden -> hidden; the network's
  * contribution to the logit is the sum of the last activation (reference deepfm_adam.py:82-88: there is no output layer).
