@@ -285,6 +285,25 @@ __device__ __forceinline__ void list_loss_dz(float z, int lane, int G, float inv
   loss = logf(s) - (z0 - m);
   dz = pos == 0 ? -(neg / s) * inv_b : (expf(z - m) / s) * inv_b;
 }
+// ... and the same formula over zj(j) = the logit of position j read from anywhere (k_fm_list_online, fmx_list_online.hip: from
+// LDS), for the caller at position `pos` whose own logit is z: the operands and the order above, so the same bits.  (The lines are
+// repeated: with list_loss_dz routed through this function -- a lambda by reference or by value, a functor struct, a stateless
+// reader, z_0 handed in -- 16 of k_fm_forward_list's 50 instantiations came out with another schedule, and their code is to stay what
+// it was, tools/isa_diff.py; as with k_fm_forward_list's own six lines.)
+template <class ReadLogit>
+__device__ __forceinline__ void list_loss_dz_of(ReadLogit zj, float z, int pos, int G, float inv_b, float &loss, float &dz) {
+  const float z0 = zj(0);
+  float m = z0;
+  for (int j = 1; j < G; ++j) m = fmaxf(m, zj(j));
+  float s = expf(z0 - m), neg = 0.f;  // neg: e_1 + ... + e_{G-1}, in that order
+  for (int j = 1; j < G; ++j) {
+    const float e = expf(zj(j) - m);
+    s += e;
+    neg += e;
+  }
+  loss = logf(s) - (z0 - m);
+  dz = pos == 0 ? -(neg / s) * inv_b : (expf(z - m) / s) * inv_b;
+}
 
 // lane ^ M exchanges without the LDS crossbar (ds_bpermute made the sort LDS-pipe bound): DPP for M = 1, 2, 4, 8,
 // v_permlane16/32_swap for M = 16, 32.

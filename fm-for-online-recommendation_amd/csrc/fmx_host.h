@@ -64,6 +64,10 @@ int afm_pair_online_buffers(int F, int k, int kp, int t, int attn_rule, bool *mo
 int afm_pair_online_launch(const fmx_table_t *table, const fmx_hyper_t *hyper, int32_t rule, const fmx_afm_t *afm, const int32_t *idx,
                            const float *xv, int32_t N_pairs, float margin, float *attn_grad_out, const fmx_mlp_opt_t *opt,
                            float *logit_out, float *loss_out, int32_t *error, int nb, bool moments_in_lds, hipStream_t st);
+// fmx_list_online.hip: k_fm_list_online, one workgroup of G waves walking N lists (fmx_fm_list_online_run; list_online_call in
+// fmx_list.inc has checked the arguments)
+int list_online_launch(const fmx_table_t *table, const fmx_hyper_t *hyper, int32_t rule, const int32_t *idx, const float *xv, int32_t N,
+                       int32_t G, uint8_t *rank_out, float *logit_out, float *loss_out, int32_t *error, hipStream_t st);
 
 }  // namespace fmxd
 

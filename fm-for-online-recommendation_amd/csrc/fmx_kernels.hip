@@ -1523,6 +1523,11 @@ int fmx_fm_list_stream(const fmx_table_t *table, const fmx_hyper_t *hyper, int32
                           static_cast<hipStream_t>(stream));
 }
 
+int fmx_fm_list_online_run(const fmx_table_t *table, const fmx_hyper_t *hyper, int32_t rule, const int32_t *idx, const float *xv, int32_t N,
+                           int32_t G, uint8_t *rank_out, float *logit_out, float *loss_out, int32_t *error, fmx_stream_t stream) {
+  return list_online_call(table, hyper, rule, idx, xv, N, G, rank_out, logit_out, loss_out, error, static_cast<hipStream_t>(stream));
+}
+
 int fmx_gather_read(const void *buf, int64_t bytes, int32_t row_bytes, int64_t n_rows_read, uint32_t seed, float *sink, fmx_stream_t stream) {
   if (!buf || !sink || bytes < 128 || n_rows_read < 1) return fail(FMX_ERR_ARG, "fmx_gather_read: bad buffer / count");
   if (row_bytes != 64 && row_bytes != 128) return fail(FMX_ERR_ARG, "fmx_gather_read: rows of 64 or 128 bytes");

@@ -1,5 +1,7 @@
 // fmx_list.inc -- listwise (sampled-softmax) training of the pure FM, the batched calls: fmx_fm_list_forward / _step / _stream.
 // Included by fmx_kernels.hip inside its anonymous namespace, behind fmx_pair.inc, whose checks it shares.
+// The online form (fmx_fm_list_online_run) has its checks at the end of this file and its kernel, k_fm_list_online, in a unit of its
+// own, fmx_list_online.hip.
 //
 // A batch of B_lists lists of G rows is B_lists G full-width rows: row G i the positive sample of list i, rows G i + 1 .. G i + G - 1
 // its negatives.  The forward's epilogue (forward_finish<LIST>, list_loss_dz in fmx_common.h) leaves the softmax cross-entropy of
@@ -104,4 +106,29 @@ int list_stream_call(const fmx_table_t *table, const fmx_hyper_t *hyper, int32_t
                        loss_out ? loss_out + s : nullptr, s_, nullptr, fwd->sample_ld, fwd->error);
   };
   return pool_loop(table, idx_pool, nullptr, n_pool, rows, n_steps, w, fwd->error, st, forward, update);
+}
+
+// fmx_fm_list_online_run: the checks, all on the host and in front of the launch; the kernel is k_fm_list_online (fmx_list_online.hip)
+int list_online_call(const fmx_table_t *table, const fmx_hyper_t *hyper, int32_t rule, const int32_t *idx, const float *xv, int32_t N,
+                     int32_t G, uint8_t *rank_out, float *logit_out, float *loss_out, int32_t *error, hipStream_t st) {
+  const char *who = "fmx_fm_list_online_run";
+  if (!table) return fail(FMX_ERR_ARG, "%s: table is null", who);
+  if (int rc = check_table(table)) return named(rc, who);
+  if (int rc = check_rule(table, rule)) return named(rc, who);
+  if (N < 0) return fail(FMX_ERR_ARG, "%s: N = %d must be >= 0", who, N);
+  if (N == 0) return FMX_OK;  // an empty stream (its buffers may be null)
+  int32_t rows = 0;
+  if (int rc = check_list_args(table, hyper, idx, N, G, &rows, who)) return rc;
+  if (int rc = check_adam(hyper, rule, N)) return named(rc, who);
+  if (!rank_out) return fail(FMX_ERR_ARG, "%s: rank_out is null", who);
+  // a wave holds its row of the list as k_fm_online holds a sample: 4 passes of RowRegs
+  const int slots = WAVE / lpr_of(table->kp);
+  if (table->n_fields > 4 * slots)
+    return fail(FMX_ERR_UNSUPPORTED, "%s: %d fields at kp = %d exceed the %d rows one wavefront holds", who, table->n_fields, table->kp,
+                4 * slots);
+  // the order of a run's additions follows its positions in the sort field's list; a split field's are counted per piece
+  if (table->n_sort_fields > 0)
+    return fail(FMX_ERR_UNSUPPORTED, "%s: tables with a sort split (n_sort_fields = %d) are not taken: walk the lists with fmx_fm_list_step", who,
+                table->n_sort_fields);
+  return list_online_launch(table, hyper, rule, idx, xv, N, G, rank_out, logit_out, loss_out, error, st);
 }

@@ -34,7 +34,8 @@ EXPORTS = ["fmx_version", "fmx_last_error_string", "fmx_set_option", "fmx_sorted
            "fmx_mlp_pair_section", "fmx_deepfm_pair_stream", "fmx_mlp_pair_fit", "fmx_online_run_mlp_pair",
            "fmx_afm_pair_forward", "fmx_afm_pair_step", "fmx_afm_pair_step_opt", "fmx_afm_pair_stream", "fmx_afm_pair_online_run",
            "fmx_afm_pair_online_form", "fmx_fm_mine_negatives",
-           "fmx_fm_list_workspace_bytes", "fmx_fm_list_forward", "fmx_fm_list_step", "fmx_fm_list_stream"]
+           "fmx_fm_list_workspace_bytes", "fmx_fm_list_forward", "fmx_fm_list_step", "fmx_fm_list_stream",
+           "fmx_fm_list_online_run"]
 
 
 I64_RETURNS = ("fmx_workspace_bytes", "fmx_mlp_section_workspace_bytes", "fmx_fm_topk_workspace_bytes",
@@ -187,6 +188,7 @@ def load():
     lib.fmx_fm_list_forward.argtypes = [TP, HP, p, p, i32, i32, f32, FP, p]
     lib.fmx_fm_list_step.argtypes = [TP, HP, i32, p, p, i32, i32, f32, p, i64, FP, p, p]
     lib.fmx_fm_list_stream.argtypes = [TP, HP, i32, p, i32, i32, i32, f32, i32, p, i64, FP, p, p]
+    lib.fmx_fm_list_online_run.argtypes = [TP, HP, i32, p, p, i32, i32, p, p, p, p, p]
     for name in EXPORTS:
         fn = getattr(lib, name)
         if name in I64_RETURNS:

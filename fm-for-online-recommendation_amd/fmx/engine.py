@@ -562,6 +562,32 @@ class FMEngine:
         self._advance(N)
         return pred, logit, loss_b
 
+    def list_online_run(self, hyper, rule, idx_d, G, xv_d=None, want_logit=False, want_loss=False):
+        """The online protocol on N device-resident lists of G rows (fmx_fm_list_online_run): per list the positive's rank among
+        its negatives (0: first), then one list step on that list.  -> (rank uint8 [N], logit [N G] or None, loss [N] or None);
+        no sync.  The table's step count advances by N."""
+        G = int(G)
+        if not 2 <= G <= _lib.LIST_MAX_G:
+            raise ValueError(f"G = {G}: a list is one positive and 1 to {_lib.LIST_MAX_G - 1} negatives")
+        if idx_d.dim() != 2 or idx_d.shape[0] % G:
+            raise ValueError(f"list rows must be [N G, F] with G = {G}, got {tuple(idx_d.shape)}")
+        N = idx_d.shape[0] // G
+        rank = torch.empty(N, dtype=torch.uint8, device=self.device)
+        logit = torch.empty(N * G, dtype=torch.float32, device=self.device) if want_logit else None
+        loss_b = torch.empty(N, dtype=torch.float32, device=self.device) if want_loss else None
+        self._steps(hyper)
+        _lib.check(self.lib.fmx_fm_list_online_run(self.table.c_struct(), hyper.ref(), _lib.RULES[rule], idx_d.data_ptr(), _ptr(xv_d),
+                                                   N, G, rank.data_ptr(), _ptr(logit), _ptr(loss_b), self.error.data_ptr(),
+                                                   self._stream()))
+        self._advance(N)
+        return rank, logit, loss_b
+
+    def list_online_run_fits(self, F, kp):
+        """Does fmx_fm_list_online_run take this table?  fmx_fm_online_run's field limit, plain fields, and no sort split (the
+        order of a list step's additions follows positions counted per sort piece)."""
+        t = self.table
+        return self.online_run_fits(F, kp) and not t.mapped and t._sort_split is None
+
     def online_run_mlp(self, hyper, rule, loss, params, k, hidden, n_layers, hedge, fm_term, hedge_b, hedge_s, alpha,
                        idx_d, xv_d, y_d, mlp_opt=None):
         """The online protocol for the classes with an MLP (fmx_online_run_mlp) -> forward() value per sample [N].

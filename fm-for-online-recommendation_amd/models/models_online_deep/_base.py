@@ -620,6 +620,62 @@ class OnlineFMBase(nn.Module):
         self._after_step()
         return out
 
+    def run_list_experiment(self, Xi, Xv, item_fields, negatives=None, n_neg=4, candidates=None, generator=None):
+        """The online protocol restated for lists: for every positive of Xi / Xv and its negatives predict the positive's rank
+        among them, then fit on that list alone -> (seconds, top-1 accuracy in %, the accuracy at every list i with
+        i % 1000 == 0 and at the last, {"correct", "wrong"}); correct: rank 0, no negative scores as high as the positive.
+        negatives: what fit_lists takes; at most 15 per positive.  On the device (fmx_fm_list_online_run: one workgroup walks the
+        stream) where run_experiment's loop runs there and the table has no sort split; otherwise a loop over fit_lists on one
+        list at a time -- the same bits.  negatives="hard" (or a fmx.pairwise.HardNegatives): blocks of remine_every positives,
+        as run_pair_experiment walks them."""
+        if self._has_mlp:
+            raise NotImplementedError(f"{self._name}.run_list_experiment: the list loss is built for the pure FM logit (FMAdam); the "
+                                      "classes with an MLP would need the softmax epilogue inside the MLP section")
+        limit = fmx._lib.LIST_MAX_G - 1
+        hard = fmx.pairwise.hard_negatives(negatives)
+        if (negatives is None or hard is not None) and not 1 <= int(n_neg) <= limit:
+            raise ValueError(f"{self._name}.run_list_experiment: n_neg = {n_neg}: a list holds 1 to {limit} negatives")
+        start = time()
+        self.train()
+
+        def walk(idx, xv, negs):
+            return self._list_loop(idx, xv, item_fields, negs, n_neg, candidates, generator)
+        if hard is not None:
+            ranks = self._walk_mined_blocks(Xi, Xv, hard, walk)
+        else:
+            idx_d, xv_d, _ = self._inputs(Xi, Xv)
+            ranks = [walk(idx_d, xv_d, negatives)]
+        ranks = [r for r in ranks if r is not None]
+        if not ranks:
+            return time() - start, 0.0, [], {"correct": 0, "wrong": 0}
+        return self._pair_experiment_result(start, torch.cat(ranks) == 0)
+
+    def _list_loop(self, idx_d, xv_d, item_fields, negatives, n_neg, candidates, generator):
+        """The predict-then-fit loop over the positives idx_d [n, F] and their negatives -> the positives' ranks uint8 [n] on the
+        device (None: no list)"""
+        n, e = idx_d.shape[0], self._engine
+        if n == 0:
+            return None
+        rows, xv = self._negative_rows(fmx.pairwise.assemble_lists, idx_d, xv_d, item_fields, negatives, n_neg, candidates, generator)
+        G = rows.shape[0] // n
+        if G - 1 > fmx._lib.LIST_MAX_G - 1:
+            raise ValueError(f"{self._name}.run_list_experiment: {G - 1} negatives per positive: a list holds 1 to "
+                             f"{fmx._lib.LIST_MAX_G - 1} negatives")
+        if self._device_loop_ok() and e.list_online_run_fits(self.field_size, self._table.kp):
+            rank, _, _ = e.list_online_run(self._hyper, self.update_rule, rows, G, xv)
+            return rank
+        fields = [int(f) for f in (item_fields if hasattr(item_fields, "__len__") else [item_fields])]
+        rank = torch.empty(n, dtype=torch.uint8, device=self.device)
+        strict, self.strict_index_check = self.strict_index_check, False      # one check after the loop, no sync inside it
+        try:
+            for i in range(n):
+                lst = rows[G * i:G * (i + 1)]
+                self.fit_lists(lst[:1], None if xv is None else xv[G * i:G * i + 1], fields, negatives=lst[1:, fields].reshape(1, G - 1, -1))
+                rank[i] = (e.logit[1:G] >= e.logit[0]).sum()     # the step's own forward: the logits before its update
+        finally:
+            self.strict_index_check = strict
+        return rank
+
     def run_pair_experiment(self, Xi, Xv, item_fields, negatives=None, n_neg=1, margin=0.0, candidates=None, generator=None):
         """The online protocol restated for pairs: for every pair predict (z_pos > z_neg), then fit on that pair alone ->
         (seconds, pairwise accuracy in %, the accuracy at every pair i with i % 1000 == 0 and at the last, {"correct", "wrong"}).
@@ -644,23 +700,31 @@ class OnlineFMBase(nn.Module):
     def _run_pair_experiment_hard(self, start, Xi, Xv, item_fields, hard, n_neg, margin, candidates, generator):
         """run_pair_experiment under mined negatives: blocks of remine_every positives, each mined under the model the blocks
         before it have trained (refresh_every = 1 per block), then walked by the same loop."""
+        def walk(idx, xv, block):
+            rows, xv = self._pair_rows(idx, xv, item_fields, block, n_neg, candidates, generator)
+            return self._pair_loop(rows, xv, item_fields, margin)
+        preds = self._walk_mined_blocks(Xi, Xv, hard, walk)
+        if not preds:
+            return time() - start, 0.0, [], {"correct": 0, "wrong": 0}
+        return self._pair_experiment_result(start, torch.cat(preds))
+
+    def _walk_mined_blocks(self, Xi, Xv, hard, walk):
+        """The block loop of the online experiments under mined negatives (pairs and lists): the positives in blocks of
+        hard.remine_every (None: one block), walk(idx, xv, block) on each with `block` the HardNegatives that mines it -- its
+        exclusions cut to the block's rows -> the list of walk's results"""
         idx_d, xv_d, _ = self._inputs(Xi, Xv)
         B = idx_d.shape[0]
         step = B if hard.remine_every is None else hard.remine_every
         block = fmx.pairwise.HardNegatives(hard.n_draw, None, 1)
         excl = fmx.recommend.exclusions_csr(hard.exclude, B, "cpu")
-        preds = []
+        out = []
         for b0 in range(0, B, max(step, 1)):
             b1 = min(B, b0 + step)
             if excl[0] is not None:
                 off, pos = excl
                 block.exclude = (off[b0:b1 + 1] - off[b0], pos[int(off[b0]):int(off[b1])])
-            rows, xv = self._pair_rows(idx_d[b0:b1], None if xv_d is None else xv_d[b0:b1], item_fields, block, n_neg, candidates,
-                                       generator)
-            preds.append(self._pair_loop(rows, xv, item_fields, margin))
-        if not preds:
-            return time() - start, 0.0, [], {"correct": 0, "wrong": 0}
-        return self._pair_experiment_result(start, torch.cat(preds))
+            out.append(walk(idx_d[b0:b1], None if xv_d is None else xv_d[b0:b1], block))
+        return out
 
     def _pair_loop(self, rows, xv, item_fields, margin):
         """The predict-then-fit loop over assembled pair rows -> the per-pair predictions uint8 [n] on the device (None: no pair)"""

@@ -260,6 +260,11 @@ class AFMAdam(nn.Module):
         raise NotImplementedError(f"{self._name}.fit_lists: the list loss is built for the pure FM logit (FMAdam); the attentional "
                                   "FM would need the softmax epilogue behind its own forward")
 
+    def run_list_experiment(self, Xi, Xv, item_fields, negatives=None, n_neg=4, candidates=None, generator=None):
+        """The online list protocol of FMAdam.run_list_experiment: not built for this model."""
+        raise NotImplementedError(f"{self._name}.run_list_experiment: the list loss is built for the pure FM logit (FMAdam); the "
+                                  "attentional FM would need the softmax epilogue behind its own forward")
+
     def run_pair_experiment(self, Xi, Xv, item_fields, negatives=None, n_neg=1, margin=0.0, candidates=None, generator=None,
                             attention=False):
         """OnlineFMBase.run_pair_experiment's arguments and 4-tuple; attention=True: for every pair predict z_pos > z_neg from the

@@ -467,6 +467,29 @@ int fmx_fm_list_stream(const fmx_table_t *table, const fmx_hyper_t *hyper, int32
                        int32_t B_lists, int32_t G, float inv_b, int32_t n_steps, void *workspace, int64_t workspace_bytes,
                        const fmx_fwd_out_t *fwd, float *loss_out, fmx_stream_t stream);
 
+/* The online predict-then-fit protocol restated for lists, on N device-resident lists idx [N G, F] (row G i the positive of list i,
+ * as above; xv of the same shape, or null: every value 1).  For every list, with the weights BEFORE the list's update:
+ *   rank_out[i]  (required) = the number of negatives of list i whose logit is >= the positive's -- 0: the positive is first; at
+ *                G = 2, rank_out[i] == 0 is fmx_fm_pair_online_run's pred_out[i];
+ *   logit_out[G i + j] (or null) = z_j;   loss_out[i] (or null) = loss_i, the bits of fmx_fm_list_step's loss_out[0] at B_lists = 1;
+ * then one list step on that list alone.  One workgroup of G waves walks the stream (wave j holds row j of the list, as
+ * fmx_fm_online_run's wavefront holds a sample).  The table ends bit-identical to N calls of fmx_fm_list_step with B_lists = 1,
+ * inv_b = 1: the terms of a row several members of a list name are added in the order the table update adds them on the sorted
+ * list of that step.  Under FMX_RULE_ADAM list i is step hyper->step + i + 1.
+ * The bias is read once and never written: it and its state (z / n, moments) stay bit-unchanged, as a list step leaves them.
+ * An out-of-range index sets *error to 1 and its occurrence is dropped, as in the step.
+ * Refusals, each decided on the host before any launch and naming the entry point: the shared list refusals above with N in the
+ * place of B_lists (N < 0: FMX_ERR_ARG), the rule against the layout and FMX_RULE_ADAM's hyper-parameters over N steps as
+ * fmx_fm_list_step checks them, rank_out null: FMX_ERR_ARG; n_fields > 4 * (64 / (kp / 4)) (a wave holds its row's table rows in
+ * registers, the field limit of fmx_fm_online_run): FMX_ERR_UNSUPPORTED; tables with a sort split (n_sort_fields > 0: the order of
+ * the step's additions follows positions counted per piece): FMX_ERR_UNSUPPORTED -- walk such tables with fmx_fm_list_step.
+ * N == 0 is FMX_OK, nothing is launched and the buffers may be null.
+ * Replaces: nothing -- the reference has no listwise loss; nearest: the pair objective of meta_fm.py:145-169 under the online
+ * protocol of fm_adam.py:90-119 (predict a sample, then fit on it). */
+int fmx_fm_list_online_run(const fmx_table_t *table, const fmx_hyper_t *hyper, int32_t rule, const int32_t *idx, const float *xv,
+                           int32_t N, int32_t G, uint8_t *rank_out, float *logit_out, float *loss_out, int32_t *error,
+                           fmx_stream_t stream);
+
 /* ---- the small relu MLP on top of the bi-interaction vector (online steps of DeepFM / NFM and the ONN classes) ----
  * params: per layer W [out, in] row-major then b [out]; layer 0 maps k -> hidden, the others hidden -> hidden; the network's
  * contribution to the logit is the sum of the last activation (reference deepfm_adam.py:82-88: there is no output layer).
