@@ -304,8 +304,8 @@ int fmx_afm_stream(const fmx_table_t *table, const fmx_hyper_t *hyper, int32_t r
   const size_t F = (size_t)table->n_fields;
   // Every batch is sorted on `stream` in front of its step, as fmx_afm_step does it: the steps are one plain queue of launches
   // (no side stream, no events; the sort-ahead loop of fmx_fm_stream is not used here).
-  fmx_hyper_t hs = hyper_for(hyper, rule);  // step s of the call is step hyper->step + s + 1 of the tables
-  for (int s = 0; s < n_steps; ++s, ++hs.step) {
+  for (int s = 0; s < n_steps; ++s) {
+    const fmx_hyper_t hs = hyper_at_step(hyper, rule, s);
     const size_t j = (size_t)(s % n_pool);
     if (int rc = afm_step_launches(table, &hs, rule, afm, idx_pool + j * B * F, xv_pool ? xv_pool + j * B * F : nullptr, y_pool + j * B, B,
                                    inv_b, workspace, w, attn_grad_out, loss_out ? loss_out + s : nullptr, error, opt, opt->step + s + 1, st))
@@ -330,8 +330,8 @@ int fmx_afm_online_run(const fmx_table_t *table, const fmx_hyper_t *hyper, int32
   const int nb = tune().afm_online_persistent ? afm_online_buffers(F, table->kp, afm->t, G, want_mom, mom) : 0;
   if (nb == 0) {
     // the per-sample launches of fmx_afm_step_opt(B = 1, inv_b = 1), queued without any host synchronisation
-    fmx_hyper_t hs = hyper_for(hyper, rule);
-    for (int i = 0; i < N; ++i, ++hs.step) {
+    for (int i = 0; i < N; ++i) {
+      const fmx_hyper_t hs = hyper_at_step(hyper, rule, i);
       if (int rc = afm_step_launches(table, &hs, rule, afm, idx + (size_t)i * F, xv ? xv + (size_t)i * F : nullptr, y + i, 1, 1.0f, workspace,
                                      w, attn_grad_out, loss_out ? loss_out + i : nullptr, error, opt, opt->step + i + 1, st,
                                      logit_out ? logit_out + i : nullptr))

@@ -232,8 +232,8 @@ int afm_pair_steps_call(const char *who, const fmx_table_t *table, const fmx_hyp
   if (int rc = check_afm_pair_step(table, hyper, rule, afm, B2, workspace, workspace_bytes, attn_grad_out, opt, with_opt, n_steps, w, who))
     return rc;
   const size_t F = (size_t)table->n_fields;
-  fmx_hyper_t hs = hyper_for(hyper, rule);  // step s of the call is step hyper->step + s + 1 of the tables
-  for (int s = 0; s < n_steps; ++s, ++hs.step) {
+  for (int s = 0; s < n_steps; ++s) {
+    const fmx_hyper_t hs = hyper_at_step(hyper, rule, s);
     const size_t j = (size_t)(s % n_pool);
     if (int rc = afm_step_launches(table, &hs, rule, afm, idx_pool + j * B2 * F, xv_pool ? xv_pool + j * B2 * F : nullptr, nullptr, B2,
                                    inv_b, workspace, w, attn_grad_out, loss_out ? loss_out + s : nullptr, error, with_opt ? opt : nullptr,
@@ -260,8 +260,8 @@ int afm_pair_online_call(const fmx_table_t *table, const fmx_hyper_t *hyper, int
   if (const int nb = afm_pair_online_buffers(table->n_fields, afm->k, table->kp, afm->t, opt->rule, &mom))
     return afm_pair_online_launch(table, hyper, rule, afm, idx, xv, N_pairs, margin, attn_grad_out, opt, logit_out, loss_out, error, nb, mom, st);
   const size_t F = (size_t)table->n_fields;
-  fmx_hyper_t hs = hyper_for(hyper, rule);
-  for (int i = 0; i < N_pairs; ++i, ++hs.step) {
+  for (int i = 0; i < N_pairs; ++i) {
+    const fmx_hyper_t hs = hyper_at_step(hyper, rule, i);
     if (int rc = afm_step_launches(table, &hs, rule, afm, idx + (size_t)i * 2 * F, xv ? xv + (size_t)i * 2 * F : nullptr, nullptr, 2, 1.0f,
                                    workspace, w, attn_grad_out, loss_out ? loss_out + i : nullptr, error, opt, opt->step + i + 1, st,
                                    logit_out ? logit_out + (size_t)i * 2 : nullptr, margin))

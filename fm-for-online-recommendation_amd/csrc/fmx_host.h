@@ -171,6 +171,13 @@ inline fmx_hyper_t hyper_for(const fmx_hyper_t *h, int rule) {
   return r;
 }
 
+// ... for step s of a call of several: step t = h->step + s + 1 of the tables (ADAM's bias correction; the others read no step)
+inline fmx_hyper_t hyper_at_step(const fmx_hyper_t *h, int rule, int s) {
+  fmx_hyper_t r = hyper_for(h, rule);
+  r.step += s;
+  return r;
+}
+
 // ... and as a kernel's argument: the kernels multiply by 1/alpha
 inline fmx_hyper_t kernel_hyper(const fmx_hyper_t *h, int rule) {
   fmx_hyper_t r = hyper_for(h, rule);

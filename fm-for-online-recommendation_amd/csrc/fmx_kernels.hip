@@ -1027,6 +1027,52 @@ int check_step_args(const fmx_table_t *table, const fmx_hyper_t *hyper, int32_t 
   return FMX_OK;
 }
 
+// ---- the step and the stream of the pure FM, once for its objectives (pointwise, pair, list).  The arguments have been
+//      checked; forward(idx, xv, y, st) launches the objective's forward into fwd; `tu` is the table as the update sees it
+//      (the list form's: list_update_table).  `rows`: the full-width rows of a step ----
+// One stream: sort -> forward -> update.  (Until r3 the sort ran on the side stream beside the forward pass; a dependency that
+// crosses streams costs 5 - 6 us on the device and four more runtime calls on the host, as much as the overlap of a 7 us forward
+// with an 18 us sort saves -- and a caller of single steps is host-bound: FMAdam.update_embedding 65 - 73 against 90 - 112 us
+// per batch, tools/class_surface_profile.py.  Loops over many batches: stream_run, where a sort launch covers 16 of them.)
+template <class Forward>
+int step_run(const fmx_table_t *table, const fmx_table_t *tu, const fmx_hyper_t *hyper, int32_t rule, const int32_t *idx, const float *xv,
+             const float *y, int32_t rows, float inv_b, const Workspace &w, const fmx_fwd_out_t *fwd, float *loss_out, hipStream_t st,
+             Forward &&forward) {
+  if (int rc = sort_impl(table, idx, rows, w.sorted, w.runs, fwd->error, st)) return rc;
+  if (int rc = forward(idx, xv, y, st)) return rc;
+  return update_impl(tu, hyper, rule, w, w.sorted, xv, fwd->S, fwd->dz, fwd->dz, nullptr, rows, fwd->loss, inv_b, loss_out, st, nullptr,
+                     fwd->sample_ld, fwd->error);
+}
+
+// n_steps of them over a pool of n_pool batches (pool_loop: the sorts of a group of steps in one launch, ahead of them)
+template <class Forward>
+int stream_run(const fmx_table_t *table, const fmx_table_t *tu, const fmx_hyper_t *hyper, int32_t rule, const int32_t *idx_pool,
+               const float *y_pool, int32_t n_pool, int32_t rows, float inv_b, int32_t n_steps, const Workspace &w, const fmx_fwd_out_t *fwd,
+               float *loss_out, hipStream_t st, Forward &&forward) {
+  auto before_update = [&](int, const int32_t *idx, const float *y, hipStream_t s_) { return forward(idx, nullptr, y, s_); };
+  auto update = [&](int s, const uint32_t *sorted, hipStream_t s_) {
+    const fmx_hyper_t hs = hyper_at_step(hyper, rule, s);
+    return update_impl(tu, &hs, rule, w, sorted, nullptr, fwd->S, fwd->dz, fwd->dz, nullptr, rows, fwd->loss, inv_b,
+                       loss_out ? loss_out + s : nullptr, s_, nullptr, fwd->sample_ld, fwd->error);
+  };
+  return pool_loop(table, idx_pool, y_pool, n_pool, rows, n_steps, w, fwd->error, st, before_update, update);
+}
+
+// the pointwise objective's forward, as step_run and stream_run call it (the pair's and the list's: pair_forward, list_forward)
+inline auto point_forward(const fmx_table_t *table, const fmx_hyper_t *hyper, int32_t B, int32_t loss_kind, float inv_b,
+                          const fmx_fwd_out_t *fwd) {
+  return [=](const int32_t *idx, const float *xv, const float *y, hipStream_t st) {
+    return forward_impl(table, hyper, idx, xv, y, B, loss_kind, inv_b, fwd, st);
+  };
+}
+
+// what the pair and list streams refuse of their pool and step count
+int check_pool_steps(int32_t n_pool, int32_t n_steps, const char *who) {
+  if (n_pool < 1) return fail(FMX_ERR_ARG, "%s: n_pool = %d must be >= 1", who, n_pool);
+  if (n_steps < 0) return fail(FMX_ERR_ARG, "%s: n_steps = %d must be >= 0", who, n_steps);
+  return FMX_OK;
+}
+
 #include "fmx_pair.inc"
 #include "fmx_list.inc"
 
@@ -1231,8 +1277,7 @@ static int deepfm_stream_impl(const fmx_table_t *table, const fmx_hyper_t *hyper
     return rc;
   };
   auto update = [&](int s, const uint32_t *sorted, hipStream_t st) {
-    fmx_hyper_t hs = hyper_for(hyper, rule);  // ... and step t = hyper->step + s + 1 of the tables (as in fmx_fm_stream)
-    hs.step += s;
+    const fmx_hyper_t hs = hyper_at_step(hyper, rule, s);  // ... and step t = hyper->step + s + 1 of the tables (as in stream_run)
     return update_impl(table, &hs, rule, w, sorted, nullptr, fwd->S, dz, fm_term ? dz : nullptr, gbi, B, nullptr, inv_b, nullptr, st, nullptr, 0,
                        fwd->error, &red);
   };
@@ -1269,8 +1314,7 @@ int fmx_deepfm_pair_stream(const fmx_table_t *table, const fmx_hyper_t *hyper, i
   const char *who = "fmx_deepfm_pair_stream";
   if (int rc = check_pair_args(table, hyper, idx_pool, B_pairs, "B_pairs", margin, who)) return rc;
   if (int rc = check_sort_geometry(table, pair_rows(B_pairs))) return rc;  // (as fmx_sort_occurrences reports it)
-  if (n_pool < 1) return fail(FMX_ERR_ARG, "%s: n_pool = %d must be >= 1", who, n_pool);
-  if (n_steps < 0) return fail(FMX_ERR_ARG, "%s: n_steps = %d must be >= 0", who, n_steps);
+  if (int rc = check_pool_steps(n_pool, n_steps, who)) return rc;
   return named(deepfm_stream_impl(table, hyper, rule, mlp, FMX_LOSS_NONE, fm_term, idx_pool, nullptr, n_pool, 2 * B_pairs, inv_b, n_steps, workspace,
                                   workspace_bytes, mlp_workspace, mlp_workspace_bytes, fwd, dz, gbi, grads, opt ? 0.f : lr_mlp, opt,
                                   loss_out, stream, who, margin),
@@ -1368,15 +1412,8 @@ int fmx_fm_step(const fmx_table_t *table, const fmx_hyper_t *hyper, int32_t rule
   if (!idx || !y) return fail(FMX_ERR_ARG, "fmx_fm_step: idx and y are required");
   hipStream_t st = static_cast<hipStream_t>(stream);
   if (int rc = check_workspace(table, B, workspace, workspace_bytes, "fmx_fm_step")) return rc;
-  const Workspace w = carve(table, B, workspace);
-  // One stream: sort -> forward -> update.  (Until r3 the sort ran on the side stream beside the forward pass; a dependency that
-  // crosses streams costs 5 - 6 us on the device and four more runtime calls on the host, as much as the overlap of a 7 us forward
-  // with an 18 us sort saves -- and a caller of single steps is host-bound: FMAdam.update_embedding 65 - 73 against 90 - 112 us
-  // per batch, tools/class_surface_profile.py.  Loops over many batches: fmx_fm_stream, where a sort launch covers 16 of them.)
-  if (int rc = sort_impl(table, idx, B, w.sorted, w.runs, fwd->error, st)) return rc;
-  if (int rc = forward_impl(table, hyper, idx, xv, y, B, loss_kind, inv_b, fwd, st)) return rc;
-  return update_impl(table, hyper, rule, w, w.sorted, xv, fwd->S, fwd->dz, fwd->dz, nullptr, B, fwd->loss, inv_b, loss_out, st,
-                     nullptr, fwd->sample_ld, fwd->error);
+  return step_run(table, table, hyper, rule, idx, xv, y, B, inv_b, carve(table, B, workspace), fwd, loss_out, st,
+                  point_forward(table, hyper, B, loss_kind, inv_b, fwd));
 }
 
 int fmx_fm_stream(const fmx_table_t *table, const fmx_hyper_t *hyper, int32_t rule, int32_t loss_kind,
@@ -1389,18 +1426,9 @@ int fmx_fm_stream(const fmx_table_t *table, const fmx_hyper_t *hyper, int32_t ru
   hipStream_t st = static_cast<hipStream_t>(stream);
   if (int rc = check_workspace(table, B, workspace, workspace_bytes, "fmx_fm_stream")) return rc;
   const Workspace w = carve(table, B, workspace);
-  if (!kernel_ms) {  // production path
-    auto forward = [&](int, const int32_t *idx, const float *y, hipStream_t st) {
-      return forward_impl(table, hyper, idx, nullptr, y, B, loss_kind, inv_b, fwd, st);
-    };
-    auto update = [&](int s, const uint32_t *sorted, hipStream_t st) {
-      fmx_hyper_t hs = hyper_for(hyper, rule);  // step s of the call is step t = hyper->step + s + 1 of the table
-      hs.step += s;
-      return update_impl(table, &hs, rule, w, sorted, nullptr, fwd->S, fwd->dz, fwd->dz, nullptr, B, fwd->loss, inv_b,
-                         loss_out ? loss_out + s : nullptr, st, nullptr, fwd->sample_ld, fwd->error);
-    };
-    return pool_loop(table, idx_pool, y_pool, n_pool, B, n_steps, w, fwd->error, st, forward, update);
-  }
+  if (!kernel_ms)  // production path
+    return stream_run(table, table, hyper, rule, idx_pool, y_pool, n_pool, B, inv_b, n_steps, w, fwd, loss_out, st,
+                      point_forward(table, hyper, B, loss_kind, inv_b, fwd));
 
   // measuring mode: everything on `stream`.  An event pair costs several microseconds of its own on this stack (slot 3
   // measures exactly that: two records with nothing between), so launches are timed in groups of up to 8 steps between
@@ -1441,8 +1469,7 @@ int fmx_fm_stream(const fmx_table_t *table, const fmx_hyper_t *hyper, int32_t ru
       (void)hipEventRecord(e[2], st);
       for (int r = 0; r < n && rc == FMX_OK; ++r) {
         const float *S = tmp + (size_t)r * region, *dz = S + (size_t)B * table->kp;
-        fmx_hyper_t hs = hyper_for(hyper, rule);
-        hs.step += first + r;
+        const fmx_hyper_t hs = hyper_at_step(hyper, rule, first + r);
         rc = update_impl(table, &hs, rule, w, w.sorted + (size_t)r * w.sorted_stride, nullptr, S, dz, dz, nullptr, B, dz + B, inv_b,
                          loss_out ? loss_out + first + r : nullptr, st, nullptr, 0, fwd->error);
       }

@@ -70,6 +70,13 @@ inline fmx_table_t list_update_table(const fmx_table_t *table, const Workspace &
   return t;
 }
 
+// the list objective's forward, as step_run and stream_run call it
+inline auto list_forward(const fmx_table_t *table, const fmx_hyper_t *hyper, int32_t rows, int32_t G, float inv_b, const fmx_fwd_out_t *fwd) {
+  return [=](const int32_t *idx, const float *xv, const float *, hipStream_t st) {
+    return list_forward_impl(table, hyper, idx, xv, rows, G, inv_b, fwd, st);
+  };
+}
+
 int list_step_call(const fmx_table_t *table, const fmx_hyper_t *hyper, int32_t rule, const int32_t *idx, const float *xv, int32_t B_lists,
                    int32_t G, float inv_b, void *workspace, int64_t workspace_bytes, const fmx_fwd_out_t *fwd, float *loss_out,
                    hipStream_t st) {
@@ -77,11 +84,7 @@ int list_step_call(const fmx_table_t *table, const fmx_hyper_t *hyper, int32_t r
   if (int rc = check_list_step(table, hyper, rule, idx, B_lists, G, workspace, workspace_bytes, fwd, 1, &rows, "fmx_fm_list_step")) return rc;
   const Workspace w = carve(table, rows, workspace);
   const fmx_table_t tu = list_update_table(table, w, workspace);
-  // one stream: sort -> list forward -> update, as fmx_fm_step
-  if (int rc = sort_impl(table, idx, rows, w.sorted, w.runs, fwd->error, st)) return rc;
-  if (int rc = list_forward_impl(table, hyper, idx, xv, rows, G, inv_b, fwd, st)) return rc;
-  return update_impl(&tu, hyper, rule, w, w.sorted, xv, fwd->S, fwd->dz, fwd->dz, nullptr, rows, fwd->loss, inv_b, loss_out, st, nullptr,
-                     fwd->sample_ld, fwd->error);
+  return step_run(table, &tu, hyper, rule, idx, xv, nullptr, rows, inv_b, w, fwd, loss_out, st, list_forward(table, hyper, rows, G, inv_b, fwd));
 }
 
 int list_stream_call(const fmx_table_t *table, const fmx_hyper_t *hyper, int32_t rule, const int32_t *idx_pool, int32_t n_pool,
@@ -91,21 +94,11 @@ int list_stream_call(const fmx_table_t *table, const fmx_hyper_t *hyper, int32_t
   int32_t rows = 0;
   if (int rc = check_list_step(table, hyper, rule, idx_pool, B_lists, G, workspace, workspace_bytes, fwd, n_steps > 0 ? n_steps : 0, &rows, who))
     return rc;
-  if (n_pool < 1) return fail(FMX_ERR_ARG, "%s: n_pool = %d must be >= 1", who, n_pool);
-  if (n_steps < 0) return fail(FMX_ERR_ARG, "%s: n_steps = %d must be >= 0", who, n_steps);
+  if (int rc = check_pool_steps(n_pool, n_steps, who)) return rc;
   const Workspace w = carve(table, rows, workspace);
   const fmx_table_t tu = list_update_table(table, w, workspace);
-  // fmx_fm_stream's loop on the rows of a step (pool_loop: the sorts of a group of steps in one launch, ahead of them)
-  auto forward = [&](int, const int32_t *idx, const float *, hipStream_t s_) {
-    return list_forward_impl(table, hyper, idx, nullptr, rows, G, inv_b, fwd, s_);
-  };
-  auto update = [&](int s, const uint32_t *sorted, hipStream_t s_) {
-    fmx_hyper_t hs = hyper_for(hyper, rule);  // step s of the call is step t = hyper->step + s + 1 of the table
-    hs.step += s;
-    return update_impl(&tu, &hs, rule, w, sorted, nullptr, fwd->S, fwd->dz, fwd->dz, nullptr, rows, fwd->loss, inv_b,
-                       loss_out ? loss_out + s : nullptr, s_, nullptr, fwd->sample_ld, fwd->error);
-  };
-  return pool_loop(table, idx_pool, nullptr, n_pool, rows, n_steps, w, fwd->error, st, forward, update);
+  return stream_run(table, &tu, hyper, rule, idx_pool, nullptr, n_pool, rows, inv_b, n_steps, w, fwd, loss_out, st,
+                    list_forward(table, hyper, rows, G, inv_b, fwd));
 }
 
 // fmx_fm_list_online_run: the checks, all on the host and in front of the launch; the kernel is k_fm_list_online (fmx_list_online.hip)

@@ -1266,8 +1266,7 @@ static int online_run_mlp_impl(const fmx_table_t *table, const fmx_hyper_t *hype
     if (int rc = mlp_launch(mlp, a, 1, table->kp, stream, who)) return rc;
     if (hedge) continue;  // Hedge trains the hidden layers and alpha only (reference deepfm_onn.py:109-154)
     if (int rc = sort_impl(table, idx_i, 1, w.sorted, w.runs, fwd->error, st)) return rc;
-    fmx_hyper_t hs = hyper_for(hyper, with_opt ? rule : -1);  // ... and step t = hyper->step + i + 1 of the tables
-    hs.step += i;
+    const fmx_hyper_t hs = hyper_at_step(hyper, with_opt ? rule : -1, i);  // ... and step t = hyper->step + i + 1 of the tables
     if (int rc = update_impl(table, &hs, rule, w, w.sorted, xv_i, fwd->S, dz, fm_term ? dz : nullptr, gbi, 1, nullptr, 1.0f, nullptr,
                              st, nullptr, 0, fwd->error))
       return rc;
@@ -1488,8 +1487,7 @@ int fmx_online_run_mlp_pair(const fmx_table_t *table, const fmx_hyper_t *hyper, 
     mlp_pair_fit_args(a, hyper, rule, margin, 1.0f, opt, opt ? opt->step + i + 1 : 0);
     if (int rc = mlp_launch(mlp, a, 2, table->kp, stream, who, true)) return rc;
     if (int rc = sort_impl(table, idx_i, 2, w.sorted, w.runs, fwd->error, st)) return rc;
-    fmx_hyper_t hs = hyper_for(hyper, opt ? rule : -1);  // pair i is step t = hyper->step + i + 1 of the tables
-    hs.step += i;
+    const fmx_hyper_t hs = hyper_at_step(hyper, opt ? rule : -1, i);  // pair i is step t = hyper->step + i + 1 of the tables
     if (int rc = update_impl(table, &hs, rule, w, w.sorted, xv_i, fwd->S, dz, fm_term ? dz : nullptr, gbi, 2, nullptr, 1.0f, nullptr, st,
                              nullptr, 0, fwd->error))
       return rc;

@@ -60,17 +60,20 @@ int check_pair_step(const fmx_table_t *table, const fmx_hyper_t *hyper, int32_t 
   return check_workspace(table, pair_rows(B_pairs), workspace, workspace_bytes, who);
 }
 
+// the pair objective's forward, as step_run and stream_run call it
+inline auto pair_forward(const fmx_table_t *table, const fmx_hyper_t *hyper, int32_t B2, float margin, float inv_b, const fmx_fwd_out_t *fwd) {
+  return [=](const int32_t *idx, const float *xv, const float *, hipStream_t st) {
+    return pair_forward_impl(table, hyper, idx, xv, B2, margin, inv_b, fwd, st);
+  };
+}
+
 int pair_step_call(const fmx_table_t *table, const fmx_hyper_t *hyper, int32_t rule, const int32_t *idx, const float *xv, int32_t B_pairs,
                    float margin, float inv_b, void *workspace, int64_t workspace_bytes, const fmx_fwd_out_t *fwd, float *loss_out,
                    hipStream_t st) {
   if (int rc = check_pair_step(table, hyper, rule, idx, B_pairs, margin, workspace, workspace_bytes, fwd, 1, "fmx_fm_pair_step")) return rc;
   const int32_t B2 = 2 * B_pairs;
-  const Workspace w = carve(table, B2, workspace);
-  // one stream: sort -> pair forward -> update, as fmx_fm_step
-  if (int rc = sort_impl(table, idx, B2, w.sorted, w.runs, fwd->error, st)) return rc;
-  if (int rc = pair_forward_impl(table, hyper, idx, xv, B2, margin, inv_b, fwd, st)) return rc;
-  return update_impl(table, hyper, rule, w, w.sorted, xv, fwd->S, fwd->dz, fwd->dz, nullptr, B2, fwd->loss, inv_b, loss_out, st, nullptr,
-                     fwd->sample_ld, fwd->error);
+  return step_run(table, table, hyper, rule, idx, xv, nullptr, B2, inv_b, carve(table, B2, workspace), fwd, loss_out, st,
+                  pair_forward(table, hyper, B2, margin, inv_b, fwd));
 }
 
 int pair_stream_call(const fmx_table_t *table, const fmx_hyper_t *hyper, int32_t rule, const int32_t *idx_pool, int32_t n_pool,
@@ -79,20 +82,8 @@ int pair_stream_call(const fmx_table_t *table, const fmx_hyper_t *hyper, int32_t
   const char *who = "fmx_fm_pair_stream";
   if (int rc = check_pair_step(table, hyper, rule, idx_pool, B_pairs, margin, workspace, workspace_bytes, fwd, n_steps > 0 ? n_steps : 0, who))
     return rc;
-  if (n_pool < 1) return fail(FMX_ERR_ARG, "%s: n_pool = %d must be >= 1", who, n_pool);
-  if (n_steps < 0) return fail(FMX_ERR_ARG, "%s: n_steps = %d must be >= 0", who, n_steps);
+  if (int rc = check_pool_steps(n_pool, n_steps, who)) return rc;
   const int32_t B2 = 2 * B_pairs;
-  const Workspace w = carve(table, B2, workspace);
-  // fmx_fm_stream's loop on the 2B rows of a step (pool_loop: the sorts of a group of steps in one launch, ahead of them)
-  auto forward = [&](int, const int32_t *idx, const float *, hipStream_t s_) {
-    return pair_forward_impl(table, hyper, idx, nullptr, B2, margin, inv_b, fwd, s_);
-  };
-  auto update = [&](int s, const uint32_t *sorted, hipStream_t s_) {
-    fmx_hyper_t hs = hyper_for(hyper, rule);  // step s of the call is step t = hyper->step + s + 1 of the table
-    hs.step += s;
-    return update_impl(table, &hs, rule, w, sorted, nullptr, fwd->S, fwd->dz, fwd->dz, nullptr, B2, fwd->loss, inv_b,
-                       loss_out ? loss_out + s : nullptr, s_, nullptr, fwd->sample_ld, fwd->error);
-  };
-  return pool_loop(table, idx_pool, nullptr, n_pool, B2, n_steps, w, fwd->error, st, forward, update);
+  return stream_run(table, table, hyper, rule, idx_pool, nullptr, n_pool, B2, inv_b, n_steps, carve(table, B2, workspace), fwd, loss_out, st,
+                    pair_forward(table, hyper, B2, margin, inv_b, fwd));
 }
-

@@ -10,6 +10,7 @@ import torch
 
 from . import _lib
 from .engine import FMEngine, MlpOpt, _ptr
+from .pairwise import n_pairs
 from .table import FlatTable
 
 
@@ -60,6 +61,7 @@ class AFMEngine:
             self._alloc(max(B, self.max_batch))
 
     _stream = FMEngine._stream
+    _steps, _advance, _counted = FMEngine._steps, FMEngine._advance, FMEngine._counted     # (opt, an AfmOpt, is its mlp_opt)
     to_device = FMEngine.to_device
     check_error_flag = FMEngine.check_error_flag
 
@@ -79,19 +81,14 @@ class AFMEngine:
         and its step count advances; None leaves them to the caller."""
         B = idx_d.shape[0]
         self._ensure(B)
-        if self.table.layout == "moments":
-            hyper.c.step = self.table.step
         head = (self.table.c_struct(), hyper.ref(), _lib.RULES[rule], C.byref(self.c_afm), idx_d.data_ptr(), _ptr(xv_d),
                 y_d.data_ptr(), B, 1.0 / B if inv_b is None else inv_b, self.workspace.data_ptr(), self.workspace.numel() * 4,
                 self.grad.data_ptr())
         tail = (self.loss_out.data_ptr(), self.error.data_ptr(), self._stream(stream))
         if opt is None:
-            _lib.check(self.lib.fmx_afm_step(*head, *tail))
+            self._counted(self.lib.fmx_afm_step, (*head, *tail), hyper)
         else:
-            _lib.check(self.lib.fmx_afm_step_opt(*head, opt.ref(), *tail))
-            opt.step += 1
-        if self.table.layout == "moments":
-            self.table.step += 1
+            self._counted(self.lib.fmx_afm_step_opt, (*head, opt.ref(), *tail), hyper, 1, opt)
 
     def stream(self, hyper, rule, idx_pool, xv_pool, y_pool, B, n_steps, opt, inv_b=None, losses=None, stream=None):
         """n_steps steps over a device-resident pool in one call (fmx_afm_stream; no sync here): idx_pool [n_pool, B, F] int32,
@@ -104,16 +101,11 @@ class AFMEngine:
         assert xv_pool is None or (xv_pool.dtype == torch.float32 and xv_pool.is_contiguous() and xv_pool.numel() == idx_pool.numel())
         assert losses is None or (losses.dtype == torch.float32 and losses.numel() >= n_steps)
         self._ensure(B)
-        if self.table.layout == "moments":
-            hyper.c.step = self.table.step
-        _lib.check(self.lib.fmx_afm_stream(self.table.c_struct(), hyper.ref(), _lib.RULES[rule], C.byref(self.c_afm),
-                                           idx_pool.data_ptr(), _ptr(xv_pool), y_pool.data_ptr(), n_pool, B,
-                                           1.0 / B if inv_b is None else inv_b, n_steps, self.workspace.data_ptr(),
-                                           self.workspace.numel() * 4, self.grad.data_ptr(), opt.ref(), _ptr(losses),
-                                           self.error.data_ptr(), self._stream(stream)))
-        opt.step += n_steps
-        if self.table.layout == "moments":
-            self.table.step += n_steps
+        self._counted(self.lib.fmx_afm_stream, (self.table.c_struct(), hyper.ref(), _lib.RULES[rule], C.byref(self.c_afm),
+                                                idx_pool.data_ptr(), _ptr(xv_pool), y_pool.data_ptr(), n_pool, B,
+                                                1.0 / B if inv_b is None else inv_b, n_steps, self.workspace.data_ptr(),
+                                                self.workspace.numel() * 4, self.grad.data_ptr(), opt.ref(), _ptr(losses),
+                                                self.error.data_ptr(), self._stream(stream)), hyper, n_steps, opt)
 
     def online_run(self, hyper, rule, idx_d, xv_d, y_d, opt, logits=None, losses=None, stream=None):
         """The online predict-then-fit loop over a device-resident stream in one call (fmx_afm_online_run; no sync here): idx_d
@@ -128,22 +120,17 @@ class AFMEngine:
         for out in (logits, losses):
             assert out is None or (out.dtype == torch.float32 and out.is_contiguous() and out.numel() >= N)
         self._ensure(1)
-        if self.table.layout == "moments":
-            hyper.c.step = self.table.step
-        _lib.check(self.lib.fmx_afm_online_run(self.table.c_struct(), hyper.ref(), _lib.RULES[rule], C.byref(self.c_afm),
-                                               idx_d.data_ptr(), _ptr(xv_d), y_d.data_ptr(), N, self.workspace.data_ptr(),
-                                               self.workspace.numel() * 4, self.grad.data_ptr(), opt.ref(), _ptr(logits),
-                                               _ptr(losses), self.error.data_ptr(), self._stream(stream)))
-        opt.step += N
-        if self.table.layout == "moments":
-            self.table.step += N
+        self._counted(self.lib.fmx_afm_online_run, (self.table.c_struct(), hyper.ref(), _lib.RULES[rule], C.byref(self.c_afm),
+                                                    idx_d.data_ptr(), _ptr(xv_d), y_d.data_ptr(), N, self.workspace.data_ptr(),
+                                                    self.workspace.numel() * 4, self.grad.data_ptr(), opt.ref(), _ptr(logits),
+                                                    _ptr(losses), self.error.data_ptr(), self._stream(stream)), hyper, N, opt)
 
     # ---- pairwise-ranking (BPR) training: rows [2P, F] from fmx.pairwise.assemble_pairs, row 2p the positive, 2p + 1 the negative ----
     def _pair_rows(self, idx_d, xv_d):
-        assert idx_d.dtype == torch.int32 and idx_d.is_contiguous() and idx_d.dim() == 2 and idx_d.shape[0] % 2 == 0
-        assert idx_d.shape[1] == self.table.n_fields
+        P = n_pairs(idx_d)
+        assert idx_d.dtype == torch.int32 and idx_d.is_contiguous() and idx_d.shape[1] == self.table.n_fields
         assert xv_d is None or (xv_d.dtype == torch.float32 and xv_d.is_contiguous() and xv_d.shape == idx_d.shape)
-        return idx_d.shape[0] // 2
+        return P
 
     def pair_forward(self, hyper, idx_d, xv_d=None, margin=0.0, inv_b=None, dz=None, stream=None):
         """-> P; the 2P logits in self.logit[:2P] (the bits of forward()), the pair losses in self.loss_b[0:2P:2] (the odd slots
@@ -162,18 +149,13 @@ class AFMEngine:
         attention parameters take its rule in the same call (fmx_afm_pair_step_opt) and its step count advances."""
         P = self._pair_rows(idx_d, xv_d)
         self._ensure(2 * P)
-        if self.table.layout == "moments":
-            hyper.c.step = self.table.step
         head = (self.table.c_struct(), hyper.ref(), _lib.RULES[rule], C.byref(self.c_afm), idx_d.data_ptr(), _ptr(xv_d), P, margin,
                 1.0 / P if inv_b is None else inv_b, self.workspace.data_ptr(), self.workspace.numel() * 4, self.grad.data_ptr())
         tail = (self.logit.data_ptr(), self.loss_out.data_ptr(), self.error.data_ptr(), self._stream(stream))
         if opt is None:
-            _lib.check(self.lib.fmx_afm_pair_step(*head, *tail))
+            self._counted(self.lib.fmx_afm_pair_step, (*head, *tail), hyper)
         else:
-            _lib.check(self.lib.fmx_afm_pair_step_opt(*head, opt.ref(), *tail))
-            opt.step += 1
-        if self.table.layout == "moments":
-            self.table.step += 1
+            self._counted(self.lib.fmx_afm_pair_step_opt, (*head, opt.ref(), *tail), hyper, 1, opt)
 
     def pair_stream(self, hyper, rule, idx_pool, xv_pool, P, n_steps, opt, margin=0.0, inv_b=None, losses=None, stream=None):
         """n_steps pair steps over a device-resident pool in one call (fmx_afm_pair_stream; no sync here): idx_pool
@@ -185,16 +167,11 @@ class AFMEngine:
         assert xv_pool is None or (xv_pool.dtype == torch.float32 and xv_pool.is_contiguous() and xv_pool.numel() == idx_pool.numel())
         assert losses is None or (losses.dtype == torch.float32 and losses.numel() >= n_steps)
         self._ensure(2 * P)
-        if self.table.layout == "moments":
-            hyper.c.step = self.table.step
-        _lib.check(self.lib.fmx_afm_pair_stream(self.table.c_struct(), hyper.ref(), _lib.RULES[rule], C.byref(self.c_afm),
-                                                idx_pool.data_ptr(), _ptr(xv_pool), n_pool, P, margin,
-                                                1.0 / P if inv_b is None else inv_b, n_steps, self.workspace.data_ptr(),
-                                                self.workspace.numel() * 4, self.grad.data_ptr(), opt.ref(), _ptr(losses),
-                                                self.error.data_ptr(), self._stream(stream)))
-        opt.step += n_steps
-        if self.table.layout == "moments":
-            self.table.step += n_steps
+        self._counted(self.lib.fmx_afm_pair_stream, (self.table.c_struct(), hyper.ref(), _lib.RULES[rule], C.byref(self.c_afm),
+                                                     idx_pool.data_ptr(), _ptr(xv_pool), n_pool, P, margin,
+                                                     1.0 / P if inv_b is None else inv_b, n_steps, self.workspace.data_ptr(),
+                                                     self.workspace.numel() * 4, self.grad.data_ptr(), opt.ref(), _ptr(losses),
+                                                     self.error.data_ptr(), self._stream(stream)), hyper, n_steps, opt)
 
     def pair_online_run(self, hyper, rule, idx_d, xv_d, opt, margin=0.0, logits=None, losses=None, stream=None):
         """The online protocol for pairs in one call (fmx_afm_pair_online_run; no sync here): every pair of idx_d [2N, F] is
@@ -205,15 +182,10 @@ class AFMEngine:
         assert logits is None or (logits.dtype == torch.float32 and logits.is_contiguous() and logits.numel() >= 2 * N)
         assert losses is None or (losses.dtype == torch.float32 and losses.is_contiguous() and losses.numel() >= N)
         self._ensure(2)
-        if self.table.layout == "moments":
-            hyper.c.step = self.table.step
-        _lib.check(self.lib.fmx_afm_pair_online_run(self.table.c_struct(), hyper.ref(), _lib.RULES[rule], C.byref(self.c_afm),
-                                                    idx_d.data_ptr(), _ptr(xv_d), N, margin, self.workspace.data_ptr(),
-                                                    self.workspace.numel() * 4, self.grad.data_ptr(), opt.ref(), _ptr(logits),
-                                                    _ptr(losses), self.error.data_ptr(), self._stream(stream)))
-        opt.step += N
-        if self.table.layout == "moments":
-            self.table.step += N
+        self._counted(self.lib.fmx_afm_pair_online_run, (self.table.c_struct(), hyper.ref(), _lib.RULES[rule], C.byref(self.c_afm),
+                                                         idx_d.data_ptr(), _ptr(xv_d), N, margin, self.workspace.data_ptr(),
+                                                         self.workspace.numel() * 4, self.grad.data_ptr(), opt.ref(), _ptr(logits),
+                                                         _ptr(losses), self.error.data_ptr(), self._stream(stream)), hyper, N, opt)
 
     def pair_online_form(self, attn_rule):
         """-> (tile buffers, moments in LDS) of the form pair_online_run takes for this table under the attention rule

@@ -5,6 +5,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from .pairwise import n_pairs
 from .table import FlatTable
 
 class Hyper:
@@ -36,6 +37,19 @@ def normalize_inputs(Xi, Xv, n_fields, feature_sizes=None):
 
 def _ptr(t):
     return None if t is None else t.data_ptr()
+
+
+def _loss_cap(loss_out, n_steps):
+    """loss_out (a contiguous device tensor with an element per step, or None) against the steps a call is asked for"""
+    if loss_out is not None and (loss_out.numel() < n_steps or not loss_out.is_contiguous()):
+        raise ValueError(f"loss_out holds {loss_out.numel()} steps, {n_steps} asked for")
+
+
+def _list_G(G):
+    G = int(G)
+    if not 2 <= G <= _lib.LIST_MAX_G:
+        raise ValueError(f"G = {G}: a list is one positive and 1 to {_lib.LIST_MAX_G - 1} negatives")
+    return G
 
 
 def mlp_struct(params, k, hidden, n_layers):
@@ -126,6 +140,41 @@ class FMEngine:
         if self.table.layout == "moments":
             self.table.step += int(n)
 
+    def _counted(self, fn, args, hyper=None, n=1, mlp_opt=None):
+        """One checked foreign call fn(*args) that takes n steps.  hyper (the one among args, when the call counts the table's
+        steps): _steps before it, _advance(n) behind it.  mlp_opt (an MlpOpt among args, or None): its struct takes its count
+        before the call and the count advances by n behind it."""
+        if hyper is not None:
+            self._steps(hyper)
+        if mlp_opt is not None:
+            mlp_opt.c.step = mlp_opt.step
+        _lib.check(fn(*args))
+        if hyper is not None:
+            self._advance(n)
+        if mlp_opt is not None:
+            mlp_opt.step += n
+
+    def _bound_run(self, fn, fixed, tail, hyper, loss_out, keep, mlp_opt=None):
+        """-> run(n_steps) of a prepare_*: _counted with everything bound -- the cap check, the counters and ONE foreign call
+        fn(*fixed, n_steps, *tail).  The bound structs are hyper's and mlp_opt's own: a second call continues both counts.
+        `keep`: what the pointers in fixed / tail refer to, kept alive with the closure."""
+        assert loss_out is None or loss_out.is_contiguous()
+        check, steps, advance = _lib.check, self._steps, self._advance
+        cap = None if loss_out is None else loss_out.numel()
+
+        def run(n_steps):
+            if cap is not None and n_steps > cap:
+                _loss_cap(loss_out, n_steps)
+            steps(hyper)
+            if mlp_opt is not None:
+                mlp_opt.c.step = mlp_opt.step
+            check(fn(*fixed, n_steps, *tail))
+            advance(n_steps)
+            if mlp_opt is not None:
+                mlp_opt.step += n_steps
+        run.keep = keep
+        return run
+
     def _ws_bytes(self):
         return self.workspace.numel() * self.workspace.element_size()
 
@@ -213,12 +262,9 @@ class FMEngine:
             loss_b = self.loss_b if loss_b is None else loss_b
             S_p, dzf_p, dzb_p, loss_p = S.data_ptr(), dz_first.data_ptr(), _ptr(dz_bi), loss_b.data_ptr()
         ws = self.workspace if workspace is None else workspace
-        self._steps(hyper)
-        _lib.check(self.lib.fmx_fm_update(self.table.c_struct(), hyper.ref(), _lib.RULES[rule], ws.data_ptr(), ws.numel() * ws.element_size(),
-                                          _ptr(xv_d), S_p, dzf_p, dzb_p, _ptr(gbi), B, ld,
-                                          loss_p if with_loss else None, inv_b,
-                                          self.loss_out.data_ptr() if with_loss else None, self._stream(stream)))
-        self._advance(1)
+        self._counted(self.lib.fmx_fm_update, (self.table.c_struct(), hyper.ref(), _lib.RULES[rule], ws.data_ptr(), ws.numel() * ws.element_size(),
+                                               _ptr(xv_d), S_p, dzf_p, dzb_p, _ptr(gbi), B, ld, loss_p if with_loss else None, inv_b,
+                                               self.loss_out.data_ptr() if with_loss else None, self._stream(stream)), hyper)
 
     def step(self, hyper, rule, loss, idx_d, xv_d, y_d, inv_b=None):
         """One pure-FM mini-batch step; the mean loss lands in self.loss_out[0] (no sync here)."""
@@ -227,13 +273,9 @@ class FMEngine:
         cached = getattr(self, "_step_out", None)
         if cached is None or cached[0] != self.S.data_ptr():       # the output struct only changes with the buffers it points at
             self._step_out = cached = (self.S.data_ptr(), self._fwd_out(want_first=False, want_bi=False))
-        out = cached[1]
-        inv_b = 1.0 / B if inv_b is None else inv_b
-        self._steps(hyper)
-        _lib.check(self.lib.fmx_fm_step(self.table.c_struct(), hyper.ref(), _lib.RULES[rule], _lib.LOSSES[loss],
-                                        idx_d.data_ptr(), _ptr(xv_d), y_d.data_ptr(), B, inv_b, self.workspace.data_ptr(), self._ws_bytes(),
-                                        C.byref(out), self.loss_out.data_ptr(), self._stream()))
-        self._advance(1)
+        self._counted(self.lib.fmx_fm_step, (self.table.c_struct(), hyper.ref(), _lib.RULES[rule], _lib.LOSSES[loss], idx_d.data_ptr(),
+                                             _ptr(xv_d), y_d.data_ptr(), B, 1.0 / B if inv_b is None else inv_b, self.workspace.data_ptr(),
+                                             self._ws_bytes(), C.byref(cached[1]), self.loss_out.data_ptr(), self._stream()), hyper)
 
     def stream(self, hyper, rule, loss, idx_pool, y_pool, n_steps, loss_out=None, timed=False):
         """The online loop over a resident pool of batches (fmx_fm_stream).  Returns per-launch ms [sort, forward, update, empty event pair] when timed (the measuring mode repeats launches: see fmx.h)."""
@@ -242,11 +284,9 @@ class FMEngine:
         self._ensure(B)
         out = self._fwd_out(want_first=False, want_bi=False)
         ms = (C.c_float * 4)() if timed else None
-        self._steps(hyper)
-        _lib.check(self.lib.fmx_fm_stream(self.table.c_struct(), hyper.ref(), _lib.RULES[rule], _lib.LOSSES[loss],
-                                          idx_pool.data_ptr(), y_pool.data_ptr(), n_pool, B, 1.0 / B, n_steps,
-                                          self.workspace.data_ptr(), self._ws_bytes(), C.byref(out), _ptr(loss_out), ms, self._stream()))
-        self._advance(n_steps)
+        self._counted(self.lib.fmx_fm_stream, (self.table.c_struct(), hyper.ref(), _lib.RULES[rule], _lib.LOSSES[loss], idx_pool.data_ptr(),
+                                               y_pool.data_ptr(), n_pool, B, 1.0 / B, n_steps, self.workspace.data_ptr(), self._ws_bytes(),
+                                               C.byref(out), _ptr(loss_out), ms, self._stream()), hyper, n_steps)
         return None if ms is None else [float(v) for v in ms]
 
     def prepare_stream(self, hyper, rule, loss, idx_pool, y_pool, loss_out=None, stream=None):
@@ -257,26 +297,12 @@ class FMEngine:
         loss_out alive and does not grow the engine between prepare and run."""
         n_pool, B, F = idx_pool.shape
         assert F == self.table.n_fields and y_pool.shape == (n_pool, B)
-        assert loss_out is None or loss_out.is_contiguous()
         self._ensure(B)
         out = self._fwd_out(want_first=False, want_bi=False)
-        fn, check = self.lib.fmx_fm_stream, _lib.check
         fixed = (self.table.c_struct(), hyper.ref(), _lib.RULES[rule], _lib.LOSSES[loss], idx_pool.data_ptr(), y_pool.data_ptr(),
                  n_pool, B, 1.0 / B)
         tail = (self.workspace.data_ptr(), self._ws_bytes(), C.byref(out), _ptr(loss_out), None, self._stream(stream))
-        cap = None if loss_out is None else loss_out.numel()
-        keep = (out, hyper, idx_pool, y_pool, loss_out, self.workspace)   # referenced by the closure: stay alive with it
-
-        steps, advance = self._steps, self._advance
-
-        def run(n_steps):
-            if cap is not None and n_steps > cap:
-                raise ValueError(f"loss_out holds {cap} steps, {n_steps} asked for")
-            steps(hyper)
-            check(fn(*fixed, n_steps, *tail))
-            advance(n_steps)        # (the bound struct is hyper's own: a second call continues the table's count)
-        run.keep = keep
-        return run
+        return self._bound_run(self.lib.fmx_fm_stream, fixed, tail, hyper, loss_out, (out, hyper, idx_pool, y_pool, loss_out, self.workspace))
 
     def prepare_deepfm_stream(self, hyper, rule, loss, params, grads, k, hidden, n_layers, lr_mlp, idx_pool, y_pool, loss_out=None,
                               stream=None, fm_term=True, mlp_opt=None):
@@ -290,27 +316,20 @@ class FMEngine:
         the table's and mlp_opt's step counts by its steps."""
         n_pool, B, F = idx_pool.shape
         assert F == self.table.n_fields and y_pool.shape == (n_pool, B)
-        assert loss_out is None or loss_out.is_contiguous()
         self._ensure(B)
         out = self._fwd_out(want_first=False, want_bi=True)
         m = self._mlp_struct(params, k, hidden, n_layers)
         self._mlp_big_buffers(m, k, hidden, n_layers, B)
-        fn, check = self.lib.fmx_deepfm_stream, _lib.check
         fixed = (self.table.c_struct(), hyper.ref(), _lib.RULES[rule], C.byref(m), _lib.LOSSES[loss], int(bool(fm_term)), idx_pool.data_ptr(), y_pool.data_ptr(),
                  n_pool, B, 1.0 / B)
+        keep = (out, m, hyper, mlp_opt, params, grads, idx_pool, y_pool, loss_out, self.workspace, self._mlp_ws, self._mlp_dz, self._mlp_gbi)
+        ws = (self.workspace.data_ptr(), self._ws_bytes(), self._mlp_ws.data_ptr())
+        bufs = (C.byref(out), self._mlp_dz.data_ptr(), self._mlp_gbi.data_ptr(), grads.data_ptr())
         if mlp_opt is not None:
-            return self._prepare_deepfm_stream_opt(hyper, mlp_opt, fixed, out, m, params, grads, idx_pool, y_pool, loss_out, stream)
-        tail = (self.workspace.data_ptr(), self._ws_bytes(), self._mlp_ws.data_ptr(), C.byref(out), self._mlp_dz.data_ptr(),
-                self._mlp_gbi.data_ptr(), grads.data_ptr(), lr_mlp, _ptr(loss_out), self._stream(stream))
-        cap = None if loss_out is None else loss_out.numel()
-        keep = (out, m, hyper, params, grads, idx_pool, y_pool, loss_out, self.workspace, self._mlp_ws, self._mlp_dz, self._mlp_gbi)
-
-        def run(n_steps):
-            if cap is not None and n_steps > cap:
-                raise ValueError(f"loss_out holds {cap} steps, {n_steps} asked for")
-            check(fn(*fixed, n_steps, *tail))
-        run.keep = keep
-        return run
+            tail = (*ws, self._mlp_ws.numel() * 4, *bufs, mlp_opt.ref(), _ptr(loss_out), self._stream(stream))
+            return self._bound_run(self.lib.fmx_deepfm_stream_opt, fixed, tail, hyper, loss_out, keep, mlp_opt)
+        # (this path's tables are in the weights or the FTRL layout: the counters of _bound_run have nothing to count)
+        return self._bound_run(self.lib.fmx_deepfm_stream, fixed, (*ws, *bufs, lr_mlp, _ptr(loss_out), self._stream(stream)), hyper, loss_out, keep)
 
     def prepare_deepfm_pair_stream(self, hyper, rule, params, grads, k, hidden, n_layers, lr_mlp, idx_pool, margin=0.0, loss_out=None,
                                    stream=None, fm_term=True, mlp_opt=None):
@@ -320,53 +339,18 @@ class FMEngine:
         mlp_opt's by its steps.  The caller keeps the tensors alive and does not grow the engine between prepare and run."""
         n_pool, B2, F = idx_pool.shape
         assert F == self.table.n_fields and B2 % 2 == 0 and B2 >= 2 and idx_pool.is_contiguous()
-        assert loss_out is None or loss_out.is_contiguous()
         B = B2 // 2
         self._ensure(B2)
         out = self._fwd_out(want_first=False, want_bi=True)
         m = self._mlp_struct(params, k, hidden, n_layers)
         self._mlp_big_buffers(m, k, hidden, n_layers, B2)
-        fn, check = self.lib.fmx_deepfm_pair_stream, _lib.check
         fixed = (self.table.c_struct(), hyper.ref(), _lib.RULES[rule], C.byref(m), int(bool(fm_term)), idx_pool.data_ptr(), n_pool, B,
                  float(margin), 1.0 / B)
         tail = (self.workspace.data_ptr(), self._ws_bytes(), self._mlp_ws.data_ptr(), self._mlp_ws.numel() * 4, C.byref(out),
                 self._mlp_dz.data_ptr(), self._mlp_gbi.data_ptr(), grads.data_ptr(), float(lr_mlp),
                 None if mlp_opt is None else mlp_opt.ref(), _ptr(loss_out), self._stream(stream))
-        cap = None if loss_out is None else loss_out.numel()
         keep = (out, m, hyper, mlp_opt, params, grads, idx_pool, loss_out, self.workspace, self._mlp_ws, self._mlp_dz, self._mlp_gbi)
-        steps, advance = self._steps, self._advance
-
-        def run(n_steps):
-            if cap is not None and n_steps > cap:
-                raise ValueError(f"loss_out holds {cap} steps, {n_steps} asked for")
-            steps(hyper)
-            if mlp_opt is not None:
-                mlp_opt.c.step = mlp_opt.step     # (the bound structs are hyper's and mlp_opt's own: a second call continues both counts)
-            check(fn(*fixed, n_steps, *tail))
-            advance(n_steps)
-            if mlp_opt is not None:
-                mlp_opt.step += n_steps
-        run.keep = keep
-        return run
-
-    def _prepare_deepfm_stream_opt(self, hyper, mlp_opt, fixed, out, m, params, grads, idx_pool, y_pool, loss_out, stream):
-        fn, check = self.lib.fmx_deepfm_stream_opt, _lib.check
-        tail = (self.workspace.data_ptr(), self._ws_bytes(), self._mlp_ws.data_ptr(), self._mlp_ws.numel() * 4, C.byref(out),
-                self._mlp_dz.data_ptr(), self._mlp_gbi.data_ptr(), grads.data_ptr(), mlp_opt.ref(), _ptr(loss_out), self._stream(stream))
-        cap = None if loss_out is None else loss_out.numel()
-        keep = (out, m, hyper, mlp_opt, params, grads, idx_pool, y_pool, loss_out, self.workspace, self._mlp_ws, self._mlp_dz, self._mlp_gbi)
-        steps, advance = self._steps, self._advance
-
-        def run(n_steps):
-            if cap is not None and n_steps > cap:
-                raise ValueError(f"loss_out holds {cap} steps, {n_steps} asked for")
-            steps(hyper)
-            mlp_opt.c.step = mlp_opt.step     # (the bound structs are hyper's and mlp_opt's own: a second call continues both counts)
-            check(fn(*fixed, n_steps, *tail))
-            advance(n_steps)
-            mlp_opt.step += n_steps
-        run.keep = keep
-        return run
+        return self._bound_run(self.lib.fmx_deepfm_pair_stream, fixed, tail, hyper, loss_out, keep, mlp_opt)
 
     # ---- the small fused MLP (online steps of DeepFM / NFM / ONN); shapes beyond its limits raise FmxError(UNSUPPORTED) ----
     MLP_MAX_B, MLP_MAX_W, MLP_MAX_L = 16, 64, 8
@@ -397,15 +381,12 @@ class FMEngine:
         dz = torch.empty(B, dtype=torch.float32, device=self.device)
         gbi = torch.empty((B, self.table.kp), dtype=torch.float32, device=self.device)
         m = self._mlp_struct(params, k, hidden, n_layers)
-        if mlp_opt is not None:
-            _lib.check(self.lib.fmx_mlp_fit_opt(C.byref(m), hyper.ref(), _lib.LOSSES[loss], self.bi.data_ptr(), self.table.kp,
-                                                base.data_ptr(), y_d.data_ptr(), B, 1.0 / B if inv_b is None else inv_b,
-                                                dz.data_ptr(), gbi.data_ptr(), self.loss_out.data_ptr(), mlp_opt.ref(), self._stream()))
-            mlp_opt.step += 1
-            return dz, gbi
-        _lib.check(self.lib.fmx_mlp_fit(C.byref(m), hyper.ref(), _lib.RULES[rule], _lib.LOSSES[loss], self.bi.data_ptr(),
-                                        self.table.kp, base.data_ptr(), y_d.data_ptr(), B, 1.0 / B if inv_b is None else inv_b,
-                                        dz.data_ptr(), gbi.data_ptr(), self.loss_out.data_ptr(), self._stream()))
+        args = (_lib.LOSSES[loss], self.bi.data_ptr(), self.table.kp, base.data_ptr(), y_d.data_ptr(), B, 1.0 / B if inv_b is None else inv_b,
+                dz.data_ptr(), gbi.data_ptr(), self.loss_out.data_ptr())
+        if mlp_opt is None:
+            self._counted(self.lib.fmx_mlp_fit, (C.byref(m), hyper.ref(), _lib.RULES[rule], *args, self._stream()))
+        else:
+            self._counted(self.lib.fmx_mlp_fit_opt, (C.byref(m), hyper.ref(), *args, mlp_opt.ref(), self._stream()), mlp_opt=mlp_opt)
         return dz, gbi
 
     def mlp_pair_fit(self, params, k, hidden, n_layers, hyper, rule, base, B_pairs, margin=0.0, inv_b=None, mlp_opt=None,
@@ -419,12 +400,10 @@ class FMEngine:
         gbi = torch.empty((B2, self.table.kp), dtype=torch.float32, device=self.device)
         logit = torch.empty(B2, dtype=torch.float32, device=self.device) if want_logit else None
         m = self._mlp_struct(params, k, hidden, n_layers)
-        _lib.check(self.lib.fmx_mlp_pair_fit(C.byref(m), hyper.ref(), _lib.RULES[rule], self.bi.data_ptr(), self.table.kp,
-                                             base.data_ptr(), int(B_pairs), float(margin), 1.0 / B_pairs if inv_b is None else inv_b,
-                                             _ptr(logit), dz.data_ptr(), gbi.data_ptr(), self.loss_out.data_ptr(),
-                                             None if mlp_opt is None else mlp_opt.ref(), self._stream()))
-        if mlp_opt is not None:
-            mlp_opt.step += 1
+        self._counted(self.lib.fmx_mlp_pair_fit, (C.byref(m), hyper.ref(), _lib.RULES[rule], self.bi.data_ptr(), self.table.kp,
+                                                  base.data_ptr(), int(B_pairs), float(margin), 1.0 / B_pairs if inv_b is None else inv_b,
+                                                  _ptr(logit), dz.data_ptr(), gbi.data_ptr(), self.loss_out.data_ptr(),
+                                                  None if mlp_opt is None else mlp_opt.ref(), self._stream()), mlp_opt=mlp_opt)
         return dz, gbi, logit
 
     def mlp_hedge_fit(self, params, k, hidden, n_layers, lr, hedge_b, hedge_s, alpha, base, y_d, B):
@@ -438,19 +417,13 @@ class FMEngine:
         N = idx_d.shape[0]
         pred = torch.empty(N, dtype=torch.uint8, device=self.device)
         loss_b = torch.empty(N, dtype=torch.float32, device=self.device) if want_loss else None
-        self._steps(hyper)
-        _lib.check(self.lib.fmx_fm_online_run(self.table.c_struct(), hyper.ref(), _lib.RULES[rule], _lib.LOSSES[loss],
-                                              idx_d.data_ptr(), _ptr(xv_d), y_d.data_ptr(), N, pred.data_ptr(), _ptr(loss_b),
-                                              self.error.data_ptr(), self._stream()))
-        self._advance(N)
+        self._counted(self.lib.fmx_fm_online_run, (self.table.c_struct(), hyper.ref(), _lib.RULES[rule], _lib.LOSSES[loss], idx_d.data_ptr(),
+                                                   _ptr(xv_d), y_d.data_ptr(), N, pred.data_ptr(), _ptr(loss_b), self.error.data_ptr(),
+                                                   self._stream()), hyper, N)
         return pred, loss_b
 
     # ---- pairwise-ranking (BPR) training: idx_d [2B, F], row 2i the positive of pair i, row 2i + 1 the negative (fmx/pairwise.py) ----
-    @staticmethod
-    def _n_pairs(idx_d):
-        if idx_d.dim() != 2 or idx_d.shape[0] % 2 or idx_d.shape[0] < 2:
-            raise ValueError(f"pair rows must be [2B, F] with B >= 1, got {tuple(idx_d.shape)}")
-        return idx_d.shape[0] // 2
+    _n_pairs = staticmethod(n_pairs)
 
     def pair_forward(self, hyper, idx_d, xv_d=None, margin=0.0, inv_b=None, want_first=False, want_bi=False, stream=None):
         """fmx_fm_pair_forward on B pairs: S / sfirst / sbi / logit of the 2B rows, and the pair loss and its dlogit in
@@ -469,35 +442,28 @@ class FMEngine:
         cached = getattr(self, "_step_out", None)
         if cached is None or cached[0] != self.S.data_ptr():
             self._step_out = cached = (self.S.data_ptr(), self._fwd_out(want_first=False, want_bi=False))
-        self._steps(hyper)
-        _lib.check(self.lib.fmx_fm_pair_step(self.table.c_struct(), hyper.ref(), _lib.RULES[rule], idx_d.data_ptr(), _ptr(xv_d), B,
-                                             float(margin), 1.0 / B if inv_b is None else inv_b, self.workspace.data_ptr(),
-                                             self._ws_bytes(), C.byref(cached[1]), self.loss_out.data_ptr(), self._stream()))
-        self._advance(1)
+        self._counted(self.lib.fmx_fm_pair_step, (self.table.c_struct(), hyper.ref(), _lib.RULES[rule], idx_d.data_ptr(), _ptr(xv_d), B,
+                                                  float(margin), 1.0 / B if inv_b is None else inv_b, self.workspace.data_ptr(),
+                                                  self._ws_bytes(), C.byref(cached[1]), self.loss_out.data_ptr(), self._stream()), hyper)
 
     def pair_stream(self, hyper, rule, idx_pool, n_steps, margin=0.0, loss_out=None):
         """n_steps pair steps over a resident pool idx_pool [n_pool, 2B, F] (fmx_fm_pair_stream); loss_out [n_steps] or None."""
         n_pool, B2, F = idx_pool.shape
         assert F == self.table.n_fields and B2 % 2 == 0 and idx_pool.is_contiguous()
-        if loss_out is not None and (loss_out.numel() < n_steps or not loss_out.is_contiguous()):
-            raise ValueError(f"loss_out holds {loss_out.numel()} steps, {n_steps} asked for")
+        _loss_cap(loss_out, n_steps)
         B = B2 // 2
         self._ensure(B2)
         out = self._fwd_out(want_first=False, want_bi=False)
-        self._steps(hyper)
-        _lib.check(self.lib.fmx_fm_pair_stream(self.table.c_struct(), hyper.ref(), _lib.RULES[rule], idx_pool.data_ptr(), n_pool, B,
-                                               float(margin), 1.0 / B, int(n_steps), self.workspace.data_ptr(), self._ws_bytes(),
-                                               C.byref(out), _ptr(loss_out), self._stream()))
-        self._advance(n_steps)
+        self._counted(self.lib.fmx_fm_pair_stream, (self.table.c_struct(), hyper.ref(), _lib.RULES[rule], idx_pool.data_ptr(), n_pool, B,
+                                                    float(margin), 1.0 / B, int(n_steps), self.workspace.data_ptr(), self._ws_bytes(),
+                                                    C.byref(out), _ptr(loss_out), self._stream()), hyper, n_steps)
 
     # ---- listwise (sampled-softmax) training: idx_d [B G, F], row G i the positive of list i, then its G - 1 negatives ----
     def _n_lists(self, rows, G):
         """-> B for B G rows; grows the buffers, and keeps the list steps' own workspace, self._list_ws, sized through
         fmx_fm_list_workspace_bytes (the step workspace and the scratch behind it that the bias rule of a list step runs on).
         The other calls' workspace and the buffers' allocation are left as they are."""
-        G = int(G)
-        if not 2 <= G <= _lib.LIST_MAX_G:
-            raise ValueError(f"G = {G}: a list is one positive and 1 to {_lib.LIST_MAX_G - 1} negatives")
+        G = _list_G(G)
         if rows < G or rows % G:
             raise ValueError(f"list rows must be [B G, F] with B >= 1 and G = {G}, got {rows} rows")
         self._ensure(rows)
@@ -528,25 +494,20 @@ class FMEngine:
             raise ValueError(f"list rows must be [B G, F], got {tuple(idx_d.shape)}")
         B = self._n_lists(idx_d.shape[0], G)
         out = self._fwd_out(want_first=False, want_bi=False)
-        self._steps(hyper)
-        _lib.check(self.lib.fmx_fm_list_step(self.table.c_struct(), hyper.ref(), _lib.RULES[rule], idx_d.data_ptr(), _ptr(xv_d), B,
-                                             int(G), 1.0 / B if inv_b is None else inv_b, self._list_ws.data_ptr(),
-                                             self._list_ws.numel() * 4, C.byref(out), self.loss_out.data_ptr(), self._stream()))
-        self._advance(1)
+        self._counted(self.lib.fmx_fm_list_step, (self.table.c_struct(), hyper.ref(), _lib.RULES[rule], idx_d.data_ptr(), _ptr(xv_d), B,
+                                                  int(G), 1.0 / B if inv_b is None else inv_b, self._list_ws.data_ptr(),
+                                                  self._list_ws.numel() * 4, C.byref(out), self.loss_out.data_ptr(), self._stream()), hyper)
 
     def list_stream(self, hyper, rule, idx_pool, G, n_steps, loss_out=None):
         """n_steps list steps over a resident pool idx_pool [n_pool, B G, F] (fmx_fm_list_stream); loss_out [n_steps] or None."""
         n_pool, rows, F = idx_pool.shape
         assert F == self.table.n_fields and idx_pool.is_contiguous()
-        if loss_out is not None and (loss_out.numel() < n_steps or not loss_out.is_contiguous()):
-            raise ValueError(f"loss_out holds {loss_out.numel()} steps, {n_steps} asked for")
+        _loss_cap(loss_out, n_steps)
         B = self._n_lists(rows, G)
         out = self._fwd_out(want_first=False, want_bi=False)
-        self._steps(hyper)
-        _lib.check(self.lib.fmx_fm_list_stream(self.table.c_struct(), hyper.ref(), _lib.RULES[rule], idx_pool.data_ptr(), n_pool, B,
-                                               int(G), 1.0 / B, int(n_steps), self._list_ws.data_ptr(), self._list_ws.numel() * 4,
-                                               C.byref(out), _ptr(loss_out), self._stream()))
-        self._advance(n_steps)
+        self._counted(self.lib.fmx_fm_list_stream, (self.table.c_struct(), hyper.ref(), _lib.RULES[rule], idx_pool.data_ptr(), n_pool, B,
+                                                    int(G), 1.0 / B, int(n_steps), self._list_ws.data_ptr(), self._list_ws.numel() * 4,
+                                                    C.byref(out), _ptr(loss_out), self._stream()), hyper, n_steps)
 
     def pair_online_run(self, hyper, rule, idx_d, xv_d=None, margin=0.0, want_logit=False, want_loss=False):
         """The online protocol on N device-resident pairs (fmx_fm_pair_online_run): per pair predict (z_pos > z_neg), then one
@@ -555,31 +516,25 @@ class FMEngine:
         pred = torch.empty(N, dtype=torch.uint8, device=self.device)
         logit = torch.empty(2 * N, dtype=torch.float32, device=self.device) if want_logit else None
         loss_b = torch.empty(N, dtype=torch.float32, device=self.device) if want_loss else None
-        self._steps(hyper)
-        _lib.check(self.lib.fmx_fm_pair_online_run(self.table.c_struct(), hyper.ref(), _lib.RULES[rule], idx_d.data_ptr(), _ptr(xv_d),
-                                                   N, float(margin), pred.data_ptr(), _ptr(logit), _ptr(loss_b),
-                                                   self.error.data_ptr(), self._stream()))
-        self._advance(N)
+        self._counted(self.lib.fmx_fm_pair_online_run, (self.table.c_struct(), hyper.ref(), _lib.RULES[rule], idx_d.data_ptr(), _ptr(xv_d),
+                                                        N, float(margin), pred.data_ptr(), _ptr(logit), _ptr(loss_b),
+                                                        self.error.data_ptr(), self._stream()), hyper, N)
         return pred, logit, loss_b
 
     def list_online_run(self, hyper, rule, idx_d, G, xv_d=None, want_logit=False, want_loss=False):
         """The online protocol on N device-resident lists of G rows (fmx_fm_list_online_run): per list the positive's rank among
         its negatives (0: first), then one list step on that list.  -> (rank uint8 [N], logit [N G] or None, loss [N] or None);
         no sync.  The table's step count advances by N."""
-        G = int(G)
-        if not 2 <= G <= _lib.LIST_MAX_G:
-            raise ValueError(f"G = {G}: a list is one positive and 1 to {_lib.LIST_MAX_G - 1} negatives")
+        G = _list_G(G)
         if idx_d.dim() != 2 or idx_d.shape[0] % G:
             raise ValueError(f"list rows must be [N G, F] with G = {G}, got {tuple(idx_d.shape)}")
         N = idx_d.shape[0] // G
         rank = torch.empty(N, dtype=torch.uint8, device=self.device)
         logit = torch.empty(N * G, dtype=torch.float32, device=self.device) if want_logit else None
         loss_b = torch.empty(N, dtype=torch.float32, device=self.device) if want_loss else None
-        self._steps(hyper)
-        _lib.check(self.lib.fmx_fm_list_online_run(self.table.c_struct(), hyper.ref(), _lib.RULES[rule], idx_d.data_ptr(), _ptr(xv_d),
-                                                   N, G, rank.data_ptr(), _ptr(logit), _ptr(loss_b), self.error.data_ptr(),
-                                                   self._stream()))
-        self._advance(N)
+        self._counted(self.lib.fmx_fm_list_online_run, (self.table.c_struct(), hyper.ref(), _lib.RULES[rule], idx_d.data_ptr(), _ptr(xv_d),
+                                                        N, G, rank.data_ptr(), _ptr(logit), _ptr(loss_b), self.error.data_ptr(),
+                                                        self._stream()), hyper, N)
         return rank, logit, loss_b
 
     def list_online_run_fits(self, F, kp):
@@ -601,21 +556,16 @@ class FMEngine:
         pred = torch.empty(N, dtype=torch.float32, device=self.device)
         if getattr(self, "_online_scratch", None) is None:
             self._online_scratch = torch.zeros(self.table.kp + 8, dtype=torch.float32, device=self.device)
+        head = (self.table.c_struct(), hyper.ref(), _lib.RULES[rule], _lib.LOSSES[loss], C.byref(m))
+        tail = (idx_d.data_ptr(), _ptr(xv_d), y_d.data_ptr(), N, self.workspace.data_ptr(), self._ws_bytes(), C.byref(out),
+                self._online_scratch.data_ptr(), pred.data_ptr())
         if mlp_opt is not None:
             if hedge:
                 raise ValueError("online_run_mlp: mlp_opt is for the fit mode (Hedge has a rule of its own)")
-            self._steps(hyper)
-            _lib.check(self.lib.fmx_online_run_mlp_opt(self.table.c_struct(), hyper.ref(), _lib.RULES[rule], _lib.LOSSES[loss], C.byref(m),
-                                                       1 if fm_term else 0, idx_d.data_ptr(), _ptr(xv_d), y_d.data_ptr(), N,
-                                                       self.workspace.data_ptr(), self._ws_bytes(), C.byref(out),
-                                                       self._online_scratch.data_ptr(), pred.data_ptr(), mlp_opt.ref(), self._stream()))
-            self._advance(N)
-            mlp_opt.step += N
-            return pred
-        _lib.check(self.lib.fmx_online_run_mlp(self.table.c_struct(), hyper.ref(), _lib.RULES[rule], _lib.LOSSES[loss], C.byref(m),
-                                               1 if hedge else 0, 1 if fm_term else 0, hedge_b, hedge_s, _ptr(alpha),
-                                               idx_d.data_ptr(), _ptr(xv_d), y_d.data_ptr(), N, self.workspace.data_ptr(), self._ws_bytes(),
-                                               C.byref(out), self._online_scratch.data_ptr(), pred.data_ptr(), self._stream()))
+            self._counted(self.lib.fmx_online_run_mlp_opt, (*head, 1 if fm_term else 0, *tail, mlp_opt.ref(), self._stream()), hyper, N, mlp_opt)
+        else:       # (tables in the weights or the FTRL layout: no step count)
+            self._counted(self.lib.fmx_online_run_mlp, (*head, 1 if hedge else 0, 1 if fm_term else 0, hedge_b, hedge_s, _ptr(alpha), *tail,
+                                                        self._stream()))
         return pred
 
     def online_run_mlp_pair(self, hyper, rule, params, k, hidden, n_layers, fm_term, idx_d, xv_d=None, margin=0.0, mlp_opt=None,
@@ -634,15 +584,11 @@ class FMEngine:
         loss_b = torch.empty(N, dtype=torch.float32, device=self.device) if want_loss else None
         if getattr(self, "_pair_online_scratch", None) is None:
             self._pair_online_scratch = torch.zeros(2 * self.table.kp + 8, dtype=torch.float32, device=self.device)
-        self._steps(hyper)
-        _lib.check(self.lib.fmx_online_run_mlp_pair(self.table.c_struct(), hyper.ref(), _lib.RULES[rule], C.byref(m),
-                                                    1 if fm_term else 0, idx_d.data_ptr(), _ptr(xv_d), N, float(margin),
-                                                    self.workspace.data_ptr(), self._ws_bytes(), C.byref(out),
-                                                    self._pair_online_scratch.data_ptr(), pred.data_ptr(), _ptr(logit), _ptr(loss_b),
-                                                    None if mlp_opt is None else mlp_opt.ref(), self._stream()))
-        self._advance(N)
-        if mlp_opt is not None:
-            mlp_opt.step += N
+        self._counted(self.lib.fmx_online_run_mlp_pair, (self.table.c_struct(), hyper.ref(), _lib.RULES[rule], C.byref(m),
+                                                         1 if fm_term else 0, idx_d.data_ptr(), _ptr(xv_d), N, float(margin),
+                                                         self.workspace.data_ptr(), self._ws_bytes(), C.byref(out),
+                                                         self._pair_online_scratch.data_ptr(), pred.data_ptr(), _ptr(logit), _ptr(loss_b),
+                                                         None if mlp_opt is None else mlp_opt.ref(), self._stream()), hyper, N, mlp_opt)
         return pred, logit, loss_b
 
     @staticmethod
@@ -687,17 +633,13 @@ class FMEngine:
         the same pass; mlp_opt.step advances by one."""
         m = self._mlp_struct(params, k, hidden, n_layers)
         self._mlp_big_buffers(m, k, hidden, n_layers, B)
-        if mlp_opt is not None:
-            _lib.check(self.lib.fmx_mlp_section_opt(C.byref(m), _lib.LOSSES[loss], bi.data_ptr(), bi.stride(0), base.data_ptr(),
-                                                    y_d.data_ptr(), B, inv_b, self._mlp_ws.data_ptr(), self._mlp_ws.numel() * 4, None,
-                                                    self._mlp_dz.data_ptr(), self._mlp_gbi.data_ptr(), self.table.kp, grads.data_ptr(),
-                                                    mlp_opt.ref(), self._mlp_loss.data_ptr(), self._stream()))
-            mlp_opt.step += 1
-            return self._mlp_loss, self._mlp_dz, self._mlp_gbi
-        _lib.check(self.lib.fmx_mlp_section(C.byref(m), _lib.LOSSES[loss], bi.data_ptr(), bi.stride(0), base.data_ptr(),
-                                            y_d.data_ptr(), B, inv_b, self._mlp_ws.data_ptr(), None, self._mlp_dz.data_ptr(),
-                                            self._mlp_gbi.data_ptr(), self.table.kp, grads.data_ptr(), lr_apply,
-                                            self._mlp_loss.data_ptr(), self._stream()))
+        head = (C.byref(m), _lib.LOSSES[loss], bi.data_ptr(), bi.stride(0), base.data_ptr(), y_d.data_ptr(), B, inv_b, self._mlp_ws.data_ptr())
+        bufs = (None, self._mlp_dz.data_ptr(), self._mlp_gbi.data_ptr(), self.table.kp, grads.data_ptr())
+        if mlp_opt is None:
+            self._counted(self.lib.fmx_mlp_section, (*head, *bufs, lr_apply, self._mlp_loss.data_ptr(), self._stream()))
+        else:
+            self._counted(self.lib.fmx_mlp_section_opt, (*head, self._mlp_ws.numel() * 4, *bufs, mlp_opt.ref(), self._mlp_loss.data_ptr(),
+                                                         self._stream()), mlp_opt=mlp_opt)
         return self._mlp_loss, self._mlp_dz, self._mlp_gbi
 
     def mlp_pair_section(self, params, grads, k, hidden, n_layers, bi, base, B_pairs, inv_b=None, margin=0.0, lr_apply=0.0,
@@ -711,13 +653,12 @@ class FMEngine:
             raise ValueError(f"mlp_pair_section: bi {tuple(bi.shape)} / base {tuple(base.shape)} do not hold 2 x {B_pairs} rows")
         m = self._mlp_struct(params, k, hidden, n_layers)
         self._mlp_big_buffers(m, k, hidden, n_layers, 2 * B_pairs)
-        _lib.check(self.lib.fmx_mlp_pair_section(C.byref(m), bi.data_ptr(), bi.stride(0), base.data_ptr(), B_pairs, float(margin),
-                                                 1.0 / B_pairs if inv_b is None else inv_b, self._mlp_ws.data_ptr(),
-                                                 self._mlp_ws.numel() * 4, self._mlp_logit.data_ptr(), self._mlp_dz.data_ptr(),
-                                                 self._mlp_gbi.data_ptr(), self.table.kp, grads.data_ptr(), lr_apply,
-                                                 None if mlp_opt is None else mlp_opt.ref(), self._mlp_loss.data_ptr(), self._stream()))
-        if mlp_opt is not None:
-            mlp_opt.step += 1
+        self._counted(self.lib.fmx_mlp_pair_section, (C.byref(m), bi.data_ptr(), bi.stride(0), base.data_ptr(), B_pairs, float(margin),
+                                                      1.0 / B_pairs if inv_b is None else inv_b, self._mlp_ws.data_ptr(),
+                                                      self._mlp_ws.numel() * 4, self._mlp_logit.data_ptr(), self._mlp_dz.data_ptr(),
+                                                      self._mlp_gbi.data_ptr(), self.table.kp, grads.data_ptr(), lr_apply,
+                                                      None if mlp_opt is None else mlp_opt.ref(), self._mlp_loss.data_ptr(),
+                                                      self._stream()), mlp_opt=mlp_opt)
         return self._mlp_loss, self._mlp_dz, self._mlp_gbi, self._mlp_logit
 
     def check_error_flag(self):

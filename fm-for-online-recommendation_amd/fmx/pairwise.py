@@ -23,6 +23,13 @@ def _item_fields(item_fields):
     return fields
 
 
+def n_pairs(idx_d):
+    """-> B of the interleaved rows [2B, F] of B pairs (FMEngine's and AFMEngine's pair calls)"""
+    if idx_d.dim() != 2 or idx_d.shape[0] % 2 or idx_d.shape[0] < 2:
+        raise ValueError(f"pair rows must be [2B, F] with B >= 1, got {tuple(idx_d.shape)}")
+    return idx_d.shape[0] // 2
+
+
 def _negatives_3d(neg_items, B, m, what="neg_items"):
     """-> [B, n_neg, m]: accepts [B, n_neg, m], [B, m] (one negative per positive) and, with one item field, [B]."""
     t = torch.as_tensor(neg_items)

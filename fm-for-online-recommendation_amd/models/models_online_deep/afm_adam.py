@@ -31,10 +31,12 @@ import fmx
 from fmx.afm import AFMEngine, AfmOpt
 
 from ._base import OnlineFMBase, _FieldView
+from ._ranking import RankingTraining
 
 
-class AFMAdam(nn.Module):
+class AFMAdam(RankingTraining, nn.Module):
     _name = "AFMAdam"
+    _logit_family = "afm"       # RankingTraining refuses the pure FM's pair and list methods and its mining by name
 
     def __init__(self, feature_sizes, embedding_size=4, attention_size=4, n_epochs=64, batch_size=256, num_classes=1, b=0.99,
                  n=0.003, use_cuda=True, update_rule="adam", ftrl=None, adam=None, adagrad=None, fused_optimizer=False):
@@ -155,7 +157,7 @@ class AFMAdam(nn.Module):
 
     def _candidate_rows(self, item_fields, candidates):
         """OnlineFMBase._candidate_rows, after this class's check that the one item field of candidates=None is a field."""
-        fields = [int(f) for f in (item_fields if hasattr(item_fields, "__len__") else [item_fields])]
+        fields = self._item_fields(item_fields)
         if candidates is None and len(fields) == 1 and not 0 <= fields[0] < self.field_size:
             raise ValueError(f"item field {fields[0]}: not a field of 0..{self.field_size - 1}")
         return OnlineFMBase._candidate_rows(self, item_fields, candidates)
@@ -226,17 +228,11 @@ class AFMAdam(nn.Module):
         return out
 
     # ---- pairwise-ranking (BPR) training on the attentional logit (fmx_afm_pair_*; the pair objective of the other classes) ----
-    _pair_rows = OnlineFMBase._pair_rows
-    _negative_rows = OnlineFMBase._negative_rows
-    _pair_experiment_result = OnlineFMBase._pair_experiment_result
-    _refuse_hard_negatives = OnlineFMBase._refuse_hard_negatives
-
     def _pair_refusal(self, method, attention):
         """The default keeps the other classes' reading of these two methods -- the pair loss of the pure FM logit, which this
         model does not have; attention=True trains on the logit forward() gives."""
         if not attention:
-            raise NotImplementedError(f"{self._name}.{method}: the pair loss is built for the pure FM logit (FMAdam); "
-                                      f"{method}(..., attention=True) trains on the pair loss of the attentional FM's logit")
+            self._pure_fm_only(method, own=("attention", "the attentional FM's"))
 
     def fit_pairs(self, Xi, Xv, item_fields, negatives=None, n_neg=1, margin=0.0, candidates=None, generator=None, attention=False):
         """OnlineFMBase.fit_pairs's arguments; attention=True: one mini-batch pair step of the whole model (tables and attention)
@@ -255,15 +251,7 @@ class AFMAdam(nn.Module):
         self._after_step()
         return out
 
-    def fit_lists(self, Xi, Xv, item_fields, negatives=None, n_neg=4, candidates=None, generator=None):
-        """The listwise (sampled-softmax) step of FMAdam.fit_lists: not built for this model."""
-        raise NotImplementedError(f"{self._name}.fit_lists: the list loss is built for the pure FM logit (FMAdam); the attentional "
-                                  "FM would need the softmax epilogue behind its own forward")
-
-    def run_list_experiment(self, Xi, Xv, item_fields, negatives=None, n_neg=4, candidates=None, generator=None):
-        """The online list protocol of FMAdam.run_list_experiment: not built for this model."""
-        raise NotImplementedError(f"{self._name}.run_list_experiment: the list loss is built for the pure FM logit (FMAdam); the "
-                                  "attentional FM would need the softmax epilogue behind its own forward")
+    # (fit_lists / run_list_experiment / mine_negatives: RankingTraining's, which refuse them for this model by name)
 
     def run_pair_experiment(self, Xi, Xv, item_fields, negatives=None, n_neg=1, margin=0.0, candidates=None, generator=None,
                             attention=False):
@@ -277,24 +265,17 @@ class AFMAdam(nn.Module):
         rows, xv = self._pair_rows(Xi, Xv, item_fields, negatives, n_neg, candidates, generator)
         n, e = rows.shape[0] // 2, self._engine
         if n == 0:
-            return time() - start, 0.0, [], {"correct": 0, "wrong": 0}
+            return self._experiment_result(start, None)
         if self._attn_fused is not None:
             logits = torch.empty(2 * n, dtype=torch.float32, device=self.device)
             e.pair_online_run(self._hyper, self.update_rule, rows, xv, self._attn_fused, margin=margin, logits=logits)
-            pred = (logits[0::2] > logits[1::2]).to(torch.uint8)
-        else:
-            fields = [int(f) for f in (item_fields if hasattr(item_fields, "__len__") else [item_fields])]
-            pred = torch.empty(n, dtype=torch.uint8, device=self.device)
-            strict, self.strict_index_check = self.strict_index_check, False      # one check after the loop, no sync inside it
-            try:
-                for i in range(n):
-                    pos, neg = rows[2 * i:2 * i + 1], rows[2 * i + 1:2 * i + 2, fields]
-                    self.fit_pairs(pos, None if xv is None else xv[2 * i:2 * i + 1], fields, negatives=neg, margin=margin,
-                                   attention=True)
-                    pred[i] = e.logit[0] > e.logit[1]            # the step's own forward: the logits before its update
-            finally:
-                self.strict_index_check = strict
-        return self._pair_experiment_result(start, pred)
+            return self._experiment_result(start, (logits[0::2] > logits[1::2]).to(torch.uint8))
+        fields = self._item_fields(item_fields)
+
+        def fit_one(i):
+            pos, pos_xv, neg = self._pair_at(rows, xv, fields, i)
+            self.fit_pairs(pos, pos_xv, fields, negatives=neg, margin=margin, attention=True)
+        return self._experiment_result(start, self._host_stream_loop(n, fit_one, lambda: e.logit[0] > e.logit[1]))
 
     def _mean_logloss(self, Xi, Xv, y, chunk=16384):
         """The mean BCE-with-logits over a data set, evaluated by batches (reference eval_by_batch, :143-165)."""

@@ -4,7 +4,8 @@
 forward = forward_fm + sum relu-MLP(bi) (deepfm_adam.py:79-89; second_order is evaluated twice there, so the table
 gradient is the FM-term gradient plus the MLP-input gradient); update_embedding: BCEwl(forward_fm) (:99-101);
 fit: BCEwl(sigmoid(forward)) (:115)."""
-from ._base import NetworkPairTraining, OnlineFMBase
+from ._base import OnlineFMBase
+from ._ranking import NetworkPairTraining
 
 
 class DeepFMAdam(NetworkPairTraining, OnlineFMBase):

@@ -3,7 +3,8 @@
 
 forward = sum_f first + bias + sum relu-MLP(bi), WITHOUT the sum_d bi_d term (nfm_adam.py:78-88);
 update_embedding: BCEwl(sigmoid(forward_fm)) (:100); fit: BCEwl(forward) (:114)."""
-from ._base import NetworkPairTraining, OnlineFMBase
+from ._base import OnlineFMBase
+from ._ranking import NetworkPairTraining
 
 
 class NFMAdam(NetworkPairTraining, OnlineFMBase):

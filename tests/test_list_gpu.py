@@ -186,18 +186,37 @@ def test_bias_is_bit_unchanged(fmx, rule):
 @pytest.mark.parametrize("rule", ["signadam", "adam"])
 @pytest.mark.parametrize("B", [7, 171])                         # 171 lists of 3: 513 rows, the sorts run ahead on the side stream
 def test_stream_is_its_steps(fmx, rule, B):
-    G, n_pool, n_steps, k = 3, 3, 5, 10
+    stream_is_its_steps(fmx, rule, B, n_pool=3, n_steps=5)
+
+
+@pytest.mark.parametrize("own_stream", [False, True])
+@pytest.mark.parametrize("rule", ["signadam", "adam"])
+@pytest.mark.parametrize("B", [7, 171])
+def test_stream_is_its_steps_through_the_whole_loop(fmx, rule, B, own_stream):
+    """37 steps over a pool of 5: sort groups of 4 + 16 + 16 + 1, so both halves of the sorted ring are used again and the pool
+    wraps.  171 lists of 3 are 513 rows, over OVERLAP_MIN_BATCH (the sorts run ahead on the side stream); 7 lists are under it
+    (every group is sorted in front of its steps).  From torch's default stream (handle 0: the loop detours off it) and from a
+    stream of its own."""
+    stream_is_its_steps(fmx, rule, B, n_pool=5, n_steps=37, own_stream=own_stream)
+
+
+def stream_is_its_steps(fmx, rule, B, n_pool, n_steps, own_stream=False):
+    G, k = 3, 10
     t1, _ = build_table(fmx, SIZES, k, RULES[rule])
     t2 = clone_table(fmx, t1)
     e1, e2 = fmx.FMEngine(t1, max_batch=B * G), fmx.FMEngine(t2, max_batch=B * G)
     pool = np.stack([make_lists(B, G, seed=100 + j)[0] for j in range(n_pool)])
     pool_d = torch.from_numpy(pool).cuda().contiguous()
     losses1 = torch.full((n_steps,), float("nan"), device="cuda")
-    e1.list_stream(fmx.Hyper(**HYP), rule, pool_d, G, n_steps, loss_out=losses1)
-    h2, losses2 = fmx.Hyper(**HYP), []
-    for s in range(n_steps):
-        e2.list_step(h2, rule, pool_d[s % n_pool], G)
-        losses2.append(e2.loss_out.clone())
+    side = torch.cuda.Stream() if own_stream else torch.cuda.default_stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        assert (torch.cuda.current_stream().cuda_stream == 0) != own_stream
+        e1.list_stream(fmx.Hyper(**HYP), rule, pool_d, G, n_steps, loss_out=losses1)
+        h2, losses2 = fmx.Hyper(**HYP), []
+        for s in range(n_steps):
+            e2.list_step(h2, rule, pool_d[s % n_pool], G)
+            losses2.append(e2.loss_out.clone())
     torch.cuda.synchronize()
     e1.check_error_flag()
     e2.check_error_flag()

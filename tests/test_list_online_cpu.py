@@ -139,9 +139,9 @@ def test_run_list_experiment_signature_and_the_limit_of_negatives():
 
 
 def test_the_block_loop_is_shared_with_the_pair_form():
-    from models.models_online_deep._base import OnlineFMBase
-    pair = inspect.getsource(OnlineFMBase._run_pair_experiment_hard)
-    lists = inspect.getsource(OnlineFMBase.run_list_experiment)
+    from models.models_online_deep._ranking import RankingTraining
+    pair = inspect.getsource(RankingTraining.run_pair_experiment)
+    lists = inspect.getsource(RankingTraining.run_list_experiment)
     assert "_walk_mined_blocks" in pair and "_walk_mined_blocks" in lists
-    assert "remine_every" in inspect.getsource(OnlineFMBase._walk_mined_blocks)
+    assert "remine_every" in inspect.getsource(RankingTraining._walk_mined_blocks)
     assert "for b0 in range" not in pair and "for b0 in range" not in lists

@@ -244,19 +244,37 @@ def test_step_within_float64(fmx, rule, shape, B):
 @pytest.mark.parametrize("rule", ["signadam", "ftrl", "adam"])
 @pytest.mark.parametrize("shape,B", [("b", 33), ("c", 130), ("b", 256)])          # 2B = 512: the sorts run ahead on the side stream
 def test_stream_is_its_steps(fmx, rule, shape, B):
+    stream_is_its_steps(fmx, rule, shape, B, n_pool=3, n_steps=7)
+
+
+@pytest.mark.parametrize("own_stream", [False, True])
+@pytest.mark.parametrize("rule", ["signadam", "adam"])
+@pytest.mark.parametrize("B", [130, 256])
+def test_stream_is_its_steps_through_the_whole_loop(fmx, rule, B, own_stream):
+    """37 steps over a pool of 5: sort groups of 4 + 16 + 16 + 1, so both halves of the sorted ring are used again and the pool
+    wraps.  2B = 512 rows is OVERLAP_MIN_BATCH (the sorts run ahead on the side stream), 2B = 260 is under it (every group is
+    sorted in front of its steps).  From torch's default stream (handle 0: the loop detours off it) and from a stream of its own."""
+    stream_is_its_steps(fmx, rule, "b", B, n_pool=5, n_steps=37, own_stream=own_stream)
+
+
+def stream_is_its_steps(fmx, rule, shape, B, n_pool, n_steps, own_stream=False):
     sizes, k = SHAPES[shape]
-    n_pool, n_steps, margin = 3, 7, 0.1 if B == 33 else 0.0
+    margin = 0.1 if B == 33 else 0.0
     t1, _ = build_table(fmx, sizes, k, RULES[rule])
     t2 = clone_table(fmx, t1)
     e1, e2 = fmx.FMEngine(t1, max_batch=2 * B), fmx.FMEngine(t2, max_batch=2 * B)
     pool = np.stack([make_pairs(sizes, B, seed=100 + j, n_item=1 + j % 2)[0] for j in range(n_pool)])
     pool_d = torch.from_numpy(pool).cuda().contiguous()
     losses1 = torch.full((n_steps,), float("nan"), device="cuda")
-    e1.pair_stream(fmx.Hyper(**HYP), rule, pool_d, n_steps, margin=margin, loss_out=losses1)
-    h2, losses2 = fmx.Hyper(**HYP), []
-    for s in range(n_steps):
-        e2.pair_step(h2, rule, pool_d[s % n_pool], None, margin=margin)
-        losses2.append(e2.loss_out.clone())
+    side = torch.cuda.Stream() if own_stream else torch.cuda.default_stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        assert (torch.cuda.current_stream().cuda_stream == 0) != own_stream
+        e1.pair_stream(fmx.Hyper(**HYP), rule, pool_d, n_steps, margin=margin, loss_out=losses1)
+        h2, losses2 = fmx.Hyper(**HYP), []
+        for s in range(n_steps):
+            e2.pair_step(h2, rule, pool_d[s % n_pool], None, margin=margin)
+            losses2.append(e2.loss_out.clone())
     torch.cuda.synchronize()
     e1.check_error_flag()
     e2.check_error_flag()
