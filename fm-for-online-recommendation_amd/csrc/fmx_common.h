@@ -35,6 +35,9 @@ struct Tune {
   int sort_e = 0;     // FMX_SORT_E: elements per thread of the bitonic sort (0 = default)
   int inline_fixup = 1;  // FMX_INLINE_FIXUP=0 / fmx_set_option("inline_fixup", 0): partial records are combined by a second
                          // launch (k_fm_fixup) instead of the in-launch hand-off; both give identical bits
+  int upd_order = 1;  // FMX_UPD_ORDER / fmx_set_option("upd_order", v): the order in which k_fm_update's grid takes the sort fields.
+                      // 0: index order; 1: ascending row count (the small fields' hand-off chains ahead of the large fields' row
+                      // burst); 2: descending (the adversarial order, for tests).  Identical bits (fmx_host.h, upd_order_of)
   int online_persistent = 1;  // FMX_ONLINE_PERSISTENT=0 / fmx_set_option("online_persistent", 0): fmx_online_run_mlp as per-sample launches
   int afm_online_persistent = 1;  // fmx_set_option("afm_online_persistent", 0): fmx_afm_online_run as per-sample launches (same bits)
   int afm_pair_online_persistent = 1;  // fmx_set_option("afm_pair_online_persistent", 0): fmx_afm_pair_online_run as queued pair steps (same bits)
@@ -46,6 +49,10 @@ struct Tune {
                          // Identical lists either way
 };
 Tune &tune();
+
+// Sort fields whose dispatch order k_fm_update carries BY VALUE in its kernel arguments, one byte each (UpdArgs::order).  A table
+// with more sort fields is updated in index order.
+constexpr int UPD_ORDER_MAX = 128;
 
 // ---- the library's RCCL communicator for the field-owner step (fmx_comm.hip) ----
 constexpr int FMX_COMM_SLOTS = 4;  // batches whose indices may be gathered + sorted ahead of their step

@@ -48,6 +48,13 @@ int forward_impl(const fmx_table_t *table, const fmx_hyper_t *hyper, const int32
                  int32_t B, int32_t loss_kind, float inv_b, const fmx_fwd_out_t *out, hipStream_t st);
 int sort_impl(const fmx_table_t *table, const int32_t *idx, int32_t B, uint32_t *sorted, uint32_t *runs, int32_t *error,
               hipStream_t st, const SortBatch *mb = nullptr);
+// fmx_kernels.hip: the dispatch order of k_fm_update's tiles for this table under tune().upd_order, packed four sort fields to a
+// word (UpdArgs::order); false: index order (upd_order = 0, more than UPD_ORDER_MAX sort fields, or the table's row counts are
+// not known).  The row counts come from a per-device cache keyed by (offsets pointer, sort fields, n_rows, largest sort field);
+// a table seen for the first time is entered with ONE blocking copy of its offsets, and only when `may_fill` (the caller's
+// stream is not capturing).  A stale entry -- another table at the same address with the same key -- or a missing one gives
+// another order of the same tiles: it can cost time, never correctness.
+bool update_order(const fmx_table_t *table, bool may_fill, uint32_t *order_words);
 // fmx_update.hip
 int update_impl(const fmx_table_t *table, const fmx_hyper_t *hyper, int32_t rule, const Workspace &w,
                 const uint32_t *sorted, const float *xv, const float *S, const float *dz_first, const float *dz_bi, const float *gbi,
@@ -149,6 +156,22 @@ inline int n_sort_fields(const fmx_table_t *t) { return t->n_sort_fields > 0 ? t
 inline const int64_t *sort_offsets(const fmx_table_t *t) { return t->n_sort_fields > 0 ? t->sort_offsets : t->field_offsets; }
 inline const int32_t *sort_cols(const fmx_table_t *t) { return t->n_sort_fields > 0 ? t->sort_cols : nullptr; }
 inline int64_t max_sort_rows(const fmx_table_t *t) { return t->n_sort_fields > 0 ? t->max_sort_field_rows : t->max_field_rows; }
+
+// The order in which k_fm_update's grid takes n sort fields of rows[i] rows each (fmx_update_order states the contract): a
+// permutation in ascending (mode 1) or descending (mode 2) row count, ties in index order; mode 0: the identity.  Returns n, or
+// 0 with nothing written when the launch carries no order for so many fields (n > UPD_ORDER_MAX) or the mode is unknown.
+inline int upd_order_of(const int64_t *rows, int n, int mode, uint8_t *order) {
+  if (n < 1 || n > UPD_ORDER_MAX || mode < 0 || mode > 2) return 0;
+  for (int i = 0; i < n; ++i) order[i] = (uint8_t)i;
+  if (mode == 0) return n;
+  for (int i = 1; i < n; ++i) {  // insertion sort: stable, and n is small
+    const uint8_t f = order[i];
+    int j = i;
+    for (; j > 0 && (mode == 1 ? rows[order[j - 1]] > rows[f] : rows[order[j - 1]] < rows[f]); --j) order[j] = order[j - 1];
+    order[j] = f;
+  }
+  return n;
+}
 
 // The caller's hyper-parameters as the launches take them: the six floats every rule reads, and the fields appended after
 // them (beta1, beta2, step) for FMX_RULE_ADAM only -- a caller built against the six-float struct passes a shorter struct and

@@ -624,6 +624,7 @@ Tune &tune() {
     if (const char *e = getenv("FMX_ONLINE_PERSISTENT")) x.online_persistent = atoi(e);
     if (const char *e = getenv("FMX_INLINE_FIXUP")) x.inline_fixup = atoi(e);
     if (const char *e = getenv("FMX_SORT_CHUNKED")) x.sort_chunked = atoi(e);
+    if (const char *e = getenv("FMX_UPD_ORDER")) x.upd_order = atoi(e);
     if (const char *e = getenv("FMX_MLP_CHAIN")) x.mlp_chain = atoi(e);
     auto ok = [](int v) { return v == 1 || v == 2 || v == 4; };
     if (!ok(x.wpb_fwd)) x.wpb_fwd = 4;
@@ -669,6 +670,64 @@ Side *side_for_current_device() {
   }
   return &sd;
 }
+
+// ---- per device, beside Side: the sort fields' row counts of the tables k_fm_update has seen, as its dispatch orders.  The
+//      offsets are device memory, so a table's first update pays one blocking copy of them (update_order, fmx_host.h) ----
+struct UpdOrders {
+  struct Entry {
+    const int64_t *offs = nullptr;  // the key: the offsets pointer the update uses, the sort fields, n_rows, the largest sort field
+    int F = 0;
+    int64_t n_rows = 0, max_rows = 0;
+    bool known = false;                   // false: the copy failed -- index order, and no second attempt
+    uint8_t order[2][UPD_ORDER_MAX];      // ascending, descending
+  };
+  static constexpr int N = 8;  // tables per device; the oldest entry is replaced
+  Entry e[N];
+  int next = 0;
+};
+
+}  // namespace
+namespace fmxd {
+
+bool update_order(const fmx_table_t *table, bool may_fill, uint32_t *order_words) {
+  memset(order_words, 0, UPD_ORDER_MAX);
+  const int mode = tune().upd_order, F = n_sort_fields(table);
+  if ((mode != 1 && mode != 2) || F < 1 || F > UPD_ORDER_MAX) return false;
+  static std::mutex mu;
+  static UpdOrders per_device[64];
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return false;
+  const int64_t *offs = sort_offsets(table);
+  std::lock_guard<std::mutex> lock(mu);
+  UpdOrders &c = per_device[dev];
+  UpdOrders::Entry *hit = nullptr;
+  for (UpdOrders::Entry &x : c.e)
+    if (x.offs == offs && x.F == F && x.n_rows == table->n_rows && x.max_rows == max_sort_rows(table)) hit = &x;
+  if (!hit) {
+    if (!may_fill) return false;
+    hit = &c.e[c.next];
+    c.next = (c.next + 1) % UpdOrders::N;
+    hit->offs = offs;
+    hit->F = F;
+    hit->n_rows = table->n_rows;
+    hit->max_rows = max_sort_rows(table);
+    int64_t off[UPD_ORDER_MAX + 1], rows[UPD_ORDER_MAX];
+    // (another thread may be capturing a stream of its own: the copy is no part of that capture, and must not end it)
+    hipStreamCaptureMode cm = hipStreamCaptureModeRelaxed;
+    const bool swapped = hipThreadExchangeStreamCaptureMode(&cm) == hipSuccess;
+    hit->known = hipMemcpy(off, offs, sizeof(int64_t) * (size_t)(F + 1), hipMemcpyDeviceToHost) == hipSuccess;
+    if (swapped) (void)hipThreadExchangeStreamCaptureMode(&cm);
+    if (!hit->known) (void)hipGetLastError();  // not this launch's error: index order for this table
+    for (int f = 0; f < F && hit->known; ++f) rows[f] = off[f + 1] - off[f];
+    if (hit->known) hit->known = upd_order_of(rows, F, 1, hit->order[0]) == F && upd_order_of(rows, F, 2, hit->order[1]) == F;
+  }
+  if (!hit->known) return false;
+  memcpy(order_words, hit->order[mode - 1], (size_t)F);  // byte i of the words: slot i's field (little-endian, as the kernel reads it)
+  return true;
+}
+
+}  // namespace fmxd
+namespace {
 
 constexpr int OVERLAP_MIN_BATCH = 512;  // below this the extra event traffic costs more than the sort
 
@@ -1095,6 +1154,7 @@ int fmx_set_option(const char *name, int value) {
   else if (!strcmp(name, "afm_online_persistent")) slot = &t.afm_online_persistent;
   else if (!strcmp(name, "afm_pair_online_persistent")) slot = &t.afm_pair_online_persistent;
   else if (!strcmp(name, "sort_chunked")) slot = &t.sort_chunked;
+  else if (!strcmp(name, "upd_order")) slot = &t.upd_order;
   else if (!strcmp(name, "mlp_chain")) slot = &t.mlp_chain;
   else return fail(FMX_ERR_ARG, "fmx_set_option: unknown option '%s'", name);
   const int old = *slot;
@@ -1103,6 +1163,13 @@ int fmx_set_option(const char *name, int value) {
 }
 
 const char *fmx_last_error_string(void) { return g_err; }
+
+int fmx_update_order(const int64_t *rows, int32_t n, int32_t mode, uint8_t *order) {
+  if (!rows || !order) return fail(FMX_ERR_ARG, "fmx_update_order: null argument");
+  if (n < 1) return fail(FMX_ERR_ARG, "fmx_update_order: n = %d must be >= 1", (int)n);
+  if (mode < 0 || mode > 2) return fail(FMX_ERR_ARG, "fmx_update_order: mode = %d is none of 0, 1, 2", (int)mode);
+  return upd_order_of(rows, n, mode, order);
+}
 
 int fmx_sorted_width(int B) {
   int w = 64;

@@ -52,6 +52,11 @@ struct UpdArgs {
   uint32_t seq;      // launch sequence number tagging the tile meta words (INL) and the slice partials of this launch
   int32_t *error;    // INL: set to 2 if a hand-off wait ran into its bound
   float inv_b;
+  // the dispatch order of the tiles (update_body): slot i of the grid's tile waves works on sort field order[i], one byte each,
+  // by value -- a wave reads its byte with one scalar load of its own kernel arguments, not from memory behind a pointer.
+  // ordered == 0: index order (slot i = field i)
+  int32_t ordered;
+  uint32_t order[UPD_ORDER_MAX / 4];
 };
 
 // tile meta states
@@ -198,10 +203,29 @@ __device__ __forceinline__ void update_body(const UpdArgs &a, const int blk) {
   const int slot = lane / LPR, q = lane % LPR;
   const int kp = LPR * 4;
   const int tiles_per_field = a.Bp >> 6;
-  const int gt = (blk - n_red) * (blockDim.x >> 6) + (threadIdx.x >> 6);
-  if (gt >= a.F * tiles_per_field) return;
-  const int f = gt / tiles_per_field;
-  const int base = (gt - f * tiles_per_field) << 6;
+  // The wave's DISPATCH SLOT d chooses its work; the STORAGE index gt = f * tiles_per_field + t (parts, meta, flag words:
+  // k_fm_fixup's and the records' addressing) follows from the work.  Slot i of the fields belongs to sort field order[i] (the
+  // host's permutation: fields in ascending row count by default, update_order), tile t of a field stays tile t.  The small
+  // fields' tiles -- chains of dependent round trips with almost no bytes -- then have their requests in ahead of the large
+  // fields' burst of row lines, and the burst's own tail is shorter for it ("r6": the launch's last
+  // large-field combiner 8.5 - 9.1 -> 8.1 - 8.4 us; descending order: +0.7 us per step).  Nothing else depends on the slot:
+  // the order is invisible in every result, and a stale or missing one costs time only.
+  const int d = (blk - n_red) * (blockDim.x >> 6) + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);  // wave-uniform: scalar
+  if (d >= a.F * tiles_per_field) return;
+  const int tshift = a.bbits - 6;  // tiles_per_field = Bp / 64 = 1 << tshift
+  int f = d >> tshift;
+  const int t = d & (tiles_per_field - 1);
+  if (a.ordered) {
+    // The byte comes through the kernel-argument segment pointer (UpdArgs is the first argument of every kernel of this body),
+    // NOT as a.order[...]: one variable index into `a` and the compiler gives up loading the arguments in one burst at the top
+    // of the kernel -- it then fetches each one where it is used, 64 scalar loads with a wait each on the wave's critical path
+    // (measured: +0.45 us per launch under every order).
+    typedef const __attribute__((address_space(4))) uint32_t karg_u32;  // the constant address space: a scalar load
+    karg_u32 *ka = (karg_u32 *)__builtin_amdgcn_kernarg_segment_ptr();
+    f = (int)((ka[offsetof(UpdArgs, order) / 4 + (f >> 2)] >> ((f & 3) * 8)) & 0xFFu);
+  }
+  const int gt = f * tiles_per_field + t;
+  const int base = t << 6;
   const uint32_t *sf = a.sorted + (size_t)f * a.Bp;
   const int bbits = a.bbits;
   const uint32_t bmask = (1u << bbits) - 1u;
@@ -463,9 +487,13 @@ __device__ __forceinline__ void update_body(const UpdArgs &a, const int blk) {
   FMX_STAMP(3, lane);  // pass 2 done: the row updates of the runs inside the tile are issued
   if (!INL) return;
   // ---- in-launch hand-off (INL): the CLOSING tile of a run sums the records of the tiles before it (they were
-  //      dispatched earlier and wait on nothing) and applies the row update -- no second launch ----
+  //      dispatched earlier and wait on nothing) and applies the row update -- no second launch.
+  //      No deadlock, whatever the dispatch order of the FIELDS: the tiles this wave waits for are tiles tj < t of ITS OWN
+  //      field, and a field's tiles keep their relative order in the grid -- slot(f, tj) = position(f) * tiles_per_field + tj
+  //      < slot(f, t).  Workgroups start in block-index order, so those waves are resident (or done) when this one runs, and
+  //      they publish before they wait for anything: a tile publishes ahead of its own combine, and a combine never waits
+  //      for a combine.  The bias / loss blocks poll only blocks behind them that wait on nothing. ----
   if (lead_state != LEAD_CLOSES) return;  // wave-uniform
-  const int t = gt - f * tiles_per_field;
   float *rp = a.rows + (row0 + tile_prevkey) * (size_t)a.stride;
   const RowRegs r = row_in;  // lanes < LPR: requested at the top (the row is final until this wave writes it)
   // this tile's own part of the run: from the registers of the lane group that closed it to every lane group's lane q
@@ -685,8 +713,10 @@ void launch_update_occ_pair(const UpdArgs &a, int rule, hipStream_t st) {
 UpdArgs fill_upd(const fmx_table_t *table, const fmx_hyper_t *hyper, const Workspace &w, const uint32_t *sorted,
                  const float *xv, const float *S, const float *dz_first, const float *dz_bi, const float *gbi, int32_t B,
                  const float *loss_b, float inv_b, float *loss_out, int32_t *step_counter, int32_t sample_ld,
-                 int32_t *err_flag) {
+                 int32_t *err_flag, hipStream_t st) {
   UpdArgs a;
+  // (a capturing stream: the order is used when the table is known already, never looked up -- the look-up is a blocking copy)
+  a.ordered = update_order(table, !is_capturing(st), a.order) ? 1 : 0;
   a.ldS = sample_ld > 0 ? sample_ld : table->kp;
   a.ld1 = sample_ld > 0 ? sample_ld : 1;
   a.ldG = sample_ld > 0 ? sample_ld : table->kp;
@@ -734,7 +764,7 @@ int update_impl(const fmx_table_t *table, const fmx_hyper_t *hyper, int32_t rule
                 const float *loss_b, float inv_b, float *loss_out, hipStream_t st,
                 int32_t *step_counter, int32_t sample_ld, int32_t *err_flag, const MlpReduceArgs *rider) {
   UpdArgs a = fill_upd(table, hyper, w, sorted, xv, S, dz_first, dz_bi, gbi, B, loss_b, inv_b, loss_out, step_counter,
-                       sample_ld, err_flag);
+                       sample_ld, err_flag, st);
   if (rule == FMX_RULE_ADAM)  // this launch is step t = hyper->step + 1: its constants in double, once (adam_consts)
     adam_consts(hyper->lr, hyper->beta1, hyper->beta2, hyper->step + 1, a.h.lr, a.h.beta1, a.h.beta2);
   if (rider) {
@@ -753,7 +783,7 @@ int update_occ_impl(const fmx_table_t *table, const fmx_hyper_t *hyper, int32_t 
                     const float *dz_first, const float *occ, int32_t ld_occ, int32_t B, const float *loss_b, float inv_b,
                     float *loss_out, hipStream_t st) {
   UpdArgs a = fill_upd(table, hyper, w, w.sorted, xv, nullptr, dz_first, nullptr, occ, B, loss_b, inv_b, loss_out, nullptr, 0,
-                       nullptr);
+                       nullptr, st);
   a.ldG = ld_occ;
   if (rule == FMX_RULE_ADAM) adam_consts(hyper->lr, hyper->beta1, hyper->beta2, hyper->step + 1, a.h.lr, a.h.beta1, a.h.beta2);
   with_lpr(table->kp, [&](auto LPR) { launch_update_occ_pair<LPR>(a, rule, st); });

@@ -35,7 +35,7 @@ EXPORTS = ["fmx_version", "fmx_last_error_string", "fmx_set_option", "fmx_sorted
            "fmx_afm_pair_forward", "fmx_afm_pair_step", "fmx_afm_pair_step_opt", "fmx_afm_pair_stream", "fmx_afm_pair_online_run",
            "fmx_afm_pair_online_form", "fmx_fm_mine_negatives",
            "fmx_fm_list_workspace_bytes", "fmx_fm_list_forward", "fmx_fm_list_step", "fmx_fm_list_stream",
-           "fmx_fm_list_online_run"]
+           "fmx_fm_list_online_run", "fmx_update_order"]
 
 
 I64_RETURNS = ("fmx_workspace_bytes", "fmx_mlp_section_workspace_bytes", "fmx_fm_topk_workspace_bytes",
@@ -109,6 +109,7 @@ def load():
     lib.fmx_set_option.argtypes = [C.c_char_p, C.c_int]
     lib.fmx_sorted_width.argtypes = [C.c_int]
     lib.fmx_sorted_bbits.argtypes = [C.c_int]
+    lib.fmx_update_order.argtypes = [p, i32, i32, p]
     lib.fmx_workspace_bytes.argtypes = [TP, i32]
     lib.fmx_fm_forward.argtypes = [TP, HP, p, p, p, i32, i32, f32, FP, p]
     lib.fmx_sort_occurrences.argtypes = [TP, p, i32, p, i64, p, p]

@@ -183,6 +183,16 @@ const char *fmx_last_error_string(void);
  * status for an unknown name.  Every switch changes HOW the same result is computed; results are identical bits.
  *   "inline_fixup" (default 1)  1: runs that cross 64-occurrence tiles are finished inside k_fm_update by an in-launch
  *                                hand-off; 0: by a second launch (k_fm_fixup).
+ *   "upd_order"    (default 1)  the order in which k_fm_update's grid takes the table's sort fields (fmx_update_order below).
+ *                                0: index order; 1: ascending row count, so that the small fields' tiles -- chains of dependent
+ *                                round trips: list, sums, hand-off flags, records, one row -- enter the memory system ahead of
+ *                                the large fields' burst of row lines; 2: descending, the adversarial order (large fields first,
+ *                                every closing tile as late as possible), for tests.  The order of dispatch is not visible in any
+ *                                result.  The library learns a table's row counts with one blocking copy of its offsets at the
+ *                                table's first update (never while the stream is capturing) and keeps them per device, keyed by
+ *                                (offsets pointer, sort fields, n_rows, largest sort field); a stale or missing entry, or a table
+ *                                of more than 128 sort fields, gives index order or another order of the same tiles: it can cost
+ *                                time, never correctness.
  *   "sort_ahead"   (default 16) most batches sorted per side-stream launch in fmx_fm_stream / fmx_deepfm_stream (1..16).
  *   "sort_chunked" (default 1)  0: one workgroup per field at every width; 1: k_sort_chunk + k_sort_merge (1,024-composite
  *                                chunks spread over the chip, stable rank merge) from 8,192 composites per field on; 2: from 2,048 on.
@@ -190,6 +200,12 @@ const char *fmx_last_error_string(void);
  *                                in one launch); same results up to summation order.
  *   "online_persistent" (default 1)  0: fmx_online_run_mlp as per-sample launches instead of one workgroup walking the stream. */
 int fmx_set_option(const char *name, int value);
+
+/* The order option "upd_order" = mode gives n sort fields of rows[i] rows each (host memory; nothing is launched): order[i] is
+ * the field the grid takes i-th.  A permutation of 0..n-1 in ascending (1) or descending (2) row count, fields of equal count
+ * in index order (empty fields count 0 rows: first when ascending); mode 0: 0..n-1.  Returns n, or 0 with nothing written for
+ * n > 128: the launch carries one byte per field by value, and such a table is updated in index order.  Negative: bad argument. */
+int fmx_update_order(const int64_t *rows, int32_t n, int32_t mode, uint8_t *order);
 
 /* Smallest sort width for a batch: max(64, next power of two >= B); and log2 of it. */
 int fmx_sorted_width(int B);
