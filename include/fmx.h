@@ -779,6 +779,9 @@ int fmx_mlp_hedge_section(const fmx_mlp_t *mlp, float lr, float hedge_b, float h
  *   BP, BN [d, 2 m] row-major and counts [2] (columns in use) are read and written back; task 0 = cls (+-1 predictions), 1 = reg
  *   status [2]: status[0] = 1 when the prediction of sample status[1] was NaN (the run stops there)
  * Limits: d <= 32, 2 m <= 128, D <= 64, else FMX_ERR_UNSUPPORTED (the caller's host path).
+ * The count after a shrink is the exact rank logic on the d x d spectrum (never more than d); it can differ from the host
+ * path's once the rounding noise of that path's 2m x 2m SVD (~ eps lambda_max: a sketch norm from about 1e4 at thres = 1e-12)
+ * exceeds thres -- B B^T agrees either way ("Sketched FTRL").
  * Replaces: SFTRL_CCFM.online_learning / _GFD (reference models/models_online/SFTRL_CCFM.py:30-121), SFTRL_Vanila.py:30-130. */
 int fmx_sftrl_run(const double *X, const double *y, int32_t N, int32_t D, int32_t d, int32_t m, double eta, double thres,
                   int32_t task, double *BP, double *BN, int32_t *counts, double *w, double *g_w, double *pred_out,
