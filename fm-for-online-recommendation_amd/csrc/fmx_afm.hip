@@ -29,6 +29,9 @@
 //   k_afm_pair<KP, FTRL, BWD>  (fmx_afm_pair.inc) pairwise-ranking training: a workgroup walks PAIRS of rows (positive, negative) and
 //                         runs k_afm's row forward and backward under the pair loss of the two logits (fmx_afm_pair_*).
 //
+//   k_afm_list<KP, FTRL, BWD>  (fmx_afm_list.inc) listwise training: a workgroup walks LISTS of G rows (a positive, G - 1 negatives) and
+//                         runs the same row forward and backward under the softmax loss of the G logits (fmx_afm_list_*).
+//
 // No float is accumulated with atomics and every sum has one fixed order that depends on (B, F, t, k) alone: results are
 // bit-identical run to run.  The table update between the two launches is fmx_fm_update_occ (fmx_kernels.hip).
 
@@ -194,26 +197,36 @@ AfmOptArgs afm_opt_args(const fmx_afm_t *afm, const fmx_mlp_opt_t &o, int32_t t)
 // k_afm_pair (fmx_afm_pair.inc) over the a.B PAIRS of the 2 a.B rows of a.idx
 template <bool BWD>
 int launch_afm_pair(const AfmArgs &a, float margin, int kp, bool ftrl, hipStream_t st);
+// k_afm_list (fmx_afm_list.inc) over the a.B LISTS of the G a.B rows of a.idx
+template <bool BWD>
+int launch_afm_list(const AfmArgs &a, int G, int kp, bool ftrl, hipStream_t st);
 
 // One step on `st`: sort -> forward + backward -> table update (its last workgroups reduce the bias gradient and the loss) ->
 // attention gradient, with the attention parameters' rule for their step opt_t when opt is given.  The arguments have been checked.
 // pair_margin >= 0: the pair mode (fmx_afm_pair_*) -- the B rows are B / 2 pairs, row 2 i the positive and row 2 i + 1 the negative,
 // forward + backward is k_afm_pair under that margin (one workgroup per pair: B / 2 partials at most); y is not read.
+// list_g >= 2: the list mode (fmx_afm_list_*) -- the B rows are B / list_g lists, row list_g i the positive of list i, forward +
+// backward is k_afm_list (one workgroup per list); the update's bias rule runs on the scratch behind the workspace
+// (list_update_table: w.bytes + LIST_BIAS_SCRATCH bytes have been checked); y is not read.
 int afm_step_launches(const fmx_table_t *table, const fmx_hyper_t *hyper, int32_t rule, const fmx_afm_t *afm, const int32_t *idx,
                       const float *xv, const float *y, int32_t B, float inv_b, void *workspace, const AfmWs &w, float *attn_grad_out,
                       float *loss_out, int32_t *error, const fmx_mlp_opt_t *opt, int32_t opt_t, hipStream_t st,
-                      float *logit_out = nullptr, float pair_margin = -1.f) {
-  const bool pair = pair_margin >= 0.f;
+                      float *logit_out = nullptr, float pair_margin = -1.f, int32_t list_g = 0) {
+  const bool pair = pair_margin >= 0.f, list = list_g >= 2;
   if (int rc = fmx_sort_occurrences(table, idx, B, workspace, w.table_bytes, error, st)) return rc;
-  AfmArgs a = fill_afm(table, afm, hyper, idx, xv, y, pair ? B / 2 : B, FMX_LOSS_BCE_LOGITS, inv_b, error);
+  AfmArgs a = fill_afm(table, afm, hyper, idx, xv, y, pair ? B / 2 : list ? B / list_g : B, FMX_LOSS_BCE_LOGITS, inv_b, error);
   a.logit = logit_out;  // [B] or null (the online runs' per-sample launches)
   a.dz = w.dz;
   a.loss = w.loss;
   a.E = w.E;
   a.part = w.part;
   const bool ftrl = table->layout == FMX_LAYOUT_FTRL;
-  if (int rc = pair ? launch_afm_pair<true>(a, pair_margin, table->kp, ftrl, st) : launch_afm<true>(a, table->kp, ftrl, st)) return rc;
-  if (int rc = fmx_fm_update_occ(table, hyper, rule, workspace, w.table_bytes, xv, w.dz, w.E, table->n_fields * table->kp, B, w.loss,
+  if (int rc = pair   ? launch_afm_pair<true>(a, pair_margin, table->kp, ftrl, st)
+               : list ? launch_afm_list<true>(a, list_g, table->kp, ftrl, st)
+                      : launch_afm<true>(a, table->kp, ftrl, st))
+    return rc;
+  const fmx_table_t tu = list ? list_update_table(table, workspace, (size_t)w.bytes) : *table;
+  if (int rc = fmx_fm_update_occ(&tu, hyper, rule, workspace, w.table_bytes, xv, w.dz, w.E, table->n_fields * table->kp, B, w.loss,
                                  inv_b, loss_out, st))
     return rc;
   const dim3 grid((a.G + 63) / 64), block(256);
@@ -243,6 +256,7 @@ int launch_afm_online_k(const AfmOnlArgs &a, hipStream_t st) {
 }
 
 #include "fmx_afm_pair.inc"
+#include "fmx_afm_list.inc"
 
 }  // namespace
 
@@ -455,6 +469,55 @@ int fmx_afm_pair_online_run(const fmx_table_t *table, const fmx_hyper_t *hyper, 
 
 int fmx_afm_pair_online_form(const fmx_table_t *table, const fmx_afm_t *afm, int32_t attn_rule, int32_t *moments_in_lds) {
   return afm_pair_online_form_call(table, afm, attn_rule, moments_in_lds);
+}
+
+// ---- listwise (sampled-softmax) training: fmx_afm_list.inc ----
+int64_t fmx_afm_list_workspace_bytes(const fmx_table_t *table, const fmx_afm_t *afm, int32_t B_lists, int32_t G) {
+  const char *who = "fmx_afm_list_workspace_bytes";
+  if (int rc = check_afm(table, afm, who)) return rc;
+  if (B_lists < 1 || G < 2 || G > LIST_MAX_G || (int64_t)B_lists * G > INT32_MAX)
+    return fail(FMX_ERR_ARG, "%s: B_lists >= 1, 2 <= G <= %d and B_lists * G within int32", who, LIST_MAX_G);
+  const AfmWs w = carve_afm(table, afm, B_lists * G, nullptr);
+  if (w.table_bytes < 0) return w.table_bytes;
+  return w.bytes + LIST_BIAS_SCRATCH;
+}
+
+int fmx_afm_list_forward(const fmx_table_t *table, const fmx_afm_t *afm, const fmx_hyper_t *hyper, const int32_t *idx, const float *xv,
+                         int32_t B_lists, int32_t G, float inv_b, float *logit_out, float *loss_out, float *dz_out, int32_t *error,
+                         fmx_stream_t stream) {
+  return afm_list_forward_call(table, afm, hyper, idx, xv, B_lists, G, inv_b, logit_out, loss_out, dz_out, error,
+                               static_cast<hipStream_t>(stream));
+}
+
+int fmx_afm_list_step(const fmx_table_t *table, const fmx_hyper_t *hyper, int32_t rule, const fmx_afm_t *afm, const int32_t *idx,
+                      const float *xv, int32_t B_lists, int32_t G, float inv_b, void *workspace, int64_t workspace_bytes,
+                      float *attn_grad_out, float *logit_out, float *loss_out, int32_t *error, fmx_stream_t stream) {
+  return afm_list_steps_call("fmx_afm_list_step", table, hyper, rule, afm, idx, xv, 1, B_lists, G, inv_b, 1, workspace, workspace_bytes,
+                             attn_grad_out, nullptr, false, logit_out, loss_out, error, static_cast<hipStream_t>(stream));
+}
+
+int fmx_afm_list_step_opt(const fmx_table_t *table, const fmx_hyper_t *hyper, int32_t rule, const fmx_afm_t *afm, const int32_t *idx,
+                          const float *xv, int32_t B_lists, int32_t G, float inv_b, void *workspace, int64_t workspace_bytes,
+                          float *attn_grad_out, const fmx_mlp_opt_t *opt, float *logit_out, float *loss_out, int32_t *error,
+                          fmx_stream_t stream) {
+  return afm_list_steps_call("fmx_afm_list_step_opt", table, hyper, rule, afm, idx, xv, 1, B_lists, G, inv_b, 1, workspace,
+                             workspace_bytes, attn_grad_out, opt, true, logit_out, loss_out, error, static_cast<hipStream_t>(stream));
+}
+
+int fmx_afm_list_stream(const fmx_table_t *table, const fmx_hyper_t *hyper, int32_t rule, const fmx_afm_t *afm, const int32_t *idx_pool,
+                        const float *xv_pool, int32_t n_pool, int32_t B_lists, int32_t G, float inv_b, int32_t n_steps, void *workspace,
+                        int64_t workspace_bytes, float *attn_grad_out, const fmx_mlp_opt_t *opt, float *loss_out, int32_t *error,
+                        fmx_stream_t stream) {
+  return afm_list_steps_call("fmx_afm_list_stream", table, hyper, rule, afm, idx_pool, xv_pool, n_pool, B_lists, G, inv_b, n_steps,
+                             workspace, workspace_bytes, attn_grad_out, opt, true, nullptr, loss_out, error,
+                             static_cast<hipStream_t>(stream));
+}
+
+int fmx_afm_list_online_run(const fmx_table_t *table, const fmx_hyper_t *hyper, int32_t rule, const fmx_afm_t *afm, const int32_t *idx,
+                            const float *xv, int32_t N, int32_t G, void *workspace, int64_t workspace_bytes, float *attn_grad_out,
+                            const fmx_mlp_opt_t *opt, float *logit_out, float *loss_out, int32_t *error, fmx_stream_t stream) {
+  return afm_list_online_call(table, hyper, rule, afm, idx, xv, N, G, workspace, workspace_bytes, attn_grad_out, opt, logit_out, loss_out,
+                              error, static_cast<hipStream_t>(stream));
 }
 
 }  // extern "C"

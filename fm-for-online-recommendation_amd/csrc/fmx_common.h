@@ -115,6 +115,7 @@ inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 
 
 constexpr uint32_t SENT = 0xFFFFFFFFu;
 constexpr int WAVE = 64;
+constexpr int LIST_MAX_G = 16;  // rows per list of the listwise losses, every model family (k_fm_forward_list: one wave per row of a workgroup)
 constexpr int MAX_SORT_WIDTH = 32768;  // 128 KiB of the 160 KiB LDS
 constexpr int SORT_CHUNK = 1024;       // composites per chunk of the chunked sort (fmx_sort.inc); the workspace holds its runs from 2 chunks on
 

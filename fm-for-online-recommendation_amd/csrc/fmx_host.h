@@ -37,6 +37,10 @@ int check_workspace(const fmx_table_t *t, int B, const void *workspace, int64_t 
 // what every pair entry point refuses before it looks further: each message names the argument
 int check_pair_args(const fmx_table_t *table, const fmx_hyper_t *hyper, const int32_t *idx, int64_t n_pairs, const char *count_name,
                     float margin, const char *who);
+// what every list entry point refuses before it looks further (check_pair_args' refusals under the count's name B_lists, then G
+// and B_lists * G); *rows = B_lists * G
+int check_list_args(const fmx_table_t *table, const fmx_hyper_t *hyper, const int32_t *idx, int32_t B_lists, int32_t G, int32_t *rows,
+                    const char *who);
 // a shared check's refusal, with the entry point in front of its message
 int named(int rc, const char *who);
 // the entry points outside the pure-FM table steps: a refusal that names the rule
@@ -210,6 +214,15 @@ inline fmx_hyper_t kernel_hyper(const fmx_hyper_t *h, int rule) {
 
 constexpr int SORT_AHEAD_MAX = 16;  // batches sorted per side-stream launch in fmx_fm_stream (r3: 16, was 8 -- every group boundary puts a
                                     // cross-stream wait of 5 - 6 us on the step's stream: 21.33 - 21.39 against 21.53 - 21.79 us per step)
+
+// The list steps' bias scratch (fmx_list.inc's header says why): bytes behind the step workspace of `step_bytes` bytes, and the table
+// as the update of a list step takes it -- the bias rule runs on that scratch
+constexpr int64_t LIST_BIAS_SCRATCH = 16;  // >= the 3 floats the bias rule of a moments table reads and writes; keeps 16-byte alignment
+inline fmx_table_t list_update_table(const fmx_table_t *table, void *workspace, size_t step_bytes) {
+  fmx_table_t t = *table;
+  t.bias = reinterpret_cast<float *>(static_cast<char *>(workspace) + step_bytes);
+  return t;
+}
 
 inline Workspace carve(const fmx_table_t *t, int B, void *base) {
   const size_t F = (size_t)n_sort_fields(t), Bp = (size_t)fmx_sorted_width(B), tiles = Bp >> 6;

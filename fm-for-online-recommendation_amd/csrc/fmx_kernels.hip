@@ -303,7 +303,6 @@ __global__ __launch_bounds__(256) void k_fm_forward(FwdArgs a) {
 // to 16 waves needs its own launch bound (128 VGPRs per wave at 1024 threads) while k_fm_forward's instantiations keep theirs.  (The
 // six lines are repeated, not shared through a device function: routed through one, the pointwise instantiations of k_fm_forward
 // came out with another register assignment, and their code is to stay what it was -- tools/isa_diff.py.)
-constexpr int LIST_MAX_G = 16;
 template <int LPR, int LAYOUT, int NPASS>
 __global__ __launch_bounds__(64 * LIST_MAX_G) void k_fm_forward_list(FwdArgs a) {
   __builtin_amdgcn_s_setprio(3);
@@ -611,6 +610,16 @@ int check_pair_args(const fmx_table_t *table, const fmx_hyper_t *hyper, const in
   if (!(margin >= 0.f) || !std::isfinite(margin)) return fail(FMX_ERR_ARG, "%s: margin = %g must be finite and >= 0", who, (double)margin);
   if (mapped(table))
     return fail(FMX_ERR_UNSUPPORTED, "%s: tables whose fields are pieces of index columns (field_cols / field_base) are not taken", who);
+  return FMX_OK;
+}
+
+int check_list_args(const fmx_table_t *table, const fmx_hyper_t *hyper, const int32_t *idx, int32_t B_lists, int32_t G, int32_t *rows,
+                    const char *who) {
+  if (int rc = check_pair_args(table, hyper, idx, B_lists, "B_lists", 0.f, who)) return rc;
+  if (G < 2) return fail(FMX_ERR_ARG, "%s: G = %d: a list is a positive and at least one negative (G >= 2)", who, G);
+  if (G > LIST_MAX_G) return fail(FMX_ERR_UNSUPPORTED, "%s: G = %d: at most %d rows per list (one workgroup holds a list's waves)", who, G, LIST_MAX_G);
+  if ((int64_t)B_lists * G > INT32_MAX) return fail(FMX_ERR_ARG, "%s: B_lists = %d, G = %d: B_lists * G rows exceed int32", who, B_lists, G);
+  *rows = B_lists * G;
   return FMX_OK;
 }
 

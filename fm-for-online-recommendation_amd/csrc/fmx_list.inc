@@ -15,20 +15,7 @@
 // exists for the first-order weights of columns every row of a list shares (the context): their gradient is zero in exact
 // arithmetic and rounding-level here, and signadam normalises such a gradient like any other.
 
-constexpr int64_t LIST_BIAS_SCRATCH = 16;  // >= the 3 floats the bias rule of a moments table reads and writes; keeps 16-byte alignment
-
 inline int64_t list_workspace_bytes(const fmx_table_t *table, int32_t rows) { return (int64_t)carve(table, rows, nullptr).bytes + LIST_BIAS_SCRATCH; }
-
-// what every list entry point refuses before it looks further; *rows = B_lists * G
-int check_list_args(const fmx_table_t *table, const fmx_hyper_t *hyper, const int32_t *idx, int32_t B_lists, int32_t G, int32_t *rows,
-                    const char *who) {
-  if (int rc = check_pair_args(table, hyper, idx, B_lists, "B_lists", 0.f, who)) return rc;
-  if (G < 2) return fail(FMX_ERR_ARG, "%s: G = %d: a list is a positive and at least one negative (G >= 2)", who, G);
-  if (G > LIST_MAX_G) return fail(FMX_ERR_UNSUPPORTED, "%s: G = %d: at most %d rows per list (one workgroup holds a list's waves)", who, G, LIST_MAX_G);
-  if ((int64_t)B_lists * G > INT32_MAX) return fail(FMX_ERR_ARG, "%s: B_lists = %d, G = %d: B_lists * G rows exceed int32", who, B_lists, G);
-  *rows = B_lists * G;
-  return FMX_OK;
-}
 
 int list_forward_impl(const fmx_table_t *table, const fmx_hyper_t *hyper, const int32_t *idx, const float *xv, int32_t rows, int32_t G,
                       float inv_b, const fmx_fwd_out_t *out, hipStream_t st) {
@@ -63,13 +50,6 @@ int check_list_step(const fmx_table_t *table, const fmx_hyper_t *hyper, int32_t 
   return FMX_OK;
 }
 
-// the table as the update of a list step takes it: the bias rule runs on the scratch behind the step workspace
-inline fmx_table_t list_update_table(const fmx_table_t *table, const Workspace &w, void *workspace) {
-  fmx_table_t t = *table;
-  t.bias = reinterpret_cast<float *>(static_cast<char *>(workspace) + w.bytes);
-  return t;
-}
-
 // the list objective's forward, as step_run and stream_run call it
 inline auto list_forward(const fmx_table_t *table, const fmx_hyper_t *hyper, int32_t rows, int32_t G, float inv_b, const fmx_fwd_out_t *fwd) {
   return [=](const int32_t *idx, const float *xv, const float *, hipStream_t st) {
@@ -83,7 +63,7 @@ int list_step_call(const fmx_table_t *table, const fmx_hyper_t *hyper, int32_t r
   int32_t rows = 0;
   if (int rc = check_list_step(table, hyper, rule, idx, B_lists, G, workspace, workspace_bytes, fwd, 1, &rows, "fmx_fm_list_step")) return rc;
   const Workspace w = carve(table, rows, workspace);
-  const fmx_table_t tu = list_update_table(table, w, workspace);
+  const fmx_table_t tu = list_update_table(table, workspace, w.bytes);
   return step_run(table, &tu, hyper, rule, idx, xv, nullptr, rows, inv_b, w, fwd, loss_out, st, list_forward(table, hyper, rows, G, inv_b, fwd));
 }
 
@@ -96,7 +76,7 @@ int list_stream_call(const fmx_table_t *table, const fmx_hyper_t *hyper, int32_t
     return rc;
   if (int rc = check_pool_steps(n_pool, n_steps, who)) return rc;
   const Workspace w = carve(table, rows, workspace);
-  const fmx_table_t tu = list_update_table(table, w, workspace);
+  const fmx_table_t tu = list_update_table(table, workspace, w.bytes);
   return stream_run(table, &tu, hyper, rule, idx_pool, nullptr, n_pool, rows, inv_b, n_steps, w, fwd, loss_out, st,
                     list_forward(table, hyper, rows, G, inv_b, fwd));
 }

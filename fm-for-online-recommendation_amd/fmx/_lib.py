@@ -35,13 +35,15 @@ EXPORTS = ["fmx_version", "fmx_last_error_string", "fmx_set_option", "fmx_sorted
            "fmx_afm_pair_forward", "fmx_afm_pair_step", "fmx_afm_pair_step_opt", "fmx_afm_pair_stream", "fmx_afm_pair_online_run",
            "fmx_afm_pair_online_form", "fmx_fm_mine_negatives",
            "fmx_fm_list_workspace_bytes", "fmx_fm_list_forward", "fmx_fm_list_step", "fmx_fm_list_stream",
-           "fmx_fm_list_online_run", "fmx_update_order"]
+           "fmx_fm_list_online_run", "fmx_update_order",
+           "fmx_afm_list_workspace_bytes", "fmx_afm_list_forward", "fmx_afm_list_step", "fmx_afm_list_step_opt",
+           "fmx_afm_list_stream", "fmx_afm_list_online_run"]
 
 
 I64_RETURNS = ("fmx_workspace_bytes", "fmx_mlp_section_workspace_bytes", "fmx_fm_topk_workspace_bytes",
                "fmx_mlp_topk_workspace_bytes", "fmx_afm_workspace_bytes", "fmx_afm_topk_workspace_bytes",
                "fmx_fm_rank_workspace_bytes", "fmx_mlp_rank_workspace_bytes", "fmx_afm_rank_workspace_bytes",
-               "fmx_fm_list_workspace_bytes")   # byte counts: int64_t in include/fmx.h
+               "fmx_fm_list_workspace_bytes", "fmx_afm_list_workspace_bytes")   # byte counts: int64_t in include/fmx.h
 
 
 class FmxError(RuntimeError):
@@ -190,6 +192,12 @@ def load():
     lib.fmx_fm_list_step.argtypes = [TP, HP, i32, p, p, i32, i32, f32, p, i64, FP, p, p]
     lib.fmx_fm_list_stream.argtypes = [TP, HP, i32, p, i32, i32, i32, f32, i32, p, i64, FP, p, p]
     lib.fmx_fm_list_online_run.argtypes = [TP, HP, i32, p, p, i32, i32, p, p, p, p, p]
+    lib.fmx_afm_list_workspace_bytes.argtypes = [TP, AP, i32, i32]
+    lib.fmx_afm_list_forward.argtypes = [TP, AP, HP, p, p, i32, i32, f32, p, p, p, p, p]
+    lib.fmx_afm_list_step.argtypes = [TP, HP, i32, AP, p, p, i32, i32, f32, p, i64, p, p, p, p, p]
+    lib.fmx_afm_list_step_opt.argtypes = [TP, HP, i32, AP, p, p, i32, i32, f32, p, i64, p, OP, p, p, p, p]
+    lib.fmx_afm_list_stream.argtypes = [TP, HP, i32, AP, p, p, i32, i32, i32, f32, i32, p, i64, p, OP, p, p, p]
+    lib.fmx_afm_list_online_run.argtypes = [TP, HP, i32, AP, p, p, i32, i32, p, i64, p, OP, p, p, p, p]
     for name in EXPORTS:
         fn = getattr(lib, name)
         if name in I64_RETURNS:

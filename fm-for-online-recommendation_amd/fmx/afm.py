@@ -1,5 +1,6 @@
 """AFMEngine: workspace + launch sequencing of the attentional FM (fmx_afm_forward / fmx_afm_step / fmx_afm_step_opt /
-fmx_afm_stream / fmx_afm_online_run, and their pairwise-ranking forms fmx_afm_pair_*) for one FlatTable.
+fmx_afm_stream / fmx_afm_online_run, their pairwise-ranking forms fmx_afm_pair_* and their listwise forms fmx_afm_list_*) for one
+FlatTable.
 
 The attention parameters live in ONE flat fp32 device buffer [ W (t x k) | b (t) | h (t) | p (k) ] (include/fmx.h, fmx_afm_t);
 the step returns their gradient in the same layout and leaves updating them to the caller -- or, given an AfmOpt, applies their
@@ -9,7 +10,7 @@ import ctypes as C
 import torch
 
 from . import _lib
-from .engine import FMEngine, MlpOpt, _ptr
+from .engine import FMEngine, MlpOpt, _list_G, _ptr
 from .pairwise import n_pairs
 from .table import FlatTable
 
@@ -185,6 +186,81 @@ class AFMEngine:
         self._counted(self.lib.fmx_afm_pair_online_run, (self.table.c_struct(), hyper.ref(), _lib.RULES[rule], C.byref(self.c_afm),
                                                          idx_d.data_ptr(), _ptr(xv_d), N, margin, self.workspace.data_ptr(),
                                                          self.workspace.numel() * 4, self.grad.data_ptr(), opt.ref(), _ptr(logits),
+                                                         _ptr(losses), self.error.data_ptr(), self._stream(stream)), hyper, N, opt)
+
+    # ---- listwise (sampled-softmax) training: rows [B G, F] from fmx.pairwise.assemble_lists, row G i the positive of list i ----
+    def _list_rows(self, idx_d, xv_d, G, ws_lists=None):
+        """-> B for the rows [B G, F] of B lists; grows the buffers, and keeps the list steps' own workspace, self._list_ws, sized
+        through fmx_afm_list_workspace_bytes for ws_lists lists (default B): the AFM step's workspace and the scratch behind it
+        that the bias rule of a list step runs on."""
+        G = _list_G(G)
+        assert idx_d.dtype == torch.int32 and idx_d.is_contiguous() and idx_d.dim() == 2 and idx_d.shape[1] == self.table.n_fields
+        assert xv_d is None or (xv_d.dtype == torch.float32 and xv_d.is_contiguous() and xv_d.shape == idx_d.shape)
+        rows = idx_d.shape[0]
+        if rows < G or rows % G:
+            raise ValueError(f"list rows must be [B G, F] with B >= 1 and G = {G}, got {rows} rows")
+        B = rows // G
+        n = B if ws_lists is None else int(ws_lists)
+        self._ensure(n * G)
+        need = int(self.lib.fmx_afm_list_workspace_bytes(self.table.c_struct(), C.byref(self.c_afm), n, G))
+        if need < 0:
+            _lib.check(need)
+        ws = getattr(self, "_list_ws", None)
+        if ws is None or need > ws.numel() * 4:
+            self._list_ws = torch.zeros(need // 4, dtype=torch.int32, device=self.device)
+        return B
+
+    def list_forward(self, hyper, idx_d, G, xv_d=None, inv_b=None, dz=None, stream=None):
+        """-> B; the B G logits in self.logit[:B G] (the bits of forward()), the list losses in self.loss_b[0:B G:G] (the
+        negatives' slots +0).  dz: an fp32 device tensor of B G elements for dlogit (inv_b folded in, default 1 / B), or None."""
+        B = self._list_rows(idx_d, xv_d, G)
+        assert dz is None or (dz.dtype == torch.float32 and dz.is_contiguous() and dz.numel() >= B * G)
+        _lib.check(self.lib.fmx_afm_list_forward(self.table.c_struct(), C.byref(self.c_afm), hyper.ref(), idx_d.data_ptr(), _ptr(xv_d),
+                                                 B, int(G), 1.0 / B if inv_b is None else inv_b, self.logit.data_ptr(),
+                                                 self.loss_b.data_ptr(), _ptr(dz), self.error.data_ptr(), self._stream(stream)))
+        return B
+
+    def list_step(self, hyper, rule, idx_d, G, xv_d=None, inv_b=None, stream=None, opt=None):
+        """One mini-batch list step: the table updated under `rule` (its bias untouched), the mean list loss in self.loss_out[0],
+        the attention gradient in self.grad, the B G logits before the update in self.logit[:B G] (no sync here).  opt (an
+        AfmOpt): the attention parameters take its rule in the same call (fmx_afm_list_step_opt) and its step count advances."""
+        B = self._list_rows(idx_d, xv_d, G)
+        head = (self.table.c_struct(), hyper.ref(), _lib.RULES[rule], C.byref(self.c_afm), idx_d.data_ptr(), _ptr(xv_d), B, int(G),
+                1.0 / B if inv_b is None else inv_b, self._list_ws.data_ptr(), self._list_ws.numel() * 4, self.grad.data_ptr())
+        tail = (self.logit.data_ptr(), self.loss_out.data_ptr(), self.error.data_ptr(), self._stream(stream))
+        if opt is None:
+            self._counted(self.lib.fmx_afm_list_step, (*head, *tail), hyper)
+        else:
+            self._counted(self.lib.fmx_afm_list_step_opt, (*head, opt.ref(), *tail), hyper, 1, opt)
+
+    def list_stream(self, hyper, rule, idx_pool, xv_pool, B, G, n_steps, opt, inv_b=None, losses=None, stream=None):
+        """n_steps list steps over a device-resident pool in one call (fmx_afm_list_stream; no sync here): idx_pool
+        [n_pool, B G, F] int32, xv_pool the same shape in fp32 or None (ones); step s takes batch s mod n_pool.  losses: an fp32
+        device tensor of n_steps elements, or None.  The table's step count and opt's advance by n_steps."""
+        B, G, n_steps = int(B), _list_G(G), int(n_steps)
+        n_pool = idx_pool.numel() // (B * G * self.table.n_fields)
+        assert n_pool >= 1 and idx_pool.numel() == n_pool * B * G * self.table.n_fields
+        assert xv_pool is None or (xv_pool.dtype == torch.float32 and xv_pool.is_contiguous() and xv_pool.numel() == idx_pool.numel())
+        assert losses is None or (losses.dtype == torch.float32 and losses.numel() >= n_steps)
+        first = idx_pool.reshape(n_pool, B * G, self.table.n_fields)[0]
+        self._list_rows(first, None, G)
+        self._counted(self.lib.fmx_afm_list_stream, (self.table.c_struct(), hyper.ref(), _lib.RULES[rule], C.byref(self.c_afm),
+                                                     idx_pool.data_ptr(), _ptr(xv_pool), n_pool, B, G,
+                                                     1.0 / B if inv_b is None else inv_b, n_steps, self._list_ws.data_ptr(),
+                                                     self._list_ws.numel() * 4, self.grad.data_ptr(), opt.ref(), _ptr(losses),
+                                                     self.error.data_ptr(), self._stream(stream)), hyper, n_steps, opt)
+
+    def list_online_run(self, hyper, rule, idx_d, G, xv_d, opt, logits=None, losses=None, stream=None):
+        """The online protocol for lists in one call (fmx_afm_list_online_run; no sync here): every list of idx_d [N G, F] is
+        predicted, then fitted on alone -- N steps of list_step(B = 1, inv_b = 1), queued.  logits: an fp32 device tensor of N G
+        elements for each list's logits BEFORE its update; losses: N elements; or None.  The table's step count and opt's
+        advance by N."""
+        N = self._list_rows(idx_d, xv_d, G, ws_lists=1)
+        assert logits is None or (logits.dtype == torch.float32 and logits.is_contiguous() and logits.numel() >= N * G)
+        assert losses is None or (losses.dtype == torch.float32 and losses.is_contiguous() and losses.numel() >= N)
+        self._counted(self.lib.fmx_afm_list_online_run, (self.table.c_struct(), hyper.ref(), _lib.RULES[rule], C.byref(self.c_afm),
+                                                         idx_d.data_ptr(), _ptr(xv_d), N, int(G), self._list_ws.data_ptr(),
+                                                         self._list_ws.numel() * 4, self.grad.data_ptr(), opt.ref(), _ptr(logits),
                                                          _ptr(losses), self.error.data_ptr(), self._stream(stream)), hyper, N, opt)
 
     def pair_online_form(self, attn_rule):

@@ -46,7 +46,7 @@ class RankingTraining:
         elif own is None:
             parts.append(f"the attentional FM would need the {epilogue} epilogue behind its own forward")
         if own is not None:
-            parts.append(f"{method}(..., {own[0]}=True) trains on the pair loss of {own[1]} logit")
+            parts.append(f"{method}(..., {own[0]}=True) trains on the {loss} loss of {own[1]} logit")
         raise NotImplementedError("; ".join(parts))
 
     # ---- positives and their negatives as rows ----

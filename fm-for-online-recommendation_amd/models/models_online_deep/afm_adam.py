@@ -1,5 +1,6 @@
 """AFMAdam: the attentional factorization machine (Xiao et al. 2017) on the gfx950 kernels (fmx_afm_forward / fmx_afm_step;
-pairwise-ranking training on the same logit: fmx_afm_pair_*, fit_pairs / run_pair_experiment with attention=True).
+pairwise-ranking training on the same logit: fmx_afm_pair_*, fit_pairs / run_pair_experiment with attention=True; listwise
+training: fmx_afm_list_*, fit_lists / run_list_experiment with attention=True).
 
 The model (include/fmx.h, DESIGN.md section 3 "AFM"): per sample, with e_f = x_f V[row_f] and w_f the first-order weight, over
 the P = F (F - 1) / 2 pairs in the order i = 0..F-2, j = i+1..F-1,
@@ -228,11 +229,11 @@ class AFMAdam(RankingTraining, nn.Module):
         return out
 
     # ---- pairwise-ranking (BPR) training on the attentional logit (fmx_afm_pair_*; the pair objective of the other classes) ----
-    def _pair_refusal(self, method, attention):
-        """The default keeps the other classes' reading of these two methods -- the pair loss of the pure FM logit, which this
+    def _pair_refusal(self, method, attention, loss="pair"):
+        """The default keeps the other classes' reading of these methods -- the pair or list loss of the pure FM logit, which this
         model does not have; attention=True trains on the logit forward() gives."""
         if not attention:
-            self._pure_fm_only(method, own=("attention", "the attentional FM's"))
+            self._pure_fm_only(method, loss, own=("attention", "the attentional FM's"))
 
     def fit_pairs(self, Xi, Xv, item_fields, negatives=None, n_neg=1, margin=0.0, candidates=None, generator=None, attention=False):
         """OnlineFMBase.fit_pairs's arguments; attention=True: one mini-batch pair step of the whole model (tables and attention)
@@ -251,7 +252,59 @@ class AFMAdam(RankingTraining, nn.Module):
         self._after_step()
         return out
 
-    # (fit_lists / run_list_experiment / mine_negatives: RankingTraining's, which refuse them for this model by name)
+    # ---- listwise (sampled-softmax) training on the attentional logit (fmx_afm_list_*; the list objective of FMAdam) ----
+    def _list_entry(self, method, negatives, n_neg, attention):
+        """What fit_lists / run_list_experiment decide before they look at the model: without attention the pure FM's refusal,
+        first; then the limit of negatives, then the mined negatives' refusal."""
+        self._pair_refusal(method, attention, "list")
+        if negatives is None or fmx.pairwise.hard_negatives(negatives) is not None:
+            self._list_limit(method, n_neg)
+        self._refuse_hard_negatives(method, negatives)
+
+    def fit_lists(self, Xi, Xv, item_fields, negatives=None, n_neg=4, candidates=None, generator=None, attention=False):
+        """FMAdam.fit_lists's arguments; attention=True: one mini-batch list step of the whole model (tables and attention) on
+        -log softmax of the positive's logit among its list's, over the logit forward() gives, inv_b = 1 / lists; returns the
+        mean list loss.  At most 15 negatives per positive; the bias does not move.  fused_optimizer=True: one
+        fmx_afm_list_step_opt call; False: fmx_afm_list_step, then the attention parameters' rule on torch, as fit_pairs splits."""
+        self._list_entry("fit_lists", negatives, n_neg, attention)
+        self.train()
+        idx_d, xv_d, _ = self._inputs(Xi, Xv)
+        rows, xv, G = self._list_rows("fit_lists", idx_d, xv_d, item_fields, negatives, n_neg, candidates, generator)
+        e = self._engine
+        e.list_step(self._hyper, self.update_rule, rows, G, xv, opt=self._attn_fused)
+        if self._attn_fused is None:
+            self._apply_attention(e.grad)
+        out = e.loss_out[0].clone()
+        self._after_step()
+        return out
+
+    def run_list_experiment(self, Xi, Xv, item_fields, negatives=None, n_neg=4, candidates=None, generator=None, attention=False):
+        """FMAdam.run_list_experiment's arguments and 4-tuple; attention=True: for every list predict the positive's rank among
+        its negatives from the logits before the list's update (correct: rank 0, no negative's logit >= the positive's), then
+        fit on that list alone.  fused_optimizer=True: one upload and ONE fmx_afm_list_online_run call; False: the host loop of
+        one-list fit_lists(attention=True) -- the same protocol."""
+        self._list_entry("run_list_experiment", negatives, n_neg, attention)
+        start = time()
+        self.train()
+        idx_d, xv_d, _ = self._inputs(Xi, Xv)
+        n, e = idx_d.shape[0], self._engine
+        if n == 0:
+            return self._experiment_result(start, None)
+        rows, xv, G = self._list_rows("run_list_experiment", idx_d, xv_d, item_fields, negatives, n_neg, candidates, generator)
+        if self._attn_fused is not None:
+            logits = torch.empty(n * G, dtype=torch.float32, device=self.device)
+            e.list_online_run(self._hyper, self.update_rule, rows, G, xv, self._attn_fused, logits=logits)
+            z = logits.view(n, G)
+            return self._experiment_result(start, ((z[:, 1:] >= z[:, :1]).sum(1) == 0).to(torch.uint8))
+        fields = self._item_fields(item_fields)
+
+        def fit_one(i):
+            lst = rows[G * i:G * (i + 1)]
+            self.fit_lists(lst[:1], None if xv is None else xv[G * i:G * i + 1], fields,
+                           negatives=lst[1:, fields].reshape(1, G - 1, -1), attention=True)
+        return self._experiment_result(start, self._host_stream_loop(n, fit_one, lambda: (e.logit[1:G] >= e.logit[0]).sum() == 0))
+
+    # (mine_negatives: RankingTraining's, which refuses it for this model by name)
 
     def run_pair_experiment(self, Xi, Xv, item_fields, negatives=None, n_neg=1, margin=0.0, candidates=None, generator=None,
                             attention=False):

@@ -1100,6 +1100,85 @@ int fmx_afm_pair_online_run(const fmx_table_t *table, const fmx_hyper_t *hyper, 
  * which kernel a result came from. */
 int fmx_afm_pair_online_form(const fmx_table_t *table, const fmx_afm_t *afm, int32_t attn_rule, int32_t *moments_in_lds);
 
+/* ---- listwise (sampled-softmax) training of the attentional FM: one positive, G - 1 negatives ----
+ * The objective and the layout are fmx_fm_list_*'s (above fmx_fm_list_workspace_bytes) over the FULL attentional logit: a batch of
+ * B_lists lists of G rows (2 <= G <= 16) is idx [B_lists G, F] (xv of the same shape, or null: ones), row G i the positive of list
+ * i, rows G i + 1 .. G i + G - 1 its negatives; z_j is the logit fmx_afm_forward gives row G i + j (its bits), and
+ *     loss_i = log sum_j exp(z_j - m) - (z_0 - m),   dz_j = p_j inv_b (j >= 1),   dz_0 = -(sum_{j>=1} p_j) inv_b
+ * evaluated by the FM family's own formula on the same operands in the same order.  One workgroup of one wavefront owns a list
+ * (k_afm_list): the negatives' forwards, then the positive's, the loss once, then the positive's backward and, after each
+ * negative's forward AGAIN, its backward -- the recomputation of fmx_afm_pair_*, for its reason.
+ * Order of the sums: the attention accumulators [ dW | db | dh | dp ] of a workgroup take a list's positive tiles first, then its
+ * negatives' tiles in row order, each in the pair order of fmx_afm_step; lists in the workgroup's walk order; the workgroups'
+ * partials in workgroup order.  No float is accumulated with atomics; every sum has one fixed order that depends on
+ * (B_lists, G, F, t, k) alone.
+ * The bias: as in fmx_fm_list_*, the table update's bias rule runs on 16 scratch bytes behind the step workspace; the forward reads
+ * the real bias, and the bias and its state (z / n, moments) are BIT-UNCHANGED under every rule, FMX_RULE_ADAM included.
+ * Refused before anything is launched, each message naming the entry point: fmx_fm_list_*'s shared refusals (a null table / hyper /
+ * idx, B_lists < 1, G < 2, B_lists G beyond int32: FMX_ERR_ARG; G > 16 and tables whose fields are pieces of index columns:
+ * FMX_ERR_UNSUPPORTED); then what fmx_afm_step / fmx_afm_step_opt refuse for B_lists G rows (the AFM's limits, a null workspace /
+ * attn_grad_out / opt, the rule against the layout, the workspace's size and alignment, the attention rule's state,
+ * FMX_RULE_ADAM's hyper-parameters, the sort's geometry).  error [1] or null: set to 1 when an index lies outside its field; that
+ * row is treated as absent, as in fmx_afm_step.
+ * Replaces: nothing -- the reference has no listwise loss.  Its nearest counterpart is the pair objective of reference
+ * models/models_meta_emb/meta_fm.py:145-169, which this generalises from one negative to G - 1 for the AFM logit. */
+
+/* Bytes of caller-owned device workspace a list step of B_lists lists of G rows needs: fmx_afm_workspace_bytes(table, afm,
+ * B_lists G) plus the 16 scratch bytes the bias rule runs on (at the end; 16-byte aligned).  Negative on a bad table or afm,
+ * B_lists < 1, G outside [2, 16] or B_lists G beyond int32.
+ * Replaces: nothing in the reference (nearest: meta_fm.py:145-169).  Restates: fmx_fm_list_workspace_bytes for the AFM step. */
+int64_t fmx_afm_list_workspace_bytes(const fmx_table_t *table, const fmx_afm_t *afm, int32_t B_lists, int32_t G);
+
+/* The forward pass of the B_lists G rows with the list epilogue.  logit_out [B_lists G]: the bits fmx_afm_forward(FMX_LOSS_NONE)
+ * gives on the same rows; loss_out [B_lists G]: loss[G i] = loss_i (unscaled), loss[G i + j] = +0 for j >= 1; dz_out [B_lists G]:
+ * dz[G i + j] = dz_j as above.  Each of the three may be null.
+ * Replaces: nothing in the reference, which has no listwise loss; nearest: the forward and loss of the pair objective
+ * (meta_fm.py:145-169) on AFMAdam.forward (afm_adam.py:43-74). */
+int fmx_afm_list_forward(const fmx_table_t *table, const fmx_afm_t *afm, const fmx_hyper_t *hyper, const int32_t *idx, const float *xv,
+                         int32_t B_lists, int32_t G, float inv_b, float *logit_out, float *loss_out, float *dz_out, int32_t *error,
+                         fmx_stream_t stream);
+
+/* One list step on one stream: fmx_sort_occurrences(B_lists G) -> list forward + backward -> fmx_fm_update_occ(B_lists G) under
+ * `rule` (its bias rule on the scratch) -> the fixed-order reduction of the attention partials.  The attention parameters are NOT
+ * updated: attn_grad_out [t k + 2 t + k] receives the gradient of inv_b * sum_i loss_i.  logit_out [B_lists G] or null: the logits
+ * before the update; loss_out [1] = inv_b * sum_i loss_i (may be null).  workspace: fmx_afm_list_workspace_bytes bytes.
+ * Replaces: nothing in the reference; nearest: fmx_afm_pair_step's objective (meta_fm.py:145-169) with G - 1 negatives. */
+int fmx_afm_list_step(const fmx_table_t *table, const fmx_hyper_t *hyper, int32_t rule, const fmx_afm_t *afm, const int32_t *idx,
+                      const float *xv, int32_t B_lists, int32_t G, float inv_b, void *workspace, int64_t workspace_bytes,
+                      float *attn_grad_out, float *logit_out, float *loss_out, int32_t *error, fmx_stream_t stream);
+
+/* fmx_afm_list_step with the attention parameters under opt's rule inside the reduction, as fmx_afm_step_opt: the call is step
+ * opt->step + 1 of the attention parameters (read, never written).  attn_grad_out, logit_out, loss_out, error and every table word
+ * are bit-identical to fmx_afm_list_step on the same inputs.
+ * Replaces: nothing in the reference; nearest: fmx_afm_pair_step_opt's objective (meta_fm.py:145-169) with G - 1 negatives. */
+int fmx_afm_list_step_opt(const fmx_table_t *table, const fmx_hyper_t *hyper, int32_t rule, const fmx_afm_t *afm, const int32_t *idx,
+                          const float *xv, int32_t B_lists, int32_t G, float inv_b, void *workspace, int64_t workspace_bytes,
+                          float *attn_grad_out, const fmx_mlp_opt_t *opt, float *logit_out, float *loss_out, int32_t *error,
+                          fmx_stream_t stream);
+
+/* n_steps list steps over a device-resident pool idx_pool [n_pool, B_lists G, F] (xv_pool the same shape, or null), issued from one
+ * call as a plain queue of launches without any host synchronisation, as fmx_afm_pair_stream: step s takes batch s mod n_pool and
+ * is step hyper->step + s + 1 of the tables and opt->step + s + 1 of the attention parameters.  loss_out [n_steps] or null.
+ * Also refused: n_pool < 1, n_steps < 0, step + n_steps beyond int32: FMX_ERR_ARG; n_steps = 0 launches nothing.
+ * The result is, bit for bit, the one of n_steps calls of fmx_afm_list_step_opt with both step counts advanced by the caller.
+ * Replaces: nothing in the reference; nearest: fmx_afm_pair_stream's objective (meta_fm.py:145-169) with G - 1 negatives. */
+int fmx_afm_list_stream(const fmx_table_t *table, const fmx_hyper_t *hyper, int32_t rule, const fmx_afm_t *afm, const int32_t *idx_pool,
+                        const float *xv_pool, int32_t n_pool, int32_t B_lists, int32_t G, float inv_b, int32_t n_steps, void *workspace,
+                        int64_t workspace_bytes, float *attn_grad_out, const fmx_mlp_opt_t *opt, float *loss_out, int32_t *error,
+                        fmx_stream_t stream);
+
+/* The online predict-then-fit protocol restated for lists on N device-resident lists idx [N G, F]: every list is predicted, then
+ * fitted on alone.  The contract: bit for bit N calls of fmx_afm_list_step_opt(B_lists = 1, inv_b = 1), list i being step
+ * hyper->step + i + 1 of the tables and opt->step + i + 1 of the attention parameters (both read, never written).  logit_out [N G]
+ * or null: each list's logits BEFORE its update (the positive is ranked first when no negative's logit is >= logit[G i]); loss_out
+ * [N] or null: each list's loss.  workspace: fmx_afm_list_workspace_bytes(table, afm, 1, G) bytes.  N < 0: FMX_ERR_ARG; N = 0
+ * launches nothing and returns 0 (the buffers may be null).  One form: the lists' step launches queued without any host
+ * synchronisation (there is no one-workgroup walker for lists).
+ * Replaces: nothing in the reference; nearest: the protocol of fm_adam.py:90-119 under the pair objective of meta_fm.py:145-169. */
+int fmx_afm_list_online_run(const fmx_table_t *table, const fmx_hyper_t *hyper, int32_t rule, const fmx_afm_t *afm, const int32_t *idx,
+                            const float *xv, int32_t N, int32_t G, void *workspace, int64_t workspace_bytes, float *attn_grad_out,
+                            const fmx_mlp_opt_t *opt, float *logit_out, float *loss_out, int32_t *error, fmx_stream_t stream);
+
 /* ---- top-K recommendation under the AFM (fmx/recommend.py, AFMAdam.recommend) ----
  * Split the fields into context fields C and item fields I (at least one of each).  A combined sample's pairs are the C x C
  * pairs (u alone), the I x I pairs (c alone) and the |C| |I| cross pairs.  Each side's own pairs reduce to (lin, m, Z, R):
