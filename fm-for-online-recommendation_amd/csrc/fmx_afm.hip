@@ -32,6 +32,11 @@
 //   k_afm_list<KP, FTRL, BWD>  (fmx_afm_list.inc) listwise training: a workgroup walks LISTS of G rows (a positive, G - 1 negatives) and
 //                         runs the same row forward and backward under the softmax loss of the G logits (fmx_afm_list_*).
 //
+// The host side defines once what the three objectives (BCE on y, pairs, lists) share: afm_step_launches, one step's launches under
+// an AfmObjective (the kind, the rows per unit, the margin); afm_steps_run, the ONE queue of steps behind every stream and every
+// queued online run; check_afm_unit_steps, the step check of the objectives that read no labels.  Every launcher raises its
+// kernel's dynamic-LDS limit through raise_lds_limit (fmx_host.h).  The entry points keep their own checks in their own order.
+//
 // No float is accumulated with atomics and every sum has one fixed order that depends on (B, F, t, k) alone: results are
 // bit-identical run to run.  The table update between the two launches is fmx_fm_update_occ (fmx_kernels.hip).
 
@@ -60,13 +65,7 @@ int check_afm(const fmx_table_t *t, const fmx_afm_t *afm, const char *who) {
 template <int KP, bool FTRL, bool BWD>
 int launch_afm_k(const AfmArgs &a, hipStream_t st) {
   const size_t lds = (size_t)afm_lds(a.F, KP, a.t, BWD).total * 4;
-  static std::once_flag once;
-  static hipError_t raised = hipSuccess;
-  std::call_once(once, [] {
-    raised = hipFuncSetAttribute(reinterpret_cast<const void *>(k_afm<KP, FTRL, BWD>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                 (int)(afm_lds(AFM_MAX_F, KP, AFM_MAX_T, BWD).total * 4));
-  });
-  if (raised != hipSuccess) return fail(FMX_ERR_LAUNCH, "hipFuncSetAttribute(k_afm): %s", hipGetErrorString(raised));
+  if (int rc = raise_lds_limit<k_afm<KP, FTRL, BWD>>((int)(afm_lds(AFM_MAX_F, KP, AFM_MAX_T, BWD).total * 4), "k_afm")) return rc;
   hipLaunchKernelGGL((k_afm<KP, FTRL, BWD>), dim3(afm_grid(a.B)), dim3(64), lds, st, a);
   return check_launch("k_afm");
 }
@@ -74,13 +73,7 @@ int launch_afm_k(const AfmArgs &a, hipStream_t st) {
 template <int KP, bool FTRL>
 int launch_afm_side_k(const AfmSideArgs &a, hipStream_t st) {
   const size_t lds = (size_t)afm_lds(a.n, KP, a.t, false).total * 4;
-  static std::once_flag once;
-  static hipError_t raised = hipSuccess;
-  std::call_once(once, [] {
-    raised = hipFuncSetAttribute(reinterpret_cast<const void *>(k_afm_side<KP, FTRL>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                 (int)(afm_lds(AFM_MAX_F, KP, AFM_MAX_T, false).total * 4));
-  });
-  if (raised != hipSuccess) return fail(FMX_ERR_LAUNCH, "hipFuncSetAttribute(k_afm_side): %s", hipGetErrorString(raised));
+  if (int rc = raise_lds_limit<k_afm_side<KP, FTRL>>((int)(afm_lds(AFM_MAX_F, KP, AFM_MAX_T, false).total * 4), "k_afm_side")) return rc;
   hipLaunchKernelGGL((k_afm_side<KP, FTRL>), dim3(afm_grid(a.R)), dim3(64), lds, st, a);
   return check_launch("k_afm_side");
 }
@@ -160,6 +153,13 @@ int check_afm_step(const fmx_table_t *table, const fmx_hyper_t *hyper, int32_t r
   return check_afm_ws(table, rule, afm, B, workspace, workspace_bytes, w, who);
 }
 
+// the attention parameters take one of four rules (fmx_mlp_opt_t's three and FMX_RULE_SIGNADAM)
+int check_attn_rule(int r, const char *who) {
+  if (r != FMX_RULE_SIGNADAM && r != FMX_RULE_SGD && r != FMX_RULE_ADAGRAD && r != FMX_RULE_ADAM)
+    return fail(FMX_ERR_ARG, "%s: the attention rule %d is not FMX_RULE_SIGNADAM, FMX_RULE_SGD, FMX_RULE_ADAGRAD or FMX_RULE_ADAM", who, r);
+  return FMX_OK;
+}
+
 // the attention parameters' optimizer state for a call of n_steps steps (fmx_mlp_opt_t with FMX_RULE_SIGNADAM accepted), and
 // what the steps' other calls would refuse after the first launch: the tables' FMX_RULE_ADAM hyper-parameters and the sort's
 // geometry.  Everything here is decided before anything is launched.
@@ -167,8 +167,7 @@ int check_afm_opt(const fmx_table_t *table, const fmx_hyper_t *hyper, int32_t ru
                   int64_t n_steps, const char *who) {
   if (!opt) return fail(FMX_ERR_ARG, "%s: null argument (opt)", who);
   const int r = opt->rule;
-  if (r != FMX_RULE_SIGNADAM && r != FMX_RULE_SGD && r != FMX_RULE_ADAGRAD && r != FMX_RULE_ADAM)
-    return fail(FMX_ERR_ARG, "%s: the attention rule %d is not FMX_RULE_SIGNADAM, FMX_RULE_SGD, FMX_RULE_ADAGRAD or FMX_RULE_ADAM", who, r);
+  if (int rc = check_attn_rule(r, who)) return rc;
   if (((r == FMX_RULE_ADAGRAD || r == FMX_RULE_ADAM) && !opt->v) || (r == FMX_RULE_ADAM && !opt->m))
     return fail(FMX_ERR_ARG, "%s: opt->v (FMX_RULE_ADAGRAD, FMX_RULE_ADAM) and opt->m (FMX_RULE_ADAM) must be given", who);
   if (r == FMX_RULE_ADAM && !(opt->beta1 >= 0.f && opt->beta1 < 1.f && opt->beta2 >= 0.f && opt->beta2 < 1.f))
@@ -194,6 +193,31 @@ AfmOptArgs afm_opt_args(const fmx_afm_t *afm, const fmx_mlp_opt_t &o, int32_t t)
   return a;
 }
 
+// The refusals of a call of n_steps steps of n_rows rows that reads no labels (the pair and the list steps), behind its objective's
+// own: the workspace and the rule (check_afm_ws), then the attention rule's state (check_afm_opt) or, without one, what it
+// decides for the tables (ADAM's hyper-parameters, the sort's geometry)
+int check_afm_unit_steps(const fmx_table_t *table, const fmx_hyper_t *hyper, int32_t rule, const fmx_afm_t *afm, int32_t n_rows,
+                         void *workspace, int64_t workspace_bytes, const float *attn_grad_out, const fmx_mlp_opt_t *opt, bool with_opt,
+                         int64_t n_steps, AfmWs &w, const char *who) {
+  if (!workspace || !attn_grad_out) return fail(FMX_ERR_ARG, "%s: null argument", who);
+  if (int rc = check_afm_ws(table, rule, afm, n_rows, workspace, workspace_bytes, w, who)) return rc;
+  if (with_opt) return check_afm_opt(table, hyper, rule, afm, n_rows, opt, n_steps, who);
+  if (int rc = named(check_adam(hyper, rule, n_steps), who)) return rc;
+  return named(check_sort_geometry(table, n_rows), who);
+}
+
+// What a step trains on.  Its rows are UNITS of `rows` rows each: samples under BCE on y (POINT); pairs, row 2 i the positive and
+// row 2 i + 1 the negative, under the pair loss with `margin` (PAIR, fmx_afm_pair_*); lists of G rows, row G i the positive of list
+// i, under the softmax loss (LIST, fmx_afm_list_*).  PAIR and LIST read no y.
+struct AfmObjective {
+  enum Kind { POINT, PAIR, LIST } kind;
+  int32_t rows;  // per unit: 1, 2 or G
+  float margin;  // PAIR
+};
+constexpr AfmObjective AFM_POINTWISE = {AfmObjective::POINT, 1, 0.f};
+inline AfmObjective afm_pairs(float margin) { return {AfmObjective::PAIR, 2, margin}; }
+inline AfmObjective afm_lists(int32_t G) { return {AfmObjective::LIST, G, 0.f}; }
+
 // k_afm_pair (fmx_afm_pair.inc) over the a.B PAIRS of the 2 a.B rows of a.idx
 template <bool BWD>
 int launch_afm_pair(const AfmArgs &a, float margin, int kp, bool ftrl, hipStream_t st);
@@ -201,29 +225,28 @@ int launch_afm_pair(const AfmArgs &a, float margin, int kp, bool ftrl, hipStream
 template <bool BWD>
 int launch_afm_list(const AfmArgs &a, int G, int kp, bool ftrl, hipStream_t st);
 
-// One step on `st`: sort -> forward + backward -> table update (its last workgroups reduce the bias gradient and the loss) ->
-// attention gradient, with the attention parameters' rule for their step opt_t when opt is given.  The arguments have been checked.
-// pair_margin >= 0: the pair mode (fmx_afm_pair_*) -- the B rows are B / 2 pairs, row 2 i the positive and row 2 i + 1 the negative,
-// forward + backward is k_afm_pair under that margin (one workgroup per pair: B / 2 partials at most); y is not read.
-// list_g >= 2: the list mode (fmx_afm_list_*) -- the B rows are B / list_g lists, row list_g i the positive of list i, forward +
-// backward is k_afm_list (one workgroup per list); the update's bias rule runs on the scratch behind the workspace
-// (list_update_table: w.bytes + LIST_BIAS_SCRATCH bytes have been checked); y is not read.
-int afm_step_launches(const fmx_table_t *table, const fmx_hyper_t *hyper, int32_t rule, const fmx_afm_t *afm, const int32_t *idx,
-                      const float *xv, const float *y, int32_t B, float inv_b, void *workspace, const AfmWs &w, float *attn_grad_out,
-                      float *loss_out, int32_t *error, const fmx_mlp_opt_t *opt, int32_t opt_t, hipStream_t st,
-                      float *logit_out = nullptr, float pair_margin = -1.f, int32_t list_g = 0) {
-  const bool pair = pair_margin >= 0.f, list = list_g >= 2;
+// One step of B rows on `st`: sort -> forward + backward -> table update (its last workgroups reduce the bias gradient and the
+// loss) -> attention gradient, with the attention parameters' rule for their step opt_t when opt is given.  The arguments have
+// been checked.  The objective decides the forward + backward: k_afm over the B samples, or k_afm_pair / k_afm_list over the
+// B / obj.rows units (one workgroup per unit: that many partials at most).  LIST: the update's bias rule runs on the scratch behind
+// the workspace (list_update_table: w.bytes + LIST_BIAS_SCRATCH bytes have been checked).
+// logit_out: [B] or null (fmx_afm_step and fmx_afm_stream keep no logits).
+int afm_step_launches(const fmx_table_t *table, const fmx_hyper_t *hyper, int32_t rule, const fmx_afm_t *afm, const AfmObjective &obj,
+                      const int32_t *idx, const float *xv, const float *y, int32_t B, float inv_b, void *workspace, const AfmWs &w,
+                      float *attn_grad_out, float *logit_out, float *loss_out, int32_t *error, const fmx_mlp_opt_t *opt, int32_t opt_t,
+                      hipStream_t st) {
+  const bool list = obj.kind == AfmObjective::LIST;
   if (int rc = fmx_sort_occurrences(table, idx, B, workspace, w.table_bytes, error, st)) return rc;
-  AfmArgs a = fill_afm(table, afm, hyper, idx, xv, y, pair ? B / 2 : list ? B / list_g : B, FMX_LOSS_BCE_LOGITS, inv_b, error);
-  a.logit = logit_out;  // [B] or null (the online runs' per-sample launches)
+  AfmArgs a = fill_afm(table, afm, hyper, idx, xv, y, B / obj.rows, FMX_LOSS_BCE_LOGITS, inv_b, error);
+  a.logit = logit_out;
   a.dz = w.dz;
   a.loss = w.loss;
   a.E = w.E;
   a.part = w.part;
   const bool ftrl = table->layout == FMX_LAYOUT_FTRL;
-  if (int rc = pair   ? launch_afm_pair<true>(a, pair_margin, table->kp, ftrl, st)
-               : list ? launch_afm_list<true>(a, list_g, table->kp, ftrl, st)
-                      : launch_afm<true>(a, table->kp, ftrl, st))
+  if (int rc = obj.kind == AfmObjective::PAIR ? launch_afm_pair<true>(a, obj.margin, table->kp, ftrl, st)
+               : list                         ? launch_afm_list<true>(a, obj.rows, table->kp, ftrl, st)
+                                              : launch_afm<true>(a, table->kp, ftrl, st))
     return rc;
   const fmx_table_t tu = list ? list_update_table(table, workspace, (size_t)w.bytes) : *table;
   if (int rc = fmx_fm_update_occ(&tu, hyper, rule, workspace, w.table_bytes, xv, w.dz, w.E, table->n_fields * table->kp, B, w.loss,
@@ -242,15 +265,34 @@ int afm_step_launches(const fmx_table_t *table, const fmx_hyper_t *hyper, int32_
   return check_launch("k_afm_reduce_opt");
 }
 
+// n_steps steps of `rows` rows each as ONE plain queue of launches on `st`: every batch is sorted in front of its step, as
+// fmx_afm_step does it (no side stream, no events, no host synchronisation; the sort-ahead loop of fmx_fm_stream is not used).
+// Step s takes batch s mod n_pool of the pools (idx [n_pool, rows, F]; xv the same or null; y [n_pool, rows], or null where the
+// objective reads none) under the tables' hyper-parameters of step s and, with opt, the attention parameters' step
+// opt->step + s + 1; its mean loss goes to loss_out[s] and its logits to logit_out + s logit_stride (either may be null).
+// The streams pass logit_stride 0; the online runs walk N units once (n_pool = n_steps = N, rows = obj.rows, inv_b = 1) and keep
+// every unit's logits before its update: logit_stride = rows.
+int afm_steps_run(const fmx_table_t *table, const fmx_hyper_t *hyper, int32_t rule, const fmx_afm_t *afm, const AfmObjective &obj,
+                  const int32_t *idx_pool, const float *xv_pool, const float *y_pool, int32_t n_pool, int32_t rows, float inv_b,
+                  int32_t n_steps, void *workspace, const AfmWs &w, float *attn_grad_out, const fmx_mlp_opt_t *opt, float *logit_out,
+                  int32_t logit_stride, float *loss_out, int32_t *error, hipStream_t st) {
+  const size_t F = (size_t)table->n_fields;
+  for (int s = 0; s < n_steps; ++s) {
+    const fmx_hyper_t hs = hyper_at_step(hyper, rule, s);
+    const size_t j = (size_t)(s % n_pool);
+    if (int rc = afm_step_launches(table, &hs, rule, afm, obj, idx_pool + j * rows * F, xv_pool ? xv_pool + j * rows * F : nullptr,
+                                   y_pool ? y_pool + j * rows : nullptr, rows, inv_b, workspace, w, attn_grad_out,
+                                   logit_out ? logit_out + (size_t)s * logit_stride : nullptr, loss_out ? loss_out + s : nullptr, error, opt,
+                                   opt ? opt->step + s + 1 : 0, st))
+      return rc;
+  }
+  return FMX_OK;
+}
+
 template <int KP>
 int launch_afm_online_k(const AfmOnlArgs &a, hipStream_t st) {
   const size_t lds = (size_t)afm_online_lds(a.F, KP, a.t, a.G, a.nb, a.mom_lds != 0).total * 4;
-  static std::once_flag once;
-  static hipError_t raised = hipSuccess;
-  std::call_once(once, [] {
-    raised = hipFuncSetAttribute(reinterpret_cast<const void *>(k_afm_online<KP>), hipFuncAttributeMaxDynamicSharedMemorySize, AFM_LDS_BYTES);
-  });
-  if (raised != hipSuccess) return fail(FMX_ERR_LAUNCH, "hipFuncSetAttribute(k_afm_online): %s", hipGetErrorString(raised));
+  if (int rc = raise_lds_limit<k_afm_online<KP>>(AFM_LDS_BYTES, "k_afm_online")) return rc;
   hipLaunchKernelGGL((k_afm_online<KP>), dim3(1), dim3(AFM_ONL_THREADS), lds, st, a);
   return check_launch("k_afm_online");
 }
@@ -290,8 +332,8 @@ int fmx_afm_step(const fmx_table_t *table, const fmx_hyper_t *hyper, int32_t rul
   const char *who = "fmx_afm_step";
   AfmWs w;
   if (int rc = check_afm_step(table, hyper, rule, afm, idx, y, B, workspace, workspace_bytes, attn_grad_out, w, who)) return rc;
-  return afm_step_launches(table, hyper, rule, afm, idx, xv, y, B, inv_b, workspace, w, attn_grad_out, loss_out, error, nullptr, 0,
-                           static_cast<hipStream_t>(stream));
+  return afm_step_launches(table, hyper, rule, afm, AFM_POINTWISE, idx, xv, y, B, inv_b, workspace, w, attn_grad_out, nullptr, loss_out,
+                           error, nullptr, 0, static_cast<hipStream_t>(stream));
 }
 
 int fmx_afm_step_opt(const fmx_table_t *table, const fmx_hyper_t *hyper, int32_t rule, const fmx_afm_t *afm, const int32_t *idx,
@@ -301,8 +343,8 @@ int fmx_afm_step_opt(const fmx_table_t *table, const fmx_hyper_t *hyper, int32_t
   AfmWs w;
   if (int rc = check_afm_step(table, hyper, rule, afm, idx, y, B, workspace, workspace_bytes, attn_grad_out, w, who)) return rc;
   if (int rc = check_afm_opt(table, hyper, rule, afm, B, opt, 1, who)) return rc;
-  return afm_step_launches(table, hyper, rule, afm, idx, xv, y, B, inv_b, workspace, w, attn_grad_out, loss_out, error, opt,
-                           opt->step + 1, static_cast<hipStream_t>(stream));
+  return afm_step_launches(table, hyper, rule, afm, AFM_POINTWISE, idx, xv, y, B, inv_b, workspace, w, attn_grad_out, nullptr, loss_out,
+                           error, opt, opt->step + 1, static_cast<hipStream_t>(stream));
 }
 
 int fmx_afm_stream(const fmx_table_t *table, const fmx_hyper_t *hyper, int32_t rule, const fmx_afm_t *afm, const int32_t *idx_pool,
@@ -314,18 +356,8 @@ int fmx_afm_stream(const fmx_table_t *table, const fmx_hyper_t *hyper, int32_t r
   if (int rc = check_afm_step(table, hyper, rule, afm, idx_pool, y_pool, B, workspace, workspace_bytes, attn_grad_out, w, who)) return rc;
   if (n_pool < 1 || n_steps < 0) return fail(FMX_ERR_ARG, "%s: n_pool = %d must be >= 1 and n_steps = %d >= 0", who, n_pool, n_steps);
   if (int rc = check_afm_opt(table, hyper, rule, afm, B, opt, n_steps, who)) return rc;
-  const hipStream_t st = static_cast<hipStream_t>(stream);
-  const size_t F = (size_t)table->n_fields;
-  // Every batch is sorted on `stream` in front of its step, as fmx_afm_step does it: the steps are one plain queue of launches
-  // (no side stream, no events; the sort-ahead loop of fmx_fm_stream is not used here).
-  for (int s = 0; s < n_steps; ++s) {
-    const fmx_hyper_t hs = hyper_at_step(hyper, rule, s);
-    const size_t j = (size_t)(s % n_pool);
-    if (int rc = afm_step_launches(table, &hs, rule, afm, idx_pool + j * B * F, xv_pool ? xv_pool + j * B * F : nullptr, y_pool + j * B, B,
-                                   inv_b, workspace, w, attn_grad_out, loss_out ? loss_out + s : nullptr, error, opt, opt->step + s + 1, st))
-      return rc;
-  }
-  return FMX_OK;
+  return afm_steps_run(table, hyper, rule, afm, AFM_POINTWISE, idx_pool, xv_pool, y_pool, n_pool, B, inv_b, n_steps, workspace, w,
+                       attn_grad_out, opt, nullptr, 0, loss_out, error, static_cast<hipStream_t>(stream));
 }
 
 int fmx_afm_online_run(const fmx_table_t *table, const fmx_hyper_t *hyper, int32_t rule, const fmx_afm_t *afm, const int32_t *idx,
@@ -342,49 +374,10 @@ int fmx_afm_online_run(const fmx_table_t *table, const fmx_hyper_t *hyper, int32
   const bool want_mom = opt->rule == FMX_RULE_ADAGRAD || opt->rule == FMX_RULE_ADAM;
   bool mom = false;
   const int nb = tune().afm_online_persistent ? afm_online_buffers(F, table->kp, afm->t, G, want_mom, mom) : 0;
-  if (nb == 0) {
-    // the per-sample launches of fmx_afm_step_opt(B = 1, inv_b = 1), queued without any host synchronisation
-    for (int i = 0; i < N; ++i) {
-      const fmx_hyper_t hs = hyper_at_step(hyper, rule, i);
-      if (int rc = afm_step_launches(table, &hs, rule, afm, idx + (size_t)i * F, xv ? xv + (size_t)i * F : nullptr, y + i, 1, 1.0f, workspace,
-                                     w, attn_grad_out, loss_out ? loss_out + i : nullptr, error, opt, opt->step + i + 1, st,
-                                     logit_out ? logit_out + i : nullptr))
-        return rc;
-    }
-    return FMX_OK;
-  }
-  AfmOnlArgs a;
-  memset(&a, 0, sizeof(a));
-  a.rows = table->rows;
-  a.foff = table->field_offsets;
-  a.bias = table->bias;
-  a.idx = idx;
-  a.xv = xv;
-  a.y = y;
-  a.params = afm->params;
-  a.m = opt->m;
-  a.v = opt->v;
-  a.grad = attn_grad_out;
-  a.logit = logit_out;
-  a.loss = loss_out;
-  a.error = error;
-  a.h = kernel_hyper(hyper, rule);  // ADAM: the kernel derives each sample's constants from lr, beta1, beta2, step
-  a.o_lr = opt->lr;
-  a.o_eps = opt->eps;
-  a.o_beta1 = opt->beta1;
-  a.o_beta2 = opt->beta2;
-  a.o_rule = opt->rule;
-  a.o_step = opt->step;
-  a.N = N;
-  a.F = F;
-  a.k = afm->k;
-  a.t = afm->t;
-  a.stride = table->row_stride;
-  a.zoff = table->z_offset;
-  a.rule = rule;
-  a.G = G;
-  a.nb = nb;
-  a.mom_lds = mom ? 1 : 0;
+  if (nb == 0)  // the per-sample launches of fmx_afm_step_opt(B = 1, inv_b = 1), queued
+    return afm_steps_run(table, hyper, rule, afm, AFM_POINTWISE, idx, xv, y, N, 1, 1.0f, N, workspace, w, attn_grad_out, opt, logit_out, 1,
+                         loss_out, error, st);
+  const AfmOnlArgs a = fill_afm_online(table, hyper, rule, afm, opt, idx, xv, y, N, attn_grad_out, logit_out, loss_out, error, nb, mom);
   return with_kp(table->kp, [&](auto KP) { return launch_afm_online_k<KP>(a, st); });
 }
 

@@ -573,6 +573,45 @@ struct AfmOnlArgs {
   int32_t o_rule, o_step;
   int32_t N, F, k, t, stride, zoff, rule, G, nb, mom_lds;
 };
+// ... filled for a stream of N units in the form afm_online_buffers gave (nb > 0 tile buffers, the moments in LDS or not); y:
+// null for the pairs.  ADAM: the kernel derives each unit's constants from lr, beta1, beta2, step of `hyper` and `opt`
+inline AfmOnlArgs fill_afm_online(const fmx_table_t *table, const fmx_hyper_t *hyper, int32_t rule, const fmx_afm_t *afm,
+                                  const fmx_mlp_opt_t *opt, const int32_t *idx, const float *xv, const float *y, int32_t N,
+                                  float *attn_grad_out, float *logit_out, float *loss_out, int32_t *error, int nb, bool moments_in_lds) {
+  AfmOnlArgs a;
+  memset(&a, 0, sizeof(a));
+  a.rows = table->rows;
+  a.foff = table->field_offsets;
+  a.bias = table->bias;
+  a.idx = idx;
+  a.xv = xv;
+  a.y = y;
+  a.params = afm->params;
+  a.m = opt->m;
+  a.v = opt->v;
+  a.grad = attn_grad_out;
+  a.logit = logit_out;
+  a.loss = loss_out;
+  a.error = error;
+  a.h = kernel_hyper(hyper, rule);
+  a.o_lr = opt->lr;
+  a.o_eps = opt->eps;
+  a.o_beta1 = opt->beta1;
+  a.o_beta2 = opt->beta2;
+  a.o_rule = opt->rule;
+  a.o_step = opt->step;
+  a.N = N;
+  a.F = table->n_fields;
+  a.k = afm->k;
+  a.t = afm->t;
+  a.stride = table->row_stride;
+  a.zoff = table->z_offset;
+  a.rule = rule;
+  a.G = afm->t * afm->k + 2 * afm->t + afm->k;
+  a.nb = nb;
+  a.mom_lds = moments_in_lds ? 1 : 0;
+  return a;
+}
 
 // the tables' rule is a workgroup-uniform run-time switch around the row helpers (a template parameter would multiply the five
 // kp instantiations by five for a few instructions per sample)

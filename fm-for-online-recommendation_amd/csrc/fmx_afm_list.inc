@@ -1,5 +1,6 @@
 // fmx_afm_list.inc -- listwise (sampled-softmax) training of the attentional FM: k_afm_list and the host code of fmx_afm_list_*
-// (included by fmx_afm.hip inside its unnamed namespace, behind fmx_afm_pair.inc, whose row helpers and step checks it shares).
+// (included by fmx_afm.hip inside its unnamed namespace, behind fmx_afm_pair.inc, whose row helpers it shares; the step's launches, the
+// queue of steps and the step checks the objectives share -- afm_step_launches, afm_steps_run, check_afm_unit_steps -- are fmx_afm.hip's).
 //
 // A batch of B_lists lists of G rows is idx [B_lists G, F] in fmx_fm_list_forward's layout: row G i the positive of list i, rows
 // G i + 1 .. G i + G - 1 its negatives.  With z_j the full AFM logit of row G i + j the loss is the softmax cross-entropy against
@@ -74,13 +75,8 @@ __global__ __launch_bounds__(64) void k_afm_list(AfmListArgs la) {
 template <int KP, bool FTRL, bool BWD>
 int launch_afm_list_k(const AfmListArgs &la, hipStream_t st) {
   const size_t lds = (size_t)(afm_lds(la.a.F, KP, la.a.t, BWD).total + LIST_MAX_G) * 4;
-  static std::once_flag once;
-  static hipError_t raised = hipSuccess;
-  std::call_once(once, [] {
-    raised = hipFuncSetAttribute(reinterpret_cast<const void *>(k_afm_list<KP, FTRL, BWD>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                 (int)((afm_lds(AFM_MAX_F, KP, AFM_MAX_T, BWD).total + LIST_MAX_G) * 4));
-  });
-  if (raised != hipSuccess) return fail(FMX_ERR_LAUNCH, "hipFuncSetAttribute(k_afm_list): %s", hipGetErrorString(raised));
+  if (int rc = raise_lds_limit<k_afm_list<KP, FTRL, BWD>>((int)((afm_lds(AFM_MAX_F, KP, AFM_MAX_T, BWD).total + LIST_MAX_G) * 4), "k_afm_list"))
+    return rc;
   hipLaunchKernelGGL((k_afm_list<KP, FTRL, BWD>), dim3(afm_grid(la.a.B)), dim3(64), lds, st, la);
   return check_launch("k_afm_list");
 }
@@ -113,11 +109,11 @@ int afm_list_forward_call(const fmx_table_t *table, const fmx_afm_t *afm, const 
   return launch_afm_list<false>(a, G, table->kp, table->layout == FMX_LAYOUT_FTRL, st);
 }
 
-// the step's workspace check: check_afm_pair_step's for B_lists G rows, with the bias scratch behind them
-int check_afm_list_step(const fmx_table_t *table, const fmx_hyper_t *hyper, int32_t rule, const fmx_afm_t *afm, int32_t rows, void *workspace,
-                        int64_t workspace_bytes, const float *attn_grad_out, const fmx_mlp_opt_t *opt, bool with_opt, int64_t n_steps,
-                        AfmWs &w, const char *who) {
-  if (int rc = check_afm_pair_step(table, hyper, rule, afm, rows, workspace, workspace_bytes, attn_grad_out, opt, with_opt, n_steps, w, who))
+// the list steps' refusals behind check_afm_list: check_afm_unit_steps' for steps of `rows` rows, then the bias scratch behind them
+int check_afm_list_steps(const fmx_table_t *table, const fmx_hyper_t *hyper, int32_t rule, const fmx_afm_t *afm, int32_t rows, void *workspace,
+                         int64_t workspace_bytes, const float *attn_grad_out, const fmx_mlp_opt_t *opt, bool with_opt, int64_t n_steps,
+                         AfmWs &w, const char *who) {
+  if (int rc = check_afm_unit_steps(table, hyper, rule, afm, rows, workspace, workspace_bytes, attn_grad_out, opt, with_opt, n_steps, w, who))
     return rc;
   if (workspace_bytes < w.bytes + LIST_BIAS_SCRATCH)
     return fail(FMX_ERR_SHAPE, "%s: workspace of %lld bytes, %lld needed: the step's and %lld bytes behind it (fmx_afm_list_workspace_bytes)", who,
@@ -125,8 +121,8 @@ int check_afm_list_step(const fmx_table_t *table, const fmx_hyper_t *hyper, int3
   return FMX_OK;
 }
 
-// fmx_afm_list_step (n_pool = n_steps = 1, no opt), fmx_afm_list_step_opt (the same with opt) and fmx_afm_list_stream: a plain
-// queue of list steps on `st`, as fmx_afm_pair_stream issues its steps
+// fmx_afm_list_step (n_pool = n_steps = 1, no opt; its logits kept), fmx_afm_list_step_opt (the same with opt) and
+// fmx_afm_list_stream: afm_steps_run's queue of list steps
 int afm_list_steps_call(const char *who, const fmx_table_t *table, const fmx_hyper_t *hyper, int32_t rule, const fmx_afm_t *afm,
                         const int32_t *idx_pool, const float *xv_pool, int32_t n_pool, int32_t B_lists, int32_t G, float inv_b,
                         int32_t n_steps, void *workspace, int64_t workspace_bytes, float *attn_grad_out, const fmx_mlp_opt_t *opt,
@@ -135,22 +131,14 @@ int afm_list_steps_call(const char *who, const fmx_table_t *table, const fmx_hyp
   if (int rc = check_afm_list(table, afm, hyper, idx_pool, B_lists, G, &rows, who)) return rc;
   if (n_pool < 1 || n_steps < 0) return fail(FMX_ERR_ARG, "%s: n_pool = %d must be >= 1 and n_steps = %d >= 0", who, n_pool, n_steps);
   AfmWs w;
-  if (int rc = check_afm_list_step(table, hyper, rule, afm, rows, workspace, workspace_bytes, attn_grad_out, opt, with_opt, n_steps, w, who))
+  if (int rc = check_afm_list_steps(table, hyper, rule, afm, rows, workspace, workspace_bytes, attn_grad_out, opt, with_opt, n_steps, w, who))
     return rc;
-  const size_t F = (size_t)table->n_fields;
-  for (int s = 0; s < n_steps; ++s) {
-    const fmx_hyper_t hs = hyper_at_step(hyper, rule, s);
-    const size_t j = (size_t)(s % n_pool);
-    if (int rc = afm_step_launches(table, &hs, rule, afm, idx_pool + j * rows * F, xv_pool ? xv_pool + j * rows * F : nullptr, nullptr, rows,
-                                   inv_b, workspace, w, attn_grad_out, loss_out ? loss_out + s : nullptr, error, with_opt ? opt : nullptr,
-                                   with_opt ? opt->step + s + 1 : 0, st, logit_out, -1.f, G))
-      return rc;
-  }
-  return FMX_OK;
+  return afm_steps_run(table, hyper, rule, afm, afm_lists(G), idx_pool, xv_pool, nullptr, n_pool, rows, inv_b, n_steps, workspace, w,
+                       attn_grad_out, with_opt ? opt : nullptr, logit_out, 0, loss_out, error, st);
 }
 
 // fmx_afm_list_online_run, the queued form: for every list, fmx_afm_list_step_opt(B_lists = 1, inv_b = 1) -- its own forward gives the
-// list's logits before its update -- without any host synchronisation
+// list's logits before its update -- as afm_steps_run's walk of the N lists
 int afm_list_online_call(const fmx_table_t *table, const fmx_hyper_t *hyper, int32_t rule, const fmx_afm_t *afm, const int32_t *idx,
                          const float *xv, int32_t N, int32_t G, void *workspace, int64_t workspace_bytes, float *attn_grad_out,
                          const fmx_mlp_opt_t *opt, float *logit_out, float *loss_out, int32_t *error, hipStream_t st) {
@@ -162,14 +150,7 @@ int afm_list_online_call(const fmx_table_t *table, const fmx_hyper_t *hyper, int
   int32_t rows = 0;
   if (int rc = check_afm_list(table, afm, hyper, idx, N, G, &rows, who)) return rc;
   AfmWs w;
-  if (int rc = check_afm_list_step(table, hyper, rule, afm, G, workspace, workspace_bytes, attn_grad_out, opt, true, N, w, who)) return rc;
-  const size_t F = (size_t)table->n_fields;
-  for (int i = 0; i < N; ++i) {
-    const fmx_hyper_t hs = hyper_at_step(hyper, rule, i);
-    if (int rc = afm_step_launches(table, &hs, rule, afm, idx + (size_t)i * G * F, xv ? xv + (size_t)i * G * F : nullptr, nullptr, G, 1.0f,
-                                   workspace, w, attn_grad_out, loss_out ? loss_out + i : nullptr, error, opt, opt->step + i + 1, st,
-                                   logit_out ? logit_out + (size_t)i * G : nullptr, -1.f, G))
-      return rc;
-  }
-  return FMX_OK;
+  if (int rc = check_afm_list_steps(table, hyper, rule, afm, G, workspace, workspace_bytes, attn_grad_out, opt, true, N, w, who)) return rc;
+  return afm_steps_run(table, hyper, rule, afm, afm_lists(G), idx, xv, nullptr, N, G, 1.0f, N, workspace, w, attn_grad_out, opt, logit_out, G,
+                       loss_out, error, st);
 }

@@ -1,5 +1,6 @@
 // fmx_afm_pair.inc -- pairwise-ranking (BPR) training of the attentional FM: k_afm_pair and the host code of fmx_afm_pair_*
-// (included by fmx_afm.hip inside its unnamed namespace, behind the host helpers it shares).
+// (included by fmx_afm.hip inside its unnamed namespace, behind the host code the objectives share: the step's launches under an
+// AfmObjective, afm_step_launches; the one queue of steps, afm_steps_run; the label-free step check, check_afm_unit_steps).
 //
 // A batch of B_pairs pairs is idx [2 B_pairs, F] in fmx_fm_pair_forward's layout: row 2 i the positive, row 2 i + 1 the negative.  With
 // d_i = z[2i] - z[2i + 1] over the full AFM logit the loss is -log(sigmoid(d_i) + margin) (pair_loss_dz, fmx_common.h; margin 0 is
@@ -166,13 +167,7 @@ __global__ __launch_bounds__(64) void k_afm_pair(AfmPairArgs pa) {
 template <int KP, bool FTRL, bool BWD>
 int launch_afm_pair_k(const AfmPairArgs &pa, hipStream_t st) {
   const size_t lds = (size_t)afm_lds(pa.a.F, KP, pa.a.t, BWD).total * 4;
-  static std::once_flag once;
-  static hipError_t raised = hipSuccess;
-  std::call_once(once, [] {
-    raised = hipFuncSetAttribute(reinterpret_cast<const void *>(k_afm_pair<KP, FTRL, BWD>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                 (int)(afm_lds(AFM_MAX_F, KP, AFM_MAX_T, BWD).total * 4));
-  });
-  if (raised != hipSuccess) return fail(FMX_ERR_LAUNCH, "hipFuncSetAttribute(k_afm_pair): %s", hipGetErrorString(raised));
+  if (int rc = raise_lds_limit<k_afm_pair<KP, FTRL, BWD>>((int)(afm_lds(AFM_MAX_F, KP, AFM_MAX_T, BWD).total * 4), "k_afm_pair")) return rc;
   hipLaunchKernelGGL((k_afm_pair<KP, FTRL, BWD>), dim3(afm_grid(pa.a.B)), dim3(64), lds, st, pa);
   return check_launch("k_afm_pair");
 }
@@ -206,21 +201,8 @@ int afm_pair_forward_call(const fmx_table_t *table, const fmx_afm_t *afm, const 
   return launch_afm_pair<false>(a, margin, table->kp, table->layout == FMX_LAYOUT_FTRL, st);
 }
 
-// the step's refusals beyond check_afm_pair, for a call of n_steps steps of n_rows rows: the workspace and the rule
-// (check_afm_ws), then the attention rule's state (check_afm_opt) or, without one, what it decides for the tables (ADAM's
-// hyper-parameters, the sort's geometry)
-int check_afm_pair_step(const fmx_table_t *table, const fmx_hyper_t *hyper, int32_t rule, const fmx_afm_t *afm, int32_t n_rows,
-                        void *workspace, int64_t workspace_bytes, const float *attn_grad_out, const fmx_mlp_opt_t *opt, bool with_opt,
-                        int64_t n_steps, AfmWs &w, const char *who) {
-  if (!workspace || !attn_grad_out) return fail(FMX_ERR_ARG, "%s: null argument", who);
-  if (int rc = check_afm_ws(table, rule, afm, n_rows, workspace, workspace_bytes, w, who)) return rc;
-  if (with_opt) return check_afm_opt(table, hyper, rule, afm, n_rows, opt, n_steps, who);
-  if (int rc = named(check_adam(hyper, rule, n_steps), who)) return rc;
-  return named(check_sort_geometry(table, n_rows), who);
-}
-
-// fmx_afm_pair_step (n_pool = n_steps = 1, no opt), fmx_afm_pair_step_opt (the same with opt) and fmx_afm_pair_stream: a plain
-// queue of pair steps on `st`, as fmx_afm_stream issues its steps
+// fmx_afm_pair_step (n_pool = n_steps = 1, no opt; its logits kept), fmx_afm_pair_step_opt (the same with opt) and
+// fmx_afm_pair_stream: afm_steps_run's queue of pair steps
 int afm_pair_steps_call(const char *who, const fmx_table_t *table, const fmx_hyper_t *hyper, int32_t rule, const fmx_afm_t *afm,
                         const int32_t *idx_pool, const float *xv_pool, int32_t n_pool, int32_t B_pairs, float margin, float inv_b,
                         int32_t n_steps, void *workspace, int64_t workspace_bytes, float *attn_grad_out, const fmx_mlp_opt_t *opt,
@@ -229,23 +211,15 @@ int afm_pair_steps_call(const char *who, const fmx_table_t *table, const fmx_hyp
   if (n_pool < 1 || n_steps < 0) return fail(FMX_ERR_ARG, "%s: n_pool = %d must be >= 1 and n_steps = %d >= 0", who, n_pool, n_steps);
   const int32_t B2 = 2 * B_pairs;
   AfmWs w;
-  if (int rc = check_afm_pair_step(table, hyper, rule, afm, B2, workspace, workspace_bytes, attn_grad_out, opt, with_opt, n_steps, w, who))
+  if (int rc = check_afm_unit_steps(table, hyper, rule, afm, B2, workspace, workspace_bytes, attn_grad_out, opt, with_opt, n_steps, w, who))
     return rc;
-  const size_t F = (size_t)table->n_fields;
-  for (int s = 0; s < n_steps; ++s) {
-    const fmx_hyper_t hs = hyper_at_step(hyper, rule, s);
-    const size_t j = (size_t)(s % n_pool);
-    if (int rc = afm_step_launches(table, &hs, rule, afm, idx_pool + j * B2 * F, xv_pool ? xv_pool + j * B2 * F : nullptr, nullptr, B2,
-                                   inv_b, workspace, w, attn_grad_out, loss_out ? loss_out + s : nullptr, error, with_opt ? opt : nullptr,
-                                   with_opt ? opt->step + s + 1 : 0, st, logit_out, margin))
-      return rc;
-  }
-  return FMX_OK;
+  return afm_steps_run(table, hyper, rule, afm, afm_pairs(margin), idx_pool, xv_pool, nullptr, n_pool, B2, inv_b, n_steps, workspace, w,
+                       attn_grad_out, with_opt ? opt : nullptr, logit_out, 0, loss_out, error, st);
 }
 
 // fmx_afm_pair_online_run.  Two forms, the same bits: k_afm_pair_online (fmx_afm_pair_online.hip), one workgroup walking the
 // stream, where afm_pair_online_buffers gives it tile buffers; otherwise, for every pair, fmx_afm_pair_step_opt(B_pairs = 1,
-// inv_b = 1) -- its own forward gives the pair's logits before its update -- queued without any host synchronisation (the form
+// inv_b = 1) -- its own forward gives the pair's logits before its update -- as afm_steps_run's walk of the N pairs (the form
 // fmx_afm_online_run falls back to)
 int afm_pair_online_call(const fmx_table_t *table, const fmx_hyper_t *hyper, int32_t rule, const fmx_afm_t *afm, const int32_t *idx,
                          const float *xv, int32_t N_pairs, float margin, void *workspace, int64_t workspace_bytes, float *attn_grad_out,
@@ -254,20 +228,13 @@ int afm_pair_online_call(const fmx_table_t *table, const fmx_hyper_t *hyper, int
   if (int rc = check_afm_pair(table, afm, hyper, idx, N_pairs > 0 ? N_pairs : 1, "N_pairs", margin, who)) return rc;
   if (N_pairs < 0) return fail(FMX_ERR_ARG, "%s: N_pairs = %d must be >= 0", who, N_pairs);
   AfmWs w;
-  if (int rc = check_afm_pair_step(table, hyper, rule, afm, 2, workspace, workspace_bytes, attn_grad_out, opt, true, N_pairs, w, who)) return rc;
+  if (int rc = check_afm_unit_steps(table, hyper, rule, afm, 2, workspace, workspace_bytes, attn_grad_out, opt, true, N_pairs, w, who)) return rc;
   if (N_pairs == 0) return FMX_OK;
   bool mom = false;
   if (const int nb = afm_pair_online_buffers(table->n_fields, afm->k, table->kp, afm->t, opt->rule, &mom))
     return afm_pair_online_launch(table, hyper, rule, afm, idx, xv, N_pairs, margin, attn_grad_out, opt, logit_out, loss_out, error, nb, mom, st);
-  const size_t F = (size_t)table->n_fields;
-  for (int i = 0; i < N_pairs; ++i) {
-    const fmx_hyper_t hs = hyper_at_step(hyper, rule, i);
-    if (int rc = afm_step_launches(table, &hs, rule, afm, idx + (size_t)i * 2 * F, xv ? xv + (size_t)i * 2 * F : nullptr, nullptr, 2, 1.0f,
-                                   workspace, w, attn_grad_out, loss_out ? loss_out + i : nullptr, error, opt, opt->step + i + 1, st,
-                                   logit_out ? logit_out + (size_t)i * 2 : nullptr, margin))
-      return rc;
-  }
-  return FMX_OK;
+  return afm_steps_run(table, hyper, rule, afm, afm_pairs(margin), idx, xv, nullptr, N_pairs, 2, 1.0f, N_pairs, workspace, w, attn_grad_out,
+                       opt, logit_out, 2, loss_out, error, st);
 }
 
 // fmx_afm_pair_online_form: which of the two forms fmx_afm_pair_online_run takes at this shape -- the structs are read, nothing
@@ -275,9 +242,7 @@ int afm_pair_online_call(const fmx_table_t *table, const fmx_hyper_t *hyper, int
 int afm_pair_online_form_call(const fmx_table_t *table, const fmx_afm_t *afm, int32_t attn_rule, int32_t *moments_in_lds) {
   const char *who = "fmx_afm_pair_online_form";
   if (int rc = check_afm(table, afm, who)) return rc;
-  if (attn_rule != FMX_RULE_SIGNADAM && attn_rule != FMX_RULE_SGD && attn_rule != FMX_RULE_ADAGRAD && attn_rule != FMX_RULE_ADAM)
-    return fail(FMX_ERR_ARG, "%s: the attention rule %d is not FMX_RULE_SIGNADAM, FMX_RULE_SGD, FMX_RULE_ADAGRAD or FMX_RULE_ADAM", who,
-                attn_rule);
+  if (int rc = check_attn_rule(attn_rule, who)) return rc;
   bool mom = false;
   const int nb = afm_pair_online_buffers(table->n_fields, afm->k, table->kp, afm->t, attn_rule, &mom);
   if (moments_in_lds) *moments_in_lds = mom ? 1 : 0;

@@ -1,6 +1,7 @@
 // fmx_afm_pair_online.hip -- k_afm_pair_online: the attentional FM's online PAIR loop (predict z_pos > z_neg, then fit on that pair)
 // in one workgroup (fmx_afm_pair_online_run; the host code that decides between this kernel and the queued pair steps is
-// afm_pair_online_call in fmx_afm_pair.inc).
+// afm_pair_online_call in fmx_afm_pair.inc).  The launch takes k_afm_online's arguments, filled by the same fill_afm_online
+// (fmx_afm_device.inc) with y null, and the margin beside them.
 //
 // A unit of its own, built from fmx_afm_device.inc: the kernel calls the device functions of k_afm / k_afm_online (stage_params,
 // score_pairs, pair_backward, add_tile, ...) and restates none of their arithmetic.  Compiled inside fmx_afm.hip, where it shares those
@@ -329,13 +330,7 @@ template <int KP>
 int launch_afm_pair_online_k(const AfmPairOnlArgs &pa, hipStream_t st) {
   const AfmOnlArgs &a = pa.o;
   const size_t lds = (size_t)afm_online_lds(a.F, KP, a.t, a.G, a.nb, a.mom_lds != 0).total * 4;
-  static std::once_flag once;
-  static hipError_t raised = hipSuccess;
-  std::call_once(once, [] {
-    raised = hipFuncSetAttribute(reinterpret_cast<const void *>(k_afm_pair_online<KP>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                 AFM_LDS_BYTES);
-  });
-  if (raised != hipSuccess) return fail(FMX_ERR_LAUNCH, "hipFuncSetAttribute(k_afm_pair_online): %s", hipGetErrorString(raised));
+  if (int rc = raise_lds_limit<k_afm_pair_online<KP>>(AFM_LDS_BYTES, "k_afm_pair_online")) return rc;
   hipLaunchKernelGGL((k_afm_pair_online<KP>), dim3(1), dim3(AFM_ONL_THREADS), lds, st, pa);
   return check_launch("k_afm_pair_online");
 }
@@ -358,36 +353,7 @@ int afm_pair_online_launch(const fmx_table_t *table, const fmx_hyper_t *hyper, i
                            float *logit_out, float *loss_out, int32_t *error, int nb, bool moments_in_lds, hipStream_t st) {
   AfmPairOnlArgs pa;
   memset(&pa, 0, sizeof(pa));
-  AfmOnlArgs &a = pa.o;
-  a.rows = table->rows;
-  a.foff = table->field_offsets;
-  a.bias = table->bias;
-  a.idx = idx;
-  a.xv = xv;
-  a.params = afm->params;
-  a.m = opt->m;
-  a.v = opt->v;
-  a.grad = attn_grad_out;
-  a.logit = logit_out;
-  a.loss = loss_out;
-  a.error = error;
-  a.h = kernel_hyper(hyper, rule);  // ADAM: the kernel derives each pair's constants from lr, beta1, beta2, step
-  a.o_lr = opt->lr;
-  a.o_eps = opt->eps;
-  a.o_beta1 = opt->beta1;
-  a.o_beta2 = opt->beta2;
-  a.o_rule = opt->rule;
-  a.o_step = opt->step;
-  a.N = N_pairs;
-  a.F = table->n_fields;
-  a.k = afm->k;
-  a.t = afm->t;
-  a.stride = table->row_stride;
-  a.zoff = table->z_offset;
-  a.rule = rule;
-  a.G = afm->t * afm->k + 2 * afm->t + afm->k;
-  a.nb = nb;
-  a.mom_lds = moments_in_lds ? 1 : 0;
+  pa.o = fill_afm_online(table, hyper, rule, afm, opt, idx, xv, nullptr, N_pairs, attn_grad_out, logit_out, loss_out, error, nb, moments_in_lds);
   pa.margin = margin;
   return with_kp(table->kp, [&](auto KP) { return launch_afm_pair_online_k<KP>(pa, st); });
 }

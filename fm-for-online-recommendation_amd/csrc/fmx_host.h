@@ -212,6 +212,19 @@ inline fmx_hyper_t kernel_hyper(const fmx_hyper_t *h, int rule) {
   return r;
 }
 
+// Raise kernel K's dynamic-LDS limit to `bytes` ONCE per process (K is one instantiation: its own flag), and report a failure
+// of that one attempt on every call, under the kernel's name: FMX_OK, or FMX_ERR_LAUNCH "hipFuncSetAttribute(<name>): ..."
+template <auto K>
+int raise_lds_limit(int bytes, const char *name) {
+  static std::once_flag once;
+  static hipError_t raised = hipSuccess;
+  std::call_once(once, [bytes] {
+    raised = hipFuncSetAttribute(reinterpret_cast<const void *>(K), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+  });
+  if (raised != hipSuccess) return fail(FMX_ERR_LAUNCH, "hipFuncSetAttribute(%s): %s", name, hipGetErrorString(raised));
+  return FMX_OK;
+}
+
 constexpr int SORT_AHEAD_MAX = 16;  // batches sorted per side-stream launch in fmx_fm_stream (r3: 16, was 8 -- every group boundary puts a
                                     // cross-stream wait of 5 - 6 us on the step's stream: 21.33 - 21.39 against 21.53 - 21.79 us per step)
 

@@ -76,20 +76,37 @@ class AFMEngine:
                                             self._stream(stream)))
         return B
 
+    # ---- the nine training calls: step / stream / online_run under BCE on y, their pair_ forms and their list_ forms ----
+    def _check(self, idx, xv, rows, y=None, outs=()):
+        """The validation behind the nine: idx int32, contiguous, `rows` rows of F indices (a pool: the rows of all its batches);
+        xv None or fp32, contiguous, an element per index; y None or fp32, an element per row; outs: (tensor or None, the
+        elements it must hold) for every fp32 output the call fills."""
+        assert idx.dtype == torch.int32 and idx.is_contiguous() and idx.numel() == rows * self.table.n_fields
+        assert xv is None or (xv.dtype == torch.float32 and xv.is_contiguous() and xv.numel() == idx.numel())
+        assert y is None or (y.dtype == torch.float32 and y.numel() == rows)
+        for out, n in outs:
+            assert out is None or (out.dtype == torch.float32 and out.is_contiguous() and out.numel() >= n)
+
+    def _call(self, kind, form, hyper, rule, idx, xv, y, dims, outs, opt, n=1, stream=None):
+        """One checked call of fmx_afm_<kind><form> that takes n steps -- for a step given an AfmOpt, its _opt form.  kind: ""
+        (BCE: y is passed), "pair_" or "list_" (the list steps' own workspace, self._list_ws).  dims: the call's counts and
+        scalars between the inputs and the workspace; outs: its output pointers behind the attention gradient (and opt)."""
+        name = f"fmx_afm_{kind}{form}" + ("_opt" if form == "step" and opt is not None else "")
+        ws = self._list_ws if kind == "list_" else self.workspace
+        args = (self.table.c_struct(), hyper.ref(), _lib.RULES[rule], C.byref(self.c_afm), idx.data_ptr(), _ptr(xv),
+                *(() if kind else (y.data_ptr(),)), *dims, ws.data_ptr(), ws.numel() * 4, self.grad.data_ptr(),
+                *(() if opt is None else (opt.ref(),)), *outs, self.error.data_ptr(), self._stream(stream))
+        self._counted(getattr(self.lib, name), args, hyper, n, opt)
+
     def step(self, hyper, rule, idx_d, xv_d, y_d, inv_b=None, stream=None, opt=None):
         """One mini-batch step: the table updated under `rule`, the mean loss in self.loss_out[0], the attention gradient in
         self.grad (no sync here).  opt (an AfmOpt): the attention parameters take its rule in the same call (fmx_afm_step_opt)
         and its step count advances; None leaves them to the caller."""
         B = idx_d.shape[0]
+        self._check(idx_d, xv_d, B, y_d)
         self._ensure(B)
-        head = (self.table.c_struct(), hyper.ref(), _lib.RULES[rule], C.byref(self.c_afm), idx_d.data_ptr(), _ptr(xv_d),
-                y_d.data_ptr(), B, 1.0 / B if inv_b is None else inv_b, self.workspace.data_ptr(), self.workspace.numel() * 4,
-                self.grad.data_ptr())
-        tail = (self.loss_out.data_ptr(), self.error.data_ptr(), self._stream(stream))
-        if opt is None:
-            self._counted(self.lib.fmx_afm_step, (*head, *tail), hyper)
-        else:
-            self._counted(self.lib.fmx_afm_step_opt, (*head, opt.ref(), *tail), hyper, 1, opt)
+        self._call("", "step", hyper, rule, idx_d, xv_d, y_d, (B, 1.0 / B if inv_b is None else inv_b), (self.loss_out.data_ptr(),),
+                   opt, 1, stream)
 
     def stream(self, hyper, rule, idx_pool, xv_pool, y_pool, B, n_steps, opt, inv_b=None, losses=None, stream=None):
         """n_steps steps over a device-resident pool in one call (fmx_afm_stream; no sync here): idx_pool [n_pool, B, F] int32,
@@ -98,15 +115,11 @@ class AFMEngine:
         n_steps; self.grad holds the last step's attention gradient."""
         B, n_steps = int(B), int(n_steps)
         n_pool = idx_pool.numel() // (B * self.table.n_fields)
-        assert idx_pool.dtype == torch.int32 and idx_pool.is_contiguous() and n_pool >= 1 and y_pool.numel() == n_pool * B
-        assert xv_pool is None or (xv_pool.dtype == torch.float32 and xv_pool.is_contiguous() and xv_pool.numel() == idx_pool.numel())
-        assert losses is None or (losses.dtype == torch.float32 and losses.numel() >= n_steps)
+        assert n_pool >= 1
+        self._check(idx_pool, xv_pool, n_pool * B, y_pool, ((losses, n_steps),))
         self._ensure(B)
-        self._counted(self.lib.fmx_afm_stream, (self.table.c_struct(), hyper.ref(), _lib.RULES[rule], C.byref(self.c_afm),
-                                                idx_pool.data_ptr(), _ptr(xv_pool), y_pool.data_ptr(), n_pool, B,
-                                                1.0 / B if inv_b is None else inv_b, n_steps, self.workspace.data_ptr(),
-                                                self.workspace.numel() * 4, self.grad.data_ptr(), opt.ref(), _ptr(losses),
-                                                self.error.data_ptr(), self._stream(stream)), hyper, n_steps, opt)
+        self._call("", "stream", hyper, rule, idx_pool, xv_pool, y_pool, (n_pool, B, 1.0 / B if inv_b is None else inv_b, n_steps),
+                   (_ptr(losses),), opt, n_steps, stream)
 
     def online_run(self, hyper, rule, idx_d, xv_d, y_d, opt, logits=None, losses=None, stream=None):
         """The online predict-then-fit loop over a device-resident stream in one call (fmx_afm_online_run; no sync here): idx_d
@@ -115,29 +128,20 @@ class AFMEngine:
         and its loss, or None.  The table's step count and opt's advance by N; self.grad holds the last sample's attention
         gradient."""
         N = int(idx_d.shape[0])
-        assert idx_d.dtype == torch.int32 and idx_d.is_contiguous() and idx_d.numel() == N * self.table.n_fields
-        assert y_d.dtype == torch.float32 and y_d.numel() == N
-        assert xv_d is None or (xv_d.dtype == torch.float32 and xv_d.is_contiguous() and xv_d.numel() == idx_d.numel())
-        for out in (logits, losses):
-            assert out is None or (out.dtype == torch.float32 and out.is_contiguous() and out.numel() >= N)
+        self._check(idx_d, xv_d, N, y_d, ((logits, N), (losses, N)))
         self._ensure(1)
-        self._counted(self.lib.fmx_afm_online_run, (self.table.c_struct(), hyper.ref(), _lib.RULES[rule], C.byref(self.c_afm),
-                                                    idx_d.data_ptr(), _ptr(xv_d), y_d.data_ptr(), N, self.workspace.data_ptr(),
-                                                    self.workspace.numel() * 4, self.grad.data_ptr(), opt.ref(), _ptr(logits),
-                                                    _ptr(losses), self.error.data_ptr(), self._stream(stream)), hyper, N, opt)
+        self._call("", "online_run", hyper, rule, idx_d, xv_d, y_d, (N,), (_ptr(logits), _ptr(losses)), opt, N, stream)
 
     # ---- pairwise-ranking (BPR) training: rows [2P, F] from fmx.pairwise.assemble_pairs, row 2p the positive, 2p + 1 the negative ----
-    def _pair_rows(self, idx_d, xv_d):
+    def _pair_rows(self, idx_d, xv_d, outs=lambda P: ()):
         P = n_pairs(idx_d)
-        assert idx_d.dtype == torch.int32 and idx_d.is_contiguous() and idx_d.shape[1] == self.table.n_fields
-        assert xv_d is None or (xv_d.dtype == torch.float32 and xv_d.is_contiguous() and xv_d.shape == idx_d.shape)
+        self._check(idx_d, xv_d, 2 * P, outs=outs(P))
         return P
 
     def pair_forward(self, hyper, idx_d, xv_d=None, margin=0.0, inv_b=None, dz=None, stream=None):
         """-> P; the 2P logits in self.logit[:2P] (the bits of forward()), the pair losses in self.loss_b[0:2P:2] (the odd slots
         +0).  dz: an fp32 device tensor of 2P elements for dlogit (inv_b folded in, default 1 / P), or None."""
-        P = self._pair_rows(idx_d, xv_d)
-        assert dz is None or (dz.dtype == torch.float32 and dz.is_contiguous() and dz.numel() >= 2 * P)
+        P = self._pair_rows(idx_d, xv_d, lambda P: ((dz, 2 * P),))
         self._ensure(2 * P)
         _lib.check(self.lib.fmx_afm_pair_forward(self.table.c_struct(), C.byref(self.c_afm), hyper.ref(), idx_d.data_ptr(), _ptr(xv_d),
                                                  P, margin, 1.0 / P if inv_b is None else inv_b, self.logit.data_ptr(),
@@ -150,13 +154,8 @@ class AFMEngine:
         attention parameters take its rule in the same call (fmx_afm_pair_step_opt) and its step count advances."""
         P = self._pair_rows(idx_d, xv_d)
         self._ensure(2 * P)
-        head = (self.table.c_struct(), hyper.ref(), _lib.RULES[rule], C.byref(self.c_afm), idx_d.data_ptr(), _ptr(xv_d), P, margin,
-                1.0 / P if inv_b is None else inv_b, self.workspace.data_ptr(), self.workspace.numel() * 4, self.grad.data_ptr())
-        tail = (self.logit.data_ptr(), self.loss_out.data_ptr(), self.error.data_ptr(), self._stream(stream))
-        if opt is None:
-            self._counted(self.lib.fmx_afm_pair_step, (*head, *tail), hyper)
-        else:
-            self._counted(self.lib.fmx_afm_pair_step_opt, (*head, opt.ref(), *tail), hyper, 1, opt)
+        self._call("pair_", "step", hyper, rule, idx_d, xv_d, None, (P, margin, 1.0 / P if inv_b is None else inv_b),
+                   (self.logit.data_ptr(), self.loss_out.data_ptr()), opt, 1, stream)
 
     def pair_stream(self, hyper, rule, idx_pool, xv_pool, P, n_steps, opt, margin=0.0, inv_b=None, losses=None, stream=None):
         """n_steps pair steps over a device-resident pool in one call (fmx_afm_pair_stream; no sync here): idx_pool
@@ -164,42 +163,33 @@ class AFMEngine:
         device tensor of n_steps elements, or None.  The table's step count and opt's advance by n_steps."""
         P, n_steps = int(P), int(n_steps)
         n_pool = idx_pool.numel() // (2 * P * self.table.n_fields)
-        assert idx_pool.dtype == torch.int32 and idx_pool.is_contiguous() and n_pool >= 1
-        assert xv_pool is None or (xv_pool.dtype == torch.float32 and xv_pool.is_contiguous() and xv_pool.numel() == idx_pool.numel())
-        assert losses is None or (losses.dtype == torch.float32 and losses.numel() >= n_steps)
+        assert n_pool >= 1
+        self._check(idx_pool, xv_pool, n_pool * 2 * P, outs=((losses, n_steps),))
         self._ensure(2 * P)
-        self._counted(self.lib.fmx_afm_pair_stream, (self.table.c_struct(), hyper.ref(), _lib.RULES[rule], C.byref(self.c_afm),
-                                                     idx_pool.data_ptr(), _ptr(xv_pool), n_pool, P, margin,
-                                                     1.0 / P if inv_b is None else inv_b, n_steps, self.workspace.data_ptr(),
-                                                     self.workspace.numel() * 4, self.grad.data_ptr(), opt.ref(), _ptr(losses),
-                                                     self.error.data_ptr(), self._stream(stream)), hyper, n_steps, opt)
+        self._call("pair_", "stream", hyper, rule, idx_pool, xv_pool, None,
+                   (n_pool, P, margin, 1.0 / P if inv_b is None else inv_b, n_steps), (_ptr(losses),), opt, n_steps, stream)
 
     def pair_online_run(self, hyper, rule, idx_d, xv_d, opt, margin=0.0, logits=None, losses=None, stream=None):
         """The online protocol for pairs in one call (fmx_afm_pair_online_run; no sync here): every pair of idx_d [2N, F] is
         predicted, then fitted on alone -- N steps of pair_step(P = 1, inv_b = 1).  logits: an fp32 device tensor of 2N elements
         for each pair's two logits BEFORE its update; losses: N elements; or None.  The table's step count and opt's advance
         by N."""
-        N = self._pair_rows(idx_d, xv_d)
-        assert logits is None or (logits.dtype == torch.float32 and logits.is_contiguous() and logits.numel() >= 2 * N)
-        assert losses is None or (losses.dtype == torch.float32 and losses.is_contiguous() and losses.numel() >= N)
+        N = self._pair_rows(idx_d, xv_d, lambda N: ((logits, 2 * N), (losses, N)))
         self._ensure(2)
-        self._counted(self.lib.fmx_afm_pair_online_run, (self.table.c_struct(), hyper.ref(), _lib.RULES[rule], C.byref(self.c_afm),
-                                                         idx_d.data_ptr(), _ptr(xv_d), N, margin, self.workspace.data_ptr(),
-                                                         self.workspace.numel() * 4, self.grad.data_ptr(), opt.ref(), _ptr(logits),
-                                                         _ptr(losses), self.error.data_ptr(), self._stream(stream)), hyper, N, opt)
+        self._call("pair_", "online_run", hyper, rule, idx_d, xv_d, None, (N, margin), (_ptr(logits), _ptr(losses)), opt, N, stream)
 
     # ---- listwise (sampled-softmax) training: rows [B G, F] from fmx.pairwise.assemble_lists, row G i the positive of list i ----
-    def _list_rows(self, idx_d, xv_d, G, ws_lists=None):
+    def _list_rows(self, idx_d, xv_d, G, ws_lists=None, outs=lambda B: ()):
         """-> B for the rows [B G, F] of B lists; grows the buffers, and keeps the list steps' own workspace, self._list_ws, sized
         through fmx_afm_list_workspace_bytes for ws_lists lists (default B): the AFM step's workspace and the scratch behind it
-        that the bias rule of a list step runs on."""
+        that the bias rule of a list step runs on.  outs(B): the outputs _check looks at."""
         G = _list_G(G)
-        assert idx_d.dtype == torch.int32 and idx_d.is_contiguous() and idx_d.dim() == 2 and idx_d.shape[1] == self.table.n_fields
-        assert xv_d is None or (xv_d.dtype == torch.float32 and xv_d.is_contiguous() and xv_d.shape == idx_d.shape)
+        assert idx_d.dim() == 2
         rows = idx_d.shape[0]
         if rows < G or rows % G:
             raise ValueError(f"list rows must be [B G, F] with B >= 1 and G = {G}, got {rows} rows")
         B = rows // G
+        self._check(idx_d, xv_d, rows, outs=outs(B))
         n = B if ws_lists is None else int(ws_lists)
         self._ensure(n * G)
         need = int(self.lib.fmx_afm_list_workspace_bytes(self.table.c_struct(), C.byref(self.c_afm), n, G))
@@ -213,8 +203,7 @@ class AFMEngine:
     def list_forward(self, hyper, idx_d, G, xv_d=None, inv_b=None, dz=None, stream=None):
         """-> B; the B G logits in self.logit[:B G] (the bits of forward()), the list losses in self.loss_b[0:B G:G] (the
         negatives' slots +0).  dz: an fp32 device tensor of B G elements for dlogit (inv_b folded in, default 1 / B), or None."""
-        B = self._list_rows(idx_d, xv_d, G)
-        assert dz is None or (dz.dtype == torch.float32 and dz.is_contiguous() and dz.numel() >= B * G)
+        B = self._list_rows(idx_d, xv_d, G, outs=lambda B: ((dz, B * int(G)),))
         _lib.check(self.lib.fmx_afm_list_forward(self.table.c_struct(), C.byref(self.c_afm), hyper.ref(), idx_d.data_ptr(), _ptr(xv_d),
                                                  B, int(G), 1.0 / B if inv_b is None else inv_b, self.logit.data_ptr(),
                                                  self.loss_b.data_ptr(), _ptr(dz), self.error.data_ptr(), self._stream(stream)))
@@ -225,13 +214,8 @@ class AFMEngine:
         the attention gradient in self.grad, the B G logits before the update in self.logit[:B G] (no sync here).  opt (an
         AfmOpt): the attention parameters take its rule in the same call (fmx_afm_list_step_opt) and its step count advances."""
         B = self._list_rows(idx_d, xv_d, G)
-        head = (self.table.c_struct(), hyper.ref(), _lib.RULES[rule], C.byref(self.c_afm), idx_d.data_ptr(), _ptr(xv_d), B, int(G),
-                1.0 / B if inv_b is None else inv_b, self._list_ws.data_ptr(), self._list_ws.numel() * 4, self.grad.data_ptr())
-        tail = (self.logit.data_ptr(), self.loss_out.data_ptr(), self.error.data_ptr(), self._stream(stream))
-        if opt is None:
-            self._counted(self.lib.fmx_afm_list_step, (*head, *tail), hyper)
-        else:
-            self._counted(self.lib.fmx_afm_list_step_opt, (*head, opt.ref(), *tail), hyper, 1, opt)
+        self._call("list_", "step", hyper, rule, idx_d, xv_d, None, (B, int(G), 1.0 / B if inv_b is None else inv_b),
+                   (self.logit.data_ptr(), self.loss_out.data_ptr()), opt, 1, stream)
 
     def list_stream(self, hyper, rule, idx_pool, xv_pool, B, G, n_steps, opt, inv_b=None, losses=None, stream=None):
         """n_steps list steps over a device-resident pool in one call (fmx_afm_list_stream; no sync here): idx_pool
@@ -239,29 +223,19 @@ class AFMEngine:
         device tensor of n_steps elements, or None.  The table's step count and opt's advance by n_steps."""
         B, G, n_steps = int(B), _list_G(G), int(n_steps)
         n_pool = idx_pool.numel() // (B * G * self.table.n_fields)
-        assert n_pool >= 1 and idx_pool.numel() == n_pool * B * G * self.table.n_fields
-        assert xv_pool is None or (xv_pool.dtype == torch.float32 and xv_pool.is_contiguous() and xv_pool.numel() == idx_pool.numel())
-        assert losses is None or (losses.dtype == torch.float32 and losses.numel() >= n_steps)
-        first = idx_pool.reshape(n_pool, B * G, self.table.n_fields)[0]
-        self._list_rows(first, None, G)
-        self._counted(self.lib.fmx_afm_list_stream, (self.table.c_struct(), hyper.ref(), _lib.RULES[rule], C.byref(self.c_afm),
-                                                     idx_pool.data_ptr(), _ptr(xv_pool), n_pool, B, G,
-                                                     1.0 / B if inv_b is None else inv_b, n_steps, self._list_ws.data_ptr(),
-                                                     self._list_ws.numel() * 4, self.grad.data_ptr(), opt.ref(), _ptr(losses),
-                                                     self.error.data_ptr(), self._stream(stream)), hyper, n_steps, opt)
+        assert n_pool >= 1
+        self._check(idx_pool, xv_pool, n_pool * B * G, outs=((losses, n_steps),))
+        self._list_rows(idx_pool.reshape(n_pool, B * G, self.table.n_fields)[0], None, G)
+        self._call("list_", "stream", hyper, rule, idx_pool, xv_pool, None, (n_pool, B, G, 1.0 / B if inv_b is None else inv_b, n_steps),
+                   (_ptr(losses),), opt, n_steps, stream)
 
     def list_online_run(self, hyper, rule, idx_d, G, xv_d, opt, logits=None, losses=None, stream=None):
         """The online protocol for lists in one call (fmx_afm_list_online_run; no sync here): every list of idx_d [N G, F] is
         predicted, then fitted on alone -- N steps of list_step(B = 1, inv_b = 1), queued.  logits: an fp32 device tensor of N G
         elements for each list's logits BEFORE its update; losses: N elements; or None.  The table's step count and opt's
         advance by N."""
-        N = self._list_rows(idx_d, xv_d, G, ws_lists=1)
-        assert logits is None or (logits.dtype == torch.float32 and logits.is_contiguous() and logits.numel() >= N * G)
-        assert losses is None or (losses.dtype == torch.float32 and losses.is_contiguous() and losses.numel() >= N)
-        self._counted(self.lib.fmx_afm_list_online_run, (self.table.c_struct(), hyper.ref(), _lib.RULES[rule], C.byref(self.c_afm),
-                                                         idx_d.data_ptr(), _ptr(xv_d), N, int(G), self._list_ws.data_ptr(),
-                                                         self._list_ws.numel() * 4, self.grad.data_ptr(), opt.ref(), _ptr(logits),
-                                                         _ptr(losses), self.error.data_ptr(), self._stream(stream)), hyper, N, opt)
+        N = self._list_rows(idx_d, xv_d, G, 1, lambda N: ((logits, N * int(G)), (losses, N)))
+        self._call("list_", "online_run", hyper, rule, idx_d, xv_d, None, (N, int(G)), (_ptr(logits), _ptr(losses)), opt, N, stream)
 
     def pair_online_form(self, attn_rule):
         """-> (tile buffers, moments in LDS) of the form pair_online_run takes for this table under the attention rule

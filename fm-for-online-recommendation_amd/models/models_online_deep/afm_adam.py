@@ -214,19 +214,23 @@ class AFMAdam(RankingTraining, nn.Module):
             else:
                 self._attn_flat.sub_(lr * g / (g.abs() + 1e-8))
 
+    def _fit_step(self, engine_step, *args, **kwargs):
+        """One step of the whole model through engine_step (AFMEngine.step / pair_step / list_step) under the model's rule; with
+        fused_optimizer=False the attention parameters' rule follows on torch.  Returns the step's mean loss."""
+        engine_step(self._hyper, self.update_rule, *args, opt=self._attn_fused, **kwargs)
+        if self._attn_fused is None:
+            self._apply_attention(self._engine.grad)
+        out = self._engine.loss_out[0].clone()
+        self._after_step()
+        return out
+
     def update_embedding(self, Xi, Xv, Y):
         """One mini-batch step of the whole model (tables and attention) on BCE-with-logits; returns the mean loss."""
         self.train()
         idx_d, xv_d, y_d = self._inputs(Xi, Xv, Y)
         if y_d.numel() != idx_d.shape[0]:
             raise ValueError(f"Target size ({y_d.numel()}) must be the same as input size ({idx_d.shape[0]})")
-        e = self._engine
-        e.step(self._hyper, self.update_rule, idx_d, xv_d, y_d, opt=self._attn_fused)
-        if self._attn_fused is None:
-            self._apply_attention(e.grad)
-        out = e.loss_out[0].clone()
-        self._after_step()
-        return out
+        return self._fit_step(self._engine.step, idx_d, xv_d, y_d)
 
     # ---- pairwise-ranking (BPR) training on the attentional logit (fmx_afm_pair_*; the pair objective of the other classes) ----
     def _pair_refusal(self, method, attention, loss="pair"):
@@ -244,13 +248,7 @@ class AFMAdam(RankingTraining, nn.Module):
         self._pair_refusal("fit_pairs", attention)
         self.train()
         rows, xv = self._pair_rows(Xi, Xv, item_fields, negatives, n_neg, candidates, generator)
-        e = self._engine
-        e.pair_step(self._hyper, self.update_rule, rows, xv, margin=margin, opt=self._attn_fused)
-        if self._attn_fused is None:
-            self._apply_attention(e.grad)
-        out = e.loss_out[0].clone()
-        self._after_step()
-        return out
+        return self._fit_step(self._engine.pair_step, rows, xv, margin=margin)
 
     # ---- listwise (sampled-softmax) training on the attentional logit (fmx_afm_list_*; the list objective of FMAdam) ----
     def _list_entry(self, method, negatives, n_neg, attention):
@@ -270,13 +268,22 @@ class AFMAdam(RankingTraining, nn.Module):
         self.train()
         idx_d, xv_d, _ = self._inputs(Xi, Xv)
         rows, xv, G = self._list_rows("fit_lists", idx_d, xv_d, item_fields, negatives, n_neg, candidates, generator)
-        e = self._engine
-        e.list_step(self._hyper, self.update_rule, rows, G, xv, opt=self._attn_fused)
-        if self._attn_fused is None:
-            self._apply_attention(e.grad)
-        out = e.loss_out[0].clone()
-        self._after_step()
-        return out
+        return self._fit_step(self._engine.list_step, rows, G, xv)
+
+    def _unit_experiment(self, start, n, rows_of, online_run, right, fit_unit):
+        """run_pair_experiment / run_list_experiment behind their refusals, for n units (pairs, lists): rows_of() -> the assembled
+        (rows, xv, G), G rows per unit.  fused_optimizer=True: one upload and ONE call online_run(rows, xv, G, logits) for the n G
+        logits before each unit's update; False: the host loop of fit_unit(rows, xv, G, i), a one-unit step whose own forward
+        leaves the unit's logits in the engine.  right(z [m, G]) -> [m] bool: the unit was predicted correctly."""
+        if n == 0:
+            return self._experiment_result(start, None)
+        rows, xv, G = rows_of()
+        if self._attn_fused is not None:
+            logits = torch.empty(n * G, dtype=torch.float32, device=self.device)
+            online_run(rows, xv, G, logits)
+            return self._experiment_result(start, right(logits.view(n, G)).to(torch.uint8))
+        return self._experiment_result(start, self._host_stream_loop(n, lambda i: fit_unit(rows, xv, G, i),
+                                                                     lambda: right(self._engine.logit[:G].view(1, G))[0]))
 
     def run_list_experiment(self, Xi, Xv, item_fields, negatives=None, n_neg=4, candidates=None, generator=None, attention=False):
         """FMAdam.run_list_experiment's arguments and 4-tuple; attention=True: for every list predict the positive's rank among
@@ -287,22 +294,17 @@ class AFMAdam(RankingTraining, nn.Module):
         start = time()
         self.train()
         idx_d, xv_d, _ = self._inputs(Xi, Xv)
-        n, e = idx_d.shape[0], self._engine
-        if n == 0:
-            return self._experiment_result(start, None)
-        rows, xv, G = self._list_rows("run_list_experiment", idx_d, xv_d, item_fields, negatives, n_neg, candidates, generator)
-        if self._attn_fused is not None:
-            logits = torch.empty(n * G, dtype=torch.float32, device=self.device)
-            e.list_online_run(self._hyper, self.update_rule, rows, G, xv, self._attn_fused, logits=logits)
-            z = logits.view(n, G)
-            return self._experiment_result(start, ((z[:, 1:] >= z[:, :1]).sum(1) == 0).to(torch.uint8))
-        fields = self._item_fields(item_fields)
 
-        def fit_one(i):
-            lst = rows[G * i:G * (i + 1)]
+        def fit_one(rows, xv, G, i):
+            fields, lst = self._item_fields(item_fields), rows[G * i:G * (i + 1)]
             self.fit_lists(lst[:1], None if xv is None else xv[G * i:G * i + 1], fields,
                            negatives=lst[1:, fields].reshape(1, G - 1, -1), attention=True)
-        return self._experiment_result(start, self._host_stream_loop(n, fit_one, lambda: (e.logit[1:G] >= e.logit[0]).sum() == 0))
+        return self._unit_experiment(
+            start, idx_d.shape[0],
+            lambda: self._list_rows("run_list_experiment", idx_d, xv_d, item_fields, negatives, n_neg, candidates, generator),
+            lambda rows, xv, G, logits: self._engine.list_online_run(self._hyper, self.update_rule, rows, G, xv, self._attn_fused,
+                                                                     logits=logits),
+            lambda z: (z[:, 1:] >= z[:, :1]).sum(1) == 0, fit_one)
 
     # (mine_negatives: RankingTraining's, which refuses it for this model by name)
 
@@ -316,19 +318,16 @@ class AFMAdam(RankingTraining, nn.Module):
         start = time()
         self.train()
         rows, xv = self._pair_rows(Xi, Xv, item_fields, negatives, n_neg, candidates, generator)
-        n, e = rows.shape[0] // 2, self._engine
-        if n == 0:
-            return self._experiment_result(start, None)
-        if self._attn_fused is not None:
-            logits = torch.empty(2 * n, dtype=torch.float32, device=self.device)
-            e.pair_online_run(self._hyper, self.update_rule, rows, xv, self._attn_fused, margin=margin, logits=logits)
-            return self._experiment_result(start, (logits[0::2] > logits[1::2]).to(torch.uint8))
-        fields = self._item_fields(item_fields)
 
-        def fit_one(i):
+        def fit_one(rows, xv, G, i):
+            fields = self._item_fields(item_fields)
             pos, pos_xv, neg = self._pair_at(rows, xv, fields, i)
             self.fit_pairs(pos, pos_xv, fields, negatives=neg, margin=margin, attention=True)
-        return self._experiment_result(start, self._host_stream_loop(n, fit_one, lambda: e.logit[0] > e.logit[1]))
+        return self._unit_experiment(
+            start, rows.shape[0] // 2, lambda: (rows, xv, 2),
+            lambda rows, xv, G, logits: self._engine.pair_online_run(self._hyper, self.update_rule, rows, xv, self._attn_fused,
+                                                                     margin=margin, logits=logits),
+            lambda z: z[:, 0] > z[:, 1], fit_one)
 
     def _mean_logloss(self, Xi, Xv, y, chunk=16384):
         """The mean BCE-with-logits over a data set, evaluated by batches (reference eval_by_batch, :143-165)."""
@@ -397,24 +396,14 @@ class AFMAdam(RankingTraining, nn.Module):
         pred = np.asarray(self.predict(data_Xi, data_Xv)).reshape(-1)
         start = time()
         y = np.asarray(data_Y).reshape(-1)
-        n = len(y)
-        pos, hit = y == 1, pred == y
-        tp, fn = np.cumsum(pos & hit), np.cumsum(pos & ~hit)
-        tn, fp = np.cumsum(~pos & hit), np.cumsum(~pos & ~hit)
-        accuracy, roc = [], []
-        for i in sorted(set(range(0, n, 1000)) | {n - 1}):
-            roc.append({"tpr": tp[i] / (tp[i] + fn[i] + 1e-16), "fpr": fp[i] / (fp[i] + tn[i] + 1e-16)})
-            accuracy.append((tp[i] + tn[i]) / (i + 1) * 100)
-        cm = {"tp": int(tp[-1]), "fp": int(fp[-1]), "tn": int(tn[-1]), "fn": int(fn[-1])}
-        return time() - start, float(accuracy[-1]), {k: float(v) for k, v in roc[-1].items()}, cm
+        return self._report(y, pred == y, start)
 
     @staticmethod
-    def _online_report(pred, data_Y, start):
-        """(seconds, accuracy %, last roc point, confusion matrix) of the predictions taken before each sample's update, with
-        the checkpoints of the other classes' run_experiment: every 1,000 samples and at the last sample."""
-        y = np.asarray(data_Y).reshape(-1)
+    def _report(y, hit, start):
+        """(seconds, accuracy %, last roc point, confusion matrix) of the predictions `hit` marks as right against the labels y,
+        with the checkpoints of the other classes' run_experiment: every 1,000 samples and at the last sample."""
         n = len(y)
-        pos, hit = y == 1, pred == (y == 1)
+        pos = y == 1
         tp, fn = np.cumsum(pos & hit), np.cumsum(pos & ~hit)
         tn, fp = np.cumsum(~pos & hit), np.cumsum(~pos & ~hit)
         accuracy, roc = [], []
@@ -451,7 +440,7 @@ class AFMAdam(RankingTraining, nn.Module):
             for i in range(N):
                 pred[i] = bool(np.asarray(self.predict(Xi[i:i + 1], Xv[i:i + 1])).reshape(-1)[0])
                 self.update_embedding(Xi[i:i + 1], Xv[i:i + 1], Y[i:i + 1])
-        return self._online_report(pred, Y, start)
+        return self._report(Y, pred == (Y == 1), start)     # the predictions taken before each sample's update
 
     # ------------------------------------------------------------------------------------------------------
     # state (the reference's keys) and pickling

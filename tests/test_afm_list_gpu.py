@@ -5,6 +5,7 @@ the two rows of a G = 2 list coincide; an index outside its field; determinism; 
 online run against one-list steps, bit for bit; AFMAdam.fit_lists / run_list_experiment(attention=True); and sixty steps that
 bring the list loss down."""
 import ctypes as C
+import functools
 import os
 import pickle
 import sys
@@ -20,7 +21,8 @@ from test_adaptive_rules_cpu import rule_apply  # noqa: E402
 from test_afm_gpu import (HYP, _attn_state, _check_rule, _model_state, _sizes, _touched, assert_exercised, engine,  # noqa: E402
                           make)
 from test_afm_pair_gpu import _assert_same, _class_data, _everything, _models, bits  # noqa: E402
-from test_afm_stream_gpu import LAYOUT, _hyper, _same_models, _stream_start, check_attention, opt_state  # noqa: E402
+from test_afm_stream_gpu import (LAYOUT, SMALL, SMALL_CASES, SMALL_RULES, _hyper, _same_models, _stream_start, check_attention,  # noqa: E402
+                                 issue, opt_state)
 
 pytestmark = pytest.mark.gpu
 
@@ -417,6 +419,76 @@ def test_list_online_run_equals_one_list_steps_bit_for_bit(rule, F, k, t, G):
         got = _everything(tb, params, opt, losses, dict(logits=logits, grad=eng.grad, error=eng.error))
         assert opt.step == 2 + N and tb.step == (N if moments else 0)
         _assert_same(got, want, f"{rule} list online run {split}")
+
+
+# ---- the one queue of steps at its smallest (test_afm_stream_gpu's SMALL): 3 lists of G = 3 a step, a pool of 3 walked twice and
+#      a step more, 5 lists online (the list run is always queued) -- without xv, and from a stream that is not torch's default ----
+@functools.lru_cache(maxsize=None)
+def _small_lists(rule, with_xv):
+    """(sizes, pool and stream on the device, what the single list steps on the default stream leave): computed once per case"""
+    F, k, t, Bl, n_pool, n_steps, N = (SMALL[kk] for kk in ("F", "k", "t", "units", "n_pool", "n_steps", "N"))
+    G = Bl
+    sizes, kind = list_sizes(F, G, 31), "random" if with_xv else "ones"
+    pool = [list_batch(sizes, Bl, G, seed=300 + j, xv_kind=kind) for j in range(n_pool)]
+    idx_pool = torch.from_numpy(np.stack([p[0] for p in pool])).cuda().contiguous()
+    xv_pool = torch.from_numpy(np.stack([p[1] for p in pool])).cuda().contiguous() if with_xv else None
+    hyp = _hyper(rule)
+    tb, params, eng, opt = _stream_start(rule, sizes, k, t, Bl * G, seed=41)
+    losses = torch.zeros(n_steps, device="cuda")
+    for s in range(n_steps):
+        j = s % n_pool
+        eng.list_step(hyp, rule, idx_pool[j], G, None if xv_pool is None else xv_pool[j], opt=opt)
+        losses[s] = eng.loss_out[0]
+    want_stream = _everything(tb, params, opt, losses)
+    assert int(eng.error.item()) == 0 and opt.step == 2 + n_steps
+
+    idx, xv, _ = list_batch(sizes, N, G, seed=340, xv_kind=kind)
+    tb, params, eng, opt = _stream_start(rule, sizes, k, t, G, seed=41)
+    idx_d, xv_d, _ = eng.to_device(idx, xv)
+    logits, losses = torch.zeros(N * G, device="cuda"), torch.zeros(N, device="cuda")
+    for i in range(N):
+        sl = slice(G * i, G * (i + 1))
+        eng.list_step(hyp, rule, idx_d[sl], G, None if xv_d is None else xv_d[sl], inv_b=1.0, opt=opt)
+        logits[sl] = eng.logit[:G]                                 # (the step's own forward: the logits before its update)
+        losses[i] = eng.loss_out[0]
+    want_online = _everything(tb, params, opt, losses, dict(logits=logits, grad=eng.grad, error=eng.error))
+    assert opt.step == 2 + N and int(want_online["error"]) == 0
+    for want in (want_stream, want_online):
+        assert bool(torch.isfinite(want["losses"]).all()) and bool((want["losses"] > 0).all())
+    return sizes, G, (idx_pool, xv_pool), (idx_d, xv_d), want_stream, want_online
+
+
+@SMALL_CASES
+@SMALL_RULES
+def test_small_list_stream_is_its_single_steps(rule, with_xv, side):
+    k, t, Bl, n_steps = (SMALL[kk] for kk in ("k", "t", "units", "n_steps"))
+    sizes, G, (idx_pool, xv_pool), _, want, _ = _small_lists(rule, with_xv)
+    tb, params, eng, opt = _stream_start(rule, sizes, k, t, Bl * G, seed=41)
+    losses = torch.full((n_steps,), -1.0, device="cuda")
+    issue(side, lambda st: eng.list_stream(_hyper(rule), rule, idx_pool, xv_pool, Bl, G, n_steps, opt, losses=losses, stream=st))
+    got = _everything(tb, params, opt, losses)
+    assert int(eng.error.item()) == 0 and opt.step == 2 + n_steps and tb.step == (n_steps if LAYOUT[rule] == "moments" else 0)
+    _assert_same(got, want, f"{rule} list stream")
+
+
+@SMALL_CASES
+@SMALL_RULES
+def test_small_list_online_run_is_its_single_steps(rule, with_xv, side):
+    """Two calls of 1 and N - 1 lists: the second call's logits start G floats in, its losses one."""
+    k, t, N = (SMALL[kk] for kk in ("k", "t", "N"))
+    sizes, G, _, (idx_d, xv_d), _, want = _small_lists(rule, with_xv)
+    tb, params, eng, opt = _stream_start(rule, sizes, k, t, G, seed=41)
+    logits, losses = torch.full((N * G,), -7.0, device="cuda"), torch.full((N,), -7.0, device="cuda")
+    hyp = _hyper(rule)
+
+    def run(st):
+        for o, n in ((0, 1), (1, N - 1)):
+            eng.list_online_run(hyp, rule, idx_d[G * o:G * (o + n)], G, None if xv_d is None else xv_d[G * o:G * (o + n)], opt,
+                                logits=logits[G * o:], losses=losses[o:], stream=st)
+    issue(side, run)
+    got = _everything(tb, params, opt, losses, dict(logits=logits, grad=eng.grad, error=eng.error))
+    assert opt.step == 2 + N and tb.step == (N if LAYOUT[rule] == "moments" else 0)
+    _assert_same(got, want, f"{rule} list online run")
 
 
 def test_list_online_run_of_zero_lists_touches_nothing():

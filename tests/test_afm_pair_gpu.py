@@ -4,6 +4,7 @@ update rule (the bias word keeps its bits: its gradient is exactly +0); exact ca
 index outside its field; determinism; the stream against its steps and the online run against single-pair steps, bit for bit;
 AFMAdam.fit_pairs / run_pair_experiment(attention=True); and sixty steps that bring the pair loss down."""
 import ctypes as C
+import functools
 import os
 import pickle
 import sys
@@ -18,7 +19,8 @@ from helpers import assert_within_f64  # noqa: E402
 from test_adaptive_rules_cpu import rule_apply  # noqa: E402
 from test_afm_gpu import (HYP, _attn_state, _check_rule, _model_state, _sizes, _touched, assert_exercised, engine,  # noqa: E402
                           make)
-from test_afm_stream_gpu import LAYOUT, _hyper, _same_models, _stream_start, check_attention, opt_state  # noqa: E402
+from test_afm_stream_gpu import (ATTN_RULE, LAYOUT, SMALL, SMALL_CASES, SMALL_RULES, _hyper, _same_models, _stream_start,  # noqa: E402
+                                 check_attention, issue, opt_state, queued_online_form)
 
 pytestmark = pytest.mark.gpu
 
@@ -365,6 +367,78 @@ def test_pair_online_run_equals_single_pair_steps_bit_for_bit(rule, F, k, t):
         got = _everything(tb, params, opt, losses, dict(logits=logits, grad=eng.grad, error=eng.error))
         assert opt.step == 2 + N and tb.step == (N if moments else 0)
         _assert_same(got, want, f"{rule} pair online run {split}")
+
+
+# ---- the one queue of steps at its smallest (test_afm_stream_gpu's SMALL): 3 pairs a step, a pool of 3 walked twice and a step
+#      more, 5 pairs online in the queued form -- without xv, and from a stream that is not torch's default ----
+@functools.lru_cache(maxsize=None)
+def _small_pairs(rule, with_xv):
+    """(sizes, pool and stream on the device, what the single pair steps on the default stream leave): computed once per case"""
+    F, k, t, P, n_pool, n_steps, N = (SMALL[kk] for kk in ("F", "k", "t", "units", "n_pool", "n_steps", "N"))
+    sizes, kind, margin = _sizes(F, 31), "random" if with_xv else "ones", 0.1
+    pool = [pair_batch(sizes, P, seed=300 + j, xv_kind=kind) for j in range(n_pool)]
+    idx_pool = torch.from_numpy(np.stack([p[0] for p in pool])).cuda().contiguous()
+    xv_pool = torch.from_numpy(np.stack([p[1] for p in pool])).cuda().contiguous() if with_xv else None
+    hyp = _hyper(rule)
+    tb, params, eng, opt = _stream_start(rule, sizes, k, t, 2 * P, seed=41)
+    losses = torch.zeros(n_steps, device="cuda")
+    for s in range(n_steps):
+        j = s % n_pool
+        eng.pair_step(hyp, rule, idx_pool[j], None if xv_pool is None else xv_pool[j], margin=margin, opt=opt)
+        losses[s] = eng.loss_out[0]
+    want_stream = _everything(tb, params, opt, losses)
+    assert int(eng.error.item()) == 0 and opt.step == 2 + n_steps
+
+    idx, xv, _ = pair_batch(sizes, N, seed=340, xv_kind=kind, share_item=True)
+    tb, params, eng, opt = _stream_start(rule, sizes, k, t, 2, seed=41)
+    idx_d, xv_d, _ = eng.to_device(idx, xv)
+    logits, losses = torch.zeros(2 * N, device="cuda"), torch.zeros(N, device="cuda")
+    for i in range(N):
+        sl = slice(2 * i, 2 * i + 2)
+        eng.pair_step(hyp, rule, idx_d[sl], None if xv_d is None else xv_d[sl], margin=margin, inv_b=1.0, opt=opt)
+        logits[sl] = eng.logit[:2]                                 # (the step's own forward: the logits before its update)
+        losses[i] = eng.loss_out[0]
+    want_online = _everything(tb, params, opt, losses, dict(logits=logits, grad=eng.grad, error=eng.error))
+    assert opt.step == 2 + N and int(want_online["error"]) == 0
+    for want in (want_stream, want_online):
+        assert bool(torch.isfinite(want["losses"]).all()) and bool((want["losses"] != 0).all())
+    return sizes, margin, (idx_pool, xv_pool), (idx_d, xv_d), want_stream, want_online
+
+
+@SMALL_CASES
+@SMALL_RULES
+def test_small_pair_stream_is_its_single_steps(rule, with_xv, side):
+    k, t, P, n_steps = (SMALL[kk] for kk in ("k", "t", "units", "n_steps"))
+    sizes, margin, (idx_pool, xv_pool), _, want, _ = _small_pairs(rule, with_xv)
+    tb, params, eng, opt = _stream_start(rule, sizes, k, t, 2 * P, seed=41)
+    losses = torch.full((n_steps,), -1.0, device="cuda")
+    issue(side, lambda st: eng.pair_stream(_hyper(rule), rule, idx_pool, xv_pool, P, n_steps, opt, margin=margin, losses=losses,
+                                           stream=st))
+    got = _everything(tb, params, opt, losses)
+    assert int(eng.error.item()) == 0 and opt.step == 2 + n_steps and tb.step == (n_steps if LAYOUT[rule] == "moments" else 0)
+    _assert_same(got, want, f"{rule} pair stream")
+
+
+@SMALL_CASES
+@SMALL_RULES
+def test_small_queued_pair_online_run_is_its_single_steps(rule, with_xv, side):
+    """The queued form in two calls of 1 and N - 1 pairs: the second call's logits start two floats in, its losses one."""
+    k, t, N = (SMALL[kk] for kk in ("k", "t", "N"))
+    sizes, margin, _, (idx_d, xv_d), _, want = _small_pairs(rule, with_xv)
+    tb, params, eng, opt = _stream_start(rule, sizes, k, t, 2, seed=41)
+    logits, losses = torch.full((2 * N,), -7.0, device="cuda"), torch.full((N,), -7.0, device="cuda")
+    hyp = _hyper(rule)
+
+    def run(st):
+        for o, n in ((0, 1), (1, N - 1)):
+            eng.pair_online_run(hyp, rule, idx_d[2 * o:2 * (o + n)], None if xv_d is None else xv_d[2 * o:2 * (o + n)], opt,
+                                margin=margin, logits=logits[2 * o:], losses=losses[o:], stream=st)
+    with queued_online_form(b"afm_pair_online_persistent"):
+        assert eng.pair_online_form(ATTN_RULE[rule])[0] == 0
+        issue(side, run)
+    got = _everything(tb, params, opt, losses, dict(logits=logits, grad=eng.grad, error=eng.error))
+    assert opt.step == 2 + N and tb.step == (N if LAYOUT[rule] == "moments" else 0)
+    _assert_same(got, want, f"{rule} queued pair online run")
 
 
 def test_pair_online_run_of_zero_pairs_touches_nothing():

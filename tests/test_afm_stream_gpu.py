@@ -2,6 +2,8 @@
 (many steps in one call) on the GPU: the step against fmx_afm_step bit for bit and against the float64 rules on afm_f64's
 gradients, adam / adagrad trajectories against float64 torch.optim.Adam / Adagrad (a dead unit's parameters still move), the
 stream against step-by-step calls bit for bit, and AFMAdam(fused_optimizer=True): update_embedding, fit, pickling, the index flag."""
+import contextlib
+import functools
 import os
 import pickle
 import sys
@@ -212,6 +214,108 @@ def test_stream_equals_step_by_step_bit_for_bit(rule, with_xv, B):
         got = _everything(tb, params, opt, losses)
         for key in want:
             assert torch.equal(got[key], want[key]), f"{rule} stream {split}: {key} differs from the single steps'"
+
+
+# ---- the one queue of steps behind the stream and the queued online run, at its smallest: kp = 4, 3 samples a step, a pool of
+#      3 walked twice and a step more, 5 samples online -- without xv, and issued from a stream that is not torch's default.
+#      (test_afm_pair_gpu and test_afm_list_gpu run the pair and list forms at the same shape.) ----
+SMALL = dict(F=5, k=3, t=4, units=3, n_pool=3, n_steps=7, N=5)
+SMALL_CASES = pytest.mark.parametrize("with_xv,side", [(False, False), (True, True)], ids=["no_xv", "side_stream"])
+SMALL_RULES = pytest.mark.parametrize("rule", ["sgd", "adam"])
+
+
+def issue(side, call):
+    """call(stream) behind everything queued so far and waited for: stream None (torch's current, the default one) or, side, a
+    stream of its own.  The comparison side of these tests is always single steps on the default stream."""
+    torch.cuda.synchronize()
+    stream = torch.cuda.Stream() if side else None
+    call(stream)
+    torch.cuda.synchronize()
+
+
+@contextlib.contextmanager
+def queued_online_form(option):
+    """Inside, the online run whose one-workgroup kernel `option` switches takes its queued form"""
+    lib = _fmx()._lib.load()
+    assert lib.fmx_set_option(option, 0) == 1
+    try:
+        yield
+    finally:
+        lib.fmx_set_option(option, 1)
+
+
+@functools.lru_cache(maxsize=None)
+def _small_bce(rule, with_xv):
+    """(sizes, pool and stream on the device, what the single steps on the default stream leave): computed once per case"""
+    F, k, t, B, n_pool, n_steps, N = (SMALL[kk] for kk in ("F", "k", "t", "units", "n_pool", "n_steps", "N"))
+    sizes, kind = _sizes(F, 31), "random" if with_xv else "ones"
+    pool = [batch(sizes, B, seed=300 + j, xv_kind=kind) for j in range(n_pool)]
+    idx_pool = torch.from_numpy(np.stack([p[0] for p in pool])).cuda().contiguous()
+    xv_pool = torch.from_numpy(np.stack([p[1] for p in pool])).cuda().contiguous() if with_xv else None
+    y_pool = torch.from_numpy(np.stack([p[2] for p in pool])).cuda().contiguous()
+    hyp = _hyper(rule)
+    tb, params, eng, opt = _stream_start(rule, sizes, k, t, B, seed=41)
+    losses = torch.zeros(n_steps, device="cuda")
+    for s in range(n_steps):
+        j = s % n_pool
+        eng.step(hyp, rule, idx_pool[j], None if xv_pool is None else xv_pool[j], y_pool[j], opt=opt)
+        losses[s] = eng.loss_out[0]
+    torch.cuda.synchronize()
+    assert int(eng.error.item()) == 0 and opt.step == 2 + n_steps
+    want_stream = _everything(tb, params, opt, losses)
+
+    idx, xv, y, _ = batch(sizes, N, seed=340, xv_kind=kind)
+    tb, params, eng, opt = _stream_start(rule, sizes, k, t, 1, seed=41)
+    idx_d, xv_d, y_d = eng.to_device(idx, xv, y)
+    logits, losses = torch.zeros(N, device="cuda"), torch.zeros(N, device="cuda")
+    for i in range(N):
+        xi = None if xv_d is None else xv_d[i:i + 1]
+        eng.forward(hyp, idx_d[i:i + 1], xi)                       # the sample's logit before its update
+        logits[i] = eng.logit[0]
+        eng.step(hyp, rule, idx_d[i:i + 1], xi, y_d[i:i + 1], inv_b=1.0, opt=opt)
+        losses[i] = eng.loss_out[0]
+    torch.cuda.synchronize()
+    assert int(eng.error.item()) == 0 and opt.step == 2 + N
+    want_online = dict(_everything(tb, params, opt, losses), logits=logits.cpu(), grad=eng.grad.cpu())
+    return sizes, (idx_pool, xv_pool, y_pool), (idx_d, xv_d, y_d), want_stream, want_online
+
+
+@SMALL_CASES
+@SMALL_RULES
+def test_small_stream_is_its_single_steps(rule, with_xv, side):
+    k, t, B, n_steps = (SMALL[kk] for kk in ("k", "t", "units", "n_steps"))
+    sizes, (idx_pool, xv_pool, y_pool), _, want, _ = _small_bce(rule, with_xv)
+    assert bool((want["losses"] > 0).all())
+    tb, params, eng, opt = _stream_start(rule, sizes, k, t, B, seed=41)
+    losses = torch.full((n_steps,), -1.0, device="cuda")
+    issue(side, lambda st: eng.stream(_hyper(rule), rule, idx_pool, xv_pool, y_pool, B, n_steps, opt, losses=losses, stream=st))
+    assert int(eng.error.item()) == 0 and opt.step == 2 + n_steps and tb.step == (n_steps if LAYOUT[rule] == "moments" else 0)
+    got = _everything(tb, params, opt, losses)
+    for key in want:
+        assert torch.equal(got[key], want[key]), f"{rule} stream: {key} differs from the single steps'"
+
+
+@SMALL_CASES
+@SMALL_RULES
+def test_small_queued_online_run_is_its_single_steps(rule, with_xv, side):
+    """The queued form in two calls of 1 and N - 1 samples: the second call's logits and losses start one sample in."""
+    k, t, N = (SMALL[kk] for kk in ("k", "t", "N"))
+    sizes, _, (idx_d, xv_d, y_d), _, want = _small_bce(rule, with_xv)
+    assert bool((want["losses"] > 0).all())
+    tb, params, eng, opt = _stream_start(rule, sizes, k, t, 1, seed=41)
+    logits, losses = torch.full((N,), -7.0, device="cuda"), torch.full((N,), -7.0, device="cuda")
+    hyp = _hyper(rule)
+
+    def run(st):
+        for o, n in ((0, 1), (1, N - 1)):
+            eng.online_run(hyp, rule, idx_d[o:o + n], None if xv_d is None else xv_d[o:o + n], y_d[o:o + n], opt, logits=logits[o:],
+                           losses=losses[o:], stream=st)
+    with queued_online_form(b"afm_online_persistent"):
+        issue(side, run)
+    assert int(eng.error.item()) == 0 and opt.step == 2 + N and tb.step == (N if LAYOUT[rule] == "moments" else 0)
+    got = dict(_everything(tb, params, opt, losses), logits=logits.cpu(), grad=eng.grad.cpu())
+    for key in want:
+        assert torch.equal(got[key], want[key]), f"{rule} queued online run: {key} differs from the single steps'"
 
 
 def test_stream_of_zero_steps_launches_nothing():
