@@ -105,7 +105,9 @@ __device__ __forceinline__ float first_lane_f(float v) { return __int_as_float(_
 // sh[3][16] and k_fm_forward_list's own launch bound -- and B a multiple of G): a workgroup holds whole lists, lane i of the first
 // wave is position i % G of list i / G, and every lane evaluates its list's softmax cross-entropy from the list's G logits
 // (list_loss_dz, fmx_common.h) -- the positive stores (loss_i, dz_0), a negative (0, dz_j).  No label and no loss_kind is read.
-template <int LPR, bool PAIR = false, bool LIST = false>
+// LISTQ (fmx_fm_list_forward_q; with LIST): y is the row's correction corr[b] (a.y, carried through sh[2] as a label is) and the
+// softmax is taken over c = z - y; the stored logit stays z.
+template <int LPR, bool PAIR = false, bool LIST = false, bool LISTQ = false>
 __device__ __forceinline__ void forward_finish(const FwdArgs &a, int b, const bool exists, const int lane, float4 s, float4 ss, float fo,
                                                bool bad, float y, const float bias) {
   const int q = lane % LPR;
@@ -156,7 +158,8 @@ __device__ __forceinline__ void forward_finish(const FwdArgs &a, int b, const bo
       if (a.out.dz) a.out.dz[(size_t)bl * a.ld1] = pos ? dz : -dz;
     } else if constexpr (LIST) {
       float loss, dz;  // (n is a multiple of G: every lane of the list is active)
-      list_loss_dz(z, lane, a.list_g, a.inv_b, loss, dz);
+      if constexpr (LISTQ) list_loss_dz(z - y, lane, a.list_g, a.inv_b, loss, dz);
+      else list_loss_dz(z, lane, a.list_g, a.inv_b, loss, dz);
       if (a.out.loss) a.out.loss[(size_t)bl * a.ld1] = lane % a.list_g == 0 ? loss : 0.f;
       if (a.out.dz) a.out.dz[(size_t)bl * a.ld1] = dz;
     } else if (a.loss_kind != FMX_LOSS_NONE) {
@@ -188,7 +191,7 @@ constexpr int64_t ROW_ABSENT = int64_t(1) << 62;  // set in a resolved row: the 
 // HAS_X: xv is not null (without values every x is 1 and nothing is loaded for it).
 // exists (wave-uniform): false for a wave behind the batch's last sample, which repeats that sample for the workgroup's barrier and
 // stores nothing.
-template <int LPR, int LAYOUT, int NPASS, bool MAPPED, bool HAS_X, bool PAIR = false, bool LIST = false>
+template <int LPR, int LAYOUT, int NPASS, bool MAPPED, bool HAS_X, bool PAIR = false, bool LIST = false, bool LISTQ = false>
 __device__ __forceinline__ void forward_sample(const FwdArgs &a, const int b, const bool exists, const int lane) {
   constexpr int SLOTS = WAVE / LPR;
   constexpr int NP = NPASS > 0 ? NPASS : 1;
@@ -202,7 +205,7 @@ __device__ __forceinline__ void forward_sample(const FwdArgs &a, const int b, co
   bool bad = false;
   // the label and the bias are only needed by the epilogue, but a load issued there is one more dependent round trip
   // at the end of every wave: request them now, with the indices (every lane the same address: one request each)
-  const float y_early = (!PAIR && !LIST && a.loss_kind != FMX_LOSS_NONE) ? a.y[b] : 0.f;
+  const float y_early = (LISTQ || (!PAIR && !LIST && a.loss_kind != FMX_LOSS_NONE)) ? a.y[b] : 0.f;  // (LISTQ: the row's correction)
   const float bias0_early = a.bias[0];
   const float bias1_early = LAYOUT == FMX_LAYOUT_WEIGHTS ? 0.f : a.bias[1];
   __builtin_amdgcn_sched_barrier(0);  // (left to itself the scheduler sinks the bias load behind the first waits of the gather:
@@ -286,7 +289,7 @@ __device__ __forceinline__ void forward_sample(const FwdArgs &a, const int b, co
     }
     FMX_FSTAMP(2, s.x + ss.x + fo);  // (every row of the pass set arrived and added)
   }
-  forward_finish<LPR, PAIR, LIST>(a, b, exists, lane, s, ss, fo, bad, y_early, bias);
+  forward_finish<LPR, PAIR, LIST, LISTQ>(a, b, exists, lane, s, ss, fo, bad, y_early, bias);
 }
 
 template <int LPR, int LAYOUT, int NPASS, bool MAPPED = false, bool PAIR = false>
@@ -311,6 +314,18 @@ __global__ __launch_bounds__(64 * LIST_MAX_G) void k_fm_forward_list(FwdArgs a) 
   if (!exists) b = a.B - 1;     // (the barrier again; B_lists G need not be a multiple of the workgroup's waves when they exceed G)
   if (a.xv) forward_sample<LPR, LAYOUT, NPASS, false, true, false, true>(a, b, exists, threadIdx.x & 63);
   else forward_sample<LPR, LAYOUT, NPASS, false, false, false, true>(a, b, exists, threadIdx.x & 63);
+}
+
+// ... and its log-Q corrected form (fmx_fm_list_forward_q): forward_finish<LIST, LISTQ>, a.y = corr.  A kernel of its own name, so
+// that k_fm_forward_list's instantiations keep theirs (tools/isa_diff.py matches kernels by name).
+template <int LPR, int LAYOUT, int NPASS>
+__global__ __launch_bounds__(64 * LIST_MAX_G) void k_fm_forward_listq(FwdArgs a) {
+  __builtin_amdgcn_s_setprio(3);
+  int b = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+  const bool exists = b < a.B;  // wave-uniform
+  if (!exists) b = a.B - 1;
+  if (a.xv) forward_sample<LPR, LAYOUT, NPASS, false, true, false, true, true>(a, b, exists, threadIdx.x & 63);
+  else forward_sample<LPR, LAYOUT, NPASS, false, false, false, true, true>(a, b, exists, threadIdx.x & 63);
 }
 
 // ------------------------------------------------------------------------------------------------------------
@@ -767,14 +782,20 @@ void launch_forward(const FwdArgs &a, int layout, hipStream_t st) {
 
 // LIST (fmx_fm_list_forward): G * max(1, 4 / G) waves per workgroup -- 4, 3, 4 at G = 2, 3, 4, then G -- so a workgroup holds whole
 // lists and no list straddles two; B_lists * G need not be a multiple of that (the waves past the last row go along to the barrier)
-template <int LPR>
+// (Q: k_fm_forward_listq, the corrected form, a.y = corr)
+template <int LPR, bool Q = false>
 void launch_forward_list(const FwdArgs &a, int layout, hipStream_t st) {
   const int G = a.list_g, wpb = G * (4 / G > 1 ? 4 / G : 1);
   const dim3 grid((a.B + wpb - 1) / wpb), block(64 * wpb);
   const int slots = WAVE / LPR, np = (a.F + slots - 1) / slots;
   auto launch = [&](auto NP) {
-    if (layout == FMX_LAYOUT_FTRL) hipLaunchKernelGGL((k_fm_forward_list<LPR, FMX_LAYOUT_FTRL, NP>), grid, block, 0, st, a);
-    else hipLaunchKernelGGL((k_fm_forward_list<LPR, FMX_LAYOUT_WEIGHTS, NP>), grid, block, 0, st, a);
+    if constexpr (Q) {
+      if (layout == FMX_LAYOUT_FTRL) hipLaunchKernelGGL((k_fm_forward_listq<LPR, FMX_LAYOUT_FTRL, NP>), grid, block, 0, st, a);
+      else hipLaunchKernelGGL((k_fm_forward_listq<LPR, FMX_LAYOUT_WEIGHTS, NP>), grid, block, 0, st, a);
+    } else {
+      if (layout == FMX_LAYOUT_FTRL) hipLaunchKernelGGL((k_fm_forward_list<LPR, FMX_LAYOUT_FTRL, NP>), grid, block, 0, st, a);
+      else hipLaunchKernelGGL((k_fm_forward_list<LPR, FMX_LAYOUT_WEIGHTS, NP>), grid, block, 0, st, a);
+    }
   };
   if (!with_one_of<1, 2, 3, 4>(np, launch)) launch(std::integral_constant<int, 0>{});
 }
@@ -1609,21 +1630,43 @@ int64_t fmx_fm_list_workspace_bytes(const fmx_table_t *table, int32_t B_lists, i
 
 int fmx_fm_list_forward(const fmx_table_t *table, const fmx_hyper_t *hyper, const int32_t *idx, const float *xv, int32_t B_lists,
                         int32_t G, float inv_b, const fmx_fwd_out_t *out, fmx_stream_t stream) {
-  return list_forward_call(table, hyper, idx, xv, B_lists, G, inv_b, out, static_cast<hipStream_t>(stream));
+  return list_forward_call(table, hyper, idx, xv, nullptr, B_lists, G, inv_b, out, static_cast<hipStream_t>(stream), "fmx_fm_list_forward");
+}
+
+int fmx_fm_list_forward_q(const fmx_table_t *table, const fmx_hyper_t *hyper, const int32_t *idx, const float *xv, const float *corr,
+                          int32_t B_lists, int32_t G, float inv_b, const fmx_fwd_out_t *out, fmx_stream_t stream) {
+  if (!corr) return fail(FMX_ERR_ARG, "fmx_fm_list_forward_q: corr is null");
+  return list_forward_call(table, hyper, idx, xv, corr, B_lists, G, inv_b, out, static_cast<hipStream_t>(stream), "fmx_fm_list_forward_q");
 }
 
 int fmx_fm_list_step(const fmx_table_t *table, const fmx_hyper_t *hyper, int32_t rule, const int32_t *idx, const float *xv,
                      int32_t B_lists, int32_t G, float inv_b, void *workspace, int64_t workspace_bytes, const fmx_fwd_out_t *fwd,
                      float *loss_out, fmx_stream_t stream) {
-  return list_step_call(table, hyper, rule, idx, xv, B_lists, G, inv_b, workspace, workspace_bytes, fwd, loss_out,
-                        static_cast<hipStream_t>(stream));
+  return list_step_call(table, hyper, rule, idx, xv, nullptr, B_lists, G, inv_b, workspace, workspace_bytes, fwd, loss_out,
+                        static_cast<hipStream_t>(stream), "fmx_fm_list_step");
+}
+
+int fmx_fm_list_step_q(const fmx_table_t *table, const fmx_hyper_t *hyper, int32_t rule, const int32_t *idx, const float *xv,
+                       const float *corr, int32_t B_lists, int32_t G, float inv_b, void *workspace, int64_t workspace_bytes,
+                       const fmx_fwd_out_t *fwd, float *loss_out, fmx_stream_t stream) {
+  if (!corr) return fail(FMX_ERR_ARG, "fmx_fm_list_step_q: corr is null");
+  return list_step_call(table, hyper, rule, idx, xv, corr, B_lists, G, inv_b, workspace, workspace_bytes, fwd, loss_out,
+                        static_cast<hipStream_t>(stream), "fmx_fm_list_step_q");
 }
 
 int fmx_fm_list_stream(const fmx_table_t *table, const fmx_hyper_t *hyper, int32_t rule, const int32_t *idx_pool, int32_t n_pool,
                        int32_t B_lists, int32_t G, float inv_b, int32_t n_steps, void *workspace, int64_t workspace_bytes,
                        const fmx_fwd_out_t *fwd, float *loss_out, fmx_stream_t stream) {
-  return list_stream_call(table, hyper, rule, idx_pool, n_pool, B_lists, G, inv_b, n_steps, workspace, workspace_bytes, fwd, loss_out,
-                          static_cast<hipStream_t>(stream));
+  return list_stream_call(table, hyper, rule, idx_pool, nullptr, n_pool, B_lists, G, inv_b, n_steps, workspace, workspace_bytes, fwd,
+                          loss_out, static_cast<hipStream_t>(stream), "fmx_fm_list_stream");
+}
+
+int fmx_fm_list_stream_q(const fmx_table_t *table, const fmx_hyper_t *hyper, int32_t rule, const int32_t *idx_pool, const float *corr_pool,
+                         int32_t n_pool, int32_t B_lists, int32_t G, float inv_b, int32_t n_steps, void *workspace,
+                         int64_t workspace_bytes, const fmx_fwd_out_t *fwd, float *loss_out, fmx_stream_t stream) {
+  if (!corr_pool) return fail(FMX_ERR_ARG, "fmx_fm_list_stream_q: corr_pool is null");
+  return list_stream_call(table, hyper, rule, idx_pool, corr_pool, n_pool, B_lists, G, inv_b, n_steps, workspace, workspace_bytes, fwd,
+                          loss_out, static_cast<hipStream_t>(stream), "fmx_fm_list_stream_q");
 }
 
 int fmx_fm_list_online_run(const fmx_table_t *table, const fmx_hyper_t *hyper, int32_t rule, const int32_t *idx, const float *xv, int32_t N,

@@ -1,4 +1,7 @@
-// fmx_list.inc -- listwise (sampled-softmax) training of the pure FM, the batched calls: fmx_fm_list_forward / _step / _stream.
+// fmx_list.inc -- listwise (sampled-softmax) training of the pure FM, the batched calls: fmx_fm_list_forward / _step / _stream and
+// their log-Q corrected forms fmx_fm_list_forward_q / _step_q / _stream_q (corr: one float per row, subtracted from the row's logit in
+// front of the softmax; it rides where the pointwise objective's label rides -- FwdArgs.y, step_run's y, stream_run's y_pool --
+// and corr == nullptr is the uncorrected call: one set of checks and one step for both).
 // Included by fmx_kernels.hip inside its anonymous namespace, behind fmx_pair.inc, whose checks it shares.
 // The online form (fmx_fm_list_online_run) has its checks at the end of this file and its kernel, k_fm_list_online, in a unit of its
 // own, fmx_list_online.hip.
@@ -17,21 +20,24 @@
 
 inline int64_t list_workspace_bytes(const fmx_table_t *table, int32_t rows) { return (int64_t)carve(table, rows, nullptr).bytes + LIST_BIAS_SCRATCH; }
 
-int list_forward_impl(const fmx_table_t *table, const fmx_hyper_t *hyper, const int32_t *idx, const float *xv, int32_t rows, int32_t G,
-                      float inv_b, const fmx_fwd_out_t *out, hipStream_t st) {
-  FwdArgs a = fill_fwd(table, hyper, idx, xv, nullptr, rows, FMX_LOSS_NONE, inv_b, out);
+int list_forward_impl(const fmx_table_t *table, const fmx_hyper_t *hyper, const int32_t *idx, const float *xv, const float *corr,
+                      int32_t rows, int32_t G, float inv_b, const fmx_fwd_out_t *out, hipStream_t st) {
+  FwdArgs a = fill_fwd(table, hyper, idx, xv, corr, rows, FMX_LOSS_NONE, inv_b, out);
   a.list_g = G;
+  if (corr) {
+    with_lpr(table->kp, [&](auto LPR) { launch_forward_list<LPR, true>(a, table->layout, st); });
+    return check_launch("k_fm_forward_listq");
+  }
   with_lpr(table->kp, [&](auto LPR) { launch_forward_list<LPR>(a, table->layout, st); });
   return check_launch("k_fm_forward_list");
 }
 
-int list_forward_call(const fmx_table_t *table, const fmx_hyper_t *hyper, const int32_t *idx, const float *xv, int32_t B_lists, int32_t G,
-                      float inv_b, const fmx_fwd_out_t *out, hipStream_t st) {
-  const char *who = "fmx_fm_list_forward";
+int list_forward_call(const fmx_table_t *table, const fmx_hyper_t *hyper, const int32_t *idx, const float *xv, const float *corr,
+                      int32_t B_lists, int32_t G, float inv_b, const fmx_fwd_out_t *out, hipStream_t st, const char *who) {
   int32_t rows = 0;
   if (int rc = check_list_args(table, hyper, idx, B_lists, G, &rows, who)) return rc;
   if (int rc = check_pair_out(table, out, "out", false, who)) return rc;
-  return list_forward_impl(table, hyper, idx, xv, rows, G, inv_b, out, st);
+  return list_forward_impl(table, hyper, idx, xv, corr, rows, G, inv_b, out, st);
 }
 
 // the checks of a step (n_steps = 1) or a stream of them, in front of the first launch
@@ -50,34 +56,34 @@ int check_list_step(const fmx_table_t *table, const fmx_hyper_t *hyper, int32_t 
   return FMX_OK;
 }
 
-// the list objective's forward, as step_run and stream_run call it
+// the list objective's forward, as step_run and stream_run call it: their per-step float pointer (the pointwise label's place) is the
+// step's corr, null for the uncorrected calls
 inline auto list_forward(const fmx_table_t *table, const fmx_hyper_t *hyper, int32_t rows, int32_t G, float inv_b, const fmx_fwd_out_t *fwd) {
-  return [=](const int32_t *idx, const float *xv, const float *, hipStream_t st) {
-    return list_forward_impl(table, hyper, idx, xv, rows, G, inv_b, fwd, st);
+  return [=](const int32_t *idx, const float *xv, const float *corr, hipStream_t st) {
+    return list_forward_impl(table, hyper, idx, xv, corr, rows, G, inv_b, fwd, st);
   };
 }
 
-int list_step_call(const fmx_table_t *table, const fmx_hyper_t *hyper, int32_t rule, const int32_t *idx, const float *xv, int32_t B_lists,
-                   int32_t G, float inv_b, void *workspace, int64_t workspace_bytes, const fmx_fwd_out_t *fwd, float *loss_out,
-                   hipStream_t st) {
+int list_step_call(const fmx_table_t *table, const fmx_hyper_t *hyper, int32_t rule, const int32_t *idx, const float *xv, const float *corr,
+                   int32_t B_lists, int32_t G, float inv_b, void *workspace, int64_t workspace_bytes, const fmx_fwd_out_t *fwd,
+                   float *loss_out, hipStream_t st, const char *who) {
   int32_t rows = 0;
-  if (int rc = check_list_step(table, hyper, rule, idx, B_lists, G, workspace, workspace_bytes, fwd, 1, &rows, "fmx_fm_list_step")) return rc;
+  if (int rc = check_list_step(table, hyper, rule, idx, B_lists, G, workspace, workspace_bytes, fwd, 1, &rows, who)) return rc;
   const Workspace w = carve(table, rows, workspace);
   const fmx_table_t tu = list_update_table(table, workspace, w.bytes);
-  return step_run(table, &tu, hyper, rule, idx, xv, nullptr, rows, inv_b, w, fwd, loss_out, st, list_forward(table, hyper, rows, G, inv_b, fwd));
+  return step_run(table, &tu, hyper, rule, idx, xv, corr, rows, inv_b, w, fwd, loss_out, st, list_forward(table, hyper, rows, G, inv_b, fwd));
 }
 
-int list_stream_call(const fmx_table_t *table, const fmx_hyper_t *hyper, int32_t rule, const int32_t *idx_pool, int32_t n_pool,
-                     int32_t B_lists, int32_t G, float inv_b, int32_t n_steps, void *workspace, int64_t workspace_bytes,
-                     const fmx_fwd_out_t *fwd, float *loss_out, hipStream_t st) {
-  const char *who = "fmx_fm_list_stream";
+int list_stream_call(const fmx_table_t *table, const fmx_hyper_t *hyper, int32_t rule, const int32_t *idx_pool, const float *corr_pool,
+                     int32_t n_pool, int32_t B_lists, int32_t G, float inv_b, int32_t n_steps, void *workspace, int64_t workspace_bytes,
+                     const fmx_fwd_out_t *fwd, float *loss_out, hipStream_t st, const char *who) {
   int32_t rows = 0;
   if (int rc = check_list_step(table, hyper, rule, idx_pool, B_lists, G, workspace, workspace_bytes, fwd, n_steps > 0 ? n_steps : 0, &rows, who))
     return rc;
   if (int rc = check_pool_steps(n_pool, n_steps, who)) return rc;
   const Workspace w = carve(table, rows, workspace);
   const fmx_table_t tu = list_update_table(table, workspace, w.bytes);
-  return stream_run(table, &tu, hyper, rule, idx_pool, nullptr, n_pool, rows, inv_b, n_steps, w, fwd, loss_out, st,
+  return stream_run(table, &tu, hyper, rule, idx_pool, corr_pool, n_pool, rows, inv_b, n_steps, w, fwd, loss_out, st,
                     list_forward(table, hyper, rows, G, inv_b, fwd));
 }
 

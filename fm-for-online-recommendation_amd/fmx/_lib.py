@@ -36,6 +36,7 @@ EXPORTS = ["fmx_version", "fmx_last_error_string", "fmx_set_option", "fmx_sorted
            "fmx_afm_pair_online_form", "fmx_fm_mine_negatives",
            "fmx_fm_list_workspace_bytes", "fmx_fm_list_forward", "fmx_fm_list_step", "fmx_fm_list_stream",
            "fmx_fm_list_online_run", "fmx_update_order",
+           "fmx_fm_list_forward_q", "fmx_fm_list_step_q", "fmx_fm_list_stream_q", "fmx_alias_sample_negatives",
            "fmx_afm_list_workspace_bytes", "fmx_afm_list_forward", "fmx_afm_list_step", "fmx_afm_list_step_opt",
            "fmx_afm_list_stream", "fmx_afm_list_online_run"]
 
@@ -192,6 +193,10 @@ def load():
     lib.fmx_fm_list_step.argtypes = [TP, HP, i32, p, p, i32, i32, f32, p, i64, FP, p, p]
     lib.fmx_fm_list_stream.argtypes = [TP, HP, i32, p, i32, i32, i32, f32, i32, p, i64, FP, p, p]
     lib.fmx_fm_list_online_run.argtypes = [TP, HP, i32, p, p, i32, i32, p, p, p, p, p]
+    lib.fmx_fm_list_forward_q.argtypes = [TP, HP, p, p, p, i32, i32, f32, FP, p]
+    lib.fmx_fm_list_step_q.argtypes = [TP, HP, i32, p, p, p, i32, i32, f32, p, i64, FP, p, p]
+    lib.fmx_fm_list_stream_q.argtypes = [TP, HP, i32, p, p, i32, i32, i32, f32, i32, p, i64, FP, p, p]
+    lib.fmx_alias_sample_negatives.argtypes = [p, p, p, i32, p, p, p, i32, i32, i32, C.c_uint64, C.c_uint64, C.c_uint32, p, p, p]
     lib.fmx_afm_list_workspace_bytes.argtypes = [TP, AP, i32, i32]
     lib.fmx_afm_list_forward.argtypes = [TP, AP, HP, p, p, i32, i32, f32, p, p, p, p, p]
     lib.fmx_afm_list_step.argtypes = [TP, HP, i32, AP, p, p, i32, i32, f32, p, i64, p, p, p, p, p]

@@ -475,39 +475,82 @@ class FMEngine:
             self._list_ws = torch.zeros(need // 4, dtype=torch.int32, device=self.device)     # (zero-filled once, as the header asks)
         return rows // G
 
+    @staticmethod
+    def _corr(corr, shape):
+        """The corrections of the corrected list calls (fmx_fm_list_*_q): one fp32 per row, contiguous, on the device"""
+        if corr.dtype != torch.float32 or tuple(corr.shape) != tuple(shape) or not corr.is_contiguous():
+            raise ValueError(f"corr: a contiguous float32 tensor of shape {tuple(shape)}, got {corr.dtype} {tuple(corr.shape)}")
+        return corr.data_ptr()
+
     def list_forward(self, hyper, idx_d, G, xv_d=None, inv_b=None, want_first=False, want_bi=False, stream=None):
         """fmx_fm_list_forward on B lists of G rows: S / sfirst / sbi / logit of the B G rows, and the softmax cross-entropy of
         every list against its first row and its dlogit in self.loss_b / self.dz (loss_b[G i] = loss_i, 0 in the negatives'
         slots).  -> B"""
+        return self._list_forward(hyper, idx_d, G, xv_d, None, inv_b, want_first, want_bi, stream)
+
+    def list_forward_q(self, hyper, idx_d, G, corr, xv_d=None, inv_b=None, want_first=False, want_bi=False, stream=None):
+        """fmx_fm_list_forward_q: list_forward with the softmax taken over logit - corr (corr fp32 [B G], log Q of every row's
+        item); self.logit and the sums stay the uncorrected forward's.  -> B"""
+        return self._list_forward(hyper, idx_d, G, xv_d, corr, inv_b, want_first, want_bi, stream)
+
+    def _list_forward(self, hyper, idx_d, G, xv_d, corr, inv_b, want_first, want_bi, stream):
         if idx_d.dim() != 2:
             raise ValueError(f"list rows must be [B G, F], got {tuple(idx_d.shape)}")
         B = self._n_lists(idx_d.shape[0], G)
         out = self._fwd_out(want_first, want_bi)
-        _lib.check(self.lib.fmx_fm_list_forward(self.table.c_struct(), hyper.ref(), idx_d.data_ptr(), _ptr(xv_d), B, int(G),
-                                                1.0 / B if inv_b is None else inv_b, C.byref(out), self._stream(stream)))
+        fn, q = (self.lib.fmx_fm_list_forward, ()) if corr is None else (self.lib.fmx_fm_list_forward_q, (self._corr(corr, idx_d.shape[:1]),))
+        _lib.check(fn(self.table.c_struct(), hyper.ref(), idx_d.data_ptr(), _ptr(xv_d), *q, B, int(G),
+                      1.0 / B if inv_b is None else inv_b, C.byref(out), self._stream(stream)))
         return B
 
     def list_step(self, hyper, rule, idx_d, G, xv_d=None, inv_b=None):
         """One list step on B lists of G rows (fmx_fm_list_step); the mean list loss lands in self.loss_out[0] (no sync here).
         The table's bias is not touched."""
+        self._list_step(hyper, rule, idx_d, G, xv_d, None, inv_b)
+
+    def list_step_q(self, hyper, rule, idx_d, G, corr, xv_d=None, inv_b=None):
+        """fmx_fm_list_step_q: list_step under the log-Q corrected loss (corr fp32 [B G], see list_forward_q)."""
+        self._list_step(hyper, rule, idx_d, G, xv_d, corr, inv_b)
+
+    def _list_step(self, hyper, rule, idx_d, G, xv_d, corr, inv_b):
         if idx_d.dim() != 2:
             raise ValueError(f"list rows must be [B G, F], got {tuple(idx_d.shape)}")
         B = self._n_lists(idx_d.shape[0], G)
         out = self._fwd_out(want_first=False, want_bi=False)
-        self._counted(self.lib.fmx_fm_list_step, (self.table.c_struct(), hyper.ref(), _lib.RULES[rule], idx_d.data_ptr(), _ptr(xv_d), B,
-                                                  int(G), 1.0 / B if inv_b is None else inv_b, self._list_ws.data_ptr(),
-                                                  self._list_ws.numel() * 4, C.byref(out), self.loss_out.data_ptr(), self._stream()), hyper)
+        fn, q = (self.lib.fmx_fm_list_step, ()) if corr is None else (self.lib.fmx_fm_list_step_q, (self._corr(corr, idx_d.shape[:1]),))
+        self._counted(fn, (self.table.c_struct(), hyper.ref(), _lib.RULES[rule], idx_d.data_ptr(), _ptr(xv_d), *q, B, int(G),
+                           1.0 / B if inv_b is None else inv_b, self._list_ws.data_ptr(), self._list_ws.numel() * 4, C.byref(out),
+                           self.loss_out.data_ptr(), self._stream()), hyper)
 
     def list_stream(self, hyper, rule, idx_pool, G, n_steps, loss_out=None):
         """n_steps list steps over a resident pool idx_pool [n_pool, B G, F] (fmx_fm_list_stream); loss_out [n_steps] or None."""
+        self._list_stream(hyper, rule, idx_pool, G, None, n_steps, loss_out)
+
+    def list_stream_q(self, hyper, rule, idx_pool, G, corr_pool, n_steps, loss_out=None):
+        """fmx_fm_list_stream_q: list_stream under the corrected loss, corr_pool fp32 [n_pool, B G] beside idx_pool."""
+        self._list_stream(hyper, rule, idx_pool, G, corr_pool, n_steps, loss_out)
+
+    def _list_stream(self, hyper, rule, idx_pool, G, corr_pool, n_steps, loss_out):
         n_pool, rows, F = idx_pool.shape
         assert F == self.table.n_fields and idx_pool.is_contiguous()
         _loss_cap(loss_out, n_steps)
         B = self._n_lists(rows, G)
         out = self._fwd_out(want_first=False, want_bi=False)
-        self._counted(self.lib.fmx_fm_list_stream, (self.table.c_struct(), hyper.ref(), _lib.RULES[rule], idx_pool.data_ptr(), n_pool, B,
-                                                    int(G), 1.0 / B, int(n_steps), self._list_ws.data_ptr(), self._list_ws.numel() * 4,
-                                                    C.byref(out), _ptr(loss_out), self._stream()), hyper, n_steps)
+        fn, q = ((self.lib.fmx_fm_list_stream, ()) if corr_pool is None
+                 else (self.lib.fmx_fm_list_stream_q, (self._corr(corr_pool, idx_pool.shape[:2]),)))
+        self._counted(fn, (self.table.c_struct(), hyper.ref(), _lib.RULES[rule], idx_pool.data_ptr(), *q, n_pool, B, int(G), 1.0 / B,
+                           int(n_steps), self._list_ws.data_ptr(), self._list_ws.numel() * 4, C.byref(out), _ptr(loss_out),
+                           self._stream()), hyper, n_steps)
+
+    def alias_sample(self, thresh, alias, logq, n_neg, n_try, own_pos=None, seed=0, offset=0, u_base=0, excl_offsets=None,
+                     excl_pos=None, U=None):
+        """fmx_alias_sample_negatives on this engine's stream: n_neg popularity-sampled negatives per row from the alias table
+        (thresh uint32 bits in an int32 tensor [N], alias int32 [N], logq fp32 [N] or None; fmx.pairwise.alias_table) ->
+        (neg_pos int32 [U, n_neg], -1 padded; neg_logq fp32 [U, n_neg], -inf padded, or None without logq).  U: own_pos's length
+        unless given.  No sync."""
+        from . import pairwise
+        return pairwise.alias_sample(thresh, alias, logq, n_neg, n_try, own_pos, seed, offset, u_base, excl_offsets, excl_pos, U,
+                                     stream=self._stream(), call=self._counted)
 
     def pair_online_run(self, hyper, rule, idx_d, xv_d=None, margin=0.0, want_logit=False, want_loss=False):
         """The online protocol on N device-resident pairs (fmx_fm_pair_online_run): per pair predict (z_pos > z_neg), then one

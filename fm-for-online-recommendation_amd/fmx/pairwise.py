@@ -10,6 +10,11 @@ HardNegatives carries the settings of that through the `negatives` argument of f
 
 Listwise (sampled-softmax) training (fmx_fm_list_*) takes the same positives and negatives as B lists of G = 1 + n_neg rows,
 [B G, F], the positive first: assemble_lists; FMEngine.list_step / list_stream take the result.
+
+Popularity-sampled negatives: alias_table builds Walker's alias table of a weight per candidate position on the host,
+alias_sample draws from it on the device (fmx_alias_sample_negatives) and returns log Q of every draw, which the corrected list
+calls (fmx_fm_list_*_q: FMEngine.list_step_q / list_stream_q) subtract from the logits.  PopularityNegatives carries the table and
+its settings through the `negatives` argument.
 """
 import torch
 
@@ -173,6 +178,147 @@ def hard_negatives(negatives):
             raise ValueError(f"negatives={negatives!r}: None (uniform), 'hard', a HardNegatives, or the negatives' item columns")
         return HardNegatives()
     return None
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# popularity-sampled negatives: draws in proportion to weights from an alias table, with log Q of every draw
+# (include/fmx.h, fmx_alias_sample_negatives; the corrected list loss that takes log Q: fmx_fm_list_*_q)
+# ---------------------------------------------------------------------------------------------------------------------------
+ALIAS_ONE = 1 << 24      # a cell's threshold is an integer in [0, 2^24]: the kernel compares the top 24 bits of a Philox word with it
+
+
+def alias_table(weights):
+    """Walker's alias table of non-negative weights [N] by Vose's construction in float64 -> (thresh uint32 [N] in [0, 2^24],
+    alias int32 [N], q float64 [N], logq float32 [N]).  A draw picks a cell p uniformly, then p with probability
+    thresh[p] / 2^24 and alias[p] otherwise, so position i is drawn with the REALISED probability
+        q_i = (thresh_i + sum_{j: alias_j = i} (2^24 - thresh_j)) / (N 2^24),
+    which differs from weights_i / sum(weights) by the 24-bit rounding of the thresholds; logq = log(q) of that q, not of the
+    weights (-inf where q = 0).  A zero-weight position has thresh = 0 and no alias entry pointing at it: it is never drawn.
+    Weights that are negative, non-finite or all zero raise ValueError."""
+    import numpy as np
+    w = np.asarray(torch.as_tensor(weights).detach().cpu() if torch.is_tensor(weights) else weights, dtype=np.float64).reshape(-1)
+    N = w.size
+    if N < 1 or not np.isfinite(w).all() or (w < 0).any() or not w.sum() > 0:
+        raise ValueError("alias_table: weights must be finite, non-negative and not all zero")
+    p = w * (N / w.sum())                                 # mean 1: a cell's own share of itself
+    thresh = np.full(N, ALIAS_ONE, dtype=np.int64)
+    alias = np.arange(N, dtype=np.int64)
+    small = [i for i in range(N) if p[i] < 1.0]
+    large = [i for i in range(N) if p[i] >= 1.0]
+    while small and large:
+        s, g = small.pop(), large[-1]
+        thresh[s], alias[s] = int(round(p[s] * ALIAS_ONE)), g
+        p[g] -= 1.0 - p[s]                                # the rest of cell s is g's
+        if p[g] < 1.0:
+            small.append(large.pop())
+    for s in small:                                       # (rounding leftovers: cells of share 1 up to float64 rounding)
+        if w[s] == 0:
+            raise ValueError("alias_table: the weights' float64 rounding left a zero-weight cell unpaired")
+    num = thresh.copy()
+    np.add.at(num, alias, ALIAS_ONE - thresh)
+    q = num / float(N * ALIAS_ONE)
+    with np.errstate(divide="ignore"):
+        logq = np.log(q).astype(np.float32)
+    return thresh.astype(np.uint32), alias.astype(np.int32), q, logq
+
+
+class PopularityNegatives:
+    """negatives=PopularityNegatives(weights, ...) of fit_lists / run_list_experiment / fit_pairs / run_pair_experiment: every
+    positive's n_neg negatives are drawn with replacement in proportion to weights ** power (fmx_alias_sample_negatives), never
+    the row's own item nor an excluded position.  weights holds one entry per candidate position: the whole item field (one item
+    field, candidates=None) or the rows of `candidates`.  correct=True: the list loss subtracts log Q(item) from every logit of
+    the list, the positive's included (fmx_fm_list_step_q) -- without it popular items are pushed down merely for being drawn
+    often; the pair loss has no correction and ignores `correct`.  exclude: per-row candidate positions never to return
+    (fmx.recommend.exclusions_csr).  n_try: draws per row, default max(64, 8 n_neg); a row with fewer than n_neg eligible draws
+    among them raises ValueError.  The table is built once (alias_table) and stays on the device across calls."""
+
+    def __init__(self, weights, power=1.0, correct=True, exclude=None, n_try=None):
+        w = torch.as_tensor(weights).detach().to("cpu", torch.float64).reshape(-1)
+        self.power, self.correct, self.exclude = float(power), bool(correct), exclude
+        self.n_try = None if n_try is None else int(n_try)
+        if self.n_try is not None and self.n_try < 1:
+            raise ValueError("PopularityNegatives: n_try must be >= 1")
+        self.thresh, self.alias, self.q, self.logq = alias_table(w.numpy() ** self.power)
+        self.N = int(w.numel())
+        self._on = {}
+
+    @classmethod
+    def from_counts(cls, column, size, power=0.75, **kw):
+        """The weights as the counts of an item column (torch.bincount over `size` items), under the word2vec power 0.75"""
+        counts = torch.bincount(torch.as_tensor(column).reshape(-1).long().cpu(), minlength=int(size))
+        if counts.numel() != int(size):
+            raise ValueError(f"PopularityNegatives.from_counts: an item index beyond size = {int(size)}")
+        return cls(counts, power=power, **kw)
+
+    def tries(self, n_neg):
+        return max(64, 8 * int(n_neg)) if self.n_try is None else self.n_try
+
+    def table(self, device):
+        """(thresh [N] -- the uint32 bits in an int32 tensor --, alias int32 [N], logq fp32 [N]) on `device`, copied once"""
+        key = str(device)
+        if key not in self._on:
+            self._on[key] = tuple(torch.from_numpy(a).to(device) for a in (self.thresh.view("int32"), self.alias, self.logq))
+        return self._on[key]
+
+    def floor_logq(self):
+        """log Q of a positive whose item the table never draws (q = 0, or no candidate position): log(2^-24 / N), below every
+        drawable position's"""
+        import math
+        return math.log(1.0 / (ALIAS_ONE * self.N))
+
+    def __getstate__(self):
+        return {k: v for k, v in self.__dict__.items() if k != "_on"}
+
+    def __setstate__(self, st):
+        self.__dict__.update(st)
+        self._on = {}
+
+
+def popularity_negatives(negatives):
+    """The PopularityNegatives behind a `negatives` argument, or None for every other value"""
+    return negatives if isinstance(negatives, PopularityNegatives) else None
+
+
+def alias_sample(thresh, alias, logq, n_neg, n_try, own_pos=None, seed=0, offset=0, u_base=0, excl_offsets=None, excl_pos=None,
+                 U=None, stream=None, call=None):
+    """The raw call of fmx_alias_sample_negatives: thresh (the uint32 bits in an int32 tensor) [N], alias int32 [N], logq fp32 [N]
+    or None, own_pos int32 [U] or None, all on one device.  U: own_pos's length unless given.  call(fn, args): who makes the
+    checked foreign call (FMEngine._counted; by default this function).  Returns (neg_pos int32 [U, n_neg], -1 padded; neg_logq
+    fp32 [U, n_neg], -inf padded, or None without logq) on the device; no sync."""
+    dev = thresh.device
+    U = int(own_pos.numel() if U is None else U)
+    n_neg = int(n_neg)
+    if own_pos is not None and (own_pos.dtype != torch.int32 or own_pos.numel() != U or not own_pos.is_contiguous()):
+        raise ValueError(f"own_pos: a contiguous int32 [U = {U}] device tensor")
+    shape = (max(U, 0), max(n_neg, 0))
+    neg_pos = torch.empty(shape, dtype=torch.int32, device=dev)
+    neg_logq = None if logq is None else torch.empty(shape, dtype=torch.float32, device=dev)
+    st = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
+
+    def ptr(t):
+        return None if t is None else t.data_ptr()
+
+    args = (thresh.data_ptr(), alias.data_ptr(), ptr(logq), thresh.numel(), ptr(excl_offsets), ptr(excl_pos), ptr(own_pos), U, n_neg,
+            int(n_try), int(seed) & (2 ** 64 - 1), int(offset) & (2 ** 64 - 1), int(u_base) & 0xFFFFFFFF, neg_pos.data_ptr(),
+            ptr(neg_logq), st)
+    fn = _lib.load().fmx_alias_sample_negatives
+    if call is None:
+        _lib.check(fn(*args))
+    else:
+        call(fn, args)
+    return neg_pos, neg_logq
+
+
+def candidate_positions(items, candidates):
+    """The position of each row of items [B, m] among the rows of candidates [N, m] (the lowest where a row is listed twice), -1
+    where it is none -> int64 [B] on items' device.  (fmx.recommend.Candidates.positions_of answers the same question for a
+    Candidates, whose construction scores every candidate row; the sampler scores nothing and has the items only.)"""
+    N = candidates.shape[0]
+    uniq, inv = torch.unique(torch.cat([candidates, items]), dim=0, return_inverse=True)
+    first = torch.full((uniq.shape[0],), N, dtype=torch.int64, device=items.device)
+    first.scatter_reduce_(0, inv[:N], torch.arange(N, dtype=torch.int64, device=items.device), reduce="amin")
+    pos = first[inv[N:]]
+    return torch.where(pos == N, torch.full_like(pos, -1), pos)
 
 
 def fm_mine_negatives(Su, au, Sc, ac, n_draw, n_neg=1, own_pos=None, seed=0, offset=0, u_base=0, excl_offsets=None, excl_pos=None,

@@ -1,5 +1,6 @@
-"""Ranking training of the model classes, defined once: pairs (BPR: fmx_fm_pair_*), lists (sampled softmax: fmx_fm_list_*) and
-mined negatives (fmx_fm_mine_negatives).
+"""Ranking training of the model classes, defined once: pairs (BPR: fmx_fm_pair_*), lists (sampled softmax: fmx_fm_list_*, and
+its log-Q corrected form fmx_fm_list_*_q), mined negatives (fmx_fm_mine_negatives) and popularity-sampled ones
+(fmx_alias_sample_negatives).
 
 RankingTraining is a mixin of OnlineFMBase (FMAdam, the DeepFM / NFM classes) and of AFMAdam.  It holds the pure FM's public
 methods, and what the three families share under them: the rows of positives and negatives, the host predict-then-fit loop, the
@@ -55,14 +56,17 @@ class RankingTraining:
         return self._negative_rows(fmx.pairwise.assemble_pairs, Xi, Xv, item_fields, negatives, n_neg, candidates, generator)
 
     def _negative_rows(self, assemble, Xi, Xv, item_fields, negatives, n_neg, candidates, generator):
-        """The positives with their negatives -- given, mined ("hard" / a HardNegatives) or drawn uniformly (None) -- laid out by
-        `assemble` (fmx.pairwise.assemble_pairs / assemble_lists)"""
+        """The positives with their negatives -- given, mined ("hard" / a HardNegatives), drawn by popularity (a
+        PopularityNegatives) or drawn uniformly (None) -- laid out by `assemble` (fmx.pairwise.assemble_pairs / assemble_lists)"""
         idx_d, xv_d, _ = self._inputs(Xi, Xv)
         fields = self._item_fields(item_fields)
         hard = fmx.pairwise.hard_negatives(negatives)
         if hard is not None:
             negatives, _ = self.mine_negatives(idx_d, xv_d, fields, hard.n_draw, n_neg=n_neg, candidates=candidates,
                                                exclude=hard.exclude, generator=generator, refresh_every=hard.refresh_every)
+        popular = fmx.pairwise.popularity_negatives(negatives)
+        if popular is not None:
+            negatives, _ = self._sample_popular(idx_d, fields, popular, n_neg, candidates, generator)
         if negatives is None:
             src = candidates if candidates is not None else [self.feature_sizes[f] for f in fields]
             negatives = fmx.pairwise.sample_negatives(idx_d, fields, src, n_neg=n_neg, generator=generator)
@@ -138,7 +142,9 @@ class RankingTraining:
         (fmx.pairwise.sample_negatives) from `candidates` ([N, m] items) or, by default, from the item fields' vocabularies --
         never the row's own item, deterministic under a seeded `generator`.
         negatives="hard" (or a fmx.pairwise.HardNegatives carrying n_draw = 32, exclude, refresh_every = 1): every positive's
-        n_neg negatives are mined by mine_negatives -- the best of n_draw drawn candidates under the current FM score."""
+        n_neg negatives are mined by mine_negatives -- the best of n_draw drawn candidates under the current FM score.
+        negatives=fmx.pairwise.PopularityNegatives(weights, ...): n_neg draws per positive in proportion to weights ** power
+        (fmx_alias_sample_negatives); the pair loss has no log-Q correction, so its `correct` is ignored here."""
         if self._logit_family != "fm":
             self._refuse_hard_negatives("fit_pairs", negatives)
         self._pure_fm_only("fit_pairs")
@@ -204,14 +210,24 @@ class RankingTraining:
         does.  Every positive of Xi / Xv [B, F] and its negatives form one list; the loss is -log softmax of the positive's
         logit among the list's.  negatives: what fit_pairs takes -- the negatives' item columns [B, n_neg, m] ([B, m]: one each),
         None for n_neg uniform draws per positive, "hard" or a fmx.pairwise.HardNegatives for the n_neg best of n_draw drawn
-        candidates under the current FM score (mine_negatives).  At most 15 negatives per positive.  The bias does not move."""
+        candidates under the current FM score (mine_negatives).  At most 15 negatives per positive.  The bias does not move.
+        negatives=fmx.pairwise.PopularityNegatives(weights, ...): n_neg draws per positive in proportion to weights ** power
+        (fmx_alias_sample_negatives); with its correct=True (the default) the step is fmx_fm_list_step_q -- log Q of every row's
+        item, the positive's included, is subtracted from the row's logit in front of the softmax."""
         self._pure_fm_only("fit_lists", "list")
-        if negatives is None or fmx.pairwise.hard_negatives(negatives) is not None:
+        popular = fmx.pairwise.popularity_negatives(negatives)
+        if negatives is None or fmx.pairwise.hard_negatives(negatives) is not None or popular is not None:
             self._list_limit("fit_lists", n_neg)
         self.train()
         idx_d, xv_d, _ = self._inputs(Xi, Xv)
+        corr = None
+        if popular is not None and popular.correct:
+            negatives, corr = self._sample_popular(idx_d, self._item_fields(item_fields), popular, n_neg, candidates, generator)
         rows, xv, G = self._list_rows("fit_lists", idx_d, xv_d, item_fields, negatives, n_neg, candidates, generator)
-        self._engine.list_step(self._hyper, self.update_rule, rows, G, xv)
+        if corr is None:
+            self._engine.list_step(self._hyper, self.update_rule, rows, G, xv)
+        else:
+            self._engine.list_step_q(self._hyper, self.update_rule, rows, G, corr.reshape(-1), xv)
         out = self._engine.loss_out[0].clone()
         self._after_step()
         return out
@@ -223,10 +239,12 @@ class RankingTraining:
         negatives: what fit_lists takes; at most 15 per positive.  On the device (fmx_fm_list_online_run: one workgroup walks the
         stream) where run_experiment's loop runs there and the table has no sort split; otherwise a loop over fit_lists on one
         list at a time -- the same bits.  negatives="hard" (or a fmx.pairwise.HardNegatives): blocks of remine_every positives,
-        as run_pair_experiment walks them."""
+        as run_pair_experiment walks them.  negatives=fmx.pairwise.PopularityNegatives(...): the host loop of one-list fit_lists
+        calls, each drawing its own negatives; the rank is read from the step's uncorrected logits (the serving score)."""
         self._pure_fm_only("run_list_experiment", "list")
         hard = fmx.pairwise.hard_negatives(negatives)
-        if negatives is None or hard is not None:
+        popular = fmx.pairwise.popularity_negatives(negatives)
+        if negatives is None or hard is not None or popular is not None:
             self._list_limit("run_list_experiment", n_neg)
         start = time()
         self.train()
@@ -235,6 +253,9 @@ class RankingTraining:
             return self._list_loop(idx, xv, item_fields, negs, n_neg, candidates, generator)
         if hard is not None:
             ranks = self._walk_mined_blocks(Xi, Xv, hard, walk)
+        elif popular is not None:
+            idx_d, xv_d, _ = self._inputs(Xi, Xv)
+            ranks = [self._popular_list_loop(idx_d, xv_d, item_fields, popular, n_neg, candidates, generator)]
         else:
             idx_d, xv_d, _ = self._inputs(Xi, Xv)
             ranks = [walk(idx_d, xv_d, negatives)]
@@ -257,8 +278,79 @@ class RankingTraining:
             self.fit_lists(lst[:1], None if xv is None else xv[G * i:G * i + 1], fields, negatives=lst[1:, fields].reshape(1, G - 1, -1))
         return self._host_stream_loop(n, fit_one, lambda: (e.logit[1:G] >= e.logit[0]).sum())
 
-    # ---- hard negatives (fmx.pairwise.mine_negatives, fmx_fm_mine_negatives) ----
-    mining_seed = 0      # the Philox seed of mine_negatives when no generator is given
+    def _popular_list_loop(self, idx_d, xv_d, item_fields, popular, n_neg, candidates, generator):
+        """The predict-then-fit loop under popularity-sampled negatives: one fit_lists call per positive, which draws that list's
+        negatives (the sampler's exclusions cut to the row) -> the positives' ranks uint8 [n] on the device (None: no list)"""
+        n, e, G = idx_d.shape[0], self._engine, 1 + int(n_neg)
+        if n == 0:
+            return None
+        whole = popular.exclude
+        off, pos = fmx.recommend.exclusions_csr(whole, n, "cpu")
+
+        def fit_one(i):
+            if off is not None:
+                popular.exclude = (off[i:i + 2] - off[i], pos[int(off[i]):int(off[i + 1])])
+            self.fit_lists(idx_d[i:i + 1], None if xv_d is None else xv_d[i:i + 1], item_fields, negatives=popular, n_neg=n_neg,
+                           candidates=candidates, generator=generator)
+        try:
+            return self._host_stream_loop(n, fit_one, lambda: (e.logit[1:G] >= e.logit[0]).sum())
+        finally:
+            popular.exclude = whole
+
+    def _refuse_corrected_lists(self, method, negatives):
+        """The list steps outside the pure FM have no corrected form (fmx_fm_list_*_q is the pure FM's): a PopularityNegatives
+        with correct=True is refused there by name"""
+        popular = fmx.pairwise.popularity_negatives(negatives)
+        if popular is not None and popular.correct and self._logit_family != "fm":
+            raise NotImplementedError(f"{self._name}.{method}: the log-Q corrected list loss is built for the pure FM logit (FMAdam; "
+                                      "fmx_fm_list_step_q); pass PopularityNegatives(..., correct=False) to train this class on "
+                                      "popularity-sampled negatives without the correction")
+
+    # ---- hard negatives (fmx.pairwise.mine_negatives, fmx_fm_mine_negatives) and the seeds of every device-side draw ----
+    mining_seed = 0      # the Philox seed of mine_negatives and of the popularity sampler when no generator is given
+
+    def _next_draw(self, generator):
+        """(seed, offset) of the next mining or sampling call: generator.initial_seed() or mining_seed, and the model's count of
+        such calls, which pickling carries"""
+        seed = int(generator.initial_seed()) if generator is not None else int(self.mining_seed)
+        offset = int(getattr(self, "_mining_offset", 0))
+        self._mining_offset = offset + 1
+        return seed, offset
+
+    def _sample_popular(self, idx_d, fields, popular, n_neg, candidates, generator):
+        """n_neg popularity-sampled negatives for every positive row of idx_d [B, F] (fmx_alias_sample_negatives under _next_draw's
+        seed and offset): never the row's own item nor one of popular.exclude's positions -> (items int64 [B, n_neg, m] in the
+        order of fields, what fit_pairs takes as negatives; log Q fp32 [B, 1 + n_neg] of every list row's item, the positive's
+        first -- a positive the table never draws takes log(2^-24 / N)).  candidates: [N, m] items (None: every row of the one
+        item field); popular's weights hold one entry per such position.  A row with fewer than n_neg eligible draws among its
+        n_try raises ValueError (one host read per call, as in mine_negatives)."""
+        pw, dev, B, m = fmx.pairwise, self.device, idx_d.shape[0], len(fields)
+        items = idx_d[:, fields].long()
+        if candidates is None:
+            if m != 1:
+                raise ValueError("candidates=None needs exactly one item field: the product of several fields' vocabularies "
+                                 "cannot be enumerated -- pass the candidate items [N, m]")
+            cand, N, own = None, int(self.feature_sizes[fields[0]]), items[:, 0]
+        else:
+            cand = torch.as_tensor(candidates).to(device=dev, dtype=torch.int64).reshape(-1, m)
+            N, own = cand.shape[0], pw.candidate_positions(items, cand)
+        if popular.N != N:
+            raise ValueError(f"{self._name}: PopularityNegatives holds {popular.N} weights for {N} candidate positions")
+        thresh, alias, logq = popular.table(dev)
+        off, pos = fmx.recommend.exclusions_csr(popular.exclude, B, dev)
+        seed, offset = self._next_draw(generator)
+        n_try = popular.tries(n_neg)
+        neg_pos, neg_logq = pw.alias_sample(thresh, alias, logq, n_neg, n_try, own.to(torch.int32).contiguous(), seed, offset, 0,
+                                            off, pos)
+        if bool((neg_pos < 0).any()):
+            raise ValueError(f"{self._name}: a row has fewer than {int(n_neg)} eligible draws among its n_try = {n_try} (the others "
+                             "were its own item or excluded): raise PopularityNegatives(n_try=...) up to 1024")
+        at = neg_pos.long()
+        neg_items = at.unsqueeze(-1) if cand is None else cand[at.reshape(-1)].reshape(B, int(n_neg), m)
+        listed = (own >= 0) & (own < N)
+        own_logq = torch.where(listed, logq[own.clamp(0, N - 1)], torch.full_like(neg_logq[:, 0], float("-inf")))
+        corr = torch.cat([own_logq.clamp(min=popular.floor_logq())[:, None], neg_logq], dim=1).contiguous()
+        return neg_items, corr
 
     def _mining_candidates(self, fields, candidates, refresh_every):
         """The fmx.recommend.Candidates of the last (item_fields, candidates), kept on the model and refreshed from the table
@@ -299,9 +391,7 @@ class RankingTraining:
         fields = self._item_fields(item_fields)
         cands = self._mining_candidates(fields, candidates, refresh_every)
         own = cands.positions_of(idx_d[:, fields], fields)
-        seed = int(generator.initial_seed()) if generator is not None else int(self.mining_seed)
-        offset = int(getattr(self, "_mining_offset", 0))
-        self._mining_offset = offset + 1
+        seed, offset = self._next_draw(generator)
         pos, score = fmx.pairwise.mine_negatives(self._table, cands, idx_d, xv_d, own, int(n_draw), int(n_neg), seed=seed,
                                                  offset=offset, exclude=exclude, hyper=self._hyper)
         missing = pos < 0

@@ -253,11 +253,13 @@ class AFMAdam(RankingTraining, nn.Module):
     # ---- listwise (sampled-softmax) training on the attentional logit (fmx_afm_list_*; the list objective of FMAdam) ----
     def _list_entry(self, method, negatives, n_neg, attention):
         """What fit_lists / run_list_experiment decide before they look at the model: without attention the pure FM's refusal,
-        first; then the limit of negatives, then the mined negatives' refusal."""
+        first; then the limit of negatives, then the mined negatives' refusal, then the corrected list loss's (a
+        PopularityNegatives with correct=True: this model's list kernels have no log-Q correction)."""
         self._pair_refusal(method, attention, "list")
-        if negatives is None or fmx.pairwise.hard_negatives(negatives) is not None:
+        if negatives is None or fmx.pairwise.hard_negatives(negatives) is not None or fmx.pairwise.popularity_negatives(negatives) is not None:
             self._list_limit(method, n_neg)
         self._refuse_hard_negatives(method, negatives)
+        self._refuse_corrected_lists(method, negatives)
 
     def fit_lists(self, Xi, Xv, item_fields, negatives=None, n_neg=4, candidates=None, generator=None, attention=False):
         """FMAdam.fit_lists's arguments; attention=True: one mini-batch list step of the whole model (tables and attention) on

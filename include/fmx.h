@@ -433,7 +433,7 @@ int fmx_fm_pair_online_run(const fmx_table_t *table, const fmx_hyper_t *hyper, i
  * loss and dz are finite for every finite set of logits (the max is subtracted: exp's argument is <= 0 and s >= 1); every lane
  * of a list evaluates the same operands in the same order, so a list's result depends on its logits and G alone, never on its
  * place in the batch or the launch's geometry.  At G = 2 this is BPR (fmx_fm_pair_forward under margin 0) in other arithmetic.  No
- * labels are read; there is no temperature and no log-Q correction.
+ * labels are read; there is no temperature.  The log-Q correction for negatives that were not drawn uniformly: fmx_fm_list_*_q below.
  * The bias: a softmax does not move under a shift of all its logits, so the bias has no gradient, and the contract is the pair
  * family's -- a list step leaves the bias and its state (z / n, moments) BIT-UNCHANGED under every rule.  The dz of a list sum to
  * zero only up to rounding, so the step does not rely on the sum: the update's bias rule runs on 16 scratch bytes behind the
@@ -482,6 +482,31 @@ int fmx_fm_list_step(const fmx_table_t *table, const fmx_hyper_t *hyper, int32_t
 int fmx_fm_list_stream(const fmx_table_t *table, const fmx_hyper_t *hyper, int32_t rule, const int32_t *idx_pool, int32_t n_pool,
                        int32_t B_lists, int32_t G, float inv_b, int32_t n_steps, void *workspace, int64_t workspace_bytes,
                        const fmx_fwd_out_t *fwd, float *loss_out, fmx_stream_t stream);
+
+/* ---- the log-Q corrected list loss: sampled softmax under negatives that were not drawn uniformly ----
+ * fmx_fm_list_forward / _step / _stream with one more array: corr [B_lists G] fp32 (the stream: corr_pool [n_pool, B_lists G], step
+ * s reading the rows of batch s mod n_pool), one value per row, typically log Q(item of the row) of the sampler that drew the
+ * negatives (fmx_alias_sample_negatives' neg_logq; the positive's item included).  With
+ *     c_j = z_j - corr[G i + j]                    one fp32 subtraction per row
+ * the loss and dz are the list family's formulas above with c in the place of z: m = max_j c_j, e_j = exp(c_j - m),
+ * s = e_0 + ... + e_{G-1} added in that order, loss_i = log(s) - (c_0 - m), dz_j = (e_j / s) inv_b, dz_0 = minus the negatives'
+ * mass times inv_b.  Without the correction an item is pushed down merely for being drawn often (Bengio & Senecal 2008; Yi et al.
+ * 2019).  out->logit, S, bi, first, sfirst and sbi stay those of the UNCORRECTED forward, bit for bit: the logit is the serving score.
+ * corr must be finite (the caller's contract; nothing checks it on the device).  A null corr / corr_pool is FMX_ERR_ARG.  Every other
+ * refusal, the workspace (fmx_fm_list_workspace_bytes), the scratch the bias rule runs on and the bit-unchanged bias are the list
+ * family's: the same host code.  With corr all +0 every output and the table are bit-identical to the uncorrected call (z - 0 is z).
+ * The correction rides where the pointwise objective's label rides (one 4-byte load per row in the forward); nothing else of the
+ * step changes.  fmx_fm_list_online_run has no corrected form.
+ * Replaces: torch.log_softmax(z - log_q) on assembled rows and autograd through it; nothing in the reference, which has no listwise
+ * loss and takes its negatives as given (meta_fm.py:145-169). */
+int fmx_fm_list_forward_q(const fmx_table_t *table, const fmx_hyper_t *hyper, const int32_t *idx, const float *xv, const float *corr,
+                          int32_t B_lists, int32_t G, float inv_b, const fmx_fwd_out_t *out, fmx_stream_t stream);
+int fmx_fm_list_step_q(const fmx_table_t *table, const fmx_hyper_t *hyper, int32_t rule, const int32_t *idx, const float *xv,
+                       const float *corr, int32_t B_lists, int32_t G, float inv_b, void *workspace, int64_t workspace_bytes,
+                       const fmx_fwd_out_t *fwd, float *loss_out, fmx_stream_t stream);
+int fmx_fm_list_stream_q(const fmx_table_t *table, const fmx_hyper_t *hyper, int32_t rule, const int32_t *idx_pool,
+                         const float *corr_pool, int32_t n_pool, int32_t B_lists, int32_t G, float inv_b, int32_t n_steps,
+                         void *workspace, int64_t workspace_bytes, const fmx_fwd_out_t *fwd, float *loss_out, fmx_stream_t stream);
 
 /* The online predict-then-fit protocol restated for lists, on N device-resident lists idx [N G, F] (row G i the positive of list i,
  * as above; xv of the same shape, or null: every value 1).  For every list, with the weights BEFORE the list's update:
@@ -1298,6 +1323,38 @@ int fmx_fm_mine_negatives(const float *Su, int32_t ld_u, const float *au, int32_
                           int32_t N, int32_t kp, const int32_t *excl_offsets, const int32_t *excl_pos, const int32_t *own_pos,
                           int32_t n_draw, int32_t n_neg, uint64_t seed, uint64_t offset, uint32_t u_base, int32_t *neg_pos,
                           float *neg_score, fmx_stream_t stream);
+
+/* ---- popularity-sampled negatives: draws from an alias table, with log Q of every draw (fmx/pairwise.py) ----
+ * Replaces: torch.multinomial(weights, n_neg, replacement=True) per batch, a redraw loop for the rows that drew their own item
+ * (one count read back per round) and a gather of log q; the reference has no counterpart (meta_fm.py:145-169 takes its negatives
+ * as given).  The cheap middle between uniform negatives, nearly all trivial on a long-tailed catalogue, and mined ones
+ * (fmx_fm_mine_negatives), which cost a scoring pass.
+ * Table (Walker's alias method, built on the host: fmx.pairwise.alias_table).  thresh [N] uint32 in [0, 2^24], alias [N] int32 in
+ * [0, N), logq [N] fp32: the log of the REALISED probability of each position,
+ *     q_i = (thresh_i + sum_{j: alias_j = i} (2^24 - thresh_j)) / (N 2^24),
+ * or null (then neg_logq must be null too).
+ * Draws.  Draw t (0 <= t < n_try) of row u takes two words of one Philox4x32-10 block (fmx_fm_mine_negatives' multipliers and Weyl
+ * constants) with
+ *     key     = (seed & 0xffffffff, seed >> 32)
+ *     counter = (offset & 0xffffffff, offset >> 32, (u_base + u) mod 2^32, 0x80000000 + (t >> 1))
+ *     a = word 2 (t & 1),  b = word 2 (t & 1) + 1,  p = (uint64(a) * N) >> 32,  position = (b >> 8) < thresh[p] ? p : alias[p]
+ * The high bit of the fourth counter word keeps these streams apart from fmx_fm_mine_negatives' under the same (seed, offset).  p is
+ * uniform over [0, N) up to the bias of at most N / 2^32 per position stated above; q is the law of a draw up to that bias.
+ * Eligibility.  A draw is eligible when its position is not own_pos[u] (int32 [U] or null; -1: none), is not in the row's exclusion
+ * list (excl_offsets [U + 1] / excl_pos: CSR as fmx_fm_topk takes it, each row's list ascending), and lies in [0, N): a corrupt alias
+ * entry is dropped, never dereferenced.  Sampling is WITH replacement: a position drawn twice is returned twice.
+ * Result.  Row u holds its first n_neg eligible draws in the order of t: neg_pos [U, n_neg] int32 padded with -1, neg_logq
+ * [U, n_neg] fp32 = logq[position] padded with -inf (or null).  A row's result depends on (seed, offset, u_base + u, N, the table,
+ * its own and excluded positions, n_neg, n_try) only -- not on U, nor on how a batch is cut into calls.
+ * Limits, all decided on the host before the launch: U, N, n_neg >= 1, n_neg <= n_try, non-null thresh / alias / neg_pos, neg_logq
+ * only with logq, excl_offsets and excl_pos together, else FMX_ERR_ARG; n_neg <= 16 and n_try <= 1024, else FMX_ERR_UNSUPPORTED.
+ * One launch (a wavefront per row: in round r lane l evaluates draw 64 r + l, a ballot and a lane prefix count keep the eligible
+ * draws in draw order; at most n_try / 64 rounds, no retry loop), no LDS, no atomics, asynchronous on `stream`, safe under graph
+ * capture; the result is identical run to run. */
+int fmx_alias_sample_negatives(const uint32_t *thresh, const int32_t *alias, const float *logq, int32_t N,
+                               const int32_t *excl_offsets, const int32_t *excl_pos, const int32_t *own_pos, int32_t U,
+                               int32_t n_neg, int32_t n_try, uint64_t seed, uint64_t offset, uint32_t u_base,
+                               int32_t *neg_pos, float *neg_logq, fmx_stream_t stream);
 
 /* Streaming read of `bytes` (multiple of 16) with 16-byte loads; sink [1] receives a checksum so the loads stay
  * live.  Used by bench.py to measure the HBM-read ceiling on the same GPU in the same run. */
