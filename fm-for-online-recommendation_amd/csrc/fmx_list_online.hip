@@ -1,23 +1,21 @@
 // fmx_list_online.hip -- k_fm_list_online: the pure FM's online LIST loop (predict the positive's rank among its negatives, then
 // one list step on that list) in one workgroup (fmx_fm_list_online_run; the checks are list_online_call in fmx_list.inc, which
-// reaches this unit through list_online_launch, fmx_host.h).
+// reaches this unit through list_online_launch, fmx_host.h).  The prefetch of the next list's rows and the forward from registers
+// are the pieces of fmx_walk.inc the other walkers use; the gather through LDS-held offsets and the run sums are this kernel's own.
 
 #include "fmx_host.h"
 
 namespace {
 
+#include "fmx_walk.inc"
+
 struct ListOnlineArgs {
-  float *rows;
-  const int64_t *foff;
-  const float *bias;   // read once, never written: a list step leaves the bias and its state alone (fmx_list.inc)
-  const int32_t *idx;  // [N G, F]: row G i the positive of list i, rows G i + 1 .. G i + G - 1 its negatives
-  const float *xv;     // [N G, F] or null
+  WalkTable t;         // idx, xv: [N G, F], row G i the positive of list i, rows G i + 1 .. G i + G - 1 its negatives.  bias: read once,
+                       // never written -- a list step leaves the bias and its state alone (fmx_list.inc)
   uint8_t *rank;       // [N] negatives of list i whose logit is >= the positive's, BEFORE the list's update
   float *logit;        // [N G] or null
   float *loss;         // [N] or null
-  int32_t *error;
-  fmx_hyper_t h;
-  int32_t N, G, F, stride, zoff;
+  int32_t G;
 };
 
 // the terms one occurrence adds to its run's sums, as update_body carries them for the pure FM: cV, and the scalars (cA, cw)
@@ -110,7 +108,6 @@ struct PlainSum {
 
 // lane j's value for a wave-uniform j: a lane read into a scalar register, no LDS round trip
 __device__ __forceinline__ float lane_f(float x, int j) { return __uint_as_float(__builtin_amdgcn_readlane(__float_as_uint(x), j)); }
-__device__ __forceinline__ float uniform_f(float x) { return __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(x))); }
 
 // ------------------------------------------------------------------------------------------------------------
 // k_fm_list_online: k_fm_online for lists (the sampled-softmax loss of fmx_list.inc)
@@ -131,7 +128,8 @@ __device__ __forceinline__ float uniform_f(float x) { return __uint_as_float(__b
 // weights layout's part of the row -- and the fit requests a field's whole row again right before it counts the field's run: the
 // bits the gather would have loaded (within a list a row is written by its run's head alone), an L2 hit under the count.
 template <int LPR, int LAYOUT, int RULE, int NP, int WAVES>
-__global__ __launch_bounds__(64 * WAVES) void k_fm_list_online(ListOnlineArgs a) {
+__global__ __launch_bounds__(64 * WAVES) void k_fm_list_online(ListOnlineArgs la) {
+  const WalkTable &a = la.t;
   constexpr bool LATE = WAVES > 8 && LAYOUT != FMX_LAYOUT_WEIGHTS;
   constexpr int SLOTS = WAVE / LPR, MAXF = NP * SLOTS, MAXG = 16;
   constexpr int kp = LPR * 4;
@@ -142,34 +140,17 @@ __global__ __launch_bounds__(64 * WAVES) void k_fm_list_online(ListOnlineArgs a)
   __shared__ int64_t foff_lds[MAXF + 1];  // the fields' first rows, read where a row's address is formed instead of held in registers
   const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);  // (w: wave-uniform, in a scalar register)
   const int slot = lane / LPR, q = lane % LPR;
-  const int G = a.G;
+  const int G = la.G;
   const float bias_w = bias_weight<LAYOUT>(a.bias[0], LAYOUT != FMX_LAYOUT_WEIGHTS ? a.bias[1] : 0.f, a.h);
   bool live[NP];
 #pragma unroll
   for (int p = 0; p < NP; ++p) live[p] = p * SLOTS + slot < a.F;
   for (int f = threadIdx.x; f <= MAXF; f += blockDim.x) foff_lds[f] = a.foff[f < a.F ? f : a.F];
   __syncthreads();
-  // this wave's row of the next list.  Branch-free, as in k_fm_online
-  uint32_t li_n[NP];
-  float x_n[NP];
-  const float *xsrc = a.xv ? a.xv : reinterpret_cast<const float *>(a.idx);
-  const bool has_x = a.xv != nullptr;
-  auto fetch_inputs = [&](int i) {
-    const bool in = i < a.N;
-    uint32_t l_[NP];
-    float x_[NP];
-#pragma unroll
-    for (int p = 0; p < NP; ++p) {
-      const size_t o = (live[p] && in) ? ((size_t)G * i + w) * a.F + p * SLOTS + slot : (size_t)0;
-      l_[p] = (uint32_t)a.idx[o];
-      x_[p] = xsrc[o];
-    }
-#pragma unroll
-    for (int p = 0; p < NP; ++p) {
-      li_n[p] = (live[p] && in) ? l_[p] : 0u;
-      x_n[p] = (has_x && live[p] && in) ? x_[p] : 1.f;
-    }
-  };
+  // this wave's row of the next list
+  const WalkX xs = walk_x(a);
+  WalkInputs<1, NP> next;
+  auto fetch_inputs = [&](int i) { walk_fetch<LPR>(next, a, xs, live, slot, i < a.N, [&](int) { return (size_t)G * i + w; }, [] {}); };
   fetch_inputs(0);
   bool bad = false;
   for (int i = 0; i < a.N; ++i) {
@@ -179,30 +160,17 @@ __global__ __launch_bounds__(64 * WAVES) void k_fm_list_online(ListOnlineArgs a)
     bool ok[NP];
 #pragma unroll
     for (int p = 0; p < NP; ++p) {
-      li[p] = li_n[p];
-      x[p] = x_n[p];
+      li[p] = next.li[0][p];
+      x[p] = next.x[0][p];
       const int64_t lo = foff_lds[p * SLOTS + slot];
       ok[p] = live[p] && li[p] < (uint32_t)(foff_lds[p * SLOTS + slot + 1] - lo);
       row[p] = load_row_sc1<LATE ? FMX_LAYOUT_WEIGHTS : LAYOUT, RULE>(a.rows + (size_t)(ok[p] ? lo + li[p] : 0) * a.stride, q, kp, a.zoff);
       bad = bad || (live[p] && !ok[p]);
     }
     fetch_inputs(i + 1);  // independent of the weights: in flight while this list is processed
-    // ---- forward of this wave's row: the arithmetic of k_fm_forward ----
-    float4 s = splat(0.f), ss = splat(0.f);
-    float fo = 0.f;
-#pragma unroll
-    for (int p = 0; p < NP; ++p) {
-      if (ok[p]) {
-        const float4 e = x[p] * row[p].v;
-        s = s + e;
-        ss = ss + e * e;
-        fo += row[p].fo.x * x[p];
-      }
-    }
-    fm_field_sums<LPR>(s, ss, fo, lane);
-    float sbi;
-    fm_bi<LPR>(s, ss, sbi);
-    fo = __shfl(fo, 0);
+    float4 s;
+    float sbi, fo;
+    walk_forward<LPR>(row, x, ok, lane, s, sbi, fo);  // this wave's row
     const float z = fo + sbi + bias_w;
     if (lane == 0) z_lds[w] = z;
     if (lane < LPR) *reinterpret_cast<float4 *>(&S_lds[w][4 * q]) = s;
@@ -227,12 +195,12 @@ __global__ __launch_bounds__(64 * WAVES) void k_fm_list_online(ListOnlineArgs a)
     list_loss_dz_of([&](int j) { return z_lds[j]; }, z_lds[pj], pj, G, 1.0f, loss, dz_all);
     const float dz = lane_f(dz_all, w);
     if (w == 0) {
-      if (a.logit && lane < G) a.logit[(size_t)G * i + lane] = z_lds[lane];
+      if (la.logit && lane < G) la.logit[(size_t)G * i + lane] = z_lds[lane];
       if (lane == 0) {
         int r = 0;
         for (int j = 1; j < G; ++j) r += z_lds[j] >= z_lds[0] ? 1 : 0;
-        a.rank[i] = (uint8_t)r;
-        if (a.loss) a.loss[i] = loss;
+        la.rank[i] = (uint8_t)r;
+        if (la.loss) la.loss[i] = loss;
       }
     }
     // ---- fit: k_fm_update on the G rows of the list (fmx_fm_list_step with B_lists = 1, inv_b = 1) ----
@@ -322,11 +290,10 @@ __global__ __launch_bounds__(64 * WAVES) void k_fm_list_online(ListOnlineArgs a)
 
 template <int LPR, int LAYOUT, int RULE>
 void launch_list_online_np(const ListOnlineArgs &a, int np, hipStream_t st) {
-  auto launch = [&](auto NP) {
+  with_walk_np(np, [&](auto NP) {
     if (a.G <= 8) hipLaunchKernelGGL((k_fm_list_online<LPR, LAYOUT, RULE, NP, 8>), dim3(1), dim3(64 * a.G), 0, st, a);
     else hipLaunchKernelGGL((k_fm_list_online<LPR, LAYOUT, RULE, NP, 16>), dim3(1), dim3(64 * a.G), 0, st, a);
-  };
-  if (!with_one_of<1, 2, 3>(np, launch)) launch(std::integral_constant<int, 4>{});
+  });
 }
 
 }  // namespace
@@ -336,22 +303,12 @@ namespace fmxd {
 int list_online_launch(const fmx_table_t *table, const fmx_hyper_t *hyper, int32_t rule, const int32_t *idx, const float *xv, int32_t N,
                        int32_t G, uint8_t *rank_out, float *logit_out, float *loss_out, int32_t *error, hipStream_t st) {
   ListOnlineArgs a;
-  a.rows = table->rows;
-  a.foff = table->field_offsets;
-  a.bias = table->bias;
-  a.idx = idx;
-  a.xv = xv;
+  a.t = walk_table(table, hyper, rule, idx, xv, error, N);
   a.rank = rank_out;
   a.logit = logit_out;
   a.loss = loss_out;
-  a.error = error;
-  a.h = kernel_hyper(hyper, rule);  // ADAM: the kernel derives each list's constants from lr, beta1, beta2, step
-  a.N = N;
   a.G = G;
-  a.F = table->n_fields;
-  a.stride = table->row_stride;
-  a.zoff = table->z_offset;
-  const int slots = WAVE / lpr_of(table->kp), np = (table->n_fields + slots - 1) / slots;
+  const int np = walk_passes(table);
   with_lpr(table->kp, [&](auto LPR) { with_rule(rule, [&](auto LAYOUT, auto RULE) { launch_list_online_np<LPR, LAYOUT, RULE>(a, np, st); }); });
   return check_launch("k_fm_list_online");
 }

@@ -1,314 +1,136 @@
 // fmx_online.hip -- the stream walkers, one wavefront or one workgroup walking a device-resident stream sample by sample (predict,
 // then fit on that sample), and their C ABI: k_fm_online (fmx_fm_online_run), k_fm_pair_online (fmx_fm_pair_online_run), k_mlp_small
 // (fmx_mlp_forward / _fit / _fit_opt / _hedge_fit), k_mlp_small_pair (fmx_mlp_pair_fit), k_online_mlp (fmx_online_run_mlp / _opt) and
-// k_online_mlp_pair (fmx_online_run_mlp_pair).  On the device they use fmx_common.h alone; the per-sample fallbacks of
-// fmx_online_run_mlp and fmx_online_run_mlp_pair issue the batched launches of the other units through fmx_host.h.
+// k_online_mlp_pair (fmx_online_run_mlp_pair).  The four walkers are two step loops -- fm_walk and mlp_walk, each over one or two
+// samples per step -- built from the per-step pieces of fmx_walk.inc; a kernel adds its objective's label, loss and outputs.  On
+// the device they use fmx_common.h alone; the queued form of fmx_online_run_mlp and fmx_online_run_mlp_pair (online_mlp_queued)
+// issues the batched launches of the other units through fmx_host.h.
 
 #include "fmx_host.h"
 
 namespace {
 
+#include "fmx_walk.inc"
+
 // ------------------------------------------------------------------------------------------------------------
-// k_fm_online: the reference's online protocol on a device-resident stream (pure FM)
+// k_fm_online, k_fm_pair_online: the reference's online protocol on a device-resident stream (pure FM)
 // ------------------------------------------------------------------------------------------------------------
 // run_experiment (reference fm_adam.py:90-119): for every sample, predict (sigmoid(forward) > 0.5), then fit on that
-// one sample.  Steps of one sample are inherently sequential (step i+1 reads the rows step i wrote), so ONE wavefront
-// walks the stream: per sample it gathers the F rows (sc1 loads: a row may have been written by the previous sample),
-// evaluates the logit, stores the prediction, and applies the rule to the same rows from registers -- the arithmetic of
-// k_fm_forward + k_fm_update at B = 1 (each row of a sample is a run of one occurrence), so the tables end
-// bit-identical to N calls of fmx_fm_step with B = 1.  The next sample's indices are fetched while the current one is
-// processed; the bias lives in registers.  Per sample: one dependent gather + the store acknowledgement (~3 us).
+// one sample.  Steps are inherently sequential (step i+1 reads the rows step i wrote), so ONE wavefront walks the stream
+// (fm_walk): per step of T samples it gathers their rows (sc1 loads: a row may have been written by the previous step),
+// evaluates the logits, stores the prediction, and applies the rule to the same rows from registers -- the arithmetic of
+// k_fm_forward + k_fm_update at B = T, so the tables end bit-identical to N calls of fmx_fm_step with B = 1 (T = 1) or of
+// fmx_fm_pair_step with one pair (T = 2: the pairwise-ranking loss of fmx_pair.inc, predict z_pos > z_neg).  The next step's
+// indices are fetched while the current one is processed; the bias lives in registers.  Per step: one dependent gather + the
+// store acknowledgement (~3 us).
 struct OnlineArgs {
-  float *rows;
-  const int64_t *foff;
-  float *bias;
-  const int32_t *idx;  // [N, F]
-  const float *xv;     // [N, F] or null
+  WalkTable t;         // idx, xv: [N, F]
   const float *y;      // [N]
   uint8_t *pred;       // [N] sigmoid(logit) > 0.5 BEFORE the sample's update
   float *loss;         // [N] or null
-  int32_t *error;
-  fmx_hyper_t h;
-  int32_t N, F, stride, zoff, loss_kind;
+  int32_t loss_kind;
 };
 
-// (The field walk below and k_online_mlp's stay two copies: one shared walk left k_fm_online's forward waiting on the prefetch
-// of the next sample with vmcnt(0) instead of the row loads only: 3.2 -> 3.6 us per sample.)
-template <int LPR, int LAYOUT, int RULE, int NP>
-__global__ __launch_bounds__(64) void k_fm_online(OnlineArgs a) {
-  constexpr int SLOTS = WAVE / LPR;
+struct PairOnlineArgs {
+  WalkTable t;         // idx, xv: [2N, F], rows 2i (positive) and 2i + 1 (negative) of pair i
+  uint8_t *pred;       // [N] z_pos > z_neg BEFORE the pair's update
+  float *logit;        // [2N] or null
+  float *loss;         // [N] or null
+  float margin;
+};
+
+// label(i): the label of step i (a load, or a constant where the objective has none).  loss_dz(i, z, y, dz): the objective's
+// loss of the T logits -- dz[t] = d loss / d z[t] at inv_b = 1 -- and its outputs, stored by lane 0.  The bias gradient is
+// block_sum's dz[0] + .. + dz[T - 1] (a pair's is exactly +0, which still goes through bias_step: ADAM's moments decay on it).
+template <int LPR, int LAYOUT, int RULE, int NP, int T, class Label, class Loss>
+__device__ __forceinline__ void fm_walk(const WalkTable &a, Label label, Loss loss_dz) {
   const int lane = threadIdx.x & 63;
   const int slot = lane / LPR, q = lane % LPR;
   const int kp = LPR * 4;
-  constexpr bool MOM = LAYOUT == FMX_LAYOUT_MOMENTS;
-  // the bias (or its (z, n), or (b, m_b, v_b)) stays in registers
-  float b0 = a.bias[0], b1 = LAYOUT != FMX_LAYOUT_WEIGHTS ? a.bias[1] : 0.f, b2 = MOM ? a.bias[2] : 0.f;
-  int64_t lo[NP];
-  uint32_t vocab[NP];
-  bool live[NP];
-#pragma unroll
-  for (int p = 0; p < NP; ++p) {
-    const int f = p * SLOTS + slot;
-    live[p] = f < a.F;
-    lo[p] = live[p] ? a.foff[f] : 0;
-    vocab[p] = live[p] ? (uint32_t)(a.foff[f + 1] - lo[p]) : 0u;
-  }
-  uint32_t li_n[NP];
-  float x_n[NP], y_n = 0.f;
-  // branch-free (see forward_sample): beyond the stream or the last field the loads read element 0 and are dropped
-  const float *xsrc = a.xv ? a.xv : reinterpret_cast<const float *>(a.idx);
-  const bool has_x = a.xv != nullptr;
+  float b0, b1, b2;
+  walk_bias_load<LAYOUT>(a.bias, b0, b1, b2);
+  const WalkFields<NP> f = walk_fields<LPR, NP>(a.foff, a.F, slot);
+  const WalkX xs = walk_x(a);
+  WalkInputs<T, NP> next;
+  float y_n = 0.f;
   auto fetch_inputs = [&](int i) {
     const bool in = i < a.N;
-    uint32_t l_[NP];
-    float x_[NP];
-#pragma unroll
-    for (int p = 0; p < NP; ++p) {
-      const size_t o = (live[p] && in) ? (size_t)i * a.F + p * SLOTS + slot : (size_t)0;
-      l_[p] = (uint32_t)a.idx[o];
-      x_[p] = xsrc[o];
-    }
-    const float yy = a.y[in ? i : 0];
-#pragma unroll
-    for (int p = 0; p < NP; ++p) {
-      li_n[p] = (live[p] && in) ? l_[p] : 0u;
-      x_n[p] = (has_x && live[p] && in) ? x_[p] : 1.f;
-    }
+    float yy = 0.f;
+    walk_fetch<LPR>(next, a, xs, f.live, slot, in, [&](int t) { return (size_t)T * i + t; }, [&] { yy = label(in ? i : 0); });
     y_n = in ? yy : 0.f;
   };
   fetch_inputs(0);
   bool bad = false;
   for (int i = 0; i < a.N; ++i) {
-    uint32_t li[NP];
-    float x[NP];
+    const WalkInputs<T, NP> in = next;
     const float y = y_n;
-#pragma unroll
-    for (int p = 0; p < NP; ++p) {
-      li[p] = li_n[p];
-      x[p] = x_n[p];
-    }
-    RowRegs row[NP];
-    bool ok[NP];
-#pragma unroll
-    for (int p = 0; p < NP; ++p) {
-      ok[p] = live[p] && li[p] < vocab[p];
-      // branch-free: a dead lane group or a bad index requests the table's first row and drops it (with a branch per
-      // pass the rows of a sample went out in NP dependent round trips)
-      row[p] = load_row_sc1<LAYOUT, RULE>(a.rows + (size_t)(ok[p] ? lo[p] + li[p] : 0) * a.stride, q, kp, a.zoff);
-      bad = bad || (live[p] && !ok[p]);
-    }
-    fetch_inputs(i + 1);  // independent of the weights: in flight while this sample is processed
-    // ---- forward: the arithmetic of k_fm_forward ----
-    float4 s = splat(0.f), ss = splat(0.f);
-    float fo = 0.f;
-#pragma unroll
-    for (int p = 0; p < NP; ++p) {
-      if (ok[p]) {
-        const float4 e = x[p] * row[p].v;
-        s = s + e;
-        ss = ss + e * e;
-        fo += row[p].fo.x * x[p];
-      }
-    }
-    fm_field_sums<LPR>(s, ss, fo, lane);
-    float sbi;
-    fm_bi<LPR>(s, ss, sbi);
-    fo = __shfl(fo, 0);
+    RowRegs row[T][NP];
+    bool ok[T][NP];
+    walk_gather<LAYOUT, RULE>(row, ok, bad, a, f, in.li, q, kp);
+    fetch_inputs(i + 1);  // independent of the weights: in flight while this step is processed
     const float bias_w = bias_weight<LAYOUT>(b0, b1, a.h);
-    const float z = fo + sbi + bias_w;
-    // ADAM: sample i is step a.h.step + i + 1 -- its constants as the host derives them for a launch (same function, same bits)
+    float4 S[T];
+    float z[T], dz[T];
+#pragma unroll
+    for (int t = 0; t < T; ++t) {
+      float sbi, fo;
+      walk_forward<LPR>(row[t], in.x[t], ok[t], lane, S[t], sbi, fo);
+      z[t] = fo + sbi + bias_w;
+    }
+    // ADAM: step i is step a.h.step + i + 1 -- its constants as the host derives them for a launch (same function, same bits)
     fmx_hyper_t h = a.h;
     if (RULE == FMX_RULE_ADAM) adam_consts(a.h.lr, a.h.beta1, a.h.beta2, a.h.step + i + 1, h.lr, h.beta1, h.beta2);
-    float loss, dz;
-    bce_loss_dz(a.loss_kind, z, y, 1.0f, loss, dz);
-    if (lane == 0) {
-      a.pred[i] = sigmoidf_(z) > 0.5f ? 1 : 0;
-      if (a.loss) a.loss[i] = loss;
-    }
-    // ---- fit: every row of the sample is a run of one occurrence (k_fm_update's sums with B = 1, inv_b = 1) ----
+    loss_dz(i, z, y, dz);
+    walk_fit<LAYOUT, RULE>(a, f, in.li, ok, row, q, kp, h, [&](int t, int p, float4 &cV, float4 &cA, float &cw) {
+      const float xG = in.x[t][p] * dz[t];  // (dz_bi == dz_first)
+      cV = xG * S[t];
+      cA = splat(in.x[t][p] * xG);
+      cw = xG;
+    });
+    float db = dz[0];
 #pragma unroll
-    for (int p = 0; p < NP; ++p) {
-      if (ok[p]) {
-        const float xG = x[p] * dz;
-        update_row<LAYOUT, RULE>(a.rows + (size_t)(lo[p] + li[p]) * a.stride, q, kp, a.zoff, row[p], xG * s, splat(x[p] * xG),
-                                 xG, h);
-      }
-    }
-    bias_step<LAYOUT, RULE>(b0, b1, b2, dz, h);  // (h is a.h but under ADAM, which pairs with MOMENTS alone)
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the row stores are acknowledged before the next sample's loads
+    for (int t = 1; t < T; ++t) db = db + dz[t];
+    bias_step<LAYOUT, RULE>(b0, b1, b2, db, h);  // (h is a.h but under ADAM, which pairs with MOMENTS alone)
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the row stores are acknowledged before the next step's loads
   }
   const bool any_bad = __ballot(bad) != 0ull;  // an out-of-range index seen by any lane group
   if (lane == 0) {
-    a.bias[0] = b0;
-    if (LAYOUT == FMX_LAYOUT_FTRL || (MOM && RULE == FMX_RULE_ADAM)) a.bias[1] = b1;
-    if (MOM) a.bias[2] = b2;
+    walk_bias_store<LAYOUT, RULE>(a.bias, b0, b1, b2);
     if (any_bad && a.error) *a.error = 1;
   }
 }
 
-// ------------------------------------------------------------------------------------------------------------
-// k_fm_pair_online: k_fm_online for pairs (the pairwise-ranking loss of fmx_pair.inc): one wavefront walks N pairs, predict
-// (z_pos > z_neg) then fit on that pair
-// ------------------------------------------------------------------------------------------------------------
-struct PairOnlineArgs {
-  float *rows;
-  const int64_t *foff;
-  float *bias;
-  const int32_t *idx;  // [2N, F]: rows 2i (positive) and 2i + 1 (negative) of pair i
-  const float *xv;     // [2N, F] or null
-  uint8_t *pred;       // [N] z_pos > z_neg BEFORE the pair's update
-  float *logit;        // [2N] or null
-  float *loss;         // [N] or null
-  int32_t *error;
-  fmx_hyper_t h;
-  int32_t N, F, stride, zoff;
-  float margin;
-};
+template <int LPR, int LAYOUT, int RULE, int NP>
+__global__ __launch_bounds__(64) void k_fm_online(OnlineArgs a) {
+  fm_walk<LPR, LAYOUT, RULE, NP, 1>(
+      a.t, [&](int i) { return a.y[i]; },
+      [&](int i, const float(&z)[1], float y, float(&dz)[1]) {
+        float loss;
+        bce_loss_dz(a.loss_kind, z[0], y, 1.0f, loss, dz[0]);
+        if ((threadIdx.x & 63) == 0) {
+          a.pred[i] = sigmoidf_(z[0]) > 0.5f ? 1 : 0;
+          if (a.loss) a.loss[i] = loss;
+        }
+      });
+}
 
-// The fit of pair i is k_fm_update on a batch of two samples (fmx_fm_pair_step with B = 1, inv_b = 1): per field the sorted list
-// holds the two occurrences by (row, sample).  Two different rows are two runs of one occurrence, each summed from zero; the same
-// row is ONE run whose sums add the positive's terms, then the negative's -- (0 + c_pos) + c_neg -- and the row takes one
-// update_row.  The bias gradient is block_sum's dz[0] + dz[1] = +0, which still goes through bias_step (ADAM's moments decay on a
-// zero gradient); the mean loss is (loss_i + 0) * inv_b.
 template <int LPR, int LAYOUT, int RULE, int NP>
 __global__ __launch_bounds__(64) void k_fm_pair_online(PairOnlineArgs a) {
-  constexpr int SLOTS = WAVE / LPR;
-  const int lane = threadIdx.x & 63;
-  const int slot = lane / LPR, q = lane % LPR;
-  const int kp = LPR * 4;
-  constexpr bool MOM = LAYOUT == FMX_LAYOUT_MOMENTS;
-  float b0 = a.bias[0], b1 = LAYOUT != FMX_LAYOUT_WEIGHTS ? a.bias[1] : 0.f, b2 = MOM ? a.bias[2] : 0.f;
-  int64_t lo[NP];
-  uint32_t vocab[NP];
-  bool live[NP];
-#pragma unroll
-  for (int p = 0; p < NP; ++p) {
-    const int f = p * SLOTS + slot;
-    live[p] = f < a.F;
-    lo[p] = live[p] ? a.foff[f] : 0;
-    vocab[p] = live[p] ? (uint32_t)(a.foff[f + 1] - lo[p]) : 0u;
-  }
-  // the next pair's indices and values: sample t = 0 (positive), 1 (negative).  Branch-free, as in k_fm_online
-  uint32_t li_n[2][NP];
-  float x_n[2][NP];
-  const float *xsrc = a.xv ? a.xv : reinterpret_cast<const float *>(a.idx);
-  const bool has_x = a.xv != nullptr;
-  auto fetch_inputs = [&](int i) {
-    const bool in = i < a.N;
-    uint32_t l_[2][NP];
-    float x_[2][NP];
-#pragma unroll
-    for (int t = 0; t < 2; ++t) {
-#pragma unroll
-      for (int p = 0; p < NP; ++p) {
-        const size_t o = (live[p] && in) ? ((size_t)2 * i + t) * a.F + p * SLOTS + slot : (size_t)0;
-        l_[t][p] = (uint32_t)a.idx[o];
-        x_[t][p] = xsrc[o];
-      }
-    }
-#pragma unroll
-    for (int t = 0; t < 2; ++t) {
-#pragma unroll
-      for (int p = 0; p < NP; ++p) {
-        li_n[t][p] = (live[p] && in) ? l_[t][p] : 0u;
-        x_n[t][p] = (has_x && live[p] && in) ? x_[t][p] : 1.f;
-      }
-    }
-  };
-  fetch_inputs(0);
-  bool bad = false;
-  for (int i = 0; i < a.N; ++i) {
-    uint32_t li[2][NP];
-    float x[2][NP];
-    RowRegs row[2][NP];
-    bool ok[2][NP];
-#pragma unroll
-    for (int t = 0; t < 2; ++t) {
-#pragma unroll
-      for (int p = 0; p < NP; ++p) {
-        li[t][p] = li_n[t][p];
-        x[t][p] = x_n[t][p];
-        ok[t][p] = live[p] && li[t][p] < vocab[p];
-        row[t][p] = load_row_sc1<LAYOUT, RULE>(a.rows + (size_t)(ok[t][p] ? lo[p] + li[t][p] : 0) * a.stride, q, kp, a.zoff);
-        bad = bad || (live[p] && !ok[t][p]);
-      }
-    }
-    fetch_inputs(i + 1);  // independent of the weights: in flight while this pair is processed
-    // ---- forward of both samples: the arithmetic of k_fm_forward ----
-    const float bias_w = bias_weight<LAYOUT>(b0, b1, a.h);
-    float4 S[2];
-    float z[2];
-#pragma unroll
-    for (int t = 0; t < 2; ++t) {
-      float4 s = splat(0.f), ss = splat(0.f);
-      float fo = 0.f;
-#pragma unroll
-      for (int p = 0; p < NP; ++p) {
-        if (ok[t][p]) {
-          const float4 e = x[t][p] * row[t][p].v;
-          s = s + e;
-          ss = ss + e * e;
-          fo += row[t][p].fo.x * x[t][p];
+  fm_walk<LPR, LAYOUT, RULE, NP, 2>(
+      a.t, [](int) { return 0.f; },
+      [&](int i, const float(&z)[2], float, float(&dz)[2]) {
+        float loss;
+        pair_loss_dz(z[0] - z[1], a.margin, 1.0f, loss, dz[0]);
+        dz[1] = -dz[0];
+        if ((threadIdx.x & 63) == 0) {
+          a.pred[i] = z[0] > z[1] ? 1 : 0;
+          if (a.logit) {
+            a.logit[2 * (size_t)i] = z[0];
+            a.logit[2 * (size_t)i + 1] = z[1];
+          }
+          if (a.loss) a.loss[i] = (0.f + loss) * 1.0f;  // the mean loss: (loss_i + 0) * inv_b
         }
-      }
-      fm_field_sums<LPR>(s, ss, fo, lane);
-      float sbi;
-      fm_bi<LPR>(s, ss, sbi);
-      fo = __shfl(fo, 0);
-      S[t] = s;
-      z[t] = fo + sbi + bias_w;
-    }
-    fmx_hyper_t h = a.h;  // ADAM: pair i is step a.h.step + i + 1 (adam_consts, as the host derives them for a launch)
-    if (RULE == FMX_RULE_ADAM) adam_consts(a.h.lr, a.h.beta1, a.h.beta2, a.h.step + i + 1, h.lr, h.beta1, h.beta2);
-    float loss, dzp;
-    pair_loss_dz(z[0] - z[1], a.margin, 1.0f, loss, dzp);
-    const float dz[2] = {dzp, -dzp};
-    if (lane == 0) {
-      a.pred[i] = z[0] > z[1] ? 1 : 0;
-      if (a.logit) {
-        a.logit[2 * (size_t)i] = z[0];
-        a.logit[2 * (size_t)i + 1] = z[1];
-      }
-      if (a.loss) a.loss[i] = (0.f + loss) * 1.0f;
-    }
-    // ---- fit ----
-#pragma unroll
-    for (int p = 0; p < NP; ++p) {
-      float4 cV[2];
-      float cA[2], cw[2];
-#pragma unroll
-      for (int t = 0; t < 2; ++t) {  // the occurrence's terms as update_body forms them (dz_bi == dz_first)
-        const float xG = x[t][p] * dz[t];
-        cV[t] = xG * S[t];
-        cA[t] = x[t][p] * xG;
-        cw[t] = x[t][p] * dz[t];
-      }
-      float *rp0 = a.rows + (size_t)(lo[p] + li[0][p]) * a.stride, *rp1 = a.rows + (size_t)(lo[p] + li[1][p]) * a.stride;
-      if (ok[0][p] && ok[1][p] && li[0][p] == li[1][p]) {  // one run of two occurrences, in sample order
-        const float4 rV = (splat(0.f) + cV[0]) + cV[1];
-        const float rA = (0.f + cA[0]) + cA[1], rw = (0.f + cw[0]) + cw[1];
-        update_row<LAYOUT, RULE>(rp0, q, kp, a.zoff, row[0][p], rV, splat(rA), rw, h);
-      } else {
-        if (ok[0][p]) update_row<LAYOUT, RULE>(rp0, q, kp, a.zoff, row[0][p], splat(0.f) + cV[0], splat(0.f + cA[0]), 0.f + cw[0], h);
-        if (ok[1][p]) update_row<LAYOUT, RULE>(rp1, q, kp, a.zoff, row[1][p], splat(0.f) + cV[1], splat(0.f + cA[1]), 0.f + cw[1], h);
-      }
-    }
-    bias_step<LAYOUT, RULE>(b0, b1, b2, dz[0] + dz[1], h);            // exactly +0
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the row stores are acknowledged before the next pair's loads
-  }
-  const bool any_bad = __ballot(bad) != 0ull;
-  if (lane == 0) {
-    a.bias[0] = b0;
-    if (LAYOUT == FMX_LAYOUT_FTRL || (MOM && RULE == FMX_RULE_ADAM)) a.bias[1] = b1;
-    if (MOM) a.bias[2] = b2;
-    if (any_bad && a.error) *a.error = 1;
-  }
-}
-
-template <int LPR, int LAYOUT, int RULE>
-void launch_pair_online_np(const PairOnlineArgs &a, int np, hipStream_t st) {
-  auto launch = [&](auto NP) { hipLaunchKernelGGL((k_fm_pair_online<LPR, LAYOUT, RULE, NP>), dim3(1), dim3(64), 0, st, a); };
-  if (!with_one_of<1, 2, 3>(np, launch)) launch(std::integral_constant<int, 4>{});
+      });
 }
 
 // ------------------------------------------------------------------------------------------------------------
@@ -536,578 +358,290 @@ __device__ void mlp_small_body(const MlpArgs &a) {
 __global__ __launch_bounds__(256) void k_mlp_small(MlpArgs a) { mlp_small_body<false>(a); }
 __global__ __launch_bounds__(256) void k_mlp_small_pair(MlpArgs a) { mlp_small_body<true>(a); }
 
+
 // ------------------------------------------------------------------------------------------------------------
-// k_online_mlp: the online predict-then-fit loop of the classes with an MLP, one workgroup walking the stream
+// k_online_mlp, k_online_mlp_pair: the online predict-then-fit loop of the classes with an MLP, one workgroup walking the stream
 // ------------------------------------------------------------------------------------------------------------
-// Per sample: wave 0 gathers the sample's rows (sc1 loads: the previous sample may have written them) and evaluates the
-// FM part exactly as k_fm_forward does; the whole workgroup runs the MLP step of k_mlp_small (fit or Hedge) on parameters
-// that live in LDS for the length of the stream; wave 0 then applies the table update of k_fm_update at B = 1 from the
-// rows it still holds (not with Hedge, which leaves the tables alone).  Same arithmetic as the per-sample launches
-// (forward, k_mlp_small, sort, update), so the parameters end bit-identical; no launch gaps, no host in the loop.
-// fmx_online_run_mlp_opt (has_opt): the network under its own persistent rule -- its moments live in LDS beside the parameters
-// (v under ADAGRAD, v and m under ADAM) and are written back at the end -- and the tables under any rule but FTRL, the MOMENTS
-// rules included.  Sample i is step hyper->step + i + 1 of the tables and opt.step + i + 1 of the network: ADAM's constants of
-// both are derived once per sample by one lane of wave 1 (adam_consts, the function the host uses for a launch: same bits) while
-// wave 0 waits for the sample's rows, and reach the other threads through LDS words.
+// Per step of T samples (mlp_walk): wave 0 gathers the samples' rows (sc1 loads: the previous step may have written them) and
+// evaluates the FM parts exactly as k_fm_forward does, leaving bi [T, kp] and base [T] in LDS; the whole workgroup runs the MLP step
+// of k_mlp_small (T = 1: fit or Hedge) or k_mlp_small_pair (T = 2: B = 2) on parameters that live in LDS for the length of the
+// stream; wave 0 then applies the table update of k_fm_update at B = T from the rows it still holds, with fm_walk's run logic (not
+// with Hedge, which leaves the tables alone).  Same arithmetic as the per-step launches (forward, k_mlp_small, sort, update), so
+// the parameters end bit-identical; no launch gaps, no host in the loop.
+// With opt (fmx_online_run_mlp_opt; fmx_online_run_mlp_pair with opt): the network under its own persistent rule -- its moments
+// live in LDS beside the parameters (v under ADAGRAD, v and m under ADAM) and are written back at the end -- and the tables under
+// any rule but FTRL, the MOMENTS rules included.  Step i is step hyper->step + i + 1 of the tables and opt.step + i + 1 of the
+// network: ADAM's constants of both are derived once per step by one lane of wave 1 while wave 0 waits for the step's rows, and
+// reach the other threads through LDS words.
 struct OnlineMlpArgs {
-  float *rows;
-  const int64_t *foff;
-  float *bias;
-  const int32_t *idx;
-  const float *xv;
+  WalkTable t;      // h: lr / eps also drive the MLP rule
   const float *y;
   float *pred;      // [N] what forward() returns for the sample, before its update
-  int32_t *error;
   float *params;    // global: copied into LDS, written back at the end
   float *alpha;     // Hedge: global [L], same treatment
-  fmx_hyper_t h;    // alpha already inverted (table rule); lr / eps also drive the MLP rule
   float hedge_b, hedge_s;
-  int32_t N, F, stride, zoff, n_params;
+  int32_t n_params;
   int32_t k, hidden, n_layers, hedge, fm_term, rule, loss_kind;
   int32_t has_opt;    // fmx_online_run_mlp_opt: the network under opt (m, v global: copied into LDS, written back at the end)
   fmx_mlp_opt_t opt;
 };
 
-__device__ __forceinline__ float uniform_f(float x) { return __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(x))); }
-
-// OPT: the instantiations of fmx_online_run_mlp_opt (has_opt); fmx_online_run_mlp's own carry none of it
-template <int LPR, int LAYOUT, int RULE, bool OPT>
-__global__ __launch_bounds__(256) void k_online_mlp(OnlineMlpArgs a) {
-  constexpr int SLOTS = WAVE / LPR, NP = 4;
-  constexpr bool MOM = LAYOUT == FMX_LAYOUT_MOMENTS;
-  extern __shared__ float p_lds[];  // [n_params] the MLP's parameters; has_opt: then v [n_params] (ADAGRAD, ADAM), then m [n_params] (ADAM)
-  __shared__ float kc[8];  // ADAM's constants of the sample: tables (step size, 1 - beta1, 1 - beta2), network (the same and eps sqrt(1 - beta2^t))
-  __shared__ float bi_lds[MLP_MAX_W], gbi_lds[MLP_MAX_W], alpha_lds[MLP_MAX_L];
-  __shared__ float base_lds, dz_lds;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int slot = lane / LPR, q = lane % LPR;
-  const int kp = LPR * 4;
-  for (int i = tid; i < a.n_params; i += blockDim.x) p_lds[i] = a.params[i];
-  const int net_rule = OPT ? a.opt.rule : -1;  // workgroup-uniform
-  const bool net_adaptive = net_rule == FMX_RULE_ADAGRAD || net_rule == FMX_RULE_ADAM, net_adam = net_rule == FMX_RULE_ADAM;
-  float *v_lds = p_lds + a.n_params, *m_lds = v_lds + a.n_params;
-  if (net_adaptive)
-    for (int i = tid; i < a.n_params; i += blockDim.x) v_lds[i] = a.opt.v[i];
-  if (net_adam)
-    for (int i = tid; i < a.n_params; i += blockDim.x) m_lds[i] = a.opt.m[i];
-  if (a.hedge && tid < a.n_layers) alpha_lds[tid] = a.alpha[tid];
-  // the bias (or its (z, n), or (b, m_b, v_b)) stays in wave 0's registers
-  float b0 = a.bias[0], b1 = LAYOUT != FMX_LAYOUT_WEIGHTS ? a.bias[1] : 0.f, b2 = MOM ? a.bias[2] : 0.f;
-  int64_t lo[NP];
-  uint32_t vocab[NP];
-  bool live[NP];
-#pragma unroll
-  for (int p = 0; p < NP; ++p) {
-    const int f = p * SLOTS + slot;
-    live[p] = f < a.F;
-    lo[p] = live[p] ? a.foff[f] : 0;
-    vocab[p] = live[p] ? (uint32_t)(a.foff[f + 1] - lo[p]) : 0u;
-  }
-  bool bad = false;
-  // wave 0: the NEXT sample's indices (and values) are requested while this one is processed -- they do not depend on the
-  // weights (as in k_fm_online); branch-free loads (see forward_sample)
-  const float *xsrc = a.xv ? a.xv : reinterpret_cast<const float *>(a.idx);
-  const bool has_x = a.xv != nullptr;
-  uint32_t l_n[NP];
-  float x_n[NP], y_n = 0.f;
-  __shared__ float y_lds;  // the sample's label, for the MLP step (its own load of y would be one more exposed round trip)
-  auto fetch_inputs = [&](int i) {
-#pragma unroll
-    for (int p = 0; p < NP; ++p) {
-      const size_t o = (live[p] && i < a.N) ? (size_t)i * a.F + p * SLOTS + slot : (size_t)0;
-      l_n[p] = (uint32_t)a.idx[o];
-      x_n[p] = xsrc[o];
-    }
-    y_n = a.y[i < a.N ? i : 0];
-  };
-  if (wave == 0) fetch_inputs(0);
-  __syncthreads();
-  for (int i = 0; i < a.N; ++i) {
-    uint32_t li[NP];
-    float x[NP];
-    RowRegs row[NP];
-    bool ok[NP];
-    float4 S = splat(0.f);
-    if (OPT && tid == WAVE && (RULE == FMX_RULE_ADAM || net_adam)) {  // one lane of wave 1, idle until the MLP step
-      if (RULE == FMX_RULE_ADAM) adam_consts(a.h.lr, a.h.beta1, a.h.beta2, a.h.step + i + 1, kc[0], kc[1], kc[2]);
-      if (net_adam) adam_consts(a.opt.lr, a.opt.beta1, a.opt.beta2, a.opt.step + i + 1, kc[3], kc[4], kc[5], a.opt.eps, &kc[6]);
-    }
-    if (wave == 0) {
-      // ---- the FM part: the arithmetic of k_fm_forward ----
-      // branch-free, all row loads together (see forward_sample / k_fm_online): with the loads of a pass under
-      // `if (live[p])` a sample's rows went out in 2 NP dependent round trips
-      {
-#pragma unroll
-        for (int p = 0; p < NP; ++p) {
-          li[p] = live[p] ? l_n[p] : 0u;
-          x[p] = (has_x && live[p]) ? x_n[p] : 1.f;
-          ok[p] = live[p] && li[p] < vocab[p];
-        }
-        if (lane == 0) y_lds = y_n;
-#pragma unroll
-        for (int p = 0; p < NP; ++p) {
-          row[p] = load_row_sc1<LAYOUT, RULE>(a.rows + (size_t)(ok[p] ? lo[p] + li[p] : 0) * a.stride, q, kp, a.zoff);
-          bad = bad || (live[p] && !ok[p]);
-        }
-        fetch_inputs(i + 1);
-      }
-      float4 s = splat(0.f), ss = splat(0.f);
-      float fo = 0.f;
-#pragma unroll
-      for (int p = 0; p < NP; ++p) {
-        if (ok[p]) {
-          const float4 e = x[p] * row[p].v;
-          s = s + e;
-          ss = ss + e * e;
-          fo += row[p].fo.x * x[p];
-        }
-      }
-      fm_field_sums<LPR>(s, ss, fo, lane);
-      S = s;
-      float sbi;
-      const float4 bi = fm_bi<LPR>(s, ss, sbi);
-      fo = __shfl(fo, 0);
-      const float bias_w = bias_weight<LAYOUT>(b0, b1, a.h);
-      if (lane < LPR) {
-        bi_lds[4 * q] = bi.x;
-        bi_lds[4 * q + 1] = bi.y;
-        bi_lds[4 * q + 2] = bi.z;
-        bi_lds[4 * q + 3] = bi.w;
-      }
-      if (lane == 0) base_lds = a.fm_term ? fo + sbi + bias_w : fo + bias_w;
-    }
-    __syncthreads();
-    // ---- the MLP step of k_mlp_small on LDS-resident parameters ----
-    MlpArgs m{};
-    m.params = p_lds;
-    m.bi = bi_lds;
-    m.base = &base_lds;
-    m.y = &y_lds;
-    m.pred_out = a.pred + i;
-    m.h = a.h;
-    m.inv_b = 1.0f;
-    m.B = 1;
-    m.k = a.k;
-    m.kp = kp;
-    m.hidden = a.hidden;
-    m.n_layers = a.n_layers;
-    if (a.hedge) {
-      m.alpha = alpha_lds;
-      m.hedge_b = a.hedge_b;
-      m.hedge_s = a.hedge_s;
-      m.mode = MLP_MODE_HEDGE;
-    } else {
-      m.dz_out = &dz_lds;
-      m.gbi_out = gbi_lds;
-      m.mode = MLP_MODE_FIT;
-      m.rule = a.rule;
-      m.loss_kind = a.loss_kind;
-      if (net_rule == FMX_RULE_SGD) {  // (mlp_small_set_opt)
-        m.rule = FMX_RULE_SGD;
-        m.h.lr = a.opt.lr;
-      } else if (net_adaptive) {
-        m.opt_rule = net_rule;
-        m.m = m_lds;
-        m.v = v_lds;
-        m.oh.lr = net_adam ? uniform_f(kc[3]) : a.opt.lr;
-        m.oh.eps = net_adam ? uniform_f(kc[6]) : a.opt.eps;
-        m.oh.beta1 = net_adam ? uniform_f(kc[4]) : 0.f;
-        m.oh.beta2 = net_adam ? uniform_f(kc[5]) : 0.f;
-      }
-    }
-    mlp_small_body<false>(m);
-    __syncthreads();
-    if (wave == 0 && !a.hedge) {
-      // ---- the table update of k_fm_update at B = 1: every row is a run of one occurrence, G = dz [+ dL/dbi] ----
-      const float dz = dz_lds;
-      const float4 g4 = {gbi_lds[4 * q], gbi_lds[4 * q + 1], gbi_lds[4 * q + 2], gbi_lds[4 * q + 3]};
-      const float4 G = splat(a.fm_term ? dz : 0.f) + g4;
-      fmx_hyper_t h = a.h;
-      if (RULE == FMX_RULE_ADAM) {  // the sample's constants, as update_impl derives them for a launch
-        h.lr = uniform_f(kc[0]);
-        h.beta1 = uniform_f(kc[1]);
-        h.beta2 = uniform_f(kc[2]);
-      }
-#pragma unroll
-      for (int p = 0; p < NP; ++p) {
-        if (ok[p]) {
-          const float4 xG = x[p] * G;
-          update_row<LAYOUT, RULE>(a.rows + (size_t)(lo[p] + li[p]) * a.stride, q, kp, a.zoff, row[p], xG * S, x[p] * xG, x[p] * dz,
-                                   h);
-        }
-      }
-      bias_step<LAYOUT, RULE>(b0, b1, b2, dz, h);
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the row stores are acknowledged before the next sample's loads
-    }
-    __syncthreads();
-  }
-  for (int i = tid; i < a.n_params; i += blockDim.x) a.params[i] = p_lds[i];
-  if (net_adaptive)
-    for (int i = tid; i < a.n_params; i += blockDim.x) a.opt.v[i] = v_lds[i];
-  if (net_adam)
-    for (int i = tid; i < a.n_params; i += blockDim.x) a.opt.m[i] = m_lds[i];
-  if (a.hedge && tid < a.n_layers) a.alpha[tid] = alpha_lds[tid];
-  if (wave == 0) {
-    const bool any_bad = __ballot(bad) != 0ull;
-    if (lane == 0) {
-      if (!a.hedge) {
-        a.bias[0] = b0;
-        if (LAYOUT == FMX_LAYOUT_FTRL || (MOM && RULE == FMX_RULE_ADAM)) a.bias[1] = b1;
-        if (MOM) a.bias[2] = b2;
-      }
-      if (any_bad && a.error) *a.error = 1;
-    }
-  }
-}
-
-// ------------------------------------------------------------------------------------------------------------
-// k_online_mlp_pair: k_online_mlp for pairs (fmx_online_run_mlp_pair): one workgroup walks N pairs, predict (z_pos > z_neg through
-// the whole network) then one pair step on that pair
-// ------------------------------------------------------------------------------------------------------------
-// Per pair: wave 0 holds BOTH samples' rows (as k_fm_pair_online does) and evaluates both FM parts with k_fm_forward's
-// arithmetic, leaving bi [2, kp] and base [2] in LDS; the whole workgroup runs mlp_small_body<true> at B = 2 on parameters (and
-// moments) that stay in LDS for the length of the stream; wave 0 then applies k_fm_update at B = 2 from the rows it still holds,
-// with k_fm_pair_online's run logic: a field whose two samples name the same valid row is ONE run of two occurrences summed in
-// sample order, (0 + c_pos) + c_neg, and takes one update_row; otherwise two runs of one, each 0 + c.  The bias gradient
-// dz[0] + dz[1] is exactly +0 and still goes through bias_step.  has_opt is a run-time word here (the weights rules take both
-// forms), so one instantiation per (kp, table rule) serves fmx_online_run_mlp_pair with and without opt.
 struct OnlineMlpPairArgs {
-  float *rows;
-  const int64_t *foff;
-  float *bias;
-  const int32_t *idx;  // [2N, F]: rows 2i (positive) and 2i + 1 (negative) of pair i
-  const float *xv;     // [2N, F] or null
+  WalkTable t;         // idx, xv: [2N, F], rows 2i (positive) and 2i + 1 (negative) of pair i; h: lr / eps also drive the MLP rule when has_opt == 0
   uint8_t *pred;       // [N] z_pos > z_neg BEFORE the pair's update
   float *logit;        // [2N] or null
   float *loss;         // [N] or null
-  int32_t *error;
   float *params;       // global: copied into LDS, written back at the end
-  fmx_hyper_t h;       // alpha already inverted (table rule); lr / eps also drive the MLP rule when has_opt == 0
-  int32_t N, F, stride, zoff, n_params;
+  int32_t n_params;
   int32_t k, hidden, n_layers, fm_term, rule;
   int32_t has_opt;     // the network under opt (m, v global: copied into LDS, written back at the end)
   float margin;
   fmx_mlp_opt_t opt;
 };
 
-template <int LPR, int LAYOUT, int RULE>
-__global__ __launch_bounds__(256) void k_online_mlp_pair(OnlineMlpPairArgs a) {
-  constexpr int SLOTS = WAVE / LPR, NP = 4;
-  constexpr bool MOM = LAYOUT == FMX_LAYOUT_MOMENTS;
-  extern __shared__ float p_lds[];  // [n_params] the MLP's parameters; then v [n_params] (ADAGRAD, ADAM), then m [n_params] (ADAM)
-  __shared__ float kc[8];           // ADAM's constants of the pair, as in k_online_mlp
-  __shared__ float bi_lds[2 * MLP_MAX_W], gbi_lds[2 * MLP_MAX_W];  // [2, kp]
-  __shared__ float base_lds[2], dz_lds[2];
+// the network's rule of a fit step as mlp_small_body takes it (mlp_small_set_opt), on the LDS-resident arrays and the step's
+// constants kc (walk_step_consts).  One assignment per field with the selects on the right: fields stored under branches can end
+// as stores through a selected address, and MlpArgs then lives in scratch
+__device__ __forceinline__ void walk_net_rule(MlpArgs &m, int net_rule, float *lds, int n_params, const float *kc, const fmx_mlp_opt_t &opt) {
+  const bool sgd = net_rule == FMX_RULE_SGD, adam = net_rule == FMX_RULE_ADAM, adaptive = adam || net_rule == FMX_RULE_ADAGRAD;
+  m.rule = sgd ? (int)FMX_RULE_SGD : m.rule;
+  m.h.lr = sgd ? opt.lr : m.h.lr;
+  m.opt_rule = adaptive ? net_rule : 0;
+  m.v = adaptive ? lds + n_params : nullptr;
+  m.m = adaptive ? lds + 2 * n_params : nullptr;
+  m.oh.lr = adam ? uniform_f(kc[3]) : adaptive ? opt.lr : 0.f;
+  m.oh.eps = adam ? uniform_f(kc[6]) : adaptive ? opt.eps : 0.f;
+  m.oh.beta1 = adam ? uniform_f(kc[4]) : 0.f;
+  m.oh.beta2 = adam ? uniform_f(kc[5]) : 0.f;
+}
+
+// a: the walker's arguments (what both structs above name alike).  hedge / alpha: the Hedge step, which trains the hidden layers
+// and alpha (staged in LDS like the network) and leaves the tables alone.  label(i): as in fm_walk.  objective(m, i, y, alpha): the
+// objective's own fields of step i's MlpArgs -- its outputs, its loss, and under Hedge the mode -- given the LDS words of the
+// step's label and of alpha.  (The pair walker has neither label nor Hedge and hands in constants.  With these parts moved out to
+// the pointwise kernel behind an objective object, k_online_mlp under the network's ADAM measured 3 - 4 % slower:
+// profiles/walker_seam_ab.txt, D.)
+template <int LPR, int LAYOUT, int RULE, int T, class Args, class Label, class Objective>
+__device__ __forceinline__ void mlp_walk(const Args &a, int net_rule, bool hedge, float *alpha, Label label, Objective objective) {
+  constexpr int NP = WALK_MAX_NP;
+  extern __shared__ float p_lds[];  // [n_params] the MLP's parameters, then its moments (walk_net_arrays)
+  __shared__ float kc[8];           // ADAM's constants of the step (walk_step_consts)
+  __shared__ float bi_lds[T * MLP_MAX_W], gbi_lds[T * MLP_MAX_W], alpha_lds[MLP_MAX_L];  // [T, kp]
+  __shared__ float base_lds[T], dz_lds[T];
+  __shared__ float y_lds;  // the step's label, for the MLP step (its own load of y would be one more exposed round trip)
+  const WalkTable &t = a.t;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int slot = lane / LPR, q = lane % LPR;
   const int kp = LPR * 4;
-  for (int i = tid; i < a.n_params; i += blockDim.x) p_lds[i] = a.params[i];
-  const int net_rule = a.has_opt ? a.opt.rule : -1;  // workgroup-uniform
-  const bool net_adaptive = net_rule == FMX_RULE_ADAGRAD || net_rule == FMX_RULE_ADAM, net_adam = net_rule == FMX_RULE_ADAM;
-  float *v_lds = p_lds + a.n_params, *m_lds = v_lds + a.n_params;
-  if (net_adaptive)
-    for (int i = tid; i < a.n_params; i += blockDim.x) v_lds[i] = a.opt.v[i];
-  if (net_adam)
-    for (int i = tid; i < a.n_params; i += blockDim.x) m_lds[i] = a.opt.m[i];
-  // the bias (or its (b, m_b, v_b)) stays in wave 0's registers
-  float b0 = a.bias[0], b1 = LAYOUT != FMX_LAYOUT_WEIGHTS ? a.bias[1] : 0.f, b2 = MOM ? a.bias[2] : 0.f;
-  int64_t lo[NP];
-  uint32_t vocab[NP];
-  bool live[NP];
-#pragma unroll
-  for (int p = 0; p < NP; ++p) {
-    const int f = p * SLOTS + slot;
-    live[p] = f < a.F;
-    lo[p] = live[p] ? a.foff[f] : 0;
-    vocab[p] = live[p] ? (uint32_t)(a.foff[f + 1] - lo[p]) : 0u;
-  }
+  walk_net_stage<false>(p_lds, a.params, a.opt, a.n_params, net_rule);
+  if (hedge && tid < a.n_layers) alpha_lds[tid] = alpha[tid];
+  float b0, b1, b2;  // in wave 0's registers
+  walk_bias_load<LAYOUT>(t.bias, b0, b1, b2);
+  const WalkFields<NP> f = walk_fields<LPR, NP>(t.foff, t.F, slot);
   bool bad = false;
-  // wave 0: the NEXT pair's indices (and values), sample t = 0 (positive), 1 (negative); branch-free, as in k_fm_pair_online
-  const float *xsrc = a.xv ? a.xv : reinterpret_cast<const float *>(a.idx);
-  const bool has_x = a.xv != nullptr;
-  uint32_t l_n[2][NP];
-  float x_n[2][NP];
+  // wave 0: the NEXT step's indices (and values) are requested while this one is processed, as in fm_walk.  This prefetch is
+  // mlp_walk's OWN, not walk_fetch: the words are kept as loaded and selected at the start of their step.  walk_fetch's selects
+  // stand behind its loads, inside wave 0's branch, and the values leave that branch only once loaded: wave 0 then waited for the
+  // prefetch (vmcnt(0)) before the MLP step's first barrier instead of leaving it in flight across the step.  With walk_fetch
+  // here k_online_mlp_pair at 5 x 10 under signadam measured 13.09 us per pair against the parent's 12.81, with this copy
+  // 12.86 against 12.88 (profiles/walker_seam_ab.txt, C)
+  constexpr int SLOTS = WAVE / LPR;
+  const WalkX xs = walk_x(t);
+  WalkInputs<T, NP> next;  // as loaded
+  float y_n = 0.f;
   auto fetch_inputs = [&](int i) {
 #pragma unroll
-    for (int t = 0; t < 2; ++t) {
+    for (int s = 0; s < T; ++s) {
 #pragma unroll
       for (int p = 0; p < NP; ++p) {
-        const size_t o = (live[p] && i < a.N) ? ((size_t)2 * i + t) * a.F + p * SLOTS + slot : (size_t)0;
-        l_n[t][p] = (uint32_t)a.idx[o];
-        x_n[t][p] = xsrc[o];
+        const size_t o = (f.live[p] && i < t.N) ? ((size_t)T * i + s) * t.F + p * SLOTS + slot : (size_t)0;
+        next.li[s][p] = (uint32_t)t.idx[o];
+        next.x[s][p] = xs.src[o];
       }
     }
+    y_n = label(i < t.N ? i : 0);
   };
   if (wave == 0) fetch_inputs(0);
   __syncthreads();
-  for (int i = 0; i < a.N; ++i) {
-    uint32_t li[2][NP];
-    float x[2][NP];
-    RowRegs row[2][NP];
-    bool ok[2][NP];
-    float4 S[2] = {splat(0.f), splat(0.f)};
-    if (tid == WAVE && (RULE == FMX_RULE_ADAM || net_adam)) {  // one lane of wave 1, idle until the MLP step
-      if (RULE == FMX_RULE_ADAM) adam_consts(a.h.lr, a.h.beta1, a.h.beta2, a.h.step + i + 1, kc[0], kc[1], kc[2]);
-      if (net_adam) adam_consts(a.opt.lr, a.opt.beta1, a.opt.beta2, a.opt.step + i + 1, kc[3], kc[4], kc[5], a.opt.eps, &kc[6]);
-    }
+  for (int i = 0; i < t.N; ++i) {
+    WalkInputs<T, NP> in;
+    RowRegs row[T][NP];
+    bool ok[T][NP];
+    float4 S[T];
+#pragma unroll
+    for (int s = 0; s < T; ++s) S[s] = splat(0.f);
+    // one lane of wave 1, idle until the MLP step
+    if (tid == WAVE && (RULE == FMX_RULE_ADAM || net_rule == FMX_RULE_ADAM)) walk_step_consts<RULE>(kc, t.h, a.opt, net_rule, i);
     if (wave == 0) {
-      // ---- the FM part of both samples: the arithmetic of k_fm_forward; all row loads together ----
+      // ---- the FM part of the step's samples ----
 #pragma unroll
-      for (int t = 0; t < 2; ++t) {
-#pragma unroll
-        for (int p = 0; p < NP; ++p) {
-          li[t][p] = live[p] ? l_n[t][p] : 0u;
-          x[t][p] = (has_x && live[p]) ? x_n[t][p] : 1.f;
-          ok[t][p] = live[p] && li[t][p] < vocab[p];
-        }
-      }
-#pragma unroll
-      for (int t = 0; t < 2; ++t) {
+      for (int s = 0; s < T; ++s) {
 #pragma unroll
         for (int p = 0; p < NP; ++p) {
-          row[t][p] = load_row_sc1<LAYOUT, RULE>(a.rows + (size_t)(ok[t][p] ? lo[p] + li[t][p] : 0) * a.stride, q, kp, a.zoff);
-          bad = bad || (live[p] && !ok[t][p]);
+          in.li[s][p] = f.live[p] ? next.li[s][p] : 0u;
+          in.x[s][p] = (xs.has && f.live[p]) ? next.x[s][p] : 1.f;
         }
       }
+      if (lane == 0) y_lds = y_n;
+      walk_gather<LAYOUT, RULE>(row, ok, bad, t, f, in.li, q, kp);
       fetch_inputs(i + 1);
-      const float bias_w = bias_weight<LAYOUT>(b0, b1, a.h);
+      const float bias_w = bias_weight<LAYOUT>(b0, b1, t.h);
 #pragma unroll
-      for (int t = 0; t < 2; ++t) {
-        float4 s = splat(0.f), ss = splat(0.f);
-        float fo = 0.f;
-#pragma unroll
-        for (int p = 0; p < NP; ++p) {
-          if (ok[t][p]) {
-            const float4 e = x[t][p] * row[t][p].v;
-            s = s + e;
-            ss = ss + e * e;
-            fo += row[t][p].fo.x * x[t][p];
-          }
-        }
-        fm_field_sums<LPR>(s, ss, fo, lane);
-        S[t] = s;
-        float sbi;
-        const float4 bi = fm_bi<LPR>(s, ss, sbi);
-        fo = __shfl(fo, 0);
+      for (int s = 0; s < T; ++s) {
+        float sbi, fo;
+        const float4 bi = walk_forward<LPR>(row[s], in.x[s], ok[s], lane, S[s], sbi, fo);
         if (lane < LPR) {
-          bi_lds[t * kp + 4 * q] = bi.x;
-          bi_lds[t * kp + 4 * q + 1] = bi.y;
-          bi_lds[t * kp + 4 * q + 2] = bi.z;
-          bi_lds[t * kp + 4 * q + 3] = bi.w;
+          bi_lds[s * kp + 4 * q] = bi.x;
+          bi_lds[s * kp + 4 * q + 1] = bi.y;
+          bi_lds[s * kp + 4 * q + 2] = bi.z;
+          bi_lds[s * kp + 4 * q + 3] = bi.w;
         }
-        if (lane == 0) base_lds[t] = a.fm_term ? fo + sbi + bias_w : fo + bias_w;
+        if (lane == 0) base_lds[s] = a.fm_term ? fo + sbi + bias_w : fo + bias_w;
       }
     }
     __syncthreads();
-    // ---- the pair step of k_mlp_small_pair at B = 2 on LDS-resident parameters ----
+    // ---- the step of k_mlp_small (B = 1) or k_mlp_small_pair (B = 2) on LDS-resident parameters ----
     MlpArgs m{};
     m.params = p_lds;
     m.bi = bi_lds;
     m.base = base_lds;
-    m.pred_out = a.logit ? a.logit + 2 * (size_t)i : nullptr;
-    m.out = a.loss ? a.loss + i : nullptr;
-    m.pair_pred = a.pred + i;
-    m.margin = a.margin;
-    m.h = a.h;
+    m.h = t.h;
     m.inv_b = 1.0f;
-    m.B = 2;
+    m.B = T;
     m.k = a.k;
     m.kp = kp;
     m.hidden = a.hidden;
     m.n_layers = a.n_layers;
-    m.dz_out = dz_lds;
-    m.gbi_out = gbi_lds;
-    m.mode = MLP_MODE_FIT;
-    m.rule = a.rule;
-    if (net_rule == FMX_RULE_SGD) {  // (mlp_small_set_opt)
-      m.rule = FMX_RULE_SGD;
-      m.h.lr = a.opt.lr;
-    } else if (net_adaptive) {
-      m.opt_rule = net_rule;
-      m.m = m_lds;
-      m.v = v_lds;
-      m.oh.lr = net_adam ? uniform_f(kc[3]) : a.opt.lr;
-      m.oh.eps = net_adam ? uniform_f(kc[6]) : a.opt.eps;
-      m.oh.beta1 = net_adam ? uniform_f(kc[4]) : 0.f;
-      m.oh.beta2 = net_adam ? uniform_f(kc[5]) : 0.f;
+    objective(m, i, &y_lds, alpha_lds);
+    if (!hedge) {
+      m.dz_out = dz_lds;
+      m.gbi_out = gbi_lds;
+      m.mode = MLP_MODE_FIT;
+      m.rule = a.rule;
+      walk_net_rule(m, net_rule, p_lds, a.n_params, kc, a.opt);
     }
-    mlp_small_body<true>(m);
+    mlp_small_body<T == 2>(m);
     __syncthreads();
-    if (wave == 0) {
-      // ---- the table update of k_fm_update at B = 2: G_t = dz_t [+ dL/dbi_t], runs as in k_fm_pair_online ----
-      const float dz[2] = {dz_lds[0], dz_lds[1]};
-      float4 G[2];
+    if (wave == 0 && !hedge) {
+      // ---- the table update of k_fm_update at B = T: G_s = dz_s [+ dL/dbi_s] ----
+      float dz[T];
+      float4 G[T];
 #pragma unroll
-      for (int t = 0; t < 2; ++t) {
-        const float4 g4 = {gbi_lds[t * kp + 4 * q], gbi_lds[t * kp + 4 * q + 1], gbi_lds[t * kp + 4 * q + 2], gbi_lds[t * kp + 4 * q + 3]};
-        G[t] = splat(a.fm_term ? dz[t] : 0.f) + g4;
+      for (int s = 0; s < T; ++s) {
+        dz[s] = dz_lds[s];
+        const float4 g4 = {gbi_lds[s * kp + 4 * q], gbi_lds[s * kp + 4 * q + 1], gbi_lds[s * kp + 4 * q + 2], gbi_lds[s * kp + 4 * q + 3]};
+        G[s] = splat(a.fm_term ? dz[s] : 0.f) + g4;
       }
-      fmx_hyper_t h = a.h;
-      if (RULE == FMX_RULE_ADAM) {  // the pair's constants, as update_impl derives them for a launch
+      fmx_hyper_t h = t.h;
+      if (RULE == FMX_RULE_ADAM) {  // the step's constants, as update_impl derives them for a launch
         h.lr = uniform_f(kc[0]);
         h.beta1 = uniform_f(kc[1]);
         h.beta2 = uniform_f(kc[2]);
       }
+      walk_fit<LAYOUT, RULE>(t, f, in.li, ok, row, q, kp, h, [&](int s, int p, float4 &cV, float4 &cA, float &cw) {
+        const float4 xG = in.x[s][p] * G[s];  // the occurrence's terms as update_body forms them with gbi
+        cV = xG * S[s];
+        cA = in.x[s][p] * xG;
+        cw = in.x[s][p] * dz[s];
+      });
+      float db = dz[0];
 #pragma unroll
-      for (int p = 0; p < NP; ++p) {
-        float4 cV[2], cA[2];
-        float cw[2];
-#pragma unroll
-        for (int t = 0; t < 2; ++t) {  // the occurrence's terms as update_body forms them with gbi
-          const float4 xG = x[t][p] * G[t];
-          cV[t] = xG * S[t];
-          cA[t] = x[t][p] * xG;
-          cw[t] = x[t][p] * dz[t];
-        }
-        float *rp0 = a.rows + (size_t)(lo[p] + li[0][p]) * a.stride, *rp1 = a.rows + (size_t)(lo[p] + li[1][p]) * a.stride;
-        if (ok[0][p] && ok[1][p] && li[0][p] == li[1][p]) {  // one run of two occurrences, in sample order
-          update_row<LAYOUT, RULE>(rp0, q, kp, a.zoff, row[0][p], (splat(0.f) + cV[0]) + cV[1], (splat(0.f) + cA[0]) + cA[1],
-                                   (0.f + cw[0]) + cw[1], h);
-        } else {
-          if (ok[0][p]) update_row<LAYOUT, RULE>(rp0, q, kp, a.zoff, row[0][p], splat(0.f) + cV[0], splat(0.f) + cA[0], 0.f + cw[0], h);
-          if (ok[1][p]) update_row<LAYOUT, RULE>(rp1, q, kp, a.zoff, row[1][p], splat(0.f) + cV[1], splat(0.f) + cA[1], 0.f + cw[1], h);
-        }
-      }
-      bias_step<LAYOUT, RULE>(b0, b1, b2, dz[0] + dz[1], h);           // exactly +0
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the row stores are acknowledged before the next pair's loads
+      for (int s = 1; s < T; ++s) db = db + dz[s];  // (a pair's: exactly +0)
+      bias_step<LAYOUT, RULE>(b0, b1, b2, db, h);
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the row stores are acknowledged before the next step's loads
     }
     __syncthreads();
   }
-  for (int i = tid; i < a.n_params; i += blockDim.x) a.params[i] = p_lds[i];
-  if (net_adaptive)
-    for (int i = tid; i < a.n_params; i += blockDim.x) a.opt.v[i] = v_lds[i];
-  if (net_adam)
-    for (int i = tid; i < a.n_params; i += blockDim.x) a.opt.m[i] = m_lds[i];
+  walk_net_stage<true>(p_lds, a.params, a.opt, a.n_params, net_rule);
+  if (hedge && tid < a.n_layers) alpha[tid] = alpha_lds[tid];
   if (wave == 0) {
     const bool any_bad = __ballot(bad) != 0ull;
     if (lane == 0) {
-      a.bias[0] = b0;
-      if (MOM && RULE == FMX_RULE_ADAM) a.bias[1] = b1;
-      if (MOM) a.bias[2] = b2;
-      if (any_bad && a.error) *a.error = 1;
+      if (!hedge) walk_bias_store<LAYOUT, RULE>(t.bias, b0, b1, b2);
+      if (any_bad && t.error) *t.error = 1;
     }
   }
 }
 
+// OPT: the instantiations of fmx_online_run_mlp_opt (has_opt); fmx_online_run_mlp's own carry none of it
+template <int LPR, int LAYOUT, int RULE, bool OPT>
+__global__ __launch_bounds__(256) void k_online_mlp(OnlineMlpArgs a) {
+  mlp_walk<LPR, LAYOUT, RULE, 1>(
+      a, OPT ? a.opt.rule : -1, a.hedge != 0, a.alpha, [&](int i) { return a.y[i]; },
+      [&](MlpArgs &m, int i, const float *y, float *alpha) {
+        m.y = y;
+        m.pred_out = a.pred + i;
+        if (a.hedge) {
+          m.alpha = alpha;
+          m.hedge_b = a.hedge_b;
+          m.hedge_s = a.hedge_s;
+          m.mode = MLP_MODE_HEDGE;
+        } else {
+          m.loss_kind = a.loss_kind;
+        }
+      });
+}
+
+// has_opt is a run-time word here (the weights rules take both forms), so one instantiation per (kp, table rule) serves
+// fmx_online_run_mlp_pair with and without opt
 template <int LPR, int LAYOUT, int RULE>
-void launch_online_np(const OnlineArgs &a, int np, hipStream_t st) {
-  auto launch = [&](auto NP) { hipLaunchKernelGGL((k_fm_online<LPR, LAYOUT, RULE, NP>), dim3(1), dim3(64), 0, st, a); };
-  if (!with_one_of<1, 2, 3>(np, launch)) launch(std::integral_constant<int, 4>{});
+__global__ __launch_bounds__(256) void k_online_mlp_pair(OnlineMlpPairArgs a) {
+  mlp_walk<LPR, LAYOUT, RULE, 2>(
+      a, a.has_opt ? a.opt.rule : -1, false, nullptr, [](int) { return 0.f; },
+      [&](MlpArgs &m, int i, const float *, float *) {
+        m.pred_out = a.logit ? a.logit + 2 * (size_t)i : nullptr;
+        m.out = a.loss ? a.loss + i : nullptr;
+        m.pair_pred = a.pred + i;
+        m.margin = a.margin;
+      });
 }
 
 constexpr int ONLINE_MLP_MAX_PARAMS = 8192;  // floats of MLP parameters kept in LDS by k_online_mlp
 // ... and with the network's moments beside them (fmx_online_run_mlp_opt): the same cap -- params, v and m are then 96 KB of
 // dynamic LDS next to the kernel's 47 KB of static arrays, of the CU's 160 KiB
 constexpr int ONLINE_MLP_OPT_MAX_PARAMS = 8192;
+constexpr int ONLINE_MLP_LDS_BYTES = 3 * ONLINE_MLP_MAX_PARAMS * 4;  // the most a launch asks for: the limit of every instantiation
 
-// the parameter arrays k_online_mlp keeps in LDS: params, v under the network's ADAGRAD / ADAM, m under its ADAM
-inline int online_mlp_arrays(const OnlineMlpArgs &a) {
-  if (!a.has_opt || a.opt.rule == FMX_RULE_SGD) return 1;
-  return a.opt.rule == FMX_RULE_ADAM ? 3 : 2;
-}
+template <class Args>
+size_t online_mlp_lds(const Args &a) { return (size_t)walk_net_arrays(a.has_opt ? a.opt.rule : -1) * a.n_params * 4; }
 
 template <int LPR, int LAYOUT, int RULE, bool OPT>
-void launch_online_mlp_k(const OnlineMlpArgs &a, hipStream_t st) {
-  static int raised = 0;  // arrays of ONLINE_MLP_MAX_PARAMS floats the kernel may ask for so far
-  const int arrays = online_mlp_arrays(a);
-  if (raised < arrays) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_online_mlp<LPR, LAYOUT, RULE, OPT>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, arrays * ONLINE_MLP_MAX_PARAMS * 4);
-    raised = arrays;
-  }
-  hipLaunchKernelGGL((k_online_mlp<LPR, LAYOUT, RULE, OPT>), dim3(1), dim3(256), (size_t)arrays * a.n_params * 4, st, a);
+int launch_online_mlp_k(const OnlineMlpArgs &a, hipStream_t st) {
+  if (int rc = raise_lds_limit<k_online_mlp<LPR, LAYOUT, RULE, OPT>>(ONLINE_MLP_LDS_BYTES, "k_online_mlp")) return rc;
+  hipLaunchKernelGGL((k_online_mlp<LPR, LAYOUT, RULE, OPT>), dim3(1), dim3(256), online_mlp_lds(a), st, a);
+  return check_launch("k_online_mlp");
 }
 
 template <int LPR, int LAYOUT, int RULE>
-void launch_online_mlp_pair_k(const OnlineMlpPairArgs &a, hipStream_t st) {
-  static int raised = 0;  // (launch_online_mlp_k)
-  const int arrays = !a.has_opt || a.opt.rule == FMX_RULE_SGD ? 1 : a.opt.rule == FMX_RULE_ADAM ? 3 : 2;
-  if (raised < arrays) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_online_mlp_pair<LPR, LAYOUT, RULE>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, arrays * ONLINE_MLP_MAX_PARAMS * 4);
-    raised = arrays;
+int launch_online_mlp_pair_k(const OnlineMlpPairArgs &a, hipStream_t st) {
+  if (int rc = raise_lds_limit<k_online_mlp_pair<LPR, LAYOUT, RULE>>(ONLINE_MLP_LDS_BYTES, "k_online_mlp_pair")) return rc;
+  hipLaunchKernelGGL((k_online_mlp_pair<LPR, LAYOUT, RULE>), dim3(1), dim3(256), online_mlp_lds(a), st, a);
+  return check_launch("k_online_mlp_pair");
+}
+
+// the table part of the network walkers' arguments and what both name alike; false: the call keeps the queued launches (the
+// network does not fit in LDS, or a sample's fields do not fit one wavefront)
+template <class Args>
+bool online_mlp_args(Args &a, const fmx_table_t *table, const fmx_hyper_t *hyper, int32_t rule, const fmx_mlp_t *mlp, int32_t fm_term,
+                     const int32_t *idx, const float *xv, int32_t *error, int32_t N, const fmx_mlp_opt_t *opt) {
+  const long long n_params = mlp_n_params(mlp);
+  if (!tune().online_persistent || n_params > (opt ? ONLINE_MLP_OPT_MAX_PARAMS : ONLINE_MLP_MAX_PARAMS) ||
+      walk_passes(table) > WALK_MAX_NP)
+    return false;
+  memset(&a, 0, sizeof(a));
+  a.t = walk_table(table, hyper, opt ? rule : -1, idx, xv, error, N);  // ADAM tables come with opt alone
+  a.params = mlp->params;
+  a.n_params = (int32_t)n_params;
+  a.k = mlp->k;
+  a.hidden = mlp->hidden;
+  a.n_layers = mlp->n_layers;
+  a.fm_term = fm_term;
+  a.rule = rule;
+  if (opt) {
+    a.has_opt = 1;
+    a.opt = *opt;
   }
-  hipLaunchKernelGGL((k_online_mlp_pair<LPR, LAYOUT, RULE>), dim3(1), dim3(256), (size_t)arrays * a.n_params * 4, st, a);
-}
-
-}  // namespace
-
-extern "C" {
-
-int fmx_fm_online_run(const fmx_table_t *table, const fmx_hyper_t *hyper, int32_t rule, int32_t loss_kind,
-                      const int32_t *idx, const float *xv, const float *y, int32_t N, uint8_t *pred_out, float *loss_out,
-                      int32_t *error, fmx_stream_t stream) {
-  if (int rc = check_table(table)) return rc;
-  if (int rc = check_rule(table, rule)) return rc;
-  if (mapped(table)) return fail(FMX_ERR_UNSUPPORTED, "fmx_fm_online_run: tables whose fields are pieces of index columns are not taken");
-  if (N < 0) return fail(FMX_ERR_ARG, "fmx_fm_online_run: N must be >= 0");
-  if (N == 0) return FMX_OK;  // an empty stream (its buffers may be null)
-  if (!hyper || !idx || !y || !pred_out) return fail(FMX_ERR_ARG, "fmx_fm_online_run: null argument");
-  if (int rc = check_adam(hyper, rule, N)) return rc;
-  if (loss_kind != FMX_LOSS_BCE_LOGITS && loss_kind != FMX_LOSS_BCE_SIGMOID) return fail(FMX_ERR_ARG, "fit needs a loss");
-  const int lpr = lpr_of(table->kp), slots = WAVE / lpr;
-  const int np = (table->n_fields + slots - 1) / slots;
-  if (np > 4)
-    return fail(FMX_ERR_UNSUPPORTED, "fmx_fm_online_run: %d fields at kp = %d exceed the %d rows one wavefront holds", table->n_fields,
-                table->kp, 4 * slots);
-  OnlineArgs a;
-  a.rows = table->rows;
-  a.foff = table->field_offsets;
-  a.bias = table->bias;
-  a.idx = idx;
-  a.xv = xv;
-  a.y = y;
-  a.pred = pred_out;
-  a.loss = loss_out;
-  a.error = error;
-  a.h = kernel_hyper(hyper, rule);  // ADAM: the kernel derives each sample's constants from lr, beta1, beta2, step
-  a.N = N;
-  a.F = table->n_fields;
-  a.stride = table->row_stride;
-  a.zoff = table->z_offset;
-  a.loss_kind = loss_kind;
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  with_lpr(table->kp, [&](auto LPR) {
-    with_rule(rule, [&](auto LAYOUT, auto RULE) { launch_online_np<LPR, LAYOUT, RULE>(a, np, st); });
-  });
-  return check_launch("k_fm_online");
-}
-
-int fmx_fm_pair_online_run(const fmx_table_t *table, const fmx_hyper_t *hyper, int32_t rule, const int32_t *idx, const float *xv,
-                           int32_t N, float margin, uint8_t *pred_out, float *logit_out, float *loss_out, int32_t *error,
-                           fmx_stream_t stream) {
-  const char *who = "fmx_fm_pair_online_run";
-  if (int rc = check_pair_args(table, hyper, idx, N, "N", margin, who)) return rc;
-  if (int rc = check_rule(table, rule)) return named(rc, who);
-  if (!pred_out) return fail(FMX_ERR_ARG, "%s: pred_out is null", who);
-  if (N > INT32_MAX / 2) return fail(FMX_ERR_ARG, "%s: N = %d: 2 * N rows exceed int32", who, N);
-  if (int rc = check_adam(hyper, rule, N)) return named(rc, who);
-  // two samples' rows in registers: 2 x 4 passes of RowRegs fit the wavefront's 512 registers, so the limit is fmx_fm_online_run's
-  const int lpr = lpr_of(table->kp), slots = WAVE / lpr;
-  const int np = (table->n_fields + slots - 1) / slots;
-  if (np > 4)
-    return fail(FMX_ERR_UNSUPPORTED, "%s: %d fields at kp = %d exceed the %d rows per sample one wavefront holds", who, table->n_fields,
-                table->kp, 4 * slots);
-  PairOnlineArgs a;
-  a.rows = table->rows;
-  a.foff = table->field_offsets;
-  a.bias = table->bias;
-  a.idx = idx;
-  a.xv = xv;
-  a.pred = pred_out;
-  a.logit = logit_out;
-  a.loss = loss_out;
-  a.error = error;
-  a.h = kernel_hyper(hyper, rule);  // ADAM: the kernel derives each pair's constants from lr, beta1, beta2, step
-  a.N = N;
-  a.F = table->n_fields;
-  a.stride = table->row_stride;
-  a.zoff = table->z_offset;
-  a.margin = margin;
-  with_lpr(table->kp, [&](auto LPR) {
-    with_rule(rule, [&](auto LAYOUT, auto RULE) { launch_pair_online_np<LPR, LAYOUT, RULE>(a, np, static_cast<hipStream_t>(stream)); });
-  });
-  return check_launch("k_fm_pair_online");
+  return true;
 }
 
 static int mlp_launch(const fmx_mlp_t *mlp, MlpArgs &a, int32_t B, int32_t kp, fmx_stream_t stream, const char *who, bool pair = false) {
@@ -1128,6 +662,110 @@ static int mlp_launch(const fmx_mlp_t *mlp, MlpArgs &a, int32_t B, int32_t kp, f
   }
   hipLaunchKernelGGL(k_mlp_small, dim3(1), dim3(256), 0, static_cast<hipStream_t>(stream), a);
   return check_launch("k_mlp_small");
+}
+
+// The queued form of the network walkers: per step of R rows forward(B = R), k_mlp_small (or _pair), sort(B = R), update(B = R), no
+// host synchronisation.  set_mode(m, i): the mode's fields of step i's MlpArgs; no_update: Hedge trains the hidden layers and alpha
+// only (reference deepfm_onn.py:109-154).  rule_t: the rule whose step count the tables' hyper-parameters follow (-1: none).
+template <class Mode>
+int online_mlp_queued(const fmx_table_t *table, const fmx_hyper_t *hyper, int32_t rule, int rule_t, const fmx_mlp_t *mlp, int32_t fm_term,
+                      const int32_t *idx, const float *xv, int32_t N, int R, void *workspace, const fmx_fwd_out_t *fwd, float *scratch,
+                      bool no_update, fmx_stream_t stream, const char *who, Mode set_mode) {
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const Workspace w = carve(table, R, workspace);
+  const size_t F = (size_t)table->n_fields;
+  fmx_fwd_out_t f1 = *fwd;  // R samples: dense outputs
+  f1.sample_ld = 0;
+  float *dz = scratch, *gbi = scratch + 8;
+  for (int i = 0; i < N; ++i) {
+    const int32_t *idx_i = idx + (size_t)i * R * F;
+    const float *xv_i = xv ? xv + (size_t)i * R * F : nullptr;
+    if (int rc = forward_impl(table, hyper, idx_i, xv_i, nullptr, R, FMX_LOSS_NONE, 1.0f, &f1, st)) return rc;
+    MlpArgs a{};
+    a.bi = fwd->bi;
+    a.base = fm_term ? fwd->logit : fwd->sfirst;
+    if (!fm_term) {  // NFM: the logit without the MLP term is the first-order sum plus the bias weight
+      a.base_bias = table->bias;
+      a.base_bias_ftrl = table->layout == FMX_LAYOUT_FTRL;
+      a.h_table = kernel_hyper(hyper, -1);
+    }
+    a.dz_out = dz;
+    a.gbi_out = gbi;
+    set_mode(a, i);
+    if (int rc = mlp_launch(mlp, a, R, table->kp, stream, who, R == 2)) return rc;
+    if (no_update) continue;
+    if (int rc = sort_impl(table, idx_i, R, w.sorted, w.runs, fwd->error, st)) return rc;
+    const fmx_hyper_t hs = hyper_at_step(hyper, rule_t, i);  // step i is step t = hyper->step + i + 1 of the tables
+    if (int rc = update_impl(table, &hs, rule, w, w.sorted, xv_i, fwd->S, dz, fm_term ? dz : nullptr, gbi, R, nullptr, 1.0f, nullptr, st,
+                             nullptr, 0, fwd->error))
+      return rc;
+  }
+  return FMX_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int fmx_fm_online_run(const fmx_table_t *table, const fmx_hyper_t *hyper, int32_t rule, int32_t loss_kind,
+                      const int32_t *idx, const float *xv, const float *y, int32_t N, uint8_t *pred_out, float *loss_out,
+                      int32_t *error, fmx_stream_t stream) {
+  if (int rc = check_table(table)) return rc;
+  if (int rc = check_rule(table, rule)) return rc;
+  if (mapped(table)) return fail(FMX_ERR_UNSUPPORTED, "fmx_fm_online_run: tables whose fields are pieces of index columns are not taken");
+  if (N < 0) return fail(FMX_ERR_ARG, "fmx_fm_online_run: N must be >= 0");
+  if (N == 0) return FMX_OK;  // an empty stream (its buffers may be null)
+  if (!hyper || !idx || !y || !pred_out) return fail(FMX_ERR_ARG, "fmx_fm_online_run: null argument");
+  if (int rc = check_adam(hyper, rule, N)) return rc;
+  if (loss_kind != FMX_LOSS_BCE_LOGITS && loss_kind != FMX_LOSS_BCE_SIGMOID) return fail(FMX_ERR_ARG, "fit needs a loss");
+  int max_fields;
+  const int np = walk_passes(table, &max_fields);
+  if (np > WALK_MAX_NP)
+    return fail(FMX_ERR_UNSUPPORTED, "fmx_fm_online_run: %d fields at kp = %d exceed the %d rows one wavefront holds", table->n_fields,
+                table->kp, max_fields);
+  OnlineArgs a;
+  a.t = walk_table(table, hyper, rule, idx, xv, error, N);
+  a.y = y;
+  a.pred = pred_out;
+  a.loss = loss_out;
+  a.loss_kind = loss_kind;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  with_lpr(table->kp, [&](auto LPR) {
+    with_rule(rule, [&](auto LAYOUT, auto RULE) {
+      with_walk_np(np, [&](auto NP) { hipLaunchKernelGGL((k_fm_online<LPR, LAYOUT, RULE, NP>), dim3(1), dim3(64), 0, st, a); });
+    });
+  });
+  return check_launch("k_fm_online");
+}
+
+int fmx_fm_pair_online_run(const fmx_table_t *table, const fmx_hyper_t *hyper, int32_t rule, const int32_t *idx, const float *xv,
+                           int32_t N, float margin, uint8_t *pred_out, float *logit_out, float *loss_out, int32_t *error,
+                           fmx_stream_t stream) {
+  const char *who = "fmx_fm_pair_online_run";
+  if (int rc = check_pair_args(table, hyper, idx, N, "N", margin, who)) return rc;
+  if (int rc = check_rule(table, rule)) return named(rc, who);
+  if (!pred_out) return fail(FMX_ERR_ARG, "%s: pred_out is null", who);
+  if (N > INT32_MAX / 2) return fail(FMX_ERR_ARG, "%s: N = %d: 2 * N rows exceed int32", who, N);
+  if (int rc = check_adam(hyper, rule, N)) return named(rc, who);
+  // two samples' rows in registers: 2 x 4 passes of RowRegs fit the wavefront's 512 registers, so the limit is fmx_fm_online_run's
+  int max_fields;
+  const int np = walk_passes(table, &max_fields);
+  if (np > WALK_MAX_NP)
+    return fail(FMX_ERR_UNSUPPORTED, "%s: %d fields at kp = %d exceed the %d rows per sample one wavefront holds", who, table->n_fields,
+                table->kp, max_fields);
+  PairOnlineArgs a;
+  a.t = walk_table(table, hyper, rule, idx, xv, error, N);
+  a.pred = pred_out;
+  a.logit = logit_out;
+  a.loss = loss_out;
+  a.margin = margin;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  with_lpr(table->kp, [&](auto LPR) {
+    with_rule(rule, [&](auto LAYOUT, auto RULE) {
+      with_walk_np(np, [&](auto NP) { hipLaunchKernelGGL((k_fm_pair_online<LPR, LAYOUT, RULE, NP>), dim3(1), dim3(64), 0, st, a); });
+    });
+  });
+  return check_launch("k_fm_pair_online");
 }
 
 // the network's optimizer state for a call of n_steps steps (fmx_mlp_fit_opt, fmx_online_run_mlp_opt): mlp_opt_check's checks of opt
@@ -1172,106 +810,57 @@ static int online_run_mlp_impl(const fmx_table_t *table, const fmx_hyper_t *hype
     return fail(FMX_ERR_UNSUPPORTED, "%s: k + layers <= %d", who, MLP_MAX_W);
   }
   if (N < 0) return fail(FMX_ERR_ARG, "%s: N must be >= 0", who);
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  {  // one workgroup walks the stream when the network fits in LDS and the fields fit one wavefront (k_online_mlp)
-    long long n_params = 0;
-    for (int l = 0; l < mlp->n_layers; ++l) n_params += (long long)mlp->hidden * (l == 0 ? mlp->k : mlp->hidden) + mlp->hidden;
-    const int lpr = lpr_of(table->kp), slots = WAVE / lpr;
-    // a fit step on FTRL tables keeps the queued launches; the MOMENTS rules are instantiated for the _opt call alone
-    const bool tables_ok = hedge || table->layout == FMX_LAYOUT_WEIGHTS || (with_opt && table->layout == FMX_LAYOUT_MOMENTS);
-    if (tune().online_persistent && n_params <= (with_opt ? ONLINE_MLP_OPT_MAX_PARAMS : ONLINE_MLP_MAX_PARAMS) &&
-        table->n_fields <= 4 * slots && tables_ok && mlp->hidden <= MLP_MAX_W && mlp->n_layers <= MLP_MAX_L &&
-        mlp->k <= MLP_MAX_W - 1 && N > 0) {
-      OnlineMlpArgs a;
-      memset(&a, 0, sizeof(a));
-      a.rows = table->rows;
-      a.foff = table->field_offsets;
-      a.bias = table->bias;
-      a.idx = idx;
-      a.xv = xv;
-      a.y = y;
-      a.pred = pred_out;
-      a.error = fwd->error;
-      a.params = mlp->params;
-      a.alpha = alpha;
-      a.h = kernel_hyper(hyper, with_opt ? rule : -1);  // ADAM tables: the kernel derives each sample's constants from lr, beta1, beta2, step
-      a.hedge_b = hedge_b;
-      a.hedge_s = hedge_s;
-      a.N = N;
-      a.F = table->n_fields;
-      a.stride = table->row_stride;
-      a.zoff = table->z_offset;
-      a.n_params = (int32_t)n_params;
-      a.k = mlp->k;
-      a.hidden = mlp->hidden;
-      a.n_layers = mlp->n_layers;
-      a.hedge = hedge;
-      a.fm_term = fm_term;
-      a.rule = rule;
-      a.loss_kind = loss_kind;
-      if (with_opt) {
-        a.has_opt = 1;
-        a.opt = *opt;
-        with_lpr(table->kp, [&](auto LPR) {
-          with_rule(rule, [&](auto LAYOUT, auto RULE) {
-            if constexpr (LAYOUT != FMX_LAYOUT_FTRL) launch_online_mlp_k<LPR, LAYOUT, RULE, true>(a, st);  // (tables_ok: never FTRL)
-          });
-        });
-        return check_launch("k_online_mlp");
-      }
-      // FTRL-layout tables are read only (Hedge): FTRL pairs with that layout alone, any rule but SGD takes SIGNADAM (a MOMENTS
-      // table, read only too, is read as a weights one)
-      const int kernel_rule = table->layout == FMX_LAYOUT_FTRL ? FMX_RULE_FTRL : rule == FMX_RULE_SGD ? FMX_RULE_SGD : FMX_RULE_SIGNADAM;
+  // one workgroup walks the stream when the network fits in LDS and the fields fit one wavefront (k_online_mlp).  A fit step on
+  // FTRL tables keeps the queued launches; the MOMENTS rules are instantiated for the _opt call alone
+  const bool tables_ok = hedge || table->layout == FMX_LAYOUT_WEIGHTS || (with_opt && table->layout == FMX_LAYOUT_MOMENTS);
+  OnlineMlpArgs a;
+  if (tables_ok && mlp->hidden <= MLP_MAX_W && mlp->n_layers <= MLP_MAX_L && mlp->k <= MLP_MAX_W - 1 && N > 0 &&
+      online_mlp_args(a, table, hyper, rule, mlp, fm_term, idx, xv, fwd->error, N, opt)) {
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    a.y = y;
+    a.pred = pred_out;
+    a.alpha = alpha;
+    a.hedge_b = hedge_b;
+    a.hedge_s = hedge_s;
+    a.hedge = hedge;
+    a.loss_kind = loss_kind;
+    int rc = FMX_OK;
+    if (with_opt) {
       with_lpr(table->kp, [&](auto LPR) {
-        with_rule_wf(kernel_rule, [&](auto LAYOUT, auto RULE) { launch_online_mlp_k<LPR, LAYOUT, RULE, false>(a, st); });
+        with_rule(rule, [&](auto LAYOUT, auto RULE) {
+          if constexpr (LAYOUT != FMX_LAYOUT_FTRL) rc = launch_online_mlp_k<LPR, LAYOUT, RULE, true>(a, st);  // (tables_ok: never FTRL)
+        });
       });
-      return check_launch("k_online_mlp");
+      return rc;
     }
+    // FTRL-layout tables are read only (Hedge): FTRL pairs with that layout alone, any rule but SGD takes SIGNADAM (a MOMENTS
+    // table, read only too, is read as a weights one)
+    const int kernel_rule = table->layout == FMX_LAYOUT_FTRL ? FMX_RULE_FTRL : rule == FMX_RULE_SGD ? FMX_RULE_SGD : FMX_RULE_SIGNADAM;
+    with_lpr(table->kp, [&](auto LPR) {
+      with_rule_wf(kernel_rule, [&](auto LAYOUT, auto RULE) { rc = launch_online_mlp_k<LPR, LAYOUT, RULE, false>(a, st); });
+    });
+    return rc;
   }
   if (int rc = check_workspace(table, 1, workspace, workspace_bytes, who)) return rc;
-  const Workspace w = carve(table, 1, workspace);
-  const size_t F = (size_t)table->n_fields;
-  fmx_fwd_out_t f1 = *fwd;  // one sample: dense outputs
-  f1.sample_ld = 0;
-  float *dz = scratch, *gbi = scratch + 8;
-  for (int i = 0; i < N; ++i) {
-    const int32_t *idx_i = idx + (size_t)i * F;
-    const float *xv_i = xv ? xv + (size_t)i * F : nullptr;
-    if (int rc = forward_impl(table, hyper, idx_i, xv_i, nullptr, 1, FMX_LOSS_NONE, 1.0f, &f1, st)) return rc;
-    MlpArgs a{};
-    a.bi = fwd->bi;
-    a.base = fm_term ? fwd->logit : fwd->sfirst;
-    if (!fm_term) {  // NFM: the logit without the MLP term is the first-order sum plus the bias weight
-      a.base_bias = table->bias;
-      a.base_bias_ftrl = table->layout == FMX_LAYOUT_FTRL;
-      a.h_table = kernel_hyper(hyper, -1);
-    }
-    a.y = y + i;
-    a.pred_out = pred_out + i;
-    a.h = hyper_for(hyper, -1);
-    a.inv_b = 1.0f;
-    if (hedge) {
-      a.alpha = alpha;
-      a.hedge_b = hedge_b;
-      a.hedge_s = hedge_s;
-      a.mode = MLP_MODE_HEDGE;
-    } else {
-      a.dz_out = dz;
-      a.gbi_out = gbi;
-      a.mode = MLP_MODE_FIT;
-      a.rule = rule;
-      a.loss_kind = loss_kind;
-      if (with_opt) mlp_small_set_opt(a, *opt, opt->step + i + 1);  // sample i of the call is step t = opt->step + i + 1 of the network
-    }
-    if (int rc = mlp_launch(mlp, a, 1, table->kp, stream, who)) return rc;
-    if (hedge) continue;  // Hedge trains the hidden layers and alpha only (reference deepfm_onn.py:109-154)
-    if (int rc = sort_impl(table, idx_i, 1, w.sorted, w.runs, fwd->error, st)) return rc;
-    const fmx_hyper_t hs = hyper_at_step(hyper, with_opt ? rule : -1, i);  // ... and step t = hyper->step + i + 1 of the tables
-    if (int rc = update_impl(table, &hs, rule, w, w.sorted, xv_i, fwd->S, dz, fm_term ? dz : nullptr, gbi, 1, nullptr, 1.0f, nullptr,
-                             st, nullptr, 0, fwd->error))
-      return rc;
-  }
-  return FMX_OK;
+  return online_mlp_queued(table, hyper, rule, with_opt ? rule : -1, mlp, fm_term, idx, xv, N, 1, workspace, fwd, scratch, hedge != 0,
+                           stream, who, [&](MlpArgs &m, int i) {
+                             m.y = y + i;
+                             m.pred_out = pred_out + i;
+                             m.h = hyper_for(hyper, -1);
+                             m.inv_b = 1.0f;
+                             if (hedge) {
+                               m.alpha = alpha;
+                               m.hedge_b = hedge_b;
+                               m.hedge_s = hedge_s;
+                               m.mode = MLP_MODE_HEDGE;
+                               return;
+                             }
+                             m.mode = MLP_MODE_FIT;
+                             m.rule = rule;
+                             m.loss_kind = loss_kind;
+                             // sample i of the call is step t = opt->step + i + 1 of the network
+                             if (with_opt) mlp_small_set_opt(m, *opt, opt->step + i + 1);
+                           });
 }
 
 int fmx_online_run_mlp(const fmx_table_t *table, const fmx_hyper_t *hyper, int32_t rule, int32_t loss_kind,
@@ -1418,81 +1007,29 @@ int fmx_online_run_mlp_pair(const fmx_table_t *table, const fmx_hyper_t *hyper, 
   if (int rc = check_sort_geometry(table, 2)) return named(rc, who);
   if (int rc = check_workspace(table, 2, workspace, workspace_bytes, who)) return rc;
   if (N == 0) return FMX_OK;
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  {  // one workgroup walks the stream when the network fits in LDS and both samples' fields fit one wavefront (k_online_mlp_pair)
-    long long n_params = 0;
-    for (int l = 0; l < mlp->n_layers; ++l) n_params += (long long)mlp->hidden * (l == 0 ? mlp->k : mlp->hidden) + mlp->hidden;
-    const int slots = WAVE / lpr_of(table->kp);
-    if (tune().online_persistent && n_params <= ONLINE_MLP_OPT_MAX_PARAMS && table->n_fields <= 4 * slots &&
-        table->layout != FMX_LAYOUT_FTRL) {
-      OnlineMlpPairArgs a;
-      memset(&a, 0, sizeof(a));
-      a.rows = table->rows;
-      a.foff = table->field_offsets;
-      a.bias = table->bias;
-      a.idx = idx;
-      a.xv = xv;
-      a.pred = pred_out;
-      a.logit = logit_out;
-      a.loss = loss_out;
-      a.error = fwd->error;
-      a.params = mlp->params;
-      a.h = kernel_hyper(hyper, opt ? rule : -1);  // ADAM tables: the kernel derives each pair's constants from lr, beta1, beta2, step
-      a.N = N;
-      a.F = table->n_fields;
-      a.stride = table->row_stride;
-      a.zoff = table->z_offset;
-      a.n_params = (int32_t)n_params;
-      a.k = mlp->k;
-      a.hidden = mlp->hidden;
-      a.n_layers = mlp->n_layers;
-      a.fm_term = fm_term;
-      a.rule = rule;
-      a.margin = margin;
-      if (opt) {
-        a.has_opt = 1;
-        a.opt = *opt;
-      }
-      with_lpr(table->kp, [&](auto LPR) {
-        with_rule(rule, [&](auto LAYOUT, auto RULE) {
-          if constexpr (LAYOUT != FMX_LAYOUT_FTRL) launch_online_mlp_pair_k<LPR, LAYOUT, RULE>(a, st);  // (never FTRL here)
-        });
+  // one workgroup walks the stream when the network fits in LDS and both samples' fields fit one wavefront (k_online_mlp_pair)
+  OnlineMlpPairArgs a;
+  if (table->layout != FMX_LAYOUT_FTRL && online_mlp_args(a, table, hyper, rule, mlp, fm_term, idx, xv, fwd->error, N, opt)) {
+    a.pred = pred_out;
+    a.logit = logit_out;
+    a.loss = loss_out;
+    a.margin = margin;
+    int rc = FMX_OK;
+    with_lpr(table->kp, [&](auto LPR) {
+      with_rule(rule, [&](auto LAYOUT, auto RULE) {
+        if constexpr (LAYOUT != FMX_LAYOUT_FTRL)  // (never FTRL here)
+          rc = launch_online_mlp_pair_k<LPR, LAYOUT, RULE>(a, static_cast<hipStream_t>(stream));
       });
-      return check_launch("k_online_mlp_pair");
-    }
+    });
+    return rc;
   }
-  // the queued form: per pair forward(B = 2), k_mlp_small_pair, sort(B = 2), update(B = 2), no host synchronisation
-  const Workspace w = carve(table, 2, workspace);
-  const size_t F = (size_t)table->n_fields;
-  fmx_fwd_out_t f2 = *fwd;  // two samples: dense outputs
-  f2.sample_ld = 0;
-  float *dz = scratch, *gbi = scratch + 8;
-  for (int i = 0; i < N; ++i) {
-    const int32_t *idx_i = idx + (size_t)i * 2 * F;
-    const float *xv_i = xv ? xv + (size_t)i * 2 * F : nullptr;
-    if (int rc = forward_impl(table, hyper, idx_i, xv_i, nullptr, 2, FMX_LOSS_NONE, 1.0f, &f2, st)) return rc;
-    MlpArgs a{};
-    a.bi = fwd->bi;
-    a.base = fm_term ? fwd->logit : fwd->sfirst;
-    if (!fm_term) {  // NFM: the logit without the MLP term is the first-order sum plus the bias weight
-      a.base_bias = table->bias;
-      a.base_bias_ftrl = table->layout == FMX_LAYOUT_FTRL;
-      a.h_table = kernel_hyper(hyper, -1);
-    }
-    a.pred_out = logit_out ? logit_out + (size_t)i * 2 : nullptr;
-    a.out = loss_out ? loss_out + i : nullptr;
-    a.pair_pred = pred_out + i;
-    a.dz_out = dz;
-    a.gbi_out = gbi;
-    mlp_pair_fit_args(a, hyper, rule, margin, 1.0f, opt, opt ? opt->step + i + 1 : 0);
-    if (int rc = mlp_launch(mlp, a, 2, table->kp, stream, who, true)) return rc;
-    if (int rc = sort_impl(table, idx_i, 2, w.sorted, w.runs, fwd->error, st)) return rc;
-    const fmx_hyper_t hs = hyper_at_step(hyper, opt ? rule : -1, i);  // pair i is step t = hyper->step + i + 1 of the tables
-    if (int rc = update_impl(table, &hs, rule, w, w.sorted, xv_i, fwd->S, dz, fm_term ? dz : nullptr, gbi, 2, nullptr, 1.0f, nullptr, st,
-                             nullptr, 0, fwd->error))
-      return rc;
-  }
-  return FMX_OK;
+  return online_mlp_queued(table, hyper, rule, opt ? rule : -1, mlp, fm_term, idx, xv, N, 2, workspace, fwd, scratch, false, stream, who,
+                           [&](MlpArgs &m, int i) {
+                             m.pred_out = logit_out ? logit_out + (size_t)i * 2 : nullptr;
+                             m.out = loss_out ? loss_out + i : nullptr;
+                             m.pair_pred = pred_out + i;
+                             mlp_pair_fit_args(m, hyper, rule, margin, 1.0f, opt, opt ? opt->step + i + 1 : 0);
+                           });
 }
 
 int fmx_mlp_hedge_fit(const fmx_mlp_t *mlp, float lr, float hedge_b, float hedge_s, float *alpha, const float *bi, int32_t kp,

@@ -634,11 +634,25 @@ def test_inline_fixup_matches_second_launch_small_shapes(fmx, k, B, rule):
         np.testing.assert_array_equal(a, b)
 
 
-@pytest.mark.parametrize("rule,k,real_x", [("signadam", 10, False), ("sgd", 4, True), ("ftrl", 16, False), ("ftrl", 8, True)])
-def test_online_run_equals_single_sample_steps(fmx, rule, k, real_x):
+# The walkers' field geometry: a wavefront takes 64 / (kp / 4) fields per pass and holds at most four passes.  (k, F) with one full
+# pass, two passes with a partly live second one, and four passes exactly at the field limit; vocabularies of 3 - 9 rows, so
+# consecutive steps (and the two samples of a pair) share rows.  MIXED_SIZES' 11 fields give one or three passes only.
+WALK_GEOMETRY = [(64, 4), (64, 5), (64, 16), (16, 16), (16, 17), (16, 64)]
+WALK_STEPS = 24
+
+
+def walk_sizes(F):
+    return [3 + i % 7 for i in range(F)]
+
+
+@pytest.mark.parametrize("rule,k,real_x,F", [
+    pytest.param("signadam", 10, False, None, id="signadam-10-False"), pytest.param("sgd", 4, True, None, id="sgd-4-True"),
+    pytest.param("ftrl", 16, False, None, id="ftrl-16-False"), pytest.param("ftrl", 8, True, None, id="ftrl-8-True")] +
+    [(rule, k, True, F) for k, F in WALK_GEOMETRY for rule in ("sgd", "ftrl")])
+def test_online_run_equals_single_sample_steps(fmx, rule, k, real_x, F):
     """fmx_fm_online_run (one wavefront walking the stream: predict, then fit, per sample) leaves the table bit-identical
     to N calls of fmx_fm_step with B = 1, and its predictions are sigmoid(logit) > 0.5 of the forward before each step."""
-    sizes, N = MIXED_SIZES, 300
+    sizes, N = (MIXED_SIZES, 300) if F is None else (walk_sizes(F), WALK_STEPS)
     pr = make_problem(sizes, k, N, seed=77, real_x=real_x, zipf=True)        # skewed: consecutive samples share rows
     loss_kind = "sigmoid"
 

@@ -12,7 +12,7 @@ import torch
 from oracle.fm_oracle import EPS32
 from helpers import assert_ftrl_step_within_f64, assert_within_f64
 from pair_f64 import pair_loss_f64, pair_step_f64
-from test_kernels_gpu import HYP, ftrl_state, ftrl_table, make_problem, weights_table
+from test_kernels_gpu import HYP, WALK_GEOMETRY, WALK_STEPS, ftrl_state, ftrl_table, make_problem, walk_sizes, weights_table
 
 pytestmark = pytest.mark.gpu
 
@@ -285,11 +285,15 @@ def stream_is_its_steps(fmx, rule, shape, B, n_pool, n_steps, own_stream=False):
 
 
 # ---- 6. the online loop is N steps of one pair ----
-@pytest.mark.parametrize("rule", list(RULES))
-@pytest.mark.parametrize("shape", ["a", "b", "c"])
+# ... and over the walkers' field geometry (test_kernels_gpu.WALK_GEOMETRY): one, two and four passes, a partly live last pass
+WALK_SHAPES = {f"k{k}-F{F}": (walk_sizes(F), k) for k, F in WALK_GEOMETRY}
+
+
+@pytest.mark.parametrize("shape,rule", [(shape, rule) for shape in ["a", "b", "c"] for rule in RULES] +
+                         [(shape, rule) for shape in WALK_SHAPES for rule in ("signadam", "adam")])
 def test_online_run_is_single_pair_steps(fmx, rule, shape):
-    sizes, k = SHAPES[shape]
-    N = 40
+    sizes, k = SHAPES[shape] if shape in SHAPES else WALK_SHAPES[shape]
+    N = 40 if shape in SHAPES else WALK_STEPS
     margin, real_x = (0.1 if shape == "b" else 0.0), shape != "b"
     rows, x, _ = make_pairs(sizes, N, seed=9, n_item=2, real_x=real_x, free_context=True)
     t1, _ = build_table(fmx, sizes, k, RULES[rule])

@@ -13,11 +13,12 @@ Each part runs in a child process of its own under a time limit; the first that 
   python tools/pair_times.py [--steps N] [--reps R] [--pairs N] [--loop-pairs M] [--out FILE]
 
   --ab-lib PATH   instead of the above: the stream walkers' instantiations one by one (k_fm_pair_online at every kp, under signadam
-            and sgd, at 2, 3 and 4 fields per lane group; k_fm_online at kp = 4; two more as controls), this tree's library against
-            another build of the same ABI at PATH, for a change that moved their instruction streams.  Fresh child processes
-            alternate PATH, this tree, PATH, ... (--ab-rounds each); every child times every instantiation (median of --reps calls
-            after a warm call) and sums the table it leaves.  Writes --out (give one): per instantiation both sides' us per item,
-            the spread of PATH's processes (max - min), the difference, and whether the tables' sums agree."""
+            and sgd, at 2, 3 and 4 fields per lane group; k_fm_online at kp = 4, 16 and 64; two more as controls), this tree's
+            library against another build of the same ABI at PATH, for a change that moved their instruction streams.  Fresh
+            child processes alternate PATH, this tree, PATH, ... (--ab-rounds each; --ab-this-first: this tree, PATH, ...); every
+            child times every instantiation (median of --reps calls after a warm call) and sums the table it leaves.  Writes
+            --out (give one): per instantiation both sides' us per item, the spread of PATH's processes (max - min), the
+            difference, and whether the tables' sums agree."""
 import argparse
 import ctypes as C
 import json
@@ -166,6 +167,8 @@ def walker_grid():
             for np_ in (2, 3, 4):
                 grid.append((f"k_fm_pair_online<{lpr}, 0, {rule_id[rule]}, {np_}>", "pair", kp, rule, np_ * slots))
     grid += [(f"k_fm_online<1, 0, {rule_id[r]}, 1>", "fm", 4, r, 39) for r in ("signadam", "sgd")]
+    grid += [("k_fm_online<4, 0, 1, 3>", "fm", 16, "sgd", 39)]      # (kp = 16 under signadam is the control below)
+    grid += [(f"k_fm_online<16, 0, {rule_id[r]}, 4>", "fm", 64, r, 16) for r in ("signadam", "sgd")]
     grid += [("control k_fm_online<4, 0, 0, 3>", "fm", 16, "signadam", 39), ("control k_fm_pair_online<4, 2, 4, 3>", "pair", 16, "adam", 39)]
     return grid
 
@@ -203,6 +206,8 @@ def child_walkers(args):
 
 def main_ab(args):
     libs = (("other", os.path.abspath(args.ab_lib)), ("this", ""))
+    if args.ab_this_first:
+        libs = libs[::-1]
     runs = {"other": [], "this": []}
     for r in range(args.ab_rounds):
         for side, lib in libs:
@@ -256,6 +261,7 @@ def main():
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "pair_times.json"))
     ap.add_argument("--ab-lib", default=None, help="time the walkers' instantiations against this build of the same ABI (see above)")
     ap.add_argument("--ab-rounds", type=int, default=3)
+    ap.add_argument("--ab-this-first", action="store_true", help="with --ab-lib: start each round with this tree's library")
     ap.add_argument("--child", default=None)
     args = ap.parse_args()
     if args.child:
