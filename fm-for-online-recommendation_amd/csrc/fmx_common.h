@@ -42,6 +42,10 @@ struct Tune {
   int afm_online_persistent = 1;  // fmx_set_option("afm_online_persistent", 0): fmx_afm_online_run as per-sample launches (same bits)
   int afm_pair_online_persistent = 1;  // fmx_set_option("afm_pair_online_persistent", 0): fmx_afm_pair_online_run as queued pair steps (same bits)
   int sort_ahead = 16;  // FMX_SORT_AHEAD: batches per side-stream sort launch in fmx_fm_stream (1..16)
+  int sort_resident = -1;  // FMX_SORT_RESIDENT / fmx_set_option("sort_resident", v): most workgroups of a side-stream group sort of
+                           // the online loop from the call's third group on (k_sort_occ_resident, at most one per CU); 0: one
+                           // workgroup per (batch, field) as everywhere else; -1: the library's default for the device
+                           // (sort_resident_cap, fmx_kernels.hip).  Identical lists
   int mlp_chain = 1;          // FMX_MLP_CHAIN=0 / fmx_set_option("mlp_chain", 0): fmx_mlp_section as separate GEMM launches
                               // (forward x L, loss, dgrad x L) instead of k_mlp_chain; same results up to summation order
   int sort_chunked = 1;  // FMX_SORT_CHUNKED / fmx_set_option("sort_chunked", v): 0: one workgroup per field (k_sort_occ) at

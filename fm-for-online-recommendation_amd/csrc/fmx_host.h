@@ -23,6 +23,8 @@ struct Workspace {
 struct SortBatch {  // several batches of a pool in one launch
   int n_pool = 1, first = 0, n_batches = 1;
   int64_t pool_stride = 0, sorted_stride = 0;
+  int resident = 0;  // > 0: at most this many workgroups, one per CU at the most, each walking several (batch, field) units
+                     // (k_sort_occ_resident: the online loop's side-stream launches); 0: one workgroup per unit
 };
 
 // ---- the shared checks (fmx_kernels.hip).  Each leaves its message in g_err; named() puts the entry point in front ----
@@ -59,6 +61,10 @@ int sort_impl(const fmx_table_t *table, const int32_t *idx, int32_t B, uint32_t 
 // stream is not capturing).  A stale entry -- another table at the same address with the same key -- or a missing one gives
 // another order of the same tiles: it can cost time, never correctness.
 bool update_order(const fmx_table_t *table, bool may_fill, uint32_t *order_words);
+// ... the order in which a resident-capped group sort walks the sort fields (k_sort_occ_resident): descending row count from the
+// same cache, never filled from here (a table's first update has filled it by the time a call's third group is sorted);
+// false: index order
+bool sort_walk_order(const fmx_table_t *table, uint32_t *order_words);
 // fmx_update.hip
 int update_impl(const fmx_table_t *table, const fmx_hyper_t *hyper, int32_t rule, const Workspace &w,
                 const uint32_t *sorted, const float *xv, const float *S, const float *dz_first, const float *dz_bi, const float *gbi,

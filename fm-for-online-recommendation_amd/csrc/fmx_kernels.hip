@@ -645,6 +645,7 @@ Tune &tune() {
     if (const char *e = getenv("FMX_WPB_UPD")) x.wpb_upd = atoi(e);
     if (const char *e = getenv("FMX_SORT_E")) x.sort_e = atoi(e);
     if (const char *e = getenv("FMX_SORT_AHEAD")) x.sort_ahead = atoi(e);
+    if (const char *e = getenv("FMX_SORT_RESIDENT")) x.sort_resident = atoi(e);
     if (const char *e = getenv("FMX_ONLINE_PERSISTENT")) x.online_persistent = atoi(e);
     if (const char *e = getenv("FMX_INLINE_FIXUP")) x.inline_fixup = atoi(e);
     if (const char *e = getenv("FMX_SORT_CHUNKED")) x.sort_chunked = atoi(e);
@@ -713,9 +714,10 @@ struct UpdOrders {
 }  // namespace
 namespace fmxd {
 
-bool update_order(const fmx_table_t *table, bool may_fill, uint32_t *order_words) {
+// order_words = the table's sort fields in ascending (mode 1) or descending (mode 2) row count, from the per-device cache
+static bool cached_order(const fmx_table_t *table, int mode, bool may_fill, uint32_t *order_words) {
   memset(order_words, 0, UPD_ORDER_MAX);
-  const int mode = tune().upd_order, F = n_sort_fields(table);
+  const int F = n_sort_fields(table);
   if ((mode != 1 && mode != 2) || F < 1 || F > UPD_ORDER_MAX) return false;
   static std::mutex mu;
   static UpdOrders per_device[64];
@@ -749,6 +751,12 @@ bool update_order(const fmx_table_t *table, bool may_fill, uint32_t *order_words
   memcpy(order_words, hit->order[mode - 1], (size_t)F);  // byte i of the words: slot i's field (little-endian, as the kernel reads it)
   return true;
 }
+
+bool update_order(const fmx_table_t *table, bool may_fill, uint32_t *order_words) {
+  return cached_order(table, tune().upd_order, may_fill, order_words);
+}
+
+bool sort_walk_order(const fmx_table_t *table, uint32_t *order_words) { return cached_order(table, 2, false, order_words); }
 
 }  // namespace fmxd
 namespace {
@@ -800,9 +808,10 @@ void launch_forward_list(const FwdArgs &a, int layout, hipStream_t st) {
   if (!with_one_of<1, 2, 3, 4>(np, launch)) launch(std::integral_constant<int, 0>{});
 }
 
+// threads and LDS bytes of a k_sort_occ workgroup at E composites per thread; sets a.small_bits
 template <int E>
-void launch_sort(SortArgs a, hipStream_t st) {
-  const int threads = a.Bp / E;
+uint32_t sort_occ_shape(SortArgs &a, int &threads) {
+  threads = a.Bp / E;
   uint32_t lds = (uint32_t)(a.Bp * sizeof(uint32_t));
   // fields of at most 511 rows take one counting pass inside the same launch (fmx_sort.inc, radix_field): on the Criteo list 24
   // of the 39 fields -- the launch's length is still the network's (the 15 larger fields), its chip time is not
@@ -811,8 +820,63 @@ void launch_sort(SortArgs a, hipStream_t st) {
     const uint32_t need = (uint32_t)radix_small_lds_bytes(a.Bp, threads);
     if (need > lds) lds = need;
   }
+  return lds;
+}
+
+template <int E>
+void launch_sort(SortArgs a, hipStream_t st) {
+  int threads;
+  const uint32_t lds = sort_occ_shape<E>(a, threads);
   const int grid = a.n_batches >= 8 ? 8 * a.F * ((a.n_batches + 7) / 8) : a.F * a.n_batches;
   hipLaunchKernelGGL((k_sort_occ<E>), dim3(grid), dim3(threads), lds, st, a);
+}
+
+// The resident-capped form (k_sort_occ_resident): min(units, cap) workgroups, rounded up to a multiple of 8 (every XCD serves
+// its own batches).  *launched = false, and nothing issued, on a device whose workgroups cannot be kept one to a CU: the caller
+// then issues the uncapped grid.
+template <int E>
+int launch_sort_resident(SortArgs a, int cap, const fmx_table_t *table, hipStream_t st, bool *launched) {
+  *launched = false;
+  int dev = 0, lds_cu = 0, lds_wg = 0;
+  if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&lds_cu, hipDeviceAttributeMaxSharedMemoryPerMultiprocessor, dev) != hipSuccess ||
+      hipDeviceGetAttribute(&lds_wg, hipDeviceAttributeMaxSharedMemoryPerBlock, dev) != hipSuccess) {
+    (void)hipGetLastError();
+    return FMX_OK;
+  }
+  int threads;
+  uint32_t lds = sort_occ_shape<E>(a, threads);
+  // ONE workgroup per CU: two of 1,024 threads fill all 8 wave slots of every SIMD and close the CU to the step's kernels, which
+  // is what this form is there to prevent.  Nothing in a launch says "one per CU"; a request for more than half of the CU's LDS
+  // does (the unit itself needs Bp words and the counters, 41 KB at Bp = 4,096 -- three would fit).  The step's kernels use
+  // next to no LDS and are not held up by it.
+  const uint32_t one_per_cu = (uint32_t)align_up((size_t)lds_cu / 2 + 1, 256);
+  if (one_per_cu > lds) lds = one_per_cu;
+  if (lds > (uint32_t)lds_wg) return FMX_OK;
+  if (int rc = raise_lds_limit<k_sort_occ_resident<E>>(lds_wg, "k_sort_occ_resident")) return rc;
+  ResidentSortArgs ra;
+  ra.s = a;
+  const int units = a.n_batches * a.F;
+  ra.n_wg = ((units < cap ? units : cap) + 7) / 8 * 8;
+  ra.ordered = sort_walk_order(table, ra.order) ? 1 : 0;
+  hipLaunchKernelGGL((k_sort_occ_resident<E>), dim3(ra.n_wg), dim3(threads), lds, st, ra);
+  *launched = true;
+  return FMX_OK;
+}
+
+// tune().sort_resident as a number of workgroups for the current device.  The default is one workgroup on HALF of the CUs (128 on
+// the MI355X), between two bounds: the update's waves must still fit in one round -- (CUs - R) x 12 + R x 8 >= 2,497 at B = 4,096
+// on the Criteo list: R <= 143 -- and the launch must end well inside the group it runs beside (16 steps, 310 us).  Measured in the
+// steady loop ("r7"): R = 32 / 64 / 96 / 128 sort for 333 / 180 / 121 / 96 us and give 22.15 / 19.27 / 19.29 /
+// 19.19 us per step against 19.60 uncapped.
+int sort_resident_cap() {
+  const int v = tune().sort_resident;
+  if (v >= 0) return v;
+  int dev = 0, cus = 0;
+  if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) {
+    (void)hipGetLastError();
+    return 0;
+  }
+  return cus / 2;
 }
 
 int prepare_sort(int B) {
@@ -891,6 +955,15 @@ int fmxd::sort_impl(const fmx_table_t *table, const int32_t *idx, int32_t B, uin
   int E = a.Bp <= 64 ? 1 : a.Bp <= 128 ? 2 : a.Bp <= 4096 ? 4 : a.Bp <= 8192 ? 8 : a.Bp <= 16384 ? 16 : 32;
   const int want = tune().sort_e;
   if (want > E && want <= 32 && (want & (want - 1)) == 0 && a.Bp / want >= 64) E = want;
+  // (not at 32 composites per thread -- lists wider than 16,384: a unit's own 128 KB of LDS keep its workgroups one to a CU as
+  // it is, and the walking loop around the widest network does not fit the registers)
+  if (mb && mb->resident > 0 && E <= 16) {
+    bool launched = false;
+    int rc = FMX_OK;
+    with_one_of<1, 2, 4, 8, 16>(E, [&](auto E_) { rc = launch_sort_resident<E_>(a, mb->resident, table, st, &launched); });
+    if (rc != FMX_OK) return rc;
+    if (launched) return check_launch("k_sort_occ_resident");
+  }
   if (!with_one_of<1, 2, 4, 8, 16>(E, [&](auto E_) { launch_sort<E_>(a, st); })) launch_sort<32>(a, st);
   return check_launch("k_sort_occ");
 }
@@ -898,15 +971,16 @@ int fmxd::sort_impl(const fmx_table_t *table, const int32_t *idx, int32_t B, uin
 namespace {
 
 // sorts steps [first_step, first_step + n) of a pool of n_pool batches (step s takes batch s mod n_pool) with one launch, into
-// n consecutive sorted buffers of the workspace from `sorted` on
+// n consecutive sorted buffers of the workspace from `sorted` on; resident > 0: the resident-capped form (SortBatch)
 int sort_pool(const fmx_table_t *table, const int32_t *idx_pool, int n_pool, int B, int first_step, int n, const Workspace &w,
-              uint32_t *sorted, int32_t *error, hipStream_t st) {
+              uint32_t *sorted, int32_t *error, hipStream_t st, int resident = 0) {
   SortBatch mb;
   mb.n_pool = n_pool;
   mb.first = first_step % n_pool;
   mb.n_batches = n;
   mb.pool_stride = (int64_t)B * (int64_t)n_cols(table);
   mb.sorted_stride = (int64_t)w.sorted_stride;
+  mb.resident = resident;
   return sort_impl(table, idx_pool, B, sorted, w.runs, error, st, &mb);
 }
 
@@ -957,8 +1031,15 @@ int pool_loop(const fmx_table_t *table, const int32_t *idx_pool, const float *y_
     if (n > n_steps - first_step) n = n_steps - first_step;
     return n;
   };
+  // The side stream's launches from the call's THIRD group on run beside a whole group of `ahead` steps and their lists are
+  // needed a group later: they take the resident-capped form, which leaves the step's kernels their wave slots (fmx_sort.inc,
+  // k_sort_occ_resident).  The first group's length is what the first update waits for, and the second group is sorted beside
+  // the first's four steps and needed right behind them (capped as well, a 20-step call took 21.7 - 22.0 us per step instead
+  // of 20.7 - 21.1): one workgroup per unit for both, as ever.
+  const int resident = sd ? sort_resident_cap() : 0;
   auto sort_group = [&](int g, int first_step, int n, hipStream_t where) -> int {  // steps [first_step, first_step + n)
-    return sort_pool(table, idx_pool, n_pool, B, first_step, n, w, w.sorted + (size_t)(g & 1) * ahead * w.sorted_stride, error, where);
+    return sort_pool(table, idx_pool, n_pool, B, first_step, n, w, w.sorted + (size_t)(g & 1) * ahead * w.sorted_stride, error, where,
+                     sd && g >= 2 ? resident : 0);
   };
   int rc = FMX_OK;
   if (sd) {
@@ -1180,6 +1261,7 @@ int fmx_set_option(const char *name, int value) {
   int *slot = nullptr;
   if (!strcmp(name, "inline_fixup")) slot = &t.inline_fixup;
   else if (!strcmp(name, "sort_ahead")) slot = &t.sort_ahead;
+  else if (!strcmp(name, "sort_resident")) slot = &t.sort_resident;
   else if (!strcmp(name, "online_persistent")) slot = &t.online_persistent;
   else if (!strcmp(name, "afm_online_persistent")) slot = &t.afm_online_persistent;
   else if (!strcmp(name, "afm_pair_online_persistent")) slot = &t.afm_pair_online_persistent;
@@ -1188,7 +1270,7 @@ int fmx_set_option(const char *name, int value) {
   else if (!strcmp(name, "mlp_chain")) slot = &t.mlp_chain;
   else return fail(FMX_ERR_ARG, "fmx_set_option: unknown option '%s'", name);
   const int old = *slot;
-  *slot = value;
+  *slot = slot == &t.sort_resident && value < 0 ? -1 : value;
   return old;
 }
 

@@ -337,6 +337,48 @@ __global__ __launch_bounds__(1024) void k_sort_occ(SortArgs a) {
   sort_field<E>(a, f, sm);
 }
 
+// The same lists from a grid of `n_wg` workgroups (a multiple of 8, at most one per unit), each walking several units: the form
+// of the online loop's side-stream group launches that run beside a whole group of steps (lists needed a group later).  It bounds how many CUs
+// carry a sort workgroup while the step's own kernels run beside it: a 1,024-thread workgroup takes 4 of a SIMD's 8 wave slots
+// and 160 of its 512 VGPRs, so a CU with one of them holds 8 waves of the FTRL update (144 VGPRs) instead of 12 and a CU with two
+// holds none -- the uncapped grid (624 workgroups for 16 Criteo batches) took the update's one round of waves to two on the
+// launches beside it.  The host requests more than half of a CU's LDS for the launch, so no CU ever holds two.
+//   * workgroup b serves XCD x = b & 7 and that XCD's batches j = x, x + 8, ... (a batch's units stay on ONE XCD, as above);
+//   * the XCD's units are dealt FIELD-major -- every batch of the first field, then the next field -- round-robin over its
+//     n_wg / 8 workgroups, fields in the host's order (largest first where the row counts are known), so the bitonic fields
+//     spread evenly and the counting-pass fields fill the tail;
+//   * the assignment is static: no atomics, no flags, no workgroup waits for another.
+// Which workgroup sorts a unit is invisible in the lists; a stale or missing order costs time only.
+struct ResidentSortArgs {
+  SortArgs s;
+  int32_t n_wg;     // the grid
+  int32_t ordered;  // 0: fields in index order
+  uint32_t order[UPD_ORDER_MAX / 4];  // position i of the walk is sort field order[i], one byte each (as UpdArgs::order)
+};
+
+template <int E>
+__global__ __launch_bounds__(1024) void k_sort_occ_resident(ResidentSortArgs ra) {
+  extern __shared__ uint32_t sm[];
+  const SortArgs &a = ra.s;
+  const int x = blockIdx.x & 7, s = blockIdx.x >> 3, per_xcd = ra.n_wg >> 3;
+  const int nb = x < a.n_batches ? (a.n_batches - x + 7) >> 3 : 0;  // this XCD's batches
+  for (int u = s; u < nb * a.F; u += per_xcd) {
+    const int pos = u / nb, j = x + 8 * (u - pos * nb);
+    int f = pos;
+    if (ra.ordered) {  // through the kernel-argument segment, not ra.order[...]: no variable index into a by-value argument (k_fm_update)
+      typedef const __attribute__((address_space(4))) uint32_t karg_u32;
+      karg_u32 *ka = (karg_u32 *)__builtin_amdgcn_kernarg_segment_ptr();
+      f = (int)((ka[offsetof(ResidentSortArgs, order) / 4 + (pos >> 2)] >> ((pos & 3) * 8)) & 0xFFu);
+      if (f >= a.F) f = pos;  // (the host sends a permutation of the fields; nothing outside the lists is written whatever it sends)
+    }
+    SortArgs ua = a;
+    ua.idx += (size_t)((a.pool_first + j) % a.n_pool) * a.pool_stride;
+    ua.sorted += (size_t)j * a.sorted_stride;
+    sort_field<E>(ua, f, sm);
+    __syncthreads();  // the next unit reuses the LDS
+  }
+}
+
 // ------------------------------------------------------------------------------------------------------------
 // k_sort_chunk + k_sort_merge: the occurrence sort for Bp >= 2 * SORT_CHUNK, spread over the chip
 // ------------------------------------------------------------------------------------------------------------

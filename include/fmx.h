@@ -194,6 +194,14 @@ const char *fmx_last_error_string(void);
  *                                of more than 128 sort fields, gives index order or another order of the same tiles: it can cost
  *                                time, never correctness.
  *   "sort_ahead"   (default 16) most batches sorted per side-stream launch in fmx_fm_stream / fmx_deepfm_stream (1..16).
+ *   "sort_resident" (default -1) most workgroups of a side-stream group sort of fmx_fm_stream / fmx_deepfm_stream, from a call's
+ *                                third group on (they run beside a whole group of steps; their lists are needed a group later): min(batches x sort fields, value)
+ *                                workgroups, rounded up to a multiple of 8, at most one per CU, each walking several (batch, sort
+ *                                field) units -- the step's own kernels keep their wave slots on every CU beside the sort.  0: one
+ *                                workgroup per unit, as the call's first two groups and every other sort are launched; -1 (any
+ *                                negative value): the library's default for the device, half of its CUs.  This is the one
+ *                                option whose previous value can be negative: -1 returned under this name is the default, not
+ *                                a status.  Also FMX_SORT_RESIDENT in the environment.
  *   "sort_chunked" (default 1)  0: one workgroup per field at every width; 1: k_sort_chunk + k_sort_merge (1,024-composite
  *                                chunks spread over the chip, stable rank merge) from 8,192 composites per field on; 2: from 2,048 on.
  *   "mlp_chain"    (default 1)  0: fmx_mlp_section as separate GEMM launches instead of k_mlp_chain (forward + loss + dgrad chain
