@@ -20,11 +20,11 @@
 //                         parameters' rule to (params[g], m[g], v[g]) and stores them (fmx_afm_step_opt, fmx_afm_stream).
 //
 //   k_afm_online<KP>      one workgroup of 8 waves walks a stream one sample at a time (fmx_afm_online_run): k_afm's sample spread over
-//                         the waves, the table update and the attention rule in the same launch; the bits of B = 1 steps (its own
-//                         comment further down).
+//                         the waves, the table update and the attention rule in the same launch; the bits of B = 1 steps.  It is
+//                         afm_walk<KP, 1> of fmx_afm_device.inc (the comment in front of the online section there).
 //
-//   k_afm_pair_online<KP> (fmx_afm_pair_online.hip, a unit of its own) k_afm_online for pairs: one workgroup walks a stream of (positive, negative) pairs
-//                         (fmx_afm_pair_online_run); the bits of B_pairs = 1 pair steps.
+//   k_afm_pair_online<KP> (fmx_afm_pair_online.hip, a unit of its own) k_afm_online for pairs, afm_walk<KP, 2>: one workgroup walks a stream of
+//                         (positive, negative) pairs (fmx_afm_pair_online_run); the bits of B_pairs = 1 pair steps.
 //
 //   k_afm_pair<KP, FTRL, BWD>  (fmx_afm_pair.inc) pairwise-ranking training: a workgroup walks PAIRS of rows (positive, negative) and
 //                         runs k_afm's row forward and backward under the pair loss of the two logits (fmx_afm_pair_*).
@@ -34,7 +34,8 @@
 //
 // The host side defines once what the three objectives (BCE on y, pairs, lists) share: afm_step_launches, one step's launches under
 // an AfmObjective (the kind, the rows per unit, the margin); afm_steps_run, the ONE queue of steps behind every stream and every
-// queued online run; check_afm_unit_steps, the step check of the objectives that read no labels.  Every launcher raises its
+// queued online run; check_afm_unit_steps, the step check of the objectives that read no labels.  The two online walkers share
+// launch_afm_walk_k and the form decision afm_online_form (fmx_afm_device.inc), each under its own option.  Every launcher raises its
 // kernel's dynamic-LDS limit through raise_lds_limit (fmx_host.h).  The entry points keep their own checks in their own order.
 //
 // No float is accumulated with atomics and every sum has one fixed order that depends on (B, F, t, k) alone: results are
@@ -289,14 +290,6 @@ int afm_steps_run(const fmx_table_t *table, const fmx_hyper_t *hyper, int32_t ru
   return FMX_OK;
 }
 
-template <int KP>
-int launch_afm_online_k(const AfmOnlArgs &a, hipStream_t st) {
-  const size_t lds = (size_t)afm_online_lds(a.F, KP, a.t, a.G, a.nb, a.mom_lds != 0).total * 4;
-  if (int rc = raise_lds_limit<k_afm_online<KP>>(AFM_LDS_BYTES, "k_afm_online")) return rc;
-  hipLaunchKernelGGL((k_afm_online<KP>), dim3(1), dim3(AFM_ONL_THREADS), lds, st, a);
-  return check_launch("k_afm_online");
-}
-
 #include "fmx_afm_pair.inc"
 #include "fmx_afm_list.inc"
 
@@ -370,15 +363,13 @@ int fmx_afm_online_run(const fmx_table_t *table, const fmx_hyper_t *hyper, int32
   if (int rc = check_afm_opt(table, hyper, rule, afm, 1, opt, N, who)) return rc;
   if (N == 0) return FMX_OK;
   const hipStream_t st = static_cast<hipStream_t>(stream);
-  const int F = table->n_fields, G = afm->t * afm->k + 2 * afm->t + afm->k;
-  const bool want_mom = opt->rule == FMX_RULE_ADAGRAD || opt->rule == FMX_RULE_ADAM;
   bool mom = false;
-  const int nb = tune().afm_online_persistent ? afm_online_buffers(F, table->kp, afm->t, G, want_mom, mom) : 0;
+  const int nb = afm_online_form(tune().afm_online_persistent, table->n_fields, afm->k, table->kp, afm->t, opt->rule, mom);
   if (nb == 0)  // the per-sample launches of fmx_afm_step_opt(B = 1, inv_b = 1), queued
     return afm_steps_run(table, hyper, rule, afm, AFM_POINTWISE, idx, xv, y, N, 1, 1.0f, N, workspace, w, attn_grad_out, opt, logit_out, 1,
                          loss_out, error, st);
   const AfmOnlArgs a = fill_afm_online(table, hyper, rule, afm, opt, idx, xv, y, N, attn_grad_out, logit_out, loss_out, error, nb, mom);
-  return with_kp(table->kp, [&](auto KP) { return launch_afm_online_k<KP>(a, st); });
+  return with_kp(table->kp, [&](auto KP) { return launch_afm_walk_k<KP, k_afm_online<KP>>(a, a, "k_afm_online", st); });
 }
 
 int fmx_afm_side(const fmx_table_t *table, const fmx_afm_t *afm, const fmx_hyper_t *hyper, const int32_t *idx, const float *xv,

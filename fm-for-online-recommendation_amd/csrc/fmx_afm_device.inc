@@ -1,7 +1,8 @@
 // fmx_afm_device.inc -- the device code of the attentional FM: the LDS carvings, the per-pair and per-tile device functions and the
-// kernels k_afm, k_afm_reduce, k_afm_reduce_opt, k_afm_side and k_afm_online (fmx_afm.hip's header describes them).  Included inside
-// the unnamed namespace of fmx_afm.hip, which launches these kernels, and of fmx_afm_pair_online.hip, whose kernel is built from the
-// same device functions in a unit of its own (with FMX_AFM_SHARED_ONLY; why: that file's header).
+// kernels k_afm, k_afm_reduce, k_afm_reduce_opt, k_afm_side and k_afm_online (fmx_afm.hip's header describes them), and the online
+// walk afm_walk<KP, T> with its onl_ pieces, the body of k_afm_online (T = 1) and of k_afm_pair_online (T = 2).  Included inside the
+// unnamed namespace of fmx_afm.hip, which launches these kernels, and of fmx_afm_pair_online.hip, whose kernel is the same walk
+// in a unit of its own (with FMX_AFM_SHARED_ONLY; why: that file's header).
 
 constexpr int AFM_TILE = 64;       // pairs per tile at most: one per lane of the wavefront
 constexpr int AFM_MAX_WG = 1024;   // workgroups of a launch; with fewer samples, one workgroup per sample
@@ -483,6 +484,9 @@ __global__ __launch_bounds__(64) void k_afm_side(AfmSideArgs a) {
 //            which stay in LDS.  The stores are acknowledged (vmcnt(0)) and a barrier passed before the next sample's gather.
 // ADAM's constants of sample i -- step hyper.step + i + 1 of the tables, opt.step + i + 1 of the attention parameters -- are
 // derived by one thread per sample with adam_consts, the function the host uses for a launch (same bits), as in k_online_mlp.
+// The kernel is afm_walk<KP, 1> below; k_afm_pair_online (fmx_afm_pair_online.hip) is afm_walk<KP, 2>, the same walk with two rows
+// in every slot.  What the two share -- prologue, fetch, ADAM's constants, forward and softmax, pass B, the attention rule, the bias
+// step, the epilogue -- is one onl_ function each; the objective and the table update's run logic are the walk's `if constexpr` parts.
 constexpr int AFM_ONL_WAVES = 8, AFM_ONL_THREADS = AFM_ONL_WAVES * WAVE;  // 2 waves per SIMD: 256 VGPRs each (pair_backward at
                                                                           // kp = 64 holds q and dL/dq: 128 registers)
 constexpr int AFM_LDS_BYTES = 160 * 1024;
@@ -612,6 +616,20 @@ inline AfmOnlArgs fill_afm_online(const fmx_table_t *table, const fmx_hyper_t *h
   a.mom_lds = moments_in_lds ? 1 : 0;
   return a;
 }
+// the form an online run takes: `option` (the entry point's "..._persistent" option) on: afm_online_buffers' tile buffers for the
+// one-workgroup kernel, mom: its moments in LDS; off, or 0 buffers: the queued steps
+inline int afm_online_form(int option, int F, int k, int kp, int t, int attn_rule, bool &mom) {
+  mom = false;
+  return option ? afm_online_buffers(F, kp, t, t * k + 2 * t + k, attn_rule == FMX_RULE_ADAGRAD || attn_rule == FMX_RULE_ADAM, mom) : 0;
+}
+// the launch of a walker K (k_afm_online<KP> or k_afm_pair_online<KP>; o: the AfmOnlArgs of its arguments): one workgroup
+template <int KP, auto K, class Args>
+int launch_afm_walk_k(const Args &args, const AfmOnlArgs &o, const char *name, hipStream_t st) {
+  const size_t lds = (size_t)afm_online_lds(o.F, KP, o.t, o.G, o.nb, o.mom_lds != 0).total * 4;
+  if (int rc = raise_lds_limit<K>(AFM_LDS_BYTES, name)) return rc;
+  hipLaunchKernelGGL(K, dim3(1), dim3(AFM_ONL_THREADS), lds, st, args);
+  return check_launch(name);
+}
 
 // the tables' rule is a workgroup-uniform run-time switch around the row helpers (a template parameter would multiply the five
 // kp instantiations by five for a few instructions per sample)
@@ -661,72 +679,298 @@ __device__ __forceinline__ void onl_column(const AfmLds &L, int g, int k, int t,
   }
 }
 
+// ---- the pieces of the walk (afm_walk below), each stated once for k_afm_online and k_afm_pair_online ----
+constexpr int onl_slots(int kp) { return (AFM_MAX_F * (kp / 4) + AFM_ONL_THREADS - 1) / AFM_ONL_THREADS; }
+// the workgroup-uniform facts of the two rules
+struct OnlRules {
+  bool ftrl, mom_rule;  // the tables': FTRL rows; rows with moments (ADAGRAD, ADAM)
+  bool o_v, o_m;        // the attention parameters' rule keeps v; keeps m
+};
+__device__ __forceinline__ OnlRules onl_rules(const AfmOnlArgs &a) {
+  return {a.rule == FMX_RULE_FTRL, a.rule == FMX_RULE_ADAGRAD || a.rule == FMX_RULE_ADAM,
+          a.o_rule == FMX_RULE_ADAGRAD || a.o_rule == FMX_RULE_ADAM, a.o_rule == FMX_RULE_ADAM};
+}
+// the slots a thread gathers and updates: slot rr = tid + p NT is lanes q of field f, for each of the unit's samples (kp = 64:
+// 64 fields x 16 threads over 512, two slots a thread)
+template <int NP>
+struct OnlSlots {
+  int fld[NP], qq[NP];
+  int64_t lo[NP];
+  uint32_t vocab[NP];
+  bool live[NP];
+};
 template <int KP>
-__global__ __launch_bounds__(AFM_ONL_THREADS) void k_afm_online(AfmOnlArgs a) {
-  constexpr int NT = AFM_ONL_THREADS, NW = AFM_ONL_WAVES, LPR = KP / 4;
-  constexpr int NP = (AFM_MAX_F * LPR + NT - 1) / NT;  // rows a thread holds (kp = 64: 64 fields x 16 threads over 512)
-  extern __shared__ float4 lds4[];
-  float *sm = reinterpret_cast<float *>(lds4);
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  const int F = a.F, k = a.k, t = a.t, P = F * (F - 1) / 2, G = a.G, nb = a.nb;
-  const AfmOnlLds O = afm_online_lds(F, KP, t, G, nb, a.mom_lds != 0);
-  const AfmLds &L = O.L;
-  const bool ftrl = a.rule == FMX_RULE_FTRL, mom_rule = a.rule == FMX_RULE_ADAGRAD || a.rule == FMX_RULE_ADAM;
-  const bool o_v = a.o_rule == FMX_RULE_ADAGRAD || a.o_rule == FMX_RULE_ADAM, o_m = a.o_rule == FMX_RULE_ADAM;
+__device__ __forceinline__ OnlSlots<onl_slots(KP)> onl_slot_table(const AfmOnlArgs &a) {
+  constexpr int NT = AFM_ONL_THREADS, LPR = KP / 4, NP = onl_slots(KP);
+  const int tid = threadIdx.x;
+  OnlSlots<NP> S;
+#pragma unroll
+  for (int p = 0; p < NP; ++p) {
+    const int rr = tid + p * NT;
+    S.fld[p] = rr / LPR;
+    S.qq[p] = rr - S.fld[p] * LPR;
+    S.live[p] = S.fld[p] < a.F;
+    S.lo[p] = S.live[p] ? a.foff[S.fld[p]] : 0;
+    S.vocab[p] = S.live[p] ? (uint32_t)(a.foff[S.fld[p] + 1] - S.lo[p]) : 0u;
+  }
+  return S;
+}
+// the (index, value) a slot holds of each of the T samples of a unit
+template <int T, int NP>
+struct OnlInputs {
+  uint32_t li[T][NP];
+  float x[T][NP];
+};
 
-  stage_params<KP>(sm, L, a.params, k, t, tid, NT);
+// The prologue: the attention parameters, the x w words, the bias words and (where they fit: a.mom_lds) the moments to LDS.  mm /
+// vv name the moments wherever they are: in LDS for the whole stream, or left in global memory (the same code through a generic
+// pointer).  (The walk builds its slot table BEHIND this call, as the kernels did.  With the table in front of it the pair walker
+// at kp = 16 and the pointwise walker at kp = 64 measured 4 - 7 % slower per unit -- profiles/afm_walk_seam_ab.txt, B.)
+template <int KP>
+__device__ __forceinline__ void onl_open(const AfmOnlArgs &a, const OnlRules &R, const AfmOnlLds &O, float *sm, float *&mm, float *&vv) {
+  constexpr int NT = AFM_ONL_THREADS;
+  const int tid = threadIdx.x;
+  stage_params<KP>(sm, O.L, a.params, a.k, a.t, tid, NT);
   if (tid < WAVE) sm[O.fo + tid] = 0.f;
   if (tid < ONL_MISC) sm[O.misc + tid] = 0.f;
   __syncthreads();
   if (tid == 0) {
     sm[O.misc] = a.bias[0];
-    if (ftrl || mom_rule) sm[O.misc + 1] = a.bias[1];
-    if (mom_rule) sm[O.misc + 2] = a.bias[2];
+    if (R.ftrl || R.mom_rule) sm[O.misc + 1] = a.bias[1];
+    if (R.mom_rule) sm[O.misc + 2] = a.bias[2];
   }
-  // the moments: in LDS for the whole stream, or left in global memory (the same code through a generic pointer)
-  float *mm = a.mom_lds ? sm + O.m : a.m, *vv = a.mom_lds ? sm + O.v : a.v;
+  mm = a.mom_lds ? sm + O.m : a.m;
+  vv = a.mom_lds ? sm + O.v : a.v;
   if (a.mom_lds) {
-    for (int g = tid; g < G; g += NT) {
-      if (o_m) mm[g] = a.m[g];
-      if (o_v) vv[g] = a.v[g];
+    for (int g = tid; g < a.G; g += NT) {
+      if (R.o_m) mm[g] = a.m[g];
+      if (R.o_v) vv[g] = a.v[g];
     }
   }
+}
 
-  // the rows this thread gathers and updates: row rr = tid + p NT is lanes q of field f
-  int fld[NP], qq[NP];
-  int64_t lo[NP];
-  uint32_t vocab[NP];
-  bool live[NP];
+// The next unit's inputs, rows T i .. T i + T - 1 of the stream.  Branch-free (k_fm_online): beyond the stream or the last field the
+// loads read element 0 and are dropped.  xsrc: the values, or without them the indices, loaded in their place and dropped (x = 1).
+// mid() stands between the loads and the selects: the unit's other load (the label) goes there, as in walk_fetch
+template <int T, int NP, class Mid>
+__device__ __forceinline__ void onl_fetch(OnlInputs<T, NP> &n, const AfmOnlArgs &a, const OnlSlots<NP> &S, const float *xsrc, bool has_x,
+                                          int i, bool in, Mid mid) {
+  uint32_t l_[T][NP];
+  float x_[T][NP];
+#pragma unroll
+  for (int s = 0; s < T; ++s) {
+#pragma unroll
+    for (int p = 0; p < NP; ++p) {
+      const size_t o = (S.live[p] && in) ? ((size_t)T * i + s) * a.F + S.fld[p] : (size_t)0;
+      l_[s][p] = (uint32_t)a.idx[o];
+      x_[s][p] = xsrc[o];
+    }
+  }
+  mid();
+#pragma unroll
+  for (int s = 0; s < T; ++s) {
+#pragma unroll
+    for (int p = 0; p < NP; ++p) {
+      n.li[s][p] = (S.live[p] && in) ? l_[s][p] : 0u;
+      n.x[s][p] = (has_x && S.live[p] && in) ? x_[s][p] : 1.f;
+    }
+  }
+}
+
+// ADAM's constants of unit i, by one thread into misc: [0..2] the tables', [3..6] the attention parameters'
+__device__ __forceinline__ void onl_unit_consts(const AfmOnlArgs &a, const OnlRules &R, const AfmOnlLds &O, float *sm, int i) {
+  if (threadIdx.x == WAVE) {
+    float *kc = sm + O.misc + ONL_KC;
+    if (a.rule == FMX_RULE_ADAM) adam_consts(a.h.lr, a.h.beta1, a.h.beta2, a.h.step + i + 1, kc[0], kc[1], kc[2]);
+    if (R.o_m) adam_consts(a.o_lr, a.o_beta1, a.o_beta2, a.o_step + i + 1, kc[3], kc[4], kc[5], a.o_eps, &kc[6]);
+  }
+}
+
+// The forward of one sample from its row registers: e = x V and x w to LDS (gather_field's products; an absent row is zeros), pass A
+// over the waves, then the softmax -- k_afm's one-wave reductions in every wave, the exponentials over all threads in between.
+// The exponentials stay in O.x, p . q in L.r; returns the logit, which every wave holds, with Z and att for pass B.  (A second
+// forward's writes of e and x w lie behind the barrier every wave passed after reading the first's.)
+template <int KP, int NP>
+__device__ __forceinline__ float onl_forward(const AfmOnlArgs &a, const OnlRules &R, const AfmOnlLds &O, float *sm, const OnlSlots<NP> &S,
+                                             const RowRegs (&row)[NP], const float (&x)[NP], const bool (&ok)[NP], float &Z, float &att) {
+  constexpr int NT = AFM_ONL_THREADS, NW = AFM_ONL_WAVES;
+  const AfmLds &L = O.L;
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, P = a.F * (a.F - 1) / 2;
 #pragma unroll
   for (int p = 0; p < NP; ++p) {
-    const int rr = tid + p * NT;
-    fld[p] = rr / LPR;
-    qq[p] = rr - fld[p] * LPR;
-    live[p] = fld[p] < F;
-    lo[p] = live[p] ? a.foff[fld[p]] : 0;
-    vocab[p] = live[p] ? (uint32_t)(a.foff[fld[p] + 1] - lo[p]) : 0u;
+    if (S.live[p]) {
+      *reinterpret_cast<float4 *>(sm + L.e + S.fld[p] * KP + 4 * S.qq[p]) = ok[p] ? x[p] * row[p].v : splat(0.f);
+      if (S.qq[p] == 0) sm[O.fo + S.fld[p]] = ok[p] ? row[p].fo.x * x[p] : 0.f;
+    }
   }
-  uint32_t li_n[NP];
-  float x_n[NP], y_n = 0.f;
-  // branch-free (k_fm_online): beyond the stream or the last field the loads read element 0 and are dropped
+  __syncthreads();
+  score_pairs<KP>(sm, L, a.F, a.t, lane, wv, NW);
+  __syncthreads();
+  float mx = -INFINITY;
+  for (int l = lane; l < P; l += WAVE) mx = fmaxf(mx, sm[L.s + l]);
+  mx = wave_max(mx);
+  for (int l = tid; l < P; l += NT) sm[O.x + l] = expf(sm[L.s + l] - mx);
+  const float fo = wave_sum(sm[O.fo + lane]);
+  __syncthreads();
+  float N = 0.f;
+  Z = 0.f;
+  for (int l = lane; l < P; l += WAVE) {
+    const float ex = sm[O.x + l];
+    Z += ex;
+    N += ex * sm[L.r + l];
+  }
+  Z = wave_sum(Z);
+  N = wave_sum(N);
+  att = N / Z;
+  const float bias_w = R.ftrl ? ftrl_w(sm[O.misc], sm[O.misc + 1], a.h) : sm[O.misc];
+  return (bias_w + fo) + att;
+}
+
+// Pass B of the sample whose forward is in LDS, under dlogit g, in rounds of nb tiles: wave w recomputes tile w of the round into
+// tile buffer w, then every thread adds the round's tiles, in tile order, into the accumulators it owns.  Ends behind a barrier
+template <int KP>
+__device__ __forceinline__ void onl_pass_b(const AfmOnlArgs &a, const AfmOnlLds &O, float *sm, float Z, float g, float att) {
+  const AfmLds &L = O.L;
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, F = a.F, t = a.t;
+  for (int i0r = 0, pbr = 0; i0r < F - 1;) {
+    int i0 = i0r, pb = pbr, cnt = 0;
+    for (; cnt < a.nb && i0 < F - 1; ++cnt) {
+      int n;
+      const int i1 = next_tile(F, i0, n);
+      if (cnt == wv && lane < n) {
+        int pi, pj;
+        tile_pair(F, i0, lane, pi, pj);
+        pair_backward<KP>(sm, L, tile_buf(O, KP, t, cnt), t, pi, pj, lane, sm[O.x + pb + lane], Z, g, att);
+      }
+      pb += n;
+      i0 = i1;
+    }
+    __syncthreads();
+    i0 = i0r;
+    for (int c = 0; c < cnt; ++c) {
+      int n;
+      const int i1 = next_tile(F, i0, n);
+      add_tile<KP>(sm, L, tile_buf(O, KP, t, c), F, t, i0, i1, n, tid, AFM_ONL_THREADS);
+      i0 = i1;
+    }
+    __syncthreads();
+    i0r = i0;
+    pbr = pb;
+  }
+}
+
+// The attention parameters' step of unit i: column c's gradient is 0 + the one workgroup's partial (afm_reduce_column), then the
+// rule, on the parameters in LDS and the moments behind mm / vv.  The last unit's gradient goes to a.grad
+template <int KP>
+__device__ __forceinline__ void onl_attn_rule(const AfmOnlArgs &a, const OnlRules &R, const AfmOnlLds &O, float *sm, float *mm, float *vv, int i) {
+  fmx_hyper_t ho;
+  ho.lr = a.o_lr;
+  ho.eps = a.o_eps;
+  if (R.o_m) {
+    const float *kc = sm + O.misc + ONL_KC;
+    ho.lr = kc[3];
+    ho.beta1 = kc[4];
+    ho.beta2 = kc[5];
+    ho.eps = kc[6];
+  }
+  for (int c = threadIdx.x; c < a.G; c += AFM_ONL_THREADS) {
+    int par, acc;
+    onl_column(O.L, c, a.k, a.t, KP, par, acc);
+    const float s = 0.f + sm[acc];
+    if (i == a.N - 1) a.grad[c] = s;
+    float p = sm[par], m = 0.f, v = 0.f;
+    if (R.o_v) v = vv[c];
+    if (R.o_m) m = mm[c];
+    switch (a.o_rule) {
+      case FMX_RULE_SIGNADAM: afm_opt_column<FMX_RULE_SIGNADAM>(p, m, v, s, ho); break;
+      case FMX_RULE_SGD: afm_opt_column<FMX_RULE_SGD>(p, m, v, s, ho); break;
+      case FMX_RULE_ADAGRAD: afm_opt_column<FMX_RULE_ADAGRAD>(p, m, v, s, ho); break;
+      default: afm_opt_column<FMX_RULE_ADAM>(p, m, v, s, ho); break;
+    }
+    if (R.o_v) vv[c] = v;
+    if (R.o_m) mm[c] = m;
+    sm[par] = p;
+  }
+}
+
+// the tables' hyper-parameters of the unit: ADAM's constants from misc
+__device__ __forceinline__ fmx_hyper_t onl_table_hyper(const AfmOnlArgs &a, const AfmOnlLds &O, const float *sm) {
+  fmx_hyper_t ht = a.h;
+  if (a.rule == FMX_RULE_ADAM) {
+    const float *kc = sm + O.misc + ONL_KC;
+    ht.lr = kc[0];
+    ht.beta1 = kc[1];
+    ht.beta2 = kc[2];
+  }
+  return ht;
+}
+// thread 0 steps the bias words, which stay in LDS, on the unit's bias gradient g
+__device__ __forceinline__ void onl_bias_words(const AfmOnlArgs &a, const AfmOnlLds &O, float *sm, float g, const fmx_hyper_t &ht) {
+  if (threadIdx.x == 0) {
+    float b0 = sm[O.misc], b1 = sm[O.misc + 1], b2 = sm[O.misc + 2];
+    onl_bias_step(a.rule, b0, b1, b2, g, ht);
+    sm[O.misc] = b0;
+    sm[O.misc + 1] = b1;
+    sm[O.misc + 2] = b2;
+  }
+}
+
+// The epilogue: the attention parameters, the moments that lived in LDS, the bias words and the index flag back to global memory
+template <int KP>
+__device__ __forceinline__ void onl_close(const AfmOnlArgs &a, const OnlRules &R, const AfmOnlLds &O, float *sm, const float *mm, const float *vv, bool bad) {
+  const int tid = threadIdx.x;
+  if (bad) sm[O.misc + ONL_FLAG] = 1.f;
+  for (int c = tid; c < a.G; c += AFM_ONL_THREADS) {
+    int par, acc;
+    onl_column(O.L, c, a.k, a.t, KP, par, acc);
+    a.params[c] = sm[par];
+    if (a.mom_lds) {
+      if (R.o_m) a.m[c] = mm[c];
+      if (R.o_v) a.v[c] = vv[c];
+    }
+  }
+  __syncthreads();
+  if (tid == 0) {
+    a.bias[0] = sm[O.misc];
+    if (R.ftrl || a.rule == FMX_RULE_ADAM) a.bias[1] = sm[O.misc + 1];
+    if (R.mom_rule) a.bias[2] = sm[O.misc + 2];
+    if (sm[O.misc + ONL_FLAG] != 0.f && a.error) *a.error = 1;
+  }
+}
+
+// The walk over a stream of N units of T samples: T = 1, k_afm_online's sample under BCE on its label; T = 2, k_afm_pair_online's
+// (positive, negative) rows 2 i and 2 i + 1 under pair_loss_dz on z_pos - z_neg (fmx_afm_pair_online.hip's header has what the pair
+// stands for).  A slot's rows of all T samples are loaded before any update and stay in registers for the unit.  Per unit:
+//   T = 1   forward; loss; pass B with g; the attention rule; every valid row is a run of one occurrence
+//   T = 2   the negative's forward, then the positive's; loss; the positive's pass B with g, its x dL/de slices to registers (EP)
+//           and its dL/de slots zeroed by their holders; the negative again from the row registers (k_afm_pair regathers; the rows
+//           have not moved, so the bits are the same), its pass B with -g -- the attention accumulators are zeroed once per unit
+//           and take the positive's tiles, then the negative's; the attention rule; a valid row both samples name in a field is
+//           ONE run of two occurrences, positive first (k_fm_pair_online's run logic), otherwise each valid row is a run of one.
+//           The bias gradient (0 + g) + (-g) = +0 still goes through the bias step: the moments decay on it
+template <int KP, int T>
+__device__ __forceinline__ void afm_walk(const AfmOnlArgs &a, float margin) {
+  static_assert(T == 1 || T == 2, "a unit of one or two samples");
+  constexpr int NT = AFM_ONL_THREADS, NP = onl_slots(KP);
+  extern __shared__ float4 lds4[];
+  float *sm = reinterpret_cast<float *>(lds4);
+  const int tid = threadIdx.x;
+  const AfmOnlLds O = afm_online_lds(a.F, KP, a.t, a.G, a.nb, a.mom_lds != 0);
+  const AfmLds &L = O.L;
+  const OnlRules R = onl_rules(a);
+  float *mm, *vv;
+  onl_open<KP>(a, R, O, sm, mm, vv);
+  const OnlSlots<NP> S = onl_slot_table<KP>(a);
+  OnlInputs<T, NP> next;
+  float y_n = 0.f;
   const float *xsrc = a.xv ? a.xv : reinterpret_cast<const float *>(a.idx);
   const bool has_x = a.xv != nullptr;
   auto fetch_inputs = [&](int i) {
     const bool in = i < a.N;
-    uint32_t l_[NP];
-    float x_[NP];
-#pragma unroll
-    for (int p = 0; p < NP; ++p) {
-      const size_t o = (live[p] && in) ? (size_t)i * F + fld[p] : (size_t)0;
-      l_[p] = (uint32_t)a.idx[o];
-      x_[p] = xsrc[o];
-    }
-    const float yy = a.y[in ? i : 0];
-#pragma unroll
-    for (int p = 0; p < NP; ++p) {
-      li_n[p] = (live[p] && in) ? l_[p] : 0u;
-      x_n[p] = (has_x && live[p] && in) ? x_[p] : 1.f;
-    }
+    float yy = 0.f;
+    onl_fetch(next, a, S, xsrc, has_x, i, in, [&] {
+      if constexpr (T == 1) yy = a.y[in ? i : 0];
+    });
     y_n = in ? yy : 0.f;
   };
   fetch_inputs(0);
@@ -734,166 +978,99 @@ __global__ __launch_bounds__(AFM_ONL_THREADS) void k_afm_online(AfmOnlArgs a) {
   __syncthreads();
 
   for (int i = 0; i < a.N; ++i) {
-    // ---- gather: the rows by sc1 loads; the next sample's inputs behind them ----
-    uint32_t li[NP];
-    float x[NP];
-    const float y = y_n;
-    RowRegs row[NP];
-    bool ok[NP];
+    // ---- gather: the unit's rows by sc1 loads; the next unit's inputs behind them ----
+    const OnlInputs<T, NP> in = next;
+    [[maybe_unused]] const float y = y_n;
+    RowRegs row[T][NP];
+    bool ok[T][NP];
 #pragma unroll
-    for (int p = 0; p < NP; ++p) {
-      li[p] = li_n[p];
-      x[p] = x_n[p];
-      ok[p] = live[p] && li[p] < vocab[p];  // (a negative index is a large unsigned one)
-      row[p] = onl_load_row(a.rule, a.rows + (size_t)(ok[p] ? lo[p] + li[p] : 0) * a.stride, qq[p], KP, a.zoff);
-      bad = bad || (live[p] && !ok[p]);
+    for (int s = 0; s < T; ++s) {
+#pragma unroll
+      for (int p = 0; p < NP; ++p) {
+        ok[s][p] = S.live[p] && in.li[s][p] < S.vocab[p];  // (a negative index is a large unsigned one)
+        row[s][p] = onl_load_row(a.rule, a.rows + (size_t)(ok[s][p] ? S.lo[p] + in.li[s][p] : 0) * a.stride, S.qq[p], KP, a.zoff);
+        bad = bad || (S.live[p] && !ok[s][p]);
+      }
     }
     fetch_inputs(i + 1);
-    if (tid == WAVE) {  // ADAM's constants of this sample: [0..2] the tables', [3..6] the attention parameters'
-      float *kc = sm + O.misc + ONL_KC;
-      if (a.rule == FMX_RULE_ADAM) adam_consts(a.h.lr, a.h.beta1, a.h.beta2, a.h.step + i + 1, kc[0], kc[1], kc[2]);
-      if (o_m) adam_consts(a.o_lr, a.o_beta1, a.o_beta2, a.o_step + i + 1, kc[3], kc[4], kc[5], a.o_eps, &kc[6]);
-    }
+    onl_unit_consts(a, R, O, sm, i);
+    // dL/de and the attention accumulators [ dW | db | dh | dp ] (one run in LDS): zero before the unit's first pass B
     for (int l = tid; l < O.acc_len; l += NT) sm[L.Ea + l] = 0.f;
-#pragma unroll
-    for (int p = 0; p < NP; ++p) {
-      if (live[p]) {  // gather_field's products: e = x V, x w; an absent row is zeros
-        *reinterpret_cast<float4 *>(sm + L.e + fld[p] * KP + 4 * qq[p]) = ok[p] ? x[p] * row[p].v : splat(0.f);
-        if (qq[p] == 0) sm[O.fo + fld[p]] = ok[p] ? row[p].fo.x * x[p] : 0.f;
+
+    // ---- forwards; the unit's loss and dlogit in every wave, on identical operands ----
+    float Z, att, loss, g;
+    [[maybe_unused]] float4 EP[NP];
+    if constexpr (T == 1) {
+      const float logit = onl_forward<KP>(a, R, O, sm, S, row[0], in.x[0], ok[0], Z, att);
+      bce_loss_dz(FMX_LOSS_BCE_LOGITS, logit, y, 1.0f, loss, g);
+      if (tid == 0) {
+        if (a.logit) a.logit[i] = logit;
+        if (a.loss) a.loss[i] = 0.f + loss;  // the update's block_sum over one sample
       }
-    }
-    __syncthreads();
-
-    // ---- pass A over the waves ----
-    score_pairs<KP>(sm, L, F, t, lane, wv, NW);
-    __syncthreads();
-
-    // ---- softmax: k_afm's one-wave reductions in every wave; the exponentials over all threads ----
-    float mx = -INFINITY;
-    for (int l = lane; l < P; l += WAVE) mx = fmaxf(mx, sm[L.s + l]);
-    mx = wave_max(mx);
-    for (int l = tid; l < P; l += NT) sm[O.x + l] = expf(sm[L.s + l] - mx);
-    const float fo = wave_sum(sm[O.fo + lane]);
-    __syncthreads();
-    float Z = 0.f, N = 0.f;
-    for (int l = lane; l < P; l += WAVE) {
-      const float ex = sm[O.x + l];
-      Z += ex;
-      N += ex * sm[L.r + l];
-    }
-    Z = wave_sum(Z);
-    N = wave_sum(N);
-    const float att = N / Z;
-    const float bias_w = ftrl ? ftrl_w(sm[O.misc], sm[O.misc + 1], a.h) : sm[O.misc];
-    const float logit = (bias_w + fo) + att;
-    float loss, g;
-    bce_loss_dz(FMX_LOSS_BCE_LOGITS, logit, y, 1.0f, loss, g);
-    if (tid == 0) {
-      if (a.logit) a.logit[i] = logit;
-      if (a.loss) a.loss[i] = 0.f + loss;  // the update's block_sum over one sample
-    }
-
-    // ---- pass B: rounds of nb tiles ----
-    for (int i0r = 0, pbr = 0; i0r < F - 1;) {
-      int i0 = i0r, pb = pbr, cnt = 0;
-      for (; cnt < nb && i0 < F - 1; ++cnt) {
-        int n;
-        const int i1 = next_tile(F, i0, n);
-        if (cnt == wv && lane < n) {
-          int pi, pj;
-          tile_pair(F, i0, lane, pi, pj);
-          pair_backward<KP>(sm, L, tile_buf(O, KP, t, cnt), t, pi, pj, lane, sm[O.x + pb + lane], Z, g, att);
+      onl_pass_b<KP>(a, O, sm, Z, g, att);
+    } else {
+      const float zn = onl_forward<KP>(a, R, O, sm, S, row[1], in.x[1], ok[1], Z, att);
+      const float zp = onl_forward<KP>(a, R, O, sm, S, row[0], in.x[0], ok[0], Z, att);
+      pair_loss_dz(zp - zn, margin, 1.0f, loss, g);
+      if (tid == 0) {
+        if (a.logit) {
+          a.logit[2 * (size_t)i] = zp;
+          a.logit[2 * (size_t)i + 1] = zn;
         }
-        pb += n;
-        i0 = i1;
+        if (a.loss) a.loss[i] = (0.f + loss) + 0.f;  // the update's block_sum over the two rows: the pair's loss, then +0
       }
-      __syncthreads();
-      i0 = i0r;
-      for (int c = 0; c < cnt; ++c) {
-        int n;
-        const int i1 = next_tile(F, i0, n);
-        add_tile<KP>(sm, L, tile_buf(O, KP, t, c), F, t, i0, i1, n, tid, NT);
-        i0 = i1;
-      }
-      __syncthreads();
-      i0r = i0;
-      pbr = pb;
-    }
-
-    // ---- the attention parameters: column g's gradient is 0 + the one workgroup's partial (afm_reduce_column), then the rule ----
-    {
-      fmx_hyper_t ho;
-      ho.lr = a.o_lr;
-      ho.eps = a.o_eps;
-      if (o_m) {
-        const float *kc = sm + O.misc + ONL_KC;
-        ho.lr = kc[3];
-        ho.beta1 = kc[4];
-        ho.beta2 = kc[5];
-        ho.eps = kc[6];
-      }
-      for (int c = tid; c < G; c += NT) {
-        int par, acc;
-        onl_column(L, c, k, t, KP, par, acc);
-        const float s = 0.f + sm[acc];
-        if (i == a.N - 1) a.grad[c] = s;
-        float p = sm[par], m = 0.f, v = 0.f;
-        if (o_v) v = vv[c];
-        if (o_m) m = mm[c];
-        switch (a.o_rule) {
-          case FMX_RULE_SIGNADAM: afm_opt_column<FMX_RULE_SIGNADAM>(p, m, v, s, ho); break;
-          case FMX_RULE_SGD: afm_opt_column<FMX_RULE_SGD>(p, m, v, s, ho); break;
-          case FMX_RULE_ADAGRAD: afm_opt_column<FMX_RULE_ADAGRAD>(p, m, v, s, ho); break;
-          default: afm_opt_column<FMX_RULE_ADAM>(p, m, v, s, ho); break;
-        }
-        if (o_v) vv[c] = v;
-        if (o_m) mm[c] = m;
-        sm[par] = p;
-      }
-    }
-    // ---- the tables: every row of the sample is a run of one occurrence of k_fm_update_occ ----
-    fmx_hyper_t ht = a.h;
-    if (a.rule == FMX_RULE_ADAM) {
-      const float *kc = sm + O.misc + ONL_KC;
-      ht.lr = kc[0];
-      ht.beta1 = kc[1];
-      ht.beta2 = kc[2];
-    }
+      onl_pass_b<KP>(a, O, sm, Z, g, att);
 #pragma unroll
-    for (int p = 0; p < NP; ++p) {
-      if (ok[p]) {
-        const float4 E = x[p] * *reinterpret_cast<const float4 *>(sm + L.Ea + fld[p] * KP + 4 * qq[p]);  // k_afm's dL/dV_row
-        onl_update_row(a.rule, a.rows + (size_t)(lo[p] + li[p]) * a.stride, qq[p], KP, a.zoff, row[p], splat(0.f) + E, 0.f + x[p] * g,
-                       ht);
+      for (int p = 0; p < NP; ++p) {
+        EP[p] = splat(0.f);
+        if (S.live[p]) {
+          float4 *ea = reinterpret_cast<float4 *>(sm + L.Ea + S.fld[p] * KP + 4 * S.qq[p]);
+          EP[p] = in.x[0][p] * *ea;  // k_afm's dL/dV_row
+          *ea = splat(0.f);
+        }
       }
+      onl_forward<KP>(a, R, O, sm, S, row[1], in.x[1], ok[1], Z, att);
+      onl_pass_b<KP>(a, O, sm, Z, -g, att);
     }
-    if (tid == 0) {
-      float b0 = sm[O.misc], b1 = sm[O.misc + 1], b2 = sm[O.misc + 2];
-      onl_bias_step(a.rule, b0, b1, b2, 0.f + g, ht);
-      sm[O.misc] = b0;
-      sm[O.misc + 1] = b1;
-      sm[O.misc + 2] = b2;
+    onl_attn_rule<KP>(a, R, O, sm, mm, vv, i);
+
+    // ---- the tables: k_fm_update_occ on the unit's rows, from the registers that hold them ----
+    const fmx_hyper_t ht = onl_table_hyper(a, O, sm);
+    if constexpr (T == 1) {
+#pragma unroll
+      for (int p = 0; p < NP; ++p) {
+        if (ok[0][p]) {
+          const float4 E = in.x[0][p] * *reinterpret_cast<const float4 *>(sm + L.Ea + S.fld[p] * KP + 4 * S.qq[p]);  // k_afm's dL/dV_row
+          onl_update_row(a.rule, a.rows + (size_t)(S.lo[p] + in.li[0][p]) * a.stride, S.qq[p], KP, a.zoff, row[0][p], splat(0.f) + E,
+                         0.f + in.x[0][p] * g, ht);
+        }
+      }
+      onl_bias_words(a, O, sm, 0.f + g, ht);
+    } else {
+      const float gn = -g;
+#pragma unroll
+      for (int p = 0; p < NP; ++p) {
+        if (S.live[p]) {
+          const float4 EN = in.x[1][p] * *reinterpret_cast<const float4 *>(sm + L.Ea + S.fld[p] * KP + 4 * S.qq[p]);
+          const float cwp = in.x[0][p] * g, cwn = in.x[1][p] * gn;
+          float *rp0 = a.rows + (size_t)(S.lo[p] + in.li[0][p]) * a.stride, *rp1 = a.rows + (size_t)(S.lo[p] + in.li[1][p]) * a.stride;
+          if (ok[0][p] && ok[1][p] && in.li[0][p] == in.li[1][p]) {
+            onl_update_row(a.rule, rp0, S.qq[p], KP, a.zoff, row[0][p], (splat(0.f) + EP[p]) + EN, (0.f + cwp) + cwn, ht);
+          } else {
+            if (ok[0][p]) onl_update_row(a.rule, rp0, S.qq[p], KP, a.zoff, row[0][p], splat(0.f) + EP[p], 0.f + cwp, ht);
+            if (ok[1][p]) onl_update_row(a.rule, rp1, S.qq[p], KP, a.zoff, row[1][p], splat(0.f) + EN, 0.f + cwn, ht);
+          }
+        }
+      }
+      onl_bias_words(a, O, sm, (0.f + g) + gn, ht);  // exactly +0: the moments still decay
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the row stores are acknowledged ...
     __syncthreads();                                   // ... before any thread's next gather
   }
+  onl_close<KP>(a, R, O, sm, mm, vv, bad);
+}
 
-  // ---- the state back to global memory ----
-  if (bad) sm[O.misc + ONL_FLAG] = 1.f;
-  for (int c = tid; c < G; c += NT) {
-    int par, acc;
-    onl_column(L, c, k, t, KP, par, acc);
-    a.params[c] = sm[par];
-    if (a.mom_lds) {
-      if (o_m) a.m[c] = mm[c];
-      if (o_v) a.v[c] = vv[c];
-    }
-  }
-  __syncthreads();
-  if (tid == 0) {
-    a.bias[0] = sm[O.misc];
-    if (ftrl || a.rule == FMX_RULE_ADAM) a.bias[1] = sm[O.misc + 1];
-    if (mom_rule) a.bias[2] = sm[O.misc + 2];
-    if (sm[O.misc + ONL_FLAG] != 0.f && a.error) *a.error = 1;
-  }
+template <int KP>
+__global__ __launch_bounds__(AFM_ONL_THREADS) void k_afm_online(AfmOnlArgs a) {
+  afm_walk<KP, 1>(a, 0.f);
 }

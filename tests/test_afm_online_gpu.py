@@ -17,6 +17,7 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from afm_f64 import afm_f64  # noqa: E402
 from helpers import assert_within_f64  # noqa: E402
 from test_afm_gpu import batch, engine, make  # noqa: E402
+from test_afm_pair_online_cpu import MOMENTS_IN_GLOBAL  # noqa: E402
 from test_afm_stream_gpu import LAYOUT, _hyper, _same_models, attn_opt, check_attention, opt_state  # noqa: E402
 
 pytestmark = pytest.mark.gpu
@@ -129,6 +130,24 @@ def test_online_run_other_shapes(F, k, t, rule, arule):
     want = per_sample(rule, arule, sizes, k, t, data)
     assert int(want["error"]) == 0
     assert_same(online(rule, arule, sizes, k, t, data), want, f"F={F} k={k} t={t}")
+
+
+def test_moments_in_global_memory():
+    """At this shape the attention moments would cost a tile buffer, so k_afm_online reads and writes them in global memory through
+    the pointer that elsewhere names LDS (the walk's shared mm / vv path; the pair kernel's test of the same name runs it for
+    pairs).  The witness that the shape takes that path is fmx_afm_pair_online_form: both entry points take the decision from
+    afm_online_buffers, each under its own option, and both options are on here."""
+    F, k, t = MOMENTS_IN_GLOBAL
+    sizes = small_sizes(F, F + 4)
+    _, _, eng, _, _ = start("adam", "adam", sizes, k, t)
+    nb, mom_lds = eng.pair_online_form("adam")
+    assert nb > 0 and not mom_lds, f"{nb} tile buffers, moments in LDS {mom_lds}: not the form this test is about"
+    data = stream_data(sizes, N_STREAM, seed=700 + F, with_xv=True)
+    want = per_sample("adam", "adam", sizes, k, t, data)
+    assert int(want["error"]) == 0
+    got = online("adam", "adam", sizes, k, t, data)
+    assert_same(got, want, "moments in global memory")
+    assert bool((got["m"] != 0).any()) and bool((got["v"] != 0).any())
 
 
 @pytest.mark.parametrize("rule,arule", [("adam", "adam"), ("ftrl", "signadam")])
