@@ -18,7 +18,10 @@
  *   - every other call is asynchronous on `stream` (a hipStream_t passed as void*) and performs no implicit
  *     synchronisation; work the library puts on its own streams is ordered behind what `stream` held at the call and
  *     `stream` is ordered behind it before the call returns.  Calls are safe to capture into a hipGraph except fmx_fm_stream
- *     (cross-stream events, optional timing); a capturing stream takes the paths without in-launch hand-offs;
+ *     (cross-stream events, optional timing); a capturing stream takes the paths without in-launch hand-offs.  A captured
+ *     launch keeps the scalars the host computed at capture: under FMX_RULE_ADAM the step constants come from hyper->step on the
+ *     host, so every replay repeats the captured step's constants -- an Adam step per replay needs a re-capture per step, or the
+ *     *_stream / online entries, which advance the count themselves;
  *   - return value: 0 on success, a negative fmx_status otherwise; the message for the calling thread is
  *     available from fmx_last_error_string();
  *   - streams: fmx_fm_stream / fmx_deepfm_stream sort on a library-owned low-priority side stream beside the caller's stream.  HIP maps

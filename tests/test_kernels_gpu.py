@@ -392,10 +392,11 @@ def test_stream_matches_repeated_steps(fmx):
 @pytest.mark.parametrize("rule", ["signadam", "sgd", "ftrl"])
 def test_stream_sort_groups_rules_and_streams(fmx, rule, B, on_side_stream):
     """As test_stream_matches_repeated_steps, through every part of the loop: B = 256 takes the single-stream loop, B = 1024
-    the sorts ahead on the side stream (OVERLAP_MIN_BATCH = 512); 21 steps over a pool of 5 batches are sort groups of
-    4 + 8 + 8 + 1 that wrap the pool and reuse both halves of the sorted ring.  Torch's default stream (handle 0, the legacy
-    default stream: the loop detours off it) and a stream of its own."""
-    stream_vs_steps(fmx, rule, B, 5, 21, on_side_stream)
+    the sorts ahead on the side stream (OVERLAP_MIN_BATCH = 512); 41 steps over a pool of 5 batches are sort groups of
+    4 + 16 + 16 + 5 (SORT_AHEAD_MAX = 16): two full groups that wrap the pool and reuse both halves of the sorted ring, and a
+    partial last group.  Torch's default stream (handle 0, the legacy default stream: the loop detours off it) and a stream of
+    its own."""
+    stream_vs_steps(fmx, rule, B, 5, 41, on_side_stream)
 
 
 def stream_vs_steps(fmx, rule, B, n_pool, n_steps, on_side_stream):

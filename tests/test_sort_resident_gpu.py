@@ -15,6 +15,8 @@ import numpy as np
 import pytest
 import torch
 
+from update_forms import same          # bit for bit, the words as integers
+
 pytestmark = pytest.mark.gpu
 
 # a one-row field, an empty one, fields of at most 511 rows (one counting pass) and larger ones (the bitonic network)
@@ -101,13 +103,6 @@ def run_steps(fmx, sizes, k, rule, idx, y, table_kw=None):
             loss[c * N_STEPS + s] = eng.loss_out[0]
     torch.cuda.synchronize()
     return dict(rows=t.rows.clone(), bias=t.bias.clone(), loss=loss, error=eng.error.clone())
-
-
-def same(got, ref, what):
-    for name in ref:
-        # bit for bit: the words as integers (a NaN would differ from itself otherwise)
-        a, b = got[name].contiguous().view(torch.int32), ref[name].contiguous().view(torch.int32)
-        assert torch.equal(a, b), f"{what}: {name}: {int((a != b).sum())} words differ"
 
 
 _REFS = {}
