@@ -1,7 +1,9 @@
 // fmx_rank.inc -- exact ranks of held-out targets (fmx_fm_rank, fmx_mlp_rank, fmx_afm_rank; include/fmx.h): the device
 // side that the three scans of fmx_topk.hip share.  Included by fmx_topk.hip ahead of its scans, which are templates on what
 // they do with a score (SCAN_TOPK / SCAN_COUNT / SCAN_KEYS below): the score is the scan's own loop, instantiated again, the
-// order is make_key's, the exclusion test is excluded().  The entry points are in fmx_rank_host.inc.
+// order is make_key's, the exclusion test is excluded().  What a scan does with a score in each of the three is stated once,
+// in ScanSink below (the AFM scan, which measured slower through it, spells it out itself); the entry points are at the end of
+// fmx_topk.hip.
 //
 // Two phases per family.  Phase 1 (SCAN_KEYS) scores the U x T target pairs and writes their keys (0: no eligible target) to
 // the workspace.  Phase 2 (SCAN_COUNT) is the family's scan with the selection slots replaced by counters: for every user of the tile the T
@@ -112,6 +114,73 @@ __device__ void emit_counts(const RankLds &r, const RankIo &io, int u0, int n, i
     io.cnt[((size_t)(u0 + j) * splits + split) * W + t] = r.cnt[i];
   }
 }
+
+// What a scan does with its scores, for the users u0 .. u0 + nu - 1 of a workgroup (nu <= NU; CHUNK: the candidates the scan
+// scores between two cuts).  The scan keeps its score loop and its barriers; the MODE is spelled out here only.
+//   open:  the mode's LDS state and the workgroup's candidates [c_begin, c_end); false when a SCAN_KEYS workgroup has no target
+//   take:  the pair (slot j, candidate c) with its score; called by whole waves
+//   cut:   after a chunk, SCAN_TOPK: the slots that could overflow go back to their K best.  Entered after a barrier.
+//   close: the workgroup's results to the workspace or the final rows.  SCAN_COUNT: entered after a barrier.
+template <int MODE, int NU, int CHUNK>
+struct ScanSink {
+  Slots s;
+  RankLds rk;
+  int target, u0, nu, c_begin, c_end;
+
+  template <class Args, class User>
+  __device__ __forceinline__ bool open(const Args &a, uint64_t *slot_lds, User first_user, int users) {
+    u0 = (int)first_user;
+    nu = users;
+    target = -1;
+    if constexpr (MODE == SCAN_TOPK) init_slots(s, slot_lds, nu, a.cap);
+    if constexpr (MODE == SCAN_COUNT) {
+      __shared__ RankShared<NU> sh;
+      init_rank(rk, sh, a.r.tkeys + (size_t)first_user * a.r.T, nu, a.r.T);
+    }
+    if constexpr (MODE == SCAN_KEYS) {
+      target = keys_target(a.r, u0, blockIdx.y, a.N);
+      if (target < 0) return false;
+    }
+    c_begin = MODE == SCAN_KEYS ? target / CHUNK * CHUNK : blockIdx.y * a.per;
+    c_end = min(a.N, c_begin + (MODE == SCAN_KEYS ? CHUNK : a.per));
+    return true;
+  }
+
+  template <class Args>
+  __device__ __forceinline__ void take(const Args &a, int j, int c, bool valid, float score) {
+    const uint64_t key = make_key(score, c);
+    if constexpr (MODE == SCAN_TOPK) {
+      bool keep = valid && score == score && key > s.thr[j];
+      if (keep && a.excl_off) keep = !excluded(a.excl_off, a.excl_pos, u0 + j, c);
+      append(s, j, a.cap, keep, key);
+    } else if constexpr (MODE == SCAN_COUNT) {
+      count_pair(rk, j, a.r.T, valid, score, key, a.excl_off, a.excl_pos, u0 + j, c);
+    } else if (valid && c == target) {  // (one user per workgroup: j = 0)
+      a.r.tkeys[(size_t)u0 * a.r.T + blockIdx.y] = target_key(score, c, a.excl_off, a.excl_pos, u0);
+    }
+  }
+
+  // after the first chunk every slot is cut to K at once (the thresholds start rising); later only slots that could overflow
+  template <class Args>
+  __device__ __forceinline__ void cut(const Args &a, int c0) {
+    if constexpr (MODE == SCAN_TOPK) compact(s, nu, a.cap, a.K, c0 == c_begin ? a.K : a.cap - CHUNK);
+  }
+
+  template <class Args>
+  __device__ __forceinline__ void close(const Args &a) {
+    if constexpr (MODE == SCAN_COUNT) emit_counts(rk, a.r, u0, nu, a.splits, blockIdx.y);
+    if constexpr (MODE == SCAN_TOPK) {
+      compact(s, nu, a.cap, a.K, -1);
+      for (int j = 0; j < nu; ++j) {
+        const int u = u0 + j;
+        if (a.splits > 1)
+          emit(s, j, a.cap, a.K, a.parts + ((size_t)u * a.splits + blockIdx.y) * a.K, nullptr, nullptr);
+        else
+          emit(s, j, a.cap, a.K, nullptr, a.top_pos + (size_t)u * a.K, a.top_score + (size_t)u * a.K);
+      }
+    }
+  }
+};
 
 // ---- the finishing launch: one workgroup per user ----------------------------------------------------------------------
 struct RankFinishArgs {

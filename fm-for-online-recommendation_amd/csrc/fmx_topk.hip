@@ -9,8 +9,11 @@
 // cut to its K best, which raises the threshold.  The set kept is the exact top K of what the slot has seen, whatever the
 // order of the appends, so the result is independent of scheduling.
 //
-// fmx_mlp_topk (the DeepFM / NFM classes, at the end of this file) feeds the same slots from a scan that runs the whole
-// network on every pair.
+// fmx_mlp_topk (the DeepFM / NFM classes) feeds the same slots from a scan that runs the whole network on every pair, and
+// fmx_afm_topk from one that computes the attentional FM's cross pairs.  The rank calls (fmx_*_rank) are the same three scans
+// with the slots replaced by counters (fmx_rank.inc, which also holds ScanSink: what a scan does with a score, stated once for
+// the FM and the network scan).  The host side of all six entry points is at the end of this file: a plan per family, a driver
+// per call.
 #include "fmx_host.h"
 
 namespace {
@@ -43,12 +46,12 @@ inline TopkGeom topk_geom(int U, int N, int K) {
   return g;
 }
 
-// Partial lists in the workspace: uint64 [U, splits, K].  Bounded by a formula that is monotone in U, N and K (the splits
-// of the geometry are not): splits <= ceil(N / TK_SPLIT_MIN) and U * splits <= U + TK_TILE_BUDGET * TK_MAX_UT.
-inline int64_t topk_ws_bytes(int U, int N, int K) {
+// The workspace holds a partial result per (user, split): uint64 [U, splits, K] lists for fmx_fm_topk, int32 [U, splits, T + 1]
+// counts for fmx_fm_rank.  U * splits is bounded by a formula that is monotone in U and N (the splits of the geometry are not):
+// splits <= ceil(N / TK_SPLIT_MIN) and U * splits <= U + TK_TILE_BUDGET * TK_MAX_UT.
+inline int64_t fm_scan_parts(int U, int N) {
   const int64_t sn = std::min<int64_t>(TK_MAX_SPLITS, (N + TK_SPLIT_MIN - 1) / TK_SPLIT_MIN);
-  const int64_t parts = std::min<int64_t>((int64_t)U * sn, (int64_t)U + (int64_t)TK_TILE_BUDGET * TK_MAX_UT);
-  return parts * K * 8;
+  return std::min<int64_t>((int64_t)U * sn, (int64_t)U + (int64_t)TK_TILE_BUDGET * TK_MAX_UT);
 }
 
 struct TopkArgs {
@@ -210,21 +213,10 @@ namespace {
 template <int KP, int MODE = SCAN_TOPK, class Args = TopkArgs>
 __global__ __launch_bounds__(TK_THREADS) void k_topk_scan(Args a) {
   extern __shared__ uint64_t tk_lds[];
-  Slots s;
-  RankLds rk;
-  int target = -1;
+  ScanSink<MODE, TK_MAX_UT, TK_THREADS> sink;
   const int u0 = blockIdx.x * a.ut, nu = min(a.ut, a.U - u0);
-  if constexpr (MODE == SCAN_TOPK) init_slots(s, tk_lds, nu, a.cap);
-  if constexpr (MODE == SCAN_COUNT) {
-    __shared__ RankShared<TK_MAX_UT> sh;
-    init_rank(rk, sh, a.r.tkeys + (size_t)u0 * a.r.T, nu, a.r.T);
-  }
-  if constexpr (MODE == SCAN_KEYS) {
-    target = keys_target(a.r, u0, blockIdx.y, a.N);
-    if (target < 0) return;
-  }
-  const int c_begin = MODE == SCAN_KEYS ? target / TK_THREADS * TK_THREADS : blockIdx.y * a.per;
-  const int c_end = min(a.N, c_begin + (MODE == SCAN_KEYS ? TK_THREADS : a.per));
+  if (!sink.open(a, tk_lds, u0, nu)) return;
+  const int c_begin = sink.c_begin, c_end = sink.c_end;
   const float *__restrict__ Su = a.Su;
   const float *__restrict__ au = a.au;
   for (int c0 = c_begin; c0 < c_end; c0 += TK_THREADS) {
@@ -251,38 +243,14 @@ __global__ __launch_bounds__(TK_THREADS) void k_topk_scan(Args a) {
       for (int r = 0; r < R; ++r) {
         const int j = j0 + r;
         if (R > 1 && j >= nu) break;
-        const uint64_t key = make_key(score[r], c);
-        if constexpr (MODE == SCAN_TOPK) {
-          bool keep = valid && score[r] == score[r] && key > s.thr[j];
-          if (keep && a.excl_off) keep = !excluded(a.excl_off, a.excl_pos, u0 + j, c);
-          append(s, j, a.cap, keep, key);
-        } else if constexpr (MODE == SCAN_COUNT) {
-          count_pair(rk, j, a.r.T, valid, score[r], key, a.excl_off, a.excl_pos, u0 + j, c);
-        } else if (valid && c == target) {
-          a.r.tkeys[(size_t)u0 * a.r.T + blockIdx.y] = target_key(score[r], c, a.excl_off, a.excl_pos, u0);
-        }
+        sink.take(a, j, c, valid, score[r]);
       }
     }
-    if constexpr (MODE == SCAN_TOPK) {
-      __syncthreads();
-      // after the first chunk every slot is cut to K at once (the thresholds start rising); later only slots that could overflow
-      compact(s, nu, a.cap, a.K, c0 == c_begin ? a.K : a.cap - TK_THREADS);
-    }
+    if constexpr (MODE == SCAN_TOPK) __syncthreads();  // every append of the chunk, before the counts are read
+    sink.cut(a, c0);
   }
-  if constexpr (MODE == SCAN_COUNT) {
-    __syncthreads();
-    emit_counts(rk, a.r, u0, nu, a.splits, blockIdx.y);
-  }
-  if constexpr (MODE == SCAN_TOPK) {
-    compact(s, nu, a.cap, a.K, -1);
-    for (int j = 0; j < nu; ++j) {
-      const int u = u0 + j;
-      if (a.splits > 1)
-        emit(s, j, a.cap, a.K, a.parts + ((size_t)u * a.splits + blockIdx.y) * a.K, nullptr, nullptr);
-      else
-        emit(s, j, a.cap, a.K, nullptr, a.top_pos + (size_t)u * a.K, a.top_score + (size_t)u * a.K);
-    }
-  }
+  if constexpr (MODE == SCAN_COUNT) __syncthreads();
+  sink.close(a);
 }
 
 // one workgroup per user: the union of the user's `splits` sorted partial lists, read depth-major (the best of every list,
@@ -393,10 +361,23 @@ inline MlpTopkGeom mlp_topk_geom(const MlpShape &s, int U, int N, int K) {
   g.splits = (N + g.per - 1) / g.per;
   return g;
 }
-// packed weights, then the partial lists uint64 [U, splits, K]: U * splits <= U * ceil(budget / U) < U + budget
-inline int64_t mlp_topk_ws_bytes(const MlpShape &s, int U, int N, int K) {
-  const int64_t parts = std::min<int64_t>((int64_t)U * tm_max_splits(s, N), (int64_t)U + TM_TILE_BUDGET);
-  return mlp_packed_floats(s, nullptr) * 4 + parts * K * 8;
+// the workspace: the packed weights, then a partial result per (user, split); U * splits <= U * ceil(budget / U) < U + budget
+inline int64_t mlp_scan_parts(const MlpShape &s, int U, int N) {
+  return std::min<int64_t>((int64_t)U * tm_max_splits(s, N), (int64_t)U + TM_TILE_BUDGET);
+}
+
+// f(WC, NCT) as integral constants: the wave grid of the network scan for NT column tiles of 16.  WC wave columns (and 4 / WC
+// wave rows); a wave owns NCT = ceil(NT / WC) column tiles of every layer.
+template <class Fn>
+decltype(auto) with_wave_grid(int NT, Fn &&f) {
+  using std::integral_constant;
+  if (NT <= 1) return f(integral_constant<int, 1>{}, integral_constant<int, 1>{});
+  if (NT == 2) return f(integral_constant<int, 2>{}, integral_constant<int, 1>{});
+  if (NT == 3) return f(integral_constant<int, 2>{}, integral_constant<int, 2>{});
+  if (NT == 4) return f(integral_constant<int, 4>{}, integral_constant<int, 1>{});
+  if (NT <= 8) return f(integral_constant<int, 4>{}, integral_constant<int, 2>{});
+  if (NT <= 12) return f(integral_constant<int, 4>{}, integral_constant<int, 3>{});
+  return f(integral_constant<int, 4>{}, integral_constant<int, 4>{});
 }
 
 // one thread per packed float
@@ -450,26 +431,15 @@ __global__ __launch_bounds__(256) void k_mlp_topk_scan(Args a) {
   const int NT = a.Hp / 16;
   const int wmax = a.K0 > a.Hp ? a.K0 : a.Hp;
   float *X = tm_lds;
-  Slots s;
-  RankLds rk;
-  int target = -1;
-  if constexpr (MODE == SCAN_TOPK) init_slots(s, reinterpret_cast<uint64_t *>(X + (size_t)TM_ROWS * wmax), 1, a.cap);
-  if constexpr (MODE == SCAN_COUNT) {
-    __shared__ RankShared<1> sh;
-    init_rank(rk, sh, a.r.tkeys + (size_t)blockIdx.x * a.r.T, 1, a.r.T);
-  }
-  if constexpr (MODE == SCAN_KEYS) {
-    target = keys_target(a.r, blockIdx.x, blockIdx.y, a.N);
-    if (target < 0) return;
-  }
+  ScanSink<MODE, 1, TM_ROWS> sink;
+  if (!sink.open(a, reinterpret_cast<uint64_t *>(X + (size_t)TM_ROWS * wmax), blockIdx.x, 1)) return;
   const int t = threadIdx.x, lane = t & 63, w = t >> 6, wr = w / WC, wc = w % WC;
   const int m = lane & 15, kq = lane >> 4;
   const int u = blockIdx.x;
   const float *__restrict__ Su = a.Su + (size_t)u * a.ld_u;
   const float *__restrict__ Bu = a.Bu + (size_t)u * a.ld_u;
   const float au = a.au[u];
-  const int c_begin = MODE == SCAN_KEYS ? target / TM_ROWS * TM_ROWS : blockIdx.y * a.per;
-  const int c_end = min(a.N, c_begin + (MODE == SCAN_KEYS ? TM_ROWS : a.per));
+  const int c_begin = sink.c_begin, c_end = sink.c_end;
   const int G0 = a.K0 / 16, Gh = a.Hp / 16;
   for (int c0 = c_begin; c0 < c_end; c0 += TM_ROWS) {
     // x0[r][d] = fma(Su[d], Sc[d], Bu[d] + Bc[d]) for d < k, 0 on the pad columns (rows past the split repeat its last one)
@@ -543,29 +513,14 @@ __global__ __launch_bounds__(256) void k_mlp_topk_scan(Args a) {
         for (int d = 1; d < a.kp; ++d) dot = fmaf(Su[d], sc[d], dot);
         base = base + dot;
       }
-      const float score = base + sum;
-      const uint64_t key = make_key(score, c);
-      if constexpr (MODE == SCAN_TOPK) {
-        bool keep = valid && score == score && key > s.thr[0];
-        if (keep && a.excl_off) keep = !excluded(a.excl_off, a.excl_pos, u, c);
-        append(s, 0, a.cap, keep, key);
-      } else if constexpr (MODE == SCAN_COUNT) {
-        count_pair(rk, 0, a.r.T, valid, score, key, a.excl_off, a.excl_pos, u, c);
-      } else if (valid && c == target) {
-        a.r.tkeys[(size_t)u * a.r.T + blockIdx.y] = target_key(score, c, a.excl_off, a.excl_pos, u);
-      }
+      sink.take(a, 0, c, valid, base + sum);
     }
-    __syncthreads();  // the row sums have been read: the next chunk may overwrite the activations
-    if constexpr (MODE == SCAN_TOPK) compact(s, 1, a.cap, a.K, c0 == c_begin ? a.K : a.cap - TM_ROWS);
+    // the row sums have been read: the next chunk may overwrite the activations.  In every mode this is also the barrier the
+    // sink's cut and close are entered after.
+    __syncthreads();
+    sink.cut(a, c0);
   }
-  if constexpr (MODE == SCAN_COUNT) emit_counts(rk, a.r, u, 1, a.splits, blockIdx.y);
-  if constexpr (MODE == SCAN_TOPK) {
-    compact(s, 1, a.cap, a.K, -1);
-    if (a.splits > 1)
-      emit(s, 0, a.cap, a.K, a.parts + ((size_t)u * a.splits + blockIdx.y) * a.K, nullptr, nullptr);
-    else
-      emit(s, 0, a.cap, a.K, nullptr, a.top_pos + (size_t)u * a.K, a.top_score + (size_t)u * a.K);
-  }
+  sink.close(a);
 }
 // ---------------------------------------------------------------------------------------------------------------------
 // fmx_afm_topk: the same selection over the exact AFM logit of the combined sample
@@ -603,12 +558,11 @@ inline int64_t at_split_min(int n_ctx, int n_item, int t, int kp) {
 inline int64_t at_max_splits(int64_t split_min, int N) { return std::min<int64_t>(AT_MAX_SPLITS, (N + split_min - 1) / split_min); }
 inline int at_kp(int k) { return k <= 4 ? 4 : k <= 8 ? 8 : k <= 16 ? 16 : k <= 32 ? 32 : 64; }
 inline int64_t at_packed_bytes(int t) { return (int64_t)align_up((size_t)(t * 64 + 2 * t + 64) * 4, 256); }
-// the padded parameter copy (sized for kp = 64), then the partial lists uint64 [U, splits, K] (U * splits < U + budget).  The
-// split minimum is taken at the smallest kp that holds k, by the workspace size and by the call alike.
-inline int64_t afm_topk_ws_bytes(const fmx_afm_t *afm, int n_ctx, int n_item, int U, int N, int K) {
+// the workspace: the padded parameter copy (sized for kp = 64), then a partial result per (user, split); U * splits < U + budget.
+// The split minimum is taken at the smallest kp that holds k, by the workspace size and by the call alike.
+inline int64_t afm_scan_parts(const fmx_afm_t *afm, int n_ctx, int n_item, int U, int N) {
   const int64_t sm = at_split_min(n_ctx, n_item, afm->t, at_kp(afm->k));
-  const int64_t parts = std::min<int64_t>((int64_t)U * at_max_splits(sm, N), (int64_t)U + AT_TILE_BUDGET);
-  return at_packed_bytes(afm->t) + parts * K * 8;
+  return std::min<int64_t>((int64_t)U * at_max_splits(sm, N), (int64_t)U + AT_TILE_BUDGET);
 }
 
 // one thread per float of the padded copy
@@ -633,6 +587,8 @@ __global__ __launch_bounds__(256) void k_afm_topk_pack(const float *params, int 
 // field i ascending), each as k_afm's pair_terms, folded into a running (max, Z, R) by online rescaling, then the two sides.
 // MODE (fmx_rank.inc): the top-K selection (Args = AfmTopkArgs), or one of the rank call's two phases (Args = AfmRankArgs; grid
 // (U, T) for SCAN_KEYS).
+// This scan spells its three modes out itself instead of going through ScanSink: with the sink its instantiations at kp = 16
+// measured 0.3 - 1.2 % slower than this text on the same score loop (profiles/scan_seam_ab.txt, section B).
 template <int KP, int MODE = SCAN_TOPK, class Args = AfmTopkArgs>
 __global__ __launch_bounds__(TK_THREADS) void k_afm_topk_scan(Args a) {
   extern __shared__ uint64_t tk_lds[];
@@ -729,20 +685,25 @@ __global__ __launch_bounds__(TK_THREADS) void k_afm_topk_scan(Args a) {
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
-// host side of the entry points
+// host side of the six entry points (fmx_{fm,mlp,afm}_{topk,rank}; include/fmx.h)
 // ---------------------------------------------------------------------------------------------------------------------
+// Two axes, each stated once.  A family's plan (FmScan, MlpScan, AfmScan) holds what both of its calls need: the checks, the
+// bound on U * splits, the pack launch and the workspace prefix it fills, the geometry, the base argument struct and the
+// dispatch to the scan's instantiation.  A call's end (TopkEnd, RankEnd) holds what it asks of any family: its size checks, its
+// outputs and what a partial result weighs.  scan_topk / scan_rank drive any plan.
 constexpr size_t slots_lds(int n, int cap) { return (size_t)n * cap * 8 + (size_t)n * 8 + (size_t)n * 4; }
-size_t mlp_topk_lds(const MlpShape &s, int cap) { return (size_t)TM_ROWS * std::max(s.K0, s.Hp) * 4 + slots_lds(1, cap); }
 
-// A launch of one of the slot kernels (256 threads).  The scans hold 64 KiB of keys or of activations plus a slot, above the
-// default dynamic LDS limit, so every slot kernel's limit is raised to 80 KiB on its first launch.
+// A launch of one of the slot kernels (256 threads).  A launch with dynamic LDS holds 64 KiB of keys or of activations plus
+// a slot, above the default dynamic LDS limit, so such a kernel's limit is raised to 80 KiB on its first launch.
 template <auto Kernel, class Args>
 int launch_slots(const char *name, dim3 grid, size_t lds, hipStream_t st, const Args &a) {
-  static const bool raised = [] {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
-    return true;
-  }();
-  (void)raised;
+  if (lds != 0) {
+    static const bool raised = [] {
+      (void)hipFuncSetAttribute(reinterpret_cast<const void *>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
+      return true;
+    }();
+    (void)raised;
+  }
   hipLaunchKernelGGL(Kernel, grid, dim3(TK_THREADS), lds, st, a);
   return check_launch(name);
 }
@@ -762,52 +723,286 @@ int merge_topk(uint64_t *parts, int32_t *top_pos, float *top_score, int32_t U, i
   return launch_slots<k_topk_merge>("k_topk_merge", dim3(U), slots_lds(1, m.cap), st, m);
 }
 
-int check_topk_sizes(const char *fn, int32_t U, int32_t N, int32_t K) {
-  if (U < 1 || N < 1) return fail(FMX_ERR_ARG, "%s: U=%d and N=%d must be >= 1", fn, U, N);
-  if (K < 1) return fail(FMX_ERR_ARG, "%s: K=%d must be >= 1", fn, K);
-  if (K > TK_MAX_K) return fail(FMX_ERR_UNSUPPORTED, "%s: K=%d, the kernels cover K <= %d", fn, K, TK_MAX_K);
-  return FMX_OK;
+// ---- the two calls ------------------------------------------------------------------------------------------------------
+// scan_K: the K of the family's geometry and arguments.  out_a / out_b: the call's two required outputs.  part_bytes: the
+// workspace behind the family's prefix, given the family's bound on U * splits.  ws_args: how the family's *_workspace_bytes
+// call begins ("", "mlp, ", "afm, n_ctx, n_item, ").
+struct TopkEnd {
+  int32_t K;
+  int32_t *top_pos;
+  float *top_score;
+  int scan_K() const { return K; }
+  const void *out_a() const { return top_pos; }
+  const void *out_b() const { return top_score; }
+  int check_sizes(const char *fn, int32_t U, int32_t N) const {
+    if (U < 1 || N < 1) return fail(FMX_ERR_ARG, "%s: U=%d and N=%d must be >= 1", fn, U, N);
+    if (K < 1) return fail(FMX_ERR_ARG, "%s: K=%d must be >= 1", fn, K);
+    if (K > TK_MAX_K) return fail(FMX_ERR_UNSUPPORTED, "%s: K=%d, the kernels cover K <= %d", fn, K, TK_MAX_K);
+    return FMX_OK;
+  }
+  int check_flag(const char *) const { return FMX_OK; }
+  int64_t part_bytes(int64_t parts, int32_t) const { return parts * K * 8; }
+  int check_ws(const char *fn, int64_t ws_bytes, int64_t need, const char *ws_args, int32_t U, int32_t N) const {
+    if (ws_bytes < need)
+      return fail(FMX_ERR_SHAPE, "%s: workspace of %lld bytes, %s_workspace_bytes(%s%d, %d, %d) = %lld", fn, (long long)ws_bytes, fn,
+                  ws_args, U, N, K, (long long)need);
+    return FMX_OK;
+  }
+};
+
+struct RankEnd {
+  const int32_t *targets;
+  int32_t T, filtered;
+  int32_t *rank_out;
+  float *score_out;
+  int32_t *n_cand_out;
+  int scan_K() const { return 1; }
+  const void *out_a() const { return targets; }
+  const void *out_b() const { return rank_out; }
+  int check_sizes(const char *fn, int32_t U, int32_t N) const {
+    if (U < 1 || N < 1) return fail(FMX_ERR_ARG, "%s: U=%d and N=%d must be >= 1", fn, U, N);
+    if (T < 1) return fail(FMX_ERR_ARG, "%s: T=%d must be >= 1", fn, T);
+    if (T > RK_MAX_T) return fail(FMX_ERR_UNSUPPORTED, "%s: T=%d, one call covers T <= %d targets per user", fn, T, RK_MAX_T);
+    return FMX_OK;
+  }
+  int check_flag(const char *fn) const {
+    if (filtered != 0 && filtered != 1) return fail(FMX_ERR_ARG, "%s: filtered=%d must be 0 or 1", fn, filtered);
+    return FMX_OK;
+  }
+  int64_t part_bytes(int64_t parts, int32_t U) const { return rank_ws_bytes(parts, U, T); }
+  int check_ws(const char *fn, int64_t ws_bytes, int64_t need, const char *, int32_t, int32_t) const {
+    if (ws_bytes < need)
+      return fail(FMX_ERR_SHAPE, "%s: workspace of %lld bytes, %s_workspace_bytes = %lld", fn, (long long)ws_bytes, fn, (long long)need);
+    return FMX_OK;
+  }
+};
+
+// ---- the three families ---------------------------------------------------------------------------------------------------
+struct ScanIn {  // what every family's call is given
+  const char *fn;
+  int32_t U, N, kp;
+  const int32_t *excl_off, *excl_pos;
+  void *ws;
+  int64_t ws_bytes;
+};
+
+// The checks of the FM and network calls on their two sides, in this order.  A kp outside 4/8/16/32/64 returns bad_kp
+// (include/fmx.h: FMX_ERR_SHAPE from the FM calls, FMX_ERR_UNSUPPORTED from the network's).
+template <class Plan, class End>
+int check_pair(const Plan &p, const End &e, int bad_kp, int64_t need, const char *ws_args) {
+  const char *fn = p.fn;
+  if (!p.Su || !p.au || !p.Sc || !p.ac || !p.ws || !e.out_a() || !e.out_b()) return fail(FMX_ERR_ARG, "%s: null argument", fn);
+  if ((p.excl_off == nullptr) != (p.excl_pos == nullptr)) return fail(FMX_ERR_ARG, "%s: excl_offsets and excl_pos go together", fn);
+  if (int rc = e.check_sizes(fn, p.U, p.N)) return rc;
+  if (int rc = e.check_flag(fn)) return rc;
+  if (!lpr_of(p.kp)) return fail(bad_kp, "%s: kp=%d must be 4/8/16/32/64", fn, p.kp);
+  if (p.ld_u < p.kp || p.ld_c < p.kp || p.ld_u % 4 || p.ld_c % 4)
+    return fail(FMX_ERR_SHAPE, "%s: ld_u=%d and ld_c=%d must be multiples of 4 and >= kp=%d", fn, p.ld_u, p.ld_c, p.kp);
+  if (!aligned16(p.Su) || !aligned16(p.Sc) || !aligned16(p.ws))
+    return fail(FMX_ERR_ALIGN, "%s: Su, Sc and the workspace must be 16-byte aligned", fn);
+  return e.check_ws(fn, p.ws_bytes, need, ws_args, p.U, p.N);
 }
 
-int check_network(const fmx_mlp_t *mlp, const char *fn = "fmx_mlp_topk") {
+struct FmScan : ScanIn {
+  using Args = TopkArgs;
+  using RankArgs = FmRankArgs;
+  static constexpr const char *names[3] = {"k_topk_scan", "k_topk_scan (rank count)", "k_topk_scan (rank keys)"};
+  const float *Su;
+  int32_t ld_u;
+  const float *au, *Sc;
+  int32_t ld_c;
+  const float *ac;
+  TopkGeom g{};
+
+  template <class End>
+  static int64_t workspace_bytes(const char *fn, const End &e, int32_t U, int32_t N) {
+    if (int rc = e.check_sizes(fn, U, N)) return rc;
+    return e.part_bytes(fm_scan_parts(U, N), U);
+  }
+  template <class End>
+  int check(const End &e) {
+    return check_pair(*this, e, FMX_ERR_SHAPE, e.part_bytes(fm_scan_parts(U, N), U), "");
+  }
+  int64_t prefix() const { return 0; }
+  int prepare(int K, hipStream_t) {
+    g = topk_geom(U, N, K);
+    return FMX_OK;
+  }
+  Args args(int K) const {
+    return Args{Su, au, Sc, ac, excl_off, excl_pos, nullptr, nullptr, nullptr, ld_u, ld_c, U, N, K, g.ut, g.cap, g.splits, g.per};
+  }
+  int splits() const { return g.splits; }
+  dim3 grid() const { return dim3(g.tiles, g.splits); }
+  template <int MODE, class A>
+  int launch(dim3 grid, A a, hipStream_t st) const {
+    if (MODE == SCAN_KEYS) a.ut = 1;  // grid (U, T): one user per workgroup
+    const size_t lds = MODE == SCAN_TOPK ? slots_lds(g.ut, g.cap) : 0;  // the counters are static LDS
+    return with_kp(kp, [&](auto KP) { return launch_slots<k_topk_scan<KP, MODE, A>>(names[MODE], grid, lds, st, a); });
+  }
+};
+
+int check_network(const char *fn, const fmx_mlp_t *mlp) {
   if (mlp->n_layers < 1 || mlp->n_layers > TM_MAX_L || mlp->hidden < 1 || mlp->hidden > TM_MAX_H || mlp->k < 1 || mlp->k > 64)
     return fail(FMX_ERR_UNSUPPORTED, "%s: needs 1 <= layers <= %d, 1 <= hidden <= %d, 1 <= k <= 64 (got %d, %d, %d)", fn, TM_MAX_L,
                 TM_MAX_H, mlp->n_layers, mlp->hidden, mlp->k);
   return FMX_OK;
 }
 
-// The checks both entry points make, in this order.  A kp outside 4/8/16/32/64 returns bad_kp (include/fmx.h: FMX_ERR_SHAPE
-// from fmx_fm_topk, FMX_ERR_UNSUPPORTED from fmx_mlp_topk).  net: fmx_mlp_topk's checked network, null for fmx_fm_topk.
-// The pointer checks (first) and the layout checks (after the sizes) of the two sides, shared with the rank calls
-// (fmx_rank.inc): out_a / out_b are the call's two required outputs.
-int check_pair_ptrs(const char *fn, const float *Su, const float *au, const float *Sc, const float *ac, const int32_t *excl_off,
-                    const int32_t *excl_pos, const void *ws, const void *out_a, const void *out_b) {
-  if (!Su || !au || !Sc || !ac || !ws || !out_a || !out_b) return fail(FMX_ERR_ARG, "%s: null argument", fn);
-  if ((excl_off == nullptr) != (excl_pos == nullptr)) return fail(FMX_ERR_ARG, "%s: excl_offsets and excl_pos go together", fn);
-  return FMX_OK;
-}
-int check_pair_layout(const char *fn, int bad_kp, const float *Su, int32_t ld_u, const float *Sc, int32_t ld_c, int32_t kp,
-                      const void *ws) {
-  if (!lpr_of(kp)) return fail(bad_kp, "%s: kp=%d must be 4/8/16/32/64", fn, kp);
-  if (ld_u < kp || ld_c < kp || ld_u % 4 || ld_c % 4)
-    return fail(FMX_ERR_SHAPE, "%s: ld_u=%d and ld_c=%d must be multiples of 4 and >= kp=%d", fn, ld_u, ld_c, kp);
-  if (!aligned16(Su) || !aligned16(Sc) || !aligned16(ws))
-    return fail(FMX_ERR_ALIGN, "%s: Su, Sc and the workspace must be 16-byte aligned", fn);
-  return FMX_OK;
+struct MlpScan : ScanIn {
+  using Args = MlpTopkArgs;
+  using RankArgs = MlpRankArgs;
+  static constexpr const char *names[3] = {"k_mlp_topk_scan", "k_mlp_topk_scan (rank count)", "k_mlp_topk_scan (rank keys)"};
+  const fmx_mlp_t *mlp;
+  int32_t fm_term;
+  const float *Su, *Bu;
+  int32_t ld_u;
+  const float *au, *Sc, *Bc;
+  int32_t ld_c;
+  const float *ac;
+  MlpShape sh{};
+  MlpTopkGeom g{};
+  MlpPackArgs pk{};
+
+  template <class End>
+  static int64_t workspace_bytes(const char *fn, const fmx_mlp_t *mlp, const End &e, int32_t U, int32_t N) {
+    if (!mlp) return fail(FMX_ERR_ARG, "%s: null mlp", fn);
+    if (int rc = e.check_sizes(fn, U, N)) return rc;
+    if (int rc = check_network(fn, mlp)) return rc;
+    const MlpShape s = mlp_shape(mlp);
+    return mlp_packed_floats(s, nullptr) * 4 + e.part_bytes(mlp_scan_parts(s, U, N), U);
+  }
+  template <class End>
+  int check(const End &e) {
+    if (!mlp || !mlp->params || !Bu || !Bc) return fail(FMX_ERR_ARG, "%s: null argument", fn);
+    if (fm_term != 0 && fm_term != 1) return fail(FMX_ERR_ARG, "%s: fm_term=%d must be 0 or 1", fn, fm_term);
+    if (int rc = check_network(fn, mlp)) return rc;
+    if (mlp->k > kp) return fail(FMX_ERR_UNSUPPORTED, "%s: k=%d exceeds kp=%d", fn, mlp->k, kp);
+    sh = mlp_shape(mlp);
+    if (int rc = check_pair(*this, e, FMX_ERR_UNSUPPORTED, prefix() + e.part_bytes(mlp_scan_parts(sh, U, N), U), "mlp, ")) return rc;
+    if (!aligned16(Bu) || !aligned16(Bc)) return fail(FMX_ERR_ALIGN, "%s: Bu and Bc must be 16-byte aligned", fn);
+    return FMX_OK;
+  }
+  int64_t prefix() const { return mlp_packed_floats(sh, nullptr) * 4; }  // the packed weights
+  int prepare(int K, hipStream_t st) {
+    g = mlp_topk_geom(sh, U, N, K);
+    pk = MlpPackArgs{mlp->params, static_cast<float *>(ws), {}, {}, {}, {}, 0, sh.k, sh.H, sh.L, sh.K0, sh.Hp, sh.NT};
+    pk.total = mlp_packed_floats(sh, &pk);
+    hipLaunchKernelGGL(k_mlp_topk_pack, dim3((unsigned)((pk.total + 255) / 256)), dim3(256), 0, st, pk);
+    return check_launch("k_mlp_topk_pack");
+  }
+  Args args(int K) const {
+    Args a{Su, Bu, au, Sc, Bc, ac, excl_off, excl_pos, pk.packed, {}, {}, nullptr, nullptr, nullptr,
+           ld_u, ld_c, U, N, K, kp, sh.k, sh.H, sh.L, sh.K0, sh.Hp, fm_term, g.cap, g.splits, g.per};
+    std::copy(pk.dst_w, pk.dst_w + sh.L, a.woff);
+    std::copy(pk.dst_b, pk.dst_b + sh.L, a.boff);
+    return a;
+  }
+  int splits() const { return g.splits; }
+  dim3 grid() const { return dim3(U, g.splits); }
+  template <int MODE, class A>
+  int launch(dim3 grid, const A &a, hipStream_t st) const {
+    // the activations, and the selection's slot behind them; the counters are static LDS
+    const size_t lds = (size_t)TM_ROWS * std::max(sh.K0, sh.Hp) * 4 + (MODE == SCAN_TOPK ? slots_lds(1, g.cap) : 0);
+    return with_wave_grid(sh.NT, [&](auto WC, auto NCT) {
+      return launch_slots<k_mlp_topk_scan<WC, NCT, MODE, A>>(names[MODE], grid, lds, st, a);
+    });
+  }
+};
+
+struct AfmScan : ScanIn {
+  using Args = AfmTopkArgs;
+  using RankArgs = AfmRankArgs;
+  static constexpr const char *names[3] = {"k_afm_topk_scan", "k_afm_topk_scan (rank count)", "k_afm_topk_scan (rank keys)"};
+  const fmx_afm_t *afm;
+  const float *Eu, *stats_u;
+  int32_t n_ctx;
+  const float *Ec, *stats_c;
+  int32_t n_item;
+  int per = 0, n_splits = 0, cap = 0;
+
+  static int check_shape(const char *fn, const fmx_afm_t *afm, int32_t n_ctx, int32_t n_item) {
+    if (afm->t < 1 || afm->t > 64 || afm->k < 1 || afm->k > 64)
+      return fail(FMX_ERR_UNSUPPORTED, "%s: needs 1 <= t <= 64 and 1 <= k <= 64 (got t=%d, k=%d)", fn, afm->t, afm->k);
+    if (n_ctx < 1 || n_item < 1) return fail(FMX_ERR_SHAPE, "%s: n_ctx=%d and n_item=%d must be >= 1", fn, n_ctx, n_item);
+    if (n_ctx + n_item > 64) return fail(FMX_ERR_UNSUPPORTED, "%s: n_ctx + n_item = %d, the AFM takes at most 64 fields", fn, n_ctx + n_item);
+    return FMX_OK;
+  }
+  template <class End>
+  static int64_t workspace_bytes(const char *fn, const fmx_afm_t *afm, int32_t n_ctx, int32_t n_item, const End &e, int32_t U, int32_t N) {
+    if (!afm) return fail(FMX_ERR_ARG, "%s: null afm", fn);
+    if (int rc = e.check_sizes(fn, U, N)) return rc;
+    if (int rc = check_shape(fn, afm, n_ctx, n_item)) return rc;
+    return at_packed_bytes(afm->t) + e.part_bytes(afm_scan_parts(afm, n_ctx, n_item, U, N), U);
+  }
+  template <class End>
+  int check(const End &e) {
+    const int64_t need = workspace_bytes(fn, afm, n_ctx, n_item, e, U, N);  // the shape checks come first
+    if (need < 0) return (int)need;
+    if (!afm->params || !Eu || !stats_u || !Ec || !stats_c || !ws || !e.out_a() || !e.out_b()) return fail(FMX_ERR_ARG, "%s: null argument", fn);
+    if ((excl_off == nullptr) != (excl_pos == nullptr)) return fail(FMX_ERR_ARG, "%s: excl_offsets and excl_pos go together", fn);
+    if (!lpr_of(kp) || kp < afm->k) return fail(FMX_ERR_SHAPE, "%s: kp=%d must be 4/8/16/32/64 and >= k=%d", fn, kp, afm->k);
+    if (!aligned16(Eu) || !aligned16(stats_u) || !aligned16(Ec) || !aligned16(stats_c) || !aligned16(ws))
+      return fail(FMX_ERR_ALIGN, "%s: Eu, stats_u, Ec, stats_c and the workspace must be 16-byte aligned", fn);
+    if (int rc = e.check_flag(fn)) return rc;
+    char ws_args[48];
+    snprintf(ws_args, sizeof ws_args, "afm, %d, %d, ", n_ctx, n_item);
+    return e.check_ws(fn, ws_bytes, need, ws_args, U, N);
+  }
+  int64_t prefix() const { return at_packed_bytes(afm->t); }  // the padded parameter copy
+  // one user per workgroup, splits = ceil(budget / U) within [1, max splits], a split a multiple of the chunk
+  int prepare(int K, hipStream_t st) {
+    const int64_t sm = at_split_min(n_ctx, n_item, afm->t, at_kp(afm->k));
+    const int64_t sp = std::max<int64_t>(1, std::min<int64_t>(at_max_splits(sm, N), (AT_TILE_BUDGET + U - 1) / U));
+    const int64_t per0 = (N + sp - 1) / sp;
+    per = (int)((per0 + TK_THREADS - 1) / TK_THREADS * TK_THREADS);
+    n_splits = (N + per - 1) / per;
+    cap = topk_cap(K);
+    const int packed_n = afm->t * kp + 2 * afm->t + kp;
+    hipLaunchKernelGGL(k_afm_topk_pack, dim3((packed_n + 255) / 256), dim3(256), 0, st, afm->params, afm->k, afm->t, kp,
+                       static_cast<float *>(ws));
+    return check_launch("k_afm_topk_pack");
+  }
+  Args args(int K) const {
+    return Args{Eu, stats_u, Ec, stats_c, static_cast<const float *>(ws), excl_off, excl_pos, nullptr, nullptr, nullptr,
+                U, N, K, afm->t, n_ctx, n_item, cap, n_splits, per};
+  }
+  int splits() const { return n_splits; }
+  dim3 grid() const { return dim3(U, n_splits); }
+  template <int MODE, class A>
+  int launch(dim3 grid, const A &a, hipStream_t st) const {
+    const size_t lds = MODE == SCAN_TOPK ? slots_lds(1, cap) : 0;
+    return with_kp(kp, [&](auto KP) { return launch_slots<k_afm_topk_scan<KP, MODE, A>>(names[MODE], grid, lds, st, a); });
+  }
+};
+
+// ---- the two drivers ------------------------------------------------------------------------------------------------------
+// the scan into partial lists behind the family's prefix (or, with one split, into the final rows), then the merge
+template <class Plan>
+int scan_topk(Plan p, const TopkEnd &e, fmx_stream_t stream) {
+  if (int rc = p.check(e)) return rc;
+  const hipStream_t st = static_cast<hipStream_t>(stream);
+  if (int rc = p.prepare(e.K, st)) return rc;
+  typename Plan::Args a = p.args(e.K);
+  a.parts = reinterpret_cast<uint64_t *>(static_cast<char *>(p.ws) + p.prefix());
+  a.top_pos = e.top_pos;
+  a.top_score = e.top_score;
+  if (int rc = p.template launch<SCAN_TOPK>(p.grid(), a, st)) return rc;
+  return merge_topk(a.parts, e.top_pos, e.top_score, p.U, e.K, p.splits(), st);
 }
 
-int check_topk_args(const char *fn, int bad_kp, const MlpShape *net, const float *Su, int32_t ld_u, const float *au, int32_t U,
-                    const float *Sc, int32_t ld_c, const float *ac, int32_t N, int32_t kp, const int32_t *excl_off,
-                    const int32_t *excl_pos, int32_t K, const void *ws, int64_t ws_bytes, const int32_t *top_pos,
-                    const float *top_score) {
-  if (int rc = check_pair_ptrs(fn, Su, au, Sc, ac, excl_off, excl_pos, ws, top_pos, top_score)) return rc;
-  if (int rc = check_topk_sizes(fn, U, N, K)) return rc;
-  if (int rc = check_pair_layout(fn, bad_kp, Su, ld_u, Sc, ld_c, kp, ws)) return rc;
-  const int64_t need = net ? mlp_topk_ws_bytes(*net, U, N, K) : topk_ws_bytes(U, N, K);
-  if (ws_bytes < need)
-    return fail(FMX_ERR_SHAPE, "%s: workspace of %lld bytes, %s_workspace_bytes(%s%d, %d, %d) = %lld", fn, (long long)ws_bytes, fn,
-                net ? "mlp, " : "", U, N, K, (long long)need);
-  return FMX_OK;
+// the targets' keys on grid (U, T), the counting scan on the family's grid, then the finishing launch; the keys and the partial
+// counts lie behind the family's prefix
+template <class Plan>
+int scan_rank(Plan p, const RankEnd &e, fmx_stream_t stream) {
+  if (int rc = p.check(e)) return rc;
+  const hipStream_t st = static_cast<hipStream_t>(stream);
+  if (int rc = p.prepare(1, st)) return rc;
+  char *base = static_cast<char *>(p.ws) + p.prefix();
+  const typename Plan::RankArgs a{p.args(1), RankIo{e.targets, reinterpret_cast<uint64_t *>(base),
+                                                    reinterpret_cast<int32_t *>(base + rank_keys_bytes(p.U, e.T)), e.T}};
+  if (int rc = p.template launch<SCAN_KEYS>(dim3(p.U, e.T), a, st)) return rc;
+  if (int rc = p.template launch<SCAN_COUNT>(p.grid(), a, st)) return rc;
+  return finish_rank(a.r, p.excl_off, p.excl_pos, p.U, p.N, p.splits(), e.filtered, e.rank_out, e.score_out, e.n_cand_out, st);
 }
 
 }  // namespace
@@ -815,162 +1010,72 @@ int check_topk_args(const char *fn, int bad_kp, const MlpShape *net, const float
 extern "C" {
 
 int64_t fmx_fm_topk_workspace_bytes(int32_t U, int32_t N, int32_t K) {
-  if (int rc = check_topk_sizes("fmx_fm_topk", U, N, K)) return rc;
-  return topk_ws_bytes(U, N, K);
+  return FmScan::workspace_bytes("fmx_fm_topk", TopkEnd{K, nullptr, nullptr}, U, N);
 }
-
+int64_t fmx_fm_rank_workspace_bytes(int32_t U, int32_t N, int32_t T) {
+  return FmScan::workspace_bytes("fmx_fm_rank", RankEnd{nullptr, T, 0, nullptr, nullptr, nullptr}, U, N);
+}
 int64_t fmx_mlp_topk_workspace_bytes(const fmx_mlp_t *mlp, int32_t U, int32_t N, int32_t K) {
-  if (!mlp) return fail(FMX_ERR_ARG, "fmx_mlp_topk: null mlp");
-  if (int rc = check_topk_sizes("fmx_mlp_topk", U, N, K)) return rc;
-  if (int rc = check_network(mlp)) return rc;
-  return mlp_topk_ws_bytes(mlp_shape(mlp), U, N, K);
+  return MlpScan::workspace_bytes("fmx_mlp_topk", mlp, TopkEnd{K, nullptr, nullptr}, U, N);
+}
+int64_t fmx_mlp_rank_workspace_bytes(const fmx_mlp_t *mlp, int32_t U, int32_t N, int32_t T) {
+  return MlpScan::workspace_bytes("fmx_mlp_rank", mlp, RankEnd{nullptr, T, 0, nullptr, nullptr, nullptr}, U, N);
+}
+int64_t fmx_afm_topk_workspace_bytes(const fmx_afm_t *afm, int32_t n_ctx, int32_t n_item, int32_t U, int32_t N, int32_t K) {
+  return AfmScan::workspace_bytes("fmx_afm_topk", afm, n_ctx, n_item, TopkEnd{K, nullptr, nullptr}, U, N);
+}
+int64_t fmx_afm_rank_workspace_bytes(const fmx_afm_t *afm, int32_t n_ctx, int32_t n_item, int32_t U, int32_t N, int32_t T) {
+  return AfmScan::workspace_bytes("fmx_afm_rank", afm, n_ctx, n_item, RankEnd{nullptr, T, 0, nullptr, nullptr, nullptr}, U, N);
 }
 
 int fmx_fm_topk(const float *Su, int32_t ld_u, const float *au, int32_t U, const float *Sc, int32_t ld_c, const float *ac, int32_t N,
                 int32_t kp, const int32_t *excl_offsets, const int32_t *excl_pos, int32_t K, void *workspace, int64_t workspace_bytes,
                 int32_t *top_pos, float *top_score, fmx_stream_t stream) {
-  if (int rc = check_topk_args("fmx_fm_topk", FMX_ERR_SHAPE, nullptr, Su, ld_u, au, U, Sc, ld_c, ac, N, kp, excl_offsets, excl_pos, K,
-                               workspace, workspace_bytes, top_pos, top_score))
-    return rc;
-  const TopkGeom g = topk_geom(U, N, K);
-  const TopkArgs a{Su, au, Sc, ac,
-                   excl_offsets, excl_pos,
-                   static_cast<uint64_t *>(workspace),
-                   top_pos, top_score,
-                   ld_u, ld_c, U, N, K, g.ut, g.cap, g.splits, g.per};
-  const hipStream_t st = static_cast<hipStream_t>(stream);
-  const dim3 grid(g.tiles, g.splits);
-  const size_t lds = slots_lds(g.ut, g.cap);
-  const int rc = with_kp(kp, [&](auto KP) { return launch_slots<k_topk_scan<KP>>("k_topk_scan", grid, lds, st, a); });
-  return rc ? rc : merge_topk(a.parts, top_pos, top_score, U, K, g.splits, st);
+  return scan_topk(FmScan{{"fmx_fm_topk", U, N, kp, excl_offsets, excl_pos, workspace, workspace_bytes}, Su, ld_u, au, Sc, ld_c, ac},
+                   TopkEnd{K, top_pos, top_score}, stream);
+}
+
+int fmx_fm_rank(const float *Su, int32_t ld_u, const float *au, int32_t U, const float *Sc, int32_t ld_c, const float *ac, int32_t N,
+                int32_t kp, const int32_t *excl_offsets, const int32_t *excl_pos, const int32_t *targets, int32_t T, int32_t filtered,
+                void *workspace, int64_t workspace_bytes, int32_t *rank_out, float *score_out, int32_t *n_cand_out,
+                fmx_stream_t stream) {
+  return scan_rank(FmScan{{"fmx_fm_rank", U, N, kp, excl_offsets, excl_pos, workspace, workspace_bytes}, Su, ld_u, au, Sc, ld_c, ac},
+                   RankEnd{targets, T, filtered, rank_out, score_out, n_cand_out}, stream);
 }
 
 int fmx_mlp_topk(const fmx_mlp_t *mlp, int32_t fm_term, const float *Su, const float *Bu, int32_t ld_u, const float *au, int32_t U,
                  const float *Sc, const float *Bc, int32_t ld_c, const float *ac, int32_t N, int32_t kp, const int32_t *excl_offsets,
                  const int32_t *excl_pos, int32_t K, void *workspace, int64_t workspace_bytes, int32_t *top_pos, float *top_score,
                  fmx_stream_t stream) {
-  if (!mlp || !mlp->params || !Bu || !Bc) return fail(FMX_ERR_ARG, "fmx_mlp_topk: null argument");
-  if (fm_term != 0 && fm_term != 1) return fail(FMX_ERR_ARG, "fmx_mlp_topk: fm_term=%d must be 0 or 1", fm_term);
-  if (int rc = check_network(mlp)) return rc;
-  if (mlp->k > kp) return fail(FMX_ERR_UNSUPPORTED, "fmx_mlp_topk: k=%d exceeds kp=%d", mlp->k, kp);
-  const MlpShape sh = mlp_shape(mlp);
-  if (int rc = check_topk_args("fmx_mlp_topk", FMX_ERR_UNSUPPORTED, &sh, Su, ld_u, au, U, Sc, ld_c, ac, N, kp, excl_offsets, excl_pos,
-                               K, workspace, workspace_bytes, top_pos, top_score))
-    return rc;
-  if (!aligned16(Bu) || !aligned16(Bc)) return fail(FMX_ERR_ALIGN, "fmx_mlp_topk: Bu and Bc must be 16-byte aligned");
-  const MlpTopkGeom g = mlp_topk_geom(sh, U, N, K);
-  MlpPackArgs p{mlp->params, static_cast<float *>(workspace), {}, {}, {}, {}, 0, sh.k, sh.H, sh.L, sh.K0, sh.Hp, sh.NT};
-  p.total = mlp_packed_floats(sh, &p);
-  MlpTopkArgs a{Su, Bu, au, Sc, Bc, ac,
-                excl_offsets, excl_pos,
-                p.packed,
-                {}, {},
-                reinterpret_cast<uint64_t *>(p.packed + p.total),
-                top_pos, top_score,
-                ld_u, ld_c, U, N, K, kp, sh.k, sh.H, sh.L, sh.K0, sh.Hp, fm_term, g.cap, g.splits, g.per};
-  std::copy(p.dst_w, p.dst_w + sh.L, a.woff);
-  std::copy(p.dst_b, p.dst_b + sh.L, a.boff);
-  const hipStream_t st = static_cast<hipStream_t>(stream);
-  hipLaunchKernelGGL(k_mlp_topk_pack, dim3((unsigned)((p.total + 255) / 256)), dim3(256), 0, st, p);
-  if (int rc = check_launch("k_mlp_topk_pack")) return rc;
-  const dim3 grid(U, g.splits);
-  const size_t lds = mlp_topk_lds(sh, g.cap);
-  int rc;
-  switch (sh.NT) {
-    case 1: rc = launch_slots<k_mlp_topk_scan<1, 1>>("k_mlp_topk_scan", grid, lds, st, a); break;
-    case 2: rc = launch_slots<k_mlp_topk_scan<2, 1>>("k_mlp_topk_scan", grid, lds, st, a); break;
-    case 3: rc = launch_slots<k_mlp_topk_scan<2, 2>>("k_mlp_topk_scan", grid, lds, st, a); break;
-    case 4: rc = launch_slots<k_mlp_topk_scan<4, 1>>("k_mlp_topk_scan", grid, lds, st, a); break;
-    case 5: case 6: case 7: case 8: rc = launch_slots<k_mlp_topk_scan<4, 2>>("k_mlp_topk_scan", grid, lds, st, a); break;
-    case 9: case 10: case 11: case 12: rc = launch_slots<k_mlp_topk_scan<4, 3>>("k_mlp_topk_scan", grid, lds, st, a); break;
-    default: rc = launch_slots<k_mlp_topk_scan<4, 4>>("k_mlp_topk_scan", grid, lds, st, a); break;
-  }
-  return rc ? rc : merge_topk(a.parts, top_pos, top_score, U, K, g.splits, st);
+  return scan_topk(MlpScan{{"fmx_mlp_topk", U, N, kp, excl_offsets, excl_pos, workspace, workspace_bytes},
+                           mlp, fm_term, Su, Bu, ld_u, au, Sc, Bc, ld_c, ac},
+                   TopkEnd{K, top_pos, top_score}, stream);
 }
 
-}  // extern "C"
-
-namespace {
-
-// what fmx_afm_topk and the AFM rank call (fmx_rank.inc) check alike, around their own size checks
-int check_afm_pair_shape(const char *fn, const fmx_afm_t *afm, int32_t n_ctx, int32_t n_item) {
-  if (afm->t < 1 || afm->t > 64 || afm->k < 1 || afm->k > 64)
-    return fail(FMX_ERR_UNSUPPORTED, "%s: needs 1 <= t <= 64 and 1 <= k <= 64 (got t=%d, k=%d)", fn, afm->t, afm->k);
-  if (n_ctx < 1 || n_item < 1) return fail(FMX_ERR_SHAPE, "%s: n_ctx=%d and n_item=%d must be >= 1", fn, n_ctx, n_item);
-  if (n_ctx + n_item > 64) return fail(FMX_ERR_UNSUPPORTED, "%s: n_ctx + n_item = %d, the AFM takes at most 64 fields", fn, n_ctx + n_item);
-  return FMX_OK;
-}
-int check_afm_pair_args(const char *fn, const fmx_afm_t *afm, const float *Eu, const float *stats_u, const float *Ec,
-                        const float *stats_c, int32_t kp, const int32_t *excl_offsets, const int32_t *excl_pos, const void *workspace,
-                        const void *out_a, const void *out_b) {
-  if (!afm->params || !Eu || !stats_u || !Ec || !stats_c || !workspace || !out_a || !out_b) return fail(FMX_ERR_ARG, "%s: null argument", fn);
-  if ((excl_offsets == nullptr) != (excl_pos == nullptr)) return fail(FMX_ERR_ARG, "%s: excl_offsets and excl_pos go together", fn);
-  if (!lpr_of(kp) || kp < afm->k)
-    return fail(FMX_ERR_SHAPE, "%s: kp=%d must be 4/8/16/32/64 and >= k=%d", fn, kp, afm->k);
-  if (!aligned16(Eu) || !aligned16(stats_u) || !aligned16(Ec) || !aligned16(stats_c) || !aligned16(workspace))
-    return fail(FMX_ERR_ALIGN, "%s: Eu, stats_u, Ec, stats_c and the workspace must be 16-byte aligned", fn);
-  return FMX_OK;
-}
-
-int check_afm_topk_shape(const fmx_afm_t *afm, int32_t n_ctx, int32_t n_item, int32_t U, int32_t N, int32_t K) {
-  if (!afm) return fail(FMX_ERR_ARG, "fmx_afm_topk: null afm");
-  if (int rc = check_topk_sizes("fmx_afm_topk", U, N, K)) return rc;
-  return check_afm_pair_shape("fmx_afm_topk", afm, n_ctx, n_item);
-}
-
-// geometry of the AFM scans: one user per workgroup, splits = ceil(budget / U) within [1, max splits], a split a multiple of
-// the chunk
-struct AfmGeom {
-  int per, splits;
-};
-inline AfmGeom afm_scan_geom(const fmx_afm_t *afm, int n_ctx, int n_item, int U, int N) {
-  const int64_t sm = at_split_min(n_ctx, n_item, afm->t, at_kp(afm->k));
-  const int64_t sp = std::max<int64_t>(1, std::min<int64_t>(at_max_splits(sm, N), (AT_TILE_BUDGET + U - 1) / U));
-  const int64_t per0 = (N + sp - 1) / sp;
-  AfmGeom g;
-  g.per = (int)((per0 + TK_THREADS - 1) / TK_THREADS * TK_THREADS);
-  g.splits = (N + g.per - 1) / g.per;
-  return g;
-}
-
-}  // namespace
-
-extern "C" {
-
-int64_t fmx_afm_topk_workspace_bytes(const fmx_afm_t *afm, int32_t n_ctx, int32_t n_item, int32_t U, int32_t N, int32_t K) {
-  if (int rc = check_afm_topk_shape(afm, n_ctx, n_item, U, N, K)) return rc;
-  return afm_topk_ws_bytes(afm, n_ctx, n_item, U, N, K);
+int fmx_mlp_rank(const fmx_mlp_t *mlp, int32_t fm_term, const float *Su, const float *Bu, int32_t ld_u, const float *au, int32_t U,
+                 const float *Sc, const float *Bc, int32_t ld_c, const float *ac, int32_t N, int32_t kp, const int32_t *excl_offsets,
+                 const int32_t *excl_pos, const int32_t *targets, int32_t T, int32_t filtered, void *workspace, int64_t workspace_bytes,
+                 int32_t *rank_out, float *score_out, int32_t *n_cand_out, fmx_stream_t stream) {
+  return scan_rank(MlpScan{{"fmx_mlp_rank", U, N, kp, excl_offsets, excl_pos, workspace, workspace_bytes},
+                           mlp, fm_term, Su, Bu, ld_u, au, Sc, Bc, ld_c, ac},
+                   RankEnd{targets, T, filtered, rank_out, score_out, n_cand_out}, stream);
 }
 
 int fmx_afm_topk(const fmx_afm_t *afm, const float *Eu, const float *stats_u, int32_t n_ctx, int32_t U, const float *Ec,
                  const float *stats_c, int32_t n_item, int32_t N, int32_t kp, const int32_t *excl_offsets, const int32_t *excl_pos,
                  int32_t K, void *workspace, int64_t workspace_bytes, int32_t *top_pos, float *top_score, fmx_stream_t stream) {
-  if (int rc = check_afm_topk_shape(afm, n_ctx, n_item, U, N, K)) return rc;
-  if (int rc = check_afm_pair_args("fmx_afm_topk", afm, Eu, stats_u, Ec, stats_c, kp, excl_offsets, excl_pos, workspace, top_pos, top_score))
-    return rc;
-  const int64_t need = afm_topk_ws_bytes(afm, n_ctx, n_item, U, N, K);
-  if (workspace_bytes < need)
-    return fail(FMX_ERR_SHAPE, "fmx_afm_topk: workspace of %lld bytes, fmx_afm_topk_workspace_bytes(afm, %d, %d, %d, %d, %d) = %lld",
-                (long long)workspace_bytes, n_ctx, n_item, U, N, K, (long long)need);
-  const AfmGeom g = afm_scan_geom(afm, n_ctx, n_item, U, N);
-  const int per = g.per, splits = g.splits;
-  AfmTopkArgs a{Eu, stats_u, Ec, stats_c,
-                static_cast<const float *>(workspace),
-                excl_offsets, excl_pos,
-                reinterpret_cast<uint64_t *>(static_cast<char *>(workspace) + at_packed_bytes(afm->t)),
-                top_pos, top_score,
-                U, N, K, afm->t, n_ctx, n_item, topk_cap(K), splits, per};
-  const hipStream_t st = static_cast<hipStream_t>(stream);
-  const int packed_n = afm->t * kp + 2 * afm->t + kp;
-  hipLaunchKernelGGL(k_afm_topk_pack, dim3((packed_n + 255) / 256), dim3(256), 0, st, afm->params, afm->k, afm->t, kp,
-                     static_cast<float *>(workspace));
-  if (int rc = check_launch("k_afm_topk_pack")) return rc;
-  const dim3 grid(U, splits);
-  const size_t lds = slots_lds(1, a.cap);
-  const int rc = with_kp(kp, [&](auto KP) { return launch_slots<k_afm_topk_scan<KP>>("k_afm_topk_scan", grid, lds, st, a); });
-  return rc ? rc : merge_topk(a.parts, top_pos, top_score, U, K, splits, st);
+  return scan_topk(AfmScan{{"fmx_afm_topk", U, N, kp, excl_offsets, excl_pos, workspace, workspace_bytes},
+                           afm, Eu, stats_u, n_ctx, Ec, stats_c, n_item},
+                   TopkEnd{K, top_pos, top_score}, stream);
+}
+
+int fmx_afm_rank(const fmx_afm_t *afm, const float *Eu, const float *stats_u, int32_t n_ctx, int32_t U, const float *Ec,
+                 const float *stats_c, int32_t n_item, int32_t N, int32_t kp, const int32_t *excl_offsets, const int32_t *excl_pos,
+                 const int32_t *targets, int32_t T, int32_t filtered, void *workspace, int64_t workspace_bytes, int32_t *rank_out,
+                 float *score_out, int32_t *n_cand_out, fmx_stream_t stream) {
+  return scan_rank(AfmScan{{"fmx_afm_rank", U, N, kp, excl_offsets, excl_pos, workspace, workspace_bytes},
+                           afm, Eu, stats_u, n_ctx, Ec, stats_c, n_item},
+                   RankEnd{targets, T, filtered, rank_out, score_out, n_cand_out}, stream);
 }
 
 }  // extern "C"
-
-#include "fmx_rank_host.inc"

@@ -353,7 +353,7 @@ def mine_negatives(table, cand, ctx_idx, ctx_xv, own_pos, n_draw, n_neg=1, seed=
     (side_sums over the non-item fields) and one mining launch.  Returns device tensors (neg_pos int32 [B, n_neg], -1 padded;
     neg_score fp32 [B, n_neg], -inf padded), each row by score descending, then position ascending."""
     from . import recommend
-    (Su, au), off, pos = recommend._context_side(table, cand, ctx_idx, ctx_xv, exclude, hyper, recommend.side_sums)
+    (Su, au), off, pos = recommend._context_side(recommend.FMScorer(), table, cand, ctx_idx, ctx_xv, exclude, hyper)
     if own_pos is not None:
         own_pos = torch.as_tensor(own_pos).to(device=table.device, dtype=torch.int32).reshape(-1).contiguous()
     return fm_mine_negatives(Su, au, cand.Sc, cand.ac, n_draw, n_neg, own_pos, seed, offset, u_base, off, pos)

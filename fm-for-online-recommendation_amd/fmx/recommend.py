@@ -259,41 +259,6 @@ def _call_buffers(need, U, K, dev, workspace, out, stream):
     return workspace.data_ptr(), workspace.numel() * workspace.element_size(), out, st
 
 
-def fm_topk(Su, au, Sc, ac, K, excl_offsets=None, excl_pos=None, workspace=None, out=None, stream=None, kp=None):
-    """The raw call: Su [U, >= kp], au [U], Sc [N, >= kp], ac [N] fp32 device tensors (row strides multiples of 4, 16-byte
-    aligned); kp defaults to Sc's width.  Returns (top_pos int32 [U, K], top_score fp32 [U, K]) on the device."""
-    U, N = Su.shape[0], Sc.shape[0]
-    kp = Sc.shape[1] if kp is None else int(kp)
-    lib = _lib.load()
-    ws, ws_n, out, st = _call_buffers(lib.fmx_fm_topk_workspace_bytes(U, N, K), U, K, Su.device, workspace, out, stream)
-    _lib.check(lib.fmx_fm_topk(Su.data_ptr(), Su.stride(0), au.data_ptr(), U, Sc.data_ptr(), Sc.stride(0), ac.data_ptr(), N, kp,
-                               _ptr(excl_offsets), _ptr(excl_pos), K, ws, ws_n, out[0].data_ptr(), out[1].data_ptr(), st))
-    return out
-
-
-def _context_side(table, candidates, ctx_idx, ctx_xv, exclude, hyper, side, fm_term=None):
-    """What topk and topk_network share before the selection: the candidates' check (fm_term: the network's, None for the
-    FM), side(table, ctx_idx, ctx_xv, context fields, hyper) over the fields that are not item fields, whose first result
-    has a row per context, and the exclusions.  Returns (side's results, exclusion offsets, exclusion positions)."""
-    if candidates.table is not table:
-        raise ValueError("candidates were computed for another table")
-    if fm_term is not None and (not isinstance(candidates, NetworkCandidates) or candidates.fm_term != int(fm_term)):
-        raise ValueError(f"candidates: a NetworkCandidates with fm_term={int(fm_term)}")
-    ctx_fields = [f for f in range(table.n_fields) if f not in candidates.item_fields]
-    sides = side(table, ctx_idx, ctx_xv, ctx_fields, hyper if hyper is not None else candidates.hyper)
-    off, pos = exclusions_csr(exclude, sides[0].shape[0], table.device)
-    return sides, off, pos
-
-
-def topk(table, ctx_idx, ctx_xv, candidates, K, exclude=None, hyper=None):
-    """Top-K candidates for every context row of ctx_idx / ctx_xv ([U, F] full width, the item columns ignored).  Returns
-    device tensors (positions int64 [U, K], -1 padded; logits fp32 [U, K], -inf padded), each row by logit descending, then
-    position ascending.  exclude: see exclusions_csr."""
-    (Su, au), off, pos = _context_side(table, candidates, ctx_idx, ctx_xv, exclude, hyper, side_sums)
-    top_pos, top_score = fm_topk(Su, au, candidates.Sc, candidates.ac, int(K), off, pos)
-    return top_pos.long(), top_score
-
-
 MLP_TOPK_MAX_HIDDEN = 256    # fmx_mlp_topk's limits (include/fmx.h); larger networks take mlp_topk_torch
 MLP_TOPK_MAX_LAYERS = 8
 MLP_TOPK_MAX_K = 256         # for every network
@@ -306,101 +271,10 @@ def _mlp_struct(mlp):
     return mlp_struct(params, k, hidden, n_layers)
 
 
-def mlp_topk(mlp, fm_term, Su, Bu, au, Sc, Bc, ac, K, excl_offsets=None, excl_pos=None, workspace=None, out=None, stream=None,
-             kp=None):
-    """The raw call of fmx_mlp_topk.  mlp = (params, k, hidden, n_layers) with params the flat fp32 device buffer; Su / Bu
-    [U, >= kp] share a row stride, Sc / Bc [N, >= kp] too (multiples of 4, 16-byte aligned); kp defaults to Sc's width.
-    Returns (top_pos int32 [U, K], top_score fp32 [U, K]) on the device."""
-    U, N = Su.shape[0], Sc.shape[0]
-    kp = Sc.shape[1] if kp is None else int(kp)
-    if Bu.stride(0) != Su.stride(0) or Bc.stride(0) != Sc.stride(0):
-        raise ValueError("Bu / Bc must share the row strides of Su / Sc")
-    lib, m = _lib.load(), _mlp_struct(mlp)
-    ws, ws_n, out, st = _call_buffers(lib.fmx_mlp_topk_workspace_bytes(C.byref(m), U, N, K), U, K, Su.device, workspace, out,
-                                      stream)
-    _lib.check(lib.fmx_mlp_topk(C.byref(m), int(fm_term), Su.data_ptr(), Bu.data_ptr(), Su.stride(0), au.data_ptr(), U,
-                                Sc.data_ptr(), Bc.data_ptr(), Sc.stride(0), ac.data_ptr(), N, kp, _ptr(excl_offsets),
-                                _ptr(excl_pos), K, ws, ws_n, out[0].data_ptr(), out[1].data_ptr(), st))
-    return out
-
-
-def mlp_topk_torch(mlp, fm_term, Su, Bu, au, Sc, Bc, ac, K, excl_offsets=None, excl_pos=None, kp=None, max_elems=1 << 25):
-    """The same score (up to fp32 summation order) and the same result order as fmx_mlp_topk, as chunked torch: for a block
-    of users, every candidate's network output, then a stable sort on (score descending, position ascending); NaN and
-    excluded candidates are never returned, rows are padded with -1 / -inf, -0 is returned as +0.  The path of networks the
-    kernel does not take, and the baseline of tools/mlp_topk_times.py."""
-    params, k, H, L = mlp
-    U, N, dev = Su.shape[0], Sc.shape[0], Su.device
-    kp = Sc.shape[1] if kp is None else int(kp)
-    Ws, off = [], 0
-    for l in range(L):
-        n_in = k if l == 0 else H
-        W = params[off:off + H * n_in].view(H, n_in)
-        b = params[off + H * n_in:off + H * n_in + H]
-        Ws.append((W, b))
-        off += H * n_in + H
-    top_pos = torch.full((U, K), -1, dtype=torch.int32, device=dev)
-    top_score = torch.full((U, K), float("-inf"), dtype=torch.float32, device=dev)
-    Sck, Bck = Sc[:, :k], Bc[:, :k]
-    ub = max(1, min(U, max_elems // max(1, N * max(H, k))))
-    cb = max(1, min(N, max_elems // max(1, ub * max(H, k))))
-    with torch.no_grad():
-        for u0 in range(0, U, ub):
-            u1 = min(U, u0 + ub)
-            score = torch.empty((u1 - u0, N), dtype=torch.float32, device=dev)
-            for c0 in range(0, N, cb):
-                c1 = min(N, c0 + cb)
-                x = (Bu[u0:u1, None, :k] + Bck[None, c0:c1]) + Su[u0:u1, None, :k] * Sck[None, c0:c1]
-                for W, b in Ws:
-                    x = torch.relu(torch.nn.functional.linear(x, W, b))
-                base = au[u0:u1, None] + ac[None, c0:c1]
-                if fm_term:
-                    base = base + Su[u0:u1, :kp] @ Sc[c0:c1, :kp].T
-                score[:, c0:c1] = base + x.sum(-1)
-            score = score + 0.0                              # -0 -> +0
-            ok = ~torch.isnan(score)
-            if excl_offsets is not None:
-                offs = excl_offsets.long().cpu()
-                for u in range(u0, u1):
-                    p = excl_pos[int(offs[u]):int(offs[u + 1])].long()
-                    p = p[p < N]
-                    ok[u - u0, p] = False
-            score = torch.where(ok, score, torch.full_like(score, float("-inf")))
-            s1, i1 = torch.sort(score, dim=1, descending=True, stable=True)
-            ok1 = torch.gather(ok, 1, i1)
-            _, i2 = torch.sort(ok1.to(torch.int8), dim=1, descending=True, stable=True)
-            idx = torch.gather(i1, 1, i2)[:, :K]
-            sc = torch.gather(s1, 1, i2)[:, :K]
-            valid = torch.gather(ok1, 1, i2)[:, :K]
-            n = idx.shape[1]
-            top_pos[u0:u1, :n] = torch.where(valid, idx, torch.full_like(idx, -1)).to(torch.int32)
-            top_score[u0:u1, :n] = torch.where(valid, sc, torch.full_like(sc, float("-inf")))
-    return top_pos, top_score
-
-
 def mlp_kernel_takes(mlp):
     """Does fmx_mlp_topk take this network?  (Else the chunked torch path; K > 256 is refused either way.)"""
     _, k, H, L = mlp
     return 1 <= H <= MLP_TOPK_MAX_HIDDEN and 1 <= L <= MLP_TOPK_MAX_LAYERS and 1 <= k <= 64
-
-
-def topk_network(table, mlp, fm_term, ctx_idx, ctx_xv, candidates, K, exclude=None, hyper=None):
-    """Top-K candidates for every context row under the DeepFM (fm_term = 1) / NFM (fm_term = 0) network mlp = (params,
-    k, hidden, n_layers): the logit of the combined sample for the Adam classes, the logit whose sigmoid forward() returns
-    for the ONN classes.  candidates: a NetworkCandidates of the same table and fm_term.  Returns device tensors (positions
-    int64 [U, K], -1 padded; scores fp32 [U, K], -inf padded), each row by score descending, then position ascending."""
-    def side(table, idx, xv, fields, hyper):
-        S, bi, sfirst, sbi, logit = side_terms(table, idx, xv, fields, hyper)
-        return S, bi, network_bases(table, sfirst, sbi, logit, fm_term, context=True).contiguous()
-
-    (S, bi, au), off, pos = _context_side(table, candidates, ctx_idx, ctx_xv, exclude, hyper, side, fm_term)
-    K = int(K)
-    args = (mlp, fm_term, S, bi, au, candidates.Sc, candidates.Bc, candidates.ac, K, off, pos)
-    if mlp_kernel_takes(mlp) or not 1 <= K <= MLP_TOPK_MAX_K:     # the kernel's checks raise on a bad K
-        top_pos, top_score = mlp_topk(*args)
-    else:
-        top_pos, top_score = mlp_topk_torch(*args)
-    return top_pos.long(), top_score
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
@@ -464,43 +338,6 @@ class AFMCandidates(Candidates):
         return self
 
 
-def afm_topk(afm, k, Eu, stats_u, Ec, stats_c, K, excl_offsets=None, excl_pos=None, workspace=None, out=None, stream=None):
-    """The raw call of fmx_afm_topk.  afm = (params, t), k the embedding size; Eu [U, n_ctx, kp], stats_u [U, 4], Ec [N, n_item,
-    kp], stats_c [N, 4] contiguous fp32 device tensors (afm_side's outputs).  Returns (top_pos int32 [U, K], top_score fp32
-    [U, K]) on the device."""
-    params, t = afm
-    U, n_ctx, kp = Eu.shape
-    N, n_item = Ec.shape[0], Ec.shape[1]
-    if Ec.shape[2] != kp or not all(x.is_contiguous() for x in (Eu, stats_u, Ec, stats_c)):
-        raise ValueError("Eu / Ec: contiguous [rows, fields, kp] with the same kp; stats contiguous [rows, 4]")
-    a = _lib.Afm(params.data_ptr(), int(k), int(t))
-    lib = _lib.load()
-    ws, ws_n, out, st = _call_buffers(lib.fmx_afm_topk_workspace_bytes(C.byref(a), n_ctx, n_item, U, N, K), U, K, Eu.device,
-                                      workspace, out, stream)
-    _lib.check(lib.fmx_afm_topk(C.byref(a), Eu.data_ptr(), stats_u.data_ptr(), n_ctx, U, Ec.data_ptr(), stats_c.data_ptr(), n_item,
-                                N, kp, _ptr(excl_offsets), _ptr(excl_pos), K, ws, ws_n, out[0].data_ptr(), out[1].data_ptr(), st))
-    return out
-
-
-def topk_afm(table, afm, ctx_idx, ctx_xv, candidates, K, exclude=None, hyper=None):
-    """Top-K candidates for every context row of ctx_idx / ctx_xv ([U, F] full width, the item columns ignored) under the AFM
-    afm = (params, t): the exact logit of the combined sample.  candidates: an AFMCandidates of the same table and attention
-    parameters.  Returns device tensors (positions int64 [U, K], -1 padded; logits fp32 [U, K], -inf padded), each row by
-    logit descending, then position ascending.  exclude: see exclusions_csr."""
-    params, t = afm[0], int(afm[1])
-    if not isinstance(candidates, AFMCandidates):
-        raise ValueError("candidates: an AFMCandidates (the AFM's candidate side)")
-    if candidates.table is table and (candidates.t != t or candidates.afm[0].data_ptr() != params.data_ptr()):
-        raise ValueError(f"candidates were computed for another attention (t={candidates.t}; this one has t={t})")
-
-    def side(table, idx, xv, fields, hyper):
-        return afm_side(table, (params, t), idx, xv, fields, True, hyper)
-
-    (Eu, stats_u), off, pos = _context_side(table, candidates, ctx_idx, ctx_xv, exclude, hyper, side)
-    top_pos, top_score = afm_topk((params, t), table.k, Eu, stats_u, candidates.Ec, candidates.stats, int(K), off, pos)
-    return top_pos.long(), top_score
-
-
 # ---------------------------------------------------------------------------------------------------------------------------
 # ranking evaluation: the rank of held-out targets among all candidates
 # ---------------------------------------------------------------------------------------------------------------------------
@@ -550,126 +387,12 @@ def _targets_arg(targets, U):
     return targets.shape[1]
 
 
-def fm_rank(Su, au, Sc, ac, targets, filtered=False, excl_offsets=None, excl_pos=None, workspace=None, out=None, stream=None,
-            kp=None):
-    """The raw call of fmx_fm_rank: fm_topk's arguments with targets int32 [U, T <= 16] (contiguous, on the device) in place
-    of K.  Returns device tensors (rank int32 [U, T], -1: not eligible; score fp32 [U, T], -inf there; n_cand int32 [U])."""
-    U, N = Su.shape[0], Sc.shape[0]
-    kp = Sc.shape[1] if kp is None else int(kp)
-    T = _targets_arg(targets, U)
-    lib = _lib.load()
-    ws, ws_n, out, st = _rank_buffers(lib.fmx_fm_rank_workspace_bytes(U, N, T), U, T, Su.device, workspace, out, stream)
-    _lib.check(lib.fmx_fm_rank(Su.data_ptr(), Su.stride(0), au.data_ptr(), U, Sc.data_ptr(), Sc.stride(0), ac.data_ptr(), N, kp,
-                               _ptr(excl_offsets), _ptr(excl_pos), targets.data_ptr(), T, int(bool(filtered)), ws, ws_n,
-                               out[0].data_ptr(), out[1].data_ptr(), out[2].data_ptr(), st))
-    return out
-
-
-def mlp_rank(mlp, fm_term, Su, Bu, au, Sc, Bc, ac, targets, filtered=False, excl_offsets=None, excl_pos=None, workspace=None,
-             out=None, stream=None, kp=None):
-    """The raw call of fmx_mlp_rank: mlp_topk's arguments with targets int32 [U, T <= 16] in place of K.  Returns as fm_rank."""
-    U, N = Su.shape[0], Sc.shape[0]
-    kp = Sc.shape[1] if kp is None else int(kp)
-    if Bu.stride(0) != Su.stride(0) or Bc.stride(0) != Sc.stride(0):
-        raise ValueError("Bu / Bc must share the row strides of Su / Sc")
-    T = _targets_arg(targets, U)
-    lib, m = _lib.load(), _mlp_struct(mlp)
-    ws, ws_n, out, st = _rank_buffers(lib.fmx_mlp_rank_workspace_bytes(C.byref(m), U, N, T), U, T, Su.device, workspace, out,
-                                      stream)
-    _lib.check(lib.fmx_mlp_rank(C.byref(m), int(fm_term), Su.data_ptr(), Bu.data_ptr(), Su.stride(0), au.data_ptr(), U,
-                                Sc.data_ptr(), Bc.data_ptr(), Sc.stride(0), ac.data_ptr(), N, kp, _ptr(excl_offsets),
-                                _ptr(excl_pos), targets.data_ptr(), T, int(bool(filtered)), ws, ws_n, out[0].data_ptr(),
-                                out[1].data_ptr(), out[2].data_ptr(), st))
-    return out
-
-
-def afm_rank(afm, k, Eu, stats_u, Ec, stats_c, targets, filtered=False, excl_offsets=None, excl_pos=None, workspace=None,
-             out=None, stream=None):
-    """The raw call of fmx_afm_rank: afm_topk's arguments with targets int32 [U, T <= 16] in place of K.  Returns as fm_rank."""
-    params, t = afm
-    U, n_ctx, kp = Eu.shape
-    N, n_item = Ec.shape[0], Ec.shape[1]
-    if Ec.shape[2] != kp or not all(x.is_contiguous() for x in (Eu, stats_u, Ec, stats_c)):
-        raise ValueError("Eu / Ec: contiguous [rows, fields, kp] with the same kp; stats contiguous [rows, 4]")
-    T = _targets_arg(targets, U)
-    a = _lib.Afm(params.data_ptr(), int(k), int(t))
-    lib = _lib.load()
-    ws, ws_n, out, st = _rank_buffers(lib.fmx_afm_rank_workspace_bytes(C.byref(a), n_ctx, n_item, U, N, T), U, T, Eu.device,
-                                      workspace, out, stream)
-    _lib.check(lib.fmx_afm_rank(C.byref(a), Eu.data_ptr(), stats_u.data_ptr(), n_ctx, U, Ec.data_ptr(), stats_c.data_ptr(), n_item,
-                                N, kp, _ptr(excl_offsets), _ptr(excl_pos), targets.data_ptr(), T, int(bool(filtered)), ws, ws_n,
-                                out[0].data_ptr(), out[1].data_ptr(), out[2].data_ptr(), st))
-    return out
-
-
 def _rank_key(score, pos):
     """The top-K order as one int64 per (score, position), greater = earlier: make_key of csrc/fmx_topk.hip (score descending,
     then position ascending, -0 taken as +0).  score fp32, pos integer, same shape."""
     b = (score.float() + 0.0).contiguous().view(torch.int32).long() & 0xFFFFFFFF
     o = torch.where(b >= 0x80000000, 0xFFFFFFFF - b, b + 0x80000000)           # the float bits made monotone
     return ((o - 0x80000000) << 32) + (0xFFFFFFFF - pos.long())                 # shifted into int64's signed range
-
-
-def mlp_rank_torch(mlp, fm_term, Su, Bu, au, Sc, Bc, ac, targets, filtered=False, excl_offsets=None, excl_pos=None, kp=None,
-                   max_elems=1 << 25):
-    """fmx_mlp_rank's definition on mlp_topk_torch's statement of the score (the same up to fp32 summation order), as chunked
-    torch: for a block of users every candidate's score, the eligible ones (not NaN, not excluded), and for each target the
-    number of eligible candidates with a greater (score, position) key.  targets: int32 [U, T], any T.  The path of networks
-    the kernel does not take, and the baseline of tools/rank_times.py.  Returns as fm_rank."""
-    params, k, H, L = mlp
-    U, N, dev = Su.shape[0], Sc.shape[0], Su.device
-    kp = Sc.shape[1] if kp is None else int(kp)
-    T = targets.shape[1]
-    Ws, off = [], 0
-    for l in range(L):
-        n_in = k if l == 0 else H
-        Ws.append((params[off:off + H * n_in].view(H, n_in), params[off + H * n_in:off + H * n_in + H]))
-        off += H * n_in + H
-    rank = torch.full((U, T), -1, dtype=torch.int32, device=dev)
-    score_out = torch.full((U, T), float("-inf"), dtype=torch.float32, device=dev)
-    n_cand = torch.zeros(U, dtype=torch.int32, device=dev)
-    Sck, Bck = Sc[:, :k], Bc[:, :k]
-    ub = max(1, min(U, max_elems // max(1, N * max(H, k))))
-    cb = max(1, min(N, max_elems // max(1, ub * max(H, k))))
-    positions = torch.arange(N, device=dev)
-    with torch.no_grad():
-        for u0 in range(0, U, ub):
-            u1 = min(U, u0 + ub)
-            score = torch.empty((u1 - u0, N), dtype=torch.float32, device=dev)
-            for c0 in range(0, N, cb):
-                c1 = min(N, c0 + cb)
-                x = (Bu[u0:u1, None, :k] + Bck[None, c0:c1]) + Su[u0:u1, None, :k] * Sck[None, c0:c1]
-                for W, b in Ws:
-                    x = torch.relu(torch.nn.functional.linear(x, W, b))
-                base = au[u0:u1, None] + ac[None, c0:c1]
-                if fm_term:
-                    base = base + Su[u0:u1, :kp] @ Sc[c0:c1, :kp].T
-                score[:, c0:c1] = base + x.sum(-1)
-            score = score + 0.0                              # -0 -> +0
-            ok = ~torch.isnan(score)
-            if excl_offsets is not None:
-                offs = excl_offsets.long().cpu()
-                for u in range(u0, u1):
-                    p = excl_pos[int(offs[u]):int(offs[u + 1])].long()
-                    p = p[(p >= 0) & (p < N)]
-                    ok[u - u0, p] = False
-            n_cand[u0:u1] = ok.sum(1).to(torch.int32)
-            key = _rank_key(torch.where(ok, score, torch.zeros_like(score)), positions[None, :].expand_as(score))
-            tg = targets[u0:u1].long()
-            inside = (tg >= 0) & (tg < N)
-            tgc = torch.where(inside, tg, torch.zeros_like(tg))
-            t_ok = inside & torch.gather(ok, 1, tgc)
-            t_key = torch.gather(key, 1, tgc)
-            for t in range(T):
-                ahead = ok & (key > t_key[:, t:t + 1])
-                if filtered:                                 # the user's other eligible targets are not counted
-                    others = torch.zeros_like(ok)
-                    rows = torch.arange(u1 - u0, device=dev)[:, None].expand(-1, T)
-                    others[rows[t_ok], tgc[t_ok]] = True
-                    ahead = ahead & ~others
-                rank[u0:u1, t] = torch.where(t_ok[:, t], ahead.sum(1), torch.full_like(tg[:, t], -1)).to(torch.int32)
-            score_out[u0:u1] = torch.where(t_ok, torch.gather(score, 1, tgc), torch.full_like(score_out[u0:u1], float("-inf")))
-    return rank, score_out, n_cand
 
 
 def _rank_chunks(call, targets, U, device, filtered):
@@ -698,47 +421,331 @@ def _rank_chunks(call, targets, U, device, filtered):
     return ranks, scores, n_cand
 
 
+# ---------------------------------------------------------------------------------------------------------------------------
+# the three families' scorers, and the two calls over any of them
+# ---------------------------------------------------------------------------------------------------------------------------
+def _raw_topk(scorer, user, cand, K, excl_offsets, excl_pos, workspace, out, stream, kp=None):
+    """fmx_<family>_topk on the two sides' tensors -> (top_pos int32 [U, K], top_score fp32 [U, K]) on the device."""
+    U, N, dev, ws_head, head = scorer.raw(user, cand, kp)
+    lib = _lib.load()
+    need = getattr(lib, f"fmx_{scorer.family}_topk_workspace_bytes")(*ws_head, U, N, K)
+    ws, ws_n, out, st = _call_buffers(need, U, K, dev, workspace, out, stream)
+    _lib.check(getattr(lib, f"fmx_{scorer.family}_topk")(*head, _ptr(excl_offsets), _ptr(excl_pos), K, ws, ws_n,
+                                                        out[0].data_ptr(), out[1].data_ptr(), st))
+    return out
+
+
+def _raw_rank(scorer, user, cand, targets, filtered, excl_offsets, excl_pos, workspace, out, stream, kp=None):
+    """fmx_<family>_rank: its top-K twin with targets int32 [U, T <= 16] (contiguous, on the device) and `filtered` in place of
+    K.  Returns device tensors (rank int32 [U, T], -1: not eligible; score fp32 [U, T], -inf there; n_cand int32 [U])."""
+    U, N, dev, ws_head, head = scorer.raw(user, cand, kp)
+    T = _targets_arg(targets, U)
+    lib = _lib.load()
+    need = getattr(lib, f"fmx_{scorer.family}_rank_workspace_bytes")(*ws_head, U, N, T)
+    ws, ws_n, out, st = _rank_buffers(need, U, T, dev, workspace, out, stream)
+    _lib.check(getattr(lib, f"fmx_{scorer.family}_rank")(*head, _ptr(excl_offsets), _ptr(excl_pos), targets.data_ptr(), T,
+                                                        int(bool(filtered)), ws, ws_n, out[0].data_ptr(), out[1].data_ptr(),
+                                                        out[2].data_ptr(), st))
+    return out
+
+
+class FMScorer:
+    """A family's score as the two calls need it: the check that candidates belong to it, its context side (`side`, whose first
+    result has a row per context), the candidates' tensors (`cand_side`), and the foreign call's arguments (`raw`: U, N, the
+    device, what its *_workspace_bytes functions take ahead of U, what its calls take up to and including kp).  This one: the
+    FM, a Candidates."""
+    family = "fm"
+
+    def check(self, table, candidates):
+        if candidates.table is not table:
+            raise ValueError("candidates were computed for another table")
+
+    def side(self, table, idx, xv, fields, hyper):
+        return side_sums(table, idx, xv, fields, hyper)
+
+    def cand_side(self, candidates):
+        return candidates.Sc, candidates.ac
+
+    def raw(self, user, cand, kp):
+        (Su, au), (Sc, ac) = user, cand
+        U, N = Su.shape[0], Sc.shape[0]
+        kp = Sc.shape[1] if kp is None else int(kp)
+        return U, N, Su.device, (), (Su.data_ptr(), Su.stride(0), au.data_ptr(), U, Sc.data_ptr(), Sc.stride(0), ac.data_ptr(), N, kp)
+
+    def topk(self, user, cand, K, off, pos):
+        return _raw_topk(self, user, cand, K, off, pos, None, None, None)
+
+    def rank(self, user, cand, targets, filtered, off, pos):
+        return _raw_rank(self, user, cand, targets, filtered, off, pos, None, None, None)
+
+
+class NetworkScorer(FMScorer):
+    """The DeepFM (fm_term = 1) / NFM (fm_term = 0) network mlp = (params, k, hidden, n_layers) on the pair's bi-interaction
+    vector; a NetworkCandidates of the same fm_term.  Networks the kernels do not take go through the torch statements."""
+    family = "mlp"
+
+    def __init__(self, mlp, fm_term):
+        self.mlp, self.fm_term = mlp, fm_term
+
+    def check(self, table, candidates):
+        super().check(table, candidates)
+        if not isinstance(candidates, NetworkCandidates) or candidates.fm_term != int(self.fm_term):
+            raise ValueError(f"candidates: a NetworkCandidates with fm_term={int(self.fm_term)}")
+
+    def side(self, table, idx, xv, fields, hyper):
+        S, bi, sfirst, sbi, logit = side_terms(table, idx, xv, fields, hyper)
+        return S, bi, network_bases(table, sfirst, sbi, logit, self.fm_term, context=True).contiguous()
+
+    def cand_side(self, candidates):
+        return candidates.Sc, candidates.Bc, candidates.ac
+
+    def raw(self, user, cand, kp):
+        (Su, Bu, au), (Sc, Bc, ac) = user, cand
+        U, N = Su.shape[0], Sc.shape[0]
+        kp = Sc.shape[1] if kp is None else int(kp)
+        if Bu.stride(0) != Su.stride(0) or Bc.stride(0) != Sc.stride(0):
+            raise ValueError("Bu / Bc must share the row strides of Su / Sc")
+        m = C.byref(_mlp_struct(self.mlp))
+        return U, N, Su.device, (m,), (m, int(self.fm_term), Su.data_ptr(), Bu.data_ptr(), Su.stride(0), au.data_ptr(), U,
+                                       Sc.data_ptr(), Bc.data_ptr(), Sc.stride(0), ac.data_ptr(), N, kp)
+
+    def topk(self, user, cand, K, off, pos):
+        if mlp_kernel_takes(self.mlp) or not 1 <= K <= MLP_TOPK_MAX_K:     # the kernel's checks raise on a bad K
+            return super().topk(user, cand, K, off, pos)
+        return mlp_topk_torch(self.mlp, self.fm_term, *user, *cand, K, off, pos)
+
+    def rank(self, user, cand, targets, filtered, off, pos):
+        if mlp_kernel_takes(self.mlp):
+            return super().rank(user, cand, targets, filtered, off, pos)
+        return mlp_rank_torch(self.mlp, self.fm_term, *user, *cand, targets, filtered, off, pos)
+
+
+class AFMScorer(FMScorer):
+    """The attentional FM afm = (params, t) over embeddings of size k; an AFMCandidates of the same attention parameters."""
+    family = "afm"
+
+    def __init__(self, afm, k):
+        self.afm, self.k = (afm[0], int(afm[1])), int(k)
+
+    def check(self, table, candidates):
+        params, t = self.afm
+        if not isinstance(candidates, AFMCandidates):
+            raise ValueError("candidates: an AFMCandidates (the AFM's candidate side)")
+        if candidates.table is table and (candidates.t != t or candidates.afm[0].data_ptr() != params.data_ptr()):
+            raise ValueError(f"candidates were computed for another attention (t={candidates.t}; this one has t={t})")
+        super().check(table, candidates)
+
+    def side(self, table, idx, xv, fields, hyper):
+        return afm_side(table, self.afm, idx, xv, fields, True, hyper)
+
+    def cand_side(self, candidates):
+        return candidates.Ec, candidates.stats
+
+    def raw(self, user, cand, kp):
+        (Eu, stats_u), (Ec, stats_c) = user, cand
+        U, n_ctx, kp = Eu.shape
+        N, n_item = Ec.shape[0], Ec.shape[1]
+        if Ec.shape[2] != kp or not all(x.is_contiguous() for x in (Eu, stats_u, Ec, stats_c)):
+            raise ValueError("Eu / Ec: contiguous [rows, fields, kp] with the same kp; stats contiguous [rows, 4]")
+        a = C.byref(_lib.Afm(self.afm[0].data_ptr(), self.k, self.afm[1]))
+        return U, N, Eu.device, (a, n_ctx, n_item), (a, Eu.data_ptr(), stats_u.data_ptr(), n_ctx, U, Ec.data_ptr(),
+                                                     stats_c.data_ptr(), n_item, N, kp)
+
+
+def _context_side(scorer, table, candidates, ctx_idx, ctx_xv, exclude, hyper):
+    """What the two calls share before the foreign call: the candidates' check, the scorer's side over the fields that are not
+    item fields, and the exclusions.  Returns (the side's tensors, exclusion offsets, exclusion positions)."""
+    scorer.check(table, candidates)
+    ctx_fields = [f for f in range(table.n_fields) if f not in candidates.item_fields]
+    user = scorer.side(table, ctx_idx, ctx_xv, ctx_fields, hyper if hyper is not None else candidates.hyper)
+    off, pos = exclusions_csr(exclude, user[0].shape[0], table.device)
+    return user, off, pos
+
+
+def scorer_topk(scorer, table, ctx_idx, ctx_xv, candidates, K, exclude=None, hyper=None):
+    """Top-K candidates for every context row of ctx_idx / ctx_xv ([U, F] full width, the item columns ignored) under the
+    scorer's family.  Returns device tensors (positions int64 [U, K], -1 padded; scores fp32 [U, K], -inf padded), each row by
+    score descending, then position ascending.  exclude: see exclusions_csr."""
+    user, off, pos = _context_side(scorer, table, candidates, ctx_idx, ctx_xv, exclude, hyper)
+    top_pos, top_score = scorer.topk(user, scorer.cand_side(candidates), int(K), off, pos)
+    return top_pos.long(), top_score
+
+
+def scorer_rank(scorer, table, ctx_idx, ctx_xv, candidates, targets, exclude=None, hyper=None, filtered=False):
+    """The rank of the target positions among all N candidates for every context row: the number of eligible candidates (not
+    NaN, not excluded) that scorer_topk's order puts in front of the target, i.e. its 0-based index in an unbounded top-K row.
+    targets: see targets_matrix (positions in the sense of the top-K results).  filtered: the user's other targets are not
+    counted (leave-n-out evaluation).  Returns device tensors (ranks int64 [U, T], -1: no eligible target; scores fp32 [U, T],
+    -inf there; n_cand int64 [U]).  More than 16 targets per user run as several calls; `filtered` across them is resolved on the
+    host side of the call (see _rank_chunks) from the returned scores and positions with the same key order."""
+    user, off, pos = _context_side(scorer, table, candidates, ctx_idx, ctx_xv, exclude, hyper)
+    cand = scorer.cand_side(candidates)
+    return _rank_chunks(lambda tg, f: scorer.rank(user, cand, tg, f, off, pos), targets, user[0].shape[0], table.device, filtered)
+
+
+# ---- the public forms, per family.  The raw calls take device tensors: Su / Bu [U, >= kp] and Sc / Bc [N, >= kp] fp32 (row
+# strides multiples of 4 and shared within a side, 16-byte aligned; kp defaults to Sc's width), au [U], ac [N]; mlp = (params, k,
+# hidden, n_layers) and afm = (params, t) with params the flat fp32 device buffer, k the embedding size; Eu [U, n_ctx, kp],
+# stats_u [U, 4], Ec [N, n_item, kp], stats_c [N, 4] contiguous (afm_side's outputs).  They return as _raw_topk / _raw_rank.
+def fm_topk(Su, au, Sc, ac, K, excl_offsets=None, excl_pos=None, workspace=None, out=None, stream=None, kp=None):
+    """The raw call of fmx_fm_topk -> (top_pos int32 [U, K], top_score fp32 [U, K]) on the device."""
+    return _raw_topk(FMScorer(), (Su, au), (Sc, ac), K, excl_offsets, excl_pos, workspace, out, stream, kp)
+
+
+def fm_rank(Su, au, Sc, ac, targets, filtered=False, excl_offsets=None, excl_pos=None, workspace=None, out=None, stream=None,
+            kp=None):
+    """The raw call of fmx_fm_rank: fm_topk's arguments with targets int32 [U, T <= 16] in place of K; returns as _raw_rank."""
+    return _raw_rank(FMScorer(), (Su, au), (Sc, ac), targets, filtered, excl_offsets, excl_pos, workspace, out, stream, kp)
+
+
+def mlp_topk(mlp, fm_term, Su, Bu, au, Sc, Bc, ac, K, excl_offsets=None, excl_pos=None, workspace=None, out=None, stream=None,
+             kp=None):
+    """The raw call of fmx_mlp_topk; returns as fm_topk."""
+    return _raw_topk(NetworkScorer(mlp, fm_term), (Su, Bu, au), (Sc, Bc, ac), K, excl_offsets, excl_pos, workspace, out, stream, kp)
+
+
+def mlp_rank(mlp, fm_term, Su, Bu, au, Sc, Bc, ac, targets, filtered=False, excl_offsets=None, excl_pos=None, workspace=None,
+             out=None, stream=None, kp=None):
+    """The raw call of fmx_mlp_rank: mlp_topk's arguments with targets int32 [U, T <= 16] in place of K; returns as fm_rank."""
+    return _raw_rank(NetworkScorer(mlp, fm_term), (Su, Bu, au), (Sc, Bc, ac), targets, filtered, excl_offsets, excl_pos, workspace,
+                     out, stream, kp)
+
+
+def afm_topk(afm, k, Eu, stats_u, Ec, stats_c, K, excl_offsets=None, excl_pos=None, workspace=None, out=None, stream=None):
+    """The raw call of fmx_afm_topk; returns as fm_topk."""
+    return _raw_topk(AFMScorer(afm, k), (Eu, stats_u), (Ec, stats_c), K, excl_offsets, excl_pos, workspace, out, stream)
+
+
+def afm_rank(afm, k, Eu, stats_u, Ec, stats_c, targets, filtered=False, excl_offsets=None, excl_pos=None, workspace=None,
+             out=None, stream=None):
+    """The raw call of fmx_afm_rank: afm_topk's arguments with targets int32 [U, T <= 16] in place of K; returns as fm_rank."""
+    return _raw_rank(AFMScorer(afm, k), (Eu, stats_u), (Ec, stats_c), targets, filtered, excl_offsets, excl_pos, workspace, out, stream)
+
+
+# The calls on a table: the FM's logit of the combined sample; topk_network / rank_network the DeepFM / NFM score (the logit of
+# the combined sample for the Adam classes, the logit whose sigmoid forward() returns for the ONN classes); topk_afm / rank_afm
+# the AFM's exact logit.  They return as scorer_topk / scorer_rank.
+def topk(table, ctx_idx, ctx_xv, candidates, K, exclude=None, hyper=None):
+    """scorer_topk under the FM's logit; candidates: a Candidates of the same table."""
+    return scorer_topk(FMScorer(), table, ctx_idx, ctx_xv, candidates, K, exclude, hyper)
+
+
 def rank(table, ctx_idx, ctx_xv, candidates, targets, exclude=None, hyper=None, filtered=False):
-    """The rank of the target positions among all N candidates for every context row of ctx_idx / ctx_xv ([U, F] full width,
-    the item columns ignored): the number of eligible candidates (not NaN, not excluded) that topk's order puts in front of
-    the target, i.e. its 0-based index in an unbounded topk row.  targets: see targets_matrix (positions in the sense of
-    topk's results).  filtered: the user's other targets are not counted (leave-n-out evaluation).  Returns device tensors
-    (ranks int64 [U, T], -1: no eligible target; scores fp32 [U, T], -inf there; n_cand int64 [U]).  More than 16 targets per
-    user run as several calls; `filtered` across them is resolved on the host side of the call (see _rank_chunks) from the
-    returned scores and positions with the same key order."""
-    (Su, au), off, pos = _context_side(table, candidates, ctx_idx, ctx_xv, exclude, hyper, side_sums)
-    return _rank_chunks(lambda tg, f: fm_rank(Su, au, candidates.Sc, candidates.ac, tg, f, off, pos), targets, Su.shape[0],
-                        table.device, filtered)
+    """scorer_rank under the FM's logit and topk's order."""
+    return scorer_rank(FMScorer(), table, ctx_idx, ctx_xv, candidates, targets, exclude, hyper, filtered)
+
+
+def topk_network(table, mlp, fm_term, ctx_idx, ctx_xv, candidates, K, exclude=None, hyper=None):
+    """scorer_topk under the DeepFM (fm_term = 1) / NFM (fm_term = 0) network mlp = (params, k, hidden, n_layers);
+    candidates: a NetworkCandidates of the same table and fm_term."""
+    return scorer_topk(NetworkScorer(mlp, fm_term), table, ctx_idx, ctx_xv, candidates, K, exclude, hyper)
 
 
 def rank_network(table, mlp, fm_term, ctx_idx, ctx_xv, candidates, targets, exclude=None, hyper=None, filtered=False):
-    """As rank, under the DeepFM (fm_term = 1) / NFM (fm_term = 0) network mlp = (params, k, hidden, n_layers) and topk_network's
-    score and order.  Networks fmx_mlp_rank does not take (hidden > 256) go through mlp_rank_torch."""
-    def side(table, idx, xv, fields, hyper):
-        S, bi, sfirst, sbi, logit = side_terms(table, idx, xv, fields, hyper)
-        return S, bi, network_bases(table, sfirst, sbi, logit, fm_term, context=True).contiguous()
+    """scorer_rank under the network's score and topk_network's order; networks fmx_mlp_rank does not take (hidden > 256) go
+    through mlp_rank_torch."""
+    return scorer_rank(NetworkScorer(mlp, fm_term), table, ctx_idx, ctx_xv, candidates, targets, exclude, hyper, filtered)
 
-    (S, bi, au), off, pos = _context_side(table, candidates, ctx_idx, ctx_xv, exclude, hyper, side, fm_term)
-    fn = mlp_rank if mlp_kernel_takes(mlp) else mlp_rank_torch
-    return _rank_chunks(lambda tg, f: fn(mlp, fm_term, S, bi, au, candidates.Sc, candidates.Bc, candidates.ac, tg, f, off, pos),
-                        targets, S.shape[0], table.device, filtered)
+
+def topk_afm(table, afm, ctx_idx, ctx_xv, candidates, K, exclude=None, hyper=None):
+    """scorer_topk under the AFM afm = (params, t): the exact logit of the combined sample; candidates: an AFMCandidates of
+    the same table and attention parameters."""
+    return scorer_topk(AFMScorer(afm, table.k), table, ctx_idx, ctx_xv, candidates, K, exclude, hyper)
 
 
 def rank_afm(table, afm, ctx_idx, ctx_xv, candidates, targets, exclude=None, hyper=None, filtered=False):
-    """As rank, under the AFM afm = (params, t) and topk_afm's score and order.  candidates: an AFMCandidates of the same table
-    and attention parameters."""
-    params, t = afm[0], int(afm[1])
-    if not isinstance(candidates, AFMCandidates):
-        raise ValueError("candidates: an AFMCandidates (the AFM's candidate side)")
-    if candidates.table is table and (candidates.t != t or candidates.afm[0].data_ptr() != params.data_ptr()):
-        raise ValueError(f"candidates were computed for another attention (t={candidates.t}; this one has t={t})")
+    """scorer_rank under the AFM's logit and topk_afm's order."""
+    return scorer_rank(AFMScorer(afm, table.k), table, ctx_idx, ctx_xv, candidates, targets, exclude, hyper, filtered)
 
-    def side(table, idx, xv, fields, hyper):
-        return afm_side(table, (params, t), idx, xv, fields, True, hyper)
 
-    (Eu, stats_u), off, pos = _context_side(table, candidates, ctx_idx, ctx_xv, exclude, hyper, side)
-    return _rank_chunks(lambda tg, f: afm_rank((params, t), table.k, Eu, stats_u, candidates.Ec, candidates.stats, tg, f, off, pos),
-                        targets, Eu.shape[0], table.device, filtered)
+# ---- the network's score as chunked torch: the path of networks the kernels do not take (hidden > 256), and the baseline of
+# tools/mlp_topk_times.py and tools/rank_times.py
+def _mlp_torch_blocks(mlp, fm_term, Su, Bu, au, Sc, Bc, ac, excl_offsets, excl_pos, kp, max_elems):
+    """fmx_mlp_topk's score (up to fp32 summation order) by blocks of users: yields (u0, u1, score fp32 [u1 - u0, N] with -0 as
+    +0, eligible bool [u1 - u0, N]: not NaN and not excluded)."""
+    params, k, H, L = mlp
+    U, N, dev = Su.shape[0], Sc.shape[0], Su.device
+    kp = Sc.shape[1] if kp is None else int(kp)
+    Ws, off = [], 0
+    for l in range(L):
+        n_in = k if l == 0 else H
+        Ws.append((params[off:off + H * n_in].view(H, n_in), params[off + H * n_in:off + H * n_in + H]))
+        off += H * n_in + H
+    Sck, Bck = Sc[:, :k], Bc[:, :k]
+    ub = max(1, min(U, max_elems // max(1, N * max(H, k))))
+    cb = max(1, min(N, max_elems // max(1, ub * max(H, k))))
+    offs = None if excl_offsets is None else excl_offsets.long().cpu()
+    for u0 in range(0, U, ub):
+        u1 = min(U, u0 + ub)
+        with torch.no_grad():
+            score = torch.empty((u1 - u0, N), dtype=torch.float32, device=dev)
+            for c0 in range(0, N, cb):
+                c1 = min(N, c0 + cb)
+                x = (Bu[u0:u1, None, :k] + Bck[None, c0:c1]) + Su[u0:u1, None, :k] * Sck[None, c0:c1]
+                for W, b in Ws:
+                    x = torch.relu(torch.nn.functional.linear(x, W, b))
+                base = au[u0:u1, None] + ac[None, c0:c1]
+                if fm_term:
+                    base = base + Su[u0:u1, :kp] @ Sc[c0:c1, :kp].T
+                score[:, c0:c1] = base + x.sum(-1)
+            score = score + 0.0                              # -0 -> +0
+            ok = ~torch.isnan(score)
+            if offs is not None:
+                for u in range(u0, u1):
+                    p = excl_pos[int(offs[u]):int(offs[u + 1])].long()
+                    ok[u - u0, p[(p >= 0) & (p < N)]] = False
+        yield u0, u1, score, ok
+
+
+def mlp_topk_torch(mlp, fm_term, Su, Bu, au, Sc, Bc, ac, K, excl_offsets=None, excl_pos=None, kp=None, max_elems=1 << 25):
+    """The same score (up to fp32 summation order) and the same result order as fmx_mlp_topk: for a block of users, every
+    candidate's network output, then a stable sort on (score descending, position ascending); NaN and excluded candidates are
+    never returned, rows are padded with -1 / -inf, -0 is returned as +0."""
+    U, dev = Su.shape[0], Su.device
+    top_pos = torch.full((U, K), -1, dtype=torch.int32, device=dev)
+    top_score = torch.full((U, K), float("-inf"), dtype=torch.float32, device=dev)
+    for u0, u1, score, ok in _mlp_torch_blocks(mlp, fm_term, Su, Bu, au, Sc, Bc, ac, excl_offsets, excl_pos, kp, max_elems):
+        score = torch.where(ok, score, torch.full_like(score, float("-inf")))
+        s1, i1 = torch.sort(score, dim=1, descending=True, stable=True)
+        ok1 = torch.gather(ok, 1, i1)
+        _, i2 = torch.sort(ok1.to(torch.int8), dim=1, descending=True, stable=True)
+        idx = torch.gather(i1, 1, i2)[:, :K]
+        sc = torch.gather(s1, 1, i2)[:, :K]
+        valid = torch.gather(ok1, 1, i2)[:, :K]
+        n = idx.shape[1]
+        top_pos[u0:u1, :n] = torch.where(valid, idx, torch.full_like(idx, -1)).to(torch.int32)
+        top_score[u0:u1, :n] = torch.where(valid, sc, torch.full_like(sc, float("-inf")))
+    return top_pos, top_score
+
+
+def mlp_rank_torch(mlp, fm_term, Su, Bu, au, Sc, Bc, ac, targets, filtered=False, excl_offsets=None, excl_pos=None, kp=None,
+                   max_elems=1 << 25):
+    """fmx_mlp_rank's definition on the same statement of the score: for a block of users the eligible candidates, and for each
+    target the number of them with a greater (score, position) key.  targets: int32 [U, T], any T.  Returns as fm_rank."""
+    U, N, dev = Su.shape[0], Sc.shape[0], Su.device
+    T = targets.shape[1]
+    rank = torch.full((U, T), -1, dtype=torch.int32, device=dev)
+    score_out = torch.full((U, T), float("-inf"), dtype=torch.float32, device=dev)
+    n_cand = torch.zeros(U, dtype=torch.int32, device=dev)
+    positions = torch.arange(N, device=dev)
+    for u0, u1, score, ok in _mlp_torch_blocks(mlp, fm_term, Su, Bu, au, Sc, Bc, ac, excl_offsets, excl_pos, kp, max_elems):
+        n_cand[u0:u1] = ok.sum(1).to(torch.int32)
+        key = _rank_key(torch.where(ok, score, torch.zeros_like(score)), positions[None, :].expand_as(score))
+        tg = targets[u0:u1].long()
+        inside = (tg >= 0) & (tg < N)
+        tgc = torch.where(inside, tg, torch.zeros_like(tg))
+        t_ok = inside & torch.gather(ok, 1, tgc)
+        t_key = torch.gather(key, 1, tgc)
+        for t in range(T):
+            ahead = ok & (key > t_key[:, t:t + 1])
+            if filtered:                                 # the user's other eligible targets are not counted
+                others = torch.zeros_like(ok)
+                rows = torch.arange(u1 - u0, device=dev)[:, None].expand(-1, T)
+                others[rows[t_ok], tgc[t_ok]] = True
+                ahead = ahead & ~others
+            rank[u0:u1, t] = torch.where(t_ok[:, t], ahead.sum(1), torch.full_like(tg[:, t], -1)).to(torch.int32)
+        score_out[u0:u1] = torch.where(t_ok, torch.gather(score, 1, tgc), torch.full_like(score_out[u0:u1], float("-inf")))
+    return rank, score_out, n_cand
 
 
 def ranking_metrics(ranks, n_cand, ks=(1, 5, 10)):

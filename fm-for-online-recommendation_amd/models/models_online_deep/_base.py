@@ -555,73 +555,15 @@ class OnlineFMBase(RankingTraining, nn.Module):
         pred = torch.sigmoid(out).cpu()
         return pred.data.numpy() > 0.5
 
-    def _candidate_rows(self, item_fields, candidates):
-        """recommend's and rank's candidates: (item fields, cand_idx, cand_xv) -- every row of the one item field when
-        candidates is None, else the caller's (cand_Xi, cand_Xv)."""
-        item_fields = self._item_fields(item_fields)
-        F = self.field_size
-        if candidates is None:
-            if len(item_fields) != 1:
-                raise ValueError("candidates=None needs exactly one item field (its rows are the candidates)")
-            f = item_fields[0]
-            cand_idx = torch.zeros((self.feature_sizes[f], F), dtype=torch.int32, device=self.device)
-            cand_idx[:, f] = torch.arange(self.feature_sizes[f], dtype=torch.int32, device=self.device)
-            cand_xv = None
-        else:
-            cand_idx, cand_xv = candidates
-        return item_fields, cand_idx, cand_xv
-
-    def recommend(self, Xi, Xv, item_fields, K, candidates=None, exclude=None, full=False):
-        """Top-K candidates for every context row (fmx/recommend.py, fmx_fm_topk).  Xi / Xv: [U, F] full-width rows whose
-        item columns are ignored (Xv may be None: all ones).  candidates=None: every row of the one item field, a position is
-        that field's local index; else (cand_Xi [N, F], cand_Xv or None) whose non-item columns are ignored.  exclude: per-user
-        position lists or a CSR pair (offsets, positions).  Returns numpy (positions int64 [U, K], -1 padded; logits fp32
-        [U, K], -inf padded), each row by logit descending, then position ascending.
-        full=True scores every pair through the whole network (fmx_mlp_topk): for DeepFMAdam / NFMAdam the logit forward()
-        returns, for DeepFMOnn / NFMOnn the logit whose sigmoid forward() returns; on FMAdam it is the default call."""
-        if self._has_mlp and not full:
-            raise NotImplementedError(f"{self._name}.recommend: the MLP on the bi-interaction vector does not decompose over "
-                                      "the context / item field split; recommend(..., full=True) scores every pair through "
-                                      "the network")
+    def _scoring(self, item_fields, candidates, full):
+        """RankingTraining's hook for recommend / rank: the FM's scorer, or the whole network's (full=True: _scoring_of)."""
         item_fields, cand_idx, cand_xv = self._candidate_rows(item_fields, candidates)
         rec, t, h = fmx.recommend, self._table, self._hyper
-        if self._has_mlp:
-            fm_term = 1 if self._fm_term_in_forward else 0
-            mlp = (self._mlp_flat, self.embedding_size, self.neuron_per_hidden_layer, self.num_hidden_layers)
-            cands = rec.NetworkCandidates(t, item_fields, cand_idx, cand_xv, fm_term=fm_term, hyper=h)
-            pos, logit = rec.topk_network(t, mlp, fm_term, Xi, Xv, cands, K, exclude=exclude, hyper=h)
-        else:
-            cands = rec.Candidates(t, item_fields, cand_idx, cand_xv, hyper=h)
-            pos, logit = rec.topk(t, Xi, Xv, cands, K, exclude=exclude, hyper=h)
-        return pos.cpu().numpy(), logit.cpu().numpy()
-
-    def rank(self, Xi, Xv, item_fields, targets, candidates=None, exclude=None, full=False, filtered=False):
-        """The rank of held-out target positions among all candidates for every context row (fmx/recommend.py, fmx_fm_rank /
-        fmx_mlp_rank): the number of eligible candidates recommend's order puts in front of the target, i.e. its 0-based index
-        in an unbounded recommend row.  Xi / Xv, item_fields, candidates, exclude, full: as recommend.  targets: [U], [U, T] or U
-        lists of positions in the sense of recommend's results (-1: padding).  filtered: the user's other targets are not
-        counted.  Returns numpy (ranks int64 [U, T], -1: not eligible; scores fp32 [U, T], -inf there; n_cand int64 [U])."""
-        if self._has_mlp and not full:
-            raise NotImplementedError(f"{self._name}.recommend: the MLP on the bi-interaction vector does not decompose over "
-                                      "the context / item field split; recommend(..., full=True) scores every pair through "
-                                      "the network")
-        item_fields, cand_idx, cand_xv = self._candidate_rows(item_fields, candidates)
-        rec, t, h = fmx.recommend, self._table, self._hyper
-        if self._has_mlp:
-            fm_term = 1 if self._fm_term_in_forward else 0
-            mlp = (self._mlp_flat, self.embedding_size, self.neuron_per_hidden_layer, self.num_hidden_layers)
-            cands = rec.NetworkCandidates(t, item_fields, cand_idx, cand_xv, fm_term=fm_term, hyper=h)
-            out = rec.rank_network(t, mlp, fm_term, Xi, Xv, cands, targets, exclude=exclude, hyper=h, filtered=filtered)
-        else:
-            cands = rec.Candidates(t, item_fields, cand_idx, cand_xv, hyper=h)
-            out = rec.rank(t, Xi, Xv, cands, targets, exclude=exclude, hyper=h, filtered=filtered)
-        return tuple(o.cpu().numpy() for o in out)
-
-    def evaluate_ranking(self, Xi, Xv, item_fields, targets, candidates=None, exclude=None, full=False, filtered=False,
-                         ks=(1, 5, 10)):
-        """fmx.recommend.ranking_metrics (hr@K, ndcg@K, mrr, auc, n) of rank(...)."""
-        ranks, _, n_cand = self.rank(Xi, Xv, item_fields, targets, candidates, exclude, full, filtered)
-        return fmx.recommend.ranking_metrics(torch.from_numpy(ranks), torch.from_numpy(n_cand), ks=ks)
+        if not self._has_mlp:
+            return rec.FMScorer(), rec.Candidates(t, item_fields, cand_idx, cand_xv, hyper=h)
+        fm_term = 1 if self._fm_term_in_forward else 0
+        mlp = (self._mlp_flat, self.embedding_size, self.neuron_per_hidden_layer, self.num_hidden_layers)
+        return rec.NetworkScorer(mlp, fm_term), rec.NetworkCandidates(t, item_fields, cand_idx, cand_xv, fm_term=fm_term, hyper=h)
 
     def _device_loop_ok(self):
         """Can run_experiment's predict-then-fit loop run on the device for this model?

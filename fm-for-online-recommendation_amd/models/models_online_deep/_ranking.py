@@ -17,6 +17,15 @@ import torch
 import fmx
 
 
+def _scoring_of(model, item_fields, candidates, full):
+    """recommend's and rank's first step: the refusal of the classes with an MLP without full=True, then the class's hook"""
+    if getattr(model, "_has_mlp", False) and not full:
+        raise NotImplementedError(f"{model._name}.recommend: the MLP on the bi-interaction vector does not decompose over "
+                                  "the context / item field split; recommend(..., full=True) scores every pair through "
+                                  "the network")
+    return model._scoring(item_fields, candidates, full)
+
+
 class RankingTraining:
     # whose logit the class trains: "fm" (the pure FM: FMAdam), "mlp" (the classes with an MLP) or "afm"
     _logit_family = "fm"
@@ -25,6 +34,57 @@ class RankingTraining:
     def _item_fields(item_fields):
         """One field index or a sequence of them -> a list of ints"""
         return [int(f) for f in (item_fields if hasattr(item_fields, "__len__") else [item_fields])]
+
+    # ---- recommendation and ranking evaluation (fmx/recommend.py) ----
+    def _candidate_rows(self, item_fields, candidates):
+        """recommend's and rank's candidates: (item fields, cand_idx, cand_xv) -- every row of the one item field when
+        candidates is None, else the caller's (cand_Xi, cand_Xv)."""
+        item_fields = self._item_fields(item_fields)
+        F = self.field_size
+        if candidates is None:
+            if len(item_fields) != 1:
+                raise ValueError("candidates=None needs exactly one item field (its rows are the candidates)")
+            f = item_fields[0]
+            cand_idx = torch.zeros((self.feature_sizes[f], F), dtype=torch.int32, device=self.device)
+            cand_idx[:, f] = torch.arange(self.feature_sizes[f], dtype=torch.int32, device=self.device)
+            cand_xv = None
+        else:
+            cand_idx, cand_xv = candidates
+        return item_fields, cand_idx, cand_xv
+
+    def _scoring(self, item_fields, candidates, full):
+        """The class's hook: -> (its fmx.recommend scorer, its candidates object over _candidate_rows(item_fields, candidates))"""
+        raise NotImplementedError
+
+    def recommend(self, Xi, Xv, item_fields, K, candidates=None, exclude=None, full=False):
+        """Top-K candidates for every context row (fmx/recommend.py; fmx_fm_topk, fmx_mlp_topk, fmx_afm_topk).  Xi / Xv: [U, F]
+        full-width rows whose item columns are ignored (Xv may be None: all ones).  candidates=None: every row of the one item
+        field, a position is that field's local index; else (cand_Xi [N, F], cand_Xv or None) whose non-item columns are
+        ignored.  exclude: per-user position lists or a CSR pair (offsets, positions).  Returns numpy (positions int64 [U, K], -1
+        padded; logits fp32 [U, K], -inf padded), each row by logit descending, then position ascending.
+        full=True scores every pair through the whole network (fmx_mlp_topk): for DeepFMAdam / NFMAdam the logit forward()
+        returns, for DeepFMOnn / NFMOnn the logit whose sigmoid forward() returns; on FMAdam it is the default call, and AFMAdam
+        accepts it for the signature: its score is always the whole model's, the exact logit forward() gives the combined sample."""
+        scorer, cands = _scoring_of(self, item_fields, candidates, full)
+        pos, logit = fmx.recommend.scorer_topk(scorer, self._table, Xi, Xv, cands, K, exclude=exclude, hyper=self._hyper)
+        return pos.cpu().numpy(), logit.cpu().numpy()
+
+    def rank(self, Xi, Xv, item_fields, targets, candidates=None, exclude=None, full=False, filtered=False):
+        """The rank of held-out target positions among all candidates for every context row (fmx/recommend.py; fmx_fm_rank,
+        fmx_mlp_rank, fmx_afm_rank): the number of eligible candidates recommend's order puts in front of the target, i.e. its
+        0-based index in an unbounded recommend row.  Xi / Xv, item_fields, candidates, exclude, full: as recommend.  targets: [U],
+        [U, T] or U lists of positions in the sense of recommend's results (-1: padding).  filtered: the user's other targets are
+        not counted.  Returns numpy (ranks int64 [U, T], -1: not eligible; scores fp32 [U, T], -inf there; n_cand int64 [U])."""
+        scorer, cands = _scoring_of(self, item_fields, candidates, full)
+        out = fmx.recommend.scorer_rank(scorer, self._table, Xi, Xv, cands, targets, exclude=exclude, hyper=self._hyper,
+                                        filtered=filtered)
+        return tuple(o.cpu().numpy() for o in out)
+
+    def evaluate_ranking(self, Xi, Xv, item_fields, targets, candidates=None, exclude=None, full=False, filtered=False,
+                         ks=(1, 5, 10)):
+        """fmx.recommend.ranking_metrics (hr@K, ndcg@K, mrr, auc, n) of rank(...)."""
+        ranks, _, n_cand = self.rank(Xi, Xv, item_fields, targets, candidates, exclude, full, filtered)
+        return fmx.recommend.ranking_metrics(torch.from_numpy(ranks), torch.from_numpy(n_cand), ks=ks)
 
     # ---- the refusals, by class and method name ----
     def _refuse_hard_negatives(self, method, negatives):

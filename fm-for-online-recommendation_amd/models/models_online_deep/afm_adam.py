@@ -156,43 +156,16 @@ class AFMAdam(RankingTraining, nn.Module):
     def predict(self, Xi, Xv):
         return self.predict_proba(Xi, Xv) > 0.5
 
-    def _candidate_rows(self, item_fields, candidates):
-        """OnlineFMBase._candidate_rows, after this class's check that the one item field of candidates=None is a field."""
+    def _scoring(self, item_fields, candidates, full):
+        """RankingTraining's hook for recommend / rank: the attentional scorer (whatever `full`), after this class's check that
+        the one item field of candidates=None is a field."""
         fields = self._item_fields(item_fields)
         if candidates is None and len(fields) == 1 and not 0 <= fields[0] < self.field_size:
             raise ValueError(f"item field {fields[0]}: not a field of 0..{self.field_size - 1}")
-        return OnlineFMBase._candidate_rows(self, item_fields, candidates)
-
-    def recommend(self, Xi, Xv, item_fields, K, candidates=None, exclude=None, full=False):
-        """Top-K candidates for every context row (fmx/recommend.py, fmx_afm_topk): the exact logit forward() gives the combined
-        sample.  Xi / Xv: [U, F] full-width rows whose item columns are ignored (Xv may be None: all ones).  candidates=None:
-        every row of the one item field, a position is that field's local index; else (cand_Xi [N, F], cand_Xv or None) whose
-        non-item columns are ignored.  exclude: per-user position lists or a CSR pair (offsets, positions).  Returns numpy
-        (positions int64 [U, K], -1 padded; logits fp32 [U, K], -inf padded), each row by logit descending, then position
-        ascending.  full is accepted for the other classes' signature: the score is always the whole model's."""
         item_fields, cand_idx, cand_xv = self._candidate_rows(item_fields, candidates)
         rec, afm = fmx.recommend, (self._attn_flat, self.attention_size)
-        cands = rec.AFMCandidates(self._table, afm, item_fields, cand_idx, cand_xv, hyper=self._hyper)
-        pos, logit = rec.topk_afm(self._table, afm, Xi, Xv, cands, K, exclude=exclude, hyper=self._hyper)
-        return pos.cpu().numpy(), logit.cpu().numpy()
-
-    def rank(self, Xi, Xv, item_fields, targets, candidates=None, exclude=None, full=False, filtered=False):
-        """The rank of held-out target positions among all candidates for every context row (fmx/recommend.py, fmx_afm_rank): the
-        number of eligible candidates recommend's order puts in front of the target, i.e. its 0-based index in an unbounded
-        recommend row.  Xi / Xv, item_fields, candidates, exclude, full: as recommend.  targets: [U], [U, T] or U lists of
-        positions in the sense of recommend's results (-1: padding).  filtered: the user's other targets are not counted.
-        Returns numpy (ranks int64 [U, T], -1: not eligible; scores fp32 [U, T], -inf there; n_cand int64 [U])."""
-        item_fields, cand_idx, cand_xv = self._candidate_rows(item_fields, candidates)
-        rec, afm = fmx.recommend, (self._attn_flat, self.attention_size)
-        cands = rec.AFMCandidates(self._table, afm, item_fields, cand_idx, cand_xv, hyper=self._hyper)
-        out = rec.rank_afm(self._table, afm, Xi, Xv, cands, targets, exclude=exclude, hyper=self._hyper, filtered=filtered)
-        return tuple(o.cpu().numpy() for o in out)
-
-    def evaluate_ranking(self, Xi, Xv, item_fields, targets, candidates=None, exclude=None, full=False, filtered=False,
-                         ks=(1, 5, 10)):
-        """fmx.recommend.ranking_metrics (hr@K, ndcg@K, mrr, auc, n) of rank(...)."""
-        ranks, _, n_cand = self.rank(Xi, Xv, item_fields, targets, candidates, exclude, full, filtered)
-        return fmx.recommend.ranking_metrics(torch.from_numpy(ranks), torch.from_numpy(n_cand), ks=ks)
+        return (rec.AFMScorer(afm, self._table.k),
+                rec.AFMCandidates(self._table, afm, item_fields, cand_idx, cand_xv, hyper=self._hyper))
 
     # ------------------------------------------------------------------------------------------------------
     # training

@@ -30,19 +30,29 @@ def targets_for(top_pos, U, N, seed):
     return tg.contiguous()
 
 
-@pytest.mark.parametrize("N", [257, 8193])
-@pytest.mark.parametrize("F, item, k, t", LAYOUTS)
-def test_afm_rank_against_topk_and_float64(F, item, k, t, N):
+def check_layout(F, item, k, t, N, Ts):
     rec, U = _rec(), 3
     r0 = run(F, item, k, t, U, N, 256, seed=N % 7)
     tg = targets_for(r0["pos"], U, N, seed=N)
     elig = torch.ones(U, N, dtype=torch.bool, device=DEV)
-    for T in (1, 2, 16):
+    for T in Ts:
         tt = tg[:, :T].contiguous() if T < 16 else tg
         r, s, n = rec.rank_afm(r0["tb"], r0["afm"], r0["ctx"], r0["cx"], r0["cands"], tt)
         check_against_topk(r, s, torch.where(tt < N, tt, torch.full_like(tt, -1)), r0["pos"], r0["val"])
         check_bracket(r, r0["score"], r0["tol"], tt, elig)
         assert bool((n == N).all())
+
+
+@pytest.mark.parametrize("N", [257, 8193])
+@pytest.mark.parametrize("F, item, k, t", LAYOUTS)
+def test_afm_rank_against_topk_and_float64(F, item, k, t, N):
+    check_layout(F, item, k, t, N, (1, 2, 16))
+
+
+@pytest.mark.parametrize("k", [5, 17, 33])
+def test_afm_rank_at_the_other_row_widths(k):
+    """LAYOUTS reaches kp 4 and 16; these are kp 8, 32 and 64 of the rank call's dispatch, under the same checks"""
+    check_layout(3, [1], k, 4, 257, (1, 16))
 
 
 def test_determinism_batch_independence_and_one_target_at_a_time():

@@ -49,9 +49,12 @@ def assert_exact(got, want):
     assert torch.equal(bits(s), bits(torch.from_numpy(ws.astype(np.float32)))), "scores differ in their bits"
 
 
+# every shape at kp 4, 16 and 64; the other two widths the dispatch knows at one pair and past one chunk
+KP_CASES = [(U, N, kp) for U, N in SHAPES for kp in (4, 16, 64)] + [(U, N, kp) for U, N in ((1, 1), (3, 257)) for kp in (8, 32)]
+
+
 @pytest.mark.parametrize("variant", ["plain", "excl", "pad", "nan"])
-@pytest.mark.parametrize("kp", [4, 16, 64])
-@pytest.mark.parametrize("U, N", SHAPES)
+@pytest.mark.parametrize("U, N, kp", KP_CASES)
 def test_fm_rank_is_the_definition_exactly(U, N, kp, variant):
     rng = np.random.default_rng(1000 * kp + N + U)
     Su, au, Sc, ac = exact_inputs(kp, U, N, seed=N + kp)

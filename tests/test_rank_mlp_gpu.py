@@ -10,7 +10,7 @@ import torch
 import fmx
 from fmx import recommend as rec
 from rank_checks import bits, check_against_topk, check_bracket
-from test_recommend_mlp_gpu import brute, make_net, make_sides
+from test_recommend_mlp_gpu import brute, check_rows, make_net, make_sides
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -48,6 +48,29 @@ def test_mlp_rank_against_topk_and_float64(U, N, k, kp, H, L, fm_term):
             check_against_topk(r, s, torch.where(t < N, t, torch.full_like(t, -1)), top_pos, top_score)
             check_bracket(r, score, tol, t, elig)
             assert bool((n == N).all())
+
+
+# hidden sizes on both sides of every boundary of the network scan's map from column tiles (hidden / 16, rounded up) to its wave
+# grid: 1, 2, 3, 4, 5..8, 9..12 and 13..16 tiles
+WAVE_GRID_HIDDEN = [16, 17, 32, 33, 48, 49, 64, 65, 128, 129, 192, 193, 256]
+
+
+@pytest.mark.parametrize("fm_term", [0, 1])
+@pytest.mark.parametrize("H", WAVE_GRID_HIDDEN)
+def test_every_wave_grid_under_both_calls(H, fm_term):
+    """N = 65: one full chunk of 64 candidates and a ragged one"""
+    L, k, kp, U, N, K, T = 2, 3, 4, 2, 65, 10, 2
+    net = make_net(k, H, L, seed=H)
+    sides = make_sides(k, kp, U, N, seed=H + fm_term)
+    score, tol = brute(net, fm_term, *sides)
+    top_pos, top_score = rec.mlp_topk(net, fm_term, *sides, K)
+    check_rows(top_pos, top_score, score, tol, K)
+    tg = torch.stack([top_pos[:, 1].to(torch.int32), torch.tensor([N - 1, 7], dtype=torch.int32, device=DEV)], 1).contiguous()
+    assert tg.shape == (U, T)
+    r, s, n = rec.mlp_rank(net, fm_term, *sides, tg, False)
+    assert check_against_topk(r, s, tg, top_pos, top_score) >= U       # the targets taken from the row are found in it
+    check_bracket(r, score, tol, tg, torch.ones(U, N, dtype=torch.bool, device=DEV))
+    assert bool((n == N).all())
 
 
 @pytest.mark.parametrize("k, kp, H, L", NETS)

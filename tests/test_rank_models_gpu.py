@@ -102,6 +102,47 @@ def test_model_rank(kind):
     assert (f[0] <= ranks).all() and (f[0][ranks >= 0] >= 0).all()
 
 
+SIZES3, ITEM3 = [13, 300, 25], 1     # three fields; the item field's 300 rows are the candidates
+
+
+def build3(kind):
+    """one model per hook that hands recommend / rank their scorer: the FM's, the network's (full=True), the attentional one"""
+    torch.manual_seed(3)
+    if kind == "FMAdam":
+        from models.models_online_deep.fm_adam import FMAdam
+        return FMAdam(SIZES3, embedding_size=10, n=0.05, update_rule="sgd"), {}
+    if kind == "DeepFMAdam":
+        from models.models_online_deep.deepfm_adam import DeepFMAdam
+        return DeepFMAdam(SIZES3, embedding_size=10, num_hidden_layers=3, neuron_per_hidden_layer=16, n=0.05,
+                          update_rule="sgd"), dict(full=True)
+    return afm_t._model("adam", SIZES3), {}
+
+
+@pytest.mark.parametrize("kind", ["FMAdam", "DeepFMAdam", "AFMAdam"])
+def test_the_methods_the_classes_share(kind):
+    """rank's scores at the head of recommend's row are recommend's logits bit for bit, at the row's indices; evaluate_ranking
+    is ranking_metrics of rank"""
+    m, kw = build3(kind)
+    rng = np.random.default_rng(7)
+    Xi = np.stack([rng.integers(0, s, U) for s in SIZES3], 1).astype(np.int64)
+    Xv = rng.uniform(0.5, 1.5, (U, len(SIZES3))).astype(np.float32)
+    K, T = 10, 4
+    pos, logit = m.recommend(Xi, Xv, [ITEM3], K, **kw)
+    assert pos.shape == (U, K) and pos.dtype == np.int64 and logit.dtype == np.float32 and (pos >= 0).all()
+    head = np.ascontiguousarray(pos[:, :T])
+    ranks, scores, n_cand = m.rank(Xi, Xv, [ITEM3], head, **kw)
+    np.testing.assert_array_equal(ranks, np.tile(np.arange(T), (U, 1)))
+    np.testing.assert_array_equal(scores.view(np.int32), np.ascontiguousarray(logit[:, :T]).view(np.int32))
+    assert n_cand.tolist() == [SIZES3[ITEM3]] * U
+    targets = head.copy()
+    targets[:, 3] = rng.integers(0, SIZES3[ITEM3], U)
+    targets[0, 2] = -1
+    ranks, _, n_cand = m.rank(Xi, Xv, [ITEM3], targets, **kw)
+    want = rec.ranking_metrics(torch.from_numpy(ranks), torch.from_numpy(n_cand), ks=(1, 5))
+    got = m.evaluate_ranking(Xi, Xv, [ITEM3], targets, ks=(1, 5), **kw)
+    assert got.keys() == want.keys() and all(got[k] == want[k] for k in got) and got["n"] == U * T - 1
+
+
 def test_refresh_is_honoured_and_mlp_classes_need_full():
     m, _ = build("FMAdam")
     Xi, Xv = fm_t.contexts(U, seed=1)
