@@ -38,13 +38,16 @@ EXPORTS = ["fmx_version", "fmx_last_error_string", "fmx_set_option", "fmx_sorted
            "fmx_fm_list_online_run", "fmx_update_order",
            "fmx_fm_list_forward_q", "fmx_fm_list_step_q", "fmx_fm_list_stream_q", "fmx_alias_sample_negatives",
            "fmx_afm_list_workspace_bytes", "fmx_afm_list_forward", "fmx_afm_list_step", "fmx_afm_list_step_opt",
-           "fmx_afm_list_stream", "fmx_afm_list_online_run"]
+           "fmx_afm_list_stream", "fmx_afm_list_online_run",
+           "fmx_fm_inbatch_splits", "fmx_fm_inbatch_lse_bytes", "fmx_fm_inbatch_forward", "fmx_fm_inbatch_backward",
+           "fmx_fm_inbatch_occ_grad", "fmx_fm_inbatch_workspace_bytes", "fmx_fm_inbatch_step", "fmx_fm_inbatch_stream"]
 
 
 I64_RETURNS = ("fmx_workspace_bytes", "fmx_mlp_section_workspace_bytes", "fmx_fm_topk_workspace_bytes",
                "fmx_mlp_topk_workspace_bytes", "fmx_afm_workspace_bytes", "fmx_afm_topk_workspace_bytes",
                "fmx_fm_rank_workspace_bytes", "fmx_mlp_rank_workspace_bytes", "fmx_afm_rank_workspace_bytes",
-               "fmx_fm_list_workspace_bytes", "fmx_afm_list_workspace_bytes")   # byte counts: int64_t in include/fmx.h
+               "fmx_fm_list_workspace_bytes", "fmx_afm_list_workspace_bytes",
+               "fmx_fm_inbatch_lse_bytes", "fmx_fm_inbatch_workspace_bytes")   # byte counts: int64_t in include/fmx.h
 
 
 class FmxError(RuntimeError):
@@ -203,6 +206,14 @@ def load():
     lib.fmx_afm_list_step_opt.argtypes = [TP, HP, i32, AP, p, p, i32, i32, f32, p, i64, p, OP, p, p, p, p]
     lib.fmx_afm_list_stream.argtypes = [TP, HP, i32, AP, p, p, i32, i32, i32, f32, i32, p, i64, p, OP, p, p, p]
     lib.fmx_afm_list_online_run.argtypes = [TP, HP, i32, AP, p, p, i32, i32, p, i64, p, OP, p, p, p, p]
+    lib.fmx_fm_inbatch_splits.argtypes = [i32, i32]
+    lib.fmx_fm_inbatch_lse_bytes.argtypes = [i32, i32]
+    lib.fmx_fm_inbatch_forward.argtypes = [p, i32, p, p, i32, p, i32, i32, p, p, f32, p, i64, p, p, p]
+    lib.fmx_fm_inbatch_backward.argtypes = [p, i32, p, p, i32, p, i32, i32, p, p, f32, p, i64, p, p, p, p]
+    lib.fmx_fm_inbatch_occ_grad.argtypes = [TP, p, p, p, i32, p, p, p, p, i32, i32, p, i32, p]
+    lib.fmx_fm_inbatch_workspace_bytes.argtypes = [TP, i32, i32]
+    lib.fmx_fm_inbatch_step.argtypes = [TP, HP, i32, p, p, p, i32, p, p, i32, f32, p, i64, FP, p, p]
+    lib.fmx_fm_inbatch_stream.argtypes = [TP, HP, i32, p, p, i32, p, p, i32, i32, f32, i32, p, i64, FP, p, p]
     for name in EXPORTS:
         fn = getattr(lib, name)
         if name in I64_RETURNS:

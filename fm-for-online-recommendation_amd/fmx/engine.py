@@ -542,6 +542,62 @@ class FMEngine:
                            int(n_steps), self._list_ws.data_ptr(), self._list_ws.numel() * 4, C.byref(out), _ptr(loss_out),
                            self._stream()), hyper, n_steps)
 
+    # ---- in-batch sampled softmax: idx_d [B, F], every row's negatives are the other rows' items (fmx_fm_inbatch_*) ----
+    def _inbatch(self, B, item_fields):
+        """-> (the item fields as the C calls take them: a host int32 array, its length); grows the buffers and keeps the in-batch
+        steps' own workspace, self._inbatch_ws, sized through fmx_fm_inbatch_workspace_bytes."""
+        fields = [int(f) for f in item_fields]
+        self._ensure(B)
+        need = int(self.lib.fmx_fm_inbatch_workspace_bytes(self.table.c_struct(), int(B), len(fields)))
+        if need < 0:
+            _lib.check(need)
+        ws = getattr(self, "_inbatch_ws", None)
+        if ws is None or need > ws.numel() * 4:
+            self._inbatch_ws = torch.zeros(need // 4, dtype=torch.int32, device=self.device)     # (zero-filled once, as the header asks)
+        return (C.c_int32 * len(fields))(*fields), len(fields)
+
+    @staticmethod
+    def _keys(key, shape):
+        if key.dtype != torch.int32 or tuple(key.shape) != tuple(shape) or not key.is_contiguous():
+            raise ValueError(f"key: a contiguous int32 tensor of shape {tuple(shape)}, got {key.dtype} {tuple(key.shape)}")
+        return key.data_ptr()
+
+    def _inbatch_out(self):
+        o = _lib.FwdOut()
+        o.loss, o.error = self.loss_b.data_ptr(), self.error.data_ptr()
+        return o
+
+    def inbatch_step(self, hyper, rule, idx_d, item_fields, xv_d=None, corr=None, key=None, inv_b=None):
+        """One in-batch step on the B rows of idx_d [B, F] (fmx_fm_inbatch_step): the softmax of every row's own item against the
+        other rows' items; corr fp32 [B] (log Q of every row's item) or None, key int32 [B] (equal keys: the same item, left out
+        of each other's softmax) or None.  The mean loss lands in self.loss_out[0], the rows' losses in self.loss_b (no sync
+        here).  The table's bias is not touched."""
+        if idx_d.dim() != 2 or idx_d.shape[1] != self.table.n_fields:
+            raise ValueError(f"in-batch rows must be [B, {self.table.n_fields}], got {tuple(idx_d.shape)}")
+        B = idx_d.shape[0]
+        fields, n = self._inbatch(B, item_fields)
+        out = self._inbatch_out()
+        self._counted(self.lib.fmx_fm_inbatch_step,
+                      (self.table.c_struct(), hyper.ref(), _lib.RULES[rule], idx_d.data_ptr(), _ptr(xv_d), fields, n,
+                       None if corr is None else self._corr(corr, (B,)), None if key is None else self._keys(key, (B,)), B,
+                       1.0 / B if inv_b is None else inv_b, self._inbatch_ws.data_ptr(), self._inbatch_ws.numel() * 4, C.byref(out),
+                       self.loss_out.data_ptr(), self._stream()), hyper)
+
+    def inbatch_stream(self, hyper, rule, idx_pool, item_fields, n_steps, corr_pool=None, key_pool=None, loss_out=None):
+        """n_steps in-batch steps over a resident pool idx_pool [n_pool, B, F] (fmx_fm_inbatch_stream) with corr_pool fp32 /
+        key_pool int32 [n_pool, B] or None; loss_out [n_steps] or None."""
+        n_pool, B, F = idx_pool.shape
+        assert F == self.table.n_fields and idx_pool.is_contiguous()
+        _loss_cap(loss_out, n_steps)
+        fields, n = self._inbatch(B, item_fields)
+        out = self._inbatch_out()
+        self._counted(self.lib.fmx_fm_inbatch_stream,
+                      (self.table.c_struct(), hyper.ref(), _lib.RULES[rule], idx_pool.data_ptr(), fields, n,
+                       None if corr_pool is None else self._corr(corr_pool, (n_pool, B)),
+                       None if key_pool is None else self._keys(key_pool, (n_pool, B)), n_pool, B, 1.0 / B, int(n_steps),
+                       self._inbatch_ws.data_ptr(), self._inbatch_ws.numel() * 4, C.byref(out), _ptr(loss_out), self._stream()),
+                      hyper, n_steps)
+
     def alias_sample(self, thresh, alias, logq, n_neg, n_try, own_pos=None, seed=0, offset=0, u_base=0, excl_offsets=None,
                      excl_pos=None, U=None):
         """fmx_alias_sample_negatives on this engine's stream: n_neg popularity-sampled negatives per row from the alias table

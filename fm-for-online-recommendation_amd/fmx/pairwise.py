@@ -15,6 +15,10 @@ Popularity-sampled negatives: alias_table builds Walker's alias table of a weigh
 alias_sample draws from it on the device (fmx_alias_sample_negatives) and returns log Q of every draw, which the corrected list
 calls (fmx_fm_list_*_q: FMEngine.list_step_q / list_stream_q) subtract from the logits.  PopularityNegatives carries the table and
 its settings through the `negatives` argument.
+
+In-batch sampled softmax (fmx_fm_inbatch_*): the positives alone, [B, F]; every row's negatives are the other rows' items.
+in_batch_keys names the rows that hold the same item, which the loss leaves out of each other's softmax;
+FMEngine.inbatch_step / inbatch_stream take the rows, the keys and log Q of every row's item.
 """
 import torch
 
@@ -33,6 +37,19 @@ def n_pairs(idx_d):
     if idx_d.dim() != 2 or idx_d.shape[0] % 2 or idx_d.shape[0] < 2:
         raise ValueError(f"pair rows must be [2B, F] with B >= 1, got {tuple(idx_d.shape)}")
     return idx_d.shape[0] // 2
+
+
+def in_batch_keys(idx, item_fields):
+    """Dense keys of the item columns of idx [B, F] for the in-batch loss (fmx_fm_inbatch_step's key): int32 [B] on idx's device,
+    equal exactly where two rows hold the same item in every item field -- the inverse of torch.unique(dim=0) over those columns."""
+    fields = _item_fields(item_fields)
+    idx = torch.as_tensor(idx)
+    if idx.dim() != 2:
+        raise ValueError(f"in_batch_keys: rows [B, F], got {tuple(idx.shape)}")
+    if not all(0 <= f < idx.shape[1] for f in fields):
+        raise ValueError(f"item_fields {fields}: fields of 0..{idx.shape[1] - 1}")
+    _, inverse = torch.unique(idx[:, fields], dim=0, return_inverse=True)
+    return inverse.reshape(-1).to(torch.int32).contiguous()
 
 
 def _negatives_3d(neg_items, B, m, what="neg_items"):

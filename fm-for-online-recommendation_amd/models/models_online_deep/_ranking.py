@@ -1,6 +1,6 @@
 """Ranking training of the model classes, defined once: pairs (BPR: fmx_fm_pair_*), lists (sampled softmax: fmx_fm_list_*, and
-its log-Q corrected form fmx_fm_list_*_q), mined negatives (fmx_fm_mine_negatives) and popularity-sampled ones
-(fmx_alias_sample_negatives).
+its log-Q corrected form fmx_fm_list_*_q), in-batch negatives (fmx_fm_inbatch_*), mined negatives (fmx_fm_mine_negatives) and
+popularity-sampled ones (fmx_alias_sample_negatives).
 
 RankingTraining is a mixin of OnlineFMBase (FMAdam, the DeepFM / NFM classes) and of AFMAdam.  It holds the pure FM's public
 methods, and what the three families share under them: the rows of positives and negatives, the host predict-then-fit loop, the
@@ -291,6 +291,50 @@ class RankingTraining:
         out = self._engine.loss_out[0].clone()
         self._after_step()
         return out
+
+    # ---- in-batch sampled softmax of the pure FM (fmx_fm_inbatch_*): the other rows' items are every row's negatives -- B - 1
+    #      negatives per positive from the B rows the batch holds anyway, where fit_lists gathers 1 + n_neg rows per positive ----
+    def fit_in_batch(self, Xi, Xv, item_fields, log_q=None, mask_duplicates=True, candidates=None):
+        """One mini-batch in-batch step under the model's update rule; returns the loss tensor (the mean loss), as fit_lists
+        does.  The positives Xi / Xv [B, F] alone: row i's loss is -log softmax of score(context i, item i) among
+        score(context i, item j) over the batch's items j, the score recommend serves.  log_q: None; an array [B], log Q of every
+        row's item, subtracted from that item's logits (Yi et al. 2019: in-batch negatives arrive in proportion to their
+        popularity); or a fmx.pairwise.PopularityNegatives, whose log q is gathered at candidates.positions_of(items) --
+        `candidates` (a fmx.recommend.Candidates over the same item fields) is then required, and an item that is no candidate
+        or is never drawn takes the sampler's floor.  mask_duplicates: rows that hold the same item (fmx.pairwise.in_batch_keys)
+        are left out of each other's softmax; False: every other row is a negative.  The bias does not move."""
+        self._pure_fm_only("fit_in_batch", "list")
+        self.train()
+        idx_d, xv_d, _ = self._inputs(Xi, Xv)
+        fields = self._item_fields(item_fields)
+        corr = self._in_batch_log_q(idx_d, fields, log_q, candidates)
+        key = fmx.pairwise.in_batch_keys(idx_d, fields) if mask_duplicates else None
+        self._engine.inbatch_step(self._hyper, self.update_rule, idx_d, fields, xv_d, corr=corr, key=key)
+        out = self._engine.loss_out[0].clone()
+        self._after_step()
+        return out
+
+    def _in_batch_log_q(self, idx_d, fields, log_q, candidates):
+        """fit_in_batch's log_q -> fp32 [B] on the device, or None"""
+        B = idx_d.shape[0]
+        popular = fmx.pairwise.popularity_negatives(log_q)
+        if popular is not None:
+            if candidates is None:
+                raise ValueError(f"{self._name}.fit_in_batch: log_q=PopularityNegatives(...) needs candidates (a "
+                                 "fmx.recommend.Candidates): its log q is read at candidates.positions_of(items)")
+            if popular.N != candidates.N:
+                raise ValueError(f"{self._name}: PopularityNegatives holds {popular.N} weights for {candidates.N} candidate positions")
+            logq = popular.table(self.device)[2]
+            own = candidates.positions_of(idx_d[:, fields], fields).long()
+            listed = own >= 0
+            corr = torch.where(listed, logq[own.clamp(min=0)], torch.full((B,), float("-inf"), device=self.device))
+            return corr.clamp(min=popular.floor_logq()).contiguous()
+        if log_q is None:
+            return None
+        corr = torch.as_tensor(log_q).to(device=self.device, dtype=torch.float32).reshape(-1).contiguous()
+        if corr.numel() != B:
+            raise ValueError(f"{self._name}.fit_in_batch: log_q holds {corr.numel()} values for {B} rows")
+        return corr
 
     def run_list_experiment(self, Xi, Xv, item_fields, negatives=None, n_neg=4, candidates=None, generator=None):
         """The online protocol restated for lists: for every positive of Xi / Xv and its negatives predict the positive's rank

@@ -542,6 +542,114 @@ int fmx_fm_list_online_run(const fmx_table_t *table, const fmx_hyper_t *hyper, i
                            int32_t N, int32_t G, uint8_t *rank_out, float *logit_out, float *loss_out, int32_t *error,
                            fmx_stream_t stream);
 
+/* ---- in-batch sampled-softmax training of the pure FM: a B x B list loss over the batch's own items ----
+ * The list family above pays for every negative as a full table row.  Here the negatives of row i are the ITEMS of the batch's other
+ * rows (Yi et al. 2019): a batch of B rows gives B - 1 negatives per positive and touches B F table rows, not B G F.
+ * THE OBJECTIVE.  Split the F fields into item fields and context fields (the complement; it may be empty).  For the B rows:
+ *     S_u[i], a_u[i]   what fmx_fm_forward gives for row i with the item fields masked (index 0, value 0): out->S, out->logit
+ *                      (bias included);
+ *     S_c[j], a_c[j]   what it gives for row j with the context fields masked: out->S, out->sfirst + out->sbi (one fp32 addition)
+ * -- fmx/recommend.py: side_sums(want_bias=True / False) -- and
+ *     score(i, j) = (a_u[i] + a_c[j]) + dot,  dot = fma(S_u[i, kp-1], S_c[j, kp-1], ... fma(S_u[i, 1], S_c[j, 1], S_u[i, 0] * S_c[j, 0]))
+ * is fmx_fm_topk's score: the training logit IS the serving score, bit for bit (fmx_fm_topk's top_score for the same pair).
+ *     key  [B] int32 or null: equal keys mean the same item.  E_i = {i} + {j != i : key[j] != key[i]} is row i's eligible set: a row
+ *          that holds row i's own item (an accidental hit) is left out of row i's softmax.  key null: every j is eligible.
+ *     corr [B] fp32, finite, or null: c_ij = score(i, j) - corr[j] (one fp32 subtraction; typically log Q(item of row j)).  corr
+ *          null: c_ij = score(i, j); with corr all +0 every output is bit-identical to the null-corr call.
+ *     m_i = max over E_i of c_ij,   e_ij = exp(c_ij - m_i),   s_i = sum over E_i of e_ij,   n_i = the same sum without j = i
+ *     (accumulated on its own in the same order, as the list loss keeps the negatives' mass),
+ *     loss_i = log(s_i) - (c_ii - m_i)
+ *     g_ij = (e_ij / s_i) inv_b for eligible j != i,    g_ii = -(n_i / s_i) inv_b,    g_ij = 0 for ineligible j
+ *     gSu[i, :] = sum_j g_ij S_c[j, :],    gSc[j, :] = sum_i g_ij S_u[i, :],    gac[j] = sum_i g_ij      (fma accumulation from +0)
+ * The max is subtracted, so s_i >= 1 and the loss and the gradients are finite for all finite inputs.  There is no temperature.
+ * THE ORDER OF EVERY SUM is fixed by B alone: with splits = min(32, ceil(B / 64)) and per = ceil(B / splits), the other side's rows
+ * are cut into the ranges [p per, min(B, (p + 1) per)) (empty ranges dropped; fmx_fm_inbatch_splits returns how many remain: one up
+ * to B = 64); a range is summed in ascending order from +0 and the ranges' sums are added in range order, m_i being the maximum over
+ * all ranges.  No float atomics; two calls on the same inputs give the same bits.
+ * THE TABLE GRADIENT per occurrence, with x the occurrence's value and v its table row (x applied, fmx_fm_update_occ's occ_grad):
+ *     item field of row j:      E = x * fma(gac[j], S_c[j] - x * v, gSc[j])          (d a_c / d v = x (S_c - x v), d dot / d S_c = gSc)
+ *     context field of row i:   E = x * gSu[i]
+ * The row sum of g is zero in exact arithmetic and the step DEFINES it as zero: there is no gau term, so the bias and the context
+ * fields' first-order weights get a gradient of exactly +0 (the step hands the update the item side's masked values: x = 0 in the
+ * context columns), and an item field's first-order weight gets x gac[j].  The bias and its state stay BIT-UNCHANGED under every
+ * rule: the update's bias rule runs on the list steps' scratch (16 bytes behind the step workspace), as in fmx_fm_list_step.  A
+ * context row is touched (its V is updated) with a +0 first-order gradient; what the rules do with that: sgd, signadam
+ * (0 / (0 + eps)), ftrl (z and n unchanged) and adagrad (v += 0, step 0) leave the first-order weight bit-unchanged; adam takes the
+ * zero-gradient step of a touched row (m and v decay, the weight moves by lr_t m / (sqrt(v) + eps)).
+ * B = 1 is legal: the loss is 0, every gradient is +-0 and the weights are bit-unchanged under sgd / signadam / ftrl.
+ * Refusals, each decided on the host before any launch and naming the entry point: a null table / hyper / idx, B < 1, n_item_fields
+ * outside [1, F], an item field out of range or repeated: FMX_ERR_ARG; kp not 4 / 8 / 16 / 32 / 64, tables whose fields are pieces of
+ * index columns (field_cols / field_base), more than 512 fields: FMX_ERR_UNSUPPORTED; a null workspace FMX_ERR_ARG, one too small
+ * FMX_ERR_SHAPE; the rule against the layout and FMX_RULE_ADAM's hyper-parameters as fmx_fm_list_step checks them; B beyond the
+ * sort's width as fmx_sort_occurrences refuses it.  FMX_VERSION stays 104: probe for the symbols.
+ * Replaces (every entry below): torch.log_softmax(S_u S_c^T + a_u + a_c^T - log_q) against the diagonal plus autograd through it and
+ * through the two masked forwards; nothing in the reference, which has no listwise loss (nearest: meta_fm.py:145-169, one negative). */
+
+/* The number of ranges the sums over the other side's rows are cut into (the formula above); negative on B < 1 or a bad kp.
+ * Replaces: nothing -- it states the launch geometry of the calls that replace torch.log_softmax(S_u S_c^T + ... - log_q). */
+int32_t fmx_fm_inbatch_splits(int32_t B, int32_t kp);
+
+/* Bytes of the lse block the forward and the backward share: m [B], s [B], n [B] at its start (each padded to 256 bytes), the
+ * splits' partial results behind them.  16-byte aligned, no initialisation needed.  Negative on B < 1 or a bad kp.
+ * Replaces: the saved tensors of autograd's torch.log_softmax(S_u S_c^T + ... - log_q) node. */
+int64_t fmx_fm_inbatch_lse_bytes(int32_t B, int32_t kp);
+
+/* loss [B] = loss_i (unscaled) of the objective above from the two sides' sums (Su [B, ld_u], Sc [B, ld_c]: ld multiples of 4, >= kp,
+ * 16-byte aligned; au, ac [B]), and (m, s, n) into the lse block for the backward.  inv_b is not read (the loss is unscaled; the
+ * argument list is the backward's).  score_out [B, B] or null: score(i, j) at i B + j, uncorrected -- for tests that hold the logits
+ * against fmx_fm_topk; the step passes null and no B x B array exists.
+ * Replaces: torch.log_softmax(S_u S_c^T + a_u + a_c^T - log_q), masked, against the diagonal. */
+int fmx_fm_inbatch_forward(const float *Su, int32_t ld_u, const float *au, const float *Sc, int32_t ld_c, const float *ac, int32_t B,
+                           int32_t kp, const float *corr, const int32_t *key, float inv_b, void *lse, int64_t lse_bytes, float *loss,
+                           float *score_out, fmx_stream_t stream);
+
+/* gSu [B, kp], gSc [B, kp] (dense, 16-byte aligned) and gac [B] of inv_b sum_i loss_i from the same inputs and the lse block the
+ * forward filled; g is recomputed from (m, s, n).  One launch of two roles (a thread per context row: gSu; a thread per item row:
+ * gSc, gac) and, from two ranges on, one that adds the ranges' sums.
+ * Replaces: autograd through torch.log_softmax(S_u S_c^T + a_u + a_c^T - log_q) to the side sums. */
+int fmx_fm_inbatch_backward(const float *Su, int32_t ld_u, const float *au, const float *Sc, int32_t ld_c, const float *ac, int32_t B,
+                            int32_t kp, const float *corr, const int32_t *key, float inv_b, void *lse, int64_t lse_bytes, float *gSu,
+                            float *gSc, float *gac, fmx_stream_t stream);
+
+/* occ_grad [B, ld_occ] in fmx_fm_update_occ's layout (field f's kp floats at b ld_occ + f kp; ld_occ a multiple of 4, >=
+ * n_fields kp) from the side gradients: E as stated above; idx [B, F] and xv [B, F] (or null: 1) are the UNMASKED batch;
+ * item_fields [n_item_fields] is a HOST array.  An index outside its field gives +0.
+ * Replaces: autograd from the side sums' gradients through the two masked forwards to the embedding rows
+ * (torch.log_softmax(S_u S_c^T + ... - log_q).backward()). */
+int fmx_fm_inbatch_occ_grad(const fmx_table_t *table, const int32_t *idx, const float *xv, const int32_t *item_fields,
+                            int32_t n_item_fields, const float *gSu, const float *gSc, const float *gac, const float *Sc, int32_t ld_c,
+                            int32_t B, float *occ_grad, int32_t ld_occ, fmx_stream_t stream);
+
+/* Bytes of caller-owned device workspace an in-batch step of B rows needs: fmx_workspace_bytes(table, B), the 16 scratch bytes of the
+ * bias rule, and behind them the step's own buffers -- the masked (idx, xv) copies, both sides' sums, the side gradients, occ_grad
+ * [B, F kp] and the lse block (whose partial sums are 2 splits B kp floats: 16 MiB at B = 4,096, kp = 16).  It does not depend on
+ * n_item_fields beyond its check.  Zero-fill once before the first use, as fmx_workspace_bytes' buffer.  Negative on a bad argument.
+ * Replaces: the temporaries of torch.log_softmax(S_u S_c^T + ... - log_q) and its autograd graph. */
+int64_t fmx_fm_inbatch_workspace_bytes(const fmx_table_t *table, int32_t B, int32_t n_item_fields);
+
+/* One in-batch step on one stream (capturable in a graph, like the other one-stream steps): the step of inv_b sum_i loss_i under any
+ * rule the table's layout takes; loss_out[0] = inv_b sum_i loss_i (fmx_fm_update_occ's fixed order).  Bit-identical to this sequence
+ * of public calls: the masked copies (idx_u, xv_u: item columns 0; idx_c, xv_c: context columns 0), fmx_sort_occurrences(idx),
+ * fmx_fm_forward(idx_u, xv_u) -> S_u, a_u = logit, fmx_fm_forward(idx_c, xv_c) -> S_c, a_c = sfirst + sbi, fmx_fm_inbatch_forward,
+ * fmx_fm_inbatch_backward, fmx_fm_inbatch_occ_grad(idx, xv), fmx_fm_update_occ(xv = xv_c, dz_first = gac, occ_grad, loss_b = loss)
+ * on the table with its bias pointed at scratch.  The step builds the masked copies in the workspace and adds sfirst + sbi inside
+ * the scans (the same fp32 addition).  item_fields is a HOST array.  fwd may be null; fwd->error (or null) receives the range-error
+ * word of the sort and the forwards, fwd->loss (or null; 16-byte aligned) the per-row losses [B]; nothing else of it is read.
+ * Replaces: torch.log_softmax(S_u S_c^T + ... - log_q) on the masked forwards + loss.backward() + optimizer.step(). */
+int fmx_fm_inbatch_step(const fmx_table_t *table, const fmx_hyper_t *hyper, int32_t rule, const int32_t *idx, const float *xv,
+                        const int32_t *item_fields, int32_t n_item_fields, const float *corr, const int32_t *key, int32_t B, float inv_b,
+                        void *workspace, int64_t workspace_bytes, const fmx_fwd_out_t *fwd, float *loss_out, fmx_stream_t stream);
+
+/* n_steps in-batch steps over a device-resident pool idx_pool [n_pool, B, F] (every feature value 1) with corr_pool / key_pool
+ * [n_pool, B] or null: step s takes batch (s mod n_pool) and, under FMX_RULE_ADAM, is step hyper->step + s + 1 of the table;
+ * loss_out [n_steps] or null.  Bit-identical to n_steps calls of fmx_fm_inbatch_step: the same launches, queued from one call.
+ * n_pool < 1 and n_steps < 0 are FMX_ERR_ARG.
+ * Replaces: the training loop around torch.log_softmax(S_u S_c^T + ... - log_q) + backward + optimizer.step(). */
+int fmx_fm_inbatch_stream(const fmx_table_t *table, const fmx_hyper_t *hyper, int32_t rule, const int32_t *idx_pool,
+                          const int32_t *item_fields, int32_t n_item_fields, const float *corr_pool, const int32_t *key_pool,
+                          int32_t n_pool, int32_t B, float inv_b, int32_t n_steps, void *workspace, int64_t workspace_bytes,
+                          const fmx_fwd_out_t *fwd, float *loss_out, fmx_stream_t stream);
+
 /* ---- the small relu MLP on top of the bi-interaction vector (online steps of DeepFM / NFM and the ONN classes) ----
  * params: per layer W [out, in] row-major then b [out]; layer 0 maps k -> hidden, the others hidden -> hidden; the network's
  * contribution to the logit is the sum of the last activation (reference deepfm_adam.py:82-88: there is no output layer).
