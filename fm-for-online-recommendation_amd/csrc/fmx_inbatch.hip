@@ -15,6 +15,7 @@
 //   k_inbatch_bwd_merge<KP>     the partial sums added in split order (not launched when there is one split)
 //   k_inbatch_occ<KP>           the per-occurrence table gradients in fmx_fm_update_occ's layout
 //   k_inbatch_mask              the two masked copies of (idx, xv) the step's side forwards read
+//   fmx_inbatch_bank.inc       the cross-batch item bank (fmx_fm_inbatch_bank_*): its scans, its backward role, its merge, its push
 // The geometry (ib_geom) is a function of B alone: every sum has one fixed order, there are no float atomics.
 // The score's products commute and so does a_u + a_c, so both roles of the backward evaluate the bits the forward evaluated.
 #include "fmx_host.h"
@@ -66,6 +67,39 @@ inline IbLse ib_lse(int B, int kp, void *base) {
   l.pgac = take(part);
   l.pgu = take(partv);
   l.pgc = take(partv);
+  l.bytes = (size_t)(p - static_cast<char *>(base));
+  return l;
+}
+
+// the bank's slots [0, M): the same formula on M (include/fmx.h: fmx_fm_inbatch_bank_splits)
+struct IbBankGeom {
+  int splits_q, per_q;
+};
+inline IbBankGeom ib_bank_geom(int M) {
+  const IbGeom g = ib_geom(M);
+  return {g.splits, g.per};
+}
+
+// the lse block of a bank call: ib_lse's members, the partial results that the bank's ranges add to laid behind the batch's
+inline IbLse ib_bank_lse(int B, int M, int kp, void *base) {
+  const int sb = ib_geom(B).splits, sa = sb + ib_bank_geom(M).splits_q;
+  const size_t row = align_up((size_t)B * 4, 256);
+  char *p = static_cast<char *>(base);
+  IbLse l;
+  auto take = [&](size_t n) {
+    float *r = reinterpret_cast<float *>(p);
+    p += align_up(n, 256);
+    return r;
+  };
+  l.m = take(row);
+  l.s = take(row);
+  l.n = take(row);
+  l.pm = take((size_t)sa * B * 4);
+  l.ps = take((size_t)sa * B * 4);
+  l.pn = take((size_t)sa * B * 4);
+  l.pgac = take((size_t)sb * B * 4);
+  l.pgu = take((size_t)sa * B * kp * 4);
+  l.pgc = take((size_t)sb * B * kp * 4);
   l.bytes = (size_t)(p - static_cast<char *>(base));
   return l;
 }
@@ -358,12 +392,13 @@ __global__ __launch_bounds__(256) void k_inbatch_mask(const int32_t *idx, const 
   xv_c[t] = item ? x : 0.f;
 }
 
+#include "fmx_inbatch_bank.inc"
+
 // ---- host ----
 
 IbArgs ib_args(const float *Su, int ld_u, const float *au, const float *Sc, int ld_c, const float *ac, const float *ac2, int B, int kp,
-               const float *corr, const int32_t *key, float inv_b, void *lse) {
+               const float *corr, const int32_t *key, float inv_b, const IbLse &l) {
   const IbGeom g = ib_geom(B);
-  const IbLse l = ib_lse(B, kp, lse);
   IbArgs a;
   memset(&a, 0, sizeof(a));
   a.Su = Su;
@@ -419,6 +454,94 @@ int ib_backward_launch(IbArgs a, int kp, float *gSu, float *gSc, float *gac, hip
   return check_launch("k_inbatch_bwd");
 }
 
+// ---- the bank's launches: the batch's kernels on the longer list of ranges, the bank's between them ----
+
+IbBankArgs ib_bank_args(const float *Su, int ld_u, const float *au, const float *Sc, int ld_c, const float *ac, const float *ac2, int B,
+                        int kp, const float *corr, const int32_t *key, const fmx_item_bank_t *bank, float inv_b, void *lse) {
+  const IbBankGeom q = ib_bank_geom(bank->capacity);
+  IbBankArgs b;
+  memset(&b, 0, sizeof(b));
+  b.a = ib_args(Su, ld_u, au, Sc, ld_c, ac, ac2, B, kp, corr, key, inv_b, ib_bank_lse(B, bank->capacity, kp, lse));
+  b.splits = b.a.splits;
+  b.a.splits += q.splits_q;
+  b.bS = bank->S;
+  b.ba = bank->a;
+  b.bcorr = bank->corr;
+  b.bkey = bank->key;
+  b.state = bank->state;
+  b.M = bank->capacity;
+  b.per_q = q.per_q;
+  return b;
+}
+
+int ib_bank_forward_launch(IbBankArgs b, int kp, float *loss, float *score_out, float *bank_score_out, hipStream_t st) {
+  const IbGeom g = ib_geom(b.a.B);
+  b.a.loss = loss;
+  b.a.score_out = score_out;
+  b.bank_score_out = bank_score_out;
+  const dim3 grid(g.tiles, g.splits), grid_q(g.tiles, ib_bank_geom(b.M).splits_q);
+  with_kp(kp, [&](auto KP) {
+    hipLaunchKernelGGL((k_inbatch_scan<KP, false>), grid, dim3(IB_THREADS), 0, st, b.a);
+    hipLaunchKernelGGL((k_inbatch_bank_scan<KP, false>), grid_q, dim3(IB_THREADS), 0, st, b);
+    hipLaunchKernelGGL((k_inbatch_scan<KP, true>), grid, dim3(IB_THREADS), 0, st, b.a);
+    hipLaunchKernelGGL((k_inbatch_bank_scan<KP, true>), grid_q, dim3(IB_THREADS), 0, st, b);
+    hipLaunchKernelGGL((k_inbatch_lse<KP>), dim3((b.a.B + 255) / 256), dim3(256), 0, st, b.a);
+  });
+  return check_launch("k_inbatch_scan / k_inbatch_bank_scan / k_inbatch_lse");
+}
+
+int ib_bank_backward_launch(IbBankArgs b, int kp, float *gSu, float *gSc, float *gac, hipStream_t st) {
+  const IbGeom g = ib_geom(b.a.B);
+  b.a.gSu = gSu;
+  b.a.gSc = gSc;
+  b.a.gac = gac;
+  with_kp(kp, [&](auto KP) {
+    hipLaunchKernelGGL((k_inbatch_bwd<KP>), dim3(g.tiles, g.splits, 2), dim3(IB_THREADS), 0, st, b.a);
+    hipLaunchKernelGGL((k_inbatch_bank_bwd<KP>), dim3(g.tiles, ib_bank_geom(b.M).splits_q), dim3(IB_THREADS), 0, st, b);
+    const int64_t n = 2 * (int64_t)b.a.B * (KP / 4) + b.a.B;
+    hipLaunchKernelGGL((k_inbatch_bank_bwd_merge<KP>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, b);
+  });
+  return check_launch("k_inbatch_bwd / k_inbatch_bank_bwd");
+}
+
+int ib_bank_push_launch(const fmx_item_bank_t *bank, const float *Sc, int ld_c, const float *ac, const float *ac2, const float *corr,
+                        const int32_t *key, int B, hipStream_t st) {
+  IbPushArgs p;
+  p.bS = bank->S;
+  p.ba = bank->a;
+  p.bcorr = bank->corr;
+  p.bkey = bank->key;
+  p.state = bank->state;
+  p.Sc = Sc;
+  p.ac = ac;
+  p.ac2 = ac2;
+  p.corr = corr;
+  p.key = key;
+  p.M = bank->capacity;
+  p.kp = bank->kp;
+  p.ld_c = ld_c;
+  p.B = B;
+  hipLaunchKernelGGL(k_inbatch_bank_push, dim3(1), dim3(IB_PUSH_THREADS), 0, st, p);
+  return check_launch("k_inbatch_bank_push");
+}
+
+// what every bank call refuses; `pushes`: the call writes B slots
+int check_bank(const fmx_item_bank_t *bank, int kp, const float *corr, const int32_t *key, int B, bool pushes, const char *who) {
+  if (!bank) return fail(FMX_ERR_ARG, "%s: bank is null", who);
+  if (!bank->S || !bank->a || !bank->state) return fail(FMX_ERR_ARG, "%s: bank->S, bank->a and bank->state are required", who);
+  if (bank->capacity < 1) return fail(FMX_ERR_ARG, "%s: bank->capacity = %d must be >= 1", who, bank->capacity);
+  if (bank->kp != kp) return fail(FMX_ERR_SHAPE, "%s: bank->kp = %d, the call's kp = %d", who, bank->kp, kp);
+  if (!aligned16(bank->S)) return fail(FMX_ERR_ALIGN, "%s: bank->S must be 16-byte aligned", who);
+  if ((corr == nullptr) != (bank->corr == nullptr))
+    return fail(FMX_ERR_ARG, "%s: corr and bank->corr must both be given or both be null", who);
+  if ((key == nullptr) != (bank->key == nullptr)) return fail(FMX_ERR_ARG, "%s: key and bank->key must both be given or both be null", who);
+  if (bank->capacity > FMX_ITEM_BANK_MAX)
+    return fail(FMX_ERR_UNSUPPORTED, "%s: bank->capacity = %d: at most %d slots are taken", who, bank->capacity, FMX_ITEM_BANK_MAX);
+  if (pushes && B > bank->capacity)
+    return fail(FMX_ERR_UNSUPPORTED, "%s: B = %d rows do not fit a bank of %d slots", who, B, bank->capacity);
+  return FMX_OK;
+}
+
 int ib_occ_launch(const fmx_table_t *table, const int32_t *idx, const float *xv, const IbMask &mask, const float *gSu, const float *gSc,
                   const float *gac, const float *Sc, int ld_c, int B, float *occ, int ld_occ, hipStream_t st) {
   IbOccArgs a;
@@ -444,7 +567,7 @@ int ib_occ_launch(const fmx_table_t *table, const int32_t *idx, const float *xv,
 
 // what the calls on the two [B, kp] arrays refuse
 int check_sides(const float *Su, int ld_u, const float *au, const float *Sc, int ld_c, const float *ac, int B, int kp, const void *lse,
-                int64_t lse_bytes, const char *who) {
+                int64_t lse_bytes, const char *who, int M = 0) {  // M: the capacity of a bank call's bank (its lse block is larger)
   if (!Su || !au || !Sc || !ac) return fail(FMX_ERR_ARG, "%s: Su, au, Sc and ac are required", who);
   if (B < 1) return fail(FMX_ERR_ARG, "%s: B = %d must be >= 1", who, B);
   if (!lpr_of(kp)) return fail(FMX_ERR_UNSUPPORTED, "%s: kp = %d must be 4, 8, 16, 32 or 64", who, kp);
@@ -453,9 +576,10 @@ int check_sides(const float *Su, int ld_u, const float *au, const float *Sc, int
   if (!aligned16(Su) || !aligned16(Sc)) return fail(FMX_ERR_ALIGN, "%s: Su and Sc must be 16-byte aligned", who);
   if (!lse) return fail(FMX_ERR_ARG, "%s: null workspace", who);
   if (!aligned16(lse)) return fail(FMX_ERR_ALIGN, "%s: workspace must be 16-byte aligned", who);
-  const int64_t need = (int64_t)ib_lse(B, kp, nullptr).bytes;
+  const int64_t need = (int64_t)(M ? ib_bank_lse(B, M, kp, nullptr) : ib_lse(B, kp, nullptr)).bytes;
   if (lse_bytes < need)
-    return fail(FMX_ERR_SHAPE, "%s: workspace of %lld bytes, %lld needed (fmx_fm_inbatch_lse_bytes)", who, (long long)lse_bytes, (long long)need);
+    return fail(FMX_ERR_SHAPE, "%s: workspace of %lld bytes, %lld needed (%s)", who, (long long)lse_bytes, (long long)need,
+                M ? "fmx_fm_inbatch_bank_lse_bytes" : "fmx_fm_inbatch_lse_bytes");
   return FMX_OK;
 }
 
@@ -492,7 +616,7 @@ struct IbWorkspace {
   void *lse;
   size_t bytes;
 };
-inline IbWorkspace ib_carve(const fmx_table_t *t, int B, void *base) {
+inline IbWorkspace ib_carve(const fmx_table_t *t, int B, void *base, int M = 0) {  // M: a bank step's capacity (its lse block)
   IbWorkspace r;
   r.w = carve(t, B, base);
   char *p = static_cast<char *>(base) + align_up(r.w.bytes + LIST_BIAS_SCRATCH, 256);
@@ -516,22 +640,22 @@ inline IbWorkspace ib_carve(const fmx_table_t *t, int B, void *base) {
   r.gSc = static_cast<float *>(take(Bk));
   r.gac = static_cast<float *>(take(B1));
   r.occ = static_cast<float *>(take(BF * t->kp));
-  r.lse = take(ib_lse(B, t->kp, nullptr).bytes);
+  r.lse = take((M ? ib_bank_lse(B, M, t->kp, nullptr) : ib_lse(B, t->kp, nullptr)).bytes);
   r.bytes = (size_t)(p - static_cast<char *>(base));
   return r;
 }
 
 int check_step(const fmx_table_t *table, const fmx_hyper_t *hyper, int rule, const int32_t *idx, int B, const int32_t *item_fields,
                int n_item_fields, const void *workspace, int64_t workspace_bytes, const fmx_fwd_out_t *fwd, int64_t n_steps, IbMask *mask,
-               const char *who) {
+               const char *who, int M = 0) {
   if (!table) return fail(FMX_ERR_ARG, "%s: table is null", who);
   if (!hyper) return fail(FMX_ERR_ARG, "%s: hyper is null", who);
   if (int rc = check_fields(table, idx, B, item_fields, n_item_fields, mask, who)) return rc;
   if (int rc = check_workspace(table, B, workspace, workspace_bytes, who)) return rc;
-  const int64_t need = (int64_t)ib_carve(table, B, nullptr).bytes;
+  const int64_t need = (int64_t)ib_carve(table, B, nullptr, M).bytes;
   if (workspace_bytes < need)
-    return fail(FMX_ERR_SHAPE, "%s: workspace of %lld bytes, %lld needed (fmx_fm_inbatch_workspace_bytes)", who, (long long)workspace_bytes,
-                (long long)need);
+    return fail(FMX_ERR_SHAPE, "%s: workspace of %lld bytes, %lld needed (%s)", who, (long long)workspace_bytes, (long long)need,
+                M ? "fmx_fm_inbatch_bank_workspace_bytes" : "fmx_fm_inbatch_workspace_bytes");
   if (int rc = check_rule(table, rule)) return named(rc, who);
   if (int rc = check_adam(hyper, rule, n_steps)) return named(rc, who);
   if (int rc = check_sort_geometry(table, B)) return named(rc, who);
@@ -539,11 +663,12 @@ int check_step(const fmx_table_t *table, const fmx_hyper_t *hyper, int rule, con
   return FMX_OK;
 }
 
-// one step; the arguments have been checked.  `hs`: the step's hyper-parameters (the stream: hyper_at_step)
+// one step; the arguments have been checked.  `hs`: the step's hyper-parameters (the stream: hyper_at_step); bank: null, or the
+// item bank of fmx_fm_inbatch_bank_step: further negatives of the loss, and the step's own items pushed behind the update
 int step_launch(const fmx_table_t *table, const fmx_hyper_t *hs, int rule, const int32_t *idx, const float *xv, const IbMask &mask,
-                const float *corr, const int32_t *key, int B, float inv_b, void *workspace, const fmx_fwd_out_t *fwd, float *loss_out,
-                hipStream_t st) {
-  const IbWorkspace b = ib_carve(table, B, workspace);
+                const float *corr, const int32_t *key, const fmx_item_bank_t *bank, int B, float inv_b, void *workspace,
+                const fmx_fwd_out_t *fwd, float *loss_out, hipStream_t st) {
+  const IbWorkspace b = ib_carve(table, B, workspace, bank ? bank->capacity : 0);
   const fmx_table_t tu = list_update_table(table, workspace, b.w.bytes);
   const int F = table->n_fields, kp = table->kp;
   int32_t *error = fwd ? fwd->error : nullptr;
@@ -565,11 +690,32 @@ int step_launch(const fmx_table_t *table, const fmx_hyper_t *hs, int rule, const
   oc.error = error;
   if (int rc = forward_impl(table, hs, b.idx_u, b.xv_u, nullptr, B, FMX_LOSS_NONE, 1.f, &ou, st)) return rc;
   if (int rc = forward_impl(table, hs, b.idx_c, b.xv_c, nullptr, B, FMX_LOSS_NONE, 1.f, &oc, st)) return rc;
-  const IbArgs a = ib_args(b.Su, kp, b.au, b.Sc, kp, b.sfirst, b.sbi, B, kp, corr, key, inv_b, b.lse);  // a_c = sfirst + sbi, added in the scan
-  if (int rc = ib_forward_launch(a, kp, loss, nullptr, st)) return rc;
-  if (int rc = ib_backward_launch(a, kp, b.gSu, b.gSc, b.gac, st)) return rc;
+  if (bank) {
+    const IbBankArgs a = ib_bank_args(b.Su, kp, b.au, b.Sc, kp, b.sfirst, b.sbi, B, kp, corr, key, bank, inv_b, b.lse);
+    if (int rc = ib_bank_forward_launch(a, kp, loss, nullptr, nullptr, st)) return rc;
+    if (int rc = ib_bank_backward_launch(a, kp, b.gSu, b.gSc, b.gac, st)) return rc;
+  } else {
+    const IbArgs a = ib_args(b.Su, kp, b.au, b.Sc, kp, b.sfirst, b.sbi, B, kp, corr, key, inv_b, ib_lse(B, kp, b.lse));  // a_c = sfirst + sbi, added in the scan
+    if (int rc = ib_forward_launch(a, kp, loss, nullptr, st)) return rc;
+    if (int rc = ib_backward_launch(a, kp, b.gSu, b.gSc, b.gac, st)) return rc;
+  }
   if (int rc = ib_occ_launch(table, idx, xv, mask, b.gSu, b.gSc, b.gac, b.Sc, kp, B, b.occ, F * kp, st)) return rc;
-  return update_occ_impl(&tu, hs, rule, b.w, b.xv_c, b.gac, b.occ, F * kp, B, loss, inv_b, loss_out, st);
+  if (int rc = update_occ_impl(&tu, hs, rule, b.w, b.xv_c, b.gac, b.occ, F * kp, B, loss, inv_b, loss_out, st)) return rc;
+  return bank ? ib_bank_push_launch(bank, b.Sc, kp, b.sfirst, b.sbi, corr, key, B, st) : FMX_OK;  // (the update leaves S_c, sfirst, sbi alone)
+}
+
+// the stream's loop, shared by the plain and the bank entry
+int stream_launch(const fmx_table_t *table, const fmx_hyper_t *hyper, int rule, const int32_t *idx_pool, const IbMask &mask,
+                  const float *corr_pool, const int32_t *key_pool, const fmx_item_bank_t *bank, int n_pool, int B, float inv_b, int n_steps,
+                  void *workspace, const fmx_fwd_out_t *fwd, float *loss_out, hipStream_t st) {
+  for (int s = 0; s < n_steps; ++s) {
+    const size_t p = (size_t)(s % n_pool);
+    const fmx_hyper_t hs = hyper_at_step(hyper, rule, s);
+    if (int rc = step_launch(table, &hs, rule, idx_pool + p * B * table->n_fields, nullptr, mask, corr_pool ? corr_pool + p * B : nullptr,
+                             key_pool ? key_pool + p * B : nullptr, bank, B, inv_b, workspace, fwd, loss_out ? loss_out + s : nullptr, st))
+      return rc;
+  }
+  return FMX_OK;
 }
 
 }  // namespace
@@ -594,7 +740,7 @@ int fmx_fm_inbatch_forward(const float *Su, int32_t ld_u, const float *au, const
   const char *who = "fmx_fm_inbatch_forward";
   if (int rc = check_sides(Su, ld_u, au, Sc, ld_c, ac, B, kp, lse, lse_bytes, who)) return rc;
   if (!loss) return fail(FMX_ERR_ARG, "%s: loss is null", who);
-  const IbArgs a = ib_args(Su, ld_u, au, Sc, ld_c, ac, nullptr, B, kp, corr, key, inv_b, lse);
+  const IbArgs a = ib_args(Su, ld_u, au, Sc, ld_c, ac, nullptr, B, kp, corr, key, inv_b, ib_lse(B, kp, lse));
   return ib_forward_launch(a, kp, loss, score_out, static_cast<hipStream_t>(stream));
 }
 
@@ -605,7 +751,7 @@ int fmx_fm_inbatch_backward(const float *Su, int32_t ld_u, const float *au, cons
   if (int rc = check_sides(Su, ld_u, au, Sc, ld_c, ac, B, kp, lse, lse_bytes, who)) return rc;
   if (!gSu || !gSc || !gac) return fail(FMX_ERR_ARG, "%s: gSu, gSc and gac are required", who);
   if (!aligned16(gSu) || !aligned16(gSc)) return fail(FMX_ERR_ALIGN, "%s: gSu and gSc must be 16-byte aligned", who);
-  const IbArgs a = ib_args(Su, ld_u, au, Sc, ld_c, ac, nullptr, B, kp, corr, key, inv_b, lse);
+  const IbArgs a = ib_args(Su, ld_u, au, Sc, ld_c, ac, nullptr, B, kp, corr, key, inv_b, ib_lse(B, kp, lse));
   return ib_backward_launch(a, kp, gSu, gSc, gac, static_cast<hipStream_t>(stream));
 }
 
@@ -641,7 +787,7 @@ int fmx_fm_inbatch_step(const fmx_table_t *table, const fmx_hyper_t *hyper, int3
   IbMask mask;
   if (int rc = check_step(table, hyper, rule, idx, B, item_fields, n_item_fields, workspace, workspace_bytes, fwd, 1, &mask, who)) return rc;
   const fmx_hyper_t hs = hyper_for(hyper, rule);
-  return step_launch(table, &hs, rule, idx, xv, mask, corr, key, B, inv_b, workspace, fwd, loss_out, static_cast<hipStream_t>(stream));
+  return step_launch(table, &hs, rule, idx, xv, mask, corr, key, nullptr, B, inv_b, workspace, fwd, loss_out, static_cast<hipStream_t>(stream));
 }
 
 int fmx_fm_inbatch_stream(const fmx_table_t *table, const fmx_hyper_t *hyper, int32_t rule, const int32_t *idx_pool,
@@ -655,15 +801,107 @@ int fmx_fm_inbatch_stream(const fmx_table_t *table, const fmx_hyper_t *hyper, in
     return rc;
   if (n_pool < 1) return fail(FMX_ERR_ARG, "%s: n_pool = %d must be >= 1", who, n_pool);
   if (n_steps < 0) return fail(FMX_ERR_ARG, "%s: n_steps = %d must be >= 0", who, n_steps);
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  for (int s = 0; s < n_steps; ++s) {
-    const size_t p = (size_t)(s % n_pool);
-    const fmx_hyper_t hs = hyper_at_step(hyper, rule, s);
-    if (int rc = step_launch(table, &hs, rule, idx_pool + p * B * table->n_fields, nullptr, mask, corr_pool ? corr_pool + p * B : nullptr,
-                             key_pool ? key_pool + p * B : nullptr, B, inv_b, workspace, fwd, loss_out ? loss_out + s : nullptr, st))
-      return rc;
-  }
-  return FMX_OK;
+  return stream_launch(table, hyper, rule, idx_pool, mask, corr_pool, key_pool, nullptr, n_pool, B, inv_b, n_steps, workspace, fwd, loss_out,
+                       static_cast<hipStream_t>(stream));
+}
+
+// ---- the cross-batch item bank ----
+
+int32_t fmx_fm_inbatch_bank_splits(int32_t M, int32_t kp) {
+  const char *who = "fmx_fm_inbatch_bank_splits";
+  if (M < 1) return fail(FMX_ERR_ARG, "%s: M = %d must be >= 1", who, M);
+  if (M > FMX_ITEM_BANK_MAX) return fail(FMX_ERR_UNSUPPORTED, "%s: M = %d: at most %d slots are taken", who, M, FMX_ITEM_BANK_MAX);
+  if (!lpr_of(kp)) return fail(FMX_ERR_UNSUPPORTED, "%s: kp = %d must be 4, 8, 16, 32 or 64", who, kp);
+  return ib_bank_geom(M).splits_q;
+}
+
+int64_t fmx_fm_inbatch_bank_lse_bytes(int32_t B, int32_t M, int32_t kp) {
+  const char *who = "fmx_fm_inbatch_bank_lse_bytes";
+  if (B < 1) return fail(FMX_ERR_ARG, "%s: B = %d must be >= 1", who, B);
+  if (M < 1) return fail(FMX_ERR_ARG, "%s: M = %d must be >= 1", who, M);
+  if (M > FMX_ITEM_BANK_MAX) return fail(FMX_ERR_UNSUPPORTED, "%s: M = %d: at most %d slots are taken", who, M, FMX_ITEM_BANK_MAX);
+  if (!lpr_of(kp)) return fail(FMX_ERR_UNSUPPORTED, "%s: kp = %d must be 4, 8, 16, 32 or 64", who, kp);
+  return (int64_t)ib_bank_lse(B, M, kp, nullptr).bytes;
+}
+
+int fmx_fm_inbatch_bank_forward(const float *Su, int32_t ld_u, const float *au, const float *Sc, int32_t ld_c, const float *ac,
+                                int32_t B, int32_t kp, const float *corr, const int32_t *key, const fmx_item_bank_t *bank, float inv_b,
+                                void *lse, int64_t lse_bytes, float *loss, float *score_out, float *bank_score_out,
+                                fmx_stream_t stream) {
+  const char *who = "fmx_fm_inbatch_bank_forward";
+  if (int rc = check_bank(bank, kp, corr, key, B, false, who)) return rc;
+  if (int rc = check_sides(Su, ld_u, au, Sc, ld_c, ac, B, kp, lse, lse_bytes, who, bank->capacity)) return rc;
+  if (!loss) return fail(FMX_ERR_ARG, "%s: loss is null", who);
+  const IbBankArgs a = ib_bank_args(Su, ld_u, au, Sc, ld_c, ac, nullptr, B, kp, corr, key, bank, inv_b, lse);
+  return ib_bank_forward_launch(a, kp, loss, score_out, bank_score_out, static_cast<hipStream_t>(stream));
+}
+
+int fmx_fm_inbatch_bank_backward(const float *Su, int32_t ld_u, const float *au, const float *Sc, int32_t ld_c, const float *ac,
+                                 int32_t B, int32_t kp, const float *corr, const int32_t *key, const fmx_item_bank_t *bank,
+                                 float inv_b, void *lse, int64_t lse_bytes, float *gSu, float *gSc, float *gac, fmx_stream_t stream) {
+  const char *who = "fmx_fm_inbatch_bank_backward";
+  if (int rc = check_bank(bank, kp, corr, key, B, false, who)) return rc;
+  if (int rc = check_sides(Su, ld_u, au, Sc, ld_c, ac, B, kp, lse, lse_bytes, who, bank->capacity)) return rc;
+  if (!gSu || !gSc || !gac) return fail(FMX_ERR_ARG, "%s: gSu, gSc and gac are required", who);
+  if (!aligned16(gSu) || !aligned16(gSc)) return fail(FMX_ERR_ALIGN, "%s: gSu and gSc must be 16-byte aligned", who);
+  const IbBankArgs a = ib_bank_args(Su, ld_u, au, Sc, ld_c, ac, nullptr, B, kp, corr, key, bank, inv_b, lse);
+  return ib_bank_backward_launch(a, kp, gSu, gSc, gac, static_cast<hipStream_t>(stream));
+}
+
+int fmx_fm_inbatch_bank_push(const fmx_item_bank_t *bank, const float *Sc, int32_t ld_c, const float *ac, const float *ac2,
+                             const float *corr, const int32_t *key, int32_t B, fmx_stream_t stream) {
+  const char *who = "fmx_fm_inbatch_bank_push";
+  if (!bank) return fail(FMX_ERR_ARG, "%s: bank is null", who);
+  if (!lpr_of(bank->kp)) return fail(FMX_ERR_UNSUPPORTED, "%s: bank->kp = %d must be 4, 8, 16, 32 or 64", who, bank->kp);
+  if (B < 1) return fail(FMX_ERR_ARG, "%s: B = %d must be >= 1", who, B);
+  if (int rc = check_bank(bank, bank->kp, corr, key, B, true, who)) return rc;
+  if (!Sc || !ac) return fail(FMX_ERR_ARG, "%s: Sc and ac are required", who);
+  if (ld_c % 4 || ld_c < bank->kp) return fail(FMX_ERR_SHAPE, "%s: ld_c = %d must be a multiple of 4 and >= kp = %d", who, ld_c, bank->kp);
+  if (!aligned16(Sc)) return fail(FMX_ERR_ALIGN, "%s: Sc must be 16-byte aligned", who);
+  return ib_bank_push_launch(bank, Sc, ld_c, ac, ac2, corr, key, B, static_cast<hipStream_t>(stream));
+}
+
+int64_t fmx_fm_inbatch_bank_workspace_bytes(const fmx_table_t *table, int32_t B, int32_t M, int32_t n_item_fields) {
+  const char *who = "fmx_fm_inbatch_bank_workspace_bytes";
+  if (!table) return fail(FMX_ERR_ARG, "%s: table is null", who);
+  if (int rc = check_table(table)) return named(rc, who);
+  if (B < 1) return fail(FMX_ERR_ARG, "%s: B = %d must be >= 1", who, B);
+  if (M < 1) return fail(FMX_ERR_ARG, "%s: M = %d must be >= 1", who, M);
+  if (M > FMX_ITEM_BANK_MAX) return fail(FMX_ERR_UNSUPPORTED, "%s: M = %d: at most %d slots are taken", who, M, FMX_ITEM_BANK_MAX);
+  if (n_item_fields < 1 || n_item_fields > table->n_fields)
+    return fail(FMX_ERR_ARG, "%s: n_item_fields = %d must lie in [1, %d]", who, n_item_fields, table->n_fields);
+  return (int64_t)ib_carve(table, B, nullptr, M).bytes;
+}
+
+int fmx_fm_inbatch_bank_step(const fmx_table_t *table, const fmx_hyper_t *hyper, int32_t rule, const int32_t *idx, const float *xv,
+                             const int32_t *item_fields, int32_t n_item_fields, const float *corr, const int32_t *key,
+                             const fmx_item_bank_t *bank, int32_t B, float inv_b, void *workspace, int64_t workspace_bytes,
+                             const fmx_fwd_out_t *fwd, float *loss_out, fmx_stream_t stream) {
+  const char *who = "fmx_fm_inbatch_bank_step";
+  IbMask mask;
+  if (!table) return fail(FMX_ERR_ARG, "%s: table is null", who);
+  if (int rc = check_bank(bank, table->kp, corr, key, B, true, who)) return rc;
+  if (int rc = check_step(table, hyper, rule, idx, B, item_fields, n_item_fields, workspace, workspace_bytes, fwd, 1, &mask, who, bank->capacity))
+    return rc;
+  const fmx_hyper_t hs = hyper_for(hyper, rule);
+  return step_launch(table, &hs, rule, idx, xv, mask, corr, key, bank, B, inv_b, workspace, fwd, loss_out, static_cast<hipStream_t>(stream));
+}
+
+int fmx_fm_inbatch_bank_stream(const fmx_table_t *table, const fmx_hyper_t *hyper, int32_t rule, const int32_t *idx_pool,
+                               const int32_t *item_fields, int32_t n_item_fields, const float *corr_pool, const int32_t *key_pool,
+                               const fmx_item_bank_t *bank, int32_t n_pool, int32_t B, float inv_b, int32_t n_steps, void *workspace,
+                               int64_t workspace_bytes, const fmx_fwd_out_t *fwd, float *loss_out, fmx_stream_t stream) {
+  const char *who = "fmx_fm_inbatch_bank_stream";
+  IbMask mask;
+  if (!table) return fail(FMX_ERR_ARG, "%s: table is null", who);
+  if (int rc = check_bank(bank, table->kp, corr_pool, key_pool, B, true, who)) return rc;
+  if (int rc = check_step(table, hyper, rule, idx_pool, B, item_fields, n_item_fields, workspace, workspace_bytes, fwd,
+                          n_steps > 0 ? n_steps : 0, &mask, who, bank->capacity))
+    return rc;
+  if (n_pool < 1) return fail(FMX_ERR_ARG, "%s: n_pool = %d must be >= 1", who, n_pool);
+  if (n_steps < 0) return fail(FMX_ERR_ARG, "%s: n_steps = %d must be >= 0", who, n_steps);
+  return stream_launch(table, hyper, rule, idx_pool, mask, corr_pool, key_pool, bank, n_pool, B, inv_b, n_steps, workspace, fwd, loss_out,
+                       static_cast<hipStream_t>(stream));
 }
 
 }  // extern "C"

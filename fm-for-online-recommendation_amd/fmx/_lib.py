@@ -40,14 +40,18 @@ EXPORTS = ["fmx_version", "fmx_last_error_string", "fmx_set_option", "fmx_sorted
            "fmx_afm_list_workspace_bytes", "fmx_afm_list_forward", "fmx_afm_list_step", "fmx_afm_list_step_opt",
            "fmx_afm_list_stream", "fmx_afm_list_online_run",
            "fmx_fm_inbatch_splits", "fmx_fm_inbatch_lse_bytes", "fmx_fm_inbatch_forward", "fmx_fm_inbatch_backward",
-           "fmx_fm_inbatch_occ_grad", "fmx_fm_inbatch_workspace_bytes", "fmx_fm_inbatch_step", "fmx_fm_inbatch_stream"]
+           "fmx_fm_inbatch_occ_grad", "fmx_fm_inbatch_workspace_bytes", "fmx_fm_inbatch_step", "fmx_fm_inbatch_stream",
+           "fmx_fm_inbatch_bank_splits", "fmx_fm_inbatch_bank_lse_bytes", "fmx_fm_inbatch_bank_forward", "fmx_fm_inbatch_bank_backward",
+           "fmx_fm_inbatch_bank_push", "fmx_fm_inbatch_bank_workspace_bytes", "fmx_fm_inbatch_bank_step", "fmx_fm_inbatch_bank_stream"]
+ITEM_BANK_MAX = 1 << 20      # FMX_ITEM_BANK_MAX: the largest capacity of an item bank
 
 
 I64_RETURNS = ("fmx_workspace_bytes", "fmx_mlp_section_workspace_bytes", "fmx_fm_topk_workspace_bytes",
                "fmx_mlp_topk_workspace_bytes", "fmx_afm_workspace_bytes", "fmx_afm_topk_workspace_bytes",
                "fmx_fm_rank_workspace_bytes", "fmx_mlp_rank_workspace_bytes", "fmx_afm_rank_workspace_bytes",
                "fmx_fm_list_workspace_bytes", "fmx_afm_list_workspace_bytes",
-               "fmx_fm_inbatch_lse_bytes", "fmx_fm_inbatch_workspace_bytes")   # byte counts: int64_t in include/fmx.h
+               "fmx_fm_inbatch_lse_bytes", "fmx_fm_inbatch_workspace_bytes",
+               "fmx_fm_inbatch_bank_lse_bytes", "fmx_fm_inbatch_bank_workspace_bytes")   # byte counts: int64_t in include/fmx.h
 
 
 class FmxError(RuntimeError):
@@ -84,6 +88,11 @@ class MlpOpt(C.Structure):
 class FwdOut(C.Structure):
     _fields_ = ([(n, C.c_void_p) for n in ("S", "bi", "first", "sfirst", "sbi", "logit", "loss", "dz", "error")]
                 + [("sample_ld", C.c_int32), ("reserved", C.c_int32)])
+
+
+class ItemBank(C.Structure):
+    _fields_ = [("S", C.c_void_p), ("a", C.c_void_p), ("corr", C.c_void_p), ("key", C.c_void_p), ("state", C.c_void_p),
+                ("capacity", C.c_int32), ("kp", C.c_int32)]
 
 
 class Afm(C.Structure):
@@ -214,6 +223,15 @@ def load():
     lib.fmx_fm_inbatch_workspace_bytes.argtypes = [TP, i32, i32]
     lib.fmx_fm_inbatch_step.argtypes = [TP, HP, i32, p, p, p, i32, p, p, i32, f32, p, i64, FP, p, p]
     lib.fmx_fm_inbatch_stream.argtypes = [TP, HP, i32, p, p, i32, p, p, i32, i32, f32, i32, p, i64, FP, p, p]
+    BP = C.POINTER(ItemBank)
+    lib.fmx_fm_inbatch_bank_splits.argtypes = [i32, i32]
+    lib.fmx_fm_inbatch_bank_lse_bytes.argtypes = [i32, i32, i32]
+    lib.fmx_fm_inbatch_bank_forward.argtypes = [p, i32, p, p, i32, p, i32, i32, p, p, BP, f32, p, i64, p, p, p, p]
+    lib.fmx_fm_inbatch_bank_backward.argtypes = [p, i32, p, p, i32, p, i32, i32, p, p, BP, f32, p, i64, p, p, p, p]
+    lib.fmx_fm_inbatch_bank_push.argtypes = [BP, p, i32, p, p, p, p, i32, p]
+    lib.fmx_fm_inbatch_bank_workspace_bytes.argtypes = [TP, i32, i32, i32]
+    lib.fmx_fm_inbatch_bank_step.argtypes = [TP, HP, i32, p, p, p, i32, p, p, BP, i32, f32, p, i64, FP, p, p]
+    lib.fmx_fm_inbatch_bank_stream.argtypes = [TP, HP, i32, p, p, i32, p, p, BP, i32, i32, f32, i32, p, i64, FP, p, p]
     for name in EXPORTS:
         fn = getattr(lib, name)
         if name in I64_RETURNS:

@@ -543,12 +543,16 @@ class FMEngine:
                            self._stream()), hyper, n_steps)
 
     # ---- in-batch sampled softmax: idx_d [B, F], every row's negatives are the other rows' items (fmx_fm_inbatch_*) ----
-    def _inbatch(self, B, item_fields):
+    def _inbatch(self, B, item_fields, bank=None):
         """-> (the item fields as the C calls take them: a host int32 array, its length); grows the buffers and keeps the in-batch
-        steps' own workspace, self._inbatch_ws, sized through fmx_fm_inbatch_workspace_bytes."""
+        steps' own workspace, self._inbatch_ws, sized through fmx_fm_inbatch_workspace_bytes (with a bank:
+        fmx_fm_inbatch_bank_workspace_bytes, which is never smaller)."""
         fields = [int(f) for f in item_fields]
         self._ensure(B)
-        need = int(self.lib.fmx_fm_inbatch_workspace_bytes(self.table.c_struct(), int(B), len(fields)))
+        if bank is None:
+            need = int(self.lib.fmx_fm_inbatch_workspace_bytes(self.table.c_struct(), int(B), len(fields)))
+        else:
+            need = int(self.lib.fmx_fm_inbatch_bank_workspace_bytes(self.table.c_struct(), int(B), int(bank.capacity), len(fields)))
         if need < 0:
             _lib.check(need)
         ws = getattr(self, "_inbatch_ws", None)
@@ -597,6 +601,36 @@ class FMEngine:
                        None if key_pool is None else self._keys(key_pool, (n_pool, B)), n_pool, B, 1.0 / B, int(n_steps),
                        self._inbatch_ws.data_ptr(), self._inbatch_ws.numel() * 4, C.byref(out), _ptr(loss_out), self._stream()),
                       hyper, n_steps)
+
+    def inbatch_bank_step(self, hyper, rule, idx_d, item_fields, bank, xv_d=None, corr=None, key=None, inv_b=None):
+        """inbatch_step with a fmx.pairwise.ItemBank (fmx_fm_inbatch_bank_step): the bank's items are further negatives of every
+        row, and the step's own items are pushed into it behind the update.  corr / key are given exactly when the bank keeps
+        them (the C call refuses a mismatch); the keys must mean the same item in every batch (fmx.pairwise.item_keys)."""
+        if idx_d.dim() != 2 or idx_d.shape[1] != self.table.n_fields:
+            raise ValueError(f"in-batch rows must be [B, {self.table.n_fields}], got {tuple(idx_d.shape)}")
+        B = idx_d.shape[0]
+        fields, n = self._inbatch(B, item_fields, bank)
+        out = self._inbatch_out()
+        self._counted(self.lib.fmx_fm_inbatch_bank_step,
+                      (self.table.c_struct(), hyper.ref(), _lib.RULES[rule], idx_d.data_ptr(), _ptr(xv_d), fields, n,
+                       None if corr is None else self._corr(corr, (B,)), None if key is None else self._keys(key, (B,)),
+                       bank.c_struct(), B, 1.0 / B if inv_b is None else inv_b, self._inbatch_ws.data_ptr(),
+                       self._inbatch_ws.numel() * 4, C.byref(out), self.loss_out.data_ptr(), self._stream()), hyper)
+
+    def inbatch_bank_stream(self, hyper, rule, idx_pool, item_fields, n_steps, bank, corr_pool=None, key_pool=None, loss_out=None):
+        """inbatch_stream with a fmx.pairwise.ItemBank (fmx_fm_inbatch_bank_stream): every step reads the bank and pushes its
+        items."""
+        n_pool, B, F = idx_pool.shape
+        assert F == self.table.n_fields and idx_pool.is_contiguous()
+        _loss_cap(loss_out, n_steps)
+        fields, n = self._inbatch(B, item_fields, bank)
+        out = self._inbatch_out()
+        self._counted(self.lib.fmx_fm_inbatch_bank_stream,
+                      (self.table.c_struct(), hyper.ref(), _lib.RULES[rule], idx_pool.data_ptr(), fields, n,
+                       None if corr_pool is None else self._corr(corr_pool, (n_pool, B)),
+                       None if key_pool is None else self._keys(key_pool, (n_pool, B)), bank.c_struct(), n_pool, B, 1.0 / B,
+                       int(n_steps), self._inbatch_ws.data_ptr(), self._inbatch_ws.numel() * 4, C.byref(out), _ptr(loss_out),
+                       self._stream()), hyper, n_steps)
 
     def alias_sample(self, thresh, alias, logq, n_neg, n_try, own_pos=None, seed=0, offset=0, u_base=0, excl_offsets=None,
                      excl_pos=None, U=None):

@@ -19,7 +19,13 @@ its settings through the `negatives` argument.
 In-batch sampled softmax (fmx_fm_inbatch_*): the positives alone, [B, F]; every row's negatives are the other rows' items.
 in_batch_keys names the rows that hold the same item, which the loss leaves out of each other's softmax;
 FMEngine.inbatch_step / inbatch_stream take the rows, the keys and log Q of every row's item.
+
+The cross-batch item bank (fmx_fm_inbatch_bank_*): ItemBank keeps the items of earlier batches on the device as further
+negatives of every later row; FMEngine.inbatch_bank_step / inbatch_bank_stream take it, item_keys gives the keys that hold
+across batches.
 """
+import ctypes as C
+
 import torch
 
 from . import _lib
@@ -50,6 +56,77 @@ def in_batch_keys(idx, item_fields):
         raise ValueError(f"item_fields {fields}: fields of 0..{idx.shape[1] - 1}")
     _, inverse = torch.unique(idx[:, fields], dim=0, return_inverse=True)
     return inverse.reshape(-1).to(torch.int32).contiguous()
+
+
+def item_keys(idx, item_fields, field_sizes):
+    """Keys of the item columns of idx [B, F] that mean the same item in EVERY batch (in_batch_keys' are dense per batch): the
+    mixed-radix number of the item fields' indices over field_sizes [F], int32 [B] on idx's device.  What a keyed ItemBank needs:
+    a banked item is compared with the items of later batches."""
+    fields = _item_fields(item_fields)
+    idx = torch.as_tensor(idx)
+    if idx.dim() != 2:
+        raise ValueError(f"item_keys: rows [B, F], got {tuple(idx.shape)}")
+    if not all(0 <= f < idx.shape[1] for f in fields):
+        raise ValueError(f"item_fields {fields}: fields of 0..{idx.shape[1] - 1}")
+    total = 1
+    for f in fields:
+        total *= int(field_sizes[f])
+    if total >= 2 ** 31:
+        raise ValueError(f"item_keys: the item fields {fields} span {total} combinations, more than an int32 key holds")
+    key = torch.zeros(idx.shape[0], dtype=torch.int64, device=idx.device)
+    for f in fields:
+        key = key * int(field_sizes[f]) + idx[:, f].long()
+    return key.to(torch.int32).contiguous()
+
+
+class ItemBank:
+    """The cross-batch item bank of fmx_fm_inbatch_bank_* (include/fmx.h: fmx_item_bank_t): a device-resident ring of `capacity`
+    slots that keeps the item-side sums (S_c, a_c) of earlier in-batch steps, which every later row takes as further negatives.
+    It owns the arrays and the zeroed state (head, count).  keyed: it keeps item keys (the steps on it must pass keys that mean
+    the same item in every batch: item_keys); corrected: it keeps log Q of every item (the steps must pass corr).
+    The values are those of the weights when the item was pushed: they go stale as training goes on, a ring of a few batches
+    bounds their age.  A captured step advances the bank on every replay; a second pass over the same data meets its own items
+    as negatives unless keys mask them."""
+
+    def __init__(self, capacity, kp, device, keyed=True, corrected=True):
+        capacity, kp = int(capacity), int(kp)
+        if capacity < 1 or capacity > _lib.ITEM_BANK_MAX:
+            raise ValueError(f"ItemBank: capacity = {capacity} must lie in [1, {_lib.ITEM_BANK_MAX}]")
+        if kp not in (4, 8, 16, 32, 64):
+            raise ValueError(f"ItemBank: kp = {kp} must be the table's padded k: 4, 8, 16, 32 or 64")
+        self.capacity, self.kp, self.device = capacity, kp, torch.device(device)
+        self.S = torch.zeros((capacity, kp), dtype=torch.float32, device=device)
+        self.a = torch.zeros(capacity, dtype=torch.float32, device=device)
+        self.corr = torch.zeros(capacity, dtype=torch.float32, device=device) if corrected else None
+        self.key = torch.zeros(capacity, dtype=torch.int32, device=device) if keyed else None
+        self.state = torch.zeros(2, dtype=torch.int32, device=device)
+        self._c = _lib.ItemBank()
+        self._c.S, self._c.a, self._c.state = self.S.data_ptr(), self.a.data_ptr(), self.state.data_ptr()
+        self._c.corr = None if self.corr is None else self.corr.data_ptr()
+        self._c.key = None if self.key is None else self.key.data_ptr()
+        self._c.capacity, self._c.kp = capacity, kp
+
+    @property
+    def keyed(self):
+        return self.key is not None
+
+    @property
+    def corrected(self):
+        return self.corr is not None
+
+    def clear(self):
+        """An empty bank again (the slots keep their bytes: a slot >= count is never read)"""
+        self.state.zero_()
+
+    def head(self):
+        return int(self.state[0].item())
+
+    def count(self):
+        """The number of valid slots: a host read (a sync), for tests and users"""
+        return int(self.state[1].item())
+
+    def c_struct(self):
+        return C.byref(self._c)
 
 
 def _negatives_3d(neg_items, B, m, what="neg_items"):

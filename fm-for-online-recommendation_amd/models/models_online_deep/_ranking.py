@@ -303,13 +303,39 @@ class RankingTraining:
         `candidates` (a fmx.recommend.Candidates over the same item fields) is then required, and an item that is no candidate
         or is never drawn takes the sampler's floor.  mask_duplicates: rows that hold the same item (fmx.pairwise.in_batch_keys)
         are left out of each other's softmax; False: every other row is a negative.  The bias does not move."""
-        self._pure_fm_only("fit_in_batch", "list")
+        return self._fit_in_batch("fit_in_batch", Xi, Xv, item_fields, log_q, mask_duplicates, candidates, None)
+
+    def fit_in_batch_bank(self, Xi, Xv, item_fields, log_q=None, mask_duplicates=True, candidates=None, bank=None):
+        """fit_in_batch with a cross-batch item bank.  bank: a fmx.pairwise.ItemBank (fmx_fm_inbatch_bank_step): the items of
+        earlier batches it keeps are further negatives of every row, and this batch's items are pushed into it behind the
+        update; None is fit_in_batch, bit for bit.  The bank must agree with the other arguments: keyed exactly when
+        mask_duplicates (the keys are then fmx.pairwise.item_keys', which hold across batches), corrected exactly when log_q is
+        given; a mismatch is a ValueError that names the argument."""
+        return self._fit_in_batch("fit_in_batch_bank", Xi, Xv, item_fields, log_q, mask_duplicates, candidates, bank)
+
+    def _fit_in_batch(self, method, Xi, Xv, item_fields, log_q, mask_duplicates, candidates, bank):
+        self._pure_fm_only(method, "list")
         self.train()
+        if bank is not None:
+            if not isinstance(bank, fmx.pairwise.ItemBank):
+                raise ValueError(f"{self._name}.{method}: bank must be a fmx.pairwise.ItemBank or None, got {type(bank).__name__}")
+            if bank.keyed != bool(mask_duplicates):
+                raise ValueError(f"{self._name}.{method}: mask_duplicates={bool(mask_duplicates)} needs a bank with "
+                                 f"keyed={bool(mask_duplicates)}; bank.keyed is {bank.keyed}")
+            if bank.corrected != (log_q is not None):
+                raise ValueError(f"{self._name}.{method}: log_q {'given' if log_q is not None else 'None'} needs a bank with "
+                                 f"corrected={log_q is not None}; bank.corrected is {bank.corrected}")
+            if bank.kp != self._table.kp:
+                raise ValueError(f"{self._name}.{method}: bank.kp = {bank.kp}, the table's kp = {self._table.kp}")
         idx_d, xv_d, _ = self._inputs(Xi, Xv)
         fields = self._item_fields(item_fields)
         corr = self._in_batch_log_q(idx_d, fields, log_q, candidates)
-        key = fmx.pairwise.in_batch_keys(idx_d, fields) if mask_duplicates else None
-        self._engine.inbatch_step(self._hyper, self.update_rule, idx_d, fields, xv_d, corr=corr, key=key)
+        if bank is None:
+            key = fmx.pairwise.in_batch_keys(idx_d, fields) if mask_duplicates else None
+            self._engine.inbatch_step(self._hyper, self.update_rule, idx_d, fields, xv_d, corr=corr, key=key)
+        else:
+            key = fmx.pairwise.item_keys(idx_d, fields, np.diff(np.asarray(self._table.offsets_host))) if mask_duplicates else None
+            self._engine.inbatch_bank_step(self._hyper, self.update_rule, idx_d, fields, bank, xv_d, corr=corr, key=key)
         out = self._engine.loss_out[0].clone()
         self._after_step()
         return out

@@ -650,6 +650,104 @@ int fmx_fm_inbatch_stream(const fmx_table_t *table, const fmx_hyper_t *hyper, in
                           int32_t n_pool, int32_t B, float inv_b, int32_t n_steps, void *workspace, int64_t workspace_bytes,
                           const fmx_fwd_out_t *fwd, float *loss_out, fmx_stream_t stream);
 
+/* ---- a cross-batch item bank for the in-batch loss: the items of earlier batches as further negatives ----
+ * (Wang et al. 2021, "Cross-Batch Negative Sampling".)  The item-side sums (S_c, a_c) an in-batch step computes anyway are kept in a
+ * device-resident ring of M slots, and every later row takes them as further negatives: one more scan over two small arrays, no
+ * table row, no sort entry, no update.  The plain objective above stands as written; this is added to it.
+ * THE BANK: caller-owned device memory and two host ints.  state[0] (head) is the next slot to write, in [0, M); state[1] (count)
+ * the number of valid slots, in [0, M]; the valid slots are always the prefix [0, count) (the ring fills upwards from slot 0 and
+ * is full from the first wrap on); a zeroed state is an empty bank.  The state lives on the device: a step is one-stream, reads
+ * nothing back and can be captured in a graph (every replay advances the bank). */
+typedef struct fmx_item_bank {
+  float *S;          /* [capacity, kp] fp32, dense, 16-byte aligned: the kept items' S_c */
+  float *a;          /* [capacity] fp32: the kept items' a_c */
+  float *corr;       /* [capacity] fp32 or null: log Q of each kept item */
+  int32_t *key;      /* [capacity] int32 or null: item keys, equal keys meaning the same item */
+  int32_t *state;    /* device int32 [2]: head, count */
+  int32_t capacity;  /* M >= 1, at most FMX_ITEM_BANK_MAX */
+  int32_t kp;        /* the padded k, equal to the table's */
+} fmx_item_bank_t;
+#define FMX_ITEM_BANK_MAX 1048576 /* the largest capacity taken (2^20 slots) */
+/* THE LOSS.  Row i's eligible set is E_i of the in-batch section plus Q_i = every slot q < count with key[i] != bank.key[q] (no
+ * keys: every q < count).  c_iq = score(i, q) - bank.corr[q] with score(i, q) = (a_u[i] + bank.a[q]) + dot, the same product chain:
+ * a banked item scores bit for bit what it scored in the batch it came from when the context side is the same.
+ *     m_i = max over E_i and Q_i;   s_i and n_i also sum e_iq = exp(c_iq - m_i) over Q_i (every bank item is a negative: it counts
+ *     in n);   loss_i and g_ii = -(n_i / s_i) inv_b keep their form;   g_iq = (e_iq / s_i) inv_b.
+ * GRADIENTS.  Bank items take none (stale values, as in the paper):
+ *     gSu[i] = sum_j g_ij S_c[j] + sum_q g_iq bank.S[q];   gSc and gac keep their definitions and change only through (m, s, n);
+ * there is still no gau term: the bias and its state stay bit-unchanged under every rule.
+ * THE ORDER OF EVERY SUM.  The batch's ranges come first, exactly as in the plain calls; the bank's follow: the slots [0, M) are cut
+ * into splits_q = min(32, ceil(M / 64)) ranges of per_q = ceil(M / splits_q) slots (empty ranges dropped; fmx_fm_inbatch_bank_splits
+ * returns how many remain) -- a function of M alone, not of count: a slot >= count is simply ineligible (and is not read).  Each
+ * range ascends from +0 and the ranges are added in order behind the batch's; the maximum is taken over all ranges of both kinds
+ * before any exponential.  No float atomics; two runs give the same bits.  With count = 0 every output of a bank call is
+ * bit-identical to the plain call's (an empty range gives -inf to the maximum and +0 to a sum).
+ * THE PUSH.  After the scans and the backward have read the bank a step writes its own B items to the slots (head + j) mod M,
+ * j = 0 .. B - 1: S_c[j], a_c[j] as the scans used it, corr[j], key[j] -- the values of the weights BEFORE the update -- then
+ * head <- (head + B) mod M, count <- min(M, count + B).  The push is a launch of its own behind the last reader of the bank.
+ * Refusals, each decided on the host before any launch and naming the entry point: a null bank, S, a or state, capacity < 1:
+ * FMX_ERR_ARG; bank->kp != the call's kp: FMX_ERR_SHAPE; S not 16-byte aligned: FMX_ERR_ALIGN; the call's corr null while bank->corr
+ * is not, or the reverse, and the same for key: FMX_ERR_ARG; capacity > FMX_ITEM_BANK_MAX: FMX_ERR_UNSUPPORTED; in the calls that
+ * push (push, step, stream) B > capacity: FMX_ERR_UNSUPPORTED; and whatever the plain call refuses, as it refuses it.
+ * Replaces (every entry below): torch.log_softmax(cat([S_u S_c^T, S_u bank.S^T], 1) + a_u + cat([a_c, bank.a])^T - cat([log_q,
+ * bank.corr])) against the diagonal, the bank detached, plus autograd through it; nothing in the reference. */
+
+/* The number of ranges the bank's slots are cut into (the formula above); negative on M < 1, M > FMX_ITEM_BANK_MAX or a bad kp.
+ * Replaces: nothing -- it states the launch geometry of the calls that replace the torch.log_softmax(cat(...)) above. */
+int32_t fmx_fm_inbatch_bank_splits(int32_t M, int32_t kp);
+
+/* Bytes of the lse block of the bank calls: m, s, n [B] at its start as in fmx_fm_inbatch_lse_bytes, the partial results of the
+ * batch's and the bank's ranges behind them.  Negative on a bad argument.
+ * Replaces: the saved tensors of autograd's torch.log_softmax(cat(...)) node. */
+int64_t fmx_fm_inbatch_bank_lse_bytes(int32_t B, int32_t M, int32_t kp);
+
+/* fmx_fm_inbatch_forward with the bank's slots as further negatives: loss [B], (m, s, n) into the lse block.  The bank is read only.
+ * score_out [B, B] or null as there; bank_score_out [B, M] or null: the uncorrected score(i, q) at i M + q for q < count, slots
+ * >= count left unwritten -- for tests.  B may exceed the capacity here.
+ * Replaces: torch.log_softmax(cat([S_u S_c^T, S_u bank.S^T], 1) + ...) against the diagonal, the bank detached. */
+int fmx_fm_inbatch_bank_forward(const float *Su, int32_t ld_u, const float *au, const float *Sc, int32_t ld_c, const float *ac,
+                                int32_t B, int32_t kp, const float *corr, const int32_t *key, const fmx_item_bank_t *bank, float inv_b,
+                                void *lse, int64_t lse_bytes, float *loss, float *score_out, float *bank_score_out,
+                                fmx_stream_t stream);
+
+/* fmx_fm_inbatch_backward from the lse block fmx_fm_inbatch_bank_forward filled: gSu with the bank's term, gSc and gac.  The item
+ * role runs as in the plain call on the merged (m, s, n); one more launch walks the bank for gSu and one adds the ranges' sums.
+ * Replaces: autograd through torch.log_softmax(cat([S_u S_c^T, S_u bank.S^T], 1) + ...) to the side sums, the bank detached. */
+int fmx_fm_inbatch_bank_backward(const float *Su, int32_t ld_u, const float *au, const float *Sc, int32_t ld_c, const float *ac,
+                                 int32_t B, int32_t kp, const float *corr, const int32_t *key, const fmx_item_bank_t *bank,
+                                 float inv_b, void *lse, int64_t lse_bytes, float *gSu, float *gSc, float *gac, fmx_stream_t stream);
+
+/* The push on its own: Sc [B, ld_c], a_c = ac (+ ac2 when it is not null: one fp32 addition), corr and key [B] (each null exactly
+ * when the bank's is) to the slots (head + j) mod M; then the state advances.  One workgroup: its threads read the state, meet at
+ * a barrier, one of them writes the new state and all of them the slots -- no second launch and no race.
+ * Replaces: the torch.cat / index_copy_ of a cross-batch negative queue (torch.log_softmax(cat(...))'s bank side). */
+int fmx_fm_inbatch_bank_push(const fmx_item_bank_t *bank, const float *Sc, int32_t ld_c, const float *ac, const float *ac2,
+                             const float *corr, const int32_t *key, int32_t B, fmx_stream_t stream);
+
+/* Bytes of a bank step's workspace: fmx_fm_inbatch_workspace_bytes' layout with the bank calls' lse block in the place of the
+ * plain one.  Zero-fill once before the first use.  Negative on a bad argument.
+ * Replaces: the temporaries of torch.log_softmax(cat(...)) and its autograd graph. */
+int64_t fmx_fm_inbatch_bank_workspace_bytes(const fmx_table_t *table, int32_t B, int32_t M, int32_t n_item_fields);
+
+/* fmx_fm_inbatch_step with the bank: one stream, capturable.  Bit-identical to this sequence of public calls: the masked copies,
+ * fmx_sort_occurrences, the two fmx_fm_forward calls, fmx_fm_inbatch_bank_forward, fmx_fm_inbatch_bank_backward,
+ * fmx_fm_inbatch_occ_grad, fmx_fm_update_occ on the table with its bias pointed at scratch, fmx_fm_inbatch_bank_push(S_c, sfirst,
+ * sbi, corr, key).  With count = 0 the table, the moments, loss_out, the per-row losses and the error word are fmx_fm_inbatch_step's
+ * bit for bit.  Four launches more than the plain step from two batch ranges on (B >= 65), five up to B = 64.
+ * Replaces: torch.log_softmax(cat(...)) on the masked forwards + loss.backward() + optimizer.step() + the queue's update. */
+int fmx_fm_inbatch_bank_step(const fmx_table_t *table, const fmx_hyper_t *hyper, int32_t rule, const int32_t *idx, const float *xv,
+                             const int32_t *item_fields, int32_t n_item_fields, const float *corr, const int32_t *key,
+                             const fmx_item_bank_t *bank, int32_t B, float inv_b, void *workspace, int64_t workspace_bytes,
+                             const fmx_fwd_out_t *fwd, float *loss_out, fmx_stream_t stream);
+
+/* fmx_fm_inbatch_stream with the bank: bit-identical to n_steps calls of fmx_fm_inbatch_bank_step, the bank's contents and state at
+ * the end included.
+ * Replaces: the training loop around torch.log_softmax(cat(...)) + backward + optimizer.step() + the queue's update. */
+int fmx_fm_inbatch_bank_stream(const fmx_table_t *table, const fmx_hyper_t *hyper, int32_t rule, const int32_t *idx_pool,
+                               const int32_t *item_fields, int32_t n_item_fields, const float *corr_pool, const int32_t *key_pool,
+                               const fmx_item_bank_t *bank, int32_t n_pool, int32_t B, float inv_b, int32_t n_steps, void *workspace,
+                               int64_t workspace_bytes, const fmx_fwd_out_t *fwd, float *loss_out, fmx_stream_t stream);
+
 /* ---- the small relu MLP on top of the bi-interaction vector (online steps of DeepFM / NFM and the ONN classes) ----
  * params: per layer W [out, in] row-major then b [out]; layer 0 maps k -> hidden, the others hidden -> hidden; the network's
  * contribution to the logit is the sum of the last activation (reference deepfm_adam.py:82-88: there is no output layer).
