@@ -85,6 +85,13 @@ int afm_pair_online_launch(const fmx_table_t *table, const fmx_hyper_t *hyper, i
 // fmx_list.inc has checked the arguments)
 int list_online_launch(const fmx_table_t *table, const fmx_hyper_t *hyper, int32_t rule, const int32_t *idx, const float *xv, int32_t N,
                        int32_t G, uint8_t *rank_out, float *logit_out, float *loss_out, int32_t *error, hipStream_t st);
+// fmx_mlp.hip (fmx_mlp_list.inc): fmx_mlp_list_section without its last launch -- `deferred` receives the arguments of the reduction
+// (mlp_section_deferred_reduce's contract; null: launched here).  B_lists lists of G rows, row G i the positive; corr [B_lists G] or
+// null.  It checks its own arguments, workspace_bytes included, in front of any launch, and never launches k_mlp_chain
+int mlp_list_section_deferred_reduce(const fmx_mlp_t *mlp, const float *bi, int32_t ld_bi, const float *base, const float *corr,
+                                     int32_t B_lists, int32_t G, float inv_b, void *workspace, int64_t workspace_bytes, float *logit_out,
+                                     float *dz_out, float *gbi_out, int32_t ld_gbi, float *grads, float lr_apply, float *loss_out,
+                                     hipStream_t st, MlpReduceArgs *deferred, const char *who);
 
 }  // namespace fmxd
 

@@ -1500,6 +1500,74 @@ int fmx_deepfm_pair_stream(const fmx_table_t *table, const fmx_hyper_t *hyper, i
                who);
 }
 
+// The list form of fmx_deepfm_pair_stream: B_lists lists of G rows are B_lists G rows of the pool (row G i the positive of list i,
+// then its G - 1 negatives), the table forward has no loss, the MLP section evaluates the list loss (fmx_mlp_list_section's body,
+// mlp_list_section_deferred_reduce in fmx_mlp_list.inc: the separate-GEMM form with k_mlp_list_loss at the loss site, never
+// k_mlp_chain), and sort and update are the pointwise stream's on those rows -- with the update on list_update_table's copy of
+// the table, so that the bias rule runs on the LIST_BIAS_SCRATCH bytes behind the step workspace (fmx_list.inc's header says
+// why; fmx_fm_list_step does the same).  The section's reduction RIDES in the table update's launch (k_fm_update_rider), as in
+// the streams above.  corr_pool [n_pool, B_lists G] or null rides where the pointwise stream's labels ride (pool_loop's y_pool).
+// A function of its own beside deepfm_stream_impl, whose inline checks of the network and opt are repeated here; the refusals of
+// the fmx_fm_list_* family come first.
+int fmx_deepfm_list_stream(const fmx_table_t *table, const fmx_hyper_t *hyper, int32_t rule, const fmx_mlp_t *mlp, int32_t fm_term,
+                           const int32_t *idx_pool, int32_t n_pool, int32_t B_lists, int32_t G, const float *corr_pool, float inv_b,
+                           int32_t n_steps, void *workspace, int64_t workspace_bytes, void *mlp_workspace, int64_t mlp_workspace_bytes,
+                           const fmx_fwd_out_t *fwd, float *dz, float *gbi, float *grads, float lr_mlp, const fmx_mlp_opt_t *opt,
+                           float *loss_out, fmx_stream_t stream) {
+  const char *who = "fmx_deepfm_list_stream";
+  int32_t B = 0;  // the rows of a step
+  if (int rc = check_list_args(table, hyper, idx_pool, B_lists, G, &B, who)) return rc;
+  if (int rc = check_sort_geometry(table, B)) return named(rc, who);
+  if (int rc = check_pool_steps(n_pool, n_steps, who)) return rc;
+  if (!opt && adaptive_rule(rule)) return refuse_adaptive(rule, who);
+  if (int rc = check_rule(table, rule)) return named(rc, who);
+  if (!mlp || !workspace || !mlp_workspace || !fwd || !fwd->S || !fwd->bi || !fwd->logit || !dz || !gbi || !grads)
+    return fail(FMX_ERR_ARG, "%s: null argument (fwd needs S, bi and logit)", who);
+  if (fwd->sample_ld != 0) return fail(FMX_ERR_ARG, "%s: dense forward outputs only (sample_ld = 0)", who);
+  // NFM: k_first_plus_bias reads bias[0], the bias weight of the weights and the moments layouts
+  if (!fm_term && (!fwd->sfirst || (opt ? table->layout == FMX_LAYOUT_FTRL : table->layout != FMX_LAYOUT_WEIGHTS)))
+    return fail(FMX_ERR_UNSUPPORTED, "%s: fm_term = 0 (NFM) needs fwd->sfirst and a table in the weights%s layout", who, opt ? " or the moments" : "");
+  if (opt) {
+    if (int rc = check_adam(hyper, rule, n_steps)) return named(rc, who);
+    if (int rc = mlp_opt_check(mlp, B, mlp_workspace, mlp_workspace_bytes, grads, opt, n_steps, who)) return rc;
+  } else {  // the size of the network's workspace is checked under either rule
+    const int64_t need = fmx_mlp_section_workspace_bytes(mlp, B);
+    if (need < 0) return fail(FMX_ERR_UNSUPPORTED, "%s: needs 1 <= layers <= %d, k >= 1, hidden >= 1", who, MLP_BIG_MAX_L);
+    if (mlp_workspace_bytes < need)
+      return fail(FMX_ERR_SHAPE, "%s: the MLP workspace holds %lld bytes, fmx_mlp_section_workspace_bytes asks for %lld", who,
+                  (long long)mlp_workspace_bytes, (long long)need);
+  }
+  if (mlp->k > table->kp) return fail(FMX_ERR_SHAPE, "%s: the MLP reads k=%d columns of a bi of kp=%d", who, mlp->k, table->kp);
+  if (!aligned16(gbi) || !aligned16(dz)) return fail(FMX_ERR_ALIGN, "%s: dz and gbi must be 16-byte aligned", who);
+  if (int rc = check_workspace(table, B, workspace, workspace_bytes, who)) return rc;
+  const Workspace w = carve(table, B, workspace);
+  // the step workspace and LIST_BIAS_SCRATCH bytes behind it (fmx_fm_list_workspace_bytes), as fmx_list.inc checks it
+  if (workspace_bytes < (int64_t)w.bytes + LIST_BIAS_SCRATCH)
+    return fail(FMX_ERR_SHAPE, "%s: workspace of %lld bytes, %lld needed: the step's and %lld bytes behind it (fmx_fm_list_workspace_bytes)", who,
+                (long long)workspace_bytes, (long long)((int64_t)w.bytes + LIST_BIAS_SCRATCH), (long long)LIST_BIAS_SCRATCH);
+  const fmx_table_t tu = list_update_table(table, workspace, w.bytes);
+  MlpReduceArgs red;  // the section's last launch, set up by before_update, rides inside the table update's (k_fm_update_rider)
+  auto before_update = [&](int s, const int32_t *idx, const float *corr, hipStream_t st) -> int {
+    int rc = forward_impl(table, hyper, idx, nullptr, nullptr, B, FMX_LOSS_NONE, inv_b, fwd, st);
+    if (rc == FMX_OK && !fm_term) {  // NFM: the network's input logit is first-order + bias; the FM logit's buffer holds it
+      hipLaunchKernelGGL(k_first_plus_bias, dim3((B + 255) / 256), dim3(256), 0, st, fwd->logit, fwd->sfirst, table->bias, B);
+      rc = check_launch("fmx_deepfm_list_stream (k_first_plus_bias)");
+    }
+    if (rc == FMX_OK)
+      rc = mlp_list_section_deferred_reduce(mlp, fwd->bi, table->kp, fwd->logit, corr, B_lists, G, inv_b, mlp_workspace, mlp_workspace_bytes,
+                                            nullptr, dz, gbi, table->kp, grads, opt ? 0.f : lr_mlp, loss_out ? loss_out + s : nullptr, st,
+                                            &red, who);
+    if (rc == FMX_OK && opt) mlp_reduce_set_opt(red, *opt, opt->step + s + 1);  // step s of the call is step t = opt->step + s + 1 of the network
+    return rc;
+  };
+  auto update = [&](int s, const uint32_t *sorted, hipStream_t st) {
+    const fmx_hyper_t hs = hyper_at_step(hyper, rule, s);  // ... and step t = hyper->step + s + 1 of the tables
+    return update_impl(&tu, &hs, rule, w, sorted, nullptr, fwd->S, dz, fm_term ? dz : nullptr, gbi, B, nullptr, inv_b, nullptr, st, nullptr, 0,
+                       fwd->error, &red);
+  };
+  return pool_loop(table, idx_pool, corr_pool, n_pool, B, n_steps, w, fwd->error, static_cast<hipStream_t>(stream), before_update, update);
+}
+
 // ---- the field-owner step with the library's own communicator (fmx_comm.hip) ----
 static int owner_geometry(const Comm *c, const fmx_table_t *table, int32_t B, int32_t slot, int &GB, const char *who) {
   if (!c) return fail(FMX_ERR_ARG, "%s: null communicator", who);

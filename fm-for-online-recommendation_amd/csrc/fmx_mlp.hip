@@ -489,3 +489,6 @@ int fmx_mlp_hedge_section(const fmx_mlp_t *mlp, float lr, float hedge_b, float h
 }
 
 }  // extern "C"
+
+// the list section (fmx_mlp_list_section, k_mlp_list_loss): beside the sections above, behind them
+#include "fmx_mlp_list.inc"

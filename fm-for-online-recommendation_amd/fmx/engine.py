@@ -352,6 +352,29 @@ class FMEngine:
         keep = (out, m, hyper, mlp_opt, params, grads, idx_pool, loss_out, self.workspace, self._mlp_ws, self._mlp_dz, self._mlp_gbi)
         return self._bound_run(self.lib.fmx_deepfm_pair_stream, fixed, tail, hyper, loss_out, keep, mlp_opt)
 
+    def prepare_deepfm_list_stream(self, hyper, rule, params, grads, k, hidden, n_layers, lr_mlp, idx_pool, G, corr_pool=None,
+                                   loss_out=None, stream=None, fm_term=True, mlp_opt=None):
+        """-> run(n_steps): prepare_deepfm_stream under the list loss (fmx_deepfm_list_stream) over a resident pool idx_pool
+        [n_pool, B_lists G, F], row G i the positive of list i, then its G - 1 negatives; no labels.  corr_pool (fp32
+        [n_pool, B_lists G], log Q of every row's item) or None.  mlp_opt None: the network under SGD by lr_mlp; an MlpOpt: its
+        rule (lr_mlp is not read).  The table workspace is the list steps' own (self._list_ws: the step workspace and the bias
+        scratch behind it); the table's bias does not move.  A run advances the table's step count (moments tables) and
+        mlp_opt's by its steps.  The caller keeps the tensors alive and does not grow the engine between prepare and run."""
+        n_pool, rows, F = idx_pool.shape
+        assert F == self.table.n_fields and idx_pool.is_contiguous()
+        G = _list_G(G)
+        B = self._n_lists(rows, G)
+        out = self._fwd_out(want_first=False, want_bi=True)
+        m = self._mlp_struct(params, k, hidden, n_layers)
+        self._mlp_big_buffers(m, k, hidden, n_layers, rows)
+        fixed = (self.table.c_struct(), hyper.ref(), _lib.RULES[rule], C.byref(m), int(bool(fm_term)), idx_pool.data_ptr(), n_pool, B, G,
+                 None if corr_pool is None else self._corr(corr_pool, (n_pool, rows)), 1.0 / B)
+        tail = (self._list_ws.data_ptr(), self._list_ws.numel() * 4, self._mlp_ws.data_ptr(), self._mlp_ws.numel() * 4, C.byref(out),
+                self._mlp_dz.data_ptr(), self._mlp_gbi.data_ptr(), grads.data_ptr(), float(lr_mlp),
+                None if mlp_opt is None else mlp_opt.ref(), _ptr(loss_out), self._stream(stream))
+        keep = (out, m, hyper, mlp_opt, params, grads, idx_pool, corr_pool, loss_out, self._list_ws, self._mlp_ws, self._mlp_dz, self._mlp_gbi)
+        return self._bound_run(self.lib.fmx_deepfm_list_stream, fixed, tail, hyper, loss_out, keep, mlp_opt)
+
     # ---- the small fused MLP (online steps of DeepFM / NFM / ONN); shapes beyond its limits raise FmxError(UNSUPPORTED) ----
     MLP_MAX_B, MLP_MAX_W, MLP_MAX_L = 16, 64, 8
 
@@ -793,6 +816,45 @@ class FMEngine:
                                                       None if mlp_opt is None else mlp_opt.ref(), self._mlp_loss.data_ptr(),
                                                       self._stream()), mlp_opt=mlp_opt)
         return self._mlp_loss, self._mlp_dz, self._mlp_gbi, self._mlp_logit
+
+    def mlp_list_section(self, params, grads, k, hidden, n_layers, bi, base, B_lists, G, inv_b=None, corr=None, lr_apply=0.0,
+                         mlp_opt=None):
+        """mlp_section under the list loss (fmx_mlp_list_section): `bi` [B_lists G, ld] and `base` [B_lists G] hold row G i = the
+        positive of list i, then its G - 1 negatives; no labels.  corr (fp32 [B_lists G], log Q of every row's item) or None: the
+        softmax runs on logit - corr.  -> (loss [1] = the mean list loss, dz [B_lists G], gbi [B_lists G, kp], logit [B_lists G]:
+        the whole network's UNCORRECTED logits, fmx_mlp_forward_batch's bits).  `grads` is filled; lr_apply != 0 also applies SGD;
+        mlp_opt (an MlpOpt): its rule instead, and its step advances by one.  The option "mlp_chain" does not reach this call."""
+        B_lists, G = int(B_lists), _list_G(G)
+        rows = B_lists * G
+        if B_lists < 1 or bi.shape[0] < rows or base.numel() < rows:
+            raise ValueError(f"mlp_list_section: bi {tuple(bi.shape)} / base {tuple(base.shape)} do not hold {B_lists} x {G} rows")
+        m = self._mlp_struct(params, k, hidden, n_layers)
+        self._mlp_big_buffers(m, k, hidden, n_layers, rows)
+        self._counted(self.lib.fmx_mlp_list_section, (C.byref(m), bi.data_ptr(), bi.stride(0), base.data_ptr(),
+                                                      None if corr is None else self._corr(corr, (rows,)), B_lists, G,
+                                                      1.0 / B_lists if inv_b is None else inv_b, self._mlp_ws.data_ptr(),
+                                                      self._mlp_ws.numel() * 4, self._mlp_logit.data_ptr(), self._mlp_dz.data_ptr(),
+                                                      self._mlp_gbi.data_ptr(), self.table.kp, grads.data_ptr(), lr_apply,
+                                                      None if mlp_opt is None else mlp_opt.ref(), self._mlp_loss.data_ptr(),
+                                                      self._stream()), mlp_opt=mlp_opt)
+        return self._mlp_loss, self._mlp_dz, self._mlp_gbi, self._mlp_logit
+
+    def list_sort_update(self, hyper, rule, idx_d, G, xv_d, dz_first, dz_bi=None, gbi=None, inv_b=None, stream=None):
+        """sort() and update() of a list step put together from the engine's calls (the classes' fit_lists(full=True)): both on
+        the list steps' own workspace, and the update on a copy of the table struct whose bias points at the scratch behind
+        that workspace -- what fmx_fm_list_step and fmx_deepfm_list_stream hand k_fm_update, so that the bias rule runs on
+        scratch and the table's bias and its state stay bit-unchanged.  S is the last forward's; no loss is reduced."""
+        rows = idx_d.shape[0]
+        B = self._n_lists(rows, G)
+        ws = self._list_ws
+        self.sort(idx_d, workspace=ws, stream=stream)
+        step_bytes = int(self.lib.fmx_workspace_bytes(self.table.c_struct(), rows))
+        t = _lib.Table()
+        C.memmove(C.byref(t), self.table.c_struct(), C.sizeof(t))
+        t.bias = ws.data_ptr() + step_bytes
+        self._counted(self.lib.fmx_fm_update, (C.byref(t), hyper.ref(), _lib.RULES[rule], ws.data_ptr(), ws.numel() * 4, _ptr(xv_d),
+                                               self.S.data_ptr(), dz_first.data_ptr(), _ptr(dz_bi), _ptr(gbi), rows, 0, None,
+                                               1.0 / B if inv_b is None else inv_b, None, self._stream(stream)), hyper)
 
     def check_error_flag(self):
         """The device-side error word (include/fmx.h, Conventions): 1 -> IndexError like nn.Embedding; 2 -> HandOffTimeout

@@ -621,3 +621,114 @@ class NetworkPairTraining:
             pos, pos_xv, neg = self._pair_at(rows, xv, fields, i)
             self._fit_pairs_full(pos, pos_xv, fields, neg, 1, margin, None, None)
         return self._experiment_result(start, self._host_stream_loop(n, fit_one, lambda: e._mlp_logit[0] > e._mlp_logit[1]))
+
+
+class NetworkListTraining:
+    """DeepFMAdam's and NFMAdam's fit_lists / run_list_experiment: RankingTraining's, with the keyword full.  full=False is the
+    pure FM's refusal, raised before any state is read (the list loss of fmx_fm_list_* is the pure FM logit's); full=True trains on
+    the list loss of the logit forward() returns (fmx_mlp_list_section).  Listed beside NetworkPairTraining, in front of
+    OnlineFMBase, in the class's bases."""
+
+    def _fit_lists_full(self, Xi, Xv, item_fields, negatives, n_neg, candidates, generator):
+        """fit_lists(full=True), the list mirror of _fit_pairs_full: the lists' rows, forward with no loss, the MLP section under
+        the list loss on bi (fmx_mlp_list_section, inv_b = 1 / lists; the sampler's log Q as its corr under
+        PopularityNegatives(correct=True)), the network's rule by _fit_pairs_full's branches, sort, and the table update with dz
+        (and dz again for the FM term where forward() has it) and gbi on the list steps' copy of the table, whose bias rule runs
+        on scratch: the bias does not move.  Every batch size goes through the section."""
+        rule = self.update_rule
+        if rule in ("adam", "adagrad") and getattr(self, "_mlp_fused", None) is None:
+            raise ValueError(f"{self._name}.fit_lists(full=True) under update_rule={rule!r} trains the hidden layers inside the MLP "
+                             "section: construct the model with fused_optimizer=True")
+        self.train()
+        idx_d, xv_d, _ = self._inputs(Xi, Xv)
+        popular = fmx.pairwise.popularity_negatives(negatives)
+        corr = None
+        if popular is not None and popular.correct:
+            negatives, corr = self._sample_popular(idx_d, self._item_fields(item_fields), popular, n_neg, candidates, generator)
+        rows, xv, G = self._list_rows("fit_lists", idx_d, xv_d, item_fields, negatives, n_neg, candidates, generator)
+        e, k, lr = self._engine, self.embedding_size, float(self.n)
+        N = e.forward(self._hyper, rows, xv)
+        B = N // G
+        if getattr(self, "_mlp_gflat", None) is None:
+            self._mlp_gflat = torch.zeros_like(self._mlp_flat)
+        loss, dz, gbi, _ = e.mlp_list_section(self._mlp_flat, self._mlp_gflat, k, self.neuron_per_hidden_layer, self.num_hidden_layers,
+                                              e.bi[:N], self._base_logit(N).contiguous(), B, G, 1.0 / B,
+                                              corr=None if corr is None else corr.reshape(-1),
+                                              lr_apply=lr if rule == "sgd" else 0.0, mlp_opt=self._mlp_fused)
+        if rule in ("signadam", "ftrl"):
+            g = self._mlp_gflat
+            with torch.no_grad():
+                self._mlp_flat.sub_(lr * g / (g.abs() + 1e-8))
+        e.list_sort_update(self._hyper, rule, rows, G, xv, dz, dz if self._fm_term_in_forward else None, gbi, inv_b=1.0 / B)
+        out = loss[0].clone()
+        self._after_step()
+        return out
+
+    def _list_full_checks(self, method, negatives, n_neg):
+        """What fit_lists / run_list_experiment(full=True) refuse before the model is looked at: mined negatives (they are mined
+        under the pure FM score), and a count of drawn negatives outside 1 .. 15"""
+        self._refuse_hard_negatives(method, negatives)
+        if negatives is None or fmx.pairwise.popularity_negatives(negatives) is not None:
+            self._list_limit(method, n_neg)
+
+    def fit_lists(self, Xi, Xv, item_fields, negatives=None, n_neg=4, candidates=None, generator=None, full=False):
+        """RankingTraining.fit_lists's arguments; full=True: one mini-batch list step of tables and network on the logit forward()
+        returns, under the model's update rule ('adam' / 'adagrad' need fused_optimizer=True).  negatives: given arrays, None
+        (uniform draws) or a fmx.pairwise.PopularityNegatives -- with its correct=True the softmax runs on logit - log Q;
+        "hard" / a HardNegatives is refused by name.  Returns the mean list loss; the bias does not move."""
+        if not full:
+            self._pure_fm_only("fit_lists", "list")
+        self._list_full_checks("fit_lists", negatives, n_neg)
+        return self._fit_lists_full(Xi, Xv, item_fields, negatives, n_neg, candidates, generator)
+
+    def run_list_experiment(self, Xi, Xv, item_fields, negatives=None, n_neg=4, candidates=None, generator=None, full=False):
+        """RankingTraining.run_list_experiment's arguments and 4-tuple; full=True: for every positive and its negatives predict the
+        positive's rank among that step's own whole-network logits (the uncorrected ones, before the update; correct: no negative
+        scores as high as the positive), then fit_lists(full=True) on that list alone -- the host loop of one-list section calls.
+        A PopularityNegatives draws every list's negatives in its own call, as the pure FM's loop does."""
+        if not full:
+            self._pure_fm_only("run_list_experiment", "list")
+        self._list_full_checks("run_list_experiment", negatives, n_neg)
+        start = time()
+        self.train()
+        idx_d, xv_d, _ = self._inputs(Xi, Xv)
+        n, e = idx_d.shape[0], self._engine
+        if n == 0:
+            return self._experiment_result(start, None)
+        popular = fmx.pairwise.popularity_negatives(negatives)
+        if popular is not None:
+            G = 1 + int(n_neg)
+            whole = popular.exclude
+            off, pos = fmx.recommend.exclusions_csr(whole, n, "cpu")
+
+            def fit_one(i):
+                if off is not None:
+                    popular.exclude = (off[i:i + 2] - off[i], pos[int(off[i]):int(off[i + 1])])
+                self._fit_lists_full(idx_d[i:i + 1], None if xv_d is None else xv_d[i:i + 1], item_fields, popular, n_neg, candidates,
+                                     generator)
+        else:
+            whole = None
+            rows, xv, G = self._list_rows("run_list_experiment", idx_d, xv_d, item_fields, negatives, n_neg, candidates, generator)
+            fields = self._item_fields(item_fields)
+
+            def fit_one(i):
+                lst = rows[G * i:G * (i + 1)]
+                self._fit_lists_full(lst[:1], None if xv is None else xv[G * i:G * i + 1], fields, lst[1:, fields].reshape(1, G - 1, -1),
+                                     G - 1, None, None)
+        try:
+            ranks = self._host_stream_loop(n, fit_one, lambda: (e._mlp_logit[1:G] >= e._mlp_logit[0]).sum())
+        finally:
+            if popular is not None:
+                popular.exclude = whole
+        return self._experiment_result(start, ranks == 0)
+
+
+class NetworkListRefused:
+    """DeepFMOnn's and NFMOnn's fit_lists / run_list_experiment: the signature of NetworkListTraining, and RankingTraining's
+    refusal under full as well -- Hedge backprop has a loss per layer, and no list form of it is built."""
+
+    def fit_lists(self, Xi, Xv, item_fields, negatives=None, n_neg=4, candidates=None, generator=None, full=False):
+        self._pure_fm_only("fit_lists", "list")
+
+    def run_list_experiment(self, Xi, Xv, item_fields, negatives=None, n_neg=4, candidates=None, generator=None, full=False):
+        self._pure_fm_only("run_list_experiment", "list")

@@ -5,10 +5,10 @@ forward = forward_fm + sum relu-MLP(bi) (deepfm_adam.py:79-89; second_order is e
 gradient is the FM-term gradient plus the MLP-input gradient); update_embedding: BCEwl(forward_fm) (:99-101);
 fit: BCEwl(sigmoid(forward)) (:115)."""
 from ._base import OnlineFMBase
-from ._ranking import NetworkPairTraining
+from ._ranking import NetworkListTraining, NetworkPairTraining
 
 
-class DeepFMAdam(NetworkPairTraining, OnlineFMBase):
+class DeepFMAdam(NetworkPairTraining, NetworkListTraining, OnlineFMBase):
     _name = "DeepFMAdam"
     _has_mlp = True
     _fm_term_in_forward = True

@@ -5,9 +5,10 @@ forward returns (last, [L,B]) with per-layer sigmoid(forward_fm + sum x_l) (deep
 backprop on the hidden layers and alpha only (:109-154); update_embedding: BCEwl(forward_fm) (:164-166);
 predict applies a second sigmoid (:173-175)."""
 from ._base import OnlineFMBase
+from ._ranking import NetworkListRefused
 
 
-class DeepFMOnn(OnlineFMBase):
+class DeepFMOnn(NetworkListRefused, OnlineFMBase):
     _name = "DeepFMOnn"
     _has_mlp = True
     _onn = True

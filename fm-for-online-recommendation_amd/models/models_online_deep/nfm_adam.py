@@ -4,10 +4,10 @@
 forward = sum_f first + bias + sum relu-MLP(bi), WITHOUT the sum_d bi_d term (nfm_adam.py:78-88);
 update_embedding: BCEwl(sigmoid(forward_fm)) (:100); fit: BCEwl(forward) (:114)."""
 from ._base import OnlineFMBase
-from ._ranking import NetworkPairTraining
+from ._ranking import NetworkListTraining, NetworkPairTraining
 
 
-class NFMAdam(NetworkPairTraining, OnlineFMBase):
+class NFMAdam(NetworkPairTraining, NetworkListTraining, OnlineFMBase):
     _name = "NFMAdam"
     _has_mlp = True
     _fm_term_in_forward = False

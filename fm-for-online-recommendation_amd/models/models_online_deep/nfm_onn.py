@@ -4,9 +4,10 @@
 As DeepFMOnn, but the per-layer logit has no sum_d bi_d term (nfm_onn.py:90-104) and update_embedding uses
 BCEwl(sigmoid(forward_fm)) (:168).  Note the reference's argument order: num_classes before batch_size (:14-15)."""
 from ._base import OnlineFMBase
+from ._ranking import NetworkListRefused
 
 
-class NFMOnn(OnlineFMBase):
+class NFMOnn(NetworkListRefused, OnlineFMBase):
     _name = "NFMOnn"
     _has_mlp = True
     _onn = True

@@ -918,6 +918,58 @@ int fmx_deepfm_pair_stream(const fmx_table_t *table, const fmx_hyper_t *hyper, i
                            const fmx_fwd_out_t *fwd, float *dz, float *gbi, float *grads, float lr_mlp, const fmx_mlp_opt_t *opt,
                            float *loss_out, fmx_stream_t stream);
 
+/* ---- listwise (sampled-softmax) training of DeepFM / NFM: the list loss on the whole network's logit ----
+ * The layout is fmx_fm_list_forward's: B_lists lists of G rows (2 <= G <= 16) are B_lists G rows, row G i the positive of list i
+ * and rows G i + 1 .. G i + G - 1 its negatives; z_b = base_b + sum_j H_L[b, j] as the pointwise section sums it, and with
+ * c_b = z_b - corr_b (corr: log Q of every row's item as in fmx_fm_list_forward_q, [B_lists G]; null: c_b = z_b, and a corr of
+ * +0 gives the same bits) loss_i = -log softmax(c[G i .. G i + G - 1])[0], evaluated as stated at fmx_fm_list_forward (one
+ * device formula for every list family).  No label is read.
+ *
+ * fmx_mlp_section on lists: bi [B_lists G, ld_bi], base [B_lists G]; logit_out [B_lists G] (may be null) is the UNCORRECTED z,
+ * the serving score, with the bits fmx_mlp_forward_batch writes for the same bi / base;
+ *   dz_out[G i + j] = inv_b * d loss_i / d z[G i + j]: negative for the positive, positive for every negative, summing to
+ *   zero over a list up to rounding; gbi_out [B_lists G, ld_gbi] and grads as in fmx_mlp_section with that dz;
+ *   loss_out [1] = inv_b * sum_i loss_i (may be null).
+ * opt null: params -= lr_apply * grads in the same pass (lr_apply = 0 leaves the parameters alone); opt given: opt->rule as in
+ * fmx_mlp_section_opt, this call being step t = opt->step + 1, and lr_apply is not read.  grads, dz_out, gbi_out and logit_out
+ * do not depend on opt / lr_apply.  workspace: fmx_mlp_section_workspace_bytes for B_lists * G rows (smaller: FMX_ERR_SHAPE).
+ * The section always runs as separate launches (the forward GEMMs, k_mlp_list_loss -- one wavefront per list --, the dgrad
+ * GEMMs, the weight gradients, the reduction): fmx_set_option("mlp_chain", ...) does not change a bit of its results.
+ * Before anything is launched: B_lists < 1, G < 2 and B_lists * G beyond int32 are FMX_ERR_ARG, G > 16 FMX_ERR_UNSUPPORTED,
+ * then what fmx_mlp_section refuses (a null mlp / params / workspace / bi / base / dz_out / gbi_out / grads: FMX_ERR_ARG; ld_bi
+ * or ld_gbi < k: FMX_ERR_SHAPE) and, with opt, what fmx_mlp_section_opt refuses.  Every message names fmx_mlp_list_section.
+ * Replaces: nn.Linear + relu + autograd of DeepFMAdam.fit / NFMAdam.fit (reference deepfm_adam.py:79-89,106-119;
+ * nfm_adam.py:78-88,105-118) under a softmax cross-entropy over the positive and its sampled negatives, which the reference
+ * does not have (nearest: the pair objective of reference models/models_meta_emb/meta_fm.py:145-169). */
+int fmx_mlp_list_section(const fmx_mlp_t *mlp, const float *bi, int32_t ld_bi, const float *base, const float *corr,
+                         int32_t B_lists, int32_t G, float inv_b, void *workspace, int64_t workspace_bytes, float *logit_out,
+                         float *dz_out, float *gbi_out, int32_t ld_gbi, float *grads, float lr_apply, const fmx_mlp_opt_t *opt,
+                         float *loss_out, fmx_stream_t stream);
+
+/* n_steps list steps of DeepFM (fm_term = 1) / NFM (fm_term = 0) over a device-resident pool idx_pool [n_pool, B_lists G, F]
+ * (every feature value 1) with corr_pool [n_pool, B_lists G] or null beside it: step s takes batch (s mod n_pool).  opt null:
+ * the checks and rules of fmx_deepfm_stream (the network under SGD by lr_mlp); opt given: those of fmx_deepfm_stream_opt (lr_mlp
+ * is not read; step s is step hyper->step + s + 1 of the tables and opt->step + s + 1 of the network).  In front of them the
+ * refusals of the fmx_fm_list_stream family: a null table / hyper / idx_pool, B_lists < 1, G < 2, B_lists * G beyond int32:
+ * FMX_ERR_ARG; G > 16, field_cols / field_base: FMX_ERR_UNSUPPORTED; B_lists * G beyond the sort's width: what
+ * fmx_sort_occurrences reports; n_pool < 1, n_steps < 0: FMX_ERR_ARG.  Every message names fmx_deepfm_list_stream, and
+ * n_steps = 0 launches nothing.  fwd, dz, gbi and mlp_workspace are sized for B_lists * G rows; mlp_workspace_bytes is checked
+ * under either rule (FMX_ERR_SHAPE).  workspace: fmx_fm_list_workspace_bytes(table, B_lists, G) bytes -- the step workspace and
+ * the 16 bytes behind it on which the bias rule runs (smaller: FMX_ERR_SHAPE): the bias of a list step has no gradient but
+ * rounding, so the table's bias and its state stay bit-unchanged under every rule, as in fmx_fm_list_step.
+ * fm_term = 1: base is the FM logit, the update takes dz_first = dz_bi = dz and gbi; fm_term = 0: base is first-order sum + bias,
+ * the update takes dz_first = dz, no dz_bi, and gbi.  The section's reduction rides in the table update's launch.
+ * The result is, bit for bit, the one of calling fmx_fm_forward with FMX_LOSS_NONE on the B_lists G rows, the NFM base add,
+ * fmx_mlp_list_section, fmx_sort_occurrences and fmx_fm_update (on a table struct whose bias points at scratch) per step, the
+ * counts advanced by the caller.  loss_out [n_steps] or null.
+ * Replaces: the mini-batch driver loop over DeepFMAdam.fit / NFMAdam.fit (reference main_experiment.py:92-105 with
+ * deepfm_adam.py:106-119, nfm_adam.py:105-118) under the list objective above. */
+int fmx_deepfm_list_stream(const fmx_table_t *table, const fmx_hyper_t *hyper, int32_t rule, const fmx_mlp_t *mlp, int32_t fm_term,
+                           const int32_t *idx_pool, int32_t n_pool, int32_t B_lists, int32_t G, const float *corr_pool, float inv_b,
+                           int32_t n_steps, void *workspace, int64_t workspace_bytes, void *mlp_workspace, int64_t mlp_workspace_bytes,
+                           const fmx_fwd_out_t *fwd, float *dz, float *gbi, float *grads, float lr_mlp, const fmx_mlp_opt_t *opt,
+                           float *loss_out, fmx_stream_t stream);
+
 /* fmx_mlp_fit (the one-workgroup kernel: B <= 16, k <= 63, hidden <= 64, layers <= 8) with the hidden layers under opt->rule
  * (FMX_RULE_SGD, FMX_RULE_ADAGRAD, FMX_RULE_ADAM as stated at fmx_mlp_opt_t: the network's ADAM is torch.optim.Adam, the tables'
  * is SparseAdam) instead of `rule`: the thread that sums a parameter's gradient over the batch in sample order applies the rule to
