@@ -250,6 +250,16 @@ inline fmx_table_t list_update_table(const fmx_table_t *table, void *workspace, 
   return t;
 }
 
+// the shape of a batch of lists, as check_list_args (fmx_kernels.hip) refuses it for the list calls on a table: the network's list
+// calls, which take no table (fmx_mlp_list_section in fmx_mlp_list.inc, fmx_mlp_list_fit in fmx_online.hip)
+inline int mlp_list_shape(int32_t B_lists, int32_t G, const char *who) {
+  if (B_lists < 1) return fail(FMX_ERR_ARG, "%s: B_lists = %d must be >= 1", who, B_lists);
+  if (G < 2) return fail(FMX_ERR_ARG, "%s: G = %d: a list is a positive and at least one negative (G >= 2)", who, G);
+  if (G > LIST_MAX_G) return fail(FMX_ERR_UNSUPPORTED, "%s: G = %d: at most %d rows per list", who, G, LIST_MAX_G);
+  if ((int64_t)B_lists * G > INT32_MAX) return fail(FMX_ERR_ARG, "%s: B_lists = %d, G = %d: B_lists * G rows exceed int32", who, B_lists, G);
+  return FMX_OK;
+}
+
 inline Workspace carve(const fmx_table_t *t, int B, void *base) {
   const size_t F = (size_t)n_sort_fields(t), Bp = (size_t)fmx_sorted_width(B), tiles = Bp >> 6;
   const size_t rec = 2 * (size_t)t->kp + 4;

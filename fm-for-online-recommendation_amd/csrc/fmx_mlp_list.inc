@@ -64,15 +64,6 @@ __global__ __launch_bounds__(256) void k_mlp_list_loss(MlpListLossArgs a) {
 
 }  // namespace
 
-// the shape of a batch of lists, as check_list_args (fmx_kernels.hip) refuses it for the list calls on a table
-static int mlp_list_shape(int32_t B_lists, int32_t G, const char *who) {
-  if (B_lists < 1) return fail(FMX_ERR_ARG, "%s: B_lists = %d must be >= 1", who, B_lists);
-  if (G < 2) return fail(FMX_ERR_ARG, "%s: G = %d: a list is a positive and at least one negative (G >= 2)", who, G);
-  if (G > LIST_MAX_G) return fail(FMX_ERR_UNSUPPORTED, "%s: G = %d: at most %d rows per list", who, G, LIST_MAX_G);
-  if ((int64_t)B_lists * G > INT32_MAX) return fail(FMX_ERR_ARG, "%s: B_lists = %d, G = %d: B_lists * G rows exceed int32", who, B_lists, G);
-  return FMX_OK;
-}
-
 // fmx_mlp_list_section without its last launch (mlp_section_deferred_reduce's contract: `deferred` receives the reduction's
 // arguments, null launches it here).  What is refused, in front of any launch: the list's shape, then mlp_big_check, the size of
 // the workspace, the null buffers and the leading dimensions

@@ -4,7 +4,8 @@
 // k_online_mlp_pair (fmx_online_run_mlp_pair).  The four walkers are two step loops -- fm_walk and mlp_walk, each over one or two
 // samples per step -- built from the per-step pieces of fmx_walk.inc; a kernel adds its objective's label, loss and outputs.  On
 // the device they use fmx_common.h alone; the queued form of fmx_online_run_mlp and fmx_online_run_mlp_pair (online_mlp_queued)
-// issues the batched launches of the other units through fmx_host.h.
+// issues the batched launches of the other units through fmx_host.h.  The list forms -- k_mlp_small_list (fmx_mlp_list_fit) and
+// k_online_mlp_list (fmx_online_run_mlp_list) -- are fmx_online_list.inc, included at the end of this file.
 
 #include "fmx_host.h"
 
@@ -172,6 +173,15 @@ struct MlpArgs {
   float margin;        // the pair loss's margin
   uint8_t *pair_pred;  // [B / 2] z[2i] > z[2i + 1], before the update; or null
 };
+
+// the list mode of the FIT step (mlp_list_body, fmx_online_list.inc): a struct of its own beside MlpArgs, whose size the other
+// kernels' descriptors carry.  The B rows are B / G lists, row G i the positive of list i
+struct MlpListPart {
+  const float *corr;  // [B] log Q of every row's item, subtracted in front of the softmax; null: no correction
+  uint8_t *rank;      // [B / G] negatives of list i whose logit is >= its positive's, before the update; or null
+  int32_t G;
+};
+int mlp_list_launch(const fmx_mlp_t *mlp, MlpArgs &a, const MlpListPart &lp, int32_t B, int32_t kp, fmx_stream_t stream);
 
 // the network's rule for its step t (1-based) as k_mlp_small takes it: ADAM's constants in double, once per step (adam_consts)
 inline void mlp_small_set_opt(MlpArgs &a, const fmx_mlp_opt_t &o, int32_t t) {
@@ -667,16 +677,21 @@ static int mlp_launch(const fmx_mlp_t *mlp, MlpArgs &a, int32_t B, int32_t kp, f
 // The queued form of the network walkers: per step of R rows forward(B = R), k_mlp_small (or _pair), sort(B = R), update(B = R), no
 // host synchronisation.  set_mode(m, i): the mode's fields of step i's MlpArgs; no_update: Hedge trains the hidden layers and alpha
 // only (reference deepfm_onn.py:109-154).  rule_t: the rule whose step count the tables' hyper-parameters follow (-1: none).
+// scratch: dz [R] at 0, gbi [R, kp] at gbi_at.  list (fmx_online_run_mlp_list): the R rows are ONE list -- k_mlp_small_list with row
+// R i of list->corr (or null) and list->rank + i, and the update on the list steps' copy of the table, whose bias rule runs on the
+// LIST_BIAS_SCRATCH bytes behind the step workspace (fmx_list.inc).
 template <class Mode>
 int online_mlp_queued(const fmx_table_t *table, const fmx_hyper_t *hyper, int32_t rule, int rule_t, const fmx_mlp_t *mlp, int32_t fm_term,
                       const int32_t *idx, const float *xv, int32_t N, int R, void *workspace, const fmx_fwd_out_t *fwd, float *scratch,
-                      bool no_update, fmx_stream_t stream, const char *who, Mode set_mode) {
+                      bool no_update, fmx_stream_t stream, const char *who, Mode set_mode, int gbi_at = 8,
+                      const MlpListPart *list = nullptr) {
   hipStream_t st = static_cast<hipStream_t>(stream);
   const Workspace w = carve(table, R, workspace);
+  const fmx_table_t tu = list ? list_update_table(table, workspace, w.bytes) : *table;
   const size_t F = (size_t)table->n_fields;
   fmx_fwd_out_t f1 = *fwd;  // R samples: dense outputs
   f1.sample_ld = 0;
-  float *dz = scratch, *gbi = scratch + 8;
+  float *dz = scratch, *gbi = scratch + gbi_at;
   for (int i = 0; i < N; ++i) {
     const int32_t *idx_i = idx + (size_t)i * R * F;
     const float *xv_i = xv ? xv + (size_t)i * R * F : nullptr;
@@ -692,11 +707,16 @@ int online_mlp_queued(const fmx_table_t *table, const fmx_hyper_t *hyper, int32_
     a.dz_out = dz;
     a.gbi_out = gbi;
     set_mode(a, i);
-    if (int rc = mlp_launch(mlp, a, R, table->kp, stream, who, R == 2)) return rc;
+    if (list) {
+      const MlpListPart lp = {list->corr ? list->corr + (size_t)i * R : nullptr, list->rank + i, R};
+      if (int rc = mlp_list_launch(mlp, a, lp, R, table->kp, stream)) return rc;
+    } else if (int rc = mlp_launch(mlp, a, R, table->kp, stream, who, R == 2)) {
+      return rc;
+    }
     if (no_update) continue;
     if (int rc = sort_impl(table, idx_i, R, w.sorted, w.runs, fwd->error, st)) return rc;
     const fmx_hyper_t hs = hyper_at_step(hyper, rule_t, i);  // step i is step t = hyper->step + i + 1 of the tables
-    if (int rc = update_impl(table, &hs, rule, w, w.sorted, xv_i, fwd->S, dz, fm_term ? dz : nullptr, gbi, R, nullptr, 1.0f, nullptr, st,
+    if (int rc = update_impl(&tu, &hs, rule, w, w.sorted, xv_i, fwd->S, dz, fm_term ? dz : nullptr, gbi, R, nullptr, 1.0f, nullptr, st,
                              nullptr, 0, fwd->error))
       return rc;
   }
@@ -1051,3 +1071,5 @@ int fmx_mlp_hedge_fit(const fmx_mlp_t *mlp, float lr, float hedge_b, float hedge
 }
 
 }  // extern "C"
+
+#include "fmx_online_list.inc"

@@ -211,6 +211,85 @@ __device__ __forceinline__ void walk_bias_store(float *bias, float b0, float b1,
   if (MOM) bias[2] = b2;
 }
 
+// ---- the list walkers (k_fm_list_online, k_online_mlp_list): the sums of a run of a single-list step ----
+// no_terms<T>(): the zero a run's sums of terms T start from (a kernel specialises it for its own terms)
+template <class T>
+__device__ __forceinline__ T no_terms();
+template <>
+__device__ __forceinline__ float4 no_terms<float4>() { return splat(0.f); }
+
+// The sums of ONE run of a field's sorted list of a single-list step, added in k_fm_update's order (update_body, fmx_update.hip).
+// There the list of G <= 16 occurrences is one tile; EPG consecutive positions are a lane group, which sums its part of a run one
+// term after the other from zero.  A run inside one group is that sum.  A run over the groups g0 .. g1 takes, as the carry into
+// g1, the segmented Hillis-Steele scan of the partials v_0 .. v_D of the groups g0 .. g1 - 1 (for off = 1, 2, 4, ...: a group at
+// distance d >= off from g0 adds the OLD value of the group at d - off), and g1 adds its own terms onto that carry one by one.
+// What the scan leaves at distance D is F(D) with F(0) = v_0, F(d) = B(d, h) + F(d - h), h the highest power of two <= d, and
+// B(e, h) = B(e, h/2) + B(e - h/2, h/2) the balanced sum of the h partials ending at e: the blocks are the set bits of D, the
+// lowest first.  add() is handed the members in list order and builds exactly that: `g` the group's sum, `s` a binary counter
+// for the block under way, `F` the carry so far.  NLVL = log2 of the largest block: positions stay below 16, so D <= 16 / EPG - 2.
+// T: all the terms (Terms), or the vector cV and the scalars (cA, cw) apart -- at 16 waves the kernel walks a run once for each,
+// which halves the registers the walk holds.
+template <int EPG, class T>
+struct RunSum {
+  static constexpr int NLVL = EPG == 1 ? 3 : EPG == 2 ? 2 : EPG == 4 ? 1 : 0;
+  T g, F, s[NLVL > 0 ? NLVL : 1];
+  int pos, first, g0, g1, D, bstart;
+  // a run of L members whose first stands at position a of the sorted list
+  __device__ __forceinline__ void init(int a, int L) {
+    g = F = no_terms<T>();
+#pragma unroll
+    for (int l = 0; l < (NLVL > 0 ? NLVL : 1); ++l) s[l] = no_terms<T>();
+    pos = first = a;
+    g0 = a / EPG;
+    g1 = (a + L - 1) / EPG;
+    D = g1 - 1 - g0;
+    bstart = 1;
+  }
+  __device__ __forceinline__ void leaf(int rel, T v) {
+    if (rel == 0) {
+      F = v;
+      return;
+    }
+    const int rem = D - (bstart - 1), h = rem & -rem, n = rel - bstart;
+    T carry = v;
+    bool go = true;
+#pragma unroll
+    for (int l = 0; l < NLVL; ++l) {
+      const bool bit = ((n >> l) & 1) != 0;
+      if (go && bit) carry = s[l] + carry;
+      if (go && !bit) {
+        s[l] = carry;
+        go = false;
+      }
+    }
+    if (n == h - 1) {
+      F = carry + F;
+      bstart += h;
+    }
+  }
+  __device__ __forceinline__ void add(T c, bool member) {
+    if (!member) return;
+    const int gi = pos / EPG;
+    if (pos % EPG == 0 || pos == first) g = (gi == g1 && g1 > g0) ? F : no_terms<T>();
+    g = g + c;
+    if ((pos + 1) % EPG == 0 && gi < g1) leaf(gi - g0, g);
+    ++pos;
+  }
+};
+
+// ... and the same interface for a run that lies in one lane group or in two neighbouring ones (D <= 0 above): its terms add up
+// one after the other from zero -- the group's sum, which is also the carry the second group goes on adding to
+template <class T>
+struct PlainSum {
+  T g;
+  __device__ __forceinline__ void add(T c, bool member) {
+    if (member) g = g + c;
+  }
+};
+
+// lane j's value for a wave-uniform j: a lane read into a scalar register, no LDS round trip
+__device__ __forceinline__ float lane_f(float x, int j) { return __uint_as_float(__builtin_amdgcn_readlane(__float_as_uint(x), j)); }
+
 // ---- the walkers with a network (k_online_mlp, k_online_mlp_pair): it lives in LDS for the length of the stream ----
 // net_rule: the network's persistent rule (fmx_mlp_opt_t.rule), or -1 where the table's rule drives it; workgroup-uniform
 

@@ -43,7 +43,7 @@ EXPORTS = ["fmx_version", "fmx_last_error_string", "fmx_set_option", "fmx_sorted
            "fmx_fm_inbatch_occ_grad", "fmx_fm_inbatch_workspace_bytes", "fmx_fm_inbatch_step", "fmx_fm_inbatch_stream",
            "fmx_fm_inbatch_bank_splits", "fmx_fm_inbatch_bank_lse_bytes", "fmx_fm_inbatch_bank_forward", "fmx_fm_inbatch_bank_backward",
            "fmx_fm_inbatch_bank_push", "fmx_fm_inbatch_bank_workspace_bytes", "fmx_fm_inbatch_bank_step", "fmx_fm_inbatch_bank_stream",
-           "fmx_mlp_list_section", "fmx_deepfm_list_stream"]
+           "fmx_mlp_list_section", "fmx_deepfm_list_stream", "fmx_mlp_list_fit", "fmx_online_run_mlp_list"]
 ITEM_BANK_MAX = 1 << 20      # FMX_ITEM_BANK_MAX: the largest capacity of an item bank
 
 
@@ -195,6 +195,8 @@ def load():
     lib.fmx_deepfm_list_stream.argtypes = [TP, HP, i32, MP, i32, p, i32, i32, i32, p, f32, i32, p, i64, p, i64, FP, p, p, p, f32, OP, p, p]
     lib.fmx_mlp_pair_fit.argtypes = [MP, HP, i32, p, i32, p, i32, f32, f32, p, p, p, p, OP, p]
     lib.fmx_online_run_mlp_pair.argtypes = [TP, HP, i32, MP, i32, p, p, i32, f32, p, i64, FP, p, p, p, p, OP, p]
+    lib.fmx_mlp_list_fit.argtypes = [MP, HP, i32, p, i32, p, p, i32, i32, f32, p, p, p, p, p, OP, p]
+    lib.fmx_online_run_mlp_list.argtypes = [TP, HP, i32, MP, i32, p, p, p, i32, i32, p, i64, FP, p, p, p, p, OP, p]
     lib.fmx_afm_pair_forward.argtypes = [TP, AP, HP, p, p, i32, f32, f32, p, p, p, p, p]
     lib.fmx_afm_pair_step.argtypes = [TP, HP, i32, AP, p, p, i32, f32, f32, p, i64, p, p, p, p, p]
     lib.fmx_afm_pair_step_opt.argtypes = [TP, HP, i32, AP, p, p, i32, f32, f32, p, i64, p, OP, p, p, p, p]

@@ -429,6 +429,28 @@ class FMEngine:
                                                   None if mlp_opt is None else mlp_opt.ref(), self._stream()), mlp_opt=mlp_opt)
         return dz, gbi, logit
 
+    def mlp_list_fit(self, params, k, hidden, n_layers, hyper, rule, base, B_lists, G, inv_b=None, corr=None, mlp_opt=None,
+                     want_logit=False, want_rank=False):
+        """mlp_fit under the list loss (fmx_mlp_list_fit) on self.bi's first B_lists G rows (at most 16), row G i the positive of
+        list i, then its G - 1 negatives; no labels.  corr (fp32 [B_lists G], log Q of every row's item) or None: the softmax runs
+        on logit - corr.  -> (dz [B_lists G], gbi [B_lists G, kp], logit [B_lists G] or None: the UNCORRECTED logits, rank uint8
+        [B_lists] or None: the negatives of list i whose logit is >= its positive's) for self.list_sort_update(); the mean list
+        loss lands in self.loss_out[0]; the hidden layers in `params` are updated in place under `rule`, or under mlp_opt's rule
+        (an MlpOpt: `rule` and hyper are not read, mlp_opt.step advances by one)."""
+        B_lists, G = int(B_lists), _list_G(G)
+        rows = B_lists * G
+        dz = torch.empty(rows, dtype=torch.float32, device=self.device)
+        gbi = torch.empty((rows, self.table.kp), dtype=torch.float32, device=self.device)
+        logit = torch.empty(rows, dtype=torch.float32, device=self.device) if want_logit else None
+        rank = torch.empty(B_lists, dtype=torch.uint8, device=self.device) if want_rank else None
+        m = self._mlp_struct(params, k, hidden, n_layers)
+        self._counted(self.lib.fmx_mlp_list_fit, (C.byref(m), hyper.ref(), _lib.RULES[rule], self.bi.data_ptr(), self.table.kp,
+                                                  base.data_ptr(), None if corr is None else self._corr(corr, (rows,)), B_lists, G,
+                                                  1.0 / B_lists if inv_b is None else inv_b, _ptr(logit), dz.data_ptr(), gbi.data_ptr(),
+                                                  self.loss_out.data_ptr(), _ptr(rank), None if mlp_opt is None else mlp_opt.ref(),
+                                                  self._stream()), mlp_opt=mlp_opt)
+        return dz, gbi, logit, rank
+
     def mlp_hedge_fit(self, params, k, hidden, n_layers, lr, hedge_b, hedge_s, alpha, base, y_d, B):
         m = self._mlp_struct(params, k, hidden, n_layers)
         _lib.check(self.lib.fmx_mlp_hedge_fit(C.byref(m), lr, hedge_b, hedge_s, alpha.data_ptr(), self.bi.data_ptr(),
@@ -746,6 +768,35 @@ class FMEngine:
                                                          self._pair_online_scratch.data_ptr(), pred.data_ptr(), _ptr(logit), _ptr(loss_b),
                                                          None if mlp_opt is None else mlp_opt.ref(), self._stream()), hyper, N, mlp_opt)
         return pred, logit, loss_b
+
+    def online_run_mlp_list(self, hyper, rule, params, k, hidden, n_layers, fm_term, idx_d, G, xv_d=None, corr=None, mlp_opt=None,
+                            want_logit=False, want_loss=False):
+        """The online protocol on N device-resident lists of G rows through the whole network of DeepFM / NFM
+        (fmx_online_run_mlp_list): idx_d [N G, F], row G i the positive of list i, then its G - 1 negatives; per list the
+        positive's rank among that step's own uncorrected logits (0: first), then one list step of tables and network on that
+        list.  corr (fp32 [N G], log Q of every row's item) or None.  -> (rank uint8 [N], logit [N G] or None, loss [N] or None);
+        no sync.  One workgroup walks the stream at G <= 8 (and a network of at most 8,192 parameters); longer lists are queued
+        launches -- the same bits.  mlp_opt None: the network under `rule` ('signadam' / 'sgd'); an MlpOpt: its rule, and the tables under any
+        rule.  The call advances the table's step count (on a moments table) and mlp_opt.step by N; the bias does not move."""
+        G = _list_G(G)
+        if idx_d.dim() != 2 or idx_d.shape[0] % G:
+            raise ValueError(f"list rows must be [N G, F] with G = {G}, got {tuple(idx_d.shape)}")
+        N = idx_d.shape[0] // G
+        self._n_lists(G, G)         # the buffers of one list, and the list steps' own workspace
+        out = self._fwd_out(want_first=False, want_bi=True)
+        m = self._mlp_struct(params, k, hidden, n_layers)
+        rank = torch.empty(N, dtype=torch.uint8, device=self.device)
+        logit = torch.empty(N * G, dtype=torch.float32, device=self.device) if want_logit else None
+        loss_b = torch.empty(N, dtype=torch.float32, device=self.device) if want_loss else None
+        if getattr(self, "_list_online_scratch", None) is None:     # dz [16], then gbi [16, kp]: every G
+            self._list_online_scratch = torch.zeros(16 + 16 * self.table.kp, dtype=torch.float32, device=self.device)
+        self._counted(self.lib.fmx_online_run_mlp_list, (self.table.c_struct(), hyper.ref(), _lib.RULES[rule], C.byref(m),
+                                                         1 if fm_term else 0, idx_d.data_ptr(), _ptr(xv_d),
+                                                         None if corr is None else self._corr(corr, (N * G,)), N, G,
+                                                         self._list_ws.data_ptr(), self._list_ws.numel() * 4, C.byref(out),
+                                                         self._list_online_scratch.data_ptr(), rank.data_ptr(), _ptr(logit), _ptr(loss_b),
+                                                         None if mlp_opt is None else mlp_opt.ref(), self._stream()), hyper, N, mlp_opt)
+        return rank, logit, loss_b
 
     @staticmethod
     def online_run_fits(n_fields, kp):

@@ -629,6 +629,27 @@ class NetworkListTraining:
     the list loss of the logit forward() returns (fmx_mlp_list_section).  Listed beside NetworkPairTraining, in front of
     OnlineFMBase, in the class's bases."""
 
+    # run_list_experiment(full=True) on the device (fmx_online_run_mlp_list) where _list_device_loop_ok() says so.  Off by
+    # default: the host loop of section calls stays the class's own path; set it to True on an instance (or the class).
+    list_loop_on_device = False
+
+    def _list_device_loop_ok(self, G=None):
+        """Can run_list_experiment(full=True)'s predict-then-fit loop run on the device for this model (at lists of G rows; None:
+        the longest, 16)?  Under 'signadam' / 'sgd', and under 'adam' / 'adagrad' with fused_optimizer=True (the hidden layers'
+        flat moments; 'ftrl' and the torch optimizer of fused_optimizer=False stay on the host loop), where the one-workgroup MLP
+        step takes the network at G rows and the table is one fmx_fm_list_online_run takes (FMEngine.list_online_run_fits: the
+        fields fit one wavefront's passes, plain fields, no sort split).
+        The device loop then follows fmx_mlp_list_fit's arithmetic -- the one-workgroup kernel's summation order -- while the host
+        loop keeps fmx_mlp_list_section at every batch size: the two differ at one list in the order of fp32 summations only, so
+        a stream through either agrees to rounding, not bit for bit."""
+        rule = self.update_rule
+        if not (rule in ("signadam", "sgd") or (rule in ("adam", "adagrad") and getattr(self, "_mlp_fused", None) is not None)):
+            return False
+        e = self._engine
+        G = fmx._lib.LIST_MAX_G if G is None else int(G)
+        return (e.mlp_fits(G, self.embedding_size, self.neuron_per_hidden_layer, self.num_hidden_layers, "fit")
+                and e.list_online_run_fits(self.field_size, self._table.kp))
+
     def _fit_lists_full(self, Xi, Xv, item_fields, negatives, n_neg, candidates, generator):
         """fit_lists(full=True), the list mirror of _fit_pairs_full: the lists' rows, forward with no loss, the MLP section under
         the list loss on bi (fmx_mlp_list_section, inv_b = 1 / lists; the sampler's log Q as its corr under
@@ -685,7 +706,12 @@ class NetworkListTraining:
         """RankingTraining.run_list_experiment's arguments and 4-tuple; full=True: for every positive and its negatives predict the
         positive's rank among that step's own whole-network logits (the uncorrected ones, before the update; correct: no negative
         scores as high as the positive), then fit_lists(full=True) on that list alone -- the host loop of one-list section calls.
-        A PopularityNegatives draws every list's negatives in its own call, as the pure FM's loop does."""
+        A PopularityNegatives draws every list's negatives in its own call, as the pure FM's loop does.
+        With the attribute list_loop_on_device set to True: one call of fmx_online_run_mlp_list where _list_device_loop_ok() says
+        so (its docstring: which models, and with which arithmetic -- the one-workgroup kernel's summation order, so it agrees
+        with the host loop to rounding, not bit for bit).  A PopularityNegatives then draws the negatives of ALL positives in
+        one sampler call up front, which consumes the generator differently from the host loop's per-list draws: the same law,
+        other draws; with its correct=True the draws' log Q is the call's corr."""
         if not full:
             self._pure_fm_only("run_list_experiment", "list")
         self._list_full_checks("run_list_experiment", negatives, n_neg)
@@ -696,6 +722,16 @@ class NetworkListTraining:
         if n == 0:
             return self._experiment_result(start, None)
         popular = fmx.pairwise.popularity_negatives(negatives)
+        if self.list_loop_on_device and self._list_device_loop_ok():
+            corr = None
+            if popular is not None:
+                negatives, corr = self._sample_popular(idx_d, self._item_fields(item_fields), popular, n_neg, candidates, generator)
+            rows, xv, G = self._list_rows("run_list_experiment", idx_d, xv_d, item_fields, negatives, n_neg, candidates, generator)
+            ranks = e.online_run_mlp_list(self._hyper, self.update_rule, self._mlp_flat, self.embedding_size, self.neuron_per_hidden_layer,
+                                          self.num_hidden_layers, self._fm_term_in_forward, rows, G, xv,
+                                          corr=corr.reshape(-1) if corr is not None and popular.correct else None,
+                                          mlp_opt=getattr(self, "_mlp_fused", None))[0]
+            return self._experiment_result(start, ranks == 0)
         if popular is not None:
             G = 1 + int(n_neg)
             whole = popular.exclude

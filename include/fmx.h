@@ -1056,6 +1056,60 @@ int fmx_online_run_mlp_pair(const fmx_table_t *table, const fmx_hyper_t *hyper, 
                             int64_t workspace_bytes, const fmx_fwd_out_t *fwd, float *scratch, uint8_t *pred_out,
                             float *logit_out, float *loss_out, const fmx_mlp_opt_t *opt, fmx_stream_t stream);
 
+/* ---- the one-workgroup list step and the online list loop of DeepFM / NFM ----
+ * fmx_mlp_fit / fmx_mlp_fit_opt on B_lists * G rows under the list loss of fmx_mlp_list_section: row G i is the positive of list
+ * i, rows G i + 1 .. G i + G - 1 its negatives, and no label is read.  z_b = base_b + sum_j x_L[b, j] summed as the pointwise
+ * modes sum it: logit_out [B_lists G] (may be null) has the bits fmx_mlp_forward writes for the same bi / base.  The softmax runs
+ * on z_b - corr_b (corr [B_lists G]: log Q of every row's item; null: no correction, bit for bit a corr of +0) with the formula and
+ * the operand order stated at fmx_fm_list_forward (one device function evaluates every list family); the logit stored is the
+ * uncorrected z.
+ *   dz_out [B_lists G] = dL/dlogit * inv_b (a list's sum to zero up to rounding; at G = 2 the two are exact negatives),
+ *   loss_out[0] (may be null) = inv_b * the ordered sum over the rows of loss_{G i} = loss_i, +0 in the negatives' slots,
+ *   gbi_out [B_lists G, kp] as fmx_mlp_fit writes it (columns k..kp-1 zeroed),
+ *   rank_out[i] (uint8 [B_lists], may be null) = the negatives of list i with z_j >= z_0 on the uncorrected logits
+ *   (fmx_fm_list_online_run's definition).
+ * The backward pass and the parameter update are fmx_mlp_fit's: opt null -- `rule` (FMX_RULE_SIGNADAM / FMX_RULE_SGD) by hyper's
+ * lr / eps; opt given -- opt->rule as in fmx_mlp_fit_opt, this call being step opt->step + 1 (read, never written), and hyper and
+ * rule are not read.  dz_out, gbi_out, logit_out, loss_out and rank_out do not depend on the rule.
+ * Limits: fmx_mlp_fit's on B_lists * G rows -- B_lists * G <= 16, 2 <= G <= 16, k <= 63, hidden <= 64, layers <= 8, else
+ * FMX_ERR_UNSUPPORTED.  Before anything is launched: the list's shape as fmx_mlp_list_section refuses it, then fmx_mlp_pair_fit's
+ * checks of mlp, rule and opt, and its null checks.
+ * Replaces: DeepFMAdam.fit / NFMAdam.fit minus the table part (reference deepfm_adam.py:106-119, nfm_adam.py:105-118) under the
+ * sampled-softmax objective.  Restates: fmx_mlp_list_section's loss at the one-workgroup step's loss site. */
+int fmx_mlp_list_fit(const fmx_mlp_t *mlp, const fmx_hyper_t *hyper, int32_t rule, const float *bi, int32_t kp,
+                     const float *base, const float *corr, int32_t B_lists, int32_t G, float inv_b, float *logit_out,
+                     float *dz_out, float *gbi_out, float *loss_out, uint8_t *rank_out, const fmx_mlp_opt_t *opt,
+                     fmx_stream_t stream);
+
+/* The online predict-then-fit protocol on N device-resident lists idx [N G, F] (xv [N G, F] or null; corr [N G] or null) through
+ * the whole network of DeepFM (fm_term = 1) / NFM (fm_term = 0): for every list, rank_out[i] = the negatives whose logit is >= the
+ * positive's, logit_out[G i .. G i + G - 1] (or null; the uncorrected logits) and loss_out[i] (or null) with the weights BEFORE
+ * the list's update, then one list step of tables and network on that list alone, inv_b = 1.  The definition, bit for bit, is N
+ * times from outside: fmx_fm_forward(B = G, FMX_LOSS_NONE), the NFM base add (sfirst + bias weight) when fm_term = 0,
+ * fmx_mlp_list_fit(B_lists = 1, inv_b = 1), fmx_sort_occurrences(B = G), fmx_fm_update(B = G, dz_first = dz, dz_bi = fm_term ? dz :
+ * null, gbi, inv_b = 1) on the list steps' copy of the table struct, whose bias points at the scratch behind the step workspace
+ * (fmx_fm_list_workspace_bytes), the caller advancing hyper->step and opt->step -- rows (moments included), params, m, v,
+ * rank_out, logit_out and loss_out.  The table's bias and its state are read and never written.  List i is step
+ * hyper->step + i + 1 of the tables and opt->step + i + 1 of the network (both read, never written).
+ * opt null / given: the pairings of fmx_online_run_mlp_pair.
+ * One workgroup of 64 max(G, 4) threads walks the stream (k_online_mlp_list: wave j holds row j of the list, the parameters and
+ * the network's moments live in LDS, at most 96 KB beside the kernel's static arrays of at most 54.1 KB: the cap of
+ * fmx_online_run_mlp_pair stands) when G <= 8, the network has at most 8,192 parameters, with or without moments,
+ * n_fields <= min(4 * (64 / (kp / 4)), 128) and the tables are not FTRL tables; otherwise (longer lists among it: at 16 waves a
+ * wave has 128 registers and the kernel would spill), and with fmx_set_option("online_persistent", 0), the four launches of every
+ * list are queued without any host synchronisation.
+ * Every argument is checked before the first launch, N = 0 included (which launches nothing; idx, xv, corr and the three outputs
+ * may then be null): what fmx_fm_list_online_run refuses of table, hyper, idx, N and G (a sort split among it:
+ * FMX_ERR_UNSUPPORTED), a null rank_out, then fmx_online_run_mlp_pair's checks of workspace, fwd, scratch, mlp, opt, rule and
+ * layout.  workspace: fmx_fm_list_workspace_bytes(table, 1, G) bytes (smaller: FMX_ERR_SHAPE); fwd: S, bi, sfirst, logit of G
+ * samples, and fwd->error takes the index flag; scratch: >= 16 + G * kp floats (dz [G] at 0, gbi [G, kp] at 16), 16-byte aligned.
+ * Replaces: the loop body of run_experiment (reference deepfm_adam.py:128-130, nfm_adam.py:128-130) restated for the
+ * sampled-softmax objective.  Restates: fmx_fm_list_online_run for the classes with a network. */
+int fmx_online_run_mlp_list(const fmx_table_t *table, const fmx_hyper_t *hyper, int32_t rule, const fmx_mlp_t *mlp,
+                            int32_t fm_term, const int32_t *idx, const float *xv, const float *corr, int32_t N, int32_t G,
+                            void *workspace, int64_t workspace_bytes, const fmx_fwd_out_t *fwd, float *scratch,
+                            uint8_t *rank_out, float *logit_out, float *loss_out, const fmx_mlp_opt_t *opt, fmx_stream_t stream);
+
 /* Hedge backprop at mini-batch sizes (the ONN classes' fit() beyond 16 samples; reference deepfm_onn.py:109-154): per
  * layer BCELoss(sigmoid(base + sum_j x_l[j]), y), hidden layers updated by lr * sum_{i >= j} alpha_i dloss_i/dlayer_j (one
  * backward pass on the same GEMMs; `grads` receives that gradient), then alpha_i <- max(alpha_i * hedge_b^loss_i,
